@@ -7,22 +7,32 @@ D = diag(U(0.01,0.1)), U = n x 8 N(0,0.01^2)); one step = 1 predict + 1 correcti
 :124-145) on a cycling landmark index, with range/bearing taken from the world's true pose.  Inputs are
 resident in HBM before the timed region; the only per-step host->device traffic is kernel arguments.
 
-Legs measured in one invocation (every leg carries its own algorithmic bytes per step, so bytes/step / ms/step <= HBM
-peak can be checked on each):
+A plain run measures the headline alone: set-up, W warm-up steps, exactly K timed steps (one block), the result line.
+Everything else below is measured only with --full (every leg carries its own algorithmic bytes per step, so
+bytes/step / ms/step <= HBM peak can be checked on each):
   * HEADLINE (`value`, `ms_per_step`, `roofline`): the update-step AS WRITTEN -- cfg.batch = 1, every correction rewrites
     P at once (EKF_SLAM.m:145 once per update-step): B_alg = w n (n+1) bytes per step, one k_downdate_w
-    launch per step, purely HBM-bound; this is the number to hold against the >= 60 % roofline target.
+    launch per step, purely HBM-bound; this is the number to hold against the >= 60 % roofline target.  With --full a timed
+    region under MIN_REGION_S is repeated and the median block quoted; a sharded run (N > 1, --force-sharded) adds one more
+    instrumented block, `breakdown_us_per_step`.
   * `deferred`: the engine's deferred mode, cfg.batch = --batch: corrections are kept as pending rank-2
     pairs (every row a later correction reads is patched on the fly) and applied to P in ONE pass per `batch`
     update-steps -- bit-identical results, B_alg / batch + O(n) bytes per step.  The timed region ends with a flush, so
     every correction has been applied to every entry of P inside it.
   * N > 1 only, `deferred_lookahead`: the same with the next batch's landmarks announced (ekf_prefetch_rows): one
     all-gather per batch instead of one per update-step.
+  * N = 1 only, `cpu_baseline` / `cpu_baselines` (--no-cpu-baseline skips them): the structured C restatement and the literal-dense
+    one, timed on the host's cores.
   * N = 1 only, `other_configs` (after the legs above, each in a child process; --no-other-configs skips it): BASELINE.json's other
     single-GPU configurations -- configs[1] (1 000 landmarks, unknown correspondence, the device-resident measure loop) and the whole
     configs[4] workload on one GPU (40 000 -> 50 000 landmarks, float tiles, the pass in F32 arithmetic): their own JSON lines, verbatim.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--landmarks 10000] [--tile 128] [--batch 32]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--landmarks 10000] [--tile 128] [--full] [--dump-outputs DIR]
+
+--dump-outputs DIR: after the timed steps, the headline leg's state after its last step goes to DIR/<name>.npy, all float64:
+x.npy (3+2N), P_digest.npy (trace, sum and sum of squares of P's lower triangle), and on one GPU P_diag_blocks.npy ((N+1) x 2 x 2,
+P(1:2,1:2) and every landmark's block) and P_rows.npy (the robot's three rows of P and a fixed, seeded sample of the others,
+dump_rows(n); under 64 MB in all).  The inputs are seeded: the same arguments give the same inputs in every run.
 
 N > 1: one process per GPU.  Started by an external launcher (RANK / WORLD_SIZE in the environment, e.g.
 `python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...`) this process is one rank; started plainly as
@@ -50,8 +60,10 @@ HBM_PEAK = 8.0e12  # B/s, MI355X_MICROARCH.md chip table
 F32_MATRIX_PEAK = 157.3e12  # FLOP/s, dense v_mfma_f32_*_f32 (256 FLOPs/cycle/CU x 256 CUs x 2.4 GHz), same table
 F64_MATRIX_PEAK = 78.6e12   # FLOP/s, dense v_mfma_f64_*
 BF16_MATRIX_PEAK = 2.5e15   # FLOP/s, dense v_mfma_f32_*_bf16 (never the 2:1-sparsity figure), same table
-MIN_REGION_S = 0.2          # a timed region shorter than this is repeated (run_leg) and the median quoted
+MIN_REGION_S = 0.2          # --full: a timed region shorter than this is repeated (run_leg) and the median quoted
 MAX_REPEATS = 9
+DUMP_ROWS = 128             # --dump-outputs: rows of P written (fewer where they would pass DUMP_ROWS_BYTES)
+DUMP_ROWS_BYTES = 48 << 20
 
 
 def make_state(N, seed):
@@ -65,6 +77,13 @@ def make_state(N, seed):
     U = rng.normal(0.0, 0.01, size=(n, 8))
     s = np.arange(1, N + 1, dtype=np.float64)
     return w, x, s, d, U
+
+
+def dump_rows(n):
+    """Rows of P that --dump-outputs writes: the robot's three, then a fixed, seeded sample of the landmark rows, ascending."""
+    m = max(3, min(DUMP_ROWS, n, DUMP_ROWS_BYTES // (8 * n)))
+    rest = np.random.default_rng(20260101).choice(np.arange(3, n), size=m - 3, replace=False)
+    return np.concatenate([[0, 1, 2], np.sort(rest)]).astype(np.int64)
 
 
 def make_steps(w, N, count, Rc):
@@ -243,10 +262,15 @@ def main():
     ap.add_argument("--force-sharded", action="store_true",
                     help="--gpus 1 only: run the SHARDED code path (row-panel extraction, RCCL all-gather on the library's own 1-rank "
                          "communicator, sharded gather; cfg.force_sharded) -- the per-step fixed cost of a shard, measurable on one GPU")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-deferred", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines")
+    ap.add_argument("--no-deferred", action="store_true", help="--full: skip the deferred legs")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="skip the `other_configs` entry (configs[1] and configs[4]'s workload on one GPU, each run in a child process)")
+                    help="--full: skip the `other_configs` entry (configs[1] and configs[4]'s workload on one GPU, each run in a child process)")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline, every other measurement: the deferred legs, the CPU baselines, other_configs, the sharded "
+                         "breakdown, and a short timed region repeated (median quoted).  Without it only the headline leg runs, once")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the headline leg's state after its last timed step to DIR/<name>.npy (float64; module docstring)")
     args = ap.parse_args()
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -287,7 +311,7 @@ def main():
     seed = 20260101 + 3
     w, x, s, d, U = make_state(N, seed)
     Rc = [.01, 5.0]                                           # EKF_SLAM.m:13
-    batch = args.batch if args.batch > 1 and not args.no_deferred else 0
+    batch = args.batch if args.full and args.batch > 1 and not args.no_deferred else 0
     d_steps = 0
     if batch:
         d_steps = args.deferred_steps if args.deferred_steps > 0 else 40 * batch
@@ -315,7 +339,7 @@ def main():
     forced = bool(args.force_sharded) and world == 1
     sharded = world > 1 or forced
 
-    def run_leg(batch, nsteps, nwarm, lookahead=False):
+    def run_leg(batch, nsteps, nwarm, lookahead=False, dump=False):
         e = Engine(mode="known", capacity=N, tile=args.tile, device=device, rank=rank, world=world, batch=batch,
                    async_flush=args.async_flush, force_sharded=1 if forced else 0)
         e.load_lowrank_state(x, s, d, U)
@@ -394,9 +418,9 @@ def main():
         e.timing_enable(L.EKF_KERNEL_DOWNDATE, True, launches=max(nwarm, nsteps) + 8)
         dts = [timed_block(True)]
         # a timed region under 0.2 s is at the mercy of one scheduling hiccup (round 3: 0.01 s regions moved by 7 % between two runs of
-        # the same build): repeat the whole block -- the count follows from the FIRST block's max-over-ranks time, so every rank takes
-        # the same number -- and quote the median
-        if dts[0] < MIN_REGION_S:
+        # the same build): with --full, repeat the whole block -- the count follows from the FIRST block's max-over-ranks time, so every
+        # rank takes the same number -- and quote the median.  A plain run times exactly its K steps, once
+        if args.full and dts[0] < MIN_REGION_S:
             want = int(np.ceil(3 * MIN_REGION_S / max(dts[0], 1e-6)))
             want = min(MAX_REPEATS, max(3, want)) | 1
             while len(dts) < want:
@@ -405,8 +429,15 @@ def main():
         launches, kernel_ms = pass_stats
         kernel, kpairs = e.downdate_kernel_name()                # what the launcher actually chose for the last launch
         e.timing_enable(L.EKF_KERNEL_DOWNDATE, False)
+        outputs = None
+        if dump:
+            # what a caller receives after the last timed step (every block ends in the same state); all-reduced digest below
+            outputs = {"x": e.get_x()}
+            if world == 1:
+                outputs["P_diag_blocks"] = e.get_P_diag_blocks()
+                outputs["P_rows"] = np.stack([e.get_P_block(int(r), 0, 1, n)[0] for r in dump_rows(n)])
         breakdown = None
-        if sharded:
+        if sharded and args.full:
             # where a sharded update-step's time goes, from one more block with HIP events around every launch of every family (the
             # events cost launches of their own: this block is never the one quoted)
             kinds = (("extraction", L.EKF_KERNEL_ROWPANEL), ("all_gather", L.EKF_KERNEL_EXCHANGE), ("gather", L.EKF_KERNEL_GATHER),
@@ -440,6 +471,8 @@ def main():
             dist.all_reduce(tdig, op=dist.ReduceOp.SUM)
             digest = tdig.cpu().numpy()
         e.close()
+        if outputs is not None:
+            outputs["P_digest"] = np.asarray(digest, dtype=np.float64)
         avg_ms = kernel_ms / max(launches, 1)
         achieved = b_alg_rank / (avg_ms * 1e-3)
         per_launch = nsteps * len(dts) / max(launches, 1)
@@ -463,7 +496,7 @@ def main():
                 "repeats": len(dts), "ms_per_step_min": min(dts) / nsteps * 1e3, "ms_per_step_max": max(dts) / nsteps * 1e3,
                 "algorithmic_bytes_per_step": b_step, "effective_GBps": b_step / (ms_step * 1e-3) / 1e9,
                 "roofline": roof, "transport": transport, "state_finite": finite, "x_end": x_end, "digest": digest,
-                "breakdown_us_per_step": breakdown}
+                "breakdown_us_per_step": breakdown, "outputs": outputs}
 
     def public(leg, note):
         out = {k: leg[k] for k in ("value", "ms_per_step", "steps", "warmup", "repeats", "ms_per_step_min", "ms_per_step_max",
@@ -479,7 +512,7 @@ def main():
             out["x_equals_as_written_leg"] = bool(np.array_equal(leg["x_end"], head["x_end"]))
         return out
 
-    head = run_leg(1, args.steps, args.warmup)
+    head = run_leg(1, args.steps, args.warmup, dump=args.dump_outputs is not None)
     dfr = dfr2 = look = None
     if batch:
         dfr = run_leg(batch, d_steps, d_warm)
@@ -539,18 +572,22 @@ def main():
             out["deferred_lookahead"] = public(look, "as `deferred`, with the landmarks of the next %d corrections announced: one "
                                                      "all-gather per batch%s" % (batch, " (ekf_prefetch_rows)" if look["transport"] != "rccl-native" else
                                                      ", issued in front of the previous batch's pass and run beside it (ekf_prefetch_next)"))
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(N, x, s, d, U, steps[args.warmup:])
             # SURVEY.md 8d asks for both restatements beside the GPU figure: [0] the primary above, [1] the literal-dense one
             out["cpu_baselines"] = [out["cpu_baseline"], cpu_baseline_dense(N, seed, Rc)]
-        if world == 1 and not args.no_other_configs and not forced:
+        if world == 1 and args.full and not args.no_other_configs and not forced:
             out["other_configs"] = other_configs()
         if head["breakdown_us_per_step"] is not None:
             out["breakdown_us_per_step"] = head["breakdown_us_per_step"]
         timed_s = head["ms_per_step"] * 1e-3 * args.steps
-        if timed_s < MIN_REGION_S:
+        if head["repeats"] > 1 and timed_s < MIN_REGION_S:
             out["config"]["note"] = ("--steps %d: one timed region of the headline leg is %.3f s (< %.1f s): the block was run %d times, "
                                      "`value` is the median block's" % (args.steps, timed_s, MIN_REGION_S, head["repeats"]))
+        if args.dump_outputs is not None:
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            for name, arr in head["outputs"].items():
+                np.save(os.path.join(args.dump_outputs, name + ".npy"), np.ascontiguousarray(arr, dtype=np.float64))
         print(json.dumps(out), file=json_out, flush=True)
     if dist is not None:
         dist.destroy_process_group()

@@ -8,7 +8,7 @@ NumPy expression (eye(n), zeros(n), the 5 x n selector F_k, n x n x n products),
 so this file is the semantic ground truth for N <~ 1k landmarks; it is O(n^3)
 per step exactly like the reference.  Angles are degrees everywhere.
 
-Follows (file:line in /root/reference):
+Follows (file:line in the reference's MATLAB sources):
   EKF_SLAM.m:26-34    constructor             EKF_SLAM_UC.m:27-36
   EKF_SLAM.m:40-51    predict                 EKF_SLAM_UC.m:42-53
   EKF_SLAM.m:56-65    f (motion model)        EKF_SLAM_UC.m:58-67

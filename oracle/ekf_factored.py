@@ -21,7 +21,7 @@ robot block and the column strip P(k, 1:3) of an append (:91-96), each landmark'
 One association differs from the dense evaluation: (eye(n) - K H) P is formed as P - K (H P) (as oracle/ekf_structured.c and the HIP
 path do); entry by entry the two differ in the last bits of the update.
 
-Follows (file:line in /root/reference): EKF_SLAM.m:26-34 (state), :40-51 + :56-65 (predict, f), :67-98 (append), :100-151 (measure),
+Follows (file:line in the reference's MATLAB sources): EKF_SLAM.m:26-34 (state), :40-51 + :56-65 (predict, f), :67-98 (append), :100-151 (measure),
 EKF_SLAM_UC.m:13,16,102-152, Correspondence.m:28-88.  Angles are degrees everywhere.
 """
 import numpy as np

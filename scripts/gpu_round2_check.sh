@@ -7,7 +7,7 @@ timeout -k 10 900 python -m pytest tests -m gpu -q -x --durations=15 > $OUT/pyte
 rc=$?
 tail -25 $OUT/pytest.log
 if [ $rc -ge 124 ]; then echo "pytest timed out"; exit $rc; fi
-timeout -k 10 400 python bench.py > $OUT/bench.json 2> $OUT/bench.err
+timeout -k 10 400 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err
 rb=$?
 cat $OUT/bench.json; tail -5 $OUT/bench.err
 if [ $rb -ge 124 ]; then echo "bench timed out"; exit $rb; fi

@@ -1,21 +1,24 @@
 #!/bin/bash
 # Rehearse bench.py's multi-rank flow on ONE GPU (gloo backend, exchange staged through the host, every rank on device 0):
 # `python bench.py --gpus N` spawns its own ranks; every world size must end with the same state digest as the
-# single-process run.  Usage: scripts/rehearse_multirank.sh [landmarks]
+# single-process run.  Usage: scripts/rehearse_multirank.sh [landmarks [output directory]]
 set -e -o pipefail
 L=${1:-2000}
-mkdir -p gpurun_out
-python bench.py --landmarks $L --steps 96 --warmup 32 --deferred-steps 128 --no-cpu-baseline 2>gpurun_out/reh_1.err > gpurun_out/reh_1.json
+OUT=${2:-$(mktemp -d)}
+mkdir -p $OUT
+python bench.py --full --landmarks $L --steps 96 --warmup 32 --deferred-steps 128 --no-cpu-baseline 2>$OUT/reh_1.err > $OUT/reh_1.json
 for n in 2 4; do
-  EKF_BENCH_BACKEND=gloo timeout -k 10 400 python bench.py --gpus $n --landmarks $L --steps 96 --warmup 32 --deferred-steps 128 2>gpurun_out/reh_$n.err > gpurun_out/reh_$n.json
+  EKF_BENCH_BACKEND=gloo timeout -k 10 400 python bench.py --full --gpus $n --landmarks $L --steps 96 --warmup 32 --deferred-steps 128 2>$OUT/reh_$n.err > $OUT/reh_$n.json
 done
-python - <<'PY'
+python - "$OUT" <<'PY'
 import json
+import os
+import sys
 import numpy as np
 ref = None
 ref_def = None
 for n in (1, 2, 4):
-    b = json.loads(open("gpurun_out/reh_%d.json" % n).readline())
+    b = json.loads(open(os.path.join(sys.argv[1], "reh_%d.json" % n)).readline())
     assert b["n_gpus"] == n
     dg = np.array(b["config"]["state_digest"])
     print("world", n, "value", round(b["value"]), "digest", dg, "transport", b["config"]["transport"],

@@ -5,6 +5,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -57,3 +58,15 @@ def test_committed_pmc_summary_covers_the_default_bench_shapes():
         assert rec["kernel"] and kernel in rec["kernel"]
         assert 1.0 <= rec["hbm_bytes_per_launch"] / b_alg < 1.10, rec
     assert bench.load_committed_pmc(10000, 128, 7) is None          # a shape nobody measured: null, not a neighbour's figure
+
+
+def test_dumped_rows_of_P_stay_within_the_output_budget():
+    """--dump-outputs: the robot's rows and a fixed sample of the others, distinct and in range, under 48 MB at any map size."""
+    sys.path.insert(0, ROOT)
+    import bench
+    for n in (3, 5, 203, 20003, 100003, 400003):
+        rows = bench.dump_rows(n)
+        assert list(rows[:3]) == [0, 1, 2] and len(set(rows.tolist())) == len(rows) and rows.max() < n
+        assert len(rows) == min(n, 128) or 8 * n * (len(rows) + 1) > bench.DUMP_ROWS_BYTES
+        assert 8 * n * len(rows) <= bench.DUMP_ROWS_BYTES
+        np.testing.assert_array_equal(rows, bench.dump_rows(n))

@@ -1,12 +1,14 @@
-"""GPU: the default single-GPU bench line as the driver runs it (a fresh child process, never an exec from this one): ONE JSON line that carries the headline
+"""GPU: the single-GPU bench line as the driver runs it (a fresh child process, never an exec from this one).  `--full`: ONE JSON line that carries the headline
 with `roofline` and -- measured in the same invocation, each in a child process of its own -- BASELINE.json's other single-GPU configurations under
 `other_configs`: configs[1] (1 000 landmarks, unknown correspondence, the device-resident measure loop) and the whole configs[4] workload on one GPU
-(40 000 -> 50 000 landmarks, float tiles, the pass in F32 arithmetic and in split arithmetic).  Short legs here (the figures to quote come from the default run); no CPU baseline."""
+(40 000 -> 50 000 landmarks, float tiles, the pass in F32 arithmetic and in split arithmetic).  Short legs here (the figures to quote come from the default run); no CPU baseline.
+A plain run: the headline alone, exactly K timed steps once, and with --dump-outputs the state its last timed step left."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -14,8 +16,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_default_bench_line_carries_the_other_single_gpu_configurations():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "64", "--warmup", "16", "--deferred-steps", "80", "--no-cpu-baseline"],
-                       capture_output=True, text=True, timeout=900, cwd=ROOT)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "64", "--warmup", "16", "--deferred-steps", "80",
+                        "--no-cpu-baseline"], capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1
@@ -47,3 +49,39 @@ def test_default_bench_line_carries_the_other_single_gpu_configurations():
         ca = oc[key]
         assert "error" not in ca, oc
         assert ca["config"]["async_flush"] and ca["config"]["state_finite"] and ca["steps"] == 9936 and ca["value"] > 0.9 * syn["value"]
+
+
+def test_plain_bench_line_is_the_headline_alone_and_dumps_the_last_state(tmp_path):
+    """No --full: the headline leg only, its K timed steps timed once; --dump-outputs writes what the timed path's last step left
+    (float64, under 64 MB), and that is what the same W + K steps give through the plain methods, bit for bit."""
+    N, K, W = 1000, 40, 8
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--landmarks", str(N), "--steps", str(K), "--warmup", str(W),
+                        "--dump-outputs", str(out)], capture_output=True, text=True, timeout=300, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    b = json.loads(lines[0])
+    assert b["steps"] == K and b["warmup"] == W and b["repeats"] == 1 and b["ms_per_step"] > 0 and b["value"] > 0
+    assert b["unit"] == "update-steps/s" and b["higher_is_better"] and b["dtype"] == "f64" and b["config"]["state_finite"]
+    for key in ("deferred", "deferred_b32", "cpu_baseline", "cpu_baselines", "other_configs", "breakdown_us_per_step"):
+        assert key not in b, key
+    got = {p.name: np.load(p) for p in out.iterdir()}
+    assert set(got) == {"x.npy", "P_digest.npy", "P_diag_blocks.npy", "P_rows.npy"}
+    assert all(a.dtype == np.float64 for a in got.values()) and sum(a.nbytes for a in got.values()) <= 64 << 20
+    np.testing.assert_array_equal(got["P_digest.npy"], np.array(b["config"]["state_digest"]))
+
+    sys.path.insert(0, ROOT)
+    import bench
+    from ekf_slam_amd import Engine
+    n = 3 + 2 * N
+    w, x, s, d, U = bench.make_state(N, 20260101 + 3)
+    e = Engine(mode="known", capacity=N, tile=128, batch=1)
+    e.load_lowrank_state(x, s, d, U)
+    for (u, z, R, k) in bench.make_steps(w, N, W + K, [.01, 5.0]):
+        e.predict(u); e.correct(z, R, k)
+    np.testing.assert_array_equal(got["x.npy"], e.get_x())
+    np.testing.assert_array_equal(got["P_diag_blocks.npy"], e.get_P_diag_blocks())
+    np.testing.assert_array_equal(got["P_rows.npy"], e.get_P()[bench.dump_rows(n)])
+    np.testing.assert_array_equal(got["P_digest.npy"], e.digest())
+    e.close()
