@@ -104,22 +104,33 @@ struct ekf_handle {
     int throttle_k = 0, since_mark = 0;
     DevState st;
     hipStream_t own_stream = nullptr, stream = nullptr;
-    // work list of owned lower-triangle tiles for the active tile rows
-    int2 *d_work = nullptr;
-    int64_t nwork = 0, work_rows = -1, work_cap = 0;
+    // Work lists of the owned lower-triangle tiles of the active tile rows, in two sets.  The pass kernels fetch their entries for their
+    // whole lifetime, so refresh_work never rewrites the set an in-flight pass (cfg.async_flush) holds: it builds the other one.
+    struct WorkSet {
+        int2 *work = nullptr;          // the tiles, row by row
+        int64_t nwork = 0;
+        // the same tiles arranged as 8 per-XCD streams of super-tiles (batched flush: keeps each XCD's K/G working set
+        // inside its own 4 MiB L2); stream x is xcd[x * xcd_len .. ), padded with (-1,-1)
+        int2 *xcd = nullptr;
+        int64_t xcd_len = 0;
+        int4 *segs = nullptr;          // cfg.pass_arith != EKF_ARITH_F64: the strip form's work list (PassAux::segs, nsegs, cols)
+        int64_t nsegs = 0, cols = 0;
+        int64_t rows = -1;             // tile rows it was built for (-1: none)
+    };
+    WorkSet ws[2];
+    int32_t ws_cur = 0;                // the newest set: what the next pass, digest or low-rank load reads
+    int32_t ws_pass = -1;              // the set the in-flight pass holds (-1: no pass in flight)
+    bool ws_unordered = false;         // ws[ws_cur] was uploaded after the last ev_pairs: a pass that only waits for ev_pairs must wait for ev_wl too
+    int64_t work_cap = 0;
     // pinned staging of the work lists (refresh_work): uploads are queued on the stream with no host wait -- a stream
     // synchronisation here drains a queue that may hold a whole batch and its pass (configs[4]: a 2.4 ms bubble per new tile row)
     char *wl_stage = nullptr;
     size_t wl_stage_bytes = 0;
     hipEvent_t ev_wl = nullptr;
     bool wl_busy = false;
-    // the same tiles arranged as 8 per-XCD streams of super-tiles (batched flush: keeps each XCD's K/G working set
-    // inside its own 4 MiB L2); stream x is work_xcd[x * xcd_len .. ), padded with (-1,-1)
-    int2 *d_work_xcd = nullptr;
-    int64_t xcd_len = 0;
-    // cfg.pass_arith = EKF_ARITH_F32: the strip form of the pass (flush32_pipe.h) -- its work list, the dump area
+    // cfg.pass_arith = EKF_ARITH_F32: the strip form of the pass (flush32_pipe.h) -- the dump area, the split planes (the work list
+    // fields are filled from the pass's WorkSet at each launch)
     PassAux aux = { nullptr, 0, nullptr, 0, 0, nullptr, nullptr };
-    int4 *d_segs = nullptr;
     int64_t segs_cap = 0;
     AssocDecision *d_partial = nullptr, *d_decision = nullptr, *h_decision = nullptr;
     AssocDecision *h_decision_dev = nullptr;   // device-side address of the mapped h_decision (k_assoc_merge, the sharded path, writes it)
@@ -245,10 +256,13 @@ int32_t use_device(ekf_handle *h) {
 
 // (re)build the list of owned tiles for the active tile rows.  The lists are built in pinned memory and uploaded by asynchronous
 // copies in stream order (the kernels that read them follow on the same stream); the staging area is reused only after the event
-// behind the previous upload has passed.
+// behind the previous upload has passed.  The upload goes to the set no in-flight pass holds: the newest set itself when the pass
+// holds the other one (or none is in flight -- the main stream is ordered after every retired pass), else the other set.
 int32_t refresh_work(ekf_handle *h) {
     const int64_t nt = ekf_tiles_for(n_mm(h), h->T);
-    if (nt == h->work_rows) return EKF_OK;
+    if (nt == h->ws[h->ws_cur].rows) return EKF_OK;
+    const int32_t to = h->ws_pass == h->ws_cur ? h->ws_cur ^ 1 : h->ws_cur;
+    ekf_handle::WorkSet &ws = h->ws[to];
     const size_t b_work = (size_t)h->work_cap * sizeof(int2), b_xcd = 8 * b_work, b_segs = (size_t)h->segs_cap * sizeof(int4);
     if (!h->wl_stage) {
         h->wl_stage_bytes = b_work + b_xcd + b_segs;
@@ -264,9 +278,9 @@ int32_t refresh_work(ekf_handle *h) {
     for (int64_t I = 0; I < nt; ++I)
         for (int64_t J = 0; J <= I; ++J)
             if (h->st.tm.mine(I, J)) w[nw++] = make_int2((int)I, (int)J);
-    if (nw) HIPCHK(h, hipMemcpyAsync(h->d_work, w, nw * sizeof(int2), hipMemcpyHostToDevice, h->stream));
-    h->nwork = (int64_t)nw;
-    h->work_rows = nt;
+    if (nw) HIPCHK(h, hipMemcpyAsync(ws.work, w, nw * sizeof(int2), hipMemcpyHostToDevice, h->stream));
+    ws.nwork = (int64_t)nw;
+    ws.rows = nt;
 
     // per-XCD streams: super-tiles of S x S tiles, largest first onto the least loaded stream
     static const int S = std::max(1, ekf_tune_int("EKF_SUPERTILE", 8));
@@ -308,23 +322,32 @@ int32_t refresh_work(ekf_handle *h) {
     REQUIRE(h, (int64_t)(8 * len) <= 8 * h->work_cap, EKF_ERR_STATE, "XCD work list overflow");
     std::fill(flat, flat + 8 * len, make_int2(-1, -1));
     for (int x = 0; x < 8; ++x) std::copy(stream[x].begin(), stream[x].end(), flat + x * len);
-    if (len) HIPCHK(h, hipMemcpyAsync(h->d_work_xcd, flat, 8 * len * sizeof(int2), hipMemcpyHostToDevice, h->stream));
-    h->xcd_len = (int64_t)len;
-    if (h->d_segs) {                                  // the strip work list of the same tiles
+    if (len) HIPCHK(h, hipMemcpyAsync(ws.xcd, flat, 8 * len * sizeof(int2), hipMemcpyHostToDevice, h->stream));
+    ws.xcd_len = (int64_t)len;
+    if (ws.segs) {                                    // the strip work list of the same tiles
         std::vector<int4> sg;
         const int64_t nsegs = build_strip_segments(h->st.tm, nt, sg);
         REQUIRE(h, (int64_t)sg.size() <= h->segs_cap, EKF_ERR_STATE, "strip work list overflow");
         if (!sg.empty()) {
             std::copy(sg.begin(), sg.end(), segs);
-            HIPCHK(h, hipMemcpyAsync(h->d_segs, segs, sg.size() * sizeof(int4), hipMemcpyHostToDevice, h->stream));
+            HIPCHK(h, hipMemcpyAsync(ws.segs, segs, sg.size() * sizeof(int4), hipMemcpyHostToDevice, h->stream));
         }
-        h->aux.segs = h->d_segs;
-        h->aux.nsegs = nsegs;
-        h->aux.cols = nt * h->T;
+        ws.nsegs = nsegs;
+        ws.cols = nt * h->T;
     }
     HIPCHK(h, hipEventRecord(h->ev_wl, h->stream));
     h->wl_busy = true;
+    h->ws_cur = to;
+    h->ws_unordered = true;
     return EKF_OK;
+}
+
+// the strip form's arguments for a pass over the work set `ws` (nullptr: the handle has no strip form)
+const PassAux *pass_aux(const ekf_handle *h, const ekf_handle::WorkSet &ws, PassAux &out) {
+    if (!ws.segs) return nullptr;
+    out = h->aux;
+    out.segs = ws.segs; out.nsegs = ws.nsegs; out.cols = ws.cols;
+    return &out;
 }
 
 struct TimedLaunch {
@@ -365,6 +388,7 @@ int32_t retire_inflight(ekf_handle *h) {
         h->appended_inflight = false;
     }
     HIPCHK(h, hipStreamWaitEvent(h->stream, h->ev_flushed, 0));
+    h->ws_pass = -1;           // (later uploads on the main stream are ordered after the pass: its work set is free)
     h->base ^= 1;
     h->st.tiles = h->tilebuf[h->base];
     h->pstart = (h->pstart + h->nfrozen) % h->st.pcap;
@@ -472,9 +496,11 @@ int32_t flush_pending(ekf_handle *h, bool batch_done = false) {
             nx.send = corr_send(h, slab_for(h, n_mm(h)));
         }
         TimedLaunch tl(h, EKF_KERNEL_DOWNDATE);
-        HIPCHK(h, launch_downdate(h->st, h->st.tiles, h->d_work, h->nwork, h->d_work_xcd, h->xcd_len, h->pstart, h->npend,
+        const ekf_handle::WorkSet &ws = h->ws[h->ws_cur];     // (in place, on the main stream: ordered after its upload)
+        PassAux ax;
+        HIPCHK(h, launch_downdate(h->st, h->st.tiles, ws.work, ws.nwork, ws.xcd, ws.xcd_len, h->pstart, h->npend,
                                   h->storage, h->grid_cap, h->stream, h->dd_kernel, nx.j >= 0 ? &nx : nullptr, &extracted, h->cfg.pass_arith,
-                                  h->d_segs ? &h->aux : nullptr));
+                                  pass_aux(h, ws, ax)));
         h->dd_pairs = h->npend;
     }
     h->npend = 0;
@@ -495,11 +521,14 @@ int32_t batch_complete(ekf_handle *h) {
     // (the previous pass precedes it in the flush stream's own order).  Recording it after that wait would chain the passes
     // through two cross-stream hand-overs per batch (previous pass -> main stream -> this pass): ~30 us per update-step at batch 1.
     HIPCHK(h, hipEventRecord(h->ev_pairs, h->stream));
+    h->ws_unordered = false;                      // every work-list upload so far precedes ev_pairs
     int32_t rc = retire_inflight(h);              // at most one flush in flight; later main-stream kernels read its output
     if (rc) return rc;
     rc = refresh_work(h);
     if (rc) return rc;
     HIPCHK(h, hipStreamWaitEvent(h->flush_stream, h->ev_pairs, 0));
+    // a work set uploaded just now (behind ev_pairs) is ordered before the pass by its own event
+    if (h->ws_unordered) HIPCHK(h, hipStreamWaitEvent(h->flush_stream, h->ev_wl, 0));
     {
         KernelTimer *t = &h->timers[EKF_KERNEL_DOWNDATE];
         hipEvent_t stop = nullptr;
@@ -514,15 +543,18 @@ int32_t batch_complete(ekf_handle *h) {
             t->used += 2;
         }
         next_pass_direction(h);
-        HIPCHK(h, launch_downdate(h->st, h->tilebuf[h->base ^ 1], h->d_work, h->nwork, h->d_work_xcd, h->xcd_len, h->pstart,
+        const ekf_handle::WorkSet &ws = h->ws[h->ws_cur];
+        PassAux ax;
+        HIPCHK(h, launch_downdate(h->st, h->tilebuf[h->base ^ 1], ws.work, ws.nwork, ws.xcd, ws.xcd_len, h->pstart,
                                   h->npend, h->storage, h->grid_cap, h->flush_stream, h->dd_kernel, nullptr, nullptr, h->cfg.pass_arith,
-                                  h->d_segs ? &h->aux : nullptr));
+                                  pass_aux(h, ws, ax)));
         h->dd_pairs = h->npend;
         if (stop) HIPCHK(h, hipEventRecord(stop, h->flush_stream));
     }
     HIPCHK(h, hipEventRecord(h->ev_flushed, h->flush_stream));
     h->nfrozen = h->npend;
     h->inflight = true;
+    h->ws_pass = h->ws_cur;                       // refresh_work leaves this set alone until the pass retires
     h->inflight_N = h->N;
     h->appended_inflight = false;
     return EKF_OK;
@@ -1228,7 +1260,7 @@ int32_t ekf_create(const ekf_config *cfg, ekf_handle **out) {
         if (h->aux.grid < 8) h->aux.grid = 8;
         const int64_t ranges = (2 * nt_cap + ekf_pipe32::kSeg * world - 1) / (ekf_pipe32::kSeg * world);
         h->segs_cap = 4 * slots + (2 * nt_cap * ranges + 8) * ekf_pipe32::kSeg;
-        HIPCHK(h, dalloc(h, &h->d_segs, (size_t)h->segs_cap));
+        for (auto &ws : h->ws) HIPCHK(h, dalloc(h, &ws.segs, (size_t)h->segs_cap));
         float *dump = nullptr;
         HIPCHK(h, dalloc(h, &dump, (size_t)h->aux.grid * ekf_pipe32::kDumpFloats));
         h->aux.dump = dump;
@@ -1239,8 +1271,10 @@ int32_t ekf_create(const ekf_config *cfg, ekf_handle **out) {
         }
     }
     HIPCHK(h, dalloc(h, &h->st.small, 32));
-    HIPCHK(h, dalloc(h, &h->d_work, (size_t)slots));
-    HIPCHK(h, dalloc(h, &h->d_work_xcd, (size_t)slots * 8));
+    for (auto &ws : h->ws) {
+        HIPCHK(h, dalloc(h, &ws.work, (size_t)slots));
+        HIPCHK(h, dalloc(h, &ws.xcd, (size_t)slots * 8));
+    }
     HIPCHK(h, dalloc(h, &h->d_partial, (size_t)((h->cap + kAssocBlock - 1) / kAssocBlock)));
     HIPCHK(h, dalloc(h, &h->d_decision, 1));
     HIPCHK(h, dalloc(h, &h->d_ticket, 1));
@@ -1886,11 +1920,11 @@ int32_t ekf_load_lowrank_state(ekf_handle *h, int64_t N, const double *x, const 
     int32_t rc = enter(h);
     if (rc) return rc;
     const int64_t n = 3 + 2 * N;
+    { const int32_t rcr = retire_inflight(h); if (rcr) return rcr; }      // (before clear_pairs: the pass reads the pair ring)
     if (N < h->N) HIPCHK(h, clear_pairs(h));
     h->N = N;
     h->s_host.assign(s, s + N);
     h->s_sorted_ok = false;
-    { const int32_t rcr = retire_inflight(h); if (rcr) return rcr; }
     h->npend = 0; h->pstart = 0;   // the whole state is replaced ...
     h->pf_valid = false;           // ... and with it every prefetched base row-panel
     h->nx_valid = false;
@@ -1903,7 +1937,7 @@ int32_t ekf_load_lowrank_state(ekf_handle *h, int64_t N, const double *x, const 
     if (e == hipSuccess) e = hipMemcpyAsync(dU, U, (size_t)(n * k) * 8, hipMemcpyHostToDevice, h->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(h->st.x[h->cur], x, (size_t)n * 8, hipMemcpyHostToDevice, h->stream);
     if (e == hipSuccess && N > 0) e = hipMemcpyAsync(h->st.s, s, (size_t)N * 8, hipMemcpyHostToDevice, h->stream);
-    if (e == hipSuccess) e = launch_lowrank(h->st, h->cur, 2 * N, h->d_work, h->nwork, dd, dU, k, h->storage, h->stream);
+    if (e == hipSuccess) e = launch_lowrank(h->st, h->cur, 2 * N, h->ws[h->ws_cur].work, h->ws[h->ws_cur].nwork, dd, dU, k, h->storage, h->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
     hipFree(dd);
     if (dU) hipFree(dU);
@@ -2026,7 +2060,7 @@ int32_t ekf_checkpoint_load(ekf_handle *h, const char *path) {
     h->N = hd.N;
     h->s_host = shost;
     h->s_sorted_ok = false;
-    h->work_rows = -1;
+    h->ws[h->ws_cur].rows = -1;  // (no pass is in flight: the newest set is rebuilt in place)
     return done(rc);
 }
 
@@ -2038,7 +2072,7 @@ int32_t ekf_P_digest(ekf_handle *h, double out[3]) {
     if (rc) return rc;
     rc = refresh_work(h);
     if (rc) return rc;
-    HIPCHK(h, launch_digest(h->st, h->cur, n_mm(h), h->d_work, h->nwork, h->d_digest, h->storage, h->stream));
+    HIPCHK(h, launch_digest(h->st, h->cur, n_mm(h), h->ws[h->ws_cur].work, h->ws[h->ws_cur].nwork, h->d_digest, h->storage, h->stream));
     HIPCHK(h, hipMemcpyAsync(h->h_small, h->d_digest, 3 * 8, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     out[0] = h->h_small[0]; out[1] = h->h_small[1]; out[2] = h->h_small[2];

@@ -1,0 +1,257 @@
+"""GPU: the asynchronous pass over P (cfg.async_flush) at a size where one pass lasts longer than a step, while streaming appends push
+the map across tile-row edges (configs[4]'s step: predict, append one landmark, correct).
+
+A tile-row crossing rebuilds the pass work lists (abi.hip: refresh_work).  A pass still in flight on the pass stream reads its work list
+for its whole lifetime, so a rebuild that overwrote the list it reads would make it skip some tiles and do others twice; a skipped tile
+keeps the values of two passes earlier, silently.  Each leg places four crossings 2 steps after a batch boundary and drives the
+asynchronous engine alone through the precomputed plan (the synchronous engine and the oracle run afterwards), so that the crossing's
+correction is issued ~0.1 ms after the boundary's: at least three rebuilds must be issued within 3/4 of the measured pass time.  It then
+compares, against the synchronous engine of the same storage and batch and against the factored F64 oracle (oracle/ekf_factored.py), x,
+the digests of P, every landmark's diagonal block and the two rows of one landmark of EVERY tile row over all columns -- rows that touch
+every tile (I, J) of the lower triangle.  The oracle alone shows that the two batches a skipped tile lacks change every tile of those rows
+by more than 20x the leg's row tolerance.  Without the work-list double buffering every leg fails here (rows off by 0.2-0.9 of their
+largest entry)."""
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+SEED = 20260101 + 5
+# Inputs: P = diag(d) + U U' (d ~ U(0.01, 0.1)), U ~ N(0, sigma) in the landmark rows and N(0, sigma_robot) in the robot rows, range /
+# bearing variance factors RC.  The correlations must be strong enough that two batches move every tile of the sampled rows well beyond
+# the row tolerance; float tiles keep U as small as that allows, since the float rounding of the rows each correction reads reaches x
+# and the F64-kept parts in proportion.  The bearing factor (0.5 instead of configs[4]'s 5) keeps the appended landmarks' own blocks, the
+# largest entries and so the scale of the row tolerance, near 2.
+INPUTS = {"f64": (0.1, 0.1, (.01, .5)), "float": (0.04, 0.04, (.01, .5)), "float_b": (0.03, 0.03, (.01, .5))}
+
+# leg: storage, batch, tile edge, the pass kernel the batch selects, shards (0: a plain engine)
+LEGS = {
+    "a_f64": ("f64", 8, 128, "k_flush_mfma<double,128,", 0),
+    # 32 pairs (not 16): at 16 the two batches a skipped tile lacks move every tile by > 20x the row tolerance only with U at 0.04, where
+    # the SYNCHRONOUS engine's x already exceeds the bound below (5.2e-9 against 1.8e-9); at 32 pairs U stays at 0.03
+    "b_f32_mixed_mfma": ("f32_mixed", 32, 256, "k_flush_mfma32<256,", 0),
+    "c_f32_mixed_strip": ("f32_mixed", 64, 256, "k_flush_strip32<8>", 0),
+    # 32 pairs (not 40): the crossings come every 128 appends, and only a batch that divides 128 keeps every crossing at the same
+    # place behind a batch boundary; 28-64 pairs all select the split kernel
+    "d_f32_split": ("f32_split", 32, 256, "k_flush_split3<2>", 0),
+    "e_f64_two_shards": ("f64", 8, 128, "k_flush_mfma<double,128,", 2),
+}
+
+
+def placement(T, batch):
+    """(N0, steps): ~20 000 landmarks; the first crossing 2 steps after the second batch boundary, two more every T / 2 appends after it
+    (the batch divides T / 2, so they all land at the same place behind a boundary)"""
+    half = T // 2
+    assert half % batch == 0
+    first = 2 * batch + 1
+    N0 = (20000 + first) // half * half - first
+    return N0, first + 3 * half + 4
+
+
+def crossings(N0, steps, T, batch):
+    """steps t whose append makes ceil(2N / T) grow (N0 + t landmarks before it, a multiple of T / 2), and those of them that fall 1-4
+    steps after a batch boundary other than the first (boundary: the correction of step kB - 1 completes batch k)"""
+    cross = [t for t in range(steps) if (N0 + t) % (T // 2) == 0 and N0 + t > 0]
+    counted = [t for t in cross if 1 <= (t + 1) % batch <= 4 and (t + 1) // batch >= 2]
+    return cross, counted
+
+
+def make_inputs(N0, steps, sigma, sigma_robot, RC):
+    from ekf_slam_amd.world import World
+    cap = N0 + steps
+    w = World(cap, SEED)
+    rng = np.random.default_rng(77)
+    n0 = 3 + 2 * N0
+    x = np.concatenate([[0.0, 0.0, 0.0], w.landmarks[:N0].reshape(-1)])
+    d = rng.uniform(0.01, 0.1, n0)
+    U = rng.normal(0.0, sigma, (n0, 8))
+    U[:3] = rng.normal(0.0, sigma_robot, (3, 8))
+    s = np.arange(1, N0 + 1.0)
+    plan = []
+    for t in range(steps):
+        u = w.step()
+        k = (t * 37) % N0 if t % 7 else N0 + (t * 5) % (t + 1)     # every 7th step: a landmark appended on the way (incl. the newest)
+        (_, r, b), = w.observe([k])
+        R = np.diag([r * RC[0], b * RC[1]])
+        plan.append((u, R, w.landmarks[N0 + t].copy(), float(N0 + t + 1), np.array([r, b]), k))
+    return (x, s, d, U), plan
+
+
+def sampled_landmarks(N, T):
+    """one landmark per tile row of the landmark block (its two rows lie in tile row 2L // T), spread over the rows' positions"""
+    nt = -(-2 * N // T)
+    half = T // 2
+    return [min(I * half + (I * 37) % half, N - 1) for I in range(nt)]
+
+
+def oracle_rows(ref, lms):
+    """P(3 + 2L : 5 + 2L, :) of the factored oracle for every landmark L of lms: (len(lms), 2, n), the correction terms in one product"""
+    m = ref.m
+    js = np.array([2 * L for L in lms])
+    base = np.stack([ref._base_rows(int(j)) for j in js])          # (k, 2, m)
+    if ref.nt:
+        Lm, Rm = ref._terms()
+        rows = np.concatenate([js, js + 1])
+        upd = Lm[rows, :2 * ref.nt] @ Rm[:2 * ref.nt, :m]
+        base[:, 0] += upd[:len(js)]
+        base[:, 1] += upd[len(js):]
+    strip = np.stack([ref.Pmr[j:j + 2] for j in js])                # (k, 2, 3)
+    return np.concatenate([strip, base], axis=2)
+
+
+def tile_change_margin(before, after, lms, N_before, T, tol_abs):
+    """smallest over the sampled rows q and over every tile column range J of (largest change in those columns) / tol_abs[q]"""
+    m = 2 * N_before
+    worst = np.inf
+    for q, L in enumerate(lms):
+        if L >= N_before:
+            continue
+        dlt = np.abs(after[q][:, 3:3 + m] - before[q][:, 3:3 + m])
+        for J in range(-(-m // T)):
+            worst = min(worst, float(dlt[:, J * T:min(m, (J + 1) * T)].max()) / tol_abs[q])
+    return worst
+
+
+def engine_rows(eng, lms, n):
+    """the same rows read from an engine, or merged from the shards of a group (NaN where a shard does not hold a tile)"""
+    out = []
+    for L in lms:
+        if hasattr(eng, "shards"):
+            merged = np.full((2, n), np.nan)
+            for e in eng.shards:
+                b = e.get_P_block(3 + 2 * L, 0, 2, n)
+                hole = np.isnan(merged)
+                merged[hole] = b[hole]
+            assert not np.isnan(merged).any()
+            out.append(merged)
+        else:
+            out.append(eng.get_P_block(3 + 2 * L, 0, 2, n))
+    return np.stack(out)
+
+
+def rel_err(a, b):
+    a, b = np.asarray(a), np.asarray(b)
+    return float(np.abs(a - b).max() / max(np.abs(b).max(), 1e-300))
+
+
+@pytest.mark.parametrize("leg", list(LEGS))
+def test_async_pass_beside_tile_row_crossings(leg):
+    from ekf_slam_amd import Engine, _lib as L
+    from ekf_slam_amd.sharding import ShardGroup
+    from oracle.ekf_factored import FactoredEKF
+    storage, batch, T, kernel, shards = LEGS[leg]
+    N0, steps = placement(T, batch)
+    cap = N0 + steps
+    cross, counted = crossings(N0, steps, T, batch)
+    print("%s: N0 %d, %d steps, batch %d, tile %d; tile-row crossings at steps %s, %s of them 1-4 steps after a batch boundary"
+          % (leg, N0, steps, batch, T, cross, counted))
+    assert len(counted) >= 4
+    (x, s, d, U), plan = make_inputs(N0, steps, *INPUTS["f64" if storage == "f64" else "float_b" if leg.startswith("b_") else "float"])
+
+    kw = dict(mode="known", capacity=cap, storage=storage, batch=batch)
+    syn = Engine(**kw)
+    asy = ShardGroup(shards, async_flush=True, **kw) if shards else Engine(async_flush=True, **kw)
+    aengines = asy.shards if shards else [asy]
+    ref = FactoredEKF(cap, "known", max_terms=steps + 4, max_appends=steps + 4)
+    for e in (syn, asy, ref):
+        e.load_lowrank_state(x, s, d, U)
+    for e in aengines:
+        e.timing_enable(L.EKF_KERNEL_DOWNDATE, True, launches=steps // batch + 8)
+
+    # 1. the asynchronous engine ALONE, nothing else on the host between its calls: the crossing's correction (the work-list rebuild) is
+    # issued while the pass launched at the boundary before it still runs -- asserted below from the host clock and the pass timers
+    import time
+    issued = []
+    names = []
+    for t, (u, R, pos, sig, z, k) in enumerate(plan):
+        asy.predict(u); asy.append(u, R, pos, sig)
+        issued.append(time.perf_counter())
+        asy.correct(z, R, k)
+        if (t + 1) % batch == 0:
+            names.append(tuple(e.downdate_kernel_name()[0] for e in aengines))
+    passes = []
+    for e in aengines:
+        cnt, ms = e.timing_read(L.EKF_KERNEL_DOWNDATE)
+        passes.append((cnt, ms / max(cnt, 1)))
+    gaps = [1e3 * (issued[t] - issued[(t + 1) // batch * batch - 1]) for t in counted]
+    print("%s: pass kernel %s; asynchronous passes per engine (count, mean ms): %s; host ms from the boundary's correction to the "
+          "crossing's: %s" % (leg, names[-1], passes, ["%.3f" % g for g in gaps]))
+    assert all(nm.startswith(kernel) for nm in names[-1]), names[-1]
+    assert all(cnt >= steps // batch - 1 and mean >= 0.5 for cnt, mean in passes), passes
+    # the premise: at least three rebuilds issued within 3/4 of a pass of the pass's launch (the host's run-ahead throttle blocks now and
+    # then, so not every crossing qualifies; the fourth is there for that).  Two shards: the longer of the two passes, since the group's
+    # host loop pays an exchange per step and the shards' passes differ in length.
+    inside = [t for t, g in zip(counted, gaps) if g <= 0.75 * max(mean for _, mean in passes)]
+    assert len(inside) >= 3, (gaps, passes)
+
+    # 2. the synchronous engine on the same plan
+    for u, R, pos, sig, z, k in plan:
+        syn.predict(u); syn.append(u, R, pos, sig); syn.correct(z, R, k)
+
+    # 3. the oracle, with its sampled rows two batch boundaries apart -- what a tile that one pass skipped lacks (the pass writes the
+    # other store, so a skipped tile keeps that store's values of two passes earlier)
+    snap_at = [(steps // batch - 2) * batch - 1, (steps // batch) * batch - 1]
+    snaps = []
+    for t, (u, R, pos, sig, z, k) in enumerate(plan):
+        ref.predict(u); ref.append(u, R, pos, sig); ref.correct(z, R, k + 1)
+        if t in snap_at:
+            lms_b = snaps[0][1] if snaps else sampled_landmarks(ref.N, T)
+            snaps.append((ref.N, lms_b, oracle_rows(ref, lms_b)))
+    assert ref.N == cap and syn.N == cap and asy.N == cap
+
+    n = 3 + 2 * cap
+    lms = sampled_landmarks(cap, T)
+    ro = oracle_rows(ref, lms)
+    rs = engine_rows(syn, lms, n)
+    ra = engine_rows(asy, lms, n)
+    xs, xa = syn.get_x(), asy.get_x()
+    ds, da = syn.digest(), asy.digest()
+    Ds, Da = syn.get_P_diag_blocks(), (asy.shards[0] if shards else asy).get_P_diag_blocks()
+    Dref = ref.diag_blocks()
+    scale = float(np.abs(ro).max())
+
+    if storage == "f64":
+        tol_x = tol_P = tol_rows = 1e-6
+    else:
+        tol_x, tol_P, tol_rows = 1e-9 + 2e-12 * steps, 2e-9 + 6e-12 * steps, 2e-7
+
+    # sensitivity of the row comparison: two batches of corrections move every tile of the sampled rows by > 20x its tolerance
+    (N_b, lms_b, before), (_, _, after) = snaps
+    margin = tile_change_margin(before, after, lms_b, N_b, T, np.full(len(lms_b), tol_rows * scale))
+    print("%s: sensitivity, smallest per-tile change of the sampled rows over two batches (steps %d -> %d) / row tolerance: %.1f"
+          % (leg, snap_at[0], snap_at[1], margin))
+    assert margin >= 20.0
+
+    def report(rows, xv, Dv):
+        pos = [tile for tile in np.argwhere(np.abs(rows - ro) > tol_rows * scale)]
+        first = None
+        if pos:
+            q, _, c = pos[0]
+            first = "landmark %d (tile row %d), column %d (tile column %d)" % (lms[q], 2 * lms[q] // T, c, max(c - 3, 0) // T)
+        return {"rows": float(np.abs(rows - ro).max()) / scale, "x": rel_err(xv, ref.x), "robot_rows": rel_err(rows[:, :, :3], ro[:, :, :3]),
+                "diag_blocks": float(np.abs(Dv[1:] - Dref).max() / np.abs(Dref).max()), "first_row_outside": first}
+
+    es, ea = report(rs, xs, Ds), report(ra, xa, Da)
+    print("%s: errors against the oracle (tolerances x %.2g, F64-kept %.2g, rows %.2g of %.3g): sync %s, async %s"
+          % (leg, tol_x, tol_P, tol_rows, scale, es, ea))
+    if storage == "f64":
+        # the asynchronous schedule runs the same kernels on the same operands in the same order: bit for bit
+        bad = np.argwhere(ra != rs)
+        assert bad.size == 0, "%s: async rows differ from sync at landmark %d (tile row %d), column %d: %r vs %r" % (
+            leg, lms[bad[0][0]], 2 * lms[bad[0][0]] // T, bad[0][2], ra[tuple(bad[0])], rs[tuple(bad[0])])
+        np.testing.assert_array_equal(xa, xs)
+        np.testing.assert_array_equal(Da, Ds)
+        if shards:
+            np.testing.assert_allclose(da, ds, rtol=1e-12)         # the shards' digests add in another order
+        else:
+            np.testing.assert_array_equal(da, ds)
+    else:
+        # float tiles: the pass's stores interleave differently with the corrections' reads (tests/test_f32_mixed_gpu.py), not bitwise
+        assert rel_err(xa, xs) <= 2 * tol_x
+        assert float(np.abs(ra - rs).max()) <= 2 * tol_rows * scale, (leg, float(np.abs(ra - rs).max()) / scale)
+        assert float(np.abs(Da - Ds).max()) <= 2 * tol_P * float(np.abs(Ds).max())
+        assert float(np.max(np.abs(da - ds) / np.abs(ds))) <= 2 * tol_P
+        assert ea["rows"] <= max(es["rows"], tol_rows / 2), (es, ea)      # the async rows are not the less accurate ones
+    for tag, r in (("sync", es), ("async", ea)):
+        assert r["rows"] <= tol_rows and r["x"] <= tol_x and r["robot_rows"] <= tol_P and r["diag_blocks"] <= tol_P, (leg, tag, r)
+    syn.close(); asy.close()
