@@ -156,9 +156,28 @@ struct ekf_handle {
     int64_t lparts_stride = 0;
     int32_t loop_set = 0;                      // set written last
     AssocHostPartial *h_lrec = nullptr, *h_lrec_dev = nullptr;     // MAPPED: kLoopRing decision records
-    struct LoopSpec { int32_t seq, is_new; int64_t idx; };
+    struct LoopSpec { int32_t seq, is_new; int64_t idx; };   // (cfg.device_assoc == 4: nothing predicted, the record IS the decision)
     std::vector<LoopSpec> lspec;               // predictions of records lrec_tail .. lrec_head-1 (ring positions mod kLoopRing)
     uint64_t lrec_head = 0, lrec_tail = 0;
+    // The device-decided branch (cfg.device_assoc == 4): the device also takes the branch of every row, so the host no longer knows N
+    // until the records of the rows it queued have landed ("settled").  N above is the settled count, N + the unsettled rows an upper
+    // bound (n_hi) that sizes grids and work lists.  The count itself lives on the device, in a ring with one slot per launch.
+    static constexpr int kNRing = 1024;
+    int64_t *d_nring = nullptr;                // DEVICE: kNRing landmark counts
+    uint64_t nrow = 0;                         // decided launches so far: slot nrow % kNRing holds the count the next one starts from
+    // Landmark-list entries of every key a queued row could append under (EKF_SLAM_UC.m:122; x, y and how many entries carry the key),
+    // one set per scan, in MAPPED memory the append branch reads; a set is reused once a record of a launch queued after its scan has
+    // landed (that scan's kernels are done).
+    static constexpr int kTabSets = 64, kTabCap = 512;
+    double *h_loctab = nullptr, *h_loctab_dev = nullptr;
+    int32_t *d_abort = nullptr;                // DEVICE: the scan whose rows stopped at a failed lookup (DevLoopArgs::abort)
+    int32_t scan_id = 0;
+    int64_t lookup_fail_hits = -1;             // settled: a row's append matched this many list entries (-1: none failed)
+    uint64_t tab_until[kTabSets] = {};
+    bool tab_used[kTabSets] = {};
+    int tab_next = 0;
+    const int64_t *inflight_dn = nullptr;      // cfg.async_flush: the ring slot holding the count at the in-flight pass's ev_pairs
+                                               // (nullptr: inflight_N is exact)
     double *d_pos_cost = nullptr, *d_sig_cost = nullptr, *d_digest = nullptr;
     double *h_small = nullptr;   // pinned 32 doubles
     // sharded correction: exchange slabs (own allocations, or caller-provided device buffers)
@@ -238,6 +257,11 @@ hipError_t dalloc(ekf_handle *h, Tp **p, size_t count) {
 }
 
 inline int64_t n_mm(const ekf_handle *h) { return 2 * h->N; }
+// cfg.device_assoc == 4: rows queued whose records have not been settled yet (each may have appended one landmark), and the upper
+// bound of N they leave; both exact (0, N) on every other handle
+inline bool decided_mode(const ekf_handle *h) { return h->cfg.mode == EKF_MODE_UC && h->cfg.device_assoc == 4; }
+inline int64_t unsettled(const ekf_handle *h) { return decided_mode(h) ? (int64_t)(h->lrec_head - h->lrec_tail) : 0; }
+inline int64_t n_hi(const ekf_handle *h) { return h->N + unsettled(h); }
 
 // Pair slots must read as zero beyond the active columns (the pass kernels read whole tile-wide slices of K and G): whenever the
 // map shrinks or the state is replaced, every ring is cleared -- the F64 pairs AND their float copies (cfg.pass_arith = EKF_ARITH_F32).
@@ -259,7 +283,7 @@ int32_t use_device(ekf_handle *h) {
 // behind the previous upload has passed.  The upload goes to the set no in-flight pass holds: the newest set itself when the pass
 // holds the other one (or none is in flight -- the main stream is ordered after every retired pass), else the other set.
 int32_t refresh_work(ekf_handle *h) {
-    const int64_t nt = ekf_tiles_for(n_mm(h), h->T);
+    const int64_t nt = ekf_tiles_for(2 * n_hi(h), h->T);          // (tiles beyond the device's count only ever see zero pairs)
     if (nt == h->ws[h->ws_cur].rows) return EKF_OK;
     const int32_t to = h->ws_pass == h->ws_cur ? h->ws_cur ^ 1 : h->ws_cur;
     ekf_handle::WorkSet &ws = h->ws[to];
@@ -383,7 +407,13 @@ int32_t retire_inflight(ekf_handle *h) {
         if (!h->ev_rows) HIPCHK(h, hipEventCreateWithFlags(&h->ev_rows, hipEventDisableTiming));
         HIPCHK(h, hipEventRecord(h->ev_rows, h->stream));
         HIPCHK(h, hipStreamWaitEvent(h->flush_stream, h->ev_rows, 0));
-        HIPCHK(h, launch_copy_rows(h->st.tm, h->tilebuf[h->base], h->tilebuf[h->base ^ 1], 2 * h->inflight_N, 2 * h->N, h->storage, h->flush_stream));
+        if (decided_mode(h)) {
+            // cfg.device_assoc == 4: from the count at the pass's ev_pairs to the count now, both the device's unless the host knows them
+            const int64_t *hi = unsettled(h) > 0 ? h->d_nring + h->nrow % ekf_handle::kNRing : nullptr;
+            HIPCHK(h, launch_copy_rows_dev(h->st.tm, h->tilebuf[h->base], h->tilebuf[h->base ^ 1], 2 * h->inflight_N, 2 * n_hi(h), h->inflight_dn,
+                                           hi, h->storage, h->flush_stream));
+        } else
+            HIPCHK(h, launch_copy_rows(h->st.tm, h->tilebuf[h->base], h->tilebuf[h->base ^ 1], 2 * h->inflight_N, 2 * h->N, h->storage, h->flush_stream));
         HIPCHK(h, hipEventRecord(h->ev_flushed, h->flush_stream));
         h->appended_inflight = false;
     }
@@ -407,7 +437,7 @@ int32_t retire_inflight(ekf_handle *h) {
 void next_pass_direction(ekf_handle *h) {
     const int force = h->cfg.pass_direction == 1 ? 0 : h->cfg.pass_direction == 2 ? 1 : -1;
     constexpr int64_t kCacheBytes = 256ll << 20;
-    const int64_t nt = ekf_tiles_for(n_mm(h), h->T);
+    const int64_t nt = ekf_tiles_for(2 * n_hi(h), h->T);
     const int64_t store = nt * (nt + 1) / 2 / std::max(1, h->cfg.world) * (int64_t)h->T * h->T * (h->storage == EKF_STORE_F64 ? 8 : 4);
     const bool alternate = force >= 0 ? force != 0 : store > kCacheBytes;
     h->st.tm.reverse = alternate ? (h->st.tm.reverse ^ 1) : 0;
@@ -556,6 +586,7 @@ int32_t batch_complete(ekf_handle *h) {
     h->inflight = true;
     h->ws_pass = h->ws_cur;                       // refresh_work leaves this set alone until the pass retires
     h->inflight_N = h->N;
+    h->inflight_dn = unsettled(h) > 0 ? h->d_nring + h->nrow % ekf_handle::kNRing : nullptr;
     h->appended_inflight = false;
     return EKF_OK;
 }
@@ -576,6 +607,7 @@ inline PartView read_part(const volatile AssocHostPartial *e) {
 // Device-resident measure loop: compare what the device decided (records in mapped memory) with what the host predicted when it
 // queued the launches.  block == false: only the records that have landed; block == true: all of them (the stream is synchronised
 // if the newest has not landed within the polling bound).
+void note_append(ekf_handle *h, double signature);
 int32_t verify_loop(ekf_handle *h, bool block) {
     if (h->lrec_tail == h->lrec_head) return EKF_OK;
     if (block) {
@@ -596,6 +628,15 @@ int32_t verify_loop(ekf_handle *h, bool block) {
             rc = fail(h, EKF_ERR_STATE, "measure: a decision record of the device-resident loop is missing");
             continue;
         }
+        if (decided_mode(h)) {
+            // cfg.device_assoc == 4: the record is the decision the device took AND carried out
+            if (v.index == -1) note_append(h, (double)(h->N + 1));     // EKF_SLAM_UC.m:122: append(.., idx) with idx = N + 1
+            else if (v.index == -4) h->lookup_fail_hits = h->N;          // (the row's key is N + 1; measure_decided reports it)
+            else if (v.index == -2)
+                rc = fail(h, EKF_ERR_STATE, "measure: the device-decided loop found stale winner entries; nothing was applied for that "
+                          "observation and the state is no longer the reference's");
+            continue;
+        }
         const bool same = sp.is_new ? v.index == -1 : (int64_t)v.index == sp.idx;
         if (!same) {
             char buf[200];
@@ -613,7 +654,7 @@ int32_t materialize_predict(ekf_handle *h) {
     if (!h->have_pp) return EKF_OK;
     h->have_pp = false;
     PredictArgs a = h->pp;
-    a.n_mm = n_mm(h); a.cur = h->cur;
+    a.n_mm = 2 * n_hi(h); a.cur = h->cur;         // (cfg.device_assoc == 4: columns beyond the device's count are never read)
     {
         TimedLaunch tl(h, EKF_KERNEL_PREDICT);
         HIPCHK(h, launch_predict(h->st, a, h->storage, h->stream));
@@ -659,6 +700,12 @@ int32_t do_append(ekf_handle *h, const double u[2], const double R[4], const dou
         HIPCHK(h, launch_append(h->st, a, h->storage, h->stream, dl, fuse));
         if (fuse) { h->have_pp = false; h->cur ^= 1; }
     }
+    note_append(h, signature);
+    return EKF_OK;
+}
+
+// the host's side of an append: the mirror of s, N, what the map's growth invalidates
+void note_append(ekf_handle *h, double signature) {
     if ((int64_t)h->s_host.size() > h->N) { h->s_host.resize((size_t)h->N); h->s_sorted_ok = false; }
     h->s_host.push_back(signature);
     if (h->s_sorted_ok && signature == signature)         // the index learns of it through its unsorted tail; NaN never matches anything
@@ -667,7 +714,11 @@ int32_t do_append(ekf_handle *h, const double u[2], const double R[4], const dou
     h->pf_valid = false;
     h->nx_valid = false;
     h->pn_idx.clear();         // (an announced prefetch spoke of the map before it grew)
-    return EKF_OK;
+}
+
+// cfg.device_assoc == 4: every row queued so far settled (N exact), for the entry points that read N or the state
+int32_t settle(ekf_handle *h) {
+    return unsettled(h) > 0 ? verify_loop(h, /*block*/ true) : EKF_OK;
 }
 
 // the buffer the PENDING exchange's contribution sits in (what a caller-run all-gather must send)
@@ -1100,6 +1151,159 @@ int32_t lookup_loc(ekf_handle *h, const double *lm_index, const double *lm_loc, 
     return EKF_OK;
 }
 
+// lookup_loc's rule for the E keys kbase+1 .. kbase+E at once (one pass over the list): out[3q .. 3q+2] = loc of key kbase+1+q and
+// the number of entries that carry it (the append branch applies an append only when that is 1); false if any key is not matched
+// exactly once
+bool resolve_keys(const double *lm_index, const double *lm_loc, int64_t L, int64_t kbase, int64_t E, double *out) {
+    for (int64_t q = 0; q < E; ++q) { out[3 * q] = 0.0; out[3 * q + 1] = 0.0; out[3 * q + 2] = 0.0; }
+    for (int64_t i = 0; i < L; ++i) {
+        const double v = lm_index[i];
+        if (!(v >= (double)(kbase + 1) && v <= (double)(kbase + E))) continue;
+        const int64_t q = (int64_t)v - kbase - 1;
+        if ((double)(kbase + 1 + q) != v) continue;                     // not an integer key
+        if ((out[3 * q + 2] += 1.0) == 1.0) { out[3 * q] = lm_loc[i]; out[3 * q + 1] = lm_loc[L + i]; }
+    }
+    bool all = true;
+    for (int64_t q = 0; q < E; ++q) all = all && out[3 * q + 2] == 1.0;
+    return all;
+}
+
+// cfg.device_assoc == 4, the device-decided branch: the rows [first, m) of a scan, queued without a single wait.  Per row ONE launch,
+// k_gather<.., kDecide>: it takes the decision the previous launch's epilogue (or, for the scan's first row, k_associate<.., kDevN>, which
+// also carries out a recorded predict) left on the device, carries it out -- correction, append, or nothing for stale winners -- and
+// evaluates the next row's association on the state it leaves.  Its record comes back through the ring of ekf_handle::h_lrec and is
+// settled later (verify_loop).  The caller has checked that capacity and the landmark list hold for every row (per-scan fallbacks).
+int32_t measure_decided_rows(ekf_handle *h, const double *obs, int64_t m, int64_t first, const double u[2], int tab_set, int64_t kbase) {
+    struct { bool have; int set; int32_t seq, nblk; } nxt = { false, 0, 0, 0 };
+    for (int64_t ii = first; ii < m; ++ii) {
+        const double z[3] = { obs[ii], obs[m + ii], obs[2 * m + ii] };
+        const double R[4] = { z[0] * h->cfg.Rc[0], 0.0, 0.0, z[1] * h->cfg.Rc[1] };   // EKF_SLAM_UC.m:110
+        if (!nxt.have) {                                               // EKF_SLAM_UC.m:119 for the scan's first row, a launch of its own
+            nxt.set = h->loop_set ^ 1; nxt.seq = next_assoc_seq(h);
+            AssocArgs a = {};
+            a.z0 = z[0]; a.z1 = z[1]; a.z2 = z[2];
+            colmajor2(R, a.R00, a.R01, a.R10, a.R11);
+            a.s_cost = h->cfg.s_cost; a.s_thresh = h->cfg.s_thresh; a.w_pos = h->cfg.w_pos;
+            a.N = n_hi(h); a.cur = h->cur; a.npend = h->npend; a.pstart = h->pstart; a.own_only = 0;
+            a.dN = unsettled(h) > 0 ? h->d_nring + h->nrow % ekf_handle::kNRing : nullptr;
+            nxt.nblk = assoc_blocks(a.N);
+            {
+                TimedLaunch tl(h, EKF_KERNEL_ASSOCIATE);
+                HIPCHK(h, launch_associate_devn(h->st, a, h->d_lparts + (int64_t)nxt.set * h->lparts_stride, nxt.seq, h->storage, h->stream,
+                                                h->have_pp ? &h->pp : nullptr));
+            }
+            if (h->have_pp) { h->have_pp = false; h->cur ^= 1; }      // the launch wrote the predicted state to the other buffer
+            h->loop_set = nxt.set;
+        }
+        if (h->lrec_head - h->lrec_tail >= (uint64_t)ekf_handle::kLoopRing) { const int32_t rc = verify_loop(h, /*block*/ true); if (rc) return rc; }
+        int32_t rc = refresh_work(h);
+        if (rc) return rc;
+        const int64_t nh = n_hi(h);                                    // before this row
+        DevLoopArgs dl = {};
+        dl.parts_in = h->d_lparts + (int64_t)nxt.set * h->lparts_stride; dl.nblk_in = nxt.nblk; dl.seq_in = nxt.seq;
+        dl.rec = h->h_lrec_dev + h->lrec_head % ekf_handle::kLoopRing;
+        dl.seq_rec = next_assoc_seq(h);
+        dl.n_known = unsettled(h) > 0 ? -1 : h->N;
+        dl.dn_in = h->d_nring + h->nrow % ekf_handle::kNRing;
+        dl.dn_out = h->d_nring + (h->nrow + 1) % ekf_handle::kNRing;
+        dl.loc = h->h_loctab_dev + (int64_t)tab_set * ekf_handle::kTabCap * 3;
+        dl.abort = h->d_abort; dl.scan_id = h->scan_id;
+        dl.loc_base = kbase;
+        dl.u0 = u[0]; dl.u1 = u[1];
+        const int set_in = nxt.set;
+        nxt.have = false;
+        if (ii + 1 < m) {                                              // the next row's association rides in this launch
+            dl.parts_out = h->d_lparts + (int64_t)(set_in ^ 1) * h->lparts_stride;
+            dl.seq_out = next_assoc_seq(h);
+            dl.z0 = obs[ii + 1]; dl.z1 = obs[m + ii + 1]; dl.z2 = obs[2 * m + ii + 1];
+            dl.R00 = dl.z0 * h->cfg.Rc[0]; dl.R01 = 0.0; dl.R10 = 0.0; dl.R11 = dl.z1 * h->cfg.Rc[1];
+            dl.s_cost = h->cfg.s_cost; dl.s_thresh = h->cfg.s_thresh; dl.w_pos = h->cfg.w_pos;
+            nxt.have = true; nxt.set = set_in ^ 1; nxt.seq = dl.seq_out; nxt.nblk = (int32_t)gather_workgroups(h->st, 2 * (nh + 1));
+        }
+        CorrectArgs a;
+        fill_correct_args(h, a, z, R, 0);
+        a.n_mm = 2 * (nh + 1);                                         // the bound after this row: sizes the grid only
+        if (h->inflight) h->appended_inflight = true;                  // (the row may append beside the pass)
+        {
+            TimedLaunch tl(h, EKF_KERNEL_GATHER);
+            HIPCHK(h, launch_gather_decided(h->st, a, dl, h->storage, h->stream));
+        }
+        if (nxt.have) h->loop_set = nxt.set;
+        h->lspec.push_back({ dl.seq_rec, 0, -1 });
+        ++h->lrec_head;
+        ++h->nrow;
+        rc = finish_step(h);                                           // every row takes a pair slot: npend stays exact
+        if (rc) return rc;
+    }
+    return EKF_OK;
+}
+
+// cfg.device_assoc == 4: the per-scan checks that keep the error semantics of the waited path exact, then the decided rows.  *waited:
+// the scan (from row *first on) must take the waited path instead (N is exact then).
+int32_t measure_decided(ekf_handle *h, const double *obs, int64_t m, const double u[2], const double *lm_index, const double *lm_loc,
+                        int64_t L, bool *waited, int64_t *first) {
+    *waited = false; *first = 0;
+    int32_t rc = verify_loop(h, /*block*/ false);                      // what earlier scans' launches have reported by now
+    if (rc) return rc;
+    if (h->N == 0 && unsettled(h) > 0) { rc = settle(h); if (rc) return rc; }      // the empty-map rule needs an exact N
+    if (h->N == 0) {
+        // EKF_SLAM_UC.m:110-111: the first row of an empty map appends under the first non-zero landmark index, signature 1
+        const double z0 = obs[0], z1 = obs[m];
+        const double R[4] = { z0 * h->cfg.Rc[0], 0.0, 0.0, z1 * h->cfg.Rc[1] };
+        double loc[2];
+        rc = lookup_loc(h, lm_index, lm_loc, L, true, 0.0, loc);
+        if (rc) return rc;
+        rc = do_append(h, u, R, loc, 1.0);
+        if (rc) return rc;
+        *first = 1;
+        if (m == 1) return EKF_OK;
+    }
+    const int64_t mr = m - *first;
+    if (n_hi(h) + mr > h->cap) {                                       // capacity: a row could append beyond it
+        rc = settle(h); if (rc) return rc;
+        if (h->N + mr > h->cap) { *waited = true; return EKF_OK; }
+    }
+    if (n_hi(h) + mr - h->N > ekf_handle::kTabCap) {
+        rc = settle(h); if (rc) return rc;
+        if (mr > ekf_handle::kTabCap) { *waited = true; return EKF_OK; }
+    }
+    const int set = h->tab_next;
+    if (h->tab_used[set] && h->lrec_tail <= h->tab_until[set]) {
+        rc = settle(h); if (rc) return rc;
+        if (h->lrec_tail <= h->tab_until[set]) HIPCHK(h, hipStreamSynchronize(h->stream));   // no later launch: wait for the scan's kernels
+    }
+    h->tab_used[set] = false;
+    double *tab = h->h_loctab + (int64_t)set * ekf_handle::kTabCap * 3;
+    // every key a row could append under: N + 1 .. n_hi + the scan's rows (lookup_loc's rule, EKF_SLAM_UC.m:122).  A key that does
+    // not resolve is an error only for a row that appends under it: the rows are queued all the same -- such a row applies nothing and
+    // stops the scan on the device -- and the scan is settled before ekf_measure returns, which then reports that row's error as the
+    // waited loop does (one wait per scan instead of one per row).
+    bool all_keys = resolve_keys(lm_index, lm_loc, L, h->N, n_hi(h) + mr - h->N, tab);
+    if (!all_keys && unsettled(h) > 0) {
+        rc = settle(h); if (rc) return rc;
+        all_keys = resolve_keys(lm_index, lm_loc, L, h->N, mr, tab);
+    }
+    const int64_t kbase = h->N;
+    h->tab_next = (set + 1) % ekf_handle::kTabSets;
+    h->scan_id = h->scan_id == INT32_MAX ? 1 : h->scan_id + 1;
+    h->lookup_fail_hits = -1;
+    rc = measure_decided_rows(h, obs, m, *first, u, set, kbase);
+    h->tab_used[set] = true;
+    h->tab_until[set] = h->lrec_head;
+    if (rc || all_keys) return rc;
+    rc = settle(h);
+    if (rc) return rc;
+    if (h->lookup_fail_hits >= 0) {
+        const int64_t q = h->lookup_fail_hits - kbase;
+        h->lookup_fail_hits = -1;
+        char buf[160];
+        snprintf(buf, sizeof buf, "measure: landmark lookup matched %lld entries (the reference's append() call is "
+                 "only well-formed for exactly one)", (long long)tab[3 * q + 2]);
+        return fail(h, EKF_ERR_LOOKUP, buf);
+    }
+    return EKF_OK;
+}
+
 }  // namespace
 
 // =====================================================================================================
@@ -1154,6 +1358,8 @@ int32_t ekf_create(const ekf_config *cfg, ekf_handle **out) {
     if (cfg->storage != EKF_STORE_F64 && cfg->storage != EKF_STORE_F32) return EKF_ERR_INVALID_ARG;
     if (cfg->mode != EKF_MODE_KNOWN && cfg->mode != EKF_MODE_UC) return EKF_ERR_INVALID_ARG;
     if (cfg->batch < 0 || cfg->batch > 64) return EKF_ERR_INVALID_ARG;
+    // the device-decided branch runs unsharded only (its sharded form is not built)
+    if (cfg->mode == EKF_MODE_UC && cfg->device_assoc == 4 && (world > 1 || cfg->force_sharded)) return EKF_ERR_INVALID_ARG;
     if (cfg->pass_arith != EKF_ARITH_F64 &&
         !((cfg->pass_arith == EKF_ARITH_F32 || cfg->pass_arith == EKF_ARITH_SPLIT3) && cfg->storage == EKF_STORE_F32 && T == 256))
         return EKF_ERR_INVALID_ARG;                   // the f32-arithmetic passes exist for float tiles of edge 256 only
@@ -1331,6 +1537,17 @@ int32_t ekf_create(const ekf_config *cfg, ekf_handle **out) {
         h->h_lrec_dev = (AssocHostPartial *)dp;
     }
     HIPCHK(h, hipHostMalloc((void **)&h->h_small, 32 * sizeof(double), hipHostMallocDefault));
+    if (cfg->mode == EKF_MODE_UC && cfg->device_assoc == 4) {
+        // the device-decided branch: the ring of landmark counts, the landmark-list sets the append branch reads
+        HIPCHK(h, dalloc(h, &h->d_nring, ekf_handle::kNRing));
+        HIPCHK(h, dalloc(h, &h->d_abort, 1));
+        const size_t bytes = 3 * sizeof(double) * ekf_handle::kTabSets * ekf_handle::kTabCap;
+        HIPCHK(h, hipHostMalloc((void **)&h->h_loctab, bytes, hipHostMallocMapped));
+        memset(h->h_loctab, 0, bytes);
+        void *dp = nullptr;
+        HIPCHK(h, hipHostGetDevicePointer(&dp, h->h_loctab, 0));
+        h->h_loctab_dev = (double *)dp;
+    }
 
     // x = [0 0 0]; P = 0.1*eye(3)   (EKF_SLAM.m:28-31, EKF_SLAM_UC.m:29-32)
     const double prr0[9] = { 0.1, 0, 0, 0, 0.1, 0, 0, 0, 0.1 };
@@ -1360,6 +1577,7 @@ int32_t ekf_destroy(ekf_handle *h) {
     if (h->h_parts) hipHostFree(h->h_parts);
     if (h->h_lrec) hipHostFree(h->h_lrec);
     if (h->h_small) hipHostFree(h->h_small);
+    if (h->h_loctab) hipHostFree(h->h_loctab);
     if (h->wl_stage) { hipHostFree(h->wl_stage); hipEventDestroy(h->ev_wl); }
     if (h->own_stream) hipStreamDestroy(h->own_stream);
     delete h;
@@ -1390,6 +1608,7 @@ int32_t ekf_flush(ekf_handle *h) {
     if (!h) return EKF_ERR_INVALID_ARG;
     REQUIRE(h, !h->pending, EKF_ERR_STATE, "flush: a sharded correction is between begin and finish");
     int32_t rc = use_device(h);
+    if (!rc) rc = settle(h);
     return rc ? rc : flush_pending(h);
 }
 
@@ -1431,12 +1650,14 @@ int32_t ekf_motion_model(const double *x, int64_t n, const double u[2], double *
 int32_t ekf_append(ekf_handle *h, const double u[2], const double R[4], const double pos[2], double signature) {
     if (!h || !u || !R || !pos) return fail(h, EKF_ERR_INVALID_ARG, "append: null argument");
     int32_t rc = use_device(h);
+    if (!rc) rc = settle(h);
     return rc ? rc : do_append(h, u, R, pos, signature);
 }
 
 int32_t ekf_correct(ekf_handle *h, const double z[2], const double R[4], int64_t idx) {
     if (!h || !z || !R) return fail(h, EKF_ERR_INVALID_ARG, "correct: null argument");
     int32_t rc = use_device(h);
+    if (!rc) rc = settle(h);
     return rc ? rc : do_correct(h, z, R, idx);
 }
 
@@ -1444,6 +1665,7 @@ int32_t ekf_associate(ekf_handle *h, const double z[3], const double R[4], int32
                       double *pos_cost, double *sig_cost) {
     if (!h || !z || !R || !is_new || !idx) return fail(h, EKF_ERR_INVALID_ARG, "associate: null argument");
     int32_t rc = use_device(h);
+    if (!rc) rc = settle(h);
     return rc ? rc : do_associate(h, z, R, is_new, idx, pos_cost, sig_cost);
 }
 
@@ -1461,6 +1683,13 @@ int32_t ekf_measure(ekf_handle *h, const double *obs, int64_t m, const double u[
             "measure: a sharded handle needs the library-owned communicator (ekf_comm_init) or an exchange hook "
             "(ekf_exchange_set_hook); with a host-run exchange call ekf_append / ekf_correct_begin / ekf_correct_finish per observation");
     const bool dev_loop = h->cfg.mode == EKF_MODE_UC && h->cfg.device_assoc == 3 && h->cfg.w_pos == 0.0;
+    int64_t first = 0;
+    if (decided_mode(h) && m > 0) {
+        // cfg.device_assoc == 4: the device-decided branch, any w_pos -- unless a per-scan check sends the scan down the waited path
+        bool waited = false;
+        rc = measure_decided(h, obs, m, u, lm_index, lm_loc, L, &waited, &first);
+        if (rc || !waited) return rc;
+    }
     if (h->sharded && (h->comm || h->xhook) && h->batch > 1 && m > 1 && h->N > 0 && !dev_loop) {      // (the device loop names its landmarks on the device)
         // the scan's corrections are known before the loop runs: fetch their base row-panels in ONE exchange
         // (rows that turn out to append drop the prefetch again; the per-row exchange then takes over)
@@ -1494,7 +1723,7 @@ int32_t ekf_measure(ekf_handle *h, const double *obs, int64_t m, const double u[
         rc = verify_loop(h, /*block*/ false);                              // what earlier scans' launches have reported by now
         if (rc) return rc;
     }
-    for (int64_t ii = 0; ii < m; ++ii) {                                   // EKF_SLAM.m:107
+    for (int64_t ii = first; ii < m; ++ii) {                               // EKF_SLAM.m:107
         const double z[3] = { obs[ii], obs[m + ii], obs[2 * m + ii] };
         const double R[4] = { z[0] * h->cfg.Rc[0], 0.0, 0.0, z[1] * h->cfg.Rc[1] };   // :108
         double loc[2];
@@ -1769,6 +1998,7 @@ int32_t ekf_shard_panel_source(int32_t world, int64_t tile_row_j, int64_t chunk,
 
 int32_t ekf_num_landmarks(ekf_handle *h, int64_t *N) {
     if (!h || !N) return fail(h, EKF_ERR_INVALID_ARG, "num_landmarks: null argument");
+    if (unsettled(h) > 0) { const int32_t rc = settle(h); if (rc) return rc; }
     *N = h->N;
     return EKF_OK;
 }
@@ -2133,6 +2363,7 @@ const char *ekf_downdate_kernel_name(const ekf_handle *h, int32_t *pairs) {
 
 int32_t ekf_downdate_algorithmic_bytes(ekf_handle *h, int64_t *bytes) {
     if (!h || !bytes) return fail(h, EKF_ERR_INVALID_ARG, "downdate_algorithmic_bytes: null argument");
+    if (unsettled(h) > 0) { const int32_t rc = settle(h); if (rc) return rc; }
     const int64_t n = 3 + n_mm(h);
     *bytes = (int64_t)elt_size(h) * n * (n + 1);
     return EKF_OK;

@@ -8,7 +8,8 @@
 // through the same per-entry functions as k_predict -- AND written to the other state buffer (a.cur ^ 1): this launch is
 // k_predict and the association of the scan's first row in one (lane k owns landmark k's two strip columns either way), so
 // the correction that follows neither waits for a k_predict launch nor folds the predict into its own latency chain.
-template <typename TS, bool kPredict>
+// kDevN (cfg.device_assoc == 4): the landmark count is read from the device (a.dN, unless nullptr); a.N only sized the grid.
+template <typename TS, bool kPredict, bool kDevN = false>
 __global__ __launch_bounds__(kAssocBlock) void k_associate(DevState st, AssocArgs a, double *__restrict__ pos_cost,
                                                            double *__restrict__ sig_cost,
                                                            AssocDecision *partial, int *ticket, AssocDecision *__restrict__ decision,
@@ -20,6 +21,7 @@ __global__ __launch_bounds__(kAssocBlock) void k_associate(DevState st, AssocArg
     const int tid = threadIdx.x;
     const int cur = a.cur;
     const int64_t k = (int64_t)blockIdx.x * kAssocBlock + tid;
+    const int64_t N = (kDevN && a.dN) ? *a.dN : a.N;
     double ll = INFINITY;
     int64_t ix = INT64_MAX;
     if (kPredict) {
@@ -38,7 +40,7 @@ __global__ __launch_bounds__(kAssocBlock) void k_associate(DevState st, AssocArg
         }
         __syncthreads();
     }
-    if (k < a.N) {
+    if (k < N) {
         const double *__restrict__ x = st.x[cur];
         const double *__restrict__ strip = st.strip[cur];
         const int64_t j = 2 * k;
@@ -128,7 +130,7 @@ __global__ __launch_bounds__(kAssocBlock) void k_associate(DevState st, AssocArg
         const bool found = ix != INT64_MAX;           // something passed the threshold (min_ll starts at Inf, :43)
         AssocDecision d;
         d.is_new = found ? 0 : 1;
-        d.index = found ? ix : a.N;                   // default index = numOfLandmarks + 1 (:40), 0-based here
+        d.index = found ? ix : N;                     // default index = numOfLandmarks + 1 (:40), 0-based here
         d.min_ll = ll;
         d.seq = seq;
         *decision = d;

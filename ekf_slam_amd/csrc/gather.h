@@ -34,16 +34,138 @@ __device__ __forceinline__ void wave_lds_sync() { asm volatile("s_waitcnt lgkmcn
 constexpr int kFuseMaxRows = 48;                     // landmark-block rows (24 landmarks) up to which the fused form is used (beyond: slower than two launches)
 constexpr int kFuseElems = kFuseMaxRows * kFuseMaxRows / 256;     // elements of the block per column lane, all in flight together
 
+// kDecide (cfg.device_assoc == 4, with kDev): the device takes the BRANCH as well.  The landmark count is the device's (DevLoopArgs::dn_in,
+// a ring slot; the grid was sized from the host's upper bound); winners that name a landmark -> the correction below, over that
+// extent; nothing below the threshold -> the append of EKF_SLAM_UC.m:121-123 (gather_decided_other); stale winner entries ->
+// nothing is applied.  Every branch leaves the state in the other buffers, writes this launch's pair slot (zeros when nothing was
+// corrected: an exact no-op for every pass and patch), stores the count it leaves to dn_out and evaluates the next observation's
+// association on the state it leaves.
+template <typename TS>
+__device__ __forceinline__ void gather_decided_other(const DevState &st, const CorrectArgs &a, const DevLoopArgs &dl, int64_t Nd,
+                                                     bool append) {
+    __shared__ double oa_ll[kGatherCols / 64];
+    __shared__ int oa_ix[kGatherCols / 64];
+    const int tid = threadIdx.x;
+    if (tid >= kGatherCols) return;                       // the helper wavefronts have no part here (a barrier counts live wavefronts)
+    const int cur = a.cur;
+    const double *__restrict__ x = st.x[cur];
+    const double *__restrict__ strip = st.strip[cur];
+    const double *__restrict__ prr = st.prr[cur];
+    double *__restrict__ x_nxt = st.x[cur ^ 1];
+    double *__restrict__ strip_nxt = st.strip[cur ^ 1];
+    double *__restrict__ prr_nxt = st.prr[cur ^ 1];
+    const double *__restrict__ dg = st.diag[st.dcur];
+    double *__restrict__ dgn = st.diag[st.dcur ^ 1];
+    TS *__restrict__ tiles = (TS *)st.tiles;
+    const int64_t ldm = st.ldm;
+    const int64_t n_old = 2 * Nd, n_new = append ? n_old + 2 : n_old;
+    const int64_t c = (int64_t)blockIdx.x * kGatherCols + tid;
+    const bool live = c < n_new;
+    double pose[3], pr[9];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) pose[i] = x[i];
+#pragma unroll
+    for (int i = 0; i < 9; ++i) pr[i] = prr[i];
+    double jxr[2][3];
+    append_jxr(dl.u0, pose[2], jxr);                      // EKF_SLAM.m:84-85 (no predict pending: the scan's first launch carried it out)
+    double xn = 0.0, t0 = 0.0, t1 = 0.0, t2 = 0.0, dgc = 0.0, dgl = 0.0;
+    if (c < n_old) {
+        t0 = strip[c]; t1 = strip[ldm + c]; t2 = strip[2 * ldm + c];
+        xn = x[3 + c];
+        const double *__restrict__ d = dg + 3 * (c >> 1);
+        if (c & 1) { dgl = d[1]; dgc = d[2]; } else dgc = d[0];
+        if (append)
+            for (int i = 0; i < 2; ++i)                   // F: P(new, lm) = jxr * P(lm, 1:3)'   (EKF_SLAM.m:95)
+                if (st.tm.mine((n_old + i) >> st.tm.shift, c >> st.tm.shift))
+                    pmm_low_store<TS>(tiles, st.tm, n_old + i, c, append_row_entry(jxr, i, t0, t1, t2));
+    } else if (live) {
+        // the new landmark's two columns: position from the landmark list (EKF_SLAM.m:79), C and I (EKF_SLAM.m:87-92)
+        const int b = (int)(c - n_old);
+        const volatile double *loc = dl.loc + 3 * (Nd - dl.loc_base);
+        double cblk[3], iblk[3][2];
+        append_blocks(jxr, pr, dl.u0, dl.u1, a.R00, a.R01, a.R10, a.R11, cblk, iblk);
+        xn = loc[b];
+        t0 = iblk[0][b]; t1 = iblk[1][b]; t2 = iblk[2][b];
+        const bool own = st.tm.mine(n_old >> st.tm.shift, n_old >> st.tm.shift);
+        if (b == 0) {
+            dgc = cblk[0];
+            if (own) pmm_low_store<TS>(tiles, st.tm, n_old, n_old, cblk[0]);
+            st.s[Nd] = (double)(Nd + 1);                  // EKF_SLAM.m:70 (signature = the new landmark's 1-based index, EKF_SLAM_UC.m:122)
+        } else {
+            dgl = cblk[1]; dgc = cblk[2];
+            if (own) { pmm_low_store<TS>(tiles, st.tm, n_old + 1, n_old, cblk[1]); pmm_low_store<TS>(tiles, st.tm, n_old + 1, n_old + 1, cblk[2]); }
+        }
+    }
+    if (live) {
+        x_nxt[3 + c] = xn;
+        strip_nxt[c] = t0; strip_nxt[ldm + c] = t1; strip_nxt[2 * ldm + c] = t2;
+        double *__restrict__ d = dgn + 3 * (c >> 1);
+        if (c & 1) { d[1] = dgl; d[2] = dgc; } else d[0] = dgc;
+    }
+    if (c < st.tm.padded(n_new)) {                        // this launch's pair slot: zeros over the whole live extent
+        const int64_t out_off = (int64_t)ring_slot(a.pstart, a.npend, st.pcap) * st.pair_stride;
+        reinterpret_cast<double2 *>(st.Gp + out_off)[c] = make_double2(0.0, 0.0);
+        reinterpret_cast<double2 *>(st.Kp + out_off)[c] = make_double2(0.0, 0.0);
+        if (st.Gp32) {
+            st.Gp32[out_off + c] = 0.0f; st.Gp32[out_off + ldm + c] = 0.0f;
+            st.Kp32[out_off + c] = -0.0f; st.Kp32[out_off + ldm + c] = -0.0f;
+        }
+    }
+    if (blockIdx.x == 0) {
+        if (tid < 9) prr_nxt[tid] = prr[tid];
+        if (tid < 3) x_nxt[tid] = x[tid];
+        if (tid == 0) *dl.dn_out = n_new >> 1;
+    }
+    if (dl.parts_out == nullptr) return;
+    // the NEXT observation's association (Correspondence.m:49-87) on the state this launch leaves: the per-entry functions of
+    // k_associate on the values just stored (landmark k = c / 2 scored by its even column lane)
+    const bool odd = (c & 1) != 0;
+    const double xn_o = lane_xor1(xn), t0_o = lane_xor1(t0), t1_o = lane_xor1(t1), t2_o = lane_xor1(t2),
+                 d10 = lane_xor1(dgl), d11 = lane_xor1(dgc);
+    double ll = INFINITY;
+    int64_t ix = INT64_MAX;
+    if (live && !odd) {
+        const int64_t k = c >> 1;
+        double q[24];
+#pragma unroll
+        for (int i = 0; i < 9; ++i) q[i] = pr[i];
+        q[9] = t0; q[10] = t0_o; q[11] = t1; q[12] = t1_o; q[13] = t2; q[14] = t2_o;
+        q[15] = dgc; q[16] = d10; q[17] = d10; q[18] = d11;
+        q[19] = pose[0]; q[20] = pose[1]; q[21] = pose[2];
+        q[22] = xn; q[23] = xn_o;
+        SmallSolve so;
+        solve_small(q, dl.z0, dl.z1, dl.R00, dl.R01, dl.R10, dl.R11, so);
+        const double n0 = so.nu[0], n1 = so.nu[1];
+        const double pc = (n0 * so.Phi[0] + n1 * so.Phi[2]) * n0 + (n0 * so.Phi[1] + n1 * so.Phi[3]) * n1;     // :69
+        const double sk = k == Nd ? (double)(Nd + 1) : st.s[k];
+        const double d = dl.z2 - sk;
+        const double sc = d * (1.0 / dl.s_cost) * d;                                                        // :71
+        const double like = (dl.w_pos != 0.0) ? (dl.w_pos * pc + sc) : sc;                                 // :74-75
+        if (like <= dl.s_thresh) { ll = like; ix = k; }                                                     // :78
+    }
+    wave_argmin_sparse(ll, ix);
+    if ((tid & 63) == 0) { oa_ll[tid >> 6] = ll; oa_ix[tid >> 6] = ix == INT64_MAX ? -1 : (int)ix; }
+    __syncthreads();
+    if (tid < 64) {
+        ll = tid < kGatherCols / 64 ? oa_ll[tid] : INFINITY;
+        ix = (tid < kGatherCols / 64 && oa_ix[tid] >= 0) ? (int64_t)oa_ix[tid] : INT64_MAX;
+        if (ix == INT64_MAX) ll = INFINITY;
+        wave_argmin_sparse(ll, ix);
+        if (tid == 0) store_partial(dl.parts_out + blockIdx.x, ll, ix == INT64_MAX ? -1 : (int)ix, dl.seq_out);
+    }
+}
+
 // kDev (device-resident measure loop): the corrected landmark is not a kernel argument but the arg-min over the
 // per-workgroup winners of this observation's association (dl.parts_in), reduced redundantly by every wavefront; and the NEXT
 // observation's association (Correspondence.m:49-87: per-landmark phi_k, Mahalanobis + signature cost, thresholded arg-min) is
 // evaluated in the epilogue by the column lanes, from the values this correction has just produced -- x', strip', Prr', the
 // landmark's own 2x2 block (its live F64 copy, to which the lanes have just applied this correction's pair) -- with the per-entry
 // functions k_associate uses: one launch per observation instead of two.
-template <typename TS, bool kSharded, bool kPredict, bool kFused = false, bool kDev = false>
+template <typename TS, bool kSharded, bool kPredict, bool kFused = false, bool kDev = false, bool kDecide = false>
 __global__ __launch_bounds__(kGatherBlock) void k_gather(DevState st, CorrectArgs a, PanelView pv, PredictArgs pa,
                                                          typename DevLoopParam<kDev>::type dl) {
     static_assert(!kDev || !kFused, "the device loop never drives the small-map fused form");
+    static_assert(!kDecide || (kDev && !kSharded && !kPredict), "the device-decided branch: unsharded, predict carried out before");
     __shared__ double pss[24];
     __shared__ SmallSolve sol;
     __shared__ PredictSmall ps;
@@ -75,6 +197,22 @@ __global__ __launch_bounds__(kGatherBlock) void k_gather(DevState st, CorrectArg
         int dix;
         reduce_partials_wave(dl.parts_in, dl.nblk_in, dl.seq_in, lane, dll, dix);
         dix = __builtin_amdgcn_readfirstlane(dix);
+        if constexpr (kDecide) {
+            const int64_t Nd = dl.n_known >= 0 ? dl.n_known : *dl.dn_in;        // the device's landmark count (a.n_mm: the host's bound)
+            a.n_mm = 2 * Nd;
+            const bool stopped = *(volatile int32_t *)dl.abort == dl.scan_id;   // an earlier row of this scan failed its lookup
+            if (stopped || !(dix >= 0 && (int64_t)dix < Nd)) {
+                int code = stopped ? -3 : dix;
+                if (code == -1 && *(const volatile double *)(dl.loc + 3 * (Nd - dl.loc_base) + 2) != 1.0) {
+                    code = -4;                                                    // the key of the append matched no entry or several
+                    if (blockIdx.x == 0 && tid == kGatherCols + 64) *(volatile int32_t *)dl.abort = dl.scan_id;
+                }
+                if (blockIdx.x == 0 && tid == kGatherCols + 128) store_partial(dl.rec, dll, code, dl.seq_rec);
+                gather_decided_other<TS>(st, a, dl, Nd, code == -1);
+                return;
+            }
+            if (blockIdx.x == 0 && tid == kGatherCols + 64) *dl.dn_out = Nd;
+        }
         if (dix >= 0 && 2 * (int64_t)dix < a.n_mm) j = 2 * (int64_t)dix;       // otherwise a.j: the launch stays inside the state
         if constexpr (kSharded) pv.Ij = j >> st.tm.shift;                       // (k_rowpanel<.., kDev> laid the panel out for this landmark)
         if (blockIdx.x == 0 && tid == kGatherCols + 128) store_partial(dl.rec, dll, dix, dl.seq_rec);   // BEARING lane 0: it has slack

@@ -87,6 +87,8 @@ struct AssocArgs {
     int32_t npend;
     int32_t pstart;
     int32_t own_only;         // sharded association with an exchange: nominate only landmarks whose diagonal block this shard holds
+    const int64_t *dN;        // k_associate<.., kDevN> (cfg.device_assoc == 4): the landmark count on the device (nullptr: N is exact);
+                              //   N is then the host's upper bound, which only sizes the grid
 };
 
 struct AssocDecision {        // written by the device, read back by the host
@@ -130,6 +132,20 @@ struct DevLoopArgs {
     double z0, z1, z2;                  // the next observation [range, bearing_deg, signature] and its R
     double R00, R01, R10, R11;
     double s_cost, s_thresh, w_pos;
+    // cfg.device_assoc == 4 (k_gather<.., kDecide>): the device also takes the branch.  The landmark count lives on the device, in a
+    // ring the host advances by one slot per launch: the launch reads *dn_in (n_known >= 0: the host knows it exactly, *dn_in is not
+    // read) and writes the count it leaves to *dn_out.  An append (winners: -1) reads the landmark-list entry of key N + 1
+    // (EKF_SLAM_UC.m:122) from loc + 3 (N - loc_base) (MAPPED host memory: x, y, number of entries that carry the key) and carries out
+    // append(u, R, loc, N + 1) -- unless the key matched no entry or several: then nothing is applied, the record says -4 and every
+    // later launch of the same scan (*abort == scan_id) applies nothing either (record -3), as the waited loop stops at that row.
+    const int64_t *dn_in;
+    int64_t *dn_out;
+    int64_t n_known;
+    const double *loc;
+    int64_t loc_base;
+    double u0, u1;
+    int32_t *abort;
+    int32_t scan_id;
 };
 
 constexpr int kAssocBlock = 256;       // 4 wavefronts = one per SIMD: the per-landmark solve is a dependent f64 chain (1024 measured slower: 16 wavefronts share one CU's f64 issue)
@@ -149,6 +165,12 @@ int gather_fuse_max_rows();
 hipError_t launch_gather_devloop(const DevState &st, const CorrectArgs &a, const PredictArgs *fused_predict, const DevLoopArgs &dl,
                                  int storage, hipStream_t s);
 int64_t gather_workgroups(const DevState &st, int64_t n_mm);
+// cfg.device_assoc == 4: the device-decided branch (k_gather<.., kDecide>).  The winners of dl.parts_in name a landmark -> the
+// correction of launch_gather_devloop; nothing below the threshold -> the append of that observation; stale winners -> nothing is
+// applied.  Either way the state is left in buffer a.cur ^ 1 (diagonal blocks: dcur ^ 1), the pair slot of ring position a.npend is
+// written (zeros when nothing was corrected) and the next observation's association is evaluated on the state the launch leaves.
+// a.n_mm: the host's upper bound of the landmark-block size AFTER this launch (sizes the grid only).
+hipError_t launch_gather_decided(const DevState &st, const CorrectArgs &a, const DevLoopArgs &dl, int storage, hipStream_t s);
 // sharded correction: (1) every shard copies the chunks of the landmark row-panel P(j:j+1,:) it owns into `send`
 // (slab layout: local chunk kl of T columns, interleaved pairs), (2) the slabs are all-gathered into `recv`
 // (world slabs of `slab` doubles), (3) the gather/solve kernel reads the panel from `recv` instead of the tiles.
@@ -210,6 +232,10 @@ int64_t build_strip_segments(const TileMap &tm, int64_t nt, std::vector<int4> &o
 hipError_t launch_associate(const DevState &st, const AssocArgs &a, double *pos_cost, double *sig_cost,
                             AssocDecision *partial, int *ticket, AssocDecision *decision, AssocHostPartial *host_partials, int seq,
                             double *cand, int storage, hipStream_t s, const PredictArgs *fused_predict = nullptr);
+// the same with the landmark count taken from a.dN when that is not nullptr (k_associate<.., kDevN>: workgroups beyond it store
+// "no winner"); the grid is sized from a.N, the host's upper bound
+hipError_t launch_associate_devn(const DevState &st, const AssocArgs &a, AssocHostPartial *host_partials, int seq, int storage,
+                                 hipStream_t s, const PredictArgs *fused_predict);
 // cand (nullptr or 4 device doubles): this shard's candidate {likelihood, index or -1, 0, 0} for the all-gather of a sharded
 // association; launch_assoc_merge takes the arg-min over the `world` gathered contributions of `count` doubles each (candidate,
 // then -- want_costs -- N position costs) and writes the decision like launch_associate does
@@ -218,6 +244,10 @@ hipError_t launch_assoc_merge(const DevState &st, const double *recv, int world,
 // dense (column-major, n x n, device) <-> tiled
 // cfg.async_flush: rows [r0, r1) of the landmark block (every local tile of the tile rows they lie in) copied from one tile store to the other
 hipError_t launch_copy_rows(const TileMap &tm, const void *src, void *dst, int64_t r0, int64_t r1, int storage, hipStream_t s);
+// the same with bounds known on the device only (cfg.device_assoc == 4): rows [2 * *n_lo, 2 * *n_hi) of the range [r0, r1) the host
+// can bound them by (a pointer that is nullptr leaves the host's bound as it is)
+hipError_t launch_copy_rows_dev(const TileMap &tm, const void *src, void *dst, int64_t r0, int64_t r1, const int64_t *n_lo,
+                                const int64_t *n_hi, int storage, hipStream_t s);
 hipError_t launch_unpack_dense(const DevState &st, int cur, int64_t n_mm, double *dense, int storage, hipStream_t s);
 hipError_t launch_pack_dense(const DevState &st, int cur, int64_t n_mm, const double *dense, int storage, hipStream_t s);
 hipError_t launch_get_block(const DevState &st, int cur, int64_t r0, int64_t c0, int64_t nr, int64_t nc,

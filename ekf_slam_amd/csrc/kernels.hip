@@ -124,6 +124,19 @@ hipError_t launch_gather_devloop(const DevState &st, const CorrectArgs &a, const
     return hipGetLastError();
 }
 
+hipError_t launch_gather_decided(const DevState &st, const CorrectArgs &a, const DevLoopArgs &dl, int storage, hipStream_t s) {
+    if (!dl.parts_in || !dl.rec || !dl.dn_out || !dl.loc || !dl.abort || dl.nblk_in < 1 || a.n_mm < 2 || (dl.n_known < 0 && !dl.dn_in))
+        return hipErrorInvalidValue;
+    const int64_t grid = gather_workgroups(st, a.n_mm);
+    PanelView pv;
+    pv.recv = nullptr; pv.slab = 0; pv.offset = 0; pv.Ij = 0; pv.patched = 0;
+    const PredictArgs pa = {};
+    EKF_STORAGE_DISPATCH(storage,
+        hipLaunchKernelGGL((k_gather<double, false, false, false, true, true>), dim3((unsigned)grid), dim3(kGatherBlock), 0, s, st, a, pv, pa, dl),
+        hipLaunchKernelGGL((k_gather<float, false, false, false, true, true>), dim3((unsigned)grid), dim3(kGatherBlock), 0, s, st, a, pv, pa, dl));
+    return hipGetLastError();
+}
+
 hipError_t launch_rowpanel(const DevState &st, int64_t j, int64_t n_mm, int pstart, int npend, double *send, int storage,
                            hipStream_t s) {
     const int64_t nloc = rowpanel_local_chunks(st.tm, j, n_mm);
@@ -497,6 +510,20 @@ hipError_t launch_associate(const DevState &st, const AssocArgs &a, double *pos_
     return hipGetLastError();
 }
 
+hipError_t launch_associate_devn(const DevState &st, const AssocArgs &a, AssocHostPartial *host_partials, int seq, int storage,
+                                 hipStream_t s, const PredictArgs *fused_predict) {
+    if (!host_partials) return hipErrorInvalidValue;
+    const int64_t grid = cdiv(a.N > 0 ? a.N : 1, kAssocBlock);
+    PredictArgs pa = {};
+    if (fused_predict) pa = *fused_predict;
+#define EKF_A(TS_, PRED_) hipLaunchKernelGGL((k_associate<TS_, PRED_, true>), dim3((unsigned)grid), dim3(kAssocBlock), 0, s, st, a, nullptr, \
+                                             nullptr, nullptr, nullptr, nullptr, host_partials, seq, nullptr, pa)
+    if (storage == 0) { if (fused_predict) EKF_A(double, true); else EKF_A(double, false); }
+    else              { if (fused_predict) EKF_A(float, true); else EKF_A(float, false); }
+#undef EKF_A
+    return hipGetLastError();
+}
+
 hipError_t launch_assoc_merge(const DevState &st, const double *recv, int world, int64_t count, int64_t N, bool want_costs,
                               double *pos_cost, AssocDecision *decision, AssocDecision *host_decision, int seq, hipStream_t s) {
     int64_t grid = want_costs ? cdiv(N > 0 ? N : 1, kBlock) : 1;
@@ -519,6 +546,24 @@ hipError_t launch_copy_rows(const TileMap &tm, const void *src, void *dst, int64
         EKF_STORAGE_DISPATCH(storage,
             hipLaunchKernelGGL(k_copy_tile_rows<double>, dim3((unsigned)grid), dim3(kBlock), 0, s, (const double *)src, (double *)dst, slot0, nslots, (int)lo, (int)(hi - lo), T),
             hipLaunchKernelGGL(k_copy_tile_rows<float>, dim3((unsigned)grid), dim3(kBlock), 0, s, (const float *)src, (float *)dst, slot0, nslots, (int)lo, (int)(hi - lo), T));
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_copy_rows_dev(const TileMap &tm, const void *src, void *dst, int64_t r0, int64_t r1, const int64_t *n_lo,
+                                const int64_t *n_hi, int storage, hipStream_t s) {
+    if (r1 <= r0) return hipSuccess;
+    const int T = tm.T;
+    if (T > kBlock * (storage == 0 ? 2 : 4)) return hipErrorInvalidValue;
+    for (int64_t I = r0 >> tm.shift; I <= (r1 - 1) >> tm.shift; ++I) {
+        const int64_t lo = std::max<int64_t>(r0, I * T) - I * T, hi = std::min<int64_t>(r1, (I + 1) * T) - I * T;
+        const int64_t slot0 = tm.row_base(I), nslots = tm.row_base(I + 1) - slot0;
+        if (nslots <= 0 || hi <= lo) continue;
+        const int lanes = T / (storage == 0 ? 2 : 4), per_wg = kBlock / lanes > 0 ? kBlock / lanes : 1;
+        const int64_t grid = cdiv(nslots * (hi - lo), per_wg);
+        EKF_STORAGE_DISPATCH(storage,
+            hipLaunchKernelGGL(k_copy_tile_rows_dev<double>, dim3((unsigned)grid), dim3(kBlock), 0, s, (const double *)src, (double *)dst, slot0, nslots, (int)lo, (int)(hi - lo), T, I * T, r0, r1, n_lo, n_hi),
+            hipLaunchKernelGGL(k_copy_tile_rows_dev<float>, dim3((unsigned)grid), dim3(kBlock), 0, s, (const float *)src, (float *)dst, slot0, nslots, (int)lo, (int)(hi - lo), T, I * T, r0, r1, n_lo, n_hi));
     }
     return hipGetLastError();
 }

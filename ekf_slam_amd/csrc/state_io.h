@@ -184,4 +184,25 @@ __global__ __launch_bounds__(kBlock) void k_copy_tile_rows(const TS *__restrict_
     *reinterpret_cast<v16_t *>(dst + off) = *reinterpret_cast<const v16_t *>(src + off);
 }
 
+// k_copy_tile_rows with bounds the device holds (cfg.device_assoc == 4): rows outside [2 * *n_lo, 2 * *n_hi) of the host's range [r0, r1)
+// are left alone (row0: the global row of local row 0 of the tile row)
+template <typename TS>
+__global__ __launch_bounds__(kBlock) void k_copy_tile_rows_dev(const TS *__restrict__ src, TS *__restrict__ dst, int64_t slot0, int64_t nslots,
+                                                             int lrow0, int nrows, int T, int64_t row0, int64_t r0, int64_t r1,
+                                                             const int64_t *n_lo, const int64_t *n_hi) {
+    constexpr int kE = 16 / (int)sizeof(TS);
+    const int lanes = T / kE;
+    const int per_wg = kBlock / lanes > 0 ? kBlock / lanes : 1;
+    const int sub = (int)threadIdx.x / lanes, piece = (int)threadIdx.x - sub * lanes;
+    const int64_t item = (int64_t)blockIdx.x * per_wg + sub;
+    if (sub >= per_wg || item >= nslots * nrows) return;
+    const int64_t slot = slot0 + item / nrows;
+    const int row = lrow0 + (int)(item % nrows);
+    const int64_t lo = n_lo ? 2 * *n_lo : r0, hi = n_hi ? 2 * *n_hi : r1;
+    if (row0 + row < lo || row0 + row >= hi) return;
+    const int64_t off = slot * (int64_t)T * T + (int64_t)row * T + (int64_t)piece * kE;
+    typedef TS v16_t __attribute__((ext_vector_type(kE)));
+    *reinterpret_cast<v16_t *>(dst + off) = *reinterpret_cast<const v16_t *>(src + off);
+}
+
 inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }

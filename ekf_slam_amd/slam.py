@@ -164,7 +164,9 @@ class EKF_SLAM(_EkfBase):
 
 
 class EKF_SLAM_UC(_EkfBase):
-    """Unknown correspondence (EKF_SLAM_UC.m); owns a Correspondence (EKF_SLAM_UC.m:16)."""
+    """Unknown correspondence (EKF_SLAM_UC.m); owns a Correspondence (EKF_SLAM_UC.m:16).  device_assoc=4 (an engine keyword) runs
+    measure() with the position-weighted likelihood (w_pos != 0, Correspondence.m:74) without a host wait per observation: the
+    device decides and carries out every row (include/ekfslam.h)."""
     _mode = "uc"
 
     def __init__(self, capacity=_DEFAULT_CAPACITY, **engine_kw):

@@ -105,8 +105,20 @@ typedef struct ekf_config {
                                     2: the kernel runs for every observation, the host dispatches on its mirror's decision (passed
                                        to the gather kernel as an argument) and VERIFIES every device decision before ekf_measure
                                        returns (EKF_ERR_STATE on a mismatch).
-                                    With w_pos != 0 the branch cannot be predicted: the device decides and is waited for (as 1)
-                                    whatever this says; ekf_associate() always runs on the device and waits. */
+                                    With w_pos != 0 the branch cannot be predicted: under 0-3 the device decides and is waited for (as 1)
+                                    whatever this says; ekf_associate() always runs on the device and waits.
+                                    4 (opt-in, unsharded handles only -- EKF_ERR_INVALID_ARG at create with world > 1 or force_sharded):
+                                       the device-decided branch, for ANY w_pos.  The device evaluates every row's association, takes
+                                       the branch (append, or correct landmark k) and carries it out; the host queues the whole scan
+                                       without a wait.  The landmark count is then the device's until the rows' records have come back
+                                       ("settled"): the next ekf_measure settles what has landed, every other call settles all of them
+                                       first and sees the state the waited mode (1) would show.  Every row takes a pending-pair slot (an
+                                       append or a stale row writes zeros): with F64 tiles the results are bit-identical to 1; with float
+                                       tiles the batch boundaries move (equal within the float tolerance).  To keep the waited mode's
+                                       errors exact a scan that could append beyond capacity_landmarks takes the waited path, and a scan
+                                       whose possible append keys do not all resolve in the landmark list is settled before ekf_measure
+                                       returns (a row whose append key fails applies nothing and stops the scan: EKF_ERR_LOOKUP, as 1).
+                                       Stale winner entries apply nothing and make the next settling call return EKF_ERR_STATE. */
     int32_t pass_direction;      /* the pass over P: 0 (default) = every other pass walks its work list backwards when the shard's
                                     tile store exceeds the 256 MiB Infinity Cache (what one pass wrote last the next reads first,
                                     on-die), forwards otherwise; 1 = always forwards; 2 = always alternate.  Same bits. */

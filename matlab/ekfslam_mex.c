@@ -45,7 +45,7 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
     if (nrhs < 1 || mxGetString(prhs[0], cmd, sizeof cmd)) mexErrMsgIdAndTxt("ekfslam:usage", "command string expected");
 
     /* ---- commands without a handle ---- */
-    if (!strcmp(cmd, "create")) {                 /* h = ekfslam_mex('create', mode, capacity [, tile [, batch [, device, rank, world [, storage [, pass_arith]]]]]) */
+    if (!strcmp(cmd, "create")) {                 /* h = ekfslam_mex('create', mode, capacity [, tile [, batch [, device, rank, world [, storage [, pass_arith [, device_assoc]]]]]]) */
         ekf_config cfg;
         ekf_handle *h = NULL;
         need(nrhs, 3, cmd);
@@ -61,6 +61,7 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
         }
         if (nrhs > 8) cfg.storage = (int32_t)mxGetScalar(prhs[8]);    /* EKF_STORE_*: 1 = float tiles (BASELINE configs[4]) */
         if (nrhs > 9) cfg.pass_arith = (int32_t)mxGetScalar(prhs[9]); /* EKF_ARITH_*: 1 = the pass over float tiles in F32 arithmetic, 2 = in split arithmetic */
+        if (nrhs > 10) cfg.device_assoc = (int32_t)mxGetScalar(prhs[10]); /* include/ekfslam.h: 4 = the device-decided branch (any w_pos) */
         int32_t rc = ekf_create(&cfg, &h);
         if (rc != EKF_OK) {
             char msg[256];

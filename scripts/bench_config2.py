@@ -44,12 +44,23 @@ def main():
     ap.add_argument("--force-sharded", action="store_true",
                     help="run the SHARDED code path on this one GPU (cfg.force_sharded, the library's own 1-rank RCCL communicator): per "
                          "correction k_rowpanel<kDev> -> ncclAllGather -> k_gather<sharded, kDev>; what a shard's measure() loop costs")
+    ap.add_argument("--w-pos", type=float, default=None,
+                    help="cfg.w_pos: weight of the Mahalanobis position cost in the association likelihood (1 = Correspondence.m:74); "
+                         "with w_pos != 0 device_assoc 0-3 wait for every decision")
+    ap.add_argument("--decided", action="store_true",
+                    help="cfg.device_assoc = 4: the device-decided branch -- the device evaluates the association, takes the branch "
+                         "(append or correct) and carries it out, for any w_pos; the host queues a whole scan without a wait")
     args = ap.parse_args()
     from ekf_slam_amd.slam import EKF_SLAM_UC, Landmark
     from ekf_slam_amd.world import SyntheticLandmark, make_run
     N = args.landmarks
     _, run = make_run(N, 20260102, 2 + args.steps, policy="nearest", m=args.m)
     shard_kw = {"force_sharded": 1} if args.force_sharded else {}
+    if args.w_pos is not None:
+        shard_kw["w_pos"] = args.w_pos
+    # --decided: room for one scan's appends beyond the map (a scan that could append past the capacity takes the waited path, so
+    # that the error comes from the row that causes it); the landmark block's leading dimension is the same as at capacity N
+    cap = N + args.m if args.decided else N
 
     def attach(engine):
         if args.force_sharded:
@@ -60,7 +71,7 @@ def main():
                 sys.exit("bench_config2.py: --force-sharded needs librccl (ekf_comm_unique_id failed)")
             engine.comm_init(raw.raw)
 
-    e = EKF_SLAM_UC(capacity=N, tile=args.tile, batch=args.batch, async_flush=args.async_flush, device_assoc=(0 if args.host_decision else 2 if args.verified else 1 if args.waited else 3), **shard_kw)
+    e = EKF_SLAM_UC(capacity=cap, tile=args.tile, batch=args.batch, async_flush=args.async_flush, device_assoc=(4 if args.decided else 0 if args.host_decision else 2 if args.verified else 1 if args.waited else 3), **shard_kw)
     attach(e._e)
     lm = Landmark('SYNTHETIC')
     t0 = time.perf_counter()
@@ -82,7 +93,7 @@ def main():
     # 35-70 ms stall (scripts/probe_queue.py) -- several times this benchmark's whole timed region.  Burn it on a throw-away engine of
     # the same configuration that replays the first scans from the same state.
     if not args.no_conditioning:
-        warm = EKF_SLAM_UC(capacity=N, tile=args.tile, batch=args.batch, async_flush=args.async_flush, device_assoc=int(eng.cfg.device_assoc), **shard_kw)
+        warm = EKF_SLAM_UC(capacity=cap, tile=args.tile, batch=args.batch, async_flush=args.async_flush, device_assoc=int(eng.cfg.device_assoc), **shard_kw)
         attach(warm._e)
         warm.x, warm.s, warm.P = e.x, e.s, e.P
         for rep in range(3):
@@ -121,14 +132,17 @@ def main():
                                   "iteration = predict + measure() over the %d nearest landmarks" % (N, args.m),
                       "deferred_batch": args.batch, "async_flush": args.async_flush, "tile": args.tile, "warmup_sweep_s": t_sweep,
                       "force_sharded": bool(args.force_sharded),
-                      "device_association": ("host mirror" if args.host_decision else "device, verified after dispatch" if args.verified
+                      "device_association": ("device-decided branch: decision taken and carried out on the device, no host wait"
+                                             if args.decided else "host mirror" if args.host_decision else "device, verified after dispatch" if args.verified
                                              else "device, waited for" if args.waited else
                                              "device-resident loop: decision produced and consumed on the device, no host wait"),
                       "associate": assoc, "gather_avg_us": (ms_ga / n_ga * 1e3) if n_ga else None,
                       "state_finite": bool(np.isfinite(x_end).all())}}
+    if args.w_pos is not None:
+        out["config"]["w_pos"] = args.w_pos
     if args.check:
         from oracle.ekf_structured import StructuredEKF
-        ref = StructuredEKF(N, "uc")
+        ref = StructuredEKF(N, "uc", **({"w_pos": args.w_pos} if args.w_pos is not None else {}))
         lr = SyntheticLandmark()
         for u, scan in run[:2]:
             ref.predict(u); ref.measure(scan, u, lr)
