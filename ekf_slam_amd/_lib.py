@@ -18,7 +18,7 @@ EKF_COMM_ID_BYTES = 128
 EKF_STORE_F64, EKF_STORE_F32 = 0, 1
 EKF_ARITH_F64, EKF_ARITH_F32, EKF_ARITH_SPLIT3 = 0, 1, 2
 (EKF_KERNEL_DOWNDATE, EKF_KERNEL_GATHER, EKF_KERNEL_PREDICT, EKF_KERNEL_ASSOCIATE, EKF_KERNEL_APPEND,
- EKF_KERNEL_ROWPANEL, EKF_KERNEL_EXCHANGE, EKF_KERNEL_COUNT) = range(8)
+ EKF_KERNEL_ROWPANEL, EKF_KERNEL_EXCHANGE, EKF_KERNEL_COMPACT, EKF_KERNEL_COUNT) = range(9)
 
 _d = ctypes.c_double
 _dp = ctypes.POINTER(ctypes.c_double)
@@ -78,6 +78,7 @@ SIGNATURES = {
     "ekf_set_x": (_i32, [_vp, _dp, _i64]),
     "ekf_get_s": (_i32, [_vp, _dp]),
     "ekf_set_s": (_i32, [_vp, _dp, _i64]),
+    "ekf_remove_landmarks": (_i32, [_vp, ctypes.POINTER(_i64), _i64]),
     "ekf_diag_poke_device_signature": (_i32, [_vp, _i64, _d]),
     "ekf_get_P": (_i32, [_vp, _dp]),
     "ekf_set_P": (_i32, [_vp, _dp, _i64]),

@@ -214,6 +214,13 @@ struct ekf_handle {
     hipEvent_t ev_pn_ready = nullptr, ev_pn_done = nullptr;
     int32_t (*xhook)(void *) = nullptr;   // ekf_exchange_set_hook: the caller's all-gather, called where the library-owned one would run
     void *xhook_ctx = nullptr;
+    // ekf_remove_landmarks: the map new landmark -> old landmark (ldm / 2 entries, built in pinned memory, uploaded in stream order; the
+    // staging area is reused only after the event behind the previous upload has passed) and the scratch the signatures are compacted into.
+    // Allocated at the first removal -- like the second tile store of a handle without cfg.async_flush (tilebuf[1]), which is kept.
+    int32_t *h_cmap = nullptr, *d_cmap = nullptr;
+    double *d_s_tmp = nullptr;
+    hipEvent_t ev_cmap = nullptr;
+    bool cmap_busy = false;
     KernelTimer timers[EKF_KERNEL_COUNT];
     std::vector<void *> allocs;
     int64_t bytes = 0;
@@ -1579,6 +1586,8 @@ int32_t ekf_destroy(ekf_handle *h) {
     if (h->h_small) hipHostFree(h->h_small);
     if (h->h_loctab) hipHostFree(h->h_loctab);
     if (h->wl_stage) { hipHostFree(h->wl_stage); hipEventDestroy(h->ev_wl); }
+    if (h->h_cmap) hipHostFree(h->h_cmap);
+    if (h->ev_cmap) hipEventDestroy(h->ev_cmap);
     if (h->own_stream) hipStreamDestroy(h->own_stream);
     delete h;
     return EKF_OK;
@@ -2049,6 +2058,103 @@ int32_t ekf_set_s(ekf_handle *h, const double *s, int64_t N) {
     h->s_host.assign(s, s + N);
     h->s_sorted_ok = false;
     return EKF_OK;
+}
+
+int32_t ekf_remove_landmarks(ekf_handle *h, const int64_t *idx, int64_t m) {
+    if (!h) return EKF_ERR_INVALID_ARG;
+    REQUIRE(h, m >= 0, EKF_ERR_INVALID_ARG, "remove_landmarks: negative count");
+    if (m == 0) return EKF_OK;
+    REQUIRE(h, h->cfg.world == 1, EKF_ERR_INVALID_ARG, "remove_landmarks: not built for sharded handles (world > 1): the tile owner is "
+            "(I + J) mod world, so a compaction would move tiles between shards");
+    REQUIRE(h, idx != nullptr, EKF_ERR_INVALID_ARG, "remove_landmarks: null index list");
+    REQUIRE(h, !h->pending, EKF_ERR_STATE, "remove_landmarks: a sharded correction is between begin and finish");
+    int32_t rc = use_device(h);
+    if (!rc) rc = verify_loop(h, /*block*/ true);      // cfg.device_assoc == 4: every queued row settled, N exact
+    if (rc) return rc;
+    const int64_t N_old = h->N;
+    for (int64_t i = 0; i < m; ++i)
+        REQUIRE(h, idx[i] >= 0 && idx[i] < N_old, EKF_ERR_INDEX, "remove_landmarks: landmark index outside the state");
+    std::vector<int64_t> rm(idx, idx + m);
+    std::sort(rm.begin(), rm.end());
+    REQUIRE(h, std::adjacent_find(rm.begin(), rm.end()) == rm.end(), EKF_ERR_INVALID_ARG, "remove_landmarks: a landmark is named twice");
+    // everything that can fail for lack of memory, before anything changes
+    const int64_t nmap = h->st.ldm / 2;
+    const bool first_removal = !h->tilebuf[1] || !h->d_cmap || !h->d_s_tmp;
+    if (!h->tilebuf[1]) {
+        char *tiles2 = nullptr;
+        HIPCHK(h, dalloc(h, &tiles2, (size_t)h->work_cap * h->T * h->T * elt_size(h)));
+        h->tilebuf[1] = tiles2;
+    }
+    if (!h->d_cmap) HIPCHK(h, dalloc(h, &h->d_cmap, (size_t)nmap));
+    if (!h->d_s_tmp) HIPCHK(h, dalloc(h, &h->d_s_tmp, (size_t)h->cap));
+    // dalloc clears on the null stream, which the handle's (non-blocking) stream does not wait for: the clears must have landed
+    // before anything below writes these buffers (ekf_create ends the same way)
+    if (first_removal) HIPCHK(h, hipDeviceSynchronize());
+    if (!h->h_cmap) HIPCHK(h, hipHostMalloc((void **)&h->h_cmap, (size_t)nmap * sizeof(int32_t), hipHostMallocDefault));
+    if (!h->ev_cmap) HIPCHK(h, hipEventCreateWithFlags(&h->ev_cmap, hipEventDisableTiming));
+    rc = materialize_predict(h);
+    if (!rc) rc = flush_pending(h);        // the pending pairs speak of the old rows; an asynchronous pass in flight is retired
+    if (rc) return rc;
+    HIPCHK(h, clear_pairs(h));
+    rc = refresh_work(h);                  // the tiles of the OLD map, row by row: the destination tiles are a suffix of that list
+    if (rc) return rc;
+    const int64_t N_new = N_old - m;
+    if (h->cmap_busy) { HIPCHK(h, hipEventSynchronize(h->ev_cmap)); h->cmap_busy = false; }
+    {
+        int64_t q = 0, k = 0;
+        for (int64_t l = 0; l < N_old; ++l) {
+            if (q < m && rm[(size_t)q] == l) { ++q; continue; }
+            h->h_cmap[k++] = (int32_t)l;
+        }
+        for (; k < nmap; ++k) h->h_cmap[k] = -1;
+    }
+    HIPCHK(h, hipMemcpyAsync(h->d_cmap, h->h_cmap, (size_t)nmap * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipEventRecord(h->ev_cmap, h->stream));
+    h->cmap_busy = true;
+    {
+        // Tile rows above the first removed landmark's do not change, and in tile-row-major order they are a prefix of the store; the
+        // rest is compacted from the current store into the other one.  Then whichever is SMALLER moves: the prefix follows
+        // (device to device) and the stores swap, or the compacted suffix is copied back and they do not -- at most 1.5 stores of
+        // traffic either way instead of 2.
+        const ekf_handle::WorkSet &ws = h->ws[h->ws_cur];
+        const int64_t nt_old = ekf_tiles_for(2 * N_old, h->T);
+        const int64_t slot0 = h->st.tm.row_base((2 * rm[0]) >> h->st.tm.shift), slot1 = h->st.tm.row_base(nt_old);
+        REQUIRE(h, ws.rows == nt_old && ws.nwork == slot1 && slot1 <= h->work_cap, EKF_ERR_STATE, "remove_landmarks: work list out of step");
+        const size_t tile_bytes = (size_t)h->T * h->T * elt_size(h);
+        char *src = (char *)h->tilebuf[h->base], *dst = (char *)h->tilebuf[h->base ^ 1];
+        {
+            TimedLaunch tl(h, EKF_KERNEL_COMPACT);
+            HIPCHK(h, launch_compact_tiles(h->st.tm, src, dst, ws.work + slot0, slot1 - slot0, h->d_cmap, h->storage, h->stream));
+        }
+        if (slot0 <= slot1 - slot0) {
+            if (slot0 > 0) HIPCHK(h, hipMemcpyAsync(dst, src, (size_t)slot0 * tile_bytes, hipMemcpyDeviceToDevice, h->stream));
+            h->base ^= 1;
+            h->st.tiles = h->tilebuf[h->base];
+        } else
+            HIPCHK(h, hipMemcpyAsync(src + (size_t)slot0 * tile_bytes, dst + (size_t)slot0 * tile_bytes, (size_t)(slot1 - slot0) * tile_bytes,
+                                     hipMemcpyDeviceToDevice, h->stream));
+    }
+    HIPCHK(h, launch_compact_state(h->st, h->cur, h->d_cmap, N_old, h->d_s_tmp, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->st.s, h->d_s_tmp, (size_t)N_old * 8, hipMemcpyDeviceToDevice, h->stream));
+    h->cur ^= 1;
+    h->st.dcur ^= 1;
+    // the host's side: the mirror of s (its sorted index is rebuilt at the next query), N, whatever spoke of the old numbering
+    h->s_host.resize((size_t)N_old, 0.0);
+    {
+        size_t k = 0, q = 0;
+        for (int64_t l = 0; l < N_old; ++l) {
+            if (q < (size_t)m && rm[q] == l) { ++q; continue; }
+            h->s_host[k++] = h->s_host[(size_t)l];
+        }
+        h->s_host.resize(k);
+    }
+    h->s_sorted_ok = false;
+    h->N = N_new;
+    h->pf_valid = false;
+    h->nx_valid = false;
+    h->pn_idx.clear();
+    h->hint_idx = -1;
+    return refresh_work(h);                // the lists of the new tile-row count (both sets respected; no pass is in flight)
 }
 
 int32_t ekf_diag_poke_device_signature(ekf_handle *h, int64_t idx, double value) {

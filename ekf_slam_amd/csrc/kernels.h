@@ -248,6 +248,14 @@ hipError_t launch_copy_rows(const TileMap &tm, const void *src, void *dst, int64
 // can bound them by (a pointer that is nullptr leaves the host's bound as it is)
 hipError_t launch_copy_rows_dev(const TileMap &tm, const void *src, void *dst, int64_t r0, int64_t r1, const int64_t *n_lo,
                                 const int64_t *n_hi, int storage, hipStream_t s);
+// Landmark removal (compact.h).  src_of (device, ldm / 2 entries): the old landmark of every landmark of the new map, strictly
+// increasing, -1 from the new count on.  launch_compact_tiles writes the `ntiles` destination tiles work[0 ..) = (I, J) of the
+// store `dst` from the store `src` (never the same store): element (r', c') = old element (src(r'), src(c')), zero beyond the new map.
+hipError_t launch_compact_tiles(const TileMap &tm, const void *src, void *dst, const int2 *work, int64_t ntiles, const int32_t *src_of,
+                                int storage, hipStream_t s);
+// ... and x, the strip and the live diagonal blocks from buffer cur / st.dcur into the other one (Prr and the pose copied), the
+// signatures into s_out (N_old doubles): N_old = landmarks before the removal
+hipError_t launch_compact_state(const DevState &st, int cur, const int32_t *src_of, int64_t N_old, double *s_out, hipStream_t s);
 hipError_t launch_unpack_dense(const DevState &st, int cur, int64_t n_mm, double *dense, int storage, hipStream_t s);
 hipError_t launch_pack_dense(const DevState &st, int cur, int64_t n_mm, const double *dense, int storage, hipStream_t s);
 hipError_t launch_get_block(const DevState &st, int cur, int64_t r0, int64_t c0, int64_t nr, int64_t nc,

@@ -38,6 +38,7 @@ namespace {
 #include "downdate.h"         // k_downdate, k_downdate_w
 #include "associate.h"        // k_associate, k_assoc_merge
 #include "state_io.h"         // dense <-> tiled, block reads, low-rank load, digest
+#include "compact.h"          // landmark removal: k_compact_tiles, k_compact_state
 
 }  // namespace
 
@@ -565,6 +566,26 @@ hipError_t launch_copy_rows_dev(const TileMap &tm, const void *src, void *dst, i
             hipLaunchKernelGGL(k_copy_tile_rows_dev<double>, dim3((unsigned)grid), dim3(kBlock), 0, s, (const double *)src, (double *)dst, slot0, nslots, (int)lo, (int)(hi - lo), T, I * T, r0, r1, n_lo, n_hi),
             hipLaunchKernelGGL(k_copy_tile_rows_dev<float>, dim3((unsigned)grid), dim3(kBlock), 0, s, (const float *)src, (float *)dst, slot0, nslots, (int)lo, (int)(hi - lo), T, I * T, r0, r1, n_lo, n_hi));
     }
+    return hipGetLastError();
+}
+
+hipError_t launch_compact_tiles(const TileMap &tm, const void *src, void *dst, const int2 *work, int64_t ntiles, const int32_t *src_of,
+                                int storage, hipStream_t s) {
+    if (ntiles <= 0) return hipSuccess;
+    if (src == dst) return hipErrorInvalidValue;                        // out of place only
+    const int64_t pieces = (int64_t)tm.T * tm.T / (storage == 0 ? 2 : 4);
+    const int items = (int)cdiv(pieces, (int64_t)kBlock * kCompactRows);
+    const int64_t grid = ntiles * items;
+    if (grid > 0x7fffffff) return hipErrorInvalidValue;
+    EKF_STORAGE_DISPATCH(storage,
+        hipLaunchKernelGGL(k_compact_tiles<double>, dim3((unsigned)grid), dim3(kBlock), 0, s, (const double *)src, (double *)dst, work, items, src_of, tm),
+        hipLaunchKernelGGL(k_compact_tiles<float>, dim3((unsigned)grid), dim3(kBlock), 0, s, (const float *)src, (float *)dst, work, items, src_of, tm));
+    return hipGetLastError();
+}
+
+hipError_t launch_compact_state(const DevState &st, int cur, const int32_t *src_of, int64_t N_old, double *s_out, hipStream_t s) {
+    const int64_t grid = cdiv(N_old > 0 ? N_old : 1, kBlock);
+    hipLaunchKernelGGL(k_compact_state, dim3((unsigned)grid), dim3(kBlock), 0, s, st, cur, src_of, N_old, s_out);
     return hipGetLastError();
 }
 

@@ -304,6 +304,13 @@ class Engine:
         Pf = np.asfortranarray(np.asarray(P, dtype=np.float64))
         self._check(self.lib.ekf_set_P(self.h, _p(Pf.reshape(-1, order="F")), Pf.shape[0]))
 
+    def remove_landmarks(self, indices):
+        """Drop the landmarks `indices` (0-based, any iterable of ints, any order) from the map on the device
+        (ekf_remove_landmarks): the survivors keep their order and their bits."""
+        idx = [int(i) for i in indices]
+        arr = (ctypes.c_int64 * max(len(idx), 1))(*idx)
+        self._check(self.lib.ekf_remove_landmarks(self.h, arr, len(idx)))
+
     def load_lowrank_state(self, x, s, d, U):
         x, s, d = _vec(x), _vec(s), _vec(d)
         U = np.asfortranarray(np.asarray(U, dtype=np.float64))

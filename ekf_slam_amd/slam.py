@@ -126,6 +126,16 @@ class _EkfBase:
     def append(self, u, R, landmarkPos, signature):
         self._e.append(u, R, landmarkPos, signature)
 
+    def remove_landmarks(self, idx):
+        """Drop landmarks idx (1-based like every landmark index of this layer; a number or any iterable, any order) from
+        the map: their entries of x, their signatures, their rows and columns of P -- on the device, survivors keep order
+        and bits (ekf_remove_landmarks).  The reference has no such method and no policy for WHICH landmark to drop: that
+        is the caller's.  Signatures are not renumbered (assign .s if the UC convention 'new signature = N + 1' collides)."""
+        idx = np.asarray(idx).reshape(-1)
+        if idx.size and not np.all(idx == np.floor(idx)):
+            raise ValueError("remove_landmarks: landmark indices are whole numbers")
+        self._e.remove_landmarks([int(i) - 1 for i in idx])
+
     def _push_params(self):
         pass
 

@@ -271,6 +271,19 @@ int32_t ekf_get_x(ekf_handle *h, double *x /* 3+2N */);
 int32_t ekf_set_x(ekf_handle *h, const double *x, int64_t n);
 int32_t ekf_get_s(ekf_handle *h, double *s /* N */);
 int32_t ekf_set_s(ekf_handle *h, const double *s, int64_t N);
+/* Remove the m landmarks idx[0 .. m-1] (0-based, any order) from the map: marginalisation in covariance form -- their entries of x,
+ * their signatures and their rows and columns of P are dropped, on the device, with no arithmetic.  Afterwards N is N - m; the surviving
+ * landmarks keep their relative order (landmark k becomes k - #{removed < k}: ties of the association still go to the lowest index, and
+ * known correspondence corrects landmark `ii`), and every surviving value of x, s and P keeps its BITS in every storage kind.
+ * Signatures are NOT renumbered: the reference's convention "a new landmark gets signature N + 1" (EKF_SLAM_UC.m:122-123) can therefore
+ * hand out a signature a surviving landmark already carries -- ekf_set_s is the caller's tool for that.
+ * Pending corrections are applied first (as for every reader of P), a recorded predict(u) is carried out, and with cfg.device_assoc = 4
+ * every queued row is settled.  The tile store is compacted OUT OF PLACE into a second store: a handle without cfg.async_flush allocates
+ * it at its first removal and keeps it (ekf_device_bytes reports it; EKF_ERR_HIP with the state untouched if that allocation fails).
+ * m == 0: EKF_OK, nothing happens.  Removing all N landmarks leaves the empty map.
+ * Refused before anything changes: idx == NULL with m > 0, m < 0, a duplicate (EKF_ERR_INVALID_ARG); an index outside [0, N)
+ * (EKF_ERR_INDEX); a handle with world > 1 (EKF_ERR_INVALID_ARG: a compaction moves tiles between shards, which is not built). */
+int32_t ekf_remove_landmarks(ekf_handle *h, const int64_t *idx, int64_t m);
 /* Diagnostic -- a fault injector for tests of the device-resident measure loop's verification, of no use to a host: overwrites the DEVICE copy
  * of signature idx (0-based) and leaves the host mirror alone.  The next ekf_measure whose association involves that landmark then queues its
  * launches from a prediction the device contradicts; every launch stays inside the state (a correction falls back to the predicted landmark,
@@ -313,7 +326,8 @@ enum { EKF_KERNEL_DOWNDATE = 0, EKF_KERNEL_GATHER = 1, EKF_KERNEL_PREDICT = 2, E
        EKF_KERNEL_APPEND = 4,
        EKF_KERNEL_ROWPANEL = 5,   /* sharded handles: the extraction of a correction's (or a prefetch's) row-panels into the send area */
        EKF_KERNEL_EXCHANGE = 6,   /* sharded handles with ekf_comm_init: the all-gather on the library's communicator */
-       EKF_KERNEL_COUNT = 7 };
+       EKF_KERNEL_COMPACT = 7,    /* ekf_remove_landmarks: the compaction of the tile store (k_compact_tiles alone, not its device-to-device copy) */
+       EKF_KERNEL_COUNT = 8 };
 /* Bracket every launch of kernel `which` with HIP events on the handle's stream (on != 0; on > 512 also reserves
  * event pairs for that many launches between two reads, so that none is created inside a timed region) and read the
  * accumulated launch count and device time; reading synchronises the stream and resets the counters. */

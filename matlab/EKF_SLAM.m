@@ -53,6 +53,13 @@ classdef EKF_SLAM < handle
                             double(reshape([lm.loc], 2, [])'));
             end
         end
+        function removeLandmarks(h, idx)
+            % Drop landmarks idx (1-based like every landmark index here; any order, any shape) from the map: their entries of
+            % x, their signatures, their rows and columns of P, on the GPU; the survivors keep their order and their bits.
+            % Not a method of the reference, which never shrinks its map; WHICH landmark to drop is the caller's policy.
+            % Signatures are not renumbered: assign h.s if the UC convention 'new signature = N + 1' would collide.
+            h.gateway('remove_landmarks', double(idx(:)));
+        end
         function B = covarianceBlock(h, r0, c0, nr, nc)   % P(r0:r0+nr-1, c0:c0+nc-1) without moving the rest of P
             B = ekfslam_mex('get_P_block', h.hnd, r0, c0, nr, nc);
         end
@@ -87,5 +94,8 @@ classdef EKF_SLAM < handle
     end
     methods (Access = protected)
         function m = abiMode(~), m = 0; end               % EKF_MODE_KNOWN
+        function varargout = gateway(h, cmd, varargin)    % ekfslam_mex(cmd, handle, args...) for commands added after the core set
+            [varargout{1:nargout}] = ekfslam_mex(cmd, h.hnd, varargin{:});
+        end
     end
 end

@@ -2,6 +2,8 @@ classdef EKF_SLAM_UC < EKF_SLAM
     % Drop-in for the reference's EKF_SLAM_UC (unknown correspondence): Rc = [.1,5], owns a Correspondence,
     % measure() associates every observation (Correspondence.m:28-88) before append / correct -- inside ekf_measure,
     % with the s_cost / s_thresh of h.correspondence forwarded before each call.
+    % removeLandmarks(idx) is inherited from EKF_SLAM: in this mode every failed association appends a landmark
+    % (EKF_SLAM_UC.m:121-123), so it is how a long run prunes spurious ones before the capacity is exhausted.
     properties
         correspondence = Correspondence(1e-11, 1e9, 'EKF_SLAM_UC');
     end

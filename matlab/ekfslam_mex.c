@@ -15,10 +15,20 @@
  * handle_of(), which rejects an empty / non-uint64 / null handle with a MATLAB error instead of dereferencing it.
  */
 #include <stdint.h>
+#include <stdlib.h>
 #include <string.h>
 
 #include "ekfslam.h"
 #include "mex.h"
+
+/* ekf_remove_landmarks is the one entry point this gateway can live without: bound weakly, so that the gateway still links
+ * against a libekfslam (or a stand-in) that predates it; 'remove_landmarks' then raises a MATLAB error instead. */
+#if defined(__GNUC__)
+#pragma weak ekf_remove_landmarks
+#define HAVE_REMOVE_LANDMARKS (ekf_remove_landmarks != 0)
+#else
+#define HAVE_REMOVE_LANDMARKS 1
+#endif
 
 static void need(int nrhs, int want, const char *cmd) {
     if (nrhs < want) mexErrMsgIdAndTxt("ekfslam:usage", "'%s' needs %d arguments, got %d", cmd, want, nrhs);
@@ -137,6 +147,18 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
         return;
     }
     if (!strcmp(cmd, "flush")) { check(h, ekf_flush(h)); return; }
+    if (!strcmp(cmd, "remove_landmarks")) {       /* (h, idx): landmark numbers, 1-based like 'correct', any order, any shape */
+        need(nrhs, 3, cmd);
+        if (!HAVE_REMOVE_LANDMARKS) mexErrMsgIdAndTxt("ekfslam:usage", "remove_landmarks: this libekfslam has no ekf_remove_landmarks");
+        const mwSize m = mxGetNumberOfElements(prhs[2]);
+        int64_t *idx0 = (int64_t *)malloc((m ? m : 1) * sizeof(int64_t));       /* freed before any MATLAB error can unwind */
+        if (!idx0) mexErrMsgIdAndTxt("ekfslam:usage", "remove_landmarks: out of memory");
+        for (mwSize i = 0; i < m; ++i) idx0[i] = (int64_t)mxGetPr(prhs[2])[i] - 1;
+        const int32_t rc = ekf_remove_landmarks(h, idx0, (int64_t)m);
+        free(idx0);
+        check(h, rc);
+        return;
+    }
     if (!strcmp(cmd, "measure")) {                /* (h, observed_LL m x 3, u, lm_index L x 1, lm_loc L x 2) */
         need(nrhs, 6, cmd);
         check(h, ekf_measure(h, mxGetPr(prhs[2]), (int64_t)mxGetM(prhs[2]), mxGetPr(prhs[3]), mxGetPr(prhs[4]),
