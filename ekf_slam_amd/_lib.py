@@ -79,6 +79,9 @@ SIGNATURES = {
     "ekf_get_s": (_i32, [_vp, _dp]),
     "ekf_set_s": (_i32, [_vp, _dp, _i64]),
     "ekf_remove_landmarks": (_i32, [_vp, ctypes.POINTER(_i64), _i64]),
+    "ekf_constrain_landmarks": (_i32, [_vp, _i64, _i64, _dp, _dp]),
+    "ekf_merge_landmarks": (_i32, [_vp, _i64, _i64, _dp]),
+    "ekf_landmark_distance": (_i32, [_vp, _i64, _i64, _dp, _dp, _dp, _dp]),
     "ekf_diag_poke_device_signature": (_i32, [_vp, _i64, _d]),
     "ekf_get_P": (_i32, [_vp, _dp]),
     "ekf_set_P": (_i32, [_vp, _dp, _i64]),

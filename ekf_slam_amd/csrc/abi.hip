@@ -180,6 +180,7 @@ struct ekf_handle {
                                                // (nullptr: inflight_N is exact)
     double *d_pos_cost = nullptr, *d_sig_cost = nullptr, *d_digest = nullptr;
     double *h_small = nullptr;   // pinned 32 doubles
+    double *d_csmall = nullptr;  // 16 doubles: the small operands of a landmark-landmark constraint (k_constrain_probe)
     // sharded correction: exchange slabs (own allocations, or caller-provided device buffers)
     bool sharded = false;          // world > 1, or cfg.force_sharded (the sharded code path with one rank, on one GPU)
     double *own_send = nullptr, *own_recv = nullptr, *send = nullptr, *recv = nullptr;
@@ -1494,6 +1495,7 @@ int32_t ekf_create(const ekf_config *cfg, ekf_handle **out) {
     HIPCHK(h, dalloc(h, &h->d_pos_cost, (size_t)h->cap));
     HIPCHK(h, dalloc(h, &h->d_sig_cost, (size_t)h->cap));
     HIPCHK(h, dalloc(h, &h->d_digest, kDigestDoubles));
+    HIPCHK(h, dalloc(h, &h->d_csmall, 16));
     {
         h->sharded = world > 1 || cfg->force_sharded != 0;
         if (h->sharded) {
@@ -2155,6 +2157,95 @@ int32_t ekf_remove_landmarks(ekf_handle *h, const int64_t *idx, int64_t m) {
     h->pn_idx.clear();
     h->hint_idx = -1;
     return refresh_work(h);                // the lists of the new tile-row count (both sets respected; no pass is in flight)
+}
+
+namespace {
+
+// The three entry points of a constraint between two landmarks (kernels.h: ConstrainArgs) share everything up to
+// the point where S = G H' + R and nu are on the host: `apply == false` (ekf_landmark_distance) stops there.
+// Order: arguments -> sharding -> exchange state -> the device loop settled (N exact) -> indices -> predict carried out, pairs
+// flushed, an asynchronous pass retired -> S, nu -> the kernel, the one-pair pass.
+int32_t constrain_impl(ekf_handle *h, const char *name, int64_t i, int64_t j, const double delta[2], const double R[4], bool apply,
+                       double *d2_out, double S_out[4]) {
+    const std::string who = std::string(name) + ": ";
+#define CREQ(cond, status, msg) do { if (!(cond)) return fail(h, (status), (who + (msg)).c_str()); } while (0)
+    CREQ(i != j, EKF_ERR_INVALID_ARG, "the two landmarks must differ");
+    double d0 = 0.0, d1 = 0.0, r00 = 0.0, r01 = 0.0, r10 = 0.0, r11 = 0.0;
+    if (delta) { d0 = delta[0]; d1 = delta[1]; }
+    if (R) colmajor2(R, r00, r01, r10, r11);
+    CREQ(std::isfinite(d0) && std::isfinite(d1), EKF_ERR_INVALID_ARG, "delta is not finite");
+    CREQ(std::isfinite(r00) && std::isfinite(r01) && std::isfinite(r10) && std::isfinite(r11), EKF_ERR_INVALID_ARG, "R is not finite");
+    CREQ(r01 == r10 && r00 >= 0.0 && r11 >= 0.0 && r00 * r11 - r01 * r10 >= 0.0, EKF_ERR_INVALID_ARG,
+         "R must be symmetric with non-negative diagonal and determinant");
+    CREQ(h->cfg.world == 1, EKF_ERR_INVALID_ARG, "not built for sharded handles (world > 1): the pair needs the row-panels of two landmarks "
+         "exchanged, and a merge ends in a compaction that would move tiles between shards");
+    CREQ(!h->pending, EKF_ERR_STATE, "a sharded correction is between begin and finish");
+    int32_t rc = use_device(h);
+    if (!rc) rc = verify_loop(h, /*block*/ true);      // cfg.device_assoc == 4: every queued row settled, N exact
+    if (rc) return rc;
+    CREQ(i >= 0 && i < h->N && j >= 0 && j < h->N, EKF_ERR_INDEX, "landmark index outside the state");
+    rc = materialize_predict(h);
+    if (!rc) rc = flush_pending(h);                    // as for every reader of P; an asynchronous pass in flight is retired
+    if (rc) return rc;
+    // S and nu on the host: both landmarks' own blocks (live F64 copies), their cross block (tiles), four entries of x
+    HIPCHK(h, launch_constrain_probe(h->st, h->cur, 2 * i, 2 * j, h->d_csmall, h->storage, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->h_small, h->d_csmall, 14 * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    const double *sm = h->h_small;
+    const double Rr[4] = { r00, r01, r10, r11 };
+    double S[4], Si[4];
+    ekfm::constrain_S(sm, sm + 3, sm + 6, Rr, S);
+    const double nu0 = d0 - (sm[10] - sm[12]), nu1 = d1 - (sm[11] - sm[13]);
+    const double det = S[0] * S[3] - S[1] * S[2];
+    const bool regular = std::isfinite(S[0]) && std::isfinite(S[1]) && std::isfinite(S[2]) && std::isfinite(S[3]) && S[0] > 0.0 && det > 0.0;
+    if (S_out) { S_out[0] = S[0]; S_out[1] = S[2]; S_out[2] = S[1]; S_out[3] = S[3]; }       // column-major
+    if (d2_out) {
+        ekfm::inv2(S, Si);
+        *d2_out = regular ? (nu0 * Si[0] + nu1 * Si[2]) * nu0 + (nu0 * Si[1] + nu1 * Si[3]) * nu1 : NAN;
+    }
+    if (!apply) return EKF_OK;
+    CREQ(regular, EKF_ERR_STATE, "S = H P H' + R is not positive definite (two perfectly correlated identical landmarks and R = 0?); "
+         "nothing was changed");
+#undef CREQ
+    rc = refresh_work(h);
+    if (rc) return rc;
+    ConstrainArgs a;
+    a.d0 = d0; a.d1 = d1; a.R00 = r00; a.R01 = r01; a.R10 = r10; a.R11 = r11;
+    a.ai = 2 * i; a.aj = 2 * j; a.n_mm = n_mm(h); a.cur = h->cur; a.npend = h->npend; a.pstart = h->pstart;     // (the ring is empty: 0, 0)
+    {
+        TimedLaunch tl(h, EKF_KERNEL_GATHER);
+        HIPCHK(h, launch_gather_constrain(h->st, a, h->storage, h->stream));
+    }
+    h->cur ^= 1;
+    h->st.dcur ^= 1;
+    h->npend += 1;
+    // whatever spoke of the old state (flush_pending drops the prefetched and the extracted row-panels)
+    h->pn_idx.clear();
+    h->hint_idx = -1;
+    rc = flush_pending(h);                             // the existing one-pair pass, before the call returns -- whatever cfg.batch says
+    if (rc) return rc;
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return EKF_OK;
+}
+
+}  // namespace
+
+int32_t ekf_constrain_landmarks(ekf_handle *h, int64_t i, int64_t j, const double delta[2], const double R[4]) {
+    if (!h) return EKF_ERR_INVALID_ARG;
+    return constrain_impl(h, "constrain_landmarks", i, j, delta, R, /*apply*/ true, nullptr, nullptr);
+}
+
+int32_t ekf_merge_landmarks(ekf_handle *h, int64_t keep, int64_t drop, const double R[4]) {
+    if (!h) return EKF_ERR_INVALID_ARG;
+    int32_t rc = constrain_impl(h, "merge_landmarks", keep, drop, nullptr, R, /*apply*/ true, nullptr, nullptr);
+    if (rc) return rc;
+    return ekf_remove_landmarks(h, &drop, 1);
+}
+
+int32_t ekf_landmark_distance(ekf_handle *h, int64_t i, int64_t j, const double delta[2], const double R[4], double *d2, double S[4]) {
+    if (!h) return EKF_ERR_INVALID_ARG;
+    if (!d2) return fail(h, EKF_ERR_INVALID_ARG, "landmark_distance: null d2");
+    return constrain_impl(h, "landmark_distance", i, j, delta, R, /*apply*/ false, d2, S);
 }
 
 int32_t ekf_diag_poke_device_signature(ekf_handle *h, int64_t idx, double value) {

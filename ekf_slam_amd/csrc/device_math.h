@@ -176,4 +176,14 @@ EKF_MHD void inv2(const double a[4], double o[4]) {
     else      { o[0] = m11; o[1] = m12; o[2] = m21; o[3] = m22; }
 }
 
+// S = G H' + R of a constraint between landmarks i and j (constrain.h), from their own 2x2 blocks pii / pjj (lower-triangle entries
+// (0,0) (1,0) (1,1)) and their cross block pij (row-major, P(a_i + r, a_j + b)); R and S row-major.  Written as
+// G(:, a_i) - G(:, a_j) + R with G = P(a_i, :) - P(a_j, :), entry by entry -- the host (the singularity check, ekf_landmark_distance)
+// and the kernel run this same function.
+EKF_MHD void constrain_S(const double pii[3], const double pjj[3], const double pij[4], const double R[4], double S[4]) {
+    for (int r = 0; r < 2; ++r)
+        for (int b = 0; b < 2; ++b)
+            S[2 * r + b] = ((pii[r + b] - pij[2 * b + r]) - (pij[2 * r + b] - pjj[r + b])) + R[2 * r + b];
+}
+
 }  // namespace ekfm

@@ -256,6 +256,22 @@ hipError_t launch_compact_tiles(const TileMap &tm, const void *src, void *dst, c
 // ... and x, the strip and the live diagonal blocks from buffer cur / st.dcur into the other one (Prr and the pose copied), the
 // signatures into s_out (N_old doubles): N_old = landmarks before the removal
 hipError_t launch_compact_state(const DevState &st, int cur, const int32_t *src_of, int64_t N_old, double *s_out, hipStream_t s);
+// A constraint between two landmarks (constrain.h): "l_i - l_j was observed as (d0, d1) with noise covariance R".
+struct ConstrainArgs {
+    double d0, d1;
+    double R00, R01, R10, R11;
+    int64_t ai, aj;           // landmark-block rows of the two landmarks (2 * index), ai != aj
+    int64_t n_mm;             // active landmark-block size (2N)
+    int32_t cur;
+    int32_t npend;            // ring position the pair goes to (the ring is empty when the kernel runs: 0) ...
+    int32_t pstart;           // ... counted from this slot
+};
+// out (device, 14 doubles): both landmarks' own 2x2 blocks (live F64 copies), their cross block (tiles), their entries of x -- what the
+// host forms S and nu from before anything changes
+hipError_t launch_constrain_probe(const DevState &st, int cur, int64_t ai, int64_t aj, double *out, int storage, hipStream_t s);
+// k_gather_constrain: the constraint's pair into the ring slot, x / Prr / strip into buffer a.cur ^ 1, every landmark's live diagonal
+// block (with the pair applied) into buffer dcur ^ 1; the caller flips both and lets a pass apply the pair to the tiles
+hipError_t launch_gather_constrain(const DevState &st, const ConstrainArgs &a, int storage, hipStream_t s);
 hipError_t launch_unpack_dense(const DevState &st, int cur, int64_t n_mm, double *dense, int storage, hipStream_t s);
 hipError_t launch_pack_dense(const DevState &st, int cur, int64_t n_mm, const double *dense, int storage, hipStream_t s);
 hipError_t launch_get_block(const DevState &st, int cur, int64_t r0, int64_t c0, int64_t nr, int64_t nc,

@@ -39,6 +39,7 @@ namespace {
 #include "associate.h"        // k_associate, k_assoc_merge
 #include "state_io.h"         // dense <-> tiled, block reads, low-rank load, digest
 #include "compact.h"          // landmark removal: k_compact_tiles, k_compact_state
+#include "constrain.h"        // a constraint between two landmarks: k_constrain_probe, k_gather_constrain
 
 }  // namespace
 
@@ -586,6 +587,27 @@ hipError_t launch_compact_tiles(const TileMap &tm, const void *src, void *dst, c
 hipError_t launch_compact_state(const DevState &st, int cur, const int32_t *src_of, int64_t N_old, double *s_out, hipStream_t s) {
     const int64_t grid = cdiv(N_old > 0 ? N_old : 1, kBlock);
     hipLaunchKernelGGL(k_compact_state, dim3((unsigned)grid), dim3(kBlock), 0, s, st, cur, src_of, N_old, s_out);
+    return hipGetLastError();
+}
+
+static bool constrain_rows_ok(int64_t ai, int64_t aj, int64_t n_mm) {
+    return ai >= 0 && aj >= 0 && ai + 1 < n_mm && aj + 1 < n_mm && (ai & 1) == 0 && (aj & 1) == 0 && ai != aj;
+}
+
+hipError_t launch_constrain_probe(const DevState &st, int cur, int64_t ai, int64_t aj, double *out, int storage, hipStream_t s) {
+    if (!out || ai < 0 || aj < 0 || ((ai | aj) & 1) || ai == aj) return hipErrorInvalidValue;
+    EKF_STORAGE_DISPATCH(storage,
+        hipLaunchKernelGGL(k_constrain_probe<double>, dim3(1), dim3(64), 0, s, st, cur, ai, aj, out),
+        hipLaunchKernelGGL(k_constrain_probe<float>, dim3(1), dim3(64), 0, s, st, cur, ai, aj, out));
+    return hipGetLastError();
+}
+
+hipError_t launch_gather_constrain(const DevState &st, const ConstrainArgs &a, int storage, hipStream_t s) {
+    if (!constrain_rows_ok(a.ai, a.aj, a.n_mm) || st.tm.padded(a.n_mm) > st.ldm || a.npend < 0 || a.npend >= st.pcap) return hipErrorInvalidValue;
+    const int64_t grid = cdiv(st.tm.padded(a.n_mm), kBlock);
+    EKF_STORAGE_DISPATCH(storage,
+        hipLaunchKernelGGL(k_gather_constrain<double>, dim3((unsigned)grid), dim3(kBlock), 0, s, st, a),
+        hipLaunchKernelGGL(k_gather_constrain<float>, dim3((unsigned)grid), dim3(kBlock), 0, s, st, a));
     return hipGetLastError();
 }
 

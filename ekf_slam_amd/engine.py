@@ -311,6 +311,35 @@ class Engine:
         arr = (ctypes.c_int64 * max(len(idx), 1))(*idx)
         self._check(self.lib.ekf_remove_landmarks(self.h, arr, len(idx)))
 
+    @staticmethod
+    def _delta_R(delta, R):
+        d = None if delta is None else _vec(delta, 2)
+        Rf = None if R is None else np.ascontiguousarray(_colmajor(R).reshape(2, 2).reshape(-1, order="F"))
+        return d, Rf
+
+    def constrain_landmarks(self, i, j, delta=None, R=None):
+        """'l_i - l_j was observed as delta with noise covariance R' (0-based i != j; delta None: (0, 0), R None: zero): the exact
+        linear Kalman update between two landmarks, formed and applied on the device before the call returns
+        (ekf_constrain_landmarks)."""
+        d, Rf = self._delta_R(delta, R)
+        self._check(self.lib.ekf_constrain_landmarks(self.h, int(i), int(j), None if d is None else _p(d), None if Rf is None else _p(Rf)))
+
+    def merge_landmarks(self, keep, drop, R=None):
+        """Fuse landmark `drop` into `keep` (0-based): constrain_landmarks(keep, drop, None, R), then remove_landmarks([drop]);
+        keep's index afterwards is keep - (drop < keep) (ekf_merge_landmarks)."""
+        _, Rf = self._delta_R(None, R)
+        self._check(self.lib.ekf_merge_landmarks(self.h, int(keep), int(drop), None if Rf is None else _p(Rf)))
+
+    def landmark_distance(self, i, j, delta=None, R=None):
+        """(d2, S): the squared Mahalanobis distance nu' S^-1 nu of 'l_i - l_j = delta' under the current state and its 2 x 2
+        innovation covariance -- what a caller gates a merge on.  Changes nothing (ekf_landmark_distance)."""
+        d, Rf = self._delta_R(delta, R)
+        d2 = ctypes.c_double()
+        S = np.empty(4)
+        self._check(self.lib.ekf_landmark_distance(self.h, int(i), int(j), None if d is None else _p(d), None if Rf is None else _p(Rf),
+                                                   ctypes.byref(d2), _p(S)))
+        return float(d2.value), S.reshape(2, 2, order="F")
+
     def load_lowrank_state(self, x, s, d, U):
         x, s, d = _vec(x), _vec(s), _vec(d)
         U = np.asfortranarray(np.asarray(U, dtype=np.float64))

@@ -135,6 +135,39 @@ class _EkfBase:
         if idx.size and not np.all(idx == np.floor(idx)):
             raise ValueError("remove_landmarks: landmark indices are whole numbers")
         self._e.remove_landmarks([int(i) - 1 for i in idx])
+        if self.log is not None:
+            self.log.record_edit("remove", idx)
+
+    @staticmethod
+    def _landmark_numbers(what, *idx):
+        v = np.asarray(idx, dtype=np.float64).reshape(-1)
+        if not np.all(v == np.floor(v)):
+            raise ValueError("%s: landmark indices are whole numbers" % what)
+        return [int(i) for i in v]
+
+    def constrain_landmarks(self, i, j, delta=None, R=None):
+        """'landmark i minus landmark j was observed as delta, with noise covariance R' (1-based i != j; delta None: (0, 0) -- the
+        same point; R None: zero): a linear EKF correction between two landmarks, on the device (ekf_constrain_landmarks).
+        The reference has no such method."""
+        i, j = self._landmark_numbers("constrain_landmarks", i, j)
+        self._e.constrain_landmarks(i - 1, j - 1, delta, R)
+        if self.log is not None:
+            self.log.record_edit("constrain", [i, j], delta, R)
+
+    def merge_landmarks(self, keep, drop, R=None):
+        """Fuse two landmarks that are the same point (1-based): constrain_landmarks(keep, drop, None, R), then
+        remove_landmarks(drop).  `keep` retains its signature; its number afterwards is keep - (drop < keep).  WHICH pairs to
+        merge is the caller's policy: landmark_distance is the gate (ekf_merge_landmarks)."""
+        keep, drop = self._landmark_numbers("merge_landmarks", keep, drop)
+        self._e.merge_landmarks(keep - 1, drop - 1, R)
+        if self.log is not None:
+            self.log.record_edit("merge", [keep, drop], None, R)
+
+    def landmark_distance(self, i, j, delta=None, R=None):
+        """(d2, S) of 'landmark i minus landmark j = delta' under the current state (1-based): the squared Mahalanobis distance
+        and the 2 x 2 innovation covariance.  Changes nothing (ekf_landmark_distance)."""
+        i, j = self._landmark_numbers("landmark_distance", i, j)
+        return self._e.landmark_distance(i - 1, j - 1, delta, R)
 
     def _push_params(self):
         pass

@@ -5,15 +5,23 @@ the odometry `u` handed to predict() (SLAM.m:105-110) and what measure() saw aft
 (EKF_SLAM.m:102,111,120): `observed_LL` (m x 3) and the landmark table (index, loc).  Replaying a log into an
 engine reproduces the run bit for bit on the same hardware, and is how a run on one machine is compared with
 another (or with the CPU oracle).  Format: one .npz with ragged arrays (`*_ptr` are CSR-style offsets).
+
+A map that can be edited (remove_landmarks / constrain_landmarks / merge_landmarks of ekf_slam_amd/slam.py) needs its edits in the
+log too, or a replay no longer reproduces the run: `record_edit` notes one, with the 1-based landmark numbers that layer consumed,
+at the position `len(log)` it was made at -- it is replayed after step len(log) - 1 and before step len(log).  A log without edits
+is written exactly as before (format 1, the same arrays); one with edits as format 2, with the edit arrays added.
 """
 import numpy as np
 
 FORMAT = "ekfslam-trajectory-1"
+FORMAT_EDITS = "ekfslam-trajectory-2"
+EDIT_KINDS = ("remove", "constrain", "merge")
 
 
 class TrajectoryLog:
     def __init__(self):
         self.u, self.obs, self.lm_index, self.lm_loc = [], [], [], []
+        self.edits = []             # (step, kind, idx (1-based numbers), delta[2], R[2x2]) in the order they were made
 
     def __len__(self):
         return len(self.u)
@@ -25,6 +33,20 @@ class TrajectoryLog:
         self.lm_index.append(np.asarray(lm_index, dtype=np.float64).reshape(-1).copy())
         self.lm_loc.append(np.asarray(lm_loc, dtype=np.float64).reshape(-1, 2).copy())
 
+    def record_edit(self, kind, idx, delta=None, R=None):
+        """A map edit made now, i.e. after the len(self) steps recorded so far.  kind: 'remove' (idx: the landmarks), 'constrain'
+        (idx: [i, j]) or 'merge' (idx: [keep, drop]); landmark numbers 1-based; delta None: (0, 0), R None: the zero matrix."""
+        if kind not in EDIT_KINDS:
+            raise ValueError("record_edit: kind is one of %s" % (EDIT_KINDS,))
+        idx = np.asarray(idx, dtype=np.float64).reshape(-1)
+        if not np.all(idx == np.floor(idx)):
+            raise ValueError("record_edit: landmark indices are whole numbers")
+        if kind != "remove" and idx.size != 2:
+            raise ValueError("record_edit: '%s' names two landmarks" % kind)
+        d = np.zeros(2) if delta is None else np.asarray(delta, dtype=np.float64).reshape(2).copy()
+        Rm = np.zeros((2, 2)) if R is None else np.asarray(R, dtype=np.float64).reshape(2, 2).copy()
+        self.edits.append((len(self), kind, idx.astype(np.int64), d, Rm))
+
     def save(self, path):
         def ragged(parts, width):
             ptr = np.cumsum([0] + [len(p) for p in parts])
@@ -33,25 +55,57 @@ class TrajectoryLog:
         obs_ptr, obs = ragged(self.obs, 3)
         lm_ptr, lmi = ragged(self.lm_index, 0)
         _, lml = ragged(self.lm_loc, 2)
-        np.savez_compressed(path, format=np.array(FORMAT), u=np.array(self.u).reshape(-1, 2), obs_ptr=obs_ptr, obs=obs,
-                            lm_ptr=lm_ptr, lm_index=lmi, lm_loc=lml)
+        arrays = dict(u=np.array(self.u).reshape(-1, 2), obs_ptr=obs_ptr, obs=obs, lm_ptr=lm_ptr, lm_index=lmi, lm_loc=lml)
+        if not self.edits:
+            np.savez_compressed(path, format=np.array(FORMAT), **arrays)
+            return
+        e_ptr, e_idx = ragged([e[2] for e in self.edits], 0)
+        np.savez_compressed(path, format=np.array(FORMAT_EDITS), edit_step=np.array([e[0] for e in self.edits], dtype=np.int64),
+                            edit_kind=np.array([EDIT_KINDS.index(e[1]) for e in self.edits], dtype=np.int64), edit_ptr=e_ptr,
+                            edit_idx=e_idx.astype(np.int64), edit_delta=np.array([e[3] for e in self.edits]).reshape(-1, 2),
+                            edit_R=np.array([e[4] for e in self.edits]).reshape(-1, 2, 2), **arrays)
 
     @staticmethod
     def load(path):
         g = np.load(path, allow_pickle=False)
-        if str(g["format"]) != FORMAT:
-            raise ValueError("not an %s file" % FORMAT)
+        fmt = str(g["format"])
+        if fmt not in (FORMAT, FORMAT_EDITS):
+            raise ValueError("not an %s / %s file" % (FORMAT, FORMAT_EDITS))
         t = TrajectoryLog()
         for k in range(len(g["u"])):
             a, b = g["obs_ptr"][k], g["obs_ptr"][k + 1]
             c, d = g["lm_ptr"][k], g["lm_ptr"][k + 1]
             t.record(g["u"][k], g["obs"][a:b], g["lm_index"][c:d], g["lm_loc"][c:d])
+        if fmt == FORMAT_EDITS:
+            for q in range(len(g["edit_step"])):
+                a, b = g["edit_ptr"][q], g["edit_ptr"][q + 1]
+                t.edits.append((int(g["edit_step"][q]), EDIT_KINDS[int(g["edit_kind"][q])], g["edit_idx"][a:b].astype(np.int64),
+                                g["edit_delta"][q].copy(), g["edit_R"][q].copy()))
         return t
 
     def replay(self, engine, start=0, stop=None):
-        """predict + measure for steps [start, stop) on anything with predict(u) / measure(obs, u, idx, loc)."""
+        """predict + measure for steps [start, stop) on anything with predict(u) / measure(obs, u, idx, loc) -- an Engine.  The edits
+        recorded at positions [start, stop) are applied in front of their step through the engine's remove_landmarks /
+        constrain_landmarks / merge_landmarks (0-based there: the recorded 1-based numbers are converted here); the ones recorded
+        at position len(self), after the last step, when stop is the end of the log."""
         stop = len(self) if stop is None else stop
+
+        def apply_edits(at):
+            for step, kind, idx, delta, R in self.edits:
+                if step != at:
+                    continue
+                idx0 = [int(i) - 1 for i in idx]
+                if kind == "remove":
+                    engine.remove_landmarks(idx0)
+                elif kind == "constrain":
+                    engine.constrain_landmarks(idx0[0], idx0[1], delta, R)
+                else:
+                    engine.merge_landmarks(idx0[0], idx0[1], R)
+
         for k in range(start, stop):
+            apply_edits(k)
             engine.predict(self.u[k])
             if len(self.obs[k]):
                 engine.measure(self.obs[k], self.u[k], self.lm_index[k], self.lm_loc[k])
+        if stop == len(self) and stop > start:
+            apply_edits(stop)

@@ -284,6 +284,29 @@ int32_t ekf_set_s(ekf_handle *h, const double *s, int64_t N);
  * Refused before anything changes: idx == NULL with m > 0, m < 0, a duplicate (EKF_ERR_INVALID_ARG); an index outside [0, N)
  * (EKF_ERR_INDEX); a handle with world > 1 (EKF_ERR_INVALID_ARG: a compaction moves tiles between shards, which is not built). */
 int32_t ekf_remove_landmarks(ekf_handle *h, const int64_t *idx, int64_t m);
+/* Tell the filter that landmarks i and j (0-based, i != j) are related: "l_i - l_j was observed as delta, with noise covariance R" -- a
+ * LINEAR correction between two landmarks (H = +I2 at landmark i's entries, -I2 at landmark j's), hence the exact Kalman update with no
+ * angles:  G = H P,  S = G H' + R,  nu = delta - (l_i - l_j),  K = G' S^-1,  x += K nu,  P -= K G  (P = (I - K H) P, EKF_SLAM.m:145, for
+ * this H).  delta == NULL means (0, 0): "the same point"; R (2 x 2, column-major) == NULL means the zero matrix.
+ * A synchronising call: the device-resident measure loop is settled, a recorded predict(u) is carried out, pending corrections are
+ * applied and an asynchronous pass is retired (as for every reader of P); then the pair (K, G) is formed on the device and applied by one
+ * pass over P BEFORE the call returns: ekf_pending reports 0 afterwards, whatever cfg.batch says.
+ * Refused before anything changes: i == j, a non-finite delta or R, an R that is not symmetric or has a negative diagonal entry or
+ * determinant (EKF_ERR_INVALID_ARG); a handle with world > 1 (EKF_ERR_INVALID_ARG: the pair needs two exchanged row-panels, which is not
+ * built for sharded handles); a sharded correction between begin and finish (EKF_ERR_STATE); an index outside [0, N) (EKF_ERR_INDEX).
+ * An S that is not finite or not positive definite (two perfectly correlated identical landmarks with R = 0 give S = 0) is refused
+ * with EKF_ERR_STATE: x, s and P are then what the getters reported before the call. */
+int32_t ekf_constrain_landmarks(ekf_handle *h, int64_t i, int64_t j, const double delta[2], const double R[4]);
+/* Fuse two landmarks that are the same point: ekf_constrain_landmarks(h, keep, drop, NULL, R) followed by
+ * ekf_remove_landmarks(h, &drop, 1) -- bit for bit what those two calls leave, with their refusals.  `keep` retains its signature, the
+ * survivors keep their order, and keep's index afterwards is keep - (drop < keep).  WHICH pairs to merge is the caller's policy
+ * (ekf_landmark_distance is the gate). */
+int32_t ekf_merge_landmarks(ekf_handle *h, int64_t keep, int64_t drop, const double R[4]);
+/* What a caller gates a merge on: *d2 = nu' S^-1 nu, the squared Mahalanobis distance of "l_i - l_j = delta" under the current state
+ * (arguments, synchronisation and refusals as for ekf_constrain_landmarks), and S (2 x 2, column-major; may be NULL).  Changes nothing:
+ * x, s, P and ekf_P_digest are afterwards what they were.  A singular S is no error here: it is returned, and *d2 is NaN. */
+int32_t ekf_landmark_distance(ekf_handle *h, int64_t i, int64_t j, const double delta[2], const double R[4],
+                              double *d2, double S[4] /* column-major, may be NULL */);
 /* Diagnostic -- a fault injector for tests of the device-resident measure loop's verification, of no use to a host: overwrites the DEVICE copy
  * of signature idx (0-based) and leaves the host mirror alone.  The next ekf_measure whose association involves that landmark then queues its
  * launches from a prediction the device contradicts; every launch stays inside the state (a correction falls back to the predicted landmark,

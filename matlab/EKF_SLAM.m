@@ -60,6 +60,28 @@ classdef EKF_SLAM < handle
             % Signatures are not renumbered: assign h.s if the UC convention 'new signature = N + 1' would collide.
             h.gateway('remove_landmarks', double(idx(:)));
         end
+        function constrainLandmarks(h, i, j, delta, R)
+            % 'landmark i minus landmark j was observed as delta (1x2), with noise covariance R (2x2)': a linear EKF correction
+            % between two landmarks (1-based, i ~= j), formed and applied on the GPU.  delta = [0 0] says 'the same point';
+            % R = zeros(2) is allowed.  Not a method of the reference.
+            if nargin < 4 || isempty(delta), delta = [0 0]; end
+            if nargin < 5 || isempty(R), R = zeros(2); end
+            h.gateway('constrain_landmarks', double(i), double(j), double(delta(:)), double(R));
+        end
+        function mergeLandmarks(h, keep, drop, R)
+            % Fuse two landmarks that are the same point: constrainLandmarks(keep, drop, [0 0], R), then removeLandmarks(drop).
+            % keep retains its signature; its number afterwards is keep - (drop < keep).  WHICH pairs to merge is the caller's
+            % policy: landmarkDistance is the gate.
+            if nargin < 4 || isempty(R), R = zeros(2); end
+            h.gateway('merge_landmarks', double(keep), double(drop), double(R));
+        end
+        function [d2, S] = landmarkDistance(h, i, j, delta, R)
+            % Squared Mahalanobis distance of 'landmark i minus landmark j = delta' under the current state, and its 2x2
+            % innovation covariance S.  Changes nothing.
+            if nargin < 4 || isempty(delta), delta = [0 0]; end
+            if nargin < 5 || isempty(R), R = zeros(2); end
+            [d2, S] = h.gateway('landmark_distance', double(i), double(j), double(delta(:)), double(R));
+        end
         function B = covarianceBlock(h, r0, c0, nr, nc)   % P(r0:r0+nr-1, c0:c0+nc-1) without moving the rest of P
             B = ekfslam_mex('get_P_block', h.hnd, r0, c0, nr, nc);
         end

@@ -21,13 +21,23 @@
 #include "ekfslam.h"
 #include "mex.h"
 
-/* ekf_remove_landmarks is the one entry point this gateway can live without: bound weakly, so that the gateway still links
- * against a libekfslam (or a stand-in) that predates it; 'remove_landmarks' then raises a MATLAB error instead. */
+/* The map-editing entry points (ekf_remove_landmarks; ekf_constrain_landmarks, ekf_merge_landmarks, ekf_landmark_distance) are the
+ * ones this gateway can live without: bound weakly, so that the gateway still links against a libekfslam (or a stand-in) that
+ * predates them; their commands then raise a MATLAB error instead. */
 #if defined(__GNUC__)
 #pragma weak ekf_remove_landmarks
+#pragma weak ekf_constrain_landmarks
+#pragma weak ekf_merge_landmarks
+#pragma weak ekf_landmark_distance
 #define HAVE_REMOVE_LANDMARKS (ekf_remove_landmarks != 0)
+#define HAVE_CONSTRAIN_LANDMARKS (ekf_constrain_landmarks != 0)
+#define HAVE_MERGE_LANDMARKS (ekf_merge_landmarks != 0)
+#define HAVE_LANDMARK_DISTANCE (ekf_landmark_distance != 0)
 #else
 #define HAVE_REMOVE_LANDMARKS 1
+#define HAVE_CONSTRAIN_LANDMARKS 1
+#define HAVE_MERGE_LANDMARKS 1
+#define HAVE_LANDMARK_DISTANCE 1
 #endif
 
 static void need(int nrhs, int want, const char *cmd) {
@@ -46,6 +56,16 @@ static ekf_handle *handle_of(int nrhs, const mxArray *prhs[]) {
 static void check(ekf_handle *h, int32_t rc) {
     if (rc != EKF_OK)
         mexErrMsgIdAndTxt("ekfslam:status", "%s: %s", ekf_status_string(rc), h ? ekf_last_error(h) : "");
+}
+
+/* delta (2 elements) and R (2 x 2, column-major as MATLAB holds it) of the landmark-landmark commands */
+static const double *two_of(const mxArray *a, const char *cmd, const char *what) {
+    if (!a || mxGetNumberOfElements(a) != 2 || !mxGetPr(a)) mexErrMsgIdAndTxt("ekfslam:usage", "%s: %s needs 2 elements", cmd, what);
+    return mxGetPr(a);
+}
+static const double *r2x2_of(const mxArray *a, const char *cmd) {
+    if (!a || mxGetNumberOfElements(a) != 4 || !mxGetPr(a)) mexErrMsgIdAndTxt("ekfslam:usage", "%s: R needs 2 x 2 elements", cmd);
+    return mxGetPr(a);
 }
 
 static int64_t nstate(ekf_handle *h) { int64_t N; check(h, ekf_num_landmarks(h, &N)); return 3 + 2 * N; }
@@ -157,6 +177,31 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
         const int32_t rc = ekf_remove_landmarks(h, idx0, (int64_t)m);
         free(idx0);
         check(h, rc);
+        return;
+    }
+    if (!strcmp(cmd, "constrain_landmarks")) {    /* (h, i, j, delta 2x1, R 2x2): landmark numbers 1-based like 'correct' */
+        need(nrhs, 6, cmd);
+        if (!HAVE_CONSTRAIN_LANDMARKS) mexErrMsgIdAndTxt("ekfslam:usage", "constrain_landmarks: this libekfslam has no ekf_constrain_landmarks");
+        check(h, ekf_constrain_landmarks(h, (int64_t)mxGetScalar(prhs[2]) - 1, (int64_t)mxGetScalar(prhs[3]) - 1, two_of(prhs[4], cmd, "delta"),
+                                         r2x2_of(prhs[5], cmd)));
+        return;
+    }
+    if (!strcmp(cmd, "merge_landmarks")) {        /* (h, keep, drop, R 2x2) */
+        need(nrhs, 5, cmd);
+        if (!HAVE_MERGE_LANDMARKS) mexErrMsgIdAndTxt("ekfslam:usage", "merge_landmarks: this libekfslam has no ekf_merge_landmarks");
+        check(h, ekf_merge_landmarks(h, (int64_t)mxGetScalar(prhs[2]) - 1, (int64_t)mxGetScalar(prhs[3]) - 1, r2x2_of(prhs[4], cmd)));
+        return;
+    }
+    if (!strcmp(cmd, "landmark_distance")) {      /* [d2, S] = (h, i, j, delta 2x1, R 2x2) */
+        double d2 = 0.0;
+        need(nrhs, 6, cmd);
+        if (!HAVE_LANDMARK_DISTANCE) mexErrMsgIdAndTxt("ekfslam:usage", "landmark_distance: this libekfslam has no ekf_landmark_distance");
+        const double *delta = two_of(prhs[4], cmd, "delta"), *R = r2x2_of(prhs[5], cmd);
+        mxArray *S = mxCreateDoubleMatrix(2, 2, mxREAL);
+        const int32_t rc = ekf_landmark_distance(h, (int64_t)mxGetScalar(prhs[2]) - 1, (int64_t)mxGetScalar(prhs[3]) - 1, delta, R, &d2, mxGetPr(S));
+        if (rc != EKF_OK) { mxDestroyArray(S); check(h, rc); }
+        plhs[0] = mxCreateDoubleScalar(d2);
+        if (nlhs > 1) plhs[1] = S; else mxDestroyArray(S);
         return;
     }
     if (!strcmp(cmd, "measure")) {                /* (h, observed_LL m x 3, u, lm_index L x 1, lm_loc L x 2) */
