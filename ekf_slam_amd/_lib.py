@@ -82,6 +82,7 @@ SIGNATURES = {
     "ekf_constrain_landmarks": (_i32, [_vp, _i64, _i64, _dp, _dp]),
     "ekf_merge_landmarks": (_i32, [_vp, _i64, _i64, _dp]),
     "ekf_landmark_distance": (_i32, [_vp, _i64, _i64, _dp, _dp, _dp, _dp]),
+    "ekf_nearest_landmarks": (_i32, [_vp, _dp, _dp, ctypes.POINTER(_i64)]),
     "ekf_diag_poke_device_signature": (_i32, [_vp, _i64, _d]),
     "ekf_get_P": (_i32, [_vp, _dp]),
     "ekf_set_P": (_i32, [_vp, _dp, _i64]),

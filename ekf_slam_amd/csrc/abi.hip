@@ -222,6 +222,9 @@ struct ekf_handle {
     double *d_s_tmp = nullptr;
     hipEvent_t ev_cmap = nullptr;
     bool cmap_busy = false;
+    // ekf_nearest_landmarks: the N (d2, partner) entries k_nearest writes and the pinned area they are read back through (cap entries
+    // each, allocated at the first search and kept; every search ends with a stream synchronisation, so the area is never busy)
+    NearestEntry *d_nearest = nullptr, *h_nearest = nullptr;
     KernelTimer timers[EKF_KERNEL_COUNT];
     std::vector<void *> allocs;
     int64_t bytes = 0;
@@ -1590,6 +1593,7 @@ int32_t ekf_destroy(ekf_handle *h) {
     if (h->wl_stage) { hipHostFree(h->wl_stage); hipEventDestroy(h->ev_wl); }
     if (h->h_cmap) hipHostFree(h->h_cmap);
     if (h->ev_cmap) hipEventDestroy(h->ev_cmap);
+    if (h->h_nearest) hipHostFree(h->h_nearest);
     if (h->own_stream) hipStreamDestroy(h->own_stream);
     delete h;
     return EKF_OK;
@@ -2193,16 +2197,12 @@ int32_t constrain_impl(ekf_handle *h, const char *name, int64_t i, int64_t j, co
     HIPCHK(h, hipStreamSynchronize(h->stream));
     const double *sm = h->h_small;
     const double Rr[4] = { r00, r01, r10, r11 };
-    double S[4], Si[4];
+    double S[4], d2;
     ekfm::constrain_S(sm, sm + 3, sm + 6, Rr, S);
     const double nu0 = d0 - (sm[10] - sm[12]), nu1 = d1 - (sm[11] - sm[13]);
-    const double det = S[0] * S[3] - S[1] * S[2];
-    const bool regular = std::isfinite(S[0]) && std::isfinite(S[1]) && std::isfinite(S[2]) && std::isfinite(S[3]) && S[0] > 0.0 && det > 0.0;
+    const bool regular = ekfm::constrain_d2(S, nu0, nu1, d2);       // the function k_nearest runs for every pair it reports
     if (S_out) { S_out[0] = S[0]; S_out[1] = S[2]; S_out[2] = S[1]; S_out[3] = S[3]; }       // column-major
-    if (d2_out) {
-        ekfm::inv2(S, Si);
-        *d2_out = regular ? (nu0 * Si[0] + nu1 * Si[2]) * nu0 + (nu0 * Si[1] + nu1 * Si[3]) * nu1 : NAN;
-    }
+    if (d2_out) *d2_out = d2;
     if (!apply) return EKF_OK;
     CREQ(regular, EKF_ERR_STATE, "S = H P H' + R is not positive definite (two perfectly correlated identical landmarks and R = 0?); "
          "nothing was changed");
@@ -2246,6 +2246,45 @@ int32_t ekf_landmark_distance(ekf_handle *h, int64_t i, int64_t j, const double 
     if (!h) return EKF_ERR_INVALID_ARG;
     if (!d2) return fail(h, EKF_ERR_INVALID_ARG, "landmark_distance: null d2");
     return constrain_impl(h, "landmark_distance", i, j, delta, R, /*apply*/ false, d2, S);
+}
+
+// Order as in constrain_impl: arguments -> sharding -> exchange state -> the device loop settled (N exact) -> predict carried out, pairs
+// flushed, an asynchronous pass retired -> the one read-only pass (k_nearest) -> the N entries through the pinned area.
+int32_t ekf_nearest_landmarks(ekf_handle *h, const double R[4], double *d2, int64_t *partner) {
+    if (!h) return EKF_ERR_INVALID_ARG;
+    REQUIRE(h, h->N == 0 || (d2 && partner), EKF_ERR_INVALID_ARG, "nearest_landmarks: null argument");
+    double r00 = 0.0, r01 = 0.0, r10 = 0.0, r11 = 0.0;
+    if (R) colmajor2(R, r00, r01, r10, r11);
+    REQUIRE(h, std::isfinite(r00) && std::isfinite(r01) && std::isfinite(r10) && std::isfinite(r11), EKF_ERR_INVALID_ARG,
+            "nearest_landmarks: R is not finite");
+    REQUIRE(h, r01 == r10 && r00 >= 0.0 && r11 >= 0.0 && r00 * r11 - r01 * r10 >= 0.0, EKF_ERR_INVALID_ARG,
+            "nearest_landmarks: R must be symmetric with non-negative diagonal and determinant");
+    REQUIRE(h, h->cfg.world == 1, EKF_ERR_INVALID_ARG, "nearest_landmarks: not built for sharded handles (world > 1): the search reads every "
+            "tile of the lower triangle, and a shard holds only its own");
+    REQUIRE(h, !h->pending, EKF_ERR_STATE, "nearest_landmarks: a sharded correction is between begin and finish");
+    int32_t rc = use_device(h);
+    if (!rc) rc = verify_loop(h, /*block*/ true);      // cfg.device_assoc == 4: every queued row settled, N exact
+    if (rc) return rc;
+    REQUIRE(h, h->N == 0 || (d2 && partner), EKF_ERR_INVALID_ARG, "nearest_landmarks: null argument");
+    rc = materialize_predict(h);
+    if (!rc) rc = flush_pending(h);                    // as for every reader of P; an asynchronous pass in flight is retired
+    if (rc) return rc;
+    const int64_t N = h->N;
+    if (N == 0) return EKF_OK;
+    if (!h->d_nearest) {
+        HIPCHK(h, dalloc(h, &h->d_nearest, (size_t)h->cap));
+        HIPCHK(h, hipDeviceSynchronize());             // dalloc clears on the null stream (see ekf_remove_landmarks)
+    }
+    if (!h->h_nearest) HIPCHK(h, hipHostMalloc((void **)&h->h_nearest, (size_t)h->cap * sizeof(NearestEntry), hipHostMallocDefault));
+    const double Rr[4] = { r00, r01, r10, r11 };
+    {
+        TimedLaunch tl(h, EKF_KERNEL_ASSOCIATE);
+        HIPCHK(h, launch_nearest(h->st, h->cur, N, Rr, h->d_nearest, h->storage, h->stream));
+    }
+    HIPCHK(h, hipMemcpyAsync(h->h_nearest, h->d_nearest, (size_t)N * sizeof(NearestEntry), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    for (int64_t i = 0; i < N; ++i) { d2[i] = h->h_nearest[i].d2; partner[i] = h->h_nearest[i].partner; }
+    return EKF_OK;
 }
 
 int32_t ekf_diag_poke_device_signature(ekf_handle *h, int64_t idx, double value) {

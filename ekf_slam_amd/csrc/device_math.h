@@ -186,4 +186,16 @@ EKF_MHD void constrain_S(const double pii[3], const double pjj[3], const double 
             S[2 * r + b] = ((pii[r + b] - pij[2 * b + r]) - (pij[2 * r + b] - pjj[r + b])) + R[2 * r + b];
 }
 
+// d2 = nu' S^-1 nu of that constraint (S row-major), the squared Mahalanobis distance a merge is gated on; returns whether S is
+// regular (finite, S00 > 0, det S > 0) and leaves NaN in d2 where it is not.  The host (ekf_landmark_distance, the refusal of a singular
+// constraint) and k_nearest (nearest.h) run this same function: with FP contraction off both give the same bits.
+EKF_MHD bool constrain_d2(const double S[4], double nu0, double nu1, double &d2) {
+    const double det = S[0] * S[3] - S[1] * S[2];
+    const bool regular = isfinite(S[0]) && isfinite(S[1]) && isfinite(S[2]) && isfinite(S[3]) && S[0] > 0.0 && det > 0.0;
+    double Si[4];
+    inv2(S, Si);
+    d2 = regular ? (nu0 * Si[0] + nu1 * Si[2]) * nu0 + (nu0 * Si[1] + nu1 * Si[3]) * nu1 : NAN;
+    return regular;
+}
+
 }  // namespace ekfm

@@ -272,6 +272,11 @@ hipError_t launch_constrain_probe(const DevState &st, int cur, int64_t ai, int64
 // k_gather_constrain: the constraint's pair into the ring slot, x / Prr / strip into buffer a.cur ^ 1, every landmark's live diagonal
 // block (with the pair applied) into buffer dcur ^ 1; the caller flips both and lets a pass apply the pair to the tiles
 hipError_t launch_gather_constrain(const DevState &st, const ConstrainArgs &a, int storage, hipStream_t s);
+// The candidate search in front of a merge (nearest.h): out[i] = (min over j < i of d2(i, j), that j; (+inf, -1) where no pair is
+// admissible) for the N landmarks of an UNSHARDED tile store (tm.world == 1: the search needs every tile), d2 as ekf_landmark_distance
+// defines it for delta = 0 and the noise covariance R (row-major).  Reads state buffer cur / diagonal buffer st.dcur, writes `out` only.
+struct alignas(16) NearestEntry { double d2; int64_t partner; };
+hipError_t launch_nearest(const DevState &st, int cur, int64_t N, const double R[4], NearestEntry *out, int storage, hipStream_t s);
 hipError_t launch_unpack_dense(const DevState &st, int cur, int64_t n_mm, double *dense, int storage, hipStream_t s);
 hipError_t launch_pack_dense(const DevState &st, int cur, int64_t n_mm, const double *dense, int storage, hipStream_t s);
 hipError_t launch_get_block(const DevState &st, int cur, int64_t r0, int64_t c0, int64_t nr, int64_t nc,

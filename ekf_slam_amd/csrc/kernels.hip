@@ -40,6 +40,7 @@ namespace {
 #include "state_io.h"         // dense <-> tiled, block reads, low-rank load, digest
 #include "compact.h"          // landmark removal: k_compact_tiles, k_compact_state
 #include "constrain.h"        // a constraint between two landmarks: k_constrain_probe, k_gather_constrain
+#include "nearest.h"          // the candidate search in front of a merge: k_nearest
 
 }  // namespace
 
@@ -608,6 +609,17 @@ hipError_t launch_gather_constrain(const DevState &st, const ConstrainArgs &a, i
     EKF_STORAGE_DISPATCH(storage,
         hipLaunchKernelGGL(k_gather_constrain<double>, dim3((unsigned)grid), dim3(kBlock), 0, s, st, a),
         hipLaunchKernelGGL(k_gather_constrain<float>, dim3((unsigned)grid), dim3(kBlock), 0, s, st, a));
+    return hipGetLastError();
+}
+
+hipError_t launch_nearest(const DevState &st, int cur, int64_t N, const double R[4], NearestEntry *out, int storage, hipStream_t s) {
+    if (N <= 0) return hipSuccess;
+    // a group of landmarks (and a float lane's two) must lie inside one tile row / one tile; landmark indices are 32-bit in the kernel
+    if (!out || !R || st.tm.world != 1 || st.tm.T < 4 || (st.tm.T / 2) % kNearestGroup != 0 || 2 * N > st.ldm || N > 0x7fffffff) return hipErrorInvalidValue;
+    const int64_t grid = cdiv(cdiv(N, (int64_t)kNearestGroup), kBlock / 64);
+    EKF_STORAGE_DISPATCH(storage,
+        hipLaunchKernelGGL(k_nearest<double>, dim3((unsigned)grid), dim3(kBlock), 0, s, st, cur, N, R[0], R[1], R[2], R[3], out),
+        hipLaunchKernelGGL(k_nearest<float>, dim3((unsigned)grid), dim3(kBlock), 0, s, st, cur, N, R[0], R[1], R[2], R[3], out));
     return hipGetLastError();
 }
 

@@ -340,6 +340,26 @@ class Engine:
                                                    ctypes.byref(d2), _p(S)))
         return float(d2.value), S.reshape(2, 2, order="F")
 
+    def nearest_landmarks(self, R=None):
+        """(d2, partner): for every landmark i (0-based) the j < i that minimises landmark_distance(i, j, None, R)[0] and that
+        minimum, bit for bit; partner is int64 with -1 (and d2 = +inf) where no pair is admissible -- landmark 0, rows whose pairs
+        are all irregular.  The lowest index wins ties.  One read-only pass over P on the device (ekf_nearest_landmarks)."""
+        _, Rf = self._delta_R(None, R)
+        N = self.N
+        d2 = np.empty(max(N, 1))
+        partner = np.empty(max(N, 1), dtype=np.int64)
+        self._check(self.lib.ekf_nearest_landmarks(self.h, None if Rf is None else _p(Rf), _p(d2),
+                                                   partner.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))))
+        return d2[:N], partner[:N]
+
+    def duplicate_candidates(self, gate, R=None):
+        """The rows of nearest_landmarks(R) with d2 <= gate as a list of (i, j, d2), 0-based, j = partner[i] < i, sorted by
+        (d2, i): what a caller would hand to merge_landmarks(keep=j, drop=i, R).  A host-side filter of the N results."""
+        d2, partner = self.nearest_landmarks(R)
+        rows = np.nonzero((partner >= 0) & (d2 <= float(gate)))[0]
+        rows = rows[np.lexsort((rows, d2[rows]))]
+        return [(int(i), int(partner[i]), float(d2[i])) for i in rows]
+
     def load_lowrank_state(self, x, s, d, U):
         x, s, d = _vec(x), _vec(s), _vec(d)
         U = np.asfortranarray(np.asarray(U, dtype=np.float64))

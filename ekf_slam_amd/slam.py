@@ -169,6 +169,35 @@ class _EkfBase:
         i, j = self._landmark_numbers("landmark_distance", i, j)
         return self._e.landmark_distance(i - 1, j - 1, delta, R)
 
+    def nearest_landmarks(self, R=None):
+        """(d2, partner) for every landmark, 1-based: partner[k - 1] is the landmark j < k that minimises
+        landmark_distance(k, j, None, R)[0], d2[k - 1] that minimum; partner 0 (and d2 = +inf) means none -- landmark 1, rows whose
+        pairs are all singular.  The lowest number wins ties.  One read-only pass over P on the device; changes nothing
+        (ekf_nearest_landmarks).  The reference has no such method."""
+        d2, partner = self._e.nearest_landmarks(R)
+        return d2, partner + 1
+
+    def duplicate_candidates(self, gate, R=None):
+        """[(i, j, d2)] of the landmarks whose nearest earlier landmark lies at or below `gate` (compare with a chi-square value,
+        2 degrees of freedom), 1-based, j < i, sorted by (d2, i)."""
+        return [(i + 1, j + 1, d2) for i, j, d2 in self._e.duplicate_candidates(gate, R)]
+
+    def fuse_duplicates(self, gate, R=None, max_merges=None):
+        """The SIMPLEST complete fusion policy, not the fastest: repeat { search; take the candidate with the smallest (d2, i) at or
+        below `gate`; merge_landmarks(keep=j, drop=i, R) } until none is left or `max_merges` merges were made.  One search plus
+        one merge per fusion (every merge changes P, hence every d2); batching disjoint pairs from one search is not built.
+        Returns the merges made as [(keep, drop, d2)], 1-based numbers as they were when each merge was made.  Every merge goes
+        through merge_landmarks, so an attached trajectory log records it."""
+        merges = []
+        while max_merges is None or len(merges) < max_merges:
+            cand = self.duplicate_candidates(gate, R)
+            if not cand:
+                break
+            i, j, d2 = cand[0]
+            self.merge_landmarks(j, i, R)
+            merges.append((j, i, d2))
+        return merges
+
     def _push_params(self):
         pass
 

@@ -307,6 +307,23 @@ int32_t ekf_merge_landmarks(ekf_handle *h, int64_t keep, int64_t drop, const dou
  * x, s, P and ekf_P_digest are afterwards what they were.  A singular S is no error here: it is returned, and *d2 is NaN. */
 int32_t ekf_landmark_distance(ekf_handle *h, int64_t i, int64_t j, const double delta[2], const double R[4],
                               double *d2, double S[4] /* column-major, may be NULL */);
+/* WHICH pairs to merge -- the candidate search in front of ekf_merge_landmarks: for every landmark i (0-based), partner[i] is the j in
+ * [0, i) that minimises d2(i, j), and d2[i] is that minimum.  d2(i, j) is BY DEFINITION the value
+ * ekf_landmark_distance(h, i, j, NULL, R, &d2, NULL) yields -- nu' S^-1 nu of "l_i - l_j = 0" under the current state, i the first
+ * argument and j < i the second (the rounding of S is not symmetric in the two, so the order is part of the definition) -- bit for bit.
+ * A pair for which ekf_landmark_distance yields NaN (S not finite, S00 <= 0 or det S <= 0) never wins: it is skipped.  The comparison
+ * is a strict < in ascending j: the lowest index wins ties, as everywhere (Correspondence.m).  Landmark 0 and any row whose pairs are
+ * all irregular get partner = -1 and d2 = +inf.  Only j < i is searched, on purpose: a duplicate is the LATER append, so a row reads as
+ * ekf_merge_landmarks(h, keep = partner[i], drop = i, R), and the output has the fixed size N.  Gating is the caller's: compare d2[i]
+ * with a chi-square value (2 degrees of freedom), as with ekf_landmark_distance.
+ * One read-only pass over the tiled P on the device.  Refusals and synchronisation in ekf_constrain_landmarks' order: h, d2 or partner
+ * NULL with N > 0, an R that ekf_constrain_landmarks would refuse (EKF_ERR_INVALID_ARG); a handle with world > 1 (EKF_ERR_INVALID_ARG:
+ * sharding -- the search needs every tile; a lone shard with cfg.force_sharded owns every tile and works); a sharded correction between
+ * begin and finish (EKF_ERR_STATE); then the device-resident measure loop is settled (N exact), a recorded predict(u) is carried out,
+ * pending corrections are applied and an asynchronous pass is retired.  N == 0: EKF_OK, nothing written.
+ * Changes nothing: x, s, P and ekf_P_digest are afterwards what they were; ekf_pending reports 0, as after ekf_landmark_distance. */
+int32_t ekf_nearest_landmarks(ekf_handle *h, const double R[4] /* 2x2 column-major, NULL = zero */,
+                              double *d2 /* N */, int64_t *partner /* N */);
 /* Diagnostic -- a fault injector for tests of the device-resident measure loop's verification, of no use to a host: overwrites the DEVICE copy
  * of signature idx (0-based) and leaves the host mirror alone.  The next ekf_measure whose association involves that landmark then queues its
  * launches from a prediction the device contradicts; every launch stays inside the state (a correction falls back to the predicted landmark,

@@ -82,6 +82,30 @@ classdef EKF_SLAM < handle
             if nargin < 5 || isempty(R), R = zeros(2); end
             [d2, S] = h.gateway('landmark_distance', double(i), double(j), double(delta(:)), double(R));
         end
+        function [d2, partner] = nearestLandmarks(h, R)
+            % For every landmark k its closest EARLIER landmark: partner(k) < k minimises landmarkDistance(k, partner(k), [0 0], R)
+            % and d2(k) is that minimum; partner(k) = 0 (and d2(k) = Inf) means none -- landmark 1, rows whose pairs are all
+            % singular.  The lowest number wins ties.  One read-only pass over P on the GPU; changes nothing.  A row reads as
+            % mergeLandmarks(partner(k), k, R); gate d2(k) with a chi-square value (2 degrees of freedom) first.
+            if nargin < 2 || isempty(R), R = zeros(2); end
+            [d2, partner] = h.gateway('nearest_landmarks', double(R));
+        end
+        function merges = fuseDuplicates(h, gate, R, maxMerges)
+            % The simplest complete fusion policy: search, merge the candidate with the smallest (d2, k) at or below the gate,
+            % search again -- until none is left or maxMerges merges were made.  merges: one row [keep drop d2] per fusion.
+            if nargin < 3 || isempty(R), R = zeros(2); end
+            if nargin < 4 || isempty(maxMerges), maxMerges = Inf; end
+            merges = zeros(0, 3);
+            while size(merges, 1) < maxMerges
+                [d2, partner] = h.nearestLandmarks(R);
+                k = find(partner > 0 & d2 <= gate);
+                if isempty(k), break; end
+                [~, q] = sortrows([d2(k), k]);
+                k = k(q(1));
+                h.mergeLandmarks(partner(k), k, R);
+                merges(end + 1, :) = [partner(k), k, d2(k)]; %#ok<AGROW>
+            end
+        end
         function B = covarianceBlock(h, r0, c0, nr, nc)   % P(r0:r0+nr-1, c0:c0+nc-1) without moving the rest of P
             B = ekfslam_mex('get_P_block', h.hnd, r0, c0, nr, nc);
         end

@@ -21,23 +21,26 @@
 #include "ekfslam.h"
 #include "mex.h"
 
-/* The map-editing entry points (ekf_remove_landmarks; ekf_constrain_landmarks, ekf_merge_landmarks, ekf_landmark_distance) are the
- * ones this gateway can live without: bound weakly, so that the gateway still links against a libekfslam (or a stand-in) that
+/* The map-editing entry points (ekf_remove_landmarks; ekf_constrain_landmarks, ekf_merge_landmarks, ekf_landmark_distance;
+ * ekf_nearest_landmarks) are the ones this gateway can live without: bound weakly, so that the gateway still links against a libekfslam (or a stand-in) that
  * predates them; their commands then raise a MATLAB error instead. */
 #if defined(__GNUC__)
 #pragma weak ekf_remove_landmarks
 #pragma weak ekf_constrain_landmarks
 #pragma weak ekf_merge_landmarks
 #pragma weak ekf_landmark_distance
+#pragma weak ekf_nearest_landmarks
 #define HAVE_REMOVE_LANDMARKS (ekf_remove_landmarks != 0)
 #define HAVE_CONSTRAIN_LANDMARKS (ekf_constrain_landmarks != 0)
 #define HAVE_MERGE_LANDMARKS (ekf_merge_landmarks != 0)
 #define HAVE_LANDMARK_DISTANCE (ekf_landmark_distance != 0)
+#define HAVE_NEAREST_LANDMARKS (ekf_nearest_landmarks != 0)
 #else
 #define HAVE_REMOVE_LANDMARKS 1
 #define HAVE_CONSTRAIN_LANDMARKS 1
 #define HAVE_MERGE_LANDMARKS 1
 #define HAVE_LANDMARK_DISTANCE 1
+#define HAVE_NEAREST_LANDMARKS 1
 #endif
 
 static void need(int nrhs, int want, const char *cmd) {
@@ -202,6 +205,23 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
         if (rc != EKF_OK) { mxDestroyArray(S); check(h, rc); }
         plhs[0] = mxCreateDoubleScalar(d2);
         if (nlhs > 1) plhs[1] = S; else mxDestroyArray(S);
+        return;
+    }
+    if (!strcmp(cmd, "nearest_landmarks")) {      /* [d2, partner] = (h, R 2x2): N x 1 each; partner 1-based, 0 = none */
+        need(nrhs, 3, cmd);
+        if (!HAVE_NEAREST_LANDMARKS) mexErrMsgIdAndTxt("ekfslam:usage", "nearest_landmarks: this libekfslam has no ekf_nearest_landmarks");
+        const double *R = r2x2_of(prhs[2], cmd);
+        const int64_t N = (nstate(h) - 3) / 2;
+        int64_t *p0 = (int64_t *)malloc((size_t)(N ? N : 1) * sizeof(int64_t));  /* freed before any MATLAB error can unwind */
+        if (!p0) mexErrMsgIdAndTxt("ekfslam:usage", "nearest_landmarks: out of memory");
+        mxArray *d2 = mxCreateDoubleMatrix((mwSize)N, 1, mxREAL), *partner = mxCreateDoubleMatrix((mwSize)N, 1, mxREAL);
+        const int32_t rc = ekf_nearest_landmarks(h, R, mxGetPr(d2), p0);
+        if (rc == EKF_OK)
+            for (int64_t i = 0; i < N; ++i) mxGetPr(partner)[i] = (double)(p0[i] + 1);       /* -1 (none) -> 0 */
+        free(p0);
+        if (rc != EKF_OK) { mxDestroyArray(d2); mxDestroyArray(partner); check(h, rc); }
+        plhs[0] = d2;
+        if (nlhs > 1) plhs[1] = partner; else mxDestroyArray(partner);
         return;
     }
     if (!strcmp(cmd, "measure")) {                /* (h, observed_LL m x 3, u, lm_index L x 1, lm_loc L x 2) */
