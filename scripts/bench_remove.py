@@ -28,7 +28,7 @@ import bench  # noqa: E402
 def traffic(N, T, w, first):
     """(bytes k_compact_tiles reads + writes, bytes the copy beside it reads + writes) for a removal whose lowest index is `first`:
     the kernel rewrites every tile from the first removed landmark's tile row on; the smaller of the untouched prefix and that
-    suffix is copied device to device (ekf_slam_amd/csrc/abi.hip: ekf_remove_landmarks)."""
+    suffix is copied device to device (ekf_slam_amd/csrc/host/edits.h: ekf_remove_landmarks)."""
     nt = (2 * N + T - 1) // T
     I0 = (2 * first) // T
     prefix = I0 * (I0 + 1) // 2

@@ -124,7 +124,7 @@ int main(int argc, char **argv) {
     const int pcap = std::max(64, npairs);
     TileMap tm = ekf_make_tilemap(T, 1, 0);
     tm.reverse = reverse;
-    // work list as abi.hip::refresh_work builds it: 8 x 8 super-tiles in row-major order, flattened, cut into 8 equal runs
+    // work list as host/passes.h::refresh_work builds it: 8 x 8 super-tiles in row-major order, flattened, cut into 8 equal runs
     std::vector<int2> flat;
     const int SS = 8;
     const int64_t ns = (nt + SS - 1) / SS;

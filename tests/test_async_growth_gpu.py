@@ -1,7 +1,7 @@
 """GPU: the asynchronous pass over P (cfg.async_flush) at a size where one pass lasts longer than a step, while streaming appends push
 the map across tile-row edges (configs[4]'s step: predict, append one landmark, correct).
 
-A tile-row crossing rebuilds the pass work lists (abi.hip: refresh_work).  A pass still in flight on the pass stream reads its work list
+A tile-row crossing rebuilds the pass work lists (csrc/host/passes.h: refresh_work).  A pass still in flight on the pass stream reads its work list
 for its whole lifetime, so a rebuild that overwrote the list it reads would make it skip some tiles and do others twice; a skipped tile
 keeps the values of two passes earlier, silently.  Each leg places four crossings 2 steps after a batch boundary and drives the
 asynchronous engine alone through the precomputed plan (the synchronous engine and the oracle run afterwards), so that the crossing's

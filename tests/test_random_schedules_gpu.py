@@ -49,7 +49,7 @@ class _Table:
 
 
 def _rccl_loads():
-    """Whether librccl loads under the names the library tries (abi.hip: rccl_load)."""
+    """Whether librccl loads under the names the library tries (csrc/host/exchange.h: rccl_load)."""
     for name in ("librccl.so.1", "librccl.so", "/opt/rocm/lib/librccl.so.1"):
         try:
             ctypes.CDLL(name, mode=ctypes.RTLD_GLOBAL)
