@@ -15,6 +15,7 @@ EKF_ERR_INVALID_ARG, EKF_ERR_NO_DEVICE, EKF_ERR_HIP, EKF_ERR_CAPACITY = 1, 2, 3,
 EKF_ERR_INDEX, EKF_ERR_LOOKUP, EKF_ERR_STATE, EKF_ERR_COMM = 5, 6, 7, 8
 EKF_MODE_KNOWN, EKF_MODE_UC = 0, 1
 EKF_COMM_ID_BYTES = 128
+EKF_MERGE_BATCH_MAX = 32
 EKF_STORE_F64, EKF_STORE_F32 = 0, 1
 EKF_ARITH_F64, EKF_ARITH_F32, EKF_ARITH_SPLIT3 = 0, 1, 2
 (EKF_KERNEL_DOWNDATE, EKF_KERNEL_GATHER, EKF_KERNEL_PREDICT, EKF_KERNEL_ASSOCIATE, EKF_KERNEL_APPEND,
@@ -81,6 +82,7 @@ SIGNATURES = {
     "ekf_remove_landmarks": (_i32, [_vp, ctypes.POINTER(_i64), _i64]),
     "ekf_constrain_landmarks": (_i32, [_vp, _i64, _i64, _dp, _dp]),
     "ekf_merge_landmarks": (_i32, [_vp, _i64, _i64, _dp]),
+    "ekf_merge_landmarks_batch": (_i32, [_vp, ctypes.POINTER(_i64), ctypes.POINTER(_i64), _i64, _dp, _dp]),
     "ekf_landmark_distance": (_i32, [_vp, _i64, _i64, _dp, _dp, _dp, _dp]),
     "ekf_nearest_landmarks": (_i32, [_vp, _dp, _dp, ctypes.POINTER(_i64)]),
     "ekf_diag_poke_device_signature": (_i32, [_vp, _i64, _d]),

@@ -198,6 +198,10 @@ struct ekf_handle {
     // ekf_nearest_landmarks: the N (d2, partner) entries k_nearest writes and the pinned area they are read back through (cap entries
     // each, allocated at the first search and kept; every search ends with a stream synchronisation, so the area is never busy)
     NearestEntry *d_nearest = nullptr, *h_nearest = nullptr;
+    // ekf_merge_landmarks_batch: its private pair ring (EKF_MERGE_BATCH_MAX F64 slots: G ring, then K ring), one record per constraint on
+    // the device and in pinned memory, the snapshot of x / strip / Prr / the diagonal blocks it restores when a pair is irregular
+    // (allocated at the first batch call and kept)
+    double *d_mring = nullptr, *d_mrec = nullptr, *h_mrec = nullptr, *d_msnap = nullptr;
     // ---- timers, what ekf_destroy releases, the error text ----
     KernelTimer timers[EKF_KERNEL_COUNT];
     std::vector<void *> allocs;       // device memory (dalloc), pinned memory (halloc) and events (new_event): what ekf_destroy releases

@@ -40,6 +40,7 @@ namespace {
 #include "state_io.h"         // dense <-> tiled, block reads, low-rank load, digest
 #include "compact.h"          // landmark removal: k_compact_tiles, k_compact_state
 #include "constrain.h"        // a constraint between two landmarks: k_constrain_probe, k_gather_constrain
+#include "merge_pass.h"       // the fused downdate-and-compact pass of a batch of merges: k_merge_pass
 #include "nearest.h"          // the candidate search in front of a merge: k_nearest
 
 }  // namespace
@@ -591,6 +592,23 @@ hipError_t launch_compact_state(const DevState &st, int cur, const int32_t *src_
     return hipGetLastError();
 }
 
+hipError_t launch_merge_pass(const DevState &st, void *dst, const int2 *work, int64_t ntiles, const int32_t *src_of, int npairs,
+                             int storage, hipStream_t s, char *kname) {
+    if (ntiles <= 0) return hipSuccess;
+    if (st.tiles == dst || !dst || !src_of || npairs < 0 || npairs > st.pcap || st.tm.world != 1) return hipErrorInvalidValue;      // out of place only
+    const int64_t pieces = (int64_t)st.tm.T * st.tm.T / (storage == 0 ? 2 : 4);
+    const int items = (int)cdiv(pieces, (int64_t)kBlock * kCompactRows);
+    const int64_t grid = ntiles * items;
+    if (grid > 0x7fffffff) return hipErrorInvalidValue;
+    EKF_STORAGE_DISPATCH(storage,
+        hipLaunchKernelGGL(k_merge_pass<double>, dim3((unsigned)grid), dim3(kBlock), 0, s, (const double *)st.tiles, (double *)dst, work, items, src_of,
+                           (const double *)st.Kp, (const double *)st.Gp, st.pair_stride, npairs, st.tm),
+        hipLaunchKernelGGL(k_merge_pass<float>, dim3((unsigned)grid), dim3(kBlock), 0, s, (const float *)st.tiles, (float *)dst, work, items, src_of,
+                           (const double *)st.Kp, (const double *)st.Gp, st.pair_stride, npairs, st.tm));
+    if (kname) snprintf(kname, 64, "k_merge_pass<%s,%d>", storage == 0 ? "double" : "float", st.tm.T);
+    return hipGetLastError();
+}
+
 static bool constrain_rows_ok(int64_t ai, int64_t aj, int64_t n_mm) {
     return ai >= 0 && aj >= 0 && ai + 1 < n_mm && aj + 1 < n_mm && (ai & 1) == 0 && (aj & 1) == 0 && ai != aj;
 }
@@ -609,6 +627,17 @@ hipError_t launch_gather_constrain(const DevState &st, const ConstrainArgs &a, i
     EKF_STORAGE_DISPATCH(storage,
         hipLaunchKernelGGL(k_gather_constrain<double>, dim3((unsigned)grid), dim3(kBlock), 0, s, st, a),
         hipLaunchKernelGGL(k_gather_constrain<float>, dim3((unsigned)grid), dim3(kBlock), 0, s, st, a));
+    return hipGetLastError();
+}
+
+hipError_t launch_gather_constrain_chain(const DevState &st, const ConstrainArgs &a, double *rec, int storage, hipStream_t s) {
+    if (!constrain_rows_ok(a.ai, a.aj, a.n_mm) || st.tm.padded(a.n_mm) > st.ldm || a.npend < 0 || a.npend >= st.pcap || a.pstart < 0 ||
+        a.pstart >= st.pcap || !rec || st.Gp32 || st.tm.world != 1)
+        return hipErrorInvalidValue;
+    const int64_t grid = cdiv(st.tm.padded(a.n_mm), kBlock);
+    EKF_STORAGE_DISPATCH(storage,
+        hipLaunchKernelGGL(k_gather_constrain_chain<double>, dim3((unsigned)grid), dim3(kBlock), 0, s, st, a, rec),
+        hipLaunchKernelGGL(k_gather_constrain_chain<float>, dim3((unsigned)grid), dim3(kBlock), 0, s, st, a, rec));
     return hipGetLastError();
 }
 

@@ -330,6 +330,26 @@ class Engine:
         _, Rf = self._delta_R(None, R)
         self._check(self.lib.ekf_merge_landmarks(self.h, int(keep), int(drop), None if Rf is None else _p(Rf)))
 
+    def merge_landmarks_batch(self, pairs, R=None):
+        """Fuse every (keep, drop) of `pairs` (0-based, at most EKF_MERGE_BATCH_MAX, numbering before the call) in one call: what
+        constrain_landmarks(keep, drop, None, R) pair by pair in list order, then ONE remove_landmarks(all drops) would leave -- m
+        chained gathers and one fused downdate-and-compact pass on the device.  A keep may be shared; no keep may be dropped.
+        Returns d2[k], the distance landmark_distance(keep_k, drop_k, None, R) would report just before constraint k
+        (ekf_merge_landmarks_batch)."""
+        rows = [tuple(p) for p in pairs]
+        if any(len(p) != 2 for p in rows):
+            raise ValueError("merge_landmarks_batch: pairs are (keep, drop)")
+        v = np.asarray(rows, dtype=np.float64).reshape(-1, 2)
+        if not np.all(v == np.floor(v)):
+            raise ValueError("merge_landmarks_batch: landmark indices are whole numbers")
+        m = v.shape[0]
+        keep = (ctypes.c_int64 * max(m, 1))(*[int(a) for a in v[:, 0]])
+        drop = (ctypes.c_int64 * max(m, 1))(*[int(a) for a in v[:, 1]])
+        _, Rf = self._delta_R(None, R)
+        d2 = np.empty(max(m, 1))
+        self._check(self.lib.ekf_merge_landmarks_batch(self.h, keep, drop, m, None if Rf is None else _p(Rf), _p(d2)))
+        return d2[:m]
+
     def landmark_distance(self, i, j, delta=None, R=None):
         """(d2, S): the squared Mahalanobis distance nu' S^-1 nu of 'l_i - l_j = delta' under the current state and its 2 x 2
         innovation covariance -- what a caller gates a merge on.  Changes nothing (ekf_landmark_distance)."""

@@ -31,6 +31,23 @@ from .world import SyntheticLandmark
 _DEFAULT_CAPACITY = 1024
 
 
+def select_merge_batch(candidates, limit):
+    """The pairs of ONE search that one merge_landmarks_batch call can take: walk the (i, j, d2) rows of duplicate_candidates in
+    their (d2, i) order and accept (keep = j, drop = i) when i is not yet a keep or a drop and j is not yet a drop -- a keep may be
+    shared, so a triple fuses in one batch; a row whose partner was just dropped waits for the next search.  Stops at `limit`
+    pairs.  Returns [(keep, drop, d2)] with the candidates' d2.  A pure function: no engine involved."""
+    keeps, drops, out = set(), set(), []
+    for i, j, d2 in candidates:
+        if len(out) >= limit:
+            break
+        if i in keeps or i in drops or j in drops:
+            continue
+        keeps.add(j)
+        drops.add(i)
+        out.append((j, i, d2))
+    return out
+
+
 class _EkfBase:
     _mode = "known"
 
@@ -163,6 +180,21 @@ class _EkfBase:
         if self.log is not None:
             self.log.record_edit("merge", [keep, drop], None, R)
 
+    def merge_landmarks_batch(self, pairs, R=None):
+        """Fuse every (keep, drop) of `pairs` (1-based numbers as they are before the call, at most EKF_MERGE_BATCH_MAX pairs) in one
+        call: constrain_landmarks(keep, drop, None, R) pair by pair in list order, then ONE remove_landmarks(all drops) -- the same
+        bits with F64 tiles, one rounding instead of m with float tiles, and one pass over P instead of 2 m.  A keep may be shared;
+        no keep may be dropped.  Returns d2[k] as landmark_distance(keep_k, drop_k, None, R) would report it just before
+        constraint k (ekf_merge_landmarks_batch).  The reference has no such method."""
+        rows = [tuple(p) for p in pairs]
+        if any(len(p) != 2 for p in rows):
+            raise ValueError("merge_landmarks_batch: pairs are (keep, drop)")
+        flat = self._landmark_numbers("merge_landmarks_batch", *[a for p in rows for a in p])
+        d2 = self._e.merge_landmarks_batch([(flat[2 * k] - 1, flat[2 * k + 1] - 1) for k in range(len(rows))], R)
+        if self.log is not None and rows:
+            self.log.record_edit("merge_batch", flat, None, R)
+        return d2
+
     def landmark_distance(self, i, j, delta=None, R=None):
         """(d2, S) of 'landmark i minus landmark j = delta' under the current state (1-based): the squared Mahalanobis distance
         and the 2 x 2 innovation covariance.  Changes nothing (ekf_landmark_distance)."""
@@ -196,6 +228,22 @@ class _EkfBase:
             i, j, d2 = cand[0]
             self.merge_landmarks(j, i, R)
             merges.append((j, i, d2))
+        return merges
+
+    def fuse_duplicates_batched(self, gate, R=None, max_merges=None):
+        """fuse_duplicates with the pairs of one search fused in ONE call: repeat { search; select_merge_batch; one
+        merge_landmarks_batch } until no candidate is left or `max_merges` merges were made -- a different policy from
+        fuse_duplicates, which searches again after every merge: here the later pairs of a batch were gated on the state before the
+        batch, and the d2 returned is the one the batch call reported (under the state after the batch's earlier pairs).
+        Returns [(keep, drop, d2)], 1-based numbers as they were when their batch was made."""
+        merges = []
+        while max_merges is None or len(merges) < max_merges:
+            limit = L.EKF_MERGE_BATCH_MAX if max_merges is None else min(L.EKF_MERGE_BATCH_MAX, max_merges - len(merges))
+            batch = select_merge_batch(self.duplicate_candidates(gate, R), limit)
+            if not batch:
+                break
+            d2 = self.merge_landmarks_batch([(k, d) for k, d, _ in batch], R)
+            merges.extend((k, d, float(v)) for (k, d, _), v in zip(batch, d2))
         return merges
 
     def _push_params(self):

@@ -9,13 +9,16 @@ another (or with the CPU oracle).  Format: one .npz with ragged arrays (`*_ptr` 
 A map that can be edited (remove_landmarks / constrain_landmarks / merge_landmarks of ekf_slam_amd/slam.py) needs its edits in the
 log too, or a replay no longer reproduces the run: `record_edit` notes one, with the 1-based landmark numbers that layer consumed,
 at the position `len(log)` it was made at -- it is replayed after step len(log) - 1 and before step len(log).  A log without edits
-is written exactly as before (format 1, the same arrays); one with edits as format 2, with the edit arrays added.
+is written exactly as before (format 1, the same arrays); one with edits as format 2, with the edit arrays added; one that holds a
+'merge_batch' edit (merge_landmarks_batch: idx = [keep1, drop1, keep2, drop2, ...], R shared) as format 3, which has the arrays of
+format 2 -- a reader of format 2 alone would not know the fourth kind.
 """
 import numpy as np
 
 FORMAT = "ekfslam-trajectory-1"
 FORMAT_EDITS = "ekfslam-trajectory-2"
-EDIT_KINDS = ("remove", "constrain", "merge")
+FORMAT_BATCH = "ekfslam-trajectory-3"
+EDIT_KINDS = ("remove", "constrain", "merge", "merge_batch")
 
 
 class TrajectoryLog:
@@ -35,13 +38,17 @@ class TrajectoryLog:
 
     def record_edit(self, kind, idx, delta=None, R=None):
         """A map edit made now, i.e. after the len(self) steps recorded so far.  kind: 'remove' (idx: the landmarks), 'constrain'
-        (idx: [i, j]) or 'merge' (idx: [keep, drop]); landmark numbers 1-based; delta None: (0, 0), R None: the zero matrix."""
+        (idx: [i, j]), 'merge' (idx: [keep, drop]) or 'merge_batch' (idx: [keep1, drop1, keep2, drop2, ...], non-empty; R shared by
+        all pairs); landmark numbers 1-based; delta None: (0, 0), R None: the zero matrix."""
         if kind not in EDIT_KINDS:
             raise ValueError("record_edit: kind is one of %s" % (EDIT_KINDS,))
         idx = np.asarray(idx, dtype=np.float64).reshape(-1)
         if not np.all(idx == np.floor(idx)):
             raise ValueError("record_edit: landmark indices are whole numbers")
-        if kind != "remove" and idx.size != 2:
+        if kind == "merge_batch":
+            if idx.size == 0 or idx.size % 2:
+                raise ValueError("record_edit: 'merge_batch' names (keep, drop) pairs, at least one")
+        elif kind != "remove" and idx.size != 2:
             raise ValueError("record_edit: '%s' names two landmarks" % kind)
         d = np.zeros(2) if delta is None else np.asarray(delta, dtype=np.float64).reshape(2).copy()
         Rm = np.zeros((2, 2)) if R is None else np.asarray(R, dtype=np.float64).reshape(2, 2).copy()
@@ -60,7 +67,8 @@ class TrajectoryLog:
             np.savez_compressed(path, format=np.array(FORMAT), **arrays)
             return
         e_ptr, e_idx = ragged([e[2] for e in self.edits], 0)
-        np.savez_compressed(path, format=np.array(FORMAT_EDITS), edit_step=np.array([e[0] for e in self.edits], dtype=np.int64),
+        fmt = FORMAT_BATCH if any(e[1] == "merge_batch" for e in self.edits) else FORMAT_EDITS
+        np.savez_compressed(path, format=np.array(fmt), edit_step=np.array([e[0] for e in self.edits], dtype=np.int64),
                             edit_kind=np.array([EDIT_KINDS.index(e[1]) for e in self.edits], dtype=np.int64), edit_ptr=e_ptr,
                             edit_idx=e_idx.astype(np.int64), edit_delta=np.array([e[3] for e in self.edits]).reshape(-1, 2),
                             edit_R=np.array([e[4] for e in self.edits]).reshape(-1, 2, 2), **arrays)
@@ -69,14 +77,14 @@ class TrajectoryLog:
     def load(path):
         g = np.load(path, allow_pickle=False)
         fmt = str(g["format"])
-        if fmt not in (FORMAT, FORMAT_EDITS):
-            raise ValueError("not an %s / %s file" % (FORMAT, FORMAT_EDITS))
+        if fmt not in (FORMAT, FORMAT_EDITS, FORMAT_BATCH):
+            raise ValueError("not an %s / %s / %s file" % (FORMAT, FORMAT_EDITS, FORMAT_BATCH))
         t = TrajectoryLog()
         for k in range(len(g["u"])):
             a, b = g["obs_ptr"][k], g["obs_ptr"][k + 1]
             c, d = g["lm_ptr"][k], g["lm_ptr"][k + 1]
             t.record(g["u"][k], g["obs"][a:b], g["lm_index"][c:d], g["lm_loc"][c:d])
-        if fmt == FORMAT_EDITS:
+        if fmt != FORMAT:
             for q in range(len(g["edit_step"])):
                 a, b = g["edit_ptr"][q], g["edit_ptr"][q + 1]
                 t.edits.append((int(g["edit_step"][q]), EDIT_KINDS[int(g["edit_kind"][q])], g["edit_idx"][a:b].astype(np.int64),
@@ -86,7 +94,7 @@ class TrajectoryLog:
     def replay(self, engine, start=0, stop=None):
         """predict + measure for steps [start, stop) on anything with predict(u) / measure(obs, u, idx, loc) -- an Engine.  The edits
         recorded at positions [start, stop) are applied in front of their step through the engine's remove_landmarks /
-        constrain_landmarks / merge_landmarks (0-based there: the recorded 1-based numbers are converted here); the ones recorded
+        constrain_landmarks / merge_landmarks / merge_landmarks_batch (0-based there: the recorded 1-based numbers are converted here); the ones recorded
         at position len(self), after the last step, when stop is the end of the log."""
         stop = len(self) if stop is None else stop
 
@@ -99,8 +107,10 @@ class TrajectoryLog:
                     engine.remove_landmarks(idx0)
                 elif kind == "constrain":
                     engine.constrain_landmarks(idx0[0], idx0[1], delta, R)
-                else:
+                elif kind == "merge":
                     engine.merge_landmarks(idx0[0], idx0[1], R)
+                else:
+                    engine.merge_landmarks_batch(list(zip(idx0[0::2], idx0[1::2])), R)
 
         for k in range(start, stop):
             apply_edits(k)

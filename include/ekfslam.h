@@ -302,6 +302,32 @@ int32_t ekf_constrain_landmarks(ekf_handle *h, int64_t i, int64_t j, const doubl
  * survivors keep their order, and keep's index afterwards is keep - (drop < keep).  WHICH pairs to merge is the caller's policy
  * (ekf_landmark_distance is the gate). */
 int32_t ekf_merge_landmarks(ekf_handle *h, int64_t keep, int64_t drop, const double R[4]);
+/* Fuse the m pairs ONE search yields (ekf_nearest_landmarks) in one call: the state is left as
+ *   ekf_constrain_landmarks(h, keep[k], drop[k], NULL, R) for k = 0 .. m-1, in list order, followed by ONE ekf_remove_landmarks(h, drop, m)
+ * would leave it -- all indices 0-based in the numbering BEFORE the call, R (2 x 2, column-major, NULL = zero) shared by all pairs.
+ * d2[k] (d2 may be NULL) is what ekf_landmark_distance(h, keep[k], drop[k], NULL, R, ..) would report immediately before constraint k,
+ * i.e. under the state after constraints 0 .. k-1.  Afterwards N is N - m, the survivors keep their order and signatures, and keep[k]
+ * has become keep[k] - #{drop < keep[k]}.  A keep may be shared by several pairs (a triple fuses in one call).
+ * With F64 tiles ekf_get_x / _s / _P / _P_diag_blocks, ekf_P_digest and d2 return the SAME BITS as that sequence of calls; with float
+ * tiles every float-stored entry is rounded ONCE where the sequence rounds it m times: equal within the float tolerance and closer to
+ * the F64 result (what cfg.batch says of corrections).  The unread upper halves of diagonal tiles mirror the canonical entries.
+ * On the device: m constraint gathers queued back to back, each reading its operands patched with the earlier pairs of the batch (a
+ * private F64 pair ring of EKF_MERGE_BATCH_MAX slots, allocated at the first batch call and kept: cfg.batch and ekf_pending are not
+ * involved), one readback of their m records, then ONE pass that applies the m pairs while it compacts the tile store out of place
+ * (one read and one write of P) -- counted under EKF_KERNEL_GATHER (m launches) and EKF_KERNEL_DOWNDATE (one), none under
+ * EKF_KERNEL_COMPACT.  A synchronising call like ekf_constrain_landmarks; ekf_pending reports 0 afterwards.
+ * Refused before anything changes, in ekf_constrain_landmarks' order: m < 0, m > EKF_MERGE_BATCH_MAX, keep or drop NULL with m > 0,
+ * keep[k] == drop[k], a landmark named twice in drop, a keep that is also a drop (every keep survives: chains are the caller's to order),
+ * an R that ekf_constrain_landmarks would refuse, a handle with world > 1 (EKF_ERR_INVALID_ARG; sharding is not built, a lone shard with
+ * cfg.force_sharded works); a sharded correction between begin and finish (EKF_ERR_STATE); an index outside [0, N) (EKF_ERR_INDEX);
+ * a failed allocation (EKF_ERR_HIP).  m == 0: EKF_OK, nothing happens.
+ * ALL OR NOTHING: if constraint k meets an S that ekf_constrain_landmarks would refuse (not finite, S00 <= 0 or det S <= 0) the call
+ * returns EKF_ERR_STATE, ekf_last_error names the pair number k, and x, s, P, the diagonal blocks and the digest are bit for bit what the
+ * getters reported before the call (d2 is not written); the handle goes on working. */
+#define EKF_MERGE_BATCH_MAX 32
+int32_t ekf_merge_landmarks_batch(ekf_handle *h, const int64_t *keep, const int64_t *drop, int64_t m,
+                                  const double R[4] /* 2x2 column-major, NULL = zero, shared by all pairs */,
+                                  double *d2 /* m, may be NULL */);
 /* What a caller gates a merge on: *d2 = nu' S^-1 nu, the squared Mahalanobis distance of "l_i - l_j = delta" under the current state
  * (arguments, synchronisation and refusals as for ekf_constrain_landmarks), and S (2 x 2, column-major; may be NULL).  Changes nothing:
  * x, s, P and ekf_P_digest are afterwards what they were.  A singular S is no error here: it is returned, and *d2 is NaN. */

@@ -106,6 +106,40 @@ classdef EKF_SLAM < handle
                 merges(end + 1, :) = [partner(k), k, d2(k)]; %#ok<AGROW>
             end
         end
+        function d2 = mergeLandmarksBatch(h, pairs, R)
+            % Fuse every row [keep drop] of pairs (k x 2, 1-based numbers as they are before the call, k <= 32) in ONE call: what
+            % constrainLandmarks(keep, drop, [0 0], R) row by row, then one removeLandmarks(all drops) would leave -- k gathers and
+            % one pass over P on the GPU instead of 2 k passes.  A keep may be shared by several rows; no keep may be dropped.
+            % d2(r): landmarkDistance(keep_r, drop_r, [0 0], R) as it is just before row r is applied.
+            if nargin < 3 || isempty(R), R = zeros(2); end
+            d2 = h.gateway('merge_landmarks_batch', double(reshape(pairs, [], 2)), double(R));
+        end
+        function merges = fuseDuplicatesBatched(h, gate, R, maxMerges)
+            % fuseDuplicates with the pairs of one search fused in one mergeLandmarksBatch call: search; walk the candidates in
+            % (d2, k) order and take [partner(k) k] when k is not yet a keep or a drop and partner(k) is not yet a drop (a keep may
+            % be shared); one batch; search again -- until no candidate is left or maxMerges merges were made.
+            % merges: one row [keep drop d2] per fusion, d2 as the batch call reported it.
+            if nargin < 3 || isempty(R), R = zeros(2); end
+            if nargin < 4 || isempty(maxMerges), maxMerges = Inf; end
+            merges = zeros(0, 3);
+            while size(merges, 1) < maxMerges
+                [d2, partner] = h.nearestLandmarks(R);
+                k = find(partner > 0 & d2 <= gate);
+                if isempty(k), break; end
+                [~, q] = sortrows([d2(k), k]);
+                k = k(q);
+                limit = min(32, maxMerges - size(merges, 1));
+                pairs = zeros(0, 2);
+                for r = 1:numel(k)
+                    if size(pairs, 1) >= limit, break; end
+                    i = k(r); j = partner(i);
+                    if any(pairs(:) == i) || any(pairs(:, 2) == j), continue; end
+                    pairs(end + 1, :) = [j, i]; %#ok<AGROW>
+                end
+                dd = h.mergeLandmarksBatch(pairs, R);
+                merges = [merges; pairs, dd(:)]; %#ok<AGROW>
+            end
+        end
         function B = covarianceBlock(h, r0, c0, nr, nc)   % P(r0:r0+nr-1, c0:c0+nc-1) without moving the rest of P
             B = ekfslam_mex('get_P_block', h.hnd, r0, c0, nr, nc);
         end

@@ -22,7 +22,7 @@
 #include "mex.h"
 
 /* The map-editing entry points (ekf_remove_landmarks; ekf_constrain_landmarks, ekf_merge_landmarks, ekf_landmark_distance;
- * ekf_nearest_landmarks) are the ones this gateway can live without: bound weakly, so that the gateway still links against a libekfslam (or a stand-in) that
+ * ekf_nearest_landmarks; ekf_merge_landmarks_batch) are the ones this gateway can live without: bound weakly, so that the gateway still links against a libekfslam (or a stand-in) that
  * predates them; their commands then raise a MATLAB error instead. */
 #if defined(__GNUC__)
 #pragma weak ekf_remove_landmarks
@@ -30,17 +30,20 @@
 #pragma weak ekf_merge_landmarks
 #pragma weak ekf_landmark_distance
 #pragma weak ekf_nearest_landmarks
+#pragma weak ekf_merge_landmarks_batch
 #define HAVE_REMOVE_LANDMARKS (ekf_remove_landmarks != 0)
 #define HAVE_CONSTRAIN_LANDMARKS (ekf_constrain_landmarks != 0)
 #define HAVE_MERGE_LANDMARKS (ekf_merge_landmarks != 0)
 #define HAVE_LANDMARK_DISTANCE (ekf_landmark_distance != 0)
 #define HAVE_NEAREST_LANDMARKS (ekf_nearest_landmarks != 0)
+#define HAVE_MERGE_LANDMARKS_BATCH (ekf_merge_landmarks_batch != 0)
 #else
 #define HAVE_REMOVE_LANDMARKS 1
 #define HAVE_CONSTRAIN_LANDMARKS 1
 #define HAVE_MERGE_LANDMARKS 1
 #define HAVE_LANDMARK_DISTANCE 1
 #define HAVE_NEAREST_LANDMARKS 1
+#define HAVE_MERGE_LANDMARKS_BATCH 1
 #endif
 
 static void need(int nrhs, int want, const char *cmd) {
@@ -222,6 +225,31 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
         if (rc != EKF_OK) { mxDestroyArray(d2); mxDestroyArray(partner); check(h, rc); }
         plhs[0] = d2;
         if (nlhs > 1) plhs[1] = partner; else mxDestroyArray(partner);
+        return;
+    }
+    if (!strcmp(cmd, "merge_landmarks_batch")) {  /* d2 = (h, pairs k x 2 [keep drop], R 2x2): k x 1; landmark numbers 1-based, as they are before the call */
+        need(nrhs, 4, cmd);
+        if (!HAVE_MERGE_LANDMARKS_BATCH) mexErrMsgIdAndTxt("ekfslam:usage", "merge_landmarks_batch: this libekfslam has no ekf_merge_landmarks_batch");
+        if (!prhs[2] || mxGetN(prhs[2]) != 2 || mxGetNumberOfElements(prhs[2]) != 2 * mxGetM(prhs[2]) || (mxGetM(prhs[2]) && !mxGetPr(prhs[2])))
+            mexErrMsgIdAndTxt("ekfslam:usage", "merge_landmarks_batch: pairs needs k x 2 elements [keep drop]");
+        const mwSize k = mxGetM(prhs[2]);
+        if (k > EKF_MERGE_BATCH_MAX) mexErrMsgIdAndTxt("ekfslam:usage", "merge_landmarks_batch: at most %d pairs in one call", EKF_MERGE_BATCH_MAX);
+        const double *R = r2x2_of(prhs[3], cmd);
+        int64_t keep0[EKF_MERGE_BATCH_MAX], drop0[EKF_MERGE_BATCH_MAX];
+        if (mxGetClassID(prhs[2]) != mxDOUBLE_CLASS) mexErrMsgIdAndTxt("ekfslam:usage", "merge_landmarks_batch: pairs must be of class double");
+        for (mwSize i = 0; i < 2 * k; ++i) {                   /* whole numbers a landmark could carry: the cast below is then exact */
+            const double v = mxGetPr(prhs[2])[i];
+            if (!(v >= -9.0e15 && v <= 9.0e15) || v != (double)(int64_t)v)
+                mexErrMsgIdAndTxt("ekfslam:usage", "merge_landmarks_batch: landmark numbers are whole numbers");
+        }
+        for (mwSize i = 0; i < k; ++i) {                       /* column-major: keeps, then drops; 1-based -> 0-based, once */
+            keep0[i] = (int64_t)mxGetPr(prhs[2])[i] - 1;
+            drop0[i] = (int64_t)mxGetPr(prhs[2])[k + i] - 1;
+        }
+        mxArray *d2 = mxCreateDoubleMatrix(k, 1, mxREAL);
+        const int32_t rc = ekf_merge_landmarks_batch(h, keep0, drop0, (int64_t)k, R, mxGetPr(d2));
+        if (rc != EKF_OK) { mxDestroyArray(d2); check(h, rc); }
+        plhs[0] = d2;
         return;
     }
     if (!strcmp(cmd, "measure")) {                /* (h, observed_LL m x 3, u, lm_index L x 1, lm_loc L x 2) */
