@@ -1,5 +1,5 @@
 // The pass over float tiles with the rank-2m product on the f32 matrix pipe, one work item per workgroup (3 to 28 pending pairs;
-// from 29 on: flush32_pipe.h).  Included by kernels.hip (inside its anonymous namespace's scope of helpers) and by
+// from 29 on: flush32_pipe.h).  Included by kernels.hip (at file scope, in front of the kernel fragments) and by
 // scripts/probes/flush32_bench.hip.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -16,6 +16,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <algorithm>
+#include <vector>
+
 #include "layout.h"
 
 namespace ekf_pipe32 {
@@ -64,6 +67,35 @@ struct StripItem { int64_t toff; int krow0, gcol0; };      // krow0 < 0: none  (
 inline int4 strip_entry(const TileMap &tm, int I, int J, int slab, int cpart) {
     const int64_t toff = tm.tile_offset(I, J) + (int64_t)(slab * kItem) * 256 + cpart * kItem;
     return make_int4((int)(uint32_t)(toff & 0xffffffffll), (int)(uint32_t)((uint64_t)toff >> 32), I * 256 + slab * kItem, J * 256 + cpart * kItem);
+}
+
+// Strip work list of the owned lower-triangle tiles of nt tile rows (host side): column ranges of kSeg consecutive OWNED 128-column items;
+// within a range the 128-row slabs from the diagonal down, each a segment of up to kSeg items; the segments, in that order, cut into 8
+// equal contiguous runs (the CUs of an XCD then work on the same column range -- the same G -- at the same time) and interleaved run by
+// run; padded with empty segments to a multiple of 8.  Returns the segment count and fills `out` with nsegs * kSeg entries.
+inline int64_t build_strip_segments(const TileMap &tm, int64_t nt, std::vector<int4> &out) {
+    constexpr int L = kSeg;
+    std::vector<std::vector<int4>> segs;
+    const int64_t ncj = 2 * nt, step = (int64_t)L * tm.world;            // a row owns every world-th tile of a range: ~L owned items per range
+    for (int64_t c0 = 0; c0 < ncj; c0 += step)
+        for (int64_t rs = 0; rs < 2 * nt; ++rs) {
+            const int64_t I = rs >> 1, cmax = 2 * I + 1;
+            if (cmax < c0) continue;
+            std::vector<int4> sg;
+            for (int64_t cj = c0; cj < c0 + step && cj <= cmax; ++cj) {
+                if (!tm.mine(I, cj >> 1)) continue;
+                sg.push_back(strip_entry(tm, (int)I, (int)(cj >> 1), (int)(rs & 1), (int)(cj & 1)));
+                if ((int)sg.size() == L) { segs.push_back(sg); sg.clear(); }
+            }
+            if (!sg.empty()) segs.push_back(sg);
+        }
+    const size_t ns = segs.size(), per = (ns + 7) / 8;
+    out.assign(per * 8 * L, make_int4(0, 0, -1, -1));
+    for (int x = 0; x < 8; ++x) {
+        const size_t lo = ns * x / 8, hi = ns * (x + 1) / 8;
+        for (size_t q = lo; q < hi; ++q) std::copy(segs[q].begin(), segs[q].end(), out.begin() + ((q - lo) * 8 + x) * L);
+    }
+    return (int64_t)(per * 8);
 }
 
 // kS: stages of eight pairs per item = ceil(npairs / 8) (a template parameter: the k-step loop is unrolled, see the tile traffic below)

@@ -1,4 +1,4 @@
-// Fragment of kernels.hip (included there, at file scope): the batched pass on the f64 matrix cores, k_flush_mfma (EKF_SLAM.m:145, m corrections at once).
+// Fragment of kernels.hip (included there at file scope, beside the other pass kernels, after flush32_mfma.h): the batched pass on the f64 matrix cores, k_flush_mfma (EKF_SLAM.m:145, m corrections at once).
 #pragma once
 
 // Batched flush on the matrix cores (f64 tiles, T = 128) -- the production flush for two or more pending pairs.
@@ -17,7 +17,7 @@
 typedef double d4_t __attribute__((ext_vector_type(4)));
 
 // Work items: 64 rows x kCols columns -- kCols = 64 (4 accumulator blocks per wavefront, five wavefronts per SIMD) up to 12 pairs, 128 beyond
-// (launch_flush_mfma).  Two chunk sizes for the 128-column items: chunks of 4 pairs fit 4 wavefronts per SIMD (122 VGPRs) and win up to ~30 pairs (28 pairs: 0.603 vs 0.634 ms; 32: 0.651 vs 0.627), where the pass is
+// (launch/pass_select.h).  Two chunk sizes for the 128-column items: chunks of 4 pairs fit 4 wavefronts per SIMD (122 VGPRs) and win up to ~30 pairs (28 pairs: 0.603 vs 0.634 ms; 32: 0.651 vs 0.627), where the pass is
 // HBM-bound and occupancy hides the tile latency; chunks of 8 pairs (3 wavefronts per SIMD, half the barriers) win beyond,
 // where the f64 MFMA rate (measured 44-48 TFLOP/s, scripts/probes/mfma_f64_rate.hip) is the limit.
 // Storage: f64 tiles with T = 128 (a work item = 64 rows x the 128 columns of a tile) and f32 tiles with T = 256 (a work item

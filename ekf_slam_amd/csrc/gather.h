@@ -495,7 +495,7 @@ __global__ __launch_bounds__(kGatherBlock) void k_gather(DevState st, CorrectArg
     {
         // unconditional, clamped addresses (a predicated form lets the compiler sink the loads below the barrier, next to their
         // use); slots past npend repeat the last pending one (cache hits), c is clamped into the padded vector
-        // One uniform base (Gp; Kp follows it in the same allocation, abi.hip) + a 32-bit per-lane element offset: the
+        // One uniform base (Gp; Kp follows it in the same allocation, host/passes.h: create_passes) + a 32-bit per-lane element offset: the
         // compiler can then use the scalar-base addressing form and the 32 loads cost one scalar add each.
         const uint32_t cc = (uint32_t)(c < pad_cols ? c : pad_cols - 1);
         const uint32_t krel = (uint32_t)((st.Kp - st.Gp) >> 1);

@@ -127,6 +127,8 @@ int32_t ekf_remove_landmarks(ekf_handle *h, const int64_t *idx, int64_t m) {
     }
     return removal_finish(h, rm, N_old);
 }
+}  // extern "C"
+
 namespace {
 // The three entry points of a constraint between two landmarks (kernels.h: ConstrainArgs) share everything up to
 // the point where S = G H' + R and nu are on the host: `apply == false` (ekf_landmark_distance) stops there.
@@ -174,6 +176,7 @@ int32_t constrain_impl(ekf_handle *h, const char *name, int64_t i, int64_t j, co
 }
 }  // namespace
 
+extern "C" {
 int32_t ekf_constrain_landmarks(ekf_handle *h, int64_t i, int64_t j, const double delta[2], const double R[4]) {
     if (!h) return EKF_ERR_INVALID_ARG;
     return constrain_impl(h, "constrain_landmarks", i, j, delta, R, /*apply*/ true, nullptr, nullptr);
@@ -190,6 +193,8 @@ int32_t ekf_landmark_distance(ekf_handle *h, int64_t i, int64_t j, const double 
     if (!d2) return fail(h, EKF_ERR_INVALID_ARG, "landmark_distance: null d2");
     return constrain_impl(h, "landmark_distance", i, j, delta, R, /*apply*/ false, d2, S);
 }
+
+}  // extern "C"
 
 namespace {
 // ekf_merge_landmarks_batch, its own buffers (allocated at the first batch call and kept, as the second tile store is): the PRIVATE pair
@@ -237,6 +242,7 @@ int32_t merge_chain(ekf_handle *h, DevState &st, int &cur, const int64_t *keep, 
 }
 }  // namespace
 
+extern "C" {
 // Order as in constrain_impl: arguments -> the rungs, with the indices checked once N is exact -> every allocation -> the chain of m
 // constraint gathers (nothing waits in between) -> their records -> the fused downdate-and-compact pass -> the rest of a removal.
 int32_t ekf_merge_landmarks_batch(ekf_handle *h, const int64_t *keep, const int64_t *drop, int64_t m, const double R[4], double *d2) {

@@ -71,7 +71,7 @@ int32_t refresh_work(ekf_handle *h) {
     ws.xcd_len = (int64_t)len;
     if (ws.segs) {                                    // the strip work list of the same tiles
         std::vector<int4> sg;
-        const int64_t nsegs = build_strip_segments(h->st.tm, nt, sg);
+        const int64_t nsegs = ekf_pipe32::build_strip_segments(h->st.tm, nt, sg);
         REQUIRE(h, (int64_t)sg.size() <= h->segs_cap, EKF_ERR_STATE, "strip work list overflow");
         if (!sg.empty()) {
             std::copy(sg.begin(), sg.end(), segs);
@@ -92,6 +92,17 @@ const PassAux *pass_aux(const ekf_handle *h, const ekf_handle::WorkSet &ws, Pass
     out = h->aux;
     out.segs = ws.segs; out.nsegs = ws.nsegs; out.cols = ws.cols;
     return &out;
+}
+
+// the pass that applies ALL pending pairs over the work set `ws` into the tile store `dst` (ax: storage for the strip form's arguments)
+PassJob pass_job(const ekf_handle *h, const ekf_handle::WorkSet &ws, void *dst, PassAux &ax) {
+    PassJob job = {};
+    job.dst = dst;
+    job.work = ws.work; job.nwork = ws.nwork; job.work_xcd = ws.xcd; job.xcd_len = ws.xcd_len;
+    job.pstart = h->pstart; job.npairs = h->npend;
+    job.grid_cap = h->grid_cap; job.arith = h->cfg.pass_arith;
+    job.aux = pass_aux(h, ws, ax);
+    return job;
 }
 
 // ekf_create, the work lists' part: both sets at capacity (after create_passes: the strip form's lists only where it exists)
@@ -210,9 +221,9 @@ int32_t flush_pending(ekf_handle *h, bool batch_done = false) {
         TimedLaunch tl(h, EKF_KERNEL_DOWNDATE);
         const ekf_handle::WorkSet &ws = h->ws[h->ws_cur];     // (in place, on the main stream: ordered after its upload)
         PassAux ax;
-        HIPCHK(h, launch_downdate(h->st, h->st.tiles, ws.work, ws.nwork, ws.xcd, ws.xcd_len, h->pstart, h->npend,
-                                  h->storage, h->grid_cap, h->stream, h->dd_kernel, nx.j >= 0 ? &nx : nullptr, &extracted, h->cfg.pass_arith,
-                                  pass_aux(h, ws, ax)));
+        PassJob job = pass_job(h, ws, h->st.tiles, ax);
+        job.nx = nx.j >= 0 ? &nx : nullptr;
+        HIPCHK(h, launch_downdate(h->st, job, h->storage, h->stream, h->dd_kernel, &extracted));
         h->dd_pairs = h->npend;
     }
     h->npend = 0;
@@ -244,9 +255,7 @@ int32_t batch_complete(ekf_handle *h) {
         next_pass_direction(h);
         const ekf_handle::WorkSet &ws = h->ws[h->ws_cur];
         PassAux ax;
-        HIPCHK(h, launch_downdate(h->st, h->tilebuf[h->base ^ 1], ws.work, ws.nwork, ws.xcd, ws.xcd_len, h->pstart,
-                                  h->npend, h->storage, h->grid_cap, h->flush_stream, h->dd_kernel, nullptr, nullptr, h->cfg.pass_arith,
-                                  pass_aux(h, ws, ax)));
+        HIPCHK(h, launch_downdate(h->st, pass_job(h, ws, h->tilebuf[h->base ^ 1], ax), h->storage, h->flush_stream, h->dd_kernel));
         h->dd_pairs = h->npend;
     }
     HIPCHK(h, hipEventRecord(h->ev_flushed, h->flush_stream));

@@ -140,6 +140,8 @@ int32_t ekf_load_lowrank_state(ekf_handle *h, int64_t N, const double *x, const 
     if (e == hipSuccess) e = launch_lowrank(h->st, h->cur, 2 * N, h->ws[h->ws_cur].work, h->ws[h->ws_cur].nwork, dd, dU, k, h->storage, h->stream);
     return synced(h, e, "load_lowrank_state");
 }
+}  // extern "C"
+
 namespace {
 struct CkptHeader {
     char magic[8];
@@ -175,6 +177,7 @@ int32_t stream_in(ekf_handle *h, FILE *f, void *dev, size_t bytes, void *stage, 
 }
 }  // namespace
 
+extern "C" {
 int32_t ekf_checkpoint_save(ekf_handle *h, const char *path) {
     if (!h || !path) return fail(h, EKF_ERR_INVALID_ARG, "checkpoint_save: null argument");
     TRY(enter_flushed(h));

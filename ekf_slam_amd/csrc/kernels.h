@@ -1,9 +1,7 @@
-// Host-side launch interface of the gfx950 kernels (implemented in kernels.hip).
+// Host-side launch interface of the gfx950 kernels: one section per family, implemented by the fragment of kernels.hip the section names.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-
-#include <vector>
 
 #include "layout.h"
 
@@ -57,20 +55,45 @@ struct DevState {
     int32_t dcur;
 };
 
-struct CorrectArgs {
-    double z0, z1;            // [range, bearing_deg]
-    double R00, R01, R10, R11;
-    int64_t j;                // landmark-block row of the corrected landmark (2*idx)
-    int64_t n_mm;             // active landmark-block size (2N)
-    int32_t cur;
-    int32_t npend;            // pending pairs before this correction; its own pair goes to ring position npend
-    int32_t pstart;           // ring slot of the oldest pending pair
-};
-
+// ---- the steps: predict, append, the gather of a correction, a shard's row-panels, association (launch/steps.h) ----
 struct PredictArgs {
     double u0, u1, C;
     int64_t n_mm;
     int32_t cur;
+};
+hipError_t launch_predict(const DevState &st, const PredictArgs &a, int storage, hipStream_t s);
+
+struct AssocHostPartial;      // (with the association, below)
+
+// Device-resident measure() loop (EKF_SLAM_UC.m:107-151 without a host round trip per observation): the association decision of
+// an observation is PRODUCED on the device (k_associate, or the epilogue of the previous observation's k_gather) as one winner per
+// workgroup, and CONSUMED on the device by the next launch (k_gather takes its landmark from the arg-min over those winners;
+// k_append checks that nothing passed the threshold).  The host only learns the decisions afterwards, from `rec`.
+struct DevLoopArgs {
+    const AssocHostPartial *parts_in;   // DEVICE: per-workgroup winners of THIS observation's association; nullptr: not in use
+    AssocHostPartial *rec;              // MAPPED HOST: the decision this launch consumed, one self-validating 16-byte store
+                                        //   (index: landmark 0-based, -1 = new landmark, -2 = a winner entry did not carry seq_in)
+    AssocHostPartial *parts_out;        // DEVICE: winners of the NEXT observation's association, evaluated in k_gather's epilogue
+                                        //   on the state this correction leaves (one entry per k_gather workgroup); nullptr: none
+    int32_t nblk_in, seq_in;            // entries of parts_in and the launch number they must carry
+    int32_t seq_rec, seq_out;           // launch numbers stamped on rec / parts_out
+    double z0, z1, z2;                  // the next observation [range, bearing_deg, signature] and its R
+    double R00, R01, R10, R11;
+    double s_cost, s_thresh, w_pos;
+    // cfg.device_assoc == 4 (k_gather<.., kDecide>): the device also takes the branch.  The landmark count lives on the device, in a
+    // ring the host advances by one slot per launch: the launch reads *dn_in (n_known >= 0: the host knows it exactly, *dn_in is not
+    // read) and writes the count it leaves to *dn_out.  An append (winners: -1) reads the landmark-list entry of key N + 1
+    // (EKF_SLAM_UC.m:122) from loc + 3 (N - loc_base) (MAPPED host memory: x, y, number of entries that carry the key) and carries out
+    // append(u, R, loc, N + 1) -- unless the key matched no entry or several: then nothing is applied, the record says -4 and every
+    // later launch of the same scan (*abort == scan_id) applies nothing either (record -3), as the waited loop stops at that row.
+    const int64_t *dn_in;
+    int64_t *dn_out;
+    int64_t n_known;
+    const double *loc;
+    int64_t loc_base;
+    double u0, u1;
+    int32_t *abort;
+    int32_t scan_id;
 };
 
 struct AppendArgs {
@@ -80,6 +103,59 @@ struct AppendArgs {
     int64_t N;                // landmarks before the append
     int32_t cur;
 };
+// dl != nullptr (device-resident measure loop): the kernel also reduces dl->parts_in and records the decision in dl->rec
+hipError_t launch_append(const DevState &st, const AppendArgs &a, int storage, hipStream_t s, const DevLoopArgs *dl = nullptr,
+                         const PredictArgs *fused_predict = nullptr);
+
+struct CorrectArgs {
+    double z0, z1;            // [range, bearing_deg]
+    double R00, R01, R10, R11;
+    int64_t j;                // landmark-block row of the corrected landmark (2*idx)
+    int64_t n_mm;             // active landmark-block size (2N)
+    int32_t cur;
+    int32_t npend;            // pending pairs before this correction; its own pair goes to ring position npend
+    int32_t pstart;           // ring slot of the oldest pending pair
+};
+// fused_predict != nullptr folds predict(u) into the correction (one launch instead of two, identical arithmetic)
+// fuse_downdate: the kernel also applies its pair to the landmark block (small maps: a.n_mm <= gather_fuse_max_rows(), one
+// workgroup); the pair is then NOT written to the pending ring and no downdate launch must follow
+hipError_t launch_gather(const DevState &st, const CorrectArgs &a, const PredictArgs *fused_predict, int storage,
+                         hipStream_t s, bool fuse_downdate);
+int gather_fuse_max_rows();
+// device-resident measure loop: the corrected landmark is the arg-min over dl.parts_in (a.j is the fallback that keeps a launch
+// whose winners name no landmark inside the state); dl.parts_out != nullptr adds the next observation's association
+hipError_t launch_gather_devloop(const DevState &st, const CorrectArgs &a, const PredictArgs *fused_predict, const DevLoopArgs &dl,
+                                 int storage, hipStream_t s);
+int64_t gather_workgroups(const DevState &st, int64_t n_mm);      // of a gather over n_mm rows: one winner entry each (dl.parts_out)
+// cfg.device_assoc == 4: the device-decided branch (k_gather<.., kDecide>).  The winners of dl.parts_in name a landmark -> the
+// correction of launch_gather_devloop; nothing below the threshold -> the append of that observation; stale winners -> nothing is
+// applied.  Either way the state is left in buffer a.cur ^ 1 (diagonal blocks: dcur ^ 1), the pair slot of ring position a.npend is
+// written (zeros when nothing was corrected) and the next observation's association is evaluated on the state the launch leaves.
+// a.n_mm: the host's upper bound of the landmark-block size AFTER this launch (sizes the grid only).
+hipError_t launch_gather_decided(const DevState &st, const CorrectArgs &a, const DevLoopArgs &dl, int storage, hipStream_t s);
+
+// sharded correction: (1) every shard copies the chunks of the landmark row-panel P(j:j+1,:) it owns into `send`
+// (slab layout: local chunk kl of T columns, interleaved pairs), (2) the slabs are all-gathered into `recv`
+// (world slabs of `slab` doubles), (3) the gather/solve kernel reads the panel from `recv` instead of the tiles.
+hipError_t launch_rowpanel(const DevState &st, int64_t j, int64_t n_mm, int pstart, int npend, double *send, int storage,
+                           hipStream_t s);
+// device-resident measure loop on a shard: the row-panel of the landmark the DEVICE's association names (dl.parts_in); j, the host
+// mirror's prediction, only when the winners name nothing inside the state
+hipError_t launch_rowpanel_dev(const DevState &st, int64_t j, int64_t n_mm, int pstart, int npend, double *send, int storage,
+                               hipStream_t s, const DevLoopArgs &dl);
+struct RowList { int32_t m; int32_t j[64]; };      // landmark-block rows (2 * landmark index) of one prefetch
+// base row-panels of m <= 64 landmarks (0-based indices idx) into send + q * slab, one launch
+hipError_t launch_rowpanel_base(const DevState &st, const int64_t *idx, int m, int64_t n_mm, double *send, int64_t slab,
+                                int storage, hipStream_t s);
+// the row-panels of m <= 64 landmarks as the tiles will hold them after the pass that applies the npend pending pairs, into send + q * slab
+hipError_t launch_rowpanel_next(const DevState &st, const int64_t *idx, int m, int64_t n_mm, int pstart, int npend, double *send,
+                                int64_t slab, int storage, hipStream_t s);
+// recv: `world` contributions `rank_stride` doubles apart; this correction's row-panel starts `offset` doubles into
+// each; patched: the pending pairs are already applied to it (k_rowpanel) -- otherwise the gather applies them
+// dl != nullptr (device-resident measure loop on a shard): as launch_gather_devloop, on the exchanged row-panel
+hipError_t launch_gather_sharded(const DevState &st, const CorrectArgs &a, const PredictArgs *fused_predict, const double *recv,
+                                 int64_t rank_stride, int64_t offset, bool patched, int storage, hipStream_t s,
+                                 const DevLoopArgs *dl = nullptr);
 
 struct AssocArgs {
     double z0, z1, z2;
@@ -120,111 +196,8 @@ inline uint32_t assoc_part_mix(uint32_t ll_lo, uint32_t ll_hi, uint32_t index) {
     return m;
 }
 
-// Device-resident measure() loop (EKF_SLAM_UC.m:107-151 without a host round trip per observation): the association decision of
-// an observation is PRODUCED on the device (k_associate, or the epilogue of the previous observation's k_gather) as one winner per
-// workgroup, and CONSUMED on the device by the next launch (k_gather takes its landmark from the arg-min over those winners;
-// k_append checks that nothing passed the threshold).  The host only learns the decisions afterwards, from `rec`.
-struct DevLoopArgs {
-    const AssocHostPartial *parts_in;   // DEVICE: per-workgroup winners of THIS observation's association; nullptr: not in use
-    AssocHostPartial *rec;              // MAPPED HOST: the decision this launch consumed, one self-validating 16-byte store
-                                        //   (index: landmark 0-based, -1 = new landmark, -2 = a winner entry did not carry seq_in)
-    AssocHostPartial *parts_out;        // DEVICE: winners of the NEXT observation's association, evaluated in k_gather's epilogue
-                                        //   on the state this correction leaves (one entry per k_gather workgroup); nullptr: none
-    int32_t nblk_in, seq_in;            // entries of parts_in and the launch number they must carry
-    int32_t seq_rec, seq_out;           // launch numbers stamped on rec / parts_out
-    double z0, z1, z2;                  // the next observation [range, bearing_deg, signature] and its R
-    double R00, R01, R10, R11;
-    double s_cost, s_thresh, w_pos;
-    // cfg.device_assoc == 4 (k_gather<.., kDecide>): the device also takes the branch.  The landmark count lives on the device, in a
-    // ring the host advances by one slot per launch: the launch reads *dn_in (n_known >= 0: the host knows it exactly, *dn_in is not
-    // read) and writes the count it leaves to *dn_out.  An append (winners: -1) reads the landmark-list entry of key N + 1
-    // (EKF_SLAM_UC.m:122) from loc + 3 (N - loc_base) (MAPPED host memory: x, y, number of entries that carry the key) and carries out
-    // append(u, R, loc, N + 1) -- unless the key matched no entry or several: then nothing is applied, the record says -4 and every
-    // later launch of the same scan (*abort == scan_id) applies nothing either (record -3), as the waited loop stops at that row.
-    const int64_t *dn_in;
-    int64_t *dn_out;
-    int64_t n_known;
-    const double *loc;
-    int64_t loc_base;
-    double u0, u1;
-    int32_t *abort;
-    int32_t scan_id;
-};
-
 constexpr int kAssocBlock = 256;       // 4 wavefronts = one per SIMD: the per-landmark solve is a dependent f64 chain (1024 measured slower: 16 wavefronts share one CU's f64 issue)
 
-hipError_t launch_predict(const DevState &st, const PredictArgs &a, int storage, hipStream_t s);
-// dl != nullptr (device-resident measure loop): the kernel also reduces dl->parts_in and records the decision in dl->rec
-hipError_t launch_append(const DevState &st, const AppendArgs &a, int storage, hipStream_t s, const DevLoopArgs *dl = nullptr,
-                         const PredictArgs *fused_predict = nullptr);
-// fused_predict != nullptr folds predict(u) into the correction (one launch instead of two, identical arithmetic)
-// fuse_downdate: the kernel also applies its pair to the landmark block (small maps: a.n_mm <= gather_fuse_max_rows(), one
-// workgroup); the pair is then NOT written to the pending ring and no downdate launch must follow
-hipError_t launch_gather(const DevState &st, const CorrectArgs &a, const PredictArgs *fused_predict, int storage,
-                         hipStream_t s, bool fuse_downdate);
-int gather_fuse_max_rows();
-// device-resident measure loop: the corrected landmark is the arg-min over dl.parts_in (a.j is the fallback that keeps a launch
-// whose winners name no landmark inside the state); dl.parts_out != nullptr adds the next observation's association
-hipError_t launch_gather_devloop(const DevState &st, const CorrectArgs &a, const PredictArgs *fused_predict, const DevLoopArgs &dl,
-                                 int storage, hipStream_t s);
-int64_t gather_workgroups(const DevState &st, int64_t n_mm);
-// cfg.device_assoc == 4: the device-decided branch (k_gather<.., kDecide>).  The winners of dl.parts_in name a landmark -> the
-// correction of launch_gather_devloop; nothing below the threshold -> the append of that observation; stale winners -> nothing is
-// applied.  Either way the state is left in buffer a.cur ^ 1 (diagonal blocks: dcur ^ 1), the pair slot of ring position a.npend is
-// written (zeros when nothing was corrected) and the next observation's association is evaluated on the state the launch leaves.
-// a.n_mm: the host's upper bound of the landmark-block size AFTER this launch (sizes the grid only).
-hipError_t launch_gather_decided(const DevState &st, const CorrectArgs &a, const DevLoopArgs &dl, int storage, hipStream_t s);
-// sharded correction: (1) every shard copies the chunks of the landmark row-panel P(j:j+1,:) it owns into `send`
-// (slab layout: local chunk kl of T columns, interleaved pairs), (2) the slabs are all-gathered into `recv`
-// (world slabs of `slab` doubles), (3) the gather/solve kernel reads the panel from `recv` instead of the tiles.
-struct RowList { int32_t m; int32_t j[64]; };      // landmark-block rows (2 * landmark index) of one prefetch
-
-// base row-panels of m <= 64 landmarks (0-based indices idx) into send + q * slab, one launch
-hipError_t launch_rowpanel_base(const DevState &st, const int64_t *idx, int m, int64_t n_mm, double *send, int64_t slab,
-                                int storage, hipStream_t s);
-// the row-panels of m <= 64 landmarks as the tiles will hold them after the pass that applies the npend pending pairs, into send + q * slab
-hipError_t launch_rowpanel_next(const DevState &st, const int64_t *idx, int m, int64_t n_mm, int pstart, int npend, double *send,
-                                int64_t slab, int storage, hipStream_t s);
-hipError_t launch_rowpanel(const DevState &st, int64_t j, int64_t n_mm, int pstart, int npend, double *send, int storage,
-                           hipStream_t s);
-// device-resident measure loop on a shard: the row-panel of the landmark the DEVICE's association names (dl.parts_in); j, the host
-// mirror's prediction, only when the winners name nothing inside the state
-hipError_t launch_rowpanel_dev(const DevState &st, int64_t j, int64_t n_mm, int pstart, int npend, double *send, int storage,
-                               hipStream_t s, const DevLoopArgs &dl);
-// recv: `world` contributions `rank_stride` doubles apart; this correction's row-panel starts `offset` doubles into
-// each; patched: the pending pairs are already applied to it (k_rowpanel) -- otherwise the gather applies them
-// dl != nullptr (device-resident measure loop on a shard): as launch_gather_devloop, on the exchanged row-panel
-hipError_t launch_gather_sharded(const DevState &st, const CorrectArgs &a, const PredictArgs *fused_predict, const double *recv,
-                                 int64_t rank_stride, int64_t offset, bool patched, int storage, hipStream_t s,
-                                 const DevLoopArgs *dl = nullptr);
-// tiles -= sum_{i < npairs} K_i G_i (in slot order) over the work list (I,J pairs, device array) of `nwork` owned
-// lower-triangle tiles: ONE pass over P for npairs update-steps
-// work_xcd / xcd_len: the same tiles as 8 per-XCD streams (stream x = work_xcd[x*xcd_len ..), padded with (-1,-1)),
-// used when several pairs are applied so that each XCD's K/G working set stays inside its own L2
-// dst: tile store the result is written to (== st.tiles for an in-place flush; a second buffer for the asynchronous
-// flush, which must not disturb kernels still reading st.tiles); pstart: ring slot of the first pair
-// kname: nullptr, or 64 bytes that receive the name of the kernel instance that was launched ("k_flush_mfma<double,128,8>")
-// nx (sharded handles; nullptr or j < 0: none): ALSO extract the row-panel of landmark-block rows nx->j, nx->j + 1 into nx->send (layout
-// of launch_rowpanel) from the updated entries; *extracted tells whether the instance that was launched did it (one pair per
-// launch, wavefront-per-row tile shapes only)
-struct NextRow { int64_t j; double *send; };
-// what the strip form of the F32-arithmetic pass needs besides the tiles and the pairs (flush32_pipe.h; nullptr: that form is not used)
-struct PassAux {
-    const int4 *segs;      // strip work list: nsegs segments of ekf_pipe32::kSeg entries (strip_entry), 8 interleaved per-XCD streams
-    int64_t nsegs;         // a multiple of 8
-    float *dump;           // kDumpFloats floats per workgroup of the pass's grid
-    int grid;              // workgroups the dump area was sized for (one per CU)
-    int64_t cols;          // rows / columns of the landmark block the active tile rows cover (a multiple of 256): what k_split_pairs cuts
-    uint16_t *Kb3, *Gb3;   // cfg.pass_arith = EKF_ARITH_SPLIT3 only (nullptr otherwise): the bf16 planes of the pending pairs, cut in front
-                           // of each pass (flush32_split.h: split_plane_elems(ldm) elements each)
-};
-size_t pass_split_plane_elems(int64_t ldm);     // uint16_t elements of PassAux::Kb3 (and of Gb3) for a landmark block of leading dimension ldm
-hipError_t launch_downdate(const DevState &st, void *dst, const int2 *work, int64_t nwork, const int2 *work_xcd, int64_t xcd_len,
-                           int pstart, int npairs, int storage, int grid_cap, hipStream_t s, char *kname, const NextRow *nx = nullptr,
-                           bool *extracted = nullptr, int arith = 0, const PassAux *aux = nullptr);
-// strip work list of the owned lower-triangle tiles of nt tile rows (host side; entries for flush32_pipe.h::k_flush_strip32): returns
-// the segment count (a multiple of 8) and fills `out` with nsegs * kSeg entries
-int64_t build_strip_segments(const TileMap &tm, int64_t nt, std::vector<int4> &out);
 // pos_cost / sig_cost: device arrays of N or nullptr; partial: device scratch of >= ceil(N/kAssocBlock) entries; ticket: a
 // device int, zero between launches (the last workgroup to finish reduces the partials and resets it: one launch, no
 // finishing kernel); decision: device copy.  host_partials != nullptr (mapped host memory, one entry per workgroup): NO cross-workgroup
@@ -244,13 +217,48 @@ hipError_t launch_associate_devn(const DevState &st, const AssocArgs &a, AssocHo
 // then -- want_costs -- N position costs) and writes the decision like launch_associate does
 hipError_t launch_assoc_merge(const DevState &st, const double *recv, int world, int64_t count, int64_t N, bool want_costs,
                               double *pos_cost, AssocDecision *decision, AssocDecision *host_decision, int seq, hipStream_t s);
-// dense (column-major, n x n, device) <-> tiled
+
+// ---- the passes over P (launch/passes.h; launch/pass_select.h decides which kernel instance runs) ----
+// nx (sharded handles): ALSO extract the row-panel of landmark-block rows j, j + 1 into send (layout of launch_rowpanel) from the updated
+// entries; j < 0: none
+struct NextRow { int64_t j; double *send; };
+// what the strip form of the F32-arithmetic pass needs besides the tiles and the pairs (flush32_pipe.h; nullptr: that form is not used)
+struct PassAux {
+    const int4 *segs;      // strip work list: nsegs segments of ekf_pipe32::kSeg entries (strip_entry), 8 interleaved per-XCD streams
+    int64_t nsegs;         // a multiple of 8
+    float *dump;           // kDumpFloats floats per workgroup of the pass's grid
+    int grid;              // workgroups the dump area was sized for (one per CU)
+    int64_t cols;          // rows / columns of the landmark block the active tile rows cover (a multiple of 256): what k_split_pairs cuts
+    uint16_t *Kb3, *Gb3;   // cfg.pass_arith = EKF_ARITH_SPLIT3 only (nullptr otherwise): the bf16 planes of the pending pairs, cut in front
+                           // of each pass (flush32_split.h: split_plane_elems(ldm) elements each)
+};
+size_t pass_split_plane_elems(int64_t ldm);     // uint16_t elements of PassAux::Kb3 (and of Gb3) for a landmark block of leading dimension ldm
+// One pass: tiles -= sum_{i < npairs} K_i G_i (in slot order) over the owned lower-triangle tiles of a work set -- ONE pass over P for
+// npairs update-steps
+struct PassJob {
+    void *dst;                 // tile store the result is written to (== st.tiles for an in-place flush; a second buffer for the asynchronous
+                               // flush, which must not disturb kernels still reading st.tiles)
+    const int2 *work;          // the work list: (I, J) of the `nwork` owned tiles (device array)
+    int64_t nwork;
+    const int2 *work_xcd;      // the same tiles as 8 per-XCD streams (stream x = work_xcd[x * xcd_len ..), padded with (-1, -1)), used when
+    int64_t xcd_len;           // several pairs are applied so that each XCD's K/G working set stays inside its own L2
+    int pstart, npairs;        // the ring window: slot of the oldest pair, pairs to apply
+    int grid_cap;              // EKF_DOWNDATE_GRID of a tuning build; 0: none
+    int arith;                 // cfg.pass_arith
+    const PassAux *aux;        // nullptr: the handle has no strip form
+    const NextRow *nx;         // nullptr: no row-panel wanted
+};
+// kname: nullptr, or 64 bytes that receive the name of the kernel instance that was launched ("k_flush_mfma<double,128,8>");
+// *extracted tells whether that instance extracted job.nx (one pair per launch, wavefront-per-row tile shapes only)
+hipError_t launch_downdate(const DevState &st, const PassJob &job, int storage, hipStream_t s, char *kname, bool *extracted = nullptr);
 // cfg.async_flush: rows [r0, r1) of the landmark block (every local tile of the tile rows they lie in) copied from one tile store to the other
 hipError_t launch_copy_rows(const TileMap &tm, const void *src, void *dst, int64_t r0, int64_t r1, int storage, hipStream_t s);
 // the same with bounds known on the device only (cfg.device_assoc == 4): rows [2 * *n_lo, 2 * *n_hi) of the range [r0, r1) the host
 // can bound them by (a pointer that is nullptr leaves the host's bound as it is)
 hipError_t launch_copy_rows_dev(const TileMap &tm, const void *src, void *dst, int64_t r0, int64_t r1, const int64_t *n_lo,
                                 const int64_t *n_hi, int storage, hipStream_t s);
+
+// ---- map edits: removal, a constraint and its chained form, the fused pass of a batch of merges, the candidate search (launch/edits.h) ----
 // Landmark removal (compact.h).  src_of (device, ldm / 2 entries): the old landmark of every landmark of the new map, strictly
 // increasing, -1 from the new count on.  launch_compact_tiles writes the `ntiles` destination tiles work[0 ..) = (I, J) of the
 // store `dst` from the store `src` (never the same store): element (r', c') = old element (src(r'), src(c')), zero beyond the new map.
@@ -292,6 +300,9 @@ hipError_t launch_merge_pass(const DevState &st, void *dst, const int2 *work, in
 // defines it for delta = 0 and the noise covariance R (row-major).  Reads state buffer cur / diagonal buffer st.dcur, writes `out` only.
 struct alignas(16) NearestEntry { double d2; int64_t partner; };
 hipError_t launch_nearest(const DevState &st, int cur, int64_t N, const double R[4], NearestEntry *out, int storage, hipStream_t s);
+
+// ---- state I/O (launch/state_io.h) ----
+// dense (column-major, n x n, device) <-> tiled
 hipError_t launch_unpack_dense(const DevState &st, int cur, int64_t n_mm, double *dense, int storage, hipStream_t s);
 hipError_t launch_pack_dense(const DevState &st, int cur, int64_t n_mm, const double *dense, int storage, hipStream_t s);
 hipError_t launch_get_block(const DevState &st, int cur, int64_t r0, int64_t c0, int64_t nr, int64_t nc,

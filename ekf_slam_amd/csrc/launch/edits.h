@@ -1,0 +1,88 @@
+// Fragment of kernels.hip, the launchers of the map edits: landmark removal (compact.h), a constraint between two landmarks and its
+// chained form (constrain.h), the fused pass of a batch of merges (merge_pass.h), the candidate search (nearest.h).
+#pragma once
+
+namespace {
+// A pass that writes `ntiles` whole destination tiles out of place, kBlock * kCompactRows 16-byte pieces per work item: the items per
+// tile and the grid; false: the grid does not fit 31 bits
+bool compact_grid(const TileMap &tm, int64_t ntiles, int storage, int &items, int64_t &grid) {
+    const int64_t pieces = (int64_t)tm.T * tm.T / (storage == 0 ? 2 : 4);
+    items = (int)cdiv(pieces, (int64_t)kBlock * kCompactRows);
+    grid = ntiles * items;
+    return grid <= 0x7fffffff;
+}
+}  // namespace
+
+hipError_t launch_compact_tiles(const TileMap &tm, const void *src, void *dst, const int2 *work, int64_t ntiles, const int32_t *src_of,
+                                int storage, hipStream_t s) {
+    if (ntiles <= 0) return hipSuccess;
+    if (src == dst) return hipErrorInvalidValue;                        // out of place only
+    int items;
+    int64_t grid;
+    if (!compact_grid(tm, ntiles, storage, items, grid)) return hipErrorInvalidValue;
+    return with_storage(storage, [&](auto ts) {
+        using TS = decltype(ts);
+        hipLaunchKernelGGL(k_compact_tiles<TS>, dim3((unsigned)grid), dim3(kBlock), 0, s, (const TS *)src, (TS *)dst, work, items, src_of, tm);
+    });
+}
+
+hipError_t launch_compact_state(const DevState &st, int cur, const int32_t *src_of, int64_t N_old, double *s_out, hipStream_t s) {
+    const int64_t grid = cdiv(N_old > 0 ? N_old : 1, kBlock);
+    hipLaunchKernelGGL(k_compact_state, dim3((unsigned)grid), dim3(kBlock), 0, s, st, cur, src_of, N_old, s_out);
+    return hipGetLastError();
+}
+
+hipError_t launch_merge_pass(const DevState &st, void *dst, const int2 *work, int64_t ntiles, const int32_t *src_of, int npairs,
+                             int storage, hipStream_t s, char *kname) {
+    if (ntiles <= 0) return hipSuccess;
+    if (st.tiles == dst || !dst || !src_of || npairs < 0 || npairs > st.pcap || st.tm.world != 1) return hipErrorInvalidValue;      // out of place only
+    int items;
+    int64_t grid;
+    if (!compact_grid(st.tm, ntiles, storage, items, grid)) return hipErrorInvalidValue;
+    if (kname) snprintf(kname, 64, "k_merge_pass<%s,%d>", storage == 0 ? "double" : "float", st.tm.T);
+    return with_storage(storage, [&](auto ts) {
+        using TS = decltype(ts);
+        hipLaunchKernelGGL(k_merge_pass<TS>, dim3((unsigned)grid), dim3(kBlock), 0, s, (const TS *)st.tiles, (TS *)dst, work, items, src_of,
+                           (const double *)st.Kp, (const double *)st.Gp, st.pair_stride, npairs, st.tm);
+    });
+}
+
+hipError_t launch_constrain_probe(const DevState &st, int cur, int64_t ai, int64_t aj, double *out, int storage, hipStream_t s) {
+    if (!out || ai < 0 || aj < 0 || ((ai | aj) & 1) || ai == aj) return hipErrorInvalidValue;
+    return with_storage(storage, [&](auto ts) {
+        hipLaunchKernelGGL(k_constrain_probe<decltype(ts)>, dim3(1), dim3(64), 0, s, st, cur, ai, aj, out);
+    });
+}
+
+namespace {
+// two different landmarks inside the map, the padded block inside the strip, the pair's ring position inside the ring
+bool constrain_args_ok(const DevState &st, const ConstrainArgs &a) {
+    const bool rows_ok = a.ai >= 0 && a.aj >= 0 && a.ai + 1 < a.n_mm && a.aj + 1 < a.n_mm && (a.ai & 1) == 0 && (a.aj & 1) == 0 && a.ai != a.aj;
+    return rows_ok && st.tm.padded(a.n_mm) <= st.ldm && a.npend >= 0 && a.npend < st.pcap;
+}
+unsigned constrain_grid(const DevState &st, const ConstrainArgs &a) { return (unsigned)cdiv(st.tm.padded(a.n_mm), kBlock); }
+}  // namespace
+
+hipError_t launch_gather_constrain(const DevState &st, const ConstrainArgs &a, int storage, hipStream_t s) {
+    if (!constrain_args_ok(st, a)) return hipErrorInvalidValue;
+    return with_storage(storage, [&](auto ts) {
+        hipLaunchKernelGGL(k_gather_constrain<decltype(ts)>, dim3(constrain_grid(st, a)), dim3(kBlock), 0, s, st, a);
+    });
+}
+
+hipError_t launch_gather_constrain_chain(const DevState &st, const ConstrainArgs &a, double *rec, int storage, hipStream_t s) {
+    if (!constrain_args_ok(st, a) || a.pstart < 0 || a.pstart >= st.pcap || !rec || st.Gp32 || st.tm.world != 1) return hipErrorInvalidValue;
+    return with_storage(storage, [&](auto ts) {
+        hipLaunchKernelGGL(k_gather_constrain_chain<decltype(ts)>, dim3(constrain_grid(st, a)), dim3(kBlock), 0, s, st, a, rec);
+    });
+}
+
+hipError_t launch_nearest(const DevState &st, int cur, int64_t N, const double R[4], NearestEntry *out, int storage, hipStream_t s) {
+    if (N <= 0) return hipSuccess;
+    // a group of landmarks (and a float lane's two) must lie inside one tile row / one tile; landmark indices are 32-bit in the kernel
+    if (!out || !R || st.tm.world != 1 || st.tm.T < 4 || (st.tm.T / 2) % kNearestGroup != 0 || 2 * N > st.ldm || N > 0x7fffffff) return hipErrorInvalidValue;
+    const int64_t grid = cdiv(cdiv(N, (int64_t)kNearestGroup), kBlock / 64);
+    return with_storage(storage, [&](auto ts) {
+        hipLaunchKernelGGL(k_nearest<decltype(ts)>, dim3((unsigned)grid), dim3(kBlock), 0, s, st, cur, N, R[0], R[1], R[2], R[3], out);
+    });
+}

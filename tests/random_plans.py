@@ -2,7 +2,7 @@
 
 `plan(seed)` returns (cfg, ops): the seed's engine configuration and its list of op records, a pure function of the seed, so that a
 failing seed can be printed and replayed.  The configuration is stratified, not drawn: `config(seed)` walks a fixed table so that 64
-seeds cover every pass kernel a full batch can select (kernels.hip: launch_downdate / launch_flush_mfma), crossed with the asynchronous
+seeds cover every pass kernel a full batch can select (csrc/launch/pass_select.h: ekf_pass::select_pass), crossed with the asynchronous
 pass, the shard layouts, the association modes and the association weight.
 
 Configuration table (ROWS): storage, tile edge, the batches of the row, and the name prefix of the pass kernel a full batch selects.
@@ -62,7 +62,8 @@ STRETCH_BREAK = FLUSHING | {"measure", "associate"}
 
 
 def expected_kernel(storage, tile, batch):
-    """Name prefix of the pass kernel a full batch of `batch` pairs selects (kernels.hip: launch_downdate_t / launch_flush_mfma)."""
+    """Name prefix of the pass kernel a full batch of `batch` pairs selects (csrc/launch/pass_select.h: ekf_pass::select_pass;
+    tests/test_pass_select_cpu.py holds the two together)."""
     if storage == "f64":
         if tile == 128:
             if batch == 1:

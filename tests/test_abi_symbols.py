@@ -3,6 +3,7 @@ include/ekfslam.h declares, and fails loudly (no fallback) when no HIP device is
 import ctypes
 import os
 import re
+import subprocess
 
 import numpy as np
 import pytest
@@ -30,6 +31,13 @@ def test_every_declared_symbol_is_exported_and_bound(L):
     for name in declared:
         assert hasattr(L, name), "libekfslam.so does not export %s" % name
     assert sorted(_lib.SIGNATURES) == declared, "ctypes binding and header disagree"
+    # ... and nothing else has C linkage: a helper defined inside extern "C" leaks into the ABI (an unnamed namespace there does not hide
+    # it), so every defined function of the dynamic symbol table that is not C++-mangled must be one the header declares
+    r = subprocess.run(["/opt/rocm/llvm/bin/llvm-readelf", "--dyn-syms", "-W", _lib.LIB_PATH], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-2000:]
+    rows = [ln.split() for ln in r.stdout.splitlines()]
+    c_names = {row[7].split("@")[0] for row in rows if len(row) == 8 and row[3] == "FUNC" and row[6] != "UND" and not row[7].startswith("_Z")}
+    assert sorted(c_names - {"_init", "_fini"}) == declared
 
 
 def test_abi_version_and_status_strings(L):

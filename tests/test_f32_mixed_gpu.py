@@ -51,7 +51,7 @@ def _run(engines, ref, steps, seed, appends=()):
 
 
 def _pass_kernel(pairs):
-    """which kernel a pass of `pairs` pending pairs over float tiles in F32 arithmetic runs (kernels.hip::launch_flush_mfma)"""
+    """which kernel a pass of `pairs` pending pairs over float tiles in F32 arithmetic runs (csrc/launch/pass_select.h: ekf_pass::select_pass)"""
     return "k_flush_strip32<" if pairs > 56 else "k_flush_mfma32<256," if pairs > 2 else "k_flush_mfma<float,256,"
 
 
