@@ -36,6 +36,19 @@ class EkfConfig(ctypes.Structure):
                 ("pass_direction", _i32), ("force_sharded", _i32), ("pass_arith", _i32), ("reserved", _i32 * 2)]
 
 
+class EkfLinearObs(ctypes.Structure):
+    """struct ekf_linear_obs (include/ekfslam.h)."""
+    _fields_ = [("z", _d * 2), ("R", _d * 4), ("Hr", _d * 6), ("lm", _i64 * 2), ("Hl", (_d * 4) * 2), ("gate", _d),
+                ("wrap_deg", _i32 * 2), ("rows", _i32)]
+
+
+class EkfLinearResult(ctypes.Structure):
+    """struct ekf_linear_result (include/ekfslam.h)."""
+    _fields_ = [("nu", _d * 2), ("S", _d * 4), ("d2", _d), ("outcome", _i32)]
+
+
+EKF_LINEAR_IRREGULAR, EKF_LINEAR_APPLIED, EKF_LINEAR_GATED = 0, 1, 2
+
 # name -> (restype, argtypes); every symbol of include/ekfslam.h
 SIGNATURES = {
     "ekf_abi_version": (_i32, []),
@@ -85,6 +98,9 @@ SIGNATURES = {
     "ekf_merge_landmarks_batch": (_i32, [_vp, ctypes.POINTER(_i64), ctypes.POINTER(_i64), _i64, _dp, _dp]),
     "ekf_landmark_distance": (_i32, [_vp, _i64, _i64, _dp, _dp, _dp, _dp]),
     "ekf_nearest_landmarks": (_i32, [_vp, _dp, _dp, ctypes.POINTER(_i64)]),
+    "ekf_observe_linear": (_i32, [_vp, ctypes.POINTER(EkfLinearObs), ctypes.POINTER(EkfLinearResult)]),
+    "ekf_linear_innovation": (_i32, [_vp, ctypes.POINTER(EkfLinearObs), ctypes.POINTER(EkfLinearResult)]),
+    "ekf_linear_rejections": (_i32, [_vp, ctypes.POINTER(_i64), ctypes.POINTER(_i64)]),
     "ekf_diag_poke_device_signature": (_i32, [_vp, _i64, _d]),
     "ekf_get_P": (_i32, [_vp, _dp]),
     "ekf_set_P": (_i32, [_vp, _dp, _i64]),

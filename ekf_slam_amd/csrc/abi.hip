@@ -10,6 +10,7 @@
 #include "host/assoc.h"        // verify_loop, the waited and the speculated association, the lookups
 #include "host/measure.h"      // ekf_measure
 #include "host/edits.h"        // remove, constrain / merge / distance, nearest
+#include "host/linear.h"       // linear observations as update-steps: observe_linear, linear_innovation, linear_rejections
 #include "host/state.h"        // get / set, low-rank load, checkpoint, digest
 #include "host/lifecycle.h"    // ekf_create, ekf_destroy, the kernel timers
 

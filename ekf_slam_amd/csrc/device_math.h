@@ -198,4 +198,57 @@ EKF_MHD bool constrain_d2(const double S[4], double nu0, double nu1, double &d2)
     return regular;
 }
 
+// a (degrees) wrapped into (-180, 180]: a - 360 ceil((a - 180) / 360), the product exact and the difference one rounding
+EKF_MHD double wrap180(double a) {
+    if (a > -180.0 && a <= 180.0) return a;
+    return fma(-360.0, ceil((a - 180.0) / 360.0), a);
+}
+
+// The small part of a LINEAR observation z = H x + noise (linear_obs.h), H = [Hr | Hl0 | Hl1] with a 2x3 block on the robot state and
+// 2x2 blocks on up to two landmarks.  sm: the kLinearSmall operands, the 7 x 7 covariance of (robot, landmark 0, landmark 1) and their
+// seven entries of x --
+//   0..8    Prr, row-major                         9 + 6b + 2t + r   P(t, a_b + r): the strip at landmark b's columns
+//   21 + 3b the own block of landmark b: (0,0) (1,0) (1,1)           27 + 2r + c   the cross block P(a_0 + r, a_1 + c)
+//   31..33  x_r      34, 35  l_0      36, 37  l_1
+// (an absent landmark: zeros, with a zero block of H).  H row-major 2 x 7, R and S row-major.  Gs = H Psm (2 x 7, row-major),
+// S = Gs H' + R, nu = z - H x with the rows named in wrap_deg wrapped into (-180, 180], every sum in ascending index order.
+// k_gather_linear, k_linear_probe and the host run this one function: with FP contraction off all give the same bits.
+constexpr int kLinearSmall = 38;
+EKF_MHD double linear_small_P(const double *sm, int i, int j) {
+    if (i < j) { const int t = i; i = j; j = t; }
+    if (i < 3) return sm[3 * i + j];
+    const int b = (i - 3) >> 1, r = (i - 3) & 1;
+    if (j < 3) return sm[9 + 6 * b + 2 * j + r];
+    const int bj = (j - 3) >> 1, c = (j - 3) & 1;
+    if (b == bj) return sm[21 + 3 * b + r + c];
+    return sm[27 + 2 * c + r];                      // i in landmark 1, j in landmark 0: P(a_0 + c, a_1 + r)
+}
+EKF_MHD void linear_small(const double *sm, const double H[14], const double z[2], const double R[4], const int wrap_deg[2],
+                          double Gs[14], double S[4], double nu[2]) {
+    for (int r = 0; r < 2; ++r) {
+        for (int j = 0; j < 7; ++j) {
+            double g = 0.0;
+            for (int i = 0; i < 7; ++i) g += H[7 * r + i] * linear_small_P(sm, i, j);
+            Gs[7 * r + j] = g;
+        }
+        double hx = 0.0;
+        for (int i = 0; i < 7; ++i) hx += H[7 * r + i] * sm[31 + i];
+        nu[r] = z[r] - hx;
+        if (wrap_deg[r]) nu[r] = wrap180(nu[r]);
+    }
+    for (int r = 0; r < 2; ++r)
+        for (int b = 0; b < 2; ++b) {
+            double s = 0.0;
+            for (int j = 0; j < 7; ++j) s += Gs[7 * r + j] * H[7 * b + j];
+            S[2 * r + b] = s + R[2 * r + b];
+        }
+}
+
+// what a linear observation does under S, nu and its gate: EKF_LINEAR_IRREGULAR (0) where constrain_d2 calls S irregular (d2 is NaN),
+// EKF_LINEAR_GATED (2) where d2 > gate, EKF_LINEAR_APPLIED (1) otherwise
+EKF_MHD int linear_outcome(const double S[4], const double nu[2], double gate, double &d2) {
+    if (!constrain_d2(S, nu[0], nu[1], d2)) return 0;
+    return d2 > gate ? 2 : 1;
+}
+
 }  // namespace ekfm

@@ -202,6 +202,12 @@ struct ekf_handle {
     // the device and in pinned memory, the snapshot of x / strip / Prr / the diagonal blocks it restores when a pair is irregular
     // (allocated at the first batch call and kept)
     double *d_mring = nullptr, *d_mrec = nullptr, *h_mrec = nullptr, *d_msnap = nullptr;
+    // ---- linear observations (ekf_observe_linear / ekf_linear_innovation) ----
+    // two records on the device and in pinned memory (the update-step's, then the probe's; behind them in the pinned area the two counters
+    // ekf_linear_rejections reads), the device counters of launches that did not apply, the event behind a waited step's readback
+    double *d_linrec = nullptr, *h_linrec = nullptr;
+    int64_t *d_lincnt = nullptr;
+    hipEvent_t ev_linrec = nullptr;
     // ---- timers, what ekf_destroy releases, the error text ----
     KernelTimer timers[EKF_KERNEL_COUNT];
     std::vector<void *> allocs;       // device memory (dalloc), pinned memory (halloc) and events (new_event): what ekf_destroy releases

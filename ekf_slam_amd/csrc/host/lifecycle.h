@@ -77,6 +77,7 @@ int32_t ekf_create(const ekf_config *cfg, ekf_handle **out) {
     TRY(create_assoc(h));
     TRY(create_exchange(h));
     TRY(create_decided(h));
+    TRY(create_linear(h));
     HIPCHK(h, hipDeviceSynchronize());      // dalloc clears on the null stream, which the handle's (non-blocking) streams do not wait for
     return EKF_OK;
 }

@@ -258,7 +258,8 @@ hipError_t launch_copy_rows(const TileMap &tm, const void *src, void *dst, int64
 hipError_t launch_copy_rows_dev(const TileMap &tm, const void *src, void *dst, int64_t r0, int64_t r1, const int64_t *n_lo,
                                 const int64_t *n_hi, int storage, hipStream_t s);
 
-// ---- map edits: removal, a constraint and its chained form, the fused pass of a batch of merges, the candidate search (launch/edits.h) ----
+// ---- map edits: removal, a constraint and its chained form, the fused pass of a batch of merges, the candidate search, and the linear
+// observation that shares the constraint's device code (launch/edits.h) ----
 // Landmark removal (compact.h).  src_of (device, ldm / 2 entries): the old landmark of every landmark of the new map, strictly
 // increasing, -1 from the new count on.  launch_compact_tiles writes the `ntiles` destination tiles work[0 ..) = (I, J) of the
 // store `dst` from the store `src` (never the same store): element (r', c') = old element (src(r'), src(c')), zero beyond the new map.
@@ -300,6 +301,30 @@ hipError_t launch_merge_pass(const DevState &st, void *dst, const int2 *work, in
 // defines it for delta = 0 and the noise covariance R (row-major).  Reads state buffer cur / diagonal buffer st.dcur, writes `out` only.
 struct alignas(16) NearestEntry { double d2; int64_t partner; };
 hipError_t launch_nearest(const DevState &st, int cur, int64_t N, const double R[4], NearestEntry *out, int storage, hipStream_t s);
+
+// A linear observation with a constant Jacobian (linear_obs.h): "H x was observed as z with noise covariance R", H = a 2x3 block on
+// the robot state and 2x2 blocks on up to two landmarks.  An UPDATE-STEP on the handle's own ring, like a correction.
+struct LinearArgs {
+    double z[2];
+    double R[4];              // row-major
+    double H[14];             // row-major 2 x 7: the robot block (columns 0..2), landmark a[0]'s (3, 4), landmark a[1]'s (5, 6); zeros where absent
+    double gate;              // applied only if d2 <= gate (+inf: always)
+    int64_t a[2];             // landmark-block rows of the landmarks that carry a block (2 * index), -1 = none; different when both >= 0
+    int64_t n_mm;             // active landmark-block size (2N)
+    int32_t wrap[2];          // row r of nu is an angle in degrees: wrapped into (-180, 180]
+    int32_t cur;
+    int32_t npend;            // pending pairs before this step; its own pair goes to ring position npend
+    int32_t pstart;           // ring slot of the oldest pending pair
+};
+// the record of a launch: S row-major, nu, d2 as ekfm::constrain_d2 gives it, the outcome (1.0 applied, 0.0 S irregular, 2.0 gated)
+constexpr int kLinearRecordDoubles = 8;
+// k_gather_linear: the observation's pair into ring position a.npend (float copies included) with every tile operand read patched with
+// the a.npend pending pairs, x / Prr / strip into buffer a.cur ^ 1, every landmark's live diagonal block into buffer dcur ^ 1, the record
+// into rec, and cnt[0] / cnt[1] (device) incremented where S was irregular / d2 beyond the gate: such a launch leaves a zero pair and
+// copies the state.  The caller ends the step as a correction's (finish_step).
+hipError_t launch_gather_linear(const DevState &st, const LinearArgs &a, double *rec, int64_t *cnt, int storage, hipStream_t s);
+// k_linear_probe: the record that launch would write under the current state, and nothing else
+hipError_t launch_linear_probe(const DevState &st, const LinearArgs &a, double *rec, int storage, hipStream_t s);
 
 // ---- state I/O (launch/state_io.h) ----
 // dense (column-major, n x n, device) <-> tiled

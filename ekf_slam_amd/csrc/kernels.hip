@@ -41,6 +41,7 @@ namespace {
 #include "state_io.h"         // dense <-> tiled, block reads, low-rank load, digest
 #include "compact.h"          // landmark removal: k_compact_tiles, k_compact_state
 #include "constrain.h"        // a constraint between two landmarks: k_constrain_probe, k_gather_constrain
+#include "linear_obs.h"       // a linear observation as an update-step: k_gather_linear, k_linear_probe
 #include "merge_pass.h"       // the fused downdate-and-compact pass of a batch of merges: k_merge_pass
 #include "nearest.h"          // the candidate search in front of a merge: k_nearest
 
@@ -51,5 +52,5 @@ namespace {
 #include "launch/steps.h"         // predict, append, gather, row-panels, association
 #include "launch/pass_select.h"   // which pass instance runs: a pure function, no HIP
 #include "launch/passes.h"        // launch_downdate, the row copies behind an asynchronous pass
-#include "launch/edits.h"         // compact, constrain, merge pass, nearest
+#include "launch/edits.h"         // compact, constrain, linear observation, merge pass, nearest
 #include "launch/state_io.h"      // dense <-> tiled, block reads, low-rank load, digest

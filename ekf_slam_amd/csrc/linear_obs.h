@@ -1,0 +1,180 @@
+// Fragment of kernels.hip (included there, inside its anonymous namespace, after constrain.h): the rank-2 pair of a LINEAR observation
+// with a constant Jacobian (ekf_observe_linear / ekf_linear_innovation): k_gather_linear, k_linear_probe.
+#pragma once
+
+// ---------------------------------------------------------------------------------------------------
+// "H x was observed as z, with noise covariance R", H = [Hr (2x3, robot) .. Hl_0 (2x2, columns a_0) .. Hl_1 (2x2, columns a_1) ..]:
+//     G = H P      S = G H' + R      nu = z - H x (rows wrapped where asked)      K = G' S^-1      x += K nu      P -= K G
+// -- the update of constrain.h for a general H (there: Hr = 0, Hl = +I2, -I2).  Unlike a constraint this is an UPDATE-STEP: the
+// launch runs on the handle's own ring while the a.npend earlier pairs are still pending, reads every tile operand patched with
+// them (constrain_row_pair_chain, pmm_low_chain) and leaves its pair in the next slot, float copies included, as k_gather does.
+// x, the strip, Prr and the live diagonal blocks carry every pending pair already and are read as they are.
+// ---------------------------------------------------------------------------------------------------
+// the record of a launch (kernels.h: kLinearRecordDoubles): S row-major (0..3) | nu (4, 5) | d2 (6) | the outcome (7): 1.0 applied, 0.0 S
+// irregular, 2.0 gated
+
+// operand e of ekfm::linear_small (device_math.h names the layout); the cross block comes from the tiles and needs the chain
+template <typename TS>
+__device__ __forceinline__ double linear_small_entry(const DevState &st, const LinearArgs &a, int e) {
+    const int cur = a.cur;
+    const int64_t a0 = a.a[0], a1 = a.a[1];
+    if (e < 9) return st.prr[cur][e];
+    if (e < 21) {
+        const int q = e - 9, b = q / 6, t = (q - 6 * b) >> 1, r = q & 1;
+        const int64_t ab = b ? a1 : a0;
+        return ab >= 0 ? st.strip[cur][t * st.ldm + ab + r] : 0.0;
+    }
+    if (e < 27) {
+        const int q = e - 21, b = q / 3;
+        const int64_t ab = b ? a1 : a0;
+        return ab >= 0 ? st.diag[st.dcur][3 * (ab >> 1) + (q - 3 * b)] : 0.0;
+    }
+    if (e < 31) return (a0 >= 0 && a1 >= 0) ? pmm_low_chain<TS>(st, a.pstart, a.npend, a0 + ((e - 27) >> 1), a1 + ((e - 27) & 1)) : 0.0;
+    if (e < 34) return st.x[cur][e - 31];
+    const int64_t ab = ((e - 34) >> 1) ? a1 : a0;
+    return ab >= 0 ? st.x[cur][3 + ab + ((e - 34) & 1)] : 0.0;
+}
+
+struct LinearSolve {
+    double Si[4];          // S^-1, row-major
+    double nu[2];
+    double Gr[2][3];       // G over the robot columns
+    double Kr[3][2];
+    double prr[9];         // Prr before the update
+    double rec[kLinearRecordDoubles];
+    int outcome;
+};
+
+// The small part, by the first wavefront of a workgroup: the kLinearSmall operands one per lane (each patched entry walks the ring
+// once, on a lane of its own), then lane 0 forms S, nu, d2, the decision, S^-1, Gr and Kr.  A launch that does not apply (S irregular,
+// d2 beyond the gate) gets zeros for S^-1, nu, Gr and Kr: every column then writes a zero pair and copies the state.
+// Called by every lane of the workgroup; ends with a barrier.
+template <typename TS>
+__device__ __forceinline__ void linear_small_part(const DevState &st, const LinearArgs &a, double *sm, LinearSolve &sol) {
+    const int tid = threadIdx.x;
+    if (tid < ekfm::kLinearSmall) sm[tid] = linear_small_entry<TS>(st, a, tid);
+    __syncthreads();
+    if (tid == 0) {
+        double Gs[14], S[4], nu[2], d2;
+        ekfm::linear_small(sm, a.H, a.z, a.R, a.wrap, Gs, S, nu);
+        const int outcome = ekfm::linear_outcome(S, nu, a.gate, d2);
+        for (int q = 0; q < 4; ++q) sol.rec[q] = S[q];
+        sol.rec[4] = nu[0]; sol.rec[5] = nu[1]; sol.rec[6] = d2; sol.rec[7] = (double)outcome;
+        sol.outcome = outcome;
+        const bool ok = outcome == 1;
+        double Si[4];
+        ekfm::inv2(S, Si);
+        for (int q = 0; q < 4; ++q) sol.Si[q] = ok ? Si[q] : 0.0;
+        sol.nu[0] = ok ? nu[0] : 0.0;
+        sol.nu[1] = ok ? nu[1] : 0.0;
+        for (int r = 0; r < 2; ++r)
+            for (int t = 0; t < 3; ++t) sol.Gr[r][t] = ok ? Gs[7 * r + t] : 0.0;
+        for (int t = 0; t < 3; ++t)
+            for (int cc = 0; cc < 2; ++cc) sol.Kr[t][cc] = sol.Gr[0][t] * sol.Si[cc] + sol.Gr[1][t] * sol.Si[2 + cc];
+        for (int q = 0; q < 9; ++q) sol.prr[q] = sm[q];
+    }
+    __syncthreads();
+}
+
+// ekf_linear_innovation: the small part alone, and nothing written but the record
+template <typename TS>
+__global__ __launch_bounds__(64) void k_linear_probe(DevState st, LinearArgs a, double *__restrict__ rec) {
+    __shared__ double sm[ekfm::kLinearSmall];
+    __shared__ LinearSolve sol;
+    linear_small_part<TS>(st, a, sm, sol);
+    if (threadIdx.x < kLinearRecordDoubles) rec[threadIdx.x] = sol.rec[threadIdx.x];
+}
+
+// One lane per landmark-block column c; 256 columns per workgroup (k_gather_constrain's shape).  Reads state buffer a.cur / diagonal
+// buffer st.dcur, writes the other ones whole; the small part is formed by EVERY workgroup (no workgroup reads what another one of
+// the launch writes).  rec: kLinearRecordDoubles doubles, cnt: the two counters of launches that did not apply (irregular, gated) --
+// both written by workgroup 0 (launches on one stream are ordered: a plain load, add and store).
+template <typename TS>
+__global__ __launch_bounds__(kBlock) void k_gather_linear(DevState st, LinearArgs a, double *__restrict__ rec, int64_t *__restrict__ cnt) {
+    __shared__ double sm[ekfm::kLinearSmall];
+    __shared__ LinearSolve sol;
+    const int tid = threadIdx.x;
+    const int cur = a.cur;
+    const double *__restrict__ x = st.x[cur];
+    const double *__restrict__ strip = st.strip[cur];
+    double *__restrict__ x_nxt = st.x[cur ^ 1];
+    double *__restrict__ strip_nxt = st.strip[cur ^ 1];
+    const int64_t ldm = st.ldm;
+    const int64_t c = (int64_t)blockIdx.x * kBlock + tid;
+    const bool live = c < a.n_mm;
+
+    // (1) the column's loads and patches; a landmark that carries no block is skipped by the whole launch
+    double m[2][2] = { { 0.0, 0.0 }, { 0.0, 0.0 } }, s0 = 0.0, s1 = 0.0, s2 = 0.0, xc = 0.0, dgc = 0.0, dgl = 0.0;
+    if (live) {
+        if (a.a[0] >= 0) constrain_row_pair_chain<TS>(st, a.pstart, a.npend, a.a[0], c, m[0][0], m[0][1]);
+        if (a.a[1] >= 0) constrain_row_pair_chain<TS>(st, a.pstart, a.npend, a.a[1], c, m[1][0], m[1][1]);
+        s0 = strip[c]; s1 = strip[ldm + c]; s2 = strip[2 * ldm + c];
+        xc = x[3 + c];
+        const double *__restrict__ dg = st.diag[st.dcur] + 3 * (c >> 1);
+        if (c & 1) { dgl = dg[1]; dgc = dg[2]; } else dgc = dg[0];
+    }
+
+    // (2) the small part, once per workgroup
+    linear_small_part<TS>(st, a, sm, sol);
+    const bool ok = sol.outcome == 1;
+
+    // (3) the column's share of G, K, x and the strip
+    const int64_t pad_end = st.tm.padded(a.n_mm);
+    const int64_t out_off = (int64_t)ring_slot(a.pstart, a.npend, st.pcap) * st.pair_stride;
+    double2 *__restrict__ Gout = reinterpret_cast<double2 *>(st.Gp + out_off);
+    double2 *__restrict__ Kout = reinterpret_cast<double2 *>(st.Kp + out_off);
+    double g0 = 0.0, g1 = 0.0, k0 = 0.0, k1 = 0.0;
+    if (live) {
+        if (ok) {
+            // G(:, c) = Hr strip(:, c) + sum_b Hl_b P(rows of l_b, c), in this order
+            g0 = (a.H[0] * s0 + a.H[1] * s1) + a.H[2] * s2;
+            g1 = (a.H[7] * s0 + a.H[8] * s1) + a.H[9] * s2;
+            if (a.a[0] >= 0) { g0 += a.H[3] * m[0][0] + a.H[4] * m[0][1]; g1 += a.H[10] * m[0][0] + a.H[11] * m[0][1]; }
+            if (a.a[1] >= 0) { g0 += a.H[5] * m[1][0] + a.H[6] * m[1][1]; g1 += a.H[12] * m[1][0] + a.H[13] * m[1][1]; }
+            k0 = g0 * sol.Si[0] + g1 * sol.Si[2];
+            k1 = g0 * sol.Si[1] + g1 * sol.Si[3];
+        }
+        Gout[c] = make_double2(g0, g1);
+        Kout[c] = make_double2(k0, k1);
+        if (st.Gp32) {                                          // the float copies, as k_gather writes them (planar, K negated)
+            st.Gp32[out_off + c] = (float)g0; st.Gp32[out_off + ldm + c] = (float)g1;
+            st.Kp32[out_off + c] = -(float)k0; st.Kp32[out_off + ldm + c] = -(float)k1;
+        }
+        x_nxt[3 + c] = xc + (k0 * sol.nu[0] + k1 * sol.nu[1]);
+        strip_nxt[c] = s0 - (sol.Kr[0][0] * g0 + sol.Kr[0][1] * g1);
+        strip_nxt[ldm + c] = s1 - (sol.Kr[1][0] * g0 + sol.Kr[1][1] * g1);
+        strip_nxt[2 * ldm + c] = s2 - (sol.Kr[2][0] * g0 + sol.Kr[2][1] * g1);
+    } else if (c < pad_end) {                                   // zeros up to the padded width: the pass reads whole tile-wide slices
+        Gout[c] = make_double2(0.0, 0.0);
+        Kout[c] = make_double2(0.0, 0.0);
+        if (st.Gp32) {
+            st.Gp32[out_off + c] = 0.0f; st.Gp32[out_off + ldm + c] = 0.0f;
+            st.Kp32[out_off + c] = -0.0f; st.Kp32[out_off + ldm + c] = -0.0f;
+        }
+    }
+    // (3b) this pair on every landmark's own 2x2 block, as k_gather step (4b): the live copies never carry a pending pair
+    {
+        const double2 kn = make_double2(k0, k1), gn = make_double2(g0, g1);
+        const double2 gl = make_double2(lane_xor1(gn.x), lane_xor1(gn.y));       // the partner column's G (odd lanes: G(:, 2k))
+        const double ndc = rank2_apply(dgc, kn, gn), ndl = rank2_apply(dgl, kn, gl);
+        if (live) {
+            double *__restrict__ dn = st.diag[st.dcur ^ 1] + 3 * (c >> 1);
+            if (c & 1) { dn[1] = ndl; dn[2] = ndc; } else dn[0] = ndc;
+        }
+    }
+    // (4) workgroup 0: x_r, Prr' = Prr - K_r G_r kept EXACTLY symmetric as k_gather_constrain keeps it (both mirrors take the
+    //     lower-triangle entry's value), the record and the counters
+    if (blockIdx.x == 0) {
+        if (tid < 3) x_nxt[tid] = x[tid] + (sol.Kr[tid][0] * sol.nu[0] + sol.Kr[tid][1] * sol.nu[1]);
+        if (tid >= 64 && tid < 73) {
+            const int q = tid - 64, r = q / 3, b = q - 3 * r;
+            const int rr = r > b ? r : b, bb = r > b ? b : r;
+            st.prr[cur ^ 1][3 * r + b] = sol.prr[3 * rr + bb] - (sol.Kr[rr][0] * sol.Gr[0][bb] + sol.Kr[rr][1] * sol.Gr[1][bb]);
+        }
+        if (tid >= 128 && tid < 128 + kLinearRecordDoubles) rec[tid - 128] = sol.rec[tid - 128];
+        if (tid == 0 && !ok) {
+            const int which = sol.outcome == 0 ? 0 : 1;
+            cnt[which] = cnt[which] + 1;
+        }
+    }
+}

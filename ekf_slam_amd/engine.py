@@ -380,6 +380,97 @@ class Engine:
         rows = rows[np.lexsort((rows, d2[rows]))]
         return [(int(i), int(partner[i]), float(d2[i])) for i in rows]
 
+    # ---- linear observations: update-steps with a constant Jacobian (include/ekfslam.h: ekf_observe_linear) ----
+    @staticmethod
+    def _linear_obs(z, R, Hr, landmarks, Hl, gate, wrap, rows):
+        rows = int(rows)
+        if rows not in (1, 2):
+            raise ValueError("linear observation: rows is 1 or 2")
+        o = L.EkfLinearObs()
+        zv = np.zeros(2)
+        zin = _vec(z)
+        if not rows <= zin.size <= 2:
+            raise ValueError("linear observation: z has `rows` values")
+        zv[:rows] = zin[:rows]
+        Rm = np.zeros((2, 2))
+        if R is not None:
+            Ra = np.asarray(R, dtype=np.float64)
+            if rows == 1 and Ra.size == 1:
+                Rm[0, 0] = float(Ra.reshape(-1)[0])
+            elif Ra.size == 4:
+                Rm[:] = Ra.reshape(2, 2)
+            else:
+                raise ValueError("linear observation: R is 2 x 2 (or a variance with rows = 1)")
+        Hrm = np.zeros((2, 3))
+        if Hr is not None:
+            Ha = np.asarray(Hr, dtype=np.float64)
+            if Ha.size == 6:
+                Hrm[:] = Ha.reshape(2, 3)
+            elif rows == 1 and Ha.size == 3:
+                Hrm[0] = Ha.reshape(-1)
+            else:
+                raise ValueError("linear observation: Hr is 2 x 3 (or 3 values with rows = 1)")
+        lms = [int(k) for k in landmarks]
+        blocks = list(Hl)
+        if len(lms) > 2 or len(blocks) != len(lms):
+            raise ValueError("linear observation: at most two landmarks, one 2 x 2 block each")
+        o.lm[0] = o.lm[1] = -1
+        for b, (k, blk) in enumerate(zip(lms, blocks)):
+            Ba = np.asarray(blk, dtype=np.float64)
+            Bm = np.zeros((2, 2))
+            if Ba.size == 4:
+                Bm[:] = Ba.reshape(2, 2)
+            elif rows == 1 and Ba.size == 2:
+                Bm[0] = Ba.reshape(-1)
+            else:
+                raise ValueError("linear observation: a landmark block is 2 x 2 (or 2 values with rows = 1)")
+            o.lm[b] = k
+            for q, v in enumerate(Bm.reshape(-1, order="F")):
+                o.Hl[b][q] = v
+        for q in range(2):
+            o.z[q] = zv[q]
+        for q, v in enumerate(Rm.reshape(-1, order="F")):
+            o.R[q] = v
+        for q, v in enumerate(Hrm.reshape(-1, order="F")):
+            o.Hr[q] = v
+        o.gate = float(gate)
+        w = tuple(wrap) + (0, 0)
+        o.wrap_deg[0], o.wrap_deg[1] = int(bool(w[0])), int(bool(w[1]))
+        o.rows = rows
+        return o
+
+    @staticmethod
+    def _linear_result(res):
+        return {"nu": np.array(res.nu[:]), "S": np.array(res.S[:]).reshape(2, 2, order="F"), "d2": float(res.d2),
+                "outcome": int(res.outcome)}
+
+    def observe_linear(self, z, R, Hr=None, landmarks=(), Hl=(), gate=float("inf"), wrap=(0, 0), rows=2, wait=False):
+        """'H x was observed as z with noise covariance R' as an UPDATE-STEP (ekf_observe_linear): H = the 2 x 3 block Hr on the robot
+        state (theta in degrees) plus one 2 x 2 block Hl[b] on each of up to two landmarks (0-based).  Enters the pending ring like a
+        correction: nothing is flushed, and with wait=False nothing is waited for (returns None).  wait=True returns
+        {'nu', 'S', 'd2', 'outcome'} of the launch (outcome: EKF_LINEAR_APPLIED / _GATED; an irregular S raises EkfError)."""
+        o = self._linear_obs(z, R, Hr, landmarks, Hl, gate, wrap, rows)
+        if not wait:
+            self._check(self.lib.ekf_observe_linear(self.h, ctypes.byref(o), None))
+            return None
+        res = L.EkfLinearResult()
+        self._check(self.lib.ekf_observe_linear(self.h, ctypes.byref(o), ctypes.byref(res)))
+        return self._linear_result(res)
+
+    def linear_innovation(self, z, R, Hr=None, landmarks=(), Hl=(), gate=float("inf"), wrap=(0, 0), rows=2):
+        """{'nu', 'S', 'd2', 'outcome'} observe_linear(..., wait=True) would report under the current state, bit for bit; changes
+        nothing and flushes nothing (ekf_linear_innovation).  An irregular S is reported (outcome EKF_LINEAR_IRREGULAR, d2 NaN)."""
+        o = self._linear_obs(z, R, Hr, landmarks, Hl, gate, wrap, rows)
+        res = L.EkfLinearResult()
+        self._check(self.lib.ekf_linear_innovation(self.h, ctypes.byref(o), ctypes.byref(res)))
+        return self._linear_result(res)
+
+    def linear_rejections(self):
+        """(irregular, gated): observe_linear launches since the last call that did not apply; synchronises and resets the counts."""
+        a, b = ctypes.c_int64(), ctypes.c_int64()
+        self._check(self.lib.ekf_linear_rejections(self.h, ctypes.byref(a), ctypes.byref(b)))
+        return int(a.value), int(b.value)
+
     def load_lowrank_state(self, x, s, d, U):
         x, s, d = _vec(x), _vec(s), _vec(d)
         U = np.asfortranarray(np.asarray(U, dtype=np.float64))

@@ -246,6 +246,51 @@ class _EkfBase:
             merges.extend((k, d, float(v)) for (k, d, _), v in zip(batch, d2))
         return merges
 
+    def observe_linear(self, z, R, Hr=None, landmarks=(), Hl=(), gate=float("inf"), wrap=(0, 0), rows=2, wait=False):
+        """'H x was observed as z with noise covariance R' for a constant H: the 2 x 3 block Hr on the robot state (x, y, theta in
+        degrees) plus one 2 x 2 block Hl[b] on each of up to two landmarks (1-based numbers) -- the exact Kalman update, as an
+        UPDATE-STEP: it enters the pending ring like a correction of measure(), flushes nothing and, unless wait=True, waits for
+        nothing.  Applied only if d2 = nu' S^-1 nu <= gate; rows named in `wrap` are angles in degrees whose innovation is wrapped
+        into (-180, 180]; rows=1 is a scalar observation.  wait=True returns {'nu', 'S', 'd2', 'outcome'} (ekf_observe_linear).
+        The reference has no such method."""
+        lms = self._landmark_numbers("observe_linear", *list(landmarks))
+        rows = int(rows)
+        if rows not in (1, 2):
+            raise ValueError("observe_linear: rows is 1 or 2")
+        obs = self._e._linear_obs(z, R, Hr, [k - 1 for k in lms], Hl, gate, wrap, rows)      # (the engine's own shape checks)
+        out = self._e.observe_linear(z, R, Hr, [k - 1 for k in lms], Hl, gate, wrap, rows, wait)
+        if self.log is not None:
+            Rm = np.array(obs.R[:]).reshape(2, 2, order="F")
+            Hrm = np.array(obs.Hr[:]).reshape(2, 3, order="F")
+            blocks = [np.array(obs.Hl[b][:]).reshape(2, 2, order="F") for b in range(len(lms))]
+            self.log.record_observation(np.array(obs.z[:]), Rm, Hrm, lms, blocks, gate, wrap, rows)
+        return out
+
+    def linear_innovation(self, z, R, Hr=None, landmarks=(), Hl=(), gate=float("inf"), wrap=(0, 0), rows=2):
+        """{'nu', 'S', 'd2', 'outcome'} observe_linear(..., wait=True) would report now (1-based landmarks); changes and flushes
+        nothing (ekf_linear_innovation)."""
+        lms = self._landmark_numbers("linear_innovation", *list(landmarks))
+        return self._e.linear_innovation(z, R, Hr, [k - 1 for k in lms], Hl, gate, wrap, rows)
+
+    def linear_rejections(self):
+        """(irregular, gated): observe_linear calls since the last look that did not apply; resets the counts."""
+        return self._e.linear_rejections()
+
+    def fix_landmark(self, i, pos, R, gate=float("inf"), wait=False):
+        """'Landmark i (1-based) is the surveyed point pos, known to within the covariance R': H = I2 on that landmark."""
+        (i,) = self._landmark_numbers("fix_landmark", i)
+        return self.observe_linear(_vec(pos, 2), R, None, [i], [np.eye(2)], gate=gate, wait=wait)
+
+    def fix_robot_position(self, pos, R, gate=float("inf"), wait=False):
+        """'The robot is at pos, to within the covariance R' (a GPS fix): Hr = [I2 0]."""
+        return self.observe_linear(_vec(pos, 2), R, np.array([[1.0, 0.0, 0.0], [0.0, 1.0, 0.0]]), gate=gate, wait=wait)
+
+    def fix_robot_heading(self, theta_deg, var, gate=float("inf"), wait=False):
+        """'The heading reads theta_deg (degrees), with variance var' (a compass): one row, Hr(0, 2) = 1, the innovation wrapped
+        into (-180, 180]."""
+        return self.observe_linear([float(theta_deg)], [[float(var), 0.0], [0.0, 0.0]], np.array([[0.0, 0.0, 1.0], [0.0, 0.0, 0.0]]),
+                                   gate=gate, wrap=(1, 0), rows=1, wait=wait)
+
     def _push_params(self):
         pass
 

@@ -11,20 +11,29 @@ log too, or a replay no longer reproduces the run: `record_edit` notes one, with
 at the position `len(log)` it was made at -- it is replayed after step len(log) - 1 and before step len(log).  A log without edits
 is written exactly as before (format 1, the same arrays); one with edits as format 2, with the edit arrays added; one that holds a
 'merge_batch' edit (merge_landmarks_batch: idx = [keep1, drop1, keep2, drop2, ...], R shared) as format 3, which has the arrays of
-format 2 -- a reader of format 2 alone would not know the fourth kind.
+format 2 -- a reader of format 2 alone would not know the fourth kind; one that holds an 'observe' edit (observe_linear: a linear
+observation made between two steps -- idx = the 0, 1 or 2 landmarks that carry a block, the delta slot = z, R, and per observation Hr,
+the landmark blocks Hl, gate, wrap and rows in arrays of their own) as format 4.
 """
 import numpy as np
 
 FORMAT = "ekfslam-trajectory-1"
 FORMAT_EDITS = "ekfslam-trajectory-2"
 FORMAT_BATCH = "ekfslam-trajectory-3"
-EDIT_KINDS = ("remove", "constrain", "merge", "merge_batch")
+FORMAT_OBSERVE = "ekfslam-trajectory-4"
+EDIT_KINDS = ("remove", "constrain", "merge", "merge_batch")        # what record_edit takes
+OBSERVE = "observe"                                                  # the fifth kind: record_observation's, number 4 in a file
+_KINDS = EDIT_KINDS + (OBSERVE,)
+_STEP_ARRAYS = ("u", "obs_ptr", "obs", "lm_ptr", "lm_index", "lm_loc")
+_EDIT_ARRAYS = ("edit_step", "edit_kind", "edit_ptr", "edit_idx", "edit_delta", "edit_R")
+_OBSERVE_ARRAYS = ("observe_edit", "observe_Hr", "observe_Hl", "observe_gate", "observe_wrap", "observe_rows")
 
 
 class TrajectoryLog:
     def __init__(self):
         self.u, self.obs, self.lm_index, self.lm_loc = [], [], [], []
         self.edits = []             # (step, kind, idx (1-based numbers), delta[2], R[2x2]) in the order they were made
+        self.observations = {}      # position in self.edits of an 'observe' edit -> {Hr (2x3), Hl (2x2x2), gate, wrap (2), rows}
 
     def __len__(self):
         return len(self.u)
@@ -54,6 +63,31 @@ class TrajectoryLog:
         Rm = np.zeros((2, 2)) if R is None else np.asarray(R, dtype=np.float64).reshape(2, 2).copy()
         self.edits.append((len(self), kind, idx.astype(np.int64), d, Rm))
 
+    def record_observation(self, z, R, Hr=None, landmarks=(), Hl=(), gate=float("inf"), wrap=(0, 0), rows=2):
+        """A linear observation (observe_linear of ekf_slam_amd/slam.py) made now, i.e. after the len(self) steps recorded so far:
+        z, R (2 x 2), the robot block Hr (2 x 3, None: zeros), the 1-based landmarks that carry a block and their 2 x 2 blocks Hl,
+        gate, wrap and rows -- full-size arrays, as the wrapper hands them to the engine."""
+        lms = np.asarray(list(landmarks), dtype=np.float64).reshape(-1)
+        if not np.all(lms == np.floor(lms)):
+            raise ValueError("record_observation: landmark indices are whole numbers")
+        blocks = [np.asarray(b, dtype=np.float64).reshape(2, 2) for b in Hl]
+        if lms.size > 2 or len(blocks) != lms.size:
+            raise ValueError("record_observation: at most two landmarks, one 2 x 2 block each")
+        if int(rows) not in (1, 2):
+            raise ValueError("record_observation: rows is 1 or 2")
+        Hlm = np.zeros((2, 2, 2))
+        for b, blk in enumerate(blocks):
+            Hlm[b] = blk
+        zv = np.zeros(2)
+        zin = np.asarray(z, dtype=np.float64).reshape(-1)
+        zv[:zin.size] = zin
+        w = tuple(wrap) + (0, 0)
+        self.observations[len(self.edits)] = dict(
+            Hr=np.zeros((2, 3)) if Hr is None else np.asarray(Hr, dtype=np.float64).reshape(2, 3).copy(), Hl=Hlm, gate=float(gate),
+            wrap=np.array([int(bool(w[0])), int(bool(w[1]))], dtype=np.int64), rows=int(rows))
+        self.edits.append((len(self), OBSERVE, lms.astype(np.int64), zv,
+                           np.zeros((2, 2)) if R is None else np.asarray(R, dtype=np.float64).reshape(2, 2).copy()))
+
     def save(self, path):
         def ragged(parts, width):
             ptr = np.cumsum([0] + [len(p) for p in parts])
@@ -68,8 +102,16 @@ class TrajectoryLog:
             return
         e_ptr, e_idx = ragged([e[2] for e in self.edits], 0)
         fmt = FORMAT_BATCH if any(e[1] == "merge_batch" for e in self.edits) else FORMAT_EDITS
+        if self.observations:
+            fmt = FORMAT_OBSERVE
+            at = sorted(self.observations)
+            ob = [self.observations[q] for q in at]
+            arrays.update(observe_edit=np.array(at, dtype=np.int64), observe_Hr=np.array([o["Hr"] for o in ob]).reshape(-1, 2, 3),
+                          observe_Hl=np.array([o["Hl"] for o in ob]).reshape(-1, 2, 2, 2), observe_gate=np.array([o["gate"] for o in ob]),
+                          observe_wrap=np.array([o["wrap"] for o in ob], dtype=np.int64).reshape(-1, 2),
+                          observe_rows=np.array([o["rows"] for o in ob], dtype=np.int64))
         np.savez_compressed(path, format=np.array(fmt), edit_step=np.array([e[0] for e in self.edits], dtype=np.int64),
-                            edit_kind=np.array([EDIT_KINDS.index(e[1]) for e in self.edits], dtype=np.int64), edit_ptr=e_ptr,
+                            edit_kind=np.array([_KINDS.index(e[1]) for e in self.edits], dtype=np.int64), edit_ptr=e_ptr,
                             edit_idx=e_idx.astype(np.int64), edit_delta=np.array([e[3] for e in self.edits]).reshape(-1, 2),
                             edit_R=np.array([e[4] for e in self.edits]).reshape(-1, 2, 2), **arrays)
 
@@ -77,8 +119,12 @@ class TrajectoryLog:
     def load(path):
         g = np.load(path, allow_pickle=False)
         fmt = str(g["format"])
-        if fmt not in (FORMAT, FORMAT_EDITS, FORMAT_BATCH):
-            raise ValueError("not an %s / %s / %s file" % (FORMAT, FORMAT_EDITS, FORMAT_BATCH))
+        if fmt not in (FORMAT, FORMAT_EDITS, FORMAT_BATCH, FORMAT_OBSERVE):
+            raise ValueError("not an %s / %s / %s / %s file" % (FORMAT, FORMAT_EDITS, FORMAT_BATCH, FORMAT_OBSERVE))
+        need = _STEP_ARRAYS + (_EDIT_ARRAYS if fmt != FORMAT else ()) + (_OBSERVE_ARRAYS if fmt == FORMAT_OBSERVE else ())
+        missing = [k for k in need if k not in g.files]
+        if missing:
+            raise ValueError("an %s file holds %s: %s is missing" % (fmt, ", ".join(need), ", ".join(missing)))
         t = TrajectoryLog()
         for k in range(len(g["u"])):
             a, b = g["obs_ptr"][k], g["obs_ptr"][k + 1]
@@ -87,23 +133,31 @@ class TrajectoryLog:
         if fmt != FORMAT:
             for q in range(len(g["edit_step"])):
                 a, b = g["edit_ptr"][q], g["edit_ptr"][q + 1]
-                t.edits.append((int(g["edit_step"][q]), EDIT_KINDS[int(g["edit_kind"][q])], g["edit_idx"][a:b].astype(np.int64),
+                t.edits.append((int(g["edit_step"][q]), _KINDS[int(g["edit_kind"][q])], g["edit_idx"][a:b].astype(np.int64),
                                 g["edit_delta"][q].copy(), g["edit_R"][q].copy()))
+        if fmt == FORMAT_OBSERVE:
+            for k, q in enumerate(g["observe_edit"]):
+                t.observations[int(q)] = dict(Hr=g["observe_Hr"][k].copy(), Hl=g["observe_Hl"][k].copy(), gate=float(g["observe_gate"][k]),
+                                              wrap=g["observe_wrap"][k].astype(np.int64), rows=int(g["observe_rows"][k]))
         return t
 
     def replay(self, engine, start=0, stop=None):
         """predict + measure for steps [start, stop) on anything with predict(u) / measure(obs, u, idx, loc) -- an Engine.  The edits
         recorded at positions [start, stop) are applied in front of their step through the engine's remove_landmarks /
-        constrain_landmarks / merge_landmarks / merge_landmarks_batch (0-based there: the recorded 1-based numbers are converted here); the ones recorded
+        constrain_landmarks / merge_landmarks / merge_landmarks_batch / observe_linear (0-based there: the recorded 1-based numbers are converted here); the ones recorded
         at position len(self), after the last step, when stop is the end of the log."""
         stop = len(self) if stop is None else stop
 
         def apply_edits(at):
-            for step, kind, idx, delta, R in self.edits:
+            for q, (step, kind, idx, delta, R) in enumerate(self.edits):
                 if step != at:
                     continue
                 idx0 = [int(i) - 1 for i in idx]
-                if kind == "remove":
+                if kind == OBSERVE:
+                    o = self.observations[q]
+                    engine.observe_linear(delta[:o["rows"]], R, o["Hr"], idx0, [o["Hl"][b] for b in range(len(idx0))], gate=o["gate"],
+                                          wrap=tuple(int(w) for w in o["wrap"]), rows=o["rows"])
+                elif kind == "remove":
                     engine.remove_landmarks(idx0)
                 elif kind == "constrain":
                     engine.constrain_landmarks(idx0[0], idx0[1], delta, R)

@@ -350,6 +350,50 @@ int32_t ekf_landmark_distance(ekf_handle *h, int64_t i, int64_t j, const double 
  * Changes nothing: x, s, P and ekf_P_digest are afterwards what they were; ekf_pending reports 0, as after ekf_landmark_distance. */
 int32_t ekf_nearest_landmarks(ekf_handle *h, const double R[4] /* 2x2 column-major, NULL = zero */,
                               double *d2 /* N */, int64_t *partner /* N */);
+/* A LINEAR observation with a constant Jacobian: "H x was observed as z, with noise covariance R" -- a surveyed landmark position, a GPS
+ * fix of the robot, a compass reading, a relation between two landmarks.  H has a 2 x 3 block on the robot state and 2 x 2 blocks on up
+ * to two landmarks, so the Kalman update is exact, with no linearisation:
+ *     G = H P,  S = G H' + R,  nu = z - H x (rows named in wrap_deg wrapped into (-180, 180]),  K = G' S^-1,  x += K nu,  P -= K G,
+ *     d2 = nu' S^-1 nu
+ * (ekf_constrain_landmarks is the case Hr = 0, Hl = (+I2, -I2)).  rows == 1 is a scalar observation: row 1 of z, H and R is ignored and
+ * runs as the exactly empty second row (H(1,:) = 0, R01 = R10 = 0, R11 = 1, z1 = 0), so S = [[s, 0], [0, 1]], nu1 = 0 and d2 = nu0^2 / s.
+ * x(3), the heading, is NOT re-wrapped afterwards (as after ekf_correct).
+ *
+ * ekf_observe_linear is an UPDATE-STEP like ekf_correct, not a synchronising edit: a recorded predict(u) is carried out, then ONE launch
+ * (counted under EKF_KERNEL_GATHER) reads its operands patched with the pairs still pending, writes its pair (K, G) into the next slot
+ * of the pending ring and updates x; ekf_pending grows by one and the pass over P runs at the batch boundary cfg.batch sets (beside
+ * the next steps with cfg.async_flush).  Nothing is flushed and, with res == NULL, nothing is waited for.  With res != NULL the call
+ * waits for that launch's record (one small readback) and reports nu, S, d2 and the outcome.
+ * An S that is not finite or not positive definite (EKF_LINEAR_IRREGULAR: a landmark fixed twice with R = 0) or a d2 above `gate`
+ * (EKF_LINEAR_GATED) turns the launch into a no-op: a zero pair takes the slot (ekf_pending still grows by one) and every value the
+ * getters report stays bit for bit what it was.  With res != NULL an irregular S returns EKF_ERR_STATE and a gated observation EKF_OK
+ * with res->outcome == EKF_LINEAR_GATED; with res == NULL the call returns EKF_OK either way and ekf_linear_rejections counts them.
+ * Refused before anything changes, in this order: obs NULL, rows not 1 or 2, a non-finite entry of z, H or R (of the rows in use), a
+ * NaN gate, an R that ekf_constrain_landmarks would refuse (rows == 1: only R00 >= 0 matters), lm[0] == lm[1] >= 0, an lm below -1
+ * (EKF_ERR_INVALID_ARG); a handle with world > 1 (EKF_ERR_INVALID_ARG: sharding -- a landmark block needs that landmark's exchanged
+ * row-panel, which is not built; a lone shard with cfg.force_sharded works); a sharded correction between begin and finish
+ * (EKF_ERR_STATE); then the device-resident measure loop is settled (N exact) and an lm outside [0, N) is EKF_ERR_INDEX.
+ *
+ * ekf_linear_innovation is the gate a host asks for: nu, S, d2 and the outcome ekf_observe_linear WOULD report under the current
+ * state, bit for bit, read patched with the pending pairs -- no flush, and x, s, P, ekf_P_digest and ekf_pending stay what they were
+ * (a recorded predict(u) is carried out first, as by every reader).  Arguments and refusals as above; an irregular S is no error here.
+ * ekf_linear_rejections synchronises, reports how many ekf_observe_linear launches since the last call did not apply (S irregular;
+ * gated) and resets both counts; either pointer may be NULL. */
+enum { EKF_LINEAR_APPLIED = 1, EKF_LINEAR_IRREGULAR = 0, EKF_LINEAR_GATED = 2 };
+typedef struct ekf_linear_obs {
+    double  z[2];         /* the observed value of H x                                                    */
+    double  R[4];         /* 2x2 column-major noise covariance (rules of ekf_constrain_landmarks' R)      */
+    double  Hr[6];        /* 2x3 column-major block on the robot state (x, y, theta in DEGREES); zeros = none */
+    int64_t lm[2];        /* 0-based landmarks carrying a block, -1 = none; if both >= 0 they differ      */
+    double  Hl[2][4];     /* 2x2 column-major block on landmark lm[b]; ignored where lm[b] == -1          */
+    double  gate;         /* apply only if d2 <= gate; +inf = no gate                                     */
+    int32_t wrap_deg[2];  /* row r is an angle in degrees: nu_r is wrapped into (-180, 180]               */
+    int32_t rows;         /* 2, or 1: a scalar observation -- row 1 of z, H, R is ignored                 */
+} ekf_linear_obs;
+typedef struct ekf_linear_result { double nu[2]; double S[4] /* column-major */; double d2; int32_t outcome; } ekf_linear_result;
+int32_t ekf_observe_linear(ekf_handle *h, const ekf_linear_obs *obs, ekf_linear_result *res /* NULL: do not wait */);
+int32_t ekf_linear_innovation(ekf_handle *h, const ekf_linear_obs *obs, ekf_linear_result *res /* required */);
+int32_t ekf_linear_rejections(ekf_handle *h, int64_t *irregular, int64_t *gated);   /* synchronises, reads and resets */
 /* Diagnostic -- a fault injector for tests of the device-resident measure loop's verification, of no use to a host: overwrites the DEVICE copy
  * of signature idx (0-based) and leaves the host mirror alone.  The next ekf_measure whose association involves that landmark then queues its
  * launches from a prediction the device contradicts; every launch stays inside the state (a correction falls back to the predicted landmark,

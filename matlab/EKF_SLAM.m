@@ -114,6 +114,41 @@ classdef EKF_SLAM < handle
             if nargin < 3 || isempty(R), R = zeros(2); end
             d2 = h.gateway('merge_landmarks_batch', double(reshape(pairs, [], 2)), double(R));
         end
+        function res = observeLinear(h, z, R, Hr, lm, Hl, gate, wrap, rows, wait)
+            % 'H x was observed as z, with noise covariance R' for a constant H: Hr (2x3) on the robot state [x y theta_deg] plus
+            % one 2x2 block Hl(:, :, b) on each of the landmarks lm (0, 1 or 2 numbers, 1-based).  An UPDATE-STEP like a correction
+            % of measure(): nothing is flushed and, unless wait is true, nothing is waited for.  Applied only if nu' S^-1 nu <= gate;
+            % rows named in wrap are angles in degrees (innovation wrapped into (-180, 180]); rows = 1: a scalar observation.
+            % wait: res = [nu(1) nu(2) S(:)' d2 outcome] (outcome 1 applied, 2 gated).  Not a method of the reference.
+            if nargin < 4 || isempty(Hr), Hr = zeros(2, 3); end
+            if nargin < 5, lm = []; end
+            if nargin < 6, Hl = []; end
+            if nargin < 7 || isempty(gate), gate = Inf; end
+            if nargin < 8 || isempty(wrap), wrap = [0 0]; end
+            if nargin < 9 || isempty(rows), rows = 2; end
+            if nargin < 10 || isempty(wait), wait = false; end
+            z = double(z(:)); if numel(z) < 2, z(2) = 0; end
+            res = h.gateway('observe_linear', z, double(R), double(Hr), double(lm(:)), double(Hl), double(gate), double(wrap(:)), ...
+                            double(rows), double(wait));
+        end
+        function res = fixLandmark(h, i, pos, R, gate, wait)
+            % 'Landmark i is the surveyed point pos, known to within the covariance R': H = eye(2) on that landmark.
+            if nargin < 5 || isempty(gate), gate = Inf; end
+            if nargin < 6 || isempty(wait), wait = false; end
+            res = h.observeLinear(pos, R, [], i, eye(2), gate, [0 0], 2, wait);
+        end
+        function res = fixRobotPosition(h, pos, R, gate, wait)
+            % 'The robot is at pos, to within the covariance R' (a GPS fix): Hr = [eye(2) [0; 0]].
+            if nargin < 4 || isempty(gate), gate = Inf; end
+            if nargin < 5 || isempty(wait), wait = false; end
+            res = h.observeLinear(pos, R, [1 0 0; 0 1 0], [], [], gate, [0 0], 2, wait);
+        end
+        function res = fixRobotHeading(h, thetaDeg, variance, gate, wait)
+            % 'The heading reads thetaDeg, with this variance' (a compass): one row, Hr(1, 3) = 1, the innovation wrapped.
+            if nargin < 4 || isempty(gate), gate = Inf; end
+            if nargin < 5 || isempty(wait), wait = false; end
+            res = h.observeLinear([thetaDeg 0], [variance 0; 0 0], [0 0 1; 0 0 0], [], [], gate, [1 0], 1, wait);
+        end
         function merges = fuseDuplicatesBatched(h, gate, R, maxMerges)
             % fuseDuplicates with the pairs of one search fused in one mergeLandmarksBatch call: search; walk the candidates in
             % (d2, k) order and take [partner(k) k] when k is not yet a keep or a drop and partner(k) is not yet a drop (a keep may

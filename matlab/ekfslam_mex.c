@@ -22,7 +22,7 @@
 #include "mex.h"
 
 /* The map-editing entry points (ekf_remove_landmarks; ekf_constrain_landmarks, ekf_merge_landmarks, ekf_landmark_distance;
- * ekf_nearest_landmarks; ekf_merge_landmarks_batch) are the ones this gateway can live without: bound weakly, so that the gateway still links against a libekfslam (or a stand-in) that
+ * ekf_nearest_landmarks; ekf_merge_landmarks_batch) and the linear observation (ekf_observe_linear) are the ones this gateway can live without: bound weakly, so that the gateway still links against a libekfslam (or a stand-in) that
  * predates them; their commands then raise a MATLAB error instead. */
 #if defined(__GNUC__)
 #pragma weak ekf_remove_landmarks
@@ -31,12 +31,14 @@
 #pragma weak ekf_landmark_distance
 #pragma weak ekf_nearest_landmarks
 #pragma weak ekf_merge_landmarks_batch
+#pragma weak ekf_observe_linear
 #define HAVE_REMOVE_LANDMARKS (ekf_remove_landmarks != 0)
 #define HAVE_CONSTRAIN_LANDMARKS (ekf_constrain_landmarks != 0)
 #define HAVE_MERGE_LANDMARKS (ekf_merge_landmarks != 0)
 #define HAVE_LANDMARK_DISTANCE (ekf_landmark_distance != 0)
 #define HAVE_NEAREST_LANDMARKS (ekf_nearest_landmarks != 0)
 #define HAVE_MERGE_LANDMARKS_BATCH (ekf_merge_landmarks_batch != 0)
+#define HAVE_OBSERVE_LINEAR (ekf_observe_linear != 0)
 #else
 #define HAVE_REMOVE_LANDMARKS 1
 #define HAVE_CONSTRAIN_LANDMARKS 1
@@ -44,6 +46,7 @@
 #define HAVE_LANDMARK_DISTANCE 1
 #define HAVE_NEAREST_LANDMARKS 1
 #define HAVE_MERGE_LANDMARKS_BATCH 1
+#define HAVE_OBSERVE_LINEAR 1
 #endif
 
 static void need(int nrhs, int want, const char *cmd) {
@@ -225,6 +228,42 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
         if (rc != EKF_OK) { mxDestroyArray(d2); mxDestroyArray(partner); check(h, rc); }
         plhs[0] = d2;
         if (nlhs > 1) plhs[1] = partner; else mxDestroyArray(partner);
+        return;
+    }
+    if (!strcmp(cmd, "observe_linear")) {         /* res = (h, z 2, R 2x2, Hr 2x3, lm 0..2 numbers (1-based), Hl 2x2xk, gate, wrap 2, rows, wait):
+                                                     wait ~= 0: res = [nu(1) nu(2) S(1,1) S(2,1) S(1,2) S(2,2) d2 outcome]; else [] and nothing waits */
+        ekf_linear_obs o;
+        ekf_linear_result res;
+        need(nrhs, 11, cmd);
+        if (!HAVE_OBSERVE_LINEAR) mexErrMsgIdAndTxt("ekfslam:usage", "observe_linear: this libekfslam has no ekf_observe_linear");
+        const double *z = two_of(prhs[2], cmd, "z"), *R = r2x2_of(prhs[3], cmd), *wrap = two_of(prhs[8], cmd, "wrap");
+        if (!prhs[4] || mxGetNumberOfElements(prhs[4]) != 6 || !mxGetPr(prhs[4])) mexErrMsgIdAndTxt("ekfslam:usage", "observe_linear: Hr needs 2 x 3 elements");
+        const mwSize k = prhs[5] ? mxGetNumberOfElements(prhs[5]) : 0;
+        if (k > 2 || (k && (mxGetClassID(prhs[5]) != mxDOUBLE_CLASS || !mxGetPr(prhs[5]))))
+            mexErrMsgIdAndTxt("ekfslam:usage", "observe_linear: lm names at most two landmarks, class double");
+        if ((prhs[6] ? mxGetNumberOfElements(prhs[6]) : 0) != 4 * k || (k && !mxGetPr(prhs[6])))
+            mexErrMsgIdAndTxt("ekfslam:usage", "observe_linear: Hl needs one 2 x 2 block per landmark");
+        for (int r = 0; r < 2; ++r) { o.z[r] = z[r]; o.lm[r] = -1; o.wrap_deg[r] = wrap[r] != 0.0; }
+        for (int q = 0; q < 8; ++q) o.Hl[q >> 2][q & 3] = 0.0;
+        for (int q = 0; q < 4; ++q) o.R[q] = R[q];
+        for (int q = 0; q < 6; ++q) o.Hr[q] = mxGetPr(prhs[4])[q];
+        for (mwSize b = 0; b < k; ++b) {                       /* whole numbers a landmark could carry; 1-based -> 0-based, once */
+            const double v = mxGetPr(prhs[5])[b];
+            if (!(v >= -9.0e15 && v <= 9.0e15) || v != (double)(int64_t)v) mexErrMsgIdAndTxt("ekfslam:usage", "observe_linear: landmark numbers are whole numbers");
+            o.lm[b] = (int64_t)v - 1;
+            for (int q = 0; q < 4; ++q) o.Hl[b][q] = mxGetPr(prhs[6])[4 * b + q];
+        }
+        o.gate = mxGetScalar(prhs[7]);
+        o.rows = (int32_t)mxGetScalar(prhs[9]);
+        const int wait = mxGetScalar(prhs[10]) != 0.0;
+        check(h, ekf_observe_linear(h, &o, wait ? &res : NULL));
+        plhs[0] = mxCreateDoubleMatrix(wait ? 1 : 0, wait ? 8 : 0, mxREAL);
+        if (wait) {
+            double *out = mxGetPr(plhs[0]);
+            out[0] = res.nu[0]; out[1] = res.nu[1];
+            for (int q = 0; q < 4; ++q) out[2 + q] = res.S[q];
+            out[6] = res.d2; out[7] = (double)res.outcome;
+        }
         return;
     }
     if (!strcmp(cmd, "merge_landmarks_batch")) {  /* d2 = (h, pairs k x 2 [keep drop], R 2x2): k x 1; landmark numbers 1-based, as they are before the call */
