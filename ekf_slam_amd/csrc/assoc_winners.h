@@ -38,6 +38,19 @@ __device__ __forceinline__ void wave_argmin_sparse(double &ll, int64_t &ix) {
     wave_argmin(ll, ix);
 }
 
+// The likelihood of one landmark for one observation (Correspondence.m:69-78) from the innovation nu and phi^-1 of solve_small, the
+// observed signature z2 and the landmark's sk: pc the Mahalanobis cost (:69), sc the signature cost (:71); returns what is compared
+// with the threshold (:74-75: the position cost takes part only where it carries a weight).  (k_associate and the kDev epilogue of
+// k_gather hold the same rule as text of their own: as a call it changes their pinned code objects.)
+__device__ __forceinline__ double assoc_likelihood(const double nu[2], const double Phi[4], double z2, double sk, double s_cost, double w_pos,
+                                                   double &pc, double &sc) {
+    const double n0 = nu[0], n1 = nu[1];
+    pc = (n0 * Phi[0] + n1 * Phi[2]) * n0 + (n0 * Phi[1] + n1 * Phi[3]) * n1;      // :69
+    const double d = z2 - sk;
+    sc = d * (1.0 / s_cost) * d;                                                  // :71
+    return (w_pos != 0.0) ? (w_pos * pc + sc) : sc;                               // :74-75
+}
+
 // One self-validating 16-byte entry (kernels.h: AssocHostPartial): payload and launch number in ONE store instruction.
 __device__ __forceinline__ void store_partial(AssocHostPartial *dst, double ll, int index, int seq) {
     typedef int part_v4 __attribute__((ext_vector_type(4)));
@@ -47,6 +60,26 @@ __device__ __forceinline__ void store_partial(AssocHostPartial *dst, double ll, 
     v.z = index;
     v.w = (int)((uint32_t)seq + assoc_part_mix((uint32_t)v.x, (uint32_t)v.y, (uint32_t)v.z));
     *reinterpret_cast<part_v4 *>(dst) = v;
+}
+
+// Workgroup arg-min over the kWaves column wavefronts (threads 0 .. 64 * kWaves - 1, all of them call; no other wavefront of the
+// workgroup is alive: a barrier counts live wavefronts only): butterflies, the wavefronts' winners through LDS, one entry per workgroup
+// for the next launch's reduce_partials_wave.  (The kDev epilogue of k_gather holds the same steps as text of its own.)
+template <int kWaves>
+__device__ __forceinline__ void columns_argmin_store(double ll, int64_t ix, AssocHostPartial *dst, int seq) {
+    __shared__ double w_ll[kWaves];
+    __shared__ int w_ix[kWaves];
+    const int tid = threadIdx.x;
+    wave_argmin_sparse(ll, ix);
+    if ((tid & 63) == 0) { w_ll[tid >> 6] = ll; w_ix[tid >> 6] = ix == INT64_MAX ? -1 : (int)ix; }
+    __syncthreads();
+    if (tid < 64) {
+        ll = tid < kWaves ? w_ll[tid] : INFINITY;
+        ix = (tid < kWaves && w_ix[tid] >= 0) ? (int64_t)w_ix[tid] : INT64_MAX;
+        if (ix == INT64_MAX) ll = INFINITY;
+        wave_argmin_sparse(ll, ix);
+        if (tid == 0) store_partial(dst, ll, ix == INT64_MAX ? -1 : (int)ix, seq);
+    }
 }
 
 // Correspondence.m:78-85 over the per-workgroup winners of one association launch (lowest likelihood, lowest index on ties --

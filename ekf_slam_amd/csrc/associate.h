@@ -72,6 +72,7 @@ __global__ __launch_bounds__(kAssocBlock) void k_associate(DevState st, AssocArg
         pss[22] = x[3 + j]; pss[23] = x[3 + j + 1];
         SmallSolve sol;
         solve_small(pss, a.z0, a.z1, a.R00, a.R01, a.R10, a.R11, sol);
+        // (the twin of assoc_winners.h's assoc_likelihood, kept as text of its own: this kernel's code objects are pinned)
         const double n0 = sol.nu[0], n1 = sol.nu[1];
         const double pc = (n0 * sol.Phi[0] + n1 * sol.Phi[2]) * n0 + (n0 * sol.Phi[1] + n1 * sol.Phi[3]) * n1;  // :69
         const double d = a.z2 - st.s[k];

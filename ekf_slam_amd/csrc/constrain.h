@@ -1,4 +1,4 @@
-// Fragment of kernels.hip (included there, inside its anonymous namespace, after tile_access.h / gather.h): the rank-2 pair of a
+// Fragment of kernels.hip (included there, inside its anonymous namespace, after pair_column.h / gather.h): the rank-2 pair of a
 // constraint BETWEEN TWO LANDMARKS (ekf_constrain_landmarks / ekf_merge_landmarks / ekf_landmark_distance): k_constrain_probe,
 // k_gather_constrain.
 #pragma once
@@ -48,120 +48,17 @@ __device__ __forceinline__ void constrain_row_pair(const DevState &st, int64_t j
     } else pmm_low_pair<TS>(tiles, st.tm, c, j, m0, m1);
 }
 
-struct ConstrainSolve {
-    double Si[4];          // S^-1, row-major
-    double nu[2];
-    double Gr[2][3];       // G over the robot columns
-    double Kr[3][2];
-    double prr[9];         // Prr before the update
-};
-
-// One lane per landmark-block column c; 256 columns per workgroup.  The ring is empty when this runs (the host flushes first), so
-// the tiles hold the live P and nothing is patched.  Reads state buffer a.cur / diagonal buffer st.dcur, writes the other ones
-// whole; the small part is formed by one lane of EVERY workgroup (no workgroup reads what another one of the launch writes).
-template <typename TS>
-__global__ __launch_bounds__(kBlock) void k_gather_constrain(DevState st, ConstrainArgs a) {
-    __shared__ ConstrainSolve sol;
-    const int tid = threadIdx.x;
-    const int cur = a.cur;
-    const double *__restrict__ x = st.x[cur];
-    const double *__restrict__ strip = st.strip[cur];
-    double *__restrict__ x_nxt = st.x[cur ^ 1];
-    double *__restrict__ strip_nxt = st.strip[cur ^ 1];
-    const int64_t ldm = st.ldm, ai = a.ai, aj = a.aj;
-    const int64_t c = (int64_t)blockIdx.x * kBlock + tid;
-    const bool live = c < a.n_mm;
-
-    // (1) the column's loads, requested before the small part is waited for
-    double mi0 = 0.0, mi1 = 0.0, mj0 = 0.0, mj1 = 0.0, s0 = 0.0, s1 = 0.0, s2 = 0.0, xc = 0.0, dgc = 0.0, dgl = 0.0;
-    if (live) {
-        constrain_row_pair<TS>(st, ai, c, mi0, mi1);
-        constrain_row_pair<TS>(st, aj, c, mj0, mj1);
-        s0 = strip[c]; s1 = strip[ldm + c]; s2 = strip[2 * ldm + c];
-        xc = x[3 + c];
-        const double *__restrict__ dg = st.diag[st.dcur] + 3 * (c >> 1);
-        if (c & 1) { dgl = dg[1]; dgc = dg[2]; } else dgc = dg[0];
-    }
-
-    // (2) the small part, once per workgroup
-    if (tid == 0) {
-        double sm[kConstrainSmall];
-#pragma unroll
-        for (int e = 0; e < kConstrainSmall; ++e) sm[e] = constrain_small_entry<TS>(st, cur, ai, aj, e);
-        const double R[4] = { a.R00, a.R01, a.R10, a.R11 };
-        double S[4];
-        ekfm::constrain_S(sm, sm + 3, sm + 6, R, S);
-        ekfm::inv2(S, sol.Si);
-        sol.nu[0] = a.d0 - (sm[10] - sm[12]);
-        sol.nu[1] = a.d1 - (sm[11] - sm[13]);
-        for (int r = 0; r < 2; ++r)
-            for (int t = 0; t < 3; ++t) sol.Gr[r][t] = strip[t * ldm + ai + r] - strip[t * ldm + aj + r];
-        for (int t = 0; t < 3; ++t)
-            for (int cc = 0; cc < 2; ++cc) sol.Kr[t][cc] = sol.Gr[0][t] * sol.Si[cc] + sol.Gr[1][t] * sol.Si[2 + cc];
-        for (int q = 0; q < 9; ++q) sol.prr[q] = st.prr[cur][q];
-    }
-    __syncthreads();
-
-    // (3) the column's share of G, K, x and the strip
-    const int64_t pad_end = st.tm.padded(a.n_mm);
-    const int64_t out_off = (int64_t)ring_slot(a.pstart, a.npend, st.pcap) * st.pair_stride;
-    double2 *__restrict__ Gout = reinterpret_cast<double2 *>(st.Gp + out_off);
-    double2 *__restrict__ Kout = reinterpret_cast<double2 *>(st.Kp + out_off);
-    double g0 = 0.0, g1 = 0.0, k0 = 0.0, k1 = 0.0;
-    if (live) {
-        g0 = mi0 - mj0; g1 = mi1 - mj1;
-        k0 = g0 * sol.Si[0] + g1 * sol.Si[2];
-        k1 = g0 * sol.Si[1] + g1 * sol.Si[3];
-        Gout[c] = make_double2(g0, g1);
-        Kout[c] = make_double2(k0, k1);
-        if (st.Gp32) {                                          // the float copies, as k_gather writes them (planar, K negated)
-            st.Gp32[out_off + c] = (float)g0; st.Gp32[out_off + ldm + c] = (float)g1;
-            st.Kp32[out_off + c] = -(float)k0; st.Kp32[out_off + ldm + c] = -(float)k1;
-        }
-        x_nxt[3 + c] = xc + (k0 * sol.nu[0] + k1 * sol.nu[1]);
-        strip_nxt[c] = s0 - (sol.Kr[0][0] * g0 + sol.Kr[0][1] * g1);
-        strip_nxt[ldm + c] = s1 - (sol.Kr[1][0] * g0 + sol.Kr[1][1] * g1);
-        strip_nxt[2 * ldm + c] = s2 - (sol.Kr[2][0] * g0 + sol.Kr[2][1] * g1);
-    } else if (c < pad_end) {                                   // zeros up to the padded width: the pass reads whole tile-wide slices
-        Gout[c] = make_double2(0.0, 0.0);
-        Kout[c] = make_double2(0.0, 0.0);
-        if (st.Gp32) {
-            st.Gp32[out_off + c] = 0.0f; st.Gp32[out_off + ldm + c] = 0.0f;
-            st.Kp32[out_off + c] = -0.0f; st.Kp32[out_off + ldm + c] = -0.0f;
-        }
-    }
-    // (3b) this pair on every landmark's own 2x2 block, as k_gather step (4b): the live copies never carry a pending pair
-    {
-        const double2 kn = make_double2(k0, k1), gn = make_double2(g0, g1);
-        const double2 gl = make_double2(lane_xor1(gn.x), lane_xor1(gn.y));       // the partner column's G (odd lanes: G(:, 2k))
-        const double ndc = rank2_apply(dgc, kn, gn), ndl = rank2_apply(dgl, kn, gl);
-        if (live) {
-            double *__restrict__ dn = st.diag[st.dcur ^ 1] + 3 * (c >> 1);
-            if (c & 1) { dn[1] = ndl; dn[2] = ndc; } else dn[0] = ndc;
-        }
-    }
-    // (4) workgroup 0: x_r and Prr' = Prr - K_r G_r, kept EXACTLY symmetric as k_gather keeps it (both mirrors take the
-    //     lower-triangle entry's value; see the comment there)
-    if (blockIdx.x == 0) {
-        if (tid < 3) x_nxt[tid] = x[tid] + (sol.Kr[tid][0] * sol.nu[0] + sol.Kr[tid][1] * sol.nu[1]);
-        if (tid >= 64 && tid < 73) {
-            const int q = tid - 64, r = q / 3, b = q - 3 * r;
-            const int rr = r > b ? r : b, bb = r > b ? b : r;
-            st.prr[cur ^ 1][3 * r + b] = sol.prr[3 * rr + bb] - (sol.Kr[rr][0] * sol.Gr[0][bb] + sol.Kr[rr][1] * sol.Gr[1][bb]);
-        }
-    }
-}
 
 // ---------------------------------------------------------------------------------------------------
-// The CHAINED form (ekf_merge_landmarks_batch): constraint number a.npend of a batch runs while the a.npend earlier pairs of the batch
-// are still PENDING in the ring st.Gp / st.Kp (the batch's private F64 ring, handed over in a by-value copy of DevState: slots
-// a.pstart + l, no float copies) -- the tiles still hold the P the batch started from.  Every tile operand is read PATCHED: base entry
-// minus sum_l K_l G_l, rank2_apply in slot order on the canonical entry (r >= c: K_l(r,:) . G_l(:,c)), which is the chain the one-pair
-// passes of a constraint-by-constraint run would have applied -- with F64 tiles the same bits, with float tiles the unrounded values.
+// Pending pairs.  Constraint number a.npend of a batch (ekf_merge_landmarks_batch) runs while the a.npend earlier pairs of the batch are
+// still PENDING in the ring st.Gp / st.Kp (the batch's private F64 ring, handed over in a by-value copy of DevState: slots a.pstart + l,
+// no float copies) -- the tiles still hold the P the batch started from.  Every tile operand is read PATCHED: base entry minus
+// sum_l K_l G_l, rank2_apply in slot order on the canonical entry (r >= c: K_l(r,:) . G_l(:,c)), which is the chain the one-pair passes
+// of a constraint-by-constraint run would have applied -- with F64 tiles the same bits, with float tiles the unrounded values.
 // x, the strip, Prr and the live diagonal blocks carry every earlier pair already (each launch writes them whole) and are read as they are.
+// A single constraint (ekf_constrain_landmarks / ekf_merge_landmarks) is the case a.npend == 0: the host flushes first, the loops below
+// are zero-trip and the tiles hold the live P.
 // ---------------------------------------------------------------------------------------------------
-// the record of a launch (kernels.h: kConstrainRecordDoubles): S row-major (0..3) | nu (4, 5) | d2 (6) | 1.0 = S regular, 0.0 = not (7)
-
 // canonical entry (r, c) of the landmark block, r >= c, in different landmarks, with the npend pending pairs applied
 template <typename TS>
 __device__ __forceinline__ double pmm_low_chain(const DevState &st, int pstart, int npend, int64_t r, int64_t c) {
@@ -195,107 +92,54 @@ __device__ __forceinline__ void constrain_row_pair_chain(const DevState &st, int
     }
 }
 
-// k_gather_constrain with a.npend earlier pairs pending, and a record of what it saw (rec: kConstrainRecordDoubles doubles, written by workgroup 0).
-// An S that is not regular (ekfm::constrain_d2) makes the launch a no-op that stays finite: a zero pair in its slot, x / strip / Prr / the
-// diagonal blocks copied -- the host reads the record afterwards and puts the batch's snapshot back.
+// One lane per landmark-block column c; 256 columns per workgroup.  Reads state buffer a.cur / diagonal buffer st.dcur, writes the other
+// ones whole; the small part is formed by one lane of EVERY workgroup (no workgroup reads what another one of the launch writes).
+// Everything after G(:, c) is pair_column.h's.  rec (device, kConstrainRecordDoubles doubles, written by workgroup 0; nullptr: no record):
+// S row-major, nu, d2, 1.0 = S regular, 0.0 = not.  An S that is not regular (ekfm::constrain_d2) makes the launch a no-op that stays
+// finite: a zero pair in its slot, x / strip / Prr / the diagonal blocks copied -- a batch's host reads the record afterwards and puts
+// its snapshot back; a single constraint's host has refused such an S before it launches.
 template <typename TS>
-__global__ __launch_bounds__(kBlock) void k_gather_constrain_chain(DevState st, ConstrainArgs a, double *__restrict__ rec) {
-    __shared__ ConstrainSolve sol;
-    __shared__ int regular;
+__global__ __launch_bounds__(kBlock) void k_gather_constrain(DevState st, ConstrainArgs a, double *__restrict__ rec) {
+    __shared__ PairSolve sol;
     const int tid = threadIdx.x;
     const int cur = a.cur;
-    const double *__restrict__ x = st.x[cur];
-    const double *__restrict__ strip = st.strip[cur];
-    double *__restrict__ x_nxt = st.x[cur ^ 1];
-    double *__restrict__ strip_nxt = st.strip[cur ^ 1];
-    const int64_t ldm = st.ldm, ai = a.ai, aj = a.aj;
+    const int64_t ai = a.ai, aj = a.aj;
     const int64_t c = (int64_t)blockIdx.x * kBlock + tid;
     const bool live = c < a.n_mm;
 
-    // (1) the column's loads and patches
-    double mi0 = 0.0, mi1 = 0.0, mj0 = 0.0, mj1 = 0.0, s0 = 0.0, s1 = 0.0, s2 = 0.0, xc = 0.0, dgc = 0.0, dgl = 0.0;
+    // (1) the column's loads and patches, requested before the small part is waited for
+    double mi0 = 0.0, mi1 = 0.0, mj0 = 0.0, mj1 = 0.0;
     if (live) {
         constrain_row_pair_chain<TS>(st, a.pstart, a.npend, ai, c, mi0, mi1);
         constrain_row_pair_chain<TS>(st, a.pstart, a.npend, aj, c, mj0, mj1);
-        s0 = strip[c]; s1 = strip[ldm + c]; s2 = strip[2 * ldm + c];
-        xc = x[3 + c];
-        const double *__restrict__ dg = st.diag[st.dcur] + 3 * (c >> 1);
-        if (c & 1) { dgl = dg[1]; dgc = dg[2]; } else dgc = dg[0];
     }
+    const ColumnOperands o = load_column_operands(st, cur, c, live);
 
     // (2) the small part, once per workgroup: the cross block comes from the tiles and needs the chain, the own blocks are live
     if (tid == 0) {
+        const double *__restrict__ strip = st.strip[cur];
         double sm[kConstrainSmall];
 #pragma unroll
         for (int e = 0; e < kConstrainSmall; ++e)
             sm[e] = (e >= 6 && e < 10) ? pmm_low_chain<TS>(st, a.pstart, a.npend, ai + ((e - 6) >> 1), aj + ((e - 6) & 1))
                                        : constrain_small_entry<TS>(st, cur, ai, aj, e);
         const double R[4] = { a.R00, a.R01, a.R10, a.R11 };
-        double S[4], d2;
+        double S[4], d2, Gr[2][3];
         ekfm::constrain_S(sm, sm + 3, sm + 6, R, S);
         const double nu0 = a.d0 - (sm[10] - sm[12]), nu1 = a.d1 - (sm[11] - sm[13]);
         const bool ok = ekfm::constrain_d2(S, nu0, nu1, d2);
-        regular = ok ? 1 : 0;
-        if (blockIdx.x == 0) {
-            for (int q = 0; q < 4; ++q) rec[q] = S[q];
-            rec[4] = nu0; rec[5] = nu1; rec[6] = d2; rec[7] = ok ? 1.0 : 0.0;
-        }
-        ekfm::inv2(S, sol.Si);
-        sol.nu[0] = nu0;
-        sol.nu[1] = nu1;
+        if (rec && blockIdx.x == 0) store_pair_record(rec, S, nu0, nu1, d2, ok ? 1.0 : 0.0);
         for (int r = 0; r < 2; ++r)
-            for (int t = 0; t < 3; ++t) sol.Gr[r][t] = strip[t * ldm + ai + r] - strip[t * ldm + aj + r];
-        for (int t = 0; t < 3; ++t)
-            for (int cc = 0; cc < 2; ++cc) sol.Kr[t][cc] = sol.Gr[0][t] * sol.Si[cc] + sol.Gr[1][t] * sol.Si[2 + cc];
-        for (int q = 0; q < 9; ++q) sol.prr[q] = st.prr[cur][q];
-        if (!ok) {
-            sol.nu[0] = sol.nu[1] = 0.0;
-            for (int q = 0; q < 4; ++q) sol.Si[q] = 0.0;
-            for (int q = 0; q < 6; ++q) { (&sol.Gr[0][0])[q] = 0.0; (&sol.Kr[0][0])[q] = 0.0; }
-        }
+            for (int t = 0; t < 3; ++t) Gr[r][t] = strip[t * st.ldm + ai + r] - strip[t * st.ldm + aj + r];
+        pair_solve(sol, S, nu0, nu1, Gr[0], Gr[1], st.prr[cur], ok);
     }
     __syncthreads();
-    const bool ok = regular != 0;
 
-    // (3) the column's share of G, K, x and the strip
-    const int64_t pad_end = st.tm.padded(a.n_mm);
-    const int64_t out_off = (int64_t)ring_slot(a.pstart, a.npend, st.pcap) * st.pair_stride;
-    double2 *__restrict__ Gout = reinterpret_cast<double2 *>(st.Gp + out_off);
-    double2 *__restrict__ Kout = reinterpret_cast<double2 *>(st.Kp + out_off);
-    double g0 = 0.0, g1 = 0.0, k0 = 0.0, k1 = 0.0;
-    if (live) {
-        if (ok) {
-            g0 = mi0 - mj0; g1 = mi1 - mj1;
-            k0 = g0 * sol.Si[0] + g1 * sol.Si[2];
-            k1 = g0 * sol.Si[1] + g1 * sol.Si[3];
-        }
-        Gout[c] = make_double2(g0, g1);
-        Kout[c] = make_double2(k0, k1);
-        x_nxt[3 + c] = xc + (k0 * sol.nu[0] + k1 * sol.nu[1]);
-        strip_nxt[c] = s0 - (sol.Kr[0][0] * g0 + sol.Kr[0][1] * g1);
-        strip_nxt[ldm + c] = s1 - (sol.Kr[1][0] * g0 + sol.Kr[1][1] * g1);
-        strip_nxt[2 * ldm + c] = s2 - (sol.Kr[2][0] * g0 + sol.Kr[2][1] * g1);
-    } else if (c < pad_end) {
-        Gout[c] = make_double2(0.0, 0.0);
-        Kout[c] = make_double2(0.0, 0.0);
-    }
-    // (3b) this pair on every landmark's own 2x2 block
-    {
-        const double2 kn = make_double2(k0, k1), gn = make_double2(g0, g1);
-        const double2 gl = make_double2(lane_xor1(gn.x), lane_xor1(gn.y));
-        const double ndc = rank2_apply(dgc, kn, gn), ndl = rank2_apply(dgl, kn, gl);
-        if (live) {
-            double *__restrict__ dn = st.diag[st.dcur ^ 1] + 3 * (c >> 1);
-            if (c & 1) { dn[1] = ndl; dn[2] = ndc; } else dn[0] = ndc;
-        }
-    }
-    // (4) workgroup 0: x_r and Prr' = Prr - K_r G_r, mirrored from the lower triangle
-    if (blockIdx.x == 0) {
-        if (tid < 3) x_nxt[tid] = x[tid] + (sol.Kr[tid][0] * sol.nu[0] + sol.Kr[tid][1] * sol.nu[1]);
-        if (tid >= 64 && tid < 73) {
-            const int q = tid - 64, r = q / 3, b = q - 3 * r;
-            const int rr = r > b ? r : b, bb = r > b ? b : r;
-            st.prr[cur ^ 1][3 * r + b] = sol.prr[3 * rr + bb] - (sol.Kr[rr][0] * sol.Gr[0][bb] + sol.Kr[rr][1] * sol.Gr[1][bb]);
-        }
-    }
+    // (3) G(:, c) = P(rows of l_i, c) - P(rows of l_j, c), and the column's share of K, x, the strip and the diagonal blocks
+    const PairDest d = pair_dest(st, cur, a.pstart, a.npend, a.n_mm);
+    double g0 = 0.0, g1 = 0.0;
+    if (live && sol.ok) { g0 = mi0 - mj0; g1 = mi1 - mj1; }
+    finish_pair_column(d, sol, o, c, g0, g1);
+    // (4) workgroup 0: x_r and Prr'
+    if (blockIdx.x == 0) store_robot_part(st, cur, d, sol, tid);
 }

@@ -11,23 +11,6 @@
 constexpr int kGatherCols = 256;
 constexpr int kGatherBlock = kGatherCols + 3 * 64;
 
-__device__ __forceinline__ double lane_bcast(double v, int src) {        // value of lane `src` (compile-time) on every lane
-    const int lo = __builtin_amdgcn_readlane(__double2loint(v), src), hi = __builtin_amdgcn_readlane(__double2hiint(v), src);
-    return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ double lane_gather(double v, int src) {       // value of lane `src` (per-lane index): ds_bpermute x 2
-    const int lo = __builtin_amdgcn_ds_bpermute(src << 2, __double2loint(v)), hi = __builtin_amdgcn_ds_bpermute(src << 2, __double2hiint(v));
-    return __hiloint2double(hi, lo);
-}
-// value of the neighbouring lane (lane ^ 1): a DPP quad permutation [1,0,3,2] -- two VALU moves, no LDS crossbar round trip (what
-// __shfl_xor's ds_bpermute costs at the tail of this kernel's latency chain)
-__device__ __forceinline__ double lane_xor1(double v) {
-    const int lo = __builtin_amdgcn_mov_dpp(__double2loint(v), 0xB1, 0xF, 0xF, true), hi = __builtin_amdgcn_mov_dpp(__double2hiint(v), 0xB1, 0xF, 0xF, true);
-    return __hiloint2double(hi, lo);
-}
-// LDS traffic of ONE wavefront is ordered; this only keeps the compiler from moving accesses across it and drains the queue
-__device__ __forceinline__ void wave_lds_sync() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
-
 // kFused (small maps, unsharded, batch 1: the whole landmark block fits ONE workgroup's columns): the rank-2 downdate of
 // EKF_SLAM.m:145 runs at the end of this kernel instead of in a launch of its own -- same arithmetic (rank2_apply per element), one
 // launch per update-step instead of two; the pair is handed over in LDS and never goes to the pending ring.
@@ -43,8 +26,6 @@ constexpr int kFuseElems = kFuseMaxRows * kFuseMaxRows / 256;     // elements of
 template <typename TS>
 __device__ __forceinline__ void gather_decided_other(const DevState &st, const CorrectArgs &a, const DevLoopArgs &dl, int64_t Nd,
                                                      bool append) {
-    __shared__ double oa_ll[kGatherCols / 64];
-    __shared__ int oa_ix[kGatherCols / 64];
     const int tid = threadIdx.x;
     if (tid >= kGatherCols) return;                       // the helper wavefronts have no part here (a barrier counts live wavefronts)
     const int cur = a.cur;
@@ -54,8 +35,6 @@ __device__ __forceinline__ void gather_decided_other(const DevState &st, const C
     double *__restrict__ x_nxt = st.x[cur ^ 1];
     double *__restrict__ strip_nxt = st.strip[cur ^ 1];
     double *__restrict__ prr_nxt = st.prr[cur ^ 1];
-    const double *__restrict__ dg = st.diag[st.dcur];
-    double *__restrict__ dgn = st.diag[st.dcur ^ 1];
     TS *__restrict__ tiles = (TS *)st.tiles;
     const int64_t ldm = st.ldm;
     const int64_t n_old = 2 * Nd, n_new = append ? n_old + 2 : n_old;
@@ -72,8 +51,7 @@ __device__ __forceinline__ void gather_decided_other(const DevState &st, const C
     if (c < n_old) {
         t0 = strip[c]; t1 = strip[ldm + c]; t2 = strip[2 * ldm + c];
         xn = x[3 + c];
-        const double *__restrict__ d = dg + 3 * (c >> 1);
-        if (c & 1) { dgl = d[1]; dgc = d[2]; } else dgc = d[0];
+        load_diag_column(st, c, dgc, dgl);
         if (append)
             for (int i = 0; i < 2; ++i)                   // F: P(new, lm) = jxr * P(lm, 1:3)'   (EKF_SLAM.m:95)
                 if (st.tm.mine((n_old + i) >> st.tm.shift, c >> st.tm.shift))
@@ -99,18 +77,10 @@ __device__ __forceinline__ void gather_decided_other(const DevState &st, const C
     if (live) {
         x_nxt[3 + c] = xn;
         strip_nxt[c] = t0; strip_nxt[ldm + c] = t1; strip_nxt[2 * ldm + c] = t2;
-        double *__restrict__ d = dgn + 3 * (c >> 1);
-        if (c & 1) { d[1] = dgl; d[2] = dgc; } else d[0] = dgc;
+        store_diag_column(st.diag[st.dcur ^ 1], c, dgc, dgl);
     }
-    if (c < st.tm.padded(n_new)) {                        // this launch's pair slot: zeros over the whole live extent
-        const int64_t out_off = (int64_t)ring_slot(a.pstart, a.npend, st.pcap) * st.pair_stride;
-        reinterpret_cast<double2 *>(st.Gp + out_off)[c] = make_double2(0.0, 0.0);
-        reinterpret_cast<double2 *>(st.Kp + out_off)[c] = make_double2(0.0, 0.0);
-        if (st.Gp32) {
-            st.Gp32[out_off + c] = 0.0f; st.Gp32[out_off + ldm + c] = 0.0f;
-            st.Kp32[out_off + c] = -0.0f; st.Kp32[out_off + ldm + c] = -0.0f;
-        }
-    }
+    if (c < st.tm.padded(n_new))                          // this launch's pair slot: zeros over the whole live extent
+        store_pair_column(pair_dest(st, cur, a.pstart, a.npend, n_new), c, 0.0, 0.0, 0.0, 0.0);
     if (blockIdx.x == 0) {
         if (tid < 9) prr_nxt[tid] = prr[tid];
         if (tid < 3) x_nxt[tid] = x[tid];
@@ -135,24 +105,11 @@ __device__ __forceinline__ void gather_decided_other(const DevState &st, const C
         q[22] = xn; q[23] = xn_o;
         SmallSolve so;
         solve_small(q, dl.z0, dl.z1, dl.R00, dl.R01, dl.R10, dl.R11, so);
-        const double n0 = so.nu[0], n1 = so.nu[1];
-        const double pc = (n0 * so.Phi[0] + n1 * so.Phi[2]) * n0 + (n0 * so.Phi[1] + n1 * so.Phi[3]) * n1;     // :69
-        const double sk = k == Nd ? (double)(Nd + 1) : st.s[k];
-        const double d = dl.z2 - sk;
-        const double sc = d * (1.0 / dl.s_cost) * d;                                                        // :71
-        const double like = (dl.w_pos != 0.0) ? (dl.w_pos * pc + sc) : sc;                                 // :74-75
+        double pc, sc;
+        const double like = assoc_likelihood(so.nu, so.Phi, dl.z2, k == Nd ? (double)(Nd + 1) : st.s[k], dl.s_cost, dl.w_pos, pc, sc);
         if (like <= dl.s_thresh) { ll = like; ix = k; }                                                     // :78
     }
-    wave_argmin_sparse(ll, ix);
-    if ((tid & 63) == 0) { oa_ll[tid >> 6] = ll; oa_ix[tid >> 6] = ix == INT64_MAX ? -1 : (int)ix; }
-    __syncthreads();
-    if (tid < 64) {
-        ll = tid < kGatherCols / 64 ? oa_ll[tid] : INFINITY;
-        ix = (tid < kGatherCols / 64 && oa_ix[tid] >= 0) ? (int64_t)oa_ix[tid] : INT64_MAX;
-        if (ix == INT64_MAX) ll = INFINITY;
-        wave_argmin_sparse(ll, ix);
-        if (tid == 0) store_partial(dl.parts_out + blockIdx.x, ll, ix == INT64_MAX ? -1 : (int)ix, dl.seq_out);
-    }
+    columns_argmin_store<kGatherCols / 64>(ll, ix, dl.parts_out + blockIdx.x, dl.seq_out);
 }
 
 // kDev (device-resident measure loop): the corrected landmark is not a kernel argument but the arg-min over the
@@ -394,11 +351,8 @@ __global__ __launch_bounds__(kGatherBlock) void k_gather(DevState st, CorrectArg
             } else if (role == 5) {
                 if (lane < 9) {
                     const int r = lane / 3, b = lane - 3 * r;
-                    // Prr' = Prr - K_r G_r, kept EXACTLY symmetric: entry (r,b) and its mirror both take the lower-triangle entry's value.
-                    // Evaluated entry by entry, K_r(r,:) G_r(:,b) and K_r(b,:) G_r(:,r) differ in the last bit; with the strip stored once
-                    // (symmetry enforced there) the antisymmetric part this leaves in the 3x3 block is not damped but AMPLIFIED by the
-                    // corrections that follow -- measured: 2e-15 after 250 SLAM iterations, 1.3e-7 after 3 000, the heading drifting from
-                    // the dense restatement with it (scripts/soak_config2.py), where the reference's dense P stays symmetric to 1e-16.
+                    // Prr' = Prr - K_r G_r, kept EXACTLY symmetric: both mirrors take the lower-triangle entry's value.  The twin of
+                    // pair_column.h's store_robot_part, which says why.
                     const int rr = r > b ? r : b, bb = r > b ? b : r;
                     prr_nxt[3 * r + b] = pss[3 * rr + bb] - (sol.Kr[rr][0] * sol.Gr[0][bb] + sol.Kr[rr][1] * sol.Gr[1][bb]);
                 }
@@ -605,7 +559,8 @@ __global__ __launch_bounds__(kGatherBlock) void k_gather(DevState st, CorrectArg
     __syncthreads();                                              // barrier B: the helpers' results are in LDS
     EKF_STAMP();                                                  // 3: solve available
 
-    // (4) the column's share of G, K, x and the strip
+    // (4) the column's share of G, K, x and the strip.  (4) and (4b) are the twin of pair_column.h's finish_pair_column / store_pair_column
+    //     (the pair's storage format, x', strip', the diagonal blocks), kept as text of its own: this kernel's code objects are pinned
     const int64_t pad_end = st.tm.padded(a.n_mm);
     const int64_t out_off = (int64_t)ring_slot(pstart, npend, st.pcap) * st.pair_stride;   // this correction's own pair
     double2 *__restrict__ Gout = reinterpret_cast<double2 *>(st.Gp + out_off);
@@ -691,7 +646,9 @@ __global__ __launch_bounds__(kGatherBlock) void k_gather(DevState st, CorrectArg
     }
     if constexpr (kDev) {
         if (next_assoc) {                                         // uniform
-            // ---- the NEXT observation's association (Correspondence.m:49-87) on the state this correction leaves.  Landmark
+            // ---- the NEXT observation's association (Correspondence.m:49-87) on the state this correction leaves (the twin of
+            //      assoc_winners.h's assoc_likelihood and columns_argmin_store, kept as text of its own: as helpers they cost this
+            //      kernel a register and 160 bytes).  Landmark
             //      k = c / 2 is scored by its even column lane; everything it needs is in this lane pair's registers (x', strip',
             //      the landmark's own 2x2 block after this correction) or in the workgroup's LDS (Prr before the correction, K_r,
             //      G_r, nu).

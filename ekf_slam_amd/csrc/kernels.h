@@ -16,7 +16,7 @@ constexpr int ekf_tune_int(const char *, int dflt) { return dflt; }
 #endif
 
 // (DevState, ConstrainArgs and kConstrainRecordDoubles below are mirrored BY HAND in tests/support/merge_batch_host_emulation.cpp, which
-// compiles constrain.h / compact.h / merge_pass.h for the host and cannot include this file (it needs the HIP headers): the
+// compiles pair_column.h / constrain.h / compact.h / merge_pass.h for the host and cannot include this file (it needs the HIP headers): the
 // duplication is intentional; a field that those kernels read and that changes here must change there.)
 // Device-resident filter state.  Passed BY VALUE to every kernel.
 //   x / prr / strip are double-buffered: every kernel reads buffer `cur` and writes a complete buffer
@@ -282,13 +282,15 @@ struct ConstrainArgs {
 // host forms S and nu from before anything changes
 hipError_t launch_constrain_probe(const DevState &st, int cur, int64_t ai, int64_t aj, double *out, int storage, hipStream_t s);
 // k_gather_constrain: the constraint's pair into the ring slot, x / Prr / strip into buffer a.cur ^ 1, every landmark's live diagonal
-// block (with the pair applied) into buffer dcur ^ 1; the caller flips both and lets a pass apply the pair to the tiles
+// block (with the pair applied) into buffer dcur ^ 1; the caller flips both and lets a pass apply the pair to the tiles.  The ring is
+// empty when it runs (a.npend == 0) and no record is written: the host has formed S from launch_constrain_probe's operands before.
 hipError_t launch_gather_constrain(const DevState &st, const ConstrainArgs &a, int storage, hipStream_t s);
 // A batch of merges (ekf_merge_landmarks_batch).  `st` is a by-value copy of the handle's DevState whose Gp / Kp / pcap name the batch's
 // PRIVATE F64 pair ring (Gp32 == nullptr); world == 1.
-// launch_gather_constrain_chain: constraint number a.npend of the batch while the a.npend earlier pairs (slots a.pstart ..) are still
-// pending -- every tile operand is read patched with them -- and a record of it into rec (device, kConstrainRecordDoubles doubles: S
-// row-major, nu, d2 as ekfm::constrain_d2 gives it, 1.0 / 0.0 = S regular or not); an irregular S leaves a zero pair and copies the state.
+// launch_gather_constrain_chain: the SAME kernel as constraint number a.npend of the batch while the a.npend earlier pairs (slots
+// a.pstart ..) are still pending -- every tile operand is read patched with them -- and a record of it into rec (device,
+// kConstrainRecordDoubles doubles: S row-major, nu, d2 as ekfm::constrain_d2 gives it, 1.0 / 0.0 = S regular or not); an irregular S
+// leaves a zero pair and copies the state.
 constexpr int kConstrainRecordDoubles = 8;
 hipError_t launch_gather_constrain_chain(const DevState &st, const ConstrainArgs &a, double *rec, int storage, hipStream_t s);
 // launch_merge_pass (merge_pass.h): the `ntiles` destination tiles work[0 ..) of the store `dst` (never st.tiles) = the compaction of

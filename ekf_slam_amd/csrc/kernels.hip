@@ -30,11 +30,13 @@
 namespace {
 
 #include "tile_access.h"      // canonical element access, rank2_apply
+#include "lane_ops.h"         // values between the lanes of a wavefront: lane_bcast, lane_gather, lane_xor1
 #include "predict.h"          // k_predict, k_predict_mfma and the shared 3x3 part
 #include "assoc_winners.h"    // association order, the self-validating winner entries
 #include "append.h"           // k_append
 #include "solve_small.h"      // the 5x5 solve, entry by entry
 #include "rowpanel.h"         // PanelView, k_rowpanel, k_rowpanel_next, k_rowpanel_base
+#include "pair_column.h"      // what every producer of a pair (K, G) does per column: the pair's slot, x', strip', the diagonal blocks
 #include "gather.h"           // k_gather
 #include "downdate.h"         // k_downdate, k_downdate_w
 #include "associate.h"        // k_associate, k_assoc_merge

@@ -66,14 +66,14 @@ unsigned constrain_grid(const DevState &st, const ConstrainArgs &a) { return (un
 hipError_t launch_gather_constrain(const DevState &st, const ConstrainArgs &a, int storage, hipStream_t s) {
     if (!constrain_args_ok(st, a)) return hipErrorInvalidValue;
     return with_storage(storage, [&](auto ts) {
-        hipLaunchKernelGGL(k_gather_constrain<decltype(ts)>, dim3(constrain_grid(st, a)), dim3(kBlock), 0, s, st, a);
+        hipLaunchKernelGGL(k_gather_constrain<decltype(ts)>, dim3(constrain_grid(st, a)), dim3(kBlock), 0, s, st, a, (double *)nullptr);
     });
 }
 
 hipError_t launch_gather_constrain_chain(const DevState &st, const ConstrainArgs &a, double *rec, int storage, hipStream_t s) {
     if (!constrain_args_ok(st, a) || a.pstart < 0 || a.pstart >= st.pcap || !rec || st.Gp32 || st.tm.world != 1) return hipErrorInvalidValue;
     return with_storage(storage, [&](auto ts) {
-        hipLaunchKernelGGL(k_gather_constrain_chain<decltype(ts)>, dim3(constrain_grid(st, a)), dim3(kBlock), 0, s, st, a, rec);
+        hipLaunchKernelGGL(k_gather_constrain<decltype(ts)>, dim3(constrain_grid(st, a)), dim3(kBlock), 0, s, st, a, rec);
     });
 }
 

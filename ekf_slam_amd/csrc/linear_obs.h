@@ -8,6 +8,9 @@
 // -- the update of constrain.h for a general H (there: Hr = 0, Hl = +I2, -I2).  Unlike a constraint this is an UPDATE-STEP: the
 // launch runs on the handle's own ring while the a.npend earlier pairs are still pending, reads every tile operand patched with
 // them (constrain_row_pair_chain, pmm_low_chain) and leaves its pair in the next slot, float copies included, as k_gather does.
+// The small part's solve, the record and workgroup 0's robot part are pair_column.h's.  The column's own share (steps (1), (3), (3b)) is
+// the twin of its load_column_operands / finish_pair_column, kept as text of its own: called from here those two cost this kernel
+// 0.1-0.4 us of its 8-17 (measured against the parent commit, profiles/pair_column/README.md), although they are the same statements.
 // x, the strip, Prr and the live diagonal blocks carry every pending pair already and are read as they are.
 // ---------------------------------------------------------------------------------------------------
 // the record of a launch (kernels.h: kLinearRecordDoubles): S row-major (0..3) | nu (4, 5) | d2 (6) | the outcome (7): 1.0 applied, 0.0 S
@@ -35,14 +38,8 @@ __device__ __forceinline__ double linear_small_entry(const DevState &st, const L
     return ab >= 0 ? st.x[cur][3 + ab + ((e - 34) & 1)] : 0.0;
 }
 
-struct LinearSolve {
-    double Si[4];          // S^-1, row-major
-    double nu[2];
-    double Gr[2][3];       // G over the robot columns
-    double Kr[3][2];
-    double prr[9];         // Prr before the update
+struct LinearSolve : PairSolve {
     double rec[kLinearRecordDoubles];
-    int outcome;
 };
 
 // The small part, by the first wavefront of a workgroup: the kLinearSmall operands one per lane (each patched entry walks the ring
@@ -58,20 +55,8 @@ __device__ __forceinline__ void linear_small_part(const DevState &st, const Line
         double Gs[14], S[4], nu[2], d2;
         ekfm::linear_small(sm, a.H, a.z, a.R, a.wrap, Gs, S, nu);
         const int outcome = ekfm::linear_outcome(S, nu, a.gate, d2);
-        for (int q = 0; q < 4; ++q) sol.rec[q] = S[q];
-        sol.rec[4] = nu[0]; sol.rec[5] = nu[1]; sol.rec[6] = d2; sol.rec[7] = (double)outcome;
-        sol.outcome = outcome;
-        const bool ok = outcome == 1;
-        double Si[4];
-        ekfm::inv2(S, Si);
-        for (int q = 0; q < 4; ++q) sol.Si[q] = ok ? Si[q] : 0.0;
-        sol.nu[0] = ok ? nu[0] : 0.0;
-        sol.nu[1] = ok ? nu[1] : 0.0;
-        for (int r = 0; r < 2; ++r)
-            for (int t = 0; t < 3; ++t) sol.Gr[r][t] = ok ? Gs[7 * r + t] : 0.0;
-        for (int t = 0; t < 3; ++t)
-            for (int cc = 0; cc < 2; ++cc) sol.Kr[t][cc] = sol.Gr[0][t] * sol.Si[cc] + sol.Gr[1][t] * sol.Si[2 + cc];
-        for (int q = 0; q < 9; ++q) sol.prr[q] = sm[q];
+        store_pair_record(sol.rec, S, nu[0], nu[1], d2, (double)outcome);
+        pair_solve(sol, S, nu[0], nu[1], Gs, Gs + 7, sm, outcome == 1);
     }
     __syncthreads();
 }
@@ -116,9 +101,9 @@ __global__ __launch_bounds__(kBlock) void k_gather_linear(DevState st, LinearArg
 
     // (2) the small part, once per workgroup
     linear_small_part<TS>(st, a, sm, sol);
-    const bool ok = sol.outcome == 1;
+    const bool ok = sol.ok != 0;
 
-    // (3) the column's share of G, K, x and the strip
+    // (3) the column's share of G, K, x and the strip (the twin of pair_column.h's finish_pair_column / store_pair_column)
     const int64_t pad_end = st.tm.padded(a.n_mm);
     const int64_t out_off = (int64_t)ring_slot(a.pstart, a.npend, st.pcap) * st.pair_stride;
     double2 *__restrict__ Gout = reinterpret_cast<double2 *>(st.Gp + out_off);
@@ -162,18 +147,12 @@ __global__ __launch_bounds__(kBlock) void k_gather_linear(DevState st, LinearArg
             if (c & 1) { dn[1] = ndl; dn[2] = ndc; } else dn[0] = ndc;
         }
     }
-    // (4) workgroup 0: x_r, Prr' = Prr - K_r G_r kept EXACTLY symmetric as k_gather_constrain keeps it (both mirrors take the
-    //     lower-triangle entry's value), the record and the counters
+    // (4) workgroup 0: x_r and Prr', the record and the counters
     if (blockIdx.x == 0) {
-        if (tid < 3) x_nxt[tid] = x[tid] + (sol.Kr[tid][0] * sol.nu[0] + sol.Kr[tid][1] * sol.nu[1]);
-        if (tid >= 64 && tid < 73) {
-            const int q = tid - 64, r = q / 3, b = q - 3 * r;
-            const int rr = r > b ? r : b, bb = r > b ? b : r;
-            st.prr[cur ^ 1][3 * r + b] = sol.prr[3 * rr + bb] - (sol.Kr[rr][0] * sol.Gr[0][bb] + sol.Kr[rr][1] * sol.Gr[1][bb]);
-        }
+        store_robot_part(st, cur, pair_dest(st, cur, a.pstart, a.npend, a.n_mm), sol, tid);
         if (tid >= 128 && tid < 128 + kLinearRecordDoubles) rec[tid - 128] = sol.rec[tid - 128];
         if (tid == 0 && !ok) {
-            const int which = sol.outcome == 0 ? 0 : 1;
+            const int which = sol.rec[7] == 0.0 ? 0 : 1;
             cnt[which] = cnt[which] + 1;
         }
     }

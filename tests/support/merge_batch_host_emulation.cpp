@@ -1,9 +1,9 @@
 // Host emulation of the batch-fusion kernels (tests/test_merge_batch_cpu.py compiles and runs it; no GPU, no HIP runtime).
-// The kernel SOURCES of ekf_slam_amd/csrc (constrain.h, compact.h, merge_pass.h, tile_access.h) are compiled for the host behind a
+// The kernel SOURCES of ekf_slam_amd/csrc (pair_column.h, constrain.h, compact.h, merge_pass.h, tile_access.h) are compiled for the host behind a
 // small shim -- thread indices as globals, __shared__ as static storage with thread 0 of a workgroup run first, lane_xor1 in two
 // passes -- and two routes are compared BIT FOR BIT on the same state:
-//   the batch:    m x k_gather_constrain_chain (earlier pairs pending in the ring), then k_merge_pass
-//   the sequence: m x (k_gather_constrain, the one-pair pass as a plain rank2_apply loop), then k_compact_tiles
+//   the batch:    m x k_gather_constrain with a record (earlier pairs pending in the ring), then k_merge_pass
+//   the sequence: m x (k_gather_constrain with npend = 0 and no record, the one-pair pass as a plain rank2_apply loop), then k_compact_tiles
 // both followed by k_compact_state.  The shim's DevState / ConstrainArgs mirror kernels.h (which needs the HIP headers).
 #include <cmath>
 #include <cstdint>
@@ -44,9 +44,16 @@ static inline void lane16_pack(const double *v, double2 &t) { t.x = v[0]; t.y = 
 static inline void lane16_pack(const double *v, float4 &t) { t.x = (float)v[0]; t.y = (float)v[1]; t.z = (float)v[2]; t.w = (float)v[3]; }
 #include "tile_access.h"
 #include "compact.h"
+#include "pair_column.h"
 #include "constrain.h"
 #include "merge_pass.h"
 
+// FNV-1a over the bytes of a route's final state: printed in each line's parentheses, so that two builds of this file can be compared
+static uint64_t fnv(uint64_t h, const double *p, size_t n) {
+    const unsigned char *b = (const unsigned char *)p;
+    for (size_t i = 0; i < 8 * n; ++i) { h ^= b[i]; h *= 1099511628211ull; }
+    return h;
+}
 template <typename F> static void launch_wg(int grid, F body) {      // thread 0 first (it fills the shared solve), two lane_xor1 passes
     for (int b = 0; b < grid; ++b) {
         for (int t = 0; t < kBlock; ++t) { xor_rec[t].clear(); xor_pos[t] = 0; }
@@ -132,7 +139,7 @@ int main() {
             A.sync();
             ConstrainArgs a = args(A, pairs[k].first, pairs[k].second, k, R);
             DevState st = A.st;
-            launch_wg(grid, [&] { k_gather_constrain_chain<double>(st, a, rec.data() + 8 * k); });
+            launch_wg(grid, [&] { k_gather_constrain<double>(st, a, rec.data() + 8 * k); });
             A.cur ^= 1; A.dcur ^= 1;
         }
         compact(A, src_of, m, true);
@@ -147,7 +154,7 @@ int main() {
             double Sm[4];
             ekfm::constrain_S(sm, sm + 3, sm + 6, R, Sm);
             if (!ekfm::constrain_d2(Sm, -(sm[10] - sm[12]), -(sm[11] - sm[13]), d2[k])) printf("irregular pair %d\n", k);
-            launch_wg(grid, [&] { k_gather_constrain<double>(st, a); });
+            launch_wg(grid, [&] { k_gather_constrain<double>(st, a, (double *)nullptr); });
             B.cur ^= 1; B.dcur ^= 1;
             // the one-pair pass, in place, over every stored entry (diagonal tiles whole)
             const double2 *G2 = (const double2 *)B.st.Gp, *K2 = (const double2 *)B.st.Kp;
@@ -172,7 +179,14 @@ int main() {
         for (int k = 0; k < m; ++k) { if (memcmp(&rec[8 * k + 6], &d2[k], 8) || rec[8 * k + 7] != 1.0) ++db; }
         if (db) printf("  d2 records: %d differ\n", db);
         bad += db;
-        printf("T=%d R%s m=%d: %d differences (d2[0]=%g d2[%d]=%g)\n", T, rcase ? "pos" : "0", m, bad, rec[6], m - 1, rec[8 * (m - 1) + 6]);
+        uint64_t hs = 14695981039346656037ull;                  // route A: x, strip, prr, diag, s, lower-triangle tiles, records
+        hs = fnv(hs, A.x[A.cur].data(), A.x[A.cur].size()); hs = fnv(hs, A.strip[A.cur].data(), A.strip[A.cur].size());
+        hs = fnv(hs, A.prr[A.cur].data(), A.prr[A.cur].size()); hs = fnv(hs, A.diag[A.dcur].data(), A.diag[A.dcur].size());
+        hs = fnv(hs, A.s.data(), A.s.size());
+        for (int r = 0; r < nt * T; ++r) for (int c = 0; c <= r; ++c) { const double u = A.tile(r, c); hs = fnv(hs, &u, 1); }
+        hs = fnv(hs, rec.data(), rec.size());
+        printf("T=%d R%s m=%d: %d differences (d2[0]=%g d2[%d]=%g state %016llx)\n", T, rcase ? "pos" : "0", m, bad, rec[6], m - 1, rec[8 * (m - 1) + 6],
+               (unsigned long long)hs);
         total_bad += bad;
     }
     return total_bad != 0;

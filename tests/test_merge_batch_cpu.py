@@ -91,7 +91,8 @@ def test_library_exports_and_binds_the_entry_point():
 def test_the_device_side_is_where_the_design_says():
     csrc = os.path.join(ROOT, "ekf_slam_amd", "csrc")
     constrain = open(os.path.join(csrc, "constrain.h")).read()
-    assert "k_gather_constrain_chain" in constrain and "ekfm::constrain_d2(" in constrain
+    assert "void k_gather_constrain(DevState st, ConstrainArgs a, double *__restrict__ rec)" in constrain and "k_gather_constrain_chain" not in constrain
+    assert "constrain_row_pair_chain" in constrain and "ekfm::constrain_d2(" in constrain
     fused = open(os.path.join(csrc, "merge_pass.h")).read()
     assert "k_merge_pass" in fused and "rank2_apply(" in fused and "__shared__" not in fused
     edits = open(os.path.join(csrc, "host", "edits.h")).read()
@@ -103,7 +104,7 @@ def test_the_device_side_is_where_the_design_says():
 
 def test_the_kernel_sources_emulated_on_the_host_give_the_sequence_bit_for_bit(tmp_path):
     """tests/support/merge_batch_host_emulation.cpp: the chain of gathers and the fused pass, compiled for the host behind a thread-index
-    shim, against the one-pair gather + pass + compaction route -- x, strip, Prr, diagonal blocks, s, tiles and d2, bit for bit, with a
+    shim, against the one-pair gather (the same kernel with nothing pending and no record) + pass + compaction route -- x, strip, Prr, diagonal blocks, s, tiles and d2, bit for bit, with a
     shared keep, keep > drop, drops at landmark 0 and N - 1, an adjacent pair, R = 0 and R > 0; address and UB sanitizers on."""
     exe = str(tmp_path / "emulation")
     r = subprocess.run(["g++", "-std=c++17", "-O1", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
