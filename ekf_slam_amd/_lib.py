@@ -49,6 +49,15 @@ class EkfLinearResult(ctypes.Structure):
 
 EKF_LINEAR_IRREGULAR, EKF_LINEAR_APPLIED, EKF_LINEAR_GATED = 0, 1, 2
 
+
+class EkfModelObs(ctypes.Structure):
+    """struct ekf_model_obs (include/ekfslam.h)."""
+    _fields_ = [("model", _i32), ("reserved", _i32), ("z", _d * 2), ("R", _d * 4), ("lm", _i64 * 2), ("anchor", _d * 2), ("gate", _d)]
+
+
+EKF_MODEL_RANGE_BEARING, EKF_MODEL_RANGE, EKF_MODEL_BEARING, EKF_MODEL_RELATIVE_XY, EKF_MODEL_LANDMARK_RANGE = 1, 2, 3, 4, 5
+EKF_MODEL_ROWS = {1: 2, 2: 1, 3: 1, 4: 2, 5: 1}       # rows of z each model reads
+
 # name -> (restype, argtypes); every symbol of include/ekfslam.h
 SIGNATURES = {
     "ekf_abi_version": (_i32, []),
@@ -101,6 +110,9 @@ SIGNATURES = {
     "ekf_observe_linear": (_i32, [_vp, ctypes.POINTER(EkfLinearObs), ctypes.POINTER(EkfLinearResult)]),
     "ekf_linear_innovation": (_i32, [_vp, ctypes.POINTER(EkfLinearObs), ctypes.POINTER(EkfLinearResult)]),
     "ekf_linear_rejections": (_i32, [_vp, ctypes.POINTER(_i64), ctypes.POINTER(_i64)]),
+    "ekf_observe_model": (_i32, [_vp, ctypes.POINTER(EkfModelObs), ctypes.POINTER(EkfLinearResult)]),
+    "ekf_model_innovation": (_i32, [_vp, ctypes.POINTER(EkfModelObs), ctypes.POINTER(EkfLinearResult)]),
+    "ekf_model_evaluate": (_i32, [_i32, _dp, _dp, _dp, _dp, _dp]),
     "ekf_diag_poke_device_signature": (_i32, [_vp, _i64, _d]),
     "ekf_get_P": (_i32, [_vp, _dp]),
     "ekf_set_P": (_i32, [_vp, _dp, _i64]),

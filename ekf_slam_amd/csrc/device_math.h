@@ -251,4 +251,75 @@ EKF_MHD int linear_outcome(const double S[4], const double nu[2], double gate, d
     return d2 > gate ? 2 : 1;
 }
 
+// The observation models of ekf_observe_model (include/ekfslam.h names them; model_obs.h runs them on the device): h(x) and its Jacobian
+// H (row-major 2 x 7 over robot | landmark 0 | landmark 1, linear_small's layout) at xs = the seven entries sm[31..37].  The target t of
+// models 1-4 is landmark 0 (has_landmark) or the fixed point `anchor`, which carries no block of H; model 5 is the distance between
+// landmarks 0 and 1 and has no robot block.  theta in degrees, so a bearing's derivatives carry k = 180/pi and RELATIVE_XY's heading
+// column 1/k.  A one-row model leaves row 1 of H and hx[1] exactly zero.  Returns whether q = |d|^2 is finite and positive; where it is
+// not (the target on the robot, a non-finite state) H and hx are zero and the caller reports EKF_LINEAR_IRREGULAR.
+// Each expression is written once: the host (ekf_model_evaluate), k_model_probe and k_gather_model give the same bits.
+EKF_MHD bool model_eval(int model, const double xs[7], const double anchor[2], bool has_landmark, double hx[2], double H[14]) {
+    for (int i = 0; i < 14; ++i) H[i] = 0.0;
+    hx[0] = hx[1] = 0.0;
+    const bool pair = model == 5;
+    const double tx = pair || has_landmark ? xs[3] : anchor[0], ty = pair || has_landmark ? xs[4] : anchor[1];
+    const double px = pair ? xs[5] : xs[0], py = pair ? xs[6] : xs[1];
+    const double dx = tx - px, dy = ty - py;
+    const double q = dx * dx + dy * dy;
+    if (!(isfinite(q) && q > 0.0) || !isfinite(xs[2])) return false;
+    const double r = sqrt(q);
+    const int tcol = 3, pcol = pair ? 5 : 0;                    // where the blocks on t and on p go
+    const bool tblock = pair || has_landmark;
+    if (model == 1 || model == 2 || model == 5) {               // row 0: the range
+        const double ex = dx / r, ey = dy / r;
+        hx[0] = r;
+        H[pcol] = -ex; H[pcol + 1] = -ey;
+        if (tblock) { H[tcol] = ex; H[tcol + 1] = ey; }
+    }
+    if (model == 1 || model == 3) {                             // the bearing: row 1 of RANGE_BEARING, row 0 of BEARING
+        const int row = model == 1 ? 7 : 0;
+        const double bx = kR2D * dy / q, by = kR2D * dx / q;
+        hx[model == 1 ? 1 : 0] = atan2d(dy, dx) - xs[2];
+        H[row] = bx; H[row + 1] = -by; H[row + 2] = -1.0;
+        if (tblock) { H[row + tcol] = -bx; H[row + tcol + 1] = by; }
+    }
+    if (model == 4) {                                           // the target in the robot frame
+        double s, c;
+        sincosd(xs[2], s, c);
+        hx[0] = c * dx + s * dy;
+        hx[1] = c * dy - s * dx;
+        H[0] = -c; H[1] = -s; H[2] = hx[1] / kR2D;
+        H[7] = s; H[8] = -c; H[9] = -hx[0] / kR2D;
+        if (tblock) { H[3] = c; H[4] = s; H[10] = -s; H[11] = c; }
+    }
+    return true;
+}
+// which rows of a model's nu are angles in degrees, wrapped into (-180, 180]
+EKF_MHD void model_wrap(int model, int wrap_deg[2]) {
+    wrap_deg[0] = model == 3;
+    wrap_deg[1] = model == 1;
+}
+
+// The small part of a MODEL observation: linear_small with nu = z - h(x) in place of z - H x (rows wrapped as model_wrap says); Gs and S
+// in linear_small's summation order, so a linear observation handed this H gives the same Gs and S bit for bit.  Kept beside
+// linear_small, not split out of it: k_gather_linear's registers are pinned.
+EKF_MHD void model_small(const double *sm, const double H[14], const double hx[2], const double z[2], const double R[4],
+                         const int wrap_deg[2], double Gs[14], double S[4], double nu[2]) {
+    for (int r = 0; r < 2; ++r) {
+        for (int j = 0; j < 7; ++j) {
+            double g = 0.0;
+            for (int i = 0; i < 7; ++i) g += H[7 * r + i] * linear_small_P(sm, i, j);
+            Gs[7 * r + j] = g;
+        }
+        nu[r] = z[r] - hx[r];
+        if (wrap_deg[r]) nu[r] = wrap180(nu[r]);
+    }
+    for (int r = 0; r < 2; ++r)
+        for (int b = 0; b < 2; ++b) {
+            double s = 0.0;
+            for (int j = 0; j < 7; ++j) s += Gs[7 * r + j] * H[7 * b + j];
+            S[2 * r + b] = s + R[2 * r + b];
+        }
+}
+
 }  // namespace ekfm

@@ -46,13 +46,15 @@ int32_t linear_parse(ekf_handle *h, const std::string &who, const ekf_linear_obs
 }
 
 // ... then the rungs: unsharded, settled (N exact), the indices, a recorded predict carried out, the work lists of the current map
-int32_t linear_rungs(ekf_handle *h, const std::string &who, const ekf_linear_obs *obs, LinearArgs &a) {
+// (A: LinearArgs, or model.h's ModelArgs; lm: the observation's two landmarks, -1 = none)
+template <typename A>
+int32_t linear_rungs(ekf_handle *h, const std::string &who, const int64_t lm[2], A &a) {
     TRY(edit_unsharded(h, who, "a landmark block needs that landmark's row-panel exchanged between the shards (a fix of the robot state "
                        "alone would not: its operands are replicated)"));
     TRY(edit_settled(h, who));
     for (int b = 0; b < 2; ++b) {
-        REQUIRE(h, obs->lm[b] < h->N, EKF_ERR_INDEX, (who + "landmark index outside the state").c_str());
-        a.a[b] = obs->lm[b] >= 0 ? 2 * obs->lm[b] : -1;
+        REQUIRE(h, lm[b] < h->N, EKF_ERR_INDEX, (who + "landmark index outside the state").c_str());
+        a.a[b] = lm[b] >= 0 ? 2 * lm[b] : -1;
     }
     TRY(materialize_predict(h));
     TRY(refresh_work(h));
@@ -74,7 +76,7 @@ int32_t ekf_observe_linear(ekf_handle *h, const ekf_linear_obs *obs, ekf_linear_
     const std::string who = "observe_linear: ";
     LinearArgs a;
     TRY(linear_parse(h, who, obs, a));
-    TRY(linear_rungs(h, who, obs, a));
+    TRY(linear_rungs(h, who, obs->lm, a));
     // no flush: the launch reads its tile operands patched with the pending pairs and writes its own into the next ring slot
     TIMED(h, EKF_KERNEL_GATHER, launch_gather_linear(h->st, a, h->d_linrec, h->d_lincnt, h->storage, h->stream));
     if (res) {
@@ -96,7 +98,7 @@ int32_t ekf_linear_innovation(ekf_handle *h, const ekf_linear_obs *obs, ekf_line
     LinearArgs a;
     TRY(linear_parse(h, who, obs, a));
     REQUIRE(h, res != nullptr, EKF_ERR_INVALID_ARG, (who + "null result").c_str());
-    TRY(linear_rungs(h, who, obs, a));
+    TRY(linear_rungs(h, who, obs->lm, a));
     double *d_rec = h->d_linrec + kLinearRecordDoubles, *h_rec = h->h_linrec + kLinearRecordDoubles;
     HIPCHK(h, launch_linear_probe(h->st, a, d_rec, h->storage, h->stream));
     HIPCHK(h, hipMemcpyAsync(h_rec, d_rec, kLinearRecordDoubles * 8, hipMemcpyDeviceToHost, h->stream));

@@ -328,6 +328,25 @@ hipError_t launch_gather_linear(const DevState &st, const LinearArgs &a, double 
 // k_linear_probe: the record that launch would write under the current state, and nothing else
 hipError_t launch_linear_probe(const DevState &st, const LinearArgs &a, double *rec, int storage, hipStream_t s);
 
+// An observation through one of the MODELS of ekf_observe_model (model_obs.h): the update-step above with h(x) and its Jacobian H
+// evaluated on the device at the live x (ekfm::model_eval), nu = z - h(x).  H is no argument: lane 0 of every workgroup forms it.
+struct ModelArgs {
+    double z[2];
+    double R[4];              // row-major
+    double anchor[2];         // the target of models 1-4 where a[0] == -1
+    double gate;
+    int64_t a[2];             // as LinearArgs::a; models 1-4: a[1] == -1, model 5: both >= 0
+    int64_t n_mm;
+    int32_t model;            // EKF_MODEL_*
+    int32_t cur;
+    int32_t npend;
+    int32_t pstart;
+};
+// k_gather_model / k_model_probe: launch_gather_linear / launch_linear_probe for a model, the record and the counters shared with them;
+// a target on the robot (q = 0) or a non-finite q counts and reports as an irregular S
+hipError_t launch_gather_model(const DevState &st, const ModelArgs &a, double *rec, int64_t *cnt, int storage, hipStream_t s);
+hipError_t launch_model_probe(const DevState &st, const ModelArgs &a, double *rec, int storage, hipStream_t s);
+
 // ---- state I/O (launch/state_io.h) ----
 // dense (column-major, n x n, device) <-> tiled
 hipError_t launch_unpack_dense(const DevState &st, int cur, int64_t n_mm, double *dense, int storage, hipStream_t s);

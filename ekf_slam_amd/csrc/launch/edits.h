@@ -1,5 +1,5 @@
 // Fragment of kernels.hip, the launchers of the map edits: landmark removal (compact.h), a constraint between two landmarks and its
-// chained form (constrain.h), a linear observation (linear_obs.h), the fused pass of a batch of merges (merge_pass.h), the candidate search (nearest.h).
+// chained form (constrain.h), a linear observation (linear_obs.h) and one through a model (model_obs.h), the fused pass of a batch of merges (merge_pass.h), the candidate search (nearest.h).
 #pragma once
 
 namespace {
@@ -79,12 +79,18 @@ hipError_t launch_gather_constrain_chain(const DevState &st, const ConstrainArgs
 
 namespace {
 // the landmarks that carry a block inside the map and different, the padded block inside the strip, the ring positions inside the ring
-bool linear_args_ok(const DevState &st, const LinearArgs &a) {
+template <typename A>
+bool linear_args_ok(const DevState &st, const A &a) {
     for (int b = 0; b < 2; ++b)
         if (a.a[b] != -1 && !(a.a[b] >= 0 && a.a[b] + 1 < a.n_mm && (a.a[b] & 1) == 0)) return false;
     if (a.a[0] >= 0 && a.a[0] == a.a[1]) return false;
     return a.n_mm >= 0 && st.tm.padded(a.n_mm) <= st.ldm && a.npend >= 0 && a.npend <= st.pcap && a.pstart >= 0 && a.pstart < st.pcap &&
            st.tm.world == 1;
+}
+// the landmark pattern of the model: the pair of model 5, at most the first one otherwise
+bool model_args_ok(const ModelArgs &a) {
+    if (a.model < 1 || a.model > 5) return false;
+    return a.model == 5 ? (a.a[0] >= 0 && a.a[1] >= 0) : a.a[1] == -1;
 }
 }  // namespace
 
@@ -100,6 +106,21 @@ hipError_t launch_linear_probe(const DevState &st, const LinearArgs &a, double *
     if (!linear_args_ok(st, a) || !rec) return hipErrorInvalidValue;
     return with_storage(storage, [&](auto ts) {
         hipLaunchKernelGGL(k_linear_probe<decltype(ts)>, dim3(1), dim3(64), 0, s, st, a, rec);
+    });
+}
+
+hipError_t launch_gather_model(const DevState &st, const ModelArgs &a, double *rec, int64_t *cnt, int storage, hipStream_t s) {
+    if (!linear_args_ok(st, a) || !model_args_ok(a) || a.npend >= st.pcap || !rec || !cnt) return hipErrorInvalidValue;
+    const int64_t grid = std::max<int64_t>(1, cdiv(st.tm.padded(a.n_mm), kBlock));
+    return with_storage(storage, [&](auto ts) {
+        hipLaunchKernelGGL(k_gather_model<decltype(ts)>, dim3((unsigned)grid), dim3(kBlock), 0, s, st, a, rec, cnt);
+    });
+}
+
+hipError_t launch_model_probe(const DevState &st, const ModelArgs &a, double *rec, int storage, hipStream_t s) {
+    if (!linear_args_ok(st, a) || !model_args_ok(a) || !rec) return hipErrorInvalidValue;
+    return with_storage(storage, [&](auto ts) {
+        hipLaunchKernelGGL(k_model_probe<decltype(ts)>, dim3(1), dim3(64), 0, s, st, a, rec);
     });
 }
 

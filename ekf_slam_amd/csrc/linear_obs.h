@@ -17,8 +17,9 @@
 // irregular, 2.0 gated
 
 // operand e of ekfm::linear_small (device_math.h names the layout); the cross block comes from the tiles and needs the chain
-template <typename TS>
-__device__ __forceinline__ double linear_small_entry(const DevState &st, const LinearArgs &a, int e) {
+// (A: LinearArgs, or model_obs.h's ModelArgs -- its fields a, cur, pstart and npend)
+template <typename TS, typename A>
+__device__ __forceinline__ double linear_small_entry(const DevState &st, const A &a, int e) {
     const int cur = a.cur;
     const int64_t a0 = a.a[0], a1 = a.a[1];
     if (e < 9) return st.prr[cur][e];

@@ -471,6 +471,82 @@ class Engine:
         self._check(self.lib.ekf_linear_rejections(self.h, ctypes.byref(a), ctypes.byref(b)))
         return int(a.value), int(b.value)
 
+    # ---- observations through a model linearised on the device (include/ekfslam.h: ekf_observe_model) ----
+    @staticmethod
+    def _model_obs(model, z, R, landmarks, anchor, gate):
+        model = int(model)
+        rows = L.EKF_MODEL_ROWS.get(model)
+        if rows is None:
+            raise ValueError("model observation: model is one of EKF_MODEL_* (1..5)")
+        o = L.EkfModelObs()
+        o.model = model
+        zin = _vec(z)
+        if not rows <= zin.size <= 2:
+            raise ValueError("model observation: z has one value per row of the model")
+        for q in range(rows):
+            o.z[q] = zin[q]
+        Rm = np.zeros((2, 2))
+        if R is not None:
+            Ra = np.asarray(R, dtype=np.float64)
+            if rows == 1 and Ra.size == 1:
+                Rm[0, 0] = float(Ra.reshape(-1)[0])
+            elif Ra.size == 4:
+                Rm[:] = Ra.reshape(2, 2)
+            else:
+                raise ValueError("model observation: R is 2 x 2 (or a variance for a one-row model)")
+        for q, v in enumerate(Rm.reshape(-1, order="F")):
+            o.R[q] = v
+        lms = [int(k) for k in landmarks]
+        if len(lms) > 2:
+            raise ValueError("model observation: at most two landmarks")
+        o.lm[0] = o.lm[1] = -1
+        for b, k in enumerate(lms):
+            o.lm[b] = k
+        if anchor is not None:
+            if lms:
+                raise ValueError("model observation: the target is a landmark or an anchor, not both")
+            av = _vec(anchor)
+            if av.size != 2:
+                raise ValueError("model observation: the anchor is a point (2 values)")
+            o.anchor[0], o.anchor[1] = av[0], av[1]
+        elif not lms:
+            raise ValueError("model observation: name the target, a landmark or an anchor")
+        o.gate = float(gate)
+        return o
+
+    def observe_model(self, model, z, R, landmarks=(), anchor=None, gate=float("inf"), wait=False):
+        """'h(x) was observed as z with noise covariance R' for one of the models EKF_MODEL_* (range and bearing, range, bearing,
+        relative position, landmark range), linearised on the device at the live x (ekf_observe_model).  landmarks: the 0-based
+        target (two for EKF_MODEL_LANDMARK_RANGE); anchor: a fixed point outside the map as the target instead.  An update-step like
+        observe_linear: nothing is flushed; wait=True returns {'nu', 'S', 'd2', 'outcome'} (a target on the robot raises EkfError)."""
+        o = self._model_obs(model, z, R, landmarks, anchor, gate)
+        if not wait:
+            self._check(self.lib.ekf_observe_model(self.h, ctypes.byref(o), None))
+            return None
+        res = L.EkfLinearResult()
+        self._check(self.lib.ekf_observe_model(self.h, ctypes.byref(o), ctypes.byref(res)))
+        return self._linear_result(res)
+
+    def model_innovation(self, model, z, R, landmarks=(), anchor=None, gate=float("inf")):
+        """{'nu', 'S', 'd2', 'outcome'} observe_model(..., wait=True) would report under the current state, bit for bit; changes and
+        flushes nothing (ekf_model_innovation)."""
+        o = self._model_obs(model, z, R, landmarks, anchor, gate)
+        res = L.EkfLinearResult()
+        self._check(self.lib.ekf_model_innovation(self.h, ctypes.byref(o), ctypes.byref(res)))
+        return self._linear_result(res)
+
+    @staticmethod
+    def model_evaluate(model, xr, t0, t1=None, lib=None):
+        """(h(x), H) of a model at the robot state xr = (x, y, theta in degrees) and the targets t0 (and t1: the second landmark of
+        EKF_MODEL_LANDMARK_RANGE): the function the kernel runs, on the host (ekf_model_evaluate).  H is 2 x 7 over
+        x, y, theta | t0 | t1; an anchor's block is simply not used."""
+        lib = L.lib() if lib is None else lib
+        hx, H = np.zeros(2), np.zeros(14)
+        rc = lib.ekf_model_evaluate(int(model), _p(_vec(xr, 3)), _p(_vec(t0, 2)), _p(_vec(t1, 2)) if t1 is not None else None, _p(hx), _p(H))
+        if rc:
+            raise L.EkfError(rc, "ekf_model_evaluate")
+        return hx, H.reshape(2, 7)
+
     def load_lowrank_state(self, x, s, d, U):
         x, s, d = _vec(x), _vec(s), _vec(d)
         U = np.asfortranarray(np.asarray(U, dtype=np.float64))

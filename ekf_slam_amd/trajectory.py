@@ -13,7 +13,9 @@ is written exactly as before (format 1, the same arrays); one with edits as form
 'merge_batch' edit (merge_landmarks_batch: idx = [keep1, drop1, keep2, drop2, ...], R shared) as format 3, which has the arrays of
 format 2 -- a reader of format 2 alone would not know the fourth kind; one that holds an 'observe' edit (observe_linear: a linear
 observation made between two steps -- idx = the 0, 1 or 2 landmarks that carry a block, the delta slot = z, R, and per observation Hr,
-the landmark blocks Hl, gate, wrap and rows in arrays of their own) as format 4.
+the landmark blocks Hl, gate, wrap and rows in arrays of their own) as format 4; one that holds an 'observe_model' edit (observe_model:
+idx = the 0, 1 or 2 landmarks, the delta slot = z, R, and per observation the model, the anchor (NaN where the target is a landmark) and
+the gate in arrays of their own) as format 5, which has the arrays of format 4 (empty where no linear observation was made).
 """
 import numpy as np
 
@@ -21,11 +23,14 @@ FORMAT = "ekfslam-trajectory-1"
 FORMAT_EDITS = "ekfslam-trajectory-2"
 FORMAT_BATCH = "ekfslam-trajectory-3"
 FORMAT_OBSERVE = "ekfslam-trajectory-4"
+FORMAT_MODEL = "ekfslam-trajectory-5"
 EDIT_KINDS = ("remove", "constrain", "merge", "merge_batch")        # what record_edit takes
 OBSERVE = "observe"                                                  # the fifth kind: record_observation's, number 4 in a file
-_KINDS = EDIT_KINDS + (OBSERVE,)
+OBSERVE_MODEL = "observe_model"                                      # the sixth kind: record_model_observation's, number 5 in a file
+_KINDS = EDIT_KINDS + (OBSERVE, OBSERVE_MODEL)
 _STEP_ARRAYS = ("u", "obs_ptr", "obs", "lm_ptr", "lm_index", "lm_loc")
 _EDIT_ARRAYS = ("edit_step", "edit_kind", "edit_ptr", "edit_idx", "edit_delta", "edit_R")
+_MODEL_ARRAYS = ("model_edit", "model_id", "model_anchor", "model_gate")
 _OBSERVE_ARRAYS = ("observe_edit", "observe_Hr", "observe_Hl", "observe_gate", "observe_wrap", "observe_rows")
 
 
@@ -33,6 +38,7 @@ class TrajectoryLog:
     def __init__(self):
         self.u, self.obs, self.lm_index, self.lm_loc = [], [], [], []
         self.edits = []             # (step, kind, idx (1-based numbers), delta[2], R[2x2]) in the order they were made
+        self.model_observations = {}  # position in self.edits of an 'observe_model' edit -> {model, anchor (2) or None, gate}
         self.observations = {}      # position in self.edits of an 'observe' edit -> {Hr (2x3), Hl (2x2x2), gate, wrap (2), rows}
 
     def __len__(self):
@@ -88,6 +94,22 @@ class TrajectoryLog:
         self.edits.append((len(self), OBSERVE, lms.astype(np.int64), zv,
                            np.zeros((2, 2)) if R is None else np.asarray(R, dtype=np.float64).reshape(2, 2).copy()))
 
+    def record_model_observation(self, model, z, R, landmarks=(), anchor=None, gate=float("inf")):
+        """An observation through a model (observe_model of ekf_slam_amd/slam.py) made now, i.e. after the len(self) steps recorded so
+        far: the model's number, z, R (2 x 2), the 1-based landmarks, the anchor (None: the target is a landmark) and the gate."""
+        lms = np.asarray(list(landmarks), dtype=np.float64).reshape(-1)
+        if not np.all(lms == np.floor(lms)):
+            raise ValueError("record_model_observation: landmark indices are whole numbers")
+        if lms.size > 2:
+            raise ValueError("record_model_observation: at most two landmarks")
+        zv = np.zeros(2)
+        zin = np.asarray(z, dtype=np.float64).reshape(-1)
+        zv[:zin.size] = zin
+        self.model_observations[len(self.edits)] = dict(
+            model=int(model), anchor=None if anchor is None else np.asarray(anchor, dtype=np.float64).reshape(2).copy(), gate=float(gate))
+        self.edits.append((len(self), OBSERVE_MODEL, lms.astype(np.int64), zv,
+                           np.zeros((2, 2)) if R is None else np.asarray(R, dtype=np.float64).reshape(2, 2).copy()))
+
     def save(self, path):
         def ragged(parts, width):
             ptr = np.cumsum([0] + [len(p) for p in parts])
@@ -102,7 +124,7 @@ class TrajectoryLog:
             return
         e_ptr, e_idx = ragged([e[2] for e in self.edits], 0)
         fmt = FORMAT_BATCH if any(e[1] == "merge_batch" for e in self.edits) else FORMAT_EDITS
-        if self.observations:
+        if self.observations or self.model_observations:
             fmt = FORMAT_OBSERVE
             at = sorted(self.observations)
             ob = [self.observations[q] for q in at]
@@ -110,6 +132,13 @@ class TrajectoryLog:
                           observe_Hl=np.array([o["Hl"] for o in ob]).reshape(-1, 2, 2, 2), observe_gate=np.array([o["gate"] for o in ob]),
                           observe_wrap=np.array([o["wrap"] for o in ob], dtype=np.int64).reshape(-1, 2),
                           observe_rows=np.array([o["rows"] for o in ob], dtype=np.int64))
+        if self.model_observations:
+            fmt = FORMAT_MODEL
+            at = sorted(self.model_observations)
+            mo = [self.model_observations[q] for q in at]
+            arrays.update(model_edit=np.array(at, dtype=np.int64), model_id=np.array([o["model"] for o in mo], dtype=np.int64),
+                          model_anchor=np.array([np.full(2, np.nan) if o["anchor"] is None else o["anchor"] for o in mo]).reshape(-1, 2),
+                          model_gate=np.array([o["gate"] for o in mo]))
         np.savez_compressed(path, format=np.array(fmt), edit_step=np.array([e[0] for e in self.edits], dtype=np.int64),
                             edit_kind=np.array([_KINDS.index(e[1]) for e in self.edits], dtype=np.int64), edit_ptr=e_ptr,
                             edit_idx=e_idx.astype(np.int64), edit_delta=np.array([e[3] for e in self.edits]).reshape(-1, 2),
@@ -119,9 +148,10 @@ class TrajectoryLog:
     def load(path):
         g = np.load(path, allow_pickle=False)
         fmt = str(g["format"])
-        if fmt not in (FORMAT, FORMAT_EDITS, FORMAT_BATCH, FORMAT_OBSERVE):
-            raise ValueError("not an %s / %s / %s / %s file" % (FORMAT, FORMAT_EDITS, FORMAT_BATCH, FORMAT_OBSERVE))
-        need = _STEP_ARRAYS + (_EDIT_ARRAYS if fmt != FORMAT else ()) + (_OBSERVE_ARRAYS if fmt == FORMAT_OBSERVE else ())
+        if fmt not in (FORMAT, FORMAT_EDITS, FORMAT_BATCH, FORMAT_OBSERVE, FORMAT_MODEL):
+            raise ValueError("not an %s / %s / %s / %s / %s file" % (FORMAT, FORMAT_EDITS, FORMAT_BATCH, FORMAT_OBSERVE, FORMAT_MODEL))
+        need = (_STEP_ARRAYS + (_EDIT_ARRAYS if fmt != FORMAT else ()) + (_OBSERVE_ARRAYS if fmt in (FORMAT_OBSERVE, FORMAT_MODEL) else ())
+                + (_MODEL_ARRAYS if fmt == FORMAT_MODEL else ()))
         missing = [k for k in need if k not in g.files]
         if missing:
             raise ValueError("an %s file holds %s: %s is missing" % (fmt, ", ".join(need), ", ".join(missing)))
@@ -135,7 +165,12 @@ class TrajectoryLog:
                 a, b = g["edit_ptr"][q], g["edit_ptr"][q + 1]
                 t.edits.append((int(g["edit_step"][q]), _KINDS[int(g["edit_kind"][q])], g["edit_idx"][a:b].astype(np.int64),
                                 g["edit_delta"][q].copy(), g["edit_R"][q].copy()))
-        if fmt == FORMAT_OBSERVE:
+        if fmt == FORMAT_MODEL:
+            for k, q in enumerate(g["model_edit"]):
+                anchor = g["model_anchor"][k].copy()
+                t.model_observations[int(q)] = dict(model=int(g["model_id"][k]), anchor=None if np.all(np.isnan(anchor)) else anchor,
+                                                    gate=float(g["model_gate"][k]))
+        if fmt in (FORMAT_OBSERVE, FORMAT_MODEL):
             for k, q in enumerate(g["observe_edit"]):
                 t.observations[int(q)] = dict(Hr=g["observe_Hr"][k].copy(), Hl=g["observe_Hl"][k].copy(), gate=float(g["observe_gate"][k]),
                                               wrap=g["observe_wrap"][k].astype(np.int64), rows=int(g["observe_rows"][k]))
@@ -144,7 +179,7 @@ class TrajectoryLog:
     def replay(self, engine, start=0, stop=None):
         """predict + measure for steps [start, stop) on anything with predict(u) / measure(obs, u, idx, loc) -- an Engine.  The edits
         recorded at positions [start, stop) are applied in front of their step through the engine's remove_landmarks /
-        constrain_landmarks / merge_landmarks / merge_landmarks_batch / observe_linear (0-based there: the recorded 1-based numbers are converted here); the ones recorded
+        constrain_landmarks / merge_landmarks / merge_landmarks_batch / observe_linear / observe_model (0-based there: the recorded 1-based numbers are converted here); the ones recorded
         at position len(self), after the last step, when stop is the end of the log."""
         stop = len(self) if stop is None else stop
 
@@ -157,6 +192,9 @@ class TrajectoryLog:
                     o = self.observations[q]
                     engine.observe_linear(delta[:o["rows"]], R, o["Hr"], idx0, [o["Hl"][b] for b in range(len(idx0))], gate=o["gate"],
                                           wrap=tuple(int(w) for w in o["wrap"]), rows=o["rows"])
+                elif kind == OBSERVE_MODEL:
+                    o = self.model_observations[q]
+                    engine.observe_model(o["model"], delta, R, idx0, anchor=o["anchor"], gate=o["gate"])
                 elif kind == "remove":
                     engine.remove_landmarks(idx0)
                 elif kind == "constrain":

@@ -394,6 +394,50 @@ typedef struct ekf_linear_result { double nu[2]; double S[4] /* column-major */;
 int32_t ekf_observe_linear(ekf_handle *h, const ekf_linear_obs *obs, ekf_linear_result *res /* NULL: do not wait */);
 int32_t ekf_linear_innovation(ekf_handle *h, const ekf_linear_obs *obs, ekf_linear_result *res /* required */);
 int32_t ekf_linear_rejections(ekf_handle *h, int64_t *irregular, int64_t *gated);   /* synchronises, reads and resets */
+/* An observation through a MODEL h(x) whose Jacobian depends on the state: "h(x) was observed as z, with noise covariance R" -- a UWB
+ * beacon (range only), a camera (bearing only), a lidar or stereo front end (the landmark's position in the robot frame), a tape measure
+ * between two beacons.  The update of ekf_observe_linear with H = dh/dx evaluated ON THE DEVICE at the live x (which carries every
+ * pending pair) and nu = z - h(x), not z - H x:
+ *     G = H P,  S = G H' + R,  nu = z - h(x) (bearings wrapped into (-180, 180]),  K = G' S^-1,  x += K nu,  P -= K G,  d2 = nu' S^-1 nu
+ * Unlike ekf_correct, which keeps the reference's conventions, the bearing innovation IS wrapped, the Jacobian carries 180/pi (theta
+ * is in degrees), R is the caller's own covariance (no range scaling) and the step can be gated.
+ * The target t of models 1-4 is landmark lm[0] (0-based) when lm[0] >= 0; with lm[0] == -1 it is the fixed point `anchor`, a known
+ * point that is not in the map: H has no landmark block then and only the robot is corrected through it.  lm[1] is -1 in both cases.
+ * EKF_MODEL_LANDMARK_RANGE takes landmarks lm[0] != lm[1], both >= 0, and has no robot block.
+ * With p = x(0:2), theta = x(2), d = t - p, q = d'd, r = sqrt(q), k = 180/pi, c = cosd(theta), s = sind(theta):
+ *   RANGE_BEARING   h = [r; atan2d(d_y, d_x) - theta]    H(x,y,theta) = [-d_x/r, -d_y/r, 0; k d_y/q, -k d_x/q, -1]
+ *                                                         H(t) = [d_x/r, d_y/r; -k d_y/q, k d_x/q]             row 1 wrapped
+ *   RANGE           its row 0 alone                       BEARING  its row 1 alone (row 0 wrapped)
+ *   RELATIVE_XY     h = [c d_x + s d_y; -s d_x + c d_y]   H(x,y,theta) = [-c, -s, h_1/k; s, -c, -h_0/k]         H(t) = [c, s; -s, c]
+ *   LANDMARK_RANGE  h = |l_0 - l_1|                       H = +e' on l_0, -e' on l_1, e = (l_0 - l_1) / |l_0 - l_1|
+ * R: 2x2 column-major with ekf_observe_linear's rules; a one-row model reads R[0] >= 0 alone and runs as the pair with the exactly
+ * empty second row (S = [[s, 0], [0, 1]], nu1 = 0), as rows == 1 does there.
+ * An UPDATE-STEP exactly as ekf_observe_linear: one launch counted under EKF_KERNEL_GATHER, no flush, ekf_pending grows by one, with
+ * res == NULL nothing is waited for; gate, res and the outcomes are its.  Where q is 0 or not finite (the target on the robot, the two
+ * landmarks of a range on one point) there is no Jacobian: the outcome is EKF_LINEAR_IRREGULAR, the launch is a finite no-op, and with
+ * res != NULL the call returns EKF_ERR_STATE.  Launches that do not apply are counted in the SAME two counters ekf_linear_rejections
+ * reads and resets: it reports linear and model observations together.
+ * Refused before anything changes, in this order: obs NULL, an unknown model, a non-finite entry of z (of the rows in use) or of the
+ * anchor (where it is the target), a bad R, a NaN gate, an lm pattern the model does not allow (EKF_ERR_INVALID_ARG); then
+ * ekf_observe_linear's rungs: world > 1 (EKF_ERR_INVALID_ARG: sharding, the anchor forms included), a sharded correction in flight
+ * (EKF_ERR_STATE), the measure loop settled, an lm outside [0, N) (EKF_ERR_INDEX).
+ * ekf_model_innovation is ekf_linear_innovation for a model: what ekf_observe_model WOULD report, bit for bit, nothing changed.
+ * ekf_model_evaluate is the function the kernel runs, on the host (pure, like ekf_motion_model): h(x) and H (row-major 2 x 7 over
+ * x, y, theta | t0 | t1; rows and blocks a model does not have are zero) at the robot state xr and the targets t0 (models 1-4: the
+ * target, landmark or anchor -- an anchor's block of H is not used) and t1 (model 5 alone: the second landmark; else may be NULL).
+ * EKF_ERR_STATE (H and hx zero) where q is 0 or not finite. */
+enum { EKF_MODEL_RANGE_BEARING = 1, EKF_MODEL_RANGE = 2, EKF_MODEL_BEARING = 3, EKF_MODEL_RELATIVE_XY = 4, EKF_MODEL_LANDMARK_RANGE = 5 };
+typedef struct ekf_model_obs {
+    int32_t model, reserved;   /* EKF_MODEL_*; reserved: 0                                                    */
+    double  z[2];              /* the observed value of h(x); a one-row model reads z[0]                      */
+    double  R[4];              /* 2x2 column-major noise covariance; a one-row model reads R[0]               */
+    int64_t lm[2];             /* 0-based landmarks, -1 = none (see above)                                    */
+    double  anchor[2];         /* the target where lm[0] == -1                                                */
+    double  gate;              /* apply only if d2 <= gate; +inf = no gate                                    */
+} ekf_model_obs;
+int32_t ekf_observe_model(ekf_handle *h, const ekf_model_obs *obs, ekf_linear_result *res /* NULL: do not wait */);
+int32_t ekf_model_innovation(ekf_handle *h, const ekf_model_obs *obs, ekf_linear_result *res /* required */);
+int32_t ekf_model_evaluate(int32_t model, const double xr[3], const double t0[2], const double t1[2], double hx[2], double H[14]);
 /* Diagnostic -- a fault injector for tests of the device-resident measure loop's verification, of no use to a host: overwrites the DEVICE copy
  * of signature idx (0-based) and leaves the host mirror alone.  The next ekf_measure whose association involves that landmark then queues its
  * launches from a prediction the device contradicts; every launch stays inside the state (a correction falls back to the predicted landmark,

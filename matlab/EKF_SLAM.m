@@ -149,6 +149,64 @@ classdef EKF_SLAM < handle
             if nargin < 5 || isempty(wait), wait = false; end
             res = h.observeLinear([thetaDeg 0], [variance 0; 0 0], [0 0 1; 0 0 0], [], [], gate, [1 0], 1, wait);
         end
+        function res = observeModel(h, model, z, R, lm, anchor, gate, wait)
+            % 'h(x) was observed as z, with noise covariance R' for a model whose Jacobian depends on the state, linearised on the
+            % GPU at the live state: model 1 range and bearing [r; deg], 2 range, 3 bearing (deg, relative to the heading),
+            % 4 the target's position in the robot frame [forward; left], 5 the distance between two landmarks.  The target is
+            % landmark lm (1-based; two numbers for model 5) or, with lm empty, the known point anchor (1x2) that is not in the
+            % map -- then only the robot is corrected.  Bearing innovations are wrapped into (-180, 180].  An UPDATE-STEP like
+            % observeLinear: nothing is flushed and, unless wait is true, nothing is waited for; applied only if nu' S^-1 nu <= gate.
+            % wait: res = [nu(1) nu(2) S(:)' d2 outcome] (outcome 1 applied, 2 gated).  Not a method of the reference.
+            if nargin < 5, lm = []; end
+            if nargin < 6, anchor = []; end
+            if nargin < 7 || isempty(gate), gate = Inf; end
+            if nargin < 8 || isempty(wait), wait = false; end
+            z = double(z(:)); if numel(z) < 2, z(2) = 0; end
+            if isscalar(R), R = [R 0; 0 0]; end
+            res = h.gateway('observe_model', double(model), z, double(R), double(lm(:)), double(anchor(:)), double(gate), double(wait));
+        end
+        function res = observeRangeBearing(h, i, z, R, gate, wait)
+            % 'Landmark i is seen at range z(1) and bearing z(2) (degrees, relative to the heading), covariance R'.
+            if nargin < 5 || isempty(gate), gate = Inf; end
+            if nargin < 6 || isempty(wait), wait = false; end
+            res = h.observeModel(1, z, R, i, [], gate, wait);
+        end
+        function res = observeRange(h, i, r, variance, gate, wait)
+            % 'Landmark i is at distance r, with this variance' (a range-only beacon).
+            if nargin < 5 || isempty(gate), gate = Inf; end
+            if nargin < 6 || isempty(wait), wait = false; end
+            res = h.observeModel(2, [r 0], [variance 0; 0 0], i, [], gate, wait);
+        end
+        function res = observeBearing(h, i, deg, variance, gate, wait)
+            % 'Landmark i is seen at bearing deg (degrees, relative to the heading), with this variance' (a camera).
+            if nargin < 5 || isempty(gate), gate = Inf; end
+            if nargin < 6 || isempty(wait), wait = false; end
+            res = h.observeModel(3, [deg 0], [variance 0; 0 0], i, [], gate, wait);
+        end
+        function res = observeRelativeXY(h, i, z, R, gate, wait)
+            % 'Landmark i lies at z = [forward left] in the robot frame, covariance R' (a lidar or stereo front end).
+            if nargin < 5 || isempty(gate), gate = Inf; end
+            if nargin < 6 || isempty(wait), wait = false; end
+            res = h.observeModel(4, z, R, i, [], gate, wait);
+        end
+        function res = observeLandmarkRange(h, i, j, dist, variance, gate, wait)
+            % 'Landmarks i and j are dist apart, with this variance' (a tape measure between two beacons).
+            if nargin < 6 || isempty(gate), gate = Inf; end
+            if nargin < 7 || isempty(wait), wait = false; end
+            res = h.observeModel(5, [dist 0], [variance 0; 0 0], [i j], [], gate, wait);
+        end
+        function res = observeAnchorRange(h, pos, r, variance, gate, wait)
+            % 'The known point pos, which is not in the map, is at distance r, with this variance' (a surveyed UWB anchor).
+            if nargin < 5 || isempty(gate), gate = Inf; end
+            if nargin < 6 || isempty(wait), wait = false; end
+            res = h.observeModel(2, [r 0], [variance 0; 0 0], [], pos, gate, wait);
+        end
+        function res = observeAnchorBearing(h, pos, deg, variance, gate, wait)
+            % 'The known point pos, which is not in the map, is seen at bearing deg, with this variance'.
+            if nargin < 5 || isempty(gate), gate = Inf; end
+            if nargin < 6 || isempty(wait), wait = false; end
+            res = h.observeModel(3, [deg 0], [variance 0; 0 0], [], pos, gate, wait);
+        end
         function merges = fuseDuplicatesBatched(h, gate, R, maxMerges)
             % fuseDuplicates with the pairs of one search fused in one mergeLandmarksBatch call: search; walk the candidates in
             % (d2, k) order and take [partner(k) k] when k is not yet a keep or a drop and partner(k) is not yet a drop (a keep may

@@ -22,7 +22,8 @@
 #include "mex.h"
 
 /* The map-editing entry points (ekf_remove_landmarks; ekf_constrain_landmarks, ekf_merge_landmarks, ekf_landmark_distance;
- * ekf_nearest_landmarks; ekf_merge_landmarks_batch) and the linear observation (ekf_observe_linear) are the ones this gateway can live without: bound weakly, so that the gateway still links against a libekfslam (or a stand-in) that
+ * ekf_nearest_landmarks; ekf_merge_landmarks_batch) the linear observation (ekf_observe_linear) and the model observation
+ * (ekf_observe_model) are the ones this gateway can live without: bound weakly, so that the gateway still links against a libekfslam (or a stand-in) that
  * predates them; their commands then raise a MATLAB error instead. */
 #if defined(__GNUC__)
 #pragma weak ekf_remove_landmarks
@@ -32,6 +33,7 @@
 #pragma weak ekf_nearest_landmarks
 #pragma weak ekf_merge_landmarks_batch
 #pragma weak ekf_observe_linear
+#pragma weak ekf_observe_model
 #define HAVE_REMOVE_LANDMARKS (ekf_remove_landmarks != 0)
 #define HAVE_CONSTRAIN_LANDMARKS (ekf_constrain_landmarks != 0)
 #define HAVE_MERGE_LANDMARKS (ekf_merge_landmarks != 0)
@@ -39,6 +41,7 @@
 #define HAVE_NEAREST_LANDMARKS (ekf_nearest_landmarks != 0)
 #define HAVE_MERGE_LANDMARKS_BATCH (ekf_merge_landmarks_batch != 0)
 #define HAVE_OBSERVE_LINEAR (ekf_observe_linear != 0)
+#define HAVE_OBSERVE_MODEL (ekf_observe_model != 0)
 #else
 #define HAVE_REMOVE_LANDMARKS 1
 #define HAVE_CONSTRAIN_LANDMARKS 1
@@ -47,6 +50,7 @@
 #define HAVE_NEAREST_LANDMARKS 1
 #define HAVE_MERGE_LANDMARKS_BATCH 1
 #define HAVE_OBSERVE_LINEAR 1
+#define HAVE_OBSERVE_MODEL 1
 #endif
 
 static void need(int nrhs, int want, const char *cmd) {
@@ -257,6 +261,38 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
         o.rows = (int32_t)mxGetScalar(prhs[9]);
         const int wait = mxGetScalar(prhs[10]) != 0.0;
         check(h, ekf_observe_linear(h, &o, wait ? &res : NULL));
+        plhs[0] = mxCreateDoubleMatrix(wait ? 1 : 0, wait ? 8 : 0, mxREAL);
+        if (wait) {
+            double *out = mxGetPr(plhs[0]);
+            out[0] = res.nu[0]; out[1] = res.nu[1];
+            for (int q = 0; q < 4; ++q) out[2 + q] = res.S[q];
+            out[6] = res.d2; out[7] = (double)res.outcome;
+        }
+        return;
+    }
+    if (!strcmp(cmd, "observe_model")) {          /* res = (h, model 1..5, z 2, R 2x2, lm 0..2 numbers (1-based), anchor [] or 2, gate, wait): the target is
+                                                     lm(1) or, with lm empty, the fixed point anchor; res as observe_linear's */
+        ekf_model_obs o;
+        ekf_linear_result res;
+        need(nrhs, 9, cmd);
+        if (!HAVE_OBSERVE_MODEL) mexErrMsgIdAndTxt("ekfslam:usage", "observe_model: this libekfslam has no ekf_observe_model");
+        const double *z = two_of(prhs[3], cmd, "z"), *R = r2x2_of(prhs[4], cmd);
+        const mwSize k = prhs[5] ? mxGetNumberOfElements(prhs[5]) : 0, na = prhs[6] ? mxGetNumberOfElements(prhs[6]) : 0;
+        if (k > 2 || (k && (mxGetClassID(prhs[5]) != mxDOUBLE_CLASS || !mxGetPr(prhs[5]))))
+            mexErrMsgIdAndTxt("ekfslam:usage", "observe_model: lm names at most two landmarks, class double");
+        if (!((na == 2 && k == 0 && mxGetPr(prhs[6])) || (na == 0 && k > 0)))
+            mexErrMsgIdAndTxt("ekfslam:usage", "observe_model: the target is a landmark (anchor empty) or an anchor of 2 elements (lm empty)");
+        o.model = (int32_t)mxGetScalar(prhs[2]); o.reserved = 0;
+        for (int r = 0; r < 2; ++r) { o.z[r] = z[r]; o.lm[r] = -1; o.anchor[r] = na ? mxGetPr(prhs[6])[r] : 0.0; }
+        for (int q = 0; q < 4; ++q) o.R[q] = R[q];
+        for (mwSize b = 0; b < k; ++b) {                       /* whole numbers a landmark could carry; 1-based -> 0-based, once */
+            const double v = mxGetPr(prhs[5])[b];
+            if (!(v >= -9.0e15 && v <= 9.0e15) || v != (double)(int64_t)v) mexErrMsgIdAndTxt("ekfslam:usage", "observe_model: landmark numbers are whole numbers");
+            o.lm[b] = (int64_t)v - 1;
+        }
+        o.gate = mxGetScalar(prhs[7]);
+        const int wait = mxGetScalar(prhs[8]) != 0.0;
+        check(h, ekf_observe_model(h, &o, wait ? &res : NULL));
         plhs[0] = mxCreateDoubleMatrix(wait ? 1 : 0, wait ? 8 : 0, mxREAL);
         if (wait) {
             double *out = mxGetPr(plhs[0]);

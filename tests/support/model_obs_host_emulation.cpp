@@ -1,0 +1,218 @@
+// Host emulation of the model-observation kernels (tests/test_model_obs_cpu.py compiles and runs it; no GPU, no HIP runtime).
+// The kernel SOURCES of ekf_slam_amd/csrc (tile_access.h, pair_column.h, constrain.h, linear_obs.h, model_obs.h) are compiled for the host
+// behind the shim of merge_batch_host_emulation.cpp -- thread indices as globals, __shared__ as static storage, every workgroup run
+// again until the small part's operands and lane_xor1's partners are there -- and two routes are compared BIT FOR BIT on
+// the same state, with 0 and with 3 pairs pending in the ring:
+//   the model:   k_gather_model, which forms H on its lane 0
+//   the twin:    k_gather_linear handed the H that ekfm::model_eval gives the host at the same x, and a z that yields the same nu
+// in the pair (G, K), the strip, Prr and the diagonal blocks; x to rounding; the record's S and outcome; k_model_probe's record against
+// the launch's.  A target on the robot must leave a zero pair, the state copied and one count.
+// The shim's DevState / LinearArgs / ModelArgs mirror kernels.h (which needs the HIP headers).
+#include <cmath>
+#include <cstdint>
+#include <cstdio>
+#include <cstring>
+#include <vector>
+#include "layout.h"
+#include "device_math.h"
+struct double2 { double x, y; }; struct float2 { float x, y; }; struct float4 { float x, y, z, w; }; struct int2 { int x, y; };
+static inline double2 make_double2(double a, double b) { return {a, b}; }
+static inline float4 make_float4(float a, float b, float c, float d) { return {a, b, c, d}; }
+#define __device__
+#define __global__
+#define __forceinline__ inline
+#define __restrict__
+#define __launch_bounds__(x)
+#define __shared__ static
+static inline void __syncthreads() {}
+struct Idx { unsigned x; };
+static Idx threadIdx, blockIdx;
+constexpr int kBlock = 256;
+static inline int ring_slot(int pstart, int i, int pcap) { const int s = pstart + i; return s >= pcap ? s - pcap : s; }
+static int xor_pass; static std::vector<double> xor_rec[kBlock]; static size_t xor_pos[kBlock];
+static inline double lane_xor1(double v) {
+    const unsigned t = threadIdx.x;
+    if (xor_pass == 0) { xor_rec[t].push_back(v); return 0.0; }
+    return xor_rec[t ^ 1][xor_pos[t]++];
+}
+struct DevState { double *x[2], *prr[2], *strip[2]; void *tiles; double *s, *Gp, *Kp; float *Gp32, *Kp32; int64_t pair_stride; int32_t pcap;
+                  double *small; int64_t ldm; TileMap tm; double *diag[2]; int32_t dcur; };
+struct ConstrainArgs { double d0, d1, R00, R01, R10, R11; int64_t ai, aj, n_mm; int32_t cur, npend, pstart; };
+struct LinearArgs { double z[2], R[4], H[14], gate; int64_t a[2], n_mm; int32_t wrap[2], cur, npend, pstart; };
+struct ModelArgs { double z[2], R[4], anchor[2], gate; int64_t a[2], n_mm; int32_t model, cur, npend, pstart; };
+constexpr int kConstrainRecordDoubles = 8, kLinearRecordDoubles = 8;
+template <typename TS> struct Lane16;
+template <> struct Lane16<double> { using type = double2; static constexpr int kCols = 2; };
+template <> struct Lane16<float>  { using type = float4;  static constexpr int kCols = 4; };
+static inline void lane16_pack(const double *v, double2 &t) { t.x = v[0]; t.y = v[1]; }
+static inline void lane16_pack(const double *v, float4 &t) { t.x = (float)v[0]; t.y = (float)v[1]; t.z = (float)v[2]; t.w = (float)v[3]; }
+#include "tile_access.h"
+#include "pair_column.h"
+#include "constrain.h"
+#include "linear_obs.h"
+#include "model_obs.h"
+
+// every workgroup three times: the first pass leaves the small part's operands in the shared storage, the second one has lane 0 form the
+// shared solve (and k_gather_model's H) from them and records what lane_xor1 hands over, the third one is the launch; what the earlier
+// passes counted is dropped
+template <typename F> static void launch_wg(int grid, int64_t *cnt, F body) {
+    for (int b = 0; b < grid; ++b) {
+        const int64_t c0 = cnt[0], c1 = cnt[1];
+        for (int pass = 0; pass < 3; ++pass) {
+            xor_pass = pass == 2;
+            if (pass < 2) for (int t = 0; t < kBlock; ++t) { xor_rec[t].clear(); xor_pos[t] = 0; }
+            cnt[0] = c0; cnt[1] = c1;
+            for (int t = 0; t < kBlock; ++t) { blockIdx.x = b; threadIdx.x = t; body(); }
+        }
+    }
+}
+struct Store {
+    int T, N, ldm, nt_cap; TileMap tm; int64_t slots;
+    std::vector<double> x[2], prr[2], strip[2], diag[2], ring, tiles; int cur = 0, dcur = 0;
+    DevState st;
+    Store(int T_, int N_, int cap) : T(T_), N(N_) {
+        tm = ekf_make_tilemap(T, 1, 0); nt_cap = (int)ekf_tiles_for(2 * cap, T); ldm = nt_cap * T; slots = tm.row_base(nt_cap);
+        for (int b = 0; b < 2; ++b) { x[b].assign(3 + ldm, 0); prr[b].assign(16, 0); strip[b].assign(3 * ldm, 0); diag[b].assign(3 * cap, 0); }
+        tiles.assign(slots * T * T, 0); ring.assign((size_t)2 * ldm * 8 * 2, 0);
+        sync();
+    }
+    Store(const Store &o) = default;
+    void sync() {
+        for (int b = 0; b < 2; ++b) { st.x[b] = x[b].data(); st.prr[b] = prr[b].data(); st.strip[b] = strip[b].data(); st.diag[b] = diag[b].data(); }
+        st.tiles = tiles.data(); st.s = nullptr; st.Gp = ring.data(); st.Kp = ring.data() + (size_t)2 * ldm * 8; st.Gp32 = st.Kp32 = nullptr;
+        st.pair_stride = 2 * ldm; st.pcap = 8; st.small = nullptr; st.ldm = ldm; st.tm = tm; st.dcur = dcur;
+    }
+    double &tile(int64_t r, int64_t c) { return tiles[tm.tile_offset(r >> tm.shift, c >> tm.shift) + ((r & (T - 1)) << tm.shift) + (c & (T - 1))]; }
+    void flip() { cur ^= 1; dcur ^= 1; sync(); }
+    int grid() const { return (int)((tm.padded(2 * N) + kBlock - 1) / kBlock); }
+};
+static double rnd() { return (rand() % 20001 - 10000) / 10000.0; }
+static void fill(Store &S) {            // P = D + U U' (k = 3), x random; tiles, strip, prr, diag consistent
+    srand(11);
+    const int n = 3 + 2 * S.N;
+    std::vector<double> U(n * 3), d(n);
+    for (auto &v : U) v = 0.3 * rnd();
+    for (auto &v : d) v = 0.1 + 0.05 * (rnd() + 1);
+    auto P = [&](int r, int c) { double v = r == c ? d[r] : 0; for (int k = 0; k < 3; ++k) v += U[r * 3 + k] * U[c * 3 + k]; return v; };
+    for (int i = 0; i < n; ++i) S.x[0][i] = 20 * rnd();
+    S.x[0][2] = 137.0 + 40 * rnd();
+    for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) S.prr[0][3 * r + c] = P(r > c ? r : c, r > c ? c : r);
+    for (int r = 0; r < 3; ++r) for (int c = 0; c < 2 * S.N; ++c) S.strip[0][r * S.ldm + c] = P(3 + c, r);
+    for (int r = 0; r < 2 * S.N; ++r) for (int c = 0; c < 2 * S.N; ++c) {
+        const bool diag = (r / S.T) == (c / S.T);
+        if (c > r && !diag) continue;
+        S.tile(r, c) = P(3 + (r > c ? r : c), 3 + (r > c ? c : r));
+    }
+    for (int k = 0; k < S.N; ++k) { S.diag[0][3 * k] = P(3 + 2 * k, 3 + 2 * k); S.diag[0][3 * k + 1] = P(4 + 2 * k, 3 + 2 * k); S.diag[0][3 * k + 2] = P(4 + 2 * k, 4 + 2 * k); }
+}
+static void run_linear(Store &S, LinearArgs a, double *rec, int64_t *cnt) {
+    a.n_mm = 2 * S.N; a.cur = S.cur; a.pstart = 0;
+    DevState st = S.st;
+    launch_wg(S.grid(), cnt, [&] { k_gather_linear<double>(st, a, rec, cnt); });
+    S.flip();
+}
+static int differ(const std::vector<double> &u, const std::vector<double> &v, const char *what) {
+    int b = 0;
+    for (size_t i = 0; i < u.size(); ++i) if (memcmp(&u[i], &v[i], 8)) ++b;
+    if (b) printf("  %s: %d differ\n", what, b);
+    return b;
+}
+
+int main() {
+    const double RP[4] = { 0.02, 0.005, 0.005, 0.03 };
+    struct Case { const char *name; int model, l0, l1; bool anchored; };
+    int total_bad = 0;
+    for (int T : { 16, 64 }) for (int pending : { 0, 3 }) {
+        const int N = 150, cap = 158, e = T == 16 ? 72 : 64;
+        Store base(T, N, cap);
+        fill(base);
+        int64_t cnt0[2] = { 0, 0 };
+        double rec0[8];
+        for (int k = 0; k < pending; ++k) {                   // some pairs pending in the ring (never applied to the tiles)
+            LinearArgs a = {};
+            for (int q = 0; q < 14; ++q) a.H[q] = 0.4 * rnd();
+            a.a[0] = 2 * (k ? 5 + 40 * k : e); a.a[1] = 2 * (N - 1 - k);
+            const double R[4] = { 0.3, 0.05, 0.05, 0.2 };
+            memcpy(a.R, R, sizeof R);
+            const double *x = base.x[base.cur].data();
+            for (int r = 0; r < 2; ++r) {
+                double hx = 0;
+                for (int i = 0; i < 3; ++i) hx += a.H[7 * r + i] * x[i];
+                for (int b = 0; b < 2; ++b) for (int c = 0; c < 2; ++c) hx += a.H[7 * r + 3 + 2 * b + c] * x[3 + a.a[b] + c];
+                a.z[r] = hx + 0.2 * rnd();
+            }
+            a.gate = INFINITY; a.npend = k;
+            run_linear(base, a, rec0, cnt0);
+            if (rec0[7] != 1.0) { printf("a pending pair did not apply\n"); return 2; }
+        }
+        const Case cases[] = { { "range and bearing, edge", 1, e, -1, false }, { "range, last", 2, N - 1, -1, false }, { "bearing, first", 3, 0, -1, false },
+                               { "relative xy, edge", 4, e, -1, false }, { "landmark range over a tile edge", 5, e, e - 1, false },
+                               { "landmark range, first and last", 5, 0, N - 1, false }, { "range and bearing, anchor", 1, -1, -1, true },
+                               { "bearing, anchor", 3, -1, -1, true }, { "range, anchor on the robot", 2, -1, -1, true } };
+        for (const Case &c : cases) {
+            Store A(base), B(base);
+            A.sync(); B.sync();
+            const double *x = A.x[A.cur].data();
+            const bool on_robot = !strcmp(c.name, "range, anchor on the robot");
+            ModelArgs m = {};
+            m.model = c.model; m.a[0] = c.l0 >= 0 ? 2 * c.l0 : -1; m.a[1] = c.l1 >= 0 ? 2 * c.l1 : -1;
+            m.anchor[0] = on_robot ? x[0] : x[0] + 9.0; m.anchor[1] = on_robot ? x[1] : x[1] - 5.0;
+            m.gate = INFINITY; m.n_mm = 2 * N; m.cur = A.cur; m.npend = pending; m.pstart = 0;
+            const bool two = c.model == 1 || c.model == 4;
+            const double R1[4] = { 0.05, 0, 0, 1.0 };
+            memcpy(m.R, two ? RP : R1, sizeof m.R);
+            double xs[7] = { x[0], x[1], x[2], 0, 0, 0, 0 }, hx[2], H[14];
+            if (c.l0 >= 0) { xs[3] = x[3 + 2 * c.l0]; xs[4] = x[4 + 2 * c.l0]; }
+            if (c.l1 >= 0) { xs[5] = x[3 + 2 * c.l1]; xs[6] = x[4 + 2 * c.l1]; }
+            const bool posed = ekfm::model_eval(c.model, xs, m.anchor, c.l0 >= 0, hx, H);
+            m.z[0] = hx[0] + 0.3; m.z[1] = two ? hx[1] - 0.4 : 0.0;
+            if (c.model == 3) m.z[0] += 360.0;                                  // (a bearing a whole turn away: the wrap brings it back)
+            double recA[8], recP[8], recB[8];
+            int64_t cntA[2] = { 0, 0 }, cntB[2] = { 0, 0 };
+            DevState stA = A.st;
+            for (int t = 0; t < 64; ++t) { blockIdx.x = 0; threadIdx.x = t; k_model_probe<double>(stA, m, recP); }      // (pass 0: the operands)
+            for (int t = 0; t < 64; ++t) { blockIdx.x = 0; threadIdx.x = t; k_model_probe<double>(stA, m, recP); }
+            launch_wg(A.grid(), cntA, [&] { k_gather_model<double>(stA, m, recA, cntA); });
+            A.flip();
+            int bad = 0;
+            if (memcmp(recA, recP, sizeof recA)) { printf("  the probe's record differs from the launch's\n"); ++bad; }
+            if (on_robot) {
+                // a finite no-op: outcome 0, d2 NaN, a zero pair, the state copied, one count
+                if (posed || recA[7] != 0.0 || !std::isnan(recA[6]) || cntA[0] != 1 || cntA[1] != 0) { printf("  on the robot: not reported as irregular\n"); ++bad; }
+                for (int q = 0; q < 6; ++q) if (!std::isfinite(recA[q])) ++bad;
+                bad += differ(A.x[A.cur], base.x[base.cur], "x") + differ(A.strip[A.cur], base.strip[base.cur], "strip") +
+                       differ(A.diag[A.dcur], base.diag[base.dcur], "diag");
+                for (int q = 0; q < 9; ++q) if (A.prr[A.cur][q] != base.prr[base.cur][q]) ++bad;
+                const size_t off = (size_t)pending * A.st.pair_stride;
+                for (int64_t q = 0; q < 2 * A.tm.padded(2 * N); ++q) if (A.st.Gp[off + q] != 0.0 || A.st.Kp[off + q] != 0.0) ++bad;
+            } else {
+                LinearArgs l = {};
+                memcpy(l.R, m.R, sizeof l.R); memcpy(l.H, H, sizeof H);
+                if (c.l0 < 0) for (int r = 0; r < 2; ++r) for (int q = 3; q < 7; ++q) l.H[7 * r + q] = 0.0;
+                l.a[0] = m.a[0]; l.a[1] = m.a[1]; l.gate = INFINITY; l.npend = pending;
+                for (int r = 0; r < 2; ++r) {
+                    double Hx = 0;
+                    for (int i = 0; i < 7; ++i) Hx += l.H[7 * r + i] * xs[i];
+                    l.z[r] = Hx + recA[4 + r];
+                }
+                run_linear(B, l, recB, cntB);
+                if (recA[7] != 1.0 || recB[7] != 1.0 || cntA[0] || cntA[1]) { printf("  not applied\n"); ++bad; }
+                if (memcmp(recA, recB, 4 * sizeof(double))) { printf("  S differs\n"); ++bad; }
+                const double want0 = 0.3, want1 = two ? -0.4 : 0.0;
+                if (std::fabs(recA[4] - want0) > 1e-11 || std::fabs(recA[5] - want1) > 1e-11) { printf("  nu = %.17g, %.17g\n", recA[4], recA[5]); ++bad; }
+                if (!two && (recA[1] != 0.0 || recA[2] != 0.0 || recA[3] != 1.0 || recA[5] != 0.0)) { printf("  the second row is not empty\n"); ++bad; }
+                bad += differ(A.strip[A.cur], B.strip[B.cur], "strip") + differ(A.prr[A.cur], B.prr[B.cur], "prr") + differ(A.diag[A.dcur], B.diag[B.dcur], "diag") +
+                       differ(A.ring, B.ring, "pair ring");
+                double dx = 0, moved = 0;
+                for (size_t i = 0; i < A.x[A.cur].size(); ++i) {
+                    dx = std::fmax(dx, std::fabs(A.x[A.cur][i] - B.x[B.cur][i]));
+                    moved = std::fmax(moved, std::fabs(A.x[A.cur][i] - base.x[base.cur][i]));
+                }
+                if (!(dx < 1e-10) || !(moved > 1e-6)) { printf("  x: differs from the twin by %g, moved by %g\n", dx, moved); ++bad; }
+            }
+            printf("T=%d pending=%d %s: %d differences\n", T, pending, c.name, bad);
+            total_bad += bad;
+        }
+    }
+    return total_bad != 0;
+}
