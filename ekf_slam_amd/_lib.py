@@ -58,6 +58,14 @@ class EkfModelObs(ctypes.Structure):
 EKF_MODEL_RANGE_BEARING, EKF_MODEL_RANGE, EKF_MODEL_BEARING, EKF_MODEL_RELATIVE_XY, EKF_MODEL_LANDMARK_RANGE = 1, 2, 3, 4, 5
 EKF_MODEL_ROWS = {1: 2, 2: 1, 3: 1, 4: 2, 5: 1}       # rows of z each model reads
 
+EKF_APPEND_MODEL_MAX = 32
+
+
+class EkfModelInit(ctypes.Structure):
+    """struct ekf_model_init (include/ekfslam.h)."""
+    _fields_ = [("model", _i32), ("reserved", _i32), ("z", _d * 2), ("R", _d * 4), ("signature", _d)]
+
+
 # name -> (restype, argtypes); every symbol of include/ekfslam.h
 SIGNATURES = {
     "ekf_abi_version": (_i32, []),
@@ -113,6 +121,8 @@ SIGNATURES = {
     "ekf_observe_model": (_i32, [_vp, ctypes.POINTER(EkfModelObs), ctypes.POINTER(EkfLinearResult)]),
     "ekf_model_innovation": (_i32, [_vp, ctypes.POINTER(EkfModelObs), ctypes.POINTER(EkfLinearResult)]),
     "ekf_model_evaluate": (_i32, [_i32, _dp, _dp, _dp, _dp, _dp]),
+    "ekf_append_model": (_i32, [_vp, ctypes.POINTER(EkfModelInit), _i64, ctypes.POINTER(_i64)]),
+    "ekf_model_invert": (_i32, [_i32, _dp, _dp, _dp, _dp, _dp]),
     "ekf_diag_poke_device_signature": (_i32, [_vp, _i64, _d]),
     "ekf_get_P": (_i32, [_vp, _dp]),
     "ekf_set_P": (_i32, [_vp, _dp, _i64]),

@@ -322,4 +322,37 @@ EKF_MHD void model_small(const double *sm, const double H[14], const double hx[2
         }
 }
 
+// The INVERSE of the two models that determine a point (ekf_append_model; append_model.h runs it on the device): the landmark t = g(x_r, z)
+// that z observes from the pose xr, with Gx = dg/dx_r (row-major 2 x 3) and Gz = dg/dz (row-major 2 x 2).  Gx is always [1 0 gth0; 0 1 gth1]:
+// only gth = dg/dtheta depends on the state.  theta and a bearing in degrees, k = 180/pi, as in model_eval -- so H_t Gz = I and
+// H_r + H_t Gx = 0 with model_eval's blocks at (xr, t).  RANGE_BEARING z = (r, b): t = p + r (cosd, sind)(theta + b); RELATIVE_XY
+// z = (a, b): t = p + Rot(theta) z.  Returns false (nothing written) for any other model.  Each expression is written once: the host
+// (ekf_model_invert) and k_append_model give the same bits.
+EKF_MHD bool model_invert(int model, const double xr[3], const double z[2], double t[2], double gth[2], double Gz[4]) {
+    if (model == 1) {
+        double s, c;
+        sincosd(xr[2] + z[1], s, c);
+        t[0] = xr[0] + z[0] * c;
+        t[1] = xr[1] + z[0] * s;
+        gth[0] = -z[0] * s / kR2D;
+        gth[1] = z[0] * c / kR2D;
+        Gz[0] = c; Gz[1] = gth[0];
+        Gz[2] = s; Gz[3] = gth[1];
+        return true;
+    }
+    if (model == 4) {
+        double s, c;
+        sincosd(xr[2], s, c);
+        const double w0 = c * z[0] - s * z[1], w1 = s * z[0] + c * z[1];
+        t[0] = xr[0] + w0;
+        t[1] = xr[1] + w1;
+        gth[0] = -w1 / kR2D;
+        gth[1] = w0 / kR2D;
+        Gz[0] = c; Gz[1] = -s;
+        Gz[2] = s; Gz[3] = c;
+        return true;
+    }
+    return false;
+}
+
 }  // namespace ekfm

@@ -107,6 +107,24 @@ struct AppendArgs {
 hipError_t launch_append(const DevState &st, const AppendArgs &a, int storage, hipStream_t s, const DevLoopArgs *dl = nullptr,
                          const PredictArgs *fused_predict = nullptr);
 
+// k_append_model (append_model.h): m <= kAppendModelMax landmarks that start from a range-and-bearing or a relative-position fix, appended
+// by ONE launch at the live robot state -- entry b becomes landmark N + b.  Nothing but new slots is written, in place on buffer cur (the
+// live diagonal copies: st.dcur); no predict is folded in.  The entries travel in the argument block.
+constexpr int kAppendModelMax = 32;
+struct AppendModelEntry {
+    double z0, z1;            // RANGE_BEARING: range, bearing in degrees; RELATIVE_XY: the landmark in the robot frame
+    double R00, R01, R10, R11;
+    double signature;
+    int32_t model, pad;       // EKF_MODEL_RANGE_BEARING (1) or EKF_MODEL_RELATIVE_XY (4)
+};
+struct AppendModelArgs {
+    int64_t N;                // landmarks before the append
+    int32_t m;                // entries in use
+    int32_t cur;
+    AppendModelEntry e[kAppendModelMax];
+};
+hipError_t launch_append_model(const DevState &st, const AppendModelArgs &a, int storage, hipStream_t s);
+
 struct CorrectArgs {
     double z0, z1;            // [range, bearing_deg]
     double R00, R01, R10, R11;

@@ -29,6 +29,15 @@ hipError_t launch_append(const DevState &st, const AppendArgs &a, int storage, h
     }); });
 }
 
+hipError_t launch_append_model(const DevState &st, const AppendModelArgs &a, int storage, hipStream_t s) {
+    if (a.N < 0 || a.m < 1 || a.m > kAppendModelMax || 2 * (a.N + a.m) > st.ldm) return hipErrorInvalidValue;
+    for (int b = 0; b < a.m; ++b) if (a.e[b].model != 1 && a.e[b].model != 4) return hipErrorInvalidValue;
+    const int64_t grid = cdiv(2 * (a.N + a.m), kBlock);
+    return with_storage(storage, [&](auto ts) {
+        hipLaunchKernelGGL(k_append_model<decltype(ts)>, dim3((unsigned)grid), dim3(kBlock), 0, s, st, a);
+    });
+}
+
 // k_gather.  The kernel is 216 VGPRs wide and every flag doubles its instantiations, so only the forms a handle can ask for exist:
 // per storage type  {plain, fused downdate, device loop} x {predict folded in or not},  the device-decided form (never with a predict),
 // sharded {plain, device loop} x {predict}  -- 11, each named by one of the launchers below.

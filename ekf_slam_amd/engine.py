@@ -547,6 +547,50 @@ class Engine:
             raise L.EkfError(rc, "ekf_model_evaluate")
         return hx, H.reshape(2, 7)
 
+    # ---- landmarks that start from a model's inverse (include/ekfslam.h: ekf_append_model) ----
+    @staticmethod
+    def _model_inits(entries):
+        entries = list(entries)
+        arr = (L.EkfModelInit * max(len(entries), 1))()
+        for o, ent in zip(arr, entries):
+            if len(ent) != 4:
+                raise ValueError("append_model: an entry is (model, z, R, signature)")
+            model, z, R, signature = ent
+            o.model = int(model)
+            zin = _vec(z)
+            if zin.size != 2:
+                raise ValueError("append_model: z has two values")
+            o.z[0], o.z[1] = zin[0], zin[1]
+            Ra = np.asarray(R, dtype=np.float64)
+            if Ra.size != 4:
+                raise ValueError("append_model: R is 2 x 2")
+            for q, v in enumerate(Ra.reshape(2, 2).reshape(-1, order="F")):
+                o.R[q] = v
+            o.signature = float(signature)
+        return arr, len(entries)
+
+    def append_model(self, entries):
+        """One scan of new landmarks: entries = [(model, z, R, signature), ...] with model EKF_MODEL_RANGE_BEARING (z = range, bearing in
+        degrees) or EKF_MODEL_RELATIVE_XY (z = the landmark in the robot frame), all inverted on the device at the live robot state and
+        appended by one launch (ekf_append_model).  Returns the 0-based index of the first one; entry b becomes landmark first + b.
+        Nothing is waited for or flushed."""
+        arr, m = self._model_inits(entries)
+        first = ctypes.c_int64(-1)
+        self._check(self.lib.ekf_append_model(self.h, arr, m, ctypes.byref(first)))
+        return int(first.value)
+
+    @staticmethod
+    def model_invert(model, xr, z, lib=None):
+        """(t, Gx, Gz): the landmark that z observes from the robot state xr = (x, y, theta in degrees) through EKF_MODEL_RANGE_BEARING
+        or EKF_MODEL_RELATIVE_XY, with Gx = dt/dx_r (2 x 3) and Gz = dt/dz (2 x 2): the function the kernel runs, on the host
+        (ekf_model_invert)."""
+        lib = L.lib() if lib is None else lib
+        t, Gx, Gz = np.zeros(2), np.zeros(6), np.zeros(4)
+        rc = lib.ekf_model_invert(int(model), _p(_vec(xr, 3)), _p(_vec(z, 2)), _p(t), _p(Gx), _p(Gz))
+        if rc:
+            raise L.EkfError(rc, "ekf_model_invert")
+        return t, Gx.reshape(2, 3), Gz.reshape(2, 2)
+
     def load_lowrank_state(self, x, s, d, U):
         x, s, d = _vec(x), _vec(s), _vec(d)
         U = np.asfortranarray(np.asarray(U, dtype=np.float64))

@@ -131,6 +131,13 @@ class ShardGroup:
         for e in self.shards:
             e.append(u, R, pos, signature)
 
+    def append_model(self, entries):
+        """Engine.append_model on every shard: everything the launch reads (x_r, Prr, the strip) is replicated, so no exchange is
+        needed; each shard writes the tiles it owns.  Returns the 0-based index of the first new landmark."""
+        entries = list(entries)
+        first = [e.append_model(entries) for e in self.shards]
+        return first[0]
+
     def correct(self, z, R, idx0):
         for e in self.shards:
             e.correct_begin(z, R, idx0)

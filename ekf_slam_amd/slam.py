@@ -340,6 +340,44 @@ class _EkfBase:
         """'The known point pos, which is not in the map, is seen at bearing deg, with variance var'."""
         return self.observe_model(L.EKF_MODEL_BEARING, [float(deg)], [[float(var), 0.0], [0.0, 0.0]], anchor=_vec(pos, 2), gate=gate, wait=wait)
 
+    def add_landmarks_model(self, entries):
+        """One scan of NEW landmarks under observe_model's conventions: entries = [(model, z, R), ...] or [(model, z, R, signature),
+        ...] with model EKF_MODEL_RANGE_BEARING (1: z = range, bearing in degrees relative to the heading) or EKF_MODEL_RELATIVE_XY (4:
+        z = (forward, left) in the robot frame) -- a one-row model does not determine a point.  Every entry is inverted on the device at
+        the live robot state and the whole scan is appended by one launch (ekf_append_model); waits for nothing, flushes nothing.  A
+        signature left out (or None) is the landmark's own 1-based number.  Returns the 1-based numbers of the new landmarks.  The
+        reference has no such method: its append takes the position from the caller's table."""
+        entries = [tuple(e) for e in entries]
+        if not 1 <= len(entries) <= L.EKF_APPEND_MODEL_MAX:
+            raise ValueError("add_landmarks_model: between 1 and %d entries" % L.EKF_APPEND_MODEL_MAX)
+        N = self._e.N
+        full = []
+        for b, e in enumerate(entries):
+            if len(e) not in (3, 4):
+                raise ValueError("add_landmarks_model: an entry is (model, z, R) or (model, z, R, signature)")
+            model = int(e[0])
+            if model not in (L.EKF_MODEL_RANGE_BEARING, L.EKF_MODEL_RELATIVE_XY):
+                raise ValueError("add_landmarks_model: model is EKF_MODEL_RANGE_BEARING (1) or EKF_MODEL_RELATIVE_XY (4)")
+            Rm = np.asarray(e[2], dtype=np.float64)
+            if Rm.size != 4:
+                raise ValueError("add_landmarks_model: R is 2 x 2")
+            sig = e[3] if len(e) == 4 and e[3] is not None else N + b + 1
+            full.append((model, _vec(e[1], 2).copy(), Rm.reshape(2, 2).copy(), float(sig)))
+        first = self._e.append_model(full)
+        if self.log is not None:
+            self.log.record_model_append(full)
+        return [first + b + 1 for b in range(len(full))]
+
+    def add_landmark_range_bearing(self, z, R, signature=None):
+        """'A landmark that is not in the map yet is seen at range z[0] and bearing z[1] (degrees, relative to the heading), covariance
+        R': it joins the map at the point that observation names.  Returns its 1-based number."""
+        return self.add_landmarks_model([(L.EKF_MODEL_RANGE_BEARING, z, R, signature)])[0]
+
+    def add_landmark_relative_xy(self, z, R, signature=None):
+        """'A landmark that is not in the map yet lies at z = (forward, left) in the robot frame, covariance R'.  Returns its 1-based
+        number."""
+        return self.add_landmarks_model([(L.EKF_MODEL_RELATIVE_XY, z, R, signature)])[0]
+
     def _push_params(self):
         pass
 

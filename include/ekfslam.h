@@ -438,6 +438,38 @@ typedef struct ekf_model_obs {
 int32_t ekf_observe_model(ekf_handle *h, const ekf_model_obs *obs, ekf_linear_result *res /* NULL: do not wait */);
 int32_t ekf_model_innovation(ekf_handle *h, const ekf_model_obs *obs, ekf_linear_result *res /* required */);
 int32_t ekf_model_evaluate(int32_t model, const double xr[3], const double t0[2], const double t1[2], double hx[2], double H[14]);
+/* New landmarks under the SAME conventions: "a landmark that is not in the map yet was seen as z through the model, with noise covariance
+ * R".  ekf_append keeps the reference's append (the position from the caller's table, Jacobians built from the motion input, no pi/180)
+ * and is the inverse of none of the models above; a filter driven through ekf_observe_model starts its landmarks here.  Only the models
+ * that determine a point are accepted, EKF_MODEL_RANGE_BEARING and EKF_MODEL_RELATIVE_XY.  With p = x(0:2), theta = x(2) in degrees,
+ * k = 180/pi, the landmark t = g(x_r, z), Gx = dg/dx_r = [1 0 g0; 0 1 g1] and Gz = dg/dz are
+ *   RANGE_BEARING  z = (r, b):  (s, c) = sincosd(theta + b)   t = p + r (c, s)   (g0, g1) = (-r s / k, r c / k)   Gz = [c g0; s g1]
+ *   RELATIVE_XY    z = (a, b):  (s, c) = sincosd(theta)       w = (c a - s b, s a + c b)   t = p + w
+ *                                                              (g0, g1) = (-w_1 / k, w_0 / k)                       Gz = [c -s; s c]
+ * evaluated ON THE DEVICE at the live x_r (which carries every pending pair), so that h(g(x, z)) = z, H_t Gz = I and H_r + H_t Gx = 0
+ * with ekf_model_evaluate's blocks: right after the call ekf_model_innovation of the same z on the new landmark reports nu = 0, S = 2 R.
+ * A batch is one scan: all m entries are inverted at the same x_r, entry b becomes landmark N + b (0-based; *first_idx = N) with
+ *     x <- t_b     s <- signature_b     P(new_b, new_b) = Gx_b Prr Gx_b' + Gz_b R_b Gz_b'     P(1:3, new_b) = Prr Gx_b'
+ *     P(new_b, old) = Gx_b P(1:3, old)                  P(new_b, new_a) = Gx_b Prr Gx_a'  (a < b)
+ * by ONE launch (counted under EKF_KERNEL_APPEND) that writes new slots only -- bit for bit what m calls with one entry leave.  The call
+ * returns without waiting for the device, does not flush and leaves ekf_pending as it found it; beside a pass in flight
+ * (cfg.async_flush) it does not wait for the pass, as ekf_append.  A recorded predict is carried out first, by a launch of its own.
+ * SHARDED handles are supported: everything the launch reads is replicated, so the same call on every shard needs no exchange.
+ * Refused with nothing changed, in this order: h or obs NULL, m < 1 or m > EKF_APPEND_MODEL_MAX (EKF_ERR_INVALID_ARG); per entry, an
+ * unknown or one-row model, a non-finite z, r <= 0 for RANGE_BEARING, an R that ekf_observe_linear's rules refuse
+ * (EKF_ERR_INVALID_ARG); then, with the measure loop settled (cfg.device_assoc = 4: N exact), a sharded correction between begin and
+ * finish (EKF_ERR_STATE); N + m > cfg.capacity_landmarks (EKF_ERR_CAPACITY: all or nothing).
+ * ekf_model_invert is the function the kernel runs, on the host (pure, like ekf_model_evaluate): t, Gx (row-major 2 x 3) and Gz
+ * (row-major 2 x 2) at the robot state xr; EKF_ERR_INVALID_ARG for a NULL argument or any other model. */
+#define EKF_APPEND_MODEL_MAX 32
+typedef struct ekf_model_init {
+    int32_t model, reserved;   /* EKF_MODEL_RANGE_BEARING or EKF_MODEL_RELATIVE_XY; reserved: 0                */
+    double  z[2];              /* the observed value                                                          */
+    double  R[4];              /* 2x2 column-major noise covariance of z                                      */
+    double  signature;
+} ekf_model_init;
+int32_t ekf_append_model(ekf_handle *h, const ekf_model_init *obs, int64_t m, int64_t *first_idx /* may be NULL */);
+int32_t ekf_model_invert(int32_t model, const double xr[3], const double z[2], double t[2], double Gx[6], double Gz[4]);
 /* Diagnostic -- a fault injector for tests of the device-resident measure loop's verification, of no use to a host: overwrites the DEVICE copy
  * of signature idx (0-based) and leaves the host mirror alone.  The next ekf_measure whose association involves that landmark then queues its
  * launches from a prediction the device contradicts; every launch stays inside the state (a correction falls back to the predicted landmark,

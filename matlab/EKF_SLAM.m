@@ -207,6 +207,30 @@ classdef EKF_SLAM < handle
             if nargin < 6 || isempty(wait), wait = false; end
             res = h.observeModel(3, [deg 0], [variance 0; 0 0], [], pos, gate, wait);
         end
+        function idx = addLandmarksModel(h, model, z, R, signature)
+            % One scan of NEW landmarks under observeModel's conventions: entry b was seen as z(b, :) through model(b) -- 1 range and
+            % bearing [r deg], 4 the position in the robot frame [forward left]; a one-row model does not determine a point -- with
+            % noise covariance R(:, :, b) (one 2x2 R: shared by all).  Every entry is inverted on the GPU at the live robot state and
+            % the whole scan (at most 32 entries) is appended by one launch; nothing is flushed or waited for.  signature: one per
+            % entry; left out or empty, each landmark's own number.  idx: the new landmarks' numbers.  Not a method of the reference,
+            % whose append takes the position from the landmark table.
+            model = double(model(:)); m = numel(model);
+            z = double(reshape(z, [], 2));
+            R = double(R); if size(R, 3) == 1, R = repmat(R, [1 1 m]); end
+            if nargin < 5 || isempty(signature), signature = numel(h.s) + (1:m)'; end
+            idx = h.gateway('append_model', model, z, R, double(signature(:)));
+        end
+        function idx = addLandmarkRangeBearing(h, z, R, signature)
+            % 'A landmark that is not in the map yet is seen at range z(1) and bearing z(2) (degrees, relative to the heading),
+            % covariance R': it joins the map at the point that observation names.
+            if nargin < 4, signature = []; end
+            idx = h.addLandmarksModel(1, z(:)', R, signature);
+        end
+        function idx = addLandmarkRelativeXY(h, z, R, signature)
+            % 'A landmark that is not in the map yet lies at z = [forward left] in the robot frame, covariance R'.
+            if nargin < 4, signature = []; end
+            idx = h.addLandmarksModel(4, z(:)', R, signature);
+        end
         function merges = fuseDuplicatesBatched(h, gate, R, maxMerges)
             % fuseDuplicates with the pairs of one search fused in one mergeLandmarksBatch call: search; walk the candidates in
             % (d2, k) order and take [partner(k) k] when k is not yet a keep or a drop and partner(k) is not yet a drop (a keep may

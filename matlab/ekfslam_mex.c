@@ -22,8 +22,8 @@
 #include "mex.h"
 
 /* The map-editing entry points (ekf_remove_landmarks; ekf_constrain_landmarks, ekf_merge_landmarks, ekf_landmark_distance;
- * ekf_nearest_landmarks; ekf_merge_landmarks_batch) the linear observation (ekf_observe_linear) and the model observation
- * (ekf_observe_model) are the ones this gateway can live without: bound weakly, so that the gateway still links against a libekfslam (or a stand-in) that
+ * ekf_nearest_landmarks; ekf_merge_landmarks_batch) the linear observation (ekf_observe_linear), the model observation
+ * (ekf_observe_model) and the append through a model (ekf_append_model) are the ones this gateway can live without: bound weakly, so that the gateway still links against a libekfslam (or a stand-in) that
  * predates them; their commands then raise a MATLAB error instead. */
 #if defined(__GNUC__)
 #pragma weak ekf_remove_landmarks
@@ -34,6 +34,7 @@
 #pragma weak ekf_merge_landmarks_batch
 #pragma weak ekf_observe_linear
 #pragma weak ekf_observe_model
+#pragma weak ekf_append_model
 #define HAVE_REMOVE_LANDMARKS (ekf_remove_landmarks != 0)
 #define HAVE_CONSTRAIN_LANDMARKS (ekf_constrain_landmarks != 0)
 #define HAVE_MERGE_LANDMARKS (ekf_merge_landmarks != 0)
@@ -42,6 +43,7 @@
 #define HAVE_MERGE_LANDMARKS_BATCH (ekf_merge_landmarks_batch != 0)
 #define HAVE_OBSERVE_LINEAR (ekf_observe_linear != 0)
 #define HAVE_OBSERVE_MODEL (ekf_observe_model != 0)
+#define HAVE_APPEND_MODEL (ekf_append_model != 0)
 #else
 #define HAVE_REMOVE_LANDMARKS 1
 #define HAVE_CONSTRAIN_LANDMARKS 1
@@ -51,6 +53,7 @@
 #define HAVE_MERGE_LANDMARKS_BATCH 1
 #define HAVE_OBSERVE_LINEAR 1
 #define HAVE_OBSERVE_MODEL 1
+#define HAVE_APPEND_MODEL 1
 #endif
 
 static void need(int nrhs, int want, const char *cmd) {
@@ -300,6 +303,31 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
             for (int q = 0; q < 4; ++q) out[2 + q] = res.S[q];
             out[6] = res.d2; out[7] = (double)res.outcome;
         }
+        return;
+    }
+    if (!strcmp(cmd, "append_model")) {           /* idx = (h, model m x 1 (1 or 4), z m x 2, R 2 x 2 x m, signature m x 1): one scan of new landmarks,
+                                                     each from its own observation; idx m x 1, their 1-based numbers */
+        need(nrhs, 6, cmd);
+        if (!HAVE_APPEND_MODEL) mexErrMsgIdAndTxt("ekfslam:usage", "append_model: this libekfslam has no ekf_append_model");
+        const mwSize m = prhs[2] ? mxGetNumberOfElements(prhs[2]) : 0;
+        if (m < 1 || m > EKF_APPEND_MODEL_MAX) mexErrMsgIdAndTxt("ekfslam:usage", "append_model: between 1 and %d entries in one call", EKF_APPEND_MODEL_MAX);
+        if (!mxGetPr(prhs[2]) || !prhs[3] || mxGetM(prhs[3]) != m || mxGetNumberOfElements(prhs[3]) != 2 * m || !mxGetPr(prhs[3]))
+            mexErrMsgIdAndTxt("ekfslam:usage", "append_model: z needs m x 2 elements, one row per entry of model");
+        if (!prhs[4] || mxGetNumberOfElements(prhs[4]) != 4 * m || !mxGetPr(prhs[4]))
+            mexErrMsgIdAndTxt("ekfslam:usage", "append_model: R needs 2 x 2 x m elements");
+        if (!prhs[5] || mxGetNumberOfElements(prhs[5]) != m || !mxGetPr(prhs[5]))
+            mexErrMsgIdAndTxt("ekfslam:usage", "append_model: signature needs m elements");
+        ekf_model_init o[EKF_APPEND_MODEL_MAX];
+        for (mwSize b = 0; b < m; ++b) {
+            o[b].model = (int32_t)mxGetPr(prhs[2])[b]; o[b].reserved = 0;
+            o[b].z[0] = mxGetPr(prhs[3])[b]; o[b].z[1] = mxGetPr(prhs[3])[m + b];       /* column-major m x 2 */
+            for (int q = 0; q < 4; ++q) o[b].R[q] = mxGetPr(prhs[4])[4 * b + q];
+            o[b].signature = mxGetPr(prhs[5])[b];
+        }
+        int64_t first = 0;
+        check(h, ekf_append_model(h, o, (int64_t)m, &first));
+        plhs[0] = mxCreateDoubleMatrix(m, 1, mxREAL);
+        for (mwSize b = 0; b < m; ++b) mxGetPr(plhs[0])[b] = (double)(first + (int64_t)b + 1);
         return;
     }
     if (!strcmp(cmd, "merge_landmarks_batch")) {  /* d2 = (h, pairs k x 2 [keep drop], R 2x2): k x 1; landmark numbers 1-based, as they are before the call */

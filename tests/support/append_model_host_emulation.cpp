@@ -1,0 +1,261 @@
+// Host emulation of k_append_model (tests/test_append_model_cpu.py compiles and runs it; no GPU, no HIP runtime).
+// The kernel SOURCES of ekf_slam_amd/csrc (tile_access.h, append.h, append_model.h, and pair_column.h / constrain.h / linear_obs.h for the
+// pairs that are left pending) are compiled for the host behind the shim of model_obs_host_emulation.cpp -- thread indices as globals,
+// __shared__ as static storage, every workgroup run again until what its first lanes leave in the shared storage is there.  For tiles of
+// edge 16 and 64, double and float tiles, 0 and 3 pairs pending in the ring, and m = 1, 3, 9 entries from 123 landmarks (the columns of
+// landmark 128 start k_append_model's second workgroup and, at T = 16, a tile row):
+//   the batch:   one launch with m entries
+//   the singles: m launches of one entry each
+// must leave the tiles, the strip, x, s, both diagonal copies and the pair ring BIT FOR BIT the same, and everything below the old map
+// untouched.  Each case's live state before (the pending pairs applied to what the tiles hold) and its new rows after are written to
+// argv[1] for the dense restatement of tests/append_model_cases.py.
+// The shim's DevState / LinearArgs / AppendModelArgs mirror kernels.h (which needs the HIP headers); what append.h's k_append names
+// besides them is declared and never defined -- the template is not instantiated here.
+#include <cmath>
+#include <cstdint>
+#include <cstdio>
+#include <cstring>
+#include <string>
+#include <vector>
+#include "layout.h"
+#include "device_math.h"
+struct double2 { double x, y; }; struct float2 { float x, y; }; struct float4 { float x, y, z, w; }; struct int2 { int x, y; };
+static inline double2 make_double2(double a, double b) { return {a, b}; }
+static inline float4 make_float4(float a, float b, float c, float d) { return {a, b, c, d}; }
+#define __device__
+#define __global__
+#define __forceinline__ inline
+#define __restrict__
+#define __launch_bounds__(x)
+#define __shared__ static
+static inline void __syncthreads() {}
+struct Idx { unsigned x; };
+static Idx threadIdx, blockIdx;
+constexpr int kBlock = 256;
+static inline int ring_slot(int pstart, int i, int pcap) { const int s = pstart + i; return s >= pcap ? s - pcap : s; }
+static int xor_pass; static std::vector<double> xor_rec[kBlock]; static size_t xor_pos[kBlock];
+static inline double lane_xor1(double v) {
+    const unsigned t = threadIdx.x;
+    if (xor_pass == 0) { xor_rec[t].push_back(v); return 0.0; }
+    return xor_rec[t ^ 1][xor_pos[t]++];
+}
+struct DevState { double *x[2], *prr[2], *strip[2]; void *tiles; double *s, *Gp, *Kp; float *Gp32, *Kp32; int64_t pair_stride; int32_t pcap;
+                  double *small; int64_t ldm; TileMap tm; double *diag[2]; int32_t dcur; };
+struct ConstrainArgs { double d0, d1, R00, R01, R10, R11; int64_t ai, aj, n_mm; int32_t cur, npend, pstart; };
+struct LinearArgs { double z[2], R[4], H[14], gate; int64_t a[2], n_mm; int32_t wrap[2], cur, npend, pstart; };
+constexpr int kConstrainRecordDoubles = 8, kLinearRecordDoubles = 8;
+constexpr int kAppendModelMax = 32;
+struct AppendModelEntry { double z0, z1, R00, R01, R10, R11, signature; int32_t model, pad; };
+struct AppendModelArgs { int64_t N; int32_t m, cur; AppendModelEntry e[kAppendModelMax]; };
+// what k_append (append.h) names: declared, never defined
+struct PredictArgs { double u0, u1, C; int64_t n_mm; int32_t cur; };
+struct AppendArgs { double u0, u1, R00, R01, R10, R11, pos0, pos1, signature; int64_t N; int32_t cur; };
+struct AssocHostPartial;
+struct DevLoopArgs { const AssocHostPartial *parts_in; AssocHostPartial *rec; int32_t nblk_in, seq_in, seq_rec; };
+struct PredictSmall { double fa, fb; double pose[3]; double prr[9]; double Q[9]; };
+void predict_small(const double pose[3], const double prr_in[9], double u0, double u1, double C, PredictSmall &o);
+void predict_strip(double &s0, double &s1, double s2, double fa, double fb);
+void reduce_partials_wave(const AssocHostPartial *parts, int nblk, int seq, int lane, double &ll, int &ix);
+void store_partial(AssocHostPartial *dst, double ll, int index, int seq);
+template <typename TS> struct Lane16;
+template <> struct Lane16<double> { using type = double2; static constexpr int kCols = 2; };
+template <> struct Lane16<float>  { using type = float4;  static constexpr int kCols = 4; };
+static inline void lane16_pack(const double *v, double2 &t) { t.x = v[0]; t.y = v[1]; }
+static inline void lane16_pack(const double *v, float4 &t) { t.x = (float)v[0]; t.y = (float)v[1]; t.z = (float)v[2]; t.w = (float)v[3]; }
+#include "tile_access.h"
+#include "append.h"
+#include "append_model.h"
+#include "pair_column.h"
+#include "constrain.h"
+#include "linear_obs.h"
+
+// k_gather_linear: every workgroup three times (model_obs_host_emulation.cpp: the operands, the shared solve and lane_xor1's partners, the launch)
+template <typename F> static void launch_wg3(int grid, int64_t *cnt, F body) {
+    for (int b = 0; b < grid; ++b) {
+        const int64_t c0 = cnt[0], c1 = cnt[1];
+        for (int pass = 0; pass < 3; ++pass) {
+            xor_pass = pass == 2;
+            if (pass < 2) for (int t = 0; t < kBlock; ++t) { xor_rec[t].clear(); xor_pos[t] = 0; }
+            cnt[0] = c0; cnt[1] = c1;
+            for (int t = 0; t < kBlock; ++t) { blockIdx.x = b; threadIdx.x = t; body(); }
+        }
+    }
+}
+// k_append_model: every workgroup twice -- the first run leaves t, dg/dtheta and Gz R Gz' of every entry in the shared storage, the second
+// one is the launch (it rewrites every slot the first one wrote; no lane reads a slot the launch writes)
+template <typename F> static void launch_wg2(int grid, F body) {
+    for (int b = 0; b < grid; ++b)
+        for (int pass = 0; pass < 2; ++pass)
+            for (int t = 0; t < kBlock; ++t) { blockIdx.x = b; threadIdx.x = t; body(); }
+}
+
+template <typename TS> struct Store {
+    int T, N, ldm, nt_cap, cap; TileMap tm; int64_t slots;
+    std::vector<double> x[2], prr[2], strip[2], diag[2], ring, s; std::vector<TS> tiles; int cur = 0, dcur = 0;
+    DevState st;
+    Store(int T_, int N_, int cap_) : T(T_), N(N_), cap(cap_) {
+        tm = ekf_make_tilemap(T, 1, 0); nt_cap = (int)ekf_tiles_for(2 * cap, T); ldm = nt_cap * T; slots = tm.row_base(nt_cap);
+        for (int b = 0; b < 2; ++b) { x[b].assign(3 + ldm, 0); prr[b].assign(16, 0); strip[b].assign(3 * ldm, 0); diag[b].assign(3 * cap, 0); }
+        tiles.assign(slots * T * T, 0); ring.assign((size_t)2 * ldm * 8 * 2, 0); s.assign(cap, 0);
+        sync();
+    }
+    Store(const Store &o) = default;
+    void sync() {
+        for (int b = 0; b < 2; ++b) { st.x[b] = x[b].data(); st.prr[b] = prr[b].data(); st.strip[b] = strip[b].data(); st.diag[b] = diag[b].data(); }
+        st.tiles = tiles.data(); st.s = s.data(); st.Gp = ring.data(); st.Kp = ring.data() + (size_t)2 * ldm * 8; st.Gp32 = st.Kp32 = nullptr;
+        st.pair_stride = 2 * ldm; st.pcap = 8; st.small = nullptr; st.ldm = ldm; st.tm = tm; st.dcur = dcur;
+    }
+    TS &tile(int64_t r, int64_t c) { return tiles[tm.tile_offset(r >> tm.shift, c >> tm.shift) + ((r & (T - 1)) << tm.shift) + (c & (T - 1))]; }
+    void flip() { cur ^= 1; dcur ^= 1; sync(); }
+    // live P(3 + r, 3 + c), r >= c, of the landmark block: the own blocks from the F64 copies, everything else the tile with the
+    // `pending` pairs of ring slots 0 .. applied in slot order (rows that did not exist when a pair was formed have K = 0)
+    double live(int64_t r, int64_t c, int pending) {
+        if ((r >> 1) == (c >> 1)) return diag[dcur][3 * (r >> 1) + (r & 1) + (c & 1)];
+        double v = (double)tile(r, c);
+        for (int i = 0; i < pending; ++i) {
+            const double *G = st.Gp + (size_t)i * st.pair_stride, *K = st.Kp + (size_t)i * st.pair_stride;
+            v = rank2_apply(v, make_double2(K[2 * r], K[2 * r + 1]), make_double2(G[2 * c], G[2 * c + 1]));
+        }
+        return v;
+    }
+};
+static double rnd() { return (rand() % 20001 - 10000) / 10000.0; }
+template <typename TS> static void fill(Store<TS> &S) {            // P = D + U U' (k = 3), x random; tiles, strip, prr, diag consistent
+    srand(11);
+    const int n = 3 + 2 * S.N;
+    std::vector<double> U(n * 3), d(n);
+    for (auto &v : U) v = 0.3 * rnd();
+    for (auto &v : d) v = 0.1 + 0.05 * (rnd() + 1);
+    auto P = [&](int r, int c) { double v = r == c ? d[r] : 0; for (int k = 0; k < 3; ++k) v += U[r * 3 + k] * U[c * 3 + k]; return v; };
+    for (int i = 0; i < n; ++i) S.x[0][i] = 20 * rnd();
+    S.x[0][2] = 137.0 + 40 * rnd();
+    for (int k = 0; k < S.N; ++k) S.s[k] = k + 1.0;
+    for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) S.prr[0][3 * r + c] = P(r > c ? r : c, r > c ? c : r);
+    for (int r = 0; r < 3; ++r) for (int c = 0; c < 2 * S.N; ++c) S.strip[0][r * S.ldm + c] = P(3 + c, r);
+    for (int r = 0; r < 2 * S.N; ++r) for (int c = 0; c < 2 * S.N; ++c) {
+        const bool diag = (r / S.T) == (c / S.T);
+        if (c > r && !diag) continue;
+        S.tile(r, c) = (TS)P(3 + (r > c ? r : c), 3 + (r > c ? c : r));
+    }
+    for (int k = 0; k < S.N; ++k) { S.diag[0][3 * k] = P(3 + 2 * k, 3 + 2 * k); S.diag[0][3 * k + 1] = P(4 + 2 * k, 3 + 2 * k); S.diag[0][3 * k + 2] = P(4 + 2 * k, 4 + 2 * k); }
+}
+template <typename TS> static void run_linear(Store<TS> &S, LinearArgs a, double *rec, int64_t *cnt) {
+    a.n_mm = 2 * S.N; a.cur = S.cur; a.pstart = 0;
+    DevState st = S.st;
+    launch_wg3((int)((S.tm.padded(2 * S.N) + kBlock - 1) / kBlock), cnt, [&] { k_gather_linear<TS>(st, a, rec, cnt); });
+    S.flip();
+}
+template <typename TS> static void run_append(Store<TS> &S, const AppendModelEntry *e, int m) {
+    AppendModelArgs a = {};
+    a.N = S.N; a.m = m; a.cur = S.cur;
+    for (int b = 0; b < m; ++b) a.e[b] = e[b];
+    DevState st = S.st;
+    launch_wg2((2 * (S.N + m) + kBlock - 1) / kBlock, [&] { k_append_model<TS>(st, a); });
+    S.N += m;
+}
+template <typename V> static int differ(const std::vector<V> &u, const std::vector<V> &v, const char *what) {
+    int b = 0;
+    for (size_t i = 0; i < u.size(); ++i) if (memcmp(&u[i], &v[i], sizeof(V))) ++b;
+    if (b) printf("  %s: %d differ\n", what, b);
+    return b;
+}
+static void put(FILE *f, const std::vector<double> &v) { fwrite(v.data(), 8, v.size(), f); }
+
+template <typename TS> static int run_cases(const char *ts, const std::string &dir) {
+    int total_bad = 0;
+    for (int T : { 16, 64 }) for (int pending : { 0, 3 }) {
+        const int N = 123, cap = 136;
+        Store<TS> base(T, N, cap);
+        fill(base);
+        int64_t cnt0[2] = { 0, 0 };
+        double rec0[8];
+        for (int k = 0; k < pending; ++k) {                   // some pairs pending in the ring (never applied to the tiles)
+            LinearArgs a = {};
+            for (int q = 0; q < 14; ++q) a.H[q] = 0.4 * rnd();
+            a.a[0] = 2 * (5 + 40 * k); a.a[1] = 2 * (N - 1 - k);
+            const double R[4] = { 0.3, 0.05, 0.05, 0.2 };
+            memcpy(a.R, R, sizeof R);
+            const double *x = base.x[base.cur].data();
+            for (int r = 0; r < 2; ++r) {
+                double hx = 0;
+                for (int i = 0; i < 3; ++i) hx += a.H[7 * r + i] * x[i];
+                for (int b = 0; b < 2; ++b) for (int c = 0; c < 2; ++c) hx += a.H[7 * r + 3 + 2 * b + c] * x[3 + a.a[b] + c];
+                a.z[r] = hx + 0.2 * rnd();
+            }
+            a.gate = INFINITY; a.npend = k;
+            run_linear(base, a, rec0, cnt0);
+            if (rec0[7] != 1.0) { printf("a pending pair did not apply\n"); return 1000; }
+        }
+        // the live state before, for the dense restatement: n, x, s, P (row-major, both triangles)
+        const int n0 = 3 + 2 * N;
+        {
+            std::vector<double> P((size_t)n0 * n0);
+            for (int r = 0; r < n0; ++r) for (int c = 0; c <= r; ++c) {
+                double v;
+                if (r < 3) v = base.prr[base.cur][3 * r + c];
+                else if (c < 3) v = base.strip[base.cur][c * base.ldm + (r - 3)];
+                else v = base.live(r - 3, c - 3, pending);
+                P[(size_t)r * n0 + c] = P[(size_t)c * n0 + r] = v;
+            }
+            FILE *f = fopen((dir + "/before_" + ts + "_" + std::to_string(T) + "_" + std::to_string(pending) + ".bin").c_str(), "wb");
+            if (!f) return 1000;
+            const double hdr[1] = { (double)n0 };
+            fwrite(hdr, 8, 1, f);
+            put(f, std::vector<double>(base.x[base.cur].begin(), base.x[base.cur].begin() + n0));
+            put(f, std::vector<double>(base.s.begin(), base.s.begin() + N));
+            put(f, P);
+            fclose(f);
+        }
+        for (int m : { 1, 3, 9 }) {
+            AppendModelEntry e[kAppendModelMax] = {};
+            for (int b = 0; b < m; ++b) {
+                e[b].model = (b + m) % 2 ? 1 : 4;
+                e[b].z0 = e[b].model == 1 ? 2.0 + 11.0 * (rnd() + 1) : 15 * rnd();
+                e[b].z1 = e[b].model == 1 ? 360.0 * rnd() : 15 * rnd();
+                const double sc = e[b].model == 1 ? 30.0 : 1.0;
+                e[b].R00 = 0.02 * (1 + 0.1 * b); e[b].R01 = e[b].R10 = 0.004 * std::sqrt(sc); e[b].R11 = 0.03 * sc;
+                e[b].signature = 5000.0 + 10 * m + b;
+            }
+            Store<TS> A(base), B(base);
+            A.sync(); B.sync();
+            run_append(A, e, m);
+            for (int b = 0; b < m; ++b) run_append(B, e + b, 1);
+            int bad = 0;
+            bad += differ(A.tiles, B.tiles, "tiles") + differ(A.s, B.s, "s") + differ(A.ring, B.ring, "pair ring") + differ(A.ring, base.ring, "pair ring against before");
+            for (int q = 0; q < 2; ++q)
+                bad += differ(A.x[q], B.x[q], "x") + differ(A.strip[q], B.strip[q], "strip") + differ(A.diag[q], B.diag[q], "diag") + differ(A.prr[q], B.prr[q], "prr");
+            // nothing below the old map moved, and the buffers the launch does not own were not touched
+            bad += differ(A.prr[A.cur], base.prr[base.cur], "prr against before") + differ(A.x[A.cur ^ 1], base.x[base.cur ^ 1], "the other x") +
+                   differ(A.strip[A.cur ^ 1], base.strip[base.cur ^ 1], "the other strip") + differ(A.diag[A.dcur ^ 1], base.diag[base.dcur ^ 1], "the other diag");
+            for (int i = 0; i < n0; ++i) if (A.x[A.cur][i] != base.x[base.cur][i]) ++bad;
+            for (int r = 0; r < 3; ++r) for (int c = 0; c < 2 * N; ++c) if (A.strip[A.cur][r * A.ldm + c] != base.strip[base.cur][r * base.ldm + c]) ++bad;
+            for (int k = 0; k < 3 * N; ++k) if (A.diag[A.dcur][k] != base.diag[base.dcur][k]) ++bad;
+            for (int r = 0; r < 2 * N; ++r) for (int c = 0; c <= r; ++c) if (memcmp(&A.tile(r, c), &base.tile(r, c), sizeof(TS))) ++bad;
+            if (A.N != N + m) ++bad;
+            // the new part after: the entries, then x, s and the rows of P from 3 + 2 N on
+            const int n1 = 3 + 2 * (N + m);
+            std::vector<double> rows((size_t)2 * m * n1), ent;
+            for (int b = 0; b < m; ++b) for (double v : { (double)e[b].model, e[b].z0, e[b].z1, e[b].R00, e[b].R01, e[b].R10, e[b].R11, e[b].signature }) ent.push_back(v);
+            for (int r = n0; r < n1; ++r) for (int c = 0; c < n1; ++c) {
+                const int hi = r > c ? r : c, lo = r > c ? c : r;
+                rows[(size_t)(r - n0) * n1 + c] = lo < 3 ? A.strip[A.cur][lo * A.ldm + (hi - 3)] : A.live(hi - 3, lo - 3, pending);
+            }
+            FILE *f = fopen((dir + "/after_" + ts + "_" + std::to_string(T) + "_" + std::to_string(pending) + "_" + std::to_string(m) + ".bin").c_str(), "wb");
+            if (!f) return 1000;
+            put(f, ent);
+            put(f, std::vector<double>(A.x[A.cur].begin() + n0, A.x[A.cur].begin() + n1));
+            put(f, std::vector<double>(A.s.begin() + N, A.s.begin() + N + m));
+            put(f, rows);
+            fclose(f);
+            printf("%s T=%d pending=%d m=%d: %d differences\n", ts, T, pending, m, bad);
+            total_bad += bad;
+        }
+    }
+    return total_bad;
+}
+
+int main(int argc, char **argv) {
+    if (argc < 2) return 2;
+    const int bad = run_cases<double>("double", argv[1]) + run_cases<float>("float", argv[1]);
+    return bad != 0;
+}

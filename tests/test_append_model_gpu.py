@@ -1,0 +1,397 @@
+"""GPU: landmarks that start from a range-and-bearing or a relative-position fix (ekf_append_model, ekf_model_invert; include/ekfslam.h,
+DESIGN.md section 3k).
+
+The yardstick is the NumPy restatement of tests/append_model_cases.py applied to THE STATE THE ENGINE REPORTED BEFORE THE CALL; stores,
+tolerances and helpers are those of tests/test_linear_obs_gpu.py.  Where two engines must agree because they ran the same arithmetic on
+the same inputs -- a batch against single calls, batch b against batch 1, the asynchronous pass against the synchronous one, the
+device-decided loop against the waited one, shards against one engine, a replayed log -- the comparison is assert_array_equal.
+
+A tile row of T = 16 holds 8 landmarks, landmark 128 is column 256: the first column of k_append_model's second workgroup and, for
+T = 64 and T = 256, the first landmark of a tile row.  The batches below start so that they straddle it."""
+import ctypes
+
+import numpy as np
+import pytest
+
+import append_model_cases as A
+import model_obs_cases as M
+import test_linear_obs_gpu as T
+from removal_cases import lowrank_data, observe
+
+pytestmark = pytest.mark.gpu
+U2, R2, RPOS, REL = T.U2, T.R2, T.RPOS, T.REL
+START = {1: 128, 2: 127, 9: 123, 32: 112}                  # landmarks before a batch of m: it ends beyond landmark 128
+
+
+def history(engines, x, ks):
+    for q in engines:
+        for k in ks:
+            q.predict(U2); q.correct(observe(x, k), R2, k)
+
+
+def pair_of(N, pending, **kw):
+    """Two engines with the same state and history: `pending` corrections, deferred where batch > pending."""
+    x = lowrank_data(N, 5)[0]
+    e, twin = T.loaded(N, 5, **kw), T.loaded(N, 5, **kw)
+    history([e, twin], x, (5, N // 2, N - 3, 11, 40)[:pending])
+    return e, twin
+
+
+def same_state(a, b):
+    assert a.N == b.N
+    for name in ("get_x", "get_s", "get_P", "get_P_diag_blocks"):
+        np.testing.assert_array_equal(getattr(a, name)(), getattr(b, name)(), err_msg=name)
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# 1. against the dense restatement
+# ------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("tile,storage", T.STORES)
+@pytest.mark.parametrize("pending", [0, 5])
+def test_a_scan_against_the_dense_restatement(tile, storage, pending):
+    N = START[9]
+    e, twin = pair_of(N, pending, capacity=N + 16, tile=tile, storage=storage, batch=8)
+    assert e.pending() == pending
+    rng = np.random.default_rng(3)
+    for name, entries in (("both models, one each", A.scan(rng, 2)), ("a scan of nine over the edges", A.scan(rng, 9, 6000.0)),
+                          ("range and bearing alone", A.scan(rng, 1, 7000.0)), ("relative xy alone", A.scan(rng, 2, 8000.0)[1:])):
+        x0, s0, P0 = T.state(twin)                            # (reading flushes the twin; e keeps its pairs pending)
+        ex, es, eP = A.append_model_dense(x0, s0, P0, entries)
+        first = e.append_model(entries)
+        assert first == x0.size // 2 - 1 and e.pending() == pending
+        twin.append_model(entries)
+        np.testing.assert_array_equal(e.get_s(), es)
+        T.check_state(e, ex, eP, storage, name)
+        pending = 0                                           # (check_state read P: the pairs are applied now)
+    assert e.N == N + 13
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# 2. a batch of m is m single calls, bit for bit
+# ------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("tile,storage", T.STORES)
+@pytest.mark.parametrize("m", [1, 2, 9, 32])
+def test_a_batch_is_bit_for_bit_its_single_calls(tile, storage, m):
+    N = START[m]
+    e, twin = pair_of(N, 3, capacity=N + 40, tile=tile, storage=storage, batch=8)
+    entries = A.scan(np.random.default_rng(m), m)
+    assert N <= 128 < N + m or m == 1                         # the batch straddles column 256 and a tile-row edge of every T
+    assert e.append_model(entries) == N
+    for b, ent in enumerate(entries):
+        assert twin.append_model([ent]) == N + b
+    assert e.pending() == twin.pending() == 3
+    same_state(e, twin)
+    assert np.all(np.isfinite(e.get_P()))
+    # ... and both go on alike: corrections of old and of new landmarks, a second scan behind them
+    x = e.get_x()
+    for q in (e, twin):
+        for k in (7, N + m - 1, N, 90):
+            q.predict(U2); q.correct(observe(x, k), R2, k)
+        q.append_model(entries[:2])
+    same_state(e, twin)
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# 3. the known answer: the model observation of the same z finds nu = 0 and S = 2 R
+# ------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("tile,storage", [(16, "f64"), (64, "f64"), (256, "f32_mixed")])
+@pytest.mark.parametrize("pending", [0, 5])
+def test_the_innovation_of_the_same_observation_is_zero_with_S_twice_R(tile, storage, pending):
+    N = START[9]
+    e, _ = pair_of(N, pending, capacity=N + 16, tile=tile, storage=storage, batch=8)
+    rng = np.random.default_rng(17)
+    for model, z, R, sig in A.scan(rng, 6):
+        k = e.append_model([(model, z, R, sig)])
+        got = e.model_innovation(model, z, R, [k])
+        znorm = max(np.abs(z).max(), 1.0)
+        err_S, err_nu = np.abs(got["S"] - 2.0 * R).max() / np.abs(R).max(), np.abs(got["nu"]).max() / znorm
+        print("model %d z %s [%s, %d pending]: |S - 2R| / |R| %.2e, |nu| / max(|z|, 1) %.2e" % (model, z, storage, pending, err_S, err_nu))
+        assert got["outcome"] == M.APPLIED and err_S < REL and err_nu < REL
+        before = e.get_x()[3 + 2 * k:5 + 2 * k]
+        assert e.observe_model(model, z, R, [k], wait=True)["outcome"] == M.APPLIED
+        moved = np.abs(e.get_x()[3 + 2 * k:5 + 2 * k] - before).max()
+        assert moved < REL * znorm, (model, moved)
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# 4. inside the engine: a schedule with every kind of call, deferred and asynchronous against batch 1
+# ------------------------------------------------------------------------------------------------------------------
+def _schedule(seed, N, steps, cap):
+    """Ops of a run from N landmarks: correct, observe_model, append_model (1-3 entries), remove, merge -- four appends early, so that the
+    map crosses the tile-row edge at 24 landmarks (T = 16) soon and the other ops work on both sides of it."""
+    rng = np.random.default_rng(seed)
+    n, ops, sig = N, [], 900.0
+    for t in range(steps):
+        r = rng.random()
+        if (2 <= t < 6 or r < 0.2) and n + 3 <= cap:
+            m = int(rng.integers(1, 4))
+            ops.append(("append_model", A.scan(rng, m, sig))); n += m; sig += m
+        elif r < 0.6:
+            ops.append(("correct", int(rng.integers(0, n)), rng.uniform(0.01, 0.05), rng.uniform(0.1, 0.4)))
+        elif r < 0.8:
+            ops.append(("observe", int(rng.choice([M.RANGE_BEARING, M.RANGE, M.RELATIVE_XY])), int(rng.integers(0, n)), 0.1 * rng.standard_normal(2)))
+        elif r < 0.9 and n > 12:
+            ops.append(("remove", int(rng.integers(0, n)))); n -= 1
+        elif n > 12:
+            i, j = (int(v) for v in rng.choice(n, 2, replace=False))
+            ops.append(("merge", i, j)); n -= 1
+        else:
+            ops.append(("correct", 0, 0.02, 0.2))
+    return ops
+
+
+def _play(e, ops):
+    beside = 0
+    for op in ops:
+        e.predict(U2)
+        if op[0] == "append_model":
+            beside += e.pending() > 0
+            e.append_model(op[1])
+        elif op[0] == "correct":
+            x = e.get_x()
+            e.correct(observe(x, op[1], op[2], op[3]), R2, op[1])
+        elif op[0] == "observe":
+            x = e.get_x()
+            rows = M.ROWS[op[1]]
+            o = M.obs(op[1], np.zeros(rows), RPOS if rows == 2 else 0.05, [op[2]])
+            o["z"][:rows] = M.jacobian(x, o)[0][:rows] + op[3][:rows]
+            e.observe_model(o["model"], o["z"][:rows], o["R"], o["landmarks"])
+        elif op[0] == "remove":
+            e.remove_landmarks([op[1]])
+        else:
+            e.merge_landmarks(op[1], op[2], np.diag([4.0, 4.0]))
+    return beside
+
+
+@pytest.fixture(scope="module")
+def schedule_reference():
+    ops = _schedule(23, 18, 70, 44)
+    one = T.loaded(18, 5, capacity=48, tile=16, batch=1)
+    _play(one, ops)
+    return ops, T.getters(one)
+
+
+@pytest.mark.parametrize("batch,asy", [(8, False), (3, True), (8, True)])
+def test_a_schedule_with_model_appends_is_bit_for_bit_that_of_batch_one(schedule_reference, batch, asy):
+    ops, want = schedule_reference
+    kinds = [op[0] for op in ops]
+    assert kinds.count("append_model") >= 8 and kinds.count("remove") >= 2 and kinds.count("merge") >= 2 and kinds.count("observe") >= 8
+    assert all(np.all(np.isfinite(g)) for g in want)
+    e = T.loaded(18, 5, capacity=48, tile=16, batch=batch, async_flush=asy)
+    beside = _play(e, ops)
+    assert beside >= 4                                        # appends with pairs pending (asynchronous: beside the pass that holds them)
+    assert e.N > 24                                           # the map crossed the tile-row edge at 24 landmarks
+    for got, ref in zip(T.getters(e), want):
+        np.testing.assert_array_equal(got, ref)
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# 5. cfg.device_assoc = 4: the next decided launch learns the new count
+# ------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("batch", [1, 8])
+def test_between_the_scans_of_the_device_decided_loop(batch):
+    from decided_plans import make_plan
+    from test_decided_assoc_gpu import PARAMS
+    from ekf_slam_amd.engine import Engine
+    plan = make_plan(7, 300, 24, 8)
+    runs, firsts = {}, {}
+    for mode in (1, 4):
+        e = Engine(mode="uc", capacity=300, device_assoc=mode, tile=16, batch=batch, **PARAMS)
+        rng = np.random.default_rng(9)
+        for t, (u, rows, idx, loc) in enumerate(plan):
+            e.predict(u)
+            e.measure(rows, u, idx, loc)
+            if t in (8, 9, 16):
+                # straight behind the scan: with device_assoc = 4 its rows are queued and nothing is settled when the call arrives
+                firsts.setdefault(mode, []).append(e.append_model(A.scan(rng, 3 if t != 9 else 1, 5000.0 + 10 * t)))
+        runs[mode] = e
+    assert runs[4].N > 40 and firsts[4] == firsts[1] and len(firsts[4]) == 3
+    T.assert_same(runs[4], runs[1])
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# 6. shards: the same call on every shard, no exchange
+# ------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("world", [2, 3])
+@pytest.mark.parametrize("batch", [1, 4])
+def test_shards_append_without_an_exchange(world, batch):
+    from ekf_slam_amd.engine import Engine
+    from ekf_slam_amd.sharding import ShardGroup
+    N = START[9]
+    x, s, d, U = lowrank_data(N, 5)
+    kw = dict(capacity=N + 16, tile=16, batch=batch)
+    g, one = ShardGroup(world, **kw), Engine(**kw)
+    for q in (g, one):
+        q.load_lowrank_state(x, s, d, U)
+        for k in (5, 60):
+            q.predict(U2); q.correct(observe(x, k), R2, k)
+    rng = np.random.default_rng(4)
+    entries = A.scan(rng, 9)
+    assert g.append_model(entries) == one.append_model(entries) == N
+    xe = one.get_x()
+    for q in (g, one):
+        for k in (7, N + 8, N, 100, N + 3):                   # old and new landmarks, across the tile-row edges the scan crossed
+            q.predict(U2); q.correct(observe(xe, k), R2, k)
+        assert q.append_model(entries[:2]) == N + 9
+    xe = one.get_x()
+    for q in (g, one):
+        q.predict(U2); q.correct(observe(xe, N + 9), R2, N + 9)
+    assert g.N == one.N == N + 11
+    Pg = g.get_P()
+    assert not np.isnan(Pg).any()
+    np.testing.assert_array_equal(Pg, one.get_P())
+    np.testing.assert_array_equal(g.get_x(), one.get_x())
+    for sh in g.shards:
+        np.testing.assert_array_equal(sh.get_s(), one.get_s())
+        np.testing.assert_array_equal(sh.get_P_diag_blocks(), one.get_P_diag_blocks())
+    g.close(); one.close()
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# 7. refusals, each before anything changes
+# ------------------------------------------------------------------------------------------------------------------
+def test_refusals_leave_the_state_alone():
+    from ekf_slam_amd import _lib as L
+    N = 60
+    x = lowrank_data(N, 5)[0]
+    kw = dict(capacity=N + 4, tile=16, batch=8)
+    e, twin = T.loaded(N, 5, **kw), T.loaded(N, 5, **kw)
+    history([e, twin], x, (4, 33))
+    history([e, twin], x, (9,))                               # pairs pending and a recorded predict behind them
+    e.predict(U2); twin.predict(U2)
+    x_before, s_before, pend = e.get_x(), e.get_s(), e.pending()      # (reading x carries out e's predict; the twin's stays recorded)
+    nan, inf = float("nan"), float("inf")
+
+    def make(m, **kw):
+        arr, _ = e._model_inits(A.scan(np.random.default_rng(2), max(m, 1)))
+        for key, (b, idx, v) in kw.items():
+            if idx is None:
+                setattr(arr[b], key, v)
+            else:
+                getattr(arr[b], key)[idx] = v
+        return arr
+
+    def unchanged(name):
+        assert b"append_model" in e.lib.ekf_last_error(e.h), name
+        assert e.pending() == pend and e.N == N, name
+        np.testing.assert_array_equal(e.get_x(), x_before, err_msg=name)
+        np.testing.assert_array_equal(e.get_s(), s_before, err_msg=name)
+
+    bad = L.EKF_ERR_INVALID_ARG
+    first = ctypes.c_int64(-7)
+    call = lambda arr, m: e.lib.ekf_append_model(e.h, arr, m, ctypes.byref(first))
+    assert e.lib.ekf_append_model(None, make(1), 1, None) == bad
+    assert call(None, 1) == bad; unchanged("null entries")
+    for m in (0, -1, 33):
+        assert call(make(33), m) == bad; unchanged("m = %d" % m)
+    cases = [("model 0", dict(model=(0, None, 0))), ("a range alone", dict(model=(0, None, M.RANGE))), ("a bearing alone", dict(model=(0, None, M.BEARING))),
+             ("a landmark range", dict(model=(0, None, M.LANDMARK_RANGE))), ("model 6", dict(model=(0, None, 6))),
+             ("NaN z", dict(z=(0, 1, nan))), ("inf z", dict(z=(1, 0, inf))), ("a range of zero", dict(z=(0, 0, 0.0))), ("a negative range", dict(z=(0, 0, -2.0))),
+             ("inf R", dict(R=(0, 0, inf))), ("asymmetric R", dict(R=(0, 1, 0.2))), ("negative diagonal", dict(R=(1, 3, -1.0))),
+             ("negative determinant", dict(R=(1, 1, 9.0)))]
+    for name, kw_ in cases:
+        (key, (b0, idx, v)), = kw_.items()
+        for b in ((0, 2) if b0 == 0 else (1,)):               # (entry 2 is of entry 0's model) the bad entry first, in the middle, last
+            arr = make(3, **{key: (b, idx, v)})
+            if name == "negative determinant":
+                arr[b].R[2] = 9.0
+            assert call(arr, 3) == bad, name
+            unchanged("%s in entry %d" % (name, b))
+    # (a relative position may lie behind the robot, and on it: no range is involved)
+    # capacity: all or nothing, also where the first entries would fit
+    assert call(make(5), 5) == L.EKF_ERR_CAPACITY; unchanged("capacity in the middle of a batch")
+    assert first.value == -7
+    # nothing of all that changed anything: the recorded predict and the pending pairs are still there, and the handle goes on like its twin
+    for q in (e, twin):
+        assert q.append_model(A.scan(np.random.default_rng(2), 4)) == N
+    assert call(make(1), 1) == L.EKF_ERR_CAPACITY; unchanged_N = e.N
+    assert unchanged_N == N + 4 and b"append_model" in e.lib.ekf_last_error(e.h)
+    T.assert_same(e, twin)
+
+
+def test_a_refusal_reads_the_same_digest_before_and_after():
+    from ekf_slam_amd import _lib as L
+    N = 60
+    x = lowrank_data(N, 5)[0]
+    e = T.loaded(N, 5, capacity=N + 2, tile=16, batch=4)
+    history([e], x, (4, 33))
+    before = T.getters(e)
+    arr, _ = e._model_inits(A.scan(np.random.default_rng(2), 3))
+    def same_as_before():
+        assert e.N == N and b"append_model" in e.lib.ekf_last_error(e.h)
+        for got, ref in zip(T.getters(e), before):            # x, s, P, the diagonal blocks, ekf_P_digest
+            np.testing.assert_array_equal(got, ref)
+
+    assert e.lib.ekf_append_model(e.h, arr, 3, None) == L.EKF_ERR_CAPACITY          # two fit, the third does not
+    same_as_before()
+    arr[1].z[0] = float("nan")
+    assert e.lib.ekf_append_model(e.h, arr, 2, None) == L.EKF_ERR_INVALID_ARG
+    same_as_before()
+    arr[1].z[0] = 1.0; arr[0].model = M.BEARING
+    assert e.lib.ekf_append_model(e.h, arr, 2, None) == L.EKF_ERR_INVALID_ARG
+    same_as_before()
+    assert e.lib.ekf_append_model(e.h, arr, 33, None) == L.EKF_ERR_INVALID_ARG
+    same_as_before()
+
+
+def test_refused_between_begin_and_finish_of_a_sharded_correction():
+    from ekf_slam_amd import _lib as L
+    N = 60
+    x = lowrank_data(N, 5)[0]
+    kw = dict(capacity=N + 4, tile=16)
+    e, twin = T.loaded(N, 5, force_sharded=1, **kw), T.loaded(N, 5, **kw)
+    harr = (ctypes.c_void_p * 1)(e.h)
+    entries = A.scan(np.random.default_rng(2), 2)
+    z = observe(x, 7)
+    e.predict(U2); twin.predict(U2)
+    e.correct_begin(z, R2, 7)
+    st, msg = T.status_of(lambda: e.append_model(entries))
+    assert st == L.EKF_ERR_STATE and "append_model" in msg and "begin and finish" in msg
+    bad = [(M.RANGE, [1.0, 2.0], RPOS, 1.0)]
+    assert T.status_of(lambda: e.append_model(bad))[0] == L.EKF_ERR_INVALID_ARG          # the arguments come first
+    assert e.lib.ekf_exchange_local(harr, 1) == 0
+    e.correct_finish()
+    twin.correct(z, R2, 7)
+    assert e.append_model(entries) == twin.append_model(entries) == N                    # a lone shard with the sharded code path simply works
+    T.assert_same(e, twin)
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# 8. the slam.py wrappers and a replayed log
+# ------------------------------------------------------------------------------------------------------------------
+def test_a_run_with_model_appends_replays_from_its_log(tmp_path):
+    from ekf_slam_amd.slam import SLAM
+    from ekf_slam_amd.trajectory import FORMAT_APPEND, TrajectoryLog
+    from ekf_slam_amd.world import make_run
+    _, run = make_run(40, 11, 24, policy="nearest", m=6)
+    run = list(run)
+    kw = dict(capacity=64, tile=16, batch=4)
+    full = SLAM('EKF_SLAM', feed=run, landmark_method='SYNTHETIC', **kw)
+    plain = SLAM('EKF_SLAM', feed=run, landmark_method='SYNTHETIC', **kw)
+    full.slam.log = TrajectoryLog()
+    rng = np.random.default_rng(6)
+    for k in range(len(run)):
+        full.runSlam(); plain.runSlam()
+        if k == 7:
+            assert full.slam.add_landmark_range_bearing([4.0, 30.0], RPOS) == 41
+            assert full.slam.s[-1] == 41.0                    # the default signature: the landmark's own number
+        if k == 12:
+            z = np.array([3.0, -2.0])
+            i = full.slam.add_landmark_relative_xy(z, RPOS, signature=777.0)
+            assert i == 42 and full.slam.model_innovation(M.RELATIVE_XY, z, RPOS, [i])["d2"] < 1e-12
+            full.slam.observe_relative_xy(i, z + [0.05, -0.02], RPOS)
+        if k == 18:
+            got = full.slam.add_landmarks_model([(m, z, R) for m, z, R, _ in A.scan(rng, 3)])
+            assert got == [43, 44, 45] and full.slam.s[-3:].tolist() == [43.0, 44.0, 45.0]
+    path = tmp_path / "grown_run.npz"
+    full.slam.log.save(path)
+    log = TrajectoryLog.load(path)
+    assert str(np.load(path)["format"]) == FORMAT_APPEND and [(e[0], e[1]) for e in log.edits] == \
+        [(8, "append_model"), (13, "append_model"), (13, "observe_model"), (19, "append_model")]
+    fresh = T.engine(**kw)
+    log.replay(fresh)
+    assert fresh.N == 45 and plain.slam._e.N == 40
+    np.testing.assert_array_equal(fresh.get_x(), full.slam.x)
+    np.testing.assert_array_equal(fresh.get_s(), full.slam.s)
+    np.testing.assert_array_equal(fresh.get_P(), full.slam.P)
+    assert np.all(np.isfinite(fresh.get_P()))
