@@ -66,6 +66,14 @@ class EkfModelInit(ctypes.Structure):
     _fields_ = [("model", _i32), ("reserved", _i32), ("z", _d * 2), ("R", _d * 4), ("signature", _d)]
 
 
+EKF_ASSOCIATE_MODEL_MAX = 32
+
+
+class EkfModelMatch(ctypes.Structure):
+    """struct ekf_model_match (include/ekfslam.h)."""
+    _fields_ = [("best", _i64), ("second", _i64), ("d2_best", _d), ("d2_second", _d), ("within_gate", _i64), ("irregular", _i64)]
+
+
 # name -> (restype, argtypes); every symbol of include/ekfslam.h
 SIGNATURES = {
     "ekf_abi_version": (_i32, []),
@@ -123,6 +131,7 @@ SIGNATURES = {
     "ekf_model_evaluate": (_i32, [_i32, _dp, _dp, _dp, _dp, _dp]),
     "ekf_append_model": (_i32, [_vp, ctypes.POINTER(EkfModelInit), _i64, ctypes.POINTER(_i64)]),
     "ekf_model_invert": (_i32, [_i32, _dp, _dp, _dp, _dp, _dp]),
+    "ekf_associate_model": (_i32, [_vp, ctypes.POINTER(EkfModelObs), _i64, ctypes.POINTER(EkfModelMatch), _dp]),
     "ekf_diag_poke_device_signature": (_i32, [_vp, _i64, _d]),
     "ekf_get_P": (_i32, [_vp, _dp]),
     "ekf_set_P": (_i32, [_vp, _dp, _i64]),

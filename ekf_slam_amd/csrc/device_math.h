@@ -355,4 +355,68 @@ EKF_MHD bool model_invert(int model, const double xr[3], const double z[2], doub
     return false;
 }
 
+// ekf_associate_model (associate_model.h runs it on the device, one lane per landmark): d2 of one observation through a model whose target
+// is ONE landmark, from the live F64 copies alone -- prr (row-major), the strip at the landmark's columns (strip6[2 t + r] = P(t, a + r)),
+// its own block diag3 ((0,0) (1,0) (1,1)), the pose xr and the landmark l.  The kLinearSmall operands are laid out exactly as
+// linear_small_entry fills them for a = {2 i, -1} (landmark 1 absent: zeros) and go through model_eval, model_wrap, model_small and
+// constrain_d2 -- no shortened form, the zero terms included: the sums are k_model_probe's, so d2 is ekf_model_innovation's bit for bit.
+// Returns whether the pair has a d2 (the target off the robot, the state finite, S regular); d2 is NaN where it has none.
+EKF_MHD bool assoc_model_d2(int model, const double z[2], const double R[4], const double prr[9], const double strip6[6],
+                            const double diag3[3], const double xr[3], const double l[2], double &d2) {
+    double sm[kLinearSmall];
+    for (int e = 0; e < kLinearSmall; ++e) sm[e] = 0.0;
+    for (int e = 0; e < 9; ++e) sm[e] = prr[e];
+    for (int e = 0; e < 6; ++e) sm[9 + e] = strip6[e];
+    for (int e = 0; e < 3; ++e) { sm[21 + e] = diag3[e]; sm[31 + e] = xr[e]; }
+    sm[34] = l[0]; sm[35] = l[1];
+    const double anchor[2] = { 0.0, 0.0 };
+    double H[14], hx[2], Gs[14], S[4], nu[2];
+    int wrap[2];
+    const bool posed = model_eval(model, sm + 31, anchor, true, hx, H);
+    model_wrap(model, wrap);
+    model_small(sm, H, hx, z, R, wrap, Gs, S, nu);
+    const bool regular = constrain_d2(S, nu[0], nu[1], d2);
+    if (!posed) d2 = NAN;
+    return posed && regular && !isnan(d2);
+}
+
+// The two best landmarks of a scan's observation and the two counts beside them (ekf_model_match's fields, in its order): the record a lane,
+// a wavefront, a workgroup and the whole grid hold alike.  Candidates are ordered by (d2, index): smaller d2 first, the lower index on equal
+// d2; index -1 is "none" (d2 = +inf) and comes after every candidate.
+struct Match2 {
+    long long best, second;
+    double d2_best, d2_second;
+    long long within, irregular;
+};
+EKF_MHD void match2_init(Match2 &m) {
+    m.best = m.second = -1;
+    m.d2_best = m.d2_second = INFINITY;
+    m.within = m.irregular = 0;
+}
+EKF_MHD bool match2_before(double d2a, long long ia, double d2b, long long ib) {
+    return ia >= 0 && (ib < 0 || d2a < d2b || (d2a == d2b && ia < ib));
+}
+// one candidate into the top two
+EKF_MHD void match2_insert(Match2 &m, double d2, long long i) {
+    const bool first = match2_before(d2, i, m.d2_best, m.best), second = match2_before(d2, i, m.d2_second, m.second);
+    if (first) { m.d2_second = m.d2_best; m.second = m.best; m.d2_best = d2; m.best = i; }
+    else if (second) { m.d2_second = d2; m.second = i; }
+}
+// landmark i with its d2 (regular: it has one): a candidate, counted where d2 <= gate; otherwise counted as irregular and never a candidate
+EKF_MHD void match2_offer(Match2 &m, double d2, long long i, bool regular, double gate) {
+    if (!regular) { m.irregular += 1; return; }
+    if (d2 <= gate) m.within += 1;
+    match2_insert(m, d2, i);
+}
+// the top two of the union and the counts added: associative and commutative (the order is total and no index occurs twice), so every
+// reduction shape gives the same record
+EKF_MHD Match2 match2_merge(const Match2 &a, const Match2 &b) {
+    Match2 r = a;
+    match2_insert(r, b.d2_best, b.best);
+    match2_insert(r, b.d2_second, b.second);
+    r.within += b.within;
+    r.irregular += b.irregular;
+    return r;
+}
+
 }  // namespace ekfm

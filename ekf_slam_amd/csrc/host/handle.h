@@ -208,6 +208,13 @@ struct ekf_handle {
     double *d_linrec = nullptr, *h_linrec = nullptr;
     int64_t *d_lincnt = nullptr;
     hipEvent_t ev_linrec = nullptr;
+    // ---- a scan matched to the map under the models' conventions (ekf_associate_model) ----
+    // one record per workgroup (am_nblk_cap per observation) and the m results on the device, the results' pinned copy and the event behind
+    // a call's readback; the results followed by the m x N block of d2_all on the device and in pinned memory (allocated when first asked for)
+    ekfm::Match2 *d_amparts = nullptr, *d_amout = nullptr, *h_amout = nullptr;
+    int64_t am_nblk_cap = 0;
+    char *d_amall = nullptr, *h_amall = nullptr;
+    hipEvent_t ev_amodel = nullptr;
     // ---- timers, what ekf_destroy releases, the error text ----
     KernelTimer timers[EKF_KERNEL_COUNT];
     std::vector<void *> allocs;       // device memory (dalloc), pinned memory (halloc) and events (new_event): what ekf_destroy releases

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "device_math.h"
 #include "layout.h"
 
 // Tuning switches.  The PRODUCT library compiles every one of them to its default constant: no environment variable changes
@@ -235,6 +236,27 @@ hipError_t launch_associate_devn(const DevState &st, const AssocArgs &a, AssocHo
 // then -- want_costs -- N position costs) and writes the decision like launch_associate does
 hipError_t launch_assoc_merge(const DevState &st, const double *recv, int world, int64_t count, int64_t N, bool want_costs,
                               double *pos_cost, AssocDecision *decision, AssocDecision *host_decision, int seq, hipStream_t s);
+
+// k_assoc_model / k_assoc_model_reduce (associate_model.h): a scan of m <= kAssocModelMax observations under ekf_observe_model's conventions
+// scored against all N landmarks, read-only, from the live F64 copies alone (x, Prr, the strip, the diagonal blocks of buffer cur / st.dcur):
+// no tile is touched, so the storage type does not matter.  The entries travel in the argument block.
+constexpr int kAssocModelMax = 32;
+struct AssocModelEntry {
+    double z[2];
+    double R[4];              // row-major; a one-row model: [r, 0, 0, 1] and z[1] = 0 (model_parse)
+    double gate;              // feeds the count `within` alone
+    int32_t model, pad;       // EKF_MODEL_* 1-4
+};
+struct AssocModelArgs {
+    int64_t N;                // landmarks, >= 1
+    int32_t m;                // entries in use
+    int32_t cur;
+    AssocModelEntry e[kAssocModelMax];
+};
+// partials (device): m * ceil(N / kAssocBlock) records, one per workgroup of the first launch; out (device): m records, the second launch's;
+// d2_all (device): nullptr, or m x N row-major, NaN where a pair has no d2.  Two launches ordered by the stream.
+hipError_t launch_assoc_model(const DevState &st, const AssocModelArgs &a, ekfm::Match2 *partials, ekfm::Match2 *out, double *d2_all,
+                              hipStream_t s);
 
 // ---- the passes over P (launch/passes.h; launch/pass_select.h decides which kernel instance runs) ----
 // nx (sharded handles): ALSO extract the row-panel of landmark-block rows j, j + 1 into send (layout of launch_rowpanel) from the updated

@@ -1,5 +1,5 @@
 // Fragment of kernels.hip, the launchers of the steps: predict, append, the gather of a correction in its five forms, a shard's
-// row-panels, the association (declared in kernels.h, in this order).
+// row-panels, the association and the model-convention association of a scan (declared in kernels.h, in this order).
 #pragma once
 
 hipError_t launch_predict(const DevState &st, const PredictArgs &a, int, hipStream_t s) {
@@ -177,5 +177,17 @@ hipError_t launch_assoc_merge(const DevState &st, const double *recv, int world,
     if (grid > 1024) grid = 1024;
     hipLaunchKernelGGL(k_assoc_merge, dim3((unsigned)grid), dim3(kBlock), 0, s, st.tm, recv, world, count, N, want_costs ? 1 : 0,
                        pos_cost, decision, host_decision, seq);
+    return hipGetLastError();
+}
+
+hipError_t launch_assoc_model(const DevState &st, const AssocModelArgs &a, ekfm::Match2 *partials, ekfm::Match2 *out, double *d2_all,
+                              hipStream_t s) {
+    if (a.N < 1 || 2 * a.N > st.ldm || a.m < 1 || a.m > kAssocModelMax || !partials || !out) return hipErrorInvalidValue;
+    for (int k = 0; k < a.m; ++k) if (a.e[k].model < 1 || a.e[k].model > 4) return hipErrorInvalidValue;
+    const int64_t nblk = cdiv(a.N, kAssocBlock);
+    hipLaunchKernelGGL(k_assoc_model, dim3((unsigned)nblk, (unsigned)a.m), dim3(kAssocBlock), 0, s, st, a, partials, d2_all);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_assoc_model_reduce, dim3((unsigned)a.m), dim3(64), 0, s, partials, (int)nblk, out);
     return hipGetLastError();
 }

@@ -591,6 +591,31 @@ class Engine:
             raise L.EkfError(rc, "ekf_model_invert")
         return t, Gx.reshape(2, 3), Gz.reshape(2, 2)
 
+    # ---- which landmark a sighting belongs to, under the models' conventions (include/ekfslam.h: ekf_associate_model) ----
+    def associate_model(self, entries, want_d2=False):
+        """One scan matched to the whole map: entries = [{'model', 'z', 'R', 'gate'}, ...] (models 1-4, at most
+        EKF_ASSOCIATE_MODEL_MAX; a gate left out is +inf).  Returns {'best', 'second', 'd2_best', 'd2_second', 'within_gate',
+        'irregular'}, one array entry per observation, landmarks 0-based and -1 = none; d2 of every (observation, landmark) is what
+        model_innovation reports for that pair, bit for bit.  want_d2 adds 'd2_all', the m x N matrix (NaN where a pair has no d2).
+        Changes, flushes and retires nothing (ekf_associate_model)."""
+        entries = list(entries)
+        m = len(entries)
+        arr = (L.EkfModelObs * max(m, 1))()
+        for k, ent in enumerate(entries):
+            arr[k] = self._model_obs(ent["model"], ent["z"], ent["R"], (), (0.0, 0.0), ent.get("gate", float("inf")))      # lm = {-1, -1}
+        out = (L.EkfModelMatch * max(m, 1))()
+        N = self.N
+        d2 = np.full((m, N), np.nan) if want_d2 else None
+        self._check(self.lib.ekf_associate_model(self.h, arr, m, out, _p(d2) if want_d2 and d2.size else None))
+        res = {"best": np.array([out[k].best for k in range(m)], dtype=np.int64),
+               "second": np.array([out[k].second for k in range(m)], dtype=np.int64),
+               "d2_best": np.array([out[k].d2_best for k in range(m)]), "d2_second": np.array([out[k].d2_second for k in range(m)]),
+               "within_gate": np.array([out[k].within_gate for k in range(m)], dtype=np.int64),
+               "irregular": np.array([out[k].irregular for k in range(m)], dtype=np.int64)}
+        if want_d2:
+            res["d2_all"] = d2
+        return res
+
     def load_lowrank_state(self, x, s, d, U):
         x, s, d = _vec(x), _vec(s), _vec(d)
         U = np.asfortranarray(np.asarray(U, dtype=np.float64))

@@ -378,6 +378,72 @@ class _EkfBase:
         number."""
         return self.add_landmarks_model([(L.EKF_MODEL_RELATIVE_XY, z, R, signature)])[0]
 
+    def associate_model(self, entries, want_d2=False):
+        """WHICH landmark each sighting of a scan belongs to, under observe_model's conventions: entries = [{'model', 'z', 'R', 'gate'},
+        ...] (models 1-4; a gate left out is +inf).  Returns {'best', 'second', 'd2_best', 'd2_second', 'within_gate', 'irregular'} with
+        one entry per observation: the 1-based landmarks with the smallest and second-smallest d2 (0 = none, d2 = +inf), how many
+        landmarks lie at or below the gate, how many have no d2.  Every d2 is what model_innovation reports for that pair, bit for bit;
+        want_d2 adds 'd2_all' (m x N).  One small launch for the whole scan against the whole map; changes and flushes nothing, so it is
+        not logged (ekf_associate_model).  The reference has no such method: its association keeps its own conventions."""
+        res = dict(self._e.associate_model(entries, want_d2))
+        res["best"] = res["best"] + 1
+        res["second"] = res["second"] + 1
+        return res
+
+    def measure_model(self, entries, gate_match, gate_new, wait=False):
+        """One scan under observe_model's conventions, observe-or-append: entries as for add_landmarks_model ([(model, z, R) or (model, z,
+        R, signature), ...], models 1 and 4).  ONE associate_model call with gate = gate_match, then, on the host and deterministic:
+          matched    exactly one landmark lies inside gate_match (within_gate == 1): that landmark, the entry's best;
+          new        d2_best > gate_new, or the map is empty (gate_new >= gate_match is required);
+          discarded  everything else: ambiguous (several inside the gate) or between the two gates.
+        Where several entries are matched to one landmark the smallest d2_best keeps it (the lower entry on a tie) and the others are
+        discarded.  The matched entries go to observe_model(..., [landmark], gate=gate_match) in scan order -- the step checks its gate
+        again at the live state -- then ALL new ones to one add_landmarks_model call.  Returns [(kind, landmark)] per entry, landmark
+        1-based and 0 for a discarded one.  Everything that changes the state goes through those two logged methods, so a replayed log
+        reproduces the run.  Unsharded handles only, as observe_model."""
+        gate_match, gate_new = float(gate_match), float(gate_new)
+        if not gate_new >= gate_match:
+            raise ValueError("measure_model: gate_new >= gate_match is required (and neither is NaN)")
+        entries = [tuple(e) for e in entries]
+        if not 1 <= len(entries) <= L.EKF_ASSOCIATE_MODEL_MAX:
+            raise ValueError("measure_model: between 1 and %d entries" % L.EKF_ASSOCIATE_MODEL_MAX)
+        for e in entries:
+            if len(e) not in (3, 4):
+                raise ValueError("measure_model: an entry is (model, z, R) or (model, z, R, signature)")
+            if int(e[0]) not in (L.EKF_MODEL_RANGE_BEARING, L.EKF_MODEL_RELATIVE_XY):
+                raise ValueError("measure_model: model is EKF_MODEL_RANGE_BEARING (1) or EKF_MODEL_RELATIVE_XY (4): a one-row model does "
+                                 "not start a landmark")
+        res = self._e.associate_model([dict(model=int(e[0]), z=e[1], R=e[2], gate=gate_match) for e in entries])
+        kinds = []
+        for k in range(len(entries)):
+            if int(res["within_gate"][k]) == 1:
+                kinds.append("matched")
+            elif int(res["best"][k]) < 0 or float(res["d2_best"][k]) > gate_new:
+                kinds.append("new")
+            else:
+                kinds.append("discarded")
+        owner = {}                       # landmark -> the matched entry that keeps it: smallest d2_best, the lower entry on a tie
+        for k, kind in enumerate(kinds):
+            if kind == "matched":
+                lm = int(res["best"][k])
+                if lm not in owner or float(res["d2_best"][k]) < float(res["d2_best"][owner[lm]]):
+                    owner[lm] = k
+        out = [None] * len(entries)
+        fresh = []
+        for k, (kind, e) in enumerate(zip(kinds, entries)):
+            lm = int(res["best"][k])
+            if kind == "matched" and owner[lm] == k:
+                self.observe_model(int(e[0]), e[1], e[2], [lm + 1], gate=gate_match, wait=wait)
+                out[k] = ("matched", lm + 1)
+            elif kind == "new":
+                fresh.append(k)
+            else:
+                out[k] = ("discarded", 0)
+        if fresh:
+            for k, number in zip(fresh, self.add_landmarks_model([entries[k] for k in fresh])):
+                out[k] = ("new", number)
+        return out
+
     def _push_params(self):
         pass
 

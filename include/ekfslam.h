@@ -470,6 +470,38 @@ typedef struct ekf_model_init {
 } ekf_model_init;
 int32_t ekf_append_model(ekf_handle *h, const ekf_model_init *obs, int64_t m, int64_t *first_idx /* may be NULL */);
 int32_t ekf_model_invert(int32_t model, const double xr[3], const double z[2], double t[2], double Gx[6], double Gz[4]);
+/* The step between the two: "WHICH landmark does this sighting belong to?", for a whole scan, under the conventions of ekf_observe_model.
+ * ekf_associate keeps the reference's (signature-only by default, an unwrapped bearing, a range-scaled R) and cannot serve a filter
+ * driven through the model calls.  For each of the m observations, d2(k, i) is, BIT FOR BIT, the d2 that ekf_model_innovation reports for
+ * obs[k] with lm[0] = i on the same handle in the same state -- pending pairs, a recorded predict (carried out first) and every storage
+ * kind included -- for EVERY landmark i, by two small launches: a one-landmark model's innovation reads nothing but the live F64 copies
+ * (x, P(1:3,1:3), P(1:3, landmark), the landmark's own 2x2 block), which carry every pending pair and are replicated on every shard.
+ *   best, second   the landmarks with the smallest and the second-smallest d2 (0-based; smaller d2 first, the lower index on equal d2);
+ *                  -1 and d2 = +inf where there is none
+ *   within_gate    landmarks with d2 <= obs[k].gate -- the gate feeds this count alone: a landmark ekf_model_innovation would call
+ *                  EKF_LINEAR_GATED still has a d2 and is a candidate; gating is the caller's job (+inf counts every regular landmark)
+ *   irregular      landmarks with no d2 (the target on the robot, a non-finite state, S not positive definite): never a candidate,
+ *                  NaN in d2_all
+ * d2_all, where not NULL, receives the whole m x N matrix, row-major: the hook for joint-compatibility or assignment solvers.
+ * Each entry of obs: the model is EKF_MODEL_RANGE_BEARING, _RANGE, _BEARING or _RELATIVE_XY (EKF_MODEL_LANDMARK_RANGE has no robot block
+ * and no single target); lm is {-1, -1}: the target is what is being searched for; anchor is ignored; z, R and gate as for
+ * ekf_observe_model.  Mixed models in one scan are allowed.
+ * The call changes nothing: no flush, ekf_pending and every bit of the state stay as found, a pass in flight (cfg.async_flush) is neither
+ * waited for nor retired; it waits for the event behind its own readback alone.  A recorded predict is carried out first, by a launch
+ * of its own.  The two launches are counted as one under EKF_KERNEL_ASSOCIATE.  SHARDED handles are supported: every shard computes the
+ * same answer from replicated data, no exchange.  N = 0: best = second = -1, d2 = +inf, counts 0, no launch.
+ * Refused in this order: h, obs or out NULL, m < 1 or m > EKF_ASSOCIATE_MODEL_MAX; per entry EKF_MODEL_LANDMARK_RANGE, lm != {-1, -1},
+ * then what ekf_observe_model refuses of model, z, R and gate (EKF_ERR_INVALID_ARG); then, with the measure loop settled
+ * (cfg.device_assoc = 4: N exact), a sharded correction between begin and finish (EKF_ERR_STATE). */
+#define EKF_ASSOCIATE_MODEL_MAX 32
+typedef struct ekf_model_match {
+    int64_t best, second;        /* 0-based landmarks with the smallest and second-smallest d2; -1 = none          */
+    double  d2_best, d2_second;  /* +inf where none                                                               */
+    int64_t within_gate;         /* landmarks with d2 <= obs.gate                                                 */
+    int64_t irregular;           /* landmarks with no d2: target on the robot, non-finite state, S not pos. def.  */
+} ekf_model_match;
+int32_t ekf_associate_model(ekf_handle *h, const ekf_model_obs *obs, int64_t m,
+                            ekf_model_match *out /* m, required */, double *d2_all /* m x N row-major, may be NULL */);
 /* Diagnostic -- a fault injector for tests of the device-resident measure loop's verification, of no use to a host: overwrites the DEVICE copy
  * of signature idx (0-based) and leaves the host mirror alone.  The next ekf_measure whose association involves that landmark then queues its
  * launches from a prediction the device contradicts; every launch stays inside the state (a correction falls back to the predicted landmark,

@@ -231,6 +231,61 @@ classdef EKF_SLAM < handle
             if nargin < 4, signature = []; end
             idx = h.addLandmarksModel(4, z(:)', R, signature);
         end
+        function [match, d2] = associateModel(h, model, z, R, gate)
+            % WHICH landmark each sighting of a scan belongs to, under observeModel's conventions: observation k was seen as z(k, :)
+            % through model(k) (1 range and bearing, 2 range, 3 bearing, 4 the position in the robot frame) with noise covariance
+            % R(:, :, k) (one 2x2 R: shared by all).  match: one row [best second d2best d2second withinGate irregular] per
+            % observation -- the landmarks with the smallest and second-smallest d2 (0 = none, d2 = Inf), how many landmarks have
+            % d2 <= gate(k) (one gate: shared; default Inf), how many have no d2.  Every d2 is what observeModel would report for
+            % that pair.  d2 (optional): N x m, column k = observation k against every landmark (NaN where a pair has no d2).  One
+            % small launch for the whole scan; changes and flushes nothing.  Not a method of the reference.
+            model = double(model(:)); m = numel(model);
+            z = double(reshape(z, [], 2));
+            R = double(R); if size(R, 3) == 1, R = repmat(R, [1 1 m]); end
+            if nargin < 5 || isempty(gate), gate = Inf; end
+            gate = double(gate(:)); if isscalar(gate), gate = repmat(gate, m, 1); end
+            if nargout > 1
+                [match, d2] = h.gateway('associate_model', model, z, R, gate);
+            else
+                match = h.gateway('associate_model', model, z, R, gate);
+            end
+        end
+        function out = measureModel(h, model, z, R, gateMatch, gateNew, signature)
+            % One scan under observeModel's conventions, observe-or-append (models 1 and 4): ONE associateModel call with
+            % gate = gateMatch, then: an observation is MATCHED when exactly one landmark lies inside gateMatch (that landmark, its
+            % best), NEW when d2best > gateNew or the map is empty (gateNew >= gateMatch), DISCARDED otherwise (ambiguous, or
+            % between the gates).  Where several are matched to one landmark the smallest d2best keeps it (the lower row on a tie),
+            % the others are discarded.  The matched ones go to observeModel(..., landmark, [], gateMatch) in scan order, then ALL
+            % new ones to one addLandmarksModel call.  out: one row [kind landmark] per observation, kind 1 matched, 2 new,
+            % 0 discarded (landmark 0).  Not a method of the reference.
+            if ~(gateNew >= gateMatch), error('EKF_SLAM:measureModel', 'gateNew >= gateMatch is required'); end
+            model = double(model(:)); m = numel(model);
+            if any(model ~= 1 & model ~= 4), error('EKF_SLAM:measureModel', 'model is 1 or 4: a one-row model does not start a landmark'); end
+            z = double(reshape(z, [], 2));
+            R = double(R); if size(R, 3) == 1, R = repmat(R, [1 1 m]); end
+            if nargin < 7, signature = []; end
+            match = h.associateModel(model, z, R, gateMatch);
+            kind = zeros(m, 1);
+            kind(match(:, 5) == 1) = 1;
+            kind(kind == 0 & (match(:, 1) == 0 | match(:, 3) > gateNew)) = 2;
+            for k = find(kind == 1)'
+                rivals = find(kind == 1 & match(:, 1) == match(k, 1));
+                [~, w] = min(match(rivals, 3));                  % the first minimum: the lower row on a tie
+                if rivals(w) ~= k, kind(k) = -1; end
+            end
+            kind(kind == -1) = 0;
+            out = zeros(m, 2);
+            for k = find(kind == 1)'
+                h.observeModel(model(k), z(k, :), R(:, :, k), match(k, 1), [], gateMatch, false);
+                out(k, :) = [1 match(k, 1)];
+            end
+            fresh = find(kind == 2);
+            if ~isempty(fresh)
+                if isempty(signature), sig = []; else, sig = signature(fresh); end
+                out(fresh, 1) = 2;
+                out(fresh, 2) = h.addLandmarksModel(model(fresh), z(fresh, :), R(:, :, fresh), sig);
+            end
+        end
         function merges = fuseDuplicatesBatched(h, gate, R, maxMerges)
             % fuseDuplicates with the pairs of one search fused in one mergeLandmarksBatch call: search; walk the candidates in
             % (d2, k) order and take [partner(k) k] when k is not yet a keep or a drop and partner(k) is not yet a drop (a keep may

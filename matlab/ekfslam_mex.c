@@ -23,7 +23,8 @@
 
 /* The map-editing entry points (ekf_remove_landmarks; ekf_constrain_landmarks, ekf_merge_landmarks, ekf_landmark_distance;
  * ekf_nearest_landmarks; ekf_merge_landmarks_batch) the linear observation (ekf_observe_linear), the model observation
- * (ekf_observe_model) and the append through a model (ekf_append_model) are the ones this gateway can live without: bound weakly, so that the gateway still links against a libekfslam (or a stand-in) that
+ * (ekf_observe_model), the append through a model (ekf_append_model) and the association of a scan under the models' conventions
+ * (ekf_associate_model) are the ones this gateway can live without: bound weakly, so that the gateway still links against a libekfslam (or a stand-in) that
  * predates them; their commands then raise a MATLAB error instead. */
 #if defined(__GNUC__)
 #pragma weak ekf_remove_landmarks
@@ -35,6 +36,7 @@
 #pragma weak ekf_observe_linear
 #pragma weak ekf_observe_model
 #pragma weak ekf_append_model
+#pragma weak ekf_associate_model
 #define HAVE_REMOVE_LANDMARKS (ekf_remove_landmarks != 0)
 #define HAVE_CONSTRAIN_LANDMARKS (ekf_constrain_landmarks != 0)
 #define HAVE_MERGE_LANDMARKS (ekf_merge_landmarks != 0)
@@ -44,6 +46,7 @@
 #define HAVE_OBSERVE_LINEAR (ekf_observe_linear != 0)
 #define HAVE_OBSERVE_MODEL (ekf_observe_model != 0)
 #define HAVE_APPEND_MODEL (ekf_append_model != 0)
+#define HAVE_ASSOCIATE_MODEL (ekf_associate_model != 0)
 #else
 #define HAVE_REMOVE_LANDMARKS 1
 #define HAVE_CONSTRAIN_LANDMARKS 1
@@ -54,6 +57,7 @@
 #define HAVE_OBSERVE_LINEAR 1
 #define HAVE_OBSERVE_MODEL 1
 #define HAVE_APPEND_MODEL 1
+#define HAVE_ASSOCIATE_MODEL 1
 #endif
 
 static void need(int nrhs, int want, const char *cmd) {
@@ -328,6 +332,43 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
         check(h, ekf_append_model(h, o, (int64_t)m, &first));
         plhs[0] = mxCreateDoubleMatrix(m, 1, mxREAL);
         for (mwSize b = 0; b < m; ++b) mxGetPr(plhs[0])[b] = (double)(first + (int64_t)b + 1);
+        return;
+    }
+    if (!strcmp(cmd, "associate_model")) {        /* [match, d2] = (h, model m x 1 (1..4), z m x 2, R 2 x 2 x m, gate m x 1): which landmark each sighting of a
+                                                     scan belongs to; match m x 6 = [best second d2_best d2_second within_gate irregular], landmarks
+                                                     1-based and 0 = none; d2 (second output, optional): N x m, column k = observation k against every landmark */
+        need(nrhs, 6, cmd);
+        if (!HAVE_ASSOCIATE_MODEL) mexErrMsgIdAndTxt("ekfslam:usage", "associate_model: this libekfslam has no ekf_associate_model");
+        const mwSize m = prhs[2] ? mxGetNumberOfElements(prhs[2]) : 0;
+        if (m < 1 || m > EKF_ASSOCIATE_MODEL_MAX) mexErrMsgIdAndTxt("ekfslam:usage", "associate_model: between 1 and %d observations in one call", EKF_ASSOCIATE_MODEL_MAX);
+        if (!mxGetPr(prhs[2]) || !prhs[3] || mxGetM(prhs[3]) != m || mxGetNumberOfElements(prhs[3]) != 2 * m || !mxGetPr(prhs[3]))
+            mexErrMsgIdAndTxt("ekfslam:usage", "associate_model: z needs m x 2 elements, one row per entry of model");
+        if (!prhs[4] || mxGetNumberOfElements(prhs[4]) != 4 * m || !mxGetPr(prhs[4]))
+            mexErrMsgIdAndTxt("ekfslam:usage", "associate_model: R needs 2 x 2 x m elements");
+        if (!prhs[5] || mxGetNumberOfElements(prhs[5]) != m || !mxGetPr(prhs[5]))
+            mexErrMsgIdAndTxt("ekfslam:usage", "associate_model: gate needs m elements");
+        ekf_model_obs o[EKF_ASSOCIATE_MODEL_MAX];
+        ekf_model_match match[EKF_ASSOCIATE_MODEL_MAX];
+        for (mwSize k = 0; k < m; ++k) {
+            o[k].model = (int32_t)mxGetPr(prhs[2])[k]; o[k].reserved = 0;
+            o[k].z[0] = mxGetPr(prhs[3])[k]; o[k].z[1] = mxGetPr(prhs[3])[m + k];       /* column-major m x 2 */
+            for (int q = 0; q < 4; ++q) o[k].R[q] = mxGetPr(prhs[4])[4 * k + q];
+            o[k].lm[0] = o[k].lm[1] = -1;
+            o[k].anchor[0] = o[k].anchor[1] = 0.0;
+            o[k].gate = mxGetPr(prhs[5])[k];
+        }
+        mxArray *all = NULL;
+        if (nlhs > 1) all = mxCreateDoubleMatrix((mwSize)((nstate(h) - 3) / 2), m, mxREAL);     /* N x m column-major is m x N row-major */
+        const bool want = all && mxGetNumberOfElements(all) > 0;
+        check(h, ekf_associate_model(h, o, (int64_t)m, match, want ? mxGetPr(all) : NULL));
+        plhs[0] = mxCreateDoubleMatrix(m, 6, mxREAL);
+        double *out = mxGetPr(plhs[0]);
+        for (mwSize k = 0; k < m; ++k) {
+            out[k] = (double)(match[k].best + 1); out[m + k] = (double)(match[k].second + 1);
+            out[2 * m + k] = match[k].d2_best; out[3 * m + k] = match[k].d2_second;
+            out[4 * m + k] = (double)match[k].within_gate; out[5 * m + k] = (double)match[k].irregular;
+        }
+        if (all) plhs[1] = all;
         return;
     }
     if (!strcmp(cmd, "merge_landmarks_batch")) {  /* d2 = (h, pairs k x 2 [keep drop], R 2x2): k x 1; landmark numbers 1-based, as they are before the call */

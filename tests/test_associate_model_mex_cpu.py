@@ -1,0 +1,176 @@
+"""CPU: the MEX gateway's `associate_model` command under the MEX mock with a recording stand-in for ekf_associate_model, the gateway
+linked against a stand-in that lacks the symbol, and the MATLAB methods that forward to the command."""
+import os
+import re
+import subprocess
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+MOCK = os.path.join(ROOT, "tests", "support", "mex_mock")
+INCLUDES = ["-I", os.path.join(ROOT, "include"), "-I", os.path.join(ROOT, "tests", "support", "mex_api_subset"), "-I", MOCK]
+GCC = ["gcc", "-std=c99", "-Wall", "-Wextra", "-Werror", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"]
+
+_STUB = r'''
+#include <math.h>
+#include <stdio.h>
+#include "ekfslam.h"
+void stub_fail_next(ekf_handle *h);
+static int fail_armed;
+void arm_failure(void) { fail_armed = 1; }
+int32_t ekf_associate_model(ekf_handle *h, const ekf_model_obs *o, int64_t m, ekf_model_match *out, double *d2_all) {
+    int64_t N = 0;
+    ekf_num_landmarks(h, &N);
+    printf("ABI ekf_associate_model m=%lld d2_all=%d\n", (long long)m, d2_all != 0);
+    for (int64_t k = 0; k < m; ++k)
+        printf("ABI   obs model=%d reserved=%d z=%g,%g R=%g,%g,%g,%g lm=%lld,%lld anchor=%g,%g gate=%g\n", (int)o[k].model, (int)o[k].reserved, o[k].z[0],
+               o[k].z[1], o[k].R[0], o[k].R[1], o[k].R[2], o[k].R[3], (long long)o[k].lm[0], (long long)o[k].lm[1], o[k].anchor[0], o[k].anchor[1], o[k].gate);
+    if (fail_armed) { fail_armed = 0; stub_fail_next(h); return ekf_flush(h); }
+    for (int64_t k = 0; k < m; ++k) {
+        out[k].best = k == 0 ? 1 : -1; out[k].second = k == 0 ? 0 : -1;
+        out[k].d2_best = k == 0 ? 0.5 : INFINITY; out[k].d2_second = k == 0 ? 7.0 : INFINITY;
+        out[k].within_gate = k == 0 ? 1 : 0; out[k].irregular = 10 * k;
+        if (d2_all) for (int64_t i = 0; i < N; ++i) d2_all[k * N + i] = 100.0 * (double)k + (double)i;      /* row-major m x N */
+    }
+    return EKF_OK;
+}
+'''
+
+_DRIVER = r'''
+#include <setjmp.h>
+#include <stdio.h>
+#include "ekfslam.h"
+#include "mex_mock.h"
+void arm_failure(void);
+static mxArray *out[4];
+static void show(const char *name, const mxArray *a) {
+    printf(" %s=%zux%zu[", name, mxGetM(a), mxGetN(a));
+    for (size_t i = 0; i < mxGetM(a) * mxGetN(a); ++i) printf(i ? ",%g" : "%g", mxGetPr(a)[i]);
+    printf("]");
+}
+static int call(const char *what, int nlhs, int nrhs, const mxArray **prhs) {
+    out[0] = out[1] = 0;
+    if (setjmp(mock_err_jmp)) { printf("MEX %s nrhs=%d -> ERROR %s | %s\n", what, nrhs, mock_err_id, mock_err_msg); return 1; }
+    mexFunction(nlhs, out, nrhs, prhs);
+    printf("MEX %s nrhs=%d -> ok", what, nrhs);
+    if (out[0] && mxGetClassID(out[0]) != mxUINT64_CLASS) show("out0", out[0]);
+    if (nlhs > 1 && out[1]) show("out1", out[1]);
+    printf("\n");
+    return 0;
+}
+#define D1(v) mock_double(1, 1, (const double[]){ v })
+int main(void) {
+    const mxArray *cr[3] = { mock_string("create"), D1(1), D1(64) };
+    if (call("create", 1, 3, cr)) return 1;
+    const mxArray *h = out[0];
+    const mxArray *sx[3] = { mock_string("set_x"), h, mock_double(9, 1, (const double[]){ 0, 0, 0, 1, 2, 3, 4, 5, 6 }) };      /* three landmarks */
+    if (call("set_x", 0, 3, sx)) return 1;
+    /* a scan of two: range and bearing (7, 8), a range 7.5; z is m x 2 column-major, R 2 x 2 x m */
+    const mxArray *model = mock_double(2, 1, (const double[]){ 1, 2 }), *z = mock_double(2, 2, (const double[]){ 7, 7.5, 8, 0 });
+    const mxArray *R = mock_double(4, 2, (const double[]){ 4, 1, 1, 9, 0.5, 0, 0, 0 }), *gate = mock_double(2, 1, (const double[]){ 9.5, 1.0 / 0.0 });
+    const mxArray *am[6] = { mock_string("associate_model"), h, model, z, R, gate };
+    if (call("associate_model", 1, 6, am)) return 1;
+    if (call("associate_model all", 2, 6, am)) return 1;
+    const mxArray *bad[6];
+    for (int q = 0; q < 6; ++q) bad[q] = am[q];
+    if (!call("associate_model", 1, 5, am)) return 1;
+    bad[2] = mock_double(0, 0, 0);
+    if (!call("associate_model none", 1, 6, bad)) return 1;
+    bad[2] = mock_double(33, 1, 0);
+    if (!call("associate_model many", 1, 6, bad)) return 1;
+    bad[2] = model; bad[3] = mock_double(2, 1, (const double[]){ 7, 8 });
+    if (!call("associate_model badz", 1, 6, bad)) return 1;
+    bad[3] = z; bad[4] = mock_double(2, 2, (const double[]){ 4, 1, 1, 9 });
+    if (!call("associate_model badr", 1, 6, bad)) return 1;
+    bad[4] = R; bad[5] = D1(9.5);
+    if (!call("associate_model badgate", 1, 6, bad)) return 1;
+    bad[5] = gate; bad[1] = D1(1);
+    if (!call("associate_model noh", 1, 6, bad)) return 1;
+    arm_failure();
+    if (!call("associate_model", 1, 6, am)) return 1;
+    const mxArray *de[2] = { mock_string("destroy"), h };
+    if (call("destroy", 0, 2, de)) return 1;
+    printf("LOCKS %d\nMISUSE %d\n", mock_lock_count, mock_misuse);
+    return 0;
+}
+'''
+
+_DRIVER_WITHOUT = r'''
+#include <setjmp.h>
+#include <stdio.h>
+#include "ekfslam.h"
+#include "mex_mock.h"
+static mxArray *out[4];
+static int call(const char *what, int nrhs, const mxArray **prhs) {
+    out[0] = 0;
+    if (setjmp(mock_err_jmp)) { printf("MEX %s nrhs=%d -> ERROR %s | %s\n", what, nrhs, mock_err_id, mock_err_msg); return 1; }
+    mexFunction(1, out, nrhs, prhs);
+    printf("MEX %s nrhs=%d -> ok\n", what, nrhs);
+    return 0;
+}
+#define D1(v) mock_double(1, 1, (const double[]){ v })
+int main(void) {
+    const mxArray *cr[3] = { mock_string("create"), D1(1), D1(64) };
+    if (call("create", 3, cr)) return 1;
+    const mxArray *h = out[0];
+    const mxArray *am[6] = { mock_string("associate_model"), h, D1(1), mock_double(1, 2, 0), mock_double(2, 2, 0), D1(1) };
+    if (!call("associate_model", 6, am)) return 1;
+    const mxArray *pr[3] = { mock_string("predict"), h, mock_double(2, 1, (const double[]){ 0.1, 3 }) };
+    if (call("predict", 3, pr)) return 1;
+    const mxArray *de[2] = { mock_string("destroy"), h };
+    if (call("destroy", 2, de)) return 1;
+    printf("LOCKS %d\nMISUSE %d\n", mock_lock_count, mock_misuse);
+    return 0;
+}
+'''
+
+
+def _build_and_run(files, exe):
+    r = subprocess.run(GCC + INCLUDES + [os.path.join(ROOT, "matlab", "ekfslam_mex.c"), os.path.join(MOCK, "mex_mock.c"),
+                                         os.path.join(MOCK, "abi_stub.c")] + files + ["-o", exe, "-lm"], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-4000:]
+    r = subprocess.run([exe], capture_output=True, text=True, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=0"))
+    assert r.returncode == 0, "the gateway misbehaved under the mock:\n" + r.stdout[-2000:] + r.stderr[-4000:]
+    return r.stdout.splitlines()
+
+
+def test_mex_gateway_marshals_a_scan_once(tmp_path):
+    stub, drv = tmp_path / "assoc_stub.c", tmp_path / "assoc_drv.c"
+    stub.write_text(_STUB)
+    drv.write_text(_DRIVER)
+    t = _build_and_run([str(stub), str(drv)], str(tmp_path / "drv"))
+    # every entry searches: lm = {-1, -1}, the anchor zero; R column-major as MATLAB holds it; the matrix only where a second output is asked for
+    i = t.index("ABI ekf_associate_model m=2 d2_all=0")
+    assert t[i + 1] == "ABI   obs model=1 reserved=0 z=7,8 R=4,1,1,9 lm=-1,-1 anchor=0,0 gate=9.5"
+    assert t[i + 2] == "ABI   obs model=2 reserved=0 z=7.5,0 R=0.5,0,0,0 lm=-1,-1 anchor=0,0 gate=inf"
+    # landmarks 1-based with 0 = none; one row per observation: best second d2_best d2_second within_gate irregular (column-major here)
+    assert t[i + 3] == "MEX associate_model nrhs=6 -> ok out0=2x6[2,0,1,0,0.5,inf,7,inf,1,0,0,10]"
+    i = t.index("ABI ekf_associate_model m=2 d2_all=1")
+    assert t[i + 3] == "MEX associate_model all nrhs=6 -> ok out0=2x6[2,0,1,0,0.5,inf,7,inf,1,0,0,10] out1=3x2[0,1,2,100,101,102]"      # N x m: column k = observation k
+    assert any(ln.startswith("MEX associate_model nrhs=5 -> ERROR ekfslam:usage") and "needs 6 arguments" in ln for ln in t)
+    for which, what in (("none", "between 1 and 32 observations"), ("many", "between 1 and 32 observations"), ("badz", "z needs m x 2 elements"),
+                        ("badr", "R needs 2 x 2 x m elements"), ("badgate", "gate needs m elements")):
+        assert any(ln.startswith("MEX associate_model %s nrhs=6 -> ERROR ekfslam:usage" % which) and what in ln for ln in t), which
+    assert any(ln.startswith("MEX associate_model noh nrhs=6 -> ERROR ekfslam:handle") for ln in t)
+    assert sum(ln.startswith("ABI ekf_associate_model") for ln in t) == 3         # the two good calls and the injected failure
+    assert "MEX associate_model nrhs=6 -> ERROR ekfslam:status | call not valid in the current state: injected failure" in t
+    assert t[-2:] == ["LOCKS 0", "MISUSE 0"]
+
+
+def test_the_gateway_still_links_against_a_library_without_the_symbol(tmp_path):
+    drv = tmp_path / "without_drv.c"
+    drv.write_text(_DRIVER_WITHOUT)
+    t = _build_and_run([str(drv)], str(tmp_path / "drv"))
+    assert any(ln.startswith("MEX associate_model ") and "ERROR ekfslam:usage" in ln and "this libekfslam has no ekf_associate_model" in ln for ln in t)
+    assert "MEX predict nrhs=3 -> ok" in t and t[-2:] == ["LOCKS 0", "MISUSE 0"]
+
+
+def test_matlab_methods_forward_to_the_gateway_command():
+    text = open(os.path.join(ROOT, "matlab", "EKF_SLAM.m")).read()
+    m = re.search(r"function\s+\[match,\s*d2\]\s*=\s*associateModel\(h,\s*model,\s*z,\s*R,\s*gate\)(.*?)\n        end\b", text, re.S)
+    assert m and m.group(1).count("h.gateway('associate_model', model, z, R, gate)") == 2
+    m = re.search(r"function\s+out\s*=\s*measureModel\(h,\s*model,\s*z,\s*R,\s*gateMatch,\s*gateNew,\s*signature\)(.*?)\n        end\n        function", text, re.S)
+    body = m.group(1)
+    assert "h.associateModel(model, z, R, gateMatch)" in body and "h.addLandmarksModel(" in body
+    assert re.search(r"h\.observeModel\(model\(k\),\s*z\(k, :\),\s*R\(:, :, k\),\s*match\(k, 1\),\s*\[\],\s*gateMatch,", body)
+    assert body.index("h.observeModel(") < body.index("h.addLandmarksModel(")               # the matched ones first, then ONE append
+    src = open(os.path.join(ROOT, "matlab", "ekfslam_mex.c")).read()
+    assert 'strcmp(cmd, "associate_model")' in src and "#pragma weak ekf_associate_model" in src
