@@ -302,7 +302,8 @@ EKF_MHD void model_wrap(int model, int wrap_deg[2]) {
 
 // The small part of a MODEL observation: linear_small with nu = z - h(x) in place of z - H x (rows wrapped as model_wrap says); Gs and S
 // in linear_small's summation order, so a linear observation handed this H gives the same Gs and S bit for bit.  Kept beside
-// linear_small, not split out of it: k_gather_linear's registers are pinned.
+// linear_small, not split out of it: k_gather_linear's registers are pinned.  (The two meet one level up: each is what
+// the small_solve overload of its argument block runs, linear_obs.h / model_obs.h.)
 EKF_MHD void model_small(const double *sm, const double H[14], const double hx[2], const double z[2], const double R[4],
                          const int wrap_deg[2], double Gs[14], double S[4], double nu[2]) {
     for (int r = 0; r < 2; ++r) {

@@ -10,6 +10,24 @@ int32_t create_linear(ekf_handle *h) {
     return new_event(h, &h->ev_linrec) == hipSuccess ? EKF_OK : fail(h, EKF_ERR_HIP, "create: the linear observation's event");
 }
 
+// The noise covariance of `rows` observed rows, row-major into out: two rows through parse_R; one row as the pair with the exactly empty
+// second row (R01 = R10 = 0, R11 = 1).  Then the gate.  (model.h's model_parse uses both.)
+int32_t parse_R_rows(ekf_handle *h, const std::string &who, int rows, const double *R, double out[4]) {
+    if (rows == 2) {
+        if (const char *bad = parse_R(R, out[0], out[1], out[2], out[3])) return fail(h, EKF_ERR_INVALID_ARG, (who + bad).c_str());
+        return EKF_OK;
+    }
+    out[0] = R[0]; out[1] = out[2] = 0.0; out[3] = 1.0;
+    REQUIRE(h, std::isfinite(out[0]), EKF_ERR_INVALID_ARG, (who + "R is not finite").c_str());
+    REQUIRE(h, out[0] >= 0.0, EKF_ERR_INVALID_ARG, (who + "R must be symmetric with non-negative diagonal and determinant").c_str());
+    return EKF_OK;
+}
+int32_t parse_gate(ekf_handle *h, const std::string &who, double gate, double &out) {
+    REQUIRE(h, !std::isnan(gate), EKF_ERR_INVALID_ARG, (who + "the gate is NaN").c_str());
+    out = gate;
+    return EKF_OK;
+}
+
 // Arguments of both entry points, in the header's order, into the kernel's form (row-major H over robot | lm[0] | lm[1], R row-major;
 // rows == 1: the exactly empty second row).  The landmark rows are filled in once N is exact (linear_rungs).
 int32_t linear_parse(ekf_handle *h, const std::string &who, const ekf_linear_obs *obs, LinearArgs &a) {
@@ -29,17 +47,8 @@ int32_t linear_parse(ekf_handle *h, const std::string &who, const ekf_linear_obs
         a.wrap[r] = obs->wrap_deg[r] != 0;
     }
     REQUIRE(h, finite, EKF_ERR_INVALID_ARG, (who + "z or H is not finite").c_str());
-    double r00, r01, r10, r11;
-    if (rows == 2) {
-        if (const char *bad = parse_R(obs->R, r00, r01, r10, r11)) return fail(h, EKF_ERR_INVALID_ARG, (who + bad).c_str());
-    } else {
-        r00 = obs->R[0]; r01 = r10 = 0.0; r11 = 1.0;
-        REQUIRE(h, std::isfinite(r00), EKF_ERR_INVALID_ARG, (who + "R is not finite").c_str());
-        REQUIRE(h, r00 >= 0.0, EKF_ERR_INVALID_ARG, (who + "R must be symmetric with non-negative diagonal and determinant").c_str());
-    }
-    a.R[0] = r00; a.R[1] = r01; a.R[2] = r10; a.R[3] = r11;
-    REQUIRE(h, !std::isnan(obs->gate), EKF_ERR_INVALID_ARG, (who + "the gate is NaN").c_str());
-    a.gate = obs->gate;
+    TRY(parse_R_rows(h, who, rows, obs->R, a.R));
+    TRY(parse_gate(h, who, obs->gate, a.gate));
     REQUIRE(h, !(obs->lm[0] >= 0 && obs->lm[0] == obs->lm[1]), EKF_ERR_INVALID_ARG, (who + "the two landmarks must differ").c_str());
     REQUIRE(h, obs->lm[0] >= -1 && obs->lm[1] >= -1, EKF_ERR_INVALID_ARG, (who + "a landmark is -1 (none) or a 0-based index").c_str());
     return EKF_OK;
@@ -68,6 +77,34 @@ void linear_fill(const double *rec, ekf_linear_result *res) {
     res->d2 = rec[6];
     res->outcome = (int32_t)rec[7];
 }
+
+// The update-step behind ekf_observe_linear and ekf_observe_model, after the rungs.  gather_launch(rec, cnt) is the launch on h->stream.
+// No flush: the launch reads its tile operands patched with the pending pairs and writes its own into the next ring slot.
+template <typename Launch>
+int32_t observe_step(ekf_handle *h, const std::string &who, ekf_linear_result *res, const char *irregular_message, Launch gather_launch) {
+    TIMED(h, EKF_KERNEL_GATHER, gather_launch(h->d_linrec, h->d_lincnt));
+    if (res) {
+        HIPCHK(h, hipMemcpyAsync(h->h_linrec, h->d_linrec, kLinearRecordDoubles * 8, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipEventRecord(h->ev_linrec, h->stream));
+    }
+    TRY(finish_step(h));
+    if (!res) return EKF_OK;
+    HIPCHK(h, hipEventSynchronize(h->ev_linrec));      // the launch's record alone: a pass that finish_step started is not waited for
+    linear_fill(h->h_linrec, res);
+    REQUIRE(h, res->outcome != EKF_LINEAR_IRREGULAR, EKF_ERR_STATE, (who + irregular_message).c_str());
+    return EKF_OK;
+}
+
+// ... and the probe behind the two *_innovation entry points: probe_launch(rec) into the record's second slot, read back and waited for
+template <typename Launch>
+int32_t probe_step(ekf_handle *h, ekf_linear_result *res, Launch probe_launch) {
+    double *d_rec = h->d_linrec + kLinearRecordDoubles, *h_rec = h->h_linrec + kLinearRecordDoubles;
+    HIPCHK(h, probe_launch(d_rec));
+    HIPCHK(h, hipMemcpyAsync(h_rec, d_rec, kLinearRecordDoubles * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    linear_fill(h_rec, res);
+    return EKF_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -77,19 +114,9 @@ int32_t ekf_observe_linear(ekf_handle *h, const ekf_linear_obs *obs, ekf_linear_
     LinearArgs a;
     TRY(linear_parse(h, who, obs, a));
     TRY(linear_rungs(h, who, obs->lm, a));
-    // no flush: the launch reads its tile operands patched with the pending pairs and writes its own into the next ring slot
-    TIMED(h, EKF_KERNEL_GATHER, launch_gather_linear(h->st, a, h->d_linrec, h->d_lincnt, h->storage, h->stream));
-    if (res) {
-        HIPCHK(h, hipMemcpyAsync(h->h_linrec, h->d_linrec, kLinearRecordDoubles * 8, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipEventRecord(h->ev_linrec, h->stream));
-    }
-    TRY(finish_step(h));
-    if (!res) return EKF_OK;
-    HIPCHK(h, hipEventSynchronize(h->ev_linrec));      // the launch's record alone: a pass that finish_step started is not waited for
-    linear_fill(h->h_linrec, res);
-    REQUIRE(h, res->outcome != EKF_LINEAR_IRREGULAR, EKF_ERR_STATE, (who + "S = H P H' + R is not positive definite (an observation of "
-            "something already known exactly, with R = 0?); nothing was changed").c_str());
-    return EKF_OK;
+    return observe_step(h, who, res, "S = H P H' + R is not positive definite (an observation of something already known exactly, with R = 0?); "
+                        "nothing was changed",
+                        [&](double *rec, int64_t *cnt) { return launch_gather_linear(h->st, a, rec, cnt, h->storage, h->stream); });
 }
 
 int32_t ekf_linear_innovation(ekf_handle *h, const ekf_linear_obs *obs, ekf_linear_result *res) {
@@ -99,12 +126,7 @@ int32_t ekf_linear_innovation(ekf_handle *h, const ekf_linear_obs *obs, ekf_line
     TRY(linear_parse(h, who, obs, a));
     REQUIRE(h, res != nullptr, EKF_ERR_INVALID_ARG, (who + "null result").c_str());
     TRY(linear_rungs(h, who, obs->lm, a));
-    double *d_rec = h->d_linrec + kLinearRecordDoubles, *h_rec = h->h_linrec + kLinearRecordDoubles;
-    HIPCHK(h, launch_linear_probe(h->st, a, d_rec, h->storage, h->stream));
-    HIPCHK(h, hipMemcpyAsync(h_rec, d_rec, kLinearRecordDoubles * 8, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    linear_fill(h_rec, res);
-    return EKF_OK;
+    return probe_step(h, res, [&](double *rec) { return launch_linear_probe(h->st, a, rec, h->storage, h->stream); });
 }
 
 int32_t ekf_linear_rejections(ekf_handle *h, int64_t *irregular, int64_t *gated) {

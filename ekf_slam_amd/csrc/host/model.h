@@ -18,17 +18,8 @@ int32_t model_parse(ekf_handle *h, const std::string &who, const ekf_model_obs *
     if (anchored)
         for (int c = 0; c < 2; ++c) { finite = finite && std::isfinite(obs->anchor[c]); a.anchor[c] = obs->anchor[c]; }
     REQUIRE(h, finite, EKF_ERR_INVALID_ARG, (who + "z or the anchor is not finite").c_str());
-    double r00, r01, r10, r11;
-    if (rows == 2) {
-        if (const char *bad = parse_R(obs->R, r00, r01, r10, r11)) return fail(h, EKF_ERR_INVALID_ARG, (who + bad).c_str());
-    } else {
-        r00 = obs->R[0]; r01 = r10 = 0.0; r11 = 1.0;
-        REQUIRE(h, std::isfinite(r00), EKF_ERR_INVALID_ARG, (who + "R is not finite").c_str());
-        REQUIRE(h, r00 >= 0.0, EKF_ERR_INVALID_ARG, (who + "R must be symmetric with non-negative diagonal and determinant").c_str());
-    }
-    a.R[0] = r00; a.R[1] = r01; a.R[2] = r10; a.R[3] = r11;
-    REQUIRE(h, !std::isnan(obs->gate), EKF_ERR_INVALID_ARG, (who + "the gate is NaN").c_str());
-    a.gate = obs->gate;
+    TRY(parse_R_rows(h, who, rows, obs->R, a.R));
+    TRY(parse_gate(h, who, obs->gate, a.gate));
     if (pair) {
         REQUIRE(h, obs->lm[0] >= 0 && obs->lm[1] >= 0, EKF_ERR_INVALID_ARG, (who + "the landmark range names two landmarks (0-based)").c_str());
         REQUIRE(h, obs->lm[0] != obs->lm[1], EKF_ERR_INVALID_ARG, (who + "the two landmarks must differ").c_str());
@@ -47,19 +38,10 @@ int32_t ekf_observe_model(ekf_handle *h, const ekf_model_obs *obs, ekf_linear_re
     ModelArgs a;
     TRY(model_parse(h, who, obs, a));
     TRY(linear_rungs(h, who, obs->lm, a));
-    // no flush, as ekf_observe_linear; h(x) and H are formed by the launch, at the x that carries every pending pair
-    TIMED(h, EKF_KERNEL_GATHER, launch_gather_model(h->st, a, h->d_linrec, h->d_lincnt, h->storage, h->stream));
-    if (res) {
-        HIPCHK(h, hipMemcpyAsync(h->h_linrec, h->d_linrec, kLinearRecordDoubles * 8, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipEventRecord(h->ev_linrec, h->stream));
-    }
-    TRY(finish_step(h));
-    if (!res) return EKF_OK;
-    HIPCHK(h, hipEventSynchronize(h->ev_linrec));
-    linear_fill(h->h_linrec, res);
-    REQUIRE(h, res->outcome != EKF_LINEAR_IRREGULAR, EKF_ERR_STATE, (who + "the target lies on the point it is observed from (or the state is "
-            "not finite), or S = H P H' + R is not positive definite; nothing was changed").c_str());
-    return EKF_OK;
+    // h(x) and H are formed by the launch, at the x that carries every pending pair
+    return observe_step(h, who, res, "the target lies on the point it is observed from (or the state is not finite), or S = H P H' + R is not "
+                        "positive definite; nothing was changed",
+                        [&](double *rec, int64_t *cnt) { return launch_gather_model(h->st, a, rec, cnt, h->storage, h->stream); });
 }
 
 int32_t ekf_model_innovation(ekf_handle *h, const ekf_model_obs *obs, ekf_linear_result *res) {
@@ -69,12 +51,7 @@ int32_t ekf_model_innovation(ekf_handle *h, const ekf_model_obs *obs, ekf_linear
     TRY(model_parse(h, who, obs, a));
     REQUIRE(h, res != nullptr, EKF_ERR_INVALID_ARG, (who + "null result").c_str());
     TRY(linear_rungs(h, who, obs->lm, a));
-    double *d_rec = h->d_linrec + kLinearRecordDoubles, *h_rec = h->h_linrec + kLinearRecordDoubles;
-    HIPCHK(h, launch_model_probe(h->st, a, d_rec, h->storage, h->stream));
-    HIPCHK(h, hipMemcpyAsync(h_rec, d_rec, kLinearRecordDoubles * 8, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    linear_fill(h_rec, res);
-    return EKF_OK;
+    return probe_step(h, res, [&](double *rec) { return launch_model_probe(h->st, a, rec, h->storage, h->stream); });
 }
 
 int32_t ekf_model_evaluate(int32_t model, const double xr[3], const double t0[2], const double t1[2], double hx[2], double H[14]) {

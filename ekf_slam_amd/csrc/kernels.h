@@ -1,9 +1,11 @@
 // Host-side launch interface of the gfx950 kernels: one section per family, implemented by the fragment of kernels.hip the section names.
+// The state and the argument blocks the launchers take are plain data and live in kernel_args.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "device_math.h"
+#include "kernel_args.h"
 #include "layout.h"
 
 // Tuning switches.  The PRODUCT library compiles every one of them to its default constant: no environment variable changes
@@ -16,125 +18,16 @@ inline int ekf_tune_int(const char *name, int dflt) { const char *v = getenv(nam
 constexpr int ekf_tune_int(const char *, int dflt) { return dflt; }
 #endif
 
-// (DevState, ConstrainArgs and kConstrainRecordDoubles below are mirrored BY HAND in tests/support/merge_batch_host_emulation.cpp, which
-// compiles pair_column.h / constrain.h / compact.h / merge_pass.h for the host and cannot include this file (it needs the HIP headers): the
-// duplication is intentional; a field that those kernels read and that changes here must change there.)
-// Device-resident filter state.  Passed BY VALUE to every kernel.
-//   x / prr / strip are double-buffered: every kernel reads buffer `cur` and writes a complete buffer
-//   `cur ^ 1`, so no workgroup ever reads a value another workgroup of the same launch overwrites.
-struct DevState {
-    double *x[2];      // state vector, 3 + ldm
-    double *prr[2];    // P(1:3,1:3), row-major 3x3
-    double *strip[2];  // P(1:3, 4:end): 3 rows of ldm
-    void   *tiles;     // local tile store of the landmark block (double or float)
-    double *s;         // signatures, cap
-    // Pending rank-2 pairs: slot i holds G_i = H_s P(S,:) over landmark columns, interleaved (G(1,c), G(2,c)),
-    // and K_i over landmark rows, interleaved (K(r,1), K(r,2)); slots are pair_stride doubles apart.  The tiles
-    // hold P_base; the live landmark block is P_base - sum_i K_i G_i (applied in slot order).
-    // The slots form a ring of `pcap` entries: a kernel that is told (pstart, npend) sees the pairs in slots
-    // (pstart + i) mod pcap, i = 0 .. npend-1, oldest first.
-    double *Gp;           // pending G pairs, then (same allocation) ...
-    double *Kp;           // ... the pending K pairs: Kp = Gp + pcap * pair_stride (k_gather relies on a 32-bit offset between them)
-    float  *Gp32;         // cfg.pass_arith = EKF_ARITH_F32 only (nullptr otherwise): float copies of the same pairs in the same slots, written by the
-    float  *Kp32;         // gather beside the F64 ones for the F32-arithmetic pass (half the operand bytes) -- PLANAR (slot s: plane x = ldm floats, then
-                          // plane y) and, for K, NEGATED (-(float)K, exact): the pass's LDS-DMA pieces are plain copies (flush32_pipe.h)
-    int64_t pair_stride;   // 2 * ldm
-    int32_t pcap;          // slots in the ring
-    double *small;     // 32: Gr[2][3] (0..5), Kr[3][2] (6..11), Q[9] (12..20)
-    int64_t ldm;       // strip leading dimension = landmark-block capacity rounded up to T
-    TileMap tm;
-    // The 2x2 DIAGONAL blocks of the landmark block, kept LIVE in F64 beside the tiles: landmark k's (P(2k,2k), P(2k+1,2k), P(2k+1,2k+1))
-    // at diag[dcur][3k .. 3k+2].  Every correction's gather kernel applies its own pair to them at once (each column lane holds K(c,:)
-    // and G(:,c)) -- the chain base - sum_i K_i G_i in slot order that a reader of the tiles would have to re-run over the pending pairs,
-    // so in F64 the values equal the patched tile entries bit for bit -- reading buffer dcur, writing dcur ^ 1 (flipped per correction,
-    // independently of `cur`: a predict does not touch them).  Why: (1) whoever needs a diagonal block (the correction's own solve, the
-    // association of every landmark) reads three doubles instead of patching a chain of pending pairs; (2) with F32 tiles these are the
-    // LARGE entries of P (an appended, not yet re-observed landmark: ~17 against a bulk of 0.1) whose sub-ulp updates a float store loses
-    // -- in F64 they lose nothing.  Replicated on every shard (the gather is).  The tiles' own copies of these entries keep being
-    // maintained by the passes but are no longer read.
-    double *diag[2];
-    int32_t dcur;
-};
-
 // ---- the steps: predict, append, the gather of a correction, a shard's row-panels, association (launch/steps.h) ----
-struct PredictArgs {
-    double u0, u1, C;
-    int64_t n_mm;
-    int32_t cur;
-};
 hipError_t launch_predict(const DevState &st, const PredictArgs &a, int storage, hipStream_t s);
 
-struct AssocHostPartial;      // (with the association, below)
-
-// Device-resident measure() loop (EKF_SLAM_UC.m:107-151 without a host round trip per observation): the association decision of
-// an observation is PRODUCED on the device (k_associate, or the epilogue of the previous observation's k_gather) as one winner per
-// workgroup, and CONSUMED on the device by the next launch (k_gather takes its landmark from the arg-min over those winners;
-// k_append checks that nothing passed the threshold).  The host only learns the decisions afterwards, from `rec`.
-struct DevLoopArgs {
-    const AssocHostPartial *parts_in;   // DEVICE: per-workgroup winners of THIS observation's association; nullptr: not in use
-    AssocHostPartial *rec;              // MAPPED HOST: the decision this launch consumed, one self-validating 16-byte store
-                                        //   (index: landmark 0-based, -1 = new landmark, -2 = a winner entry did not carry seq_in)
-    AssocHostPartial *parts_out;        // DEVICE: winners of the NEXT observation's association, evaluated in k_gather's epilogue
-                                        //   on the state this correction leaves (one entry per k_gather workgroup); nullptr: none
-    int32_t nblk_in, seq_in;            // entries of parts_in and the launch number they must carry
-    int32_t seq_rec, seq_out;           // launch numbers stamped on rec / parts_out
-    double z0, z1, z2;                  // the next observation [range, bearing_deg, signature] and its R
-    double R00, R01, R10, R11;
-    double s_cost, s_thresh, w_pos;
-    // cfg.device_assoc == 4 (k_gather<.., kDecide>): the device also takes the branch.  The landmark count lives on the device, in a
-    // ring the host advances by one slot per launch: the launch reads *dn_in (n_known >= 0: the host knows it exactly, *dn_in is not
-    // read) and writes the count it leaves to *dn_out.  An append (winners: -1) reads the landmark-list entry of key N + 1
-    // (EKF_SLAM_UC.m:122) from loc + 3 (N - loc_base) (MAPPED host memory: x, y, number of entries that carry the key) and carries out
-    // append(u, R, loc, N + 1) -- unless the key matched no entry or several: then nothing is applied, the record says -4 and every
-    // later launch of the same scan (*abort == scan_id) applies nothing either (record -3), as the waited loop stops at that row.
-    const int64_t *dn_in;
-    int64_t *dn_out;
-    int64_t n_known;
-    const double *loc;
-    int64_t loc_base;
-    double u0, u1;
-    int32_t *abort;
-    int32_t scan_id;
-};
-
-struct AppendArgs {
-    double u0, u1;
-    double R00, R01, R10, R11;
-    double pos0, pos1, signature;
-    int64_t N;                // landmarks before the append
-    int32_t cur;
-};
 // dl != nullptr (device-resident measure loop): the kernel also reduces dl->parts_in and records the decision in dl->rec
 hipError_t launch_append(const DevState &st, const AppendArgs &a, int storage, hipStream_t s, const DevLoopArgs *dl = nullptr,
                          const PredictArgs *fused_predict = nullptr);
 
-// k_append_model (append_model.h): m <= kAppendModelMax landmarks that start from a range-and-bearing or a relative-position fix, appended
-// by ONE launch at the live robot state -- entry b becomes landmark N + b.  Nothing but new slots is written, in place on buffer cur (the
-// live diagonal copies: st.dcur); no predict is folded in.  The entries travel in the argument block.
-constexpr int kAppendModelMax = 32;
-struct AppendModelEntry {
-    double z0, z1;            // RANGE_BEARING: range, bearing in degrees; RELATIVE_XY: the landmark in the robot frame
-    double R00, R01, R10, R11;
-    double signature;
-    int32_t model, pad;       // EKF_MODEL_RANGE_BEARING (1) or EKF_MODEL_RELATIVE_XY (4)
-};
-struct AppendModelArgs {
-    int64_t N;                // landmarks before the append
-    int32_t m;                // entries in use
-    int32_t cur;
-    AppendModelEntry e[kAppendModelMax];
-};
+// k_append_model (append_model.h): a.m <= kAppendModelMax landmarks appended by ONE launch at the live robot state
 hipError_t launch_append_model(const DevState &st, const AppendModelArgs &a, int storage, hipStream_t s);
 
-struct CorrectArgs {
-    double z0, z1;            // [range, bearing_deg]
-    double R00, R01, R10, R11;
-    int64_t j;                // landmark-block row of the corrected landmark (2*idx)
-    int64_t n_mm;             // active landmark-block size (2N)
-    int32_t cur;
-    int32_t npend;            // pending pairs before this correction; its own pair goes to ring position npend
-    int32_t pstart;           // ring slot of the oldest pending pair
-};
 // fused_predict != nullptr folds predict(u) into the correction (one launch instead of two, identical arithmetic)
 // fuse_downdate: the kernel also applies its pair to the landmark block (small maps: a.n_mm <= gather_fuse_max_rows(), one
 // workgroup); the pair is then NOT written to the pending ring and no downdate launch must follow
@@ -175,19 +68,6 @@ hipError_t launch_rowpanel_next(const DevState &st, const int64_t *idx, int m, i
 hipError_t launch_gather_sharded(const DevState &st, const CorrectArgs &a, const PredictArgs *fused_predict, const double *recv,
                                  int64_t rank_stride, int64_t offset, bool patched, int storage, hipStream_t s,
                                  const DevLoopArgs *dl = nullptr);
-
-struct AssocArgs {
-    double z0, z1, z2;
-    double R00, R01, R10, R11;
-    double s_cost, s_thresh, w_pos;
-    int64_t N;
-    int32_t cur;
-    int32_t npend;
-    int32_t pstart;
-    int32_t own_only;         // sharded association with an exchange: nominate only landmarks whose diagonal block this shard holds
-    const int64_t *dN;        // k_associate<.., kDevN> (cfg.device_assoc == 4): the landmark count on the device (nullptr: N is exact);
-                              //   N is then the host's upper bound, which only sizes the grid
-};
 
 struct AssocDecision {        // written by the device, read back by the host
     int64_t index;            // 0-based; == N for a new landmark
@@ -237,22 +117,7 @@ hipError_t launch_associate_devn(const DevState &st, const AssocArgs &a, AssocHo
 hipError_t launch_assoc_merge(const DevState &st, const double *recv, int world, int64_t count, int64_t N, bool want_costs,
                               double *pos_cost, AssocDecision *decision, AssocDecision *host_decision, int seq, hipStream_t s);
 
-// k_assoc_model / k_assoc_model_reduce (associate_model.h): a scan of m <= kAssocModelMax observations under ekf_observe_model's conventions
-// scored against all N landmarks, read-only, from the live F64 copies alone (x, Prr, the strip, the diagonal blocks of buffer cur / st.dcur):
-// no tile is touched, so the storage type does not matter.  The entries travel in the argument block.
-constexpr int kAssocModelMax = 32;
-struct AssocModelEntry {
-    double z[2];
-    double R[4];              // row-major; a one-row model: [r, 0, 0, 1] and z[1] = 0 (model_parse)
-    double gate;              // feeds the count `within` alone
-    int32_t model, pad;       // EKF_MODEL_* 1-4
-};
-struct AssocModelArgs {
-    int64_t N;                // landmarks, >= 1
-    int32_t m;                // entries in use
-    int32_t cur;
-    AssocModelEntry e[kAssocModelMax];
-};
+// k_assoc_model / k_assoc_model_reduce (associate_model.h): a scan of a.m <= kAssocModelMax observations scored against all N landmarks, read-only.
 // partials (device): m * ceil(N / kAssocBlock) records, one per workgroup of the first launch; out (device): m records, the second launch's;
 // d2_all (device): nullptr, or m x N row-major, NaN where a pair has no d2.  Two launches ordered by the stream.
 hipError_t launch_assoc_model(const DevState &st, const AssocModelArgs &a, ekfm::Match2 *partials, ekfm::Match2 *out, double *d2_all,
@@ -308,16 +173,6 @@ hipError_t launch_compact_tiles(const TileMap &tm, const void *src, void *dst, c
 // ... and x, the strip and the live diagonal blocks from buffer cur / st.dcur into the other one (Prr and the pose copied), the
 // signatures into s_out (N_old doubles): N_old = landmarks before the removal
 hipError_t launch_compact_state(const DevState &st, int cur, const int32_t *src_of, int64_t N_old, double *s_out, hipStream_t s);
-// A constraint between two landmarks (constrain.h): "l_i - l_j was observed as (d0, d1) with noise covariance R".
-struct ConstrainArgs {
-    double d0, d1;
-    double R00, R01, R10, R11;
-    int64_t ai, aj;           // landmark-block rows of the two landmarks (2 * index), ai != aj
-    int64_t n_mm;             // active landmark-block size (2N)
-    int32_t cur;
-    int32_t npend;            // ring position the pair goes to (the ring is empty when the kernel runs: 0) ...
-    int32_t pstart;           // ... counted from this slot
-};
 // out (device, 14 doubles): both landmarks' own 2x2 blocks (live F64 copies), their cross block (tiles), their entries of x -- what the
 // host forms S and nu from before anything changes
 hipError_t launch_constrain_probe(const DevState &st, int cur, int64_t ai, int64_t aj, double *out, int storage, hipStream_t s);
@@ -331,7 +186,6 @@ hipError_t launch_gather_constrain(const DevState &st, const ConstrainArgs &a, i
 // a.pstart ..) are still pending -- every tile operand is read patched with them -- and a record of it into rec (device,
 // kConstrainRecordDoubles doubles: S row-major, nu, d2 as ekfm::constrain_d2 gives it, 1.0 / 0.0 = S regular or not); an irregular S
 // leaves a zero pair and copies the state.
-constexpr int kConstrainRecordDoubles = 8;
 hipError_t launch_gather_constrain_chain(const DevState &st, const ConstrainArgs &a, double *rec, int storage, hipStream_t s);
 // launch_merge_pass (merge_pass.h): the `ntiles` destination tiles work[0 ..) of the store `dst` (never st.tiles) = the compaction of
 // launch_compact_tiles applied to st.tiles - sum_{i < npairs} K_i G_i (ring slots 0 .. npairs-1, in slot order), each element loaded once,
@@ -341,25 +195,9 @@ hipError_t launch_merge_pass(const DevState &st, void *dst, const int2 *work, in
 // The candidate search in front of a merge (nearest.h): out[i] = (min over j < i of d2(i, j), that j; (+inf, -1) where no pair is
 // admissible) for the N landmarks of an UNSHARDED tile store (tm.world == 1: the search needs every tile), d2 as ekf_landmark_distance
 // defines it for delta = 0 and the noise covariance R (row-major).  Reads state buffer cur / diagonal buffer st.dcur, writes `out` only.
-struct alignas(16) NearestEntry { double d2; int64_t partner; };
 hipError_t launch_nearest(const DevState &st, int cur, int64_t N, const double R[4], NearestEntry *out, int storage, hipStream_t s);
 
-// A linear observation with a constant Jacobian (linear_obs.h): "H x was observed as z with noise covariance R", H = a 2x3 block on
-// the robot state and 2x2 blocks on up to two landmarks.  An UPDATE-STEP on the handle's own ring, like a correction.
-struct LinearArgs {
-    double z[2];
-    double R[4];              // row-major
-    double H[14];             // row-major 2 x 7: the robot block (columns 0..2), landmark a[0]'s (3, 4), landmark a[1]'s (5, 6); zeros where absent
-    double gate;              // applied only if d2 <= gate (+inf: always)
-    int64_t a[2];             // landmark-block rows of the landmarks that carry a block (2 * index), -1 = none; different when both >= 0
-    int64_t n_mm;             // active landmark-block size (2N)
-    int32_t wrap[2];          // row r of nu is an angle in degrees: wrapped into (-180, 180]
-    int32_t cur;
-    int32_t npend;            // pending pairs before this step; its own pair goes to ring position npend
-    int32_t pstart;           // ring slot of the oldest pending pair
-};
-// the record of a launch: S row-major, nu, d2 as ekfm::constrain_d2 gives it, the outcome (1.0 applied, 0.0 S irregular, 2.0 gated)
-constexpr int kLinearRecordDoubles = 8;
+// A linear observation with a constant Jacobian (linear_obs.h), an UPDATE-STEP on the handle's own ring, like a correction.
 // k_gather_linear: the observation's pair into ring position a.npend (float copies included) with every tile operand read patched with
 // the a.npend pending pairs, x / Prr / strip into buffer a.cur ^ 1, every landmark's live diagonal block into buffer dcur ^ 1, the record
 // into rec, and cnt[0] / cnt[1] (device) incremented where S was irregular / d2 beyond the gate: such a launch leaves a zero pair and
@@ -368,20 +206,7 @@ hipError_t launch_gather_linear(const DevState &st, const LinearArgs &a, double 
 // k_linear_probe: the record that launch would write under the current state, and nothing else
 hipError_t launch_linear_probe(const DevState &st, const LinearArgs &a, double *rec, int storage, hipStream_t s);
 
-// An observation through one of the MODELS of ekf_observe_model (model_obs.h): the update-step above with h(x) and its Jacobian H
-// evaluated on the device at the live x (ekfm::model_eval), nu = z - h(x).  H is no argument: lane 0 of every workgroup forms it.
-struct ModelArgs {
-    double z[2];
-    double R[4];              // row-major
-    double anchor[2];         // the target of models 1-4 where a[0] == -1
-    double gate;
-    int64_t a[2];             // as LinearArgs::a; models 1-4: a[1] == -1, model 5: both >= 0
-    int64_t n_mm;
-    int32_t model;            // EKF_MODEL_*
-    int32_t cur;
-    int32_t npend;
-    int32_t pstart;
-};
+// An observation through one of the MODELS of ekf_observe_model (model_obs.h): the same step with H formed on the device.
 // k_gather_model / k_model_probe: launch_gather_linear / launch_linear_probe for a model, the record and the counters shared with them;
 // a target on the robot (q = 0) or a non-finite q counts and reports as an irregular S
 hipError_t launch_gather_model(const DevState &st, const ModelArgs &a, double *rec, int64_t *cnt, int storage, hipStream_t s);

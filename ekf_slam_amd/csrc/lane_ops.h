@@ -1,6 +1,6 @@
 // Fragment of kernels.hip (included there, inside its anonymous namespace, in front of every kernel family): values that travel between
-// the lanes of one wavefront without LDS memory, and the wavefront's own LDS ordering.  (The host emulation of
-// tests/support/merge_batch_host_emulation.cpp supplies a lane_xor1 of its own and does not include this file.)
+// the lanes of one wavefront without LDS memory, and the wavefront's own LDS ordering.  (The host emulations of
+// tests/support supply a lane_xor1 of their own, kernel_host_shim.h, and do not include this file.)
 #pragma once
 
 __device__ __forceinline__ double lane_bcast(double v, int src) {        // value of lane `src` (compile-time) on every lane

@@ -92,36 +92,37 @@ bool model_args_ok(const ModelArgs &a) {
     if (a.model < 1 || a.model > 5) return false;
     return a.model == 5 ? (a.a[0] >= 0 && a.a[1] >= 0) : a.a[1] == -1;
 }
+// One launch of an update-step over the padded landmark block, 256 columns per workgroup (an empty map: workgroup 0 alone, for x_r and
+// Prr), and of its probe (one wavefront).  kernel: a generic lambda that names the instance for a storage tag, `[](auto ts) { return
+// k_gather_linear<decltype(ts)>; }`; ok: the caller's argument check.
+template <typename K, typename A>
+hipError_t launch_step(bool ok, K kernel, const DevState &st, const A &a, double *rec, int64_t *cnt, int storage, hipStream_t s) {
+    if (!ok) return hipErrorInvalidValue;
+    const int64_t grid = std::max<int64_t>(1, cdiv(st.tm.padded(a.n_mm), kBlock));
+    return with_storage(storage, [&](auto ts) { hipLaunchKernelGGL(kernel(ts), dim3((unsigned)grid), dim3(kBlock), 0, s, st, a, rec, cnt); });
+}
+template <typename K, typename A>
+hipError_t launch_step_probe(bool ok, K kernel, const DevState &st, const A &a, double *rec, int storage, hipStream_t s) {
+    if (!ok) return hipErrorInvalidValue;
+    return with_storage(storage, [&](auto ts) { hipLaunchKernelGGL(kernel(ts), dim3(1), dim3(64), 0, s, st, a, rec); });
+}
 }  // namespace
 
 hipError_t launch_gather_linear(const DevState &st, const LinearArgs &a, double *rec, int64_t *cnt, int storage, hipStream_t s) {
-    if (!linear_args_ok(st, a) || a.npend >= st.pcap || !rec || !cnt) return hipErrorInvalidValue;
-    const int64_t grid = std::max<int64_t>(1, cdiv(st.tm.padded(a.n_mm), kBlock));      // (an empty map: workgroup 0 alone, for x_r and Prr)
-    return with_storage(storage, [&](auto ts) {
-        hipLaunchKernelGGL(k_gather_linear<decltype(ts)>, dim3((unsigned)grid), dim3(kBlock), 0, s, st, a, rec, cnt);
-    });
+    return launch_step(linear_args_ok(st, a) && a.npend < st.pcap && rec && cnt, [](auto ts) { return k_gather_linear<decltype(ts)>; }, st, a, rec, cnt, storage, s);
 }
 
 hipError_t launch_linear_probe(const DevState &st, const LinearArgs &a, double *rec, int storage, hipStream_t s) {
-    if (!linear_args_ok(st, a) || !rec) return hipErrorInvalidValue;
-    return with_storage(storage, [&](auto ts) {
-        hipLaunchKernelGGL(k_linear_probe<decltype(ts)>, dim3(1), dim3(64), 0, s, st, a, rec);
-    });
+    return launch_step_probe(linear_args_ok(st, a) && rec, [](auto ts) { return k_linear_probe<decltype(ts)>; }, st, a, rec, storage, s);
 }
 
 hipError_t launch_gather_model(const DevState &st, const ModelArgs &a, double *rec, int64_t *cnt, int storage, hipStream_t s) {
-    if (!linear_args_ok(st, a) || !model_args_ok(a) || a.npend >= st.pcap || !rec || !cnt) return hipErrorInvalidValue;
-    const int64_t grid = std::max<int64_t>(1, cdiv(st.tm.padded(a.n_mm), kBlock));
-    return with_storage(storage, [&](auto ts) {
-        hipLaunchKernelGGL(k_gather_model<decltype(ts)>, dim3((unsigned)grid), dim3(kBlock), 0, s, st, a, rec, cnt);
-    });
+    return launch_step(linear_args_ok(st, a) && model_args_ok(a) && a.npend < st.pcap && rec && cnt, [](auto ts) { return k_gather_model<decltype(ts)>; }, st, a, rec, cnt,
+                       storage, s);
 }
 
 hipError_t launch_model_probe(const DevState &st, const ModelArgs &a, double *rec, int storage, hipStream_t s) {
-    if (!linear_args_ok(st, a) || !model_args_ok(a) || !rec) return hipErrorInvalidValue;
-    return with_storage(storage, [&](auto ts) {
-        hipLaunchKernelGGL(k_model_probe<decltype(ts)>, dim3(1), dim3(64), 0, s, st, a, rec);
-    });
+    return launch_step_probe(linear_args_ok(st, a) && model_args_ok(a) && rec, [](auto ts) { return k_model_probe<decltype(ts)>; }, st, a, rec, storage, s);
 }
 
 hipError_t launch_nearest(const DevState &st, int cur, int64_t N, const double R[4], NearestEntry *out, int storage, hipStream_t s) {

@@ -8,8 +8,13 @@
 // -- the update of constrain.h for a general H (there: Hr = 0, Hl = +I2, -I2).  Unlike a constraint this is an UPDATE-STEP: the
 // launch runs on the handle's own ring while the a.npend earlier pairs are still pending, reads every tile operand patched with
 // them (constrain_row_pair_chain, pmm_low_chain) and leaves its pair in the next slot, float copies included, as k_gather does.
+// ONE BODY, two kernels.  step_small_part and gather_step_body are templates over the argument block and the workgroup's solve; what
+// differs between a step with a constant H and one through a model (model_obs.h) is two overloads found by their argument types:
+//     small_solve(a, sm, sol)   lane 0's work on the loaded operands: S, nu, the outcome, the record, the solve (a model: h(x) and H first)
+//     step_H(a, sol)            where the column lanes read H: the argument block, or the LDS copy a model's lane 0 left
+// Both kernels compile to the code they had as two texts (profiles/observe_step/README.md).
 // The small part's solve, the record and workgroup 0's robot part are pair_column.h's.  The column's own share (steps (1), (3), (3b)) is
-// the twin of its load_column_operands / finish_pair_column, kept as text of its own: called from here those two cost this kernel
+// the twin of its load_column_operands / finish_pair_column, kept as text of its own: called from here those two cost k_gather_linear
 // 0.1-0.4 us of its 8-17 (measured against the parent commit, profiles/pair_column/README.md), although they are the same statements.
 // x, the strip, Prr and the live diagonal blocks carry every pending pair already and are read as they are.
 // ---------------------------------------------------------------------------------------------------
@@ -43,22 +48,25 @@ struct LinearSolve : PairSolve {
     double rec[kLinearRecordDoubles];
 };
 
+// Lane 0's share of the small part: S, nu, d2, the decision, S^-1, Gr and Kr from the operands in sm.  A launch that does not apply (S
+// irregular, d2 beyond the gate) gets zeros for S^-1, nu, Gr and Kr: every column then writes a zero pair and copies the state.
+__device__ __forceinline__ void small_solve(const LinearArgs &a, double *sm, LinearSolve &sol) {
+    double Gs[14], S[4], nu[2], d2;
+    ekfm::linear_small(sm, a.H, a.z, a.R, a.wrap, Gs, S, nu);
+    const int outcome = ekfm::linear_outcome(S, nu, a.gate, d2);
+    store_pair_record(sol.rec, S, nu[0], nu[1], d2, (double)outcome);
+    pair_solve(sol, S, nu[0], nu[1], Gs, Gs + 7, sm, outcome == 1);
+}
+__device__ __forceinline__ const double *step_H(const LinearArgs &a, const LinearSolve &) { return a.H; }
+
 // The small part, by the first wavefront of a workgroup: the kLinearSmall operands one per lane (each patched entry walks the ring
-// once, on a lane of its own), then lane 0 forms S, nu, d2, the decision, S^-1, Gr and Kr.  A launch that does not apply (S irregular,
-// d2 beyond the gate) gets zeros for S^-1, nu, Gr and Kr: every column then writes a zero pair and copies the state.
-// Called by every lane of the workgroup; ends with a barrier.
-template <typename TS>
-__device__ __forceinline__ void linear_small_part(const DevState &st, const LinearArgs &a, double *sm, LinearSolve &sol) {
+// once, on a lane of its own), then lane 0's small_solve.  Called by every lane of the workgroup; ends with a barrier.
+template <typename TS, typename A, typename Solve>
+__device__ __forceinline__ void step_small_part(const DevState &st, const A &a, double *sm, Solve &sol) {
     const int tid = threadIdx.x;
     if (tid < ekfm::kLinearSmall) sm[tid] = linear_small_entry<TS>(st, a, tid);
     __syncthreads();
-    if (tid == 0) {
-        double Gs[14], S[4], nu[2], d2;
-        ekfm::linear_small(sm, a.H, a.z, a.R, a.wrap, Gs, S, nu);
-        const int outcome = ekfm::linear_outcome(S, nu, a.gate, d2);
-        store_pair_record(sol.rec, S, nu[0], nu[1], d2, (double)outcome);
-        pair_solve(sol, S, nu[0], nu[1], Gs, Gs + 7, sm, outcome == 1);
-    }
+    if (tid == 0) small_solve(a, sm, sol);
     __syncthreads();
 }
 
@@ -67,7 +75,7 @@ template <typename TS>
 __global__ __launch_bounds__(64) void k_linear_probe(DevState st, LinearArgs a, double *__restrict__ rec) {
     __shared__ double sm[ekfm::kLinearSmall];
     __shared__ LinearSolve sol;
-    linear_small_part<TS>(st, a, sm, sol);
+    step_small_part<TS>(st, a, sm, sol);
     if (threadIdx.x < kLinearRecordDoubles) rec[threadIdx.x] = sol.rec[threadIdx.x];
 }
 
@@ -75,10 +83,8 @@ __global__ __launch_bounds__(64) void k_linear_probe(DevState st, LinearArgs a, 
 // buffer st.dcur, writes the other ones whole; the small part is formed by EVERY workgroup (no workgroup reads what another one of
 // the launch writes).  rec: kLinearRecordDoubles doubles, cnt: the two counters of launches that did not apply (irregular, gated) --
 // both written by workgroup 0 (launches on one stream are ordered: a plain load, add and store).
-template <typename TS>
-__global__ __launch_bounds__(kBlock) void k_gather_linear(DevState st, LinearArgs a, double *__restrict__ rec, int64_t *__restrict__ cnt) {
-    __shared__ double sm[ekfm::kLinearSmall];
-    __shared__ LinearSolve sol;
+template <typename TS, typename A, typename Solve>
+__device__ __forceinline__ void gather_step_body(const DevState &st, const A &a, double *sm, Solve &sol, double *__restrict__ rec, int64_t *__restrict__ cnt) {
     const int tid = threadIdx.x;
     const int cur = a.cur;
     const double *__restrict__ x = st.x[cur];
@@ -100,9 +106,10 @@ __global__ __launch_bounds__(kBlock) void k_gather_linear(DevState st, LinearArg
         if (c & 1) { dgl = dg[1]; dgc = dg[2]; } else dgc = dg[0];
     }
 
-    // (2) the small part, once per workgroup
-    linear_small_part<TS>(st, a, sm, sol);
+    // (2) the small part, once per workgroup (a model: and H)
+    step_small_part<TS>(st, a, sm, sol);
     const bool ok = sol.ok != 0;
+    const double *H = step_H(a, sol);
 
     // (3) the column's share of G, K, x and the strip (the twin of pair_column.h's finish_pair_column / store_pair_column)
     const int64_t pad_end = st.tm.padded(a.n_mm);
@@ -113,10 +120,10 @@ __global__ __launch_bounds__(kBlock) void k_gather_linear(DevState st, LinearArg
     if (live) {
         if (ok) {
             // G(:, c) = Hr strip(:, c) + sum_b Hl_b P(rows of l_b, c), in this order
-            g0 = (a.H[0] * s0 + a.H[1] * s1) + a.H[2] * s2;
-            g1 = (a.H[7] * s0 + a.H[8] * s1) + a.H[9] * s2;
-            if (a.a[0] >= 0) { g0 += a.H[3] * m[0][0] + a.H[4] * m[0][1]; g1 += a.H[10] * m[0][0] + a.H[11] * m[0][1]; }
-            if (a.a[1] >= 0) { g0 += a.H[5] * m[1][0] + a.H[6] * m[1][1]; g1 += a.H[12] * m[1][0] + a.H[13] * m[1][1]; }
+            g0 = (H[0] * s0 + H[1] * s1) + H[2] * s2;
+            g1 = (H[7] * s0 + H[8] * s1) + H[9] * s2;
+            if (a.a[0] >= 0) { g0 += H[3] * m[0][0] + H[4] * m[0][1]; g1 += H[10] * m[0][0] + H[11] * m[0][1]; }
+            if (a.a[1] >= 0) { g0 += H[5] * m[1][0] + H[6] * m[1][1]; g1 += H[12] * m[1][0] + H[13] * m[1][1]; }
             k0 = g0 * sol.Si[0] + g1 * sol.Si[2];
             k1 = g0 * sol.Si[1] + g1 * sol.Si[3];
         }
@@ -157,4 +164,12 @@ __global__ __launch_bounds__(kBlock) void k_gather_linear(DevState st, LinearArg
             cnt[which] = cnt[which] + 1;
         }
     }
+}
+
+// the step with H in the argument block (model_obs.h: k_gather_model, the same body with H formed on the device)
+template <typename TS>
+__global__ __launch_bounds__(kBlock) void k_gather_linear(DevState st, LinearArgs a, double *__restrict__ rec, int64_t *__restrict__ cnt) {
+    __shared__ double sm[ekfm::kLinearSmall];
+    __shared__ LinearSolve sol;
+    gather_step_body<TS>(st, a, sm, sol, rec, cnt);
 }

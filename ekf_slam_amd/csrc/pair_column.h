@@ -1,8 +1,8 @@
 // Fragment of kernels.hip (included there, inside its anonymous namespace, after tile_access.h / lane_ops.h): what every kernel that
 // produces a rank-2 pair (K, G) does per landmark-block column once G(:, c) is known.  k_gather_constrain (constrain.h) is built from
-// it; k_gather_linear (linear_obs.h) takes the small part, the record and the robot part; the branch of k_gather that corrects nothing
-// (gather.h: gather_decided_other) the zero pair slot and the diagonal-block copy.
-// Compiles for the host too (tests/support/merge_batch_host_emulation.cpp): DevState, double2, ring_slot, rank2_apply, lane_xor1 and
+// it; gather_step_body (linear_obs.h: k_gather_linear, and model_obs.h's k_gather_model) takes the small part's solve, the record and the
+// robot part; the branch of k_gather that corrects nothing (gather.h: gather_decided_other) the zero pair slot and the diagonal-block copy.
+// Compiles for the host too (behind tests/support/kernel_host_shim.h): DevState, double2, ring_slot, rank2_apply, lane_xor1 and
 // ekfm:: functions only.
 //
 // TWINS.  The main body of k_gather (gather.h, steps (4), (4b) and the helper wavefronts' tail) and the column steps of k_gather_linear

@@ -1,6 +1,6 @@
 // Host emulation of k_append_model (tests/test_append_model_cpu.py compiles and runs it; no GPU, no HIP runtime).
 // The kernel SOURCES of ekf_slam_amd/csrc (tile_access.h, append.h, append_model.h, and pair_column.h / constrain.h / linear_obs.h for the
-// pairs that are left pending) are compiled for the host behind the shim of model_obs_host_emulation.cpp -- thread indices as globals,
+// pairs that are left pending) are compiled for the host behind kernel_host_shim.h -- thread indices as globals,
 // __shared__ as static storage, every workgroup run again until what its first lanes leave in the shared storage is there.  For tiles of
 // edge 16 and 64, double and float tiles, 0 and 3 pairs pending in the ring, and m = 1, 3, 9 entries from 123 landmarks (the columns of
 // landmark 128 start k_append_model's second workgroup and, at T = 16, a tile row):
@@ -9,59 +9,20 @@
 // must leave the tiles, the strip, x, s, both diagonal copies and the pair ring BIT FOR BIT the same, and everything below the old map
 // untouched.  Each case's live state before (the pending pairs applied to what the tiles hold) and its new rows after are written to
 // argv[1] for the dense restatement of tests/append_model_cases.py.
-// The shim's DevState / LinearArgs / AppendModelArgs mirror kernels.h (which needs the HIP headers); what append.h's k_append names
-// besides them is declared and never defined -- the template is not instantiated here.
+// What append.h's k_append names besides the argument blocks is declared and never defined -- the template is not instantiated here.
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
 #include <string>
 #include <vector>
-#include "layout.h"
-#include "device_math.h"
-struct double2 { double x, y; }; struct float2 { float x, y; }; struct float4 { float x, y, z, w; }; struct int2 { int x, y; };
-static inline double2 make_double2(double a, double b) { return {a, b}; }
-static inline float4 make_float4(float a, float b, float c, float d) { return {a, b, c, d}; }
-#define __device__
-#define __global__
-#define __forceinline__ inline
-#define __restrict__
-#define __launch_bounds__(x)
-#define __shared__ static
-static inline void __syncthreads() {}
-struct Idx { unsigned x; };
-static Idx threadIdx, blockIdx;
-constexpr int kBlock = 256;
-static inline int ring_slot(int pstart, int i, int pcap) { const int s = pstart + i; return s >= pcap ? s - pcap : s; }
-static int xor_pass; static std::vector<double> xor_rec[kBlock]; static size_t xor_pos[kBlock];
-static inline double lane_xor1(double v) {
-    const unsigned t = threadIdx.x;
-    if (xor_pass == 0) { xor_rec[t].push_back(v); return 0.0; }
-    return xor_rec[t ^ 1][xor_pos[t]++];
-}
-struct DevState { double *x[2], *prr[2], *strip[2]; void *tiles; double *s, *Gp, *Kp; float *Gp32, *Kp32; int64_t pair_stride; int32_t pcap;
-                  double *small; int64_t ldm; TileMap tm; double *diag[2]; int32_t dcur; };
-struct ConstrainArgs { double d0, d1, R00, R01, R10, R11; int64_t ai, aj, n_mm; int32_t cur, npend, pstart; };
-struct LinearArgs { double z[2], R[4], H[14], gate; int64_t a[2], n_mm; int32_t wrap[2], cur, npend, pstart; };
-constexpr int kConstrainRecordDoubles = 8, kLinearRecordDoubles = 8;
-constexpr int kAppendModelMax = 32;
-struct AppendModelEntry { double z0, z1, R00, R01, R10, R11, signature; int32_t model, pad; };
-struct AppendModelArgs { int64_t N; int32_t m, cur; AppendModelEntry e[kAppendModelMax]; };
+#include "kernel_host_shim.h"
 // what k_append (append.h) names: declared, never defined
-struct PredictArgs { double u0, u1, C; int64_t n_mm; int32_t cur; };
-struct AppendArgs { double u0, u1, R00, R01, R10, R11, pos0, pos1, signature; int64_t N; int32_t cur; };
-struct AssocHostPartial;
-struct DevLoopArgs { const AssocHostPartial *parts_in; AssocHostPartial *rec; int32_t nblk_in, seq_in, seq_rec; };
 struct PredictSmall { double fa, fb; double pose[3]; double prr[9]; double Q[9]; };
 void predict_small(const double pose[3], const double prr_in[9], double u0, double u1, double C, PredictSmall &o);
 void predict_strip(double &s0, double &s1, double s2, double fa, double fb);
 void reduce_partials_wave(const AssocHostPartial *parts, int nblk, int seq, int lane, double &ll, int &ix);
 void store_partial(AssocHostPartial *dst, double ll, int index, int seq);
-template <typename TS> struct Lane16;
-template <> struct Lane16<double> { using type = double2; static constexpr int kCols = 2; };
-template <> struct Lane16<float>  { using type = float4;  static constexpr int kCols = 4; };
-static inline void lane16_pack(const double *v, double2 &t) { t.x = v[0]; t.y = v[1]; }
-static inline void lane16_pack(const double *v, float4 &t) { t.x = (float)v[0]; t.y = (float)v[1]; t.z = (float)v[2]; t.w = (float)v[3]; }
 #include "tile_access.h"
 #include "append.h"
 #include "append_model.h"
@@ -69,18 +30,6 @@ static inline void lane16_pack(const double *v, float4 &t) { t.x = (float)v[0]; 
 #include "constrain.h"
 #include "linear_obs.h"
 
-// k_gather_linear: every workgroup three times (model_obs_host_emulation.cpp: the operands, the shared solve and lane_xor1's partners, the launch)
-template <typename F> static void launch_wg3(int grid, int64_t *cnt, F body) {
-    for (int b = 0; b < grid; ++b) {
-        const int64_t c0 = cnt[0], c1 = cnt[1];
-        for (int pass = 0; pass < 3; ++pass) {
-            xor_pass = pass == 2;
-            if (pass < 2) for (int t = 0; t < kBlock; ++t) { xor_rec[t].clear(); xor_pos[t] = 0; }
-            cnt[0] = c0; cnt[1] = c1;
-            for (int t = 0; t < kBlock; ++t) { blockIdx.x = b; threadIdx.x = t; body(); }
-        }
-    }
-}
 // k_append_model: every workgroup twice -- the first run leaves t, dg/dtheta and Gz R Gz' of every entry in the shared storage, the second
 // one is the launch (it rewrites every slot the first one wrote; no lane reads a slot the launch writes)
 template <typename F> static void launch_wg2(int grid, F body) {

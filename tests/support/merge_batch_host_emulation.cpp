@@ -1,47 +1,16 @@
 // Host emulation of the batch-fusion kernels (tests/test_merge_batch_cpu.py compiles and runs it; no GPU, no HIP runtime).
-// The kernel SOURCES of ekf_slam_amd/csrc (pair_column.h, constrain.h, compact.h, merge_pass.h, tile_access.h) are compiled for the host behind a
-// small shim -- thread indices as globals, __shared__ as static storage with thread 0 of a workgroup run first, lane_xor1 in two
+// The kernel SOURCES of ekf_slam_amd/csrc (pair_column.h, constrain.h, compact.h, merge_pass.h, tile_access.h) are compiled for the host behind
+// kernel_host_shim.h -- thread indices as globals, __shared__ as static storage with thread 0 of a workgroup run first, lane_xor1 in two
 // passes -- and two routes are compared BIT FOR BIT on the same state:
 //   the batch:    m x k_gather_constrain with a record (earlier pairs pending in the ring), then k_merge_pass
 //   the sequence: m x (k_gather_constrain with npend = 0 and no record, the one-pair pass as a plain rank2_apply loop), then k_compact_tiles
-// both followed by k_compact_state.  The shim's DevState / ConstrainArgs mirror kernels.h (which needs the HIP headers).
+// both followed by k_compact_state.
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
 #include <vector>
-#include "layout.h"
-#include "device_math.h"
-struct double2 { double x, y; }; struct float2 { float x, y; }; struct float4 { float x, y, z, w; }; struct int2 { int x, y; };
-static inline double2 make_double2(double a, double b) { return {a, b}; }
-static inline float4 make_float4(float a, float b, float c, float d) { return {a, b, c, d}; }
-#define __device__
-#define __global__
-#define __forceinline__ inline
-#define __restrict__
-#define __launch_bounds__(x)
-#define __shared__ static
-static inline void __syncthreads() {}
-struct Idx { unsigned x; };
-static Idx threadIdx, blockIdx;
-constexpr int kBlock = 256;
-static inline int ring_slot(int pstart, int i, int pcap) { const int s = pstart + i; return s >= pcap ? s - pcap : s; }
-// lane_xor1: two passes per workgroup -- the first records what every lane hands over, the second returns the partner's
-static int xor_pass; static std::vector<double> xor_rec[kBlock]; static size_t xor_pos[kBlock];
-static inline double lane_xor1(double v) {
-    const unsigned t = threadIdx.x;
-    if (xor_pass == 0) { xor_rec[t].push_back(v); return 0.0; }
-    return xor_rec[t ^ 1][xor_pos[t]++];
-}
-struct DevState { double *x[2], *prr[2], *strip[2]; void *tiles; double *s, *Gp, *Kp; float *Gp32, *Kp32; int64_t pair_stride; int32_t pcap;
-                  double *small; int64_t ldm; TileMap tm; double *diag[2]; int32_t dcur; };
-struct ConstrainArgs { double d0, d1, R00, R01, R10, R11; int64_t ai, aj, n_mm; int32_t cur, npend, pstart; };
-constexpr int kConstrainRecordDoubles = 8;
-template <typename TS> struct Lane16;
-template <> struct Lane16<double> { using type = double2; static constexpr int kCols = 2; };
-template <> struct Lane16<float>  { using type = float4;  static constexpr int kCols = 4; };
-static inline void lane16_pack(const double *v, double2 &t) { t.x = v[0]; t.y = v[1]; }
-static inline void lane16_pack(const double *v, float4 &t) { t.x = (float)v[0]; t.y = (float)v[1]; t.z = (float)v[2]; t.w = (float)v[3]; }
+#include "kernel_host_shim.h"
 #include "tile_access.h"
 #include "compact.h"
 #include "pair_column.h"

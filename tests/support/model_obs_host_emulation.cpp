@@ -1,71 +1,24 @@
 // Host emulation of the model-observation kernels (tests/test_model_obs_cpu.py compiles and runs it; no GPU, no HIP runtime).
 // The kernel SOURCES of ekf_slam_amd/csrc (tile_access.h, pair_column.h, constrain.h, linear_obs.h, model_obs.h) are compiled for the host
-// behind the shim of merge_batch_host_emulation.cpp -- thread indices as globals, __shared__ as static storage, every workgroup run
+// behind kernel_host_shim.h -- thread indices as globals, __shared__ as static storage, every workgroup run
 // again until the small part's operands and lane_xor1's partners are there -- and two routes are compared BIT FOR BIT on
 // the same state, with 0 and with 3 pairs pending in the ring:
 //   the model:   k_gather_model, which forms H on its lane 0
 //   the twin:    k_gather_linear handed the H that ekfm::model_eval gives the host at the same x, and a z that yields the same nu
 // in the pair (G, K), the strip, Prr and the diagonal blocks; x to rounding; the record's S and outcome; k_model_probe's record against
 // the launch's.  A target on the robot must leave a zero pair, the state copied and one count.
-// The shim's DevState / LinearArgs / ModelArgs mirror kernels.h (which needs the HIP headers).
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
 #include <vector>
-#include "layout.h"
-#include "device_math.h"
-struct double2 { double x, y; }; struct float2 { float x, y; }; struct float4 { float x, y, z, w; }; struct int2 { int x, y; };
-static inline double2 make_double2(double a, double b) { return {a, b}; }
-static inline float4 make_float4(float a, float b, float c, float d) { return {a, b, c, d}; }
-#define __device__
-#define __global__
-#define __forceinline__ inline
-#define __restrict__
-#define __launch_bounds__(x)
-#define __shared__ static
-static inline void __syncthreads() {}
-struct Idx { unsigned x; };
-static Idx threadIdx, blockIdx;
-constexpr int kBlock = 256;
-static inline int ring_slot(int pstart, int i, int pcap) { const int s = pstart + i; return s >= pcap ? s - pcap : s; }
-static int xor_pass; static std::vector<double> xor_rec[kBlock]; static size_t xor_pos[kBlock];
-static inline double lane_xor1(double v) {
-    const unsigned t = threadIdx.x;
-    if (xor_pass == 0) { xor_rec[t].push_back(v); return 0.0; }
-    return xor_rec[t ^ 1][xor_pos[t]++];
-}
-struct DevState { double *x[2], *prr[2], *strip[2]; void *tiles; double *s, *Gp, *Kp; float *Gp32, *Kp32; int64_t pair_stride; int32_t pcap;
-                  double *small; int64_t ldm; TileMap tm; double *diag[2]; int32_t dcur; };
-struct ConstrainArgs { double d0, d1, R00, R01, R10, R11; int64_t ai, aj, n_mm; int32_t cur, npend, pstart; };
-struct LinearArgs { double z[2], R[4], H[14], gate; int64_t a[2], n_mm; int32_t wrap[2], cur, npend, pstart; };
-struct ModelArgs { double z[2], R[4], anchor[2], gate; int64_t a[2], n_mm; int32_t model, cur, npend, pstart; };
-constexpr int kConstrainRecordDoubles = 8, kLinearRecordDoubles = 8;
-template <typename TS> struct Lane16;
-template <> struct Lane16<double> { using type = double2; static constexpr int kCols = 2; };
-template <> struct Lane16<float>  { using type = float4;  static constexpr int kCols = 4; };
-static inline void lane16_pack(const double *v, double2 &t) { t.x = v[0]; t.y = v[1]; }
-static inline void lane16_pack(const double *v, float4 &t) { t.x = (float)v[0]; t.y = (float)v[1]; t.z = (float)v[2]; t.w = (float)v[3]; }
+#include "kernel_host_shim.h"
 #include "tile_access.h"
 #include "pair_column.h"
 #include "constrain.h"
 #include "linear_obs.h"
 #include "model_obs.h"
 
-// every workgroup three times: the first pass leaves the small part's operands in the shared storage, the second one has lane 0 form the
-// shared solve (and k_gather_model's H) from them and records what lane_xor1 hands over, the third one is the launch; what the earlier
-// passes counted is dropped
-template <typename F> static void launch_wg(int grid, int64_t *cnt, F body) {
-    for (int b = 0; b < grid; ++b) {
-        const int64_t c0 = cnt[0], c1 = cnt[1];
-        for (int pass = 0; pass < 3; ++pass) {
-            xor_pass = pass == 2;
-            if (pass < 2) for (int t = 0; t < kBlock; ++t) { xor_rec[t].clear(); xor_pos[t] = 0; }
-            cnt[0] = c0; cnt[1] = c1;
-            for (int t = 0; t < kBlock; ++t) { blockIdx.x = b; threadIdx.x = t; body(); }
-        }
-    }
-}
 struct Store {
     int T, N, ldm, nt_cap; TileMap tm; int64_t slots;
     std::vector<double> x[2], prr[2], strip[2], diag[2], ring, tiles; int cur = 0, dcur = 0;
@@ -108,7 +61,7 @@ static void fill(Store &S) {            // P = D + U U' (k = 3), x random; tiles
 static void run_linear(Store &S, LinearArgs a, double *rec, int64_t *cnt) {
     a.n_mm = 2 * S.N; a.cur = S.cur; a.pstart = 0;
     DevState st = S.st;
-    launch_wg(S.grid(), cnt, [&] { k_gather_linear<double>(st, a, rec, cnt); });
+    launch_wg3(S.grid(), cnt, [&] { k_gather_linear<double>(st, a, rec, cnt); });
     S.flip();
 }
 static int differ(const std::vector<double> &u, const std::vector<double> &v, const char *what) {
@@ -172,7 +125,7 @@ int main() {
             DevState stA = A.st;
             for (int t = 0; t < 64; ++t) { blockIdx.x = 0; threadIdx.x = t; k_model_probe<double>(stA, m, recP); }      // (pass 0: the operands)
             for (int t = 0; t < 64; ++t) { blockIdx.x = 0; threadIdx.x = t; k_model_probe<double>(stA, m, recP); }
-            launch_wg(A.grid(), cntA, [&] { k_gather_model<double>(stA, m, recA, cntA); });
+            launch_wg3(A.grid(), cntA, [&] { k_gather_model<double>(stA, m, recA, cntA); });
             A.flip();
             int bad = 0;
             if (memcmp(recA, recP, sizeof recA)) { printf("  the probe's record differs from the launch's\n"); ++bad; }
