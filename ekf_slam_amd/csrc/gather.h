@@ -17,16 +17,48 @@ constexpr int kGatherBlock = kGatherCols + 3 * 64;
 constexpr int kFuseMaxRows = 48;                     // landmark-block rows (24 landmarks) up to which the fused form is used (beyond: slower than two launches)
 constexpr int kFuseElems = kFuseMaxRows * kFuseMaxRows / 256;     // elements of the block per column lane, all in flight together
 
-// kDecide (cfg.device_assoc == 4, with kDev): the device takes the BRANCH as well.  The landmark count is the device's (DevLoopArgs::dn_in,
-// a ring slot; the grid was sized from the host's upper bound); winners that name a landmark -> the correction below, over that
-// extent; nothing below the threshold -> the append of EKF_SLAM_UC.m:121-123 (gather_decided_other); stale winner entries ->
-// nothing is applied.  Every branch leaves the state in the other buffers, writes this launch's pair slot (zeros when nothing was
-// corrected: an exact no-op for every pass and patch), stores the count it leaves to dn_out and evaluates the next observation's
-// association on the state it leaves.
+// The PHASES of k_gather: what a wavefront computes between two points of the schedule.  No phase holds a barrier, a wait on an LDS flag
+// or a stamp: those are k_gather's own body, which calls the phases in program order.
+
+// clock64() stamps of the probe builds (Makefile: stamps; scripts/probe_gather_*.py read them through the Q slots); empty in the product
+struct GatherStamps {
+#ifdef EKF_GATHER_STAMPS
+    long long t[12]; int n = 0;
+    __device__ __forceinline__ void mark() { t[n++] = clock64(); }
+#else
+    __device__ __forceinline__ void mark() {}
+#endif
+};
+// The 24 operands of solve_small for landmark k = c / 2, on its even column lane (the *_o values: the odd partner's, by lane_xor1):
+// Prr (0..8) | strip(t, 2k), strip(t, 2k+1) for t = 0..2 (9..14) | the landmark's 2x2 block, row-major with both mirrors (15..18) |
+// the pose (19..21) | the landmark (22, 23)
+__device__ __forceinline__ void pack_assoc_operands(double (&q)[24], const double (&prr)[9], const double (&pose)[3], double t0, double t0_o, double t1,
+                                                    double t1_o, double t2, double t2_o, double d00, double d10, double d11, double xn, double xn_o) {
+#pragma unroll
+    for (int i = 0; i < 9; ++i) q[i] = prr[i];
+    q[9] = t0; q[10] = t0_o; q[11] = t1; q[12] = t1_o; q[13] = t2; q[14] = t2_o;
+    q[15] = d00; q[16] = d10; q[17] = d10; q[18] = d11;
+    q[19] = pose[0]; q[20] = pose[1]; q[21] = pose[2];
+    q[22] = xn; q[23] = xn_o;
+}
+
+// ======== kDecide (cfg.device_assoc == 4, with kDev): the branches that correct nothing
+// The device takes the BRANCH as well.  The landmark count is the device's (DevLoopArgs::dn_in, a ring slot; the grid was sized from
+// the host's upper bound); winners that name a landmark -> the correction of k_gather's main body, over that extent; nothing below
+// the threshold -> the append of EKF_SLAM_UC.m:121-123 (here); stale winner entries -> nothing is applied.  Every branch leaves the
+// state in the other buffers, writes this launch's pair slot (zeros when nothing was corrected: an exact no-op for every pass and
+// patch), stores the count it leaves to dn_out and evaluates the next observation's association on the state it leaves.
+// `code`: the winner (-1 nothing passed the threshold, -2 stale entries) or -3, an earlier row of this scan failed its lookup.
 template <typename TS>
-__device__ __forceinline__ void gather_decided_other(const DevState &st, const CorrectArgs &a, const DevLoopArgs &dl, int64_t Nd,
-                                                     bool append) {
+__device__ __forceinline__ void gather_decided_other(const DevState &st, const CorrectArgs &a, const DevLoopArgs &dl, int64_t Nd, int code,
+                                                     double dll) {
     const int tid = threadIdx.x;
+    if (code == -1 && *(const volatile double *)(dl.loc + 3 * (Nd - dl.loc_base) + 2) != 1.0) {
+        code = -4;                                        // the key of the append matched no entry or several
+        if (blockIdx.x == 0 && tid == kGatherCols + 64) *(volatile int32_t *)dl.abort = dl.scan_id;
+    }
+    if (blockIdx.x == 0 && tid == kGatherCols + 128) store_partial(dl.rec, dll, code, dl.seq_rec);
+    const bool append = code == -1;
     if (tid >= kGatherCols) return;                       // the helper wavefronts have no part here (a barrier counts live wavefronts)
     const int cur = a.cur;
     const double *__restrict__ x = st.x[cur];
@@ -97,12 +129,7 @@ __device__ __forceinline__ void gather_decided_other(const DevState &st, const C
     if (live && !odd) {
         const int64_t k = c >> 1;
         double q[24];
-#pragma unroll
-        for (int i = 0; i < 9; ++i) q[i] = pr[i];
-        q[9] = t0; q[10] = t0_o; q[11] = t1; q[12] = t1_o; q[13] = t2; q[14] = t2_o;
-        q[15] = dgc; q[16] = d10; q[17] = d10; q[18] = d11;
-        q[19] = pose[0]; q[20] = pose[1]; q[21] = pose[2];
-        q[22] = xn; q[23] = xn_o;
+        pack_assoc_operands(q, pr, pose, t0, t0_o, t1, t1_o, t2, t2_o, dgc, d10, d11, xn, xn_o);
         SmallSolve so;
         solve_small(q, dl.z0, dl.z1, dl.R00, dl.R01, dl.R10, dl.R11, so);
         double pc, sc;
@@ -112,12 +139,154 @@ __device__ __forceinline__ void gather_decided_other(const DevState &st, const C
     columns_argmin_store<kGatherCols / 64>(ll, ix, dl.parts_out + blockIdx.x, dl.seq_out);
 }
 
-// kDev (device-resident measure loop): the corrected landmark is not a kernel argument but the arg-min over the
-// per-workgroup winners of this observation's association (dl.parts_in), reduced redundantly by every wavefront; and the NEXT
-// observation's association (Correspondence.m:49-87: per-landmark phi_k, Mahalanobis + signature cost, thresholded arg-min) is
-// evaluated in the epilogue by the column lanes, from the values this correction has just produced -- x', strip', Prr', the
-// landmark's own 2x2 block (its live F64 copy, to which the lanes have just applied this correction's pair) -- with the per-entry
-// functions k_associate uses: one launch per observation instead of two.
+// ======== helper wavefronts
+// BEARING: nu = z - z_k, z_k = [sqrt(q); wrapTo360(atan2d(dy,dx) - heading)]  (EKF_SLAM.m:125-130,144), from the PREDICTED pose when
+// predict is folded in -- same expressions as the chain wavefront's, so the same bits
+template <bool kPredict>
+__device__ __forceinline__ void bearing_innovation(double small_v, int lane, const CorrectArgs &a, const PredictArgs &pa, SmallSolve &sol) {
+    const double bx = lane_bcast(small_v, 0), by = lane_bcast(small_v, 1), bth = lane_bcast(small_v, 2),
+                 blx = lane_bcast(small_v, 3), bly = lane_bcast(small_v, 4);
+    if (lane == 0) {
+        double pose[3] = { bx, by, bth };
+        if (kPredict) {
+            const double2 sc2 = sincosd_ni(pose[2] + pa.u1);
+            const double sn2 = sc2.x, cs2 = sc2.y;
+            const double p0 = predict_pose_entry(pose, 0, pa.u0, pa.u1, sn2, cs2), p1 = predict_pose_entry(pose, 1, pa.u0, pa.u1, sn2, cs2),
+                         p2 = predict_pose_entry(pose, 2, pa.u0, pa.u1, sn2, cs2);
+            pose[0] = p0; pose[1] = p1; pose[2] = p2;
+        }
+        const double d0 = blx - pose[0], d1 = bly - pose[1];
+        const double bearing = bearing_ni(d1, d0, pose[2]);
+        const double sq = sqrt(d0 * d0 + d1 * d1);
+        sol.nu[0] = a.z0 - sq;                                    // :144 (bearing NOT wrapped)
+        sol.nu[1] = a.z1 - bearing;
+    }
+}
+// CHAIN, once the landmark's 2x2 block is in pss[15..18]: G(:,S) and phi, one entry per lane (EKF_SLAM.m:141); inv(phi) by every lane (:143)
+__device__ __forceinline__ void chain_solve(const double *pss, double R00, double R01, double R10, double R11, int lane, SmallSolve &so,
+                                            double (&GS)[2][5]) {
+    const int ra = lane >= 5 ? 1 : 0;                         // row of this lane's G(:,S) entry
+    double hsel[5];
+#pragma unroll
+    for (int t = 0; t < 5; ++t) hsel[t] = ra ? so.Hs[1][t] : so.Hs[0][t];
+    const double e_gs = solve_gs_entry(pss, hsel, lane < 10 ? lane - 5 * ra : 0);
+#pragma unroll
+    for (int i = 0; i < 10; ++i) GS[i / 5][i % 5] = lane_bcast(e_gs, i);
+    double e_phi;
+    {
+        const int aa = (lane >> 1) & 1, bb = lane & 1;
+        double gsel[5], hb[5];
+#pragma unroll
+        for (int t = 0; t < 5; ++t) { gsel[t] = aa ? GS[1][t] : GS[0][t]; hb[t] = bb ? so.Hs[1][t] : so.Hs[0][t]; }
+        const double Rab = aa == 0 ? (bb == 0 ? R00 : R01) : (bb == 0 ? R10 : R11);
+        e_phi = solve_phi_entry(gsel, hb, Rab);                                      // :141
+    }
+    const double phi[4] = { lane_bcast(e_phi, 0), lane_bcast(e_phi, 1), lane_bcast(e_phi, 2), lane_bcast(e_phi, 3) };
+    ekfm::inv2(phi, so.Phi);                                  // :143 phi_k^-1 (every lane, redundantly)
+}
+// CHAIN publishes the solve: K_r and G_r are formed by every lane (18 operations, static indices, no divergent branches -- the per-lane
+// form with its select chains was 200 instructions), then lane 0 stores the whole struct; nu is BEARING's
+__device__ __forceinline__ void chain_publish(SmallSolve &so, const double (&GS)[2][5], int lane, SmallSolve &sol) {
+#pragma unroll
+    for (int b = 0; b < 3; ++b) {
+        so.Gr[0][b] = GS[0][b]; so.Gr[1][b] = GS[1][b];
+#pragma unroll
+        for (int cc = 0; cc < 2; ++cc) so.Kr[b][cc] = solve_kr_entry(GS[0][b], GS[1][b], so.Phi[cc], so.Phi[2 + cc]);
+    }
+    if (lane == 0) {
+#pragma unroll
+        for (int i = 0; i < 10; ++i) sol.Hs[i / 5][i % 5] = so.Hs[i / 5][i % 5];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) sol.Phi[i] = so.Phi[i];
+#pragma unroll
+        for (int i = 0; i < 6; ++i) { sol.Kr[i / 2][i % 2] = so.Kr[i / 2][i % 2]; sol.Gr[i / 3][i % 3] = so.Gr[i / 3][i % 3]; }
+    }
+}
+
+// ======== column lanes
+// (2b) this column's operands of the first kPre pending pairs (G_i(:,c) left of j, K_i(c,:) right of it), all in flight together.
+// Unconditional, clamped addresses (a predicated form lets the compiler sink the loads below the barrier, next to their use); slots
+// past npend repeat the last pending one (cache hits), c is clamped into the padded vector.  One uniform base (Gp; Kp follows it in
+// the same allocation, host/passes.h: create_passes) + a 32-bit per-lane element offset: the compiler can then use the scalar-base
+// addressing form and the loads cost one scalar add each.  Groups of 8 are skipped when no pending pair falls into them (immediate
+// mode, the start of every batch); the group test uses npre_ld, k_gather's OPAQUE copy of npre.
+template <int kPre>
+__device__ __forceinline__ void prefetch_pending(double2 (&pre)[kPre], const DevState &st, int64_t c, int64_t pad_cols, bool rowpart, int pstart,
+                                                 int64_t ps2, int npre, int npre_ld) {
+    const uint32_t cc = (uint32_t)(c < pad_cols ? c : pad_cols - 1);
+    const uint32_t krel = (uint32_t)((st.Kp - st.Gp) >> 1);
+    const uint32_t lane_off = cc + (rowpart ? 0u : krel);
+    const char *__restrict__ ub = reinterpret_cast<const char *>(st.Gp);
+    const uint32_t lane_bytes = lane_off * 16u;
+    // slot offsets advance incrementally around the ring (scalar unit: one add, one wrap test per pair)
+    // (32-bit: 2 * pcap * pair_stride / 2 <= 256 * 2 * capacity elements of 16 bytes stays far below 2^32)
+    const uint32_t step = (uint32_t)ps2, wrap = (uint32_t)st.pcap * step;
+    uint32_t off = (uint32_t)pstart * step;
+#pragma unroll
+    for (int g0 = 0; g0 < kPre; g0 += 8) {
+        if (g0 < npre_ld) {
+#pragma unroll
+            for (int t = 0; t < 8; ++t) {
+                pre[g0 + t] = *reinterpret_cast<const double2 *>(ub + (uint64_t)off * 16u + lane_bytes);
+                if (g0 + t + 1 < npre) { off += step; if (off == wrap) off = 0; }
+            }
+        }
+    }
+}
+// (3) the pending pairs on this lane's two row entries, in slot order.  kRow: the column lies left of j, the entries are P(j, c),
+// P(j+1, c) = P(c, j)', patched with K_i(j,:), K_i(j+1,:) (uniform, from `upatch`) and the lane's G_i(:, c); otherwise right of
+// j+1: P(c, j), P(c, j+1) with the lane's K_i(c,:) and the uniform G_i(:,j), G_i(:,j+1).  The first npre pairs are in `pre`
+// (groups of 8, uniform test; inside a group no branches: select); beyond kPre pending pairs (async flush, batch > kPre) chunks of 8
+// independent loads applied in order, then singles.
+template <bool kRow, int kPre>
+__device__ __forceinline__ void apply_pending_column(double &m0, double &m1, const double2 (&pre)[kPre], const double2 *upatch, const double *ring,
+                                                     int64_t c, int npre, int npend, int pstart, int pcap, int64_t ps2) {
+    constexpr int u0 = kRow ? 0 : 2, u1 = u0 + 1;
+    auto apply = [](double m, const double2 &uni, const double2 &own) { return kRow ? rank2_apply(m, uni, own) : rank2_apply(m, own, uni); };
+#pragma unroll
+    for (int g0 = 0; g0 < kPre; g0 += 8)
+        if (g0 < npre) {
+            double2 ua[8], ub[8];
+#pragma unroll
+            for (int t = 0; t < 8; ++t) { ua[t] = upatch[4 * (g0 + t) + u0]; ub[t] = upatch[4 * (g0 + t) + u1]; }
+#pragma unroll
+            for (int t = 0; t < 8; ++t) {
+                const double v0 = apply(m0, ua[t], pre[g0 + t]), v1 = apply(m1, ub[t], pre[g0 + t]);
+                m0 = g0 + t < npre ? v0 : m0; m1 = g0 + t < npre ? v1 : m1;
+            }
+        }
+    const double2 *__restrict__ rp = reinterpret_cast<const double2 *>(ring) + c;
+    int i = npre;
+    for (; i + 8 <= npend; i += 8) {
+        double2 own[8];
+#pragma unroll
+        for (int q = 0; q < 8; ++q) own[q] = rp[(int64_t)ring_slot(pstart, i + q, pcap) * ps2];
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+            m0 = apply(m0, upatch[4 * (i + q) + u0], own[q]);
+            m1 = apply(m1, upatch[4 * (i + q) + u1], own[q]);
+        }
+    }
+    for (; i < npend; ++i) {
+        const double2 own = rp[(int64_t)ring_slot(pstart, i, pcap) * ps2];
+        m0 = apply(m0, upatch[4 * i + u0], own);
+        m1 = apply(m1, upatch[4 * i + u1], own);
+    }
+}
+// c == j + 1: canonical (j+1,j) and (j+1,j+1), every operand uniform
+__device__ __forceinline__ void apply_pending_corner(double &m0, double &m1, const double2 *upatch, int npend) {
+    for (int i = 0; i < npend; ++i) {
+        m0 = rank2_apply(m0, upatch[4 * i + 1], upatch[4 * i + 2]);
+        m1 = rank2_apply(m1, upatch[4 * i + 1], upatch[4 * i + 3]);
+    }
+}
+
+// The SCHEDULE of one correction: which wavefront requests what, and in what order, around barrier 0, the two LDS flags and barrier B.
+// Every barrier, flag wait, scheduling fence and stamp is here, in program order; the phases above sit between them.
+// kDev (device-resident measure loop): the corrected landmark is not a kernel argument but the arg-min over the per-workgroup winners
+// of this observation's association (dl.parts_in), reduced redundantly by every wavefront; and the NEXT observation's association
+// (Correspondence.m:49-87) is evaluated in the epilogue by the column lanes, from the values this correction has just produced, with
+// the per-entry functions k_associate uses: one launch per observation instead of two.  kDecide: gather_decided_other.
 template <typename TS, bool kSharded, bool kPredict, bool kFused = false, bool kDev = false, bool kDecide = false>
 __global__ __launch_bounds__(kGatherBlock) void k_gather(DevState st, CorrectArgs a, PanelView pv, PredictArgs pa,
                                                          typename DevLoopParam<kDev>::type dl) {
@@ -148,8 +317,8 @@ __global__ __launch_bounds__(kGatherBlock) void k_gather(DevState st, CorrectArg
     const int64_t ldm = st.ldm;
     const int npend = a.npend, pstart = a.pstart;
     if constexpr (kDev) {
-        // EKF_SLAM_UC.m:119-125: idx comes from the association, on the device.  Every wavefront reduces the winners itself
-        // (<= 64 entries: one 16-byte load per lane + a butterfly) -- no LDS, no barrier in front of the j-dependent loads.
+        // The landmark of the launch.  EKF_SLAM_UC.m:119-125: idx comes from the association, on the device.  Every wavefront reduces
+        // the winners itself (<= 64 entries: one 16-byte load per lane + a butterfly) -- no LDS, no barrier in front of the j-dependent loads.
         double dll;
         int dix;
         reduce_partials_wave(dl.parts_in, dl.nblk_in, dl.seq_in, lane, dll, dix);
@@ -158,14 +327,8 @@ __global__ __launch_bounds__(kGatherBlock) void k_gather(DevState st, CorrectArg
             const int64_t Nd = dl.n_known >= 0 ? dl.n_known : *dl.dn_in;        // the device's landmark count (a.n_mm: the host's bound)
             a.n_mm = 2 * Nd;
             const bool stopped = *(volatile int32_t *)dl.abort == dl.scan_id;   // an earlier row of this scan failed its lookup
-            if (stopped || !(dix >= 0 && (int64_t)dix < Nd)) {
-                int code = stopped ? -3 : dix;
-                if (code == -1 && *(const volatile double *)(dl.loc + 3 * (Nd - dl.loc_base) + 2) != 1.0) {
-                    code = -4;                                                    // the key of the append matched no entry or several
-                    if (blockIdx.x == 0 && tid == kGatherCols + 64) *(volatile int32_t *)dl.abort = dl.scan_id;
-                }
-                if (blockIdx.x == 0 && tid == kGatherCols + 128) store_partial(dl.rec, dll, code, dl.seq_rec);
-                gather_decided_other<TS>(st, a, dl, Nd, code == -1);
+            if (stopped || !(dix >= 0 && (int64_t)dix < Nd)) {                  // nothing to correct: append or leave, and the launch is over
+                gather_decided_other<TS>(st, a, dl, Nd, stopped ? -3 : dix, dll);
                 return;
             }
             if (blockIdx.x == 0 && tid == kGatherCols + 64) *dl.dn_out = Nd;
@@ -185,24 +348,18 @@ __global__ __launch_bounds__(kGatherBlock) void k_gather(DevState st, CorrectArg
                      "s"(a.pstart));
     }
     const bool do_patch = !kSharded || !pv.patched;       // base values in hand: apply the pending pairs here
-#ifdef EKF_GATHER_STAMPS
-    long long stamp[12]; int nst = 0;
-#define EKF_STAMP() do { stamp[nst++] = clock64(); } while (0)
-    EKF_STAMP();
-#else
-#define EKF_STAMP() do { } while (0)
-#endif
-
+    GatherStamps stamps;                                  // EKF_STAMP sites: stamps.mark(), an empty call in the product
+    stamps.mark();
     if (role >= 4) {
         // =========================================== helper wavefronts ===========================================
-        // (1h) the small operands, one per lane: the CHAIN wavefront takes what the previous kernel wrote a moment ago (robot block,
-        //      strip columns j, j+1, pose, landmark: 20 doubles, cache-resident), the DIAG wavefront the landmark's own 2x2 block
-        //      (the live F64 copy) -- two wavefronts, two load queues, so the chain's sincos starts when the
-        //      POSE has arrived, not when the slowest of 24 loads has (vector-memory results return in order per wavefront).
-        //      Unconditional selected addresses, see the column path.
         // Synchronisation: ONE early hardware barrier ("0", right after everyone has REQUESTED its loads, so that the two LDS flags
         // below are known to be reset) and one at the end ("B").  In between the wavefronts meet through LDS flags only, each waiting
         // for exactly what it needs: CHAIN, BEARING and DIAG for their own loads.
+        // (1h) the small operands, one per lane: the CHAIN wavefront takes what the previous kernel wrote a moment ago (robot block,
+        //      strip columns j, j+1, pose, landmark: 20 doubles, cache-resident), the DIAG wavefront the landmark's own 2x2 block (the
+        //      live F64 copy) -- two wavefronts, two load queues, so the chain's
+        //      sincos starts when the POSE has arrived, not when the slowest of 24 loads has (vector-memory results return in order
+        //      per wavefront).  Unconditional selected addresses, see the column path.
         double small_v = 0.0;
         if (role == 4) {
             const double *sp = prr_cur;                                  // idle lanes re-read Prr(1,1), unused
@@ -223,42 +380,23 @@ __global__ __launch_bounds__(kGatherBlock) void k_gather(DevState st, CorrectArg
         }
         __builtin_amdgcn_sched_barrier(0);
         asm volatile("s_barrier" ::: "memory");                       // barrier 0: no waitcnt -- the loads stay in flight across it
-        EKF_STAMP();                                                  // 1
+        stamps.mark();                                               // 1
         if (role == 4 && (lane < 15 || (lane >= 19 && lane < 24))) pss[lane] = small_v;      // (the column lanes read these after B)
         if (role == 5 && lane < 4) pss[15 + lane] = small_v;
-        EKF_STAMP();                                                  // 2: own operands arrived
+        stamps.mark();                                               // 2: own operands arrived
         if (role == 5) {
             // ---- DIAG: the block is in pss[15..18] (written above): tell the CHAIN wavefront
             wave_lds_sync();
             if (lane == 0) *(volatile int *)&diag_ready = 1;              // (one wavefront: LDS order = program order)
-            EKF_STAMP();                                                  // (probe, DIAG view) flag set
+            stamps.mark();                                               // (probe, DIAG view) flag set
         } else if (role == 6) {
-            // ---- BEARING: nu = z - z_k, z_k = [sqrt(q); wrapTo360(atan2d(dy,dx) - heading)]  (EKF_SLAM.m:125-130,144), from the
-            //      PREDICTED pose when predict is folded in -- same expressions as the chain wavefront's, so the same bits
-            const double bx = lane_bcast(small_v, 0), by = lane_bcast(small_v, 1), bth = lane_bcast(small_v, 2),
-                         blx = lane_bcast(small_v, 3), bly = lane_bcast(small_v, 4);
-            if (lane == 0) {
-                double pose[3] = { bx, by, bth };
-                if (kPredict) {
-                    const double2 sc2 = sincosd_ni(pose[2] + pa.u1);
-                    const double sn2 = sc2.x, cs2 = sc2.y;
-                    const double p0 = predict_pose_entry(pose, 0, pa.u0, pa.u1, sn2, cs2), p1 = predict_pose_entry(pose, 1, pa.u0, pa.u1, sn2, cs2),
-                                 p2 = predict_pose_entry(pose, 2, pa.u0, pa.u1, sn2, cs2);
-                    pose[0] = p0; pose[1] = p1; pose[2] = p2;
-                }
-                const double d0 = blx - pose[0], d1 = bly - pose[1];
-                const double bearing = bearing_ni(d1, d0, pose[2]);
-                const double sq = sqrt(d0 * d0 + d1 * d1);
-                sol.nu[0] = a.z0 - sq;                                    // :144 (bearing NOT wrapped)
-                sol.nu[1] = a.z1 - bearing;
-            }
+            bearing_innovation<kPredict>(small_v, lane, a, pa, sol);     // ---- BEARING: nu
         } else {
-            // ---- CHAIN: each matrix entry of the solve is formed on its own lane.  Every lane holds the 24 small operands in
-            //      registers (static indices only: an array indexed by the lane would live in scratch memory) and SELECTS the ones
-            //      its entry needs; what every lane needs identically (pose, H_s, inv(phi)) is computed redundantly; entries travel
-            //      between lanes by v_readlane (G(:,S), phi) or, where each lane needs a different subset, through `pss` in LDS.
-            // every lane gets the 20 operands this wavefront loaded (lane i holds operand i) by v_readlane: wave-uniform values, no
-            // LDS round trip; 15..18 (the landmark's own 2x2 block) belong to DIAG and are read later, from LDS
+            // ---- CHAIN: each matrix entry of the solve is formed on its own lane.  Every lane holds the 24 small operands in registers
+            //      (static indices only: an array indexed by the lane would live in scratch memory; lane i loaded operand i, they come by
+            //      v_readlane; 15..18, the landmark's own 2x2 block, are DIAG's and read later, from LDS) and SELECTS the ones its entry
+            //      needs; what every lane needs identically (pose, H_s, inv(phi)) is computed redundantly; entries travel between lanes
+            //      by v_readlane (G(:,S), phi) or, where each lane needs a different subset, through `pss` in LDS.
             double p[24];
 #pragma unroll
             for (int i = 0; i < 24; ++i) p[i] = (i >= 15 && i < 19) ? 0.0 : lane_bcast(small_v, i);
@@ -267,7 +405,7 @@ __global__ __launch_bounds__(kGatherBlock) void k_gather(DevState st, CorrectArg
             if (kPredict) {
                 // predict(u) folded into this correction: same per-entry arithmetic as k_predict (predict_*_entry)
                 const double2 sc_l = sincosd_ni((lane & 1) ? pose[2] + pa.u1 : pose[2]);   // lane 0: pre-motion heading, lane 1: + u2
-                EKF_STAMP();                                          // (probe) sincos
+                stamps.mark();                                          // (probe) sincos
                 const double sn = lane_bcast(sc_l.x, 0), cs = lane_bcast(sc_l.y, 0), sn2 = lane_bcast(sc_l.x, 1), cs2 = lane_bcast(sc_l.y, 1);
                 double W[3];
                 predict_common(pa.u0, pa.u1, sn, cs, fa, fb, W);
@@ -292,7 +430,7 @@ __global__ __launch_bounds__(kGatherBlock) void k_gather(DevState st, CorrectArg
                 const double p0 = predict_pose_entry(pose, 0, pa.u0, pa.u1, sn2, cs2), p1 = predict_pose_entry(pose, 1, pa.u0, pa.u1, sn2, cs2),
                              p2 = predict_pose_entry(pose, 2, pa.u0, pa.u1, sn2, cs2);      // every lane (3 operations)
                 pose[0] = p0; pose[1] = p1; pose[2] = p2;
-                EKF_STAMP();                                          // (probe) entries formed
+                stamps.mark();                                          // (probe) entries formed
                 if (lane < 15) pss[lane] = EKF_SEL(is_prr) ? e_prr : e_strip;   // the column lanes and the G(:,S) lanes read Prr', strip' from here
                 if (lane < 9) ps.Q[lane] = e_q;
                 if (lane == 0) { ps.fa = fa; ps.fb = fb; }
@@ -301,45 +439,13 @@ __global__ __launch_bounds__(kGatherBlock) void k_gather(DevState st, CorrectArg
             SmallSolve so;
             double sq;
             solve_hs(p[22] - pose[0], p[23] - pose[1], sq, so.Hs);    // EKF_SLAM.m:125-127,137-138 (every lane, redundantly)
-            EKF_STAMP();                                              // 3: H_s
+            stamps.mark();                                           // 3: H_s
             while (*(volatile int *)&diag_ready == 0) { }             // the DIAG wavefront's (patched) 2x2 block is in pss[15..18]
             wave_lds_sync();                                          // pss: predicted entries (own writes) and that block
-            const int ra = lane >= 5 ? 1 : 0;                         // row of this lane's G(:,S) entry
-            double hsel[5];
-#pragma unroll
-            for (int t = 0; t < 5; ++t) hsel[t] = ra ? so.Hs[1][t] : so.Hs[0][t];
-            const double e_gs = solve_gs_entry(pss, hsel, lane < 10 ? lane - 5 * ra : 0);
             double GS[2][5];
-#pragma unroll
-            for (int i = 0; i < 10; ++i) GS[i / 5][i % 5] = lane_bcast(e_gs, i);
-            double e_phi;
-            {
-                const int aa = (lane >> 1) & 1, bb = lane & 1;
-                double gsel[5], hb[5];
-#pragma unroll
-                for (int t = 0; t < 5; ++t) { gsel[t] = aa ? GS[1][t] : GS[0][t]; hb[t] = bb ? so.Hs[1][t] : so.Hs[0][t]; }
-                const double Rab = aa == 0 ? (bb == 0 ? a.R00 : a.R01) : (bb == 0 ? a.R10 : a.R11);
-                e_phi = solve_phi_entry(gsel, hb, Rab);                                      // :141
-            }
-            const double phi[4] = { lane_bcast(e_phi, 0), lane_bcast(e_phi, 1), lane_bcast(e_phi, 2), lane_bcast(e_phi, 3) };
-            ekfm::inv2(phi, so.Phi);                                  // :143 phi_k^-1 (every lane, redundantly)
-            EKF_STAMP();                                              // 4: solve
-            // publish: K_r and G_r are formed by every lane (18 operations, static indices, no divergent branches -- the per-lane
-            // form with its select chains was 200 instructions), then lane 0 stores the whole struct; nu is BEARING's
-#pragma unroll
-            for (int b = 0; b < 3; ++b) {
-                so.Gr[0][b] = GS[0][b]; so.Gr[1][b] = GS[1][b];
-#pragma unroll
-                for (int cc = 0; cc < 2; ++cc) so.Kr[b][cc] = solve_kr_entry(GS[0][b], GS[1][b], so.Phi[cc], so.Phi[2 + cc]);
-            }
-            if (lane == 0) {
-#pragma unroll
-                for (int i = 0; i < 10; ++i) sol.Hs[i / 5][i % 5] = so.Hs[i / 5][i % 5];
-#pragma unroll
-                for (int i = 0; i < 4; ++i) sol.Phi[i] = so.Phi[i];
-#pragma unroll
-                for (int i = 0; i < 6; ++i) { sol.Kr[i / 2][i % 2] = so.Kr[i / 2][i % 2]; sol.Gr[i / 3][i % 3] = so.Gr[i / 3][i % 3]; }
-            }
+            chain_solve(pss, a.R00, a.R01, a.R10, a.R11, lane, so, GS);
+            stamps.mark();                                           // 4: solve
+            chain_publish(so, GS, lane, sol);
         }
         __syncthreads();                                              // barrier B: sol, ps, pss complete
         if (blockIdx.x == 0) {
@@ -351,10 +457,9 @@ __global__ __launch_bounds__(kGatherBlock) void k_gather(DevState st, CorrectArg
             } else if (role == 5) {
                 if (lane < 9) {
                     const int r = lane / 3, b = lane - 3 * r;
-                    // Prr' = Prr - K_r G_r, kept EXACTLY symmetric: both mirrors take the lower-triangle entry's value.  The twin of
-                    // pair_column.h's store_robot_part, which says why.
-                    const int rr = r > b ? r : b, bb = r > b ? b : r;
-                    prr_nxt[3 * r + b] = pss[3 * rr + bb] - (sol.Kr[rr][0] * sol.Gr[0][bb] + sol.Kr[rr][1] * sol.Gr[1][bb]);
+                    // Prr' = Prr - K_r G_r, kept EXACTLY symmetric: both mirrors take the lower-triangle entry's value
+                    // (pair_column.h: robot_block_entry, which says why)
+                    prr_nxt[3 * r + b] = robot_block_entry(pss, sol, r, b);
                 }
             } else {
                 if (lane < 6) { const int r = lane / 3, b = lane - 3 * r; st.small[3 * r + b] = sol.Gr[r][b]; }
@@ -364,14 +469,12 @@ __global__ __launch_bounds__(kGatherBlock) void k_gather(DevState st, CorrectArg
 #endif
             }
         }
-#ifdef EKF_GATHER_STAMPS
-        EKF_STAMP();                                                  // barrier B passed
+        stamps.mark();                                               // barrier B passed
 #if EKF_GATHER_STAMPS == 2                                                // the CHAIN wavefront's view (the Q slots hold one view per build)
-        if (blockIdx.x == 0 && tid == kGatherCols) for (int i = 0; i < 9; ++i) st.small[12 + i] = (double)(stamp[i] - stamp[0]);
+        if (blockIdx.x == 0 && tid == kGatherCols) for (int i = 0; i < 9; ++i) st.small[12 + i] = (double)(stamps.t[i] - stamps.t[0]);
 #endif
 #if EKF_GATHER_STAMPS == 3                                                // the DIAG wavefront's view
-        if (blockIdx.x == 0 && tid == kGatherCols + 64) for (int i = 0; i < 9; ++i) st.small[12 + i] = (double)(stamp[i] - stamp[0]);
-#endif
+        if (blockIdx.x == 0 && tid == kGatherCols + 64) for (int i = 0; i < 9; ++i) st.small[12 + i] = (double)(stamps.t[i] - stamps.t[0]);
 #endif
         return;
     }
@@ -396,7 +499,7 @@ __global__ __launch_bounds__(kGatherBlock) void k_gather(DevState st, CorrectArg
     // clocks, and the CHAIN wavefront -- the critical path of the launch -- would stand at this barrier for all of them (it did:
     // the column lanes then waited ~2 000 clocks for the solve at barrier B).  No waitcnt: the loads stay in flight across it.
     asm volatile("s_barrier" ::: "memory");
-    EKF_STAMP();                                                  // a: uniform operands requested, barrier 0 passed
+    stamps.mark();                                               // a: uniform operands requested, barrier 0 passed
     //     Then what this column needs: the two landmark rows at column c (canonical lower-triangle entries: row part left of
     //     j, column part right of j+1 -- one 16-byte load there, j is even; from the tiles or from the exchanged row-panel),
     //     the strip column, x(c) ...
@@ -423,7 +526,7 @@ __global__ __launch_bounds__(kGatherBlock) void k_gather(DevState st, CorrectArg
         if (c & 1) { dgl = dg[1]; dgc = dg[2]; } else dgc = dg[0];
     }
     __builtin_amdgcn_sched_barrier(0);
-    EKF_STAMP();                                                  // b: all loads requested
+    stamps.mark();                                               // b: all loads requested
     // (2) stage the uniform operands (waits for the FIRST group of loads only); the four column wavefronts and DIAG meet on a
     //     counter in LDS -- the CHAIN and BEARING wavefronts do not take part
     upatch[tid] = up0; upatch[tid + kGatherCols] = up1;           // unconditional (entries past 4*npend are never read)
@@ -431,13 +534,14 @@ __global__ __launch_bounds__(kGatherBlock) void k_gather(DevState st, CorrectArg
     if ((tid & 63) == 0) atomicAdd(&staged_cnt, 1);
     while (*(volatile int *)&staged_cnt < 4) { }
     wave_lds_sync();
-    EKF_STAMP();                                                  // 1: uniform operands staged
+    stamps.mark();                                               // 1: uniform operands staged
 
     // (2b) this column's operands of the first kPre pending pairs (G_i(:,c) left of j, K_i(c,:) right of it), all in flight
     //     together (fetched 8 at a time inside the patch loop they cost one L2 round trip per 8 pairs).  Requested AFTER barrier
     //     A: issuing these up to 32 loads takes the column wavefronts ~2 000 clocks, and before the barrier that was 2 000 clocks
     //     the helper wavefronts -- the critical path -- spent waiting for them; behind it the column lanes have ~3 000 clocks of
-    //     slack until the solve is published (scripts/probe_gather_phases.py).
+    //     slack until the solve is published (scripts/probe_gather_phases.py).  The loads' group tests use an OPAQUE copy of npre:
+    //     with the condition of the use sites the compiler would merge each group of loads into the block that consumes it, below B.
     // 32 pairs: a 64-pair variant (344 VGPRs, one workgroup per CU) was slower under an asynchronous flush (tuning log, sweep 12)
     constexpr int kPre = 32;
     const int npre = do_patch ? (npend < kPre ? npend : kPre) : 0;
@@ -446,107 +550,15 @@ __global__ __launch_bounds__(kGatherBlock) void k_gather(DevState st, CorrectArg
     double2 pre[kPre];
     bool next_assoc = false;
     if constexpr (kDev) next_assoc = dl.parts_out != nullptr;
-    {
-        // unconditional, clamped addresses (a predicated form lets the compiler sink the loads below the barrier, next to their
-        // use); slots past npend repeat the last pending one (cache hits), c is clamped into the padded vector
-        // One uniform base (Gp; Kp follows it in the same allocation, host/passes.h: create_passes) + a 32-bit per-lane element offset: the
-        // compiler can then use the scalar-base addressing form and the 32 loads cost one scalar add each.
-        const uint32_t cc = (uint32_t)(c < pad_cols ? c : pad_cols - 1);
-        const uint32_t krel = (uint32_t)((st.Kp - st.Gp) >> 1);
-        const uint32_t lane_off = cc + (rowpart ? 0u : krel);
-        const char *__restrict__ ub = reinterpret_cast<const char *>(st.Gp);
-        const uint32_t lane_bytes = lane_off * 16u;              // < 2^32: see below
-        // slot offsets advance incrementally around the ring (scalar unit: one add, one wrap test per pair)
-        // (32-bit: 2 * pcap * pair_stride / 2 <= 256 * 2 * capacity elements of 16 bytes stays far below 2^32)
-        const uint32_t step = (uint32_t)ps2, wrap = (uint32_t)st.pcap * step;
-        uint32_t off = (uint32_t)pstart * step;
-        // Groups of 8 are skipped when no pending pair falls into them (immediate mode, the start of every batch).  The group
-        // test uses an OPAQUE copy of npre: with the same condition as at the use sites the compiler would merge each group
-        // of loads into the block that consumes it, below the barrier.
-        int npre_ld = npre;
-        asm volatile("" : "+s"(npre_ld));
-#pragma unroll
-        for (int g0 = 0; g0 < kPre; g0 += 8) {
-            if (g0 < npre_ld) {
-#pragma unroll
-                for (int t = 0; t < 8; ++t) {
-                    pre[g0 + t] = *reinterpret_cast<const double2 *>(ub + (uint64_t)off * 16u + lane_bytes);
-                    if (g0 + t + 1 < npre) { off += step; if (off == wrap) off = 0; }
-                }
-            }
-        }
-    }
-
+    int npre_ld = npre;
+    asm volatile("" : "+s"(npre_ld));
+    prefetch_pending<kPre>(pre, st, c, pad_cols, rowpart, pstart, ps2, npre, npre_ld);
 
     // (3) every lane applies the pending pairs to its own two row entries while the helper wavefronts run the solve
     if (live && do_patch) {
-        if (rowpart) {
-#pragma unroll
-            for (int g0 = 0; g0 < kPre; g0 += 8)
-                if (g0 < npre) {                                  // uniform; inside a group no branches: select
-                    double2 ua[8], ub[8];
-#pragma unroll
-                    for (int t = 0; t < 8; ++t) { ua[t] = upatch[4 * (g0 + t) + 0]; ub[t] = upatch[4 * (g0 + t) + 1]; }
-#pragma unroll
-                    for (int t = 0; t < 8; ++t) {
-                        const double v0 = rank2_apply(m0, ua[t], pre[g0 + t]), v1 = rank2_apply(m1, ub[t], pre[g0 + t]);
-                        m0 = g0 + t < npre ? v0 : m0; m1 = g0 + t < npre ? v1 : m1;
-                    }
-                }
-            // more than kPre pending pairs (async flush, batch > kPre): chunks of 8 independent loads, applied in order
-            const double2 *__restrict__ gp = reinterpret_cast<const double2 *>(st.Gp) + c;
-            int i = npre;
-            for (; i + 8 <= npend; i += 8) {
-                double2 g[8];
-#pragma unroll
-                for (int q = 0; q < 8; ++q) g[q] = gp[(int64_t)ring_slot(pstart, i + q, st.pcap) * ps2];
-#pragma unroll
-                for (int q = 0; q < 8; ++q) {
-                    m0 = rank2_apply(m0, upatch[4 * (i + q) + 0], g[q]);
-                    m1 = rank2_apply(m1, upatch[4 * (i + q) + 1], g[q]);
-                }
-            }
-            for (; i < npend; ++i) {
-                const double2 g = gp[(int64_t)ring_slot(pstart, i, st.pcap) * ps2];
-                m0 = rank2_apply(m0, upatch[4 * i + 0], g);
-                m1 = rank2_apply(m1, upatch[4 * i + 1], g);
-            }
-        } else if (colpart) {
-#pragma unroll
-            for (int g0 = 0; g0 < kPre; g0 += 8)
-                if (g0 < npre) {
-                    double2 ua[8], ub[8];
-#pragma unroll
-                    for (int t = 0; t < 8; ++t) { ua[t] = upatch[4 * (g0 + t) + 2]; ub[t] = upatch[4 * (g0 + t) + 3]; }
-#pragma unroll
-                    for (int t = 0; t < 8; ++t) {
-                        const double v0 = rank2_apply(m0, pre[g0 + t], ua[t]), v1 = rank2_apply(m1, pre[g0 + t], ub[t]);
-                        m0 = g0 + t < npre ? v0 : m0; m1 = g0 + t < npre ? v1 : m1;
-                    }
-                }
-            const double2 *__restrict__ kp = reinterpret_cast<const double2 *>(st.Kp) + c;
-            int i = npre;
-            for (; i + 8 <= npend; i += 8) {
-                double2 k[8];
-#pragma unroll
-                for (int q = 0; q < 8; ++q) k[q] = kp[(int64_t)ring_slot(pstart, i + q, st.pcap) * ps2];
-#pragma unroll
-                for (int q = 0; q < 8; ++q) {
-                    m0 = rank2_apply(m0, k[q], upatch[4 * (i + q) + 2]);
-                    m1 = rank2_apply(m1, k[q], upatch[4 * (i + q) + 3]);
-                }
-            }
-            for (; i < npend; ++i) {
-                const double2 k = kp[(int64_t)ring_slot(pstart, i, st.pcap) * ps2];
-                m0 = rank2_apply(m0, k, upatch[4 * i + 2]);
-                m1 = rank2_apply(m1, k, upatch[4 * i + 3]);
-            }
-        } else {                                               // c == j + 1: canonical (j+1,j) and (j+1,j+1)
-            for (int i = 0; i < npend; ++i) {
-                m0 = rank2_apply(m0, upatch[4 * i + 1], upatch[4 * i + 2]);
-                m1 = rank2_apply(m1, upatch[4 * i + 1], upatch[4 * i + 3]);
-            }
-        }
+        if (rowpart) apply_pending_column<true, kPre>(m0, m1, pre, upatch, st.Gp, c, npre, npend, pstart, st.pcap, ps2);
+        else if (colpart) apply_pending_column<false, kPre>(m0, m1, pre, upatch, st.Kp, c, npre, npend, pstart, st.pcap, ps2);
+        else apply_pending_corner(m0, m1, upatch, npend);
     }
     // rows j, j+1 at columns j and j+1 are the landmark's own diagonal block: the live F64 copies (no pending pair to apply; the same bits
     // as the patched tile entries with F64 tiles, the unrounded values with F32 tiles)
@@ -555,13 +567,12 @@ __global__ __launch_bounds__(kGatherBlock) void k_gather(DevState st, CorrectArg
         if (c == j) { m0 = dgc; m1 = dgl_p; }                      // P(j, j), P(j+1, j)
         else if (c == j + 1) { m0 = dgl; m1 = dgc; }               // P(j+1, j), P(j+1, j+1)
     }
-    EKF_STAMP();                                                  // 2: patches done
+    stamps.mark();                                               // 2: patches done
     __syncthreads();                                              // barrier B: the helpers' results are in LDS
-    EKF_STAMP();                                                  // 3: solve available
+    stamps.mark();                                               // 3: solve available
 
     // (4) the column's share of G, K, x and the strip.  (4) and (4b) are the twin of pair_column.h's finish_pair_column / store_pair_column
-    //     (the pair's storage format, x', strip', the diagonal blocks), kept as text of its own: this kernel's code objects are pinned
-    const int64_t pad_end = st.tm.padded(a.n_mm);
+    //     (the pair's storage format, x', strip', the diagonal blocks), kept as text of its own: as a function, (4b) alone, <.., predict, dev> takes 217 VGPRs for 216
     const int64_t out_off = (int64_t)ring_slot(pstart, npend, st.pcap) * st.pair_stride;   // this correction's own pair
     double2 *__restrict__ Gout = reinterpret_cast<double2 *>(st.Gp + out_off);
     double2 *__restrict__ Kout = reinterpret_cast<double2 *>(st.Kp + out_off);
@@ -590,7 +601,7 @@ __global__ __launch_bounds__(kGatherBlock) void k_gather(DevState st, CorrectArg
         sn[c] = t0;
         sn[ldm + c] = t1;
         sn[2 * ldm + c] = t2;
-    } else if (c < pad_end && !kFused) {
+    } else if (c < pad_cols && !kFused) {
         // zero the tail of the last tile so the downdate leaves the unused part of edge tiles untouched
         Gout[c] = make_double2(0.0, 0.0);
         Kout[c] = make_double2(0.0, 0.0);
@@ -647,36 +658,29 @@ __global__ __launch_bounds__(kGatherBlock) void k_gather(DevState st, CorrectArg
     if constexpr (kDev) {
         if (next_assoc) {                                         // uniform
             // ---- the NEXT observation's association (Correspondence.m:49-87) on the state this correction leaves (the twin of
-            //      assoc_winners.h's assoc_likelihood and columns_argmin_store, kept as text of its own: as helpers they cost this
-            //      kernel a register and 160 bytes).  Landmark
+            //      assoc_winners.h's assoc_likelihood and columns_argmin_store, kept as text of its own: as helpers they cost the
+            //      device-loop forms a register and 384-428 bytes).  Landmark
             //      k = c / 2 is scored by its even column lane; everything it needs is in this lane pair's registers (x', strip',
             //      the landmark's own 2x2 block after this correction) or in the workgroup's LDS (Prr before the correction, K_r,
             //      G_r, nu).
             __shared__ double na_ll[kGatherCols / 64];
             __shared__ int na_ix[kGatherCols / 64];
             const bool odd = (c & 1) != 0;
-            const double dcc = ndc, dlo = ndl;                    // the landmark's own block after this correction: computed above, live
-            // odd lane -> even lane
             const double xn_o = lane_xor1(xn), t0_o = lane_xor1(t0), t1_o = lane_xor1(t1), t2_o = lane_xor1(t2),
-                         d10 = lane_xor1(dlo), d11 = lane_xor1(dcc);
+                         d10 = lane_xor1(ndl), d11 = lane_xor1(ndc);      // (the block after this correction)
             double ll = INFINITY;
             int64_t ix = INT64_MAX;
             if (live && !odd) {
                 const int64_t k = c >> 1;
-                double q[24];
+                double prr_n[9], pose_n[3], q[24];
 #pragma unroll
                 for (int r = 0; r < 3; ++r)
 #pragma unroll
-                    for (int b = 0; b < 3; ++b) {                 // Prr' as the DIAG wavefront stores it (lower-triangle value, mirrored)
-                        const int rr = r > b ? r : b, bb = r > b ? b : r;
-                        q[3 * r + b] = pss[3 * rr + bb] - (sol.Kr[rr][0] * sol.Gr[0][bb] + sol.Kr[rr][1] * sol.Gr[1][bb]);
-                    }
-                q[9] = t0; q[10] = t0_o; q[11] = t1; q[12] = t1_o; q[13] = t2; q[14] = t2_o;
-                q[15] = dcc; q[16] = d10; q[17] = d10; q[18] = d11;
+                    for (int b = 0; b < 3; ++b) prr_n[3 * r + b] = robot_block_entry(pss, sol, r, b);     // Prr' as the DIAG wavefront stores it
 #pragma unroll
                 for (int l = 0; l < 3; ++l)                       // x_r' as the CHAIN wavefront stores it (x(3) NOT re-wrapped)
-                    q[19 + l] = pose_sh[l] + (sol.Kr[l][0] * sol.nu[0] + sol.Kr[l][1] * sol.nu[1]);
-                q[22] = xn; q[23] = xn_o;
+                    pose_n[l] = pose_sh[l] + (sol.Kr[l][0] * sol.nu[0] + sol.Kr[l][1] * sol.nu[1]);
+                pack_assoc_operands(q, prr_n, pose_n, t0, t0_o, t1, t1_o, t2, t2_o, ndc, d10, d11, xn, xn_o);
                 SmallSolve so2;
                 solve_small(q, dl.z0, dl.z1, dl.R00, dl.R01, dl.R10, dl.R11, so2);
                 const double n0 = so2.nu[0], n1 = so2.nu[1];
@@ -701,11 +705,10 @@ __global__ __launch_bounds__(kGatherBlock) void k_gather(DevState st, CorrectArg
         }
     }
 #ifdef EKF_GATHER_STAMPS
-    EKF_STAMP();                                                  // 4: outputs issued
+    stamps.mark();                                               // 4: outputs issued
     __syncthreads();
 #if EKF_GATHER_STAMPS == 1                                                // column lane 0's view
-    if (c == 0) for (int i = 0; i < 7; ++i) st.small[12 + i] = (double)(stamp[i] - stamp[0]);
+    if (c == 0) for (int i = 0; i < 7; ++i) st.small[12 + i] = (double)(stamps.t[i] - stamps.t[0]);
 #endif
 #endif
-#undef EKF_STAMP
 }

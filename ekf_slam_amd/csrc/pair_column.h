@@ -5,9 +5,10 @@
 // Compiles for the host too (behind tests/support/kernel_host_shim.h): DevState, double2, ring_slot, rank2_apply, lane_xor1 and
 // ekfm:: functions only.
 //
-// TWINS.  The main body of k_gather (gather.h, steps (4), (4b) and the helper wavefronts' tail) and the column steps of k_gather_linear
-// hold the same steps as text of their own: k_gather is tuned to the clock and its code objects are pinned, and k_gather_linear lost
-// 0.1-0.4 us of its 8-17 when it called load_column_operands / finish_pair_column.  A change to a rule below is made there as well.
+// TWINS.  Steps (4), (4b) of k_gather (gather.h) and the column steps of k_gather_linear hold the same steps as text of their own:
+// (4b) alone as a function costs k_gather<.., predict, dev> a VGPR (216 -> 217), and k_gather_linear lost 0.1-0.4 us of its 8-17 when it
+// called load_column_operands / finish_pair_column.  A change to a rule below is made there as well.  The robot block's rule is ONE
+// text: robot_block_entry, which k_gather's helper wavefronts and its kDev epilogue call too (no register, no byte).
 #pragma once
 
 // ---------------------------------------------------------------------------------------------------
@@ -139,17 +140,21 @@ __device__ __forceinline__ void finish_pair_column(const PairDest &d, const Pair
     if (live) store_diag_column(d.diag, c, ndc, ndl);
 }
 
-// Workgroup 0 (tid: the lane's index in it): x_r' = x_r + K_r nu and Prr' = Prr - K_r G_r.
-// Prr' is kept EXACTLY symmetric: entry (r, b) and its mirror both take the lower-triangle entry's value.  Evaluated entry by entry,
+// Prr'(r, b) = Prr(r, b) - K_r(r, :) G_r(:, b), kept EXACTLY symmetric: entry (r, b) and its mirror both take the lower-triangle entry's value.  Evaluated entry by entry,
 // K_r(r,:) G_r(:,b) and K_r(b,:) G_r(:,r) differ in the last bit; with the strip stored once (symmetry enforced there) the antisymmetric
 // part this leaves in the 3x3 block is not damped but AMPLIFIED by the corrections that follow -- measured: 2e-15 after 250 SLAM
 // iterations, 1.3e-7 after 3 000, the heading drifting from the dense restatement with it (scripts/soak_config2.py), where the
-// reference's dense P stays symmetric to 1e-16.  (k_gather's twins: its helper wavefronts' tail, and the Prr' its kDev epilogue forms.)
+// reference's dense P stays symmetric to 1e-16.  (Also called by k_gather: its helper wavefronts' tail, and the Prr' its kDev epilogue forms.)
+template <typename Sol>
+__device__ __forceinline__ double robot_block_entry(const double *prr, const Sol &sol, int r, int b) {
+    const int rr = r > b ? r : b, bb = r > b ? b : r;
+    return prr[3 * rr + bb] - (sol.Kr[rr][0] * sol.Gr[0][bb] + sol.Kr[rr][1] * sol.Gr[1][bb]);
+}
+// Workgroup 0 (tid: the lane's index in it): x_r' = x_r + K_r nu and Prr' = Prr - K_r G_r.
 __device__ __forceinline__ void store_robot_part(const DevState &st, int cur, const PairDest &d, const PairSolve &sol, int tid) {
     if (tid < 3) d.x[tid] = buffer_of(st.x, cur)[tid] + (sol.Kr[tid][0] * sol.nu[0] + sol.Kr[tid][1] * sol.nu[1]);
     if (tid >= 64 && tid < 73) {
         const int q = tid - 64, r = q / 3, b = q - 3 * r;
-        const int rr = r > b ? r : b, bb = r > b ? b : r;
-        buffer_of(st.prr, cur ^ 1)[3 * r + b] = sol.prr[3 * rr + bb] - (sol.Kr[rr][0] * sol.Gr[0][bb] + sol.Kr[rr][1] * sol.Gr[1][bb]);
+        buffer_of(st.prr, cur ^ 1)[3 * r + b] = robot_block_entry(sol.prr, sol, r, b);
     }
 }
