@@ -420,4 +420,113 @@ EKF_MHD Match2 match2_merge(const Match2 &a, const Match2 &b) {
     return r;
 }
 
+// The MOTION models of ekf_predict_model (include/ekfslam.h names them; predict_model.h runs them on the device): the new pose
+// xn = f(x_r, u), the two entries fa = F(0,2), fb = F(1,2) of F = df/dx_r = I + [0 0 fa; 0 0 fb; 0 0 0], and V = df/du (row-major 3 x 3; a
+// model with two inputs leaves column 2 zero).  theta, the turn and V's heading row in degrees, so the heading column of F and the turn
+// column of V carry 1/k, k = 180/pi.  The new heading is wrapTo360(theta + turn) as ekf_predict forms it; sincosd is taken of the unwrapped
+// sums.  fa, fb and V depend on theta and u alone, never on the position.
+//   1 TURN_DRIVE  u = (d, t):      turn by t, then drive d -- the reference's own f (EKF_SLAM.m:58-60), with its true Jacobians
+//   2 ARC         u = (d, t):      the circular arc of length d that turns by t, in chord form: chord d g along theta + t/2, g = sin a / a,
+//                                  a = t / (2k); finite at t = 0 (g, g' = dg/da from their series below kMotionSeries)
+//   3 POSE_DELTA  u = (dx, dy, t): the pose increment in the robot frame (a scan matcher, integrated odometry)
+// Returns false (nothing written) for any other model.  The sincos is a parameter because the kernels keep ONE machine-code body of it
+// (predict.h: sincosd_ni); each expression is written once, so the host (ekf_motion_evaluate), the host emulation and k_predict_model
+// give the same bits with FP contraction off.
+constexpr double kMotionSeries = 0.5;
+// g(a) = sin a / a and g'(a) = (a cos a - sin a) / a^2 given sin a and cos a.  Below kMotionSeries the closed form of g' cancels (its
+// relative error grows as 3 eps / a^2) and both are 0 / 0 at a = 0: there the Taylor series, cut where the next term is below half an ulp
+// at the switch (g: a^16 / 17! = 4e-20; g': 16 a^15 / 17! = 1.4e-18 against 0.16).
+EKF_MHD void motion_chord(double a, double sa, double ca, double &g, double &gp) {
+    if (fabs(a) < kMotionSeries) {
+        const double z = a * a;
+        double r = 1.0 / 1307674368000.0;                       // 1 / 15!
+        r = fma(r, z, -1.0 / 6227020800.0);                     // 1 / 13!
+        r = fma(r, z, 1.0 / 39916800.0);
+        r = fma(r, z, -1.0 / 362880.0);
+        r = fma(r, z, 1.0 / 5040.0);
+        r = fma(r, z, -1.0 / 120.0);
+        r = fma(r, z, 1.0 / 6.0);
+        g = fma(-z, r, 1.0);
+        double q = -14.0 / 1307674368000.0;                     // -2n / (2n + 1)!, n = 7 .. 1
+        q = fma(q, z, 12.0 / 6227020800.0);
+        q = fma(q, z, -10.0 / 39916800.0);
+        q = fma(q, z, 8.0 / 362880.0);
+        q = fma(q, z, -6.0 / 5040.0);
+        q = fma(q, z, 4.0 / 120.0);
+        q = fma(q, z, -2.0 / 6.0);
+        gp = a * q;
+    } else {
+        g = sa / a;
+        gp = (a * ca - sa) / (a * a);
+    }
+}
+struct MotionSinCos {
+    EKF_MHD void operator()(double a, double &sn, double &cs) const { sincosd(a, sn, cs); }
+};
+template <typename SinCos>
+EKF_MHD bool motion_eval_with(const SinCos &sc, int model, const double xr[3], const double u[3], double xn[3], double &fa, double &fb,
+                              double V[9]) {
+    if (model < 1 || model > 3) return false;
+    for (int i = 0; i < 9; ++i) V[i] = 0.0;
+    double s, c;
+    if (model == 3) {
+        sc(xr[2], s, c);
+        const double w0 = c * u[0] - s * u[1], w1 = s * u[0] + c * u[1];
+        xn[0] = xr[0] + w0;
+        xn[1] = xr[1] + w1;
+        xn[2] = wrapTo360(xr[2] + u[2]);
+        fa = -w1 / kR2D;
+        fb = w0 / kR2D;
+        V[0] = c; V[1] = -s;
+        V[3] = s; V[4] = c;
+        V[8] = 1.0;
+        return true;
+    }
+    double dg = u[0], g = 1.0, gp = 0.0;                       // the chord and what it is of the arc
+    if (model == 2) {
+        const double half = 0.5 * u[1], a = half / kR2D;
+        double sa, ca;
+        sc(half, sa, ca);
+        motion_chord(a, sa, ca, g, gp);
+        dg = u[0] * g;
+        sc(xr[2] + half, s, c);
+    } else {
+        sc(xr[2] + u[1], s, c);
+    }
+    xn[0] = xr[0] + dg * c;                                     // EKF_SLAM.m:58-60 where model == 1
+    xn[1] = xr[1] + dg * s;
+    xn[2] = wrapTo360(xr[2] + u[1]);
+    fa = -dg * s / kR2D;
+    fb = dg * c / kR2D;
+    if (model == 2) {
+        V[0] = g * c; V[1] = u[0] * (gp * c - g * s) / (2.0 * kR2D);
+        V[3] = g * s; V[4] = u[0] * (gp * s + g * c) / (2.0 * kR2D);
+    } else {
+        V[0] = c; V[1] = fa;
+        V[3] = s; V[4] = fb;
+    }
+    V[7] = 1.0;
+    return true;
+}
+EKF_MHD bool motion_eval(int model, const double xr[3], const double u[3], double xn[3], double &fa, double &fb, double V[9]) {
+    return motion_eval_with(MotionSinCos(), model, xr, u, xn, fa, fb, V);
+}
+// the turn of a step: the entry of u that the heading takes up
+EKF_MHD double motion_turn(int model, const double u[3]) { return model == 3 ? u[2] : u[1]; }
+// entry (i, j) of Q = V M V' (V row-major 3 x 3, M symmetric from its lower triangle m6 = (0,0) (1,0) (1,1) (2,0) (2,1) (2,2)): T = V M, then
+// T V', both sums in ascending index order, the zero terms of a two-input model included
+EKF_MHD double motion_M(const double m6[6], int r, int c) {
+    if (r < c) { const int t = r; r = c; c = t; }
+    return m6[r * (r + 1) / 2 + c];
+}
+EKF_MHD double motion_noise_entry(const double V[9], const double m6[6], int i, int j) {
+    double q = 0.0;
+    for (int k = 0; k < 3; ++k) {
+        double t = 0.0;
+        for (int l = 0; l < 3; ++l) t += V[3 * i + l] * motion_M(m6, l, k);
+        q += t * V[3 * j + k];
+    }
+    return q;
+}
+
 }  // namespace ekfm

@@ -108,6 +108,23 @@ struct AppendModelArgs {
     AppendModelEntry e[kAppendModelMax];
 };
 
+// k_predict_model (predict_model.h): a chain of m <= kPredictModelMax motion steps through the models of ekfm::motion_eval, carried out in
+// order by ONE launch that reads buffer cur and writes buffer cur ^ 1, as k_predict.  No tile is read: the storage type does not matter.
+// The steps travel in the argument block, M as its six unique entries -- 80 bytes a step, 2.5 KiB at 32 (nine entries a step would not fit
+// the 4 KiB argument block beside DevState).
+constexpr int kPredictModelMax = 32;
+struct PredictModelStep {
+    int32_t model, pad;       // EKF_MOTION_TURN_DRIVE (1), _ARC (2) or _POSE_DELTA (3)
+    double u[3];              // (d, turn, -), (arc length, turn, -) or (dx, dy, turn); angles in degrees
+    double m6[6];             // the inputs' covariance, lower triangle (0,0) (1,0) (1,1) (2,0) (2,1) (2,2); a two-input model: row 2 zero
+};
+struct PredictModelArgs {
+    int64_t n_mm;             // strip columns carried along (2 * landmarks)
+    int32_t m;                // steps in use
+    int32_t cur;
+    PredictModelStep e[kPredictModelMax];
+};
+
 struct CorrectArgs {
     double z0, z1;            // [range, bearing_deg]
     double R00, R01, R10, R11;

@@ -21,6 +21,9 @@ constexpr int ekf_tune_int(const char *, int dflt) { return dflt; }
 // ---- the steps: predict, append, the gather of a correction, a shard's row-panels, association (launch/steps.h) ----
 hipError_t launch_predict(const DevState &st, const PredictArgs &a, int storage, hipStream_t s);
 
+// k_predict_model (predict_model.h): a.m <= kPredictModelMax motion steps carried out in order by ONE launch; buffer a.cur -> a.cur ^ 1
+hipError_t launch_predict_model(const DevState &st, const PredictModelArgs &a, hipStream_t s);
+
 // dl != nullptr (device-resident measure loop): the kernel also reduces dl->parts_in and records the decision in dl->rec
 hipError_t launch_append(const DevState &st, const AppendArgs &a, int storage, hipStream_t s, const DevLoopArgs *dl = nullptr,
                          const PredictArgs *fused_predict = nullptr);

@@ -8,6 +8,7 @@
 //
 // Reference expressions realised (file:line in the reference tree):
 //   k_predict    P = F*P*F' + Q, x = f(x,u), wrapTo360          EKF_SLAM.m:40-51,56-65
+//   k_predict_model  the same step with true Jacobians, m per launch  (no counterpart: EKF_SLAM.m:58-60 is its model 1's f)
 //   k_append     state/covariance growth                         EKF_SLAM.m:67-98 (append.m:1-27)
 //   k_gather     z_k, H_k, phi_k, K, x += K nu                   EKF_SLAM.m:125-144
 //   k_downdate*  P = (I - K H_k) P  ==  P - K (H_k P)            EKF_SLAM.m:145
@@ -32,6 +33,7 @@ namespace {
 #include "tile_access.h"      // canonical element access, rank2_apply
 #include "lane_ops.h"         // values between the lanes of a wavefront: lane_bcast, lane_gather, lane_xor1
 #include "predict.h"          // k_predict, k_predict_mfma and the shared 3x3 part
+#include "predict_model.h"    // k_predict_model: a chain of motion steps through the models of ekfm::motion_eval, one launch
 #include "assoc_winners.h"    // association order, the self-validating winner entries
 #include "append.h"           // k_append
 #include "append_model.h"     // k_append_model: a scan's landmarks from range-bearing / relative-position fixes, one launch

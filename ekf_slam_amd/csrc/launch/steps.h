@@ -1,4 +1,4 @@
-// Fragment of kernels.hip, the launchers of the steps: predict, append, the gather of a correction in its five forms, a shard's
+// Fragment of kernels.hip, the launchers of the steps: predict, a chain of model predicts, append, the gather of a correction in its five forms, a shard's
 // row-panels, the association and the model-convention association of a scan (declared in kernels.h, in this order).
 #pragma once
 
@@ -15,6 +15,14 @@ hipError_t launch_predict(const DevState &st, const PredictArgs &a, int, hipStre
     }
     const int64_t grid = cdiv(a.n_mm > 0 ? a.n_mm : 1, kBlock);
     hipLaunchKernelGGL(k_predict, dim3((unsigned)grid), dim3(kBlock), 0, s, st, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_predict_model(const DevState &st, const PredictModelArgs &a, hipStream_t s) {
+    if (a.n_mm < 0 || a.n_mm > st.ldm || a.m < 1 || a.m > kPredictModelMax) return hipErrorInvalidValue;
+    for (int b = 0; b < a.m; ++b) if (a.e[b].model < 1 || a.e[b].model > 3) return hipErrorInvalidValue;
+    const int64_t grid = cdiv(a.n_mm > 0 ? a.n_mm : 1, kBlock);
+    hipLaunchKernelGGL(k_predict_model, dim3((unsigned)grid), dim3(kBlock), 0, s, st, a);
     return hipGetLastError();
 }
 

@@ -616,6 +616,54 @@ class Engine:
             res["d2_all"] = d2
         return res
 
+    # ---- motion steps through a model with its true Jacobians (include/ekfslam.h: ekf_predict_model) ----
+    @staticmethod
+    def _motions(steps):
+        steps = list(steps)
+        arr = (L.EkfMotion * max(len(steps), 1))()
+        for o, st in zip(arr, steps):
+            if len(st) != 3:
+                raise ValueError("predict_model: a step is (model, u, M)")
+            model, u, M = st
+            o.model = int(model)
+            nu = L.EKF_MOTION_INPUTS.get(o.model, 3)
+            uin = _vec(u)
+            if uin.size != nu:
+                raise ValueError("predict_model: u has %d values for this model" % nu)
+            for q in range(nu):
+                o.u[q] = uin[q]
+            Ma = np.asarray(M, dtype=np.float64)
+            if Ma.size != nu * nu:
+                raise ValueError("predict_model: M is %d x %d for this model" % (nu, nu))
+            full = np.zeros((3, 3))
+            full[:nu, :nu] = Ma.reshape(nu, nu)
+            for q, v in enumerate(full.reshape(-1, order="F")):
+                o.M[q] = v
+        return arr, len(steps)
+
+    def predict_model(self, steps):
+        """A chain of motion steps: steps = [(model, u, M), ...] with model EKF_MOTION_TURN_DRIVE (u = d, turn), EKF_MOTION_ARC (u = arc
+        length, turn) or EKF_MOTION_POSE_DELTA (u = dx, dy, turn in the robot frame); angles in degrees, M the covariance of u (2 x 2 or
+        3 x 3).  x_r' = f(x_r, u), P' = F P F' + V M V' with the true Jacobians, step after step in ONE launch (ekf_predict_model).
+        Eager: a recorded predict is carried out first.  Nothing is waited for or flushed."""
+        arr, m = self._motions(steps)
+        self._check(self.lib.ekf_predict_model(self.h, arr, m))
+
+    @staticmethod
+    def motion_evaluate(model, xr, u, lib=None):
+        """(x_new, F, V) of a motion model at the robot state xr = (x, y, theta in degrees): the new pose, F = df/dx_r (3 x 3) and
+        V = df/du (3 x 3; a model with two inputs leaves the last column zero): the function the kernel runs, on the host
+        (ekf_motion_evaluate)."""
+        lib = L.lib() if lib is None else lib
+        uin = np.zeros(3)
+        uv = _vec(u)
+        uin[:min(uv.size, 3)] = uv[:3]
+        xn, F, V = np.zeros(3), np.zeros(9), np.zeros(9)
+        rc = lib.ekf_motion_evaluate(int(model), _p(_vec(xr, 3)), _p(uin), _p(xn), _p(F), _p(V))
+        if rc:
+            raise L.EkfError(rc, "ekf_motion_evaluate")
+        return xn, F.reshape(3, 3, order="F"), V.reshape(3, 3, order="F")
+
     def load_lowrank_state(self, x, s, d, U):
         x, s, d = _vec(x), _vec(s), _vec(d)
         U = np.asfortranarray(np.asarray(U, dtype=np.float64))

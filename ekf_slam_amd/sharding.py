@@ -127,6 +127,13 @@ class ShardGroup:
         for e in self.shards:
             e.predict(u)
 
+    def predict_model(self, steps):
+        """Engine.predict_model on every shard: everything the launch reads and writes (x_r, Prr, the strip) is replicated, so no
+        exchange is needed."""
+        steps = list(steps)
+        for e in self.shards:
+            e.predict_model(steps)
+
     def append(self, u, R, pos, signature):
         for e in self.shards:
             e.append(u, R, pos, signature)

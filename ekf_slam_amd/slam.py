@@ -368,6 +368,63 @@ class _EkfBase:
             self.log.record_model_append(full)
         return [first + b + 1 for b in range(len(full))]
 
+    def predict_model(self, steps):
+        """Motion under observe_model's conventions: one step (model, u, M) or a list of them, model EKF_MOTION_TURN_DRIVE (1: u = (d, deg)
+        -- turn, then drive), EKF_MOTION_ARC (2: u = (arc length, deg)) or EKF_MOTION_POSE_DELTA (3: u = (dx, dy, deg) in the robot frame);
+        M the covariance of u.  x_r' = f(x_r, u) and P' = F P F' + V M V' with the true Jacobians (theta in degrees: the factor pi/180
+        where it belongs), the whole list in one launch; waits for nothing, flushes nothing (ekf_predict_model).
+        The reference has no such method: its predict keeps F at the pre-motion heading without pi/180 and a rank-one Q, and stays."""
+        steps = list(steps)
+        if len(steps) == 3 and np.isscalar(steps[0]):          # one step
+            steps = [tuple(steps)]
+        steps = [tuple(st) for st in steps]
+        if not 1 <= len(steps) <= L.EKF_PREDICT_MODEL_MAX:
+            raise ValueError("predict_model: between 1 and %d steps" % L.EKF_PREDICT_MODEL_MAX)
+        full = []
+        for st in steps:
+            if len(st) != 3:
+                raise ValueError("predict_model: a step is (model, u, M)")
+            model = int(st[0])
+            if model not in L.EKF_MOTION_INPUTS:
+                raise ValueError("predict_model: model is EKF_MOTION_TURN_DRIVE (1), EKF_MOTION_ARC (2) or EKF_MOTION_POSE_DELTA (3)")
+            nu = L.EKF_MOTION_INPUTS[model]
+            Mm = np.asarray(st[2], dtype=np.float64)
+            if Mm.size != nu * nu:
+                raise ValueError("predict_model: M is %d x %d for this model" % (nu, nu))
+            full.append((model, _vec(st[1], nu).copy(), Mm.reshape(nu, nu).copy()))
+        self._e.predict_model(full)
+        if self.log is not None:
+            self.log.record_model_predict(full)
+
+    @staticmethod
+    def _motion_steps(model, cols, M):
+        """One step from scalars, or a list of steps from equally long sequences (M: one matrix for all, or one per step)."""
+        cols = [np.asarray(c, dtype=np.float64) for c in cols]
+        if all(c.ndim == 0 for c in cols):
+            return [(model, [float(c) for c in cols], M)]
+        cols = [c.reshape(-1) for c in cols]
+        m = cols[0].size
+        if any(c.size != m for c in cols):
+            raise ValueError("predict_model: the inputs of a list of steps are equally long")
+        Ma = np.asarray(M, dtype=np.float64)
+        Ms = [Ma[b] for b in range(m)] if Ma.ndim == 3 and Ma.shape[0] == m else [Ma] * m
+        return [(model, [float(c[b]) for c in cols], Ms[b]) for b in range(m)]
+
+    def predict_turn_drive(self, d, deg, M):
+        """'The robot turned by deg degrees, then drove d; (d, deg) has the covariance M' -- one step, or a list of them from equally long
+        sequences.  The reference has no such method: this is its f with the true Jacobians."""
+        self.predict_model(self._motion_steps(L.EKF_MOTION_TURN_DRIVE, (d, deg), M))
+
+    def predict_arc(self, d, deg, M):
+        """'The robot drove an arc of length d while turning by deg degrees; (d, deg) has the covariance M' -- what wheel odometry
+        integrates to over one increment; one step or a list.  The reference has no such method."""
+        self.predict_model(self._motion_steps(L.EKF_MOTION_ARC, (d, deg), M))
+
+    def predict_pose_delta(self, dx, dy, deg, M):
+        """'The pose changed by (dx, dy, deg) in the robot frame, with covariance M (3 x 3)' -- a scan matcher's or integrated odometry's
+        increment; with zeros, additive noise M in the robot frame; one step or a list.  The reference has no such method."""
+        self.predict_model(self._motion_steps(L.EKF_MOTION_POSE_DELTA, (dx, dy, deg), M))
+
     def add_landmark_range_bearing(self, z, R, signature=None):
         """'A landmark that is not in the map yet is seen at range z[0] and bearing z[1] (degrees, relative to the heading), covariance
         R': it joins the map at the point that observation names.  Returns its 1-based number."""

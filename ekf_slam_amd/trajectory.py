@@ -17,7 +17,9 @@ the landmark blocks Hl, gate, wrap and rows in arrays of their own) as format 4;
 idx = the 0, 1 or 2 landmarks, the delta slot = z, R, and per observation the model, the anchor (NaN where the target is a landmark) and
 the gate in arrays of their own) as format 5, which has the arrays of format 4 (empty where no linear observation was made); one that
 holds an 'append_model' edit (add_landmarks_model: one scan of new landmarks, idx empty, and per scan its entries -- model, z, R, signature
--- in arrays of their own behind CSR offsets) as format 6, which has the arrays of format 5 (empty where there is nothing to hold).
+-- in arrays of their own behind CSR offsets) as format 6, which has the arrays of format 5 (empty where there is nothing to hold); one
+that holds a 'predict_model' edit (predict_model: one chain of motion steps, idx empty, and per chain its steps -- model, u, M -- in arrays
+of their own behind CSR offsets) as format 7, which has the arrays of format 6 (empty where there is nothing to hold).
 """
 import numpy as np
 
@@ -27,15 +29,19 @@ FORMAT_BATCH = "ekfslam-trajectory-3"
 FORMAT_OBSERVE = "ekfslam-trajectory-4"
 FORMAT_MODEL = "ekfslam-trajectory-5"
 FORMAT_APPEND = "ekfslam-trajectory-6"
+FORMAT_PREDICT = "ekfslam-trajectory-7"
 EDIT_KINDS = ("remove", "constrain", "merge", "merge_batch")        # what record_edit takes
 OBSERVE = "observe"                                                  # the fifth kind: record_observation's, number 4 in a file
 OBSERVE_MODEL = "observe_model"                                      # the sixth kind: record_model_observation's, number 5 in a file
 APPEND_MODEL = "append_model"                                        # the seventh kind: record_model_append's, number 6 in a file
-_KINDS = EDIT_KINDS + (OBSERVE, OBSERVE_MODEL, APPEND_MODEL)
+PREDICT_MODEL = "predict_model"                                      # the eighth kind: record_model_predict's, number 7 in a file
+_KINDS = EDIT_KINDS + (OBSERVE, OBSERVE_MODEL, APPEND_MODEL, PREDICT_MODEL)
+_FORMATS = (FORMAT, FORMAT_EDITS, FORMAT_BATCH, FORMAT_OBSERVE, FORMAT_MODEL, FORMAT_APPEND, FORMAT_PREDICT)
 _STEP_ARRAYS = ("u", "obs_ptr", "obs", "lm_ptr", "lm_index", "lm_loc")
 _EDIT_ARRAYS = ("edit_step", "edit_kind", "edit_ptr", "edit_idx", "edit_delta", "edit_R")
 _MODEL_ARRAYS = ("model_edit", "model_id", "model_anchor", "model_gate")
 _APPEND_ARRAYS = ("append_edit", "append_ptr", "append_model", "append_z", "append_R", "append_signature")
+_PREDICT_ARRAYS = ("predict_edit", "predict_ptr", "predict_model", "predict_u", "predict_M")
 _OBSERVE_ARRAYS = ("observe_edit", "observe_Hr", "observe_Hl", "observe_gate", "observe_wrap", "observe_rows")
 
 
@@ -45,6 +51,7 @@ class TrajectoryLog:
         self.edits = []             # (step, kind, idx (1-based numbers), delta[2], R[2x2]) in the order they were made
         self.model_observations = {}  # position in self.edits of an 'observe_model' edit -> {model, anchor (2) or None, gate}
         self.model_appends = {}     # position in self.edits of an 'append_model' edit -> [(model, z (2), R (2x2), signature), ...]
+        self.model_predicts = {}    # position in self.edits of a 'predict_model' edit -> [(model, u (2 or 3), M (2x2 or 3x3)), ...]
         self.observations = {}      # position in self.edits of an 'observe' edit -> {Hr (2x3), Hl (2x2x2), gate, wrap (2), rows}
 
     def __len__(self):
@@ -126,6 +133,20 @@ class TrajectoryLog:
         self.model_appends[len(self.edits)] = ents
         self.edits.append((len(self), APPEND_MODEL, np.zeros(0, dtype=np.int64), np.zeros(2), np.zeros((2, 2))))
 
+    def record_model_predict(self, steps):
+        """One chain of motion steps (predict_model of ekf_slam_amd/slam.py) made now, i.e. after the len(self) steps recorded so far:
+        steps = [(model, u, M), ...], at least one, u and M of the size the model reads (2 and 2 x 2, or 3 and 3 x 3)."""
+        sts = []
+        for model, u, M in steps:
+            uv, Mm = np.asarray(u, dtype=np.float64).reshape(-1).copy(), np.asarray(M, dtype=np.float64)
+            if uv.size not in (2, 3) or Mm.size != uv.size * uv.size:
+                raise ValueError("record_model_predict: u has 2 or 3 values and M is square of that size")
+            sts.append((int(model), uv, Mm.reshape(uv.size, uv.size).copy()))
+        if not sts:
+            raise ValueError("record_model_predict: at least one step")
+        self.model_predicts[len(self.edits)] = sts
+        self.edits.append((len(self), PREDICT_MODEL, np.zeros(0, dtype=np.int64), np.zeros(2), np.zeros((2, 2))))
+
     def save(self, path):
         def ragged(parts, width):
             ptr = np.cumsum([0] + [len(p) for p in parts])
@@ -140,7 +161,7 @@ class TrajectoryLog:
             return
         e_ptr, e_idx = ragged([e[2] for e in self.edits], 0)
         fmt = FORMAT_BATCH if any(e[1] == "merge_batch" for e in self.edits) else FORMAT_EDITS
-        if self.observations or self.model_observations or self.model_appends:
+        if self.observations or self.model_observations or self.model_appends or self.model_predicts:
             fmt = FORMAT_OBSERVE
             at = sorted(self.observations)
             ob = [self.observations[q] for q in at]
@@ -148,20 +169,30 @@ class TrajectoryLog:
                           observe_Hl=np.array([o["Hl"] for o in ob]).reshape(-1, 2, 2, 2), observe_gate=np.array([o["gate"] for o in ob]),
                           observe_wrap=np.array([o["wrap"] for o in ob], dtype=np.int64).reshape(-1, 2),
                           observe_rows=np.array([o["rows"] for o in ob], dtype=np.int64))
-        if self.model_observations or self.model_appends:
+        if self.model_observations or self.model_appends or self.model_predicts:
             fmt = FORMAT_MODEL
             at = sorted(self.model_observations)
             mo = [self.model_observations[q] for q in at]
             arrays.update(model_edit=np.array(at, dtype=np.int64), model_id=np.array([o["model"] for o in mo], dtype=np.int64),
                           model_anchor=np.array([np.full(2, np.nan) if o["anchor"] is None else o["anchor"] for o in mo]).reshape(-1, 2),
                           model_gate=np.array([o["gate"] for o in mo]))
-        if self.model_appends:
+        if self.model_appends or self.model_predicts:
             fmt = FORMAT_APPEND
             at = sorted(self.model_appends)
             ents = [e for q in at for e in self.model_appends[q]]
             arrays.update(append_edit=np.array(at, dtype=np.int64), append_ptr=np.cumsum([0] + [len(self.model_appends[q]) for q in at]),
                           append_model=np.array([e[0] for e in ents], dtype=np.int64), append_z=np.array([e[1] for e in ents]).reshape(-1, 2),
                           append_R=np.array([e[2] for e in ents]).reshape(-1, 2, 2), append_signature=np.array([e[3] for e in ents]))
+        if self.model_predicts:
+            fmt = FORMAT_PREDICT
+            at = sorted(self.model_predicts)
+            sts = [e for q in at for e in self.model_predicts[q]]
+            U, Mf = np.zeros((len(sts), 3)), np.zeros((len(sts), 3, 3))          # a model with two inputs: the leading entries
+            for k, (_, u, M) in enumerate(sts):
+                U[k, :u.size] = u
+                Mf[k, :u.size, :u.size] = M
+            arrays.update(predict_edit=np.array(at, dtype=np.int64), predict_ptr=np.cumsum([0] + [len(self.model_predicts[q]) for q in at]),
+                          predict_model=np.array([e[0] for e in sts], dtype=np.int64), predict_u=U, predict_M=Mf)
         np.savez_compressed(path, format=np.array(fmt), edit_step=np.array([e[0] for e in self.edits], dtype=np.int64),
                             edit_kind=np.array([_KINDS.index(e[1]) for e in self.edits], dtype=np.int64), edit_ptr=e_ptr,
                             edit_idx=e_idx.astype(np.int64), edit_delta=np.array([e[3] for e in self.edits]).reshape(-1, 2),
@@ -171,12 +202,11 @@ class TrajectoryLog:
     def load(path):
         g = np.load(path, allow_pickle=False)
         fmt = str(g["format"])
-        if fmt not in (FORMAT, FORMAT_EDITS, FORMAT_BATCH, FORMAT_OBSERVE, FORMAT_MODEL, FORMAT_APPEND):
-            raise ValueError("not an %s / %s / %s / %s / %s / %s file" % (FORMAT, FORMAT_EDITS, FORMAT_BATCH, FORMAT_OBSERVE, FORMAT_MODEL,
-                                                                         FORMAT_APPEND))
-        need = (_STEP_ARRAYS + (_EDIT_ARRAYS if fmt != FORMAT else ())
-                + (_OBSERVE_ARRAYS if fmt in (FORMAT_OBSERVE, FORMAT_MODEL, FORMAT_APPEND) else ())
-                + (_MODEL_ARRAYS if fmt in (FORMAT_MODEL, FORMAT_APPEND) else ()) + (_APPEND_ARRAYS if fmt == FORMAT_APPEND else ()))
+        if fmt not in _FORMATS:
+            raise ValueError("not an %s file" % " / ".join(_FORMATS))
+        ver = _FORMATS.index(fmt) + 1
+        need = (_STEP_ARRAYS + (_EDIT_ARRAYS if ver >= 2 else ()) + (_OBSERVE_ARRAYS if ver >= 4 else ())
+                + (_MODEL_ARRAYS if ver >= 5 else ()) + (_APPEND_ARRAYS if ver >= 6 else ()) + (_PREDICT_ARRAYS if ver >= 7 else ()))
         missing = [k for k in need if k not in g.files]
         if missing:
             raise ValueError("an %s file holds %s: %s is missing" % (fmt, ", ".join(need), ", ".join(missing)))
@@ -190,17 +220,27 @@ class TrajectoryLog:
                 a, b = g["edit_ptr"][q], g["edit_ptr"][q + 1]
                 t.edits.append((int(g["edit_step"][q]), _KINDS[int(g["edit_kind"][q])], g["edit_idx"][a:b].astype(np.int64),
                                 g["edit_delta"][q].copy(), g["edit_R"][q].copy()))
-        if fmt == FORMAT_APPEND:
+        if ver >= 7:
+            from ._lib import EKF_MOTION_INPUTS
+            for k, q in enumerate(g["predict_edit"]):
+                a, b = int(g["predict_ptr"][k]), int(g["predict_ptr"][k + 1])
+                sts = []
+                for e in range(a, b):
+                    model = int(g["predict_model"][e])
+                    nu = EKF_MOTION_INPUTS.get(model, 3)
+                    sts.append((model, g["predict_u"][e][:nu].copy(), g["predict_M"][e][:nu, :nu].copy()))
+                t.model_predicts[int(q)] = sts
+        if ver >= 6:
             for k, q in enumerate(g["append_edit"]):
                 a, b = int(g["append_ptr"][k]), int(g["append_ptr"][k + 1])
                 t.model_appends[int(q)] = [(int(g["append_model"][e]), g["append_z"][e].copy(), g["append_R"][e].copy(),
                                             float(g["append_signature"][e])) for e in range(a, b)]
-        if fmt in (FORMAT_MODEL, FORMAT_APPEND):
+        if ver >= 5:
             for k, q in enumerate(g["model_edit"]):
                 anchor = g["model_anchor"][k].copy()
                 t.model_observations[int(q)] = dict(model=int(g["model_id"][k]), anchor=None if np.all(np.isnan(anchor)) else anchor,
                                                     gate=float(g["model_gate"][k]))
-        if fmt in (FORMAT_OBSERVE, FORMAT_MODEL, FORMAT_APPEND):
+        if ver >= 4:
             for k, q in enumerate(g["observe_edit"]):
                 t.observations[int(q)] = dict(Hr=g["observe_Hr"][k].copy(), Hl=g["observe_Hl"][k].copy(), gate=float(g["observe_gate"][k]),
                                               wrap=g["observe_wrap"][k].astype(np.int64), rows=int(g["observe_rows"][k]))
@@ -209,7 +249,7 @@ class TrajectoryLog:
     def replay(self, engine, start=0, stop=None):
         """predict + measure for steps [start, stop) on anything with predict(u) / measure(obs, u, idx, loc) -- an Engine.  The edits
         recorded at positions [start, stop) are applied in front of their step through the engine's remove_landmarks /
-        constrain_landmarks / merge_landmarks / merge_landmarks_batch / observe_linear / observe_model / append_model (0-based there: the recorded 1-based numbers are converted here); the ones recorded
+        constrain_landmarks / merge_landmarks / merge_landmarks_batch / observe_linear / observe_model / append_model / predict_model (0-based there: the recorded 1-based numbers are converted here); the ones recorded
         at position len(self), after the last step, when stop is the end of the log."""
         stop = len(self) if stop is None else stop
 
@@ -227,6 +267,8 @@ class TrajectoryLog:
                     engine.observe_model(o["model"], delta, R, idx0, anchor=o["anchor"], gate=o["gate"])
                 elif kind == APPEND_MODEL:
                     engine.append_model(self.model_appends[q])
+                elif kind == PREDICT_MODEL:
+                    engine.predict_model(self.model_predicts[q])
                 elif kind == "remove":
                     engine.remove_landmarks(idx0)
                 elif kind == "constrain":

@@ -502,6 +502,41 @@ typedef struct ekf_model_match {
 } ekf_model_match;
 int32_t ekf_associate_model(ekf_handle *h, const ekf_model_obs *obs, int64_t m,
                             ekf_model_match *out /* m, required */, double *d2_all /* m x N row-major, may be NULL */);
+/* The MOTION step under the same conventions: "the robot moved by u through the model, and u has the covariance M".  ekf_predict keeps the
+ * reference's step (F(1,3), F(2,3) at the pre-motion heading and without pi/180, Q = (W C) W' of rank one) and is consistent with none of
+ * the calls above: a filter driven through ekf_observe_model / ekf_append_model moves here.  With p = x(0:2), theta = x(2) in degrees,
+ * k = 180/pi, the step is x_r' = f(x_r, u), P' = F P F' + V M V' with F = df/dx_r = I + [0 0 F02; 0 0 F12; 0 0 0] (the identity over the map)
+ * and V = df/du:
+ *   TURN_DRIVE  u = (d, t): turn by t degrees, then drive d.    (s, c) = sincosd(theta + t)       p' = p + d (c, s)
+ *               (F02, F12) = (-d s / k, d c / k)                V = [c F02; s F12; 0 1]            -- the reference's f: the same pose, bit for bit
+ *   ARC         u = (d, t): an arc of length d that turns by t. a = t / (2k), g = sin a / a, g' = (a cos a - sin a) / a^2 (both from their
+ *               series for |a| < 1/2: finite at t = 0, where the arc is the straight line), (s, c) = sincosd(theta + t / 2)
+ *               p' = p + d g (c, s)      (F02, F12) = (-d g s / k, d g c / k)      V = [g c, d (g' c - g s) / (2k); g s, d (g' s + g c) / (2k); 0 1]
+ *   POSE_DELTA  u = (dx, dy, t) in the robot frame.             (s, c) = sincosd(theta)            w = (c dx - s dy, s dx + c dy)   p' = p + w
+ *               (F02, F12) = (-w_1 / k, w_0 / k)                V = [c -s 0; s c 0; 0 0 1]         -- with u = 0: additive noise M in the robot frame
+ * and theta' = wrapTo360(theta + t) in all three, as ekf_predict forms it (so a sum of exactly 360 stays 360).  M is column-major 3 x 3; a
+ * model with two inputs reads its leading 2 x 2 block, M[0], M[1], M[3], M[4], and u[0], u[1] alone.
+ * A chain of m steps is carried out in order by ONE launch (counted under EKF_KERNEL_PREDICT) that reads and writes x, P(1:3,1:3) and
+ * P(1:3, map) once -- bit for bit what m calls with one step leave.  The landmarks, the landmark block of P, its pending pairs and s are
+ * not touched.  The call is EAGER (ekf_predict is recorded and carried out by whatever comes next; a recorded one is carried out first, by
+ * a launch of its own), returns without waiting for the device, does not flush and leaves ekf_pending as it found it; beside a pass in
+ * flight (cfg.async_flush) it does not wait for the pass.  ekf_get_Q reports the LAST step's V M V' afterwards.
+ * SHARDED handles are supported: everything the launch reads and writes is replicated, so the same call on every shard needs no exchange.
+ * Refused with nothing changed, in this order: h or steps NULL, m < 1 or m > EKF_PREDICT_MODEL_MAX; per step an unknown model,
+ * reserved != 0, a non-finite entry of u in use, then an M (the part in use) that is not finite, not exactly symmetric, or has a negative
+ * diagonal entry, a negative 2 x 2 principal minor or, with three inputs, a negative determinant (all EKF_ERR_INVALID_ARG); then, with the
+ * measure loop settled, a sharded correction between begin and finish (EKF_ERR_STATE).
+ * ekf_motion_evaluate is the function the kernel runs, on the host (pure, like ekf_model_evaluate): x_new, F and V (both column-major
+ * 3 x 3) at the robot state xr; EKF_ERR_INVALID_ARG for a NULL argument or an unknown model. */
+enum { EKF_MOTION_TURN_DRIVE = 1, EKF_MOTION_ARC = 2, EKF_MOTION_POSE_DELTA = 3 };
+#define EKF_PREDICT_MODEL_MAX 32
+typedef struct ekf_motion {
+    int32_t model, reserved;   /* EKF_MOTION_*; reserved: 0                                                    */
+    double  u[3];              /* the inputs; angles in degrees                                               */
+    double  M[9];              /* column-major covariance of u                                                */
+} ekf_motion;
+int32_t ekf_predict_model(ekf_handle *h, const ekf_motion *steps, int64_t m);
+int32_t ekf_motion_evaluate(int32_t model, const double xr[3], const double u[3], double x_new[3], double F[9], double V[9]);
 /* Diagnostic -- a fault injector for tests of the device-resident measure loop's verification, of no use to a host: overwrites the DEVICE copy
  * of signature idx (0-based) and leaves the host mirror alone.  The next ekf_measure whose association involves that landmark then queues its
  * launches from a prediction the device contradicts; every launch stays inside the state (a correction falls back to the predicted landmark,

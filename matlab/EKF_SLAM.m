@@ -231,6 +231,32 @@ classdef EKF_SLAM < handle
             if nargin < 4, signature = []; end
             idx = h.addLandmarksModel(4, z(:)', R, signature);
         end
+        function predictModel(h, model, u, M)
+            % MOTION under observeModel's conventions: step b moves the robot by u(b, :) through model(b) -- 1 turn-then-drive
+            % [d deg], 2 an arc [length deg], 3 a pose increment in the robot frame [dx dy deg] -- and u has the covariance
+            % M(:, :, b) (2x2 for models 1 and 2, 3x3 for model 3, or 3x3 throughout with the leading block in use; one M: shared by
+            % all).  x_r <- f(x_r, u), P <- F P F' + V M V' with the true Jacobians (theta in degrees: the factor pi/180 where it
+            % belongs), the whole chain (at most 32 steps) in order by one launch; nothing is flushed or waited for.  Not a method of
+            % the reference, whose predict keeps F at the pre-motion heading without pi/180 and a rank-one Q.
+            model = double(model(:)); m = numel(model);
+            u = double(u); if size(u, 1) ~= m, u = reshape(u, m, []); end
+            u(:, end + 1:3) = 0;
+            M = double(M); if size(M, 3) == 1, M = repmat(M, [1 1 m]); end
+            M3 = zeros(3, 3, m); M3(1:size(M, 1), 1:size(M, 2), :) = M;
+            h.gateway('predict_model', model, u, M3);
+        end
+        function predictTurnDrive(h, d, deg, M)
+            % 'The robot turned by deg degrees, then drove d; [d deg] has the covariance M (2x2)'; vectors d, deg: a chain of steps.
+            h.predictModel(ones(numel(d), 1), [d(:) deg(:)], M);
+        end
+        function predictArc(h, d, deg, M)
+            % 'The robot drove an arc of length d while turning by deg degrees; [d deg] has the covariance M (2x2)'.
+            h.predictModel(2 * ones(numel(d), 1), [d(:) deg(:)], M);
+        end
+        function predictPoseDelta(h, dx, dy, deg, M)
+            % 'The pose changed by [dx dy deg] in the robot frame, with covariance M (3x3)'; zeros: additive noise M in the robot frame.
+            h.predictModel(3 * ones(numel(dx), 1), [dx(:) dy(:) deg(:)], M);
+        end
         function [match, d2] = associateModel(h, model, z, R, gate)
             % WHICH landmark each sighting of a scan belongs to, under observeModel's conventions: observation k was seen as z(k, :)
             % through model(k) (1 range and bearing, 2 range, 3 bearing, 4 the position in the robot frame) with noise covariance

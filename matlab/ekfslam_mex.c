@@ -23,8 +23,8 @@
 
 /* The map-editing entry points (ekf_remove_landmarks; ekf_constrain_landmarks, ekf_merge_landmarks, ekf_landmark_distance;
  * ekf_nearest_landmarks; ekf_merge_landmarks_batch) the linear observation (ekf_observe_linear), the model observation
- * (ekf_observe_model), the append through a model (ekf_append_model) and the association of a scan under the models' conventions
- * (ekf_associate_model) are the ones this gateway can live without: bound weakly, so that the gateway still links against a libekfslam (or a stand-in) that
+ * (ekf_observe_model), the append through a model (ekf_append_model), the association of a scan under the models' conventions
+ * (ekf_associate_model) and the motion steps under them (ekf_predict_model) are the ones this gateway can live without: bound weakly, so that the gateway still links against a libekfslam (or a stand-in) that
  * predates them; their commands then raise a MATLAB error instead. */
 #if defined(__GNUC__)
 #pragma weak ekf_remove_landmarks
@@ -37,6 +37,7 @@
 #pragma weak ekf_observe_model
 #pragma weak ekf_append_model
 #pragma weak ekf_associate_model
+#pragma weak ekf_predict_model
 #define HAVE_REMOVE_LANDMARKS (ekf_remove_landmarks != 0)
 #define HAVE_CONSTRAIN_LANDMARKS (ekf_constrain_landmarks != 0)
 #define HAVE_MERGE_LANDMARKS (ekf_merge_landmarks != 0)
@@ -47,6 +48,7 @@
 #define HAVE_OBSERVE_MODEL (ekf_observe_model != 0)
 #define HAVE_APPEND_MODEL (ekf_append_model != 0)
 #define HAVE_ASSOCIATE_MODEL (ekf_associate_model != 0)
+#define HAVE_PREDICT_MODEL (ekf_predict_model != 0)
 #else
 #define HAVE_REMOVE_LANDMARKS 1
 #define HAVE_CONSTRAIN_LANDMARKS 1
@@ -58,6 +60,7 @@
 #define HAVE_OBSERVE_MODEL 1
 #define HAVE_APPEND_MODEL 1
 #define HAVE_ASSOCIATE_MODEL 1
+#define HAVE_PREDICT_MODEL 1
 #endif
 
 static void need(int nrhs, int want, const char *cmd) {
@@ -369,6 +372,25 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
             out[4 * m + k] = (double)match[k].within_gate; out[5 * m + k] = (double)match[k].irregular;
         }
         if (all) plhs[1] = all;
+        return;
+    }
+    if (!strcmp(cmd, "predict_model")) {          /* (h, model m x 1 (1..3), u m x 3, M 3 x 3 x m): a chain of motion steps with their true Jacobians, in order,
+                                                     one launch; a model with two inputs reads u(:, 1:2) and M(1:2, 1:2, k) */
+        need(nrhs, 5, cmd);
+        if (!HAVE_PREDICT_MODEL) mexErrMsgIdAndTxt("ekfslam:usage", "predict_model: this libekfslam has no ekf_predict_model");
+        const mwSize m = prhs[2] ? mxGetNumberOfElements(prhs[2]) : 0;
+        if (m < 1 || m > EKF_PREDICT_MODEL_MAX) mexErrMsgIdAndTxt("ekfslam:usage", "predict_model: between 1 and %d steps in one call", EKF_PREDICT_MODEL_MAX);
+        if (!mxGetPr(prhs[2]) || !prhs[3] || mxGetM(prhs[3]) != m || mxGetNumberOfElements(prhs[3]) != 3 * m || !mxGetPr(prhs[3]))
+            mexErrMsgIdAndTxt("ekfslam:usage", "predict_model: u needs m x 3 elements, one row per entry of model");
+        if (!prhs[4] || mxGetNumberOfElements(prhs[4]) != 9 * m || !mxGetPr(prhs[4]))
+            mexErrMsgIdAndTxt("ekfslam:usage", "predict_model: M needs 3 x 3 x m elements");
+        ekf_motion o[EKF_PREDICT_MODEL_MAX];
+        for (mwSize b = 0; b < m; ++b) {
+            o[b].model = (int32_t)mxGetPr(prhs[2])[b]; o[b].reserved = 0;
+            for (int q = 0; q < 3; ++q) o[b].u[q] = mxGetPr(prhs[3])[q * m + b];        /* column-major m x 3 */
+            for (int q = 0; q < 9; ++q) o[b].M[q] = mxGetPr(prhs[4])[9 * b + q];
+        }
+        check(h, ekf_predict_model(h, o, (int64_t)m));
         return;
     }
     if (!strcmp(cmd, "merge_landmarks_batch")) {  /* d2 = (h, pairs k x 2 [keep drop], R 2x2): k x 1; landmark numbers 1-based, as they are before the call */
