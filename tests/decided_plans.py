@@ -10,6 +10,8 @@ import math
 
 import numpy as np
 
+PARAMS = dict(w_pos=1.0, Rc=(0.01, 0.01), s_thresh=0.5)     # the position-weighted likelihood: its cost rejects some signature matches
+
 _D2R = math.pi / 180.0
 
 

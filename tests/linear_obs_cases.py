@@ -184,3 +184,16 @@ def random_state(rng, N, corr=0.6):
     P = A @ A.T / (n + 4) + np.diag(0.2 + rng.random(n))
     x = np.concatenate([[1.0, -2.0, 30.0], 20.0 * rng.standard_normal(2 * N)])
     return x, P, np.arange(1, N + 1, dtype=np.float64)
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# the shapes shared by the GPU tests of the linear and the model families
+# ------------------------------------------------------------------------------------------------------------------
+N0 = 150                        # 300 columns: two workgroups of a gather, the second one partly idle
+STORES = [(16, "f64"), (64, "f64"), (256, "f32"), (256, "f32_mixed"), (256, "f32_split")]       # helpers.STORES_ALL without tile 128, as this family has run since ekf_observe_linear
+
+
+def edge_landmark(T):
+    """First landmark of a tile row near the middle of the map; the middle itself where one tile row holds the whole map."""
+    per_row = T // 2
+    return per_row * max(1, (N0 // 2) // per_row) if per_row < N0 else N0 // 2

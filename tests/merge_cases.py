@@ -3,7 +3,7 @@ linear Kalman update between two landmarks as include/ekfslam.h states it, an in
 factored form for the states P = diag(d) + U U' the tests at size start from.  No GPU, no library."""
 import numpy as np
 
-from removal_cases import expected_after
+from removal_cases import expected_after, observe
 
 
 def _args(x, i, j, delta, R):
@@ -118,3 +118,33 @@ class Factored:
         self.x, self.d, self.U = np.delete(self.x, ent), np.delete(self.d, ent), np.delete(self.U, ent, axis=0)
         self.K = [np.delete(K, ent, axis=0) for K in self.K]
         self.G = [np.delete(G, ent, axis=1) for G in self.G]
+
+
+def tile_edge_landmark(T, N):
+    """First landmark of a tile row near the middle of a map of N landmarks (tile edge T elements)."""
+    per_row = T // 2
+    return per_row * max(1, (N // 2) // per_row)
+
+
+def continuation(ex, es, tile, batch, capacity, hole):
+    """Operations (pure function of the state after the merge): appends that cross a tile-row edge, measure() scans with corrections
+    around the merged pair and new landmarks, two full batches of corrections."""
+    N = es.size
+    per_row = tile // 2
+    ops = []
+    n_app = per_row - N % per_row + 3
+    assert N + n_app + 8 <= capacity
+    rng = np.random.default_rng(2)
+    for i in range(n_app):
+        ops.append(("append", rng.uniform(-20, 20, 2), 5000.0 + i))
+    around = sorted({max(hole - 1, 0), min(hole, N - 1), min(hole + 1, N - 1), 1, N - 2, N // 3})
+    lm_index = np.arange(1, capacity + 1, dtype=np.float64)
+    lm_loc = np.random.default_rng(3).uniform(-20, 20, (capacity, 2))
+    for t in range(3):
+        rows = [list(observe(ex, k, dr=0.01 * (t + 1))) + [float(es[k])] for k in around[t::2] + around[:2]]
+        rows.append([3.0 + t, 45.0, 9e6 + t])                # matches no signature: appended (EKF_SLAM_UC.m:121-123)
+        ops.append(("measure", np.array(rows), lm_index, lm_loc))
+    for i in range(2 * batch):
+        k = around[i % len(around)] if i % 3 else int(rng.integers(0, N))
+        ops.append(("correct", observe(ex, k, dr=0.02), k))
+    return ops

@@ -145,3 +145,31 @@ def observe_model_dense(x, P, o):
         return x.copy(), P.copy(), res
     Kg = G.T @ np.linalg.inv(S)
     return x + Kg @ nu, P - Kg @ G, res
+
+
+def fmt(vals):
+    """A line of operands for the host programs of tests/support: every value with all its digits."""
+    return " ".join(repr(float(v)) for v in vals)
+
+
+def small_line(o, x, P):
+    """The 38 operands of linear_small for observation o on the dense state (x, P)."""
+    lm = o["landmarks"]
+    rows = list(range(3)) + sum(([3 + 2 * k, 4 + 2 * k] for k in lm), [])
+    Ps, xs = np.zeros((7, 7)), np.zeros(7)
+    Ps[:len(rows), :len(rows)] = P[np.ix_(rows, rows)]
+    xs[:len(rows)] = x[rows]
+    sm = list(Ps[:3, :3].reshape(-1))
+    for b in range(2):
+        sm += [Ps[t, 3 + 2 * b + r] for t in range(3) for r in range(2)]
+    for b in range(2):
+        a = 3 + 2 * b
+        sm += [Ps[a, a], Ps[a + 1, a], Ps[a + 1, a + 1]]
+    sm += [Ps[3 + r, 5 + c] for r in range(2) for c in range(2)]
+    sm += list(xs)
+    R = effective_R(o)
+    anchor = [0.0, 0.0] if o["anchor"] is None else o["anchor"]
+    z = o["z"].copy()
+    if o["rows"] == 1:
+        z[1] = 0.0
+    return "small %d %d %s" % (o["model"], 1 if lm else 0, fmt(list(z) + list(R.reshape(-1)) + [o["gate"]] + list(anchor) + sm))

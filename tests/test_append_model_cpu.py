@@ -12,10 +12,8 @@ import pytest
 
 import append_model_cases as A
 import model_obs_cases as M
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-RPOS = np.array([[0.02, 0.005], [0.005, 0.03]])
-REL = 1e-6
+from helpers import REL, RPOS, RecorderBase, host_build, line_program, same_npz
+from mex_harness import PRELUDE_SHOWN, ROOT, driver, driver_without, transcript_of
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -24,17 +22,12 @@ REL = 1e-6
 @pytest.fixture(scope="module")
 def host(tmp_path_factory):
     """The stand-alone host build of ekfm::model_invert (and model_eval at the point it returns): host(cases) -> one dict per case."""
-    exe = str(tmp_path_factory.mktemp("model_invert") / "model_invert_host")
-    subprocess.run(["g++", "-O2", "-mfma", "-ffp-contract=off", "-I", os.path.join(ROOT, "ekf_slam_amd", "csrc"),
-                    os.path.join(ROOT, "tests", "support", "model_invert_host.cpp"), "-o", exe], check=True)
+    rows_of = line_program(tmp_path_factory, "model_invert_host")
 
     def run(cases):
         lines = ["invert %d %s" % (m, " ".join(repr(float(v)) for v in list(xr) + list(z))) for m, xr, z in cases]
-        out = subprocess.run([exe], input="\n".join(lines) + "\n", check=True, capture_output=True, text=True).stdout
-        rows = [[float(v) for v in ln.split()] for ln in out.strip().split("\n")]
-        assert len(rows) == len(cases)
         return [dict(ok=r[0] == 1, t=np.array(r[1:3]), gth=np.array(r[3:5]), Gz=np.array(r[5:9]).reshape(2, 2), posed=r[9] == 1,
-                     hx=np.array(r[10:12]), H=np.array(r[12:26]).reshape(2, 7)) for r in rows]
+                     hx=np.array(r[10:12]), H=np.array(r[12:26]).reshape(2, 7)) for r in rows_of(lines)]
     return run
 
 
@@ -133,9 +126,7 @@ def test_the_dense_restatement_is_the_block_form_of_the_joint_covariance():
 def test_kernel_source_on_the_host_batches_bit_for_bit_and_matches_the_dense_restatement(tmp_path):
     """tests/support/append_model_host_emulation.cpp: k_append_model with m = 1, 3, 9 entries against m launches of one, tiles of edge 16
     and 64, double and float, 0 and 3 pairs pending; then every case's new rows against append_model_dense on the live state before."""
-    exe = str(tmp_path / "append_model_host_emulation")
-    subprocess.run(["g++", "-O2", "-mfma", "-ffp-contract=off", "-std=c++17", "-I", os.path.join(ROOT, "ekf_slam_amd", "csrc"),
-                    os.path.join(ROOT, "tests", "support", "append_model_host_emulation.cpp"), "-o", exe], check=True)
+    exe = host_build("append_model_host_emulation", str(tmp_path / "append_model_host_emulation"))
     r = subprocess.run([exe, str(tmp_path)], capture_output=True, text=True)
     lines = r.stdout.strip().split("\n")
     assert r.returncode == 0, r.stdout[-3000:]
@@ -192,12 +183,6 @@ def _steps(log, n):
         log.record([0.1, 1.0 + k], np.array([[1.0, 2.0, 3.0]]) if k % 2 else None, [1.0, 2.0], [[0.0, 1.0], [2.0, 3.0]])
 
 
-def _same_file(a, b):
-    ga, gb = np.load(a), np.load(b)
-    return ga.files == gb.files and all(ga[k].dtype == gb[k].dtype and ga[k].shape == gb[k].shape and ga[k].tobytes() == gb[k].tobytes()
-                                        for k in ga.files)
-
-
 def test_trajectory_format_six_round_trip_and_the_older_formats(tmp_path):
     from ekf_slam_amd.trajectory import (FORMAT, FORMAT_APPEND, FORMAT_BATCH, FORMAT_EDITS, FORMAT_MODEL, FORMAT_OBSERVE, TrajectoryLog)
     assert FORMAT_APPEND == "ekfslam-trajectory-6"
@@ -222,7 +207,7 @@ def test_trajectory_format_six_round_trip_and_the_older_formats(tmp_path):
         back = TrajectoryLog.load(tmp_path / (name + ".npz"))
         assert len(back) == len(log) and len(back.edits) == len(log.edits) and back.model_appends == {}
         back.save(tmp_path / (name + "_again.npz"))
-        assert _same_file(tmp_path / (name + ".npz"), tmp_path / (name + "_again.npz"))
+        assert same_npz(tmp_path / (name + ".npz"), tmp_path / (name + "_again.npz"))
     # version 6: scans of new landmarks among the other edits
     scan3 = A.scan(np.random.default_rng(1), 3, 700.0)
     six = TrajectoryLog(); _steps(six, 2)
@@ -245,7 +230,7 @@ def test_trajectory_format_six_round_trip_and_the_older_formats(tmp_path):
         assert got[0] == want[0] and got[3] == want[3]
         np.testing.assert_array_equal(got[1], want[1]); np.testing.assert_array_equal(got[2], want[2])
     back.save(tmp_path / "six_again.npz")
-    assert _same_file(tmp_path / "six.npz", tmp_path / "six_again.npz")
+    assert same_npz(tmp_path / "six.npz", tmp_path / "six_again.npz")
     r = _Replayed()
     back.replay(r)
     assert r.calls == [("predict",), ("predict",), ("measure",), ("remove", [6]),
@@ -271,22 +256,12 @@ def test_trajectory_format_six_round_trip_and_the_older_formats(tmp_path):
 # ------------------------------------------------------------------------------------------------------------------
 # the Python layers over a stand-in for the library
 # ------------------------------------------------------------------------------------------------------------------
-class _Recorder:
+class _Recorder(RecorderBase):
+    status_string = b"landmark capacity exhausted"
+    last_error = b"append_model: injected"
+
     def __init__(self, N=7):
         self.calls, self.fail, self.N = [], 0, N
-
-    def ekf_config_default(self, pcfg, mode):
-        from ekf_slam_amd import _lib as L
-        cfg = ctypes.cast(pcfg, ctypes.POINTER(L.EkfConfig)).contents
-        cfg.mode, cfg.batch = mode, 1
-        return 0
-
-    def ekf_create(self, pcfg, ph):
-        ctypes.cast(ph, ctypes.POINTER(ctypes.c_void_p)).contents.value = 0x1000
-        return 0
-
-    def ekf_destroy(self, h):
-        return 0
 
     def ekf_num_landmarks(self, h, pn):
         pn._obj.value = self.N
@@ -304,12 +279,6 @@ class _Recorder:
         self.calls.append(("invert", model, [xr[i] for i in range(3)], [z[0], z[1]]))
         t[1], Gx[5], Gz[2] = 7.0, 8.0, 9.0
         return self.fail
-
-    def ekf_status_string(self, rc):
-        return b"landmark capacity exhausted"
-
-    def ekf_last_error(self, h):
-        return b"append_model: injected"
 
 
 def test_engine_and_slam_layers_marshal_a_scan_once(monkeypatch):
@@ -379,9 +348,6 @@ def test_shard_group_sends_the_scan_to_every_shard(monkeypatch):
 # ------------------------------------------------------------------------------------------------------------------
 # the MEX gateway
 # ------------------------------------------------------------------------------------------------------------------
-MOCK = os.path.join(ROOT, "tests", "support", "mex_mock")
-INCLUDES = ["-I", os.path.join(ROOT, "include"), "-I", os.path.join(ROOT, "tests", "support", "mex_api_subset"), "-I", MOCK]
-GCC = ["gcc", "-std=c99", "-Wall", "-Wextra", "-Werror", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"]
 
 _STUB = r'''
 #include <stdio.h>
@@ -401,31 +367,7 @@ int32_t ekf_append_model(ekf_handle *h, const ekf_model_init *o, int64_t m, int6
 }
 '''
 
-_DRIVER = r'''
-#include <setjmp.h>
-#include <stdio.h>
-#include "ekfslam.h"
-#include "mex_mock.h"
-void arm_failure(void);
-static mxArray *out[4];
-static int call(const char *what, int nlhs, int nrhs, const mxArray **prhs) {
-    out[0] = 0;
-    if (setjmp(mock_err_jmp)) { printf("MEX %s nrhs=%d -> ERROR %s | %s\n", what, nrhs, mock_err_id, mock_err_msg); return 1; }
-    mexFunction(nlhs, out, nrhs, prhs);
-    printf("MEX %s nrhs=%d -> ok", what, nrhs);
-    if (out[0] && mxGetClassID(out[0]) != mxUINT64_CLASS) {
-        printf(" out0=%zux%zu[", mxGetM(out[0]), mxGetN(out[0]));
-        for (size_t i = 0; i < mxGetM(out[0]) * mxGetN(out[0]); ++i) printf(i ? ",%g" : "%g", mxGetPr(out[0])[i]);
-        printf("]");
-    }
-    printf("\n");
-    return 0;
-}
-#define D1(v) mock_double(1, 1, (const double[]){ v })
-int main(void) {
-    const mxArray *cr[3] = { mock_string("create"), D1(1), D1(64) };
-    if (call("create", 1, 3, cr)) return 1;
-    const mxArray *h = out[0];
+_DRIVER = driver(r'''
     /* one entry: range and bearing */
     const mxArray *z1 = mock_double(1, 2, (const double[]){ 7, 8 }), *R1 = mock_double(2, 2, (const double[]){ 4, 1, 1, 9 });
     const mxArray *one[6] = { mock_string("append_model"), h, D1(1), z1, R1, D1(41) };
@@ -454,57 +396,16 @@ int main(void) {
     if (!call("append_model noh", 1, 6, bad)) return 1;
     arm_failure();
     if (!call("append_model", 1, 6, one)) return 1;
-    const mxArray *de[2] = { mock_string("destroy"), h };
-    if (call("destroy", 0, 2, de)) return 1;
-    printf("LOCKS %d\nMISUSE %d\n", mock_lock_count, mock_misuse);
-    return 0;
-}
-'''
+''', PRELUDE_SHOWN)
 
-_DRIVER_WITHOUT = r'''
-#include <setjmp.h>
-#include <stdio.h>
-#include "ekfslam.h"
-#include "mex_mock.h"
-static mxArray *out[4];
-static int call(const char *what, int nrhs, const mxArray **prhs) {
-    out[0] = 0;
-    if (setjmp(mock_err_jmp)) { printf("MEX %s nrhs=%d -> ERROR %s | %s\n", what, nrhs, mock_err_id, mock_err_msg); return 1; }
-    mexFunction(1, out, nrhs, prhs);
-    printf("MEX %s nrhs=%d -> ok\n", what, nrhs);
-    return 0;
-}
-#define D1(v) mock_double(1, 1, (const double[]){ v })
-int main(void) {
-    const mxArray *cr[3] = { mock_string("create"), D1(1), D1(64) };
-    if (call("create", 3, cr)) return 1;
-    const mxArray *h = out[0];
+_DRIVER_WITHOUT = driver_without(r'''
     const mxArray *ap[6] = { mock_string("append_model"), h, D1(1), mock_double(1, 2, (const double[]){ 7, 8 }), mock_double(2, 2, (const double[]){ 4, 1, 1, 9 }), D1(41) };
-    if (!call("append_model", 6, ap)) return 1;
-    const mxArray *pr[3] = { mock_string("predict"), h, mock_double(2, 1, (const double[]){ 0.1, 3 }) };
-    if (call("predict", 3, pr)) return 1;
-    const mxArray *de[2] = { mock_string("destroy"), h };
-    if (call("destroy", 2, de)) return 1;
-    printf("LOCKS %d\nMISUSE %d\n", mock_lock_count, mock_misuse);
-    return 0;
-}
-'''
-
-
-def _build_and_run(files, exe):
-    r = subprocess.run(GCC + INCLUDES + [os.path.join(ROOT, "matlab", "ekfslam_mex.c"), os.path.join(MOCK, "mex_mock.c"),
-                                         os.path.join(MOCK, "abi_stub.c")] + files + ["-o", exe, "-lm"], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-4000:]
-    r = subprocess.run([exe], capture_output=True, text=True, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=0"))
-    assert r.returncode == 0, "the gateway misbehaved under the mock:\n" + r.stdout[-2000:] + r.stderr[-4000:]
-    return r.stdout.splitlines()
+    if (!call("append_model", 1, 6, ap)) return 1;
+''')
 
 
 def test_mex_gateway_marshals_a_scan_once(tmp_path):
-    stub, drv = tmp_path / "append_stub.c", tmp_path / "append_drv.c"
-    stub.write_text(_STUB)
-    drv.write_text(_DRIVER)
-    t = _build_and_run([str(stub), str(drv)], str(tmp_path / "drv"))
+    t = transcript_of(tmp_path, _STUB, _DRIVER)
     # R column-major as MATLAB holds it; the ABI's 0-based first index comes back as 1-based numbers, one per entry
     i = t.index("ABI ekf_append_model m=1 first=1 | model=1 reserved=0 z=7,8 R=4,1,1,9 s=41")
     assert t[i + 1] == "MEX append_model nrhs=6 -> ok out0=1x1[41]"
@@ -522,9 +423,7 @@ def test_mex_gateway_marshals_a_scan_once(tmp_path):
 
 
 def test_the_gateway_still_links_against_a_library_without_the_symbol(tmp_path):
-    drv = tmp_path / "without_drv.c"
-    drv.write_text(_DRIVER_WITHOUT)
-    t = _build_and_run([str(drv)], str(tmp_path / "drv"))
+    t = transcript_of(tmp_path, _DRIVER_WITHOUT)
     assert any(ln.startswith("MEX append_model ") and "ERROR ekfslam:usage" in ln and "this libekfslam has no ekf_append_model" in ln for ln in t)
     assert "MEX predict nrhs=3 -> ok" in t and t[-2:] == ["LOCKS 0", "MISUSE 0"]
 

@@ -2,7 +2,7 @@
 DESIGN.md section 3k).
 
 The yardstick is the NumPy restatement of tests/append_model_cases.py applied to THE STATE THE ENGINE REPORTED BEFORE THE CALL; stores,
-tolerances and helpers are those of tests/test_linear_obs_gpu.py.  Where two engines must agree because they ran the same arithmetic on
+tolerances and helpers are those of tests/helpers.py.  Where two engines must agree because they ran the same arithmetic on
 the same inputs -- a batch against single calls, batch b against batch 1, the asynchronous pass against the synchronous one, the
 device-decided loop against the waited one, shards against one engine, a replayed log -- the comparison is assert_array_equal.
 
@@ -15,11 +15,11 @@ import pytest
 
 import append_model_cases as A
 import model_obs_cases as M
-import test_linear_obs_gpu as T
+from helpers import R2, REL, RPOS, U2, assert_same, check_state, engine, getters, loaded, state, status_of
+from linear_obs_cases import STORES
 from removal_cases import lowrank_data, observe
 
 pytestmark = pytest.mark.gpu
-U2, R2, RPOS, REL = T.U2, T.R2, T.RPOS, T.REL
 START = {1: 128, 2: 127, 9: 123, 32: 112}                  # landmarks before a batch of m: it ends beyond landmark 128
 
 
@@ -32,7 +32,7 @@ def history(engines, x, ks):
 def pair_of(N, pending, **kw):
     """Two engines with the same state and history: `pending` corrections, deferred where batch > pending."""
     x = lowrank_data(N, 5)[0]
-    e, twin = T.loaded(N, 5, **kw), T.loaded(N, 5, **kw)
+    e, twin = loaded(N, 5, **kw), loaded(N, 5, **kw)
     history([e, twin], x, (5, N // 2, N - 3, 11, 40)[:pending])
     return e, twin
 
@@ -46,7 +46,7 @@ def same_state(a, b):
 # ------------------------------------------------------------------------------------------------------------------
 # 1. against the dense restatement
 # ------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("tile,storage", T.STORES)
+@pytest.mark.parametrize("tile,storage", STORES)
 @pytest.mark.parametrize("pending", [0, 5])
 def test_a_scan_against_the_dense_restatement(tile, storage, pending):
     N = START[9]
@@ -55,13 +55,13 @@ def test_a_scan_against_the_dense_restatement(tile, storage, pending):
     rng = np.random.default_rng(3)
     for name, entries in (("both models, one each", A.scan(rng, 2)), ("a scan of nine over the edges", A.scan(rng, 9, 6000.0)),
                           ("range and bearing alone", A.scan(rng, 1, 7000.0)), ("relative xy alone", A.scan(rng, 2, 8000.0)[1:])):
-        x0, s0, P0 = T.state(twin)                            # (reading flushes the twin; e keeps its pairs pending)
+        x0, s0, P0 = state(twin)                            # (reading flushes the twin; e keeps its pairs pending)
         ex, es, eP = A.append_model_dense(x0, s0, P0, entries)
         first = e.append_model(entries)
         assert first == x0.size // 2 - 1 and e.pending() == pending
         twin.append_model(entries)
         np.testing.assert_array_equal(e.get_s(), es)
-        T.check_state(e, ex, eP, storage, name)
+        check_state(e, ex, eP, storage, name)
         pending = 0                                           # (check_state read P: the pairs are applied now)
     assert e.N == N + 13
 
@@ -69,7 +69,7 @@ def test_a_scan_against_the_dense_restatement(tile, storage, pending):
 # ------------------------------------------------------------------------------------------------------------------
 # 2. a batch of m is m single calls, bit for bit
 # ------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("tile,storage", T.STORES)
+@pytest.mark.parametrize("tile,storage", STORES)
 @pytest.mark.parametrize("m", [1, 2, 9, 32])
 def test_a_batch_is_bit_for_bit_its_single_calls(tile, storage, m):
     N = START[m]
@@ -166,9 +166,9 @@ def _play(e, ops):
 @pytest.fixture(scope="module")
 def schedule_reference():
     ops = _schedule(23, 18, 70, 44)
-    one = T.loaded(18, 5, capacity=48, tile=16, batch=1)
+    one = loaded(18, 5, capacity=48, tile=16, batch=1)
     _play(one, ops)
-    return ops, T.getters(one)
+    return ops, getters(one)
 
 
 @pytest.mark.parametrize("batch,asy", [(8, False), (3, True), (8, True)])
@@ -177,11 +177,11 @@ def test_a_schedule_with_model_appends_is_bit_for_bit_that_of_batch_one(schedule
     kinds = [op[0] for op in ops]
     assert kinds.count("append_model") >= 8 and kinds.count("remove") >= 2 and kinds.count("merge") >= 2 and kinds.count("observe") >= 8
     assert all(np.all(np.isfinite(g)) for g in want)
-    e = T.loaded(18, 5, capacity=48, tile=16, batch=batch, async_flush=asy)
+    e = loaded(18, 5, capacity=48, tile=16, batch=batch, async_flush=asy)
     beside = _play(e, ops)
     assert beside >= 4                                        # appends with pairs pending (asynchronous: beside the pass that holds them)
     assert e.N > 24                                           # the map crossed the tile-row edge at 24 landmarks
-    for got, ref in zip(T.getters(e), want):
+    for got, ref in zip(getters(e), want):
         np.testing.assert_array_equal(got, ref)
 
 
@@ -191,7 +191,7 @@ def test_a_schedule_with_model_appends_is_bit_for_bit_that_of_batch_one(schedule
 @pytest.mark.parametrize("batch", [1, 8])
 def test_between_the_scans_of_the_device_decided_loop(batch):
     from decided_plans import make_plan
-    from test_decided_assoc_gpu import PARAMS
+    from decided_plans import PARAMS
     from ekf_slam_amd.engine import Engine
     plan = make_plan(7, 300, 24, 8)
     runs, firsts = {}, {}
@@ -206,7 +206,7 @@ def test_between_the_scans_of_the_device_decided_loop(batch):
                 firsts.setdefault(mode, []).append(e.append_model(A.scan(rng, 3 if t != 9 else 1, 5000.0 + 10 * t)))
         runs[mode] = e
     assert runs[4].N > 40 and firsts[4] == firsts[1] and len(firsts[4]) == 3
-    T.assert_same(runs[4], runs[1])
+    assert_same(runs[4], runs[1])
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -255,7 +255,7 @@ def test_refusals_leave_the_state_alone():
     N = 60
     x = lowrank_data(N, 5)[0]
     kw = dict(capacity=N + 4, tile=16, batch=8)
-    e, twin = T.loaded(N, 5, **kw), T.loaded(N, 5, **kw)
+    e, twin = loaded(N, 5, **kw), loaded(N, 5, **kw)
     history([e, twin], x, (4, 33))
     history([e, twin], x, (9,))                               # pairs pending and a recorded predict behind them
     e.predict(U2); twin.predict(U2)
@@ -306,20 +306,20 @@ def test_refusals_leave_the_state_alone():
         assert q.append_model(A.scan(np.random.default_rng(2), 4)) == N
     assert call(make(1), 1) == L.EKF_ERR_CAPACITY; unchanged_N = e.N
     assert unchanged_N == N + 4 and b"append_model" in e.lib.ekf_last_error(e.h)
-    T.assert_same(e, twin)
+    assert_same(e, twin)
 
 
 def test_a_refusal_reads_the_same_digest_before_and_after():
     from ekf_slam_amd import _lib as L
     N = 60
     x = lowrank_data(N, 5)[0]
-    e = T.loaded(N, 5, capacity=N + 2, tile=16, batch=4)
+    e = loaded(N, 5, capacity=N + 2, tile=16, batch=4)
     history([e], x, (4, 33))
-    before = T.getters(e)
+    before = getters(e)
     arr, _ = e._model_inits(A.scan(np.random.default_rng(2), 3))
     def same_as_before():
         assert e.N == N and b"append_model" in e.lib.ekf_last_error(e.h)
-        for got, ref in zip(T.getters(e), before):            # x, s, P, the diagonal blocks, ekf_P_digest
+        for got, ref in zip(getters(e), before):            # x, s, P, the diagonal blocks, ekf_P_digest
             np.testing.assert_array_equal(got, ref)
 
     assert e.lib.ekf_append_model(e.h, arr, 3, None) == L.EKF_ERR_CAPACITY          # two fit, the third does not
@@ -339,21 +339,21 @@ def test_refused_between_begin_and_finish_of_a_sharded_correction():
     N = 60
     x = lowrank_data(N, 5)[0]
     kw = dict(capacity=N + 4, tile=16)
-    e, twin = T.loaded(N, 5, force_sharded=1, **kw), T.loaded(N, 5, **kw)
+    e, twin = loaded(N, 5, force_sharded=1, **kw), loaded(N, 5, **kw)
     harr = (ctypes.c_void_p * 1)(e.h)
     entries = A.scan(np.random.default_rng(2), 2)
     z = observe(x, 7)
     e.predict(U2); twin.predict(U2)
     e.correct_begin(z, R2, 7)
-    st, msg = T.status_of(lambda: e.append_model(entries))
+    st, msg = status_of(lambda: e.append_model(entries))
     assert st == L.EKF_ERR_STATE and "append_model" in msg and "begin and finish" in msg
     bad = [(M.RANGE, [1.0, 2.0], RPOS, 1.0)]
-    assert T.status_of(lambda: e.append_model(bad))[0] == L.EKF_ERR_INVALID_ARG          # the arguments come first
+    assert status_of(lambda: e.append_model(bad))[0] == L.EKF_ERR_INVALID_ARG          # the arguments come first
     assert e.lib.ekf_exchange_local(harr, 1) == 0
     e.correct_finish()
     twin.correct(z, R2, 7)
     assert e.append_model(entries) == twin.append_model(entries) == N                    # a lone shard with the sharded code path simply works
-    T.assert_same(e, twin)
+    assert_same(e, twin)
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -388,7 +388,7 @@ def test_a_run_with_model_appends_replays_from_its_log(tmp_path):
     log = TrajectoryLog.load(path)
     assert str(np.load(path)["format"]) == FORMAT_APPEND and [(e[0], e[1]) for e in log.edits] == \
         [(8, "append_model"), (13, "append_model"), (13, "observe_model"), (19, "append_model")]
-    fresh = T.engine(**kw)
+    fresh = engine(**kw)
     log.replay(fresh)
     assert fresh.N == 45 and plain.slam._e.N == 40
     np.testing.assert_array_equal(fresh.get_x(), full.slam.x)

@@ -2,46 +2,29 @@
 the host) against the dense restatement of tests/associate_model_cases.py and against the existing small part, and the Python layers --
 Engine.associate_model, the 1-based wrapper, the observe-or-append policy measure_model -- over a stand-in for the library.  No GPU."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import associate_model_cases as A
 import model_obs_cases as M
+from helpers import RPOS, line_program
 from removal_cases import lowrank_data
-from test_model_obs_cpu import _fmt, small_line
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-RPOS = np.array([[0.02, 0.005], [0.005, 0.03]])
 INF = float("inf")
 N0 = 150
-
-
-def _host(tmp_path_factory, name):
-    exe = str(tmp_path_factory.mktemp(name) / name)
-    subprocess.run(["g++", "-O2", "-mfma", "-ffp-contract=off", "-I", os.path.join(ROOT, "ekf_slam_amd", "csrc"),
-                    os.path.join(ROOT, "tests", "support", name + ".cpp"), "-o", exe], check=True)
-
-    def run(lines):
-        out = subprocess.run([exe], input="\n".join(lines) + "\n", check=True, capture_output=True, text=True).stdout
-        rows = [[float(v) for v in ln.split()] for ln in out.strip().split("\n")]
-        assert len(rows) == len(lines)
-        return rows
-    return run
 
 
 @pytest.fixture(scope="module")
 def host(tmp_path_factory):
     """The stand-alone host build of ekfm::assoc_model_d2 / Match2: host(lines) -> one list of floats per line."""
-    return _host(tmp_path_factory, "associate_model_host")
+    return line_program(tmp_path_factory, "associate_model_host")
 
 
 @pytest.fixture(scope="module")
 def small_host(tmp_path_factory):
     """... and the existing one of ekfm::model_eval / model_small (tests/support/model_eval_host.cpp)."""
-    return _host(tmp_path_factory, "model_eval_host")
+    return line_program(tmp_path_factory, "model_eval_host")
 
 
 @pytest.fixture(scope="module")
@@ -71,7 +54,7 @@ def d2_line(ent, x, P, i):
     a = 3 + 2 * i
     strip6 = [P[t, a + r] for t in range(3) for r in range(2)]
     diag3 = [P[a, a], P[a + 1, a], P[a + 1, a + 1]]
-    return "d2 %d %s" % (ent["model"], _fmt(list(z) + list(M.effective_R(o).reshape(-1)) + list(P[:3, :3].reshape(-1)) + strip6 + diag3 + list(x[:3]) + list(x[a:a + 2])))
+    return "d2 %d %s" % (ent["model"], M.fmt(list(z) + list(M.effective_R(o).reshape(-1)) + list(P[:3, :3].reshape(-1)) + strip6 + diag3 + list(x[:3]) + list(x[a:a + 2])))
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -99,7 +82,7 @@ def test_assoc_model_d2_is_model_small_and_constrain_d2_bit_for_bit(host, small_
     for ent in entries:
         for i in range(N0):
             lines_new.append(d2_line(ent, x, P, i))
-            lines_old.append(small_line(M.obs(ent["model"], ent["z"], ent["R"], [i], None, ent["gate"]), x, P))
+            lines_old.append(M.small_line(M.obs(ent["model"], ent["z"], ent["R"], [i], None, ent["gate"]), x, P))
     new, old = host(lines_new), small_host(lines_old)
     np.testing.assert_array_equal([r[1] for r in new], [r[2] for r in old])        # d2, through %.17g: equal numbers are equal bits
     assert [r[0] for r in new] == [r[0] for r in old] == [1.0] * len(new)
@@ -113,7 +96,7 @@ def test_a_target_on_the_robot_a_non_finite_state_and_a_singular_S_have_no_d2(ho
     flat = np.zeros_like(P)
     cases = [(on_robot, P, ent), (lost, P, ent), (x, flat, A.entry(M.RELATIVE_XY, [1.0, 2.0], np.zeros((2, 2))))]
     got = host([d2_line(e, xs, Ps, 0) for xs, Ps, e in cases])
-    old = small_host([small_line(M.obs(e["model"], e["z"], e["R"], [0]), xs, Ps) for xs, Ps, e in cases])
+    old = small_host([M.small_line(M.obs(e["model"], e["z"], e["R"], [0]), xs, Ps) for xs, Ps, e in cases])
     for g, o in zip(got, old):
         assert g[0] == 0.0 and np.isnan(g[1]) and np.isnan(o[2]) and o[1] == M.IRREGULAR
 

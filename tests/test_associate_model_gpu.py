@@ -2,7 +2,7 @@
 observe-or-append policy on top of it (measure_model of ekf_slam_amd/slam.py).
 
 The yardstick is the NumPy restatement of tests/associate_model_cases.py -- d2 of every (observation, landmark) pair, the top two by
-(d2, index) -- applied to THE STATE THE ENGINE REPORTS; stores, tolerances and helpers are those of tests/test_linear_obs_gpu.py.  Where
+(d2, index) -- applied to THE STATE THE ENGINE REPORTS; stores, tolerances and helpers are those of tests/helpers.py.  Where
 the contract is equality -- every d2 against ekf_model_innovation's, a scan against its single calls, the shards against one engine, a
 twin that never associated, a replayed log -- the comparison is assert_array_equal.
 
@@ -18,12 +18,13 @@ import pytest
 
 import append_model_cases as AP
 import associate_model_cases as A
+import helpers
 import model_obs_cases as M
-import test_linear_obs_gpu as T
+from helpers import R2, REL, RPOS, U2, assert_same, check_state, engine, getters, state, status_of
+from linear_obs_cases import STORES
 from removal_cases import lowrank_data, observe
 
 pytestmark = pytest.mark.gpu
-U2, R2, RPOS, REL = T.U2, T.R2, T.RPOS, T.REL
 RRB = np.diag([0.02, 0.5])
 GATE = 9.21
 KEYS = ("best", "second", "d2_best", "d2_second", "within_gate", "irregular")
@@ -55,7 +56,7 @@ def scan_of_eight(x, N, tile):
 
 
 def loaded(N, history=True, **kw):
-    e = T.loaded(N, 5, **kw)
+    e = helpers.loaded(N, 5, **kw)
     if history:
         x = lowrank_data(N, 5)[0]
         for k in (5, edge_landmark(N, kw.get("tile", 16)), N - 3):
@@ -90,10 +91,10 @@ def against_restatement(got, x0, P0, entries, tol, label):
 # 1. against the dense restatement, every store
 # ------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("N", [150, 300])
-@pytest.mark.parametrize("tile,storage", T.STORES)
+@pytest.mark.parametrize("tile,storage", STORES)
 def test_a_scan_against_the_dense_restatement(tile, storage, N):
     e = loaded(N, capacity=N + 8, tile=tile, storage=storage)
-    x0, _, P0 = T.state(e)
+    x0, _, P0 = state(e)
     entries, lms = scan_of_eight(x0, N, tile)
     got = e.associate_model(entries, want_d2=True)
     assert got["d2_all"].shape == (8, N)
@@ -114,7 +115,7 @@ def test_every_d2_is_bit_for_bit_that_of_model_innovation(tile, storage, pending
     N = 150
     x = lowrank_data(N, 5)[0]
     kw = dict(capacity=N + 8, tile=tile, storage=storage, batch=8)
-    e, twin = T.loaded(N, 5, **kw), T.loaded(N, 5, **kw)
+    e, twin = helpers.loaded(N, 5, **kw), helpers.loaded(N, 5, **kw)
     for q in (e, twin):
         for k in (5, edge_landmark(N, tile), N - 3, 11, 40)[:pending]:
             q.predict(U2); q.correct(observe(x, k), R2, k)
@@ -130,7 +131,7 @@ def test_every_d2_is_bit_for_bit_that_of_model_innovation(tile, storage, pending
         want = A.top_two(D[k], GATE)
         assert [got[key][k] for key in KEYS] == [want[key] for key in KEYS]
     assert e.pending() == twin.pending() == pending
-    T.assert_same(e, twin)                                    # x, s, P, the diagonal blocks and the digest of a twin that never asked
+    assert_same(e, twin)                                    # x, s, P, the diagonal blocks and the digest of a twin that never asked
     e.close(); twin.close()
 
 
@@ -167,11 +168,11 @@ def test_a_recorded_predict_is_carried_out_first():
     assert e.pending() == twin.pending() == 3
     z = observe(x, 9)
     e.correct(z, R2, 9); twin.correct(z, R2, 9)               # the twin's correction folds its predict in; e's was carried out by a launch of its own
-    T.assert_same(e, twin)
+    assert_same(e, twin)
     # ... and the association was made at the predicted state: the one a third engine reports after the same predict
     third = loaded(N, **kw)
     third.predict(U2)
-    x0, _, P0 = T.state(third)
+    x0, _, P0 = state(third)
     against_restatement(got, x0, P0, entries, REL, "behind a recorded predict")
     assert_equal_results(got, third.associate_model(entries, want_d2=True), "after the state was read")
     for q in (e, twin, third):
@@ -189,7 +190,7 @@ def _set_x(e, x):
 
 def test_an_empty_map_and_a_map_of_one():
     from ekf_slam_amd import _lib as L
-    e = T.engine(capacity=8, tile=16)
+    e = engine(capacity=8, tile=16)
     e.timing_enable(L.EKF_KERNEL_ASSOCIATE)
     entries = [A.entry(M.RANGE_BEARING, [5.0, 30.0], RRB, GATE), A.entry(M.BEARING, [12.0], 0.5)]
     got = e.associate_model(entries, want_d2=True)
@@ -214,7 +215,7 @@ def test_a_landmark_on_the_robot_is_irregular_and_never_the_best():
     x = e.get_x()
     x[3 + 2 * 13:5 + 2 * 13] = x[:2]
     _set_x(e, x)
-    x0, _, P0 = T.state(e)
+    x0, _, P0 = state(e)
     entries = [aimed(x0, m, k) for m, k in zip(MODELS, (12, 14, 0, N - 1))] + [A.entry(M.RELATIVE_XY, [0.0, 0.0], RPOS, GATE)]
     got = e.associate_model(entries, want_d2=True)
     assert got["irregular"].tolist() == [1] * 5 and np.all(np.isnan(got["d2_all"][:, 13]))
@@ -229,7 +230,7 @@ def test_a_landmark_on_the_robot_is_irregular_and_never_the_best():
 def test_two_identical_landmarks_tie_and_the_lower_index_is_the_best():
     N = 40
     e = loaded(N, history=False, capacity=N + 8, tile=16)
-    x, s, P = T.state(e)
+    x, s, P = state(e)
     i, j = 9, 31
     a, b = 3 + 2 * i, 3 + 2 * j
     x[b:b + 2] = x[a:a + 2]
@@ -256,7 +257,7 @@ def test_between_two_batches_of_an_asynchronous_pass(tile, storage):
     N = 150
     x = lowrank_data(N, 5)[0]
     kw = dict(capacity=N + 8, tile=tile, storage=storage, batch=4)
-    e, twin = T.loaded(N, 5, async_flush=True, **kw), T.loaded(N, 5, **kw)
+    e, twin = helpers.loaded(N, 5, async_flush=True, **kw), helpers.loaded(N, 5, **kw)
     steps = (5, edge_landmark(N, tile), N - 3, 11, 40, 77, 2, 120)
     for q in (e, twin):
         for k in steps[:4]:                                   # the batch completes: its pass starts (asynchronous: on the pass stream)
@@ -272,7 +273,7 @@ def test_between_two_batches_of_an_asynchronous_pass(tile, storage):
     for q in (e, twin):
         for k in steps[6:]:
             q.predict(U2); q.correct(observe(x, k), R2, k)
-    T.assert_same(e, twin)
+    assert_same(e, twin)
     e.close(); twin.close()
 
 
@@ -323,10 +324,10 @@ def test_refusals_leave_the_state_alone():
     from ekf_slam_amd import _lib as L
     N = 60
     x = lowrank_data(N, 5)[0]
-    e = T.loaded(N, 5, capacity=N + 4, tile=16, batch=4)
+    e = helpers.loaded(N, 5, capacity=N + 4, tile=16, batch=4)
     for k in (4, 33):
         e.predict(U2); e.correct(observe(x, k), R2, k)
-    before = T.getters(e)
+    before = getters(e)
     xe = e.get_x()
     good = [aimed(xe, m, k) for m, k in zip(MODELS, (1, 20, 41, 59))]
     out = (L.EkfModelMatch * 33)()
@@ -339,7 +340,7 @@ def test_refusals_leave_the_state_alone():
         if handle_text:
             assert b"associate_model" in e.lib.ekf_last_error(e.h), name
         assert e.N == N and all(out[k].best == -7 for k in range(33)), name
-        for got, ref in zip(T.getters(e), before):            # x, s, P, the diagonal blocks, ekf_P_digest
+        for got, ref in zip(getters(e), before):            # x, s, P, the diagonal blocks, ekf_P_digest
             np.testing.assert_array_equal(got, ref, err_msg=name)
 
     call = lambda arr, m, o=out, d=None: e.lib.ekf_associate_model(e.h, arr, m, o, d)
@@ -366,7 +367,7 @@ def test_refusals_leave_the_state_alone():
     arr = _raw(e, good)
     arr[0].anchor[0], arr[1].anchor[1], arr[2].gate = nan, inf, inf
     assert call(arr, 4) == 0 and out[2].within_gate == N and out[0].best == 1 and out[4].best == -7
-    for got, ref in zip(T.getters(e), before):
+    for got, ref in zip(getters(e), before):
         np.testing.assert_array_equal(got, ref)
     e.close()
 
@@ -376,21 +377,21 @@ def test_refused_between_begin_and_finish_of_a_sharded_correction():
     N = 60
     x = lowrank_data(N, 5)[0]
     kw = dict(capacity=N + 4, tile=16)
-    e, twin = T.loaded(N, 5, force_sharded=1, **kw), T.loaded(N, 5, **kw)
+    e, twin = helpers.loaded(N, 5, force_sharded=1, **kw), helpers.loaded(N, 5, **kw)
     harr = (ctypes.c_void_p * 1)(e.h)
     entries = [aimed(x, m, k) for m, k in zip(MODELS, (1, 20, 41, 59))]
     z = observe(x, 7)
     e.predict(U2); twin.predict(U2)
     e.correct_begin(z, R2, 7)
-    st, msg = T.status_of(lambda: e.associate_model(entries))
+    st, msg = status_of(lambda: e.associate_model(entries))
     assert st == L.EKF_ERR_STATE and "associate_model" in msg and "begin and finish" in msg
     bad = [dict(entries[0], model=M.LANDMARK_RANGE)]
-    assert T.status_of(lambda: e.associate_model(bad))[0] == L.EKF_ERR_INVALID_ARG            # the arguments come first
+    assert status_of(lambda: e.associate_model(bad))[0] == L.EKF_ERR_INVALID_ARG            # the arguments come first
     assert e.lib.ekf_exchange_local(harr, 1) == 0
     e.correct_finish()
     twin.correct(z, R2, 7)
     assert_equal_results(e.associate_model(entries, want_d2=True), twin.associate_model(entries, want_d2=True), "a lone shard")
-    T.assert_same(e, twin)
+    assert_same(e, twin)
     e.close(); twin.close()
 
 
@@ -415,7 +416,7 @@ def test_measure_model_end_to_end_and_its_replay(tmp_path):
     f.log = TrajectoryLog()
     f.predict(U2)
     f.log.record(U2, None, [], [])                            # (what measure() records of a step without sightings)
-    x0, s0, P0 = T.state(f._e)
+    x0, s0, P0 = state(f._e)
     # chosen by the restatement among sightings of the first 40 landmarks: three with exactly one landmark inside the gate, one with several
     cand = [aimed(x0, M.RANGE_BEARING if k % 2 == 0 else M.RELATIVE_XY, k) for k in range(40)]
     res, _ = A.match(x0, P0, cand)
@@ -439,15 +440,15 @@ def test_measure_model_end_to_end_and_its_replay(tmp_path):
         ex, eP, r = M.observe_model_dense(ex, eP, o)
         assert r["outcome"] == M.APPLIED
     ex, es, eP = AP.append_model_dense(ex, es, eP, [AP.entry(picks[q]["model"], picks[q]["z"], picks[q]["R"], N + 1 + b) for b, q in enumerate((1, 4))])
-    T.check_state(f._e, ex, eP, "f64", "measure_model")
+    check_state(f._e, ex, eP, "f64", "measure_model")
     np.testing.assert_array_equal(f.s, es)
     # a replay of the saved log leaves the same bits
     path = tmp_path / "measured.npz"
     f.log.save(path)
     log = TrajectoryLog.load(path)
     assert [e[1] for e in log.edits] == ["observe_model"] * 3 + ["append_model"]
-    fresh = T.engine(**kw)
+    fresh = engine(**kw)
     start(fresh)
     log.replay(fresh)
-    T.assert_same(fresh, f._e)
+    assert_same(fresh, f._e)
     fresh.close()

@@ -14,6 +14,8 @@ largest entry)."""
 import numpy as np
 import pytest
 
+from helpers import rel_err
+
 pytestmark = pytest.mark.gpu
 
 SEED = 20260101 + 5
@@ -127,11 +129,6 @@ def engine_rows(eng, lms, n):
         else:
             out.append(eng.get_P_block(3 + 2 * L, 0, 2, n))
     return np.stack(out)
-
-
-def rel_err(a, b):
-    a, b = np.asarray(a), np.asarray(b)
-    return float(np.abs(a - b).max() / max(np.abs(b).max(), 1e-300))
 
 
 @pytest.mark.parametrize("leg", list(LEGS))

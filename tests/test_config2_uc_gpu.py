@@ -10,14 +10,10 @@ to 1e-6."""
 import numpy as np
 import pytest
 
+from helpers import REL, rel_err
+
 pytestmark = pytest.mark.gpu
-REL = 1e-6
 N, M, ITERS = 1000, 8, 200
-
-
-def rel_err(a, b):
-    a, b = np.asarray(a), np.asarray(b)
-    return float(np.abs(a - b).max() / max(np.abs(b).max(), 1e-300))
 
 
 def test_one_thousand_landmarks_unknown_correspondence(oracle_lib):

@@ -9,9 +9,7 @@ import subprocess
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-MOCK = os.path.join(ROOT, "tests", "support", "mex_mock")
-INCLUDES = ["-I", os.path.join(ROOT, "include"), "-I", os.path.join(ROOT, "tests", "support", "mex_api_subset"), "-I", MOCK]
+from mex_harness import INCLUDES, MOCK, ROOT
 
 _WRAP = r'''
 #include <stdio.h>

@@ -8,16 +8,10 @@ import time
 import numpy as np
 import pytest
 
-from decided_plans import make_plan, oracle_run
+from decided_plans import PARAMS, make_plan, oracle_run
+from helpers import REL, rel_err
 
 pytestmark = pytest.mark.gpu
-REL = 1e-6
-PARAMS = dict(w_pos=1.0, Rc=(0.01, 0.01), s_thresh=0.5)     # the position cost rejects some signature matches (decided_plans)
-
-
-def rel_err(a, b):
-    a, b = np.asarray(a), np.asarray(b)
-    return float(np.abs(a - b).max() / max(np.abs(b).max(), 1e-300))
 
 
 def engine(device_assoc, capacity, **kw):

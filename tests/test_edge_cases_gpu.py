@@ -6,13 +6,9 @@ heading wrapped at exactly 360 (wrapTo360(360) = 360), capacity reached exactly.
 import numpy as np
 import pytest
 
+from helpers import REL, rel_err
+
 pytestmark = pytest.mark.gpu
-REL = 1e-6
-
-
-def rel_err(a, b):
-    a, b = np.asarray(a), np.asarray(b)
-    return float(np.abs(a - b).max() / max(np.abs(b).max(), 1e-300))
 
 
 def _pair(N, seed, tile=16, batch=1, mode="known"):

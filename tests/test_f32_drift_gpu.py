@@ -22,14 +22,11 @@ import os
 import numpy as np
 import pytest
 
+from helpers import rel_err
+
 pytestmark = pytest.mark.gpu
 EPS32 = 6e-8
 STEPS, EVERY, N0 = 2000, 250, 2000
-
-
-def rel_err(a, b):
-    a, b = np.asarray(a), np.asarray(b)
-    return float(np.abs(a - b).max() / max(np.abs(b).max(), 1e-300))
 
 
 def bound_P(k, storage="f32"):

@@ -14,13 +14,10 @@ schedules agree bit for bit, tests/test_deferred_gpu.py.)"""
 import numpy as np
 import pytest
 
+from helpers import rel_err
+
 pytestmark = pytest.mark.gpu
 TOL_X, TOL_P = 1e-6, 1e-6
-
-
-def rel_err(a, b):
-    a, b = np.asarray(a), np.asarray(b)
-    return float(np.abs(a - b).max() / max(np.abs(b).max(), 1e-300))
 
 
 def _state(N, seed):

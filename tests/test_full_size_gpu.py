@@ -7,14 +7,10 @@ deferred engine (batch 4, asynchronous flush) equal to the immediate one bit for
 import numpy as np
 import pytest
 
+from helpers import REL, rel_err
+
 pytestmark = pytest.mark.gpu
-REL = 1e-6
 N = 10000
-
-
-def rel_err(a, b):
-    a, b = np.asarray(a), np.asarray(b)
-    return float(np.abs(a - b).max() / max(np.abs(b).max(), 1e-300))
 
 
 def test_ten_thousand_landmarks_against_oracle(oracle_lib):

@@ -4,9 +4,9 @@ import numpy as np
 import pytest
 
 from golden_util import load, rel_err, replay_append3, replay_slam
+from helpers import REL
 
 pytestmark = pytest.mark.gpu
-REL = 1e-6
 
 
 @pytest.mark.parametrize("name,mode,tile", [("slam20_known.npz", "known", 16), ("slam20_uc.npz", "uc", 16),

@@ -6,14 +6,9 @@ that tolerance, and the tests additionally report the (much smaller) error actua
 import numpy as np
 import pytest
 
+from helpers import REL, rel_err
+
 pytestmark = pytest.mark.gpu
-
-REL = 1e-6
-
-
-def rel_err(a, b):
-    a, b = np.asarray(a), np.asarray(b)
-    return float(np.abs(a - b).max() / max(np.abs(b).max(), 1e-300))
 
 
 def _random_spd_state(N, seed):

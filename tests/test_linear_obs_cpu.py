@@ -1,15 +1,13 @@
 """CPU: the arithmetic of a linear observation (tests/linear_obs_cases.py: hand-derived answers, dense against information form, dense
 against merge_cases for H = (+I, -I)), the fifth kind of the trajectory log, and the argument handling of the Python layers over a
 stand-in for the library.  No GPU."""
-import ctypes
 
 import numpy as np
 import pytest
 
 import linear_obs_cases as C
+from helpers import RPOS, RecorderBase
 from merge_cases import constrain_dense
-
-RPOS = np.array([[0.02, 0.005], [0.005, 0.03]])
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -218,22 +216,11 @@ def test_trajectory_format_four_round_trip_and_the_older_formats(tmp_path):
 # ------------------------------------------------------------------------------------------------------------------
 # the Python layers over a stand-in for the library
 # ------------------------------------------------------------------------------------------------------------------
-class _Recorder:
+class _Recorder(RecorderBase):
+    last_error = b"observe_linear: injected"
+
     def __init__(self):
         self.calls, self.fail = [], 0
-
-    def ekf_config_default(self, pcfg, mode):
-        from ekf_slam_amd import _lib as L
-        cfg = ctypes.cast(pcfg, ctypes.POINTER(L.EkfConfig)).contents
-        cfg.mode, cfg.batch = mode, 1
-        return 0
-
-    def ekf_create(self, pcfg, ph):
-        ctypes.cast(ph, ctypes.POINTER(ctypes.c_void_p)).contents.value = 0x1000
-        return 0
-
-    def ekf_destroy(self, h):
-        return 0
 
     def _note(self, name, pobs, pres):
         o = pobs._obj
@@ -257,12 +244,6 @@ class _Recorder:
     def ekf_linear_rejections(self, h, pa, pb):
         pa._obj.value, pb._obj.value = 3, 4
         return 0
-
-    def ekf_status_string(self, rc):
-        return b"call not valid in the current state"
-
-    def ekf_last_error(self, h):
-        return b"observe_linear: injected"
 
 
 def test_engine_and_slam_layers_marshal_an_observation_once(monkeypatch):

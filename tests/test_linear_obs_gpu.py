@@ -2,7 +2,7 @@
 DESIGN.md section 3i).
 
 The yardstick is the NumPy restatement of tests/linear_obs_cases.py applied to THE STATE THE ENGINE REPORTED BEFORE THE CALL (so float
-tiles start from the same rounded inputs).  Tolerances as tests/test_merge_landmarks_gpu.py states them: F64 tiles REL = 1e-6
+tiles start from the same rounded inputs).  Tolerances as tests/helpers.py states them: F64 tiles REL = 1e-6
 (BASELINE.json's bar; the measured values are printed), float tiles DESIGN.md section 5's bounds for one step -- x 1e-9, the entries
 of P kept in F64 (robot rows, the landmarks' own 2 x 2 blocks) 2e-9, float-stored entries 2e-7 of the row's largest.  Where two
 engines must agree because they ran the same kernels on the same inputs, the comparison is assert_array_equal.
@@ -14,53 +14,12 @@ import numpy as np
 import pytest
 
 import linear_obs_cases as C
+from decided_plans import PARAMS
+from helpers import R2, REL, RPOS, U2, assert_same, check_state, engine, getters, loaded, rel_err, state, status_of
+from linear_obs_cases import N0, STORES, edge_landmark
 from removal_cases import lowrank_data, observe
 
 pytestmark = pytest.mark.gpu
-REL = 1e-6
-TOL_X32, TOL_KEPT32, TOL_ROW32 = 1e-9, 2e-9, 2e-7
-N0 = 150
-U2 = np.array([0.1, 1.0])
-R2 = np.diag([0.1, 0.2])
-RPOS = np.array([[0.02, 0.005], [0.005, 0.03]])
-STORES = [(16, "f64"), (64, "f64"), (256, "f32"), (256, "f32_mixed"), (256, "f32_split")]
-
-
-def rel_err(a, b):
-    a, b = np.asarray(a), np.asarray(b)
-    return float(np.abs(a - b).max() / max(np.abs(b).max(), 1e-300))
-
-
-def engine(mode="known", **kw):
-    from ekf_slam_amd.engine import Engine
-    return Engine(mode=mode, **kw)
-
-
-def loaded(N, seed, mode="known", **kw):
-    x0, s, d, U = lowrank_data(N, seed)
-    e = engine(mode, **kw)
-    e.load_lowrank_state(x0, s, d, U)
-    return e
-
-
-def state(e):
-    return e.get_x(), e.get_s(), e.get_P()
-
-
-def blocks_of(P):
-    n = P.shape[0]
-    starts = np.concatenate([[0], np.arange(3, n, 2)])
-    return np.array([P[a:a + 2, a:a + 2] for a in starts])
-
-
-def getters(e):
-    return [e.get_x(), e.get_s(), e.get_P(), e.get_P_diag_blocks(), e.digest()]
-
-
-def assert_same(a, b):
-    assert a.N == b.N
-    for u, v in zip(getters(a), getters(b)):
-        np.testing.assert_array_equal(u, v)
 
 
 def send(e, o, wait=False):
@@ -69,39 +28,6 @@ def send(e, o, wait=False):
 
 def ask(e, o):
     return e.linear_innovation(o["z"][:o["rows"]], o["R"], o["Hr"], o["landmarks"], o["Hl"], gate=o["gate"], wrap=o["wrap"], rows=o["rows"])
-
-
-def check_state(e, ex, eP, storage, label):
-    x, P, blocks = e.get_x(), e.get_P(), e.get_P_diag_blocks()
-    np.testing.assert_array_equal(P, P.T)
-    n = ex.size
-    kept = np.zeros((n, n), dtype=bool)
-    kept[:3, :] = kept[:, :3] = True
-    for a in range(3, n, 2):
-        kept[a:a + 2, a:a + 2] = True
-    scale = np.abs(eP).max()
-    err_x, err_P, err_b = rel_err(x, ex), rel_err(P, eP), rel_err(blocks, blocks_of(eP))
-    err_kept = float(np.abs(P - eP)[kept].max() / scale)
-    err_row = float((np.abs(P - eP).max(axis=1) / np.abs(eP).max(axis=1)).max())
-    print("%s [%s]: rel err x %.2e P %.2e blocks %.2e F64-kept %.2e worst row %.2e" % (label, storage, err_x, err_P, err_b, err_kept, err_row))
-    if storage == "f64":
-        assert err_x < REL and err_P < REL and err_b < REL
-    else:
-        assert err_x < TOL_X32 and err_kept < TOL_KEPT32 and err_b < TOL_KEPT32 and err_row <= TOL_ROW32
-
-
-def status_of(fn):
-    from ekf_slam_amd._lib import EkfError
-    try:
-        fn()
-    except EkfError as ex:
-        return ex.status, str(ex)
-    return 0, ""
-
-
-def edge_landmark(T):
-    per_row = T // 2
-    return per_row * max(1, (N0 // 2) // per_row) if per_row < N0 else N0 // 2
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -441,7 +367,6 @@ def test_a_lone_shard_with_the_sharded_code_path_simply_works(batch):
 # ------------------------------------------------------------------------------------------------------------------
 # 8. unknown correspondence: observations between the scans of the device-resident loops
 # ------------------------------------------------------------------------------------------------------------------
-POS = dict(w_pos=1.0, Rc=(0.01, 0.01), s_thresh=0.5)         # the position-weighted likelihood of tests/test_decided_assoc_gpu.py
 
 
 def _uc_run(device_assoc, params):
@@ -471,7 +396,7 @@ def test_observations_between_scans_signature_only():
 
 
 def test_observations_between_scans_position_weighted():
-    runs = {m: _uc_run(m, POS) for m in (1, 4)}
+    runs = {m: _uc_run(m, PARAMS) for m in (1, 4)}
     assert_same(runs[4], runs[1])
 
 

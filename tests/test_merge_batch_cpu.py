@@ -11,14 +11,10 @@ import subprocess
 import numpy as np
 import pytest
 
+from helpers import RPOS, RecorderBase
 from merge_batch_cases import INDEX, INVALID_ARG, MERGE_BATCH_MAX, chain_regularity, dense_of, merge_batch_dense, planted, refusal, survivor_index
 from merge_cases import merge_dense
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-MOCK = os.path.join(ROOT, "tests", "support", "mex_mock")
-INCLUDES = ["-I", os.path.join(ROOT, "include"), "-I", os.path.join(ROOT, "tests", "support", "mex_api_subset"), "-I", MOCK]
-GCC = ["gcc", "-std=c99", "-Wall", "-Wextra", "-Werror", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"]
-RPOS = np.array([[0.02, 0.005], [0.005, 0.03]])
+from mex_harness import PRELUDE_SHOWN, ROOT, driver, driver_without, transcript_of
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -119,24 +115,13 @@ def test_the_kernel_sources_emulated_on_the_host_give_the_sequence_bit_for_bit(t
 # ------------------------------------------------------------------------------------------------------------------
 # the Python layers
 # ------------------------------------------------------------------------------------------------------------------
-class _Recorder:
+class _Recorder(RecorderBase):
     """Stand-in for the loaded library (no GPU here)."""
+
+    last_error = b"merge_landmarks_batch: pair 1: injected"
 
     def __init__(self, N=9):
         self.calls, self.N, self.fail = [], N, 0
-
-    def ekf_config_default(self, pcfg, mode):
-        from ekf_slam_amd import _lib as L
-        cfg = ctypes.cast(pcfg, ctypes.POINTER(L.EkfConfig)).contents
-        cfg.mode, cfg.batch = mode, 1
-        return 0
-
-    def ekf_create(self, pcfg, ph):
-        ctypes.cast(ph, ctypes.POINTER(ctypes.c_void_p)).contents.value = 0x1000
-        return 0
-
-    def ekf_destroy(self, h):
-        return 0
 
     def ekf_num_landmarks(self, h, pn):
         pn._obj.value = self.N
@@ -159,12 +144,6 @@ class _Recorder:
     def ekf_remove_landmarks(self, h, idx, m):
         self.calls.append(("remove", [int(idx[k]) for k in range(m)]))
         return 0
-
-    def ekf_status_string(self, rc):
-        return b"call not valid in the current state"
-
-    def ekf_last_error(self, h):
-        return b"merge_landmarks_batch: pair 1: injected"
 
 
 def test_engine_and_slam_layers_convert_indices_once_and_log_one_edit(monkeypatch):
@@ -350,30 +329,7 @@ int32_t ekf_merge_landmarks_batch(ekf_handle *h, const int64_t *keep, const int6
 }
 '''
 
-_DRIVER = r'''
-#include <setjmp.h>
-#include <stdio.h>
-#include "ekfslam.h"
-#include "mex_mock.h"
-void arm_failure(void);
-static mxArray *out[4];
-static int call(const char *what, int nlhs, int nrhs, const mxArray **prhs) {
-    out[0] = 0;
-    if (setjmp(mock_err_jmp)) { printf("MEX %s nrhs=%d -> ERROR %s | %s\n", what, nrhs, mock_err_id, mock_err_msg); return 1; }
-    mexFunction(nlhs, out, nrhs, prhs);
-    printf("MEX %s nrhs=%d -> ok", what, nrhs);
-    if (out[0] && mxGetClassID(out[0]) != mxUINT64_CLASS) {
-        printf(" out0=%zux%zu[", mxGetM(out[0]), mxGetN(out[0]));
-        for (size_t i = 0; i < mxGetM(out[0]) * mxGetN(out[0]); ++i) printf(i ? ",%g" : "%g", mxGetPr(out[0])[i]);
-        printf("]");
-    }
-    printf("\n");
-    return 0;
-}
-int main(void) {
-    const mxArray *cr[3] = { mock_string("create"), mock_double(1, 1, (const double[]){ 1 }), mock_double(1, 1, (const double[]){ 64 }) };
-    if (call("create", 1, 3, cr)) return 1;
-    const mxArray *h = out[0];
+_DRIVER = driver(r'''
     const mxArray *R = mock_double(2, 2, (const double[]){ 4, 1, 1, 9 });
     /* pairs = [3 5; 1 2; 3 8], column-major: the keeps, then the drops */
     const mxArray *pairs = mock_double(3, 2, (const double[]){ 3, 1, 3, 5, 2, 8 });
@@ -394,56 +350,16 @@ int main(void) {
         return 1;
     arm_failure();
     if (!call("merge_landmarks_batch", 1, 4, mb)) return 1;
-    const mxArray *de[2] = { mock_string("destroy"), h };
-    if (call("destroy", 0, 2, de)) return 1;
-    printf("LOCKS %d\nMISUSE %d\n", mock_lock_count, mock_misuse);
-    return 0;
-}
-'''
+''', PRELUDE_SHOWN)
 
-_DRIVER_WITHOUT = r'''
-#include <setjmp.h>
-#include <stdio.h>
-#include "ekfslam.h"
-#include "mex_mock.h"
-static mxArray *out[4];
-static int call(const char *what, int nrhs, const mxArray **prhs) {
-    out[0] = 0;
-    if (setjmp(mock_err_jmp)) { printf("MEX %s nrhs=%d -> ERROR %s | %s\n", what, nrhs, mock_err_id, mock_err_msg); return 1; }
-    mexFunction(1, out, nrhs, prhs);
-    printf("MEX %s nrhs=%d -> ok\n", what, nrhs);
-    return 0;
-}
-int main(void) {
-    const mxArray *cr[3] = { mock_string("create"), mock_double(1, 1, (const double[]){ 1 }), mock_double(1, 1, (const double[]){ 64 }) };
-    if (call("create", 3, cr)) return 1;
-    const mxArray *h = out[0];
+_DRIVER_WITHOUT = driver_without(r'''
     const mxArray *mb[4] = { mock_string("merge_landmarks_batch"), h, mock_double(1, 2, (const double[]){ 1, 2 }), mock_double(2, 2, (const double[]){ 0, 0, 0, 0 }) };
-    if (!call("merge_landmarks_batch", 4, mb)) return 1;
-    const mxArray *pr[3] = { mock_string("predict"), h, mock_double(2, 1, (const double[]){ 0.1, 3 }) };
-    if (call("predict", 3, pr)) return 1;
-    const mxArray *de[2] = { mock_string("destroy"), h };
-    if (call("destroy", 2, de)) return 1;
-    printf("LOCKS %d\nMISUSE %d\n", mock_lock_count, mock_misuse);
-    return 0;
-}
-'''
-
-
-def _build_and_run(files, exe):
-    r = subprocess.run(GCC + INCLUDES + [os.path.join(ROOT, "matlab", "ekfslam_mex.c"), os.path.join(MOCK, "mex_mock.c"),
-                                         os.path.join(MOCK, "abi_stub.c")] + files + ["-o", exe, "-lm"], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-4000:]
-    r = subprocess.run([exe], capture_output=True, text=True, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=0"))
-    assert r.returncode == 0, "the gateway misbehaved under the mock:\n" + r.stdout[-2000:] + r.stderr[-4000:]
-    return r.stdout.splitlines()
+    if (!call("merge_landmarks_batch", 1, 4, mb)) return 1;
+''')
 
 
 def test_mex_gateway_converts_the_pairs_once(tmp_path):
-    stub, drv = tmp_path / "batch_stub.c", tmp_path / "batch_drv.c"
-    stub.write_text(_STUB)
-    drv.write_text(_DRIVER)
-    t = _build_and_run([str(stub), str(drv)], str(tmp_path / "drv"))
+    t = transcript_of(tmp_path, _STUB, _DRIVER)
     # MATLAB's [3 5; 1 2; 3 8] arrives as 0-based (2<-4)(0<-1)(2<-7), R column-major as MATLAB holds it
     i = t.index("ABI ekf_merge_landmarks_batch m=3 R=4,1,1,9 pairs=(2<-4)(0<-1)(2<-7)")
     assert t[i + 1] == "MEX merge_landmarks_batch nrhs=4 -> ok out0=3x1[0.5,1,1.5]"
@@ -461,9 +377,7 @@ def test_mex_gateway_converts_the_pairs_once(tmp_path):
 
 
 def test_the_gateway_still_links_against_a_library_without_the_symbol(tmp_path):
-    drv = tmp_path / "without_drv.c"
-    drv.write_text(_DRIVER_WITHOUT)
-    t = _build_and_run([str(drv)], str(tmp_path / "drv"))
+    t = transcript_of(tmp_path, _DRIVER_WITHOUT)
     assert any(ln.startswith("MEX merge_landmarks_batch ") and "ERROR ekfslam:usage" in ln and "this libekfslam has no ekf_merge_landmarks_batch" in ln
                for ln in t)
     assert "MEX predict nrhs=3 -> ok" in t and t[-2:] == ["LOCKS 0", "MISUSE 0"]

@@ -3,7 +3,7 @@
 The definition is the yardstick: the call leaves what ekf_constrain_landmarks pair by pair in list order, then ONE
 ekf_remove_landmarks of all drops would leave.  With F64 tiles that is checked with assert_array_equal against a twin that makes
 exactly those public calls; in every storage kind against tests/merge_batch_cases.merge_batch_dense applied to the state the engine
-reported before the call, by the ONE-step tolerances of tests/test_merge_landmarks_gpu.py (the batch rounds a float entry once).
+reported before the call, by the ONE-step tolerances of tests/helpers.py (the batch rounds a float entry once).
 
 Float contingency (the bounds are not loosened): where a float bound does not hold on these inputs the bar is
 max(bound, 2 x the error the sequential route measures on the same inputs); both routes' errors are printed."""
@@ -12,13 +12,13 @@ import ctypes
 import numpy as np
 import pytest
 
+from helpers import R2, REL, RPOS, STORES_ALL, TOL_KEPT32, TOL_ROW32, TOL_X32, U2, assert_same, blocks_of, engine, loaded, rel_err, run_ops, state, status_of
 from merge_batch_cases import MERGE_BATCH_MAX, chain_regularity, dense_of, merge_batch_dense, nearest_dense, planted, survivor_index
-from merge_cases import Factored
+from merge_cases import Factored, continuation, tile_edge_landmark
 from removal_cases import lowrank_data, observe
-from test_merge_landmarks_gpu import (N0, R2, REL, RPOS, STORES, TOL_KEPT32, TOL_ROW32, TOL_X32, U2, _continuation, _run, assert_same,
-                                      blocks_of, engine, loaded, rel_err, state, status_of, tile_edge_landmark)
 
 pytestmark = pytest.mark.gpu
+N0 = 300
 SEED = 7
 FUSED = "k_merge_pass"
 
@@ -56,7 +56,7 @@ def regular_on_the_numpy_side(e, pairs, R, floor=1e-3):
 # 1. F64: the same bits as the sequence of public calls
 # ------------------------------------------------------------------------------------------------------------------
 def _bit_cases(T):
-    edge = tile_edge_landmark(T)
+    edge = tile_edge_landmark(T, N0)
     pl = planted(N0, SEED)[4]
     used = {v for p in pl for v in p}
     extra_keeps = [k for k in range(0, N0 // 2) if k not in used][:16]
@@ -138,7 +138,7 @@ def _errors(e, ex, es, eP):
             "row": float((np.abs(P - eP).max(axis=1) / np.abs(eP).max(axis=1)).max())}
 
 
-@pytest.mark.parametrize("tile,storage", STORES)
+@pytest.mark.parametrize("tile,storage", STORES_ALL)
 @pytest.mark.parametrize("rname", ["R0", "Rpos"])
 def test_every_store_against_the_dense_restatement(tile, storage, rname):
     R = None if rname == "R0" else RPOS
@@ -230,9 +230,9 @@ def test_the_engine_goes_on_like_a_twin_given_the_expected_state(tile, storage, 
     ex, es, eP = state(e)
     twin = engine("uc", **kw)
     twin.set_state(ex, eP, es)
-    ops = _continuation(ex, es, tile, batch, cap, survivor_index(pairs, pairs[3][1]))      # appends over a tile-row edge, UC scans, corrections
-    _run(e, ops)
-    _run(twin, ops)
+    ops = continuation(ex, es, tile, batch, cap, survivor_index(pairs, pairs[3][1]))      # appends over a tile-row edge, UC scans, corrections
+    run_ops(e, ops)
+    run_ops(twin, ops)
     assert e.N == twin.N and e.N > es.size + 3
     if storage == "f64":
         assert_same(e, twin)
@@ -389,9 +389,9 @@ def test_checkpoint_after_a_batch(tile, storage, tmp_path):
     fresh = engine("uc", **kw)
     fresh.checkpoint_load(path)
     np.testing.assert_array_equal(fresh.get_P(), eP)
-    ops = _continuation(ex, es, tile, 8, cap, 100)
-    _run(e, ops)
-    _run(fresh, ops)
+    ops = continuation(ex, es, tile, 8, cap, 100)
+    run_ops(e, ops)
+    run_ops(fresh, ops)
     assert_same(e, fresh)
 
 

@@ -7,18 +7,14 @@ numbers once, and still links against a stand-in that lacks the new symbols."""
 import ctypes
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
+from helpers import RecorderBase
 from merge_cases import Factored, constrain_dense, constrain_information, merge_dense
+from mex_harness import ROOT, driver, driver_without, prelude, transcript_of
 from removal_cases import expected_after, lowrank_data
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-MOCK = os.path.join(ROOT, "tests", "support", "mex_mock")
-INCLUDES = ["-I", os.path.join(ROOT, "include"), "-I", os.path.join(ROOT, "tests", "support", "mex_api_subset"), "-I", MOCK]
-GCC = ["gcc", "-std=c99", "-Wall", "-Wextra", "-Werror", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"]
 
 
 def test_library_exports_and_binds_the_entry_points():
@@ -105,24 +101,14 @@ def test_kalman_form_against_information_form(i, j):
     assert mx.size == ex2.size and ms.size == 299 and mP.shape == eP2.shape
 
 
-class _Recorder:
+class _Recorder(RecorderBase):
     """Stand-in for the loaded library: records the calls of the three entry points and of ekf_remove_landmarks (no GPU here)."""
+
+    status_string = b"landmark index out of range"
+    last_error = b"merge_landmarks: landmark index outside the state"
 
     def __init__(self, status=0):
         self.calls, self.status = [], status
-
-    def ekf_config_default(self, pcfg, mode):
-        from ekf_slam_amd import _lib as L
-        cfg = ctypes.cast(pcfg, ctypes.POINTER(L.EkfConfig)).contents
-        cfg.mode, cfg.batch = mode, 1
-        return 0
-
-    def ekf_create(self, pcfg, ph):
-        ctypes.cast(ph, ctypes.POINTER(ctypes.c_void_p)).contents.value = 0x1000
-        return 0
-
-    def ekf_destroy(self, h):
-        return 0
 
     @staticmethod
     def _v(p, n):
@@ -146,12 +132,6 @@ class _Recorder:
     def ekf_remove_landmarks(self, h, arr, m):
         self.calls.append(("remove", [int(arr[k]) for k in range(m)]))
         return self.status
-
-    def ekf_status_string(self, rc):
-        return b"landmark index out of range"
-
-    def ekf_last_error(self, h):
-        return b"merge_landmarks: landmark index outside the state"
 
 
 def test_engine_and_slam_layers_reach_the_library_with_the_right_indices(monkeypatch):
@@ -224,27 +204,11 @@ int32_t ekf_landmark_distance(ekf_handle *h, int64_t i, int64_t j, const double 
 }
 '''
 
-_DRIVER = r'''
-#include <setjmp.h>
-#include <stdio.h>
-#include "ekfslam.h"
-#include "mex_mock.h"
-void arm_failure(void);
-static mxArray *out[4];
-static int call(const char *what, int nlhs, int nrhs, const mxArray **prhs) {
-    out[0] = 0; out[1] = 0;
-    if (setjmp(mock_err_jmp)) { printf("MEX %s nrhs=%d -> ERROR %s | %s\n", what, nrhs, mock_err_id, mock_err_msg); return 1; }
-    mexFunction(nlhs, out, nrhs, prhs);
-    printf("MEX %s nrhs=%d -> ok", what, nrhs);
-    if (out[0]) printf(" d2=%g", mxGetScalar(out[0]));
+_SHOWN = prelude(r'''    if (out[0]) printf(" d2=%g", mxGetScalar(out[0]));
     if (out[1]) printf(" S=%zux%zu[%g,%g,%g,%g]", mxGetM(out[1]), mxGetN(out[1]), mxGetPr(out[1])[0], mxGetPr(out[1])[1], mxGetPr(out[1])[2], mxGetPr(out[1])[3]);
-    printf("\n");
-    return 0;
-}
-int main(void) {
-    const mxArray *cr[3] = { mock_string("create"), mock_double(1, 1, (const double[]){ 1 }), mock_double(1, 1, (const double[]){ 64 }) };
-    if (call("create", 1, 3, cr)) return 1;
-    const mxArray *h = out[0];
+''')
+
+_DRIVER = driver(r'''
     const mxArray *delta = mock_double(2, 1, (const double[]){ 0.5, -1 }), *R = mock_double(2, 2, (const double[]){ 4, 1, 1, 9 });
     const mxArray *con[6] = { mock_string("constrain_landmarks"), h, mock_double(1, 1, (const double[]){ 3 }), mock_double(1, 1, (const double[]){ 7 }), delta, R };
     const mxArray *mer[5] = { mock_string("merge_landmarks"), h, mock_double(1, 1, (const double[]){ 8 }), mock_double(1, 1, (const double[]){ 2 }), R };
@@ -262,62 +226,21 @@ int main(void) {
     if (!call("merge_landmarks", 0, 5, mer)) return 1;
     arm_failure();
     if (!call("landmark_distance", 2, 6, dis)) return 1;
-    const mxArray *de[2] = { mock_string("destroy"), h };
-    if (call("destroy", 0, 2, de)) return 1;
-    printf("LOCKS %d\nMISUSE %d\n", mock_lock_count, mock_misuse);
-    return 0;
-}
-'''
+''', _SHOWN)
 
-_DRIVER_WITHOUT = r'''
-#include <setjmp.h>
-#include <stdio.h>
-#include "ekfslam.h"
-#include "mex_mock.h"
-static mxArray *out[4];
-static int call(const char *what, int nrhs, const mxArray **prhs) {
-    out[0] = 0;
-    if (setjmp(mock_err_jmp)) { printf("MEX %s nrhs=%d -> ERROR %s | %s\n", what, nrhs, mock_err_id, mock_err_msg); return 1; }
-    mexFunction(1, out, nrhs, prhs);
-    printf("MEX %s nrhs=%d -> ok\n", what, nrhs);
-    return 0;
-}
-int main(void) {
-    const mxArray *cr[3] = { mock_string("create"), mock_double(1, 1, (const double[]){ 1 }), mock_double(1, 1, (const double[]){ 64 }) };
-    if (call("create", 3, cr)) return 1;
-    const mxArray *h = out[0];
+_DRIVER_WITHOUT = driver_without(r'''
     const mxArray *delta = mock_double(2, 1, (const double[]){ 0, 0 }), *R = mock_double(2, 2, (const double[]){ 0, 0, 0, 0 });
     const mxArray *one = mock_double(1, 1, (const double[]){ 1 }), *two = mock_double(1, 1, (const double[]){ 2 });
     const mxArray *con[6] = { mock_string("constrain_landmarks"), h, one, two, delta, R };
     const mxArray *mer[5] = { mock_string("merge_landmarks"), h, one, two, R };
     const mxArray *dis[6] = { mock_string("landmark_distance"), h, one, two, delta, R };
-    if (!call("constrain_landmarks", 6, con) || !call("merge_landmarks", 5, mer) || !call("landmark_distance", 6, dis)) return 1;
-    const mxArray *pr[3] = { mock_string("predict"), h, mock_double(2, 1, (const double[]){ 0.1, 3 }) };
-    if (call("predict", 3, pr)) return 1;
-    const mxArray *de[2] = { mock_string("destroy"), h };
-    if (call("destroy", 2, de)) return 1;
-    printf("LOCKS %d\nMISUSE %d\n", mock_lock_count, mock_misuse);
-    return 0;
-}
-'''
-
-
-def _build_and_run(d, files, exe):
-    r = subprocess.run(GCC + INCLUDES + [os.path.join(ROOT, "matlab", "ekfslam_mex.c"), os.path.join(MOCK, "mex_mock.c"),
-                                         os.path.join(MOCK, "abi_stub.c")] + files + ["-o", exe], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-4000:]
-    r = subprocess.run([exe], capture_output=True, text=True, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=0"))
-    assert r.returncode == 0, "the gateway misbehaved under the mock:\n" + r.stdout[-2000:] + r.stderr[-4000:]
-    return r.stdout.splitlines()
+    if (!call("constrain_landmarks", 1, 6, con) || !call("merge_landmarks", 1, 5, mer) || !call("landmark_distance", 1, 6, dis)) return 1;
+''')
 
 
 @pytest.fixture(scope="module")
 def transcript(tmp_path_factory):
-    d = tmp_path_factory.mktemp("mexmerge")
-    stub, drv = d / "merge_stub.c", d / "merge_drv.c"
-    stub.write_text(_STUB)
-    drv.write_text(_DRIVER)
-    return _build_and_run(d, [str(stub), str(drv)], str(d / "drv"))
+    return transcript_of(tmp_path_factory.mktemp("mexmerge"), _STUB, _DRIVER)
 
 
 def test_mex_gateway_hands_one_based_numbers_on_as_zero_based(transcript):
@@ -342,9 +265,7 @@ def test_mex_gateway_hands_one_based_numbers_on_as_zero_based(transcript):
 
 
 def test_the_gateway_still_links_against_a_library_without_the_new_symbols(tmp_path):
-    drv = tmp_path / "without_drv.c"
-    drv.write_text(_DRIVER_WITHOUT)
-    t = _build_and_run(tmp_path, [str(drv)], str(tmp_path / "drv"))
+    t = transcript_of(tmp_path, _DRIVER_WITHOUT)
     for cmd, sym in (("constrain_landmarks", "ekf_constrain_landmarks"), ("merge_landmarks", "ekf_merge_landmarks"),
                      ("landmark_distance", "ekf_landmark_distance")):
         assert any(ln.startswith("MEX %s " % cmd) and "ERROR ekfslam:usage" in ln and "this libekfslam has no %s" % sym in ln for ln in t)

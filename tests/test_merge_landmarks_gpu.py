@@ -14,91 +14,13 @@ import ctypes
 import numpy as np
 import pytest
 
-from merge_cases import Factored, constrain_dense, merge_dense
+from decided_plans import PARAMS
+from helpers import R2, REL, RPOS, STORES_ALL, TOL_KEPT32, TOL_ROW32, TOL_X32, U2, assert_same, check_state, engine, loaded, rel_err, run_ops, state, status_of
+from merge_cases import Factored, constrain_dense, continuation, merge_dense, tile_edge_landmark
 from removal_cases import lowrank_data, observe
 
 pytestmark = pytest.mark.gpu
-REL = 1e-6                      # BASELINE.json's bar against the oracle
-TOL_X32, TOL_KEPT32, TOL_ROW32 = 1e-9, 2e-9, 2e-7        # DESIGN.md section 5, one step
 N0 = 300
-U2 = np.array([0.1, 1.0])
-R2 = np.diag([0.1, 0.2])
-RPOS = np.array([[0.02, 0.005], [0.005, 0.03]])
-STORES = [(16, "f64"), (64, "f64"), (128, "f64"), (256, "f32"), (256, "f32_mixed"), (256, "f32_split")]
-
-
-def rel_err(a, b):
-    a, b = np.asarray(a), np.asarray(b)
-    return float(np.abs(a - b).max() / max(np.abs(b).max(), 1e-300))
-
-
-def engine(mode="known", **kw):
-    from ekf_slam_amd.engine import Engine
-    return Engine(mode=mode, **kw)
-
-
-def loaded(N, seed, mode="known", x=None, **kw):
-    x0, s, d, U = lowrank_data(N, seed)
-    e = engine(mode, **kw)
-    e.load_lowrank_state(x0 if x is None else x, s, d, U)
-    return e
-
-
-def state(e):
-    return e.get_x(), e.get_s(), e.get_P()
-
-
-def blocks_of(P):
-    n = P.shape[0]
-    starts = np.concatenate([[0], np.arange(3, n, 2)])
-    return np.array([P[a:a + 2, a:a + 2] for a in starts])
-
-
-def assert_same(a, b, digest=True):
-    assert a.N == b.N
-    np.testing.assert_array_equal(a.get_x(), b.get_x())
-    np.testing.assert_array_equal(a.get_s(), b.get_s())
-    np.testing.assert_array_equal(a.get_P(), b.get_P())
-    np.testing.assert_array_equal(a.get_P_diag_blocks(), b.get_P_diag_blocks())
-    if digest:
-        np.testing.assert_array_equal(a.digest(), b.digest())
-
-
-def check_state(e, ex, es, eP, storage, label):
-    """x, s, P and the diagonal blocks of e against the expectation, by the module's tolerances; P symmetric as read."""
-    x, s, P = state(e)
-    blocks = e.get_P_diag_blocks()
-    assert e.N == es.size
-    np.testing.assert_array_equal(s, es)
-    np.testing.assert_array_equal(P, P.T)
-    n = ex.size
-    kept = np.zeros((n, n), dtype=bool)                      # what float handles keep in F64
-    kept[:3, :] = kept[:, :3] = True
-    for a in range(3, n, 2):
-        kept[a:a + 2, a:a + 2] = True
-    scale = np.abs(eP).max()
-    err_x, err_P, err_b = rel_err(x, ex), rel_err(P, eP), rel_err(blocks, blocks_of(eP))
-    err_kept = float(np.abs(P - eP)[kept].max() / scale)
-    err_row = float((np.abs(P - eP).max(axis=1) / np.abs(eP).max(axis=1)).max())
-    print("%s [%s]: rel err x %.2e P %.2e blocks %.2e F64-kept %.2e worst row %.2e" % (label, storage, err_x, err_P, err_b, err_kept, err_row))
-    if storage == "f64":
-        assert err_x < REL and err_P < REL and err_b < REL
-    else:
-        assert err_x < TOL_X32 and err_kept < TOL_KEPT32 and err_b < TOL_KEPT32 and err_row <= TOL_ROW32
-
-
-def status_of(fn):
-    from ekf_slam_amd._lib import EkfError
-    try:
-        fn()
-    except EkfError as ex:
-        return ex.status, str(ex)
-    return 0, ""
-
-
-def tile_edge_landmark(T):
-    per_row = T // 2
-    return per_row * max(1, (N0 // 2) // per_row)            # first landmark of a tile row near the middle of the map
 
 
 def near(x, keep, drop, off=(0.05, -0.03)):
@@ -112,7 +34,7 @@ def near(x, keep, drop, off=(0.05, -0.03)):
 # 1. constrain and merge against the dense restatement
 # ------------------------------------------------------------------------------------------------------------------
 def _cases(T):
-    e = tile_edge_landmark(T)
+    e = tile_edge_landmark(T, N0)
     d = np.array([0.3, -0.1])
     # name: (i, j, delta, R) of the constrain, then (keep, drop, R) of the merge that follows on the same handle
     return {"same_tile_i_lt_j_R0": ((e + 1, e + 2, None, None), (e + 2, e + 3, RPOS)),
@@ -121,7 +43,7 @@ def _cases(T):
             "last_first_Rpos": ((N0 - 1, 0, None, RPOS), (0, N0 - 1, RPOS))}
 
 
-@pytest.mark.parametrize("tile,storage", STORES)
+@pytest.mark.parametrize("tile,storage", STORES_ALL)
 @pytest.mark.parametrize("name", ["same_tile_i_lt_j_R0", "over_tile_edge_i_gt_j_delta_Rpos", "first_last_delta_R0", "last_first_Rpos"])
 def test_constrain_and_merge_against_the_dense_restatement(tile, storage, name):
     (i, j, delta, R), (keep, drop, Rm) = _cases(tile)[name]
@@ -130,7 +52,7 @@ def test_constrain_and_merge_against_the_dense_restatement(tile, storage, name):
     ex, eP, d2, S = constrain_dense(x0, P0, i, j, delta, R)
     e.constrain_landmarks(i, j, delta, R)
     assert e.pending() == 0 and e.N == N0
-    check_state(e, ex, s0, eP, storage, "constrain (%d, %d) d2 %.0f" % (i, j, d2))
+    check_state(e, ex, eP, storage, "constrain (%d, %d) d2 %.0f" % (i, j, d2), es=s0)
     if R is None:                                            # R = 0: the constraint now holds exactly
         got = e.get_x()
         want = np.zeros(2) if delta is None else delta
@@ -140,7 +62,7 @@ def test_constrain_and_merge_against_the_dense_restatement(tile, storage, name):
     e.merge_landmarks(keep, drop, Rm)
     assert e.pending() == 0 and e.N == N0 - 1
     np.testing.assert_array_equal(ms, np.delete(s1, drop))   # keep retains its signature, the survivors their order
-    check_state(e, mx, ms, mP, storage, "merge (%d <- %d)" % (keep, drop))
+    check_state(e, mx, mP, storage, "merge (%d <- %d)" % (keep, drop), es=ms)
     k2 = keep - (drop < keep)
     assert e.get_s()[k2] == s1[keep]
 
@@ -148,9 +70,9 @@ def test_constrain_and_merge_against_the_dense_restatement(tile, storage, name):
 # ------------------------------------------------------------------------------------------------------------------
 # 2. merge == constrain + remove
 # ------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("tile,storage", STORES)
+@pytest.mark.parametrize("tile,storage", STORES_ALL)
 def test_merge_is_constrain_then_remove_bit_for_bit(tile, storage):
-    edge = tile_edge_landmark(tile)
+    edge = tile_edge_landmark(tile, N0)
     a = loaded(N0, 5, capacity=N0 + 8, tile=tile, storage=storage, batch=4)
     b = loaded(N0, 5, capacity=N0 + 8, tile=tile, storage=storage, batch=4)
     x = lowrank_data(N0, 5)[0]
@@ -205,41 +127,6 @@ def test_with_corrections_pending_and_a_lazy_predict(mode, batch, asy):
 # ------------------------------------------------------------------------------------------------------------------
 # 4. the engine goes on correctly
 # ------------------------------------------------------------------------------------------------------------------
-def _continuation(ex, es, tile, batch, capacity, hole):
-    """Operations (pure function of the state after the merge): appends that cross a tile-row edge, measure() scans with corrections
-    around the merged pair and new landmarks, two full batches of corrections."""
-    N = es.size
-    per_row = tile // 2
-    ops = []
-    n_app = per_row - N % per_row + 3
-    assert N + n_app + 8 <= capacity
-    rng = np.random.default_rng(2)
-    for i in range(n_app):
-        ops.append(("append", rng.uniform(-20, 20, 2), 5000.0 + i))
-    around = sorted({max(hole - 1, 0), min(hole, N - 1), min(hole + 1, N - 1), 1, N - 2, N // 3})
-    lm_index = np.arange(1, capacity + 1, dtype=np.float64)
-    lm_loc = np.random.default_rng(3).uniform(-20, 20, (capacity, 2))
-    for t in range(3):
-        rows = [list(observe(ex, k, dr=0.01 * (t + 1))) + [float(es[k])] for k in around[t::2] + around[:2]]
-        rows.append([3.0 + t, 45.0, 9e6 + t])                # matches no signature: appended (EKF_SLAM_UC.m:121-123)
-        ops.append(("measure", np.array(rows), lm_index, lm_loc))
-    for i in range(2 * batch):
-        k = around[i % len(around)] if i % 3 else int(rng.integers(0, N))
-        ops.append(("correct", observe(ex, k, dr=0.02), k))
-    return ops
-
-
-def _run(e, ops):
-    for op in ops:
-        e.predict(U2)
-        if op[0] == "append":
-            e.append(U2, R2, op[1], op[2])
-        elif op[0] == "measure":
-            e.measure(op[1], U2, op[2], op[3])
-        else:
-            e.correct(op[1], R2, op[2])
-
-
 @pytest.mark.parametrize("tile,storage,batch,asy", [(16, "f64", 8, False), (64, "f64", 8, True), (128, "f64", 32, False),
                                                     (256, "f32", 8, False), (256, "f32_mixed", 8, False), (256, "f32_mixed", 64, True),
                                                     (256, "f32_split", 32, False)])
@@ -258,13 +145,13 @@ def test_the_engine_goes_on_like_a_twin_given_the_expected_state(tile, storage, 
     assert d2 < 1.0                                          # a duplicate: the gate a caller would apply lets it through
     mx, ms, mP = merge_dense(x0, s0, P0, keep, drop, RPOS)
     e.merge_landmarks(keep, drop, RPOS)
-    check_state(e, mx, ms, mP, storage, "life-like merge (%d <- %d) d2 %.3f" % (keep, drop, d2))
+    check_state(e, mx, mP, storage, "life-like merge (%d <- %d) d2 %.3f" % (keep, drop, d2), es=ms)
     ex, es, eP = state(e)
     twin = engine("uc", **kw)
     twin.set_state(ex, eP, es)
-    ops = _continuation(ex, es, tile, batch, cap, drop)
-    _run(e, ops)
-    _run(twin, ops)
+    ops = continuation(ex, es, tile, batch, cap, drop)
+    run_ops(e, ops)
+    run_ops(twin, ops)
     assert e.N == twin.N and e.N > es.size + 3
     if storage == "f64":
         assert_same(e, twin)                                 # the same bits
@@ -278,7 +165,6 @@ def test_the_engine_goes_on_like_a_twin_given_the_expected_state(tile, storage, 
 # ------------------------------------------------------------------------------------------------------------------
 # 5. association sees the new map
 # ------------------------------------------------------------------------------------------------------------------
-POS = dict(w_pos=1.0, Rc=(0.01, 0.01), s_thresh=0.5)         # the position-weighted likelihood of tests/test_decided_assoc_gpu.py
 K_KEEP, K_GONE = 50, 100
 
 
@@ -324,7 +210,7 @@ def test_association_sees_the_new_map_signature_only(early):
 
 @pytest.mark.parametrize("early", [False, True])
 def test_association_sees_the_new_map_position_weighted(early):
-    runs = {m: _assoc_run(m, POS, early) for m in (0, 1, 4)}
+    runs = {m: _assoc_run(m, PARAMS, early) for m in (0, 1, 4)}
     for m in (0, 4):                                         # mode 4 with `early`: the merge arrives on unsettled rows
         assert_same(runs[m], runs[1])
 
@@ -332,9 +218,9 @@ def test_association_sees_the_new_map_position_weighted(early):
 # ------------------------------------------------------------------------------------------------------------------
 # 6. the distance
 # ------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("tile,storage", STORES)
+@pytest.mark.parametrize("tile,storage", STORES_ALL)
 def test_landmark_distance_matches_and_changes_nothing(tile, storage):
-    edge = tile_edge_landmark(tile)
+    edge = tile_edge_landmark(tile, N0)
     e = loaded(N0, 5, capacity=N0 + 8, tile=tile, storage=storage, batch=8)
     x = lowrank_data(N0, 5)[0]
     for k in (4, edge, 200):
@@ -482,9 +368,9 @@ def test_checkpoint_after_a_merge(tile, storage, tmp_path):
     fresh = engine("uc", **kw)
     fresh.checkpoint_load(path)
     np.testing.assert_array_equal(fresh.get_P(), eP)
-    ops = _continuation(ex, es, tile, 8, cap, 200)
-    _run(e, ops)
-    _run(fresh, ops)
+    ops = continuation(ex, es, tile, 8, cap, 200)
+    run_ops(e, ops)
+    run_ops(fresh, ops)
     assert_same(e, fresh)
 
 

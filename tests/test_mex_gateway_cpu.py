@@ -18,9 +18,7 @@ import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-MOCK = os.path.join(ROOT, "tests", "support", "mex_mock")
-INCLUDES = ["-I", os.path.join(ROOT, "include"), "-I", os.path.join(ROOT, "tests", "support", "mex_api_subset"), "-I", MOCK]
+from mex_harness import INCLUDES, MOCK, ROOT, build_and_run
 
 
 def test_mex_gateway_type_checks_against_the_abi():
@@ -60,16 +58,7 @@ def test_matlab_classes_only_use_commands_the_gateway_implements():
 
 @pytest.fixture(scope="module")
 def transcript(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("mexmock") / "mexdrv")
-    r = subprocess.run(["gcc", "-std=c99", "-Wall", "-Wextra", "-Werror", "-g", "-fsanitize=address,undefined",
-                        "-fno-sanitize-recover=undefined"] + INCLUDES +
-                       [os.path.join(ROOT, "matlab", "ekfslam_mex.c")] +
-                       [os.path.join(MOCK, f) for f in ("mex_mock.c", "abi_stub.c", "driver.c")] + ["-o", exe],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-4000:]
-    r = subprocess.run([exe], capture_output=True, text=True, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=0"))
-    assert r.returncode == 0, "the gateway crashed under the mock:\n" + r.stdout[-2000:] + r.stderr[-4000:]
-    return r.stdout.splitlines()
+    return build_and_run([os.path.join(MOCK, "driver.c")], str(tmp_path_factory.mktemp("mexmock") / "mexdrv"))
 
 
 def _after(lines, mex_prefix, nth=0):

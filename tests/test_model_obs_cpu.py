@@ -1,65 +1,26 @@
 """CPU: the observation models of ekf_observe_model (tests/model_obs_cases.py: hand-derived answers; the compiled ekfm::model_eval of
 ekf_slam_amd/csrc/device_math.h against the closed forms and finite differences), the sixth kind of the trajectory log, and the argument
 handling of the Python layers over a stand-in for the library.  No GPU."""
-import ctypes
-import os
 import subprocess
 
 import numpy as np
 import pytest
 
 import model_obs_cases as M
+from helpers import RPOS, RecorderBase, host_build, line_program, same_npz
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-RPOS = np.array([[0.02, 0.005], [0.005, 0.03]])
 INF = float("inf")
 
 
 @pytest.fixture(scope="module")
 def host(tmp_path_factory):
     """The stand-alone host build of ekfm::model_eval / model_small: host(lines) -> one list of floats per line."""
-    exe = str(tmp_path_factory.mktemp("model_eval") / "model_eval_host")
-    subprocess.run(["g++", "-O2", "-mfma", "-ffp-contract=off", "-I", os.path.join(ROOT, "ekf_slam_amd", "csrc"),
-                    os.path.join(ROOT, "tests", "support", "model_eval_host.cpp"), "-o", exe], check=True)
-
-    def run(lines):
-        out = subprocess.run([exe], input="\n".join(lines) + "\n", check=True, capture_output=True, text=True).stdout
-        rows = [[float(v) for v in ln.split()] for ln in out.strip().split("\n")]
-        assert len(rows) == len(lines)
-        return rows
-    return run
-
-
-def _fmt(vals):
-    return " ".join(repr(float(v)) for v in vals)
+    return line_program(tmp_path_factory, "model_eval_host")
 
 
 def eval_line(model, xr, t0, t1=None, anchored=False):
     t1 = [0.0, 0.0] if t1 is None else t1
-    return "eval %d %d %s" % (model, 0 if anchored else 1, _fmt(list(xr) + ([0.0, 0.0] if anchored else list(t0)) + list(t1) + list(t0 if anchored else [0.0, 0.0])))
-
-
-def small_line(o, x, P):
-    """The 38 operands of linear_small for observation o on the dense state (x, P)."""
-    lm = o["landmarks"]
-    rows = list(range(3)) + sum(([3 + 2 * k, 4 + 2 * k] for k in lm), [])
-    Ps, xs = np.zeros((7, 7)), np.zeros(7)
-    Ps[:len(rows), :len(rows)] = P[np.ix_(rows, rows)]
-    xs[:len(rows)] = x[rows]
-    sm = list(Ps[:3, :3].reshape(-1))
-    for b in range(2):
-        sm += [Ps[t, 3 + 2 * b + r] for t in range(3) for r in range(2)]
-    for b in range(2):
-        a = 3 + 2 * b
-        sm += [Ps[a, a], Ps[a + 1, a], Ps[a + 1, a + 1]]
-    sm += [Ps[3 + r, 5 + c] for r in range(2) for c in range(2)]
-    sm += list(xs)
-    R = M.effective_R(o)
-    anchor = [0.0, 0.0] if o["anchor"] is None else o["anchor"]
-    z = o["z"].copy()
-    if o["rows"] == 1:
-        z[1] = 0.0
-    return "small %d %d %s" % (o["model"], 1 if lm else 0, _fmt(list(z) + list(R.reshape(-1)) + [o["gate"]] + list(anchor) + sm))
+    return "eval %d %d %s" % (model, 0 if anchored else 1, M.fmt(list(xr) + ([0.0, 0.0] if anchored else list(t0)) + list(t1) + list(t0 if anchored else [0.0, 0.0])))
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -78,7 +39,7 @@ def test_a_range_of_six_to_a_landmark_five_away(host):
     np.testing.assert_allclose(res["S"], [[4.0, 0.0], [0.0, 1.0]], atol=1e-15)
     np.testing.assert_allclose(x2, [-0.15, -0.2, 0.0, 3.15, 4.2], atol=1e-15)
     # the compiled function: the same H bit for bit (3/5 and 4/5 are correctly rounded divisions), S, nu, d2
-    ev, sm = host([eval_line(M.RANGE, x[:3], x[3:5]), small_line(o, x, P)])
+    ev, sm = host([eval_line(M.RANGE, x[:3], x[3:5]), M.small_line(o, x, P)])
     assert ev[0] == 1 and ev[1:3] == [5.0, 0.0] and ev[3:10] == [-0.6, -0.8, 0.0, 0.6, 0.8, 0.0, 0.0] and not any(ev[10:])
     assert sm[:2] == [1, 1] and sm[3:5] == [1.0, 0.0] and sm[2] == pytest.approx(0.25, abs=1e-15)
     np.testing.assert_allclose(sm[5:9], [4.0, 0.0, 0.0, 1.0], atol=1e-15)
@@ -95,7 +56,7 @@ def test_a_bearing_across_180_degrees_is_wrapped(host):
         o = M.obs(model, z, np.diag([0.1, 0.3]) if model == M.RANGE_BEARING else 0.3, [0])
         res = M.observe_model_dense(x, P, o)[2]
         assert res["nu"][row] == pytest.approx(1.0, abs=1e-12)
-        sm = host([small_line(o, x, P)])[0]
+        sm = host([M.small_line(o, x, P)])[0]
         assert sm[1] == 1 and sm[3 + row] == pytest.approx(1.0, abs=1e-12)
         np.testing.assert_allclose(sm[5:9], res["S"].reshape(-1), rtol=0, atol=1e-13 * np.abs(res["S"]).max())
         assert sm[2] == pytest.approx(res["d2"], rel=1e-11)
@@ -176,7 +137,7 @@ def test_a_target_on_the_robot_is_irregular_and_finite(host):
     for row in host(lines):
         assert row[0] == 0 and not any(row[1:])              # h and H are zero: nothing that is not finite leaves the function
     o = M.obs(M.RANGE, [1.0], 0.5, [0])
-    sm = host([small_line(o, x, P), small_line(M.obs(M.RANGE_BEARING, [1.0, 2.0], RPOS, anchor=x[:2]), x[:3], P[:3, :3])])
+    sm = host([M.small_line(o, x, P), M.small_line(M.obs(M.RANGE_BEARING, [1.0, 2.0], RPOS, anchor=x[:2]), x[:3], P[:3, :3])])
     for row in sm:
         assert row[:2] == [0, 0] and np.isnan(row[2]) and np.all(np.isfinite(row[3:])) and not any(row[9:])
     x2, P2, res = M.observe_model_dense(x, P, o)
@@ -207,9 +168,7 @@ def test_dense_update_with_a_model_is_the_linear_update_with_its_jacobian():
 def test_kernel_sources_on_the_host_match_the_linear_gather_bit_for_bit(tmp_path):
     """tests/support/model_obs_host_emulation.cpp: k_gather_model against k_gather_linear handed the Jacobian model_eval gives the host,
     with 0 and 3 pairs pending, tiles of edge 16 and 64; k_model_probe against the launch; a target on the robot as a finite no-op."""
-    exe = str(tmp_path / "model_obs_host_emulation")
-    subprocess.run(["g++", "-O2", "-mfma", "-ffp-contract=off", "-std=c++17", "-I", os.path.join(ROOT, "ekf_slam_amd", "csrc"),
-                    os.path.join(ROOT, "tests", "support", "model_obs_host_emulation.cpp"), "-o", exe], check=True)
+    exe = host_build("model_obs_host_emulation", str(tmp_path / "model_obs_host_emulation"))
     r = subprocess.run([exe], capture_output=True, text=True)
     lines = r.stdout.strip().split("\n")
     assert r.returncode == 0, r.stdout[-3000:]
@@ -245,14 +204,6 @@ def _steps(log, n):
         log.record([0.1, 1.0 + k], np.array([[1.0, 2.0, 3.0]]) if k % 2 else None, [1.0, 2.0], [[0.0, 1.0], [2.0, 3.0]])
 
 
-def _same_file(a, b):
-    """Two .npz files hold the same arrays in the same order, name by name, dtype, shape and bytes (the zip container itself carries
-    the time of writing, so the files are compared member by member)."""
-    ga, gb = np.load(a), np.load(b)
-    return ga.files == gb.files and all(ga[k].dtype == gb[k].dtype and ga[k].shape == gb[k].shape and ga[k].tobytes() == gb[k].tobytes()
-                                        for k in ga.files)
-
-
 def test_trajectory_format_five_round_trip_and_the_older_formats(tmp_path):
     from ekf_slam_amd.trajectory import FORMAT, FORMAT_BATCH, FORMAT_EDITS, FORMAT_MODEL, FORMAT_OBSERVE, TrajectoryLog
     assert FORMAT_MODEL == "ekfslam-trajectory-5"
@@ -274,7 +225,7 @@ def test_trajectory_format_five_round_trip_and_the_older_formats(tmp_path):
         back = TrajectoryLog.load(tmp_path / (name + ".npz"))
         assert len(back) == len(log) and len(back.edits) == len(log.edits) and back.model_observations == {}
         back.save(tmp_path / (name + "_again.npz"))
-        assert _same_file(tmp_path / (name + ".npz"), tmp_path / (name + "_again.npz"))
+        assert same_npz(tmp_path / (name + ".npz"), tmp_path / (name + "_again.npz"))
     # version 5: model observations among the other edits, with and without linear ones
     five = TrajectoryLog(); _steps(five, 2)
     five.record_edit("remove", [7])
@@ -295,7 +246,7 @@ def test_trajectory_format_five_round_trip_and_the_older_formats(tmp_path):
     assert back.model_observations[3]["anchor"].tolist() == [10.0, -4.0] and back.model_observations[3]["gate"] == INF
     np.testing.assert_array_equal(back.edits[1][3], [5.0, 30.0]); np.testing.assert_array_equal(back.edits[1][4], RPOS)
     back.save(tmp_path / "five_again.npz")
-    assert _same_file(tmp_path / "five.npz", tmp_path / "five_again.npz")
+    assert same_npz(tmp_path / "five.npz", tmp_path / "five_again.npz")
     r = _Replayed()
     back.replay(r)
     assert r.calls == [("predict",), ("predict",), ("measure",), ("remove", [6]),
@@ -321,22 +272,11 @@ def test_trajectory_format_five_round_trip_and_the_older_formats(tmp_path):
 # ------------------------------------------------------------------------------------------------------------------
 # the Python layers over a stand-in for the library
 # ------------------------------------------------------------------------------------------------------------------
-class _Recorder:
+class _Recorder(RecorderBase):
+    last_error = b"observe_model: injected"
+
     def __init__(self):
         self.calls, self.fail = [], 0
-
-    def ekf_config_default(self, pcfg, mode):
-        from ekf_slam_amd import _lib as L
-        cfg = ctypes.cast(pcfg, ctypes.POINTER(L.EkfConfig)).contents
-        cfg.mode, cfg.batch = mode, 1
-        return 0
-
-    def ekf_create(self, pcfg, ph):
-        ctypes.cast(ph, ctypes.POINTER(ctypes.c_void_p)).contents.value = 0x1000
-        return 0
-
-    def ekf_destroy(self, h):
-        return 0
 
     def _note(self, name, pobs, pres):
         o = pobs._obj
@@ -360,12 +300,6 @@ class _Recorder:
         self.calls.append(("evaluate", model, [xr[i] for i in range(3)], [t0[0], t0[1]], None if not t1 else [t1[0], t1[1]]))
         hx[0], H[13] = 7.0, 9.0
         return self.fail
-
-    def ekf_status_string(self, rc):
-        return b"call not valid in the current state"
-
-    def ekf_last_error(self, h):
-        return b"observe_model: injected"
 
 
 def test_engine_and_slam_layers_marshal_a_model_observation_once(monkeypatch):

@@ -2,7 +2,7 @@
 include/ekfslam.h).
 
 The yardstick is the NumPy restatement of tests/model_obs_cases.py applied to THE STATE THE ENGINE REPORTED BEFORE THE CALL; stores,
-tolerances and helpers are those of tests/test_linear_obs_gpu.py.  Where two engines must agree because they ran the same arithmetic
+tolerances and helpers are those of tests/helpers.py.  Where two engines must agree because they ran the same arithmetic
 on the same inputs -- k_gather_model against k_gather_linear handed the Jacobian the host evaluates, batch b against batch 1, the
 device-resident association loops against the waited one, a replayed log -- the comparison is assert_array_equal.
 
@@ -13,11 +13,12 @@ import numpy as np
 import pytest
 
 import model_obs_cases as M
-import test_linear_obs_gpu as T
+from decided_plans import PARAMS
+from helpers import R2, REL, RPOS, U2, assert_same, check_state, engine, getters, loaded, rel_err, state, status_of
+from linear_obs_cases import N0, STORES, edge_landmark
 from removal_cases import lowrank_data, observe
 
 pytestmark = pytest.mark.gpu
-N0, U2, R2, RPOS, REL = T.N0, T.U2, T.R2, T.RPOS, T.REL
 NAMES = {M.RANGE_BEARING: "range and bearing", M.RANGE: "range", M.BEARING: "bearing", M.RELATIVE_XY: "relative xy", M.LANDMARK_RANGE: "landmark range"}
 
 
@@ -50,7 +51,7 @@ def history(engines, x, ks):
 def _specs(T_):
     """(name, model, landmarks, anchor offset from the robot or None): every model at the first, the last and a tile-row-edge landmark,
     the anchor forms, and the landmark pairs in one tile, in different tile rows, adjacent over a tile edge, in both orders."""
-    e = T.edge_landmark(T_)
+    e = edge_landmark(T_)
     out = []
     for m in (M.RANGE_BEARING, M.RANGE, M.BEARING, M.RELATIVE_XY):
         for k, where in ((0, "first"), (N0 - 1, "last"), (e, "tile-row edge")):
@@ -62,22 +63,22 @@ def _specs(T_):
     return out
 
 
-@pytest.mark.parametrize("tile,storage", T.STORES)
+@pytest.mark.parametrize("tile,storage", STORES)
 def test_every_model_against_the_dense_restatement(tile, storage):
-    e = T.loaded(N0, 5, capacity=N0 + 8, tile=tile, storage=storage)
+    e = loaded(N0, 5, capacity=N0 + 8, tile=tile, storage=storage)
     x = lowrank_data(N0, 5)[0]
-    history([e], x, (5, T.edge_landmark(tile), N0 - 3))     # some history first, so that P is not the loaded one
+    history([e], x, (5, edge_landmark(tile), N0 - 3))     # some history first, so that P is not the loaded one
     for name, m, lms, off in _specs(tile):
-        x0, _, P0 = T.state(e)
+        x0, _, P0 = state(e)
         o = near(x0, m, lms, None if off is None else x0[:2] + off)
         ex, eP, want = M.observe_model_dense(x0, P0, o)
         got = send(e, o, wait=True)
         assert got["outcome"] == want["outcome"] == M.APPLIED, name
         tol = REL if storage == "f64" else 1e-9               # F64 arithmetic on what the getters report, in every storage kind
-        errs = (T.rel_err(got["nu"], want["nu"]), T.rel_err(got["S"], want["S"]), abs(got["d2"] - want["d2"]) / want["d2"])
+        errs = (rel_err(got["nu"], want["nu"]), rel_err(got["S"], want["S"]), abs(got["d2"] - want["d2"]) / want["d2"])
         print("%s [%s]: d2 %.4g rel err nu %.2e S %.2e d2 %.2e" % ((name, storage, got["d2"]) + errs))
         assert max(errs) < tol, name
-        T.check_state(e, ex, eP, storage, name)
+        check_state(e, ex, eP, storage, name)
         if o["rows"] == 1:
             assert got["S"][0, 1] == 0.0 and got["S"][1].tolist() == [0.0, 1.0] and got["nu"][1] == 0.0
     assert e.N == N0 and e.linear_rejections() == (0, 0)
@@ -91,12 +92,12 @@ def test_every_model_against_the_dense_restatement(tile, storage):
 def test_P_is_bit_for_bit_that_of_observe_linear_with_the_evaluated_jacobian(tile, storage, pending):
     from ekf_slam_amd.engine import Engine
     x = lowrank_data(N0, 5)[0]
-    ed = T.edge_landmark(tile)
+    ed = edge_landmark(tile)
     kw = dict(capacity=N0 + 8, tile=tile, storage=storage, batch=8)
     for name, m, lms, off in (("range and bearing", M.RANGE_BEARING, [ed], None), ("range", M.RANGE, [N0 - 1], None), ("bearing", M.BEARING, [0], None),
                               ("relative xy", M.RELATIVE_XY, [ed], None), ("landmark range", M.LANDMARK_RANGE, [ed, ed - 1], None),
                               ("range and bearing, anchor", M.RANGE_BEARING, [], np.array([9.0, 5.0])), ("bearing, anchor", M.BEARING, [], np.array([-6.0, 11.0]))):
-        e, twin = T.loaded(N0, 5, **kw), T.loaded(N0, 5, **kw)
+        e, twin = loaded(N0, 5, **kw), loaded(N0, 5, **kw)
         history([e, twin], x, (5, ed, N0 - 3, 11, 40)[:pending])
         assert e.pending() == pending
         xe = e.get_x()
@@ -178,9 +179,9 @@ def _play(e, ops):
 @pytest.fixture(scope="module")
 def schedule_reference():
     ops = _schedule(18, 20, 60, 8)
-    one = T.loaded(20, 5, capacity=40, tile=16, batch=1)
+    one = loaded(20, 5, capacity=40, tile=16, batch=1)
     _play(one, ops)
-    return ops, T.getters(one), one.linear_rejections()
+    return ops, getters(one), one.linear_rejections()
 
 
 @pytest.mark.parametrize("batch,asy", [(3, False), (8, False), (3, True), (8, True)])
@@ -189,11 +190,11 @@ def test_a_schedule_with_model_observations_is_deferred_like_corrections(schedul
     assert sum(op[0] == "observe" for op in ops) >= 12 and sum(op[0] == "append" for op in ops) >= 5 and rejected[1] >= 1
     assert {op[1]["model"] for op in ops if op[0] == "observe"} == {1, 2, 3, 4, 5}
     assert all(np.all(np.isfinite(g)) for g in want)
-    e = T.loaded(20, 5, capacity=40, tile=16, batch=batch, async_flush=asy)
+    e = loaded(20, 5, capacity=40, tile=16, batch=batch, async_flush=asy)
     pend = _play(e, ops)
     assert max(pend) >= batch - 1 and (not asy or max(pend) > batch)      # the ring was in use (asynchronous: beyond one batch, so it wrapped)
     assert e.N > 24                                           # the appends crossed the tile-row edge at 24 landmarks
-    for got, ref in zip(T.getters(e), want):
+    for got, ref in zip(getters(e), want):
         np.testing.assert_array_equal(got, ref)
     assert e.linear_rejections() == rejected
 
@@ -201,7 +202,7 @@ def test_a_schedule_with_model_observations_is_deferred_like_corrections(schedul
 def test_a_model_observation_waits_for_the_batch_boundary():
     from ekf_slam_amd import _lib as L
     x = lowrank_data(N0, 5)[0]
-    e = T.loaded(N0, 5, capacity=N0 + 8, tile=64, batch=4)
+    e = loaded(N0, 5, capacity=N0 + 8, tile=64, batch=4)
     e.timing_enable(L.EKF_KERNEL_DOWNDATE, True, 16)
     e.timing_enable(L.EKF_KERNEL_GATHER, True, 16)
     e.timing_read(L.EKF_KERNEL_DOWNDATE); e.timing_read(L.EKF_KERNEL_GATHER)
@@ -221,8 +222,8 @@ def test_a_model_observation_waits_for_the_batch_boundary():
 def test_model_innovation_reports_what_the_observation_will_and_changes_nothing(tile, storage, asy):
     x = lowrank_data(N0, 5)[0]
     kw = dict(capacity=N0 + 8, tile=tile, storage=storage, batch=8, async_flush=asy)
-    e, twin = T.loaded(N0, 5, **kw), T.loaded(N0, 5, **kw)
-    history([e, twin], x, (5, T.edge_landmark(tile), N0 - 3, 11, 12, 40, 41, 42, 43, 44, 45))      # a full batch and three more
+    e, twin = loaded(N0, 5, **kw), loaded(N0, 5, **kw)
+    history([e, twin], x, (5, edge_landmark(tile), N0 - 3, 11, 12, 40, 41, 42, 43, 44, 45))      # a full batch and three more
     pend = e.pending()
     assert pend >= 3
     for name, m, lms, off in _specs(tile)[::2]:
@@ -238,7 +239,7 @@ def test_model_innovation_reports_what_the_observation_will_and_changes_nothing(
         for key in ("nu", "S", "d2", "outcome"):
             np.testing.assert_array_equal(np.asarray(got[key]), np.asarray(want[key]), err_msg=name + " " + key)
         pend = e.pending()
-    T.assert_same(e, twin)                                    # the twin never asked
+    assert_same(e, twin)                                    # the twin never asked
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -248,10 +249,10 @@ def test_gated_and_irregular_observations_change_nothing():
     from ekf_slam_amd import _lib as L
     x = lowrank_data(N0, 5)[0]
     kw = dict(capacity=N0 + 8, tile=64, batch=4)
-    e, twin = T.loaded(N0, 5, **kw), T.loaded(N0, 5, **kw)
+    e, twin = loaded(N0, 5, **kw), loaded(N0, 5, **kw)
     history([e, twin], x, (9,))                              # a pair pending
     assert e.linear_rejections() == (0, 0)
-    before = T.getters(twin)
+    before = getters(twin)
     xe = e.get_x()
     gated = near(xe, M.RANGE_BEARING, [12], dz=(2.0, 9.0))
     d2 = ask(e, gated)["d2"]
@@ -261,7 +262,7 @@ def test_gated_and_irregular_observations_change_nothing():
     # with a result: the outcome comes back, nothing read afterwards differs
     res = send(e, gated, wait=True)
     assert res["outcome"] == L.EKF_LINEAR_GATED and res["d2"] == d2 and e.pending() == 2
-    st, msg = T.status_of(lambda: send(e, on_robot, wait=True))
+    st, msg = status_of(lambda: send(e, on_robot, wait=True))
     assert st == L.EKF_ERR_STATE and "observe_model" in msg and e.pending() == 3
     inn = ask(e, on_robot)
     assert inn["outcome"] == L.EKF_LINEAR_IRREGULAR and np.isnan(inn["d2"]) and np.all(np.isfinite(inn["S"])) and np.all(np.isfinite(inn["nu"]))
@@ -271,7 +272,7 @@ def test_gated_and_irregular_observations_change_nothing():
     send(e, M.obs(M.RELATIVE_XY, [1.0, 2.0], RPOS, anchor=xe[:2]))
     assert e.pending() == 1
     assert e.linear_rejections() == (1, 1) and e.linear_rejections() == (0, 0)
-    for got, ref in zip(T.getters(e), before):
+    for got, ref in zip(getters(e), before):
         assert np.all(np.isfinite(got))
         np.testing.assert_array_equal(got, ref)
     # the same observation with a gate a factor 3 above d2 applies, and the handle goes on like a twin that never saw the no-ops
@@ -279,8 +280,8 @@ def test_gated_and_irregular_observations_change_nothing():
     for q in (e, twin):
         assert send(q, gated, wait=True)["outcome"] == L.EKF_LINEAR_APPLIED
         q.predict(U2); q.correct(observe(x, 12), R2, 12)
-    T.assert_same(e, twin)
-    assert T.rel_err(e.get_x()[27:29], before[0][27:29]) > 1e-6
+    assert_same(e, twin)
+    assert rel_err(e.get_x()[27:29], before[0][27:29]) > 1e-6
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -290,7 +291,7 @@ def test_refusals_leave_the_state_alone():
     from ekf_slam_amd import _lib as L
     x = lowrank_data(N0, 5)[0]
     kw = dict(capacity=N0 + 8, tile=64, batch=8)
-    e, twin = T.loaded(N0, 5, **kw), T.loaded(N0, 5, **kw)
+    e, twin = loaded(N0, 5, **kw), loaded(N0, 5, **kw)
     history([e, twin], x, (4, 77))
     x_before, pend = e.get_x(), e.pending()
     nan, inf = float("nan"), float("inf")
@@ -331,7 +332,7 @@ def test_refusals_leave_the_state_alone():
     one = make(M.RANGE, z=(1, nan), R=(3, -5.0)); one.R[1] = 7.0; one.anchor[0] = nan
     assert e.lib.ekf_model_innovation(e.h, ctypes.byref(one), ctypes.byref(res)) == L.EKF_OK and res.S[1] == 0.0 and res.S[3] == 1.0
     assert e.linear_rejections() == (0, 0)
-    T.assert_same(e, twin)
+    assert_same(e, twin)
     # ekf_model_evaluate: pure, refuses what it cannot evaluate
     hx, H = np.zeros(2), np.zeros(14)
     p = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
@@ -340,20 +341,20 @@ def test_refusals_leave_the_state_alone():
     assert e.lib.ekf_model_evaluate(2, p(xr), p(t0), None, p(hx), p(H)) == L.EKF_OK and hx[0] == 5.0
     assert e.lib.ekf_model_evaluate(2, p(xr), p(xr[:2].copy()), None, p(hx), p(H)) == L.EKF_ERR_STATE and not H.any() and not hx.any()
     # sharded handles: refused, the anchor forms included, and the message says why; the arguments are checked first
-    sh = T.engine(capacity=64, tile=16, world=2, rank=0)
+    sh = engine(capacity=64, tile=16, world=2, rank=0)
     for fn in (lambda: send(sh, M.obs(M.RANGE, [1.0], 0.5, [0])), lambda: send(sh, M.obs(M.RANGE, [1.0], 0.5, anchor=[3.0, 4.0])),
                lambda: ask(sh, M.obs(M.BEARING, [1.0], 0.5, anchor=[3.0, 4.0]))):
-        st, msg = T.status_of(fn)
+        st, msg = status_of(fn)
         assert st == bad and "shard" in msg
-    st, msg = T.status_of(lambda: send(sh, M.obs(M.RANGE, [nan], 0.5, anchor=[3.0, 4.0])))
+    st, msg = status_of(lambda: send(sh, M.obs(M.RANGE, [nan], 0.5, anchor=[3.0, 4.0])))
     assert st == bad and "shard" not in msg
 
 
 @pytest.mark.parametrize("batch", [1, 4])
 def test_a_lone_shard_with_the_sharded_code_path_simply_works(batch):
     x = lowrank_data(N0, 5)[0]
-    e = T.loaded(N0, 5, capacity=N0 + 8, tile=64, force_sharded=1, batch=batch)
-    twin = T.loaded(N0, 5, capacity=N0 + 8, tile=64, batch=batch)
+    e = loaded(N0, 5, capacity=N0 + 8, tile=64, force_sharded=1, batch=batch)
+    twin = loaded(N0, 5, capacity=N0 + 8, tile=64, batch=batch)
     harr = (ctypes.c_void_p * 1)(e.h)
 
     def corrections(ks):
@@ -373,7 +374,7 @@ def test_a_lone_shard_with_the_sharded_code_path_simply_works(batch):
     for q in (e, twin):
         assert send(q, near(x, M.RELATIVE_XY, [149]), wait=True)["outcome"] == 1
     corrections((1, 148))
-    T.assert_same(e, twin)
+    assert_same(e, twin)
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -381,7 +382,7 @@ def test_a_lone_shard_with_the_sharded_code_path_simply_works(batch):
 # ------------------------------------------------------------------------------------------------------------------
 def _uc_run(device_assoc, params):
     cap = N0 + 40
-    e = T.loaded(N0, 3, "uc", capacity=cap, tile=64, batch=8, device_assoc=device_assoc, **params)
+    e = loaded(N0, 3, "uc", capacity=cap, tile=64, batch=8, device_assoc=device_assoc, **params)
     lm_index = np.arange(1, cap + 1, dtype=np.float64)
     lm_loc = np.random.default_rng(5).uniform(-20, 20, (cap, 2))
     for t in range(3):
@@ -401,12 +402,12 @@ def _uc_run(device_assoc, params):
 
 def test_model_observations_between_scans_signature_only():
     runs = {m: _uc_run(m, dict(w_pos=0.0)) for m in (1, 3)}
-    T.assert_same(runs[3], runs[1])
+    assert_same(runs[3], runs[1])
 
 
 def test_model_observations_between_scans_position_weighted():
-    runs = {m: _uc_run(m, T.POS) for m in (1, 4)}
-    T.assert_same(runs[4], runs[1])
+    runs = {m: _uc_run(m, PARAMS) for m in (1, 4)}
+    assert_same(runs[4], runs[1])
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -445,10 +446,10 @@ def test_a_run_with_model_observations_replays_from_its_log(tmp_path):
     log = TrajectoryLog.load(path)
     assert str(np.load(path)["format"]) == FORMAT_MODEL and [(e[0], e[1], e[2].tolist()) for e in log.edits] == \
         [(8, "observe_model", []), (13, "observe_model", [3]), (19, "observe_model", [1, 2]), (19, "observe_model", [3]), (19, "observe_model", [1])]
-    fresh = T.engine(**kw)
+    fresh = engine(**kw)
     log.replay(fresh)
     np.testing.assert_array_equal(fresh.get_x(), full.slam.x)
     np.testing.assert_array_equal(fresh.get_s(), full.slam.s)
     np.testing.assert_array_equal(fresh.get_P(), full.slam.P)
     assert full.slam.linear_rejections() == (0, 0)
-    assert T.rel_err(full.slam.x, plain.slam.x) > 1e-6        # the observations did move the map
+    assert rel_err(full.slam.x, plain.slam.x) > 1e-6        # the observations did move the map

@@ -2,12 +2,8 @@
 linked against a stand-in that lacks the symbol, and the MATLAB methods that forward to the command."""
 import os
 import re
-import subprocess
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-MOCK = os.path.join(ROOT, "tests", "support", "mex_mock")
-INCLUDES = ["-I", os.path.join(ROOT, "include"), "-I", os.path.join(ROOT, "tests", "support", "mex_api_subset"), "-I", MOCK]
-GCC = ["gcc", "-std=c99", "-Wall", "-Wextra", "-Werror", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"]
+from mex_harness import PRELUDE_SHOWN, ROOT, driver, driver_without, transcript_of
 
 _STUB = r'''
 #include <stdio.h>
@@ -24,31 +20,7 @@ int32_t ekf_observe_model(ekf_handle *h, const ekf_model_obs *o, ekf_linear_resu
 }
 '''
 
-_DRIVER = r'''
-#include <setjmp.h>
-#include <stdio.h>
-#include "ekfslam.h"
-#include "mex_mock.h"
-void arm_failure(void);
-static mxArray *out[4];
-static int call(const char *what, int nlhs, int nrhs, const mxArray **prhs) {
-    out[0] = 0;
-    if (setjmp(mock_err_jmp)) { printf("MEX %s nrhs=%d -> ERROR %s | %s\n", what, nrhs, mock_err_id, mock_err_msg); return 1; }
-    mexFunction(nlhs, out, nrhs, prhs);
-    printf("MEX %s nrhs=%d -> ok", what, nrhs);
-    if (out[0] && mxGetClassID(out[0]) != mxUINT64_CLASS) {
-        printf(" out0=%zux%zu[", mxGetM(out[0]), mxGetN(out[0]));
-        for (size_t i = 0; i < mxGetM(out[0]) * mxGetN(out[0]); ++i) printf(i ? ",%g" : "%g", mxGetPr(out[0])[i]);
-        printf("]");
-    }
-    printf("\n");
-    return 0;
-}
-#define D1(v) mock_double(1, 1, (const double[]){ v })
-int main(void) {
-    const mxArray *cr[3] = { mock_string("create"), D1(1), D1(64) };
-    if (call("create", 1, 3, cr)) return 1;
-    const mxArray *h = out[0];
+_DRIVER = driver(r'''
     const mxArray *z = mock_double(2, 1, (const double[]){ 7, 8 }), *R = mock_double(2, 2, (const double[]){ 4, 1, 1, 9 });
     const mxArray *lm1 = D1(5), *lm2 = mock_double(2, 1, (const double[]){ 5, 3 }), *none = mock_double(0, 0, 0);
     const mxArray *anchor = mock_double(2, 1, (const double[]){ 10, -4 });
@@ -84,57 +56,16 @@ int main(void) {
     if (!call("observe_model noh", 1, 9, bad)) return 1;
     arm_failure();
     if (!call("observe_model", 1, 9, rb)) return 1;
-    const mxArray *de[2] = { mock_string("destroy"), h };
-    if (call("destroy", 0, 2, de)) return 1;
-    printf("LOCKS %d\nMISUSE %d\n", mock_lock_count, mock_misuse);
-    return 0;
-}
-'''
+''', PRELUDE_SHOWN)
 
-_DRIVER_WITHOUT = r'''
-#include <setjmp.h>
-#include <stdio.h>
-#include "ekfslam.h"
-#include "mex_mock.h"
-static mxArray *out[4];
-static int call(const char *what, int nrhs, const mxArray **prhs) {
-    out[0] = 0;
-    if (setjmp(mock_err_jmp)) { printf("MEX %s nrhs=%d -> ERROR %s | %s\n", what, nrhs, mock_err_id, mock_err_msg); return 1; }
-    mexFunction(1, out, nrhs, prhs);
-    printf("MEX %s nrhs=%d -> ok\n", what, nrhs);
-    return 0;
-}
-#define D1(v) mock_double(1, 1, (const double[]){ v })
-int main(void) {
-    const mxArray *cr[3] = { mock_string("create"), D1(1), D1(64) };
-    if (call("create", 3, cr)) return 1;
-    const mxArray *h = out[0];
+_DRIVER_WITHOUT = driver_without(r'''
     const mxArray *ob[9] = { mock_string("observe_model"), h, D1(2), mock_double(2, 1, 0), mock_double(2, 2, 0), D1(1), mock_double(0, 0, 0), D1(1), D1(0) };
-    if (!call("observe_model", 9, ob)) return 1;
-    const mxArray *pr[3] = { mock_string("predict"), h, mock_double(2, 1, (const double[]){ 0.1, 3 }) };
-    if (call("predict", 3, pr)) return 1;
-    const mxArray *de[2] = { mock_string("destroy"), h };
-    if (call("destroy", 2, de)) return 1;
-    printf("LOCKS %d\nMISUSE %d\n", mock_lock_count, mock_misuse);
-    return 0;
-}
-'''
-
-
-def _build_and_run(files, exe):
-    r = subprocess.run(GCC + INCLUDES + [os.path.join(ROOT, "matlab", "ekfslam_mex.c"), os.path.join(MOCK, "mex_mock.c"),
-                                         os.path.join(MOCK, "abi_stub.c")] + files + ["-o", exe, "-lm"], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-4000:]
-    r = subprocess.run([exe], capture_output=True, text=True, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=0"))
-    assert r.returncode == 0, "the gateway misbehaved under the mock:\n" + r.stdout[-2000:] + r.stderr[-4000:]
-    return r.stdout.splitlines()
+    if (!call("observe_model", 1, 9, ob)) return 1;
+''')
 
 
 def test_mex_gateway_marshals_a_model_observation_once(tmp_path):
-    stub, drv = tmp_path / "model_stub.c", tmp_path / "model_drv.c"
-    stub.write_text(_STUB)
-    drv.write_text(_DRIVER)
-    t = _build_and_run([str(stub), str(drv)], str(tmp_path / "drv"))
+    t = transcript_of(tmp_path, _STUB, _DRIVER)
     # MATLAB's lm = 5 arrives 0-based once, R column-major as MATLAB holds it; no result asked for: an empty output
     i = t.index("ABI ekf_observe_model model=1 reserved=0 z=7,8 R=4,1,1,9 lm=4,-1 anchor=0,0 gate=9.5 wait=0")
     assert t[i + 1] == "MEX observe_model nrhs=9 -> ok out0=0x0[]"
@@ -153,9 +84,7 @@ def test_mex_gateway_marshals_a_model_observation_once(tmp_path):
 
 
 def test_the_gateway_still_links_against_a_library_without_the_symbol(tmp_path):
-    drv = tmp_path / "without_drv.c"
-    drv.write_text(_DRIVER_WITHOUT)
-    t = _build_and_run([str(drv)], str(tmp_path / "drv"))
+    t = transcript_of(tmp_path, _DRIVER_WITHOUT)
     assert any(ln.startswith("MEX observe_model ") and "ERROR ekfslam:usage" in ln and "this libekfslam has no ekf_observe_model" in ln for ln in t)
     assert "MEX predict nrhs=3 -> ok" in t and t[-2:] == ["LOCKS 0", "MISUSE 0"]
 

@@ -7,20 +7,15 @@ a stand-in that lacks the symbol."""
 import ctypes
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
+from helpers import RPOS, RecorderBase
 from merge_cases import constrain_dense
+from mex_harness import PRELUDE_SHOWN, ROOT, driver, driver_without, transcript_of
 from nearest_cases import fuse_dense, nearest_dense, nearest_lowrank, pair_matrix, plant_duplicates
 from removal_cases import lowrank_data
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-MOCK = os.path.join(ROOT, "tests", "support", "mex_mock")
-INCLUDES = ["-I", os.path.join(ROOT, "include"), "-I", os.path.join(ROOT, "tests", "support", "mex_api_subset"), "-I", MOCK]
-GCC = ["gcc", "-std=c99", "-Wall", "-Wextra", "-Werror", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"]
-RPOS = np.array([[0.02, 0.005], [0.005, 0.03]])
 
 
 def test_library_exports_and_binds_the_entry_point():
@@ -129,8 +124,12 @@ def test_the_numpy_fusion_loop_merges_the_planted_pairs_in_order_of_distance():
     assert fuse_dense(x, s, P, gate, RPOS, max_merges=1)[3] == merges[:1]
 
 
-class _Recorder:
+class _Recorder(RecorderBase):
     """Stand-in for the loaded library (no GPU here): five landmarks; landmark 0 has no partner, landmark 3 neither."""
+
+    status_string = b"ok"
+    last_error = b""
+
     D2 = [np.inf, 0.25, 7.0, np.inf, 0.125]
     PARTNER = [-1, 0, 0, -1, 2]
 
@@ -138,19 +137,6 @@ class _Recorder:
         self.calls = []
         self.N = 5
         self.D2, self.PARTNER = list(self.D2), list(self.PARTNER)
-
-    def ekf_config_default(self, pcfg, mode):
-        from ekf_slam_amd import _lib as L
-        cfg = ctypes.cast(pcfg, ctypes.POINTER(L.EkfConfig)).contents
-        cfg.mode, cfg.batch = mode, 1
-        return 0
-
-    def ekf_create(self, pcfg, ph):
-        ctypes.cast(ph, ctypes.POINTER(ctypes.c_void_p)).contents.value = 0x1000
-        return 0
-
-    def ekf_destroy(self, h):
-        return 0
 
     def ekf_num_landmarks(self, h, pn):
         pn._obj.value = self.N
@@ -172,12 +158,6 @@ class _Recorder:
         self.D2 = [np.inf if p < 0 else v for v, p in zip(self.D2, self.PARTNER)]
         self.N -= 1
         return 0
-
-    def ekf_status_string(self, rc):
-        return b"ok"
-
-    def ekf_last_error(self, h):
-        return b""
 
 
 def test_engine_and_slam_layers_convert_indices_once(monkeypatch):
@@ -237,31 +217,7 @@ int32_t ekf_nearest_landmarks(ekf_handle *h, const double R[4], double *d2, int6
 }
 '''
 
-_DRIVER = r'''
-#include <setjmp.h>
-#include <stdio.h>
-#include "ekfslam.h"
-#include "mex_mock.h"
-void arm_failure(void);
-static mxArray *out[4];
-static int call(const char *what, int nlhs, int nrhs, const mxArray **prhs) {
-    out[0] = 0; out[1] = 0;
-    if (setjmp(mock_err_jmp)) { printf("MEX %s nrhs=%d -> ERROR %s | %s\n", what, nrhs, mock_err_id, mock_err_msg); return 1; }
-    mexFunction(nlhs, out, nrhs, prhs);
-    printf("MEX %s nrhs=%d -> ok", what, nrhs);
-    for (int k = 0; k < 2; ++k)
-        if (out[k] && mxGetClassID(out[k]) != mxUINT64_CLASS) {
-            printf(" out%d=%zux%zu[", k, mxGetM(out[k]), mxGetN(out[k]));
-            for (size_t i = 0; i < mxGetM(out[k]) * mxGetN(out[k]); ++i) printf(i ? ",%g" : "%g", mxGetPr(out[k])[i]);
-            printf("]");
-        }
-    printf("\n");
-    return 0;
-}
-int main(void) {
-    const mxArray *cr[3] = { mock_string("create"), mock_double(1, 1, (const double[]){ 1 }), mock_double(1, 1, (const double[]){ 64 }) };
-    if (call("create", 1, 3, cr)) return 1;
-    const mxArray *h = out[0];
+_DRIVER = driver(r'''
     const mxArray *R = mock_double(2, 2, (const double[]){ 4, 1, 1, 9 });
     const mxArray *near[3] = { mock_string("nearest_landmarks"), h, R };
     if (call("nearest_landmarks", 2, 3, near)) return 1;                       /* the empty map */
@@ -273,56 +229,16 @@ int main(void) {
     if (!call("nearest_landmarks", 2, 2, near) || !call("nearest_landmarks", 2, 3, badr) || !call("nearest_landmarks", 2, 3, noh)) return 1;
     arm_failure();
     if (!call("nearest_landmarks", 2, 3, near)) return 1;
-    const mxArray *de[2] = { mock_string("destroy"), h };
-    if (call("destroy", 0, 2, de)) return 1;
-    printf("LOCKS %d\nMISUSE %d\n", mock_lock_count, mock_misuse);
-    return 0;
-}
-'''
+''', PRELUDE_SHOWN)
 
-_DRIVER_WITHOUT = r'''
-#include <setjmp.h>
-#include <stdio.h>
-#include "ekfslam.h"
-#include "mex_mock.h"
-static mxArray *out[4];
-static int call(const char *what, int nrhs, const mxArray **prhs) {
-    out[0] = 0;
-    if (setjmp(mock_err_jmp)) { printf("MEX %s nrhs=%d -> ERROR %s | %s\n", what, nrhs, mock_err_id, mock_err_msg); return 1; }
-    mexFunction(1, out, nrhs, prhs);
-    printf("MEX %s nrhs=%d -> ok\n", what, nrhs);
-    return 0;
-}
-int main(void) {
-    const mxArray *cr[3] = { mock_string("create"), mock_double(1, 1, (const double[]){ 1 }), mock_double(1, 1, (const double[]){ 64 }) };
-    if (call("create", 3, cr)) return 1;
-    const mxArray *h = out[0];
+_DRIVER_WITHOUT = driver_without(r'''
     const mxArray *near[3] = { mock_string("nearest_landmarks"), h, mock_double(2, 2, (const double[]){ 0, 0, 0, 0 }) };
-    if (!call("nearest_landmarks", 3, near)) return 1;
-    const mxArray *pr[3] = { mock_string("predict"), h, mock_double(2, 1, (const double[]){ 0.1, 3 }) };
-    if (call("predict", 3, pr)) return 1;
-    const mxArray *de[2] = { mock_string("destroy"), h };
-    if (call("destroy", 2, de)) return 1;
-    printf("LOCKS %d\nMISUSE %d\n", mock_lock_count, mock_misuse);
-    return 0;
-}
-'''
-
-
-def _build_and_run(files, exe):
-    r = subprocess.run(GCC + INCLUDES + [os.path.join(ROOT, "matlab", "ekfslam_mex.c"), os.path.join(MOCK, "mex_mock.c"),
-                                         os.path.join(MOCK, "abi_stub.c")] + files + ["-o", exe, "-lm"], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-4000:]
-    r = subprocess.run([exe], capture_output=True, text=True, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=0"))
-    assert r.returncode == 0, "the gateway misbehaved under the mock:\n" + r.stdout[-2000:] + r.stderr[-4000:]
-    return r.stdout.splitlines()
+    if (!call("nearest_landmarks", 1, 3, near)) return 1;
+''')
 
 
 def test_mex_gateway_hands_out_one_based_partners(tmp_path):
-    stub, drv = tmp_path / "nearest_stub.c", tmp_path / "nearest_drv.c"
-    stub.write_text(_STUB)
-    drv.write_text(_DRIVER)
-    t = _build_and_run([str(stub), str(drv)], str(tmp_path / "drv"))
+    t = transcript_of(tmp_path, _STUB, _DRIVER)
     i = t.index("ABI ekf_nearest_landmarks N=0 R=4,1,1,9")
     assert t[i + 1] == "MEX nearest_landmarks nrhs=3 -> ok out0=0x1[] out1=0x1[]"
     i = t.index("ABI ekf_nearest_landmarks N=3 R=4,1,1,9")
@@ -337,9 +253,7 @@ def test_mex_gateway_hands_out_one_based_partners(tmp_path):
 
 
 def test_the_gateway_still_links_against_a_library_without_the_symbol(tmp_path):
-    drv = tmp_path / "without_drv.c"
-    drv.write_text(_DRIVER_WITHOUT)
-    t = _build_and_run([str(drv)], str(tmp_path / "drv"))
+    t = transcript_of(tmp_path, _DRIVER_WITHOUT)
     assert any(ln.startswith("MEX nearest_landmarks ") and "ERROR ekfslam:usage" in ln and "this libekfslam has no ekf_nearest_landmarks" in ln
                for ln in t)
     assert "MEX predict nrhs=3 -> ok" in t and t[-2:] == ["LOCKS 0", "MISUSE 0"]

@@ -10,30 +10,14 @@ import ctypes
 import numpy as np
 import pytest
 
+from decided_plans import PARAMS
+from helpers import R2, REL, RPOS, STORES_ALL, U2, check_state, engine, loaded, status_of
 from nearest_cases import PLANTS, fuse_dense, nearest_dense, nearest_lowrank, plant_duplicates
 from removal_cases import lowrank_data, observe
 
 pytestmark = pytest.mark.gpu
-REL = 1e-6                      # BASELINE.json's bar against the oracle
 BAND = 1.0 + 1e-6               # a row whose runner-up lies inside this factor of its minimum has no unambiguous partner
-TOL_X32, TOL_KEPT32, TOL_ROW32 = 1e-9, 2e-9, 2e-7        # DESIGN.md section 5 (tests/test_merge_landmarks_gpu.py::check_state)
 N0 = 300
-U2 = np.array([0.1, 1.0])
-R2 = np.diag([0.1, 0.2])
-RPOS = np.array([[0.02, 0.005], [0.005, 0.03]])
-STORES = [(16, "f64"), (64, "f64"), (128, "f64"), (256, "f32"), (256, "f32_mixed"), (256, "f32_split")]
-
-
-def engine(mode="known", **kw):
-    from ekf_slam_amd.engine import Engine
-    return Engine(mode=mode, **kw)
-
-
-def loaded(N, seed, mode="known", x=None, **kw):
-    x0, s, d, U = lowrank_data(N, seed)
-    e = engine(mode, **kw)
-    e.load_lowrank_state(x0 if x is None else x, s, d, U)
-    return e
 
 
 def planted(seed=5, mode="known", history=(5, 128, 290), **kw):
@@ -64,15 +48,6 @@ def check_against_numpy(e, R, label):
     return d2, partner
 
 
-def status_of(fn):
-    from ekf_slam_amd._lib import EkfError
-    try:
-        fn()
-    except EkfError as ex:
-        return ex.status, str(ex)
-    return 0, ""
-
-
 # ------------------------------------------------------------------------------------------------------------------
 # 1. hand-checked states
 # ------------------------------------------------------------------------------------------------------------------
@@ -90,7 +65,7 @@ def mirrored_state():
     return x, np.array([1.0, 2.0, 3.0]), P
 
 
-@pytest.mark.parametrize("tile,storage", STORES)
+@pytest.mark.parametrize("tile,storage", STORES_ALL)
 def test_hand_checked_answers(tile, storage):
     e = engine(capacity=8, tile=tile, storage=storage)
     e.set_state(*[known_answer_state()[k] for k in (0, 2, 1)])
@@ -115,7 +90,7 @@ def test_hand_checked_answers(tile, storage):
 # ------------------------------------------------------------------------------------------------------------------
 # 2. against NumPy, 3. the definition bit for bit, 4. changes nothing
 # ------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("tile,storage", STORES)
+@pytest.mark.parametrize("tile,storage", STORES_ALL)
 @pytest.mark.parametrize("R", [RPOS, None], ids=["Rpos", "R0"])
 def test_against_numpy_with_planted_duplicates(tile, storage, R):
     e = planted(capacity=N0 + 8, tile=tile, storage=storage, batch=8)
@@ -124,7 +99,7 @@ def test_against_numpy_with_planted_duplicates(tile, storage, R):
         assert partner[drop] == keep and d2[drop] < 0.1
 
 
-@pytest.mark.parametrize("tile,storage", STORES)
+@pytest.mark.parametrize("tile,storage", STORES_ALL)
 @pytest.mark.parametrize("R", [RPOS, None], ids=["Rpos", "R0"])
 def test_every_value_is_the_landmark_distance_of_its_pair_bit_for_bit(tile, storage, R):
     e = planted(capacity=N0 + 8, tile=tile, storage=storage, batch=8)
@@ -138,7 +113,7 @@ def test_every_value_is_the_landmark_distance_of_its_pair_bit_for_bit(tile, stor
         assert d2[i] == row.min() and partner[i] == int(np.argmin(row))
 
 
-@pytest.mark.parametrize("tile,storage", STORES)
+@pytest.mark.parametrize("tile,storage", STORES_ALL)
 def test_the_search_changes_nothing(tile, storage):
     e = planted(capacity=N0 + 8, tile=tile, storage=storage, batch=8)
     x0, s0, P0, b0, dg0 = e.get_x(), e.get_s(), e.get_P(), e.get_P_diag_blocks(), e.digest()
@@ -172,9 +147,6 @@ def test_pending_pairs_and_a_lazy_predict_are_carried_out_first():
     np.testing.assert_array_equal(runs[0][1], runs[1][1])
 
 
-POS = dict(w_pos=1.0, Rc=(0.01, 0.01), s_thresh=0.5)         # the position-weighted likelihood of tests/test_decided_assoc_gpu.py
-
-
 def test_right_after_queued_scans_on_a_device_decided_asynchronous_handle():
     cap = N0 + 40
     x = plant_duplicates(lowrank_data(N0, 3)[0])
@@ -182,7 +154,7 @@ def test_right_after_queued_scans_on_a_device_decided_asynchronous_handle():
     lm_loc = np.random.default_rng(5).uniform(-20, 20, (cap, 2))
     runs = []
     for kw in (dict(device_assoc=4, async_flush=True), dict(device_assoc=1)):
-        e = loaded(N0, 3, "uc", x=x, capacity=cap, tile=64, batch=8, **kw, **POS)
+        e = loaded(N0, 3, "uc", x=x, capacity=cap, tile=64, batch=8, **kw, **PARAMS)
         for t in range(2):                                   # two scans that correct and append; with device_assoc = 4 nothing is settled
             e.predict(U2)
             x0 = e.get_x()                                   # (the pose the scan is taken from: the position cost is strict)
@@ -200,7 +172,7 @@ def test_right_after_queued_scans_on_a_device_decided_asynchronous_handle():
 # ------------------------------------------------------------------------------------------------------------------
 # 6. a map that changed shape
 # ------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("tile,storage", STORES)
+@pytest.mark.parametrize("tile,storage", STORES_ALL)
 def test_after_appends_a_removal_and_a_merge(tile, storage):
     per_row = tile // 2
     cap = N0 + per_row + 16
@@ -227,7 +199,7 @@ def test_after_appends_a_removal_and_a_merge(tile, storage):
 # ------------------------------------------------------------------------------------------------------------------
 # 7. an irregular pair never wins
 # ------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("tile,storage", STORES)
+@pytest.mark.parametrize("tile,storage", STORES_ALL)
 def test_two_identical_perfectly_correlated_landmarks(tile, storage):
     """S = 0 exactly (every value is representable in float): the pair is skipped."""
     x = np.array([0.5, -0.25, 30.0, 2.0, 1.0, 2.0, 1.0])
@@ -323,29 +295,6 @@ def test_a_lone_shard_works_and_refuses_between_begin_and_finish():
 # ------------------------------------------------------------------------------------------------------------------
 # 9. fuse_duplicates on a handle
 # ------------------------------------------------------------------------------------------------------------------
-def _check_state(e, ex, es, eP, storage, label):
-    """tests/test_merge_landmarks_gpu.py::check_state: x, s, P and the diagonal blocks against the expectation."""
-    x, s, P, blocks = e.get_x(), e.get_s(), e.get_P(), e.get_P_diag_blocks()
-    assert e.N == es.size
-    np.testing.assert_array_equal(s, es)
-    np.testing.assert_array_equal(P, P.T)
-    n = ex.size
-    starts = np.concatenate([[0], np.arange(3, n, 2)])
-    kept = np.zeros((n, n), dtype=bool)
-    kept[:3, :] = kept[:, :3] = True
-    for a in range(3, n, 2):
-        kept[a:a + 2, a:a + 2] = True
-    rel = lambda u, v: float(np.abs(u - v).max() / max(np.abs(v).max(), 1e-300))
-    err_x, err_P, err_b = rel(x, ex), rel(P, eP), rel(blocks, np.array([eP[a:a + 2, a:a + 2] for a in starts]))
-    err_kept = float(np.abs(P - eP)[kept].max() / np.abs(eP).max())
-    err_row = float((np.abs(P - eP).max(axis=1) / np.abs(eP).max(axis=1)).max())
-    print("%s [%s]: rel err x %.2e P %.2e blocks %.2e F64-kept %.2e worst row %.2e" % (label, storage, err_x, err_P, err_b, err_kept, err_row))
-    if storage == "f64":
-        assert err_x < REL and err_P < REL and err_b < REL
-    else:
-        assert err_x < TOL_X32 and err_kept < TOL_KEPT32 and err_b < TOL_KEPT32 and err_row <= TOL_ROW32
-
-
 @pytest.mark.parametrize("tile,storage", [(16, "f64"), (128, "f64"), (256, "f32"), (256, "f32_mixed")])
 def test_fuse_duplicates_makes_the_merges_of_the_numpy_mirror(tile, storage):
     from ekf_slam_amd.slam import EKF_SLAM_UC
@@ -371,7 +320,7 @@ def test_fuse_duplicates_makes_the_merges_of_the_numpy_mirror(tile, storage):
     print("fuse [%d %s]: %d merges, gate %.4g in the gap (%.4g, %.4g), rel err of the d2 %.2e" % (tile, storage, len(merges), gate, lo, hi, err))
     assert err < (REL if storage == "f64" else 1e-5)
     assert f._e.N == N0 - len(PLANTS) and f.duplicate_candidates(gate, RPOS) == []
-    _check_state(f._e, mx, ms, mP, storage, "after %d fusions" % len(merges))
+    check_state(f._e, mx, mP, storage, "after %d fusions" % len(merges), es=ms)
     # max_merges stops the loop
     g = EKF_SLAM_UC(capacity=N0 + 8, tile=tile, storage=storage, batch=8)
     g._e.set_state(x, P, s)

@@ -12,10 +12,7 @@ from oracle.ekf_structured import StructuredEKF
 from oracle.matlab_compat import atan2d, cosd, inv2, sind, wrapTo360
 
 import kat_cases as K
-
-
-def rel_err(a, b):
-    return float(np.abs(np.asarray(a) - np.asarray(b)).max() / max(np.abs(np.asarray(b)).max(), 1e-300))
+from helpers import rel_err
 
 
 def test_kat1_predict_from_ctor_state_dense():

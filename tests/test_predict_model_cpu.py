@@ -4,19 +4,16 @@ switch; the known answer of a heading variance turned into a lateral one; k_pred
 single launches bit for bit, every case against the dense restatement); the eighth kind of the trajectory log; the argument handling of the
 Python layers over a stand-in for the library.  (The MEX gateway's command: tests/test_predict_model_mex_cpu.py.)"""
 import ctypes
-import os
 import subprocess
 
 import numpy as np
 import pytest
 
 import predict_model_cases as PM
+from helpers import REL, RecorderBase, host_build, line_program, same_npz
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REL = 1e-6
 M2 = np.array([[0.04, 0.01], [0.01, 0.09]])
 M3 = np.array([[0.04, 0.01, 0.0], [0.01, 0.09, 0.02], [0.0, 0.02, 0.25]])
-GXX = ["g++", "-O2", "-mfma", "-ffp-contract=off", "-std=c++17", "-I", os.path.join(ROOT, "ekf_slam_amd", "csrc")]
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -25,15 +22,7 @@ GXX = ["g++", "-O2", "-mfma", "-ffp-contract=off", "-std=c++17", "-I", os.path.j
 @pytest.fixture(scope="module")
 def host(tmp_path_factory):
     """The stand-alone host build of ekfm::motion_eval / motion_chord / motion_noise_entry: host(lines) -> one row of floats per line."""
-    exe = str(tmp_path_factory.mktemp("motion_eval") / "motion_eval_host")
-    subprocess.run(GXX + [os.path.join(ROOT, "tests", "support", "motion_eval_host.cpp"), "-o", exe], check=True)
-
-    def run(lines):
-        out = subprocess.run([exe], input="\n".join(lines) + "\n", check=True, capture_output=True, text=True).stdout
-        rows = [[float(v) for v in ln.split()] for ln in out.strip().split("\n")]
-        assert len(rows) == len(lines)
-        return rows
-    return run
+    return line_program(tmp_path_factory, "motion_eval_host")
 
 
 def _eval(host, cases):
@@ -208,8 +197,7 @@ def test_kernel_source_on_the_host_chains_bit_for_bit_and_matches_the_dense_rest
         full = np.zeros((3, 3)); full[:u.size, :u.size] = M
         raw[b, 4:] = full.reshape(-1)
     raw.tofile(tmp_path / "chain.bin")
-    exe = str(tmp_path / "predict_model_host_emulation")
-    subprocess.run(GXX + [os.path.join(ROOT, "tests", "support", "predict_model_host_emulation.cpp"), "-o", exe], check=True)
+    exe = host_build("predict_model_host_emulation", str(tmp_path / "predict_model_host_emulation"))
     r = subprocess.run([exe, str(tmp_path)], capture_output=True, text=True)
     lines = r.stdout.strip().split("\n")
     assert r.returncode == 0, r.stdout[-3000:]
@@ -275,12 +263,6 @@ def _steps(log, n):
         log.record([0.1, 1.0 + k], np.array([[1.0, 2.0, 3.0]]) if k % 2 else None, [1.0, 2.0], [[0.0, 1.0], [2.0, 3.0]])
 
 
-def _same_file(a, b):
-    ga, gb = np.load(a), np.load(b)
-    return ga.files == gb.files and all(ga[k].dtype == gb[k].dtype and ga[k].shape == gb[k].shape and ga[k].tobytes() == gb[k].tobytes()
-                                        for k in ga.files)
-
-
 def test_trajectory_format_seven_round_trip_and_the_older_formats(tmp_path):
     import append_model_cases as A
     from ekf_slam_amd import trajectory as TR
@@ -304,7 +286,7 @@ def test_trajectory_format_seven_round_trip_and_the_older_formats(tmp_path):
         back = TrajectoryLog.load(p)
         assert len(back) == len(log) and len(back.edits) == len(log.edits) and back.model_predicts == {}
         back.save(tmp_path / ("v%d_again.npz" % v))
-        assert _same_file(p, tmp_path / ("v%d_again.npz" % v))
+        assert same_npz(p, tmp_path / ("v%d_again.npz" % v))
     # version 7: chains of motion steps among the other edits
     chain = PM.chain(np.random.default_rng(3), 5)
     seven = TrajectoryLog(); _steps(seven, 2)
@@ -326,7 +308,7 @@ def test_trajectory_format_seven_round_trip_and_the_older_formats(tmp_path):
         assert got[0] == want[0]
         np.testing.assert_array_equal(got[1], want[1]); np.testing.assert_array_equal(got[2], want[2])
     back.save(tmp_path / "seven_again.npz")
-    assert _same_file(tmp_path / "seven.npz", tmp_path / "seven_again.npz")
+    assert same_npz(tmp_path / "seven.npz", tmp_path / "seven_again.npz")
     r = _Replayed()
     back.replay(r)
     assert r.calls == [("predict",), ("predict",), ("measure",), ("remove", [6]),
@@ -350,22 +332,12 @@ def test_trajectory_format_seven_round_trip_and_the_older_formats(tmp_path):
 # ------------------------------------------------------------------------------------------------------------------
 # the Python layers over a stand-in for the library
 # ------------------------------------------------------------------------------------------------------------------
-class _Recorder:
+class _Recorder(RecorderBase):
+    status_string = b"invalid argument"
+    last_error = b"predict_model: injected"
+
     def __init__(self):
         self.calls, self.fail = [], 0
-
-    def ekf_config_default(self, pcfg, mode):
-        from ekf_slam_amd import _lib as L
-        cfg = ctypes.cast(pcfg, ctypes.POINTER(L.EkfConfig)).contents
-        cfg.mode, cfg.batch = mode, 1
-        return 0
-
-    def ekf_create(self, pcfg, ph):
-        ctypes.cast(ph, ctypes.POINTER(ctypes.c_void_p)).contents.value = 0x1000
-        return 0
-
-    def ekf_destroy(self, h):
-        return 0
 
     def ekf_predict_model(self, h, arr, m):
         self.calls.append(("predict_model", m, [(o.model, o.reserved, list(o.u), list(o.M)) for o in list(arr)[:m]]))
@@ -375,12 +347,6 @@ class _Recorder:
         self.calls.append(("evaluate", model, [xr[i] for i in range(3)], [u[i] for i in range(3)]))
         xn[2], F[6], V[1] = 7.0, 8.0, 9.0
         return self.fail
-
-    def ekf_status_string(self, rc):
-        return b"invalid argument"
-
-    def ekf_last_error(self, h):
-        return b"predict_model: injected"
 
 
 def test_engine_and_slam_layers_marshal_a_chain_once(monkeypatch):

@@ -2,7 +2,7 @@
 include/ekfslam.h).
 
 The yardstick is the NumPy restatement of tests/predict_model_cases.py applied to THE STATE THE ENGINE REPORTED BEFORE THE CALL; stores,
-tolerances and helpers are those of tests/test_linear_obs_gpu.py.  Where two engines must agree because they ran the same arithmetic on
+tolerances and helpers are those of tests/helpers.py.  Where two engines must agree because they ran the same arithmetic on
 the same inputs -- a chain against single calls, batch b against batch 1, the asynchronous pass against the synchronous one, the device
 loops against the waited one, shards against one engine, a replayed log -- the comparison is assert_array_equal.
 
@@ -15,11 +15,11 @@ import pytest
 import append_model_cases as A
 import model_obs_cases as M
 import predict_model_cases as PM
-import test_linear_obs_gpu as T
+from helpers import R2, REL, RPOS, U2, assert_same, check_state, engine, getters, loaded, rel_err, state, status_of
+from linear_obs_cases import N0, STORES
 from removal_cases import lowrank_data, observe
 
 pytestmark = pytest.mark.gpu
-U2, R2, RPOS, REL, N0 = T.U2, T.R2, T.RPOS, T.REL, T.N0
 M2 = np.array([[0.04, 0.01], [0.01, 0.09]])
 M3 = np.array([[0.04, 0.01, 0.0], [0.01, 0.09, 0.02], [0.0, 0.02, 0.25]])
 
@@ -33,7 +33,7 @@ def history(engines, x, ks):
 def group_of(count, N, pending, **kw):
     """`count` engines with the same state and history: `pending` corrections, deferred where batch > pending."""
     x = lowrank_data(N, 5)[0]
-    es = [T.loaded(N, 5, **kw) for _ in range(count)]
+    es = [loaded(N, 5, **kw) for _ in range(count)]
     history(es, x, (5, N // 2, N - 3, 11, 40)[:pending])
     return es
 
@@ -55,7 +55,7 @@ def observe_through_model(e, model, k, noise):
 # ------------------------------------------------------------------------------------------------------------------
 # 1. against the dense restatement
 # ------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("tile,storage", T.STORES)
+@pytest.mark.parametrize("tile,storage", STORES)
 @pytest.mark.parametrize("pending", [0, 5])
 def test_chains_against_the_dense_restatement(tile, storage, pending):
     # e gets the calls; twin gets them too and is read BEFORE each (reading flushes it; e keeps its pairs pending); still gets none
@@ -66,16 +66,16 @@ def test_chains_against_the_dense_restatement(tile, storage, pending):
     assert {s[0] for s in mixed} == {1, 2, 3}
     for name, steps in (("turn and drive", [PM.step(PM.TURN_DRIVE, [1.5, 40.0], M2)]), ("an arc", [PM.step(PM.ARC, [2.0, -75.0], M2)]),
                         ("a pose increment", [PM.step(PM.POSE_DELTA, [0.4, -0.3, 200.0], M3)]), ("a mixed chain of nine", mixed)):
-        x0, s0, P0 = T.state(twin)
+        x0, s0, P0 = state(twin)
         ex, eP, eQ = PM.predict_model_dense(x0, P0, steps)
         e.predict_model(steps)
         assert e.pending() == pending
         twin.predict_model(steps)
-        T.check_state(e, ex, eP, storage, name)
+        check_state(e, ex, eP, storage, name)
         pending = 0                                           # (check_state read P: the pairs are applied now)
         # x, Prr and the strip rows are F64 in every store and carry this call's error alone
         x, P = e.get_x(), e.get_P()
-        errs = (T.rel_err(x, ex), float(np.abs(P[:3] - eP[:3]).max() / np.abs(eP).max()), T.rel_err(e.get_Q3(), eQ))
+        errs = (rel_err(x, ex), float(np.abs(P[:3] - eP[:3]).max() / np.abs(eP).max()), rel_err(e.get_Q3(), eQ))
         print("%s [%s]: rel err x %.2e robot rows of P %.2e Q %.2e" % ((name, storage) + errs))
         assert max(errs) < REL, name
         # the landmarks, the landmark block, its live diagonal blocks and s: the bits of an engine that got no predict
@@ -88,7 +88,7 @@ def test_chains_against_the_dense_restatement(tile, storage, pending):
 # ------------------------------------------------------------------------------------------------------------------
 # 2. a chain of m is m single calls, bit for bit
 # ------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("tile,storage", T.STORES)
+@pytest.mark.parametrize("tile,storage", STORES)
 @pytest.mark.parametrize("m", [1, 2, 9, 32])
 def test_a_chain_is_bit_for_bit_its_single_calls(tile, storage, m):
     e, twin = group_of(2, N0, 3, capacity=N0 + 8, tile=tile, storage=storage, batch=8)
@@ -124,7 +124,7 @@ def test_the_known_answer_on_a_fresh_handle(N):
         P0[3, 3] = P0[4, 4] = 0.5
         P0[2, 3] = P0[3, 2] = 0.3
     s0 = np.arange(1.0, N + 1.0)
-    e, twin = T.engine(capacity=4, tile=16), T.engine(capacity=4, tile=16)
+    e, twin = engine(capacity=4, tile=16), engine(capacity=4, tile=16)
     for q in (e, twin):
         q.set_state(x0, P0, s0)
     # P = diag(0, 0, 4 deg^2), theta = 0, drive 10 straight: P_yy = (10 pi / 180)^2 * 4 and P_xy = 0
@@ -138,7 +138,7 @@ def test_the_known_answer_on_a_fresh_handle(N):
     # the same f, another F: the twin's P_yy is k^2 times as large (its Q = (W C) W' has no y entry at theta = 0)
     assert Pt[1, 1] == 400.0 and abs(Pt[1, 1] / Pe[1, 1] - PM.K ** 2) < 1e-9 * PM.K ** 2
     ex, eP, _ = PM.predict_model_dense(x0, P0, [PM.step(PM.TURN_DRIVE, [10.0, 0.0], np.zeros((2, 2)))])
-    assert T.rel_err(Pe, eP) < REL and (not N or abs(Pe[1, 3] - 10.0 / PM.K * 0.3) < 1e-12)
+    assert rel_err(Pe, eP) < REL and (not N or abs(Pe[1, 3] - 10.0 / PM.K * 0.3) < 1e-12)
     # a step that turns, over 360: still the reference's pose, bit for bit
     e.predict_model([(PM.TURN_DRIVE, [3.7, 123.4], M2), (PM.TURN_DRIVE, [0.9, 300.0], M2)])
     twin.predict([3.7, 123.4]); twin.predict([0.9, 300.0])
@@ -149,11 +149,11 @@ def test_the_known_answer_on_a_fresh_handle(N):
     steps = [PM.step(PM.POSE_DELTA, [0.1, 0.2, 3.0], M3), PM.step(PM.ARC, [2.0, 40.0], M2)]
     e.predict_model(steps)
     ex, eP, eQ = PM.predict_model_dense(xb, Pb, steps)
-    assert T.rel_err(e.get_Q3(), eQ) < REL and T.rel_err(e.get_P(), eP) < REL and T.rel_err(e.get_x(), ex) < REL
+    assert rel_err(e.get_Q3(), eQ) < REL and rel_err(e.get_P(), eP) < REL and rel_err(e.get_x(), ex) < REL
     # the host's copy of the kernel's function agrees with the restatement
     xn, F, V = e.motion_evaluate(PM.ARC, xb[:3], [2.0, 40.0])
     wF, wV = PM.F_V_of(PM.ARC, xb[:3], [2.0, 40.0])
-    assert T.rel_err(F, wF) < 1e-12 and T.rel_err(V[:, :2], wV) < 1e-12 and not V[:, 2].any()
+    assert rel_err(F, wF) < 1e-12 and rel_err(V[:, :2], wV) < 1e-12 and not V[:, 2].any()
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -205,9 +205,9 @@ def _play(e, ops):
 @pytest.fixture(scope="module")
 def schedule_reference():
     ops = _schedule(29, 18, 70, 44)
-    one = T.loaded(18, 5, capacity=48, tile=16, batch=1)
+    one = loaded(18, 5, capacity=48, tile=16, batch=1)
     _play(one, ops)
-    return ops, one.N, T.getters(one)
+    return ops, one.N, getters(one)
 
 
 @pytest.mark.parametrize("batch,asy", [(1, True), (8, False), (8, True)])
@@ -216,11 +216,11 @@ def test_a_schedule_with_model_predicts_is_bit_for_bit_that_of_batch_one(schedul
     kinds = [op[0] for op in ops]
     assert kinds.count("predict_model") >= 10 and kinds.count("append_model") >= 5 and kinds.count("remove") >= 2 and kinds.count("observe") >= 6
     assert all(np.all(np.isfinite(g)) for g in want) and N > 24               # the map crossed the tile-row edge at 24 landmarks
-    e = T.loaded(18, 5, capacity=48, tile=16, batch=batch, async_flush=asy)
+    e = loaded(18, 5, capacity=48, tile=16, batch=batch, async_flush=asy)
     beside = _play(e, ops)
     assert batch == 1 or beside >= 4                          # chains with pairs pending (asynchronous: beside the pass that holds them)
     assert e.N == N
-    for got, ref in zip(T.getters(e), want):
+    for got, ref in zip(getters(e), want):
         np.testing.assert_array_equal(got, ref)
 
 
@@ -229,7 +229,7 @@ def test_a_schedule_with_model_predicts_is_bit_for_bit_that_of_batch_one(schedul
 # ------------------------------------------------------------------------------------------------------------------
 def test_between_the_scans_of_the_device_decided_loop():
     from decided_plans import make_plan
-    from test_decided_assoc_gpu import PARAMS
+    from decided_plans import PARAMS
     from ekf_slam_amd.engine import Engine
     plan = make_plan(7, 300, 24, 8)
     runs = {}
@@ -243,7 +243,7 @@ def test_between_the_scans_of_the_device_decided_loop():
                 e.predict_model([(PM.POSE_DELTA, [0.0, 0.0, 0.0], M3 * 1e-4), (PM.ARC, [1e-3, 0.01 * t], M2 * 1e-4)])
         runs[mode] = e
     assert runs[4].N > 40
-    T.assert_same(runs[4], runs[1])
+    assert_same(runs[4], runs[1])
 
 
 def test_between_the_scans_of_the_device_resident_loop():
@@ -261,7 +261,7 @@ def test_between_the_scans_of_the_device_resident_loop():
             if t in (3, 4, 9):
                 e.predict_model([(PM.POSE_DELTA, [0.0, 0.0, 0.0], M3 * 1e-4), (PM.ARC, [1e-3, 0.01 * t], M2 * 1e-4)])
     assert gpus[3]._e.cfg.device_assoc == 3 and gpus[1]._e.N > 6
-    T.assert_same(gpus[3]._e, gpus[1]._e)
+    assert_same(gpus[3]._e, gpus[1]._e)
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -305,21 +305,21 @@ def test_refused_between_begin_and_finish_of_a_sharded_correction():
     N = 60
     x = lowrank_data(N, 5)[0]
     kw = dict(capacity=N + 4, tile=16)
-    e, twin = T.loaded(N, 5, force_sharded=1, **kw), T.loaded(N, 5, **kw)
+    e, twin = loaded(N, 5, force_sharded=1, **kw), loaded(N, 5, **kw)
     harr = (ctypes.c_void_p * 1)(e.h)
     steps = PM.chain(np.random.default_rng(2), 4)
     z = observe(x, 7)
     e.predict(U2); twin.predict(U2)
     e.correct_begin(z, R2, 7)
-    st, msg = T.status_of(lambda: e.predict_model(steps))
+    st, msg = status_of(lambda: e.predict_model(steps))
     assert st == L.EKF_ERR_STATE and "predict_model" in msg and "begin and finish" in msg
     bad = [(PM.TURN_DRIVE, [1.0, float("nan")], M2)]
-    assert T.status_of(lambda: e.predict_model(bad))[0] == L.EKF_ERR_INVALID_ARG         # the arguments come first
+    assert status_of(lambda: e.predict_model(bad))[0] == L.EKF_ERR_INVALID_ARG         # the arguments come first
     assert e.lib.ekf_exchange_local(harr, 1) == 0
     e.correct_finish()
     twin.correct(z, R2, 7)
     e.predict_model(steps); twin.predict_model(steps)                                   # a lone shard with the sharded code path simply works
-    T.assert_same(e, twin)
+    assert_same(e, twin)
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -330,7 +330,7 @@ def test_refusals_leave_the_state_alone():
     N = 60
     x = lowrank_data(N, 5)[0]
     kw = dict(capacity=N + 4, tile=16, batch=8)
-    e, twin = T.loaded(N, 5, **kw), T.loaded(N, 5, **kw)
+    e, twin = loaded(N, 5, **kw), loaded(N, 5, **kw)
     history([e, twin], x, (4, 33, 9))                         # pairs pending and a recorded predict behind them
     e.predict(U2); twin.predict(U2)
     x_before, s_before, pend = e.get_x(), e.get_s(), e.pending()      # (reading x carries out e's predict; the twin's stays recorded)
@@ -385,7 +385,7 @@ def test_refusals_leave_the_state_alone():
     twin.predict_model(good)
     # nothing of all that changed anything: the recorded predict and the pending pairs were still there
     assert e.pending() == twin.pending() == pend
-    T.assert_same(e, twin)
+    assert_same(e, twin)
     assert not np.array_equal(e.get_x()[:3], x_before[:3]) and np.array_equal(e.get_s(), s_before)
 
 
@@ -417,7 +417,7 @@ def test_a_run_with_model_predicts_replays_from_its_log(tmp_path):
     assert str(np.load(path)["format"]) == FORMAT_PREDICT and [(e[0], e[1]) for e in log.edits] == \
         [(8, "predict_model"), (13, "predict_model"), (13, "predict_model"), (19, "predict_model")]
     assert [len(log.model_predicts[q]) for q in range(4)] == [1, 3, 1, 2]
-    fresh = T.engine(**kw)
+    fresh = engine(**kw)
     log.replay(fresh)
     assert fresh.N == 40 and not np.array_equal(plain.slam.x, full.slam.x)
     np.testing.assert_array_equal(fresh.get_x(), full.slam.x)
@@ -431,7 +431,7 @@ def test_a_run_with_model_predicts_replays_from_its_log(tmp_path):
 # ------------------------------------------------------------------------------------------------------------------
 def test_a_chain_of_thirty_two_at_ten_thousand_landmarks():
     N = 10000
-    e, twin = T.loaded(N, 5, capacity=N, tile=128), T.loaded(N, 5, capacity=N, tile=128)
+    e, twin = loaded(N, 5, capacity=N, tile=128), loaded(N, 5, capacity=N, tile=128)
     steps = PM.chain(np.random.default_rng(32), 32)
     e.predict_model(steps)
     for st in steps:

@@ -2,12 +2,8 @@
 against a stand-in that lacks the symbol, and the MATLAB methods that forward to the command."""
 import os
 import re
-import subprocess
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-MOCK = os.path.join(ROOT, "tests", "support", "mex_mock")
-INCLUDES = ["-I", os.path.join(ROOT, "include"), "-I", os.path.join(ROOT, "tests", "support", "mex_api_subset"), "-I", MOCK]
-GCC = ["gcc", "-std=c99", "-Wall", "-Wextra", "-Werror", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"]
+from mex_harness import OPEN_SILENT, ROOT, driver, driver_without, transcript_of
 
 _STUB = r'''
 #include <stdio.h>
@@ -27,25 +23,7 @@ int32_t ekf_predict_model(ekf_handle *h, const ekf_motion *o, int64_t m) {
 }
 '''
 
-_DRIVER = r'''
-#include <setjmp.h>
-#include <stdio.h>
-#include "ekfslam.h"
-#include "mex_mock.h"
-void arm_failure(void);
-static mxArray *out[4];
-static int call(const char *what, int nlhs, int nrhs, const mxArray **prhs) {
-    out[0] = 0;
-    if (setjmp(mock_err_jmp)) { printf("MEX %s nrhs=%d -> ERROR %s | %s\n", what, nrhs, mock_err_id, mock_err_msg); return 1; }
-    mexFunction(nlhs, out, nrhs, prhs);
-    printf("MEX %s nrhs=%d -> ok\n", what, nrhs);
-    return 0;
-}
-#define D1(v) mock_double(1, 1, (const double[]){ v })
-int main(void) {
-    const mxArray *cr[3] = { mock_string("create"), D1(1), D1(64) };
-    if (call("create", 1, 3, cr)) return 1;
-    const mxArray *h = out[0];
+_DRIVER = driver(r'''
     /* one step: turn 30, drive 5 */
     const mxArray *u1 = mock_double(1, 3, (const double[]){ 5, 30, 0 }), *M1 = mock_double(3, 3, (const double[]){ 4, 1, 0, 1, 9, 0, 0, 0, 0 });
     const mxArray *one[5] = { mock_string("predict_model"), h, D1(1), u1, M1 };
@@ -74,59 +52,16 @@ int main(void) {
     if (!call("predict_model noh", 0, 5, bad)) return 1;
     arm_failure();
     if (!call("predict_model", 0, 5, one)) return 1;
-    const mxArray *de[2] = { mock_string("destroy"), h };
-    if (call("destroy", 0, 2, de)) return 1;
-    printf("LOCKS %d\nMISUSE %d\n", mock_lock_count, mock_misuse);
-    return 0;
-}
-'''
+''')
 
-_DRIVER_WITHOUT = r'''
-#include <setjmp.h>
-#include <stdio.h>
-#include "ekfslam.h"
-#include "mex_mock.h"
-static mxArray *out[4];
-static int call(const char *what, int nrhs, const mxArray **prhs) {
-    out[0] = 0;
-    if (setjmp(mock_err_jmp)) { printf("MEX %s nrhs=%d -> ERROR %s | %s\n", what, nrhs, mock_err_id, mock_err_msg); return 1; }
-    mexFunction(0, out, nrhs, prhs);
-    printf("MEX %s nrhs=%d -> ok\n", what, nrhs);
-    return 0;
-}
-#define D1(v) mock_double(1, 1, (const double[]){ v })
-int main(void) {
-    const mxArray *cr[3] = { mock_string("create"), D1(1), D1(64) };
-    out[0] = 0;
-    if (setjmp(mock_err_jmp)) return 1;
-    mexFunction(1, out, 3, cr);
-    const mxArray *h = out[0];
+_DRIVER_WITHOUT = driver_without(r'''
     const mxArray *pm[5] = { mock_string("predict_model"), h, D1(1), mock_double(1, 3, (const double[]){ 5, 30, 0 }), mock_double(3, 3, (const double[]){ 4, 1, 0, 1, 9, 0, 0, 0, 0 }) };
-    if (!call("predict_model", 5, pm)) return 1;
-    const mxArray *pr[3] = { mock_string("predict"), h, mock_double(2, 1, (const double[]){ 0.1, 3 }) };
-    if (call("predict", 3, pr)) return 1;
-    const mxArray *de[2] = { mock_string("destroy"), h };
-    if (call("destroy", 2, de)) return 1;
-    printf("LOCKS %d\nMISUSE %d\n", mock_lock_count, mock_misuse);
-    return 0;
-}
-'''
-
-
-def _build_and_run(files, exe):
-    r = subprocess.run(GCC + INCLUDES + [os.path.join(ROOT, "matlab", "ekfslam_mex.c"), os.path.join(MOCK, "mex_mock.c"),
-                                         os.path.join(MOCK, "abi_stub.c")] + files + ["-o", exe, "-lm"], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-4000:]
-    r = subprocess.run([exe], capture_output=True, text=True, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=0"))
-    assert r.returncode == 0, "the gateway misbehaved under the mock:\n" + r.stdout[-2000:] + r.stderr[-4000:]
-    return r.stdout.splitlines()
+    if (!call("predict_model", 0, 5, pm)) return 1;
+''', OPEN_SILENT)
 
 
 def test_mex_gateway_marshals_a_chain_once(tmp_path):
-    stub, drv = tmp_path / "predict_stub.c", tmp_path / "predict_drv.c"
-    stub.write_text(_STUB)
-    drv.write_text(_DRIVER)
-    t = _build_and_run([str(stub), str(drv)], str(tmp_path / "drv"))
+    t = transcript_of(tmp_path, _STUB, _DRIVER)
     # u row by row out of the column-major m x 3; M column-major as MATLAB holds it, page by page
     i = t.index("ABI ekf_predict_model m=1")
     assert t[i + 1] == "ABI   step model=1 reserved=0 u=5,30,0 M=4,1,0,1,9,0,0,0,0"
@@ -146,9 +81,7 @@ def test_mex_gateway_marshals_a_chain_once(tmp_path):
 
 
 def test_the_gateway_still_links_against_a_library_without_the_symbol(tmp_path):
-    drv = tmp_path / "without_drv.c"
-    drv.write_text(_DRIVER_WITHOUT)
-    t = _build_and_run([str(drv)], str(tmp_path / "drv"))
+    t = transcript_of(tmp_path, _DRIVER_WITHOUT)
     assert any(ln.startswith("MEX predict_model ") and "ERROR ekfslam:usage" in ln and "this libekfslam has no ekf_predict_model" in ln for ln in t)
     assert "MEX predict nrhs=3 -> ok" in t and t[-2:] == ["LOCKS 0", "MISUSE 0"]
 

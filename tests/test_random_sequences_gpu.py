@@ -10,13 +10,9 @@ import os
 import numpy as np
 import pytest
 
+from helpers import REL, rel_err
+
 pytestmark = pytest.mark.gpu
-REL = 1e-6
-
-
-def rel_err(a, b):
-    a, b = np.asarray(a), np.asarray(b)
-    return float(np.abs(a - b).max() / max(np.abs(b).max(), 1e-300))
 
 
 class _Table:

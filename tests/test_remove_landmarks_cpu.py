@@ -6,16 +6,13 @@ the GPU tests compare against is right on a case written out by hand."""
 import ctypes
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
+from helpers import RecorderBase
+from mex_harness import ROOT, driver, transcript_of
 from removal_cases import expected_after, lowrank_data, lowrank_minus, removal_sets
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-MOCK = os.path.join(ROOT, "tests", "support", "mex_mock")
-INCLUDES = ["-I", os.path.join(ROOT, "include"), "-I", os.path.join(ROOT, "tests", "support", "mex_api_subset"), "-I", MOCK]
 
 
 def test_library_exports_and_binds_the_entry_point():
@@ -50,56 +47,23 @@ int32_t ekf_remove_landmarks(ekf_handle *h, const int64_t *idx, int64_t m) {
 }
 '''
 
-_DRIVER = r'''
-#include <setjmp.h>
-#include <stdio.h>
-#include "ekfslam.h"
-#include "mex_mock.h"
-void arm_failure(void);
-static mxArray *out[4];
-static int call(const char *what, int nrhs, const mxArray **prhs) {
-    out[0] = 0;
-    if (setjmp(mock_err_jmp)) { printf("MEX %s nrhs=%d -> ERROR %s | %s\n", what, nrhs, mock_err_id, mock_err_msg); return 1; }
-    mexFunction(1, out, nrhs, prhs);
-    printf("MEX %s nrhs=%d -> ok\n", what, nrhs);
-    return 0;
-}
-int main(void) {
-    const mxArray *cr[3] = { mock_string("create"), mock_double(1, 1, (const double[]){ 1 }), mock_double(1, 1, (const double[]){ 64 }) };
-    if (call("create", 3, cr)) return 1;
-    const mxArray *h = out[0];
+_DRIVER = driver(r'''
     const mxArray *row[3] = { mock_string("remove_landmarks"), h, mock_double(1, 3, (const double[]){ 3, 1, 7 }) };
     const mxArray *col[3] = { mock_string("remove_landmarks"), h, mock_double(2, 1, (const double[]){ 5, 4 }) };
     const mxArray *none[3] = { mock_string("remove_landmarks"), h, mock_double(0, 0, (const double[]){ 0 }) };
     const mxArray *few[2] = { mock_string("remove_landmarks"), h };
     const mxArray *nohandle[3] = { mock_string("remove_landmarks"), mock_double(1, 1, (const double[]){ 1 }), mock_double(1, 1, (const double[]){ 1 }) };
-    if (call("remove_landmarks", 3, row) || call("remove_landmarks", 3, col) || call("remove_landmarks", 3, none)) return 1;
-    if (!call("remove_landmarks", 2, few)) return 1;
-    if (!call("remove_landmarks", 3, nohandle)) return 1;
+    if (call("remove_landmarks", 1, 3, row) || call("remove_landmarks", 1, 3, col) || call("remove_landmarks", 1, 3, none)) return 1;
+    if (!call("remove_landmarks", 1, 2, few)) return 1;
+    if (!call("remove_landmarks", 1, 3, nohandle)) return 1;
     arm_failure();
-    if (!call("remove_landmarks", 3, row)) return 1;
-    const mxArray *de[2] = { mock_string("destroy"), h };
-    if (call("destroy", 2, de)) return 1;
-    printf("LOCKS %d\nMISUSE %d\n", mock_lock_count, mock_misuse);
-    return 0;
-}
-'''
+    if (!call("remove_landmarks", 1, 3, row)) return 1;
+''')
 
 
 @pytest.fixture(scope="module")
 def transcript(tmp_path_factory):
-    d = tmp_path_factory.mktemp("mexremove")
-    stub, drv, exe = d / "remove_stub.c", d / "remove_drv.c", str(d / "drv")
-    stub.write_text(_STUB)
-    drv.write_text(_DRIVER)
-    r = subprocess.run(["gcc", "-std=c99", "-Wall", "-Wextra", "-Werror", "-g", "-fsanitize=address,undefined",
-                        "-fno-sanitize-recover=undefined"] + INCLUDES +
-                       [os.path.join(ROOT, "matlab", "ekfslam_mex.c"), os.path.join(MOCK, "mex_mock.c"), os.path.join(MOCK, "abi_stub.c"),
-                        str(stub), str(drv), "-o", exe], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-4000:]
-    r = subprocess.run([exe], capture_output=True, text=True, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=0"))
-    assert r.returncode == 0, "the gateway misbehaved under the mock:\n" + r.stdout[-2000:] + r.stderr[-4000:]
-    return r.stdout.splitlines()
+    return transcript_of(tmp_path_factory.mktemp("mexremove"), _STUB, _DRIVER)
 
 
 def test_mex_gateway_hands_one_based_numbers_on_as_zero_based(transcript):
@@ -128,34 +92,18 @@ def test_matlab_method_forwards_to_the_gateway_command():
     assert '"remove_landmarks"' in open(os.path.join(ROOT, "matlab", "ekfslam_mex.c")).read()
 
 
-class _Recorder:
+class _Recorder(RecorderBase):
     """Stand-in for the loaded library: records ekf_remove_landmarks calls (no GPU here)."""
+
+    status_string = b"landmark index out of range"
+    last_error = b"remove_landmarks: landmark index outside the state"
 
     def __init__(self, status=0):
         self.calls, self.status = [], status
 
-    def ekf_config_default(self, pcfg, mode):
-        from ekf_slam_amd import _lib as L
-        cfg = ctypes.cast(pcfg, ctypes.POINTER(L.EkfConfig)).contents
-        cfg.mode, cfg.batch = mode, 1
-        return 0
-
-    def ekf_create(self, pcfg, ph):
-        ctypes.cast(ph, ctypes.POINTER(ctypes.c_void_p)).contents.value = 0x1000
-        return 0
-
-    def ekf_destroy(self, h):
-        return 0
-
     def ekf_remove_landmarks(self, h, arr, m):
         self.calls.append(([int(arr[i]) for i in range(m)], int(m)))
         return self.status
-
-    def ekf_status_string(self, rc):
-        return b"landmark index out of range"
-
-    def ekf_last_error(self, h):
-        return b"remove_landmarks: landmark index outside the state"
 
 
 def test_engine_and_slam_layers_reach_the_library_with_the_right_indices(monkeypatch):

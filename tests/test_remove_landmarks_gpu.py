@@ -11,61 +11,19 @@ import ctypes
 import numpy as np
 import pytest
 
+from decided_plans import PARAMS
+from helpers import R2, REL, STORES_ALL, U2, assert_same, engine, loaded, rel_err, run_ops, state, status_of
 from removal_cases import expected_after, lowrank_data, lowrank_minus, observe, removal_sets
 
 pytestmark = pytest.mark.gpu
-REL = 1e-6                      # BASELINE.json's bar against the oracle
 N0 = 300
-U2 = np.array([0.1, 1.0])
-R2 = np.diag([0.1, 0.2])
 SET_NAMES = ["first", "last", "middle", "adjacent_over_tile_edge", "whole_tile_row", "every_second", "random_tenth", "all"]
-STORES = [(16, "f64"), (64, "f64"), (128, "f64"), (256, "f32"), (256, "f32_mixed"), (256, "f32_split")]
-
-
-def rel_err(a, b):
-    a, b = np.asarray(a), np.asarray(b)
-    return float(np.abs(a - b).max() / max(np.abs(b).max(), 1e-300))
-
-
-def engine(mode="known", **kw):
-    from ekf_slam_amd.engine import Engine
-    return Engine(mode=mode, **kw)
-
-
-def loaded(N, seed, mode="known", **kw):
-    x, s, d, U = lowrank_data(N, seed)
-    e = engine(mode, **kw)
-    e.load_lowrank_state(x, s, d, U)
-    return e
-
-
-def state(e):
-    return e.get_x(), e.get_s(), e.get_P()
-
-
-def assert_same(a, b, digest=True):
-    assert a.N == b.N
-    np.testing.assert_array_equal(a.get_x(), b.get_x())
-    np.testing.assert_array_equal(a.get_s(), b.get_s())
-    np.testing.assert_array_equal(a.get_P(), b.get_P())
-    np.testing.assert_array_equal(a.get_P_diag_blocks(), b.get_P_diag_blocks())
-    if digest:
-        np.testing.assert_array_equal(a.digest(), b.digest())
-
-
-def status_of(fn):
-    from ekf_slam_amd._lib import EkfError
-    try:
-        fn()
-    except EkfError as ex:
-        return ex.status, str(ex)
-    return 0, ""
 
 
 # ------------------------------------------------------------------------------------------------------------------
 # 1. bit for bit against numpy.delete
 # ------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("tile,storage", STORES)
+@pytest.mark.parametrize("tile,storage", STORES_ALL)
 @pytest.mark.parametrize("name", SET_NAMES)
 def test_bit_for_bit_against_numpy_delete(tile, storage, name):
     idx = removal_sets(N0, tile, 11)[name]
@@ -178,17 +136,6 @@ def _continuation(ex, es, tile, batch, capacity, removed):
     return ops
 
 
-def _run(e, ops):
-    for op in ops:
-        e.predict(U2)
-        if op[0] == "append":
-            e.append(U2, R2, op[1], op[2])
-        elif op[0] == "measure":
-            e.measure(op[1], U2, op[2], op[3])
-        else:
-            e.correct(op[1], R2, op[2])
-
-
 @pytest.mark.parametrize("tile,storage,batch,asy", [(16, "f64", 8, False), (64, "f64", 8, True), (128, "f64", 32, False),
                                                     (256, "f32", 8, False), (256, "f32_mixed", 8, False), (256, "f32_mixed", 64, True),
                                                     (256, "f32_split", 32, False)])
@@ -205,8 +152,8 @@ def test_the_engine_goes_on_like_a_twin_given_the_expected_state(tile, storage, 
     twin = engine("uc", **kw)
     twin.set_state(ex, eP, es)
     ops = _continuation(ex, es, tile, batch, cap, idx)
-    _run(e, ops)
-    _run(twin, ops)
+    run_ops(e, ops)
+    run_ops(twin, ops)
     assert e.N == twin.N and e.N > es.size + 3
     if storage != "f64":
         # DESIGN.md section 5's tolerances at the least (x, F64-kept entries; float-stored entries against the row's largest) ...
@@ -220,7 +167,6 @@ def test_the_engine_goes_on_like_a_twin_given_the_expected_state(tile, storage, 
 # ------------------------------------------------------------------------------------------------------------------
 # 4. association sees the new map
 # ------------------------------------------------------------------------------------------------------------------
-POS = dict(w_pos=1.0, Rc=(0.01, 0.01), s_thresh=0.5)         # the position-weighted likelihood of tests/test_decided_assoc_gpu.py
 K_GONE = 100
 
 
@@ -264,7 +210,7 @@ def test_association_sees_the_new_map_signature_only(early):
 
 @pytest.mark.parametrize("early", [False, True])
 def test_association_sees_the_new_map_position_weighted(early):
-    runs = {m: _assoc_run(m, POS, early) for m in (0, 1, 4)}
+    runs = {m: _assoc_run(m, PARAMS, early) for m in (0, 1, 4)}
     for m in (0, 4):                                         # mode 4 with `early`: the removal arrives on unsettled rows
         assert_same(runs[m], runs[1])
 
@@ -395,8 +341,8 @@ def test_checkpoint_after_a_removal(tile, storage, tmp_path):
     fresh.checkpoint_load(path)
     np.testing.assert_array_equal(fresh.get_P(), eP)
     ops = _continuation(ex, es, tile, 8, cap, idx)
-    _run(e, ops)
-    _run(fresh, ops)
+    run_ops(e, ops)
+    run_ops(fresh, ops)
     assert_same(e, fresh)
 
 

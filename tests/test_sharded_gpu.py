@@ -11,14 +11,10 @@ import sys
 import numpy as np
 import pytest
 
+from helpers import REL, rel_err
+
 pytestmark = pytest.mark.gpu
-REL = 1e-6
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def rel_err(a, b):
-    a, b = np.asarray(a), np.asarray(b)
-    return float(np.abs(a - b).max() / max(np.abs(b).max(), 1e-300))
 
 
 def _state(N, seed):
