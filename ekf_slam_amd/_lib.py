@@ -74,6 +74,15 @@ class EkfModelMatch(ctypes.Structure):
     _fields_ = [("best", _i64), ("second", _i64), ("d2_best", _d), ("d2_second", _d), ("within_gate", _i64), ("irregular", _i64)]
 
 
+EKF_JOINT_MAX = 32
+EKF_JOINT_HYP_MAX = 256
+
+
+class EkfJointResult(ctypes.Structure):
+    """struct ekf_joint_result (include/ekfslam.h)."""
+    _fields_ = [("d2", _d), ("dof", _i32), ("pairings", _i32), ("outcome", _i32), ("first_irregular", _i32)]
+
+
 EKF_MOTION_TURN_DRIVE, EKF_MOTION_ARC, EKF_MOTION_POSE_DELTA = 1, 2, 3
 EKF_MOTION_INPUTS = {1: 2, 2: 2, 3: 3}                # entries of u (and rows of M) each motion model reads
 EKF_PREDICT_MODEL_MAX = 32
@@ -142,6 +151,8 @@ SIGNATURES = {
     "ekf_append_model": (_i32, [_vp, ctypes.POINTER(EkfModelInit), _i64, ctypes.POINTER(_i64)]),
     "ekf_model_invert": (_i32, [_i32, _dp, _dp, _dp, _dp, _dp]),
     "ekf_associate_model": (_i32, [_vp, ctypes.POINTER(EkfModelObs), _i64, ctypes.POINTER(EkfModelMatch), _dp]),
+    "ekf_joint_innovation": (_i32, [_vp, ctypes.POINTER(EkfModelObs), _i64, ctypes.POINTER(_i64), _i64, ctypes.POINTER(EkfJointResult), _dp, _dp,
+                                    _dp]),
     "ekf_predict_model": (_i32, [_vp, ctypes.POINTER(EkfMotion), _i64]),
     "ekf_motion_evaluate": (_i32, [_i32, _dp, _dp, _dp, _dp, _dp]),
     "ekf_diag_poke_device_signature": (_i32, [_vp, _i64, _d]),

@@ -14,6 +14,7 @@
 #include "host/model.h"        // ... through a model linearised on the device: observe_model, model_innovation, model_evaluate
 #include "host/append_model.h" // landmarks that start from such a model's inverse, a scan per launch: append_model, model_invert
 #include "host/associate_model.h" // which landmark a sighting belongs to, a scan per call: associate_model
+#include "host/joint.h"        // ... and a whole scan's pairings judged jointly, nh hypotheses per call: joint_innovation
 #include "host/predict_model.h" // motion steps with true Jacobians, a chain per launch: predict_model, motion_evaluate
 #include "host/state.h"        // get / set, low-rank load, checkpoint, digest
 #include "host/lifecycle.h"    // ekf_create, ekf_destroy, the kernel timers

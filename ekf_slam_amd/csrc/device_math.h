@@ -529,4 +529,91 @@ EKF_MHD double motion_noise_entry(const double V[9], const double m6[6], int i, 
     return q;
 }
 
+// JOINT compatibility of a scan's pairings (ekf_joint_innovation; joint.h runs these on the device): observation k paired with landmark
+// l_k for every paired k, the rows stacked -- S = H P H' + blockdiag(R_k), d2 = nu' S^-1 nu.
+// One pairing: assoc_model_d2's operands through the same model_eval, model_wrap and model_small, so S (row-major) and nu are
+// ekf_model_innovation's for that pair bit for bit; what the off-diagonal blocks need of H is left in Hr (row-major 2 x 3, the robot block)
+// and Ht (row-major 2 x 2, the target's).  Returns whether the pair is posed (model_eval).
+EKF_MHD bool joint_pairing(int model, const double z[2], const double R[4], const double prr[9], const double strip6[6], const double diag3[3],
+                           const double xr[3], const double l[2], double Hr[6], double Ht[4], double S[4], double nu[2]) {
+    double sm[kLinearSmall];
+    for (int e = 0; e < kLinearSmall; ++e) sm[e] = 0.0;
+    for (int e = 0; e < 9; ++e) sm[e] = prr[e];
+    for (int e = 0; e < 6; ++e) sm[9 + e] = strip6[e];
+    for (int e = 0; e < 3; ++e) { sm[21 + e] = diag3[e]; sm[31 + e] = xr[e]; }
+    sm[34] = l[0]; sm[35] = l[1];
+    const double anchor[2] = { 0.0, 0.0 };
+    double H[14], hx[2], Gs[14];
+    int wrap[2];
+    const bool posed = model_eval(model, sm + 31, anchor, true, hx, H);
+    model_wrap(model, wrap);
+    model_small(sm, H, hx, z, R, wrap, Gs, S, nu);
+    for (int r = 0; r < 2; ++r) {
+        for (int t = 0; t < 3; ++t) Hr[3 * r + t] = H[7 * r + t];
+        for (int c = 0; c < 2; ++c) Ht[2 * r + c] = H[7 * r + 3 + c];
+    }
+    return posed;
+}
+// The 2 x 2 block S_ab (row-major) of two pairings a != b on different landmarks:
+//     S_ab = Har (Prr Hbr' + strip_b Hbt') + Hat (strip_a' Hbr' + Pab Hbt')
+// prr row-major (read from its lower triangle, as linear_small_P does), strip_x[2 t + r] = P(t, l_x + r), pab[2 r + c] = P(l_a + r, l_b + c).
+// Every sum in ascending index order, the robot's terms before the landmark's; the host build of the tests compiles this same text.
+EKF_MHD void joint_cross_block(const double Har[6], const double Hat[4], const double Hbr[6], const double Hbt[4], const double prr[9],
+                               const double strip_a[6], const double strip_b[6], const double pab[4], double Sab[4]) {
+    double M1[6], M2[4];                            // M1 = Prr Hbr' + strip_b Hbt' (3 x 2), M2 = strip_a' Hbr' + Pab Hbt' (2 x 2)
+    for (int t = 0; t < 3; ++t)
+        for (int j = 0; j < 2; ++j) {
+            double v = 0.0;
+            for (int u = 0; u < 3; ++u) v += (t >= u ? prr[3 * t + u] : prr[3 * u + t]) * Hbr[3 * j + u];
+            for (int c = 0; c < 2; ++c) v += strip_b[2 * t + c] * Hbt[2 * j + c];
+            M1[2 * t + j] = v;
+        }
+    for (int r = 0; r < 2; ++r)
+        for (int j = 0; j < 2; ++j) {
+            double v = 0.0;
+            for (int t = 0; t < 3; ++t) v += strip_a[2 * t + r] * Hbr[3 * j + t];
+            for (int c = 0; c < 2; ++c) v += pab[2 * r + c] * Hbt[2 * j + c];
+            M2[2 * r + j] = v;
+        }
+    for (int i = 0; i < 2; ++i)
+        for (int j = 0; j < 2; ++j) {
+            double v = 0.0;
+            for (int t = 0; t < 3; ++t) v += Har[3 * i + t] * M1[2 * t + j];
+            for (int r = 0; r < 2; ++r) v += Hat[2 * i + r] * M2[2 * r + j];
+            Sab[2 * i + j] = v;
+        }
+}
+// The right-looking Cholesky factorisation of the n x n matrix A (lower triangle, leading dimension ld) with the forward substitution
+// riding along: y enters as nu and leaves as L^-1 nu, being one more row of A below the last.  Step k is a pivot, a column scale and a
+// trailing update, each entry's terms subtracted in ascending k -- so L's (and y's) leading part depends on A's leading block alone, with
+// the same bits whatever follows.  Written per lane: lane `lane` of `lanes` takes every lanes-th entry of a step's phase, the phases
+// separated by the caller (a barrier on the device; the host runs them with one lane).
+EKF_MHD bool joint_pivot(double p, double &lkk) {
+    lkk = sqrt(p);
+    return isfinite(p) && p > 0.0;
+}
+EKF_MHD void joint_factor_scale(double *A, int ld, double *y, int n, int k, double lkk, int lane, int lanes) {
+    for (int i = k + 1 + lane; i <= n; i += lanes) {
+        if (i < n) A[i * ld + k] = A[i * ld + k] / lkk;
+        else y[k] = y[k] / lkk;
+    }
+}
+EKF_MHD void joint_factor_update(double *A, int ld, double *y, int n, int k, int lane, int lanes) {
+    const int w = n - k - 1;                        // trailing rows; entry e < w * w: (i, j) = k + 1 + (e / w, e % w), the lower triangle kept
+    for (int e = lane; e < w * w + w; e += lanes) {
+        if (e < w * w) {
+            const int i = k + 1 + e / w, j = k + 1 + e % w;
+            if (j <= i) A[i * ld + j] = A[i * ld + j] - A[i * ld + k] * A[j * ld + k];
+        } else {
+            const int i = k + 1 + (e - w * w);
+            y[i] = y[i] - A[i * ld + k] * y[k];
+        }
+    }
+}
+// a pairing's two rows added to the running d2, in row order
+EKF_MHD double joint_prefix_add(double acc, double y0, double y1) {
+    acc = acc + y0 * y0;
+    return acc + y1 * y1;
+}
+
 }  // namespace ekfm

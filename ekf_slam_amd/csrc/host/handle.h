@@ -215,6 +215,13 @@ struct ekf_handle {
     int64_t am_nblk_cap = 0;
     char *d_amall = nullptr, *h_amall = nullptr;
     hipEvent_t ev_amodel = nullptr;
+    // ---- the joint compatibility of a scan's pairings (ekf_joint_innovation) ----
+    // the hypotheses on the device and in pinned memory; the records, prefixes and nu of a call (joint_out_bytes) likewise, and the event behind
+    // a call's readback; the stacked S of every hypothesis, 8 MiB on either side, allocated when first asked for
+    int64_t *d_jhyp = nullptr, *h_jhyp = nullptr;
+    char *d_jout = nullptr, *h_jout = nullptr;
+    double *d_jS = nullptr, *h_jS = nullptr;
+    hipEvent_t ev_joint = nullptr;
     // ---- timers, what ekf_destroy releases, the error text ----
     KernelTimer timers[EKF_KERNEL_COUNT];
     std::vector<void *> allocs;       // device memory (dalloc), pinned memory (halloc) and events (new_event): what ekf_destroy releases

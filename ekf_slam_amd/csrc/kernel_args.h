@@ -165,6 +165,27 @@ struct AssocModelArgs {
     AssocModelEntry e[kAssocModelMax];
 };
 
+// k_joint_innovation (joint.h): nh <= kJointHypMax hypotheses over one scan of m <= kJointMax observations, each pairing observation k
+// with landmark hyp[i * m + k] (or -1: left out), judged JOINTLY -- one workgroup per hypothesis, read-only.  The scan travels in the
+// argument block as k_assoc_model's does (the gate is not read); the hypotheses are a device array.  The cross blocks P(l_a, l_b) come
+// from the tiles patched with the npend pending pairs from ring slot pstart.
+constexpr int kJointMax = kAssocModelMax;
+constexpr int kJointHypMax = 256;
+constexpr int kJointRows = 2 * kJointMax;   // rows of the largest stacked S
+struct JointArgs {
+    int64_t N;                // landmarks; every hypothesis entry is -1 or below N
+    int32_t m;                // entries in use
+    int32_t cur;
+    int32_t npend;
+    int32_t pstart;
+    AssocModelEntry e[kJointMax];
+};
+// one hypothesis's answer: ekf_joint_result, field by field (outcome: 1 regular, 0 irregular)
+struct JointRecord {
+    double d2;
+    int32_t dof, pairings, outcome, first_irregular;
+};
+
 // ---- map edits, and the observations that share the constraint's device code ----
 // A constraint between two landmarks (constrain.h): "l_i - l_j was observed as (d0, d1) with noise covariance R".
 struct ConstrainArgs {

@@ -215,6 +215,12 @@ hipError_t launch_linear_probe(const DevState &st, const LinearArgs &a, double *
 hipError_t launch_gather_model(const DevState &st, const ModelArgs &a, double *rec, int64_t *cnt, int storage, hipStream_t s);
 hipError_t launch_model_probe(const DevState &st, const ModelArgs &a, double *rec, int storage, hipStream_t s);
 
+// The joint compatibility of a scan's pairings (joint.h): k_joint_innovation, one workgroup per hypothesis, read-only.  hyp (device): nh x a.m
+// landmarks, 0-based or -1, every one below a.N and none twice in a row; out (device): nh records; d2_prefix (nh x m), nu (nh x 2m) and S
+// (nh x (2m x 2m column-major)), device or nullptr, laid out by scan index.  Tile operands are read patched with the a.npend pending pairs.
+hipError_t launch_joint_innovation(const DevState &st, const JointArgs &a, const int64_t *hyp, int nh, JointRecord *out, double *d2_prefix,
+                                   double *nu, double *S, int storage, hipStream_t s);
+
 // ---- state I/O (launch/state_io.h) ----
 // dense (column-major, n x n, device) <-> tiled
 hipError_t launch_unpack_dense(const DevState &st, int cur, int64_t n_mm, double *dense, int storage, hipStream_t s);

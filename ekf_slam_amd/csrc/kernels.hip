@@ -49,6 +49,7 @@ namespace {
 #include "linear_obs.h"       // a linear observation as an update-step: k_gather_linear, k_linear_probe
 #include "model_obs.h"        // ... through a range / bearing / relative-position model evaluated at the live x: k_gather_model, k_model_probe
 #include "associate_model.h" // a scan against the whole map under the models' conventions: k_assoc_model, k_assoc_model_reduce
+#include "joint.h"            // a scan's pairings judged jointly, a hypothesis per workgroup: k_joint_innovation
 #include "merge_pass.h"       // the fused downdate-and-compact pass of a batch of merges: k_merge_pass
 #include "nearest.h"          // the candidate search in front of a merge: k_nearest
 
@@ -59,5 +60,5 @@ namespace {
 #include "launch/steps.h"         // predict, append, gather, row-panels, association
 #include "launch/pass_select.h"   // which pass instance runs: a pure function, no HIP
 #include "launch/passes.h"        // launch_downdate, the row copies behind an asynchronous pass
-#include "launch/edits.h"         // compact, constrain, linear observation, merge pass, nearest
+#include "launch/edits.h"         // compact, constrain, linear observation, joint innovation, merge pass, nearest
 #include "launch/state_io.h"      // dense <-> tiled, block reads, low-rank load, digest

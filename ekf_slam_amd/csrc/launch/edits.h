@@ -1,5 +1,5 @@
 // Fragment of kernels.hip, the launchers of the map edits: landmark removal (compact.h), a constraint between two landmarks and its
-// chained form (constrain.h), a linear observation (linear_obs.h) and one through a model (model_obs.h), the fused pass of a batch of merges (merge_pass.h), the candidate search (nearest.h).
+// chained form (constrain.h), a linear observation (linear_obs.h) and one through a model (model_obs.h), the joint innovation of a scan's pairings (joint.h), the fused pass of a batch of merges (merge_pass.h), the candidate search (nearest.h).
 #pragma once
 
 namespace {
@@ -123,6 +123,17 @@ hipError_t launch_gather_model(const DevState &st, const ModelArgs &a, double *r
 
 hipError_t launch_model_probe(const DevState &st, const ModelArgs &a, double *rec, int storage, hipStream_t s) {
     return launch_step_probe(linear_args_ok(st, a) && model_args_ok(a) && rec, [](auto ts) { return k_model_probe<decltype(ts)>; }, st, a, rec, storage, s);
+}
+
+hipError_t launch_joint_innovation(const DevState &st, const JointArgs &a, const int64_t *hyp, int nh, JointRecord *out, double *d2_prefix,
+                                   double *nu, double *S, int storage, hipStream_t s) {
+    // the scan and the hypotheses inside their limits, the map inside the strip, the ring window inside the ring, every tile held here
+    if (a.m < 1 || a.m > kJointMax || nh < 1 || nh > kJointHypMax || !hyp || !out || a.N < 0 || 2 * a.N > st.ldm || a.npend < 0 ||
+        a.npend > st.pcap || a.pstart < 0 || a.pstart >= st.pcap || st.tm.world != 1)
+        return hipErrorInvalidValue;
+    return with_storage(storage, [&](auto ts) {
+        hipLaunchKernelGGL(k_joint_innovation<decltype(ts)>, dim3((unsigned)nh), dim3(kJointBlock), 0, s, st, a, hyp, out, d2_prefix, nu, S);
+    });
 }
 
 hipError_t launch_nearest(const DevState &st, int cur, int64_t N, const double R[4], NearestEntry *out, int storage, hipStream_t s) {

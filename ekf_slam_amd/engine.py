@@ -616,6 +616,48 @@ class Engine:
             res["d2_all"] = d2
         return res
 
+    # ---- a scan's pairings judged jointly (include/ekfslam.h: ekf_joint_innovation) ----
+    def joint_innovation(self, entries, hypotheses, want_prefix=True, want_nu=False, want_S=False):
+        """The joint compatibility of a scan's pairings: entries as for associate_model (the gate is not read), hypotheses an nh x m
+        array, row i pairing observation k with the 0-based landmark hypotheses[i][k] or leaving it out (-1).  Returns {'d2', 'dof',
+        'pairings', 'outcome', 'first_irregular'} with one entry per hypothesis -- d2 = nu' S^-1 nu over the stacked paired rows, NaN
+        where a pairing is irregular -- plus 'd2_prefix' (nh x m: the joint d2 of the pairings among observations 0..k), 'nu'
+        (nh x 2m) and 'S' (nh x 2m x 2m) by scan index where asked.  More than EKF_JOINT_HYP_MAX hypotheses go out as several calls.
+        Changes and flushes nothing (ekf_joint_innovation)."""
+        entries = list(entries)
+        m = len(entries)
+        arr = (L.EkfModelObs * max(m, 1))()
+        for k, ent in enumerate(entries):
+            arr[k] = self._model_obs(ent["model"], ent["z"], ent["R"], (), (0.0, 0.0), ent.get("gate", float("inf")))      # lm = {-1, -1}
+        hyp_in = np.asarray(hypotheses)
+        if hyp_in.ndim != 2 or hyp_in.shape[1] != m or hyp_in.shape[0] < 1:
+            raise ValueError("joint_innovation: hypotheses is nh x m, one landmark (or -1) per entry of the scan")
+        if not np.all(hyp_in == np.floor(hyp_in)):
+            raise ValueError("joint_innovation: landmark indices are whole numbers")
+        hyp = np.ascontiguousarray(hyp_in, dtype=np.int64)
+        nh = hyp.shape[0]
+        res = {"d2": np.empty(nh), "dof": np.empty(nh, dtype=np.int64), "pairings": np.empty(nh, dtype=np.int64),
+               "outcome": np.empty(nh, dtype=np.int64), "first_irregular": np.empty(nh, dtype=np.int64)}
+        prefix = np.full((nh, m), np.nan) if want_prefix else None
+        nu = np.zeros((nh, 2 * m)) if want_nu else None
+        S = np.zeros((nh, 2 * m, 2 * m)) if want_S else None
+        for lo in range(0, nh, L.EKF_JOINT_HYP_MAX):
+            hi = min(nh, lo + L.EKF_JOINT_HYP_MAX)
+            out = (L.EkfJointResult * (hi - lo))()
+            part = np.ascontiguousarray(hyp[lo:hi])
+            self._check(self.lib.ekf_joint_innovation(self.h, arr, m, part.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), hi - lo, out,
+                                                      _p(prefix[lo:hi]) if want_prefix else None, _p(nu[lo:hi]) if want_nu else None,
+                                                      _p(S[lo:hi]) if want_S else None))
+            for key in res:
+                res[key][lo:hi] = [getattr(out[i], key) for i in range(hi - lo)]
+        if want_prefix:
+            res["d2_prefix"] = prefix
+        if want_nu:
+            res["nu"] = nu
+        if want_S:
+            res["S"] = S.transpose(0, 2, 1).copy()      # column-major blocks
+        return res
+
     # ---- motion steps through a model with its true Jacobians (include/ekfslam.h: ekf_predict_model) ----
     @staticmethod
     def _motions(steps):

@@ -20,6 +20,7 @@ the 2x2 diagonal covariance blocks); the ROS subscribers of SLAM.m:23-24 are rep
 (u, scan) feed.
 """
 import ctypes
+import math
 import warnings
 
 import numpy as np
@@ -29,6 +30,68 @@ from .engine import Engine, _p, _vec
 from .world import SyntheticLandmark
 
 _DEFAULT_CAPACITY = 1024
+
+
+def _gamma_p(a, x):
+    """The regularised lower incomplete gamma function P(a, x), a > 0, x >= 0: its series below a + 1, the continued fraction of its
+    complement above."""
+    if x <= 0.0:
+        return 0.0
+    front = math.exp(a * math.log(x) - x - math.lgamma(a))
+    if x < a + 1.0:
+        term = total = 1.0 / a
+        n = a
+        while abs(term) > abs(total) * 1e-17:
+            n += 1.0
+            term *= x / n
+            total += term
+        return front * total
+    tiny = 1e-300
+    b = x + 1.0 - a
+    c, d = 1.0 / tiny, 1.0 / b
+    frac = d
+    for i in range(1, 10000):
+        an = -i * (i - a)
+        b += 2.0
+        d = an * d + b
+        d = tiny if abs(d) < tiny else d
+        c = b + an / c
+        c = tiny if abs(c) < tiny else c
+        d = 1.0 / d
+        delta = d * c
+        frac *= delta
+        if abs(delta - 1.0) < 1e-16:
+            break
+    return 1.0 - front * frac
+
+
+def chi2_quantile(p, dof):
+    """The value a chi-square variable with dof degrees of freedom stays below with probability p (0 < p < 1): Newton's iteration on the
+    regularised incomplete gamma function, kept inside a bracket; dof = 0 gives 0.  What a joint d2 is gated against."""
+    p, dof = float(p), int(dof)
+    if not 0.0 < p < 1.0 or dof < 0:
+        raise ValueError("chi2_quantile: 0 < p < 1 and dof >= 0")
+    if dof == 0:
+        return 0.0
+    a = 0.5 * dof
+    lo, hi = 0.0, max(1.0, a)
+    while _gamma_p(a, hi) < p:
+        lo, hi = hi, 2.0 * hi
+    x = 0.5 * (lo + hi)
+    for _ in range(200):
+        f = _gamma_p(a, x) - p
+        if f > 0.0:
+            hi = x
+        else:
+            lo = x
+        dens = math.exp((a - 1.0) * math.log(x) - x - math.lgamma(a))
+        step = x - f / dens if dens > 0.0 else x
+        nxt = step if lo < step < hi else 0.5 * (lo + hi)
+        if abs(nxt - x) <= 1e-14 * x:
+            x = nxt
+            break
+        x = nxt
+    return 2.0 * x
 
 
 def select_merge_batch(candidates, limit):
@@ -500,6 +563,94 @@ class _EkfBase:
             for k, number in zip(fresh, self.add_landmarks_model([entries[k] for k in fresh])):
                 out[k] = ("new", number)
         return out
+
+    def joint_innovation(self, entries, hypotheses, want_prefix=True, want_nu=False, want_S=False):
+        """The joint compatibility of a scan's pairings: entries as for associate_model, hypotheses nh x m with the 1-based landmark each
+        observation is paired with, 0 = left out.  Returns {'d2', 'dof', 'pairings', 'outcome', 'first_irregular'} per hypothesis
+        (first_irregular: the 1-based entry of the scan, 0 = none), d2 = nu' S^-1 nu over the stacked paired rows with S = H P H' +
+        blockdiag(R) -- what a joint-compatibility search tests against chi2_quantile(p, dof) -- plus 'd2_prefix' (nh x m), 'nu' and 'S' by
+        scan index where asked.  Changes and flushes nothing, so it is not logged (ekf_joint_innovation).  Unsharded handles only."""
+        hyp = np.asarray(hypotheses, dtype=np.float64)
+        if hyp.ndim != 2:
+            raise ValueError("joint_innovation: hypotheses is nh x m")
+        numbers = np.array(self._landmark_numbers("joint_innovation", *hyp.reshape(-1).tolist()), dtype=np.int64).reshape(hyp.shape)
+        if np.any(numbers < 0):
+            raise ValueError("joint_innovation: a landmark is 1-based, 0 = the observation is left out")
+        res = dict(self._e.joint_innovation(entries, numbers - 1, want_prefix, want_nu, want_S))
+        res["first_irregular"] = res["first_irregular"] + 1
+        return res
+
+    def measure_model_joint(self, entries, gate_match, gate_new, joint_p=0.99, beam=64, wait=False):
+        """measure_model with the ambiguity discard replaced by a JOINT-compatibility search: entries, gate_match, gate_new and wait as
+        there.  ONE associate_model(..., want_d2=True) call: the candidates of an entry are the landmarks with individual d2 <= gate_match,
+        at most the 4 closest (by (d2, landmark)); an entry without a candidate is new where d2_best > gate_new (or the map is empty) and
+        discarded otherwise.  Then a level-synchronous branch and bound over the entries that have candidates, in scan order: at level k
+        every surviving partial hypothesis is extended by each candidate of entry k it has not used yet and by "left out", ALL extensions
+        of a level go to ONE joint_innovation call, and an extension survives where its prefix d2 <= chi2_quantile(joint_p, dof).  Where
+        more than `beam` survive, the best by (pairings descending, joint d2 ascending, hypothesis ascending) are kept.  The winner is the
+        survivor first in that order: its pairings go to observe_model(..., gate=gate_match) in scan order, then ALL new entries to one
+        add_landmarks_model call; the rest is discarded.  Returns ([(kind, landmark)] per entry as measure_model, whether the beam cut
+        the search).  Everything that changes the state goes through those two logged methods, so a replayed log reproduces the run."""
+        gate_match, gate_new, joint_p = float(gate_match), float(gate_new), float(joint_p)
+        if not gate_new >= gate_match:
+            raise ValueError("measure_model_joint: gate_new >= gate_match is required (and neither is NaN)")
+        if not 0.0 < joint_p < 1.0:
+            raise ValueError("measure_model_joint: joint_p lies strictly between 0 and 1")
+        if int(beam) != beam or beam < 1:
+            raise ValueError("measure_model_joint: beam is a whole number >= 1")
+        entries = [tuple(e) for e in entries]
+        if not 1 <= len(entries) <= L.EKF_JOINT_MAX:
+            raise ValueError("measure_model_joint: between 1 and %d entries" % L.EKF_JOINT_MAX)
+        for e in entries:
+            if len(e) not in (3, 4):
+                raise ValueError("measure_model_joint: an entry is (model, z, R) or (model, z, R, signature)")
+            if int(e[0]) not in (L.EKF_MODEL_RANGE_BEARING, L.EKF_MODEL_RELATIVE_XY):
+                raise ValueError("measure_model_joint: model is EKF_MODEL_RANGE_BEARING (1) or EKF_MODEL_RELATIVE_XY (4): a one-row model "
+                                 "does not start a landmark")
+        scan = [dict(model=int(e[0]), z=e[1], R=e[2], gate=gate_match) for e in entries]
+        res = self._e.associate_model(scan, want_d2=True)
+        cands, kinds = [], []
+        for k in range(len(entries)):
+            row = np.asarray(res["d2_all"][k], dtype=np.float64)
+            inside = sorted((float(row[i]), int(i)) for i in np.flatnonzero(row <= gate_match))       # (NaN compares false: never a candidate)
+            cands.append([i for _, i in inside[:4]])
+            if cands[k]:
+                kinds.append("search")
+            elif int(res["best"][k]) < 0 or float(res["d2_best"][k]) > gate_new:
+                kinds.append("new")
+            else:
+                kinds.append("discarded")
+        searched = [k for k, kind in enumerate(kinds) if kind == "search"]
+        order = lambda h: (-h[1], h[2], h[0])                                   # (hypothesis, pairings, joint d2)
+        alive, truncated = [((), 0, 0.0)], False
+        sub = [scan[k] for k in searched]
+        for level, k in enumerate(searched):
+            ext = [hyp + (c,) for hyp, _, _ in alive for c in cands[k] + [-1] if c < 0 or c not in hyp]
+            pad = [-1] * (len(searched) - level - 1)
+            ans = self._e.joint_innovation(sub, np.array([list(h) + pad for h in ext], dtype=np.int64).reshape(len(ext), len(searched)))
+            alive = []
+            for h, d2 in zip(ext, np.asarray(ans["d2_prefix"])[:, level]):
+                pairings = sum(1 for c in h if c >= 0)
+                if float(d2) <= chi2_quantile(joint_p, 2 * pairings):             # (models 1 and 4: two rows a pairing; NaN never survives)
+                    alive.append((h, pairings, float(d2)))
+            alive.sort(key=order)
+            if len(alive) > beam:
+                alive, truncated = alive[:int(beam)], True
+        winner = dict(zip(searched, alive[0][0])) if searched else {}
+        out = [None] * len(entries)
+        fresh = []
+        for k, (kind, e) in enumerate(zip(kinds, entries)):
+            if winner.get(k, -1) >= 0:
+                self.observe_model(int(e[0]), e[1], e[2], [winner[k] + 1], gate=gate_match, wait=wait)
+                out[k] = ("matched", winner[k] + 1)
+            elif kind == "new":
+                fresh.append(k)
+            else:
+                out[k] = ("discarded", 0)
+        if fresh:
+            for k, number in zip(fresh, self.add_landmarks_model([entries[k] for k in fresh])):
+                out[k] = ("new", number)
+        return out, truncated
 
     def _push_params(self):
         pass

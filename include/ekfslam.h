@@ -502,6 +502,47 @@ typedef struct ekf_model_match {
 } ekf_model_match;
 int32_t ekf_associate_model(ekf_handle *h, const ekf_model_obs *obs, int64_t m,
                             ekf_model_match *out /* m, required */, double *d2_all /* m x N row-major, may be NULL */);
+/* A scan judged AS A WHOLE: the joint compatibility of its pairings.  ekf_associate_model scores every observation against every landmark
+ * one at a time; where the pose is uncertain and the map locally tight several landmarks pass an observation's gate, and only a JOINT test
+ * uses that all innovations of a scan share the robot's error.  A hypothesis pairs observation k with landmark hyp[i * m + k] (0-based) or
+ * leaves it out (-1); with H_k and nu_k exactly as ekf_observe_model forms them for obs[k] at that landmark -- on the device, at the live x,
+ * bearings wrapped -- the paired rows are stacked:
+ *     S = H P H' + blockdiag(R_k),   d2 = nu' S^-1 nu   (Cholesky and a forward substitution in F64)
+ * A one-row model enters as the pair with the exactly empty second row (S_kk = [[s, 0], [0, 1]], nu_1 = 0): it adds nothing to d2 and 1 to
+ * dof.  Entries left out occupy no rows.  Each diagonal block S_kk and nu_k are ekf_model_innovation's for that pair, bit for bit.
+ *   d2_prefix[i * m + k]   the joint d2 of the pairings among observations 0 .. k: 0 before the first pairing, repeated over entries left
+ *                          out -- what a branch and bound needs at depth k.  It depends on those pairings alone, with the same bits
+ *                          whatever follows them.
+ *   nu, S                  by SCAN index: an entry left out has zero rows in nu, the identity on S's diagonal and zeros elsewhere.
+ * A pairing is IRREGULAR where its target lies on the robot or its state is not finite, or where the Cholesky pivot of one of its rows is
+ * not finite and positive.  For the first such pairing of a hypothesis: outcome = EKF_LINEAR_IRREGULAR, first_irregular = its scan index, d2
+ * and every prefix from there on are NaN, the prefixes before it are what they would be without it.  Irregular hypotheses do not fail the
+ * call.  A hypothesis with no pairing is legal: d2 = 0, dof = 0, regular.
+ * obs: entries as ekf_associate_model takes them (models 1-4, lm = {-1, -1}, the anchor ignored); the gate is ignored: testing d2 against
+ * chi2(dof) is the caller's job.
+ * The call changes nothing: no flush, ekf_pending and every bit of the state stay as found; the cross blocks P(l_a, l_b) are read from the
+ * current tile store patched with the pending pairs, beside a pass in flight (cfg.async_flush), as ekf_linear_innovation reads; it waits
+ * for the event behind its own readback alone.  A recorded predict is carried out first.  One launch, one workgroup per hypothesis,
+ * counted under EKF_KERNEL_ASSOCIATE.
+ * Refused in this order, with nothing done: h, obs, hyp or out NULL, m outside 1 .. EKF_JOINT_MAX, nh outside 1 .. EKF_JOINT_HYP_MAX, an
+ * entry ekf_associate_model refuses, a hypothesis entry below -1, a landmark twice in one hypothesis (EKF_ERR_INVALID_ARG); then
+ * ekf_observe_linear's rungs: world > 1 (EKF_ERR_INVALID_ARG: sharding -- the cross blocks live in other shards' tiles; a lone
+ * cfg.force_sharded shard works), a sharded correction between begin and finish (EKF_ERR_STATE); then a landmark >= N (EKF_ERR_INDEX). */
+#define EKF_JOINT_MAX      32      /* observations per scan (= EKF_ASSOCIATE_MODEL_MAX)        */
+#define EKF_JOINT_HYP_MAX  256     /* hypotheses per call                                      */
+typedef struct ekf_joint_result {
+    double  d2;                    /* joint nu' S^-1 nu over all pairings; NaN where irregular */
+    int32_t dof;                   /* real rows: 2 per two-row model, 1 per one-row model      */
+    int32_t pairings;              /* entries of the hypothesis that are >= 0                  */
+    int32_t outcome;               /* EKF_LINEAR_APPLIED (= regular) or EKF_LINEAR_IRREGULAR   */
+    int32_t first_irregular;       /* scan index of the first pairing with no d2, else -1      */
+} ekf_joint_result;
+int32_t ekf_joint_innovation(ekf_handle *h, const ekf_model_obs *obs, int64_t m,
+                             const int64_t *hyp /* nh x m row-major: 0-based landmark or -1 */, int64_t nh,
+                             ekf_joint_result *out   /* nh, required */,
+                             double *d2_prefix       /* nh x m, may be NULL */,
+                             double *nu              /* nh x 2m, may be NULL */,
+                             double *S               /* nh x (2m x 2m column-major), may be NULL */);
 /* The MOTION step under the same conventions: "the robot moved by u through the model, and u has the covariance M".  ekf_predict keeps the
  * reference's step (F(1,3), F(2,3) at the pre-motion heading and without pi/180, Q = (W C) W' of rank one) and is consistent with none of
  * the calls above: a filter driven through ekf_observe_model / ekf_append_model moves here.  With p = x(0:2), theta = x(2) in degrees,

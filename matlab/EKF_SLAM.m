@@ -312,6 +312,23 @@ classdef EKF_SLAM < handle
                 out(fresh, 2) = h.addLandmarksModel(model(fresh), z(fresh, :), R(:, :, fresh), sig);
             end
         end
+        function [res, prefix] = jointInnovation(h, model, z, R, hyp)
+            % The JOINT compatibility of a scan's pairings, under observeModel's conventions: hyp(i, k) is the landmark observation k
+            % (model(k), z(k, :), R(:, :, k) as for associateModel) is paired with in hypothesis i, 0 = left out.  res: one row
+            % [d2 dof pairings outcome firstIrregular] per hypothesis -- d2 = nu' * inv(S) * nu over the stacked paired rows with
+            % S = H*P*H' + blkdiag(R), what a joint-compatibility search tests against the chi-square quantile of dof; outcome 1 regular,
+            % 0 irregular (d2 NaN; firstIrregular: the entry of the scan, 0 = none).  prefix (optional): nh x m, the joint d2 of the
+            % pairings among observations 1..k.  At most 256 hypotheses a call; changes and flushes nothing.  Not a method of the reference.
+            model = double(model(:)); m = numel(model);
+            z = double(reshape(z, [], 2));
+            R = double(R); if size(R, 3) == 1, R = repmat(R, [1 1 m]); end
+            hyp = double(reshape(hyp, [], m));
+            if nargout > 1
+                [res, prefix] = h.gateway('joint_innovation', model, z, R, hyp);
+            else
+                res = h.gateway('joint_innovation', model, z, R, hyp);
+            end
+        end
         function merges = fuseDuplicatesBatched(h, gate, R, maxMerges)
             % fuseDuplicates with the pairs of one search fused in one mergeLandmarksBatch call: search; walk the candidates in
             % (d2, k) order and take [partner(k) k] when k is not yet a keep or a drop and partner(k) is not yet a drop (a keep may

@@ -14,6 +14,7 @@
  * that it validates itself) are dispatched before anything looks at prhs[1] as a handle; every other command goes through
  * handle_of(), which rejects an empty / non-uint64 / null handle with a MATLAB error instead of dereferencing it.
  */
+#include <math.h>
 #include <stdint.h>
 #include <stdlib.h>
 #include <string.h>
@@ -24,7 +25,7 @@
 /* The map-editing entry points (ekf_remove_landmarks; ekf_constrain_landmarks, ekf_merge_landmarks, ekf_landmark_distance;
  * ekf_nearest_landmarks; ekf_merge_landmarks_batch) the linear observation (ekf_observe_linear), the model observation
  * (ekf_observe_model), the append through a model (ekf_append_model), the association of a scan under the models' conventions
- * (ekf_associate_model) and the motion steps under them (ekf_predict_model) are the ones this gateway can live without: bound weakly, so that the gateway still links against a libekfslam (or a stand-in) that
+ * (ekf_associate_model), the joint compatibility of a scan's pairings (ekf_joint_innovation) and the motion steps under them (ekf_predict_model) are the ones this gateway can live without: bound weakly, so that the gateway still links against a libekfslam (or a stand-in) that
  * predates them; their commands then raise a MATLAB error instead. */
 #if defined(__GNUC__)
 #pragma weak ekf_remove_landmarks
@@ -38,6 +39,7 @@
 #pragma weak ekf_append_model
 #pragma weak ekf_associate_model
 #pragma weak ekf_predict_model
+#pragma weak ekf_joint_innovation
 #define HAVE_REMOVE_LANDMARKS (ekf_remove_landmarks != 0)
 #define HAVE_CONSTRAIN_LANDMARKS (ekf_constrain_landmarks != 0)
 #define HAVE_MERGE_LANDMARKS (ekf_merge_landmarks != 0)
@@ -49,6 +51,7 @@
 #define HAVE_APPEND_MODEL (ekf_append_model != 0)
 #define HAVE_ASSOCIATE_MODEL (ekf_associate_model != 0)
 #define HAVE_PREDICT_MODEL (ekf_predict_model != 0)
+#define HAVE_JOINT_INNOVATION (ekf_joint_innovation != 0)
 #else
 #define HAVE_REMOVE_LANDMARKS 1
 #define HAVE_CONSTRAIN_LANDMARKS 1
@@ -61,6 +64,7 @@
 #define HAVE_APPEND_MODEL 1
 #define HAVE_ASSOCIATE_MODEL 1
 #define HAVE_PREDICT_MODEL 1
+#define HAVE_JOINT_INNOVATION 1
 #endif
 
 static void need(int nrhs, int want, const char *cmd) {
@@ -372,6 +376,64 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
             out[4 * m + k] = (double)match[k].within_gate; out[5 * m + k] = (double)match[k].irregular;
         }
         if (all) plhs[1] = all;
+        return;
+    }
+    if (!strcmp(cmd, "joint_innovation")) {       /* [res, prefix] = (h, model m x 1 (1..4), z m x 2, R 2 x 2 x m, hyp nh x m): the joint compatibility of a scan's
+                                                     pairings; hyp(i, k) = the landmark (1-based) observation k is paired with in hypothesis i, 0 = left out;
+                                                     res nh x 5 = [d2 dof pairings outcome firstIrregular] (the entry of the scan, 1-based, 0 = none);
+                                                     prefix (second output, optional): nh x m, the joint d2 of the pairings among observations 1..k */
+        need(nrhs, 6, cmd);
+        if (!HAVE_JOINT_INNOVATION) mexErrMsgIdAndTxt("ekfslam:usage", "joint_innovation: this libekfslam has no ekf_joint_innovation");
+        const mwSize m = prhs[2] ? mxGetNumberOfElements(prhs[2]) : 0;
+        if (m < 1 || m > EKF_JOINT_MAX) mexErrMsgIdAndTxt("ekfslam:usage", "joint_innovation: between 1 and %d observations in one call", EKF_JOINT_MAX);
+        if (!mxGetPr(prhs[2]) || !prhs[3] || mxGetM(prhs[3]) != m || mxGetNumberOfElements(prhs[3]) != 2 * m || !mxGetPr(prhs[3]))
+            mexErrMsgIdAndTxt("ekfslam:usage", "joint_innovation: z needs m x 2 elements, one row per entry of model");
+        if (!prhs[4] || mxGetNumberOfElements(prhs[4]) != 4 * m || !mxGetPr(prhs[4]))
+            mexErrMsgIdAndTxt("ekfslam:usage", "joint_innovation: R needs 2 x 2 x m elements");
+        const mwSize nh = prhs[5] ? mxGetM(prhs[5]) : 0;
+        if (nh < 1 || nh > EKF_JOINT_HYP_MAX) mexErrMsgIdAndTxt("ekfslam:usage", "joint_innovation: between 1 and %d hypotheses in one call", EKF_JOINT_HYP_MAX);
+        if (mxGetN(prhs[5]) != m || mxGetNumberOfElements(prhs[5]) != nh * m || !mxGetPr(prhs[5]))
+            mexErrMsgIdAndTxt("ekfslam:usage", "joint_innovation: hyp needs nh x m elements, one column per entry of model");
+        ekf_model_obs o[EKF_JOINT_MAX];
+        for (mwSize k = 0; k < m; ++k) {
+            o[k].model = (int32_t)mxGetPr(prhs[2])[k]; o[k].reserved = 0;
+            o[k].z[0] = mxGetPr(prhs[3])[k]; o[k].z[1] = mxGetPr(prhs[3])[m + k];       /* column-major m x 2 */
+            for (int q = 0; q < 4; ++q) o[k].R[q] = mxGetPr(prhs[4])[4 * k + q];
+            o[k].lm[0] = o[k].lm[1] = -1;
+            o[k].anchor[0] = o[k].anchor[1] = 0.0;
+            o[k].gate = HUGE_VAL;
+        }
+        int64_t *hyp = (int64_t *)malloc((size_t)(nh * m) * sizeof(int64_t));           /* freed before any MATLAB error can unwind */
+        ekf_joint_result *res = (ekf_joint_result *)malloc((size_t)nh * sizeof(ekf_joint_result));
+        if (!hyp || !res) { free(hyp); free(res); mexErrMsgIdAndTxt("ekfslam:usage", "joint_innovation: out of memory"); }
+        bool whole = true;
+        for (mwSize i = 0; i < nh; ++i)
+            for (mwSize k = 0; k < m; ++k) {
+                const double v = mxGetPr(prhs[5])[k * nh + i];                            /* column-major nh x m -> row-major, 1-based -> 0-based */
+                whole = whole && v >= 0.0 && v < 9.0e15 && (double)(int64_t)v == v;      /* (no libm call: the gateway links without it) */
+                hyp[i * m + k] = whole ? (int64_t)v - 1 : -1;
+            }
+        if (!whole) { free(hyp); free(res); mexErrMsgIdAndTxt("ekfslam:usage", "joint_innovation: hyp holds landmark numbers (1-based), 0 = left out"); }
+        mxArray *rowmajor = nlhs > 1 ? mxCreateDoubleMatrix(m, nh, mxREAL) : NULL;       /* m x nh column-major is nh x m row-major */
+        const int32_t rc = ekf_joint_innovation(h, o, (int64_t)m, hyp, (int64_t)nh, res, rowmajor ? mxGetPr(rowmajor) : NULL, NULL, NULL);
+        mxArray *out = NULL, *prefix = NULL;
+        if (rc == EKF_OK) {
+            out = mxCreateDoubleMatrix(nh, 5, mxREAL);
+            for (mwSize i = 0; i < nh; ++i) {
+                mxGetPr(out)[i] = res[i].d2; mxGetPr(out)[nh + i] = (double)res[i].dof; mxGetPr(out)[2 * nh + i] = (double)res[i].pairings;
+                mxGetPr(out)[3 * nh + i] = (double)res[i].outcome; mxGetPr(out)[4 * nh + i] = (double)(res[i].first_irregular + 1);
+            }
+            if (rowmajor) {
+                prefix = mxCreateDoubleMatrix(nh, m, mxREAL);
+                for (mwSize i = 0; i < nh; ++i)
+                    for (mwSize k = 0; k < m; ++k) mxGetPr(prefix)[k * nh + i] = mxGetPr(rowmajor)[i * m + k];
+            }
+        }
+        free(hyp); free(res);
+        if (rowmajor) mxDestroyArray(rowmajor);
+        check(h, rc);
+        plhs[0] = out;
+        if (prefix) plhs[1] = prefix;
         return;
     }
     if (!strcmp(cmd, "predict_model")) {          /* (h, model m x 1 (1..3), u m x 3, M 3 x 3 x m): a chain of motion steps with their true Jacobians, in order,
