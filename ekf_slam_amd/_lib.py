@@ -58,6 +58,14 @@ class EkfModelObs(ctypes.Structure):
 EKF_MODEL_RANGE_BEARING, EKF_MODEL_RANGE, EKF_MODEL_BEARING, EKF_MODEL_RELATIVE_XY, EKF_MODEL_LANDMARK_RANGE = 1, 2, 3, 4, 5
 EKF_MODEL_ROWS = {1: 2, 2: 1, 3: 1, 4: 2, 5: 1}       # rows of z each model reads
 
+EKF_MODEL_ITER_MAX = 16
+
+
+class EkfIteratedResult(ctypes.Structure):
+    """struct ekf_iterated_result (include/ekfslam.h)."""
+    _fields_ = [("S", _d * 4), ("nu", _d * 2), ("used", _i32), ("converged", _i32), ("last_step", _d), ("x_local", _d * 7)]
+
+
 EKF_APPEND_MODEL_MAX = 32
 
 
@@ -148,6 +156,12 @@ SIGNATURES = {
     "ekf_observe_model": (_i32, [_vp, ctypes.POINTER(EkfModelObs), ctypes.POINTER(EkfLinearResult)]),
     "ekf_model_innovation": (_i32, [_vp, ctypes.POINTER(EkfModelObs), ctypes.POINTER(EkfLinearResult)]),
     "ekf_model_evaluate": (_i32, [_i32, _dp, _dp, _dp, _dp, _dp]),
+    "ekf_observe_model_iterated": (_i32, [_vp, ctypes.POINTER(EkfModelObs), _i32, _d, ctypes.POINTER(EkfLinearResult),
+                                          ctypes.POINTER(EkfIteratedResult)]),
+    "ekf_model_innovation_iterated": (_i32, [_vp, ctypes.POINTER(EkfModelObs), _i32, _d, ctypes.POINTER(EkfLinearResult),
+                                             ctypes.POINTER(EkfIteratedResult)]),
+    "ekf_model_iterate": (_i32, [_i32, _dp, _dp, _i32, _dp, _dp, _d, _i32, _d, ctypes.POINTER(EkfLinearResult),
+                                 ctypes.POINTER(EkfIteratedResult)]),
     "ekf_append_model": (_i32, [_vp, ctypes.POINTER(EkfModelInit), _i64, ctypes.POINTER(_i64)]),
     "ekf_model_invert": (_i32, [_i32, _dp, _dp, _dp, _dp, _dp]),
     "ekf_associate_model": (_i32, [_vp, ctypes.POINTER(EkfModelObs), _i64, ctypes.POINTER(EkfModelMatch), _dp]),

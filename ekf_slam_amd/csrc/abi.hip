@@ -12,6 +12,7 @@
 #include "host/edits.h"        // remove, constrain / merge / distance, nearest
 #include "host/linear.h"       // linear observations as update-steps: observe_linear, linear_innovation, linear_rejections
 #include "host/model.h"        // ... through a model linearised on the device: observe_model, model_innovation, model_evaluate
+#include "host/model_iter.h"   // ... relinearised on the device, the iterated EKF update: observe_model_iterated, model_innovation_iterated, model_iterate
 #include "host/append_model.h" // landmarks that start from such a model's inverse, a scan per launch: append_model, model_invert
 #include "host/associate_model.h" // which landmark a sighting belongs to, a scan per call: associate_model
 #include "host/joint.h"        // ... and a whole scan's pairings judged jointly, nh hypotheses per call: joint_innovation

@@ -19,6 +19,11 @@
 #define EKF_SEL(c) (c)
 #endif
 
+// A compiler-level fence, no instruction: what was read from memory before it is read again after it.  ekfm::model_iterate puts one at the
+// top of its loop so that the 38 operands in LDS are re-read by each linearisation instead of being held in registers across all of them
+// (held, k_gather_model_iter needs 323 registers and one workgroup fills a CU; re-read, an LDS load costs nothing beside the loop's divisions).
+#define EKF_REREAD() __asm__ __volatile__("" ::: "memory")
+
 namespace ekfm {
 
 constexpr double kD2R = 0.017453292519943295;
@@ -321,6 +326,69 @@ EKF_MHD void model_small(const double *sm, const double H[14], const double hx[2
             for (int j = 0; j < 7; ++j) s += Gs[7 * r + j] * H[7 * b + j];
             S[2 * r + b] = s + R[2 * r + b];
         }
+}
+
+// The ITERATED small part of a model observation (ekf_observe_model_iterated; model_iter.h runs it on lane 0): Gauss-Newton on the MAP
+// cost over the seven entries x0 = sm[31..37] under their 7 x 7 covariance P in sm, relinearising h up to `iterations` times --
+//     xi_0 = x0;   (h_i, H_i) at xi_i;   Gs_i = H_i P;   S_i = Gs_i H_i' + R       (model_small: its sums, its order)
+//     r_i = wrap(z - h_i) - H_i (x0 - xi_i)     (i = 0: wrap(z - h_0) alone, no second term formed)
+//     xi_{i+1} = x0 + Gs_i' S_i^-1 r_i;   step = max_k |xi_{i+1}[k] - xi_i[k]|;   stop after i = iterations - 1 or where step <= tol
+// The GATE is read at the first linearisation only: outcome0 / d2_0 / S_0 / nu_0 are ekf_model_innovation's, and a first linearisation
+// that does not apply ends the loop with used = 0.  A later iterate that is not posed (model_eval false) or whose S is irregular
+// (constrain_d2) makes the whole call EKF_LINEAR_IRREGULAR, all or nothing: used = the linearisations whose step was taken.
+// `converged` is step <= tol, so under tol = 0 a step of exactly 0 (a model that is linear in effect) counts as converged and stops.
+// H, Gs, S and r are the LAST linearisation's, the operands of the pair; xi is xi_used, the seven entries the pair leaves in x.
+// With iterations = 1 model_eval, model_wrap, model_small and linear_outcome run in model_obs.h's order: the same bits.
+constexpr int kModelIterMax = 16;
+struct ModelIterate {
+    double S0[4], nu0[2], d2;      // the first linearisation's, what the 8-double record reports
+    double xi[7];
+    double last_step;
+    int used, converged;
+};
+EKF_MHD int model_iterate(int model, const double *sm, const double anchor[2], bool has_landmark, const double z[2], const double R[4],
+                          double gate, int iterations, double tol, double H[14], double Gs[14], double S[4], double r[2], ModelIterate &it) {
+    double hx[2], xi[7];
+    int wrap[2];
+    model_wrap(model, wrap);
+    for (int k = 0; k < 7; ++k) xi[k] = sm[31 + k];
+    it.last_step = 0.0;
+    it.used = it.converged = 0;
+    int outcome = 1;
+    for (int i = 0; i < iterations; ++i) {
+        EKF_REREAD();
+        const bool posed = model_eval(model, xi, anchor, has_landmark, hx, H);
+        model_small(sm, H, hx, z, R, wrap, Gs, S, r);
+        if (i == 0) {
+            outcome = linear_outcome(S, r, gate, it.d2);
+            if (!posed) { outcome = 0; it.d2 = NAN; }
+            for (int q = 0; q < 4; ++q) it.S0[q] = S[q];
+            it.nu0[0] = r[0]; it.nu0[1] = r[1];
+        } else {
+            for (int q = 0; q < 2; ++q) {
+                double hd = 0.0;
+                for (int k = 0; k < 7; ++k) hd += H[7 * q + k] * (sm[31 + k] - xi[k]);
+                r[q] -= hd;
+            }
+            double d2i;
+            if (!posed || !constrain_d2(S, r[0], r[1], d2i)) outcome = 0;
+        }
+        if (outcome != 1) break;
+        double Si[4], step = 0.0;
+        inv2(S, Si);
+        for (int k = 0; k < 7; ++k) {
+            const double k0 = Gs[k] * Si[0] + Gs[7 + k] * Si[2], k1 = Gs[k] * Si[1] + Gs[7 + k] * Si[3];
+            const double nx = sm[31 + k] + (k0 * r[0] + k1 * r[1]);
+            step = fmax(step, fabs(nx - xi[k]));
+            xi[k] = nx;
+        }
+        it.last_step = step;
+        it.used = i + 1;
+        it.converged = step <= tol;
+        if (it.converged) break;
+    }
+    for (int k = 0; k < 7; ++k) it.xi[k] = xi[k];
+    return outcome;
 }
 
 // The INVERSE of the two models that determine a point (ekf_append_model; append_model.h runs it on the device): the landmark t = g(x_r, z)

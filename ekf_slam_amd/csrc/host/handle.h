@@ -208,6 +208,9 @@ struct ekf_handle {
     double *d_linrec = nullptr, *h_linrec = nullptr;
     int64_t *d_lincnt = nullptr;
     hipEvent_t ev_linrec = nullptr;
+    // ---- model observations relinearised on the device (ekf_observe_model_iterated / ekf_model_innovation_iterated) ----
+    // the iteration record of the update-step, then the probe's, on the device and in pinned memory; read back behind ev_linrec
+    double *d_itrec = nullptr, *h_itrec = nullptr;
     // ---- a scan matched to the map under the models' conventions (ekf_associate_model) ----
     // one record per workgroup (am_nblk_cap per observation) and the m results on the device, the results' pinned copy and the event behind
     // a call's readback; the results followed by the m x N block of d2_all on the device and in pinned memory (allocated when first asked for)

@@ -234,3 +234,14 @@ struct ModelArgs {
     int32_t npend;
     int32_t pstart;
 };
+
+// ... relinearised up to `iterations` times on lane 0 (model_iter.h, ekfm::model_iterate): ModelArgs and the loop's two controls.  The pair
+// of the LAST linearisation goes to the ring; the launch's shape, its operands and its outputs are k_gather_model's.
+struct IterModelArgs : ModelArgs {
+    int32_t iterations;       // 1 .. ekfm::kModelIterMax
+    int32_t pad_;
+    double tol;               // the loop stops where the largest move of an entry is <= tol (0: all of them, but for a move of exactly 0)
+};
+// the second record of such a launch: the last linearisation's S row-major (0..3) | its residual r (4, 5) | used (6) | converged (7) |
+// the last step (8) | xi_used (9..15)
+constexpr int kIterRecordDoubles = 16;

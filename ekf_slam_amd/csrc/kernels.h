@@ -214,6 +214,11 @@ hipError_t launch_linear_probe(const DevState &st, const LinearArgs &a, double *
 // a target on the robot (q = 0) or a non-finite q counts and reports as an irregular S
 hipError_t launch_gather_model(const DevState &st, const ModelArgs &a, double *rec, int64_t *cnt, int storage, hipStream_t s);
 hipError_t launch_model_probe(const DevState &st, const ModelArgs &a, double *rec, int storage, hipStream_t s);
+// ... relinearised (model_iter.h).  k_gather_model_iter / k_model_iter_probe: the two launches above with ekfm::model_iterate on lane 0 and the
+// last linearisation's pair; rec keeps the FIRST linearisation's S, nu and d2 and the overall outcome, so the counters and the gate mean
+// what they mean above, and itrec (device, kIterRecordDoubles doubles) takes the iteration record
+hipError_t launch_gather_model_iter(const DevState &st, const IterModelArgs &a, double *rec, int64_t *cnt, double *itrec, int storage, hipStream_t s);
+hipError_t launch_model_iter_probe(const DevState &st, const IterModelArgs &a, double *rec, double *itrec, int storage, hipStream_t s);
 
 // The joint compatibility of a scan's pairings (joint.h): k_joint_innovation, one workgroup per hypothesis, read-only.  hyp (device): nh x a.m
 // landmarks, 0-based or -1, every one below a.N and none twice in a row; out (device): nh records; d2_prefix (nh x m), nu (nh x 2m) and S

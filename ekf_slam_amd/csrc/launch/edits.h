@@ -125,6 +125,23 @@ hipError_t launch_model_probe(const DevState &st, const ModelArgs &a, double *re
     return launch_step_probe(linear_args_ok(st, a) && model_args_ok(a) && rec, [](auto ts) { return k_model_probe<decltype(ts)>; }, st, a, rec, storage, s);
 }
 
+// the relinearised step: launch_step's grid and launch_step_probe's wavefront, with the iteration record as one more argument
+hipError_t launch_gather_model_iter(const DevState &st, const IterModelArgs &a, double *rec, int64_t *cnt, double *itrec, int storage, hipStream_t s) {
+    if (!(linear_args_ok(st, a) && model_args_ok(a) && a.npend < st.pcap && rec && cnt && itrec) || a.iterations < 1 ||
+        a.iterations > ekfm::kModelIterMax || !(a.tol >= 0.0))
+        return hipErrorInvalidValue;
+    const int64_t grid = std::max<int64_t>(1, cdiv(st.tm.padded(a.n_mm), kBlock));
+    return with_storage(storage, [&](auto ts) {
+        hipLaunchKernelGGL(k_gather_model_iter<decltype(ts)>, dim3((unsigned)grid), dim3(kBlock), 0, s, st, a, rec, cnt, itrec);
+    });
+}
+
+hipError_t launch_model_iter_probe(const DevState &st, const IterModelArgs &a, double *rec, double *itrec, int storage, hipStream_t s) {
+    if (!(linear_args_ok(st, a) && model_args_ok(a) && rec && itrec) || a.iterations < 1 || a.iterations > ekfm::kModelIterMax || !(a.tol >= 0.0))
+        return hipErrorInvalidValue;
+    return with_storage(storage, [&](auto ts) { hipLaunchKernelGGL(k_model_iter_probe<decltype(ts)>, dim3(1), dim3(64), 0, s, st, a, rec, itrec); });
+}
+
 hipError_t launch_joint_innovation(const DevState &st, const JointArgs &a, const int64_t *hyp, int nh, JointRecord *out, double *d2_prefix,
                                    double *nu, double *S, int storage, hipStream_t s) {
     // the scan and the hypotheses inside their limits, the map inside the strip, the ring window inside the ring, every tile held here

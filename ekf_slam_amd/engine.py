@@ -535,6 +535,51 @@ class Engine:
         self._check(self.lib.ekf_model_innovation(self.h, ctypes.byref(o), ctypes.byref(res)))
         return self._linear_result(res)
 
+    # ---- ... relinearised on the device: the iterated EKF update (include/ekfslam.h: ekf_observe_model_iterated) ----
+    @staticmethod
+    def _iterated_result(first, it):
+        out = Engine._linear_result(first)
+        out["iterated"] = {"S": np.array(it.S[:]).reshape(2, 2, order="F"), "nu": np.array(it.nu[:]), "used": int(it.used),
+                           "converged": bool(it.converged), "last_step": float(it.last_step), "x_local": np.array(it.x_local[:])}
+        return out
+
+    def observe_model_iterated(self, model, z, R, landmarks=(), anchor=None, gate=float("inf"), iterations=3, tol=0.0, wait=False):
+        """observe_model with h relinearised up to `iterations` times (1..16) on the device, Gauss-Newton on the MAP cost over the
+        robot and the target(s); stops early where no entry moves by more than tol (ekf_observe_model_iterated).  One launch and one
+        pair in the ring, like observe_model; the gate is read at the first linearisation.  wait=True returns observe_model's dict (the
+        FIRST linearisation's nu, S, d2; the call's outcome) with 'iterated': {'S', 'nu', 'used', 'converged', 'last_step', 'x_local'}
+        of the linearisation that made the pair.  An iterate without a Jacobian or with an irregular S raises EkfError; nothing is
+        changed then."""
+        o = self._model_obs(model, z, R, landmarks, anchor, gate)
+        if not wait:
+            self._check(self.lib.ekf_observe_model_iterated(self.h, ctypes.byref(o), int(iterations), float(tol), None, None))
+            return None
+        first, it = L.EkfLinearResult(), L.EkfIteratedResult()
+        self._check(self.lib.ekf_observe_model_iterated(self.h, ctypes.byref(o), int(iterations), float(tol), ctypes.byref(first), ctypes.byref(it)))
+        return self._iterated_result(first, it)
+
+    def model_innovation_iterated(self, model, z, R, landmarks=(), anchor=None, gate=float("inf"), iterations=3, tol=0.0):
+        """What observe_model_iterated(..., wait=True) would report under the current state, bit for bit; changes and flushes nothing
+        (ekf_model_innovation_iterated).  An irregular outcome is reported, not raised."""
+        o = self._model_obs(model, z, R, landmarks, anchor, gate)
+        first, it = L.EkfLinearResult(), L.EkfIteratedResult()
+        self._check(self.lib.ekf_model_innovation_iterated(self.h, ctypes.byref(o), int(iterations), float(tol), ctypes.byref(first), ctypes.byref(it)))
+        return self._iterated_result(first, it)
+
+    @staticmethod
+    def model_iterate(model, sm, z, R, anchor=None, has_landmark=True, gate=float("inf"), iterations=3, tol=0.0, lib=None):
+        """The loop the kernel runs, on the host (ekf_model_iterate): sm = the 38 operands of the small part (include/ekfslam.h names the
+        layout), R the 2 x 2 the kernel sees (a one-row model: [[r, 0], [0, 1]]).  Returns model_innovation_iterated's dict."""
+        lib = L.lib() if lib is None else lib
+        first, it = L.EkfLinearResult(), L.EkfIteratedResult()
+        Rm = np.ascontiguousarray(np.asarray(R, dtype=np.float64).reshape(2, 2).reshape(-1, order="F"))
+        av = _vec(anchor, 2) if anchor is not None else np.zeros(2)
+        rc = lib.ekf_model_iterate(int(model), _p(_vec(sm, 38)), _p(av), int(bool(has_landmark)), _p(_vec(z, 2)), _p(Rm), float(gate),
+                                   int(iterations), float(tol), ctypes.byref(first), ctypes.byref(it))
+        if rc:
+            raise L.EkfError(rc, "ekf_model_iterate")
+        return Engine._iterated_result(first, it)
+
     @staticmethod
     def model_evaluate(model, xr, t0, t1=None, lib=None):
         """(h(x), H) of a model at the robot state xr = (x, y, theta in degrees) and the targets t0 (and t1: the second landmark of

@@ -354,13 +354,16 @@ class _EkfBase:
         return self.observe_linear([float(theta_deg)], [[float(var), 0.0], [0.0, 0.0]], np.array([[0.0, 0.0, 1.0], [0.0, 0.0, 0.0]]),
                                    gate=gate, wrap=(1, 0), rows=1, wait=wait)
 
-    def observe_model(self, model, z, R, landmarks=(), anchor=None, gate=float("inf"), wait=False):
+    def observe_model(self, model, z, R, landmarks=(), anchor=None, gate=float("inf"), wait=False, iterations=1, tol=0.0):
         """'h(x) was observed as z with noise covariance R' for one of the models EKF_MODEL_* of include/ekfslam.h -- range and
         bearing (1), range (2), bearing (3), the target's position in the robot frame (4), the distance between two landmarks (5) --
         linearised on the device at the live state, the bearing innovation wrapped.  landmarks: the 1-based target (two for model 5);
         anchor: a known point outside the map as the target instead (only the robot is corrected).  An UPDATE-STEP like
         observe_linear: flushes nothing and, unless wait=True, waits for nothing; applied only if d2 <= gate.  wait=True returns
-        {'nu', 'S', 'd2', 'outcome'} (ekf_observe_model).  The reference has no such method."""
+        {'nu', 'S', 'd2', 'outcome'} (ekf_observe_model).  iterations > 1 (or a tol > 0) relinearises: observe_model_iterated.  The
+        reference has no such method."""
+        if int(iterations) != 1 or float(tol) != 0.0:
+            return self.observe_model_iterated(model, z, R, landmarks, anchor, gate, iterations, tol, wait)
         lms = self._landmark_numbers("observe_model", *list(landmarks))
         obs = self._e._model_obs(model, z, R, [k - 1 for k in lms], anchor, gate)           # (the engine's own shape checks)
         out = self._e.observe_model(model, z, R, [k - 1 for k in lms], anchor, gate, wait)
@@ -375,33 +378,61 @@ class _EkfBase:
         lms = self._landmark_numbers("model_innovation", *list(landmarks))
         return self._e.model_innovation(model, z, R, [k - 1 for k in lms], anchor, gate)
 
-    def observe_range_bearing(self, i, z, R, gate=float("inf"), wait=False):
+    def observe_model_iterated(self, model, z, R, landmarks=(), anchor=None, gate=float("inf"), iterations=3, tol=0.0, wait=False):
+        """observe_model as the ITERATED EKF update: h is relinearised up to `iterations` times (1..16) on the device -- Gauss-Newton on
+        the MAP cost over the robot and the target(s) -- until no entry moves by more than tol, and the last linearisation makes the
+        step's one pair.  Worth it where the prior is wide against the sensor: a new landmark, a heading known to ten degrees, a precise
+        fix.  One launch, no flush, like observe_model; the gate is read at the first linearisation.  wait=True returns observe_model's
+        dict (the first linearisation's) with 'iterated': {'S', 'nu', 'used', 'converged', 'last_step', 'x_local'}
+        (ekf_observe_model_iterated).  The reference has no such method."""
+        lms = self._landmark_numbers("observe_model_iterated", *list(landmarks))
+        obs = self._e._model_obs(model, z, R, [k - 1 for k in lms], anchor, gate)           # (the engine's own shape checks)
+        out = self._e.observe_model_iterated(model, z, R, [k - 1 for k in lms], anchor, gate, iterations, tol, wait)
+        if self.log is not None:
+            self.log.record_model_observation_iterated(obs.model, np.array(obs.z[:]), np.array(obs.R[:]).reshape(2, 2, order="F"), lms,
+                                                       None if lms else np.array(obs.anchor[:]), gate, iterations, tol)
+        return out
+
+    def model_innovation_iterated(self, model, z, R, landmarks=(), anchor=None, gate=float("inf"), iterations=3, tol=0.0):
+        """What observe_model_iterated(..., wait=True) would report now (1-based landmarks); changes and flushes nothing
+        (ekf_model_innovation_iterated)."""
+        lms = self._landmark_numbers("model_innovation_iterated", *list(landmarks))
+        return self._e.model_innovation_iterated(model, z, R, [k - 1 for k in lms], anchor, gate, iterations, tol)
+
+    def observe_range_bearing(self, i, z, R, gate=float("inf"), wait=False, iterations=1, tol=0.0):
         """'Landmark i (1-based) is seen at range z[0] and bearing z[1] (degrees, relative to the heading), covariance R'."""
-        return self.observe_model(L.EKF_MODEL_RANGE_BEARING, _vec(z, 2), R, [i], gate=gate, wait=wait)
+        return self.observe_model(L.EKF_MODEL_RANGE_BEARING, _vec(z, 2), R, [i], gate=gate, wait=wait,
+                                  iterations=iterations, tol=tol)
 
-    def observe_range(self, i, r, var, gate=float("inf"), wait=False):
+    def observe_range(self, i, r, var, gate=float("inf"), wait=False, iterations=1, tol=0.0):
         """'Landmark i is at distance r, with variance var' (a range-only beacon)."""
-        return self.observe_model(L.EKF_MODEL_RANGE, [float(r)], [[float(var), 0.0], [0.0, 0.0]], [i], gate=gate, wait=wait)
+        return self.observe_model(L.EKF_MODEL_RANGE, [float(r)], [[float(var), 0.0], [0.0, 0.0]], [i], gate=gate, wait=wait,
+                                  iterations=iterations, tol=tol)
 
-    def observe_bearing(self, i, deg, var, gate=float("inf"), wait=False):
+    def observe_bearing(self, i, deg, var, gate=float("inf"), wait=False, iterations=1, tol=0.0):
         """'Landmark i is seen at bearing deg (degrees, relative to the heading), with variance var' (a camera)."""
-        return self.observe_model(L.EKF_MODEL_BEARING, [float(deg)], [[float(var), 0.0], [0.0, 0.0]], [i], gate=gate, wait=wait)
+        return self.observe_model(L.EKF_MODEL_BEARING, [float(deg)], [[float(var), 0.0], [0.0, 0.0]], [i], gate=gate, wait=wait,
+                                  iterations=iterations, tol=tol)
 
-    def observe_relative_xy(self, i, z, R, gate=float("inf"), wait=False):
+    def observe_relative_xy(self, i, z, R, gate=float("inf"), wait=False, iterations=1, tol=0.0):
         """'Landmark i lies at z = (forward, left) in the robot frame, covariance R' (a lidar or stereo front end)."""
-        return self.observe_model(L.EKF_MODEL_RELATIVE_XY, _vec(z, 2), R, [i], gate=gate, wait=wait)
+        return self.observe_model(L.EKF_MODEL_RELATIVE_XY, _vec(z, 2), R, [i], gate=gate, wait=wait,
+                                  iterations=iterations, tol=tol)
 
-    def observe_landmark_range(self, i, j, dist, var, gate=float("inf"), wait=False):
+    def observe_landmark_range(self, i, j, dist, var, gate=float("inf"), wait=False, iterations=1, tol=0.0):
         """'Landmarks i and j are dist apart, with variance var' (a tape measure between two beacons)."""
-        return self.observe_model(L.EKF_MODEL_LANDMARK_RANGE, [float(dist)], [[float(var), 0.0], [0.0, 0.0]], [i, j], gate=gate, wait=wait)
+        return self.observe_model(L.EKF_MODEL_LANDMARK_RANGE, [float(dist)], [[float(var), 0.0], [0.0, 0.0]], [i, j], gate=gate, wait=wait,
+                                  iterations=iterations, tol=tol)
 
-    def observe_anchor_range(self, pos, r, var, gate=float("inf"), wait=False):
+    def observe_anchor_range(self, pos, r, var, gate=float("inf"), wait=False, iterations=1, tol=0.0):
         """'The known point pos, which is not in the map, is at distance r, with variance var' (a surveyed UWB anchor)."""
-        return self.observe_model(L.EKF_MODEL_RANGE, [float(r)], [[float(var), 0.0], [0.0, 0.0]], anchor=_vec(pos, 2), gate=gate, wait=wait)
+        return self.observe_model(L.EKF_MODEL_RANGE, [float(r)], [[float(var), 0.0], [0.0, 0.0]], anchor=_vec(pos, 2), gate=gate, wait=wait,
+                                  iterations=iterations, tol=tol)
 
-    def observe_anchor_bearing(self, pos, deg, var, gate=float("inf"), wait=False):
+    def observe_anchor_bearing(self, pos, deg, var, gate=float("inf"), wait=False, iterations=1, tol=0.0):
         """'The known point pos, which is not in the map, is seen at bearing deg, with variance var'."""
-        return self.observe_model(L.EKF_MODEL_BEARING, [float(deg)], [[float(var), 0.0], [0.0, 0.0]], anchor=_vec(pos, 2), gate=gate, wait=wait)
+        return self.observe_model(L.EKF_MODEL_BEARING, [float(deg)], [[float(var), 0.0], [0.0, 0.0]], anchor=_vec(pos, 2), gate=gate, wait=wait,
+                                  iterations=iterations, tol=tol)
 
     def add_landmarks_model(self, entries):
         """One scan of NEW landmarks under observe_model's conventions: entries = [(model, z, R), ...] or [(model, z, R, signature),

@@ -19,7 +19,9 @@ the gate in arrays of their own) as format 5, which has the arrays of format 4 (
 holds an 'append_model' edit (add_landmarks_model: one scan of new landmarks, idx empty, and per scan its entries -- model, z, R, signature
 -- in arrays of their own behind CSR offsets) as format 6, which has the arrays of format 5 (empty where there is nothing to hold); one
 that holds a 'predict_model' edit (predict_model: one chain of motion steps, idx empty, and per chain its steps -- model, u, M -- in arrays
-of their own behind CSR offsets) as format 7, which has the arrays of format 6 (empty where there is nothing to hold).
+of their own behind CSR offsets) as format 7, which has the arrays of format 6 (empty where there is nothing to hold); one that holds an
+'observe_model_iterated' edit (observe_model_iterated: an 'observe_model' edit's slots, and per observation the model, the anchor, the
+gate, iterations and tol in arrays of their own) as format 8, which has the arrays of format 7 (empty where there is nothing to hold).
 """
 import numpy as np
 
@@ -30,18 +32,21 @@ FORMAT_OBSERVE = "ekfslam-trajectory-4"
 FORMAT_MODEL = "ekfslam-trajectory-5"
 FORMAT_APPEND = "ekfslam-trajectory-6"
 FORMAT_PREDICT = "ekfslam-trajectory-7"
+FORMAT_ITERATED = "ekfslam-trajectory-8"
 EDIT_KINDS = ("remove", "constrain", "merge", "merge_batch")        # what record_edit takes
 OBSERVE = "observe"                                                  # the fifth kind: record_observation's, number 4 in a file
 OBSERVE_MODEL = "observe_model"                                      # the sixth kind: record_model_observation's, number 5 in a file
 APPEND_MODEL = "append_model"                                        # the seventh kind: record_model_append's, number 6 in a file
 PREDICT_MODEL = "predict_model"                                      # the eighth kind: record_model_predict's, number 7 in a file
-_KINDS = EDIT_KINDS + (OBSERVE, OBSERVE_MODEL, APPEND_MODEL, PREDICT_MODEL)
-_FORMATS = (FORMAT, FORMAT_EDITS, FORMAT_BATCH, FORMAT_OBSERVE, FORMAT_MODEL, FORMAT_APPEND, FORMAT_PREDICT)
+OBSERVE_MODEL_ITERATED = "observe_model_iterated"                    # the ninth kind: record_model_observation_iterated's, number 8 in a file
+_KINDS = EDIT_KINDS + (OBSERVE, OBSERVE_MODEL, APPEND_MODEL, PREDICT_MODEL, OBSERVE_MODEL_ITERATED)
+_FORMATS = (FORMAT, FORMAT_EDITS, FORMAT_BATCH, FORMAT_OBSERVE, FORMAT_MODEL, FORMAT_APPEND, FORMAT_PREDICT, FORMAT_ITERATED)
 _STEP_ARRAYS = ("u", "obs_ptr", "obs", "lm_ptr", "lm_index", "lm_loc")
 _EDIT_ARRAYS = ("edit_step", "edit_kind", "edit_ptr", "edit_idx", "edit_delta", "edit_R")
 _MODEL_ARRAYS = ("model_edit", "model_id", "model_anchor", "model_gate")
 _APPEND_ARRAYS = ("append_edit", "append_ptr", "append_model", "append_z", "append_R", "append_signature")
 _PREDICT_ARRAYS = ("predict_edit", "predict_ptr", "predict_model", "predict_u", "predict_M")
+_ITERATED_ARRAYS = ("iter_edit", "iter_model", "iter_anchor", "iter_gate", "iter_iterations", "iter_tol")
 _OBSERVE_ARRAYS = ("observe_edit", "observe_Hr", "observe_Hl", "observe_gate", "observe_wrap", "observe_rows")
 
 
@@ -52,6 +57,7 @@ class TrajectoryLog:
         self.model_observations = {}  # position in self.edits of an 'observe_model' edit -> {model, anchor (2) or None, gate}
         self.model_appends = {}     # position in self.edits of an 'append_model' edit -> [(model, z (2), R (2x2), signature), ...]
         self.model_predicts = {}    # position in self.edits of a 'predict_model' edit -> [(model, u (2 or 3), M (2x2 or 3x3)), ...]
+        self.model_iterations = {}  # position in self.edits of an 'observe_model_iterated' edit -> {model, anchor or None, gate, iterations, tol}
         self.observations = {}      # position in self.edits of an 'observe' edit -> {Hr (2x3), Hl (2x2x2), gate, wrap (2), rows}
 
     def __len__(self):
@@ -123,6 +129,23 @@ class TrajectoryLog:
         self.edits.append((len(self), OBSERVE_MODEL, lms.astype(np.int64), zv,
                            np.zeros((2, 2)) if R is None else np.asarray(R, dtype=np.float64).reshape(2, 2).copy()))
 
+    def record_model_observation_iterated(self, model, z, R, landmarks=(), anchor=None, gate=float("inf"), iterations=1, tol=0.0):
+        """A relinearised observation through a model (observe_model_iterated of ekf_slam_amd/slam.py) made now, i.e. after the len(self)
+        steps recorded so far: record_model_observation's arguments, then the number of linearisations and the stopping tolerance."""
+        lms = np.asarray(list(landmarks), dtype=np.float64).reshape(-1)
+        if not np.all(lms == np.floor(lms)):
+            raise ValueError("record_model_observation_iterated: landmark indices are whole numbers")
+        if lms.size > 2:
+            raise ValueError("record_model_observation_iterated: at most two landmarks")
+        zv = np.zeros(2)
+        zin = np.asarray(z, dtype=np.float64).reshape(-1)
+        zv[:zin.size] = zin
+        self.model_iterations[len(self.edits)] = dict(
+            model=int(model), anchor=None if anchor is None else np.asarray(anchor, dtype=np.float64).reshape(2).copy(), gate=float(gate),
+            iterations=int(iterations), tol=float(tol))
+        self.edits.append((len(self), OBSERVE_MODEL_ITERATED, lms.astype(np.int64), zv,
+                           np.zeros((2, 2)) if R is None else np.asarray(R, dtype=np.float64).reshape(2, 2).copy()))
+
     def record_model_append(self, entries):
         """One scan of new landmarks (add_landmarks_model of ekf_slam_amd/slam.py) made now, i.e. after the len(self) steps recorded so
         far: entries = [(model, z, R, signature), ...], at least one, as the wrapper hands them to the engine."""
@@ -161,7 +184,7 @@ class TrajectoryLog:
             return
         e_ptr, e_idx = ragged([e[2] for e in self.edits], 0)
         fmt = FORMAT_BATCH if any(e[1] == "merge_batch" for e in self.edits) else FORMAT_EDITS
-        if self.observations or self.model_observations or self.model_appends or self.model_predicts:
+        if self.observations or self.model_observations or self.model_appends or self.model_predicts or self.model_iterations:
             fmt = FORMAT_OBSERVE
             at = sorted(self.observations)
             ob = [self.observations[q] for q in at]
@@ -169,21 +192,21 @@ class TrajectoryLog:
                           observe_Hl=np.array([o["Hl"] for o in ob]).reshape(-1, 2, 2, 2), observe_gate=np.array([o["gate"] for o in ob]),
                           observe_wrap=np.array([o["wrap"] for o in ob], dtype=np.int64).reshape(-1, 2),
                           observe_rows=np.array([o["rows"] for o in ob], dtype=np.int64))
-        if self.model_observations or self.model_appends or self.model_predicts:
+        if self.model_observations or self.model_appends or self.model_predicts or self.model_iterations:
             fmt = FORMAT_MODEL
             at = sorted(self.model_observations)
             mo = [self.model_observations[q] for q in at]
             arrays.update(model_edit=np.array(at, dtype=np.int64), model_id=np.array([o["model"] for o in mo], dtype=np.int64),
                           model_anchor=np.array([np.full(2, np.nan) if o["anchor"] is None else o["anchor"] for o in mo]).reshape(-1, 2),
                           model_gate=np.array([o["gate"] for o in mo]))
-        if self.model_appends or self.model_predicts:
+        if self.model_appends or self.model_predicts or self.model_iterations:
             fmt = FORMAT_APPEND
             at = sorted(self.model_appends)
             ents = [e for q in at for e in self.model_appends[q]]
             arrays.update(append_edit=np.array(at, dtype=np.int64), append_ptr=np.cumsum([0] + [len(self.model_appends[q]) for q in at]),
                           append_model=np.array([e[0] for e in ents], dtype=np.int64), append_z=np.array([e[1] for e in ents]).reshape(-1, 2),
                           append_R=np.array([e[2] for e in ents]).reshape(-1, 2, 2), append_signature=np.array([e[3] for e in ents]))
-        if self.model_predicts:
+        if self.model_predicts or self.model_iterations:
             fmt = FORMAT_PREDICT
             at = sorted(self.model_predicts)
             sts = [e for q in at for e in self.model_predicts[q]]
@@ -193,6 +216,14 @@ class TrajectoryLog:
                 Mf[k, :u.size, :u.size] = M
             arrays.update(predict_edit=np.array(at, dtype=np.int64), predict_ptr=np.cumsum([0] + [len(self.model_predicts[q]) for q in at]),
                           predict_model=np.array([e[0] for e in sts], dtype=np.int64), predict_u=U, predict_M=Mf)
+        if self.model_iterations:
+            fmt = FORMAT_ITERATED
+            at = sorted(self.model_iterations)
+            mo = [self.model_iterations[q] for q in at]
+            arrays.update(iter_edit=np.array(at, dtype=np.int64), iter_model=np.array([o["model"] for o in mo], dtype=np.int64),
+                          iter_anchor=np.array([np.full(2, np.nan) if o["anchor"] is None else o["anchor"] for o in mo]).reshape(-1, 2),
+                          iter_gate=np.array([o["gate"] for o in mo]), iter_iterations=np.array([o["iterations"] for o in mo], dtype=np.int64),
+                          iter_tol=np.array([o["tol"] for o in mo]))
         np.savez_compressed(path, format=np.array(fmt), edit_step=np.array([e[0] for e in self.edits], dtype=np.int64),
                             edit_kind=np.array([_KINDS.index(e[1]) for e in self.edits], dtype=np.int64), edit_ptr=e_ptr,
                             edit_idx=e_idx.astype(np.int64), edit_delta=np.array([e[3] for e in self.edits]).reshape(-1, 2),
@@ -206,7 +237,7 @@ class TrajectoryLog:
             raise ValueError("not an %s file" % " / ".join(_FORMATS))
         ver = _FORMATS.index(fmt) + 1
         need = (_STEP_ARRAYS + (_EDIT_ARRAYS if ver >= 2 else ()) + (_OBSERVE_ARRAYS if ver >= 4 else ())
-                + (_MODEL_ARRAYS if ver >= 5 else ()) + (_APPEND_ARRAYS if ver >= 6 else ()) + (_PREDICT_ARRAYS if ver >= 7 else ()))
+                + (_MODEL_ARRAYS if ver >= 5 else ()) + (_APPEND_ARRAYS if ver >= 6 else ()) + (_PREDICT_ARRAYS if ver >= 7 else ()) + (_ITERATED_ARRAYS if ver >= 8 else ()))
         missing = [k for k in need if k not in g.files]
         if missing:
             raise ValueError("an %s file holds %s: %s is missing" % (fmt, ", ".join(need), ", ".join(missing)))
@@ -220,6 +251,11 @@ class TrajectoryLog:
                 a, b = g["edit_ptr"][q], g["edit_ptr"][q + 1]
                 t.edits.append((int(g["edit_step"][q]), _KINDS[int(g["edit_kind"][q])], g["edit_idx"][a:b].astype(np.int64),
                                 g["edit_delta"][q].copy(), g["edit_R"][q].copy()))
+        if ver >= 8:
+            for k, q in enumerate(g["iter_edit"]):
+                anchor = g["iter_anchor"][k].copy()
+                t.model_iterations[int(q)] = dict(model=int(g["iter_model"][k]), anchor=None if np.all(np.isnan(anchor)) else anchor,
+                                                  gate=float(g["iter_gate"][k]), iterations=int(g["iter_iterations"][k]), tol=float(g["iter_tol"][k]))
         if ver >= 7:
             from ._lib import EKF_MOTION_INPUTS
             for k, q in enumerate(g["predict_edit"]):
@@ -249,7 +285,7 @@ class TrajectoryLog:
     def replay(self, engine, start=0, stop=None):
         """predict + measure for steps [start, stop) on anything with predict(u) / measure(obs, u, idx, loc) -- an Engine.  The edits
         recorded at positions [start, stop) are applied in front of their step through the engine's remove_landmarks /
-        constrain_landmarks / merge_landmarks / merge_landmarks_batch / observe_linear / observe_model / append_model / predict_model (0-based there: the recorded 1-based numbers are converted here); the ones recorded
+        constrain_landmarks / merge_landmarks / merge_landmarks_batch / observe_linear / observe_model / observe_model_iterated / append_model / predict_model (0-based there: the recorded 1-based numbers are converted here); the ones recorded
         at position len(self), after the last step, when stop is the end of the log."""
         stop = len(self) if stop is None else stop
 
@@ -265,6 +301,10 @@ class TrajectoryLog:
                 elif kind == OBSERVE_MODEL:
                     o = self.model_observations[q]
                     engine.observe_model(o["model"], delta, R, idx0, anchor=o["anchor"], gate=o["gate"])
+                elif kind == OBSERVE_MODEL_ITERATED:
+                    o = self.model_iterations[q]
+                    engine.observe_model_iterated(o["model"], delta, R, idx0, anchor=o["anchor"], gate=o["gate"], iterations=o["iterations"],
+                                                  tol=o["tol"])
                 elif kind == APPEND_MODEL:
                     engine.append_model(self.model_appends[q])
                 elif kind == PREDICT_MODEL:

@@ -438,6 +438,37 @@ typedef struct ekf_model_obs {
 int32_t ekf_observe_model(ekf_handle *h, const ekf_model_obs *obs, ekf_linear_result *res /* NULL: do not wait */);
 int32_t ekf_model_innovation(ekf_handle *h, const ekf_model_obs *obs, ekf_linear_result *res /* required */);
 int32_t ekf_model_evaluate(int32_t model, const double xr[3], const double t0[2], const double t1[2], double hx[2], double H[14]);
+/* The same observation RELINEARISED: the iterated EKF update (IEKF), Gauss-Newton on the MAP cost
+ *     J(x) = (x - x0)' P^-1 (x - x0) + nu(x)' R^-1 nu(x),  nu(x) = z - h(x) (bearings wrapped).
+ * ekf_observe_model linearises h once, at the prior x0; where the prior is wide against the sensor (a new landmark, a heading known to
+ * ten degrees, a precise fix) that step lands off the mode.  Here the device repeats, over the seven entries xs = (robot, lm[0], lm[1])
+ * and their 7 x 7 covariance, up to `iterations` times (1 .. EKF_MODEL_ITER_MAX):
+ *     xi_0 = xs;  (h_i, H_i) at xi_i;  S_i = H_i P H_i' + R;  r_i = wrap(z - h_i) - H_i (xs - xi_i);  xi_{i+1} = xs + P H_i' S_i^-1 r_i
+ * and stops after the last one or where step = max_k |xi_{i+1}[k] - xi_i[k]| <= tol (tol = 0: all of them -- but a step of exactly 0,
+ * a model that is linear in effect, counts as converged and stops).  The LAST linearisation's H, S and r then make the one rank-2 pair of
+ * the step: K = P H' S^-1, x += K r, P -= K H P.  One launch counted under EKF_KERNEL_GATHER with the traffic of ekf_observe_model's, no
+ * flush, ekf_pending grows by one.  With iterations = 1 it writes ekf_observe_model's bits.
+ * The GATE is read at the first linearisation only: `first` is what ekf_model_innovation reports (its S, nu, d2), and a call is accepted
+ * or rejected exactly as it says; first->outcome is the call's.  A later iterate with no Jacobian (q = 0 or not finite) or an irregular S
+ * makes the whole call EKF_LINEAR_IRREGULAR: all or nothing, a finite no-op, counted once by ekf_linear_rejections, EKF_ERR_STATE with
+ * first != NULL.  With first == NULL nothing is waited for (and `it` must be NULL).
+ * it (may be NULL): S (column-major) and nu = r of the linearisation that made the pair; used = the linearisations whose step was taken
+ * (0: the first one did not apply; on a later irregular iterate, the ones before it, and S / nu are that iterate's); converged = the
+ * last step was <= tol; last_step; x_local = xi_used, the seven entries the pair leaves in x (absent landmarks: 0).
+ * Refusals: ekf_observe_model's, in its order, then iterations outside 1 .. EKF_MODEL_ITER_MAX or a NaN or negative tol
+ * (EKF_ERR_INVALID_ARG), then its rungs (unsharded, settled).
+ * ekf_model_innovation_iterated: the two records ekf_observe_model_iterated WOULD report, bit for bit, nothing changed.
+ * ekf_model_iterate is the loop the kernel runs, on the host (pure): sm = the 38 operands (Prr row-major 0..8 | the strip at lm[b]'s
+ * columns 9 + 6b + 2t + r | lm[b]'s own block (0,0) (1,0) (1,1) at 21 + 3b | the cross block 27 + 2r + c | the seven entries 31..37), R
+ * column-major 2 x 2 as the kernel sees it (a one-row model: [r, 0, 0, 1]), first required, it may be NULL. */
+#define EKF_MODEL_ITER_MAX 16
+typedef struct ekf_iterated_result { double S[4] /* column-major */; double nu[2]; int32_t used; int32_t converged; double last_step; double x_local[7]; } ekf_iterated_result;
+int32_t ekf_observe_model_iterated(ekf_handle *h, const ekf_model_obs *obs, int32_t iterations, double tol,
+                                   ekf_linear_result *first /* NULL: do not wait */, ekf_iterated_result *it /* may be NULL */);
+int32_t ekf_model_innovation_iterated(ekf_handle *h, const ekf_model_obs *obs, int32_t iterations, double tol,
+                                      ekf_linear_result *first /* required */, ekf_iterated_result *it /* may be NULL */);
+int32_t ekf_model_iterate(int32_t model, const double sm[38], const double anchor[2], int32_t has_landmark, const double z[2], const double R[4],
+                          double gate, int32_t iterations, double tol, ekf_linear_result *first, ekf_iterated_result *it);
 /* New landmarks under the SAME conventions: "a landmark that is not in the map yet was seen as z through the model, with noise covariance
  * R".  ekf_append keeps the reference's append (the position from the caller's table, Jacobians built from the motion input, no pi/180)
  * and is the inverse of none of the models above; a filter driven through ekf_observe_model starts its landmarks here.  Only the models

@@ -25,7 +25,8 @@
 /* The map-editing entry points (ekf_remove_landmarks; ekf_constrain_landmarks, ekf_merge_landmarks, ekf_landmark_distance;
  * ekf_nearest_landmarks; ekf_merge_landmarks_batch) the linear observation (ekf_observe_linear), the model observation
  * (ekf_observe_model), the append through a model (ekf_append_model), the association of a scan under the models' conventions
- * (ekf_associate_model), the joint compatibility of a scan's pairings (ekf_joint_innovation) and the motion steps under them (ekf_predict_model) are the ones this gateway can live without: bound weakly, so that the gateway still links against a libekfslam (or a stand-in) that
+ * (ekf_associate_model), the joint compatibility of a scan's pairings (ekf_joint_innovation), the relinearised model observation
+ * (ekf_observe_model_iterated) and the motion steps under them (ekf_predict_model) are the ones this gateway can live without: bound weakly, so that the gateway still links against a libekfslam (or a stand-in) that
  * predates them; their commands then raise a MATLAB error instead. */
 #if defined(__GNUC__)
 #pragma weak ekf_remove_landmarks
@@ -40,6 +41,7 @@
 #pragma weak ekf_associate_model
 #pragma weak ekf_predict_model
 #pragma weak ekf_joint_innovation
+#pragma weak ekf_observe_model_iterated
 #define HAVE_REMOVE_LANDMARKS (ekf_remove_landmarks != 0)
 #define HAVE_CONSTRAIN_LANDMARKS (ekf_constrain_landmarks != 0)
 #define HAVE_MERGE_LANDMARKS (ekf_merge_landmarks != 0)
@@ -52,6 +54,7 @@
 #define HAVE_ASSOCIATE_MODEL (ekf_associate_model != 0)
 #define HAVE_PREDICT_MODEL (ekf_predict_model != 0)
 #define HAVE_JOINT_INNOVATION (ekf_joint_innovation != 0)
+#define HAVE_OBSERVE_MODEL_ITERATED (ekf_observe_model_iterated != 0)
 #else
 #define HAVE_REMOVE_LANDMARKS 1
 #define HAVE_CONSTRAIN_LANDMARKS 1
@@ -65,6 +68,7 @@
 #define HAVE_ASSOCIATE_MODEL 1
 #define HAVE_PREDICT_MODEL 1
 #define HAVE_JOINT_INNOVATION 1
+#define HAVE_OBSERVE_MODEL_ITERATED 1
 #endif
 
 static void need(int nrhs, int want, const char *cmd) {
@@ -313,6 +317,47 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
             out[0] = res.nu[0]; out[1] = res.nu[1];
             for (int q = 0; q < 4; ++q) out[2 + q] = res.S[q];
             out[6] = res.d2; out[7] = (double)res.outcome;
+        }
+        return;
+    }
+    if (!strcmp(cmd, "observe_model_iterated")) { /* res = (h, model 1..5, z 2, R 2x2, lm 0..2 numbers (1-based), anchor [] or 2, gate, iterations 1..16, tol, wait):
+                                                     observe_model relinearised on the device; res (wait): observe_model's 8 values of the FIRST linearisation,
+                                                     then S(:)' nu(1) nu(2) used converged lastStep xLocal(1:7) of the one that made the pair */
+        ekf_model_obs o;
+        ekf_linear_result res;
+        ekf_iterated_result it;
+        need(nrhs, 11, cmd);
+        if (!HAVE_OBSERVE_MODEL_ITERATED) mexErrMsgIdAndTxt("ekfslam:usage", "observe_model_iterated: this libekfslam has no ekf_observe_model_iterated");
+        const double *z = two_of(prhs[3], cmd, "z"), *R = r2x2_of(prhs[4], cmd);
+        const mwSize k = prhs[5] ? mxGetNumberOfElements(prhs[5]) : 0, na = prhs[6] ? mxGetNumberOfElements(prhs[6]) : 0;
+        if (k > 2 || (k && (mxGetClassID(prhs[5]) != mxDOUBLE_CLASS || !mxGetPr(prhs[5]))))
+            mexErrMsgIdAndTxt("ekfslam:usage", "observe_model_iterated: lm names at most two landmarks, class double");
+        if (!((na == 2 && k == 0 && mxGetPr(prhs[6])) || (na == 0 && k > 0)))
+            mexErrMsgIdAndTxt("ekfslam:usage", "observe_model_iterated: the target is a landmark (anchor empty) or an anchor of 2 elements (lm empty)");
+        o.model = (int32_t)mxGetScalar(prhs[2]); o.reserved = 0;
+        for (int r = 0; r < 2; ++r) { o.z[r] = z[r]; o.lm[r] = -1; o.anchor[r] = na ? mxGetPr(prhs[6])[r] : 0.0; }
+        for (int q = 0; q < 4; ++q) o.R[q] = R[q];
+        for (mwSize b = 0; b < k; ++b) {                       /* whole numbers a landmark could carry; 1-based -> 0-based, once */
+            const double v = mxGetPr(prhs[5])[b];
+            if (!(v >= -9.0e15 && v <= 9.0e15) || v != (double)(int64_t)v) mexErrMsgIdAndTxt("ekfslam:usage", "observe_model_iterated: landmark numbers are whole numbers");
+            o.lm[b] = (int64_t)v - 1;
+        }
+        o.gate = mxGetScalar(prhs[7]);
+        const double n = mxGetScalar(prhs[8]);
+        if (!(n >= 1.0 && n <= (double)EKF_MODEL_ITER_MAX) || n != (double)(int32_t)n)
+            mexErrMsgIdAndTxt("ekfslam:usage", "observe_model_iterated: iterations is a whole number, 1 .. %d", EKF_MODEL_ITER_MAX);
+        const double tol = mxGetScalar(prhs[9]);
+        const int wait = mxGetScalar(prhs[10]) != 0.0;
+        check(h, ekf_observe_model_iterated(h, &o, (int32_t)n, tol, wait ? &res : NULL, wait ? &it : NULL));
+        plhs[0] = mxCreateDoubleMatrix(wait ? 1 : 0, wait ? 24 : 0, mxREAL);
+        if (wait) {
+            double *out = mxGetPr(plhs[0]);
+            out[0] = res.nu[0]; out[1] = res.nu[1];
+            for (int q = 0; q < 4; ++q) { out[2 + q] = res.S[q]; out[8 + q] = it.S[q]; }
+            out[6] = res.d2; out[7] = (double)res.outcome;
+            out[12] = it.nu[0]; out[13] = it.nu[1];
+            out[14] = (double)it.used; out[15] = (double)it.converged; out[16] = it.last_step;
+            for (int q = 0; q < 7; ++q) out[17 + q] = it.x_local[q];
         }
         return;
     }
