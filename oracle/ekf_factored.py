@@ -18,6 +18,11 @@ and every read the reference makes of P -- the five rows and five columns S = {1
 robot block and the column strip P(k, 1:3) of an append (:91-96), each landmark's 5 x 5 sub-block of an association
 (Correspondence.m:66) -- is evaluated from that form in F64.  Cost per step O(n (k + 2 t)) instead of O(n^3).
 
+Beyond the reference's predict / append / correct it has the three generic forms the newer families reduce to, in the same
+representation: update_linear (a Kalman update-step with a given H over the robot and up to two landmarks, one or two rows),
+append_jacobian (an append with given Gx, Gz) and predict_affine (a motion step with a given F and additive noise); pinned to the dense
+forms of tests/*_cases.py at N <= 200 to 1e-11 (tests/test_oracle_factored.py).
+
 One association differs from the dense evaluation: (eye(n) - K H) P is formed as P - K (H P) (as oracle/ekf_structured.c and the HIP
 path do); entry by entry the two differ in the last bits of the update.
 
@@ -291,6 +296,81 @@ class FactoredEKF:
         Rm[2 * t:2 * t + 2, :m] = Gm
         Rm[2 * t:2 * t + 2, m:] = 0.0
         self.nt = t + 1
+
+    # ---- the generic forms the newer update-step, append and motion families reduce to (include/ekfslam.h), in the same representation ----
+    def update_linear(self, Hr, landmarks, Hl, nu, R):
+        """One Kalman update-step with a GIVEN Jacobian: H = the r x 3 block Hr on the robot state plus one r x 2 block Hl[b] on each of
+        up to two landmarks (0-based), r = 1 or 2; nu (r) the innovation, R (r x r) its noise.  G = H P from the rows of P, S = G H' + R,
+        K = P H' S^-1 from the columns, x += K nu, P -= K G: `correct` with the linearisation handed in.  One term is added; a one-row
+        step leaves the term's second row zero.  Returns S."""
+        nu = np.asarray(nu, float).reshape(-1)
+        r = nu.size
+        assert r in (1, 2) and len(landmarks) == len(Hl) <= 2
+        Hr = np.asarray(Hr, float).reshape(r, 3)
+        R = np.asarray(R, float).reshape(r, r)
+        m = self.m
+        js = [2 * int(k) for k in landmarks]
+        Hl = [np.asarray(b, float).reshape(r, 2) for b in Hl]
+        assert all(0 <= j < m for j in js)
+        Gr, Gm = Hr @ self.Prr, Hr @ self.Prm[:, :m]                    # G = H P  (r x n)
+        PHr, PHm = self.Prr @ Hr.T, self.Pmr[:m] @ Hr.T                 # P H'     (n x r)
+        for j, B in zip(js, Hl):
+            Gr = Gr + B @ self.Pmr[j:j + 2]
+            Gm = Gm + B @ self.Pmm_rows(j)
+            PHr = PHr + self.Prm[:, j:j + 2] @ B.T
+            PHm = PHm + self.Pmm_cols(j) @ B.T
+        S = Gr @ Hr.T + R
+        for j, B in zip(js, Hl):
+            S = S + Gm[:, j:j + 2] @ B.T
+        Si = np.linalg.inv(S)
+        Kr, Km = PHr @ Si, PHm @ Si
+        self.x = self.x + np.concatenate([Kr @ nu, Km @ nu])
+        self.Prr = self.Prr - Kr @ Gr
+        self.Prm[:, :m] = self.Prm[:, :m] - Kr @ Gm
+        self.Pmr[:m] = self.Pmr[:m] - Km @ Gr
+        Lm, Rm = self._terms()
+        t = self.nt
+        assert t < self.tmax, "FactoredEKF: max_terms corrections reached"
+        Lm[:, 2 * t:2 * t + 2] = 0.0
+        Rm[2 * t:2 * t + 2, :] = 0.0
+        Lm[:m, 2 * t:2 * t + r] = -Km
+        Rm[2 * t:2 * t + r, :m] = Gm
+        self.nt = t + 1
+        return S
+
+    def append_jacobian(self, Gx, Gz, R, landmarkPos, signature):
+        """A landmark appended with GIVEN Jacobians of its position: Gx (2 x 3) over the robot state, Gz (2 x 2) over the observation of
+        noise R.  Own block Gx Prr Gx' + Gz R Gz', row panel Gx P(r, old), strips Gx Prr and its mirror: `append` with the reference's
+        jxr / jz handed in.  The landmarks of one scan are m calls in order at the same robot state: a later one's panel then reaches
+        over the earlier ones' columns (Gx_b Prr Gx_a')."""
+        assert self.N < self.cap
+        Gx, Gz, R = np.asarray(Gx, float).reshape(2, 3), np.asarray(Gz, float).reshape(2, 2), np.asarray(R, float).reshape(2, 2)
+        self.s.append(signature)
+        m = self.m
+        self.x = np.concatenate([self.x, [landmarkPos[0], landmarkPos[1]]])
+        if self.RP is None:
+            self.RP = np.zeros((2 * self.amax, 2 * self.cap))
+        a = len(self.ma)
+        assert a < self.amax
+        self.RP[2 * a:2 * a + 2, :m] = Gx @ self.Prm[:, :m]
+        self.Prm[:, m:m + 2] = self.Prr @ Gx.T
+        self.Pmr[m:m + 2, :] = Gx @ self.Prr
+        self.Ca.append(Gx @ self.Prr @ Gx.T + Gz @ R @ Gz.T)
+        self.ma.append(m)
+        self.N += 1
+
+    def predict_affine(self, F, Q, pose):
+        """A motion step with a GIVEN Jacobian F (3 x 3) over the robot state, additive noise Q (3 x 3) and new pose: Prr = F Prr F' + Q
+        and both strips, as `predict` does with the reference's F."""
+        F, Q = np.asarray(F, float).reshape(3, 3), np.asarray(Q, float).reshape(3, 3)
+        m = self.m
+        self.Prr = F @ self.Prr @ F.T + Q
+        self.Prm[:, :m] = F @ self.Prm[:, :m]
+        self.Pmr[:m] = self.Pmr[:m] @ F.T
+        self.Q = Q
+        x = self.x.copy()
+        x[:3] = np.asarray(pose, float).reshape(3)
+        self.x = x
 
     # ---- Correspondence.m:28-88 --------------------------------------------------------------------------------------------------------
     def estimateCorrespondence(self, z, R):
