@@ -113,12 +113,17 @@ def same_npz(a, b):
 # ------------------------------------------------------------------------------------------------------------------
 # host builds of kernel source.  -mfma and -ffp-contract=off decide the bits that the "chain against singles, bit for bit" tests compare.
 # ------------------------------------------------------------------------------------------------------------------
-GXX_HOST = ["g++", "-O2", "-mfma", "-ffp-contract=off", "-std=c++17", "-I", os.path.join(ROOT, "ekf_slam_amd", "csrc")]
+GXX = ["g++", "-std=c++17", "-I", os.path.join(ROOT, "ekf_slam_amd", "csrc")]
+GXX_HOST = GXX + ["-O2", "-mfma", "-ffp-contract=off"]
 
 
-def host_build(source_name, exe):
-    """tests/support/<source_name>.cpp built for the host as the program exe."""
-    subprocess.run(GXX_HOST + [os.path.join(ROOT, "tests", "support", source_name + ".cpp"), "-o", exe], check=True)
+def host_build(source_name, exe, flags=None):
+    """tests/support/<source_name>.cpp built for the host as the program exe, with GXX_HOST -- or, for a build that has to name its own
+    (a sanitizer build), with flags in place of GXX_HOST's -O2 -mfma -ffp-contract=off.  A failed build raises with the end of the
+    compiler's stderr."""
+    source = os.path.join(ROOT, "tests", "support", source_name + ".cpp")
+    r = subprocess.run((GXX_HOST if flags is None else GXX + list(flags)) + [source, "-o", exe], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-4000:]
     return exe
 
 

@@ -23,99 +23,27 @@ void predict_small(const double pose[3], const double prr_in[9], double u0, doub
 void predict_strip(double &s0, double &s1, double s2, double fa, double fb);
 void reduce_partials_wave(const AssocHostPartial *parts, int nblk, int seq, int lane, double &ll, int &ix);
 void store_partial(AssocHostPartial *dst, double ll, int index, int seq);
-#include "tile_access.h"
+#include "emulated_state.h"
 #include "append.h"
 #include "append_model.h"
-#include "pair_column.h"
-#include "constrain.h"
-#include "linear_obs.h"
 
 // k_append_model: every workgroup twice -- the first run leaves t, dg/dtheta and Gz R Gz' of every entry in the shared storage, the second
-// one is the launch (it rewrites every slot the first one wrote; no lane reads a slot the launch writes)
-template <typename F> static void launch_wg2(int grid, F body) {
-    for (int b = 0; b < grid; ++b)
-        for (int pass = 0; pass < 2; ++pass)
-            for (int t = 0; t < kBlock; ++t) { blockIdx.x = b; threadIdx.x = t; body(); }
-}
-
-template <typename TS> struct Store {
-    int T, N, ldm, nt_cap, cap; TileMap tm; int64_t slots;
-    std::vector<double> x[2], prr[2], strip[2], diag[2], ring, s; std::vector<TS> tiles; int cur = 0, dcur = 0;
-    DevState st;
-    Store(int T_, int N_, int cap_) : T(T_), N(N_), cap(cap_) {
-        tm = ekf_make_tilemap(T, 1, 0); nt_cap = (int)ekf_tiles_for(2 * cap, T); ldm = nt_cap * T; slots = tm.row_base(nt_cap);
-        for (int b = 0; b < 2; ++b) { x[b].assign(3 + ldm, 0); prr[b].assign(16, 0); strip[b].assign(3 * ldm, 0); diag[b].assign(3 * cap, 0); }
-        tiles.assign(slots * T * T, 0); ring.assign((size_t)2 * ldm * 8 * 2, 0); s.assign(cap, 0);
-        sync();
-    }
-    Store(const Store &o) = default;
-    void sync() {
-        for (int b = 0; b < 2; ++b) { st.x[b] = x[b].data(); st.prr[b] = prr[b].data(); st.strip[b] = strip[b].data(); st.diag[b] = diag[b].data(); }
-        st.tiles = tiles.data(); st.s = s.data(); st.Gp = ring.data(); st.Kp = ring.data() + (size_t)2 * ldm * 8; st.Gp32 = st.Kp32 = nullptr;
-        st.pair_stride = 2 * ldm; st.pcap = 8; st.small = nullptr; st.ldm = ldm; st.tm = tm; st.dcur = dcur;
-    }
-    TS &tile(int64_t r, int64_t c) { return tiles[tm.tile_offset(r >> tm.shift, c >> tm.shift) + ((r & (T - 1)) << tm.shift) + (c & (T - 1))]; }
-    void flip() { cur ^= 1; dcur ^= 1; sync(); }
-    // live P(3 + r, 3 + c), r >= c, of the landmark block: the own blocks from the F64 copies, everything else the tile with the
-    // `pending` pairs of ring slots 0 .. applied in slot order (rows that did not exist when a pair was formed have K = 0)
-    double live(int64_t r, int64_t c, int pending) {
-        if ((r >> 1) == (c >> 1)) return diag[dcur][3 * (r >> 1) + (r & 1) + (c & 1)];
-        double v = (double)tile(r, c);
-        for (int i = 0; i < pending; ++i) {
-            const double *G = st.Gp + (size_t)i * st.pair_stride, *K = st.Kp + (size_t)i * st.pair_stride;
-            v = rank2_apply(v, make_double2(K[2 * r], K[2 * r + 1]), make_double2(G[2 * c], G[2 * c + 1]));
-        }
-        return v;
-    }
-};
-static double rnd() { return (rand() % 20001 - 10000) / 10000.0; }
-template <typename TS> static void fill(Store<TS> &S) {            // P = D + U U' (k = 3), x random; tiles, strip, prr, diag consistent
-    srand(11);
-    const int n = 3 + 2 * S.N;
-    std::vector<double> U(n * 3), d(n);
-    for (auto &v : U) v = 0.3 * rnd();
-    for (auto &v : d) v = 0.1 + 0.05 * (rnd() + 1);
-    auto P = [&](int r, int c) { double v = r == c ? d[r] : 0; for (int k = 0; k < 3; ++k) v += U[r * 3 + k] * U[c * 3 + k]; return v; };
-    for (int i = 0; i < n; ++i) S.x[0][i] = 20 * rnd();
-    S.x[0][2] = 137.0 + 40 * rnd();
-    for (int k = 0; k < S.N; ++k) S.s[k] = k + 1.0;
-    for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) S.prr[0][3 * r + c] = P(r > c ? r : c, r > c ? c : r);
-    for (int r = 0; r < 3; ++r) for (int c = 0; c < 2 * S.N; ++c) S.strip[0][r * S.ldm + c] = P(3 + c, r);
-    for (int r = 0; r < 2 * S.N; ++r) for (int c = 0; c < 2 * S.N; ++c) {
-        const bool diag = (r / S.T) == (c / S.T);
-        if (c > r && !diag) continue;
-        S.tile(r, c) = (TS)P(3 + (r > c ? r : c), 3 + (r > c ? c : r));
-    }
-    for (int k = 0; k < S.N; ++k) { S.diag[0][3 * k] = P(3 + 2 * k, 3 + 2 * k); S.diag[0][3 * k + 1] = P(4 + 2 * k, 3 + 2 * k); S.diag[0][3 * k + 2] = P(4 + 2 * k, 4 + 2 * k); }
-}
-template <typename TS> static void run_linear(Store<TS> &S, LinearArgs a, double *rec, int64_t *cnt) {
-    a.n_mm = 2 * S.N; a.cur = S.cur; a.pstart = 0;
-    DevState st = S.st;
-    launch_wg3((int)((S.tm.padded(2 * S.N) + kBlock - 1) / kBlock), cnt, [&] { k_gather_linear<TS>(st, a, rec, cnt); });
-    S.flip();
-}
+// one is the launch (it rewrites every slot the first one wrote; no lane reads a slot the launch writes); no lane exchange
 template <typename TS> static void run_append(Store<TS> &S, const AppendModelEntry *e, int m) {
     AppendModelArgs a = {};
     a.N = S.N; a.m = m; a.cur = S.cur;
     for (int b = 0; b < m; ++b) a.e[b] = e[b];
     DevState st = S.st;
-    launch_wg2((2 * (S.N + m) + kBlock - 1) / kBlock, [&] { k_append_model<TS>(st, a); });
+    launch_wg((2 * (S.N + m) + kBlock - 1) / kBlock, { 2, -1 }, [&] { k_append_model<TS>(st, a); });
     S.N += m;
 }
-template <typename V> static int differ(const std::vector<V> &u, const std::vector<V> &v, const char *what) {
-    int b = 0;
-    for (size_t i = 0; i < u.size(); ++i) if (memcmp(&u[i], &v[i], sizeof(V))) ++b;
-    if (b) printf("  %s: %d differ\n", what, b);
-    return b;
-}
-static void put(FILE *f, const std::vector<double> &v) { fwrite(v.data(), 8, v.size(), f); }
 
 template <typename TS> static int run_cases(const char *ts, const std::string &dir) {
     int total_bad = 0;
     for (int T : { 16, 64 }) for (int pending : { 0, 3 }) {
         const int N = 123, cap = 136;
         Store<TS> base(T, N, cap);
-        fill(base);
+        fill(base, 11, true);
         int64_t cnt0[2] = { 0, 0 };
         double rec0[8];
         for (int k = 0; k < pending; ++k) {                   // some pairs pending in the ring (never applied to the tiles)
@@ -150,9 +78,9 @@ template <typename TS> static int run_cases(const char *ts, const std::string &d
             if (!f) return 1000;
             const double hdr[1] = { (double)n0 };
             fwrite(hdr, 8, 1, f);
-            put(f, std::vector<double>(base.x[base.cur].begin(), base.x[base.cur].begin() + n0));
-            put(f, std::vector<double>(base.s.begin(), base.s.begin() + N));
-            put(f, P);
+            put(f, base.x[base.cur].data(), n0);
+            put(f, base.s.data(), N);
+            put(f, P.data(), P.size());
             fclose(f);
         }
         for (int m : { 1, 3, 9 }) {
@@ -191,10 +119,10 @@ template <typename TS> static int run_cases(const char *ts, const std::string &d
             }
             FILE *f = fopen((dir + "/after_" + ts + "_" + std::to_string(T) + "_" + std::to_string(pending) + "_" + std::to_string(m) + ".bin").c_str(), "wb");
             if (!f) return 1000;
-            put(f, ent);
-            put(f, std::vector<double>(A.x[A.cur].begin() + n0, A.x[A.cur].begin() + n1));
-            put(f, std::vector<double>(A.s.begin() + N, A.s.begin() + N + m));
-            put(f, rows);
+            put(f, ent.data(), ent.size());
+            put(f, A.x[A.cur].data() + n0, n1 - n0);
+            put(f, A.s.data() + N, m);
+            put(f, rows.data(), rows.size());
             fclose(f);
             printf("%s T=%d pending=%d m=%d: %d differences\n", ts, T, pending, m, bad);
             total_bad += bad;

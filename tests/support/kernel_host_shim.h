@@ -1,8 +1,8 @@
 // The shim behind which the host emulations of tests/support compile the kernel SOURCES of ekf_slam_amd/csrc with g++ (no GPU, no HIP
 // runtime): the HIP keywords as empty macros, the vector types the kernels name, thread indices as globals, __shared__ as static storage,
 // lane_xor1 in two passes.  The state and the argument blocks are the kernels' own: kernel_args.h needs no HIP header.
-// Each emulation runs a workgroup's lanes one after another and the whole workgroup again until what its first lanes leave in the shared
-// storage is there (its own launch_wg*), so __syncthreads is empty.
+// An emulation runs a workgroup's lanes one after another and the whole workgroup again until what its first lanes leave in the shared
+// storage is there (launch_wg of emulated_state.h, which also holds the state the kernels run on), so __syncthreads is empty.
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -36,18 +36,3 @@ template <> struct Lane16<double> { using type = double2; static constexpr int k
 template <> struct Lane16<float>  { using type = float4;  static constexpr int kCols = 4; };
 static inline void lane16_pack(const double *v, double2 &t) { t.x = v[0]; t.y = v[1]; }
 static inline void lane16_pack(const double *v, float4 &t) { t.x = (float)v[0]; t.y = (float)v[1]; t.z = (float)v[2]; t.w = (float)v[3]; }
-
-// k_gather_linear / k_gather_model: every workgroup three times -- the first pass leaves the small part's operands in the shared storage, the
-// second one has lane 0 form the shared solve (and a model's H) from them and records what lane_xor1 hands over, the third one is the
-// launch; what the earlier passes counted in cnt is dropped
-template <typename F> static void launch_wg3(int grid, int64_t *cnt, F body) {
-    for (int b = 0; b < grid; ++b) {
-        const int64_t c0 = cnt[0], c1 = cnt[1];
-        for (int pass = 0; pass < 3; ++pass) {
-            xor_pass = pass == 2;
-            if (pass < 2) for (int t = 0; t < kBlock; ++t) { xor_rec[t].clear(); xor_pos[t] = 0; }
-            cnt[0] = c0; cnt[1] = c1;
-            for (int t = 0; t < kBlock; ++t) { blockIdx.x = b; threadIdx.x = t; body(); }
-        }
-    }
-}

@@ -14,41 +14,9 @@
 #include <string>
 #include <vector>
 #include "kernel_host_shim.h"
-#include "tile_access.h"
-#include "pair_column.h"
-#include "constrain.h"
-#include "linear_obs.h"
+#include "emulated_state.h"
 #include "model_obs.h"
 #include "model_iter.h"
-
-struct Store {
-    int T, N, ldm, nt_cap; TileMap tm; int64_t slots;
-    std::vector<double> x[2], prr[2], strip[2], diag[2], ring, tiles; int cur = 0, dcur = 0;
-    DevState st;
-    Store(int T_, int N_, int cap) : T(T_), N(N_) {
-        tm = ekf_make_tilemap(T, 1, 0); nt_cap = (int)ekf_tiles_for(2 * cap, T); ldm = nt_cap * T; slots = tm.row_base(nt_cap);
-        for (int b = 0; b < 2; ++b) { x[b].assign(3 + ldm, 0); prr[b].assign(16, 0); strip[b].assign(3 * ldm, 0); diag[b].assign(3 * cap, 0); }
-        tiles.assign(slots * T * T, 0); ring.assign((size_t)2 * ldm * 8 * 2, 0);
-        sync();
-    }
-    Store(const Store &o) = default;
-    void sync() {
-        st = DevState();
-        for (int b = 0; b < 2; ++b) { st.x[b] = x[b].data(); st.prr[b] = prr[b].data(); st.strip[b] = strip[b].data(); st.diag[b] = diag[b].data(); }
-        st.tiles = tiles.data(); st.s = nullptr; st.Gp = ring.data(); st.Kp = ring.data() + (size_t)2 * ldm * 8; st.Gp32 = st.Kp32 = nullptr;
-        st.pair_stride = 2 * ldm; st.pcap = 8; st.small = nullptr; st.ldm = ldm; st.tm = tm; st.dcur = dcur;
-    }
-    double &tile(int64_t r, int64_t c) { return tiles[tm.tile_offset(r >> tm.shift, c >> tm.shift) + ((r & (T - 1)) << tm.shift) + (c & (T - 1))]; }
-    void flip() { cur ^= 1; dcur ^= 1; sync(); }
-    int grid() const { const int g = (int)((tm.padded(2 * N) + kBlock - 1) / kBlock); return g > 0 ? g : 1; }
-};
-static int differ(const std::vector<double> &u, const std::vector<double> &v, const char *what) {
-    int b = 0;
-    for (size_t i = 0; i < u.size(); ++i) if (memcmp(&u[i], &v[i], 8)) ++b;
-    if (b) printf("  %s: %d differ\n", what, b);
-    return b;
-}
-static void put(FILE *f, const double *v, size_t n) { fwrite(v, 8, n, f); }
 
 int main(int argc, char **argv) {
     if (argc < 2) return 2;
@@ -68,14 +36,7 @@ int main(int argc, char **argv) {
     auto P = [&](int r, int c) { return Pd[(size_t)r * n + c]; };
     Store base(T, N, N + 2);
     for (int i = 0; i < n; ++i) base.x[0][i] = x0[i];
-    for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) base.prr[0][3 * r + c] = P(r > c ? r : c, r > c ? c : r);
-    for (int r = 0; r < 3; ++r) for (int c = 0; c < 2 * N; ++c) base.strip[0][r * base.ldm + c] = P(3 + c, r);
-    for (int r = 0; r < 2 * N; ++r) for (int c = 0; c < 2 * N; ++c) {
-        const bool diag = (r / T) == (c / T);
-        if (c > r && !diag) continue;
-        base.tile(r, c) = P(3 + (r > c ? r : c), 3 + (r > c ? c : r));
-    }
-    for (int k = 0; k < N; ++k) { base.diag[0][3 * k] = P(3 + 2 * k, 3 + 2 * k); base.diag[0][3 * k + 1] = P(4 + 2 * k, 3 + 2 * k); base.diag[0][3 * k + 2] = P(4 + 2 * k, 4 + 2 * k); }
+    scatter(base, P);
     const int ncases = (int)raw[at++];
     int total_bad = 0;
     for (int k = 0; k < ncases; ++k) {
@@ -91,15 +52,15 @@ int main(int argc, char **argv) {
         double recA[8], itA[16], recP[8], itP[16], recB[8];
         int64_t cntA[2] = { 0, 0 }, cntB[2] = { 0, 0 };
         DevState stA = A.st, stB = B.st;
-        for (int pass = 0; pass < 2; ++pass)
-            for (int t = 0; t < 64; ++t) { blockIdx.x = 0; threadIdx.x = t; k_model_iter_probe<double>(stA, m, recP, itP); }
-        launch_wg3(A.grid(), cntA, [&] { k_gather_model_iter<double>(stA, m, recA, cntA, itA); });
+        // the probe: one workgroup of 64 lanes twice (pass 0: the operands), no lane exchange; the launches: run_linear's three passes
+        launch_wg(1, { 2, -1, nullptr, 64 }, [&] { k_model_iter_probe<double>(stA, m, recP, itP); });
+        launch_wg(A.grid(), { 3, 2, cntA }, [&] { k_gather_model_iter<double>(stA, m, recA, cntA, itA); });
         A.flip();
         int bad = 0;
         if (memcmp(recA, recP, sizeof recA) || memcmp(itA, itP, sizeof itA)) { printf("  the probe's records differ from the launch's\n"); ++bad; }
         if (m.iterations == 1) {
             const ModelArgs &plain = m;
-            launch_wg3(B.grid(), cntB, [&] { k_gather_model<double>(stB, plain, recB, cntB); });
+            launch_wg(B.grid(), { 3, 2, cntB }, [&] { k_gather_model<double>(stB, plain, recB, cntB); });
             B.flip();
             if (memcmp(recA, recB, sizeof recA)) { printf("  the record differs from k_gather_model's\n"); ++bad; }
             if (cntA[0] != cntB[0] || cntA[1] != cntB[1]) { printf("  the counters differ\n"); ++bad; }

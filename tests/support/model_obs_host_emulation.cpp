@@ -13,63 +13,8 @@
 #include <cstring>
 #include <vector>
 #include "kernel_host_shim.h"
-#include "tile_access.h"
-#include "pair_column.h"
-#include "constrain.h"
-#include "linear_obs.h"
+#include "emulated_state.h"
 #include "model_obs.h"
-
-struct Store {
-    int T, N, ldm, nt_cap; TileMap tm; int64_t slots;
-    std::vector<double> x[2], prr[2], strip[2], diag[2], ring, tiles; int cur = 0, dcur = 0;
-    DevState st;
-    Store(int T_, int N_, int cap) : T(T_), N(N_) {
-        tm = ekf_make_tilemap(T, 1, 0); nt_cap = (int)ekf_tiles_for(2 * cap, T); ldm = nt_cap * T; slots = tm.row_base(nt_cap);
-        for (int b = 0; b < 2; ++b) { x[b].assign(3 + ldm, 0); prr[b].assign(16, 0); strip[b].assign(3 * ldm, 0); diag[b].assign(3 * cap, 0); }
-        tiles.assign(slots * T * T, 0); ring.assign((size_t)2 * ldm * 8 * 2, 0);
-        sync();
-    }
-    Store(const Store &o) = default;
-    void sync() {
-        for (int b = 0; b < 2; ++b) { st.x[b] = x[b].data(); st.prr[b] = prr[b].data(); st.strip[b] = strip[b].data(); st.diag[b] = diag[b].data(); }
-        st.tiles = tiles.data(); st.s = nullptr; st.Gp = ring.data(); st.Kp = ring.data() + (size_t)2 * ldm * 8; st.Gp32 = st.Kp32 = nullptr;
-        st.pair_stride = 2 * ldm; st.pcap = 8; st.small = nullptr; st.ldm = ldm; st.tm = tm; st.dcur = dcur;
-    }
-    double &tile(int64_t r, int64_t c) { return tiles[tm.tile_offset(r >> tm.shift, c >> tm.shift) + ((r & (T - 1)) << tm.shift) + (c & (T - 1))]; }
-    void flip() { cur ^= 1; dcur ^= 1; sync(); }
-    int grid() const { return (int)((tm.padded(2 * N) + kBlock - 1) / kBlock); }
-};
-static double rnd() { return (rand() % 20001 - 10000) / 10000.0; }
-static void fill(Store &S) {            // P = D + U U' (k = 3), x random; tiles, strip, prr, diag consistent
-    srand(11);
-    const int n = 3 + 2 * S.N;
-    std::vector<double> U(n * 3), d(n);
-    for (auto &v : U) v = 0.3 * rnd();
-    for (auto &v : d) v = 0.1 + 0.05 * (rnd() + 1);
-    auto P = [&](int r, int c) { double v = r == c ? d[r] : 0; for (int k = 0; k < 3; ++k) v += U[r * 3 + k] * U[c * 3 + k]; return v; };
-    for (int i = 0; i < n; ++i) S.x[0][i] = 20 * rnd();
-    S.x[0][2] = 137.0 + 40 * rnd();
-    for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) S.prr[0][3 * r + c] = P(r > c ? r : c, r > c ? c : r);
-    for (int r = 0; r < 3; ++r) for (int c = 0; c < 2 * S.N; ++c) S.strip[0][r * S.ldm + c] = P(3 + c, r);
-    for (int r = 0; r < 2 * S.N; ++r) for (int c = 0; c < 2 * S.N; ++c) {
-        const bool diag = (r / S.T) == (c / S.T);
-        if (c > r && !diag) continue;
-        S.tile(r, c) = P(3 + (r > c ? r : c), 3 + (r > c ? c : r));
-    }
-    for (int k = 0; k < S.N; ++k) { S.diag[0][3 * k] = P(3 + 2 * k, 3 + 2 * k); S.diag[0][3 * k + 1] = P(4 + 2 * k, 3 + 2 * k); S.diag[0][3 * k + 2] = P(4 + 2 * k, 4 + 2 * k); }
-}
-static void run_linear(Store &S, LinearArgs a, double *rec, int64_t *cnt) {
-    a.n_mm = 2 * S.N; a.cur = S.cur; a.pstart = 0;
-    DevState st = S.st;
-    launch_wg3(S.grid(), cnt, [&] { k_gather_linear<double>(st, a, rec, cnt); });
-    S.flip();
-}
-static int differ(const std::vector<double> &u, const std::vector<double> &v, const char *what) {
-    int b = 0;
-    for (size_t i = 0; i < u.size(); ++i) if (memcmp(&u[i], &v[i], 8)) ++b;
-    if (b) printf("  %s: %d differ\n", what, b);
-    return b;
-}
 
 int main() {
     const double RP[4] = { 0.02, 0.005, 0.005, 0.03 };
@@ -78,7 +23,7 @@ int main() {
     for (int T : { 16, 64 }) for (int pending : { 0, 3 }) {
         const int N = 150, cap = 158, e = T == 16 ? 72 : 64;
         Store base(T, N, cap);
-        fill(base);
+        fill(base, 11, true);
         int64_t cnt0[2] = { 0, 0 };
         double rec0[8];
         for (int k = 0; k < pending; ++k) {                   // some pairs pending in the ring (never applied to the tiles)
@@ -123,9 +68,9 @@ int main() {
             double recA[8], recP[8], recB[8];
             int64_t cntA[2] = { 0, 0 }, cntB[2] = { 0, 0 };
             DevState stA = A.st;
-            for (int t = 0; t < 64; ++t) { blockIdx.x = 0; threadIdx.x = t; k_model_probe<double>(stA, m, recP); }      // (pass 0: the operands)
-            for (int t = 0; t < 64; ++t) { blockIdx.x = 0; threadIdx.x = t; k_model_probe<double>(stA, m, recP); }
-            launch_wg3(A.grid(), cntA, [&] { k_gather_model<double>(stA, m, recA, cntA); });
+            // the probe: one workgroup of 64 lanes twice (pass 0: the operands), no lane exchange; the launch: run_linear's three passes
+            launch_wg(1, { 2, -1, nullptr, 64 }, [&] { k_model_probe<double>(stA, m, recP); });
+            launch_wg(A.grid(), { 3, 2, cntA }, [&] { k_gather_model<double>(stA, m, recA, cntA); });
             A.flip();
             int bad = 0;
             if (memcmp(recA, recP, sizeof recA)) { printf("  the probe's record differs from the launch's\n"); ++bad; }

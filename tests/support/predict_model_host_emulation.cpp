@@ -18,62 +18,20 @@
 static Idx gridDim;
 #define ext_vector_type(n) vector_size(8 * n)
 #define __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, x, y, z) (c)
+#include "emulated_state.h"
 #include "predict.h"
 #include "predict_model.h"
 
-template <typename F> static void launch_wg2(int grid, F body) {
-    for (int b = 0; b < grid; ++b)
-        for (int pass = 0; pass < 2; ++pass)
-            for (int t = 0; t < kBlock; ++t) { blockIdx.x = b; threadIdx.x = t; body(); }
-}
-
-struct Store {
-    int N, ldm;
-    std::vector<double> x[2], prr[2], strip[2], small;
-    int cur = 0;
-    DevState st;
-    explicit Store(int N_) : N(N_) {
-        ldm = ((2 * N + 15) / 16 + 1) * 16;
-        for (int b = 0; b < 2; ++b) { x[b].assign(3 + ldm, -7.0); prr[b].assign(9, -7.0); strip[b].assign(3 * ldm, -7.0); }
-        small.assign(32, -7.0);
-        sync();
-    }
-    Store(const Store &o) = default;
-    void sync() {
-        st = DevState();
-        for (int b = 0; b < 2; ++b) { st.x[b] = x[b].data(); st.prr[b] = prr[b].data(); st.strip[b] = strip[b].data(); }
-        st.small = small.data(); st.ldm = ldm;
-    }
-};
-static double rnd() { return (rand() % 20001 - 10000) / 10000.0; }
-static void fill(Store &S) {                                   // P(robot and strip rows) = D + U U' (k = 3), x random
-    srand(13);
-    const int n = 3 + 2 * S.N;
-    std::vector<double> U(n * 3), d(n);
-    for (auto &v : U) v = 0.3 * rnd();
-    for (auto &v : d) v = 0.1 + 0.05 * (rnd() + 1);
-    auto P = [&](int r, int c) { double v = r == c ? d[r] : 0; for (int k = 0; k < 3; ++k) v += U[r * 3 + k] * U[c * 3 + k]; return v; };
-    for (int i = 0; i < n; ++i) S.x[0][i] = 20 * rnd();
-    S.x[0][2] = 137.0 + 40 * rnd();
-    for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) S.prr[0][3 * r + c] = P(r > c ? r : c, r > c ? c : r);
-    for (int r = 0; r < 3; ++r) for (int c = 0; c < 2 * S.N; ++c) S.strip[0][r * S.ldm + c] = P(3 + c, r);
-}
-static void run_predict(Store &S, const PredictModelStep *e, int m) {
+// k_predict_model: every workgroup twice -- the first run leaves fa and fb of every step in the shared storage; no lane exchange
+static void run_predict(Store<> &S, const PredictModelStep *e, int m) {
     PredictModelArgs a = {};
     a.n_mm = 2 * S.N; a.m = m; a.cur = S.cur;
     for (int b = 0; b < m; ++b) a.e[b] = e[b];
     DevState st = S.st;
     const int cols = 2 * S.N > 0 ? 2 * S.N : 1;
-    launch_wg2((cols + kBlock - 1) / kBlock, [&] { k_predict_model(st, a); });
+    launch_wg((cols + kBlock - 1) / kBlock, { 2, -1 }, [&] { k_predict_model(st, a); });
     S.cur ^= 1;
 }
-static int differ(const std::vector<double> &u, const std::vector<double> &v, const char *what) {
-    int b = 0;
-    for (size_t i = 0; i < u.size(); ++i) if (memcmp(&u[i], &v[i], 8)) ++b;
-    if (b) printf("  %s: %d differ\n", what, b);
-    return b;
-}
-static void put(FILE *f, const double *v, size_t n) { fwrite(v, 8, n, f); }
 
 int main(int argc, char **argv) {
     if (argc < 2) return 2;
@@ -94,8 +52,9 @@ int main(int argc, char **argv) {
     }
     int total_bad = 0;
     for (int N : { 0, 1, 150 }) {
-        Store base(N);
-        fill(base);
+        Store<> base(16, N, N + 8);                           // (ldm: the 2 N columns and at least one more, rounded up to 16)
+        base.poison(-7.0);
+        fill(base, 13, true);
         const int n0 = 3 + 2 * N;
         {
             FILE *f = fopen((dir + "/before_" + std::to_string(N) + ".bin").c_str(), "wb");

@@ -11,7 +11,7 @@ import subprocess
 import numpy as np
 import pytest
 
-from helpers import RPOS, RecorderBase
+from helpers import RPOS, RecorderBase, host_build
 from merge_batch_cases import INDEX, INVALID_ARG, MERGE_BATCH_MAX, chain_regularity, dense_of, merge_batch_dense, planted, refusal, survivor_index
 from merge_cases import merge_dense
 from mex_harness import PRELUDE_SHOWN, ROOT, driver, driver_without, transcript_of
@@ -102,11 +102,8 @@ def test_the_kernel_sources_emulated_on_the_host_give_the_sequence_bit_for_bit(t
     """tests/support/merge_batch_host_emulation.cpp: the chain of gathers and the fused pass, compiled for the host behind a thread-index
     shim, against the one-pair gather (the same kernel with nothing pending and no record) + pass + compaction route -- x, strip, Prr, diagonal blocks, s, tiles and d2, bit for bit, with a
     shared keep, keep > drop, drops at landmark 0 and N - 1, an adjacent pair, R = 0 and R > 0; address and UB sanitizers on."""
-    exe = str(tmp_path / "emulation")
-    r = subprocess.run(["g++", "-std=c++17", "-O1", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                        "-I", os.path.join(ROOT, "ekf_slam_amd", "csrc"), os.path.join(ROOT, "tests", "support", "merge_batch_host_emulation.cpp"),
-                        "-o", exe], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-4000:]
+    exe = host_build("merge_batch_host_emulation", str(tmp_path / "emulation"),
+                     ["-O1", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"])
     r = subprocess.run([exe], capture_output=True, text=True, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=0"))
     lines = r.stdout.splitlines()
     assert r.returncode == 0 and len(lines) == 4 and all(ln.endswith(")") and ": 0 differences" in ln for ln in lines), r.stdout[-2000:] + r.stderr[-4000:]
