@@ -1,26 +1,12 @@
-"""Thin object wrapper over the C ABI handle: one Engine == one ekf_handle == one filter state in HBM."""
+"""Thin object wrapper over the C ABI handle: one Engine == one ekf_handle == one filter state in HBM.  What turns arguments into
+what the ABI takes lives in marshal.py; the methods here add the handle, the call and the status check."""
 import ctypes
 
 import numpy as np
 
 from . import _lib as L
-
-_dp = ctypes.POINTER(ctypes.c_double)
-
-
-def _vec(v, n=None):
-    a = np.ascontiguousarray(np.asarray(v, dtype=np.float64).reshape(-1))
-    if n is not None and a.size != n:
-        raise ValueError("expected %d values, got %d" % (n, a.size))
-    return a
-
-
-def _p(a):
-    return a.ctypes.data_as(_dp)
-
-
-def _colmajor(M):
-    return np.asfortranarray(np.asarray(M, dtype=np.float64))
+from . import marshal
+from .marshal import _colmajor, _p, _vec, host_call, index_array, noise, p_or_null
 
 
 class Engine:
@@ -58,11 +44,9 @@ class Engine:
         self.h = ctypes.c_void_p()
         rc = self.lib.ekf_create(ctypes.byref(cfg), ctypes.byref(self.h))
         if rc != L.EKF_OK:
-            msg = self.lib.ekf_last_error(self.h).decode() if self.h else ""
-            if self.h:
-                self.lib.ekf_destroy(self.h)
-                self.h = None
-            raise L.EkfError(rc, self.lib.ekf_status_string(rc).decode() + (": " + msg if msg else ""))
+            err = self._error(rc)                 # (the message is read while the handle lives)
+            self.close()
+            raise err
 
     def close(self):
         if getattr(self, "h", None):
@@ -75,10 +59,13 @@ class Engine:
         except Exception:
             pass
 
+    def _error(self, rc, h="self"):
+        msg = self.lib.ekf_last_error(self.h).decode() if (h == "self" and self.h) else ""
+        return L.EkfError(rc, self.lib.ekf_status_string(rc).decode() + (": " + msg if msg else ""))
+
     def _check(self, rc, h="self"):
         if rc != L.EKF_OK:
-            msg = self.lib.ekf_last_error(self.h).decode() if (h == "self" and self.h) else ""
-            raise L.EkfError(rc, self.lib.ekf_status_string(rc).decode() + (": " + msg if msg else ""))
+            raise self._error(rc, h)
 
     # ---- hot path ----
     def predict(self, u):
@@ -147,25 +134,22 @@ class Engine:
 
     def prefetch_rows(self, idx0_list):
         """One exchange for the base row-panels of the landmarks the next corrections touch (sharded handles)."""
-        arr = (ctypes.c_int64 * len(idx0_list))(*[int(i) for i in idx0_list])
         if self._host_exchange is not None:
-            self._check(self.lib.ekf_prefetch_begin(self.h, arr, len(idx0_list)))
+            self.prefetch_begin(idx0_list)
             self._host_exchange(self)
-            self._check(self.lib.ekf_prefetch_finish(self.h))
+            self.prefetch_finish()
             return
-        self._check(self.lib.ekf_prefetch_rows(self.h, arr, len(idx0_list)))
+        self._check(self.lib.ekf_prefetch_rows(self.h, *index_array(idx0_list)))
 
     def prefetch_next(self, idx0_list):
         """Announce the landmarks of the batch AFTER the current one (ekf_prefetch_next): extracted in front of the current batch's
         pass as that pass will leave them, exchanged beside it.  Library-owned communicator or exchange hook only."""
         if self._host_exchange is not None:
             raise L.EkfError(L.EKF_ERR_STATE, "prefetch_next: the host-run all-gather cannot run inside the library's flush")
-        arr = (ctypes.c_int64 * len(idx0_list))(*[int(i) for i in idx0_list])
-        self._check(self.lib.ekf_prefetch_next(self.h, arr, len(idx0_list)))
+        self._check(self.lib.ekf_prefetch_next(self.h, *index_array(idx0_list)))
 
     def prefetch_begin(self, idx0_list):
-        arr = (ctypes.c_int64 * len(idx0_list))(*[int(i) for i in idx0_list])
-        self._check(self.lib.ekf_prefetch_begin(self.h, arr, len(idx0_list)))
+        self._check(self.lib.ekf_prefetch_begin(self.h, *index_array(idx0_list)))
 
     def prefetch_finish(self):
         self._check(self.lib.ekf_prefetch_finish(self.h))
@@ -194,13 +178,17 @@ class Engine:
             self.associate_begin(z, R, want_costs)
             self._host_exchange(self)
             return self.associate_finish(want_costs)
+        return self._association(want_costs, lambda *out: self.lib.ekf_associate(
+            self.h, _p(_vec(z, 3)), _p(_colmajor(R).reshape(-1, order="F")), *out))
+
+    def _association(self, want_costs, call):
+        """The answer of ekf_associate / ekf_associate_finish: call(is_new, idx, position costs, signature costs) fills the outputs made
+        here -- the cost arrays only where asked for, null otherwise."""
         is_new, idx = ctypes.c_int32(), ctypes.c_int64()
         N = self.N
         pc = np.zeros(max(N, 1)) if want_costs else None
         sc = np.zeros(max(N, 1)) if want_costs else None
-        self._check(self.lib.ekf_associate(self.h, _p(_vec(z, 3)), _p(_colmajor(R).reshape(-1, order="F")),
-                                           ctypes.byref(is_new), ctypes.byref(idx),
-                                           _p(pc) if want_costs else None, _p(sc) if want_costs else None))
+        self._check(call(ctypes.byref(is_new), ctypes.byref(idx), p_or_null(pc), p_or_null(sc)))
         if want_costs:
             return bool(is_new.value), int(idx.value), pc[:N], sc[:N]
         return bool(is_new.value), int(idx.value)
@@ -211,15 +199,7 @@ class Engine:
                                                  1 if want_costs else 0))
 
     def associate_finish(self, want_costs=False):
-        is_new, idx = ctypes.c_int32(), ctypes.c_int64()
-        N = self.N
-        pc = np.zeros(max(N, 1)) if want_costs else None
-        sc = np.zeros(max(N, 1)) if want_costs else None
-        self._check(self.lib.ekf_associate_finish(self.h, ctypes.byref(is_new), ctypes.byref(idx),
-                                                  _p(pc) if want_costs else None, _p(sc) if want_costs else None))
-        if want_costs:
-            return bool(is_new.value), int(idx.value), pc[:N], sc[:N]
-        return bool(is_new.value), int(idx.value)
+        return self._association(want_costs, lambda *out: self.lib.ekf_associate_finish(self.h, *out))
 
     def measure(self, observed_LL, u, lm_index, lm_loc):
         obs = np.asfortranarray(np.asarray(observed_LL, dtype=np.float64).reshape(-1, 3))
@@ -296,39 +276,44 @@ class Engine:
         self._check(self.lib.ekf_get_Q(self.h, _p(q)))
         return q.reshape(3, 3, order="F")
 
-    def set_state(self, x, P, s):
+    def set_x(self, x):
+        """x fixes the landmark count: (x.size - 3) / 2."""
         x = _vec(x)
         self._check(self.lib.ekf_set_x(self.h, _p(x), x.size))
+
+    def set_s(self, s):
         s = _vec(s)
         self._check(self.lib.ekf_set_s(self.h, _p(s) if s.size else None, s.size))
-        Pf = np.asfortranarray(np.asarray(P, dtype=np.float64))
+
+    def set_P(self, P):
+        Pf = _colmajor(P)
         self._check(self.lib.ekf_set_P(self.h, _p(Pf.reshape(-1, order="F")), Pf.shape[0]))
+
+    def set_state(self, x, P, s):
+        self.set_x(x)
+        self.set_s(s)
+        self.set_P(P)
 
     def remove_landmarks(self, indices):
         """Drop the landmarks `indices` (0-based, any iterable of ints, any order) from the map on the device
         (ekf_remove_landmarks): the survivors keep their order and their bits."""
-        idx = [int(i) for i in indices]
-        arr = (ctypes.c_int64 * max(len(idx), 1))(*idx)
-        self._check(self.lib.ekf_remove_landmarks(self.h, arr, len(idx)))
+        self._check(self.lib.ekf_remove_landmarks(self.h, *index_array(indices)))
 
     @staticmethod
     def _delta_R(delta, R):
-        d = None if delta is None else _vec(delta, 2)
-        Rf = None if R is None else np.ascontiguousarray(_colmajor(R).reshape(2, 2).reshape(-1, order="F"))
-        return d, Rf
+        """(delta, R) of a constraint between two landmarks as pointers; null where left out (delta: (0, 0), R: zero)."""
+        return p_or_null(None if delta is None else _vec(delta, 2)), p_or_null(noise(R))
 
     def constrain_landmarks(self, i, j, delta=None, R=None):
         """'l_i - l_j was observed as delta with noise covariance R' (0-based i != j; delta None: (0, 0), R None: zero): the exact
         linear Kalman update between two landmarks, formed and applied on the device before the call returns
         (ekf_constrain_landmarks)."""
-        d, Rf = self._delta_R(delta, R)
-        self._check(self.lib.ekf_constrain_landmarks(self.h, int(i), int(j), None if d is None else _p(d), None if Rf is None else _p(Rf)))
+        self._check(self.lib.ekf_constrain_landmarks(self.h, int(i), int(j), *self._delta_R(delta, R)))
 
     def merge_landmarks(self, keep, drop, R=None):
         """Fuse landmark `drop` into `keep` (0-based): constrain_landmarks(keep, drop, None, R), then remove_landmarks([drop]);
         keep's index afterwards is keep - (drop < keep) (ekf_merge_landmarks)."""
-        _, Rf = self._delta_R(None, R)
-        self._check(self.lib.ekf_merge_landmarks(self.h, int(keep), int(drop), None if Rf is None else _p(Rf)))
+        self._check(self.lib.ekf_merge_landmarks(self.h, int(keep), int(drop), p_or_null(noise(R))))
 
     def merge_landmarks_batch(self, pairs, R=None):
         """Fuse every (keep, drop) of `pairs` (0-based, at most EKF_MERGE_BATCH_MAX, numbering before the call) in one call: what
@@ -342,33 +327,28 @@ class Engine:
         v = np.asarray(rows, dtype=np.float64).reshape(-1, 2)
         if not np.all(v == np.floor(v)):
             raise ValueError("merge_landmarks_batch: landmark indices are whole numbers")
-        m = v.shape[0]
-        keep = (ctypes.c_int64 * max(m, 1))(*[int(a) for a in v[:, 0]])
-        drop = (ctypes.c_int64 * max(m, 1))(*[int(a) for a in v[:, 1]])
-        _, Rf = self._delta_R(None, R)
+        (keep, m), (drop, _) = index_array(v[:, 0]), index_array(v[:, 1])
         d2 = np.empty(max(m, 1))
-        self._check(self.lib.ekf_merge_landmarks_batch(self.h, keep, drop, m, None if Rf is None else _p(Rf), _p(d2)))
+        self._check(self.lib.ekf_merge_landmarks_batch(self.h, keep, drop, m, p_or_null(noise(R)), _p(d2)))
         return d2[:m]
 
     def landmark_distance(self, i, j, delta=None, R=None):
         """(d2, S): the squared Mahalanobis distance nu' S^-1 nu of 'l_i - l_j = delta' under the current state and its 2 x 2
         innovation covariance -- what a caller gates a merge on.  Changes nothing (ekf_landmark_distance)."""
-        d, Rf = self._delta_R(delta, R)
         d2 = ctypes.c_double()
         S = np.empty(4)
-        self._check(self.lib.ekf_landmark_distance(self.h, int(i), int(j), None if d is None else _p(d), None if Rf is None else _p(Rf),
-                                                   ctypes.byref(d2), _p(S)))
+        self._check(self.lib.ekf_landmark_distance(self.h, int(i), int(j), *self._delta_R(delta, R), ctypes.byref(d2), _p(S)))
         return float(d2.value), S.reshape(2, 2, order="F")
 
     def nearest_landmarks(self, R=None):
         """(d2, partner): for every landmark i (0-based) the j < i that minimises landmark_distance(i, j, None, R)[0] and that
         minimum, bit for bit; partner is int64 with -1 (and d2 = +inf) where no pair is admissible -- landmark 0, rows whose pairs
         are all irregular.  The lowest index wins ties.  One read-only pass over P on the device (ekf_nearest_landmarks)."""
-        _, Rf = self._delta_R(None, R)
+        Rp = p_or_null(noise(R))
         N = self.N
         d2 = np.empty(max(N, 1))
         partner = np.empty(max(N, 1), dtype=np.int64)
-        self._check(self.lib.ekf_nearest_landmarks(self.h, None if Rf is None else _p(Rf), _p(d2),
+        self._check(self.lib.ekf_nearest_landmarks(self.h, Rp, _p(d2),
                                                    partner.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))))
         return d2[:N], partner[:N]
 
@@ -380,90 +360,37 @@ class Engine:
         rows = rows[np.lexsort((rows, d2[rows]))]
         return [(int(i), int(partner[i]), float(d2[i])) for i in rows]
 
+    # ---- update-steps from one struct (marshal.py builds it; slam.py hands in the one it logs from) ----
+    _linear_obs = staticmethod(marshal.linear_obs)
+    _model_obs = staticmethod(marshal.model_obs)
+    _model_inits = staticmethod(marshal.model_inits)
+    _motions = staticmethod(marshal.motions)
+
+    def _observe(self, name, o, wait):
+        """ekf_observe_linear / ekf_observe_model / their _innovation twins on the struct o: the result dict where waited for."""
+        res = L.EkfLinearResult() if wait else None
+        self._check(getattr(self.lib, name)(self.h, ctypes.byref(o), ctypes.byref(res) if wait else None))
+        return marshal.linear_result(res) if wait else None
+
+    def _observe_iterated(self, name, o, iterations, tol, wait):
+        """ekf_observe_model_iterated / ekf_model_innovation_iterated on the struct o."""
+        first, it = (L.EkfLinearResult(), L.EkfIteratedResult()) if wait else (None, None)
+        self._check(getattr(self.lib, name)(self.h, ctypes.byref(o), int(iterations), float(tol), ctypes.byref(first) if wait else None,
+                                            ctypes.byref(it) if wait else None))
+        return marshal.iterated_result(first, it) if wait else None
+
     # ---- linear observations: update-steps with a constant Jacobian (include/ekfslam.h: ekf_observe_linear) ----
-    @staticmethod
-    def _linear_obs(z, R, Hr, landmarks, Hl, gate, wrap, rows):
-        rows = int(rows)
-        if rows not in (1, 2):
-            raise ValueError("linear observation: rows is 1 or 2")
-        o = L.EkfLinearObs()
-        zv = np.zeros(2)
-        zin = _vec(z)
-        if not rows <= zin.size <= 2:
-            raise ValueError("linear observation: z has `rows` values")
-        zv[:rows] = zin[:rows]
-        Rm = np.zeros((2, 2))
-        if R is not None:
-            Ra = np.asarray(R, dtype=np.float64)
-            if rows == 1 and Ra.size == 1:
-                Rm[0, 0] = float(Ra.reshape(-1)[0])
-            elif Ra.size == 4:
-                Rm[:] = Ra.reshape(2, 2)
-            else:
-                raise ValueError("linear observation: R is 2 x 2 (or a variance with rows = 1)")
-        Hrm = np.zeros((2, 3))
-        if Hr is not None:
-            Ha = np.asarray(Hr, dtype=np.float64)
-            if Ha.size == 6:
-                Hrm[:] = Ha.reshape(2, 3)
-            elif rows == 1 and Ha.size == 3:
-                Hrm[0] = Ha.reshape(-1)
-            else:
-                raise ValueError("linear observation: Hr is 2 x 3 (or 3 values with rows = 1)")
-        lms = [int(k) for k in landmarks]
-        blocks = list(Hl)
-        if len(lms) > 2 or len(blocks) != len(lms):
-            raise ValueError("linear observation: at most two landmarks, one 2 x 2 block each")
-        o.lm[0] = o.lm[1] = -1
-        for b, (k, blk) in enumerate(zip(lms, blocks)):
-            Ba = np.asarray(blk, dtype=np.float64)
-            Bm = np.zeros((2, 2))
-            if Ba.size == 4:
-                Bm[:] = Ba.reshape(2, 2)
-            elif rows == 1 and Ba.size == 2:
-                Bm[0] = Ba.reshape(-1)
-            else:
-                raise ValueError("linear observation: a landmark block is 2 x 2 (or 2 values with rows = 1)")
-            o.lm[b] = k
-            for q, v in enumerate(Bm.reshape(-1, order="F")):
-                o.Hl[b][q] = v
-        for q in range(2):
-            o.z[q] = zv[q]
-        for q, v in enumerate(Rm.reshape(-1, order="F")):
-            o.R[q] = v
-        for q, v in enumerate(Hrm.reshape(-1, order="F")):
-            o.Hr[q] = v
-        o.gate = float(gate)
-        w = tuple(wrap) + (0, 0)
-        o.wrap_deg[0], o.wrap_deg[1] = int(bool(w[0])), int(bool(w[1]))
-        o.rows = rows
-        return o
-
-    @staticmethod
-    def _linear_result(res):
-        return {"nu": np.array(res.nu[:]), "S": np.array(res.S[:]).reshape(2, 2, order="F"), "d2": float(res.d2),
-                "outcome": int(res.outcome)}
-
     def observe_linear(self, z, R, Hr=None, landmarks=(), Hl=(), gate=float("inf"), wrap=(0, 0), rows=2, wait=False):
         """'H x was observed as z with noise covariance R' as an UPDATE-STEP (ekf_observe_linear): H = the 2 x 3 block Hr on the robot
         state (theta in degrees) plus one 2 x 2 block Hl[b] on each of up to two landmarks (0-based).  Enters the pending ring like a
         correction: nothing is flushed, and with wait=False nothing is waited for (returns None).  wait=True returns
         {'nu', 'S', 'd2', 'outcome'} of the launch (outcome: EKF_LINEAR_APPLIED / _GATED; an irregular S raises EkfError)."""
-        o = self._linear_obs(z, R, Hr, landmarks, Hl, gate, wrap, rows)
-        if not wait:
-            self._check(self.lib.ekf_observe_linear(self.h, ctypes.byref(o), None))
-            return None
-        res = L.EkfLinearResult()
-        self._check(self.lib.ekf_observe_linear(self.h, ctypes.byref(o), ctypes.byref(res)))
-        return self._linear_result(res)
+        return self._observe("ekf_observe_linear", marshal.linear_obs(z, R, Hr, landmarks, Hl, gate, wrap, rows), wait)
 
     def linear_innovation(self, z, R, Hr=None, landmarks=(), Hl=(), gate=float("inf"), wrap=(0, 0), rows=2):
         """{'nu', 'S', 'd2', 'outcome'} observe_linear(..., wait=True) would report under the current state, bit for bit; changes
         nothing and flushes nothing (ekf_linear_innovation).  An irregular S is reported (outcome EKF_LINEAR_IRREGULAR, d2 NaN)."""
-        o = self._linear_obs(z, R, Hr, landmarks, Hl, gate, wrap, rows)
-        res = L.EkfLinearResult()
-        self._check(self.lib.ekf_linear_innovation(self.h, ctypes.byref(o), ctypes.byref(res)))
-        return self._linear_result(res)
+        return self._observe("ekf_linear_innovation", marshal.linear_obs(z, R, Hr, landmarks, Hl, gate, wrap, rows), True)
 
     def linear_rejections(self):
         """(irregular, gated): observe_linear launches since the last call that did not apply; synchronises and resets the counts."""
@@ -472,77 +399,19 @@ class Engine:
         return int(a.value), int(b.value)
 
     # ---- observations through a model linearised on the device (include/ekfslam.h: ekf_observe_model) ----
-    @staticmethod
-    def _model_obs(model, z, R, landmarks, anchor, gate):
-        model = int(model)
-        rows = L.EKF_MODEL_ROWS.get(model)
-        if rows is None:
-            raise ValueError("model observation: model is one of EKF_MODEL_* (1..5)")
-        o = L.EkfModelObs()
-        o.model = model
-        zin = _vec(z)
-        if not rows <= zin.size <= 2:
-            raise ValueError("model observation: z has one value per row of the model")
-        for q in range(rows):
-            o.z[q] = zin[q]
-        Rm = np.zeros((2, 2))
-        if R is not None:
-            Ra = np.asarray(R, dtype=np.float64)
-            if rows == 1 and Ra.size == 1:
-                Rm[0, 0] = float(Ra.reshape(-1)[0])
-            elif Ra.size == 4:
-                Rm[:] = Ra.reshape(2, 2)
-            else:
-                raise ValueError("model observation: R is 2 x 2 (or a variance for a one-row model)")
-        for q, v in enumerate(Rm.reshape(-1, order="F")):
-            o.R[q] = v
-        lms = [int(k) for k in landmarks]
-        if len(lms) > 2:
-            raise ValueError("model observation: at most two landmarks")
-        o.lm[0] = o.lm[1] = -1
-        for b, k in enumerate(lms):
-            o.lm[b] = k
-        if anchor is not None:
-            if lms:
-                raise ValueError("model observation: the target is a landmark or an anchor, not both")
-            av = _vec(anchor)
-            if av.size != 2:
-                raise ValueError("model observation: the anchor is a point (2 values)")
-            o.anchor[0], o.anchor[1] = av[0], av[1]
-        elif not lms:
-            raise ValueError("model observation: name the target, a landmark or an anchor")
-        o.gate = float(gate)
-        return o
-
     def observe_model(self, model, z, R, landmarks=(), anchor=None, gate=float("inf"), wait=False):
         """'h(x) was observed as z with noise covariance R' for one of the models EKF_MODEL_* (range and bearing, range, bearing,
         relative position, landmark range), linearised on the device at the live x (ekf_observe_model).  landmarks: the 0-based
         target (two for EKF_MODEL_LANDMARK_RANGE); anchor: a fixed point outside the map as the target instead.  An update-step like
         observe_linear: nothing is flushed; wait=True returns {'nu', 'S', 'd2', 'outcome'} (a target on the robot raises EkfError)."""
-        o = self._model_obs(model, z, R, landmarks, anchor, gate)
-        if not wait:
-            self._check(self.lib.ekf_observe_model(self.h, ctypes.byref(o), None))
-            return None
-        res = L.EkfLinearResult()
-        self._check(self.lib.ekf_observe_model(self.h, ctypes.byref(o), ctypes.byref(res)))
-        return self._linear_result(res)
+        return self._observe("ekf_observe_model", marshal.model_obs(model, z, R, landmarks, anchor, gate), wait)
 
     def model_innovation(self, model, z, R, landmarks=(), anchor=None, gate=float("inf")):
         """{'nu', 'S', 'd2', 'outcome'} observe_model(..., wait=True) would report under the current state, bit for bit; changes and
         flushes nothing (ekf_model_innovation)."""
-        o = self._model_obs(model, z, R, landmarks, anchor, gate)
-        res = L.EkfLinearResult()
-        self._check(self.lib.ekf_model_innovation(self.h, ctypes.byref(o), ctypes.byref(res)))
-        return self._linear_result(res)
+        return self._observe("ekf_model_innovation", marshal.model_obs(model, z, R, landmarks, anchor, gate), True)
 
     # ---- ... relinearised on the device: the iterated EKF update (include/ekfslam.h: ekf_observe_model_iterated) ----
-    @staticmethod
-    def _iterated_result(first, it):
-        out = Engine._linear_result(first)
-        out["iterated"] = {"S": np.array(it.S[:]).reshape(2, 2, order="F"), "nu": np.array(it.nu[:]), "used": int(it.used),
-                           "converged": bool(it.converged), "last_step": float(it.last_step), "x_local": np.array(it.x_local[:])}
-        return out
-
     def observe_model_iterated(self, model, z, R, landmarks=(), anchor=None, gate=float("inf"), iterations=3, tol=0.0, wait=False):
         """observe_model with h relinearised up to `iterations` times (1..16) on the device, Gauss-Newton on the MAP cost over the
         robot and the target(s); stops early where no entry moves by more than tol (ekf_observe_model_iterated).  One launch and one
@@ -550,76 +419,45 @@ class Engine:
         FIRST linearisation's nu, S, d2; the call's outcome) with 'iterated': {'S', 'nu', 'used', 'converged', 'last_step', 'x_local'}
         of the linearisation that made the pair.  An iterate without a Jacobian or with an irregular S raises EkfError; nothing is
         changed then."""
-        o = self._model_obs(model, z, R, landmarks, anchor, gate)
-        if not wait:
-            self._check(self.lib.ekf_observe_model_iterated(self.h, ctypes.byref(o), int(iterations), float(tol), None, None))
-            return None
-        first, it = L.EkfLinearResult(), L.EkfIteratedResult()
-        self._check(self.lib.ekf_observe_model_iterated(self.h, ctypes.byref(o), int(iterations), float(tol), ctypes.byref(first), ctypes.byref(it)))
-        return self._iterated_result(first, it)
+        o = marshal.model_obs(model, z, R, landmarks, anchor, gate)
+        return self._observe_iterated("ekf_observe_model_iterated", o, iterations, tol, wait)
 
     def model_innovation_iterated(self, model, z, R, landmarks=(), anchor=None, gate=float("inf"), iterations=3, tol=0.0):
         """What observe_model_iterated(..., wait=True) would report under the current state, bit for bit; changes and flushes nothing
         (ekf_model_innovation_iterated).  An irregular outcome is reported, not raised."""
-        o = self._model_obs(model, z, R, landmarks, anchor, gate)
-        first, it = L.EkfLinearResult(), L.EkfIteratedResult()
-        self._check(self.lib.ekf_model_innovation_iterated(self.h, ctypes.byref(o), int(iterations), float(tol), ctypes.byref(first), ctypes.byref(it)))
-        return self._iterated_result(first, it)
+        o = marshal.model_obs(model, z, R, landmarks, anchor, gate)
+        return self._observe_iterated("ekf_model_innovation_iterated", o, iterations, tol, True)
 
     @staticmethod
     def model_iterate(model, sm, z, R, anchor=None, has_landmark=True, gate=float("inf"), iterations=3, tol=0.0, lib=None):
         """The loop the kernel runs, on the host (ekf_model_iterate): sm = the 38 operands of the small part (include/ekfslam.h names the
         layout), R the 2 x 2 the kernel sees (a one-row model: [[r, 0], [0, 1]]).  Returns model_innovation_iterated's dict."""
-        lib = L.lib() if lib is None else lib
         first, it = L.EkfLinearResult(), L.EkfIteratedResult()
-        Rm = np.ascontiguousarray(np.asarray(R, dtype=np.float64).reshape(2, 2).reshape(-1, order="F"))
         av = _vec(anchor, 2) if anchor is not None else np.zeros(2)
-        rc = lib.ekf_model_iterate(int(model), _p(_vec(sm, 38)), _p(av), int(bool(has_landmark)), _p(_vec(z, 2)), _p(Rm), float(gate),
-                                   int(iterations), float(tol), ctypes.byref(first), ctypes.byref(it))
-        if rc:
-            raise L.EkfError(rc, "ekf_model_iterate")
-        return Engine._iterated_result(first, it)
+        Rf = noise(np.asarray(R, dtype=np.float64))           # (as an array: R is not optional here)
+        host_call("ekf_model_iterate", lib, int(model), _p(_vec(sm, 38)), _p(av), int(bool(has_landmark)), _p(_vec(z, 2)), _p(Rf),
+                  float(gate), int(iterations), float(tol), ctypes.byref(first), ctypes.byref(it))
+        return marshal.iterated_result(first, it)
 
     @staticmethod
     def model_evaluate(model, xr, t0, t1=None, lib=None):
         """(h(x), H) of a model at the robot state xr = (x, y, theta in degrees) and the targets t0 (and t1: the second landmark of
         EKF_MODEL_LANDMARK_RANGE): the function the kernel runs, on the host (ekf_model_evaluate).  H is 2 x 7 over
         x, y, theta | t0 | t1; an anchor's block is simply not used."""
-        lib = L.lib() if lib is None else lib
         hx, H = np.zeros(2), np.zeros(14)
-        rc = lib.ekf_model_evaluate(int(model), _p(_vec(xr, 3)), _p(_vec(t0, 2)), _p(_vec(t1, 2)) if t1 is not None else None, _p(hx), _p(H))
-        if rc:
-            raise L.EkfError(rc, "ekf_model_evaluate")
+        host_call("ekf_model_evaluate", lib, int(model), _p(_vec(xr, 3)), _p(_vec(t0, 2)), p_or_null(None if t1 is None else _vec(t1, 2)),
+                  _p(hx), _p(H))
         return hx, H.reshape(2, 7)
 
     # ---- landmarks that start from a model's inverse (include/ekfslam.h: ekf_append_model) ----
-    @staticmethod
-    def _model_inits(entries):
-        entries = list(entries)
-        arr = (L.EkfModelInit * max(len(entries), 1))()
-        for o, ent in zip(arr, entries):
-            if len(ent) != 4:
-                raise ValueError("append_model: an entry is (model, z, R, signature)")
-            model, z, R, signature = ent
-            o.model = int(model)
-            zin = _vec(z)
-            if zin.size != 2:
-                raise ValueError("append_model: z has two values")
-            o.z[0], o.z[1] = zin[0], zin[1]
-            Ra = np.asarray(R, dtype=np.float64)
-            if Ra.size != 4:
-                raise ValueError("append_model: R is 2 x 2")
-            for q, v in enumerate(Ra.reshape(2, 2).reshape(-1, order="F")):
-                o.R[q] = v
-            o.signature = float(signature)
-        return arr, len(entries)
-
     def append_model(self, entries):
         """One scan of new landmarks: entries = [(model, z, R, signature), ...] with model EKF_MODEL_RANGE_BEARING (z = range, bearing in
         degrees) or EKF_MODEL_RELATIVE_XY (z = the landmark in the robot frame), all inverted on the device at the live robot state and
         appended by one launch (ekf_append_model).  Returns the 0-based index of the first one; entry b becomes landmark first + b.
         Nothing is waited for or flushed."""
-        arr, m = self._model_inits(entries)
+        return self._append_model(*marshal.model_inits(entries))
+
+    def _append_model(self, arr, m):
         first = ctypes.c_int64(-1)
         self._check(self.lib.ekf_append_model(self.h, arr, m, ctypes.byref(first)))
         return int(first.value)
@@ -629,11 +467,8 @@ class Engine:
         """(t, Gx, Gz): the landmark that z observes from the robot state xr = (x, y, theta in degrees) through EKF_MODEL_RANGE_BEARING
         or EKF_MODEL_RELATIVE_XY, with Gx = dt/dx_r (2 x 3) and Gz = dt/dz (2 x 2): the function the kernel runs, on the host
         (ekf_model_invert)."""
-        lib = L.lib() if lib is None else lib
         t, Gx, Gz = np.zeros(2), np.zeros(6), np.zeros(4)
-        rc = lib.ekf_model_invert(int(model), _p(_vec(xr, 3)), _p(_vec(z, 2)), _p(t), _p(Gx), _p(Gz))
-        if rc:
-            raise L.EkfError(rc, "ekf_model_invert")
+        host_call("ekf_model_invert", lib, int(model), _p(_vec(xr, 3)), _p(_vec(z, 2)), _p(t), _p(Gx), _p(Gz))
         return t, Gx.reshape(2, 3), Gz.reshape(2, 2)
 
     # ---- which landmark a sighting belongs to, under the models' conventions (include/ekfslam.h: ekf_associate_model) ----
@@ -643,11 +478,7 @@ class Engine:
         'irregular'}, one array entry per observation, landmarks 0-based and -1 = none; d2 of every (observation, landmark) is what
         model_innovation reports for that pair, bit for bit.  want_d2 adds 'd2_all', the m x N matrix (NaN where a pair has no d2).
         Changes, flushes and retires nothing (ekf_associate_model)."""
-        entries = list(entries)
-        m = len(entries)
-        arr = (L.EkfModelObs * max(m, 1))()
-        for k, ent in enumerate(entries):
-            arr[k] = self._model_obs(ent["model"], ent["z"], ent["R"], (), (0.0, 0.0), ent.get("gate", float("inf")))      # lm = {-1, -1}
+        arr, m = marshal.scan_obs(entries)
         out = (L.EkfModelMatch * max(m, 1))()
         N = self.N
         d2 = np.full((m, N), np.nan) if want_d2 else None
@@ -669,11 +500,7 @@ class Engine:
         where a pairing is irregular -- plus 'd2_prefix' (nh x m: the joint d2 of the pairings among observations 0..k), 'nu'
         (nh x 2m) and 'S' (nh x 2m x 2m) by scan index where asked.  More than EKF_JOINT_HYP_MAX hypotheses go out as several calls.
         Changes and flushes nothing (ekf_joint_innovation)."""
-        entries = list(entries)
-        m = len(entries)
-        arr = (L.EkfModelObs * max(m, 1))()
-        for k, ent in enumerate(entries):
-            arr[k] = self._model_obs(ent["model"], ent["z"], ent["R"], (), (0.0, 0.0), ent.get("gate", float("inf")))      # lm = {-1, -1}
+        arr, m = marshal.scan_obs(entries)
         hyp_in = np.asarray(hypotheses)
         if hyp_in.ndim != 2 or hyp_in.shape[1] != m or hyp_in.shape[0] < 1:
             raise ValueError("joint_innovation: hypotheses is nh x m, one landmark (or -1) per entry of the scan")
@@ -704,36 +531,14 @@ class Engine:
         return res
 
     # ---- motion steps through a model with its true Jacobians (include/ekfslam.h: ekf_predict_model) ----
-    @staticmethod
-    def _motions(steps):
-        steps = list(steps)
-        arr = (L.EkfMotion * max(len(steps), 1))()
-        for o, st in zip(arr, steps):
-            if len(st) != 3:
-                raise ValueError("predict_model: a step is (model, u, M)")
-            model, u, M = st
-            o.model = int(model)
-            nu = L.EKF_MOTION_INPUTS.get(o.model, 3)
-            uin = _vec(u)
-            if uin.size != nu:
-                raise ValueError("predict_model: u has %d values for this model" % nu)
-            for q in range(nu):
-                o.u[q] = uin[q]
-            Ma = np.asarray(M, dtype=np.float64)
-            if Ma.size != nu * nu:
-                raise ValueError("predict_model: M is %d x %d for this model" % (nu, nu))
-            full = np.zeros((3, 3))
-            full[:nu, :nu] = Ma.reshape(nu, nu)
-            for q, v in enumerate(full.reshape(-1, order="F")):
-                o.M[q] = v
-        return arr, len(steps)
-
     def predict_model(self, steps):
         """A chain of motion steps: steps = [(model, u, M), ...] with model EKF_MOTION_TURN_DRIVE (u = d, turn), EKF_MOTION_ARC (u = arc
         length, turn) or EKF_MOTION_POSE_DELTA (u = dx, dy, turn in the robot frame); angles in degrees, M the covariance of u (2 x 2 or
         3 x 3).  x_r' = f(x_r, u), P' = F P F' + V M V' with the true Jacobians, step after step in ONE launch (ekf_predict_model).
         Eager: a recorded predict is carried out first.  Nothing is waited for or flushed."""
-        arr, m = self._motions(steps)
+        self._predict_model(*marshal.motions(steps))
+
+    def _predict_model(self, arr, m):
         self._check(self.lib.ekf_predict_model(self.h, arr, m))
 
     @staticmethod
@@ -741,14 +546,11 @@ class Engine:
         """(x_new, F, V) of a motion model at the robot state xr = (x, y, theta in degrees): the new pose, F = df/dx_r (3 x 3) and
         V = df/du (3 x 3; a model with two inputs leaves the last column zero): the function the kernel runs, on the host
         (ekf_motion_evaluate)."""
-        lib = L.lib() if lib is None else lib
         uin = np.zeros(3)
         uv = _vec(u)
         uin[:min(uv.size, 3)] = uv[:3]
         xn, F, V = np.zeros(3), np.zeros(9), np.zeros(9)
-        rc = lib.ekf_motion_evaluate(int(model), _p(_vec(xr, 3)), _p(uin), _p(xn), _p(F), _p(V))
-        if rc:
-            raise L.EkfError(rc, "ekf_motion_evaluate")
+        host_call("ekf_motion_evaluate", lib, int(model), _p(_vec(xr, 3)), _p(uin), _p(xn), _p(F), _p(V))
         return xn, F.reshape(3, 3, order="F"), V.reshape(3, 3, order="F")
 
     def load_lowrank_state(self, x, s, d, U):

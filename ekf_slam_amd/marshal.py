@@ -1,0 +1,213 @@
+"""What turns Python arguments into what the C ABI takes, and the ABI's result structs into what the callers get: every conversion that
+needs no handle.  engine.py goes through these for each entry point; slam.py calls the struct builders itself, so that a wrapper builds
+ONE struct per call, hands that object to the Engine and writes its log from it.  Functions only; nothing here touches the state."""
+import ctypes
+
+import numpy as np
+
+from . import _lib as L
+
+_dp = ctypes.POINTER(ctypes.c_double)
+INF = float("inf")
+
+
+# ---- pointers ----
+def _vec(v, n=None):
+    a = np.ascontiguousarray(np.asarray(v, dtype=np.float64).reshape(-1))
+    if n is not None and a.size != n:
+        raise ValueError("expected %d values, got %d" % (n, a.size))
+    return a
+
+
+def _p(a):
+    return a.ctypes.data_as(_dp)
+
+
+def p_or_null(a):
+    return None if a is None else _p(a)
+
+
+def _colmajor(M):
+    return np.asfortranarray(np.asarray(M, dtype=np.float64))
+
+
+def index_array(indices):
+    """(int64[], count) of any iterable of whole numbers; an empty one still has a slot to point at."""
+    idx = [int(i) for i in indices]
+    return (ctypes.c_int64 * max(len(idx), 1))(*idx), len(idx)
+
+
+def _fill(dst, values):
+    """The leading entries of a struct's array from an array or a list (one slice assignment: a third of the cost of entry by entry)."""
+    values = values.tolist() if isinstance(values, np.ndarray) else list(values)
+    dst[:len(values)] = values
+
+
+# ---- the noise matrix ----
+def noise(R, who=None, one_row=False, or_what=""):
+    """R as the ABI takes it: the four doubles of a 2 x 2 matrix, column-major; None (a null pointer, or a struct's zeros) where R is
+    None.  one_row: a single value is the variance of the one row, R(0, 0).  Any other size is refused as '<who>: R is 2 x 2<or_what>'
+    (who None: by the reshape itself)."""
+    if R is None:
+        return None
+    Ra = np.asarray(R, dtype=np.float64)
+    if one_row and Ra.size == 1:
+        return np.array([float(Ra.reshape(-1)[0]), 0.0, 0.0, 0.0])
+    if who is not None and Ra.size != 4:
+        raise ValueError("%s: R is 2 x 2%s" % (who, or_what))
+    return np.ascontiguousarray(Ra.reshape(2, 2).reshape(-1, order="F"))
+
+
+# ---- the structs ----
+def linear_obs(z, R, Hr, landmarks, Hl, gate, wrap, rows):
+    """struct ekf_linear_obs of observe_linear's arguments (landmarks 0-based): full-size blocks, zero where rows = 1 leaves them out."""
+    who = "linear observation"
+    rows = int(rows)
+    if rows not in (1, 2):
+        raise ValueError("%s: rows is 1 or 2" % who)
+    o = L.EkfLinearObs()
+    zin = _vec(z)
+    if not rows <= zin.size <= 2:
+        raise ValueError("%s: z has `rows` values" % who)
+    _fill(o.z, zin[:rows])
+    Rf = noise(R, who, rows == 1, " (or a variance with rows = 1)")
+    if Rf is not None:
+        _fill(o.R, Rf)
+
+    def block(M, width, what):
+        """2 x width, or its first row alone where rows = 1; column-major."""
+        Ma = np.asarray(M, dtype=np.float64)
+        full = np.zeros((2, width))
+        if Ma.size == 2 * width:
+            full[:] = Ma.reshape(2, width)
+        elif rows == 1 and Ma.size == width:
+            full[0] = Ma.reshape(-1)
+        else:
+            raise ValueError("%s: %s" % (who, what))
+        return full.reshape(-1, order="F")
+    if Hr is not None:
+        _fill(o.Hr, block(Hr, 3, "Hr is 2 x 3 (or 3 values with rows = 1)"))
+    lms = [int(k) for k in landmarks]
+    blocks = list(Hl)
+    if len(lms) > 2 or len(blocks) != len(lms):
+        raise ValueError("%s: at most two landmarks, one 2 x 2 block each" % who)
+    o.lm[0] = o.lm[1] = -1
+    for b, (k, blk) in enumerate(zip(lms, blocks)):
+        _fill(o.Hl[b], block(blk, 2, "a landmark block is 2 x 2 (or 2 values with rows = 1)"))
+        o.lm[b] = k
+    o.gate = float(gate)
+    w = tuple(wrap) + (0, 0)
+    o.wrap_deg[0], o.wrap_deg[1] = int(bool(w[0])), int(bool(w[1]))
+    o.rows = rows
+    return o
+
+
+def model_obs(model, z, R, landmarks, anchor, gate):
+    """struct ekf_model_obs of observe_model's arguments (landmarks 0-based; the target is they or the anchor)."""
+    who = "model observation"
+    model = int(model)
+    rows = L.EKF_MODEL_ROWS.get(model)
+    if rows is None:
+        raise ValueError("%s: model is one of EKF_MODEL_* (1..5)" % who)
+    o = L.EkfModelObs()
+    o.model = model
+    zin = _vec(z)
+    if not rows <= zin.size <= 2:
+        raise ValueError("%s: z has one value per row of the model" % who)
+    _fill(o.z, zin[:rows])
+    Rf = noise(R, who, rows == 1, " (or a variance for a one-row model)")
+    if Rf is not None:
+        _fill(o.R, Rf)
+    lms = [int(k) for k in landmarks]
+    if len(lms) > 2:
+        raise ValueError("%s: at most two landmarks" % who)
+    o.lm[0] = o.lm[1] = -1
+    _fill(o.lm, lms)
+    if anchor is not None:
+        if lms:
+            raise ValueError("%s: the target is a landmark or an anchor, not both" % who)
+        av = _vec(anchor)
+        if av.size != 2:
+            raise ValueError("%s: the anchor is a point (2 values)" % who)
+        o.anchor[0], o.anchor[1] = av[0], av[1]
+    elif not lms:
+        raise ValueError("%s: name the target, a landmark or an anchor" % who)
+    o.gate = float(gate)
+    return o
+
+
+def scan_obs(entries):
+    """(ekf_model_obs[], m) of a scan [{'model', 'z', 'R', 'gate'}, ...] that is matched against the whole map: no target named
+    (lm = {-1, -1}), a gate left out is +inf."""
+    entries = list(entries)
+    arr = (L.EkfModelObs * max(len(entries), 1))()
+    for k, ent in enumerate(entries):
+        arr[k] = model_obs(ent["model"], ent["z"], ent["R"], (), (0.0, 0.0), ent.get("gate", INF))
+    return arr, len(entries)
+
+
+def model_inits(entries, who="append_model"):
+    """(ekf_model_init[], m) of a scan of new landmarks [(model, z, R, signature), ...]."""
+    entries = list(entries)
+    arr = (L.EkfModelInit * max(len(entries), 1))()
+    for o, ent in zip(arr, entries):
+        if len(ent) != 4:
+            raise ValueError("%s: an entry is (model, z, R, signature)" % who)
+        model, z, R, signature = ent
+        o.model = int(model)
+        zin = _vec(z)
+        if zin.size != 2:
+            raise ValueError("%s: z has two values" % who)
+        _fill(o.z, zin)
+        _fill(o.R, noise(np.asarray(R, dtype=np.float64), who))      # (as an array: R is not optional here)
+        o.signature = float(signature)
+    return arr, len(entries)
+
+
+def motions(steps, known_models=False):
+    """(ekf_motion[], m) of a chain of motion steps [(model, u, M), ...]: u and M of the size the model reads, M column-major in the
+    3 x 3 slot.  A model without an entry in EKF_MOTION_INPUTS is refused here where known_models is set, else left to the library."""
+    who = "predict_model"
+    steps = list(steps)
+    arr = (L.EkfMotion * max(len(steps), 1))()
+    for o, st in zip(arr, steps):
+        if len(st) != 3:
+            raise ValueError("%s: a step is (model, u, M)" % who)
+        model, u, M = st
+        o.model = int(model)
+        if known_models and o.model not in L.EKF_MOTION_INPUTS:
+            raise ValueError("%s: model is EKF_MOTION_TURN_DRIVE (1), EKF_MOTION_ARC (2) or EKF_MOTION_POSE_DELTA (3)" % who)
+        nu = L.EKF_MOTION_INPUTS.get(o.model, 3)
+        uin = _vec(u)
+        if uin.size != nu:
+            raise ValueError("%s: u has %d values for this model" % (who, nu))
+        _fill(o.u, uin)
+        Ma = np.asarray(M, dtype=np.float64)
+        if Ma.size != nu * nu:
+            raise ValueError("%s: M is %d x %d for this model" % (who, nu, nu))
+        full = np.zeros((3, 3))
+        full[:nu, :nu] = Ma.reshape(nu, nu)
+        _fill(o.M, full.reshape(-1, order="F"))
+    return arr, len(steps)
+
+
+# ---- the results ----
+def linear_result(res):
+    return {"nu": np.array(res.nu[:]), "S": np.array(res.S[:]).reshape(2, 2, order="F"), "d2": float(res.d2),
+            "outcome": int(res.outcome)}
+
+
+def iterated_result(first, it):
+    out = linear_result(first)
+    out["iterated"] = {"S": np.array(it.S[:]).reshape(2, 2, order="F"), "nu": np.array(it.nu[:]), "used": int(it.used),
+                       "converged": bool(it.converged), "last_step": float(it.last_step), "x_local": np.array(it.x_local[:])}
+    return out
+
+
+# ---- the library's pure host functions ----
+def host_call(name, lib, *args):
+    """One of the functions that take no handle (the kernels' own text, compiled for the host): `lib` None is the loaded library; a
+    status raises EkfError(status, name)."""
+    rc = getattr(L.lib() if lib is None else lib, name)(*args)
+    if rc:
+        raise L.EkfError(rc, name)

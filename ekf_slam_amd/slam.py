@@ -19,14 +19,15 @@ Differences forced by the host language: x is a 1-D array (the reference's 1 x n
 the 2x2 diagonal covariance blocks); the ROS subscribers of SLAM.m:23-24 are replaced by a scripted
 (u, scan) feed.
 """
-import ctypes
 import math
 import warnings
 
 import numpy as np
 
 from . import _lib as L
-from .engine import Engine, _p, _vec
+from . import marshal
+from .engine import Engine
+from .marshal import _p, _vec
 from .world import SyntheticLandmark
 
 _DEFAULT_CAPACITY = 1024
@@ -127,8 +128,7 @@ class _EkfBase:
 
     @x.setter
     def x(self, v):                 # assignable like the reference's (EKF_SLAM.m:6-9); x fixes the landmark count
-        v = _vec(v)
-        self._e._check(self._e.lib.ekf_set_x(self._e.h, _p(v), v.size))
+        self._e.set_x(v)
 
     @property
     def P(self):
@@ -136,8 +136,7 @@ class _EkfBase:
 
     @P.setter
     def P(self, v):
-        Pf = np.asfortranarray(np.asarray(v, dtype=np.float64))
-        self._e._check(self._e.lib.ekf_set_P(self._e.h, _p(Pf.reshape(-1, order="F")), Pf.shape[0]))
+        self._e.set_P(v)
 
     @property
     def s(self):
@@ -145,8 +144,7 @@ class _EkfBase:
 
     @s.setter
     def s(self, v):
-        v = _vec(v)
-        self._e._check(self._e.lib.ekf_set_s(self._e.h, _p(v) if v.size else None, v.size))
+        self._e.set_s(v)
 
     @property
     def Q(self):
@@ -198,9 +196,7 @@ class _EkfBase:
         n = x.size
         x_new = np.empty(n)
         F = np.empty(n * n)
-        rc = self._e.lib.ekf_motion_model(_p(x), n, _p(_vec(u, 2)), _p(x_new), _p(F))
-        if rc:
-            raise L.EkfError(rc, "ekf_motion_model")
+        marshal.host_call("ekf_motion_model", self._e.lib, _p(x), n, _p(_vec(u, 2)), _p(x_new), _p(F))
         return x_new, F.reshape(n, n, order="F")
 
     def append(self, u, R, landmarkPos, signature):
@@ -320,8 +316,8 @@ class _EkfBase:
         rows = int(rows)
         if rows not in (1, 2):
             raise ValueError("observe_linear: rows is 1 or 2")
-        obs = self._e._linear_obs(z, R, Hr, [k - 1 for k in lms], Hl, gate, wrap, rows)      # (the engine's own shape checks)
-        out = self._e.observe_linear(z, R, Hr, [k - 1 for k in lms], Hl, gate, wrap, rows, wait)
+        obs = marshal.linear_obs(z, R, Hr, [k - 1 for k in lms], Hl, gate, wrap, rows)      # the one struct: sent, then logged from
+        out = self._e._observe("ekf_observe_linear", obs, wait)
         if self.log is not None:
             Rm = np.array(obs.R[:]).reshape(2, 2, order="F")
             Hrm = np.array(obs.Hr[:]).reshape(2, 3, order="F")
@@ -365,12 +361,16 @@ class _EkfBase:
         if int(iterations) != 1 or float(tol) != 0.0:
             return self.observe_model_iterated(model, z, R, landmarks, anchor, gate, iterations, tol, wait)
         lms = self._landmark_numbers("observe_model", *list(landmarks))
-        obs = self._e._model_obs(model, z, R, [k - 1 for k in lms], anchor, gate)           # (the engine's own shape checks)
-        out = self._e.observe_model(model, z, R, [k - 1 for k in lms], anchor, gate, wait)
+        obs = marshal.model_obs(model, z, R, [k - 1 for k in lms], anchor, gate)           # the one struct: sent, then logged from
+        out = self._e._observe("ekf_observe_model", obs, wait)
         if self.log is not None:
-            self.log.record_model_observation(obs.model, np.array(obs.z[:]), np.array(obs.R[:]).reshape(2, 2, order="F"), lms,
-                                              None if lms else np.array(obs.anchor[:]), gate)
+            self.log.record_model_observation(*self._logged_model_obs(obs, lms), gate)
         return out
+
+    @staticmethod
+    def _logged_model_obs(obs, lms):
+        """What the log holds of a model observation's struct: model, z, R (2 x 2), the 1-based landmarks, the anchor or None."""
+        return obs.model, np.array(obs.z[:]), np.array(obs.R[:]).reshape(2, 2, order="F"), lms, None if lms else np.array(obs.anchor[:])
 
     def model_innovation(self, model, z, R, landmarks=(), anchor=None, gate=float("inf")):
         """{'nu', 'S', 'd2', 'outcome'} observe_model(..., wait=True) would report now (1-based landmarks); changes and flushes
@@ -386,11 +386,10 @@ class _EkfBase:
         dict (the first linearisation's) with 'iterated': {'S', 'nu', 'used', 'converged', 'last_step', 'x_local'}
         (ekf_observe_model_iterated).  The reference has no such method."""
         lms = self._landmark_numbers("observe_model_iterated", *list(landmarks))
-        obs = self._e._model_obs(model, z, R, [k - 1 for k in lms], anchor, gate)           # (the engine's own shape checks)
-        out = self._e.observe_model_iterated(model, z, R, [k - 1 for k in lms], anchor, gate, iterations, tol, wait)
+        obs = marshal.model_obs(model, z, R, [k - 1 for k in lms], anchor, gate)           # the one struct: sent, then logged from
+        out = self._e._observe_iterated("ekf_observe_model_iterated", obs, iterations, tol, wait)
         if self.log is not None:
-            self.log.record_model_observation_iterated(obs.model, np.array(obs.z[:]), np.array(obs.R[:]).reshape(2, 2, order="F"), lms,
-                                                       None if lms else np.array(obs.anchor[:]), gate, iterations, tol)
+            self.log.record_model_observation_iterated(*self._logged_model_obs(obs, lms), gate, iterations, tol)
         return out
 
     def model_innovation_iterated(self, model, z, R, landmarks=(), anchor=None, gate=float("inf"), iterations=3, tol=0.0):
@@ -449,18 +448,14 @@ class _EkfBase:
         for b, e in enumerate(entries):
             if len(e) not in (3, 4):
                 raise ValueError("add_landmarks_model: an entry is (model, z, R) or (model, z, R, signature)")
-            model = int(e[0])
-            if model not in (L.EKF_MODEL_RANGE_BEARING, L.EKF_MODEL_RELATIVE_XY):
+            if int(e[0]) not in (L.EKF_MODEL_RANGE_BEARING, L.EKF_MODEL_RELATIVE_XY):
                 raise ValueError("add_landmarks_model: model is EKF_MODEL_RANGE_BEARING (1) or EKF_MODEL_RELATIVE_XY (4)")
-            Rm = np.asarray(e[2], dtype=np.float64)
-            if Rm.size != 4:
-                raise ValueError("add_landmarks_model: R is 2 x 2")
-            sig = e[3] if len(e) == 4 and e[3] is not None else N + b + 1
-            full.append((model, _vec(e[1], 2).copy(), Rm.reshape(2, 2).copy(), float(sig)))
-        first = self._e.append_model(full)
+            full.append(e[:3] + (e[3] if len(e) == 4 and e[3] is not None else N + b + 1,))
+        arr, m = marshal.model_inits(full, "add_landmarks_model")           # the shapes are checked here; the one array: sent, then logged from
+        first = self._e._append_model(arr, m)
         if self.log is not None:
-            self.log.record_model_append(full)
-        return [first + b + 1 for b in range(len(full))]
+            self.log.record_model_append([(o.model, np.array(o.z[:]), np.array(o.R[:]).reshape(2, 2, order="F"), o.signature) for o in arr[:m]])
+        return [first + b + 1 for b in range(m)]
 
     def predict_model(self, steps):
         """Motion under observe_model's conventions: one step (model, u, M) or a list of them, model EKF_MOTION_TURN_DRIVE (1: u = (d, deg)
@@ -471,24 +466,14 @@ class _EkfBase:
         steps = list(steps)
         if len(steps) == 3 and np.isscalar(steps[0]):          # one step
             steps = [tuple(steps)]
-        steps = [tuple(st) for st in steps]
         if not 1 <= len(steps) <= L.EKF_PREDICT_MODEL_MAX:
             raise ValueError("predict_model: between 1 and %d steps" % L.EKF_PREDICT_MODEL_MAX)
-        full = []
-        for st in steps:
-            if len(st) != 3:
-                raise ValueError("predict_model: a step is (model, u, M)")
-            model = int(st[0])
-            if model not in L.EKF_MOTION_INPUTS:
-                raise ValueError("predict_model: model is EKF_MOTION_TURN_DRIVE (1), EKF_MOTION_ARC (2) or EKF_MOTION_POSE_DELTA (3)")
-            nu = L.EKF_MOTION_INPUTS[model]
-            Mm = np.asarray(st[2], dtype=np.float64)
-            if Mm.size != nu * nu:
-                raise ValueError("predict_model: M is %d x %d for this model" % (nu, nu))
-            full.append((model, _vec(st[1], nu).copy(), Mm.reshape(nu, nu).copy()))
-        self._e.predict_model(full)
+        arr, m = marshal.motions(steps, known_models=True)                  # the shapes are checked here; the one array: sent, then logged from
+        self._e._predict_model(arr, m)
         if self.log is not None:
-            self.log.record_model_predict(full)
+            sizes = [L.EKF_MOTION_INPUTS[o.model] for o in arr[:m]]   # u and M of the size the model reads
+            self.log.record_model_predict([(o.model, np.array(o.u[:nu]), np.array(o.M[:]).reshape(3, 3, order="F")[:nu, :nu])
+                                           for o, nu in zip(arr[:m], sizes)])
 
     @staticmethod
     def _motion_steps(model, cols, M):
@@ -555,16 +540,8 @@ class _EkfBase:
         gate_match, gate_new = float(gate_match), float(gate_new)
         if not gate_new >= gate_match:
             raise ValueError("measure_model: gate_new >= gate_match is required (and neither is NaN)")
-        entries = [tuple(e) for e in entries]
-        if not 1 <= len(entries) <= L.EKF_ASSOCIATE_MODEL_MAX:
-            raise ValueError("measure_model: between 1 and %d entries" % L.EKF_ASSOCIATE_MODEL_MAX)
-        for e in entries:
-            if len(e) not in (3, 4):
-                raise ValueError("measure_model: an entry is (model, z, R) or (model, z, R, signature)")
-            if int(e[0]) not in (L.EKF_MODEL_RANGE_BEARING, L.EKF_MODEL_RELATIVE_XY):
-                raise ValueError("measure_model: model is EKF_MODEL_RANGE_BEARING (1) or EKF_MODEL_RELATIVE_XY (4): a one-row model does "
-                                 "not start a landmark")
-        res = self._e.associate_model([dict(model=int(e[0]), z=e[1], R=e[2], gate=gate_match) for e in entries])
+        entries, scan = self._measure_scan("measure_model", entries, L.EKF_ASSOCIATE_MODEL_MAX, gate_match)
+        res = self._e.associate_model(scan)
         kinds = []
         for k in range(len(entries)):
             if int(res["within_gate"][k]) == 1:
@@ -579,13 +556,33 @@ class _EkfBase:
                 lm = int(res["best"][k])
                 if lm not in owner or float(res["d2_best"][k]) < float(res["d2_best"][owner[lm]]):
                     owner[lm] = k
+        return self._measure_carry_out(entries, kinds, {k: lm for lm, k in owner.items()}, gate_match, wait)
+
+    @staticmethod
+    def _measure_scan(who, entries, cap, gate_match):
+        """The opening measure_model and measure_model_joint share: the entries as tuples, checked -- between 1 and cap of them, (model,
+        z, R) or (model, z, R, signature), models 1 and 4 -- and the scan that ONE associate_model call takes, gate = gate_match."""
+        entries = [tuple(e) for e in entries]
+        if not 1 <= len(entries) <= cap:
+            raise ValueError("%s: between 1 and %d entries" % (who, cap))
+        for e in entries:
+            if len(e) not in (3, 4):
+                raise ValueError("%s: an entry is (model, z, R) or (model, z, R, signature)" % who)
+            if int(e[0]) not in (L.EKF_MODEL_RANGE_BEARING, L.EKF_MODEL_RELATIVE_XY):
+                raise ValueError("%s: model is EKF_MODEL_RANGE_BEARING (1) or EKF_MODEL_RELATIVE_XY (4): a one-row model does not start a "
+                                 "landmark" % who)
+        return entries, [dict(model=int(e[0]), z=e[1], R=e[2], gate=gate_match) for e in entries]
+
+    def _measure_carry_out(self, entries, kinds, paired, gate_match, wait):
+        """The close they share: entry k with a landmark in `paired` ({entry: 0-based landmark}) goes to observe_model(..., gate=gate_match),
+        in scan order; then ALL entries whose kind is 'new' to one add_landmarks_model call; the rest is discarded.  Returns [(kind,
+        landmark)] per entry, landmark 1-based and 0 for a discarded one."""
         out = [None] * len(entries)
         fresh = []
         for k, (kind, e) in enumerate(zip(kinds, entries)):
-            lm = int(res["best"][k])
-            if kind == "matched" and owner[lm] == k:
-                self.observe_model(int(e[0]), e[1], e[2], [lm + 1], gate=gate_match, wait=wait)
-                out[k] = ("matched", lm + 1)
+            if k in paired:
+                self.observe_model(int(e[0]), e[1], e[2], [paired[k] + 1], gate=gate_match, wait=wait)
+                out[k] = ("matched", paired[k] + 1)
             elif kind == "new":
                 fresh.append(k)
             else:
@@ -629,16 +626,7 @@ class _EkfBase:
             raise ValueError("measure_model_joint: joint_p lies strictly between 0 and 1")
         if int(beam) != beam or beam < 1:
             raise ValueError("measure_model_joint: beam is a whole number >= 1")
-        entries = [tuple(e) for e in entries]
-        if not 1 <= len(entries) <= L.EKF_JOINT_MAX:
-            raise ValueError("measure_model_joint: between 1 and %d entries" % L.EKF_JOINT_MAX)
-        for e in entries:
-            if len(e) not in (3, 4):
-                raise ValueError("measure_model_joint: an entry is (model, z, R) or (model, z, R, signature)")
-            if int(e[0]) not in (L.EKF_MODEL_RANGE_BEARING, L.EKF_MODEL_RELATIVE_XY):
-                raise ValueError("measure_model_joint: model is EKF_MODEL_RANGE_BEARING (1) or EKF_MODEL_RELATIVE_XY (4): a one-row model "
-                                 "does not start a landmark")
-        scan = [dict(model=int(e[0]), z=e[1], R=e[2], gate=gate_match) for e in entries]
+        entries, scan = self._measure_scan("measure_model_joint", entries, L.EKF_JOINT_MAX, gate_match)
         res = self._e.associate_model(scan, want_d2=True)
         cands, kinds = [], []
         for k in range(len(entries)):
@@ -667,21 +655,8 @@ class _EkfBase:
             alive.sort(key=order)
             if len(alive) > beam:
                 alive, truncated = alive[:int(beam)], True
-        winner = dict(zip(searched, alive[0][0])) if searched else {}
-        out = [None] * len(entries)
-        fresh = []
-        for k, (kind, e) in enumerate(zip(kinds, entries)):
-            if winner.get(k, -1) >= 0:
-                self.observe_model(int(e[0]), e[1], e[2], [winner[k] + 1], gate=gate_match, wait=wait)
-                out[k] = ("matched", winner[k] + 1)
-            elif kind == "new":
-                fresh.append(k)
-            else:
-                out[k] = ("discarded", 0)
-        if fresh:
-            for k, number in zip(fresh, self.add_landmarks_model([entries[k] for k in fresh])):
-                out[k] = ("new", number)
-        return out, truncated
+        winner = {k: c for k, c in zip(searched, alive[0][0]) if c >= 0} if searched else {}
+        return self._measure_carry_out(entries, kinds, winner, gate_match, wait), truncated
 
     def _push_params(self):
         pass

@@ -309,3 +309,15 @@ def test_engine_and_slam_layers_marshal_an_observation_once(monkeypatch):
         with pytest.raises(L.EkfError) as info:
             f.fix_landmark(1, [0.0, 0.0], None, wait=True)
         assert info.value.status == L.EKF_ERR_STATE and "observe_linear" in str(info.value) and len(f.log.edits) == 4
+        # the log holds what the library received, field by field: the four calls above and one with every block general
+        rec.fail = 0
+        f.observe_linear([1.5, -2.5], [[0.5, 0.1], [0.2, 0.25]], Hr, [4, 2], Hl, gate=9.0, wrap=(0, 1))
+        sent = [c for c in rec.calls if c[0] == "observe"]
+        del sent[4]                                           # the refused one
+        assert len(sent) == len(f.log.edits) == 5 and sent[4][3] == [1.0, 4.0, 2.0, 5.0, 3.0, 6.0] and sent[4][2] == [0.5, 0.2, 0.1, 0.25]
+        for (_, z, Rc, Hrc, lm, Hlc, gate, wrap, rows, _), (_, _, idx, zl, Rl), q in zip(sent, f.log.edits, range(5)):
+            o = f.log.observations[q]
+            assert zl.tolist() == z and Rl.reshape(-1, order="F").tolist() == Rc and o["Hr"].reshape(-1, order="F").tolist() == Hrc
+            assert [k - 1 for k in idx.tolist()] + [-1] * (2 - idx.size) == lm
+            assert [o["Hl"][b].reshape(-1, order="F").tolist() for b in range(2)] == Hlc
+            assert (o["gate"], o["wrap"].tolist(), o["rows"]) == (gate, wrap, rows)

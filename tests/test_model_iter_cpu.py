@@ -458,3 +458,15 @@ def test_engine_and_slam_layers_marshal_an_iterated_observation_once(monkeypatch
         with pytest.raises(L.EkfError) as info:
             f.observe_range(1, 0.0, 0.5, wait=True, iterations=3)
         assert info.value.status == L.EKF_ERR_STATE and "observe_model_iterated" in str(info.value) and len(f.log.edits) == m
+        # the log holds what the library received, field by field: the eight iterated calls above and one with a general R
+        rec.fail = 0
+        f.observe_model_iterated(L.EKF_MODEL_RELATIVE_XY, [1.5, -2.5], [[0.5, 0.1], [0.2, 0.25]], [4], gate=9.0, iterations=7, tol=0.125)
+        sent = [c for c in rec.calls if c[0] == "observe_iterated"]
+        del sent[8]                                           # the refused one
+        assert len(sent) == 9 and len(f.log.edits) == 18 and sent[8][3] == [0.5, 0.2, 0.1, 0.25]
+        for (_, model, z, Rc, lm, anchor, gate, _, iterations, tol, _), (_, _, idx, zl, Rl), q in zip(sent, f.log.edits[9:], range(9, 18)):
+            o = f.log.model_iterations[q]
+            assert zl.tolist() == z and Rl.reshape(-1, order="F").tolist() == Rc
+            assert (o["model"], o["gate"], o["iterations"], o["tol"]) == (model, gate, iterations, tol)
+            assert [k - 1 for k in idx.tolist()] + [-1] * (2 - idx.size) == lm
+            assert (anchor == [0.0, 0.0] and o["anchor"] is None) if idx.size else o["anchor"].tolist() == anchor

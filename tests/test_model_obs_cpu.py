@@ -365,3 +365,14 @@ def test_engine_and_slam_layers_marshal_a_model_observation_once(monkeypatch):
         with pytest.raises(L.EkfError) as info:
             f.observe_range(1, 0.0, 0.5, wait=True)
         assert info.value.status == L.EKF_ERR_STATE and "observe_model" in str(info.value) and len(f.log.edits) == 7
+        # the log holds what the library received, field by field: the seven calls above and one with a general R
+        rec.fail = 0
+        f.observe_model(L.EKF_MODEL_RELATIVE_XY, [1.5, -2.5], [[0.5, 0.1], [0.2, 0.25]], [4], gate=9.0)
+        sent = [c for c in rec.calls if c[0] == "observe"]
+        del sent[7]                                           # the refused one
+        assert len(sent) == len(f.log.edits) == 8 and sent[7][3] == [0.5, 0.2, 0.1, 0.25]
+        for (_, model, z, Rc, lm, anchor, gate, _), (_, _, idx, zl, Rl), q in zip(sent, f.log.edits, range(8)):
+            o = f.log.model_observations[q]
+            assert zl.tolist() == z and Rl.reshape(-1, order="F").tolist() == Rc and (o["model"], o["gate"]) == (model, gate)
+            assert [k - 1 for k in idx.tolist()] + [-1] * (2 - idx.size) == lm
+            assert (anchor == [0.0, 0.0] and o["anchor"] is None) if idx.size else o["anchor"].tolist() == anchor
