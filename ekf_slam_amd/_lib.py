@@ -167,6 +167,7 @@ SIGNATURES = {
     "ekf_associate_model": (_i32, [_vp, ctypes.POINTER(EkfModelObs), _i64, ctypes.POINTER(EkfModelMatch), _dp]),
     "ekf_joint_innovation": (_i32, [_vp, ctypes.POINTER(EkfModelObs), _i64, ctypes.POINTER(_i64), _i64, ctypes.POINTER(EkfJointResult), _dp, _dp,
                                     _dp]),
+    "ekf_observe_model_joint": (_i32, [_vp, ctypes.POINTER(EkfModelObs), _i64, ctypes.POINTER(_i64), _d, ctypes.POINTER(EkfJointResult), _dp, _dp]),
     "ekf_predict_model": (_i32, [_vp, ctypes.POINTER(EkfMotion), _i64]),
     "ekf_motion_evaluate": (_i32, [_i32, _dp, _dp, _dp, _dp, _dp]),
     "ekf_diag_poke_device_signature": (_i32, [_vp, _i64, _d]),

@@ -200,7 +200,7 @@ struct ekf_handle {
     NearestEntry *d_nearest = nullptr, *h_nearest = nullptr;
     // ekf_merge_landmarks_batch: its private pair ring (EKF_MERGE_BATCH_MAX F64 slots: G ring, then K ring), one record per constraint on
     // the device and in pinned memory, the snapshot of x / strip / Prr / the diagonal blocks it restores when a pair is irregular
-    // (allocated at the first batch call and kept)
+    // (allocated at the first batch call and kept); ekf_observe_model_joint puts its pairs into the same ring (host/joint_update.h)
     double *d_mring = nullptr, *d_mrec = nullptr, *h_mrec = nullptr, *d_msnap = nullptr;
     // ---- linear observations (ekf_observe_linear / ekf_linear_innovation) ----
     // two records on the device and in pinned memory (the update-step's, then the probe's; behind them in the pinned area the two counters
@@ -225,6 +225,9 @@ struct ekf_handle {
     char *d_jout = nullptr, *h_jout = nullptr;
     double *d_jS = nullptr, *h_jS = nullptr;
     hipEvent_t ev_joint = nullptr;
+    // ---- a scan's pairings applied as one joint update (ekf_observe_model_joint) ----
+    // what k_joint_factor hands k_gather_joint (allocated at the first call and kept); its pairs go to d_mring above
+    JointBlock *d_jblock = nullptr;
     // ---- timers, what ekf_destroy releases, the error text ----
     KernelTimer timers[EKF_KERNEL_COUNT];
     std::vector<void *> allocs;       // device memory (dalloc), pinned memory (halloc) and events (new_event): what ekf_destroy releases

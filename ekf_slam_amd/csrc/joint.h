@@ -1,5 +1,5 @@
 // Fragment of kernels.hip (included there, inside its anonymous namespace, after associate_model.h): the joint compatibility of a scan's
-// pairings (ekf_joint_innovation): k_joint_innovation.
+// pairings (ekf_joint_innovation): k_joint_innovation, and its phases as functions that k_joint_factor (joint_update.h) calls too.
 #pragma once
 
 // ---------------------------------------------------------------------------------------------------
@@ -20,43 +20,51 @@
 //   (5) lane 0: the prefixes, summed over y^2 in ascending row order, and the record.
 // LDS: S dense, 64 x 64 doubles = 32 KiB, and 3.6 KiB of per-pairing operands.
 // ---------------------------------------------------------------------------------------------------
-constexpr int kJointBlock = 256;
+#ifndef EKF_JOINT_LANES
+#define EKF_JOINT_LANES 256
+#endif
+constexpr int kJointBlock = EKF_JOINT_LANES;     // (a host emulation runs the phases with ONE lane: every phase is a loop strided by it)
 
+// The LDS of one hypothesis and phases (1)-(4) as ONE text: k_joint_innovation below and k_joint_factor (joint_update.h) both call
+// joint_phases, so S, nu, L and y = L^-1 nu are the same bits in both by construction.
+struct JointLds {
+    double A[kJointRows * kJointRows];
+    double y[kJointRows];
+    double Hr[kJointMax][6], Ht[kJointMax][4], strips[kJointMax][6], prr[9];
+    int64_t lm[kJointMax];                          // by scan index: the hypothesis
+    int pair_of[kJointMax];                         // by scan index: the pairing, -1 = left out
+    int scan_of[kJointMax];                         // by pairing: the scan index
+    int posed[kJointMax];                           // by pairing
+};
+struct JointCounts { int np, dof, bad; };           // pairings, real rows, the first irregular pairing (np: none)
+
+// hyp: the hypothesis's m entries; nu_out / S_out: this hypothesis's 2m / 4m^2 entries, or nullptr.  Called by all kJointBlock lanes.
 template <typename TS>
-__global__ __launch_bounds__(kJointBlock) void k_joint_innovation(DevState st, JointArgs a, const int64_t *__restrict__ hyp,
-                                                                  JointRecord *__restrict__ out, double *__restrict__ d2_prefix,
-                                                                  double *__restrict__ nu_out, double *__restrict__ S_out) {
-    __shared__ double A[kJointRows * kJointRows];
-    __shared__ double y[kJointRows];
-    __shared__ double Hr[kJointMax][6], Ht[kJointMax][4], strips[kJointMax][6], prr[9];
-    __shared__ int64_t lm[kJointMax];               // by scan index: the hypothesis
-    __shared__ int pair_of[kJointMax];              // by scan index: the pairing, -1 = left out
-    __shared__ int scan_of[kJointMax];              // by pairing: the scan index
-    __shared__ int posed[kJointMax];                // by pairing
-    const int tid = threadIdx.x;
+__device__ __forceinline__ JointCounts joint_phases(const DevState &st, const JointArgs &a, const int64_t *__restrict__ hyp, JointLds &sh,
+                                                    int tid, double *__restrict__ nu_out, double *__restrict__ S_out) {
+    double *A = sh.A, *y = sh.y;
     const int m = a.m, cur = a.cur;
-    const int64_t hi = blockIdx.x;
     constexpr int ld = kJointRows;
 
-    if (tid < m) lm[tid] = hyp[hi * m + tid];
-    if (tid >= 64 && tid < 73) prr[tid - 64] = st.prr[cur][tid - 64];
+    for (int k = tid; k < m; k += kJointBlock) sh.lm[k] = hyp[k];
+    for (int q = tid; q < 9; q += kJointBlock) sh.prr[q] = st.prr[cur][q];
     __syncthreads();
     int np = 0, dof = 0;                            // pairings, real rows: every lane counts them alike
     for (int k = 0; k < m; ++k)
-        if (lm[k] >= 0) { ++np; dof += (a.e[k].model == 1 || a.e[k].model == 4) ? 2 : 1; }
+        if (sh.lm[k] >= 0) { ++np; dof += (a.e[k].model == 1 || a.e[k].model == 4) ? 2 : 1; }
     const int n = 2 * np;
 
     // (1) per pairing
-    if (tid < m) {
+    for (int ks = tid; ks < m; ks += kJointBlock) {       // (on the device one trip at most, m <= kJointMax <= kJointBlock: the break below says so)
         int p = -1;
-        if (lm[tid] >= 0) {
+        if (sh.lm[ks] >= 0) {
             p = 0;
-            for (int k = 0; k < tid; ++k) p += lm[k] >= 0;
+            for (int k = 0; k < ks; ++k) p += sh.lm[k] >= 0;
         }
-        pair_of[tid] = p;
+        sh.pair_of[ks] = p;
         if (p >= 0) {
-            const AssocModelEntry &e = a.e[tid];
-            const int64_t i = lm[tid];
+            const AssocModelEntry &e = a.e[ks];
+            const int64_t i = sh.lm[ks];
             const double *__restrict__ x = st.x[cur];
             const double *__restrict__ strip = st.strip[cur] + 2 * i;
             const double *__restrict__ dg = st.diag[st.dcur] + 3 * i;
@@ -68,14 +76,15 @@ __global__ __launch_bounds__(kJointBlock) void k_joint_innovation(DevState st, J
             const double strip6[6] = { strip[0], strip[1], strip[ldm], strip[ldm + 1], strip[2 * ldm], strip[2 * ldm + 1] };
             const double diag3[3] = { dg[0], dg[1], dg[2] };
             double S[4], nu[2], hr[6], ht[4];
-            posed[p] = ekfm::joint_pairing(e.model, e.z, e.R, p9, strip6, diag3, xr, l, hr, ht, S, nu) ? 1 : 0;
-            scan_of[p] = tid;
-            for (int q = 0; q < 6; ++q) { Hr[p][q] = hr[q]; strips[p][q] = strip6[q]; }
-            for (int q = 0; q < 4; ++q) Ht[p][q] = ht[q];
+            sh.posed[p] = ekfm::joint_pairing(e.model, e.z, e.R, p9, strip6, diag3, xr, l, hr, ht, S, nu) ? 1 : 0;
+            sh.scan_of[p] = ks;
+            for (int q = 0; q < 6; ++q) { sh.Hr[p][q] = hr[q]; sh.strips[p][q] = strip6[q]; }
+            for (int q = 0; q < 4; ++q) sh.Ht[p][q] = ht[q];
             y[2 * p] = nu[0]; y[2 * p + 1] = nu[1];
             A[(2 * p) * ld + 2 * p] = S[0]; A[(2 * p) * ld + 2 * p + 1] = S[1];       // the block whole: S[1] is what the record reports
             A[(2 * p + 1) * ld + 2 * p] = S[2]; A[(2 * p + 1) * ld + 2 * p + 1] = S[3];
         }
+        if (kJointBlock >= kJointMax) break;
     }
     __syncthreads();
 
@@ -84,10 +93,10 @@ __global__ __launch_bounds__(kJointBlock) void k_joint_innovation(DevState st, J
         int pa = 1;
         while (pa * (pa + 1) / 2 <= idx) ++pa;
         const int pb = idx - pa * (pa - 1) / 2;
-        const int64_t ra = 2 * lm[scan_of[pa]], rb = 2 * lm[scan_of[pb]];
+        const int64_t ra = 2 * sh.lm[sh.scan_of[pa]], rb = 2 * sh.lm[sh.scan_of[pb]];
         double pab[4], Sab[4];
         for (int q = 0; q < 4; ++q) pab[q] = pmm_low_chain<TS>(st, a.pstart, a.npend, ra + (q >> 1), rb + (q & 1));
-        ekfm::joint_cross_block(Hr[pa], Ht[pa], Hr[pb], Ht[pb], prr, strips[pa], strips[pb], pab, Sab);
+        ekfm::joint_cross_block(sh.Hr[pa], sh.Ht[pa], sh.Hr[pb], sh.Ht[pb], sh.prr, sh.strips[pa], sh.strips[pb], pab, Sab);
         for (int q = 0; q < 4; ++q) A[(2 * pa + (q >> 1)) * ld + 2 * pb + (q & 1)] = Sab[q];
     }
     __syncthreads();
@@ -95,26 +104,26 @@ __global__ __launch_bounds__(kJointBlock) void k_joint_innovation(DevState st, J
     // (3) nu and S by scan index, before the factorisation overwrites them
     if (nu_out)
         for (int i = tid; i < 2 * m; i += kJointBlock) {
-            const int p = pair_of[i >> 1];
-            nu_out[hi * 2 * m + i] = p >= 0 ? y[2 * p + (i & 1)] : 0.0;
+            const int p = sh.pair_of[i >> 1];
+            nu_out[i] = p >= 0 ? y[2 * p + (i & 1)] : 0.0;
         }
     if (S_out)
         for (int e = tid; e < 4 * m * m; e += kJointBlock) {
             const int i = e % (2 * m), j = e / (2 * m);             // column-major
-            const int pi = pair_of[i >> 1], pj = pair_of[j >> 1];
+            const int pi = sh.pair_of[i >> 1], pj = sh.pair_of[j >> 1];
             double v = i == j ? 1.0 : 0.0;
             if (pi >= 0 && pj >= 0) {
                 const int ri = 2 * pi + (i & 1), rj = 2 * pj + (j & 1);
                 v = (ri >= rj || pi == pj) ? A[ri * ld + rj] : A[rj * ld + ri];
             }
-            S_out[hi * 4 * m * m + e] = v;
+            S_out[e] = v;
         }
     __syncthreads();
 
     // (4) the factorisation, up to the first pairing that has no d2
     int bad = np;                                   // the first irregular pairing; np: none
     for (int p = np - 1; p >= 0; --p)
-        if (!posed[p]) bad = p;
+        if (!sh.posed[p]) bad = p;
     for (int k = 0; k < 2 * bad; ++k) {
         double lkk;
         if (!ekfm::joint_pivot(A[k * ld + k], lkk)) { bad = k >> 1; break; }       // every lane reads the same pivot: a uniform exit
@@ -123,19 +132,34 @@ __global__ __launch_bounds__(kJointBlock) void k_joint_innovation(DevState st, J
         ekfm::joint_factor_update(A, ld, y, n, k, tid, kJointBlock);
         __syncthreads();
     }
+    const JointCounts cnt = { np, dof, bad };
+    return cnt;
+}
 
-    // (5) the prefixes and the record
-    if (tid == 0) {
-        double acc = 0.0;
-        for (int k = 0; k < m; ++k) {
-            const int p = pair_of[k];
-            if (p >= 0) acc = p < bad ? ekfm::joint_prefix_add(acc, y[2 * p], y[2 * p + 1]) : NAN;
-            if (d2_prefix) d2_prefix[hi * m + k] = acc;
-        }
-        JointRecord r;
-        r.d2 = acc; r.dof = dof; r.pairings = np;
-        r.outcome = bad < np ? 0 : 1;
-        r.first_irregular = bad < np ? scan_of[bad] : -1;
-        out[hi] = r;
+// (5) by ONE lane: the prefixes (d2_prefix: this hypothesis's m entries, or nullptr), summed over y^2 in ascending row order, and the record
+__device__ __forceinline__ JointRecord joint_record(const JointLds &sh, const JointCounts &cnt, int m, double *__restrict__ d2_prefix) {
+    double acc = 0.0;
+    for (int k = 0; k < m; ++k) {
+        const int p = sh.pair_of[k];
+        if (p >= 0) acc = p < cnt.bad ? ekfm::joint_prefix_add(acc, sh.y[2 * p], sh.y[2 * p + 1]) : NAN;
+        if (d2_prefix) d2_prefix[k] = acc;
     }
+    JointRecord r;
+    r.d2 = acc; r.dof = cnt.dof; r.pairings = cnt.np;
+    r.outcome = cnt.bad < cnt.np ? 0 : 1;
+    r.first_irregular = cnt.bad < cnt.np ? sh.scan_of[cnt.bad] : -1;
+    return r;
+}
+
+template <typename TS>
+__global__ __launch_bounds__(kJointBlock) void k_joint_innovation(DevState st, JointArgs a, const int64_t *__restrict__ hyp,
+                                                                  JointRecord *__restrict__ out, double *__restrict__ d2_prefix,
+                                                                  double *__restrict__ nu_out, double *__restrict__ S_out) {
+    __shared__ JointLds sh;
+    const int tid = threadIdx.x;
+    const int m = a.m;
+    const int64_t hi = blockIdx.x;
+    const JointCounts cnt = joint_phases<TS>(st, a, hyp + hi * m, sh, tid, nu_out ? nu_out + hi * 2 * m : nullptr,
+                                             S_out ? S_out + hi * 4 * m * m : nullptr);
+    if (tid == 0) out[hi] = joint_record(sh, cnt, m, d2_prefix ? d2_prefix + hi * m : nullptr);
 }

@@ -186,6 +186,24 @@ struct JointRecord {
     int32_t dof, pairings, outcome, first_irregular;
 };
 
+// The joint UPDATE of one hypothesis (joint_update.h, ekf_observe_model_joint): k_joint_factor leaves what k_gather_joint needs in one device
+// block -- with L L' = S the factor of the stacked S, y = L^-1 nu, the Jacobian blocks of every pairing and the robot part
+// W_r = L^-1 G_r, G_r(2p + r, t) = H_p^r(r, :) Prr(:, t) + H_p^t(r, :) strip(t, l_p)' -- and k_gather_joint forms W = L^-1 H P column by column.
+struct JointBlock {
+    double L[kJointRows * kJointRows];      // the lower triangle, leading dimension kJointRows; rows below 2 np
+    double y[kJointRows];
+    double Wr[kJointRows][3];
+    double Hr[kJointMax][6], Ht[kJointMax][4];   // by pairing, row-major 2 x 3 and 2 x 2
+    int64_t lm[kJointMax];                  // by pairing: the landmark
+    int32_t np, pad;                        // pairings (rows: 2 np)
+    JointRecord rec;
+};
+struct JointUpdateArgs {
+    int64_t n_mm;             // active landmark-block size (2N)
+    int32_t cur;
+    int32_t np;               // pairings, as the host read them back in the record: the pairs go to ring slots 0 .. np - 1
+};
+
 // ---- map edits, and the observations that share the constraint's device code ----
 // A constraint between two landmarks (constrain.h): "l_i - l_j was observed as (d0, d1) with noise covariance R".
 struct ConstrainArgs {

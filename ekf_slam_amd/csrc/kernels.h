@@ -226,6 +226,16 @@ hipError_t launch_model_iter_probe(const DevState &st, const IterModelArgs &a, d
 hipError_t launch_joint_innovation(const DevState &st, const JointArgs &a, const int64_t *hyp, int nh, JointRecord *out, double *d2_prefix,
                                    double *nu, double *S, int storage, hipStream_t s);
 
+// The joint UPDATE of one hypothesis (joint_update.h, ekf_observe_model_joint), on a flushed state (a.npend == 0).
+// launch_joint_factor: k_joint_factor, one workgroup, read-only -- k_joint_innovation's phases for the one hypothesis hyp (device, a.m entries),
+// so out / nu / S are what launch_joint_innovation reports for it bit for bit, and blk (device) takes what the gather needs.
+hipError_t launch_joint_factor(const DevState &st, const JointArgs &a, const int64_t *hyp, JointBlock *blk, JointRecord *out, double *nu, double *S,
+                               int storage, hipStream_t s);
+// launch_gather_joint: k_gather_joint over the padded landmark block.  `st` is a by-value copy of the handle's DevState whose Gp / Kp / pcap
+// name a PRIVATE F64 pair ring (Gp32 == nullptr): the a.np pairs go to its slots 0 .. a.np - 1, x / Prr / strip into buffer a.cur ^ 1, every
+// landmark's live diagonal block into buffer dcur ^ 1; the caller flips both and lets ONE pass apply the pairs to the tiles.
+hipError_t launch_gather_joint(const DevState &st, const JointUpdateArgs &a, const JointBlock *blk, int storage, hipStream_t s);
+
 // ---- state I/O (launch/state_io.h) ----
 // dense (column-major, n x n, device) <-> tiled
 hipError_t launch_unpack_dense(const DevState &st, int cur, int64_t n_mm, double *dense, int storage, hipStream_t s);

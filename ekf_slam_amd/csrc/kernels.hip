@@ -51,6 +51,7 @@ namespace {
 #include "model_iter.h"       // ... relinearised on lane 0 (the iterated EKF update): k_gather_model_iter, k_model_iter_probe
 #include "associate_model.h" // a scan against the whole map under the models' conventions: k_assoc_model, k_assoc_model_reduce
 #include "joint.h"            // a scan's pairings judged jointly, a hypothesis per workgroup: k_joint_innovation
+#include "joint_update.h"     // ... and applied as one joint update: k_joint_factor, k_gather_joint
 #include "merge_pass.h"       // the fused downdate-and-compact pass of a batch of merges: k_merge_pass
 #include "nearest.h"          // the candidate search in front of a merge: k_nearest
 
@@ -61,5 +62,5 @@ namespace {
 #include "launch/steps.h"         // predict, append, gather, row-panels, association
 #include "launch/pass_select.h"   // which pass instance runs: a pure function, no HIP
 #include "launch/passes.h"        // launch_downdate, the row copies behind an asynchronous pass
-#include "launch/edits.h"         // compact, constrain, linear observation, joint innovation, merge pass, nearest
+#include "launch/edits.h"         // compact, constrain, linear observation, joint innovation and joint update, merge pass, nearest
 #include "launch/state_io.h"      // dense <-> tiled, block reads, low-rank load, digest

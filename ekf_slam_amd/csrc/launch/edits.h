@@ -1,5 +1,5 @@
 // Fragment of kernels.hip, the launchers of the map edits: landmark removal (compact.h), a constraint between two landmarks and its
-// chained form (constrain.h), a linear observation (linear_obs.h) and one through a model (model_obs.h), the joint innovation of a scan's pairings (joint.h), the fused pass of a batch of merges (merge_pass.h), the candidate search (nearest.h).
+// chained form (constrain.h), a linear observation (linear_obs.h) and one through a model (model_obs.h), the joint innovation of a scan's pairings (joint.h) and their joint update (joint_update.h), the fused pass of a batch of merges (merge_pass.h), the candidate search (nearest.h).
 #pragma once
 
 namespace {
@@ -150,6 +150,30 @@ hipError_t launch_joint_innovation(const DevState &st, const JointArgs &a, const
         return hipErrorInvalidValue;
     return with_storage(storage, [&](auto ts) {
         hipLaunchKernelGGL(k_joint_innovation<decltype(ts)>, dim3((unsigned)nh), dim3(kJointBlock), 0, s, st, a, hyp, out, d2_prefix, nu, S);
+    });
+}
+
+hipError_t launch_joint_factor(const DevState &st, const JointArgs &a, const int64_t *hyp, JointBlock *blk, JointRecord *out, double *nu, double *S,
+                               int storage, hipStream_t s) {
+    // launch_joint_innovation's checks for one hypothesis on a flushed state
+    if (a.m < 1 || a.m > kJointMax || !hyp || !blk || !out || a.N < 0 || 2 * a.N > st.ldm || a.npend != 0 || a.pstart < 0 || a.pstart >= st.pcap ||
+        st.tm.world != 1)
+        return hipErrorInvalidValue;
+    return with_storage(storage, [&](auto ts) {
+        hipLaunchKernelGGL(k_joint_factor<decltype(ts)>, dim3(1), dim3(kJointBlock), 0, s, st, a, hyp, blk, out, nu, S);
+    });
+}
+
+hipError_t launch_gather_joint(const DevState &st, const JointUpdateArgs &a, const JointBlock *blk, int storage, hipStream_t s) {
+    // the pairs inside the private F64 ring, the padded block inside the strip, every tile held here
+    if (!blk || a.np < 1 || a.np > kJointMax || a.np > st.pcap || a.n_mm < 2 || (a.n_mm & 1) || st.tm.padded(a.n_mm) > st.ldm || st.Gp32 || st.Kp32 ||
+        !st.Gp || !st.Kp || st.tm.world != 1)
+        return hipErrorInvalidValue;
+    const unsigned grid = (unsigned)cdiv(st.tm.padded(a.n_mm), kBlock);
+    return with_storage(storage, [&](auto ts) {
+        using TS = decltype(ts);
+        if (a.np <= 8) hipLaunchKernelGGL((k_gather_joint<TS, 8>), dim3(grid), dim3(kBlock), 0, s, st, a, blk);
+        else hipLaunchKernelGGL((k_gather_joint<TS, 32>), dim3(grid), dim3(kBlock), 0, s, st, a, blk);
     });
 }
 

@@ -530,6 +530,32 @@ class Engine:
             res["S"] = S.transpose(0, 2, 1).copy()      # column-major blocks
         return res
 
+    # ---- ... and applied as ONE joint update (include/ekfslam.h: ekf_observe_model_joint) ----
+    def observe_model_joint(self, entries, landmarks, gate=float("inf"), want_nu=False, want_S=False):
+        """One hypothesis of joint_innovation APPLIED as one joint update: entries as for associate_model (the per-entry gate is not
+        read), landmarks the 0-based landmark each observation is paired with or -1 = left out.  All pairings are linearised once at the
+        live state and stacked; x' = x + W' y, P' = P - W' W with W = L^-1 H P, L L' = S -- applied only if the joint d2 <= gate.  The
+        pending pairs are flushed first and ONE pass over P applies all pairings; nothing is waited for at the end.  Returns {'d2',
+        'dof', 'pairings', 'outcome', 'first_irregular'} -- joint_innovation's for that hypothesis on the flushed state, bit for bit;
+        outcome EKF_LINEAR_APPLIED or EKF_LINEAR_GATED -- plus 'nu' (2m) and 'S' (2m x 2m) by scan index where asked.  A pairing with
+        no d2 raises EkfError and changes nothing (ekf_observe_model_joint)."""
+        arr, m = marshal.scan_obs(entries)
+        return self._observe_joint(arr, m, landmarks, gate, want_nu, want_S)
+
+    def _observe_joint(self, arr, m, landmarks, gate=float("inf"), want_nu=False, want_S=False):
+        """ekf_observe_model_joint on the built scan (arr, m)."""
+        lms = np.asarray(landmarks, dtype=np.float64).reshape(-1)
+        if lms.size != m:
+            raise ValueError("observe_model_joint: one landmark (or -1) per entry of the scan")
+        if not np.all(lms == np.floor(lms)):
+            raise ValueError("observe_model_joint: landmark indices are whole numbers")
+        idx, _ = marshal.index_array(lms.tolist())
+        res = L.EkfJointResult()
+        nu = np.zeros(2 * m) if want_nu else None
+        S = np.zeros(4 * m * m) if want_S else None
+        self._check(self.lib.ekf_observe_model_joint(self.h, arr, m, idx, float(gate), ctypes.byref(res), p_or_null(nu), p_or_null(S)))
+        return marshal.joint_result(res, m, nu, S)
+
     # ---- motion steps through a model with its true Jacobians (include/ekfslam.h: ekf_predict_model) ----
     def predict_model(self, steps):
         """A chain of motion steps: steps = [(model, u, M), ...] with model EKF_MOTION_TURN_DRIVE (u = d, turn), EKF_MOTION_ARC (u = arc

@@ -204,6 +204,17 @@ def iterated_result(first, it):
     return out
 
 
+def joint_result(res, m, nu=None, S=None):
+    """One struct ekf_joint_result as a dict, with 'nu' (2m) and 'S' (2m x 2m, from the column-major buffer) by scan index where given."""
+    out = {"d2": float(res.d2), "dof": int(res.dof), "pairings": int(res.pairings), "outcome": int(res.outcome),
+           "first_irregular": int(res.first_irregular)}
+    if nu is not None:
+        out["nu"] = nu
+    if S is not None:
+        out["S"] = S.reshape(2 * m, 2 * m).T.copy()
+    return out
+
+
 # ---- the library's pure host functions ----
 def host_call(name, lib, *args):
     """One of the functions that take no handle (the kernels' own text, compiled for the host): `lib` None is the loaded library; a

@@ -608,7 +608,26 @@ class _EkfBase:
         res["first_irregular"] = res["first_irregular"] + 1
         return res
 
-    def measure_model_joint(self, entries, gate_match, gate_new, joint_p=0.99, beam=64, wait=False):
+    def observe_model_joint(self, entries, landmarks, gate=float("inf"), want_nu=False, want_S=False):
+        """One hypothesis of joint_innovation APPLIED as ONE joint update: entries as for associate_model ([{'model', 'z', 'R'}, ...],
+        models 1-4), landmarks the 1-based landmark each observation is paired with, 0 = left out.  All pairings are linearised once, at
+        the live state, and stacked: the update that runs is the one whose joint d2 is reported, it does not depend on scan order, and it
+        costs one pass over P however many pairings there are (sequential observe_model steps relinearise after each one).  Applied only
+        if the joint d2 <= gate.  The pending pairs are flushed first.  Returns {'d2', 'dof', 'pairings', 'outcome', 'first_irregular'}
+        (first_irregular 1-based, 0 = none) plus 'nu' and 'S' by scan index where asked; a pairing with no d2 raises EkfError and
+        changes nothing (ekf_observe_model_joint).  Unsharded handles only.  The reference has no such method."""
+        numbers = self._landmark_numbers("observe_model_joint", *list(landmarks))
+        if any(k < 0 for k in numbers):
+            raise ValueError("observe_model_joint: a landmark is 1-based, 0 = the observation is left out")
+        arr, m = marshal.scan_obs(entries)                                  # the one array: sent, then logged from
+        res = dict(self._e._observe_joint(arr, m, [k - 1 for k in numbers], gate, want_nu, want_S))
+        res["first_irregular"] = res["first_irregular"] + 1
+        if self.log is not None:
+            self.log.record_model_observation_joint(
+                [(o.model, np.array(o.z[:]), np.array(o.R[:]).reshape(2, 2, order="F"), k) for o, k in zip(arr[:m], numbers)], gate)
+        return res
+
+    def measure_model_joint(self, entries, gate_match, gate_new, joint_p=0.99, beam=64, wait=False, joint_update=False):
         """measure_model with the ambiguity discard replaced by a JOINT-compatibility search: entries, gate_match, gate_new and wait as
         there.  ONE associate_model(..., want_d2=True) call: the candidates of an entry are the landmarks with individual d2 <= gate_match,
         at most the 4 closest (by (d2, landmark)); an entry without a candidate is new where d2_best > gate_new (or the map is empty) and
@@ -618,7 +637,9 @@ class _EkfBase:
         more than `beam` survive, the best by (pairings descending, joint d2 ascending, hypothesis ascending) are kept.  The winner is the
         survivor first in that order: its pairings go to observe_model(..., gate=gate_match) in scan order, then ALL new entries to one
         add_landmarks_model call; the rest is discarded.  Returns ([(kind, landmark)] per entry as measure_model, whether the beam cut
-        the search).  Everything that changes the state goes through those two logged methods, so a replayed log reproduces the run."""
+        the search).  Everything that changes the state goes through those two logged methods, so a replayed log reproduces the run.
+        joint_update=True applies the winner's pairings by ONE observe_model_joint(gate=inf) call instead -- the update whose joint d2 the
+        search tested, one pass over P -- which is logged as well."""
         gate_match, gate_new, joint_p = float(gate_match), float(gate_new), float(joint_p)
         if not gate_new >= gate_match:
             raise ValueError("measure_model_joint: gate_new >= gate_match is required (and neither is NaN)")
@@ -656,6 +677,14 @@ class _EkfBase:
             if len(alive) > beam:
                 alive, truncated = alive[:int(beam)], True
         winner = {k: c for k, c in zip(searched, alive[0][0]) if c >= 0} if searched else {}
+        if joint_update and winner:
+            # the winner's pairings in scan order as one joint update, then the close without them: the new entries and the discards
+            self.observe_model_joint([dict(model=int(e[0]), z=e[1], R=e[2]) for e in (entries[k] for k in sorted(winner))],
+                                     [winner[k] + 1 for k in sorted(winner)])
+            out = self._measure_carry_out(entries, ["discarded" if k in winner else kind for k, kind in enumerate(kinds)], {}, gate_match, wait)
+            for k in winner:
+                out[k] = ("matched", winner[k] + 1)
+            return out, truncated
         return self._measure_carry_out(entries, kinds, winner, gate_match, wait), truncated
 
     def _push_params(self):

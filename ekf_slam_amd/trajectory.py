@@ -28,13 +28,15 @@ FORMAT_MODEL = "ekfslam-trajectory-5"
 FORMAT_APPEND = "ekfslam-trajectory-6"
 FORMAT_PREDICT = "ekfslam-trajectory-7"
 FORMAT_ITERATED = "ekfslam-trajectory-8"
+FORMAT_JOINT = "ekfslam-trajectory-9"
 EDIT_KINDS = ("remove", "constrain", "merge", "merge_batch")        # what record_edit takes
 OBSERVE = "observe"                                                  # record_observation's
 OBSERVE_MODEL = "observe_model"                                      # record_model_observation's
 APPEND_MODEL = "append_model"                                        # record_model_append's
 PREDICT_MODEL = "predict_model"                                      # record_model_predict's
 OBSERVE_MODEL_ITERATED = "observe_model_iterated"                    # record_model_observation_iterated's
-_FORMATS = (FORMAT, FORMAT_EDITS, FORMAT_BATCH, FORMAT_OBSERVE, FORMAT_MODEL, FORMAT_APPEND, FORMAT_PREDICT, FORMAT_ITERATED)
+OBSERVE_MODEL_JOINT = "observe_model_joint"                          # record_model_observation_joint's
+_FORMATS = (FORMAT, FORMAT_EDITS, FORMAT_BATCH, FORMAT_OBSERVE, FORMAT_MODEL, FORMAT_APPEND, FORMAT_PREDICT, FORMAT_ITERATED, FORMAT_JOINT)
 _STEP_ARRAYS = ("u", "obs_ptr", "obs", "lm_ptr", "lm_index", "lm_loc")
 _EDIT_ARRAYS = ("edit_step", "edit_kind", "edit_ptr", "edit_idx", "edit_delta", "edit_R")
 
@@ -90,6 +92,13 @@ _KINDS_TABLE = (
                                                             iterations=o["iterations"], tol=o["tol"]),
           "model_iterations", "iter", (_Field("model", "model", _I, ()), _ANCHOR, _Field("gate", "gate", _F, ()),
                                        _Field("iterations", "iterations", _I, ()), _Field("tol", "tol", _F, ()))),
+    # observe_model_joint: one scan applied as one joint update, idx empty, the first value of the delta slot = the gate (R zero); per scan
+    # its entries (model, z, R, landmark), the landmark 1-based and 0 = left out
+    _Kind(OBSERVE_MODEL_JOINT, 9,
+          lambda e, idx0, d, R, entries: e.observe_model_joint([dict(model=m, z=z, R=Rk) for m, z, Rk, _ in entries],
+                                                               [lm - 1 for _, _, _, lm in entries], gate=float(d[0])),
+          "model_joints", "joint",
+          (_Field("model", 0, _I, ()), _Field("z", 1, _F, (2,)), _Field("R", 2, _F, (2, 2)), _Field("landmark", 3, _I, ())), True),
 )
 _KINDS = tuple(k.name for k in _KINDS_TABLE)
 _KIND = {k.name: k for k in _KINDS_TABLE}
@@ -142,6 +151,7 @@ class TrajectoryLog:
         self.model_appends = {}     # position in self.edits of an 'append_model' edit -> [(model, z (2), R (2x2), signature), ...]
         self.model_predicts = {}    # position in self.edits of a 'predict_model' edit -> [(model, u (2 or 3), M (2x2 or 3x3)), ...]
         self.model_iterations = {}  # position in self.edits of an 'observe_model_iterated' edit -> {model, anchor or None, gate, iterations, tol}
+        self.model_joints = {}      # position in self.edits of an 'observe_model_joint' edit -> [(model, z (2), R (2x2), landmark 1-based or 0), ...]
         self.observations = {}      # position in self.edits of an 'observe' edit -> {Hr (2x3), Hl (2x2x2), gate, wrap (2), rows}
 
     def __len__(self):
@@ -219,6 +229,17 @@ class TrajectoryLog:
         self._record(OBSERVE_MODEL_ITERATED, self._landmarks("record_model_observation_iterated", list(landmarks), 2), z, R, dict(
             model=int(model), anchor=None if anchor is None else np.asarray(anchor, dtype=np.float64).reshape(2).copy(), gate=float(gate),
             iterations=int(iterations), tol=float(tol)))
+
+    def record_model_observation_joint(self, entries, gate=float("inf")):
+        """One scan applied as ONE joint update (observe_model_joint of ekf_slam_amd/slam.py) made now, i.e. after the len(self) steps
+        recorded so far: entries = [(model, z, R, landmark), ...], at least one, z padded to two values and R 2 x 2 as the wrapper hands
+        them to the engine, the landmark 1-based and 0 where the observation is left out; then the joint gate."""
+        lms = self._landmarks("record_model_observation_joint", [e[3] for e in entries])
+        ents = [(int(m), np.asarray(z, dtype=np.float64).reshape(2).copy(), np.asarray(R, dtype=np.float64).reshape(2, 2).copy(), int(lm))
+                for (m, z, R, _), lm in zip(entries, lms)]
+        if not ents:
+            raise ValueError("record_model_observation_joint: at least one entry")
+        self._record(OBSERVE_MODEL_JOINT, z=(float(gate),), payload=ents)
 
     def record_model_append(self, entries):
         """One scan of new landmarks (add_landmarks_model of ekf_slam_amd/slam.py) made now, i.e. after the len(self) steps recorded so

@@ -574,6 +574,37 @@ int32_t ekf_joint_innovation(ekf_handle *h, const ekf_model_obs *obs, int64_t m,
                              double *d2_prefix       /* nh x m, may be NULL */,
                              double *nu              /* nh x 2m, may be NULL */,
                              double *S               /* nh x (2m x 2m column-major), may be NULL */);
+/* ... and APPLIED as a whole: one hypothesis of ekf_joint_innovation as ONE joint update.  All np paired observations are linearised once, at
+ * the live state, and stacked; with L L' = S (the Cholesky factor of the stacked S), W = L^-1 H P (2 np rows) and y = L^-1 nu
+ *     x' = x + W' y        P' = P - W' W
+ * the symmetric form, with no back substitution: its pairs are (K_p, G_p) = (rows 2p, 2p + 1 of W, twice).  Unlike np sequential
+ * ekf_observe_model steps, which relinearise at the state the previous one left, the update that runs is the one whose d2 was tested, and it
+ * does not depend on scan order; it costs two small launches and ONE pass over P whatever np is.
+ * obs, m, lm: exactly one hypothesis of ekf_joint_innovation -- m in 1 .. EKF_JOINT_MAX, models 1-4, a one-row model as the pair with the
+ * exactly empty second row, the per-entry gate and the anchor ignored, no landmark twice.  res (required), nu and S are bit for bit what
+ * ekf_joint_innovation reports for that hypothesis on the flushed state (with F64 tiles also against a call made before the flush, which is
+ * bit-exact there).  res->outcome:
+ *   EKF_LINEAR_APPLIED    joint d2 <= gate (+inf: no gate): the update above ran.
+ *   EKF_LINEAR_GATED      d2 > gate: EKF_OK, nothing changed beyond the flush.
+ *   EKF_LINEAR_IRREGULAR  a pairing has no d2: EKF_ERR_STATE naming its scan index (res->first_irregular), nothing changed beyond the flush --
+ *                         the record is read back and waited for before anything is written -- and the handle goes on working.
+ * Neither is counted by ekf_linear_rejections: the decision is taken on the host.  No pairing at all (every lm[k] == -1): EKF_OK, applied,
+ * d2 = 0, no launch of its own and no flush (the rungs below come first: a recorded predict is carried out).
+ * The call does not enter the handle's pending ring.  It takes ekf_merge_landmarks_batch's route: the pending pairs are applied first (a
+ * flush, which retires a pass in flight), its own np pairs go to that call's private F64 ring (EKF_MERGE_BATCH_MAX >= EKF_JOINT_MAX slots,
+ * allocated at first use, counted by ekf_device_bytes), and one F64-arithmetic pass applies them in place on the main stream -- float tiles
+ * are rounded once per entry, whatever cfg.pass_arith.  Afterwards ekf_pending is 0 and ekf_downdate_kernel_name reports that pass with
+ * pairs = np.  The call does not wait at its end.  Launches count under EKF_KERNEL_ASSOCIATE, _GATHER and _DOWNDATE.
+ * Order of a call: ekf_joint_innovation's argument refusals in its order (nh = 1), a NaN gate (EKF_ERR_INVALID_ARG); ekf_observe_linear's
+ * rungs (world > 1: EKF_ERR_INVALID_ARG, a lone cfg.force_sharded shard works; a sharded correction between begin and finish:
+ * EKF_ERR_STATE; a recorded predict carried out); a landmark >= N (EKF_ERR_INDEX); allocations; the flush; the factor launch, its readback
+ * and the decision; the gather launch; the pass. */
+int32_t ekf_observe_model_joint(ekf_handle *h, const ekf_model_obs *obs, int64_t m,
+                                const int64_t *lm       /* m: 0-based landmark, or -1 = left out */,
+                                double gate             /* apply only if joint d2 <= gate; +inf = none */,
+                                ekf_joint_result *res   /* required */,
+                                double *nu              /* 2m, may be NULL */,
+                                double *S               /* 2m x 2m column-major, may be NULL */);
 /* The MOTION step under the same conventions: "the robot moved by u through the model, and u has the covariance M".  ekf_predict keeps the
  * reference's step (F(1,3), F(2,3) at the pre-motion heading and without pi/180, Q = (W C) W' of rank one) and is consistent with none of
  * the calls above: a filter driven through ekf_observe_model / ekf_append_model moves here.  With p = x(0:2), theta = x(2) in degrees,

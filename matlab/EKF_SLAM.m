@@ -348,6 +348,18 @@ classdef EKF_SLAM < handle
                 res = h.gateway('joint_innovation', model, z, R, hyp);
             end
         end
+        function res = observeModelJoint(h, model, z, R, lm, gate)
+            % One hypothesis of jointInnovation APPLIED as one joint update: lm(k) is the landmark observation k (model(k), z(k, :),
+            % R(:, :, k)) is paired with, 0 = left out.  All pairings are linearised once, at the live state, and stacked -- the update
+            % whose joint d2 is reported, independent of scan order, one pass over P -- and applied only if d2 <= gate (default Inf).
+            % res = [d2 dof pairings outcome firstIrregular], outcome 1 applied, 2 gated; a pairing without a d2 is an error and changes
+            % nothing.  The pending corrections are applied first.  Not a method of the reference.
+            if nargin < 6 || isempty(gate), gate = Inf; end
+            model = double(model(:)); m = numel(model);
+            z = double(reshape(z, [], 2));
+            R = double(R); if size(R, 3) == 1, R = repmat(R, [1 1 m]); end
+            res = h.gateway('observe_model_joint', model, z, R, double(lm(:)), double(gate));
+        end
         function merges = fuseDuplicatesBatched(h, gate, R, maxMerges)
             % fuseDuplicates with the pairs of one search fused in one mergeLandmarksBatch call: search; walk the candidates in
             % (d2, k) order and take [partner(k) k] when k is not yet a keep or a drop and partner(k) is not yet a drop (a keep may

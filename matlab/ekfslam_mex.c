@@ -25,7 +25,8 @@
 /* The map-editing entry points (ekf_remove_landmarks; ekf_constrain_landmarks, ekf_merge_landmarks, ekf_landmark_distance;
  * ekf_nearest_landmarks; ekf_merge_landmarks_batch) the linear observation (ekf_observe_linear), the model observation
  * (ekf_observe_model), the append through a model (ekf_append_model), the association of a scan under the models' conventions
- * (ekf_associate_model), the joint compatibility of a scan's pairings (ekf_joint_innovation), the relinearised model observation
+ * (ekf_associate_model), the joint compatibility of a scan's pairings (ekf_joint_innovation) and their joint update
+ * (ekf_observe_model_joint), the relinearised model observation
  * (ekf_observe_model_iterated) and the motion steps under them (ekf_predict_model) are the ones this gateway can live without: bound weakly, so that the gateway still links against a libekfslam (or a stand-in) that
  * predates them; their commands then raise a MATLAB error instead. */
 #if defined(__GNUC__)
@@ -42,6 +43,7 @@
 #pragma weak ekf_predict_model
 #pragma weak ekf_joint_innovation
 #pragma weak ekf_observe_model_iterated
+#pragma weak ekf_observe_model_joint
 #define HAVE_REMOVE_LANDMARKS (ekf_remove_landmarks != 0)
 #define HAVE_CONSTRAIN_LANDMARKS (ekf_constrain_landmarks != 0)
 #define HAVE_MERGE_LANDMARKS (ekf_merge_landmarks != 0)
@@ -55,6 +57,7 @@
 #define HAVE_PREDICT_MODEL (ekf_predict_model != 0)
 #define HAVE_JOINT_INNOVATION (ekf_joint_innovation != 0)
 #define HAVE_OBSERVE_MODEL_ITERATED (ekf_observe_model_iterated != 0)
+#define HAVE_OBSERVE_MODEL_JOINT (ekf_observe_model_joint != 0)
 #else
 #define HAVE_REMOVE_LANDMARKS 1
 #define HAVE_CONSTRAIN_LANDMARKS 1
@@ -69,6 +72,7 @@
 #define HAVE_PREDICT_MODEL 1
 #define HAVE_JOINT_INNOVATION 1
 #define HAVE_OBSERVE_MODEL_ITERATED 1
+#define HAVE_OBSERVE_MODEL_JOINT 1
 #endif
 
 static void need(int nrhs, int want, const char *cmd) {
@@ -479,6 +483,42 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
         check(h, rc);
         plhs[0] = out;
         if (prefix) plhs[1] = prefix;
+        return;
+    }
+    if (!strcmp(cmd, "observe_model_joint")) {    /* res = (h, model m x 1 (1..4), z m x 2, R 2 x 2 x m, lm m x 1, gate): the scan's pairings applied as ONE joint
+                                                     update; lm(k) = the landmark (1-based) observation k is paired with, 0 = left out; applied only if the
+                                                     joint d2 <= gate; res 1 x 5 = [d2 dof pairings outcome firstIrregular] (outcome 1 applied, 2 gated) */
+        need(nrhs, 7, cmd);
+        if (!HAVE_OBSERVE_MODEL_JOINT) mexErrMsgIdAndTxt("ekfslam:usage", "observe_model_joint: this libekfslam has no ekf_observe_model_joint");
+        const mwSize m = prhs[2] ? mxGetNumberOfElements(prhs[2]) : 0;
+        if (m < 1 || m > EKF_JOINT_MAX) mexErrMsgIdAndTxt("ekfslam:usage", "observe_model_joint: between 1 and %d observations in one call", EKF_JOINT_MAX);
+        if (!mxGetPr(prhs[2]) || !prhs[3] || mxGetM(prhs[3]) != m || mxGetNumberOfElements(prhs[3]) != 2 * m || !mxGetPr(prhs[3]))
+            mexErrMsgIdAndTxt("ekfslam:usage", "observe_model_joint: z needs m x 2 elements, one row per entry of model");
+        if (!prhs[4] || mxGetNumberOfElements(prhs[4]) != 4 * m || !mxGetPr(prhs[4]))
+            mexErrMsgIdAndTxt("ekfslam:usage", "observe_model_joint: R needs 2 x 2 x m elements");
+        if (!prhs[5] || mxGetNumberOfElements(prhs[5]) != m || !mxGetPr(prhs[5]))
+            mexErrMsgIdAndTxt("ekfslam:usage", "observe_model_joint: lm needs m elements, one per entry of model");
+        if (!prhs[6] || mxGetNumberOfElements(prhs[6]) != 1 || !mxGetPr(prhs[6]))
+            mexErrMsgIdAndTxt("ekfslam:usage", "observe_model_joint: gate is one number (Inf: no gate)");
+        ekf_model_obs o[EKF_JOINT_MAX];
+        int64_t lm[EKF_JOINT_MAX];
+        for (mwSize k = 0; k < m; ++k) {
+            o[k].model = (int32_t)mxGetPr(prhs[2])[k]; o[k].reserved = 0;
+            o[k].z[0] = mxGetPr(prhs[3])[k]; o[k].z[1] = mxGetPr(prhs[3])[m + k];       /* column-major m x 2 */
+            for (int q = 0; q < 4; ++q) o[k].R[q] = mxGetPr(prhs[4])[4 * k + q];
+            o[k].lm[0] = o[k].lm[1] = -1;
+            o[k].anchor[0] = o[k].anchor[1] = 0.0;
+            o[k].gate = HUGE_VAL;
+            const double v = mxGetPr(prhs[5])[k];                                       /* 1-based -> 0-based, 0 (left out) -> -1 */
+            if (!(v >= 0.0 && v < 9.0e15 && (double)(int64_t)v == v))                   /* (no libm call: the gateway links without it) */
+                mexErrMsgIdAndTxt("ekfslam:usage", "observe_model_joint: lm holds landmark numbers (1-based), 0 = left out");
+            lm[k] = (int64_t)v - 1;
+        }
+        ekf_joint_result res;
+        check(h, ekf_observe_model_joint(h, o, (int64_t)m, lm, mxGetPr(prhs[6])[0], &res, NULL, NULL));
+        plhs[0] = mxCreateDoubleMatrix(1, 5, mxREAL);
+        mxGetPr(plhs[0])[0] = res.d2; mxGetPr(plhs[0])[1] = (double)res.dof; mxGetPr(plhs[0])[2] = (double)res.pairings;
+        mxGetPr(plhs[0])[3] = (double)res.outcome; mxGetPr(plhs[0])[4] = (double)(res.first_irregular + 1);
         return;
     }
     if (!strcmp(cmd, "predict_model")) {          /* (h, model m x 1 (1..3), u m x 3, M 3 x 3 x m): a chain of motion steps with their true Jacobians, in order,
