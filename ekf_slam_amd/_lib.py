@@ -82,6 +82,15 @@ class EkfModelMatch(ctypes.Structure):
     _fields_ = [("best", _i64), ("second", _i64), ("d2_best", _d), ("d2_second", _d), ("within_gate", _i64), ("irregular", _i64)]
 
 
+EKF_ASSIGN_MODEL_MAX = 32
+EKF_ASSIGN_CANDIDATES = 32
+
+
+class EkfModelAssigned(ctypes.Structure):
+    """struct ekf_model_assigned (include/ekfslam.h)."""
+    _fields_ = [("landmark", _i64), ("d2", _d), ("ncand", _i64), ("reserved", _i64)]
+
+
 EKF_JOINT_MAX = 32
 EKF_JOINT_HYP_MAX = 256
 
@@ -165,6 +174,8 @@ SIGNATURES = {
     "ekf_append_model": (_i32, [_vp, ctypes.POINTER(EkfModelInit), _i64, ctypes.POINTER(_i64)]),
     "ekf_model_invert": (_i32, [_i32, _dp, _dp, _dp, _dp, _dp]),
     "ekf_associate_model": (_i32, [_vp, ctypes.POINTER(EkfModelObs), _i64, ctypes.POINTER(EkfModelMatch), _dp]),
+    "ekf_assign_model": (_i32, [_vp, ctypes.POINTER(EkfModelObs), _i64, ctypes.POINTER(EkfModelAssigned), ctypes.POINTER(EkfModelMatch),
+                                ctypes.POINTER(_i64), _dp, _dp]),
     "ekf_joint_innovation": (_i32, [_vp, ctypes.POINTER(EkfModelObs), _i64, ctypes.POINTER(_i64), _i64, ctypes.POINTER(EkfJointResult), _dp, _dp,
                                     _dp]),
     "ekf_observe_model_joint": (_i32, [_vp, ctypes.POINTER(EkfModelObs), _i64, ctypes.POINTER(_i64), _d, ctypes.POINTER(EkfJointResult), _dp, _dp]),

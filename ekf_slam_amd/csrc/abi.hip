@@ -15,6 +15,7 @@
 #include "host/model_iter.h"   // ... relinearised on the device, the iterated EKF update: observe_model_iterated, model_innovation_iterated, model_iterate
 #include "host/append_model.h" // landmarks that start from such a model's inverse, a scan per launch: append_model, model_invert
 #include "host/associate_model.h" // which landmark a sighting belongs to, a scan per call: associate_model
+#include "host/assign_model.h" // ... and the scan assigned to the map one-to-one: assign_model
 #include "host/joint.h"        // ... and a whole scan's pairings judged jointly, nh hypotheses per call: joint_innovation
 #include "host/joint_update.h" // ... and applied as ONE joint update behind a flush: observe_model_joint
 #include "host/predict_model.h" // motion steps with true Jacobians, a chain per launch: predict_model, motion_evaluate

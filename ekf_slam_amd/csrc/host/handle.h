@@ -218,6 +218,12 @@ struct ekf_handle {
     int64_t am_nblk_cap = 0;
     char *d_amall = nullptr, *h_amall = nullptr;
     hipEvent_t ev_amodel = nullptr;
+    // ---- the scan assigned to the map one-to-one (ekf_assign_model) ----
+    // one candidate list per workgroup (am_nblk_cap per observation) and the selected list per observation on the device; the result block
+    // on the device and in pinned memory, and the event behind a call's readback (the Match2 records per workgroup are d_amparts above)
+    ekfm::CandList *d_aslists = nullptr, *d_assel = nullptr;
+    AssignResult *d_asres = nullptr, *h_asres = nullptr;
+    hipEvent_t ev_assign = nullptr;
     // ---- the joint compatibility of a scan's pairings (ekf_joint_innovation) ----
     // the hypotheses on the device and in pinned memory; the records, prefixes and nu of a call (joint_out_bytes) likewise, and the event behind
     // a call's readback; the stacked S of every hypothesis, 8 MiB on either side, allocated when first asked for

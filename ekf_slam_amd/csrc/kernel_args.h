@@ -165,6 +165,27 @@ struct AssocModelArgs {
     AssocModelEntry e[kAssocModelMax];
 };
 
+// k_assign_candidates / k_assign_select / k_assign_solve (assign_model.h): the scan of k_assoc_model assigned to the map one-to-one.  The
+// first launch takes AssocModelArgs as k_assoc_model does; the solver needs only the gates.  Everything a call returns lies in ONE block,
+// so that one copy brings it back: the head (out, total, match) always, the lists behind it where they are asked for.
+constexpr int kAssignCandidates = 32;
+struct AssignSolveArgs {
+    int32_t m, pad;
+    double gate[kAssocModelMax];
+};
+struct AssignedRecord {        // ekf_model_assigned, field by field
+    int64_t landmark;
+    double d2;
+    int64_t ncand, reserved;
+};
+struct AssignResult {
+    AssignedRecord out[kAssocModelMax];
+    double total, pad;
+    int64_t match[kAssocModelMax * 6];                        // kAssocModelMax records of ekfm::Match2 (= ekf_model_match)
+    int64_t cand[kAssocModelMax * kAssignCandidates];         // row-major, -1 behind a row's ncand entries
+    double cand_d2[kAssocModelMax * kAssignCandidates];       // ... +inf there
+};
+
 // k_joint_innovation (joint.h): nh <= kJointHypMax hypotheses over one scan of m <= kJointMax observations, each pairing observation k
 // with landmark hyp[i * m + k] (or -1: left out), judged JOINTLY -- one workgroup per hypothesis, read-only.  The scan travels in the
 // argument block as k_assoc_model's does (the gate is not read); the hypotheses are a device array.  The cross blocks P(l_a, l_b) come

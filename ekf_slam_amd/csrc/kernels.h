@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "device_math.h"
+#include "assign_math.h"
 #include "kernel_args.h"
 #include "layout.h"
 
@@ -125,6 +126,12 @@ hipError_t launch_assoc_merge(const DevState &st, const double *recv, int world,
 // d2_all (device): nullptr, or m x N row-major, NaN where a pair has no d2.  Two launches ordered by the stream.
 hipError_t launch_assoc_model(const DevState &st, const AssocModelArgs &a, ekfm::Match2 *partials, ekfm::Match2 *out, double *d2_all,
                               hipStream_t s);
+
+// k_assign_candidates / k_assign_select / k_assign_solve (assign_model.h): the same scan assigned one-to-one, read-only.  partials as above;
+// lists (device): m * ceil(N / kAssocBlock) candidate lists, one per workgroup of the first launch; sel (device): kAssocModelMax lists, the
+// second launch's; res (device): the block everything a call returns is left in.  Three launches ordered by the stream.
+hipError_t launch_assign_model(const DevState &st, const AssocModelArgs &a, ekfm::Match2 *partials, ekfm::CandList *lists, ekfm::CandList *sel,
+                               AssignResult *res, hipStream_t s);
 
 // ---- the passes over P (launch/passes.h; launch/pass_select.h decides which kernel instance runs) ----
 // nx (sharded handles): ALSO extract the row-panel of landmark-block rows j, j + 1 into send (layout of launch_rowpanel) from the updated

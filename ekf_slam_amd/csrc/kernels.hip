@@ -50,6 +50,7 @@ namespace {
 #include "model_obs.h"        // ... through a range / bearing / relative-position model evaluated at the live x: k_gather_model, k_model_probe
 #include "model_iter.h"       // ... relinearised on lane 0 (the iterated EKF update): k_gather_model_iter, k_model_iter_probe
 #include "associate_model.h" // a scan against the whole map under the models' conventions: k_assoc_model, k_assoc_model_reduce
+#include "assign_model.h"    // ... and assigned to it one-to-one: k_assign_candidates, k_assign_select, k_assign_solve
 #include "joint.h"            // a scan's pairings judged jointly, a hypothesis per workgroup: k_joint_innovation
 #include "joint_update.h"     // ... and applied as one joint update: k_joint_factor, k_gather_joint
 #include "merge_pass.h"       // the fused downdate-and-compact pass of a batch of merges: k_merge_pass

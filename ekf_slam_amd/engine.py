@@ -492,6 +492,24 @@ class Engine:
             res["d2_all"] = d2
         return res
 
+    # ---- ... and assigned to the map one-to-one (include/ekfslam.h: ekf_assign_model) ----
+    def assign_model(self, entries, want_candidates=False):
+        """One scan assigned to the whole map, each landmark to at most one observation: entries as for associate_model, every gate
+        finite -- it is the price of leaving the observation out.  Returns 'landmark' (0-based, -1 = left out), 'd2' (that pair's, +inf
+        where left out), 'ncand' (candidates kept: landmarks inside the gate, at most EKF_ASSIGN_CANDIDATES), one array entry per
+        observation; 'total', the minimised sum of the assigned d2 and the gates of the left-out; the six keys of associate_model, the same
+        bits; and with want_candidates 'cand' / 'cand_d2', m x EKF_ASSIGN_CANDIDATES, each row the kept landmarks by (d2, index) with
+        -1 / +inf behind them.  Changes, flushes and retires nothing (ekf_assign_model)."""
+        arr, m = marshal.scan_obs(entries)
+        out, match = (L.EkfModelAssigned * max(m, 1))(), (L.EkfModelMatch * max(m, 1))()
+        total = ctypes.c_double(0.0)
+        cand = np.full((m, L.EKF_ASSIGN_CANDIDATES), -1, dtype=np.int64) if want_candidates else None
+        cand_d2 = np.full((m, L.EKF_ASSIGN_CANDIDATES), np.inf) if want_candidates else None
+        self._check(self.lib.ekf_assign_model(self.h, arr, m, out, match,
+                                              cand.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)) if want_candidates else None,
+                                              _p(cand_d2) if want_candidates else None, ctypes.byref(total)))
+        return marshal.assigned_result(out, match, m, total.value, cand, cand_d2)
+
     # ---- a scan's pairings judged jointly (include/ekfslam.h: ekf_joint_innovation) ----
     def joint_innovation(self, entries, hypotheses, want_prefix=True, want_nu=False, want_S=False):
         """The joint compatibility of a scan's pairings: entries as for associate_model (the gate is not read), hypotheses an nh x m

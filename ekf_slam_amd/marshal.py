@@ -215,6 +215,26 @@ def joint_result(res, m, nu=None, S=None):
     return out
 
 
+MATCH_KEYS = (("best", np.int64), ("second", np.int64), ("d2_best", np.float64), ("d2_second", np.float64), ("within_gate", np.int64),
+              ("irregular", np.int64))
+
+
+def match_result(match, m):
+    """m structs ekf_model_match as {'best', 'second', 'd2_best', 'd2_second', 'within_gate', 'irregular'}, one array entry each."""
+    return {key: np.array([getattr(match[k], key) for k in range(m)], dtype=dt) for key, dt in MATCH_KEYS}
+
+
+def assigned_result(out, match, m, total, cand=None, cand_d2=None):
+    """What ekf_assign_model returned, as arrays with one entry per observation (landmarks 0-based, -1 = left out or none): 'landmark',
+    'd2', 'ncand', the six keys of match_result, the float 'total', and the m x EKF_ASSIGN_CANDIDATES 'cand' / 'cand_d2' where given."""
+    res = {"landmark": np.array([out[k].landmark for k in range(m)], dtype=np.int64), "d2": np.array([out[k].d2 for k in range(m)], dtype=np.float64),
+           "ncand": np.array([out[k].ncand for k in range(m)], dtype=np.int64), "total": float(total)}
+    res.update(match_result(match, m))
+    if cand is not None:
+        res["cand"], res["cand_d2"] = cand, cand_d2
+    return res
+
+
 # ---- the library's pure host functions ----
 def host_call(name, lib, *args):
     """One of the functions that take no handle (the kernels' own text, compiled for the host): `lib` None is the loaded library; a

@@ -207,6 +207,16 @@ class ShardGroup:
                 np.testing.assert_array_equal(r[key], v, err_msg="shards disagree on associate_model's " + key)
         return res[0]
 
+    def assign_model(self, entries, want_candidates=False):
+        """Engine.assign_model on every shard: each assigns the scan from replicated data, no exchange.  The shards must agree bit for
+        bit; returns the first shard's answer."""
+        entries = list(entries)
+        res = [e.assign_model(entries, want_candidates) for e in self.shards]
+        for r in res[1:]:
+            for key, v in res[0].items():
+                np.testing.assert_array_equal(r[key], v, err_msg="shards disagree on assign_model's " + key)
+        return res[0]
+
     def run_threaded(self, fn):
         """fn(shard) on every shard, ONE HOST THREAD PER SHARD, with the exchange hook of transport (d) (include/ekfslam.h) set:
         wherever a library call needs an all-gather -- ekf_correct, ekf_prefetch_rows, the middle of ekf_measure's loop, a batch's

@@ -558,6 +558,42 @@ class _EkfBase:
                     owner[lm] = k
         return self._measure_carry_out(entries, kinds, {k: lm for lm, k in owner.items()}, gate_match, wait)
 
+    def assign_model(self, entries, want_candidates=False):
+        """WHICH observation of a scan gets WHICH landmark when they compete: the one-to-one assignment that minimises the summed d2, with
+        the entry's gate as the price of leaving it out (entries as for associate_model, every gate finite).  Returns 'landmark' (1-based,
+        0 = left out), 'd2', 'ncand', 'total', associate_model's six keys ('best' and 'second' 1-based, 0 = none) and, with
+        want_candidates, 'cand' / 'cand_d2' (m x EKF_ASSIGN_CANDIDATES, 1-based, 0 behind a row's ncand entries).  Changes and flushes
+        nothing, so it is not logged (ekf_assign_model).  The reference has no such method."""
+        res = dict(self._e.assign_model(entries, want_candidates))
+        for key in ("landmark", "best", "second") + (("cand",) if want_candidates else ()):
+            res[key] = res[key] + 1
+        return res
+
+    def measure_model_assigned(self, entries, gate_match, gate_new, wait=False):
+        """measure_model with the ambiguity discard replaced by the global-nearest-neighbour ASSIGNMENT: entries, gate_match, gate_new and
+        wait as there.  ONE assign_model call with gate = gate_match, then per entry
+          matched    it has an assigned landmark;
+          new        no landmark lies inside gate_match (ncand == 0) and d2_best > gate_new, or the map is empty;
+          discarded  everything else: left out by the assignment although a landmark was inside its gate, or between the two gates.
+        The matched entries go to observe_model(..., [landmark], gate=gate_match) in scan order, then ALL new ones to one
+        add_landmarks_model call.  Returns [(kind, landmark)] per entry as measure_model.  Everything that changes the state goes through
+        those two logged methods, so a replayed log reproduces the run.  Unsharded handles only, as observe_model."""
+        gate_match, gate_new = float(gate_match), float(gate_new)
+        if not gate_new >= gate_match:
+            raise ValueError("measure_model_assigned: gate_new >= gate_match is required (and neither is NaN)")
+        entries, scan = self._measure_scan("measure_model_assigned", entries, L.EKF_ASSIGN_MODEL_MAX, gate_match)
+        res = self._e.assign_model(scan)
+        kinds, paired = [], {}
+        for k in range(len(entries)):
+            if int(res["landmark"][k]) >= 0:
+                kinds.append("matched")
+                paired[k] = int(res["landmark"][k])
+            elif int(res["ncand"][k]) == 0 and (int(res["best"][k]) < 0 or float(res["d2_best"][k]) > gate_new):
+                kinds.append("new")
+            else:
+                kinds.append("discarded")
+        return self._measure_carry_out(entries, kinds, paired, gate_match, wait)
+
     @staticmethod
     def _measure_scan(who, entries, cap, gate_match):
         """The opening measure_model and measure_model_joint share: the entries as tuples, checked -- between 1 and cap of them, (model,
@@ -627,7 +663,8 @@ class _EkfBase:
                 [(o.model, np.array(o.z[:]), np.array(o.R[:]).reshape(2, 2, order="F"), k) for o, k in zip(arr[:m], numbers)], gate)
         return res
 
-    def measure_model_joint(self, entries, gate_match, gate_new, joint_p=0.99, beam=64, wait=False, joint_update=False):
+    def measure_model_joint(self, entries, gate_match, gate_new, joint_p=0.99, beam=64, wait=False, joint_update=False,
+                            device_candidates=False):
         """measure_model with the ambiguity discard replaced by a JOINT-compatibility search: entries, gate_match, gate_new and wait as
         there.  ONE associate_model(..., want_d2=True) call: the candidates of an entry are the landmarks with individual d2 <= gate_match,
         at most the 4 closest (by (d2, landmark)); an entry without a candidate is new where d2_best > gate_new (or the map is empty) and
@@ -639,7 +676,9 @@ class _EkfBase:
         add_landmarks_model call; the rest is discarded.  Returns ([(kind, landmark)] per entry as measure_model, whether the beam cut
         the search).  Everything that changes the state goes through those two logged methods, so a replayed log reproduces the run.
         joint_update=True applies the winner's pairings by ONE observe_model_joint(gate=inf) call instead -- the update whose joint d2 the
-        search tested, one pass over P -- which is logged as well."""
+        search tested, one pass over P -- which is logged as well.  device_candidates=True takes the candidates and the best d2 from ONE
+        assign_model(want_candidates=True) call instead: the same landmarks in the same order, so the outcome and the log are the same,
+        and the m x N matrix does not come back to the host."""
         gate_match, gate_new, joint_p = float(gate_match), float(gate_new), float(joint_p)
         if not gate_new >= gate_match:
             raise ValueError("measure_model_joint: gate_new >= gate_match is required (and neither is NaN)")
@@ -648,12 +687,15 @@ class _EkfBase:
         if int(beam) != beam or beam < 1:
             raise ValueError("measure_model_joint: beam is a whole number >= 1")
         entries, scan = self._measure_scan("measure_model_joint", entries, L.EKF_JOINT_MAX, gate_match)
-        res = self._e.associate_model(scan, want_d2=True)
+        res = self._e.assign_model(scan, want_candidates=True) if device_candidates else self._e.associate_model(scan, want_d2=True)
         cands, kinds = [], []
         for k in range(len(entries)):
-            row = np.asarray(res["d2_all"][k], dtype=np.float64)
-            inside = sorted((float(row[i]), int(i)) for i in np.flatnonzero(row <= gate_match))       # (NaN compares false: never a candidate)
-            cands.append([i for _, i in inside[:4]])
+            if device_candidates:
+                cands.append([int(i) for i in res["cand"][k][:min(4, int(res["ncand"][k]))]])          # (already ordered by (d2, landmark))
+            else:
+                row = np.asarray(res["d2_all"][k], dtype=np.float64)
+                inside = sorted((float(row[i]), int(i)) for i in np.flatnonzero(row <= gate_match))   # (NaN compares false: never a candidate)
+                cands.append([i for _, i in inside[:4]])
             if cands[k]:
                 kinds.append("search")
             elif int(res["best"][k]) < 0 or float(res["d2_best"][k]) > gate_new:

@@ -533,6 +533,46 @@ typedef struct ekf_model_match {
 } ekf_model_match;
 int32_t ekf_associate_model(ekf_handle *h, const ekf_model_obs *obs, int64_t m,
                             ekf_model_match *out /* m, required */, double *d2_all /* m x N row-major, may be NULL */);
+/* The step between "score" and "apply": WHICH observation gets WHICH landmark when they compete -- the global-nearest-neighbour assignment
+ * of a scan, decided on the device without the m x N matrix leaving it.
+ *   d2            d2(k, i) is ekf_associate_model's, and so ekf_model_innovation's, bit for bit (the same function on the same operands):
+ *                 pending pairs, a recorded predict (carried out first) and every storage kind included.
+ *   match[k]      where not NULL: the record ekf_associate_model returns for the same scan, bit for bit.
+ *   candidates    of observation k: the landmarks that have a d2 with d2 <= obs[k].gate, ordered by (d2, index) -- smaller d2 first, the
+ *                 lower index on equal d2 -- of which the first EKF_ASSIGN_CANDIDATES are KEPT.  out[k].ncand is how many were kept
+ *                 (match[k].within_gate still counts all of them); cand / cand_d2, where not NULL (both or neither), receive the kept
+ *                 lists, m x EKF_ASSIGN_CANDIDATES row-major, with -1 / +inf in the slots behind ncand.
+ *   assignment    among all injective partial maps a: observation -> landmark whose every pair (k, a_k) is a candidate of k -- over the
+ *                 WHOLE map, not only the kept lists -- one that minimises  J = sum over the assigned d2(k, a_k) + sum over the left-out
+ *                 obs[k].gate:  the gate is the price of leaving an observation out.  out[k].landmark is a_k (0-based) or -1 = left
+ *                 out; out[k].d2 is that pair's d2, the same bits as in cand_d2, or +inf; *total, where not NULL, is J summed in scan
+ *                 order.  Keeping EKF_ASSIGN_CANDIDATES >= m candidates per observation loses nothing: an observation assigned outside
+ *                 its m cheapest landmarks can move to one of them that the other m - 1 leave free, at no higher cost.
+ *   ties          which of several optimal assignments is returned is fixed by the implementation (deterministic: no atomics, nothing that
+ *                 depends on the order in which lanes arrive); beyond that it is contract only as: the host build of the same source
+ *                 (csrc/assign_math.h) returns the same one for the same lists.
+ * Each entry of obs as for ekf_associate_model, except that the gate must be finite.  The call's place in a handle's order is
+ * ekf_associate_model's: it changes and flushes nothing, ekf_pending and every bit of the state stay as found, it runs beside a pass in
+ * flight and waits for the event behind its own readback alone; a recorded predict is carried out first.  Three launches, counted as one
+ * under EKF_KERNEL_ASSOCIATE.  SHARDED handles are supported: every shard computes the same answer from replicated data, no exchange.
+ * N = 0: every observation left out, ncand 0, the lists empty, total = sum of the gates, no launch.
+ * Refused in this order: h, obs or out NULL, m < 1 or m > EKF_ASSIGN_MODEL_MAX; per entry what ekf_associate_model refuses; cand without
+ * cand_d2 or the reverse; a gate that is not finite (EKF_ERR_INVALID_ARG); then a sharded correction between begin and finish
+ * (EKF_ERR_STATE). */
+#define EKF_ASSIGN_MODEL_MAX   32   /* observations per scan (= EKF_ASSOCIATE_MODEL_MAX) */
+#define EKF_ASSIGN_CANDIDATES  32   /* candidates kept per observation                    */
+typedef struct ekf_model_assigned {
+    int64_t landmark;            /* 0-based landmark the observation is assigned to; -1 = left out */
+    double  d2;                  /* that pair's d2; +inf where left out                            */
+    int64_t ncand;               /* candidates kept: min(within_gate, EKF_ASSIGN_CANDIDATES)       */
+    int64_t reserved;            /* 0                                                              */
+} ekf_model_assigned;
+int32_t ekf_assign_model(ekf_handle *h, const ekf_model_obs *obs, int64_t m,
+                         ekf_model_assigned *out        /* m */,
+                         ekf_model_match    *match      /* m, or NULL */,
+                         int64_t            *cand       /* m x EKF_ASSIGN_CANDIDATES row-major, or NULL */,
+                         double             *cand_d2    /* same shape, or NULL (both or neither) */,
+                         double             *total      /* or NULL */);
 /* A scan judged AS A WHOLE: the joint compatibility of its pairings.  ekf_associate_model scores every observation against every landmark
  * one at a time; where the pose is uncertain and the map locally tight several landmarks pass an observation's gate, and only a JOINT test
  * uses that all innovations of a scan share the robot's error.  A hypothesis pairs observation k with landmark hyp[i * m + k] (0-based) or

@@ -295,6 +295,53 @@ classdef EKF_SLAM < handle
                 match = h.gateway('associate_model', model, z, R, gate);
             end
         end
+        function [res, total, cand, candD2] = assignModel(h, model, z, R, gate)
+            % WHICH observation of a scan gets WHICH landmark when they compete: the one-to-one assignment that minimises the summed
+            % d2, with gate(k) (one gate: shared; finite) as the price of leaving observation k out; arguments as for associateModel.
+            % res: one row [landmark d2 ncand best second d2best d2second withinGate irregular] per observation -- the landmark it is
+            % assigned to (0 = left out, d2 = Inf), how many candidates (landmarks with d2 <= gate, at most 32) were kept, and
+            % associateModel's record.  total: the minimised sum.  cand, candD2 (optional): m x 32, row k = the kept candidates of
+            % observation k by (d2, landmark), 0 / Inf behind them.  Decided on the device; changes and flushes nothing.  Not a
+            % method of the reference.
+            model = double(model(:)); m = numel(model);
+            z = double(reshape(z, [], 2));
+            R = double(R); if size(R, 3) == 1, R = repmat(R, [1 1 m]); end
+            gate = double(gate(:)); if isscalar(gate), gate = repmat(gate, m, 1); end
+            if nargout > 2
+                [res, total, cand, candD2] = h.gateway('assign_model', model, z, R, gate);
+            else
+                [res, total] = h.gateway('assign_model', model, z, R, gate);
+            end
+        end
+        function out = measureModelAssigned(h, model, z, R, gateMatch, gateNew, signature)
+            % measureModel with the ambiguity discard replaced by the global-nearest-neighbour ASSIGNMENT: ONE assignModel call with
+            % gate = gateMatch, then: an observation is MATCHED when it has an assigned landmark, NEW when no landmark lies inside
+            % gateMatch (ncand == 0) and d2best > gateNew or the map is empty (gateNew >= gateMatch), DISCARDED otherwise.  The
+            % matched ones go to observeModel(..., landmark, [], gateMatch) in scan order, then ALL new ones to one
+            % addLandmarksModel call.  out: one row [kind landmark] per observation, kind 1 matched, 2 new, 0 discarded
+            % (landmark 0).  Not a method of the reference.
+            if ~(gateNew >= gateMatch), error('EKF_SLAM:measureModelAssigned', 'gateNew >= gateMatch is required'); end
+            model = double(model(:)); m = numel(model);
+            if any(model ~= 1 & model ~= 4), error('EKF_SLAM:measureModelAssigned', 'model is 1 or 4: a one-row model does not start a landmark'); end
+            z = double(reshape(z, [], 2));
+            R = double(R); if size(R, 3) == 1, R = repmat(R, [1 1 m]); end
+            if nargin < 7, signature = []; end
+            res = h.assignModel(model, z, R, gateMatch);
+            kind = zeros(m, 1);
+            kind(res(:, 1) > 0) = 1;
+            kind(kind == 0 & res(:, 3) == 0 & (res(:, 4) == 0 | res(:, 6) > gateNew)) = 2;
+            out = zeros(m, 2);
+            for k = find(kind == 1)'
+                h.observeModel(model(k), z(k, :), R(:, :, k), res(k, 1), [], gateMatch, false);
+                out(k, :) = [1 res(k, 1)];
+            end
+            fresh = find(kind == 2);
+            if ~isempty(fresh)
+                if isempty(signature), sig = []; else, sig = signature(fresh); end
+                out(fresh, 1) = 2;
+                out(fresh, 2) = h.addLandmarksModel(model(fresh), z(fresh, :), R(:, :, fresh), sig);
+            end
+        end
         function out = measureModel(h, model, z, R, gateMatch, gateNew, signature)
             % One scan under observeModel's conventions, observe-or-append (models 1 and 4): ONE associateModel call with
             % gate = gateMatch, then: an observation is MATCHED when exactly one landmark lies inside gateMatch (that landmark, its

@@ -25,7 +25,7 @@
 /* The map-editing entry points (ekf_remove_landmarks; ekf_constrain_landmarks, ekf_merge_landmarks, ekf_landmark_distance;
  * ekf_nearest_landmarks; ekf_merge_landmarks_batch) the linear observation (ekf_observe_linear), the model observation
  * (ekf_observe_model), the append through a model (ekf_append_model), the association of a scan under the models' conventions
- * (ekf_associate_model), the joint compatibility of a scan's pairings (ekf_joint_innovation) and their joint update
+ * (ekf_associate_model) and its one-to-one assignment (ekf_assign_model), the joint compatibility of a scan's pairings (ekf_joint_innovation) and their joint update
  * (ekf_observe_model_joint), the relinearised model observation
  * (ekf_observe_model_iterated) and the motion steps under them (ekf_predict_model) are the ones this gateway can live without: bound weakly, so that the gateway still links against a libekfslam (or a stand-in) that
  * predates them; their commands then raise a MATLAB error instead. */
@@ -40,6 +40,7 @@
 #pragma weak ekf_observe_model
 #pragma weak ekf_append_model
 #pragma weak ekf_associate_model
+#pragma weak ekf_assign_model
 #pragma weak ekf_predict_model
 #pragma weak ekf_joint_innovation
 #pragma weak ekf_observe_model_iterated
@@ -54,6 +55,7 @@
 #define HAVE_OBSERVE_MODEL (ekf_observe_model != 0)
 #define HAVE_APPEND_MODEL (ekf_append_model != 0)
 #define HAVE_ASSOCIATE_MODEL (ekf_associate_model != 0)
+#define HAVE_ASSIGN_MODEL (ekf_assign_model != 0)
 #define HAVE_PREDICT_MODEL (ekf_predict_model != 0)
 #define HAVE_JOINT_INNOVATION (ekf_joint_innovation != 0)
 #define HAVE_OBSERVE_MODEL_ITERATED (ekf_observe_model_iterated != 0)
@@ -69,6 +71,7 @@
 #define HAVE_OBSERVE_MODEL 1
 #define HAVE_APPEND_MODEL 1
 #define HAVE_ASSOCIATE_MODEL 1
+#define HAVE_ASSIGN_MODEL 1
 #define HAVE_PREDICT_MODEL 1
 #define HAVE_JOINT_INNOVATION 1
 #define HAVE_OBSERVE_MODEL_ITERATED 1
@@ -425,6 +428,58 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
             out[4 * m + k] = (double)match[k].within_gate; out[5 * m + k] = (double)match[k].irregular;
         }
         if (all) plhs[1] = all;
+        return;
+    }
+    if (!strcmp(cmd, "assign_model")) {           /* [res, total, cand, candD2] = (h, model m x 1 (1..4), z m x 2, R 2 x 2 x m, gate m x 1, all finite): which
+                                                     observation of a scan gets which landmark when they compete; res m x 9 = [landmark d2 ncand best second
+                                                     d2_best d2_second within_gate irregular], landmarks 1-based and 0 = left out / none; total: the minimised
+                                                     sum; cand, candD2 (third and fourth output, optional): m x 32, row k = the candidates kept for observation k
+                                                     by (d2, landmark), 0 / Inf behind them */
+        need(nrhs, 6, cmd);
+        if (!HAVE_ASSIGN_MODEL) mexErrMsgIdAndTxt("ekfslam:usage", "assign_model: this libekfslam has no ekf_assign_model");
+        const mwSize m = prhs[2] ? mxGetNumberOfElements(prhs[2]) : 0;
+        if (m < 1 || m > EKF_ASSIGN_MODEL_MAX) mexErrMsgIdAndTxt("ekfslam:usage", "assign_model: between 1 and %d observations in one call", EKF_ASSIGN_MODEL_MAX);
+        if (!mxGetPr(prhs[2]) || !prhs[3] || mxGetM(prhs[3]) != m || mxGetNumberOfElements(prhs[3]) != 2 * m || !mxGetPr(prhs[3]))
+            mexErrMsgIdAndTxt("ekfslam:usage", "assign_model: z needs m x 2 elements, one row per entry of model");
+        if (!prhs[4] || mxGetNumberOfElements(prhs[4]) != 4 * m || !mxGetPr(prhs[4]))
+            mexErrMsgIdAndTxt("ekfslam:usage", "assign_model: R needs 2 x 2 x m elements");
+        if (!prhs[5] || mxGetNumberOfElements(prhs[5]) != m || !mxGetPr(prhs[5]))
+            mexErrMsgIdAndTxt("ekfslam:usage", "assign_model: gate needs m elements");
+        ekf_model_obs o[EKF_ASSIGN_MODEL_MAX];
+        ekf_model_assigned as[EKF_ASSIGN_MODEL_MAX];
+        ekf_model_match match[EKF_ASSIGN_MODEL_MAX];
+        static int64_t cand[EKF_ASSIGN_MODEL_MAX * EKF_ASSIGN_CANDIDATES];
+        static double cand_d2[EKF_ASSIGN_MODEL_MAX * EKF_ASSIGN_CANDIDATES];
+        for (mwSize k = 0; k < m; ++k) {
+            o[k].model = (int32_t)mxGetPr(prhs[2])[k]; o[k].reserved = 0;
+            o[k].z[0] = mxGetPr(prhs[3])[k]; o[k].z[1] = mxGetPr(prhs[3])[m + k];       /* column-major m x 2 */
+            for (int q = 0; q < 4; ++q) o[k].R[q] = mxGetPr(prhs[4])[4 * k + q];
+            o[k].lm[0] = o[k].lm[1] = -1;
+            o[k].anchor[0] = o[k].anchor[1] = 0.0;
+            o[k].gate = mxGetPr(prhs[5])[k];
+        }
+        const bool lists = nlhs > 2;
+        double total = 0.0;
+        check(h, ekf_assign_model(h, o, (int64_t)m, as, match, lists ? cand : NULL, lists ? cand_d2 : NULL, &total));
+        plhs[0] = mxCreateDoubleMatrix(m, 9, mxREAL);
+        double *out = mxGetPr(plhs[0]);
+        for (mwSize k = 0; k < m; ++k) {
+            out[k] = (double)(as[k].landmark + 1); out[m + k] = as[k].d2; out[2 * m + k] = (double)as[k].ncand;
+            out[3 * m + k] = (double)(match[k].best + 1); out[4 * m + k] = (double)(match[k].second + 1);
+            out[5 * m + k] = match[k].d2_best; out[6 * m + k] = match[k].d2_second;
+            out[7 * m + k] = (double)match[k].within_gate; out[8 * m + k] = (double)match[k].irregular;
+        }
+        if (nlhs > 1) plhs[1] = mxCreateDoubleScalar(total);
+        if (lists) {
+            plhs[2] = mxCreateDoubleMatrix(m, EKF_ASSIGN_CANDIDATES, mxREAL);
+            mxArray *d2 = nlhs > 3 ? mxCreateDoubleMatrix(m, EKF_ASSIGN_CANDIDATES, mxREAL) : NULL;
+            for (mwSize k = 0; k < m; ++k)
+                for (mwSize s = 0; s < EKF_ASSIGN_CANDIDATES; ++s) {                  /* row-major m x 32 -> column-major */
+                    mxGetPr(plhs[2])[s * m + k] = (double)(cand[k * EKF_ASSIGN_CANDIDATES + s] + 1);
+                    if (d2) mxGetPr(d2)[s * m + k] = cand_d2[k * EKF_ASSIGN_CANDIDATES + s];
+                }
+            if (d2) plhs[3] = d2;
+        }
         return;
     }
     if (!strcmp(cmd, "joint_innovation")) {       /* [res, prefix] = (h, model m x 1 (1..4), z m x 2, R 2 x 2 x m, hyp nh x m): the joint compatibility of a scan's
