@@ -100,6 +100,16 @@ class EkfJointResult(ctypes.Structure):
     _fields_ = [("d2", _d), ("dof", _i32), ("pairings", _i32), ("outcome", _i32), ("first_irregular", _i32)]
 
 
+EKF_JOINT_ITER_MAX = EKF_MODEL_ITER_MAX
+EKF_JOINT_SUB_MAX = 3 + 2 * EKF_JOINT_MAX
+
+
+class EkfJointIterResult(ctypes.Structure):
+    """struct ekf_joint_iter_result (include/ekfslam.h)."""
+    _fields_ = [("used", _i32), ("converged", _i32), ("last_step", _d), ("d2_last", _d), ("irregular_at", _i32), ("irregular_obs", _i32),
+                ("ns", _i32), ("reserved", _i32), ("x_sub", _d * EKF_JOINT_SUB_MAX)]
+
+
 EKF_MOTION_TURN_DRIVE, EKF_MOTION_ARC, EKF_MOTION_POSE_DELTA = 1, 2, 3
 EKF_MOTION_INPUTS = {1: 2, 2: 2, 3: 3}                # entries of u (and rows of M) each motion model reads
 EKF_PREDICT_MODEL_MAX = 32
@@ -179,6 +189,9 @@ SIGNATURES = {
     "ekf_joint_innovation": (_i32, [_vp, ctypes.POINTER(EkfModelObs), _i64, ctypes.POINTER(_i64), _i64, ctypes.POINTER(EkfJointResult), _dp, _dp,
                                     _dp]),
     "ekf_observe_model_joint": (_i32, [_vp, ctypes.POINTER(EkfModelObs), _i64, ctypes.POINTER(_i64), _d, ctypes.POINTER(EkfJointResult), _dp, _dp]),
+    "ekf_observe_model_joint_iterated": (_i32, [_vp, ctypes.POINTER(EkfModelObs), _i64, ctypes.POINTER(_i64), _d, _i32, _d,
+                                                ctypes.POINTER(EkfJointResult), ctypes.POINTER(EkfJointIterResult), _dp, _dp]),
+    "ekf_joint_iterate": (_i32, [_dp, _dp, ctypes.POINTER(EkfModelObs), _i64, _i32, _d, ctypes.POINTER(EkfJointIterResult), _dp, _dp]),
     "ekf_predict_model": (_i32, [_vp, ctypes.POINTER(EkfMotion), _i64]),
     "ekf_motion_evaluate": (_i32, [_i32, _dp, _dp, _dp, _dp, _dp]),
     "ekf_diag_poke_device_signature": (_i32, [_vp, _i64, _d]),

@@ -684,4 +684,78 @@ EKF_MHD double joint_prefix_add(double acc, double y0, double y1) {
     return acc + y1 * y1;
 }
 
+// The ITERATED joint update (ekf_observe_model_joint_iterated; joint_iter.h runs these on the device, ekf_joint_iterate on the host with
+// one lane): Gauss-Newton on the MAP cost over the sub-state xi = (x_r, l_0 .. l_{np-1}), ns = 3 + 2 np entries, under its PRIOR covariance
+//     P_sub = [Prr, the strip columns of the paired landmarks; their own blocks; the blocks P(l_a, l_b)]
+// kept as the operands joint_pairing and joint_cross_block read: prr (row-major, its lower triangle read), strips[6 p + 2 t + r] =
+// P(t, l_p + r), diag3[3 p ..] = P(l_p, l_p)'s (0,0) (1,0) (1,1), pab[4 (a (a - 1) / 2 + b) + 2 r + c] = P(l_a + r, l_b + c) for a > b.
+//     xi_0 = x0;   (H_i, nu_i = wrap(z - h(xi_i))) per pairing, S_i = H_i P_sub H_i' + R from the PRIOR operands (joint_pairing,
+//     joint_cross_block: their sums, their order);   r_i = nu_i - H_i (x0 - xi_i)   (i = 0: nu_0 alone, no second term formed)
+//     L_i L_i' = S_i, y_i = L_i^-1 r_i (joint_factor_*);   v = L_i^-T y_i (joint_back_step);   u = H_i' v (joint_iter_Htv)
+//     xi_{i+1} = x0 + P_sub u (joint_iter_move);   step = max_k |xi_{i+1}[k] - xi_i[k]| (joint_iter_step)
+// The move is the back-substitution form, O(ns^2): the other form, W_sub' y_i with the full W_sub = L_i^-1 H_i P_sub, costs O(ns^3) and a
+// second ns x 2 np array on-die for a vector that is needed once per linearisation.
+// P_sub(k, j), k, j < ns:
+EKF_MHD double joint_sub_P(const double prr[9], const double *strips, const double *diag3, const double *pab, int k, int j) {
+    if (k < j) { const int t = k; k = j; j = t; }              // the lower triangle: k >= j
+    if (k < 3) return prr[3 * k + j];
+    const int pa = (k - 3) >> 1, ra = (k - 3) & 1;
+    if (j < 3) return strips[6 * pa + 2 * j + ra];
+    const int pb = (j - 3) >> 1, rb = (j - 3) & 1;
+    if (pa == pb) return diag3[3 * pa + ra + rb];              // (0,0) (1,0) (1,1)
+    return pab[4 * (pa * (pa - 1) / 2 + pb) + 2 * ra + rb];
+}
+// One pairing of linearisation i >= 1: joint_pairing at (xir, xil) with the prior operands, then the residual r = nu - H (x0 - xi), the
+// robot's three terms before the landmark's two, each row's sum formed before it is subtracted (model_iterate's order).
+EKF_MHD bool joint_iter_pairing(int model, const double z[2], const double R[4], const double prr[9], const double strip6[6], const double diag3[3],
+                                const double x0r[3], const double x0l[2], const double xir[3], const double xil[2], double Hr[6], double Ht[4],
+                                double S[4], double r[2]) {
+    const bool posed = joint_pairing(model, z, R, prr, strip6, diag3, xir, xil, Hr, Ht, S, r);
+    for (int q = 0; q < 2; ++q) {
+        double hd = 0.0;
+        for (int t = 0; t < 3; ++t) hd += Hr[3 * q + t] * (x0r[t] - xir[t]);
+        for (int c = 0; c < 2; ++c) hd += Ht[2 * q + c] * (x0l[c] - xil[c]);
+        r[q] -= hd;
+    }
+    return posed;
+}
+// Step k = n - 1 .. 0 of v = L^-T t on the factored A (strict lower triangle L, the pivot L_kk^2 on the diagonal, as joint_factor_* leave
+// it): v[k] = t[k] / L_kk, then t[i] loses L(k, i) v[k] for every i < k -- so entry i's terms are subtracted in DESCENDING k.  Every lane
+// forms v[k] itself from t[k], which the step before finished; lane 0 stores it.  One phase a step, the caller separates the steps.
+EKF_MHD void joint_back_step(const double *A, int ld, double *t, double *v, int k, int lane, int lanes) {
+    const double vk = t[k] / sqrt(A[k * ld + k]);
+    if (lane == 0) v[k] = vk;
+    for (int i = lane; i < k; i += lanes) t[i] = t[i] - A[k * ld + i] * vk;
+}
+// u = H' v over the sub-state: the robot's entry t sums over the pairings in ascending row order, a landmark's entry over its own two rows
+EKF_MHD void joint_iter_Htv(const double *Hr, const double *Ht, const double *v, int np, double *u, int lane, int lanes) {
+    for (int k = lane; k < 3 + 2 * np; k += lanes) {
+        double s = 0.0;
+        if (k < 3) {
+            for (int i = 0; i < 2 * np; ++i) s += Hr[6 * (i >> 1) + 3 * (i & 1) + k] * v[i];
+        } else {
+            const int p = (k - 3) >> 1, c = (k - 3) & 1;
+            for (int q = 0; q < 2; ++q) s += Ht[4 * p + 2 * q + c] * v[2 * p + q];
+        }
+        u[k] = s;
+    }
+}
+// xn = x0 + P_sub u, entry k's sum in ascending j and added to x0[k] last; dstep[k] = |xn[k] - xi[k]|
+EKF_MHD void joint_iter_move(const double prr[9], const double *strips, const double *diag3, const double *pab, int np, const double *x0,
+                             const double *u, const double *xi, double *xn, double *dstep, int lane, int lanes) {
+    const int ns = 3 + 2 * np;
+    for (int k = lane; k < ns; k += lanes) {
+        double s = 0.0;
+        for (int j = 0; j < ns; ++j) s += joint_sub_P(prr, strips, diag3, pab, k, j) * u[j];
+        xn[k] = x0[k] + s;
+        dstep[k] = fabs(xn[k] - xi[k]);
+    }
+}
+// the largest move, in ascending k (fmax: a NaN entry is passed over, as in model_iterate); every lane reads the same ns entries
+EKF_MHD double joint_iter_step(const double *dstep, int ns) {
+    double step = 0.0;
+    for (int k = 0; k < ns; ++k) step = fmax(step, dstep[k]);
+    return step;
+}
+
 }  // namespace ekfm

@@ -234,6 +234,9 @@ struct ekf_handle {
     // ---- a scan's pairings applied as one joint update (ekf_observe_model_joint) ----
     // what k_joint_factor hands k_gather_joint (allocated at the first call and kept); its pairs go to d_mring above
     JointBlock *d_jblock = nullptr;
+    // ... relinearised (ekf_observe_model_joint_iterated): k_joint_factor_iter's iteration record on the device and in pinned memory (allocated at
+    // the first call and kept); read back behind ev_joint
+    double *d_jiter = nullptr, *h_jiter = nullptr;
     // ---- timers, what ekf_destroy releases, the error text ----
     KernelTimer timers[EKF_KERNEL_COUNT];
     std::vector<void *> allocs;       // device memory (dalloc), pinned memory (halloc) and events (new_event): what ekf_destroy releases

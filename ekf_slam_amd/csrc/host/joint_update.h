@@ -1,4 +1,4 @@
-// Fragment of abi.hip, a scan's pairings applied as ONE joint update (ekf_observe_model_joint): ekf_joint_innovation's arguments and rungs for one
+// Fragment of abi.hip, a scan's pairings applied as ONE joint update (ekf_observe_model_joint, and ekf_observe_model_joint_iterated through it): ekf_joint_innovation's arguments and rungs for one
 // hypothesis, then ekf_merge_landmarks_batch's route -- flush first, the pairs into the batch's private F64 ring, one F64-arithmetic pass
 // through launch_downdate -- so the handle's own ring, cfg.batch and cfg.pass_arith are not involved.
 #pragma once
@@ -13,15 +13,17 @@ int32_t joint_update_alloc(ekf_handle *h) {
     if (first) HIPCHK(h, hipDeviceSynchronize());          // dalloc clears on the null stream (see removal_alloc)
     return EKF_OK;
 }
-}  // namespace
 
-extern "C" {
+// The loop's controls of ekf_observe_model_joint_iterated (host/joint_iter.h); nullptr: the plain call, linearised once by k_joint_factor.
+struct JointIterCtl { int32_t iterations; double tol; ekf_joint_iter_result *it; };
+int32_t joint_iter_alloc(ekf_handle *h);
+void joint_iter_fill(const double *rec, ekf_joint_iter_result *it);
+
+// ekf_observe_model_joint and ekf_observe_model_joint_iterated: ONE text for the arguments and the order of a call.
 // Order: arguments -> the rungs, with the landmarks checked once N is exact -> allocations -> flush -> factor launch, readback, wait, decision
 // -> gather launch -> the pass, in place on the main stream.
-int32_t ekf_observe_model_joint(ekf_handle *h, const ekf_model_obs *obs, int64_t m, const int64_t *lm, double gate, ekf_joint_result *res,
-                                double *nu, double *S) {
-    if (!h) return EKF_ERR_INVALID_ARG;
-    const std::string who = "observe_model_joint: ";
+int32_t observe_joint(ekf_handle *h, const std::string &who, const ekf_model_obs *obs, int64_t m, const int64_t *lm, double gate,
+                      const JointIterCtl *ctl, ekf_joint_result *res, double *nu, double *S) {
     REQUIRE(h, obs != nullptr && lm != nullptr && res != nullptr, EKF_ERR_INVALID_ARG, (who + "null argument").c_str());
     REQUIRE(h, m >= 1 && m <= EKF_JOINT_MAX, EKF_ERR_INVALID_ARG, (who + "between 1 and EKF_JOINT_MAX observations").c_str());
     AssocModelArgs scan;
@@ -37,6 +39,10 @@ int32_t ekf_observe_model_joint(ekf_handle *h, const ekf_model_obs *obs, int64_t
     }
     double g;
     TRY(parse_gate(h, who, gate, g));
+    if (ctl) {
+        REQUIRE(h, ctl->iterations >= 1 && ctl->iterations <= EKF_JOINT_ITER_MAX, EKF_ERR_INVALID_ARG, (who + "iterations is 1 .. EKF_JOINT_ITER_MAX").c_str());
+        REQUIRE(h, ctl->tol >= 0.0, EKF_ERR_INVALID_ARG, (who + "tol is a number >= 0").c_str());          // (a NaN fails the comparison)
+    }
     ModelArgs rung;
     const int64_t none[2] = { -1, -1 };
     TRY(linear_rungs(h, who, none, rung));
@@ -46,9 +52,15 @@ int32_t ekf_observe_model_joint(ekf_handle *h, const ekf_model_obs *obs, int64_t
         res->d2 = 0.0; res->dof = 0; res->pairings = 0; res->outcome = EKF_LINEAR_APPLIED; res->first_irregular = -1;
         if (nu) for (int64_t i = 0; i < 2 * m; ++i) nu[i] = 0.0;
         if (S) for (int64_t e = 0; e < 4 * m * m; ++e) S[e] = e % (2 * m) == e / (2 * m) ? 1.0 : 0.0;
+        if (ctl && ctl->it) {
+            ekf_joint_iter_result empty = ekf_joint_iter_result();
+            empty.converged = 1; empty.irregular_at = empty.irregular_obs = -1;
+            *ctl->it = empty;
+        }
         return EKF_OK;
     }
     TRY(joint_update_alloc(h));
+    if (ctl) TRY(joint_iter_alloc(h));
     if (S) TRY(joint_S_block(h));
     TRY(flush_pending(h));                 // retires a pass in flight; from here on the tiles hold the live P and the ring is empty
 
@@ -62,8 +74,15 @@ int32_t ekf_observe_model_joint(ekf_handle *h, const ekf_model_obs *obs, int64_t
     HIPCHK(h, hipMemcpyAsync(h->d_jhyp, h->h_jhyp, (size_t)m * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
     {
         TimedLaunch tl(h, EKF_KERNEL_ASSOCIATE);
-        HIPCHK(h, launch_joint_factor(h->st, a, h->d_jhyp, h->d_jblock, d_rec, d_nu, S ? h->d_jS : nullptr, h->storage, h->stream));
+        if (ctl) {
+            JointIterArgs ia = JointIterArgs();
+            ia.gate = g; ia.tol = ctl->tol; ia.iterations = ctl->iterations;
+            HIPCHK(h, launch_joint_factor_iter(h->st, a, ia, h->d_jhyp, h->d_jblock, d_rec, h->d_jiter, d_nu, S ? h->d_jS : nullptr, h->storage, h->stream));
+        } else {
+            HIPCHK(h, launch_joint_factor(h->st, a, h->d_jhyp, h->d_jblock, d_rec, d_nu, S ? h->d_jS : nullptr, h->storage, h->stream));
+        }
     }
+    if (ctl) HIPCHK(h, hipMemcpyAsync(h->h_jiter, h->d_jiter, kJointIterRecordDoubles * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipMemcpyAsync(h->h_jout, h->d_jout, bytes, hipMemcpyDeviceToHost, h->stream));
     if (S) HIPCHK(h, hipMemcpyAsync(h->h_jS, h->d_jS, s_bytes, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipEventRecord(h->ev_joint, h->stream));
@@ -71,6 +90,7 @@ int32_t ekf_observe_model_joint(ekf_handle *h, const ekf_model_obs *obs, int64_t
     memcpy(res, h->h_jout, sizeof(ekf_joint_result));
     if (nu) memcpy(nu, h->h_jout + sizeof(JointRecord) + (size_t)m * 8, (size_t)2 * m * sizeof(double));
     if (S) memcpy(S, h->h_jS, s_bytes);
+    if (ctl && ctl->it) joint_iter_fill(h->h_jiter, ctl->it);
     // the decision, on the host, before anything is written
     if (res->outcome != EKF_LINEAR_APPLIED) {
         res->outcome = EKF_LINEAR_IRREGULAR;
@@ -78,6 +98,12 @@ int32_t ekf_observe_model_joint(ekf_handle *h, const ekf_model_obs *obs, int64_t
                     "robot, a state that is not finite, or a stacked S that is not positive definite); nothing was changed").c_str());
     }
     if (!(res->d2 <= g)) { res->outcome = EKF_LINEAR_GATED; return EKF_OK; }
+    if (ctl && h->h_jiter[4] >= 0.0) {
+        res->outcome = EKF_LINEAR_IRREGULAR;
+        return fail(h, EKF_ERR_STATE, (who + "observation " + std::to_string((int)h->h_jiter[5]) + " at linearisation " + std::to_string((int)h->h_jiter[4]) +
+                    ": the pairing is not posed at that iterate (its target on the robot, an iterate that is not finite), or the stacked S is not "
+                    "positive definite there; nothing was changed").c_str());
+    }
 
     // the gather, on a view of the state whose pair ring is the private one
     DevState st = h->st;
@@ -106,5 +132,13 @@ int32_t ekf_observe_model_joint(ekf_handle *h, const ekf_model_obs *obs, int64_t
     }
     tiles_changed(h);
     return EKF_OK;
+}
+}  // namespace
+
+extern "C" {
+int32_t ekf_observe_model_joint(ekf_handle *h, const ekf_model_obs *obs, int64_t m, const int64_t *lm, double gate, ekf_joint_result *res,
+                                double *nu, double *S) {
+    if (!h) return EKF_ERR_INVALID_ARG;
+    return observe_joint(h, "observe_model_joint: ", obs, m, lm, gate, nullptr, res, nu, S);
 }
 }  // extern "C"

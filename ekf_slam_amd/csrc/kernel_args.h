@@ -224,6 +224,19 @@ struct JointUpdateArgs {
     int32_t cur;
     int32_t np;               // pairings, as the host read them back in the record: the pairs go to ring slots 0 .. np - 1
 };
+// ... relinearised up to `iterations` times (joint_iter.h, ekf_observe_model_joint_iterated): the loop's controls beside JointArgs.  The
+// JointBlock is the LAST linearisation's; the gate is read at the first.
+struct JointIterArgs {
+    double gate;              // d2 of the first linearisation above it: no step is taken (used = 0)
+    double tol;               // the loop stops where the largest move of an entry is <= tol
+    int32_t iterations;       // 1 .. kJointIterMax
+    int32_t pad_;
+};
+constexpr int kJointIterMax = 16;
+constexpr int kJointSubMax = 3 + 2 * kJointMax;       // entries of the largest sub-state (x_r and the paired landmarks)
+// the second record of such a launch: used (0) | converged (1) | the last step (2) | d2 of the last linearisation (3) | the linearisation
+// that was irregular, or -1 (4) | the scan index of its first irregular pairing, or -1 (5) | ns (6) | 0 (7) | x'_sub = xi_used (8 .. 8 + ns)
+constexpr int kJointIterRecordDoubles = 8 + kJointSubMax + 1;
 
 // ---- map edits, and the observations that share the constraint's device code ----
 // A constraint between two landmarks (constrain.h): "l_i - l_j was observed as (d0, d1) with noise covariance R".

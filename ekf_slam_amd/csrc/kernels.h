@@ -238,6 +238,10 @@ hipError_t launch_joint_innovation(const DevState &st, const JointArgs &a, const
 // so out / nu / S are what launch_joint_innovation reports for it bit for bit, and blk (device) takes what the gather needs.
 hipError_t launch_joint_factor(const DevState &st, const JointArgs &a, const int64_t *hyp, JointBlock *blk, JointRecord *out, double *nu, double *S,
                                int storage, hipStream_t s);
+// launch_joint_factor_iter (joint_iter.h): k_joint_factor_iter, launch_joint_factor relinearised up to ia.iterations times -- out / nu / S are
+// the FIRST linearisation's (the same bits), blk the LAST one's, itrec (device, kJointIterRecordDoubles doubles) the iteration record.
+hipError_t launch_joint_factor_iter(const DevState &st, const JointArgs &a, const JointIterArgs &ia, const int64_t *hyp, JointBlock *blk,
+                                    JointRecord *out, double *itrec, double *nu, double *S, int storage, hipStream_t s);
 // launch_gather_joint: k_gather_joint over the padded landmark block.  `st` is a by-value copy of the handle's DevState whose Gp / Kp / pcap
 // name a PRIVATE F64 pair ring (Gp32 == nullptr): the a.np pairs go to its slots 0 .. a.np - 1, x / Prr / strip into buffer a.cur ^ 1, every
 // landmark's live diagonal block into buffer dcur ^ 1; the caller flips both and lets ONE pass apply the pairs to the tiles.

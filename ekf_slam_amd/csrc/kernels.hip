@@ -53,6 +53,7 @@ namespace {
 #include "assign_model.h"    // ... and assigned to it one-to-one: k_assign_candidates, k_assign_select, k_assign_solve
 #include "joint.h"            // a scan's pairings judged jointly, a hypothesis per workgroup: k_joint_innovation
 #include "joint_update.h"     // ... and applied as one joint update: k_joint_factor, k_gather_joint
+#include "joint_iter.h"       // ... relinearised: k_joint_factor_iter
 #include "merge_pass.h"       // the fused downdate-and-compact pass of a batch of merges: k_merge_pass
 #include "nearest.h"          // the candidate search in front of a merge: k_nearest
 

@@ -1,5 +1,5 @@
 // Fragment of kernels.hip, the launchers of the map edits: landmark removal (compact.h), a constraint between two landmarks and its
-// chained form (constrain.h), a linear observation (linear_obs.h) and one through a model (model_obs.h), the joint innovation of a scan's pairings (joint.h) and their joint update (joint_update.h), the fused pass of a batch of merges (merge_pass.h), the candidate search (nearest.h).
+// chained form (constrain.h), a linear observation (linear_obs.h) and one through a model (model_obs.h), the joint innovation of a scan's pairings (joint.h) and their joint update (joint_update.h, joint_iter.h), the fused pass of a batch of merges (merge_pass.h), the candidate search (nearest.h).
 #pragma once
 
 namespace {
@@ -161,6 +161,17 @@ hipError_t launch_joint_factor(const DevState &st, const JointArgs &a, const int
         return hipErrorInvalidValue;
     return with_storage(storage, [&](auto ts) {
         hipLaunchKernelGGL(k_joint_factor<decltype(ts)>, dim3(1), dim3(kJointBlock), 0, s, st, a, hyp, blk, out, nu, S);
+    });
+}
+
+hipError_t launch_joint_factor_iter(const DevState &st, const JointArgs &a, const JointIterArgs &ia, const int64_t *hyp, JointBlock *blk,
+                                    JointRecord *out, double *itrec, double *nu, double *S, int storage, hipStream_t s) {
+    // launch_joint_factor's checks, and the loop's controls inside their limits
+    if (a.m < 1 || a.m > kJointMax || !hyp || !blk || !out || !itrec || a.N < 0 || 2 * a.N > st.ldm || a.npend != 0 || a.pstart < 0 ||
+        a.pstart >= st.pcap || st.tm.world != 1 || ia.iterations < 1 || ia.iterations > kJointIterMax || !(ia.tol >= 0.0) || ia.gate != ia.gate)
+        return hipErrorInvalidValue;
+    return with_storage(storage, [&](auto ts) {
+        hipLaunchKernelGGL(k_joint_factor_iter<decltype(ts)>, dim3(1), dim3(kJointBlock), 0, s, st, a, ia, hyp, blk, out, itrec, nu, S);
     });
 }
 

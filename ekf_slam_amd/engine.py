@@ -549,30 +549,62 @@ class Engine:
         return res
 
     # ---- ... and applied as ONE joint update (include/ekfslam.h: ekf_observe_model_joint) ----
-    def observe_model_joint(self, entries, landmarks, gate=float("inf"), want_nu=False, want_S=False):
+    def observe_model_joint(self, entries, landmarks, gate=float("inf"), want_nu=False, want_S=False, iterations=1, tol=0.0):
         """One hypothesis of joint_innovation APPLIED as one joint update: entries as for associate_model (the per-entry gate is not
         read), landmarks the 0-based landmark each observation is paired with or -1 = left out.  All pairings are linearised once at the
         live state and stacked; x' = x + W' y, P' = P - W' W with W = L^-1 H P, L L' = S -- applied only if the joint d2 <= gate.  The
         pending pairs are flushed first and ONE pass over P applies all pairings; nothing is waited for at the end.  Returns {'d2',
         'dof', 'pairings', 'outcome', 'first_irregular'} -- joint_innovation's for that hypothesis on the flushed state, bit for bit;
         outcome EKF_LINEAR_APPLIED or EKF_LINEAR_GATED -- plus 'nu' (2m) and 'S' (2m x 2m) by scan index where asked.  A pairing with
-        no d2 raises EkfError and changes nothing (ekf_observe_model_joint)."""
+        no d2 raises EkfError and changes nothing (ekf_observe_model_joint).
+        iterations > 1 RELINEARISES the whole scan up to that many times on the device (Gauss-Newton over the robot and the paired
+        landmarks, stopping where no entry moves by more than tol) and applies the last linearisation; the gate and the dict above are the
+        first one's, and 'used', 'converged', 'step' are added.  An iterate that is irregular raises EkfError and changes nothing
+        (ekf_observe_model_joint_iterated)."""
         arr, m = marshal.scan_obs(entries)
-        return self._observe_joint(arr, m, landmarks, gate, want_nu, want_S)
+        return self._observe_joint(arr, m, landmarks, gate, want_nu, want_S, iterations, tol)
 
-    def _observe_joint(self, arr, m, landmarks, gate=float("inf"), want_nu=False, want_S=False):
-        """ekf_observe_model_joint on the built scan (arr, m)."""
+    def _observe_joint(self, arr, m, landmarks, gate=float("inf"), want_nu=False, want_S=False, iterations=1, tol=0.0):
+        """ekf_observe_model_joint on the built scan (arr, m); iterations > 1: ekf_observe_model_joint_iterated."""
         lms = np.asarray(landmarks, dtype=np.float64).reshape(-1)
         if lms.size != m:
             raise ValueError("observe_model_joint: one landmark (or -1) per entry of the scan")
         if not np.all(lms == np.floor(lms)):
             raise ValueError("observe_model_joint: landmark indices are whole numbers")
+        if int(iterations) != iterations:
+            raise ValueError("observe_model_joint: iterations is a whole number")
         idx, _ = marshal.index_array(lms.tolist())
         res = L.EkfJointResult()
         nu = np.zeros(2 * m) if want_nu else None
         S = np.zeros(4 * m * m) if want_S else None
-        self._check(self.lib.ekf_observe_model_joint(self.h, arr, m, idx, float(gate), ctypes.byref(res), p_or_null(nu), p_or_null(S)))
-        return marshal.joint_result(res, m, nu, S)
+        if int(iterations) == 1:
+            self._check(self.lib.ekf_observe_model_joint(self.h, arr, m, idx, float(gate), ctypes.byref(res), p_or_null(nu), p_or_null(S)))
+            return marshal.joint_result(res, m, nu, S)
+        it = L.EkfJointIterResult()
+        self._check(self.lib.ekf_observe_model_joint_iterated(self.h, arr, m, idx, float(gate), int(iterations), float(tol), ctypes.byref(res),
+                                                              ctypes.byref(it), p_or_null(nu), p_or_null(S)))
+        out = marshal.joint_result(res, m, nu, S)
+        more = marshal.joint_iter_result(it)
+        out.update(used=more["used"], converged=more["converged"], step=more["step"])
+        return out
+
+    @staticmethod
+    def joint_iterate(x_sub, P_sub, entries, iterations=3, tol=0.0, lib=None):
+        """The loop the kernel runs, on the host (ekf_joint_iterate): x_sub = (x_r, l_0 .. l_{np-1}), P_sub its ns x ns covariance, entries
+        as for associate_model, every one paired with its own landmark of the sub-state.  Returns (x', P', record) with the record
+        {'used', 'converged', 'step', 'd2_last', 'irregular_at', 'irregular_obs', 'x_sub'}; an irregular linearisation leaves x' and P' equal
+        to the inputs."""
+        arr, m = marshal.scan_obs(entries)
+        xs = np.ascontiguousarray(x_sub, dtype=np.float64).reshape(-1)
+        ns = 3 + 2 * m
+        Ps = np.asfortranarray(np.asarray(P_sub, dtype=np.float64))
+        if xs.size != ns or Ps.shape != (ns, ns):
+            raise ValueError("joint_iterate: x_sub has 3 + 2 np entries and P_sub is square of that size")
+        Pf = np.ascontiguousarray(Ps.T)                            # (column-major in memory)
+        xo, Po = np.zeros(ns), np.zeros((ns, ns))
+        it = L.EkfJointIterResult()
+        host_call("ekf_joint_iterate", lib, _p(xs), _p(Pf), arr, m, int(iterations), float(tol), ctypes.byref(it), _p(xo), _p(Po))
+        return xo, Po.T.copy(), marshal.joint_iter_result(it)
 
     # ---- motion steps through a model with its true Jacobians (include/ekfslam.h: ekf_predict_model) ----
     def predict_model(self, steps):

@@ -215,6 +215,12 @@ def joint_result(res, m, nu=None, S=None):
     return out
 
 
+def joint_iter_result(it):
+    """One struct ekf_joint_iter_result as a dict: 'used', 'converged', 'step', 'd2_last', 'irregular_at', 'irregular_obs' and 'x_sub' (ns)."""
+    return {"used": int(it.used), "converged": bool(it.converged), "step": float(it.last_step), "d2_last": float(it.d2_last),
+            "irregular_at": int(it.irregular_at), "irregular_obs": int(it.irregular_obs), "x_sub": np.array(it.x_sub[:int(it.ns)])}
+
+
 MATCH_KEYS = (("best", np.int64), ("second", np.int64), ("d2_best", np.float64), ("d2_second", np.float64), ("within_gate", np.int64),
               ("irregular", np.int64))
 

@@ -644,27 +644,34 @@ class _EkfBase:
         res["first_irregular"] = res["first_irregular"] + 1
         return res
 
-    def observe_model_joint(self, entries, landmarks, gate=float("inf"), want_nu=False, want_S=False):
+    def observe_model_joint(self, entries, landmarks, gate=float("inf"), want_nu=False, want_S=False, iterations=1, tol=0.0):
         """One hypothesis of joint_innovation APPLIED as ONE joint update: entries as for associate_model ([{'model', 'z', 'R'}, ...],
         models 1-4), landmarks the 1-based landmark each observation is paired with, 0 = left out.  All pairings are linearised once, at
         the live state, and stacked: the update that runs is the one whose joint d2 is reported, it does not depend on scan order, and it
         costs one pass over P however many pairings there are (sequential observe_model steps relinearise after each one).  Applied only
         if the joint d2 <= gate.  The pending pairs are flushed first.  Returns {'d2', 'dof', 'pairings', 'outcome', 'first_irregular'}
         (first_irregular 1-based, 0 = none) plus 'nu' and 'S' by scan index where asked; a pairing with no d2 raises EkfError and
-        changes nothing (ekf_observe_model_joint).  Unsharded handles only.  The reference has no such method."""
+        changes nothing (ekf_observe_model_joint).  iterations > 1 relinearises the whole scan up to that many times (Gauss-Newton over
+        the robot and the paired landmarks, stopping where no entry moves by more than tol), applies the last linearisation -- the gate
+        and the dict are the first one's -- and adds 'used', 'converged', 'step' (ekf_observe_model_joint_iterated).  Unsharded handles
+        only.  The reference has no such method."""
         numbers = self._landmark_numbers("observe_model_joint", *list(landmarks))
         if any(k < 0 for k in numbers):
             raise ValueError("observe_model_joint: a landmark is 1-based, 0 = the observation is left out")
         arr, m = marshal.scan_obs(entries)                                  # the one array: sent, then logged from
-        res = dict(self._e._observe_joint(arr, m, [k - 1 for k in numbers], gate, want_nu, want_S))
+        iterated = iterations != 1
+        res = dict(self._e._observe_joint(arr, m, [k - 1 for k in numbers], gate, want_nu, want_S, *((iterations, tol) if iterated else ())))
         res["first_irregular"] = res["first_irregular"] + 1
         if self.log is not None:
-            self.log.record_model_observation_joint(
-                [(o.model, np.array(o.z[:]), np.array(o.R[:]).reshape(2, 2, order="F"), k) for o, k in zip(arr[:m], numbers)], gate)
+            logged = [(o.model, np.array(o.z[:]), np.array(o.R[:]).reshape(2, 2, order="F"), k) for o, k in zip(arr[:m], numbers)]
+            if iterated:
+                self.log.record_model_observation_joint_iterated(logged, gate, iterations, tol)
+            else:
+                self.log.record_model_observation_joint(logged, gate)
         return res
 
     def measure_model_joint(self, entries, gate_match, gate_new, joint_p=0.99, beam=64, wait=False, joint_update=False,
-                            device_candidates=False):
+                            device_candidates=False, joint_iterations=1, joint_tol=0.0):
         """measure_model with the ambiguity discard replaced by a JOINT-compatibility search: entries, gate_match, gate_new and wait as
         there.  ONE associate_model(..., want_d2=True) call: the candidates of an entry are the landmarks with individual d2 <= gate_match,
         at most the 4 closest (by (d2, landmark)); an entry without a candidate is new where d2_best > gate_new (or the map is empty) and
@@ -676,7 +683,8 @@ class _EkfBase:
         add_landmarks_model call; the rest is discarded.  Returns ([(kind, landmark)] per entry as measure_model, whether the beam cut
         the search).  Everything that changes the state goes through those two logged methods, so a replayed log reproduces the run.
         joint_update=True applies the winner's pairings by ONE observe_model_joint(gate=inf) call instead -- the update whose joint d2 the
-        search tested, one pass over P -- which is logged as well.  device_candidates=True takes the candidates and the best d2 from ONE
+        search tested, one pass over P -- which is logged as well; joint_iterations > 1 (read only with joint_update=True) relinearises
+        that update up to so many times, stopping at joint_tol (observe_model_joint's iterations and tol).  device_candidates=True takes the candidates and the best d2 from ONE
         assign_model(want_candidates=True) call instead: the same landmarks in the same order, so the outcome and the log are the same,
         and the m x N matrix does not come back to the host."""
         gate_match, gate_new, joint_p = float(gate_match), float(gate_new), float(joint_p)
@@ -722,7 +730,8 @@ class _EkfBase:
         if joint_update and winner:
             # the winner's pairings in scan order as one joint update, then the close without them: the new entries and the discards
             self.observe_model_joint([dict(model=int(e[0]), z=e[1], R=e[2]) for e in (entries[k] for k in sorted(winner))],
-                                     [winner[k] + 1 for k in sorted(winner)])
+                                     [winner[k] + 1 for k in sorted(winner)],
+                                     **(dict(iterations=joint_iterations, tol=joint_tol) if joint_iterations != 1 else {}))
             out = self._measure_carry_out(entries, ["discarded" if k in winner else kind for k, kind in enumerate(kinds)], {}, gate_match, wait)
             for k in winner:
                 out[k] = ("matched", winner[k] + 1)

@@ -29,6 +29,7 @@ FORMAT_APPEND = "ekfslam-trajectory-6"
 FORMAT_PREDICT = "ekfslam-trajectory-7"
 FORMAT_ITERATED = "ekfslam-trajectory-8"
 FORMAT_JOINT = "ekfslam-trajectory-9"
+FORMAT_JOINT_ITERATED = "ekfslam-trajectory-10"
 EDIT_KINDS = ("remove", "constrain", "merge", "merge_batch")        # what record_edit takes
 OBSERVE = "observe"                                                  # record_observation's
 OBSERVE_MODEL = "observe_model"                                      # record_model_observation's
@@ -36,7 +37,9 @@ APPEND_MODEL = "append_model"                                        # record_mo
 PREDICT_MODEL = "predict_model"                                      # record_model_predict's
 OBSERVE_MODEL_ITERATED = "observe_model_iterated"                    # record_model_observation_iterated's
 OBSERVE_MODEL_JOINT = "observe_model_joint"                          # record_model_observation_joint's
-_FORMATS = (FORMAT, FORMAT_EDITS, FORMAT_BATCH, FORMAT_OBSERVE, FORMAT_MODEL, FORMAT_APPEND, FORMAT_PREDICT, FORMAT_ITERATED, FORMAT_JOINT)
+OBSERVE_MODEL_JOINT_ITERATED = "observe_model_joint_iterated"        # record_model_observation_joint_iterated's
+_FORMATS = (FORMAT, FORMAT_EDITS, FORMAT_BATCH, FORMAT_OBSERVE, FORMAT_MODEL, FORMAT_APPEND, FORMAT_PREDICT, FORMAT_ITERATED, FORMAT_JOINT,
+            FORMAT_JOINT_ITERATED)
 _STEP_ARRAYS = ("u", "obs_ptr", "obs", "lm_ptr", "lm_index", "lm_loc")
 _EDIT_ARRAYS = ("edit_step", "edit_kind", "edit_ptr", "edit_idx", "edit_delta", "edit_R")
 
@@ -99,6 +102,14 @@ _KINDS_TABLE = (
                                                                [lm - 1 for _, _, _, lm in entries], gate=float(d[0])),
           "model_joints", "joint",
           (_Field("model", 0, _I, ()), _Field("z", 1, _F, (2,)), _Field("R", 2, _F, (2, 2)), _Field("landmark", 3, _I, ())), True),
+    # observe_model_joint_iterated: that scan relinearised, idx empty, the delta slot = (gate, tol), the first value of the R slot = the
+    # number of linearisations; per scan its entries as above
+    _Kind(OBSERVE_MODEL_JOINT_ITERATED, 10,
+          lambda e, idx0, d, R, entries: e.observe_model_joint([dict(model=m, z=z, R=Rk) for m, z, Rk, _ in entries],
+                                                               [lm - 1 for _, _, _, lm in entries], gate=float(d[0]),
+                                                               iterations=int(R[0, 0]), tol=float(d[1])),
+          "model_joint_iterations", "jointiter",
+          (_Field("model", 0, _I, ()), _Field("z", 1, _F, (2,)), _Field("R", 2, _F, (2, 2)), _Field("landmark", 3, _I, ())), True),
 )
 _KINDS = tuple(k.name for k in _KINDS_TABLE)
 _KIND = {k.name: k for k in _KINDS_TABLE}
@@ -152,6 +163,7 @@ class TrajectoryLog:
         self.model_predicts = {}    # position in self.edits of a 'predict_model' edit -> [(model, u (2 or 3), M (2x2 or 3x3)), ...]
         self.model_iterations = {}  # position in self.edits of an 'observe_model_iterated' edit -> {model, anchor or None, gate, iterations, tol}
         self.model_joints = {}      # position in self.edits of an 'observe_model_joint' edit -> [(model, z (2), R (2x2), landmark 1-based or 0), ...]
+        self.model_joint_iterations = {}  # position in self.edits of an 'observe_model_joint_iterated' edit -> the same list
         self.observations = {}      # position in self.edits of an 'observe' edit -> {Hr (2x3), Hl (2x2x2), gate, wrap (2), rows}
 
     def __len__(self):
@@ -240,6 +252,16 @@ class TrajectoryLog:
         if not ents:
             raise ValueError("record_model_observation_joint: at least one entry")
         self._record(OBSERVE_MODEL_JOINT, z=(float(gate),), payload=ents)
+
+    def record_model_observation_joint_iterated(self, entries, gate=float("inf"), iterations=1, tol=0.0):
+        """That scan RELINEARISED (observe_model_joint(..., iterations > 1) of ekf_slam_amd/slam.py) made now:
+        record_model_observation_joint's arguments, then the number of linearisations and the stopping tolerance."""
+        lms = self._landmarks("record_model_observation_joint_iterated", [e[3] for e in entries])
+        ents = [(int(m), np.asarray(z, dtype=np.float64).reshape(2).copy(), np.asarray(R, dtype=np.float64).reshape(2, 2).copy(), int(lm))
+                for (m, z, R, _), lm in zip(entries, lms)]
+        if not ents:
+            raise ValueError("record_model_observation_joint_iterated: at least one entry")
+        self._record(OBSERVE_MODEL_JOINT_ITERATED, z=(float(gate), float(tol)), R=[[float(int(iterations)), 0.0], [0.0, 0.0]], payload=ents)
 
     def record_model_append(self, entries):
         """One scan of new landmarks (add_landmarks_model of ekf_slam_amd/slam.py) made now, i.e. after the len(self) steps recorded so

@@ -645,6 +645,44 @@ int32_t ekf_observe_model_joint(ekf_handle *h, const ekf_model_obs *obs, int64_t
                                 ekf_joint_result *res   /* required */,
                                 double *nu              /* 2m, may be NULL */,
                                 double *S               /* 2m x 2m column-major, may be NULL */);
+/* ... and RELINEARISED: the iterated joint update, Gauss-Newton on the MAP cost of the whole scan over the sub-state
+ * xi = (x_r, l_0 .. l_{np-1}) (pairing p = the p-th paired entry in scan order; ns = 3 + 2 np <= EKF_JOINT_SUB_MAX entries) under its prior
+ * covariance P_sub, up to `iterations` times (1 .. EKF_JOINT_ITER_MAX):
+ *     xi_0 = x0;   H_i, nu_i = wrap(z - h(xi_i)) per pairing, S_i = H_i P_sub H_i' + blockdiag(R) from the PRIOR covariance;
+ *     r_i = nu_i - H_i (x0 - xi_i)   (i = 0: nu_0 alone);   L_i L_i' = S_i, y_i = L_i^-1 r_i;
+ *     xi_{i+1} = x0 + P_sub H_i' L_i^-T y_i;   step = max_k |xi_{i+1}[k] - xi_i[k]|;   stop after i = iterations - 1 or where step <= tol
+ * (tol = 0: a step of exactly 0 counts as converged).  The update that is applied is the LAST linearisation's, over the whole state and by
+ * ekf_observe_model_joint's two launches unchanged: x' = x0 + W' y_last, P' = P - W' W, W = L_last^-1 H_last P.  With iterations = 1 the state is
+ * ekf_observe_model_joint's bit for bit.  Plain Gauss-Newton: no damping, no line search.
+ * The GATE is read at the first linearisation; res, nu and S are the first linearisation's: ekf_joint_innovation's bits.  A first linearisation
+ * that is irregular or gated behaves as in ekf_observe_model_joint (it->used = 0).  A LATER iterate with a pairing that is not posed or a
+ * pivot that is not finite and positive makes the whole call EKF_LINEAR_IRREGULAR: EKF_ERR_STATE naming the scan index and the
+ * linearisation (it->irregular_obs, it->irregular_at), nothing changed beyond the flush, and the handle goes on working.
+ * it (may be NULL): used = the linearisations whose step was taken, converged = step <= tol, the last step, d2 of the last linearisation,
+ * and x_sub = xi_used (ns entries, zeros behind them).  No pairing at all: the empty update, used = 0, converged = 1.
+ * Order of a call: ekf_observe_model_joint's, with iterations outside 1 .. EKF_JOINT_ITER_MAX or a NaN or negative tol refused
+ * (EKF_ERR_INVALID_ARG) after its argument refusals and before the rungs.  The iteration record's device buffer is allocated at first use
+ * and counted by ekf_device_bytes.
+ * ekf_joint_iterate is the loop the kernel runs, on the host (pure, no handle): x_sub (ns), P_sub (ns x ns column-major, its lower triangle
+ * read), the np entries of obs (models 1-4; lm, anchor and gate ignored), all paired.  x_out / P_out receive x' and P' over the sub-state;
+ * an irregular linearisation (it->irregular_at >= 0, the first included; irregular_obs = the entry) leaves them equal to the inputs. */
+#define EKF_JOINT_ITER_MAX EKF_MODEL_ITER_MAX
+#define EKF_JOINT_SUB_MAX  (3 + 2 * EKF_JOINT_MAX)
+typedef struct ekf_joint_iter_result {
+    int32_t used, converged;
+    double  last_step;
+    double  d2_last;
+    int32_t irregular_at;          /* the linearisation that was irregular, or -1              */
+    int32_t irregular_obs;         /* the scan index of its first irregular pairing, or -1     */
+    int32_t ns, reserved;
+    double  x_sub[EKF_JOINT_SUB_MAX];
+} ekf_joint_iter_result;
+int32_t ekf_observe_model_joint_iterated(ekf_handle *h, const ekf_model_obs *obs, int64_t m, const int64_t *lm, double gate,
+                                         int32_t iterations, double tol, ekf_joint_result *res /* required */,
+                                         ekf_joint_iter_result *it /* may be NULL */, double *nu /* 2m, may be NULL */,
+                                         double *S /* 2m x 2m column-major, may be NULL */);
+int32_t ekf_joint_iterate(const double *x_sub, const double *P_sub, const ekf_model_obs *obs, int64_t np, int32_t iterations, double tol,
+                          ekf_joint_iter_result *it, double *x_out, double *P_out);
 /* The MOTION step under the same conventions: "the robot moved by u through the model, and u has the covariance M".  ekf_predict keeps the
  * reference's step (F(1,3), F(2,3) at the pre-motion heading and without pi/180, Q = (W C) W' of rank one) and is consistent with none of
  * the calls above: a filter driven through ekf_observe_model / ekf_append_model moves here.  With p = x(0:2), theta = x(2) in degrees,

@@ -407,6 +407,19 @@ classdef EKF_SLAM < handle
             R = double(R); if size(R, 3) == 1, R = repmat(R, [1 1 m]); end
             res = h.gateway('observe_model_joint', model, z, R, double(lm(:)), double(gate));
         end
+        function res = observeModelJointIterated(h, model, z, R, lm, gate, iterations, tol)
+            % observeModelJoint RELINEARISED: Gauss-Newton over the robot and the paired landmarks, up to `iterations` linearisations
+            % (1..16, default 3), stopping where no entry moves by more than tol (default 0); the last linearisation is applied.  The gate
+            % is read at the first one.  res = [d2 dof pairings outcome firstIrregular used converged step], the first five the first
+            % linearisation's; an iterate that is irregular is an error and changes nothing.  Not a method of the reference.
+            if nargin < 6 || isempty(gate), gate = Inf; end
+            if nargin < 7 || isempty(iterations), iterations = 3; end
+            if nargin < 8 || isempty(tol), tol = 0; end
+            model = double(model(:)); m = numel(model);
+            z = double(reshape(z, [], 2));
+            R = double(R); if size(R, 3) == 1, R = repmat(R, [1 1 m]); end
+            res = h.gateway('observe_model_joint_iterated', model, z, R, double(lm(:)), double(gate), double(iterations), double(tol));
+        end
         function merges = fuseDuplicatesBatched(h, gate, R, maxMerges)
             % fuseDuplicates with the pairs of one search fused in one mergeLandmarksBatch call: search; walk the candidates in
             % (d2, k) order and take [partner(k) k] when k is not yet a keep or a drop and partner(k) is not yet a drop (a keep may

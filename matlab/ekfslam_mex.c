@@ -26,7 +26,7 @@
  * ekf_nearest_landmarks; ekf_merge_landmarks_batch) the linear observation (ekf_observe_linear), the model observation
  * (ekf_observe_model), the append through a model (ekf_append_model), the association of a scan under the models' conventions
  * (ekf_associate_model) and its one-to-one assignment (ekf_assign_model), the joint compatibility of a scan's pairings (ekf_joint_innovation) and their joint update
- * (ekf_observe_model_joint), the relinearised model observation
+ * (ekf_observe_model_joint, relinearised: ekf_observe_model_joint_iterated), the relinearised model observation
  * (ekf_observe_model_iterated) and the motion steps under them (ekf_predict_model) are the ones this gateway can live without: bound weakly, so that the gateway still links against a libekfslam (or a stand-in) that
  * predates them; their commands then raise a MATLAB error instead. */
 #if defined(__GNUC__)
@@ -45,6 +45,7 @@
 #pragma weak ekf_joint_innovation
 #pragma weak ekf_observe_model_iterated
 #pragma weak ekf_observe_model_joint
+#pragma weak ekf_observe_model_joint_iterated
 #define HAVE_REMOVE_LANDMARKS (ekf_remove_landmarks != 0)
 #define HAVE_CONSTRAIN_LANDMARKS (ekf_constrain_landmarks != 0)
 #define HAVE_MERGE_LANDMARKS (ekf_merge_landmarks != 0)
@@ -60,6 +61,7 @@
 #define HAVE_JOINT_INNOVATION (ekf_joint_innovation != 0)
 #define HAVE_OBSERVE_MODEL_ITERATED (ekf_observe_model_iterated != 0)
 #define HAVE_OBSERVE_MODEL_JOINT (ekf_observe_model_joint != 0)
+#define HAVE_OBSERVE_MODEL_JOINT_ITERATED (ekf_observe_model_joint_iterated != 0)
 #else
 #define HAVE_REMOVE_LANDMARKS 1
 #define HAVE_CONSTRAIN_LANDMARKS 1
@@ -76,6 +78,7 @@
 #define HAVE_JOINT_INNOVATION 1
 #define HAVE_OBSERVE_MODEL_ITERATED 1
 #define HAVE_OBSERVE_MODEL_JOINT 1
+#define HAVE_OBSERVE_MODEL_JOINT_ITERATED 1
 #endif
 
 static void need(int nrhs, int want, const char *cmd) {
@@ -107,6 +110,34 @@ static const double *r2x2_of(const mxArray *a, const char *cmd) {
 }
 
 static int64_t nstate(ekf_handle *h) { int64_t N; check(h, ekf_num_landmarks(h, &N)); return 3 + 2 * N; }
+
+/* The scan and its pairings of observe_model_joint and observe_model_joint_iterated, checked and unpacked ONCE: prhs[2..6] = model m x 1,
+ * z m x 2, R 2 x 2 x m, lm m x 1 (1-based, 0 = left out), gate.  Returns m. */
+static mwSize joint_scan(const char *cmd, const mxArray *prhs[], ekf_model_obs o[EKF_JOINT_MAX], int64_t lm[EKF_JOINT_MAX]) {
+    const mwSize m = prhs[2] ? mxGetNumberOfElements(prhs[2]) : 0;
+    if (m < 1 || m > EKF_JOINT_MAX) mexErrMsgIdAndTxt("ekfslam:usage", "%s: between 1 and %d observations in one call", cmd, EKF_JOINT_MAX);
+    if (!mxGetPr(prhs[2]) || !prhs[3] || mxGetM(prhs[3]) != m || mxGetNumberOfElements(prhs[3]) != 2 * m || !mxGetPr(prhs[3]))
+        mexErrMsgIdAndTxt("ekfslam:usage", "%s: z needs m x 2 elements, one row per entry of model", cmd);
+    if (!prhs[4] || mxGetNumberOfElements(prhs[4]) != 4 * m || !mxGetPr(prhs[4]))
+        mexErrMsgIdAndTxt("ekfslam:usage", "%s: R needs 2 x 2 x m elements", cmd);
+    if (!prhs[5] || mxGetNumberOfElements(prhs[5]) != m || !mxGetPr(prhs[5]))
+        mexErrMsgIdAndTxt("ekfslam:usage", "%s: lm needs m elements, one per entry of model", cmd);
+    if (!prhs[6] || mxGetNumberOfElements(prhs[6]) != 1 || !mxGetPr(prhs[6]))
+        mexErrMsgIdAndTxt("ekfslam:usage", "%s: gate is one number (Inf: no gate)", cmd);
+    for (mwSize k = 0; k < m; ++k) {
+        o[k].model = (int32_t)mxGetPr(prhs[2])[k]; o[k].reserved = 0;
+        o[k].z[0] = mxGetPr(prhs[3])[k]; o[k].z[1] = mxGetPr(prhs[3])[m + k];       /* column-major m x 2 */
+        for (int q = 0; q < 4; ++q) o[k].R[q] = mxGetPr(prhs[4])[4 * k + q];
+        o[k].lm[0] = o[k].lm[1] = -1;
+        o[k].anchor[0] = o[k].anchor[1] = 0.0;
+        o[k].gate = HUGE_VAL;
+        const double v = mxGetPr(prhs[5])[k];                                       /* 1-based -> 0-based, 0 (left out) -> -1 */
+        if (!(v >= 0.0 && v < 9.0e15 && (double)(int64_t)v == v))                   /* (no libm call: the gateway links without it) */
+            mexErrMsgIdAndTxt("ekfslam:usage", "%s: lm holds landmark numbers (1-based), 0 = left out", cmd);
+        lm[k] = (int64_t)v - 1;
+    }
+    return m;
+}
 
 void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
     char cmd[32];
@@ -545,35 +576,37 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
                                                      joint d2 <= gate; res 1 x 5 = [d2 dof pairings outcome firstIrregular] (outcome 1 applied, 2 gated) */
         need(nrhs, 7, cmd);
         if (!HAVE_OBSERVE_MODEL_JOINT) mexErrMsgIdAndTxt("ekfslam:usage", "observe_model_joint: this libekfslam has no ekf_observe_model_joint");
-        const mwSize m = prhs[2] ? mxGetNumberOfElements(prhs[2]) : 0;
-        if (m < 1 || m > EKF_JOINT_MAX) mexErrMsgIdAndTxt("ekfslam:usage", "observe_model_joint: between 1 and %d observations in one call", EKF_JOINT_MAX);
-        if (!mxGetPr(prhs[2]) || !prhs[3] || mxGetM(prhs[3]) != m || mxGetNumberOfElements(prhs[3]) != 2 * m || !mxGetPr(prhs[3]))
-            mexErrMsgIdAndTxt("ekfslam:usage", "observe_model_joint: z needs m x 2 elements, one row per entry of model");
-        if (!prhs[4] || mxGetNumberOfElements(prhs[4]) != 4 * m || !mxGetPr(prhs[4]))
-            mexErrMsgIdAndTxt("ekfslam:usage", "observe_model_joint: R needs 2 x 2 x m elements");
-        if (!prhs[5] || mxGetNumberOfElements(prhs[5]) != m || !mxGetPr(prhs[5]))
-            mexErrMsgIdAndTxt("ekfslam:usage", "observe_model_joint: lm needs m elements, one per entry of model");
-        if (!prhs[6] || mxGetNumberOfElements(prhs[6]) != 1 || !mxGetPr(prhs[6]))
-            mexErrMsgIdAndTxt("ekfslam:usage", "observe_model_joint: gate is one number (Inf: no gate)");
         ekf_model_obs o[EKF_JOINT_MAX];
         int64_t lm[EKF_JOINT_MAX];
-        for (mwSize k = 0; k < m; ++k) {
-            o[k].model = (int32_t)mxGetPr(prhs[2])[k]; o[k].reserved = 0;
-            o[k].z[0] = mxGetPr(prhs[3])[k]; o[k].z[1] = mxGetPr(prhs[3])[m + k];       /* column-major m x 2 */
-            for (int q = 0; q < 4; ++q) o[k].R[q] = mxGetPr(prhs[4])[4 * k + q];
-            o[k].lm[0] = o[k].lm[1] = -1;
-            o[k].anchor[0] = o[k].anchor[1] = 0.0;
-            o[k].gate = HUGE_VAL;
-            const double v = mxGetPr(prhs[5])[k];                                       /* 1-based -> 0-based, 0 (left out) -> -1 */
-            if (!(v >= 0.0 && v < 9.0e15 && (double)(int64_t)v == v))                   /* (no libm call: the gateway links without it) */
-                mexErrMsgIdAndTxt("ekfslam:usage", "observe_model_joint: lm holds landmark numbers (1-based), 0 = left out");
-            lm[k] = (int64_t)v - 1;
-        }
+        const mwSize m = joint_scan(cmd, prhs, o, lm);
         ekf_joint_result res;
         check(h, ekf_observe_model_joint(h, o, (int64_t)m, lm, mxGetPr(prhs[6])[0], &res, NULL, NULL));
         plhs[0] = mxCreateDoubleMatrix(1, 5, mxREAL);
         mxGetPr(plhs[0])[0] = res.d2; mxGetPr(plhs[0])[1] = (double)res.dof; mxGetPr(plhs[0])[2] = (double)res.pairings;
         mxGetPr(plhs[0])[3] = (double)res.outcome; mxGetPr(plhs[0])[4] = (double)(res.first_irregular + 1);
+        return;
+    }
+    if (!strcmp(cmd, "observe_model_joint_iterated")) {   /* res = (h, model, z, R, lm, gate, iterations, tol): observe_model_joint relinearised up to
+                                                     `iterations` times (1..16), stopping where no entry moves by more than tol; the gate and res(1:5) are the
+                                                     first linearisation's; res 1 x 8 = [d2 dof pairings outcome firstIrregular used converged step] */
+        need(nrhs, 9, cmd);
+        if (!HAVE_OBSERVE_MODEL_JOINT_ITERATED)
+            mexErrMsgIdAndTxt("ekfslam:usage", "observe_model_joint_iterated: this libekfslam has no ekf_observe_model_joint_iterated");
+        ekf_model_obs o[EKF_JOINT_MAX];
+        int64_t lm[EKF_JOINT_MAX];
+        const mwSize m = joint_scan(cmd, prhs, o, lm);
+        if (!prhs[7] || mxGetNumberOfElements(prhs[7]) != 1 || !mxGetPr(prhs[7]) || !prhs[8] || mxGetNumberOfElements(prhs[8]) != 1 || !mxGetPr(prhs[8]))
+            mexErrMsgIdAndTxt("ekfslam:usage", "observe_model_joint_iterated: iterations and tol are one number each");
+        const double n = mxGetPr(prhs[7])[0];
+        if (!(n >= 1.0 && n <= (double)EKF_JOINT_ITER_MAX && (double)(int32_t)n == n))
+            mexErrMsgIdAndTxt("ekfslam:usage", "observe_model_joint_iterated: iterations is a whole number, 1 .. %d", EKF_JOINT_ITER_MAX);
+        ekf_joint_result res;
+        ekf_joint_iter_result it;
+        check(h, ekf_observe_model_joint_iterated(h, o, (int64_t)m, lm, mxGetPr(prhs[6])[0], (int32_t)n, mxGetPr(prhs[8])[0], &res, &it, NULL, NULL));
+        plhs[0] = mxCreateDoubleMatrix(1, 8, mxREAL);
+        mxGetPr(plhs[0])[0] = res.d2; mxGetPr(plhs[0])[1] = (double)res.dof; mxGetPr(plhs[0])[2] = (double)res.pairings;
+        mxGetPr(plhs[0])[3] = (double)res.outcome; mxGetPr(plhs[0])[4] = (double)(res.first_irregular + 1);
+        mxGetPr(plhs[0])[5] = (double)it.used; mxGetPr(plhs[0])[6] = (double)it.converged; mxGetPr(plhs[0])[7] = it.last_step;
         return;
     }
     if (!strcmp(cmd, "predict_model")) {          /* (h, model m x 1 (1..3), u m x 3, M 3 x 3 x m): a chain of motion steps with their true Jacobians, in order,
