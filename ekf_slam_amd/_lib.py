@@ -48,6 +48,7 @@ class EkfLinearResult(ctypes.Structure):
 
 
 EKF_LINEAR_IRREGULAR, EKF_LINEAR_APPLIED, EKF_LINEAR_GATED = 0, 1, 2
+EKF_LINEAR_UNASSIGNED = 3                             # a step of ekf_observe_model_assigned whose observation was left out
 
 
 class EkfModelObs(ctypes.Structure):
@@ -186,6 +187,8 @@ SIGNATURES = {
     "ekf_associate_model": (_i32, [_vp, ctypes.POINTER(EkfModelObs), _i64, ctypes.POINTER(EkfModelMatch), _dp]),
     "ekf_assign_model": (_i32, [_vp, ctypes.POINTER(EkfModelObs), _i64, ctypes.POINTER(EkfModelAssigned), ctypes.POINTER(EkfModelMatch),
                                 ctypes.POINTER(_i64), _dp, _dp]),
+    "ekf_observe_model_assigned": (_i32, [_vp, ctypes.POINTER(EkfModelObs), _i64]),
+    "ekf_assigned_scan_result": (_i32, [_vp, ctypes.POINTER(_i64), ctypes.POINTER(EkfModelAssigned), ctypes.POINTER(EkfLinearResult), _dp]),
     "ekf_joint_innovation": (_i32, [_vp, ctypes.POINTER(EkfModelObs), _i64, ctypes.POINTER(_i64), _i64, ctypes.POINTER(EkfJointResult), _dp, _dp,
                                     _dp]),
     "ekf_observe_model_joint": (_i32, [_vp, ctypes.POINTER(EkfModelObs), _i64, ctypes.POINTER(_i64), _d, ctypes.POINTER(EkfJointResult), _dp, _dp]),

@@ -16,6 +16,7 @@
 #include "host/append_model.h" // landmarks that start from such a model's inverse, a scan per launch: append_model, model_invert
 #include "host/associate_model.h" // which landmark a sighting belongs to, a scan per call: associate_model
 #include "host/assign_model.h" // ... and the scan assigned to the map one-to-one: assign_model
+#include "host/model_assigned.h" // ... and assigned, then applied step by step with no wait between: observe_model_assigned, assigned_scan_result
 #include "host/joint.h"        // ... and a whole scan's pairings judged jointly, nh hypotheses per call: joint_innovation
 #include "host/joint_update.h" // ... and applied as ONE joint update behind a flush: observe_model_joint
 #include "host/joint_iter.h"   // ... relinearised: observe_model_joint_iterated, joint_iterate

@@ -13,7 +13,12 @@ static_assert(sizeof(ekfm::CandList) == 16 + 16 * EKF_ASSIGN_CANDIDATES, "CandLi
 int32_t create_assign_model(ekf_handle *h) {
     HIPCHK(h, dalloc(h, &h->d_aslists, (size_t)kAssocModelMax * h->am_nblk_cap));
     HIPCHK(h, dalloc(h, &h->d_assel, (size_t)kAssocModelMax));
-    HIPCHK(h, dalloc(h, &h->d_asres, 1));
+    // the result block, with the step records of ekf_observe_model_assigned in front of it in the same allocation: one copy then brings back
+    // the records and the block's head (host/model_assigned.h)
+    constexpr size_t recs = (size_t)kAssocModelMax * kLinearRecordDoubles;
+    HIPCHK(h, dalloc(h, &h->d_scanrec, recs + sizeof(AssignResult) / sizeof(double)));
+    h->d_asres = reinterpret_cast<AssignResult *>(h->d_scanrec + recs);
+    static_assert(sizeof(AssignResult) % sizeof(double) == 0, "the result block is whole doubles");
     return stage_alloc(h, &h->h_asres, sizeof(AssignResult), &h->ev_assign);
 }
 }  // namespace

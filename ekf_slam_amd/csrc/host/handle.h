@@ -224,6 +224,15 @@ struct ekf_handle {
     ekfm::CandList *d_aslists = nullptr, *d_assel = nullptr;
     AssignResult *d_asres = nullptr, *h_asres = nullptr;
     hipEvent_t ev_assign = nullptr;
+    // ---- ... and applied with no wait between the two (ekf_observe_model_assigned) ----
+    // one record per step of the scan on the device (in front of d_asres, in its allocation); the pinned block of the LATEST scan -- the
+    // records, then the head of the result block -- and the event behind its copy; scan_m: that scan's size (0: none yet); scan_host: the
+    // block was filled by the host (an empty map: no launch, no event)
+    double *d_scanrec = nullptr;
+    char *h_scan = nullptr;
+    hipEvent_t ev_scan = nullptr;
+    int64_t scan_m = 0;
+    bool scan_host = false;
     // ---- the joint compatibility of a scan's pairings (ekf_joint_innovation) ----
     // the hypotheses on the device and in pinned memory; the records, prefixes and nu of a call (joint_out_bytes) likewise, and the event behind
     // a call's readback; the stacked S of every hypothesis, 8 MiB on either side, allocated when first asked for

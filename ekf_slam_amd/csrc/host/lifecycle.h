@@ -81,6 +81,7 @@ int32_t ekf_create(const ekf_config *cfg, ekf_handle **out) {
     TRY(create_model_iter(h));
     TRY(create_assoc_model(h));
     TRY(create_assign_model(h));
+    TRY(create_model_assigned(h));
     TRY(create_joint(h));
     HIPCHK(h, hipDeviceSynchronize());      // dalloc clears on the null stream, which the handle's (non-blocking) streams do not wait for
     return EKF_OK;

@@ -287,6 +287,14 @@ struct ModelArgs {
     int32_t pstart;
 };
 
+// ... with the landmark read on the device from an AssignedRecord an earlier launch left (model_assigned.h): ModelArgs with a[0], a[1] and
+// `skipped` set by the KERNEL at entry -- the host leaves them -1, -1, 0.  skipped: the record names no landmark below n_mm / 2, the step is a
+// finite no-op with outcome 3.0 (EKF_LINEAR_UNASSIGNED) that no counter counts.
+struct AssignedModelArgs : ModelArgs {
+    int32_t skipped;
+    int32_t pad_;
+};
+
 // ... relinearised up to `iterations` times on lane 0 (model_iter.h, ekfm::model_iterate): ModelArgs and the loop's two controls.  The pair
 // of the LAST linearisation goes to the ring; the launch's shape, its operands and its outputs are k_gather_model's.
 struct IterModelArgs : ModelArgs {

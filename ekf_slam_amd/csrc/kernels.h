@@ -221,6 +221,12 @@ hipError_t launch_linear_probe(const DevState &st, const LinearArgs &a, double *
 // a target on the robot (q = 0) or a non-finite q counts and reports as an irregular S
 hipError_t launch_gather_model(const DevState &st, const ModelArgs &a, double *rec, int64_t *cnt, int storage, hipStream_t s);
 hipError_t launch_model_probe(const DevState &st, const ModelArgs &a, double *rec, int storage, hipStream_t s);
+// ... with the landmark read on the device (model_assigned.h).  k_gather_model_assigned: launch_gather_model for the landmark slot->landmark
+// (device: AssignResult::out[k] of an earlier launch_assign_model on the same stream), a.a left {-1, -1} and a.skipped 0 by the caller; a
+// slot that names no landmark below a.n_mm / 2 makes the launch a finite no-op -- a zero pair, the state copied, outcome 3.0 and d2 NaN in
+// rec, neither counter touched.  rec: the scan's record of this observation, kLinearRecordDoubles doubles
+hipError_t launch_gather_model_assigned(const DevState &st, const AssignedModelArgs &a, const AssignedRecord *slot, double *rec, int64_t *cnt,
+                                        int storage, hipStream_t s);
 // ... relinearised (model_iter.h).  k_gather_model_iter / k_model_iter_probe: the two launches above with ekfm::model_iterate on lane 0 and the
 // last linearisation's pair; rec keeps the FIRST linearisation's S, nu and d2 and the overall outcome, so the counters and the gate mean
 // what they mean above, and itrec (device, kIterRecordDoubles doubles) takes the iteration record

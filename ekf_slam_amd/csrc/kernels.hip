@@ -48,6 +48,7 @@ namespace {
 #include "constrain.h"        // a constraint between two landmarks: k_constrain_probe, k_gather_constrain
 #include "linear_obs.h"       // a linear observation as an update-step: k_gather_linear, k_linear_probe
 #include "model_obs.h"        // ... through a range / bearing / relative-position model evaluated at the live x: k_gather_model, k_model_probe
+#include "model_assigned.h"   // ... with the landmark read from a scan's assignment on the device: k_gather_model_assigned
 #include "model_iter.h"       // ... relinearised on lane 0 (the iterated EKF update): k_gather_model_iter, k_model_iter_probe
 #include "associate_model.h" // a scan against the whole map under the models' conventions: k_assoc_model, k_assoc_model_reduce
 #include "assign_model.h"    // ... and assigned to it one-to-one: k_assign_candidates, k_assign_select, k_assign_solve

@@ -125,6 +125,19 @@ hipError_t launch_model_probe(const DevState &st, const ModelArgs &a, double *re
     return launch_step_probe(linear_args_ok(st, a) && model_args_ok(a) && rec, [](auto ts) { return k_model_probe<decltype(ts)>; }, st, a, rec, storage, s);
 }
 
+// the step whose landmark the device reads: launch_step's grid (it depends on n_mm alone), with the slot as one more argument; the host
+// names no landmark (the kernel checks the one it reads against n_mm) and a model that takes one target
+hipError_t launch_gather_model_assigned(const DevState &st, const AssignedModelArgs &a, const AssignedRecord *slot, double *rec, int64_t *cnt,
+                                        int storage, hipStream_t s) {
+    if (!(linear_args_ok(st, a) && a.model >= 1 && a.model <= 4 && a.a[0] == -1 && a.a[1] == -1 && a.skipped == 0 && a.npend < st.pcap && slot &&
+          rec && cnt))
+        return hipErrorInvalidValue;
+    const int64_t grid = std::max<int64_t>(1, cdiv(st.tm.padded(a.n_mm), kBlock));
+    return with_storage(storage, [&](auto ts) {
+        hipLaunchKernelGGL(k_gather_model_assigned<decltype(ts)>, dim3((unsigned)grid), dim3(kBlock), 0, s, st, a, slot, rec, cnt);
+    });
+}
+
 // the relinearised step: launch_step's grid and launch_step_probe's wavefront, with the iteration record as one more argument
 hipError_t launch_gather_model_iter(const DevState &st, const IterModelArgs &a, double *rec, int64_t *cnt, double *itrec, int storage, hipStream_t s) {
     if (!(linear_args_ok(st, a) && model_args_ok(a) && a.npend < st.pcap && rec && cnt && itrec) || a.iterations < 1 ||

@@ -12,7 +12,9 @@
 // differs between a step with a constant H and one through a model (model_obs.h) is two overloads found by their argument types:
 //     small_solve(a, sm, sol)   lane 0's work on the loaded operands: S, nu, the outcome, the record, the solve (a model: h(x) and H first)
 //     step_H(a, sol)            where the column lanes read H: the argument block, or the LDS copy a model's lane 0 left
-// Both kernels compile to the code they had as two texts (profiles/observe_step/README.md).
+//     step_counted(a, sol)      whether a launch that did not apply is counted: always, but for model_assigned.h's skipped step
+// Both kernels compile to the code they had as two texts (profiles/observe_step/README.md), and to the same code with the third
+// overload in the body (profiles/observe_assigned/README.md).
 // The small part's solve, the record and workgroup 0's robot part are pair_column.h's.  The column's own share (steps (1), (3), (3b)) is
 // the twin of its load_column_operands / finish_pair_column, kept as text of its own: called from here those two cost k_gather_linear
 // 0.1-0.4 us of its 8-17 (measured against the parent commit, profiles/pair_column/README.md), although they are the same statements.
@@ -58,6 +60,10 @@ __device__ __forceinline__ void small_solve(const LinearArgs &a, double *sm, Lin
     pair_solve(sol, S, nu[0], nu[1], Gs, Gs + 7, sm, outcome == 1);
 }
 __device__ __forceinline__ const double *step_H(const LinearArgs &a, const LinearSolve &) { return a.H; }
+// whether a launch that did not apply goes into one of the two counters: every step's does, but for a step that was never meant to
+// apply (model_assigned.h's overload: an observation its scan's assignment left out)
+template <typename A, typename Solve>
+__device__ __forceinline__ bool step_counted(const A &, const Solve &) { return true; }
 
 // The small part, by the first wavefront of a workgroup: the kLinearSmall operands one per lane (each patched entry walks the ring
 // once, on a lane of its own), then lane 0's small_solve.  Called by every lane of the workgroup; ends with a barrier.
@@ -159,7 +165,7 @@ __device__ __forceinline__ void gather_step_body(const DevState &st, const A &a,
     if (blockIdx.x == 0) {
         store_robot_part(st, cur, pair_dest(st, cur, a.pstart, a.npend, a.n_mm), sol, tid);
         if (tid >= 128 && tid < 128 + kLinearRecordDoubles) rec[tid - 128] = sol.rec[tid - 128];
-        if (tid == 0 && !ok) {
+        if (tid == 0 && !ok && step_counted(a, sol)) {
             const int which = sol.rec[7] == 0.0 ? 0 : 1;
             cnt[which] = cnt[which] + 1;
         }

@@ -510,6 +510,28 @@ class Engine:
                                               _p(cand_d2) if want_candidates else None, ctypes.byref(total)))
         return marshal.assigned_result(out, match, m, total.value, cand, cand_d2)
 
+    # ---- ... and assigned, then applied, with no wait between the two (include/ekfslam.h: ekf_observe_model_assigned) ----
+    def observe_model_assigned(self, entries):
+        """One scan assigned to the map and applied by the device alone: assign_model's launches, then one observe_model step per entry
+        whose landmark the launch reads on the device -- a finite no-op for an entry that was left out.  entries as for assign_model (every
+        gate finite: the price of leaving the entry out and the gate of its step).  Queues everything and returns; nothing is waited for
+        or flushed, pending grows by the number of entries (ekf_observe_model_assigned).  assigned_scan_result() fetches what happened."""
+        self._observe_model_assigned(*marshal.scan_obs(entries))
+
+    def _observe_model_assigned(self, arr, m):
+        self._check(self.lib.ekf_observe_model_assigned(self.h, arr, m))
+
+    def assigned_scan_result(self):
+        """The latest observe_model_assigned scan, waited for (its own event alone): {'landmark', 'd2', 'ncand', 'total'} as assign_model
+        would have returned them at the state the scan saw (0-based, -1 = left out), and per step 'nu' (m x 2), 'S' (m x 2 x 2),
+        'outcome' (EKF_LINEAR_APPLIED / _GATED / _IRREGULAR, EKF_LINEAR_UNASSIGNED for a left-out entry) and 'step_d2' (NaN where there
+        is none).  Outcomes are data, nothing raises for them; before any scan EkfError (ekf_assigned_scan_result)."""
+        m = ctypes.c_int64(0)
+        out, res = (L.EkfModelAssigned * L.EKF_ASSIGN_MODEL_MAX)(), (L.EkfLinearResult * L.EKF_ASSIGN_MODEL_MAX)()
+        total = ctypes.c_double(0.0)
+        self._check(self.lib.ekf_assigned_scan_result(self.h, ctypes.byref(m), out, res, ctypes.byref(total)))
+        return marshal.assigned_scan_result(out, res, int(m.value), total.value)
+
     # ---- a scan's pairings judged jointly (include/ekfslam.h: ekf_joint_innovation) ----
     def joint_innovation(self, entries, hypotheses, want_prefix=True, want_nu=False, want_S=False):
         """The joint compatibility of a scan's pairings: entries as for associate_model (the gate is not read), hypotheses an nh x m

@@ -241,6 +241,16 @@ def assigned_result(out, match, m, total, cand=None, cand_d2=None):
     return res
 
 
+def assigned_scan_result(out, res, m, total):
+    """What ekf_assigned_scan_result reported of a scan, as arrays with one entry per observation: the assignment's 'landmark' (0-based, -1 =
+    left out), 'd2', 'ncand' and the float 'total'; each step's 'nu' (m x 2), 'S' (m x 2 x 2), 'outcome' and 'step_d2'."""
+    steps = [linear_result(res[k]) for k in range(m)]
+    return {"landmark": np.array([out[k].landmark for k in range(m)], dtype=np.int64), "d2": np.array([out[k].d2 for k in range(m)], dtype=np.float64),
+            "ncand": np.array([out[k].ncand for k in range(m)], dtype=np.int64), "total": float(total),
+            "nu": np.array([s["nu"] for s in steps]).reshape(m, 2), "S": np.array([s["S"] for s in steps]).reshape(m, 2, 2),
+            "outcome": np.array([s["outcome"] for s in steps], dtype=np.int64), "step_d2": np.array([s["d2"] for s in steps], dtype=np.float64)}
+
+
 # ---- the library's pure host functions ----
 def host_call(name, lib, *args):
     """One of the functions that take no handle (the kernels' own text, compiled for the host): `lib` None is the loaded library; a

@@ -217,6 +217,14 @@ class ShardGroup:
                 np.testing.assert_array_equal(r[key], v, err_msg="shards disagree on assign_model's " + key)
         return res[0]
 
+    def observe_model_assigned(self, entries):
+        """Not built for sharded handles, as observe_model is not: the scan's steps need each landmark's row-panel exchanged between the
+        shards.  The call goes to the shards, and the first one's library refuses it before anything changes (EkfError, invalid argument,
+        the message names sharding)."""
+        entries = list(entries)
+        for e in self.shards:
+            e.observe_model_assigned(entries)
+
     def run_threaded(self, fn):
         """fn(shard) on every shard, ONE HOST THREAD PER SHARD, with the exchange hook of transport (d) (include/ekfslam.h) set:
         wherever a library call needs an all-gather -- ekf_correct, ekf_prefetch_rows, the middle of ekf_measure's loop, a batch's

@@ -569,7 +569,7 @@ class _EkfBase:
             res[key] = res[key] + 1
         return res
 
-    def measure_model_assigned(self, entries, gate_match, gate_new, wait=False):
+    def measure_model_assigned(self, entries, gate_match, gate_new, wait=False, device_apply=False):
         """measure_model with the ambiguity discard replaced by the global-nearest-neighbour ASSIGNMENT: entries, gate_match, gate_new and
         wait as there.  ONE assign_model call with gate = gate_match, then per entry
           matched    it has an assigned landmark;
@@ -577,11 +577,25 @@ class _EkfBase:
           discarded  everything else: left out by the assignment although a landmark was inside its gate, or between the two gates.
         The matched entries go to observe_model(..., [landmark], gate=gate_match) in scan order, then ALL new ones to one
         add_landmarks_model call.  Returns [(kind, landmark)] per entry as measure_model.  Everything that changes the state goes through
-        those two logged methods, so a replayed log reproduces the run.  Unsharded handles only, as observe_model."""
+        those two logged methods, so a replayed log reproduces the run.  Unsharded handles only, as observe_model.
+        device_apply=True lets the DEVICE consume the assignment (ekf_observe_model_assigned): ONE observe_model_assigned call queues the
+        assignment and a step per entry -- the matched ones applied as above, every other one a finite no-op that takes a ring slot --
+        then the result is fetched: the one wait, now behind the queued steps instead of in front of them (wait is not read).  The kinds
+        are the ones above, classified from WHAT THE RESULT BLOCK HOLDS, which has no match records: an entry is new where ncand == 0 and
+        either the map was empty or gate_new == gate_match (ncand == 0 then says d2_best > gate_new); with gate_new > gate_match the
+        d2_best of those entries alone comes from one associate_model call made AFTER the scan's steps -- at the state the new landmarks
+        are started from, not the one the scan was assigned at.  Then ALL new entries go to one add_landmarks_model call.
+        The log gets no new kind: the scan is recorded after the fetch through record_model_observation, one edit per entry in scan
+        order -- a matched entry with its landmark and gate_match, every other one with landmark 1 and a gate of -1.0, an observe_model
+        that cannot apply (d2 >= 0 > -1, or irregular) and leaves the same zero pair in the same ring slot.  A replay therefore
+        reproduces x, s and P bit for bit on every storage kind and batch size; only what linear_rejections counts differs, by those
+        entries.  On F64 tiles the state after a flush is the default path's bit for bit."""
         gate_match, gate_new = float(gate_match), float(gate_new)
         if not gate_new >= gate_match:
             raise ValueError("measure_model_assigned: gate_new >= gate_match is required (and neither is NaN)")
         entries, scan = self._measure_scan("measure_model_assigned", entries, L.EKF_ASSIGN_MODEL_MAX, gate_match)
+        if device_apply:
+            return self._measure_assigned_on_device(entries, scan, gate_match, gate_new)
         res = self._e.assign_model(scan)
         kinds, paired = [], {}
         for k in range(len(entries)):
@@ -593,6 +607,31 @@ class _EkfBase:
             else:
                 kinds.append("discarded")
         return self._measure_carry_out(entries, kinds, paired, gate_match, wait)
+
+    def _measure_assigned_on_device(self, entries, scan, gate_match, gate_new):
+        """measure_model_assigned(..., device_apply=True) behind its checks: the scan queued, the result fetched, the kinds, the log, the
+        new landmarks."""
+        arr, m = marshal.scan_obs(scan)                                     # the one array: sent, then logged from
+        empty = self._e.N == 0
+        self._e._observe_model_assigned(arr, m)
+        res = self._e.assigned_scan_result()
+        paired = {k: int(res["landmark"][k]) for k in range(m) if int(res["landmark"][k]) >= 0}
+        loose = [k for k in range(m) if k not in paired and int(res["ncand"][k]) == 0]
+        if loose and not empty and gate_new > gate_match:
+            far = self._e.associate_model([scan[k] for k in loose])
+            loose = [k for k, best, d2 in zip(loose, far["best"], far["d2_best"]) if int(best) < 0 or float(d2) > gate_new]
+        if self.log is not None and not empty:                              # (an empty map: no step was queued)
+            for k, o in enumerate(arr[:m]):
+                z, R = np.array(o.z[:]), np.array(o.R[:]).reshape(2, 2, order="F")
+                if k in paired:
+                    self.log.record_model_observation(o.model, z, R, [paired[k] + 1], None, gate_match)
+                else:
+                    self.log.record_model_observation(o.model, z, R, [1], None, -1.0)
+        out = [("matched", paired[k] + 1) if k in paired else ("discarded", 0) for k in range(m)]
+        if loose:
+            for k, number in zip(loose, self.add_landmarks_model([entries[k] for k in loose])):
+                out[k] = ("new", number)
+        return out
 
     @staticmethod
     def _measure_scan(who, entries, cap, gate_match):

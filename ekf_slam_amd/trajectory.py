@@ -13,6 +13,13 @@ an observation).  What a kind holds beyond that is its PAYLOAD, kept in a dictio
 the format that first carries each, the arrays a file has for it and how a replay applies it are ONE table, `_KINDS_TABLE` below.  A file
 is written in the highest format any of its edits needs (no edits: format 1, the same arrays as ever) and holds the arrays of every kind
 up to that format, empty where nothing was recorded -- a reader of an older format alone would not know the newer kinds.
+
+A scan the DEVICE assigned and applied (measure_model_assigned(..., device_apply=True) of ekf_slam_amd/slam.py) has NO kind of its own: once
+its result has been fetched it is recorded as one 'observe_model' edit per entry, in scan order -- an assigned entry with its landmark and
+the scan's gate, an entry that was left out with landmark 1 and a gate of -1.0.  On replay the latter is an observe_model that cannot
+apply (d2 >= 0 > -1, or irregular): it leaves the zero pair in the ring slot the device's skipped step left, so a replay reproduces x, s
+and P bit for bit on every storage kind and batch size.  Only what linear_rejections counts differs, by the left-out entries: the replay
+counts each as gated (or irregular), the device's skipped step is counted by neither counter.
 """
 from collections import namedtuple
 

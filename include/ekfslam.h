@@ -379,7 +379,8 @@ int32_t ekf_nearest_landmarks(ekf_handle *h, const double R[4] /* 2x2 column-maj
  * (a recorded predict(u) is carried out first, as by every reader).  Arguments and refusals as above; an irregular S is no error here.
  * ekf_linear_rejections synchronises, reports how many ekf_observe_linear launches since the last call did not apply (S irregular;
  * gated) and resets both counts; either pointer may be NULL. */
-enum { EKF_LINEAR_APPLIED = 1, EKF_LINEAR_IRREGULAR = 0, EKF_LINEAR_GATED = 2 };
+enum { EKF_LINEAR_APPLIED = 1, EKF_LINEAR_IRREGULAR = 0, EKF_LINEAR_GATED = 2,
+       EKF_LINEAR_UNASSIGNED = 3 /* a step of ekf_observe_model_assigned whose observation the assignment left out; nothing else reports it */ };
 typedef struct ekf_linear_obs {
     double  z[2];         /* the observed value of H x                                                    */
     double  R[4];         /* 2x2 column-major noise covariance (rules of ekf_constrain_landmarks' R)      */
@@ -573,6 +574,37 @@ int32_t ekf_assign_model(ekf_handle *h, const ekf_model_obs *obs, int64_t m,
                          int64_t            *cand       /* m x EKF_ASSIGN_CANDIDATES row-major, or NULL */,
                          double             *cand_d2    /* same shape, or NULL (both or neither) */,
                          double             *total      /* or NULL */);
+/* "Decide" and "apply" with NO host wait between them.  After ekf_assign_model the host reads out[k].landmark and only then can it name the
+ * target of each ekf_observe_model: the device idles for that round trip once per scan.  ekf_observe_model_assigned queues both: the three
+ * launches of the assignment, then, for k = 0 .. m - 1 in scan order, ONE update-step whose launch reads out[k].landmark ON THE DEVICE:
+ *   assigned    ekf_observe_model's update-step for obs[k] at that landmark: relinearised at the then-live state (which carries the steps
+ *               before it), gated by obs[k].gate, the same launch shape, one pair into the pending ring.
+ *   left out    (-1) a finite no-op as a gated step is: a zero pair takes the ring slot and the state is copied.  Its record says outcome
+ *               EKF_LINEAR_UNASSIGNED, d2 NaN, S and nu zero, and ekf_linear_rejections does NOT count it.  Irregular and gated steps of
+ *               assigned observations are counted as ekf_observe_model counts them.
+ * THE REFERENCE SEQUENCE.  On the same state the call leaves, bit for bit, the x, s, P (ekf_get_P) and ekf_pending that this leaves:
+ *     ekf_assign_model(obs, m, out, ...);  then for k in scan order
+ *         out[k].landmark >= 0:  ekf_observe_model(obs[k] with lm[0] = out[k].landmark, NULL)
+ *         otherwise:             ekf_observe_model(obs[k] with lm[0] = 0 and gate = -1, NULL)       (a step that cannot apply)
+ * on every storage kind and batch size; on F64 tiles it also equals, after ekf_flush, the sequence with the left-out entries omitted.
+ * obs and m as for ekf_assign_model: 1 <= m <= EKF_ASSIGN_MODEL_MAX, models 1-4, lm = {-1, -1}, every gate finite -- it is both the price
+ * of leaving the observation out and the gate of its step.
+ * The call's place in a handle's order is ekf_observe_model's: unsharded, the measure loop settled, a recorded predict carried out first; it
+ * waits for nothing and flushes nothing.  ekf_pending grows by m; the batch and cfg.async_flush bookkeeping runs after every step as after
+ * every update-step, so a scan may cross a batch boundary and a pass over P may start in the middle of it.  The assignment counts as one
+ * launch under EKF_KERNEL_ASSOCIATE, the steps as m under EKF_KERNEL_GATHER.  Behind the last step ONE asynchronous copy brings the scan's
+ * result into pinned memory of the handle's own, with an event behind it.  N = 0: no launch, nothing changes (ekf_pending too), and the
+ * result says every observation is left out, ncand 0, total = the sum of the gates.
+ * Refused with every bit of the state and ekf_pending as found, in this order: ekf_assign_model's refusals (h or obs NULL, m out of range,
+ * per entry what ekf_associate_model refuses, a gate that is not finite: EKF_ERR_INVALID_ARG; a sharded correction between begin and
+ * finish: EKF_ERR_STATE), then ekf_observe_model's for a handle with world > 1 (EKF_ERR_INVALID_ARG).
+ * ekf_assigned_scan_result waits for the event of the LATEST scan alone -- a pass in flight is not waited for -- and reports it: *m its size,
+ * out[k] and *total what ekf_assign_model would have returned for that scan at the state it saw, bit for bit; res[k] the nu, S, d2 and
+ * outcome of step k, for an assigned k what ekf_observe_model(..., res) reports.  Every pointer may be NULL.  A later scan replaces an
+ * earlier scan's result.  Outcomes are data: an irregular step does not make this call fail.  Before any scan: EKF_ERR_STATE. */
+int32_t ekf_observe_model_assigned(ekf_handle *h, const ekf_model_obs *obs, int64_t m);
+int32_t ekf_assigned_scan_result(ekf_handle *h, int64_t *m /* or NULL */, ekf_model_assigned *out /* m, or NULL */,
+                                 ekf_linear_result *res /* m, or NULL */, double *total /* or NULL */);
 /* A scan judged AS A WHOLE: the joint compatibility of its pairings.  ekf_associate_model scores every observation against every landmark
  * one at a time; where the pose is uncertain and the map locally tight several landmarks pass an observation's gate, and only a JOINT test
  * uses that all innovations of a scan share the robot's error.  A hypothesis pairs observation k with landmark hyp[i * m + k] (0-based) or
