@@ -184,6 +184,7 @@ SIGNATURES = {
                                  ctypes.POINTER(EkfIteratedResult)]),
     "ekf_append_model": (_i32, [_vp, ctypes.POINTER(EkfModelInit), _i64, ctypes.POINTER(_i64)]),
     "ekf_model_invert": (_i32, [_i32, _dp, _dp, _dp, _dp, _dp]),
+    "ekf_join_map": (_i32, [_vp, _vp, _d, ctypes.POINTER(_i64)]),
     "ekf_associate_model": (_i32, [_vp, ctypes.POINTER(EkfModelObs), _i64, ctypes.POINTER(EkfModelMatch), _dp]),
     "ekf_assign_model": (_i32, [_vp, ctypes.POINTER(EkfModelObs), _i64, ctypes.POINTER(EkfModelAssigned), ctypes.POINTER(EkfModelMatch),
                                 ctypes.POINTER(_i64), _dp, _dp]),

@@ -108,6 +108,17 @@ struct AppendModelArgs {
     AppendModelEntry e[kAppendModelMax];
 };
 
+// k_join_state / k_join_rows (join_map.h): the M landmarks of a LOCAL handle, expressed in the frame of this handle's robot pose and
+// independent of its P, joined into the map behind its N landmarks -- local landmark i becomes landmark N + i, the robot composes with the
+// local one.  The local handle's DevState travels beside the global one; both are flushed and live on the same device.
+struct JoinMapArgs {
+    int64_t N;                // landmarks of the global map before the join
+    int64_t M;                // landmarks of the local map
+    double signature_offset;  // added to every local signature
+    int32_t cur;              // the global handle's live buffer: read; cur ^ 1 is written whole
+    int32_t lcur;             // the local handle's live buffer: read only
+};
+
 // k_predict_model (predict_model.h): a chain of m <= kPredictModelMax motion steps through the models of ekfm::motion_eval, carried out in
 // order by ONE launch that reads buffer cur and writes buffer cur ^ 1, as k_predict.  No tile is read: the storage type does not matter.
 // The steps travel in the argument block, M as its six unique entries -- 80 bytes a step, 2.5 KiB at 32 (nine entries a step would not fit

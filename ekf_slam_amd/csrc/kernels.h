@@ -32,6 +32,13 @@ hipError_t launch_append(const DevState &st, const AppendArgs &a, int storage, h
 // k_append_model (append_model.h): a.m <= kAppendModelMax landmarks appended by ONE launch at the live robot state
 hipError_t launch_append_model(const DevState &st, const AppendModelArgs &a, int storage, hipStream_t s);
 
+// k_join_state / k_join_rows (join_map.h): the M landmarks of the flushed local state `lo` (same device, read only) joined behind the N of
+// `st`.  launch_join_state: x, Prr and the strip from buffer a.cur into a complete buffer a.cur ^ 1, s and the live diagonal copies of the
+// new landmarks; the caller flips cur.  launch_join_rows (a.M >= 1, both stores unsharded): tile rows 2 N .. 2 (N + M) - 1, columns <= row,
+// from buffer a.cur of `st` and the tiles (local_storage) and live diagonal copies of `lo`.  Neither reads what the other writes.
+hipError_t launch_join_state(const DevState &st, const DevState &lo, const JoinMapArgs &a, hipStream_t s);
+hipError_t launch_join_rows(const DevState &st, const DevState &lo, const JoinMapArgs &a, int storage, int local_storage, hipStream_t s);
+
 // fused_predict != nullptr folds predict(u) into the correction (one launch instead of two, identical arithmetic)
 // fuse_downdate: the kernel also applies its pair to the landmark block (small maps: a.n_mm <= gather_fuse_max_rows(), one
 // workgroup); the pair is then NOT written to the pending ring and no downdate launch must follow

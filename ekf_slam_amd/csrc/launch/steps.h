@@ -1,4 +1,4 @@
-// Fragment of kernels.hip, the launchers of the steps: predict, a chain of model predicts, append, the gather of a correction in its five forms, a shard's
+// Fragment of kernels.hip, the launchers of the steps: predict, a chain of model predicts, append, the join of a local map, the gather of a correction in its five forms, a shard's
 // row-panels, the association and the model-convention association of a scan (declared in kernels.h, in this order).
 #pragma once
 
@@ -44,6 +44,24 @@ hipError_t launch_append_model(const DevState &st, const AppendModelArgs &a, int
     return with_storage(storage, [&](auto ts) {
         hipLaunchKernelGGL(k_append_model<decltype(ts)>, dim3((unsigned)grid), dim3(kBlock), 0, s, st, a);
     });
+}
+
+hipError_t launch_join_state(const DevState &st, const DevState &lo, const JoinMapArgs &a, hipStream_t s) {
+    if (a.N < 0 || a.M < 0 || 2 * (a.N + a.M) > st.ldm || 2 * a.M > lo.ldm) return hipErrorInvalidValue;
+    const int64_t cols = 2 * (a.N + a.M);
+    const int64_t grid = cdiv(cols > 0 ? cols : 1, kBlock);
+    hipLaunchKernelGGL(k_join_state, dim3((unsigned)grid), dim3(kBlock), 0, s, st, lo, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_join_rows(const DevState &st, const DevState &lo, const JoinMapArgs &a, int storage, int local_storage, hipStream_t s) {
+    if (a.N < 0 || a.M < 1 || 2 * (a.N + a.M) > st.ldm || 2 * a.M > lo.ldm || st.tm.world != 1 || lo.tm.world != 1) return hipErrorInvalidValue;
+    const int64_t per_row = cdiv(a.N + a.M, kBlock);          // workgroups per new landmark: 256 column landmarks each
+    const int64_t grid = a.M * per_row;
+    if (grid > 0x7fffffffll) return hipErrorInvalidValue;
+    return with_storage(storage, [&](auto td) { with_storage(local_storage, [&](auto tsrc) {
+        hipLaunchKernelGGL((k_join_rows<decltype(td), decltype(tsrc)>), dim3((unsigned)grid), dim3(kBlock), 0, s, st, lo, a, (int32_t)per_row);
+    }); });
 }
 
 // k_gather.  The kernel is 216 VGPRs wide and every flag doubles its instantiations, so only the forms a handle can ask for exist:

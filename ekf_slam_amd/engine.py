@@ -462,6 +462,22 @@ class Engine:
         self._check(self.lib.ekf_append_model(self.h, arr, m, ctypes.byref(first)))
         return int(first.value)
 
+    # ---- a local map joined into this one (include/ekfslam.h: ekf_join_map) ----
+    def join_map(self, local_engine, signature_offset=0.0):
+        """Join the map of `local_engine` -- a filter of its own, started at this one's robot pose and independent of it, any tile edge
+        and storage kind, on the same device -- into this one on the device: the robot composes with the local robot, local landmark i
+        becomes landmark first + i with signature s_local[i] + signature_offset, the local cross-covariances kept (P' = J blockdiag(P,
+        PL) J').  A synchronising call on both engines: pending is 0 on both afterwards and the local one, otherwise untouched, may be
+        closed at once.  Returns the 0-based index of the first new landmark (ekf_join_map)."""
+        if not isinstance(local_engine, Engine):
+            raise TypeError("join_map: the local map is an Engine")
+        return self._join_map(local_engine, marshal.join_offset(signature_offset))
+
+    def _join_map(self, local_engine, offset):
+        first = ctypes.c_int64(-1)
+        self._check(self.lib.ekf_join_map(self.h, local_engine.h, offset, ctypes.byref(first)))
+        return int(first.value)
+
     @staticmethod
     def model_invert(model, xr, z, lib=None):
         """(t, Gx, Gz): the landmark that z observes from the robot state xr = (x, y, theta in degrees) through EKF_MODEL_RANGE_BEARING

@@ -146,6 +146,14 @@ def scan_obs(entries):
     return arr, len(entries)
 
 
+def join_offset(signature_offset, who="join_map"):
+    """signature_offset of join_map as the ABI takes it: one finite double."""
+    v = float(signature_offset)
+    if not np.isfinite(v):
+        raise ValueError("%s: signature_offset is finite" % who)
+    return ctypes.c_double(v)
+
+
 def model_inits(entries, who="append_model"):
     """(ekf_model_init[], m) of a scan of new landmarks [(model, z, R, signature), ...]."""
     entries = list(entries)

@@ -145,6 +145,11 @@ class ShardGroup:
         first = [e.append_model(entries) for e in self.shards]
         return first[0]
 
+    def join_map(self, local_engine, signature_offset=0.0):
+        """Not built for a shard group: the join writes and reads whole tile rows and a shard holds only its own tiles.  The call goes
+        to the first shard so that the refusal is the library's (EKF_ERR_INVALID_ARG, nothing changed)."""
+        return self.shards[0].join_map(local_engine, signature_offset)
+
     def correct(self, z, R, idx0):
         for e in self.shards:
             e.correct_begin(z, R, idx0)

@@ -305,6 +305,31 @@ class _EkfBase:
             merges.extend((k, d, float(v)) for (k, d, _), v in zip(batch, d2))
         return merges
 
+    def join_map(self, local, signature_offset=0.0):
+        """Join the map of `local` -- another filter of this layer (or an Engine) that was started at this one's robot pose, typically with
+        x = 0 and P = 0 at the moment this one stopped moving, and is independent of it -- into this one, on the device: the robot
+        composes with the local robot, the local landmarks are appended behind this map's in the global frame with signature
+        s_local + signature_offset, and the local map's own cross-covariances are kept (P' = J blockdiag(P, PL) J').  A synchronising
+        call on both; `local` is left as it was and may be dropped at once.  Returns the 1-based numbers of the new landmarks
+        (ekf_join_map).  The reference has no such method."""
+        le = local._e if isinstance(local, _EkfBase) else local
+        if not isinstance(le, Engine):
+            raise TypeError("join_map: the local map is a filter of this layer or an Engine")
+        offset = marshal.join_offset(signature_offset)                     # the one value: sent, then logged from
+        first = self._e._join_map(le, offset)
+        M = self._e.N - first
+        if self.log is not None:
+            self.log.record_map_join(le.get_x(), le.get_s(), le.get_P(), offset.value)     # (read once, after the call's flush)
+        return [first + b + 1 for b in range(M)]
+
+    def join_submap(self, local, gate=None, R=None, signature_offset=0.0):
+        """The map-joining POLICY: join_map(local, signature_offset), then, when `gate` is given, fuse_duplicates_batched(gate, R) -- the
+        landmarks both maps saw are found by the search and fused.  Returns (the 1-based numbers the new landmarks had right after the
+        join, the fused pairs [(keep, drop, d2)] as fuse_duplicates_batched reports them).  Both halves go through logged methods."""
+        new = self.join_map(local, signature_offset)
+        fused = self.fuse_duplicates_batched(gate, R) if gate is not None else []
+        return new, fused
+
     def observe_linear(self, z, R, Hr=None, landmarks=(), Hl=(), gate=float("inf"), wrap=(0, 0), rows=2, wait=False):
         """'H x was observed as z with noise covariance R' for a constant H: the 2 x 3 block Hr on the robot state (x, y, theta in
         degrees) plus one 2 x 2 block Hl[b] on each of up to two landmarks (1-based numbers) -- the exact Kalman update, as an

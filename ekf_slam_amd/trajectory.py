@@ -37,6 +37,7 @@ FORMAT_PREDICT = "ekfslam-trajectory-7"
 FORMAT_ITERATED = "ekfslam-trajectory-8"
 FORMAT_JOINT = "ekfslam-trajectory-9"
 FORMAT_JOINT_ITERATED = "ekfslam-trajectory-10"
+FORMAT_JOIN_MAP = "ekfslam-trajectory-11"
 EDIT_KINDS = ("remove", "constrain", "merge", "merge_batch")        # what record_edit takes
 OBSERVE = "observe"                                                  # record_observation's
 OBSERVE_MODEL = "observe_model"                                      # record_model_observation's
@@ -45,8 +46,11 @@ PREDICT_MODEL = "predict_model"                                      # record_mo
 OBSERVE_MODEL_ITERATED = "observe_model_iterated"                    # record_model_observation_iterated's
 OBSERVE_MODEL_JOINT = "observe_model_joint"                          # record_model_observation_joint's
 OBSERVE_MODEL_JOINT_ITERATED = "observe_model_joint_iterated"        # record_model_observation_joint_iterated's
+JOIN_MAP = "join_map"                                                # record_map_join's
 _FORMATS = (FORMAT, FORMAT_EDITS, FORMAT_BATCH, FORMAT_OBSERVE, FORMAT_MODEL, FORMAT_APPEND, FORMAT_PREDICT, FORMAT_ITERATED, FORMAT_JOINT,
             FORMAT_JOINT_ITERATED)
+# ... the ten formats of a log that speaks of ONE map; a log with a join also holds a second map's state and is written in the eleventh
+_ALL_FORMATS = _FORMATS + (FORMAT_JOIN_MAP,)
 _STEP_ARRAYS = ("u", "obs_ptr", "obs", "lm_ptr", "lm_index", "lm_loc")
 _EDIT_ARRAYS = ("edit_step", "edit_kind", "edit_ptr", "edit_idx", "edit_delta", "edit_R")
 
@@ -60,13 +64,39 @@ _ANCHOR = _Field("anchor", "anchor", _F, (2,), True)                 # NaN where
 # carries it.  replay(engine, idx0, delta, R, payload): applies one, landmarks 0-based.  store: the TrajectoryLog dictionary of its
 # payloads (None: the edit tuple is all there is); prefix, fields: the file's arrays for them, behind `<prefix>_edit`, the positions of
 # the edits they belong to.  entries: the payload is a list of tuples (fields keyed by index) behind the CSR offsets `<prefix>_ptr`.
-# trim(entry): what a loaded entry is cut back to.
-_Kind = namedtuple("_Kind", "name format replay store prefix fields entries trim", defaults=(None, None, (), False, None))
+# trim(entry): what a loaded entry is cut back to.  ragged: the payload is a dictionary; a field of tail None is an array whose size differs
+# from edit to edit and travels flattened behind CSR offsets of its own, `<prefix>_<suffix>_ptr` (shape(key, flat) gives a loaded one its
+# shape), a field of tail () is one number per edit.
+_Kind = namedtuple("_Kind", "name format replay store prefix fields entries trim ragged shape",
+                   defaults=(None, None, (), False, None, False, None))
 
 
 def _replay_observe(engine, idx0, z, R, o):
     engine.observe_linear(z[:o["rows"]], R, o["Hr"], idx0, [o["Hl"][b] for b in range(len(idx0))], gate=o["gate"],
                           wrap=tuple(int(w) for w in o["wrap"]), rows=o["rows"])
+
+
+def _replay_join(engine, idx0, d, R, o):
+    """The local map into a scratch F64 engine on the engine's device, then the join: exact for a local map that had float tiles too,
+    since every float is a double and the live diagonal copies are F64 on every storage kind."""
+    from .engine import Engine
+    M = o["s"].size
+    local = Engine(mode="known", capacity=max(M, 1), storage="f64", device=int(engine.cfg.device))
+    try:
+        local.set_x(o["x"])
+        if M:
+            local.set_s(o["s"])
+        local.set_P(o["P"])
+        engine.join_map(local, o["offset"])
+    finally:
+        local.close()
+
+
+def _join_shape(key, flat):
+    if key == "P":
+        n = int(round(flat.size ** 0.5))
+        return flat.reshape(n, n)
+    return flat
 
 
 def _trim_motion(step):
@@ -117,12 +147,19 @@ _KINDS_TABLE = (
                                                                iterations=int(R[0, 0]), tol=float(d[1])),
           "model_joint_iterations", "jointiter",
           (_Field("model", 0, _I, ()), _Field("z", 1, _F, (2,)), _Field("R", 2, _F, (2, 2)), _Field("landmark", 3, _I, ())), True),
+    # join_map: a local map joined into the map, idx empty; per join the local x, s and dense P (as read once after the call's flush) and
+    # the signature offset: the three arrays flattened behind CSR offsets of their own, the offset one number per join
+    _Kind(JOIN_MAP, 11, _replay_join, "map_joins", "join",
+          (_Field("x", "x", _F, None), _Field("s", "s", _F, None), _Field("P", "P", _F, None), _Field("offset", "offset", _F, ())),
+          ragged=True, shape=_join_shape),
 )
 _KINDS = tuple(k.name for k in _KINDS_TABLE)
 _KIND = {k.name: k for k in _KINDS_TABLE}
 
 
 def _arrays_of(kind):
+    if kind.ragged:
+        return (kind.prefix + "_edit",) + tuple(kind.prefix + "_" + f.suffix + t for f in kind.fields for t in (("_ptr", "") if f.tail is None else ("",)))
     return (kind.prefix + "_edit",) + ((kind.prefix + "_ptr",) if kind.entries else ()) + tuple(kind.prefix + "_" + f.suffix for f in kind.fields)
 
 
@@ -131,6 +168,15 @@ def _pack(kind, store):
     at = sorted(store)
     out = {kind.prefix + "_edit": np.array(at, dtype=np.int64)}
     items = [store[q] for q in at]
+    if kind.ragged:
+        for f in kind.fields:
+            if f.tail is not None:
+                out[kind.prefix + "_" + f.suffix] = np.array([it[f.key] for it in items], dtype=f.dtype)
+                continue
+            parts = [np.asarray(it[f.key], dtype=f.dtype).reshape(-1) for it in items]
+            out[kind.prefix + "_" + f.suffix + "_ptr"] = np.cumsum([0] + [p.size for p in parts]).astype(np.int64)
+            out[kind.prefix + "_" + f.suffix] = np.concatenate(parts) if parts else np.zeros(0, dtype=f.dtype)
+        return out
     if kind.entries:
         out[kind.prefix + "_ptr"] = np.cumsum([0] + [len(p) for p in items])
         items = [e for p in items for e in p]
@@ -153,7 +199,16 @@ def _unpack(kind, g, store):
             return None
         return v.astype(np.int64) if f.dtype is _I else v.copy()
     for k, q in enumerate(g[kind.prefix + "_edit"]):
-        if kind.entries:
+        if kind.ragged:
+            payload = {}
+            for f in kind.fields:
+                if f.tail is not None:
+                    payload[f.key] = value(f, k)
+                    continue
+                ptr = g[kind.prefix + "_" + f.suffix + "_ptr"]
+                payload[f.key] = kind.shape(f.key, g[kind.prefix + "_" + f.suffix][int(ptr[k]):int(ptr[k + 1])].copy())
+            store[int(q)] = payload
+        elif kind.entries:
             a, b = int(g[kind.prefix + "_ptr"][k]), int(g[kind.prefix + "_ptr"][k + 1])
             entries = [tuple(value(f, e) for f in kind.fields) for e in range(a, b)]
             store[int(q)] = [kind.trim(e) for e in entries] if kind.trim else entries
@@ -171,6 +226,7 @@ class TrajectoryLog:
         self.model_iterations = {}  # position in self.edits of an 'observe_model_iterated' edit -> {model, anchor or None, gate, iterations, tol}
         self.model_joints = {}      # position in self.edits of an 'observe_model_joint' edit -> [(model, z (2), R (2x2), landmark 1-based or 0), ...]
         self.model_joint_iterations = {}  # position in self.edits of an 'observe_model_joint_iterated' edit -> the same list
+        self.map_joins = {}         # position in self.edits of a 'join_map' edit -> {x (3 + 2 M), s (M), P dense, offset}: the local map
         self.observations = {}      # position in self.edits of an 'observe' edit -> {Hr (2x3), Hl (2x2x2), gate, wrap (2), rows}
 
     def __len__(self):
@@ -279,6 +335,17 @@ class TrajectoryLog:
             raise ValueError("record_model_append: at least one entry")
         self._record(APPEND_MODEL, payload=ents)
 
+    def record_map_join(self, x, s, P, signature_offset=0.0):
+        """A local map joined into the map (join_map of ekf_slam_amd/slam.py) made now, i.e. after the len(self) steps recorded so far:
+        the local state x (3 + 2 M), its signatures s (M) and its dense covariance P as they were when the join read them, then the
+        signature offset."""
+        xv = np.asarray(x, dtype=np.float64).reshape(-1).copy()
+        sv = np.asarray(s, dtype=np.float64).reshape(-1).copy()
+        Pm = np.asarray(P, dtype=np.float64)
+        if xv.size < 3 or (xv.size - 3) % 2 or sv.size != (xv.size - 3) // 2 or Pm.size != xv.size * xv.size:
+            raise ValueError("record_map_join: x has 3 + 2 M values, s has M and P is square of x's size")
+        self._record(JOIN_MAP, payload=dict(x=xv, s=sv, P=Pm.reshape(xv.size, xv.size).copy(), offset=float(signature_offset)))
+
     def record_model_predict(self, steps):
         """One chain of motion steps (predict_model of ekf_slam_amd/slam.py) made now, i.e. after the len(self) steps recorded so far:
         steps = [(model, u, M), ...], at least one, u and M of the size the model reads (2 and 2 x 2, or 3 and 3 x 3)."""
@@ -298,7 +365,7 @@ class TrajectoryLog:
             data = np.concatenate(parts) if parts and ptr[-1] else np.zeros((0, width) if width else (0,))
             return ptr, data
         ver = max([1] + [_KIND[e[1]].format for e in self.edits])
-        arrays = dict(format=np.array(_FORMATS[ver - 1]))
+        arrays = dict(format=np.array(_ALL_FORMATS[ver - 1]))
         if self.edits:
             e_ptr, e_idx = ragged([e[2] for e in self.edits], 0)
             arrays.update(edit_step=np.array([e[0] for e in self.edits], dtype=np.int64),
@@ -318,9 +385,9 @@ class TrajectoryLog:
     def load(path):
         g = np.load(path, allow_pickle=False)
         fmt = str(g["format"])
-        if fmt not in _FORMATS:
-            raise ValueError("not an %s file" % " / ".join(_FORMATS))
-        ver = _FORMATS.index(fmt) + 1
+        if fmt not in _ALL_FORMATS:
+            raise ValueError("not an %s file" % " / ".join(_ALL_FORMATS))
+        ver = _ALL_FORMATS.index(fmt) + 1
         held = [kind for kind in _KINDS_TABLE if kind.store and kind.format <= ver]
         need = _STEP_ARRAYS + (_EDIT_ARRAYS if ver >= 2 else ()) + tuple(name for kind in held for name in _arrays_of(kind))
         missing = [k for k in need if k not in g.files]

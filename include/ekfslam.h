@@ -502,6 +502,36 @@ typedef struct ekf_model_init {
 } ekf_model_init;
 int32_t ekf_append_model(ekf_handle *h, const ekf_model_init *obs, int64_t m, int64_t *first_idx /* may be NULL */);
 int32_t ekf_model_invert(int32_t model, const double xr[3], const double z[2], double t[2], double Gx[6], double Gz[4]);
+/* MAP JOINING: a LOCAL map joined into this one on the device.  `local` holds y = [q; m_1 .. m_M] with covariance PL: a filter of its own
+ * (any tile edge, any storage kind, same cfg.device) that was started at the pose r = x(0:2) of `h` -- typically ekf_set_x(0), ekf_set_P(0)
+ * at the moment `h` stops moving -- so y is expressed in the frame of r and is independent of P.  With theta = r(2) in degrees, k = 180/pi,
+ * Rot = Rot(theta) and w(v) = Rot v:
+ *     r'  = r (+) q      p' = p + w(q(0:1)), theta' = wrapTo360(theta + q(2)): ekf_motion_evaluate's EKF_MOTION_POSE_DELTA at (r, q),
+ *                        J1 = its F, J2 = its V = blockdiag(Rot, 1)
+ *     g_i = p + w(m_i)   ekf_model_invert's EKF_MODEL_RELATIVE_XY at (r, m_i), Gx_i = [1 0 -w_1(m_i)/k; 0 1 w_0(m_i)/k], Gz = Rot
+ * The old landmarks stay; local landmark i becomes landmark N + i (0-based; *first_idx = N) with signature s_local[i] + signature_offset, and
+ * P' = J blockdiag(P, PL) J', block by block (strip = P(1:3, landmarks)):
+ *     P'(1:3,1:3)     = J1 P(1:3,1:3) J1' + J2 PL_qq J2'           strip'(old c) = J1 strip(:, c)
+ *     strip'(new i)   = J1 (P(1:3,1:3) Gx_i') + J2 PL(q, m_i) Rot'
+ *     P'(new i, old c) = Gx_i strip(:, c)  (the OLD strip)         P'(new i, new a) = Gx_i (P(1:3,1:3) Gx_a') + Rot PL(m_i, m_a) Rot'
+ * and nothing of P(old, old) read or written.  Two launches, counted under EKF_KERNEL_APPEND: the small part and the strip (one lane per
+ * column), and the new tile rows (one lane per 2 x 2 block, the local tile store read once, the new rows written once).  M has no limit but
+ * the capacity; M = 0 is a pure pose composition -- bit for bit ekf_predict_model's POSE_DELTA step with u = q, M = PL_qq -- and N = 0 is
+ * allowed.  A local map with q = 0, PL_qq = 0, PL(q, .) = 0 and a block-diagonal PL_mm leaves bit for bit what ekf_append_model leaves for
+ * EKF_MODEL_RELATIVE_XY entries (z = m_i, R = PL(m_i, m_i)).  What makes it a join: the local map's internal geometry does not depend on
+ * where it is attached -- a RELATIVE_XY innovation of new landmark N + i on `h` reports the nu and S it reports for landmark i on `local`.
+ * A SYNCHRONISING call on BOTH handles, like ekf_constrain_landmarks: both are settled, recorded predicts carried out, pending pairs applied,
+ * an asynchronous pass retired (ekf_pending is 0 on both afterwards); `local`'s stream is drained before `h`'s stream reads its buffers and
+ * `h`'s stream is drained before the call returns, so ekf_destroy(local) or any edit of it right afterwards is safe.  Apart from that flush
+ * `local` is left bit for bit as it was.  The usual next steps are ekf_nearest_landmarks and ekf_merge_landmarks_batch, which fuse the
+ * landmarks both maps saw.
+ * Refused with nothing changed: h or local NULL, h == local, a non-finite signature_offset, either handle sharded (world > 1 or
+ * cfg.force_sharded), different cfg.device (EKF_ERR_INVALID_ARG); then, with both measure loops settled, N + M > cfg.capacity_landmarks
+ * of `h` (EKF_ERR_CAPACITY: all or nothing).  A step that fails on `local` (settling or flushing it) is reported on `h`, its message
+ * quoting `local`'s, which `local`'s own ekf_last_error holds as well.  The host's mirror of the new signatures is taken from `local`'s
+ * mirror (what ekf_set_s / the appends gave it), as ekf_remove_landmarks takes its own: a signature written to the device behind the
+ * library's back (ekf_diag_poke_device_signature) reaches the device copy of `h` but not its mirror. */
+int32_t ekf_join_map(ekf_handle *h, ekf_handle *local, double signature_offset, int64_t *first_idx /* may be NULL */);
 /* The step between the two: "WHICH landmark does this sighting belong to?", for a whole scan, under the conventions of ekf_observe_model.
  * ekf_associate keeps the reference's (signature-only by default, an unwrapped bearing, a range-scaled R) and cannot serve a filter
  * driven through the model calls.  For each of the m observations, d2(k, i) is, BIT FOR BIT, the d2 that ekf_model_innovation reports for

@@ -239,6 +239,16 @@ classdef EKF_SLAM < handle
             if nargin < 5 || isempty(signature), signature = numel(h.s) + (1:m)'; end
             idx = h.gateway('append_model', model, z, R, double(signature(:)));
         end
+        function idx = joinMap(h, local, signatureOffset)
+            % MAP JOINING: the map of `local` -- another EKF_SLAM / EKF_SLAM_UC object, started at this one's robot pose (x = 0, P = 0 at
+            % the moment this one stops moving) and independent of it -- is joined into this one on the GPU: the robot composes with the
+            % local robot, the local landmarks follow this map's in the global frame with signature s_local + signatureOffset (left out:
+            % 0), and the local map's own cross-covariances are kept.  Both objects are flushed; `local` is otherwise untouched and may
+            % be deleted at once.  idx: the new landmarks' numbers.  Follow it with fuseDuplicatesBatched(gate, R) to fuse the landmarks
+            % both maps saw.  Not a method of the reference.
+            if nargin < 3 || isempty(signatureOffset), signatureOffset = 0; end
+            idx = h.gateway('join_map', local.hnd, double(signatureOffset));
+        end
         function idx = addLandmarkRangeBearing(h, z, R, signature)
             % 'A landmark that is not in the map yet is seen at range z(1) and bearing z(2) (degrees, relative to the heading),
             % covariance R': it joins the map at the point that observation names.

@@ -27,7 +27,7 @@
  * (ekf_observe_model), the append through a model (ekf_append_model), the association of a scan under the models' conventions
  * (ekf_associate_model) and its one-to-one assignment (ekf_assign_model), the joint compatibility of a scan's pairings (ekf_joint_innovation) and their joint update
  * (ekf_observe_model_joint, relinearised: ekf_observe_model_joint_iterated), the relinearised model observation
- * (ekf_observe_model_iterated) and the motion steps under them (ekf_predict_model) are the ones this gateway can live without: bound weakly, so that the gateway still links against a libekfslam (or a stand-in) that
+ * (ekf_observe_model_iterated), the motion steps under them (ekf_predict_model) and the join of a local map (ekf_join_map) are the ones this gateway can live without: bound weakly, so that the gateway still links against a libekfslam (or a stand-in) that
  * predates them; their commands then raise a MATLAB error instead. */
 #if defined(__GNUC__)
 #pragma weak ekf_remove_landmarks
@@ -46,6 +46,7 @@
 #pragma weak ekf_observe_model_iterated
 #pragma weak ekf_observe_model_joint
 #pragma weak ekf_observe_model_joint_iterated
+#pragma weak ekf_join_map
 #define HAVE_REMOVE_LANDMARKS (ekf_remove_landmarks != 0)
 #define HAVE_CONSTRAIN_LANDMARKS (ekf_constrain_landmarks != 0)
 #define HAVE_MERGE_LANDMARKS (ekf_merge_landmarks != 0)
@@ -62,6 +63,7 @@
 #define HAVE_OBSERVE_MODEL_ITERATED (ekf_observe_model_iterated != 0)
 #define HAVE_OBSERVE_MODEL_JOINT (ekf_observe_model_joint != 0)
 #define HAVE_OBSERVE_MODEL_JOINT_ITERATED (ekf_observe_model_joint_iterated != 0)
+#define HAVE_JOIN_MAP (ekf_join_map != 0)
 #else
 #define HAVE_REMOVE_LANDMARKS 1
 #define HAVE_CONSTRAIN_LANDMARKS 1
@@ -79,6 +81,7 @@
 #define HAVE_OBSERVE_MODEL_ITERATED 1
 #define HAVE_OBSERVE_MODEL_JOINT 1
 #define HAVE_OBSERVE_MODEL_JOINT_ITERATED 1
+#define HAVE_JOIN_MAP 1
 #endif
 
 static void need(int nrhs, int want, const char *cmd) {
@@ -420,6 +423,24 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
         }
         int64_t first = 0;
         check(h, ekf_append_model(h, o, (int64_t)m, &first));
+        plhs[0] = mxCreateDoubleMatrix(m, 1, mxREAL);
+        for (mwSize b = 0; b < m; ++b) mxGetPr(plhs[0])[b] = (double)(first + (int64_t)b + 1);
+        return;
+    }
+    if (!strcmp(cmd, "join_map")) {               /* idx = (h, hlocal, signature_offset): the map of the handle hlocal joined into h on the device; idx M x 1,
+                                                     the 1-based numbers of the new landmarks (0 x 1 for a local map without landmarks) */
+        need(nrhs, 4, cmd);
+        if (!HAVE_JOIN_MAP) mexErrMsgIdAndTxt("ekfslam:usage", "join_map: this libekfslam has no ekf_join_map");
+        if (!prhs[2] || mxGetClassID(prhs[2]) != mxUINT64_CLASS || mxGetNumberOfElements(prhs[2]) != 1 || !mxGetData(prhs[2]))
+            mexErrMsgIdAndTxt("ekfslam:handle", "join_map: the third argument must be the uint64 handle of the local map");
+        ekf_handle *local = (ekf_handle *)(uintptr_t)(*(const uint64_t *)mxGetData(prhs[2]));
+        if (!local) mexErrMsgIdAndTxt("ekfslam:handle", "join_map: null local handle (already destroyed?)");
+        if (!prhs[3] || mxGetNumberOfElements(prhs[3]) != 1 || !mxGetPr(prhs[3]))
+            mexErrMsgIdAndTxt("ekfslam:usage", "join_map: signature_offset is one number");
+        int64_t first = 0, after = 0;
+        check(h, ekf_join_map(h, local, mxGetPr(prhs[3])[0], &first));
+        check(h, ekf_num_landmarks(h, &after));
+        const mwSize m = after > first ? (mwSize)(after - first) : 0;
         plhs[0] = mxCreateDoubleMatrix(m, 1, mxREAL);
         for (mwSize b = 0; b < m; ++b) mxGetPr(plhs[0])[b] = (double)(first + (int64_t)b + 1);
         return;
