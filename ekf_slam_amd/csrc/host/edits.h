@@ -7,6 +7,13 @@ int32_t edit_unsharded(ekf_handle *h, const std::string &who, const char *why) {
     return fail(h, EKF_ERR_INVALID_ARG, (who + "not built for sharded handles (world > 1): " + why).c_str());
 }
 
+// rung 1 of a call on TWO handles (join_map.h, extract_map.h), reported on `h`: `who_of` -- `which` names it -- runs no sharded code path in
+// either sense (`why`: what the call would need of a shard)
+int32_t pair_unsharded(ekf_handle *h, ekf_handle *who_of, const std::string &who, const char *which, const char *why) {
+    if (who_of->cfg.world == 1 && !who_of->sharded) return EKF_OK;
+    return fail(h, EKF_ERR_INVALID_ARG, (who + which + " is sharded (world > 1 or cfg.force_sharded): " + why).c_str());
+}
+
 // rung 2: no exchange pending, the device current, every queued row of the device loops settled (cfg.device_assoc == 4: N exact)
 int32_t edit_settled(ekf_handle *h, const std::string &who) {
     if (h->pending) return fail(h, EKF_ERR_STATE, (who + "a sharded correction is between begin and finish").c_str());

@@ -195,6 +195,9 @@ struct ekf_handle {
     double *d_s_tmp = nullptr;
     hipEvent_t ev_cmap = nullptr;
     bool cmap_busy = false;
+    // ekf_extract_map, on the DESTINATION handle: the list destination landmark -> source landmark (cap entries, allocated at the first
+    // extraction into this handle and kept; every extraction ends with a stream synchronisation, so the list is never busy)
+    int32_t *d_xidx = nullptr;
     // ekf_nearest_landmarks: the N (d2, partner) entries k_nearest writes and the pinned area they are read back through (cap entries
     // each, allocated at the first search and kept; every search ends with a stream synchronisation, so the area is never busy)
     NearestEntry *d_nearest = nullptr, *h_nearest = nullptr;

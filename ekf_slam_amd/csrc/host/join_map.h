@@ -3,14 +3,6 @@
 // handle's stream drained before the call returns -- so the caller may destroy or edit the local handle at once.  Unsharded only: the rows
 // kernel writes every tile of the new rows and reads every tile of the local store.
 #pragma once
-namespace {
-int32_t join_unsharded(ekf_handle *h, ekf_handle *who_of, const std::string &who, const char *which) {
-    if (who_of->cfg.world == 1 && !who_of->sharded) return EKF_OK;
-    return fail(h, EKF_ERR_INVALID_ARG, (who + which + " is sharded (world > 1 or cfg.force_sharded): the join writes and reads whole tile rows, "
-                "and a shard holds only its own tiles").c_str());
-}
-}  // namespace
-
 extern "C" {
 int32_t ekf_join_map(ekf_handle *h, ekf_handle *local, double signature_offset, int64_t *first_idx) {
     if (!h) return EKF_ERR_INVALID_ARG;
@@ -18,8 +10,9 @@ int32_t ekf_join_map(ekf_handle *h, ekf_handle *local, double signature_offset, 
     REQUIRE(h, local != nullptr, EKF_ERR_INVALID_ARG, (who + "null local handle").c_str());
     REQUIRE(h, local != h, EKF_ERR_INVALID_ARG, (who + "a map cannot be joined into itself").c_str());
     REQUIRE(h, std::isfinite(signature_offset), EKF_ERR_INVALID_ARG, (who + "signature_offset is not finite").c_str());
-    TRY(join_unsharded(h, h, who, "the handle"));
-    TRY(join_unsharded(h, local, who, "the local handle"));
+    const char *why = "the join writes and reads whole tile rows, and a shard holds only its own tiles";
+    TRY(pair_unsharded(h, h, who, "the handle", why));
+    TRY(pair_unsharded(h, local, who, "the local handle", why));
     REQUIRE(h, h->cfg.device == local->cfg.device, EKF_ERR_INVALID_ARG, (who + "both handles must live on the same device").c_str());
     // both settled (N and M exact), then the capacity: all or nothing, before anything is flushed
     TRY(edit_settled(h, who));

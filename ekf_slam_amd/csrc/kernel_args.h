@@ -119,6 +119,17 @@ struct JoinMapArgs {
     int32_t lcur;             // the local handle's live buffer: read only
 };
 
+// k_extract_state / k_extract_rows (extract_map.h): m landmarks of a flushed SOURCE handle, named by a device list idx (distinct, any order),
+// taken out into another handle on the same device, whose whole state is replaced -- destination landmark k is source landmark idx[k].
+// The source's DevState travels beside the destination's; the source is read only.
+struct ExtractMapArgs {
+    int64_t m;                // landmarks taken out
+    int64_t cols;             // padded(2 m) of the destination's tile map: the columns k_extract_state writes (zero from 2 m on)
+    int32_t frame;            // 0: EKF_FRAME_MAP, the marginal as it is; 1: EKF_FRAME_ROBOT, relative to the robot
+    int32_t scur;             // the source's live buffer: read only
+    int32_t dcur;             // the destination buffer that is written whole (its diagonal copies: diag[dcur of its DevState])
+};
+
 // k_predict_model (predict_model.h): a chain of m <= kPredictModelMax motion steps through the models of ekfm::motion_eval, carried out in
 // order by ONE launch that reads buffer cur and writes buffer cur ^ 1, as k_predict.  No tile is read: the storage type does not matter.
 // The steps travel in the argument block, M as its six unique entries -- 80 bytes a step, 2.5 KiB at 32 (nine entries a step would not fit

@@ -39,6 +39,14 @@ hipError_t launch_append_model(const DevState &st, const AppendModelArgs &a, int
 hipError_t launch_join_state(const DevState &st, const DevState &lo, const JoinMapArgs &a, hipStream_t s);
 hipError_t launch_join_rows(const DevState &st, const DevState &lo, const JoinMapArgs &a, int storage, int local_storage, hipStream_t s);
 
+// k_extract_state / k_extract_rows (extract_map.h): the a.m landmarks idx[0 .. m) (device list, distinct, each inside the map of `src`) of the
+// flushed source state `src` (same device, read only) into `dst`, every value of which is replaced.  launch_extract_state: x, Prr, the strip
+// (buffer a.dcur, whole), s and the live diagonal copies.  launch_extract_rows (a.m >= 1, both stores unsharded): tile rows
+// 0 .. padded(2 m) - 1 of dst, diagonal tiles whole, zero beyond 2 m.  Neither reads what the other writes.
+hipError_t launch_extract_state(const DevState &dst, const DevState &src, const ExtractMapArgs &a, const int32_t *idx, hipStream_t s);
+hipError_t launch_extract_rows(const DevState &dst, const DevState &src, const ExtractMapArgs &a, const int32_t *idx, int storage, int src_storage,
+                               hipStream_t s);
+
 // fused_predict != nullptr folds predict(u) into the correction (one launch instead of two, identical arithmetic)
 // fuse_downdate: the kernel also applies its pair to the landmark block (small maps: a.n_mm <= gather_fuse_max_rows(), one
 // workgroup); the pair is then NOT written to the pending ring and no downdate launch must follow

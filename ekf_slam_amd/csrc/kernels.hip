@@ -38,6 +38,7 @@ namespace {
 #include "append.h"           // k_append
 #include "append_model.h"     // k_append_model: a scan's landmarks from range-bearing / relative-position fixes, one launch
 #include "join_map.h"         // k_join_state, k_join_rows: a local map joined into the map (a composition of the two above)
+#include "extract_map.h"      // k_extract_state, k_extract_rows: part of a map taken out into another handle
 #include "solve_small.h"      // the 5x5 solve, entry by entry
 #include "rowpanel.h"         // PanelView, k_rowpanel, k_rowpanel_next, k_rowpanel_base
 #include "pair_column.h"      // what every producer of a pair (K, G) does per column: the pair's slot, x', strip', the diagonal blocks

@@ -1,4 +1,4 @@
-// Fragment of kernels.hip, the launchers of the map edits: landmark removal (compact.h), a constraint between two landmarks and its
+// Fragment of kernels.hip, the launchers of the map edits: landmark removal (compact.h), part of a map taken out into another handle (extract_map.h), a constraint between two landmarks and its
 // chained form (constrain.h), a linear observation (linear_obs.h) and one through a model (model_obs.h), the joint innovation of a scan's pairings (joint.h) and their joint update (joint_update.h, joint_iter.h), the fused pass of a batch of merges (merge_pass.h), the candidate search (nearest.h).
 #pragma once
 
@@ -30,6 +30,28 @@ hipError_t launch_compact_state(const DevState &st, int cur, const int32_t *src_
     const int64_t grid = cdiv(N_old > 0 ? N_old : 1, kBlock);
     hipLaunchKernelGGL(k_compact_state, dim3((unsigned)grid), dim3(kBlock), 0, s, st, cur, src_of, N_old, s_out);
     return hipGetLastError();
+}
+
+hipError_t launch_extract_state(const DevState &dst, const DevState &src, const ExtractMapArgs &a, const int32_t *idx, hipStream_t s) {
+    // the columns written inside the destination's strip (whole tiles: zero from 2 m on), the list there where a landmark is read
+    if (a.m < 0 || a.cols != dst.tm.padded(2 * a.m) || a.cols > dst.ldm || (a.m > 0 && !idx) || (a.frame != 0 && a.frame != 1)) return hipErrorInvalidValue;
+    const int64_t grid = cdiv(a.cols > 0 ? a.cols : 1, kBlock);
+    hipLaunchKernelGGL(k_extract_state, dim3((unsigned)grid), dim3(kBlock), 0, s, dst, src, a, idx);
+    return hipGetLastError();
+}
+
+hipError_t launch_extract_rows(const DevState &dst, const DevState &src, const ExtractMapArgs &a, const int32_t *idx, int storage, int src_storage,
+                               hipStream_t s) {
+    if (a.m < 1 || a.cols != dst.tm.padded(2 * a.m) || a.cols > dst.ldm || !idx || (a.frame != 0 && a.frame != 1) || dst.tm.world != 1 ||
+        src.tm.world != 1 || dst.tiles == src.tiles)
+        return hipErrorInvalidValue;
+    const int64_t rows = a.cols / 2;                        // destination landmarks, the zero ones of the last tile row included
+    const int64_t per_row = cdiv(rows, kBlock);             // workgroups per destination landmark: 256 column landmarks each
+    const int64_t grid = rows * per_row;
+    if (grid > 0x7fffffffll) return hipErrorInvalidValue;
+    return with_storage(storage, [&](auto td) { with_storage(src_storage, [&](auto tsrc) {
+        hipLaunchKernelGGL((k_extract_rows<decltype(td), decltype(tsrc)>), dim3((unsigned)grid), dim3(kBlock), 0, s, dst, src, a, idx, (int32_t)per_row);
+    }); });
 }
 
 hipError_t launch_merge_pass(const DevState &st, void *dst, const int2 *work, int64_t ntiles, const int32_t *src_of, int npairs,

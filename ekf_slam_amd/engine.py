@@ -478,6 +478,43 @@ class Engine:
         self._check(self.lib.ekf_join_map(self.h, local_engine.h, offset, ctypes.byref(first)))
         return int(first.value)
 
+    # ---- part of this map taken out into another engine (include/ekfslam.h: ekf_extract_map) ----
+    def extract_map(self, indices, frame="map", into=None, **engine_kw):
+        """Take the robot and the landmarks `indices` (0-based, distinct, any order) out into another engine on the same device, whose
+        whole state is replaced: destination landmark k is landmark indices[k].  frame="map": the marginal as it is, every value
+        keeping its bits; frame="robot": the landmarks relative to the robot (RELATIVE_XY), the robot's own uncertainty folded in, the
+        destination's robot at zero with P = 0 -- the shape join_map expects of a local map.  `into`: an existing Engine of any tile
+        edge and storage kind with capacity >= len(indices); None: one is made with capacity max(m, 1) and this engine's mode, device
+        and storage kind unless `engine_kw` says otherwise.  A synchronising call on both engines; this one is only flushed.  Returns
+        the destination Engine (ekf_extract_map)."""
+        return self._extract_map(marshal.extract_args(indices, frame), into, engine_kw)
+
+    def _storage_name(self):
+        if self.cfg.storage == L.EKF_STORE_F64:
+            return "f64"
+        return {L.EKF_ARITH_F32: "f32_mixed", L.EKF_ARITH_SPLIT3: "f32_split"}.get(self.cfg.pass_arith, "f32")
+
+    def _extract_map(self, args, into=None, engine_kw=None):
+        arr, m, frame = args
+        engine_kw = dict(engine_kw or {})
+        made = into is None
+        if made:
+            kw = dict(mode="known" if self.cfg.mode == L.EKF_MODE_KNOWN else "uc", capacity=max(m, 1), storage=self._storage_name(),
+                      device=self.cfg.device)
+            kw.update(engine_kw)
+            into = Engine(**kw)
+        elif engine_kw:
+            raise TypeError("extract_map: engine keywords make a new destination; `into` is an existing one")
+        elif not isinstance(into, Engine):
+            raise TypeError("extract_map: the destination is an Engine")
+        try:
+            self._check(self.lib.ekf_extract_map(self.h, arr, m, frame, into.h))
+        except Exception:
+            if made:
+                into.close()
+            raise
+        return into
+
     @staticmethod
     def model_invert(model, xr, z, lib=None):
         """(t, Gx, Gz): the landmark that z observes from the robot state xr = (x, y, theta in degrees) through EKF_MODEL_RANGE_BEARING

@@ -154,6 +154,16 @@ def join_offset(signature_offset, who="join_map"):
     return ctypes.c_double(v)
 
 
+def extract_args(indices, frame, who="extract_map"):
+    """(int64[], m, frame) of extract_map as the ABI takes them: the 0-based landmarks in the caller's order and EKF_FRAME_MAP /
+    EKF_FRAME_ROBOT for frame = "map" / "robot"; anything else is refused here."""
+    frames = {"map": L.EKF_FRAME_MAP, "robot": L.EKF_FRAME_ROBOT}
+    if not isinstance(frame, str) or frame not in frames:
+        raise ValueError("%s: frame is 'map' or 'robot'" % who)
+    arr, m = index_array(indices)
+    return arr, m, ctypes.c_int32(frames[frame])
+
+
 def model_inits(entries, who="append_model"):
     """(ekf_model_init[], m) of a scan of new landmarks [(model, z, R, signature), ...]."""
     entries = list(entries)

@@ -150,6 +150,11 @@ class ShardGroup:
         to the first shard so that the refusal is the library's (EKF_ERR_INVALID_ARG, nothing changed)."""
         return self.shards[0].join_map(local_engine, signature_offset)
 
+    def extract_map(self, indices, frame="map", into=None, **engine_kw):
+        """Not built for a shard group: the extraction reads tiles anywhere in the store and a shard holds only its own.  The call goes
+        to the first shard so that the refusal is the library's (EKF_ERR_INVALID_ARG, nothing changed)."""
+        return self.shards[0].extract_map(indices, frame, into, **engine_kw)
+
     def correct(self, z, R, idx0):
         for e in self.shards:
             e.correct_begin(z, R, idx0)

@@ -330,6 +330,39 @@ class _EkfBase:
         fused = self.fuse_duplicates_batched(gate, R) if gate is not None else []
         return new, fused
 
+    @classmethod
+    def _around(cls, e):
+        """A filter of this class around an engine that exists already (extract_map's destination)."""
+        f = cls.__new__(cls)
+        f._e, f.landmark_list, f.observed, f.log = e, None, None, None
+        if cls._mode == "uc":
+            f.correspondence = Correspondence(e.cfg.s_cost, e.cfg.s_thresh, 'EKF_SLAM_UC')
+        return f
+
+    def extract_map(self, idx, frame="map", **engine_kw):
+        """The robot and landmarks idx (1-based, a number or any iterable, distinct, any order) taken out into a NEW filter of this class:
+        its landmark k is landmark idx[k] of this one.  frame="map": their joint Gaussian as it is, bit for bit; frame="robot": the
+        landmarks relative to the robot with the robot's own uncertainty folded in, the new filter's robot at zero with P = 0 -- a
+        planner's small relative covariance, and what join_map expects of a local map.  O(m^2) on the device whatever the size of this
+        map; this filter is only flushed, so nothing is logged.  `engine_kw` go to the new engine (tile, storage, capacity, ...; by
+        default capacity max(m, 1) and this engine's storage kind) (ekf_extract_map).  The reference has no such method."""
+        numbers = self._landmark_numbers("extract_map", *np.asarray(idx).reshape(-1))
+        args = marshal.extract_args([i - 1 for i in numbers], frame)             # the one marshal: 0-based from here on
+        return type(self)._around(self._e._extract_map(args, None, engine_kw))
+
+    def landmarks_near_robot(self, radius):
+        """The 1-based numbers of the landmarks within `radius` of the robot, ascending, from one read of x."""
+        x = self._e.get_x()
+        d = x[3:].reshape(-1, 2) - x[0:2]
+        return [int(k) + 1 for k in np.nonzero(np.hypot(d[:, 0], d[:, 1]) <= float(radius))[0]]
+
+    def split_submap(self, idx, frame="map", **engine_kw):
+        """The archive-before-remove POLICY: extract_map(idx, frame), then remove_landmarks(idx) on this filter.  Returns the new filter
+        that holds what was taken out.  The extraction changes nothing here, so the log holds the removal alone."""
+        sub = self.extract_map(idx, frame, **engine_kw)
+        self.remove_landmarks(idx)
+        return sub
+
     def observe_linear(self, z, R, Hr=None, landmarks=(), Hl=(), gate=float("inf"), wrap=(0, 0), rows=2, wait=False):
         """'H x was observed as z with noise covariance R' for a constant H: the 2 x 3 block Hr on the robot state (x, y, theta in
         degrees) plus one 2 x 2 block Hl[b] on each of up to two landmarks (1-based numbers) -- the exact Kalman update, as an

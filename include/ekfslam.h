@@ -532,6 +532,37 @@ int32_t ekf_model_invert(int32_t model, const double xr[3], const double z[2], d
  * mirror (what ekf_set_s / the appends gave it), as ekf_remove_landmarks takes its own: a signature written to the device behind the
  * library's back (ekf_diag_poke_device_signature) reaches the device copy of `h` but not its mirror. */
 int32_t ekf_join_map(ekf_handle *h, ekf_handle *local, double signature_offset, int64_t *first_idx /* may be NULL */);
+/* MAP EXTRACTION, the other direction: part of this map taken out into a handle of its own, on the device.  idx[0 .. m-1] are 0-based
+ * landmarks of `h`, distinct, in ANY order; destination landmark k is source landmark idx[k] and keeps its signature.  `dst` is an existing
+ * handle on the same cfg.device with any tile edge and storage kind and capacity_landmarks >= m; its WHOLE state (x, s, P) is replaced --
+ * what it held, pending pairs and a recorded predict included, is dropped, as by ekf_load_lowrank_state.  Afterwards ekf_num_landmarks(dst)
+ * is m and ekf_pending(dst) is 0.  Marginalisation in covariance form is a selection, so the call costs O(m^2) bytes whatever N is.
+ * With strip = P(1:3, landmarks), theta = x(2) in degrees, k = 180/pi, c / s the cosine / sine of theta:
+ *   EKF_FRAME_MAP    the joint Gaussian of the robot and the chosen landmarks as it is: x' = [r; l_idx[0]; ..], P' = P(sel, sel) with
+ *                    sel = rows (robot, l_idx[0], .., l_idx[m-1]).  Nothing is computed: every value keeps its bits between stores of
+ *                    one kind, a float store widens exactly into an F64 store, an F64 store is rounded once per tile entry into a float
+ *                    store (x, P(1:3,1:3), the strip and the landmarks' own 2 x 2 blocks are F64 on every handle and stay exact).
+ *   EKF_FRAME_ROBOT  the same landmarks relative to the robot, the robot's own uncertainty folded in to first order: the robot of dst is
+ *                    (0, 0, 0) with P'(1:3, :) = 0; landmark k is m_k = (c dx + s dy, c dy - s dx), d = l_idx[k] - r(0:1): bit for bit
+ *                    ekf_model_evaluate's EKF_MODEL_RELATIVE_XY hx at (r, l_idx[k]); and with that model's blocks
+ *                    Hr_k = [-c -s m_k(1)/k; s -c -m_k(0)/k] on the robot and Hl = [c s; -s c] on the landmark
+ *                      P'(k, a) = Hr_k P(1:3,1:3) Hr_a' + Hr_k strip(:, idx[a]) Hl' + Hl strip(:, idx[k])' Hr_a' + Hl P(l_idx[k], l_idx[a]) Hl'
+ *                    (the four terms formed in this order and added left to right).  That is exactly the shape ekf_join_map expects of
+ *                    a `local`: q = 0, PL_qq = 0, PL(q, .) = 0.  A landmark exactly on the robot is regular here (m_k = 0, a zero
+ *                    heading column in Hr_k) and is not refused.
+ * A landmark's own 2 x 2 block is taken from the live F64 diagonal copy in either frame.  m == 0 is allowed: a robot-only dst (in the
+ * robot frame the zero pose with P = 0).  Two launches on dst's stream, counted on `h` under EKF_KERNEL_COMPACT; the index list is uploaded
+ * once into a device buffer dst keeps (ekf_device_bytes of dst reports it).
+ * A SYNCHRONISING call on BOTH handles, like ekf_join_map: `h` is settled and flushed as for every reader of P (a recorded predict carried
+ * out, pending pairs applied, an asynchronous pass retired) and otherwise keeps every bit; `h`'s stream is drained before dst's stream
+ * reads its buffers, and dst's stream is drained before the call returns.
+ * Refused with nothing changed on either handle: h or dst NULL, h == dst, idx NULL with m > 0, m < 0, a landmark named twice, a frame that
+ * is neither constant, either handle sharded (world > 1 or cfg.force_sharded), different cfg.device (EKF_ERR_INVALID_ARG); then, with both
+ * measure loops settled, an index outside [0, N) (EKF_ERR_INDEX) and m > capacity_landmarks of dst (EKF_ERR_CAPACITY).  The message is in
+ * ekf_last_error(h); a step that fails on dst is reported on `h`, quoting dst's own message.  The host's mirror of dst's signatures is taken
+ * from `h`'s mirror, as ekf_join_map takes it. */
+enum { EKF_FRAME_MAP = 0, EKF_FRAME_ROBOT = 1 };
+int32_t ekf_extract_map(ekf_handle *h, const int64_t *idx, int64_t m, int32_t frame, ekf_handle *dst);
 /* The step between the two: "WHICH landmark does this sighting belong to?", for a whole scan, under the conventions of ekf_observe_model.
  * ekf_associate keeps the reference's (signature-only by default, an unwrapped bearing, a range-scaled R) and cannot serve a filter
  * driven through the model calls.  For each of the m observations, d2(k, i) is, BIT FOR BIT, the d2 that ekf_model_innovation reports for

@@ -249,6 +249,21 @@ classdef EKF_SLAM < handle
             if nargin < 3 || isempty(signatureOffset), signatureOffset = 0; end
             idx = h.gateway('join_map', local.hnd, double(signatureOffset));
         end
+        function extractMap(h, idx, frame, dst)
+            % MAP EXTRACTION: the robot and landmarks idx (1-based, distinct, any order, any shape) of this map are taken out into `dst`
+            % -- another EKF_SLAM / EKF_SLAM_UC object, any tile edge and storage kind, capacity >= numel(idx) -- whose whole state is
+            % replaced: its landmark k is landmark idx(k) of this one.  frame 'map' (empty: 'map'): their joint Gaussian as it is, bit
+            % for bit; frame 'robot': the landmarks relative to the robot with the robot's own uncertainty folded in, dst's robot at zero
+            % with P = 0 -- what joinMap expects of a local map.  On the GPU, O(numel(idx)^2) whatever the size of this map; this object
+            % is only flushed.  Follow it with removeLandmarks(idx) to archive a region before dropping it.  Not a method of the reference.
+            if isempty(frame), frame = 'map'; end
+            switch frame
+                case 'map', f = 0;
+                case 'robot', f = 1;
+                otherwise, error('ekfslam:usage', 'extractMap: frame is ''map'' or ''robot''');
+            end
+            h.gateway('extract_map', double(idx(:)), f, dst.hnd);
+        end
         function idx = addLandmarkRangeBearing(h, z, R, signature)
             % 'A landmark that is not in the map yet is seen at range z(1) and bearing z(2) (degrees, relative to the heading),
             % covariance R': it joins the map at the point that observation names.

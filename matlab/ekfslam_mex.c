@@ -27,7 +27,7 @@
  * (ekf_observe_model), the append through a model (ekf_append_model), the association of a scan under the models' conventions
  * (ekf_associate_model) and its one-to-one assignment (ekf_assign_model), the joint compatibility of a scan's pairings (ekf_joint_innovation) and their joint update
  * (ekf_observe_model_joint, relinearised: ekf_observe_model_joint_iterated), the relinearised model observation
- * (ekf_observe_model_iterated), the motion steps under them (ekf_predict_model) and the join of a local map (ekf_join_map) are the ones this gateway can live without: bound weakly, so that the gateway still links against a libekfslam (or a stand-in) that
+ * (ekf_observe_model_iterated), the motion steps under them (ekf_predict_model), the join of a local map (ekf_join_map) and the extraction of part of the map (ekf_extract_map) are the ones this gateway can live without: bound weakly, so that the gateway still links against a libekfslam (or a stand-in) that
  * predates them; their commands then raise a MATLAB error instead. */
 #if defined(__GNUC__)
 #pragma weak ekf_remove_landmarks
@@ -47,6 +47,7 @@
 #pragma weak ekf_observe_model_joint
 #pragma weak ekf_observe_model_joint_iterated
 #pragma weak ekf_join_map
+#pragma weak ekf_extract_map
 #define HAVE_REMOVE_LANDMARKS (ekf_remove_landmarks != 0)
 #define HAVE_CONSTRAIN_LANDMARKS (ekf_constrain_landmarks != 0)
 #define HAVE_MERGE_LANDMARKS (ekf_merge_landmarks != 0)
@@ -64,6 +65,7 @@
 #define HAVE_OBSERVE_MODEL_JOINT (ekf_observe_model_joint != 0)
 #define HAVE_OBSERVE_MODEL_JOINT_ITERATED (ekf_observe_model_joint_iterated != 0)
 #define HAVE_JOIN_MAP (ekf_join_map != 0)
+#define HAVE_EXTRACT_MAP (ekf_extract_map != 0)
 #else
 #define HAVE_REMOVE_LANDMARKS 1
 #define HAVE_CONSTRAIN_LANDMARKS 1
@@ -82,6 +84,7 @@
 #define HAVE_OBSERVE_MODEL_JOINT 1
 #define HAVE_OBSERVE_MODEL_JOINT_ITERATED 1
 #define HAVE_JOIN_MAP 1
+#define HAVE_EXTRACT_MAP 1
 #endif
 
 static void need(int nrhs, int want, const char *cmd) {
@@ -443,6 +446,27 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
         const mwSize m = after > first ? (mwSize)(after - first) : 0;
         plhs[0] = mxCreateDoubleMatrix(m, 1, mxREAL);
         for (mwSize b = 0; b < m; ++b) mxGetPr(plhs[0])[b] = (double)(first + (int64_t)b + 1);
+        return;
+    }
+    if (!strcmp(cmd, "extract_map")) {            /* (h, idx, frame, hdst): landmarks idx (1-based, distinct, any order, any shape) and the robot taken out into
+                                                     the handle hdst, whose whole state is replaced; frame 0: the map frame, 1: the robot frame; no output */
+        need(nrhs, 5, cmd);
+        if (!HAVE_EXTRACT_MAP) mexErrMsgIdAndTxt("ekfslam:usage", "extract_map: this libekfslam has no ekf_extract_map");
+        if (!prhs[4] || mxGetClassID(prhs[4]) != mxUINT64_CLASS || mxGetNumberOfElements(prhs[4]) != 1 || !mxGetData(prhs[4]))
+            mexErrMsgIdAndTxt("ekfslam:handle", "extract_map: the fifth argument must be the uint64 handle of the destination");
+        ekf_handle *dst = (ekf_handle *)(uintptr_t)(*(const uint64_t *)mxGetData(prhs[4]));
+        if (!dst) mexErrMsgIdAndTxt("ekfslam:handle", "extract_map: null destination handle (already destroyed?)");
+        if (!prhs[3] || mxGetNumberOfElements(prhs[3]) != 1 || !mxGetPr(prhs[3]) || (mxGetPr(prhs[3])[0] != 0.0 && mxGetPr(prhs[3])[0] != 1.0))
+            mexErrMsgIdAndTxt("ekfslam:usage", "extract_map: frame is 0 (map) or 1 (robot)");
+        const int32_t frame = (int32_t)mxGetPr(prhs[3])[0];
+        const mwSize m = prhs[2] ? mxGetNumberOfElements(prhs[2]) : 0;
+        if (m && !mxGetPr(prhs[2])) mexErrMsgIdAndTxt("ekfslam:usage", "extract_map: idx holds landmark numbers");
+        int64_t *idx0 = (int64_t *)malloc((m ? m : 1) * sizeof(int64_t));       /* freed before any MATLAB error can unwind */
+        if (!idx0) mexErrMsgIdAndTxt("ekfslam:usage", "extract_map: out of memory");
+        for (mwSize i = 0; i < m; ++i) idx0[i] = (int64_t)mxGetPr(prhs[2])[i] - 1;
+        const int32_t rc = ekf_extract_map(h, idx0, (int64_t)m, frame, dst);
+        free(idx0);
+        check(h, rc);
         return;
     }
     if (!strcmp(cmd, "associate_model")) {        /* [match, d2] = (h, model m x 1 (1..4), z m x 2, R 2 x 2 x m, gate m x 1): which landmark each sighting of a
