@@ -16,7 +16,7 @@ EKF_ERR_INDEX, EKF_ERR_LOOKUP, EKF_ERR_STATE, EKF_ERR_COMM = 5, 6, 7, 8
 EKF_MODE_KNOWN, EKF_MODE_UC = 0, 1
 EKF_COMM_ID_BYTES = 128
 EKF_MERGE_BATCH_MAX = 32
-EKF_FRAME_MAP, EKF_FRAME_ROBOT = 0, 1                  # ekf_extract_map: the marginal as it is / relative to the robot
+EKF_FRAME_MAP, EKF_FRAME_ROBOT = 0, 1                  # ekf_extract_map, ekf_transform_map: the map's own frame / the robot's
 EKF_STORE_F64, EKF_STORE_F32 = 0, 1
 EKF_ARITH_F64, EKF_ARITH_F32, EKF_ARITH_SPLIT3 = 0, 1, 2
 (EKF_KERNEL_DOWNDATE, EKF_KERNEL_GATHER, EKF_KERNEL_PREDICT, EKF_KERNEL_ASSOCIATE, EKF_KERNEL_APPEND,
@@ -187,6 +187,7 @@ SIGNATURES = {
     "ekf_model_invert": (_i32, [_i32, _dp, _dp, _dp, _dp, _dp]),
     "ekf_join_map": (_i32, [_vp, _vp, _d, ctypes.POINTER(_i64)]),
     "ekf_extract_map": (_i32, [_vp, ctypes.POINTER(_i64), _i64, _i32, _vp]),
+    "ekf_transform_map": (_i32, [_vp, _i32, _dp, _dp]),
     "ekf_associate_model": (_i32, [_vp, ctypes.POINTER(EkfModelObs), _i64, ctypes.POINTER(EkfModelMatch), _dp]),
     "ekf_assign_model": (_i32, [_vp, ctypes.POINTER(EkfModelObs), _i64, ctypes.POINTER(EkfModelAssigned), ctypes.POINTER(EkfModelMatch),
                                 ctypes.POINTER(_i64), _dp, _dp]),

@@ -130,6 +130,18 @@ struct ExtractMapArgs {
     int32_t dcur;             // the destination buffer that is written whole (its diagonal copies: diag[dcur of its DevState])
 };
 
+// k_transform_state / k_transform_tiles (transform_map.h): the WHOLE map of a flushed handle moved into another frame, in place -- by the
+// rigid transform t = (tx, ty, phi) whose covariance is Sigma (form 0: Sigma = 0, the rotation alone; form 1: the Sigma terms added), or
+// into the frame of the robot's own pose (form 2: t and Sigma are not read).  N and s stay.
+struct TransformMapArgs {
+    int64_t N;                // landmarks
+    int64_t cols;             // padded(2 N): the columns k_transform_state writes (zero from 2 N on)
+    int32_t form;             // 0: rigid, exact; 1: rigid, uncertain; 2: robot frame
+    int32_t cur;              // the live buffer: read; k_transform_state writes cur ^ 1 whole (the diagonal copies: dcur -> dcur ^ 1)
+    double t[3];              // the transform, phi in degrees
+    double Sigma[9];          // its covariance, row-major (symmetric)
+};
+
 // k_predict_model (predict_model.h): a chain of m <= kPredictModelMax motion steps through the models of ekfm::motion_eval, carried out in
 // order by ONE launch that reads buffer cur and writes buffer cur ^ 1, as k_predict.  No tile is read: the storage type does not matter.
 // The steps travel in the argument block, M as its six unique entries -- 80 bytes a step, 2.5 KiB at 32 (nine entries a step would not fit

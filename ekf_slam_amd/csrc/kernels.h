@@ -47,6 +47,13 @@ hipError_t launch_extract_state(const DevState &dst, const DevState &src, const 
 hipError_t launch_extract_rows(const DevState &dst, const DevState &src, const ExtractMapArgs &a, const int32_t *idx, int storage, int src_storage,
                                hipStream_t s);
 
+// k_transform_state / k_transform_tiles (transform_map.h): the whole map of the flushed state `st` moved into another frame.
+// launch_transform_state: x, Prr and the strip from buffer a.cur into a complete buffer a.cur ^ 1, the live diagonal copies from st.dcur
+// into st.dcur ^ 1; the caller flips both.  launch_transform_tiles (unsharded): the `ntiles` tiles of `work` -- the list of the active tile
+// rows, padded(2 N) / T of them -- IN PLACE in st.tiles, from buffer a.cur / st.dcur.  Neither reads what the other writes.
+hipError_t launch_transform_state(const DevState &st, const TransformMapArgs &a, hipStream_t s);
+hipError_t launch_transform_tiles(const DevState &st, const TransformMapArgs &a, const int2 *work, int64_t ntiles, int storage, hipStream_t s);
+
 // fused_predict != nullptr folds predict(u) into the correction (one launch instead of two, identical arithmetic)
 // fuse_downdate: the kernel also applies its pair to the landmark block (small maps: a.n_mm <= gather_fuse_max_rows(), one
 // workgroup); the pair is then NOT written to the pending ring and no downdate launch must follow

@@ -47,6 +47,7 @@ namespace {
 #include "associate.h"        // k_associate, k_assoc_merge
 #include "state_io.h"         // dense <-> tiled, block reads, low-rank load, digest
 #include "compact.h"          // landmark removal: k_compact_tiles, k_compact_state
+#include "transform_map.h"    // k_transform_state, k_transform_tiles: the whole map moved into another frame, in place (extract_map.h's and join_map.h's blocks, downdate.h's Lane16)
 #include "constrain.h"        // a constraint between two landmarks: k_constrain_probe, k_gather_constrain
 #include "linear_obs.h"       // a linear observation as an update-step: k_gather_linear, k_linear_probe
 #include "model_obs.h"        // ... through a range / bearing / relative-position model evaluated at the live x: k_gather_model, k_model_probe

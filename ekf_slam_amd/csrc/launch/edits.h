@@ -54,6 +54,41 @@ hipError_t launch_extract_rows(const DevState &dst, const DevState &src, const E
     }); });
 }
 
+namespace {
+bool transform_args_ok(const DevState &st, const TransformMapArgs &a) {
+    return a.N >= 0 && a.cols == st.tm.padded(2 * a.N) && a.cols <= st.ldm && a.form >= 0 && a.form <= 2 && (a.cur == 0 || a.cur == 1);
+}
+}  // namespace
+
+hipError_t launch_transform_state(const DevState &st, const TransformMapArgs &a, hipStream_t s) {
+    if (!transform_args_ok(st, a)) return hipErrorInvalidValue;
+    const int64_t grid = cdiv(a.cols > 0 ? a.cols : 1, kBlock);
+    if (a.form == 0) hipLaunchKernelGGL(k_transform_state<0>, dim3((unsigned)grid), dim3(kBlock), 0, s, st, a);
+    else if (a.form == 1) hipLaunchKernelGGL(k_transform_state<1>, dim3((unsigned)grid), dim3(kBlock), 0, s, st, a);
+    else hipLaunchKernelGGL(k_transform_state<2>, dim3((unsigned)grid), dim3(kBlock), 0, s, st, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_transform_tiles(const DevState &st, const TransformMapArgs &a, const int2 *work, int64_t ntiles, int storage, hipStream_t s) {
+    if (ntiles <= 0 || a.N <= 0) return hipSuccess;
+    // the list is that of the active tile rows (every tile it names lies inside the store), every tile held here; a tile row holds whole
+    // 16-byte pieces and a workgroup whole tile rows of them
+    const int pieces_per_row = st.tm.T / (storage == 0 ? 2 : 4);
+    if (!transform_args_ok(st, a) || !work || st.tm.world != 1 || ntiles != st.tm.row_base(a.cols >> st.tm.shift) || pieces_per_row < 1 ||
+        kBlock % pieces_per_row != 0)
+        return hipErrorInvalidValue;
+    const int64_t units = (int64_t)(st.tm.T / 2) * pieces_per_row;
+    const int items = (int)cdiv(units, (int64_t)kBlock * kTransformUnits);
+    const int64_t grid = ntiles * items;
+    if (grid > 0x7fffffffll) return hipErrorInvalidValue;
+    return with_storage(storage, [&](auto ts) {
+        using TS = decltype(ts);
+        if (a.form == 0) hipLaunchKernelGGL((k_transform_tiles<TS, 0>), dim3((unsigned)grid), dim3(kBlock), 0, s, st, a, work, items);
+        else if (a.form == 1) hipLaunchKernelGGL((k_transform_tiles<TS, 1>), dim3((unsigned)grid), dim3(kBlock), 0, s, st, a, work, items);
+        else hipLaunchKernelGGL((k_transform_tiles<TS, 2>), dim3((unsigned)grid), dim3(kBlock), 0, s, st, a, work, items);
+    });
+}
+
 hipError_t launch_merge_pass(const DevState &st, void *dst, const int2 *work, int64_t ntiles, const int32_t *src_of, int npairs,
                              int storage, hipStream_t s, char *kname) {
     if (ntiles <= 0) return hipSuccess;

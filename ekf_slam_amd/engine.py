@@ -515,6 +515,19 @@ class Engine:
             raise
         return into
 
+    # ---- the whole map moved into another frame, in place (include/ekfslam.h: ekf_transform_map) ----
+    def transform_map(self, frame="map", t=None, Sigma=None):
+        """Move the whole state into another frame on the device, in place.  frame="map": by the rigid transform t = (tx, ty, phi in
+        degrees) whose 3 x 3 covariance is Sigma (None: exact) -- the robot composes behind t (POSE_DELTA), every landmark follows
+        (RELATIVE_XY's inverse), P' = T P T' + A Sigma A'.  frame="robot": the robot's own pose becomes the origin, bit for bit what
+        extract_map(range(N), "robot") writes into another engine; t and Sigma stay None.  N and s stay.  A synchronising call: pending
+        is 0 afterwards (ekf_transform_map)."""
+        self._transform_map(marshal.transform_args(frame, t, Sigma))
+
+    def _transform_map(self, args):
+        frame, tv, Sv = args
+        self._check(self.lib.ekf_transform_map(self.h, frame, marshal.p_or_null(tv), marshal.p_or_null(Sv)))
+
     @staticmethod
     def model_invert(model, xr, z, lib=None):
         """(t, Gx, Gz): the landmark that z observes from the robot state xr = (x, y, theta in degrees) through EKF_MODEL_RANGE_BEARING

@@ -164,6 +164,38 @@ def extract_args(indices, frame, who="extract_map"):
     return arr, m, ctypes.c_int32(frames[frame])
 
 
+def transform_args(frame, t, Sigma, who="transform_map"):
+    """(frame, t[3] or None, Sigma[9] column-major or None) of transform_map as the ABI takes them, the arrays kept so that the caller
+    logs from what was sent.  frame "map": t = (tx, ty, phi in degrees), finite; Sigma None (an exact transform) or 3 x 3, finite,
+    symmetric, with a non-negative diagonal and non-negative leading principal minors.  frame "robot": neither.  Anything else is
+    refused here, before any call."""
+    frames = {"map": L.EKF_FRAME_MAP, "robot": L.EKF_FRAME_ROBOT}
+    if not isinstance(frame, str) or frame not in frames:
+        raise ValueError("%s: frame is 'map' or 'robot'" % who)
+    if frame == "robot":
+        if t is not None or Sigma is not None:
+            raise ValueError("%s: frame 'robot' takes neither t nor Sigma" % who)
+        return ctypes.c_int32(frames[frame]), None, None
+    if t is None:
+        raise ValueError("%s: frame 'map' needs the transform t = (tx, ty, phi)" % who)
+    tv = _vec(t)
+    if tv.size != 3 or not np.all(np.isfinite(tv)):
+        raise ValueError("%s: t is three finite values (tx, ty, phi in degrees)" % who)
+    Sv = None
+    if Sigma is not None:
+        Sm = np.asarray(Sigma, dtype=np.float64)
+        if Sm.size != 9 or not np.all(np.isfinite(Sm)):
+            raise ValueError("%s: Sigma is 3 x 3 and finite" % who)
+        Sm = Sm.reshape(3, 3)
+        S = [float(v) for v in Sm.reshape(-1)]                             # the library's own expressions, row-major
+        m2 = S[0] * S[4] - S[1] * S[3]
+        m3 = S[0] * (S[4] * S[8] - S[5] * S[7]) - S[1] * (S[3] * S[8] - S[5] * S[6]) + S[2] * (S[3] * S[7] - S[4] * S[6])
+        if not np.array_equal(Sm, Sm.T) or np.any(np.diag(Sm) < 0) or m2 < 0 or m3 < 0:
+            raise ValueError("%s: Sigma is symmetric with a non-negative diagonal and non-negative leading principal minors" % who)
+        Sv = np.ascontiguousarray(Sm.reshape(-1, order="F"))
+    return ctypes.c_int32(frames[frame]), tv, Sv
+
+
 def model_inits(entries, who="append_model"):
     """(ekf_model_init[], m) of a scan of new landmarks [(model, z, R, signature), ...]."""
     entries = list(entries)

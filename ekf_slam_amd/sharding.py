@@ -155,6 +155,11 @@ class ShardGroup:
         to the first shard so that the refusal is the library's (EKF_ERR_INVALID_ARG, nothing changed)."""
         return self.shards[0].extract_map(indices, frame, into, **engine_kw)
 
+    def transform_map(self, frame="map", t=None, Sigma=None):
+        """Not built for a shard group: the tile kernel walks the unsharded work list (the exact rigid form would need no exchange).  The
+        call goes to the first shard so that the refusal is the library's (EKF_ERR_INVALID_ARG, nothing changed)."""
+        return self.shards[0].transform_map(frame, t, Sigma)
+
     def correct(self, z, R, idx0):
         for e in self.shards:
             e.correct_begin(z, R, idx0)

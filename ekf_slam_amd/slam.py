@@ -363,6 +363,45 @@ class _EkfBase:
         self.remove_landmarks(idx)
         return sub
 
+    def _transform(self, frame, t, Sigma):
+        args = marshal.transform_args(frame, t, Sigma)                     # the one marshal: sent, then logged from
+        self._e._transform_map(args)
+        if self.log is not None:
+            self.log.record_map_transform(frame, args[1], None if args[2] is None else args[2].reshape(3, 3, order="F"))
+
+    def transform_map(self, t, Sigma=None):
+        """Move the whole map by the rigid transform t = (tx, ty, phi in degrees), in place on the device: the robot becomes t (+) r, every
+        landmark t_xy + Rot(phi) l, and P' = T P T' + A Sigma A' with Sigma the 3 x 3 covariance of t itself (None: an exact transform,
+        the rotation alone) -- georeferencing a finished map into a surveyed frame.  The filter keeps its engine, its log and its
+        landmark numbers (ekf_transform_map, EKF_FRAME_MAP).  The reference has no such method."""
+        self._transform("map", t, Sigma)
+
+    def recenter_on_robot(self):
+        """Re-anchor the whole filter at the robot: its pose becomes the origin with P(robot, .) = 0 and every landmark is expressed
+        relative to it, the robot's uncertainty folded into the landmarks -- the robocentric remedy for EKF-SLAM's inconsistency, and
+        the shape join_map expects of a local map (ekf_transform_map, EKF_FRAME_ROBOT).  The reference has no such method."""
+        self._transform("robot", None, None)
+
+    def align_to_anchors(self, numbers, positions, Sigma=None):
+        """The georeferencing POLICY: the closed-form 2-D rigid least-squares fit (rotation and translation, no scale) of the current
+        estimates of landmarks `numbers` (1-based, at least two) onto their surveyed `positions` (one row each), on the host, then ONE
+        transform_map(t, Sigma) through the logged method.  Returns (t, the rms residual of the fit)."""
+        numbers = self._landmark_numbers("align_to_anchors", *np.asarray(numbers).reshape(-1))
+        q = np.asarray(positions, dtype=np.float64).reshape(-1, 2)
+        if len(numbers) < 2 or q.shape[0] != len(numbers):
+            raise ValueError("align_to_anchors: at least two landmarks, one surveyed position each")
+        x = self._e.get_x()
+        p = np.array([x[3 + 2 * (i - 1):5 + 2 * (i - 1)] for i in numbers])
+        pc, qc = p - p.mean(axis=0), q - q.mean(axis=0)
+        phi = np.arctan2(np.sum(pc[:, 0] * qc[:, 1] - pc[:, 1] * qc[:, 0]), np.sum(pc[:, 0] * qc[:, 0] + pc[:, 1] * qc[:, 1]))
+        c, s = np.cos(phi), np.sin(phi)
+        Rot = np.array([[c, -s], [s, c]])
+        txy = q.mean(axis=0) - Rot @ p.mean(axis=0)
+        t = np.array([txy[0], txy[1], np.degrees(phi)])
+        rms = float(np.sqrt(np.mean(np.sum((p @ Rot.T + txy - q) ** 2, axis=1))))
+        self.transform_map(t, Sigma)
+        return t, rms
+
     def observe_linear(self, z, R, Hr=None, landmarks=(), Hl=(), gate=float("inf"), wrap=(0, 0), rows=2, wait=False):
         """'H x was observed as z with noise covariance R' for a constant H: the 2 x 3 block Hr on the robot state (x, y, theta in
         degrees) plus one 2 x 2 block Hl[b] on each of up to two landmarks (1-based numbers) -- the exact Kalman update, as an

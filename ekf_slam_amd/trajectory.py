@@ -38,6 +38,7 @@ FORMAT_ITERATED = "ekfslam-trajectory-8"
 FORMAT_JOINT = "ekfslam-trajectory-9"
 FORMAT_JOINT_ITERATED = "ekfslam-trajectory-10"
 FORMAT_JOIN_MAP = "ekfslam-trajectory-11"
+FORMAT_TRANSFORM_MAP = "ekfslam-trajectory-12"
 EDIT_KINDS = ("remove", "constrain", "merge", "merge_batch")        # what record_edit takes
 OBSERVE = "observe"                                                  # record_observation's
 OBSERVE_MODEL = "observe_model"                                      # record_model_observation's
@@ -47,10 +48,13 @@ OBSERVE_MODEL_ITERATED = "observe_model_iterated"                    # record_mo
 OBSERVE_MODEL_JOINT = "observe_model_joint"                          # record_model_observation_joint's
 OBSERVE_MODEL_JOINT_ITERATED = "observe_model_joint_iterated"        # record_model_observation_joint_iterated's
 JOIN_MAP = "join_map"                                                # record_map_join's
+TRANSFORM_MAP = "transform_map"                                      # record_map_transform's
 _FORMATS = (FORMAT, FORMAT_EDITS, FORMAT_BATCH, FORMAT_OBSERVE, FORMAT_MODEL, FORMAT_APPEND, FORMAT_PREDICT, FORMAT_ITERATED, FORMAT_JOINT,
             FORMAT_JOINT_ITERATED)
 # ... the ten formats of a log that speaks of ONE map; a log with a join also holds a second map's state and is written in the eleventh
 _ALL_FORMATS = _FORMATS + (FORMAT_JOIN_MAP,)
+# ... and every format a file may carry: the twelfth adds the map's change of frame (the two tuples above are counted by their users)
+_EVERY_FORMAT = _ALL_FORMATS + (FORMAT_TRANSFORM_MAP,)
 _STEP_ARRAYS = ("u", "obs_ptr", "obs", "lm_ptr", "lm_index", "lm_loc")
 _EDIT_ARRAYS = ("edit_step", "edit_kind", "edit_ptr", "edit_idx", "edit_delta", "edit_R")
 
@@ -152,6 +156,12 @@ _KINDS_TABLE = (
     _Kind(JOIN_MAP, 11, _replay_join, "map_joins", "join",
           (_Field("x", "x", _F, None), _Field("s", "s", _F, None), _Field("P", "P", _F, None), _Field("offset", "offset", _F, ())),
           ragged=True, shape=_join_shape),
+    # transform_map: the whole map moved into another frame, idx empty; per transform the frame (0: the rigid transform t with covariance
+    # Sigma, None travelling as NaN: an exact one; 1: the robot's own frame, t and Sigma both None)
+    _Kind(TRANSFORM_MAP, 12,
+          lambda e, idx0, d, R, o: e.transform_map("robot" if o["frame"] else "map", o["t"], o["Sigma"]),
+          "map_transforms", "transform",
+          (_Field("frame", "frame", _I, ()), _Field("t", "t", _F, (3,), True), _Field("Sigma", "Sigma", _F, (3, 3), True))),
 )
 _KINDS = tuple(k.name for k in _KINDS_TABLE)
 _KIND = {k.name: k for k in _KINDS_TABLE}
@@ -226,6 +236,7 @@ class TrajectoryLog:
         self.model_iterations = {}  # position in self.edits of an 'observe_model_iterated' edit -> {model, anchor or None, gate, iterations, tol}
         self.model_joints = {}      # position in self.edits of an 'observe_model_joint' edit -> [(model, z (2), R (2x2), landmark 1-based or 0), ...]
         self.model_joint_iterations = {}  # position in self.edits of an 'observe_model_joint_iterated' edit -> the same list
+        self.map_transforms = {}    # position in self.edits of a 'transform_map' edit -> {frame 0 / 1, t (3) or None, Sigma (3x3) or None}
         self.map_joins = {}         # position in self.edits of a 'join_map' edit -> {x (3 + 2 M), s (M), P dense, offset}: the local map
         self.observations = {}      # position in self.edits of an 'observe' edit -> {Hr (2x3), Hl (2x2x2), gate, wrap (2), rows}
 
@@ -346,6 +357,18 @@ class TrajectoryLog:
             raise ValueError("record_map_join: x has 3 + 2 M values, s has M and P is square of x's size")
         self._record(JOIN_MAP, payload=dict(x=xv, s=sv, P=Pm.reshape(xv.size, xv.size).copy(), offset=float(signature_offset)))
 
+    def record_map_transform(self, frame, t=None, Sigma=None):
+        """The whole map moved into another frame (transform_map / recenter_on_robot of ekf_slam_amd/slam.py) now, i.e. after the
+        len(self) steps recorded so far: frame "map" with the rigid transform t (3) and its covariance Sigma (3 x 3, None: exact), or
+        frame "robot" with neither."""
+        if frame not in ("map", "robot"):
+            raise ValueError("record_map_transform: frame is 'map' or 'robot'")
+        if (frame == "map") != (t is not None) or (frame == "robot" and Sigma is not None):
+            raise ValueError("record_map_transform: 'map' takes t and maybe Sigma, 'robot' takes neither")
+        tv = None if t is None else np.asarray(t, dtype=np.float64).reshape(3).copy()
+        Sm = None if Sigma is None else np.asarray(Sigma, dtype=np.float64).reshape(3, 3).copy()
+        self._record(TRANSFORM_MAP, payload=dict(frame=int(frame == "robot"), t=tv, Sigma=Sm))
+
     def record_model_predict(self, steps):
         """One chain of motion steps (predict_model of ekf_slam_amd/slam.py) made now, i.e. after the len(self) steps recorded so far:
         steps = [(model, u, M), ...], at least one, u and M of the size the model reads (2 and 2 x 2, or 3 and 3 x 3)."""
@@ -365,7 +388,7 @@ class TrajectoryLog:
             data = np.concatenate(parts) if parts and ptr[-1] else np.zeros((0, width) if width else (0,))
             return ptr, data
         ver = max([1] + [_KIND[e[1]].format for e in self.edits])
-        arrays = dict(format=np.array(_ALL_FORMATS[ver - 1]))
+        arrays = dict(format=np.array(_EVERY_FORMAT[ver - 1]))
         if self.edits:
             e_ptr, e_idx = ragged([e[2] for e in self.edits], 0)
             arrays.update(edit_step=np.array([e[0] for e in self.edits], dtype=np.int64),
@@ -385,9 +408,9 @@ class TrajectoryLog:
     def load(path):
         g = np.load(path, allow_pickle=False)
         fmt = str(g["format"])
-        if fmt not in _ALL_FORMATS:
-            raise ValueError("not an %s file" % " / ".join(_ALL_FORMATS))
-        ver = _ALL_FORMATS.index(fmt) + 1
+        if fmt not in _EVERY_FORMAT:
+            raise ValueError("not an %s file" % " / ".join(_EVERY_FORMAT))
+        ver = _EVERY_FORMAT.index(fmt) + 1
         held = [kind for kind in _KINDS_TABLE if kind.store and kind.format <= ver]
         need = _STEP_ARRAYS + (_EDIT_ARRAYS if ver >= 2 else ()) + tuple(name for kind in held for name in _arrays_of(kind))
         missing = [k for k in need if k not in g.files]

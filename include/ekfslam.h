@@ -563,6 +563,37 @@ int32_t ekf_join_map(ekf_handle *h, ekf_handle *local, double signature_offset, 
  * from `h`'s mirror, as ekf_join_map takes it. */
 enum { EKF_FRAME_MAP = 0, EKF_FRAME_ROBOT = 1 };
 int32_t ekf_extract_map(ekf_handle *h, const int64_t *idx, int64_t m, int32_t frame, ekf_handle *dst);
+/* THE FRAME OF A MAP: the whole state of `h` moved into another frame, IN PLACE -- no second handle, the handle keeps its log and its
+ * configuration.  N, s and the numbering stay.  k = 180/pi.
+ *   EKF_FRAME_MAP    the map stays a map, moved by the rigid transform t = (tx, ty, phi), phi in degrees; Sigma is the column-major 3 x 3
+ *                    covariance of t, independent of the state (NULL or all zeros: an exact transform).  With (s, c) the degree sine and
+ *                    cosine of phi, Rot = [c -s; s c] and w(v) = Rot v:
+ *                      r'   = t (+) r         bit for bit ekf_motion_evaluate's EKF_MOTION_POSE_DELTA at (xr = t, u = r): p' = t_xy + w(p),
+ *                                             theta' = wrapTo360(phi + theta); F is that call's F, V = blockdiag(Rot, 1) its V
+ *                      l_i' = t_xy + w(l_i)   bit for bit ekf_model_invert's EKF_MODEL_RELATIVE_XY at (t, l_i);
+ *                                             A_i = its Gx = [1 0 -w_1(l_i)/k; 0 1 w_0(l_i)/k]
+ *                    and P' = T P T' + A Sigma A', T = blockdiag(V, Rot, .., Rot), A = (F; A_1; ..; A_N), block by block, every sum left to
+ *                    right and the rotation term first (strip = P(1:3, landmarks)):
+ *                      P'(1:3,1:3) = V P(1:3,1:3) V' + F Sigma F'       strip'(:, i) = V strip(:, i) Rot' + F Sigma A_i'
+ *                      P'(i, j)    = Rot P(i, j) Rot' + A_i Sigma A_j'
+ *                    With Sigma NULL or zero the Sigma terms are not formed: the rotation alone, so t = 0 leaves every value equal as a
+ *                    number and phi = 90 is a signed permutation of P's entries (the degree sine and cosine are exact there).  This is
+ *                    ekf_join_map's J with the roles swapped: the transform plays the global robot, the whole map the local one.
+ *   EKF_FRAME_ROBOT  the robot's own pose becomes the origin; t and Sigma must be NULL.  The result is bit for bit what
+ *                    ekf_extract_map(h, [0 .. N-1], EKF_FRAME_ROBOT, dst) writes into a dst of the same tile edge and storage kind (x, s,
+ *                    P, the diagonal copies; a float tile is widened to F64 and the result rounded once): the robot at (0, 0, 0) with
+ *                    P'(1:3, :) = 0 -- the shape ekf_join_map expects of a `local`.  A landmark exactly on the robot is regular.
+ * A landmark's own 2 x 2 block is formed from the live F64 diagonal copy and written to the copy and to the tile.  Two launches, counted
+ * under EKF_KERNEL_COMPACT: the small part and the strip (one lane per column, into the other buffer set), and ONE IN-PLACE PASS over the
+ * current tile store (a lane owns whole 2 x 2 blocks, 16-byte accesses; diagonal tiles stored whole, their halves equal bit for bit;
+ * entries beyond 2 N stay zero; a second store of cfg.async_flush or of a removal is untouched).  N = 0 is allowed and launches no pass.
+ * A SYNCHRONISING call, like ekf_constrain_landmarks: the measure loop settled, a recorded predict carried out, pending pairs applied, an
+ * asynchronous pass retired; the stream is drained before the call returns and ekf_pending is 0.  Prefetched row-panels are dropped as for
+ * a replaced covariance; an announced prefetch and the hint stay (the numbering did not change).
+ * Refused with nothing changed and nothing flushed: h NULL, a frame that is neither constant, EKF_FRAME_MAP with t NULL or not finite, Sigma
+ * not finite, not symmetric, or with a negative diagonal entry or a negative leading principal minor, EKF_FRAME_ROBOT with t or Sigma given,
+ * a sharded handle (world > 1) (EKF_ERR_INVALID_ARG); a sharded correction between begin and finish (EKF_ERR_STATE). */
+int32_t ekf_transform_map(ekf_handle *h, int32_t frame, const double t[3] /* EKF_FRAME_ROBOT: NULL */, const double Sigma[9] /* may be NULL */);
 /* The step between the two: "WHICH landmark does this sighting belong to?", for a whole scan, under the conventions of ekf_observe_model.
  * ekf_associate keeps the reference's (signature-only by default, an unwrapped bearing, a range-scaled R) and cannot serve a filter
  * driven through the model calls.  For each of the m observations, d2(k, i) is, BIT FOR BIT, the d2 that ekf_model_innovation reports for

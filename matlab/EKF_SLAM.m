@@ -264,6 +264,20 @@ classdef EKF_SLAM < handle
             end
             h.gateway('extract_map', double(idx(:)), f, dst.hnd);
         end
+        function transformMap(h, t, Sigma)
+            % THE FRAME OF THE MAP: the whole map moved by the rigid transform t = [tx ty phi] (phi in degrees), in place on the GPU: the
+            % robot becomes t (+) r, every landmark t(1:2)' + Rot(phi) * l, and P' = T P T' + A Sigma A' with Sigma the 3 x 3 covariance
+            % of t itself (left out or empty: an exact transform, the rotation alone) -- georeferencing a finished map into a surveyed
+            % frame.  The object keeps its handle and its landmark numbers.  Not a method of the reference.
+            if nargin < 3, Sigma = []; end
+            h.gateway('transform_map', 0, double(t(:)), double(Sigma));
+        end
+        function recenterOnRobot(h)
+            % The filter re-anchored at the robot: its pose becomes the origin with P(1:3, :) = 0 and every landmark is expressed relative
+            % to it, the robot's uncertainty folded into the landmarks -- the robocentric remedy for EKF-SLAM's inconsistency, and the
+            % shape joinMap expects of a local map.  Bit for bit extractMap(1:N, 'robot', dst), without a second object.
+            h.gateway('transform_map', 1, [], []);
+        end
         function idx = addLandmarkRangeBearing(h, z, R, signature)
             % 'A landmark that is not in the map yet is seen at range z(1) and bearing z(2) (degrees, relative to the heading),
             % covariance R': it joins the map at the point that observation names.

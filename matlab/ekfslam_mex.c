@@ -27,7 +27,7 @@
  * (ekf_observe_model), the append through a model (ekf_append_model), the association of a scan under the models' conventions
  * (ekf_associate_model) and its one-to-one assignment (ekf_assign_model), the joint compatibility of a scan's pairings (ekf_joint_innovation) and their joint update
  * (ekf_observe_model_joint, relinearised: ekf_observe_model_joint_iterated), the relinearised model observation
- * (ekf_observe_model_iterated), the motion steps under them (ekf_predict_model), the join of a local map (ekf_join_map) and the extraction of part of the map (ekf_extract_map) are the ones this gateway can live without: bound weakly, so that the gateway still links against a libekfslam (or a stand-in) that
+ * (ekf_observe_model_iterated), the motion steps under them (ekf_predict_model), the join of a local map (ekf_join_map), the extraction of part of the map (ekf_extract_map) and the map's change of frame (ekf_transform_map) are the ones this gateway can live without: bound weakly, so that the gateway still links against a libekfslam (or a stand-in) that
  * predates them; their commands then raise a MATLAB error instead. */
 #if defined(__GNUC__)
 #pragma weak ekf_remove_landmarks
@@ -48,6 +48,7 @@
 #pragma weak ekf_observe_model_joint_iterated
 #pragma weak ekf_join_map
 #pragma weak ekf_extract_map
+#pragma weak ekf_transform_map
 #define HAVE_REMOVE_LANDMARKS (ekf_remove_landmarks != 0)
 #define HAVE_CONSTRAIN_LANDMARKS (ekf_constrain_landmarks != 0)
 #define HAVE_MERGE_LANDMARKS (ekf_merge_landmarks != 0)
@@ -66,6 +67,7 @@
 #define HAVE_OBSERVE_MODEL_JOINT_ITERATED (ekf_observe_model_joint_iterated != 0)
 #define HAVE_JOIN_MAP (ekf_join_map != 0)
 #define HAVE_EXTRACT_MAP (ekf_extract_map != 0)
+#define HAVE_TRANSFORM_MAP (ekf_transform_map != 0)
 #else
 #define HAVE_REMOVE_LANDMARKS 1
 #define HAVE_CONSTRAIN_LANDMARKS 1
@@ -85,6 +87,7 @@
 #define HAVE_OBSERVE_MODEL_JOINT_ITERATED 1
 #define HAVE_JOIN_MAP 1
 #define HAVE_EXTRACT_MAP 1
+#define HAVE_TRANSFORM_MAP 1
 #endif
 
 static void need(int nrhs, int want, const char *cmd) {
@@ -467,6 +470,20 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
         const int32_t rc = ekf_extract_map(h, idx0, (int64_t)m, frame, dst);
         free(idx0);
         check(h, rc);
+        return;
+    }
+    if (!strcmp(cmd, "transform_map")) {          /* (h, frame, t, Sigma): the whole map moved into another frame, in place.  frame 0: by the rigid transform
+                                                     t (3 values: tx, ty, phi in degrees) with covariance Sigma (3 x 3, or empty: exact); frame 1: into the
+                                                     robot's own frame, t and Sigma both empty; no output */
+        need(nrhs, 5, cmd);
+        if (!HAVE_TRANSFORM_MAP) mexErrMsgIdAndTxt("ekfslam:usage", "transform_map: this libekfslam has no ekf_transform_map");
+        if (!prhs[2] || mxGetNumberOfElements(prhs[2]) != 1 || !mxGetPr(prhs[2]) || (mxGetPr(prhs[2])[0] != 0.0 && mxGetPr(prhs[2])[0] != 1.0))
+            mexErrMsgIdAndTxt("ekfslam:usage", "transform_map: frame is 0 (map) or 1 (robot)");
+        const int32_t frame = (int32_t)mxGetPr(prhs[2])[0];
+        const mwSize nt = prhs[3] ? mxGetNumberOfElements(prhs[3]) : 0, ns = prhs[4] ? mxGetNumberOfElements(prhs[4]) : 0;
+        if (frame == 1 ? (nt != 0 || ns != 0) : (nt != 3 || !mxGetPr(prhs[3]) || (ns != 0 && (ns != 9 || !mxGetPr(prhs[4])))))
+            mexErrMsgIdAndTxt("ekfslam:usage", "transform_map: frame 0 takes t (3 values) and Sigma (3 x 3 or empty), frame 1 takes both empty");
+        check(h, ekf_transform_map(h, frame, nt ? mxGetPr(prhs[3]) : NULL, ns ? mxGetPr(prhs[4]) : NULL));      /* (MATLAB arrays are column-major) */
         return;
     }
     if (!strcmp(cmd, "associate_model")) {        /* [match, d2] = (h, model m x 1 (1..4), z m x 2, R 2 x 2 x m, gate m x 1): which landmark each sighting of a
