@@ -102,6 +102,16 @@ class EkfJointResult(ctypes.Structure):
     _fields_ = [("d2", _d), ("dof", _i32), ("pairings", _i32), ("outcome", _i32), ("first_irregular", _i32)]
 
 
+EKF_JOINT_SEARCH_CAND = 4
+EKF_JOINT_SEARCH_BEAM_MAX = 64
+
+
+class EkfJointSearchResult(ctypes.Structure):
+    """struct ekf_joint_search_result (include/ekfslam.h)."""
+    _fields_ = [("lm", _i64 * EKF_JOINT_MAX), ("d2", _d), ("dof", _i32), ("pairings", _i32), ("truncated", _i32), ("nalive", _i32),
+                ("irregular", _i32), ("tested", _i32 * EKF_JOINT_MAX), ("survived", _i32 * EKF_JOINT_MAX)]
+
+
 EKF_JOINT_ITER_MAX = EKF_MODEL_ITER_MAX
 EKF_JOINT_SUB_MAX = 3 + 2 * EKF_JOINT_MAX
 
@@ -195,6 +205,8 @@ SIGNATURES = {
     "ekf_assigned_scan_result": (_i32, [_vp, ctypes.POINTER(_i64), ctypes.POINTER(EkfModelAssigned), ctypes.POINTER(EkfLinearResult), _dp]),
     "ekf_joint_innovation": (_i32, [_vp, ctypes.POINTER(EkfModelObs), _i64, ctypes.POINTER(_i64), _i64, ctypes.POINTER(EkfJointResult), _dp, _dp,
                                     _dp]),
+    "ekf_joint_search": (_i32, [_vp, ctypes.POINTER(EkfModelObs), _i64, _dp, _i32, ctypes.POINTER(EkfJointSearchResult),
+                                ctypes.POINTER(EkfModelMatch), ctypes.POINTER(_i64), _dp, ctypes.POINTER(_i64), _dp]),
     "ekf_observe_model_joint": (_i32, [_vp, ctypes.POINTER(EkfModelObs), _i64, ctypes.POINTER(_i64), _d, ctypes.POINTER(EkfJointResult), _dp, _dp]),
     "ekf_observe_model_joint_iterated": (_i32, [_vp, ctypes.POINTER(EkfModelObs), _i64, ctypes.POINTER(_i64), _d, _i32, _d,
                                                 ctypes.POINTER(EkfJointResult), ctypes.POINTER(EkfJointIterResult), _dp, _dp]),

@@ -21,6 +21,7 @@
 #include "host/assign_model.h" // ... and the scan assigned to the map one-to-one: assign_model
 #include "host/model_assigned.h" // ... and assigned, then applied step by step with no wait between: observe_model_assigned, assigned_scan_result
 #include "host/joint.h"        // ... and a whole scan's pairings judged jointly, nh hypotheses per call: joint_innovation
+#include "host/joint_search.h" // ... and searched on the device for the jointly compatible hypothesis, one readback: joint_search
 #include "host/joint_update.h" // ... and applied as ONE joint update behind a flush: observe_model_joint
 #include "host/joint_iter.h"   // ... relinearised: observe_model_joint_iterated, joint_iterate
 #include "host/predict_model.h" // motion steps with true Jacobians, a chain per launch: predict_model, motion_evaluate

@@ -683,6 +683,70 @@ EKF_MHD double joint_prefix_add(double acc, double y0, double y1) {
     acc = acc + y0 * y0;
     return acc + y1 * y1;
 }
+// The ROW-APPEND of that factorisation (ekf_joint_search; joint_search.h runs these on the device): a hypothesis is its parent plus one
+// pairing, so its factor is the parent's with the two rows i0, i0 + 1 appended, in O(i0^2) where a factorisation from scratch costs
+// O(i0^3).  L (leading dimension ld) is the parent's factor with the PIVOT'S ROOT l_kk on its diagonal (joint_factor_* leave l_kk^2 there),
+// y its L^-1 nu.  The two rows enter in a0 / a1 as their S entries -- a0[0 .. i0], a1[0 .. i0 + 1] -- each with its nu behind its diagonal
+// entry (a0[i0 + 1], a1[i0 + 2]), and leave in l0 / l1 laid out alike: L's entries, the pivot's root on the diagonal, then y.  Every entry
+// sees the operations joint_factor_scale / joint_factor_update apply to it, in their order -- a = a - L_ik L_jk for ascending k, then
+// a / l_jj -- so L, y and every prefix are the right-looking factorisation's bit for bit.  Step k < i0, lane `lane` of `lanes`, the steps
+// separated by the caller (a barrier); l0 / l1 do not alias a0 / a1 (a step's divisor a[k] is read by every lane).
+EKF_MHD void joint_append_step(const double *L, int ld, const double *y, double *a0, double *a1, double *l0, double *l1, int i0, int k,
+                               int lane, int lanes) {
+    const double lkk = L[k * ld + k];
+    const double e0 = a0[k] / lkk, e1 = a1[k] / lkk;
+    if (lane == 0) { l0[k] = e0; l1[k] = e1; }
+    for (int j = k + 1 + lane; j <= i0 + 2; j += lanes) {
+        if (j < i0) {
+            const double ljk = L[j * ld + k];
+            a0[j] = a0[j] - e0 * ljk;
+            a1[j] = a1[j] - e1 * ljk;
+        } else if (j == i0) {                       // row i0's diagonal; row i0 + 1 against row i0
+            a0[j] = a0[j] - e0 * e0;
+            a1[j] = a1[j] - e1 * e0;
+        } else if (j == i0 + 1) {                   // row i0's y; row i0 + 1's diagonal
+            a0[j] = a0[j] - e0 * y[k];
+            a1[j] = a1[j] - e1 * e1;
+        } else {                                    // row i0 + 1's y
+            a1[j] = a1[j] - e1 * y[k];
+        }
+    }
+}
+// ... and the close, by ONE lane behind the last step: row i0's pivot and y, step i0 of row i0 + 1, its pivot and y.  False where a pivot
+// fails joint_pivot: the pairing is irregular and nothing of l0 / l1 is to be read.
+EKF_MHD bool joint_append_close(const double *a0, double *a1, double *l0, double *l1, int i0) {
+    double lkk;
+    if (!joint_pivot(a0[i0], lkk)) return false;
+    l0[i0] = lkk;
+    const double y0 = a0[i0 + 1] / lkk;
+    l0[i0 + 1] = y0;
+    const double e1 = a1[i0] / lkk;
+    l1[i0] = e1;
+    a1[i0 + 1] = a1[i0 + 1] - e1 * e1;
+    a1[i0 + 2] = a1[i0 + 2] - e1 * y0;
+    if (!joint_pivot(a1[i0 + 1], lkk)) return false;
+    l1[i0 + 1] = lkk;
+    l1[i0 + 2] = a1[i0 + 2] / lkk;
+    return true;
+}
+// The ORDER of a joint-compatibility search's survivors: more pairings first, then the smaller joint d2, then the hypothesis, compared
+// entry by entry in scan order on the 0-based landmark with -1 for left out -- Python's order of the tuples (-pairings, d2, hypothesis).
+// A hypothesis is given as its parent's n entries and its own last one.  No d2 here is NaN (a NaN does not survive its test).
+EKF_MHD bool joint_search_before(int pa, double da, const long long *ha, long long ta, int pb, double db, const long long *hb, long long tb,
+                                 int n) {
+    if (pa != pb) return pa > pb;
+    if (da != db) return da < db;
+    for (int k = 0; k < n; ++k)
+        if (ha[k] != hb[k]) return ha[k] < hb[k];
+    return ta < tb;
+}
+// an extension's test: NaN never survives
+EKF_MHD bool joint_search_passes(double d2, double threshold) { return d2 <= threshold; }
+// the cut: how many of `survived` stay alive under `beam`, and whether that is a cut -- exactly `beam` survivors is none
+EKF_MHD int joint_search_cut(int survived, int beam, bool &truncated) {
+    truncated = survived > beam;
+    return truncated ? beam : survived;
+}
 
 // The ITERATED joint update (ekf_observe_model_joint_iterated; joint_iter.h runs these on the device, ekf_joint_iterate on the host with
 // one lane): Gauss-Newton on the MAP cost over the sub-state xi = (x_r, l_0 .. l_{np-1}), ns = 3 + 2 np entries, under its PRIOR covariance

@@ -243,6 +243,11 @@ struct ekf_handle {
     char *d_jout = nullptr, *h_jout = nullptr;
     double *d_jS = nullptr, *h_jS = nullptr;
     hipEvent_t ev_joint = nullptr;
+    // ---- ... searched on the device (ekf_joint_search) ----
+    // the store of operands, extensions and nodes, and the block a call brings back on the device and in pinned memory (allocated at the
+    // first call and kept); read back behind ev_joint
+    JointSearchStore *d_jsearch = nullptr;
+    JointSearchOut *d_jsout = nullptr, *h_jsout = nullptr;
     // ---- a scan's pairings applied as one joint update (ekf_observe_model_joint) ----
     // what k_joint_factor hands k_gather_joint (allocated at the first call and kept); its pairs go to d_mring above
     JointBlock *d_jblock = nullptr;

@@ -241,6 +241,66 @@ struct JointRecord {
     int32_t dof, pairings, outcome, first_irregular;
 };
 
+// The joint-compatibility SEARCH over a scan (joint_search.h, ekf_joint_search): a level per scan index, at most kJointSearchBeam
+// hypotheses alive between two levels, each extended by the first kJointSearchCand candidates of the level's entry and by "left out".
+// Everything lives in ONE device store: the operands of the (entry, candidate) pairs, the extensions of the level in flight, and per
+// level and alive slot a NODE -- the two factor rows its pairing appended (ekfm::joint_append_*: L's entries, the pivot's root, then y),
+// the hypothesis so far, and per earlier level the slot of its ancestor and the candidate it took, which is how a workgroup finds its
+// parent's factor rows without copying them.  Node level k holds what is alive BEFORE scan index k; level 0 is the empty hypothesis.
+constexpr int kJointSearchCand = 4;
+constexpr int kJointSearchBeam = 64;
+constexpr int kJointSearchExt = kJointSearchBeam * kJointSearchCand;        // extensions that append rows: (parent, candidate)
+constexpr int kJointSearchSlots = kJointSearchBeam * (kJointSearchCand + 1);   // ... and "left out" behind each parent's candidates
+constexpr int kJointSearchRow = kJointRows + 2;                             // a row's entries, its diagonal, its y (row 63: 65 entries)
+struct JointSearchResult {        // ekf_joint_search_result, field by field
+    int64_t lm[kJointMax];
+    double d2;
+    int32_t dof, pairings, truncated, nalive, irregular;
+    int32_t tested[kJointMax], survived[kJointMax];
+};
+struct JointSearchOperand {       // ekfm::joint_pairing's outputs for one (entry, candidate)
+    double Hr[6], Ht[4], strip[6], S[4], nu[2];
+    int64_t lm;
+    int32_t posed, pad;
+};
+struct JointSearchExt {
+    double row[2][kJointSearchRow];
+    double d2;                    // NaN: irregular
+};
+struct JointSearchNode {
+    double row[2][kJointSearchRow];
+    double d2;
+    int64_t hyp[kJointMax];       // by scan index: the 0-based landmark, -1 = left out
+    int32_t anc[kJointMax];       // by scan index k: its ancestor's slot at node level k + 1
+    int32_t slot[kJointMax];      // by scan index: the candidate taken, -1 = left out
+    int32_t dof, pairings;
+};
+struct JointSearchStore {
+    JointSearchOperand op[kJointMax * kJointSearchCand];
+    int32_t nalive[kJointMax + 2];                // by node level: hypotheses alive
+    int32_t nirregular[kJointMax + 2];            // by node level: extensions without a d2 so far
+    JointSearchExt ext[kJointSearchExt];
+    JointSearchNode node[(kJointMax + 1) * kJointSearchBeam];
+};
+// what one call brings back, in the order of what is asked for: the head always, the final beam, the candidate lists
+struct JointSearchOut {
+    JointSearchResult res;
+    int64_t match[kJointMax * 6];                             // ekfm::Match2 (= ekf_model_match) per entry
+    double alive_d2[kJointSearchBeam];                        // NaN behind nalive
+    int64_t alive_hyp[kJointSearchBeam * kJointMax];          // row-major nalive x m, -1 behind
+    int64_t cand[kJointMax * kAssignCandidates];              // k_assign_select's lists
+    double cand_d2[kJointMax * kAssignCandidates];
+};
+struct JointSearchArgs {          // k_joint_search_extend
+    int64_t N;
+    int32_t m, level, cur, npend, pstart, pad;
+};
+struct JointSearchLevelArgs {     // k_joint_search_select
+    double threshold[kJointRows + 1];     // by dof
+    int32_t rows[kJointMax];              // by scan index: 2 for a two-row model, 1 for a one-row model
+    int32_t m, level, beam, pad;
+};
+
 // The joint UPDATE of one hypothesis (joint_update.h, ekf_observe_model_joint): k_joint_factor leaves what k_gather_joint needs in one device
 // block -- with L L' = S the factor of the stacked S, y = L^-1 nu, the Jacobian blocks of every pairing and the robot part
 // W_r = L^-1 G_r, G_r(2p + r, t) = H_p^r(r, :) Prr(:, t) + H_p^t(r, :) strip(t, l_p)' -- and k_gather_joint forms W = L^-1 H P column by column.

@@ -154,6 +154,9 @@ hipError_t launch_assoc_model(const DevState &st, const AssocModelArgs &a, ekfm:
 // second launch's; res (device): the block everything a call returns is left in.  Three launches ordered by the stream.
 hipError_t launch_assign_model(const DevState &st, const AssocModelArgs &a, ekfm::Match2 *partials, ekfm::CandList *lists, ekfm::CandList *sel,
                                AssignResult *res, hipStream_t s);
+// ... its first two launches alone: the lists in sel and the match records in res->match, no solve (ekf_joint_search reads sel on the device)
+hipError_t launch_assign_lists(const DevState &st, const AssocModelArgs &a, ekfm::Match2 *partials, ekfm::CandList *lists, ekfm::CandList *sel,
+                               AssignResult *res, hipStream_t s);
 
 // ---- the passes over P (launch/passes.h; launch/pass_select.h decides which kernel instance runs) ----
 // nx (sharded handles): ALSO extract the row-panel of landmark-block rows j, j + 1 into send (layout of launch_rowpanel) from the updated
@@ -260,6 +263,16 @@ hipError_t launch_model_iter_probe(const DevState &st, const IterModelArgs &a, d
 // (nh x (2m x 2m column-major)), device or nullptr, laid out by scan index.  Tile operands are read patched with the a.npend pending pairs.
 hipError_t launch_joint_innovation(const DevState &st, const JointArgs &a, const int64_t *hyp, int nh, JointRecord *out, double *d2_prefix,
                                    double *nu, double *S, int storage, hipStream_t s);
+
+// The joint-compatibility search over a scan (joint_search.h), read-only, behind launch_assign_lists on the same stream: sel (device) its
+// lists, match (device) its records.  launch_joint_search_prepare: one launch -- the operands of every (entry, candidate), the lists and
+// records copied into out, the empty hypothesis.  launch_joint_search_level: scan index `level`'s two launches, k_joint_search_extend over the
+// fixed grid of kJointSearchExt and k_joint_search_select; `which`: 0 both, 1 the extend alone, 2 the select alone (a caller that times
+// each).  Neither reads anything on the host.
+hipError_t launch_joint_search_prepare(const DevState &st, const JointArgs &a, const ekfm::CandList *sel, const int64_t *match,
+                                       JointSearchStore *store, JointSearchOut *out, hipStream_t s);
+hipError_t launch_joint_search_level(const DevState &st, const JointSearchArgs &a, const JointSearchLevelArgs &la, const ekfm::CandList *sel,
+                                     JointSearchStore *store, JointSearchOut *out, int which, int storage, hipStream_t s);
 
 // The joint UPDATE of one hypothesis (joint_update.h, ekf_observe_model_joint), on a flushed state (a.npend == 0).
 // launch_joint_factor: k_joint_factor, one workgroup, read-only -- k_joint_innovation's phases for the one hypothesis hyp (device, a.m entries),

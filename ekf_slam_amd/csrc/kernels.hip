@@ -56,6 +56,7 @@ namespace {
 #include "associate_model.h" // a scan against the whole map under the models' conventions: k_assoc_model, k_assoc_model_reduce
 #include "assign_model.h"    // ... and assigned to it one-to-one: k_assign_candidates, k_assign_select, k_assign_solve
 #include "joint.h"            // a scan's pairings judged jointly, a hypothesis per workgroup: k_joint_innovation
+#include "joint_search.h"     // ... and searched for the jointly compatible hypothesis, level by level: k_joint_search_prepare / _extend / _select
 #include "joint_update.h"     // ... and applied as one joint update: k_joint_factor, k_gather_joint
 #include "joint_iter.h"       // ... relinearised: k_joint_factor_iter
 #include "merge_pass.h"       // the fused downdate-and-compact pass of a batch of merges: k_merge_pass
@@ -68,5 +69,5 @@ namespace {
 #include "launch/steps.h"         // predict, append, gather, row-panels, association
 #include "launch/pass_select.h"   // which pass instance runs: a pure function, no HIP
 #include "launch/passes.h"        // launch_downdate, the row copies behind an asynchronous pass
-#include "launch/edits.h"         // compact, constrain, linear observation, joint innovation and joint update, merge pass, nearest
+#include "launch/edits.h"         // compact, constrain, linear observation, joint innovation, joint search and joint update, merge pass, nearest
 #include "launch/state_io.h"      // dense <-> tiled, block reads, low-rank load, digest

@@ -223,6 +223,28 @@ hipError_t launch_joint_innovation(const DevState &st, const JointArgs &a, const
     });
 }
 
+hipError_t launch_joint_search_prepare(const DevState &st, const JointArgs &a, const ekfm::CandList *sel, const int64_t *match,
+                                       JointSearchStore *store, JointSearchOut *out, hipStream_t s) {
+    if (a.m < 1 || a.m > kJointMax || !sel || !match || !store || !out || a.N < 1 || 2 * a.N > st.ldm) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_joint_search_prepare, dim3((unsigned)a.m), dim3(kJointSearchBlock), 0, s, st, a, sel, match, store, out);
+    return hipGetLastError();
+}
+
+hipError_t launch_joint_search_level(const DevState &st, const JointSearchArgs &a, const JointSearchLevelArgs &la, const ekfm::CandList *sel,
+                                     JointSearchStore *store, JointSearchOut *out, int which, int storage, hipStream_t s) {
+    // launch_joint_innovation's checks, the level inside the scan, the beam inside the store
+    if (a.m < 1 || a.m > kJointMax || a.level < 0 || a.level >= a.m || la.m != a.m || la.level != a.level || la.beam < 1 ||
+        la.beam > kJointSearchBeam || !sel || !store || !out || a.N < 1 || 2 * a.N > st.ldm || a.npend < 0 || a.npend > st.pcap || a.pstart < 0 ||
+        a.pstart >= st.pcap || st.tm.world != 1)
+        return hipErrorInvalidValue;
+    return with_storage(storage, [&](auto ts) {
+        if (which != 2)
+            hipLaunchKernelGGL(k_joint_search_extend<decltype(ts)>, dim3(kJointSearchExt), dim3(kJointSearchBlock), 0, s, st, a, sel, store);
+        if (which != 1)
+            hipLaunchKernelGGL(k_joint_search_select, dim3(1), dim3(kJointSearchSelectBlock), 0, s, la, sel, store, out);
+    });
+}
+
 hipError_t launch_joint_factor(const DevState &st, const JointArgs &a, const int64_t *hyp, JointBlock *blk, JointRecord *out, double *nu, double *S,
                                int storage, hipStream_t s) {
     // launch_joint_innovation's checks for one hypothesis on a flushed state

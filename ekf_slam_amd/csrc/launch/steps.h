@@ -218,6 +218,19 @@ hipError_t launch_assoc_model(const DevState &st, const AssocModelArgs &a, ekfm:
     return hipGetLastError();
 }
 
+hipError_t launch_assign_lists(const DevState &st, const AssocModelArgs &a, ekfm::Match2 *partials, ekfm::CandList *lists, ekfm::CandList *sel,
+                               AssignResult *res, hipStream_t s) {
+    if (a.N < 1 || 2 * a.N > st.ldm || a.m < 1 || a.m > kAssocModelMax || !partials || !lists || !sel || !res) return hipErrorInvalidValue;
+    for (int k = 0; k < a.m; ++k)
+        if (a.e[k].model < 1 || a.e[k].model > 4 || !std::isfinite(a.e[k].gate)) return hipErrorInvalidValue;
+    const int64_t nblk = cdiv(a.N, kAssocBlock);
+    hipLaunchKernelGGL(k_assign_candidates, dim3((unsigned)nblk, (unsigned)a.m), dim3(kAssocBlock), 0, s, st, a, partials, lists);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_assign_select, dim3((unsigned)a.m), dim3(kAssocBlock), 0, s, partials, lists, (int)nblk, (ekfm::Match2 *)res->match, sel);
+    return hipGetLastError();
+}
+
 hipError_t launch_assign_model(const DevState &st, const AssocModelArgs &a, ekfm::Match2 *partials, ekfm::CandList *lists, ekfm::CandList *sel,
                                AssignResult *res, hipStream_t s) {
     if (a.N < 1 || 2 * a.N > st.ldm || a.m < 1 || a.m > kAssocModelMax || !partials || !lists || !sel || !res) return hipErrorInvalidValue;

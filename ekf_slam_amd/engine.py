@@ -636,6 +636,32 @@ class Engine:
             res["S"] = S.transpose(0, 2, 1).copy()      # column-major blocks
         return res
 
+    # ---- ... and searched on the device (include/ekfslam.h: ekf_joint_search) ----
+    def joint_search(self, entries, thresholds, beam=64, want_candidates=False, want_alive=False):
+        """The joint-compatibility search over one scan, on the device with one readback: entries as for assign_model (every gate
+        finite: it decides what a candidate is), thresholds[dof] for dof 0 .. 2m, beam in 1 .. EKF_JOINT_SEARCH_BEAM_MAX.  Level k
+        extends every alive hypothesis by the first EKF_JOINT_SEARCH_CAND candidates of entry k and by "left out"; an extension
+        survives where its joint d2 <= thresholds[dof]; survivors are ordered by (pairings descending, d2 ascending, hypothesis
+        ascending) and cut at beam.  Returns the winner's 'landmark' (0-based, -1 = left out), 'd2', 'dof', 'pairings', 'truncated',
+        'nalive', 'irregular' (extensions without a d2), 'tested' / 'survived' per scan index, the keys of associate_model (its per-entry
+        'irregular' as 'match_irregular'), with want_candidates 'cand' /
+        'cand_d2' as assign_model returns them and with want_alive 'alive' (nalive x m) / 'alive_d2', the final beam in order.  Every d2 is
+        joint_innovation's d2_prefix for that hypothesis bit for bit.  Changes and flushes nothing (ekf_joint_search)."""
+        arr, m = marshal.scan_obs(entries)
+        thr = marshal.joint_search_thresholds(thresholds, m)
+        if int(beam) != beam:
+            raise ValueError("joint_search: beam is a whole number")
+        res, match = L.EkfJointSearchResult(), (L.EkfModelMatch * max(m, 1))()
+        cand = np.full((m, L.EKF_ASSIGN_CANDIDATES), -1, dtype=np.int64) if want_candidates else None
+        cand_d2 = np.full((m, L.EKF_ASSIGN_CANDIDATES), np.inf) if want_candidates else None
+        alive = np.full((L.EKF_JOINT_SEARCH_BEAM_MAX, max(m, 1)), -1, dtype=np.int64) if want_alive else None
+        alive_d2 = np.full(L.EKF_JOINT_SEARCH_BEAM_MAX, np.nan) if want_alive else None
+        i64p = ctypes.POINTER(ctypes.c_int64)
+        self._check(self.lib.ekf_joint_search(self.h, arr, m, _p(thr), int(beam), ctypes.byref(res), match,
+                                              cand.ctypes.data_as(i64p) if want_candidates else None, _p(cand_d2) if want_candidates else None,
+                                              alive.ctypes.data_as(i64p) if want_alive else None, _p(alive_d2) if want_alive else None))
+        return marshal.joint_search_result(res, match, m, cand, cand_d2, alive, alive_d2)
+
     # ---- ... and applied as ONE joint update (include/ekfslam.h: ekf_observe_model_joint) ----
     def observe_model_joint(self, entries, landmarks, gate=float("inf"), want_nu=False, want_S=False, iterations=1, tol=0.0):
         """One hypothesis of joint_innovation APPLIED as one joint update: entries as for associate_model (the per-entry gate is not

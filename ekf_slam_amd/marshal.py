@@ -291,6 +291,30 @@ def assigned_result(out, match, m, total, cand=None, cand_d2=None):
     return res
 
 
+def joint_search_thresholds(thresholds, m):
+    """The 2m + 1 thresholds of ekf_joint_search, by dof, as one contiguous float64 array."""
+    thr = np.ascontiguousarray(np.asarray(thresholds, dtype=np.float64).reshape(-1))
+    if thr.size != 2 * m + 1:
+        raise ValueError("joint_search: thresholds has 2 m + 1 entries, one per dof 0 .. 2 m")
+    return thr
+
+
+def joint_search_result(res, match, m, cand=None, cand_d2=None, alive_hyp=None, alive_d2=None):
+    """What ekf_joint_search returned: the winner's 'landmark' (m, 0-based, -1 = left out), 'd2', 'dof', 'pairings', 'truncated' (bool),
+    'nalive', 'irregular' (extensions without a d2), 'tested' / 'survived' (m, by scan index), the keys of match_result -- its per-entry
+    count of landmarks without a d2 as 'match_irregular' -- and where given 'cand' / 'cand_d2' (m x EKF_ASSIGN_CANDIDATES) and 'alive'
+    (nalive x m) / 'alive_d2' (nalive): the final beam in order."""
+    out = {"landmark": np.array(res.lm[:m], dtype=np.int64), "d2": float(res.d2), "dof": int(res.dof), "pairings": int(res.pairings),
+           "truncated": bool(res.truncated), "nalive": int(res.nalive), "irregular": int(res.irregular),
+           "tested": np.array(res.tested[:m], dtype=np.int64), "survived": np.array(res.survived[:m], dtype=np.int64)}
+    out.update({("match_irregular" if key == "irregular" else key): val for key, val in match_result(match, m).items()})
+    if cand is not None:
+        out["cand"], out["cand_d2"] = cand, cand_d2
+    if alive_hyp is not None:
+        out["alive"], out["alive_d2"] = alive_hyp[:out["nalive"]].copy(), alive_d2[:out["nalive"]].copy()
+    return out
+
+
 def assigned_scan_result(out, res, m, total):
     """What ekf_assigned_scan_result reported of a scan, as arrays with one entry per observation: the assignment's 'landmark' (0-based, -1 =
     left out), 'd2', 'ncand' and the float 'total'; each step's 'nu' (m x 2), 'S' (m x 2 x 2), 'outcome' and 'step_d2'."""

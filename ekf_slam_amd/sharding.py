@@ -240,6 +240,11 @@ class ShardGroup:
         for e in self.shards:
             e.observe_model_assigned(entries)
 
+    def joint_search(self, entries, thresholds, beam=64, want_candidates=False, want_alive=False):
+        """Not built for a shard group: the cross blocks P(l_a, l_b) of a hypothesis live in other shards' tiles.  The call goes to the
+        first shard so that the refusal is the library's (EKF_ERR_INVALID_ARG, nothing changed)."""
+        return self.shards[0].joint_search(entries, thresholds, beam, want_candidates, want_alive)
+
     def run_threaded(self, fn):
         """fn(shard) on every shard, ONE HOST THREAD PER SHARD, with the exchange hook of transport (d) (include/ekfslam.h) set:
         wherever a library call needs an all-gather -- ekf_correct, ekf_prefetch_rows, the middle of ekf_measure's loop, a batch's

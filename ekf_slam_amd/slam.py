@@ -780,6 +780,26 @@ class _EkfBase:
         res["first_irregular"] = res["first_irregular"] + 1
         return res
 
+    def joint_search(self, entries, joint_p=0.99, beam=64, want_candidates=False, want_alive=False):
+        """The joint-compatibility SEARCH over a scan, on the device with one readback: entries as for assign_model (every gate finite: it
+        decides what a candidate is).  Level k extends every alive hypothesis by the 4 closest candidates of entry k and by "left out"; an
+        extension survives where its joint d2 <= chi2_quantile(joint_p, dof); survivors are ordered by (pairings descending, joint d2
+        ascending, hypothesis ascending) and cut at beam (at most EKF_JOINT_SEARCH_BEAM_MAX).  Returns the winner's 'landmark' (1-based,
+        0 = left out), 'd2', 'dof', 'pairings', 'truncated', 'nalive', 'irregular', 'tested' / 'survived' per entry, associate_model's
+        keys ('best' and 'second' 1-based, 0 = none; its 'irregular' as 'match_irregular') and, where asked, 'cand' / 'cand_d2' as assign_model returns them and 'alive' /
+        'alive_d2', the final beam in order (1-based, 0 = left out).  Every d2 is joint_innovation's d2_prefix for that hypothesis bit for
+        bit.  Changes and flushes nothing, so it is not logged (ekf_joint_search).  Unsharded handles only.  The reference has no such
+        method."""
+        joint_p = float(joint_p)
+        if not 0.0 < joint_p < 1.0:
+            raise ValueError("joint_search: joint_p lies strictly between 0 and 1")
+        entries = list(entries)
+        thresholds = [chi2_quantile(joint_p, dof) for dof in range(2 * len(entries) + 1)]
+        res = dict(self._e.joint_search(entries, thresholds, beam, want_candidates, want_alive))
+        for key in ("landmark", "best", "second") + (("cand",) if want_candidates else ()) + (("alive",) if want_alive else ()):
+            res[key] = res[key] + 1
+        return res
+
     def observe_model_joint(self, entries, landmarks, gate=float("inf"), want_nu=False, want_S=False, iterations=1, tol=0.0):
         """One hypothesis of joint_innovation APPLIED as ONE joint update: entries as for associate_model ([{'model', 'z', 'R'}, ...],
         models 1-4), landmarks the 1-based landmark each observation is paired with, 0 = left out.  All pairings are linearised once, at
@@ -807,7 +827,7 @@ class _EkfBase:
         return res
 
     def measure_model_joint(self, entries, gate_match, gate_new, joint_p=0.99, beam=64, wait=False, joint_update=False,
-                            device_candidates=False, joint_iterations=1, joint_tol=0.0):
+                            device_candidates=False, joint_iterations=1, joint_tol=0.0, device_search=False):
         """measure_model with the ambiguity discard replaced by a JOINT-compatibility search: entries, gate_match, gate_new and wait as
         there.  ONE associate_model(..., want_d2=True) call: the candidates of an entry are the landmarks with individual d2 <= gate_match,
         at most the 4 closest (by (d2, landmark)); an entry without a candidate is new where d2_best > gate_new (or the map is empty) and
@@ -822,7 +842,11 @@ class _EkfBase:
         search tested, one pass over P -- which is logged as well; joint_iterations > 1 (read only with joint_update=True) relinearises
         that update up to so many times, stopping at joint_tol (observe_model_joint's iterations and tol).  device_candidates=True takes the candidates and the best d2 from ONE
         assign_model(want_candidates=True) call instead: the same landmarks in the same order, so the outcome and the log are the same,
-        and the m x N matrix does not come back to the host."""
+        and the m x N matrix does not come back to the host.  device_search=True lets the DEVICE walk the search: ONE joint_search call
+        (gate = gate_match, thresholds chi2_quantile(joint_p, dof)) replaces both the candidate call and the level loop -- the same
+        candidates, tests and order, every d2 the same bits, so the winner, `truncated`, the state and the log are the default path's; the
+        kinds come from its match records (an entry has candidates where within_gate > 0).  beam is then at most
+        EKF_JOINT_SEARCH_BEAM_MAX (ValueError); device_candidates is not read."""
         gate_match, gate_new, joint_p = float(gate_match), float(gate_new), float(joint_p)
         if not gate_new >= gate_match:
             raise ValueError("measure_model_joint: gate_new >= gate_match is required (and neither is NaN)")
@@ -831,6 +855,14 @@ class _EkfBase:
         if int(beam) != beam or beam < 1:
             raise ValueError("measure_model_joint: beam is a whole number >= 1")
         entries, scan = self._measure_scan("measure_model_joint", entries, L.EKF_JOINT_MAX, gate_match)
+        if device_search:
+            if beam > L.EKF_JOINT_SEARCH_BEAM_MAX:
+                raise ValueError("measure_model_joint: with device_search the beam is at most EKF_JOINT_SEARCH_BEAM_MAX")
+            res = self._e.joint_search(scan, [chi2_quantile(joint_p, dof) for dof in range(2 * len(entries) + 1)], int(beam))
+            kinds = ["search" if int(res["within_gate"][k]) > 0 else
+                     "new" if int(res["best"][k]) < 0 or float(res["d2_best"][k]) > gate_new else "discarded" for k in range(len(entries))]
+            winner = {k: int(lm) for k, lm in enumerate(res["landmark"]) if int(lm) >= 0}
+            return self._measure_joint_close(entries, kinds, winner, res["truncated"], gate_match, wait, joint_update, joint_iterations, joint_tol)
         res = self._e.assign_model(scan, want_candidates=True) if device_candidates else self._e.associate_model(scan, want_d2=True)
         cands, kinds = [], []
         for k in range(len(entries)):
@@ -863,6 +895,11 @@ class _EkfBase:
             if len(alive) > beam:
                 alive, truncated = alive[:int(beam)], True
         winner = {k: c for k, c in zip(searched, alive[0][0]) if c >= 0} if searched else {}
+        return self._measure_joint_close(entries, kinds, winner, truncated, gate_match, wait, joint_update, joint_iterations, joint_tol)
+
+    def _measure_joint_close(self, entries, kinds, winner, truncated, gate_match, wait, joint_update, joint_iterations, joint_tol):
+        """measure_model_joint behind its search, whichever side walked it: the winner ({entry: 0-based landmark}) applied, the new entries
+        started, the rest discarded."""
         if joint_update and winner:
             # the winner's pairings in scan order as one joint update, then the close without them: the new entries and the discards
             self.observe_model_joint([dict(model=int(e[0]), z=e[1], R=e[2]) for e in (entries[k] for k in sorted(winner))],

@@ -738,6 +738,51 @@ int32_t ekf_joint_innovation(ekf_handle *h, const ekf_model_obs *obs, int64_t m,
                              double *d2_prefix       /* nh x m, may be NULL */,
                              double *nu              /* nh x 2m, may be NULL */,
                              double *S               /* nh x (2m x 2m column-major), may be NULL */);
+/* ... and SEARCHED: the joint-compatibility search that a caller otherwise walks with one ekf_assign_model call and one ekf_joint_innovation
+ * call per scan entry, as launches queued on the device with no host wait between them and ONE readback at the end.
+ *   candidates  entry k's are the first min(EKF_JOINT_SEARCH_CAND, ncand_k) landmarks of its ekf_assign_model candidate list (inside the
+ *               entry's gate, ordered by (d2, index)), read on the device from the buffer ekf_assign_model's second launch leaves.
+ *   levels      the scan indices 0 .. m-1 in order, from the empty hypothesis (d2 = 0, dof = 0).  At level k every alive hypothesis is
+ *               extended by each candidate of entry k it has not used yet, in list order, then by "left out".  An entry without
+ *               candidates extends every hypothesis by "left out" alone: nothing is tested (tested[k] = survived[k] = 0).
+ *   test        an extension survives where d2 <= threshold[dof], d2 its joint d2 and dof its real row count (ekf_joint_result.dof's
+ *               rule); NaN never survives.  "Left out" keeps its parent's d2 and dof and is tested like the rest.
+ *   order       survivors by (pairings descending, d2 ascending, hypothesis ascending: entry by entry in scan order on the 0-based
+ *               landmark, -1 for left out).  Where more than `beam` survive the first `beam` are kept and truncated is set; exactly
+ *               `beam` survivors is no cut.
+ *   winner      the first hypothesis in that order after the last level: there is always one, all entries left out.
+ * Every d2 the search forms is, BIT FOR BIT, the d2_prefix ekf_joint_innovation reports for that hypothesis at that scan index on the same
+ * state: a hypothesis's factor is its parent's with two rows appended, every entry seeing the right-looking factorisation's operations
+ * in their order.  An extension whose new pairing is irregular (ekf_joint_innovation's rule) has no d2, does not survive and is counted in
+ * `irregular`.
+ * match / cand / cand_d2 are ekf_assign_model's for the same scan, the same bits (ekf_model_match.within_gate == 0 says an entry has no
+ * candidate).  N == 0: no launch, the winner all -1, d2 = 0, nalive = 1, the lists empty as ekf_assign_model returns them.
+ * The call's place in a handle's order is ekf_joint_innovation's: settled, a recorded predict carried out first, no flush, ekf_pending and
+ * every bit of x, s and P as found, the cross blocks read patched with the pending pairs beside a pass in flight, and it waits for the
+ * event behind its own readback alone.  Launches count under EKF_KERNEL_ASSOCIATE: the candidate part once, as ekf_assign_model's; then
+ * the prepare launch and each level's two launches once each.  The search's scratch is allocated at the first call, kept, and reported by
+ * ekf_device_bytes.
+ * Refused in this order, with nothing done: ekf_assign_model's argument refusals in its order (res required where it requires out);
+ * threshold NULL or an entry of threshold[0 .. 2m] NaN, infinite or negative; beam outside 1 .. EKF_JOINT_SEARCH_BEAM_MAX; alive_hyp
+ * and alive_d2 not both given or both NULL (EKF_ERR_INVALID_ARG); then ekf_observe_linear's rungs as ekf_joint_innovation has them. */
+#define EKF_JOINT_SEARCH_CAND      4
+#define EKF_JOINT_SEARCH_BEAM_MAX  64
+typedef struct ekf_joint_search_result {
+    int64_t lm[EKF_JOINT_MAX];        /* the winner by scan index: 0-based landmark, -1 = left out (entries >= m: -1) */
+    double  d2;  int32_t dof, pairings;
+    int32_t truncated;                /* 1 where a level had more than `beam` survivors               */
+    int32_t nalive;                   /* hypotheses alive after the last level (after the cut)        */
+    int32_t irregular;                /* extensions that had no d2, over all levels                   */
+    int32_t tested[EKF_JOINT_MAX];    /* by scan index: extensions formed at that level               */
+    int32_t survived[EKF_JOINT_MAX];  /* ... that passed their threshold, before the cut              */
+} ekf_joint_search_result;
+int32_t ekf_joint_search(ekf_handle *h, const ekf_model_obs *obs, int64_t m,
+                         const double *threshold /* 2m + 1, by dof; finite, >= 0 */, int32_t beam,
+                         ekf_joint_search_result *res     /* required */,
+                         ekf_model_match *match           /* m, or NULL: ekf_assign_model's records, the same bits */,
+                         int64_t *cand, double *cand_d2   /* m x EKF_ASSIGN_CANDIDATES, both or neither: ekf_assign_model's lists */,
+                         int64_t *alive_hyp               /* EKF_JOINT_SEARCH_BEAM_MAX x m, or NULL: the final beam in order, -1 behind nalive rows */,
+                         double  *alive_d2                /* EKF_JOINT_SEARCH_BEAM_MAX, or NULL (NaN behind nalive) */);
 /* ... and APPLIED as a whole: one hypothesis of ekf_joint_innovation as ONE joint update.  All np paired observations are linearised once, at
  * the live state, and stacked; with L L' = S (the Cholesky factor of the stacked S), W = L^-1 H P (2 np rows) and y = L^-1 nu
  *     x' = x + W' y        P' = P - W' W

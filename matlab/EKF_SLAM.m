@@ -434,6 +434,19 @@ classdef EKF_SLAM < handle
                 res = h.gateway('joint_innovation', model, z, R, hyp);
             end
         end
+        function [res, lm, match] = jointSearch(h, model, z, R, gate, threshold, beam)
+            % The joint-compatibility SEARCH over a scan on the device, one wait: entries as for jointInnovation, gate the candidate gate of
+            % every entry (finite), threshold(dof + 1) the bound of a joint d2 with dof real rows (dof = 0 .. 2m, e.g. chi-square quantiles),
+            % beam at most 64 (default 64).  Level k extends every alive hypothesis by the 4 closest candidates of entry k and by "left out".
+            % res = [d2 dof pairings truncated nalive irregular] of the winner; lm(k): the landmark entry k is paired with, 0 = left out;
+            % match: one row [withinGate best d2Best] per entry (withinGate == 0: no candidate).  Changes and flushes nothing.  Not a method
+            % of the reference.
+            if nargin < 7, beam = 64; end
+            model = double(model(:)); m = numel(model);
+            z = double(reshape(z, [], 2));
+            R = double(R); if size(R, 3) == 1, R = repmat(R, [1 1 m]); end
+            [res, lm, match] = h.gateway('joint_search', model, z, R, double(gate), double(threshold(:)), double(beam));
+        end
         function res = observeModelJoint(h, model, z, R, lm, gate)
             % One hypothesis of jointInnovation APPLIED as one joint update: lm(k) is the landmark observation k (model(k), z(k, :),
             % R(:, :, k)) is paired with, 0 = left out.  All pairings are linearised once, at the live state, and stacked -- the update

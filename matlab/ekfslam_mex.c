@@ -43,6 +43,7 @@
 #pragma weak ekf_assign_model
 #pragma weak ekf_predict_model
 #pragma weak ekf_joint_innovation
+#pragma weak ekf_joint_search
 #pragma weak ekf_observe_model_iterated
 #pragma weak ekf_observe_model_joint
 #pragma weak ekf_observe_model_joint_iterated
@@ -62,6 +63,7 @@
 #define HAVE_ASSIGN_MODEL (ekf_assign_model != 0)
 #define HAVE_PREDICT_MODEL (ekf_predict_model != 0)
 #define HAVE_JOINT_INNOVATION (ekf_joint_innovation != 0)
+#define HAVE_JOINT_SEARCH (ekf_joint_search != 0)
 #define HAVE_OBSERVE_MODEL_ITERATED (ekf_observe_model_iterated != 0)
 #define HAVE_OBSERVE_MODEL_JOINT (ekf_observe_model_joint != 0)
 #define HAVE_OBSERVE_MODEL_JOINT_ITERATED (ekf_observe_model_joint_iterated != 0)
@@ -631,6 +633,56 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
         check(h, rc);
         plhs[0] = out;
         if (prefix) plhs[1] = prefix;
+        return;
+    }
+    if (!strcmp(cmd, "joint_search")) {           /* [res, lm, match] = (h, model m x 1 (1..4), z m x 2, R 2 x 2 x m, gate, threshold (2m + 1), beam): the
+                                                     joint-compatibility search on the device, one wait; gate: the candidate gate of every entry (finite);
+                                                     threshold(dof + 1) for dof 0 .. 2m; res 1 x 6 = [d2 dof pairings truncated nalive irregular];
+                                                     lm m x 1: the winner (1-based, 0 = left out); match (optional) m x 3 = [withinGate best d2Best] per
+                                                     entry (best 1-based, 0 = none): withinGate == 0 says the entry had no candidate */
+        need(nrhs, 8, cmd);
+        if (!HAVE_JOINT_SEARCH) mexErrMsgIdAndTxt("ekfslam:usage", "joint_search: this libekfslam has no ekf_joint_search");
+        const mwSize m = prhs[2] ? mxGetNumberOfElements(prhs[2]) : 0;
+        if (m < 1 || m > EKF_JOINT_MAX) mexErrMsgIdAndTxt("ekfslam:usage", "joint_search: between 1 and %d observations in one call", EKF_JOINT_MAX);
+        if (!mxGetPr(prhs[2]) || !prhs[3] || mxGetM(prhs[3]) != m || mxGetNumberOfElements(prhs[3]) != 2 * m || !mxGetPr(prhs[3]))
+            mexErrMsgIdAndTxt("ekfslam:usage", "joint_search: z needs m x 2 elements, one row per entry of model");
+        if (!prhs[4] || mxGetNumberOfElements(prhs[4]) != 4 * m || !mxGetPr(prhs[4]))
+            mexErrMsgIdAndTxt("ekfslam:usage", "joint_search: R needs 2 x 2 x m elements");
+        if (!prhs[5] || mxGetNumberOfElements(prhs[5]) != 1 || !mxGetPr(prhs[5]))
+            mexErrMsgIdAndTxt("ekfslam:usage", "joint_search: gate is one number");
+        if (!prhs[6] || mxGetNumberOfElements(prhs[6]) != 2 * m + 1 || !mxGetPr(prhs[6]))
+            mexErrMsgIdAndTxt("ekfslam:usage", "joint_search: threshold needs 2 m + 1 elements, one per dof 0 .. 2 m");
+        if (!prhs[7] || mxGetNumberOfElements(prhs[7]) != 1 || !mxGetPr(prhs[7]))
+            mexErrMsgIdAndTxt("ekfslam:usage", "joint_search: beam is one number");
+        const double beam = mxGetScalar(prhs[7]);
+        if (!(beam >= 1.0 && beam <= (double)EKF_JOINT_SEARCH_BEAM_MAX) || (double)(int32_t)beam != beam)
+            mexErrMsgIdAndTxt("ekfslam:usage", "joint_search: beam is a whole number between 1 and %d", EKF_JOINT_SEARCH_BEAM_MAX);
+        ekf_model_obs o[EKF_JOINT_MAX];
+        for (mwSize k = 0; k < m; ++k) {
+            o[k].model = (int32_t)mxGetPr(prhs[2])[k]; o[k].reserved = 0;
+            o[k].z[0] = mxGetPr(prhs[3])[k]; o[k].z[1] = mxGetPr(prhs[3])[m + k];       /* column-major m x 2 */
+            for (int q = 0; q < 4; ++q) o[k].R[q] = mxGetPr(prhs[4])[4 * k + q];
+            o[k].lm[0] = o[k].lm[1] = -1;
+            o[k].anchor[0] = o[k].anchor[1] = 0.0;
+            o[k].gate = mxGetScalar(prhs[5]);
+        }
+        ekf_joint_search_result res;
+        ekf_model_match match[EKF_JOINT_MAX];
+        check(h, ekf_joint_search(h, o, (int64_t)m, mxGetPr(prhs[6]), (int32_t)beam, &res, match, NULL, NULL, NULL, NULL));
+        plhs[0] = mxCreateDoubleMatrix(1, 6, mxREAL);
+        const double head[6] = { res.d2, (double)res.dof, (double)res.pairings, (double)res.truncated, (double)res.nalive, (double)res.irregular };
+        for (int q = 0; q < 6; ++q) mxGetPr(plhs[0])[q] = head[q];
+        if (nlhs > 1) {
+            plhs[1] = mxCreateDoubleMatrix(m, 1, mxREAL);
+            for (mwSize k = 0; k < m; ++k) mxGetPr(plhs[1])[k] = (double)(res.lm[k] + 1);
+        }
+        if (nlhs > 2) {
+            plhs[2] = mxCreateDoubleMatrix(m, 3, mxREAL);
+            for (mwSize k = 0; k < m; ++k) {
+                mxGetPr(plhs[2])[k] = (double)match[k].within_gate; mxGetPr(plhs[2])[m + k] = (double)(match[k].best + 1);
+                mxGetPr(plhs[2])[2 * m + k] = match[k].d2_best;
+            }
+        }
         return;
     }
     if (!strcmp(cmd, "observe_model_joint")) {    /* res = (h, model m x 1 (1..4), z m x 2, R 2 x 2 x m, lm m x 1, gate): the scan's pairings applied as ONE joint
