@@ -132,6 +132,15 @@ class EkfMotion(ctypes.Structure):
     _fields_ = [("model", _i32), ("reserved", _i32), ("u", _d * 3), ("M", _d * 9)]
 
 
+EKF_FACTOR_REF_MAX = 8                                # reference states of one ekf_factor_map call
+
+
+class EkfFactorInfo(ctypes.Structure):
+    """struct ekf_factor_info (include/ekfslam.h)."""
+    _fields_ = [("n", _i64), ("definite", _i32), ("bad_index", _i64), ("bad_pivot", _d), ("logdet", _d), ("logdet_map", _d),
+                ("min_pivot", _d), ("max_pivot", _d)]
+
+
 # name -> (restype, argtypes); every symbol of include/ekfslam.h
 SIGNATURES = {
     "ekf_abi_version": (_i32, []),
@@ -198,6 +207,7 @@ SIGNATURES = {
     "ekf_join_map": (_i32, [_vp, _vp, _d, ctypes.POINTER(_i64)]),
     "ekf_extract_map": (_i32, [_vp, ctypes.POINTER(_i64), _i64, _i32, _vp]),
     "ekf_transform_map": (_i32, [_vp, _i32, _dp, _dp]),
+    "ekf_factor_map": (_i32, [_vp, _dp, _i32, ctypes.POINTER(EkfFactorInfo), _dp]),
     "ekf_associate_model": (_i32, [_vp, ctypes.POINTER(EkfModelObs), _i64, ctypes.POINTER(EkfModelMatch), _dp]),
     "ekf_assign_model": (_i32, [_vp, ctypes.POINTER(EkfModelObs), _i64, ctypes.POINTER(EkfModelAssigned), ctypes.POINTER(EkfModelMatch),
                                 ctypes.POINTER(_i64), _dp, _dp]),

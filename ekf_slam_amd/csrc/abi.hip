@@ -17,6 +17,7 @@
 #include "host/join_map.h"     // a local submap joined into the map, its own cross-covariances kept: join_map
 #include "host/extract_map.h"  // part of the map taken out into another handle, in the map frame or the robot frame: extract_map
 #include "host/transform_map.h" // the whole map moved into another frame, in place: transform_map
+#include "host/factor_map.h"   // the Cholesky factorisation of P in a scratch store -- definiteness, log det, NEES: factor_map
 #include "host/associate_model.h" // which landmark a sighting belongs to, a scan per call: associate_model
 #include "host/assign_model.h" // ... and the scan assigned to the map one-to-one: assign_model
 #include "host/model_assigned.h" // ... and assigned, then applied step by step with no wait between: observe_model_assigned, assigned_scan_result

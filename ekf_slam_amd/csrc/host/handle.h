@@ -205,6 +205,12 @@ struct ekf_handle {
     // the device and in pinned memory, the snapshot of x / strip / Prr / the diagonal blocks it restores when a pair is irregular
     // (allocated at the first batch call and kept); ekf_observe_model_joint puts its pairs into the same ring (host/joint_update.h)
     double *d_mring = nullptr, *d_mrec = nullptr, *h_mrec = nullptr, *d_msnap = nullptr;
+    // ekf_factor_map: the factor store (F64 lower-triangle tiles of edge factor_tile_edge() for f_rows rows), and in ONE second allocation
+    // the right-hand sides, the result block with the pivots behind it and the reference states; the pinned images of the last two.
+    // Allocated at the first call for the N of that call, grown (freed and allocated anew) when N has outgrown them, released by
+    // ekf_destroy itself -- they are not in the registries below, which only ever grow.  f_bytes of them are counted in `bytes`.
+    double *d_ftiles = nullptr, *d_fsmall = nullptr, *h_fres = nullptr, *h_fref = nullptr;
+    int64_t f_rows = -1, f_bytes = 0;
     // ---- linear observations (ekf_observe_linear / ekf_linear_innovation) ----
     // two records on the device and in pinned memory (the update-step's, then the probe's; behind them in the pinned area the two counters
     // ekf_linear_rejections reads), the device counters of launches that did not apply, the event behind a waited step's readback

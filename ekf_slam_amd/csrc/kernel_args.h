@@ -142,6 +142,24 @@ struct TransformMapArgs {
     double Sigma[9];          // its covariance, row-major (symmetric)
 };
 
+// k_factor_* (factor_map.h): the Cholesky factorisation of P of a flushed handle in a scratch store of its own -- F64 lower-triangle tiles
+// of edge tm.T under their own tile map (world = 1), whatever the handle's tile edge and storage kind are.  Nothing of the state is written.
+constexpr int kFactorRefMax = 8;                  // reference states of one call
+constexpr int kFactorRhs = 3 + kFactorRefMax + 1; // doubles per row of the right-hand sides: the strip's three, one per reference, one of padding
+constexpr int kFactorRes = 16;                    // doubles of the result block (factor_map.h: k_factor_finish); the pivots follow it
+struct FactorMapArgs {
+    double *tiles;            // the factor store: row_base(rows / tm.T) tiles
+    double *rhs;              // rows x kFactorRhs, row-major
+    double *res;              // kFactorRes doubles of status and results (cleared before the first launch), then `rows` pivots (the diagonal of L)
+    const double *ref;        // nref reference states on the device, ref_stride doubles apart (nullptr with nref == 0)
+    TileMap tm;               // of the factor store
+    int64_t N;                // landmarks
+    int64_t rows;             // 2 N rounded up to whole tile rows of the factor store
+    int64_t ref_stride;
+    int32_t nref;             // 0 .. kFactorRefMax
+    int32_t cur;              // the live buffer of x, Prr and the strip (the diagonal copies: dcur of the DevState)
+};
+
 // k_predict_model (predict_model.h): a chain of m <= kPredictModelMax motion steps through the models of ekfm::motion_eval, carried out in
 // order by ONE launch that reads buffer cur and writes buffer cur ^ 1, as k_predict.  No tile is read: the storage type does not matter.
 // The steps travel in the argument block, M as its six unique entries -- 80 bytes a step, 2.5 KiB at 32 (nine entries a step would not fit

@@ -54,6 +54,16 @@ hipError_t launch_extract_rows(const DevState &dst, const DevState &src, const E
 hipError_t launch_transform_state(const DevState &st, const TransformMapArgs &a, hipStream_t s);
 hipError_t launch_transform_tiles(const DevState &st, const TransformMapArgs &a, const int2 *work, int64_t ntiles, int storage, hipStream_t s);
 
+// k_factor_* (factor_map.h): P of the flushed state `st` factored in the scratch store `a` names -- read-only on st.  The caller queues the
+// whole right-looking blocked Cholesky with no host wait: launch_factor_load (the tiles and the right-hand sides; unsharded tile maps only),
+// then per tile column k = 0 .. a.rows / a.tm.T - 1 launch_factor_column's three parts in order (the last column has parts 1 and 2 empty),
+// then launch_factor_finish (the reductions and the 3 x 3 tail).  a.res must be cleared in front of them (stream order); every launch
+// returns at once when a.res[0] says that a pivot failed.  factor_tile_edge(): the edge of the factor store's tiles (the one that is built).
+int factor_tile_edge();
+hipError_t launch_factor_load(const DevState &st, const FactorMapArgs &a, int storage, hipStream_t s);
+hipError_t launch_factor_column(const FactorMapArgs &a, int k, int part, hipStream_t s);      // part 0: diagonal, 1: panel, 2: trailing update
+hipError_t launch_factor_finish(const DevState &st, const FactorMapArgs &a, hipStream_t s);
+
 // fused_predict != nullptr folds predict(u) into the correction (one launch instead of two, identical arithmetic)
 // fuse_downdate: the kernel also applies its pair to the landmark block (small maps: a.n_mm <= gather_fuse_max_rows(), one
 // workgroup); the pair is then NOT written to the pending ring and no downdate launch must follow

@@ -61,6 +61,7 @@ namespace {
 #include "joint_iter.h"       // ... relinearised: k_joint_factor_iter
 #include "merge_pass.h"       // the fused downdate-and-compact pass of a batch of merges: k_merge_pass
 #include "nearest.h"          // the candidate search in front of a merge: k_nearest
+#include "factor_map.h"       // the Cholesky factorisation of P in a scratch store: k_factor_load / _rhs / _diag / _panel / _trail / _finish
 
 }  // namespace
 
@@ -69,5 +70,5 @@ namespace {
 #include "launch/steps.h"         // predict, append, gather, row-panels, association
 #include "launch/pass_select.h"   // which pass instance runs: a pure function, no HIP
 #include "launch/passes.h"        // launch_downdate, the row copies behind an asynchronous pass
-#include "launch/edits.h"         // compact, constrain, linear observation, joint innovation, joint search and joint update, merge pass, nearest
+#include "launch/edits.h"         // compact, constrain, linear observation, joint innovation, joint search and joint update, merge pass, nearest, the factorisation
 #include "launch/state_io.h"      // dense <-> tiled, block reads, low-rank load, digest

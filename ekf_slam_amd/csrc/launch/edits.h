@@ -289,3 +289,48 @@ hipError_t launch_nearest(const DevState &st, int cur, int64_t N, const double R
         hipLaunchKernelGGL(k_nearest<decltype(ts)>, dim3((unsigned)grid), dim3(kBlock), 0, s, st, cur, N, R[0], R[1], R[2], R[3], out);
     });
 }
+
+// ---- the factorisation of P (factor_map.h) ----
+// The factor store's tile edge.  64: a diagonal tile and the right-hand sides take 40 KiB of LDS, a lane of k_factor_panel holds a whole
+// row in registers, a workgroup of k_factor_trail is four wavefronts with no LDS at all.  Edge 128 (a 128 KiB diagonal tile) is not built.
+constexpr int kFactorTile = 64;
+int factor_tile_edge() { return kFactorTile; }
+
+namespace {
+bool factor_args_ok(const FactorMapArgs &a) {
+    return a.tiles && a.rhs && a.res && a.N >= 0 && a.tm.T == kFactorTile && a.tm.world == 1 && a.rows == a.tm.padded(2 * a.N) &&
+           a.nref >= 0 && a.nref <= kFactorRefMax && (a.nref == 0 || (a.ref && a.ref_stride >= 3 + 2 * a.N)) && (a.cur == 0 || a.cur == 1);
+}
+}  // namespace
+
+hipError_t launch_factor_load(const DevState &st, const FactorMapArgs &a, int storage, hipStream_t s) {
+    // every tile of the source is read from this handle's store (an unsharded tile map), every landmark below 2 N lies inside it
+    if (!factor_args_ok(a) || st.tm.world != 1 || 2 * a.N > st.ldm) return hipErrorInvalidValue;
+    if (a.rows == 0) return hipSuccess;
+    const int64_t ntiles = a.tm.row_base(a.rows / kFactorTile);
+    if (ntiles > 0x7fffffffll) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_factor_rhs, dim3((unsigned)cdiv(a.rows, (int64_t)kFactorBlock)), dim3(kFactorBlock), 0, s, st, a);
+    return with_storage(storage, [&](auto ts) {
+        hipLaunchKernelGGL((k_factor_load<decltype(ts), kFactorTile>), dim3((unsigned)ntiles), dim3(kFactorBlock), 0, s, st, a);
+    });
+}
+
+hipError_t launch_factor_column(const FactorMapArgs &a, int k, int part, hipStream_t s) {
+    const int64_t nF = a.rows / kFactorTile, m = nF - 1 - k;
+    if (!factor_args_ok(a) || k < 0 || k >= nF || part < 0 || part > 2) return hipErrorInvalidValue;
+    if (part == 0) hipLaunchKernelGGL(k_factor_diag<kFactorTile>, dim3(1), dim3(kFactorBlock), 0, s, a, k);
+    else if (m == 0) return hipSuccess;
+    else if (part == 1) hipLaunchKernelGGL(k_factor_panel<kFactorTile>, dim3((unsigned)m), dim3(64), 0, s, a, k);
+    else {
+        const int64_t grid = m * (m + 1) / 2;
+        if (grid > 0x7fffffffll) return hipErrorInvalidValue;
+        hipLaunchKernelGGL(k_factor_trail<kFactorTile>, dim3((unsigned)grid), dim3(4 * kFactorTile), 0, s, a, k);
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_factor_finish(const DevState &st, const FactorMapArgs &a, hipStream_t s) {
+    if (!factor_args_ok(a)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_factor_finish, dim3(1), dim3(kFactorBlock), 0, s, st, a);
+    return hipGetLastError();
+}

@@ -528,6 +528,22 @@ class Engine:
         frame, tv, Sv = args
         self._check(self.lib.ekf_transform_map(self.h, frame, marshal.p_or_null(tv), marshal.p_or_null(Sv)))
 
+    # ---- the factorisation of P: definiteness, log det, NEES (include/ekfslam.h: ekf_factor_map) ----
+    def factor_map(self, ref=None):
+        """One Cholesky factorisation of P on the device -- of exactly what get_P() would report, the landmark block eliminated first
+        (rows ascending), the robot last.  Returns a dict: n = 3 + 2 N, definite, bad_index (-1, or the index into x of the first pivot
+        that failed in that order: 3 + r for landmark row r, 0 .. 2 for the robot), bad_pivot, logdet (NaN where not definite),
+        logdet_map (the landmark block alone), min_pivot, max_pivot, and d2: for each of the 1 to 8 reference states in `ref` (one
+        state, or one per row) nu' P^-1 nu with nu = x - ref, the heading entry wrapped into (-180, 180]; NaN where not definite.
+        A P that is not definite is a result, not an error.  Read-only and synchronising: pending is 0 afterwards; nothing is kept
+        between calls (ekf_factor_map)."""
+        return self._factor_map(marshal.factor_args(ref, 3 + 2 * self.N))
+
+    def _factor_map(self, args):
+        ref, nref, info, d2 = args
+        self._check(self.lib.ekf_factor_map(self.h, marshal.p_or_null(ref), nref, ctypes.byref(info), marshal.p_or_null(d2)))
+        return marshal.factor_result(args)
+
     @staticmethod
     def model_invert(model, xr, z, lib=None):
         """(t, Gx, Gz): the landmark that z observes from the robot state xr = (x, y, theta in degrees) through EKF_MODEL_RANGE_BEARING

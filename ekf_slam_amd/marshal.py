@@ -196,6 +196,35 @@ def transform_args(frame, t, Sigma, who="transform_map"):
     return ctypes.c_int32(frames[frame]), tv, Sv
 
 
+def factor_args(ref, n, who="factor_map"):
+    """(ref or None, nref, info, d2 or None) of factor_map as the ABI takes them, the arrays kept so that factor_result reads what the
+    call wrote.  ref: None, one reference state of n = 3 + 2 N finite entries, or 1 to 8 of them as the rows of a 2-D array.  Anything
+    else is refused here, before any call."""
+    info = L.EkfFactorInfo()
+    if ref is None:
+        return None, ctypes.c_int32(0), info, None
+    rv = np.ascontiguousarray(np.asarray(ref, dtype=np.float64))
+    if rv.ndim == 1:
+        rv = rv.reshape(1, -1)
+    if rv.ndim != 2 or not 1 <= rv.shape[0] <= L.EKF_FACTOR_REF_MAX:
+        raise ValueError("%s: ref is 1 to %d reference states, one per row" % (who, L.EKF_FACTOR_REF_MAX))
+    if rv.shape[1] != n:
+        raise ValueError("%s: a reference state has 3 + 2 N = %d entries, got %d" % (who, n, rv.shape[1]))
+    if not np.all(np.isfinite(rv)):
+        raise ValueError("%s: ref is not finite" % who)
+    return rv, ctypes.c_int32(rv.shape[0]), info, np.full(rv.shape[0], np.nan)
+
+
+def factor_result(args):
+    """What factor_map returns from what the call wrote: the fields of ekf_factor_info by name, and 'd2' -- one entry per reference
+    state, empty without any."""
+    _, _, info, d2 = args
+    out = dict(n=int(info.n), definite=bool(info.definite), bad_index=int(info.bad_index), bad_pivot=float(info.bad_pivot),
+               logdet=float(info.logdet), logdet_map=float(info.logdet_map), min_pivot=float(info.min_pivot), max_pivot=float(info.max_pivot))
+    out["d2"] = np.zeros(0) if d2 is None else d2
+    return out
+
+
 def model_inits(entries, who="append_model"):
     """(ekf_model_init[], m) of a scan of new landmarks [(model, z, R, signature), ...]."""
     entries = list(entries)

@@ -160,6 +160,11 @@ class ShardGroup:
         call goes to the first shard so that the refusal is the library's (EKF_ERR_INVALID_ARG, nothing changed)."""
         return self.shards[0].transform_map(frame, t, Sigma)
 
+    def factor_map(self, ref=None):
+        """Not built for a shard group: the factorisation reads and updates every tile of the lower triangle, and every shard holds only
+        its own.  The call goes to the first shard so that the refusal is the library's (EKF_ERR_INVALID_ARG, nothing changed)."""
+        return self.shards[0].factor_map(ref)
+
     def correct(self, z, R, idx0):
         for e in self.shards:
             e.correct_begin(z, R, idx0)

@@ -273,6 +273,36 @@ class _EkfBase:
         2 degrees of freedom), 1-based, j < i, sorted by (d2, i)."""
         return [(i + 1, j + 1, d2) for i, j, d2 in self._e.duplicate_candidates(gate, R)]
 
+    def factor_map(self, ref=None):
+        """The Cholesky factorisation of P on the device as a dict: definite, bad_index, bad_pivot, logdet, logdet_map, min_pivot,
+        max_pivot and d2 per reference state (Engine.factor_map; ekf_factor_map).  Read-only: nothing goes into the trajectory log.
+        For a SUBSET of the landmarks, extract_map them first and call factor_map on the small filter.  The reference has no such
+        method."""
+        return self._e.factor_map(ref)
+
+    def nees(self, x_true):
+        """(d2, dof): the normalised estimation error squared (x - x_true)' P^-1 (x - x_true) of the whole state against the ground
+        truth x_true (3 + 2 N entries, the heading difference wrapped), and its degrees of freedom 3 + 2 N -- the standard consistency
+        measure of EKF-SLAM.  NaN where P is not positive definite (factor_map says where)."""
+        res = self._e.factor_map(np.asarray(x_true, dtype=np.float64).reshape(-1))
+        return float(res["d2"][0]), res["n"]
+
+    def nees_within(self, x_true, p=0.95):
+        """(inside, d2, (lo, hi)): whether nees(x_true) lies inside the two-sided chi-square interval of probability p for 3 + 2 N degrees
+        of freedom, lo = chi2_quantile((1 - p) / 2, dof) and hi = chi2_quantile((1 + p) / 2, dof).  Below lo the filter is too
+        cautious, above hi it is overconfident; a P that is not definite is outside."""
+        if not 0.0 < float(p) < 1.0:
+            raise ValueError("nees_within: 0 < p < 1")
+        d2, dof = self.nees(x_true)
+        lo, hi = chi2_quantile(0.5 * (1.0 - float(p)), dof), chi2_quantile(0.5 * (1.0 + float(p)), dof)
+        return bool(lo <= d2 <= hi), d2, (lo, hi)
+
+    def map_entropy(self):
+        """The differential entropy of the Gaussian the filter carries, 1/2 (n log(2 pi e) + log det P) in nats with n = 3 + 2 N: what an
+        exploration planner or a 'is this submap worth keeping' policy ranks by.  NaN where P is not positive definite."""
+        res = self._e.factor_map()
+        return 0.5 * (res["n"] * math.log(2.0 * math.pi * math.e) + res["logdet"])
+
     def fuse_duplicates(self, gate, R=None, max_merges=None):
         """The SIMPLEST complete fusion policy, not the fastest: repeat { search; take the candidate with the smallest (d2, i) at or
         below `gate`; merge_landmarks(keep=j, drop=i, R) } until none is left or `max_merges` merges were made.  One search plus

@@ -594,6 +594,51 @@ int32_t ekf_extract_map(ekf_handle *h, const int64_t *idx, int64_t m, int32_t fr
  * not finite, not symmetric, or with a negative diagonal entry or a negative leading principal minor, EKF_FRAME_ROBOT with t or Sigma given,
  * a sharded handle (world > 1) (EKF_ERR_INVALID_ARG); a sharded correction between begin and finish (EKF_ERR_STATE). */
 int32_t ekf_transform_map(ekf_handle *h, int32_t frame, const double t[3] /* EKF_FRAME_ROBOT: NULL */, const double Sigma[9] /* may be NULL */);
+/* THE FACTORISATION OF P: is the matrix `h` carries still a covariance (float tiles, split arithmetic and thousands of downdates can leave
+ * it indefinite), what is its log determinant (the entropy of the map), and what is the normalised estimation error squared (NEES) of x
+ * against a reference state -- all three from ONE Cholesky factorisation P = L L' on the device, of exactly the matrix ekf_get_P would
+ * report at that moment: the tiles (float tiles widened to F64), every landmark's own 2 x 2 block from the live F64 copy, rows at and
+ * beyond 2 N left out.  All arithmetic and the factor are F64 for every storage kind.
+ *   ELIMINATION ORDER: THE LANDMARK BLOCK FIRST, in ascending row order (index 3, 4, .. of x), THE ROBOT LAST (index 0, 1, 2).  So
+ *   P(4:end, 4:end) = L L' is a factorisation of the landmark block alone, and the robot is a 3 x 3 tail: W = L^-1 P(4:end, 1:3),
+ *   S_r = P(1:3, 1:3) - W' W, S_r = L_r L_r'.  A pivot is the value under the square root: it fails when it is <= 0 or not finite.
+ *   Determinant, definiteness and d2 do not depend on the order; bad_index does: it is the FIRST pivot that fails IN THIS ORDER.
+ * info (always written on EKF_OK):
+ *   n           3 + 2 N
+ *   definite    1: every pivot was > 0 and finite; 0: the factorisation stopped at bad_index
+ *   bad_index   -1, or the index into x of the pivot that failed: 3 + r for row r of the landmark block, 0 .. 2 for the robot
+ *   bad_pivot   that pivot's value (0.0, negative, NaN or infinite); 0.0 where definite
+ *   logdet      log det P = 2 sum log L_ii, summed on the host in elimination order; NaN where not definite
+ *   logdet_map  log det of the landmark block alone (0 for N = 0); NaN only where a LANDMARK pivot failed
+ *   min_pivot, max_pivot   the smallest and the largest L_ii^2 over the pivots taken (NaN when none was taken)
+ * A filter that starts at a known pose has P(1:3, 1:3) = 0: the call reports definite = 0, bad_index = 0, bad_pivot = 0.0 and a valid
+ * logdet_map.  That is a result (EKF_OK), not an error.
+ * ref: NULL, or nref (1 .. 8) reference states of 3 + 2 N finite entries each, one after another; then d2[q] = nu' P^-1 nu with
+ * nu = x - ref_q, its heading entry (degrees) wrapped into (-180, 180]; NaN where P is not definite.  The solve rides the factorisation:
+ * the strip and the nu's are right-hand sides of its forward substitution.
+ * A right-looking blocked Cholesky in a scratch store the handle owns: F64 lower-triangle tiles of edge 64 whatever the handle's tile edge
+ * is, 8 (n^2 / 2 + 12 n) bytes, allocated at the first call for the N of that call, grown when N has outgrown it, counted by
+ * ekf_device_bytes and released by ekf_destroy.  Per tile column: the diagonal tile in LDS by one workgroup, the panel below it, the
+ * trailing update on the F64 matrix cores; nothing waits in between and one readback ends the call.  A pivot that fails makes every later
+ * launch return at once.  Launches count under EKF_KERNEL_COMPACT (load, right-hand sides, tail), EKF_KERNEL_GATHER (diagonal tiles and
+ * panels, one count per column) and EKF_KERNEL_DOWNDATE (trailing updates).
+ * A SYNCHRONISING, READ-ONLY call like ekf_nearest_landmarks: the measure loop settled, a recorded predict carried out, pending pairs
+ * applied, an asynchronous pass retired; ekf_pending is 0 afterwards, and x, s, P, the diagonal blocks and ekf_P_digest are bit for bit
+ * those of a handle that only flushed.  Nothing is kept between calls: every call factors.
+ * Refused with nothing changed and nothing flushed: h or info NULL, ref given with nref outside 1 .. 8 or without d2, a handle with
+ * world > 1 (sharding: every shard holds only its own tiles; a lone shard with cfg.force_sharded works) (EKF_ERR_INVALID_ARG); a sharded
+ * correction between begin and finish (EKF_ERR_STATE); then, once N is exact, a ref entry that is not finite (EKF_ERR_INVALID_ARG);
+ * EKF_ERR_HIP if the scratch store cannot be allocated, before anything is queued. */
+typedef struct ekf_factor_info {
+    int64_t n;
+    int32_t definite;
+    int64_t bad_index;
+    double bad_pivot;
+    double logdet;
+    double logdet_map;
+    double min_pivot, max_pivot;
+} ekf_factor_info;
+int32_t ekf_factor_map(ekf_handle *h, const double *ref /* nref x (3 + 2N), may be NULL */, int32_t nref, ekf_factor_info *info, double *d2 /* nref */);
 /* The step between the two: "WHICH landmark does this sighting belong to?", for a whole scan, under the conventions of ekf_observe_model.
  * ekf_associate keeps the reference's (signature-only by default, an unwrapped bearing, a range-scaled R) and cannot serve a filter
  * driven through the model calls.  For each of the m observations, d2(k, i) is, BIT FOR BIT, the d2 that ekf_model_innovation reports for

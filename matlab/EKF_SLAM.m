@@ -278,6 +278,18 @@ classdef EKF_SLAM < handle
             % shape joinMap expects of a local map.  Bit for bit extractMap(1:N, 'robot', dst), without a second object.
             h.gateway('transform_map', 1, [], []);
         end
+        function [info, d2] = factorMap(h, ref)
+            % THE FACTORISATION OF P: one Cholesky factorisation of the covariance on the GPU, of exactly what getP would return, the
+            % landmark block eliminated first (rows ascending), the robot last.  info is a struct: n, definite, bad_index (0, or the
+            % 1-based index into x of the first pivot that failed in that order), bad_pivot, logdet (NaN where P is not positive
+            % definite), logdet_map (the landmark block alone), min_pivot, max_pivot.  ref (left out or empty: none): n x q reference
+            % states as columns, q = 1 .. 8; d2(k) = (x - ref(:,k))' * inv(P) * (x - ref(:,k)) with the heading difference wrapped --
+            % the NEES against ground truth.  Read-only.  Not a method of the reference.
+            if nargin < 2, ref = []; end
+            [v, d2] = h.gateway('factor_map', double(ref));
+            info = struct('n', v(1), 'definite', v(2) ~= 0, 'bad_index', v(3), 'bad_pivot', v(4), 'logdet', v(5), 'logdet_map', v(6), ...
+                          'min_pivot', v(7), 'max_pivot', v(8));
+        end
         function idx = addLandmarkRangeBearing(h, z, R, signature)
             % 'A landmark that is not in the map yet is seen at range z(1) and bearing z(2) (degrees, relative to the heading),
             % covariance R': it joins the map at the point that observation names.

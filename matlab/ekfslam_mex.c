@@ -27,7 +27,7 @@
  * (ekf_observe_model), the append through a model (ekf_append_model), the association of a scan under the models' conventions
  * (ekf_associate_model) and its one-to-one assignment (ekf_assign_model), the joint compatibility of a scan's pairings (ekf_joint_innovation) and their joint update
  * (ekf_observe_model_joint, relinearised: ekf_observe_model_joint_iterated), the relinearised model observation
- * (ekf_observe_model_iterated), the motion steps under them (ekf_predict_model), the join of a local map (ekf_join_map), the extraction of part of the map (ekf_extract_map) and the map's change of frame (ekf_transform_map) are the ones this gateway can live without: bound weakly, so that the gateway still links against a libekfslam (or a stand-in) that
+ * (ekf_observe_model_iterated), the motion steps under them (ekf_predict_model), the join of a local map (ekf_join_map), the extraction of part of the map (ekf_extract_map), the map's change of frame (ekf_transform_map) and the factorisation of P (ekf_factor_map) are the ones this gateway can live without: bound weakly, so that the gateway still links against a libekfslam (or a stand-in) that
  * predates them; their commands then raise a MATLAB error instead. */
 #if defined(__GNUC__)
 #pragma weak ekf_remove_landmarks
@@ -50,6 +50,7 @@
 #pragma weak ekf_join_map
 #pragma weak ekf_extract_map
 #pragma weak ekf_transform_map
+#pragma weak ekf_factor_map
 #define HAVE_REMOVE_LANDMARKS (ekf_remove_landmarks != 0)
 #define HAVE_CONSTRAIN_LANDMARKS (ekf_constrain_landmarks != 0)
 #define HAVE_MERGE_LANDMARKS (ekf_merge_landmarks != 0)
@@ -70,6 +71,7 @@
 #define HAVE_JOIN_MAP (ekf_join_map != 0)
 #define HAVE_EXTRACT_MAP (ekf_extract_map != 0)
 #define HAVE_TRANSFORM_MAP (ekf_transform_map != 0)
+#define HAVE_FACTOR_MAP (ekf_factor_map != 0)
 #else
 #define HAVE_REMOVE_LANDMARKS 1
 #define HAVE_CONSTRAIN_LANDMARKS 1
@@ -90,6 +92,7 @@
 #define HAVE_JOIN_MAP 1
 #define HAVE_EXTRACT_MAP 1
 #define HAVE_TRANSFORM_MAP 1
+#define HAVE_FACTOR_MAP 1
 #endif
 
 static void need(int nrhs, int want, const char *cmd) {
@@ -486,6 +489,27 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
         if (frame == 1 ? (nt != 0 || ns != 0) : (nt != 3 || !mxGetPr(prhs[3]) || (ns != 0 && (ns != 9 || !mxGetPr(prhs[4])))))
             mexErrMsgIdAndTxt("ekfslam:usage", "transform_map: frame 0 takes t (3 values) and Sigma (3 x 3 or empty), frame 1 takes both empty");
         check(h, ekf_transform_map(h, frame, nt ? mxGetPr(prhs[3]) : NULL, ns ? mxGetPr(prhs[4]) : NULL));      /* (MATLAB arrays are column-major) */
+        return;
+    }
+    if (!strcmp(cmd, "factor_map")) {             /* [info, d2] = (h, ref): the Cholesky factorisation of P on the device.  ref: empty, or n x q (q = 1 .. 8)
+                                                     reference states as columns, n = 3 + 2 N.  info = [n definite bad_index bad_pivot logdet logdet_map
+                                                     min_pivot max_pivot], bad_index 1-based into x and 0 = none; d2: q x 1 (0 x 1 without ref) */
+        ekf_factor_info info;
+        need(nrhs, 3, cmd);
+        if (!HAVE_FACTOR_MAP) mexErrMsgIdAndTxt("ekfslam:usage", "factor_map: this libekfslam has no ekf_factor_map");
+        const int64_t n = nstate(h);
+        const mwSize nel = prhs[2] ? mxGetNumberOfElements(prhs[2]) : 0;
+        const mwSize q = nel / (mwSize)n;
+        if (nel != 0 && (!mxGetPr(prhs[2]) || q * (mwSize)n != nel || q < 1 || q > 8))
+            mexErrMsgIdAndTxt("ekfslam:usage", "factor_map: ref is empty or n x q, n = 3 + 2 N entries a column and q = 1 .. 8 columns");
+        mxArray *d2 = mxCreateDoubleMatrix(q, 1, mxREAL);
+        const int32_t rc = ekf_factor_map(h, nel ? mxGetPr(prhs[2]) : NULL, (int32_t)q, &info, nel ? mxGetPr(d2) : NULL);
+        if (rc != EKF_OK) { mxDestroyArray(d2); check(h, rc); }
+        plhs[0] = mxCreateDoubleMatrix(1, 8, mxREAL);
+        double *o = mxGetPr(plhs[0]);
+        o[0] = (double)info.n; o[1] = (double)info.definite; o[2] = (double)(info.bad_index + 1); o[3] = info.bad_pivot;
+        o[4] = info.logdet; o[5] = info.logdet_map; o[6] = info.min_pivot; o[7] = info.max_pivot;
+        if (nlhs > 1) plhs[1] = d2; else mxDestroyArray(d2);
         return;
     }
     if (!strcmp(cmd, "associate_model")) {        /* [match, d2] = (h, model m x 1 (1..4), z m x 2, R 2 x 2 x m, gate m x 1): which landmark each sighting of a
