@@ -21,6 +21,9 @@ tests/test_oracle_factored.py) follow.  Compared: x, the digests, every landmark
 landmark per tile row and of EVERY landmark append_model added.  From the oracle alone: two batches move every tile of the sampled rows,
 and every appended row has in every tile column of the map before it an entry, of at least 20x the row tolerance.
 
+The entry points added since (the joint updates, join / extract / transform / factor_map, observe_model_assigned, assign_model,
+joint_search) meet a pass in flight in tests/test_beside_pass_newer_gpu.py, which reuses _engines and _passes.
+
 Sizes and the measured premise (MI355X): see MEASURED below."""
 import time
 
