@@ -219,7 +219,8 @@ __global__ __launch_bounds__(4 * TF) void k_factor_trail(FactorMapArgs a, int k)
 // pairwise tree in LDS: a fixed order for a given `rows`.  sums: W'W as (00, 10, 11, 20, 21, 22), then per reference (W'w)_0..2, |w|^2.
 // Lane 0 then takes the 3 x 3 tail in the order robot 0, 1, 2 and writes the result block:
 //   res[0] status, res[1] index into x and res[2] value of the pivot that failed, res[3..5] the tail's diagonal of L_r, res[6] how many
-//   of them were taken, res[8 + q] d2 of reference q.
+//   of them were taken, res[8 + q] d2 of reference q.  Where a.lr_off is given and the tail was taken whole, L_r's entries below the
+//   diagonal go there, (1,0), (2,0), (2,1): the result block has no room for them, and nothing in it moves.
 __global__ __launch_bounds__(kFactorBlock) void k_factor_finish(DevState st, FactorMapArgs a) {
     __shared__ double red[kFactorBlock];
     __shared__ double sums[kFactorSums];
@@ -270,6 +271,7 @@ __global__ __launch_bounds__(kFactorBlock) void k_factor_finish(DevState st, Fac
     }
     a.res[3] = l00; a.res[4] = l11; a.res[5] = l22; a.res[6] = (double)taken;
     if (taken < 3) { a.res[1] = (double)taken; a.res[2] = d; a.res[0] = 2.0; return; }
+    if (a.lr_off) { a.lr_off[0] = l10; a.lr_off[1] = l20; a.lr_off[2] = l21; }      // (ekf_sample_map: the rest of L_r)
     for (int q = 0; q < a.nref; ++q) {
         const double *__restrict__ x = st.x[a.cur], *__restrict__ ref = a.ref + q * a.ref_stride;
         const double t0 = (x[0] - ref[0]) - sums[6 + 4 * q], t1 = (x[1] - ref[1]) - sums[7 + 4 * q];

@@ -4,8 +4,12 @@
 // ekf_nearest_landmarks: a recorded predict carried out, the pending pairs applied, an asynchronous pass retired; x, s, P, the diagonal
 // copies and the digest are afterwards those of a handle that only flushed.  No invalidation function is called and nothing is kept
 // between calls: every call factors.  Unsharded only: the load reads every tile, and a shard holds only its own.
+// ekf_sample_map is the same factorisation (factor_run below is the body of both) with the draws x + C xi queued behind it, a chunk of
+// factor_chunk() draws at a time through pinned staging that does not grow with the number of draws.
 #pragma once
 namespace {
+constexpr int kSampleSlots = 4;            // chunks of pinned staging per direction (ekf_handle::ev_fslot)
+
 void factor_release(ekf_handle *h) {
     if (h->d_ftiles) hipFree(h->d_ftiles);
     if (h->d_fsmall) hipFree(h->d_fsmall);
@@ -15,12 +19,25 @@ void factor_release(ekf_handle *h) {
     h->bytes -= h->f_bytes;
     h->f_bytes = 0;
     h->f_rows = -1;
+    // the draws' part
+    if (h->d_fsample) hipFree(h->d_fsample);
+    if (h->h_fxi) hipHostFree(h->h_fxi);
+    if (h->h_fy) hipHostFree(h->h_fy);
+    h->d_fsample = h->h_fxi = h->h_fy = nullptr;
+    h->bytes -= h->fs_bytes;
+    h->fs_bytes = 0;
+    h->fs_rows = -1;
 }
 
-// doubles of the second allocation for `rows` rows: the right-hand sides, the result block and the pivots, the reference states
+// doubles of the second allocation for `rows` rows: the right-hand sides, the result block and the pivots, the reference states, L_r's
+// entries below the diagonal (three, and one of padding)
 size_t factor_rhs_doubles(int64_t rows) { return (size_t)rows * kFactorRhs; }
 size_t factor_res_doubles(int64_t rows) { return (size_t)kFactorRes + (size_t)rows; }
 size_t factor_ref_doubles(int64_t rows) { return (size_t)kFactorRefMax * (size_t)(3 + rows); }
+constexpr size_t kFactorTailDoubles = 4;
+// a chunk of draws or of samples: factor_chunk() columns of rows + 3 entries and one of padding
+int64_t sample_ld(int64_t rows) { return rows + 4; }
+size_t sample_chunk_doubles(int64_t rows) { return (size_t)sample_ld(rows) * (size_t)factor_chunk(); }
 
 // The scratch for `rows` rows (a multiple of the factor store's tile edge), everything that can fail for lack of memory, before anything
 // is queued.  Nothing is cleared (dalloc would clear on the null stream, which the handle's streams do not wait for): the launches write
@@ -32,7 +49,7 @@ int32_t factor_alloc(ekf_handle *h, int64_t rows) {
     const TileMap tm = ekf_make_tilemap(TF, 1, 0);
     const int64_t slots = tm.row_base(rows / TF);
     const size_t tile_bytes = (size_t)(slots > 0 ? slots : 1) * TF * TF * sizeof(double);
-    const size_t small_bytes = (factor_rhs_doubles(rows) + factor_res_doubles(rows) + factor_ref_doubles(rows)) * sizeof(double);
+    const size_t small_bytes = (factor_rhs_doubles(rows) + factor_res_doubles(rows) + factor_ref_doubles(rows) + kFactorTailDoubles) * sizeof(double);
     hipError_t e = hipMalloc((void **)&h->d_ftiles, tile_bytes);
     if (e == hipSuccess) e = hipMalloc((void **)&h->d_fsmall, small_bytes);
     if (e == hipSuccess) e = hipHostMalloc((void **)&h->h_fres, factor_res_doubles(rows) * sizeof(double), hipHostMallocDefault);
@@ -46,30 +63,57 @@ int32_t factor_alloc(ekf_handle *h, int64_t rows) {
     h->bytes += h->f_bytes;
     return EKF_OK;
 }
-}  // namespace
 
-extern "C" {
-// Order as in ekf_nearest_landmarks: arguments -> the rungs, with what depends on N checked once N is exact -> every allocation -> the
-// flush -> the launches, none waited for -> ONE readback (the result block and the pivots) -> the sums, on the host, in index order.
-int32_t ekf_factor_map(ekf_handle *h, const double *ref, int32_t nref, ekf_factor_info *info, double *d2) {
-    if (!h) return EKF_ERR_INVALID_ARG;
-    const std::string who = "factor_map: ";
-    REQUIRE(h, info != nullptr, EKF_ERR_INVALID_ARG, (who + "null info").c_str());
-    if (ref) {
-        REQUIRE(h, nref >= 1 && nref <= kFactorRefMax, EKF_ERR_INVALID_ARG, (who + "nref is 1 to 8 reference states").c_str());
-        REQUIRE(h, d2 != nullptr, EKF_ERR_INVALID_ARG, (who + "ref given without d2").c_str());
-    } else
-        nref = 0;
+// ... and what the draws need on top (after factor_alloc of the same call, which releases this part too when it grows): a chunk of
+// draws, a chunk of samples, the partial blocks; the pinned slots; their events.  Its size depends on the rows alone, not on k.
+int32_t sample_alloc(ekf_handle *h, int64_t rows) {
+    for (hipEvent_t &ev : h->ev_fslot) if (!ev) HIPCHK(h, new_event(h, &ev));
+    if (h->fs_rows >= rows) return EKF_OK;
+    if (h->d_fsample) hipFree(h->d_fsample);
+    if (h->h_fxi) hipHostFree(h->h_fxi);
+    if (h->h_fy) hipHostFree(h->h_fy);
+    h->d_fsample = h->h_fxi = h->h_fy = nullptr;
+    h->bytes -= h->fs_bytes;
+    h->fs_bytes = 0;
+    h->fs_rows = -1;
+    const size_t chunk = sample_chunk_doubles(rows), part = (size_t)factor_partial_doubles(rows);
+    const size_t dev_bytes = (2 * chunk + (part ? part : 1)) * sizeof(double);
+    hipError_t e = hipMalloc((void **)&h->d_fsample, dev_bytes);
+    if (e == hipSuccess) e = hipHostMalloc((void **)&h->h_fxi, kSampleSlots * chunk * sizeof(double), hipHostMallocDefault);
+    if (e == hipSuccess) e = hipHostMalloc((void **)&h->h_fy, kSampleSlots * chunk * sizeof(double), hipHostMallocDefault);
+    if (e != hipSuccess) {
+        factor_release(h);
+        return fail(h, EKF_ERR_HIP, "sample_map: the chunks of draws and samples could not be allocated; nothing was changed", e);
+    }
+    h->fs_rows = rows;
+    h->fs_bytes = (int64_t)dev_bytes;
+    h->bytes += h->fs_bytes;
+    return EKF_OK;
+}
+
+// The body of ekf_factor_map and of ekf_sample_map (xi given: k draws, out their samples; ref is then NULL).  Order as in
+// ekf_nearest_landmarks: the rungs, with what depends on N checked once N is exact -> every allocation -> the flush -> the launches, none
+// waited for -> ONE readback (the result block and the pivots) -> the sums, on the host, in index order.  The draws go between the finish
+// and the readback: per chunk the upload of a pinned slot, the two launches and the download into a pinned slot, queued back to back; the
+// host waits only where it takes a slot again, kSampleSlots chunks later, for that slot's own download.  There is ONE chunk of draws and
+// one of samples on the device and one stream, so the copies and the launches of successive chunks run one after another; the pinned
+// slots take the host's packing and unpacking out of that line, nothing more.  `queued` is set once the launches begin: out is written
+// only from there on (slots are unpacked into it before the status is known).
+int32_t factor_body(ekf_handle *h, const std::string &who, const double *ref, int32_t nref, ekf_factor_info *info, double *d2, const double *xi,
+                    int64_t k, double *out, bool &queued) {
     TRY(edit_unsharded(h, who, "the factorisation reads and updates every tile of the lower triangle, and every shard holds only its own tiles"));
     TRY(edit_settled(h, who));
     const int64_t N = h->N, n = 3 + 2 * N;                 // (N is exact only now)
     for (int64_t i = 0; i < (int64_t)nref * n; ++i)
         REQUIRE(h, std::isfinite(ref[i]), EKF_ERR_INVALID_ARG, (who + "ref is not finite").c_str());
+    if (xi)
+        for (int64_t i = 0; i < k * n; ++i) REQUIRE(h, std::isfinite(xi[i]), EKF_ERR_INVALID_ARG, (who + "xi is not finite").c_str());
     const int TF = factor_tile_edge();
     FactorMapArgs a = {};
     a.tm = ekf_make_tilemap(TF, 1, 0);
     a.N = N; a.rows = a.tm.padded(2 * N); a.nref = nref; a.ref_stride = n;
     TRY(factor_alloc(h, a.rows));
+    if (xi) TRY(sample_alloc(h, a.rows));
     TRY(edit_flushed(h));
     TRY(refresh_work(h));
     a.tiles = h->d_ftiles;
@@ -77,25 +121,64 @@ int32_t ekf_factor_map(ekf_handle *h, const double *ref, int32_t nref, ekf_facto
     a.res = a.rhs + factor_rhs_doubles(h->f_rows);
     double *d_ref = a.res + factor_res_doubles(h->f_rows);
     a.ref = nref ? d_ref : nullptr;
+    a.lr_off = xi ? d_ref + factor_ref_doubles(h->f_rows) : nullptr;
     a.cur = h->cur;
+    queued = true;
     HIPCHK(h, hipMemsetAsync(a.res, 0, kFactorRes * sizeof(double), h->stream));
     if (nref) {
         std::memcpy(h->h_fref, ref, (size_t)nref * n * sizeof(double));
         HIPCHK(h, hipMemcpyAsync(d_ref, h->h_fref, (size_t)nref * n * sizeof(double), hipMemcpyHostToDevice, h->stream));
     }
     // timed by family: the load, the right-hand sides and the tail under EKF_KERNEL_COMPACT, the diagonal tiles and the panels under
-    // EKF_KERNEL_GATHER, the trailing updates under EKF_KERNEL_DOWNDATE
+    // EKF_KERNEL_GATHER, the trailing updates under EKF_KERNEL_DOWNDATE; the draws' apply pass under EKF_KERNEL_ASSOCIATE (free in this
+    // call) and their sums under EKF_KERNEL_COMPACT
     if (N > 0) TIMED(h, EKF_KERNEL_COMPACT, launch_factor_load(h->st, a, h->storage, h->stream));
     const int64_t nF = a.rows / TF;
-    for (int64_t k = 0; k < nF; ++k) {
+    for (int64_t c = 0; c < nF; ++c) {
         {
             TimedLaunch tl(h, EKF_KERNEL_GATHER);
-            HIPCHK(h, launch_factor_column(a, (int)k, 0, h->stream));
-            HIPCHK(h, launch_factor_column(a, (int)k, 1, h->stream));
+            HIPCHK(h, launch_factor_column(a, (int)c, 0, h->stream));
+            HIPCHK(h, launch_factor_column(a, (int)c, 1, h->stream));
         }
-        if (k + 1 < nF) TIMED(h, EKF_KERNEL_DOWNDATE, launch_factor_column(a, (int)k, 2, h->stream));
+        if (c + 1 < nF) TIMED(h, EKF_KERNEL_DOWNDATE, launch_factor_column(a, (int)c, 2, h->stream));
     }
     TIMED(h, EKF_KERNEL_COMPACT, launch_factor_finish(h->st, a, h->stream));
+    // the draws: xi's rows permuted into elimination order as columns of a chunk on the way in (a partial last chunk zero-padded), the
+    // samples permuted back into rows of `out` on the way out
+    const int64_t C = factor_chunk(), ld = sample_ld(a.rows), nchunks = xi ? (k + C - 1) / C : 0;
+    const size_t chunk = sample_chunk_doubles(a.rows);
+    auto unpack = [&](int64_t j) {
+        const double *y = h->h_fy + (size_t)(j % kSampleSlots) * chunk;
+        for (int64_t c = 0; c < C && j * C + c < k; ++c) {
+            double *o = out + (j * C + c) * n;
+            std::memcpy(o, y + c * ld + a.rows, 3 * sizeof(double));
+            std::memcpy(o + 3, y + c * ld, (size_t)(2 * N) * sizeof(double));
+        }
+    };
+    if (xi) {
+        FactorSampleArgs sa = {};
+        double *d_xi = h->d_fsample, *d_y = d_xi + sample_chunk_doubles(h->fs_rows);
+        sa.xi = d_xi; sa.y = d_y; sa.part = d_y + sample_chunk_doubles(h->fs_rows); sa.ld = ld;
+        for (int64_t j = 0; j < nchunks; ++j) {
+            const int slot = (int)(j % kSampleSlots);
+            if (j >= kSampleSlots) {
+                HIPCHK(h, hipEventSynchronize(h->ev_fslot[slot]));
+                unpack(j - kSampleSlots);
+            }
+            double *u = h->h_fxi + (size_t)slot * chunk;
+            std::memset(u, 0, chunk * sizeof(double));
+            for (int64_t c = 0; c < C && j * C + c < k; ++c) {
+                const double *row = xi + (j * C + c) * n;
+                std::memcpy(u + c * ld, row + 3, (size_t)(2 * N) * sizeof(double));
+                std::memcpy(u + c * ld + a.rows, row, 3 * sizeof(double));
+            }
+            HIPCHK(h, hipMemcpyAsync(d_xi, u, chunk * sizeof(double), hipMemcpyHostToDevice, h->stream));
+            TIMED(h, EKF_KERNEL_ASSOCIATE, launch_factor_sample(h->st, a, sa, 0, h->stream));
+            TIMED(h, EKF_KERNEL_COMPACT, launch_factor_sample(h->st, a, sa, 1, h->stream));
+            HIPCHK(h, hipMemcpyAsync(h->h_fy + (size_t)slot * chunk, d_y, chunk * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+            HIPCHK(h, hipEventRecord(h->ev_fslot[slot], h->stream));
+        }
+    }
     HIPCHK(h, hipMemcpyAsync(h->h_fres, a.res, (kFactorRes + (size_t)(2 * N)) * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     // the host's part: 2 sum log L_ii in index order (the landmark rows, then the robot), the smallest and largest pivot taken
@@ -121,6 +204,46 @@ int32_t ekf_factor_map(ekf_handle *h, const double *ref, int32_t nref, ekf_facto
     info->min_pivot = lo;
     info->max_pivot = hi;
     for (int q = 0; q < nref; ++q) d2[q] = status == 0 ? res[8 + q] : NAN;
+    // the samples of the last slots; where a pivot failed the launches returned at once and every entry is NaN
+    if (xi && status == 0)
+        for (int64_t j = nchunks > kSampleSlots ? nchunks - kSampleSlots : 0; j < nchunks; ++j) unpack(j);
+    else if (xi)
+        for (int64_t i = 0; i < k * n; ++i) out[i] = NAN;
     return EKF_OK;
+}
+
+// ... and no half-written samples: a call that fails once its launches have begun (EKF_ERR_HIP) leaves every entry of out NaN, as a
+// pivot that failed does; a refusal before that leaves out untouched.
+int32_t factor_run(ekf_handle *h, const std::string &who, const double *ref, int32_t nref, ekf_factor_info *info, double *d2, const double *xi,
+                   int64_t k, double *out) {
+    bool queued = false;
+    const int32_t rc = factor_body(h, who, ref, nref, info, d2, xi, k, out, queued);
+    if (rc != EKF_OK && xi && queued)
+        for (int64_t i = 0; i < k * (3 + 2 * h->N); ++i) out[i] = NAN;
+    return rc;
+}
+}  // namespace
+
+extern "C" {
+int32_t ekf_factor_map(ekf_handle *h, const double *ref, int32_t nref, ekf_factor_info *info, double *d2) {
+    if (!h) return EKF_ERR_INVALID_ARG;
+    const std::string who = "factor_map: ";
+    REQUIRE(h, info != nullptr, EKF_ERR_INVALID_ARG, (who + "null info").c_str());
+    if (ref) {
+        REQUIRE(h, nref >= 1 && nref <= kFactorRefMax, EKF_ERR_INVALID_ARG, (who + "nref is 1 to 8 reference states").c_str());
+        REQUIRE(h, d2 != nullptr, EKF_ERR_INVALID_ARG, (who + "ref given without d2").c_str());
+    } else
+        nref = 0;
+    return factor_run(h, who, ref, nref, info, d2, nullptr, 0, nullptr);
+}
+
+int32_t ekf_sample_map(ekf_handle *h, const double *xi, int64_t k, double *out, ekf_factor_info *info) {
+    if (!h) return EKF_ERR_INVALID_ARG;
+    const std::string who = "sample_map: ";
+    REQUIRE(h, xi != nullptr, EKF_ERR_INVALID_ARG, (who + "null xi").c_str());
+    REQUIRE(h, out != nullptr, EKF_ERR_INVALID_ARG, (who + "null out").c_str());
+    REQUIRE(h, info != nullptr, EKF_ERR_INVALID_ARG, (who + "null info").c_str());
+    REQUIRE(h, k >= 1, EKF_ERR_INVALID_ARG, (who + "k is at least 1 draw").c_str());
+    return factor_run(h, who, nullptr, 0, info, nullptr, xi, k, out);
 }
 }  // extern "C"

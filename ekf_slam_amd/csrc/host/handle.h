@@ -211,6 +211,12 @@ struct ekf_handle {
     // ekf_destroy itself -- they are not in the registries below, which only ever grow.  f_bytes of them are counted in `bytes`.
     double *d_ftiles = nullptr, *d_fsmall = nullptr, *h_fres = nullptr, *h_fref = nullptr;
     int64_t f_rows = -1, f_bytes = 0;
+    // ekf_sample_map, part of the same scratch (released with it): in ONE device allocation a chunk of draws, a chunk of samples and the
+    // partial blocks of one apply pass, for fs_rows rows; kSampleSlots chunks of pinned staging per direction, and the event behind each
+    // slot's readback (made once, destroyed with the handle's other events).  fs_bytes of the device part are counted in `bytes`.
+    double *d_fsample = nullptr, *h_fxi = nullptr, *h_fy = nullptr;
+    hipEvent_t ev_fslot[4] = { nullptr, nullptr, nullptr, nullptr };
+    int64_t fs_rows = -1, fs_bytes = 0;
     // ---- linear observations (ekf_observe_linear / ekf_linear_innovation) ----
     // two records on the device and in pinned memory (the update-step's, then the probe's; behind them in the pinned area the two counters
     // ekf_linear_rejections reads), the device counters of launches that did not apply, the event behind a waited step's readback

@@ -158,7 +158,25 @@ struct FactorMapArgs {
     int64_t ref_stride;
     int32_t nref;             // 0 .. kFactorRefMax
     int32_t cur;              // the live buffer of x, Prr and the strip (the diagonal copies: dcur of the DevState)
+    double *lr_off;           // where k_factor_finish stores L_r(1,0), L_r(2,0), L_r(2,1) once the tail is taken whole; nullptr: not stored
 };
+
+// k_factor_apply / k_factor_sample (sample_map.h): x + C xi for one chunk of kFactorChunk draws behind a factorisation that FactorMapArgs
+// describes.  A chunk is kFactorChunk COLUMNS ld doubles apart, one draw a column in elimination order: entries [0, rows) the landmark
+// part (zero from 2 N on), entries rows .. rows + 2 the robot's.  Tile row I of the factor store is cut into segments of S tiles
+// (I / S + 1 of them); every segment leaves one partial block of tm.T x kFactorChunk doubles, row-major.
+constexpr int kFactorChunk = 16;                  // one v_mfma_f64_16x16x4_f64 N-width
+struct FactorSampleArgs {
+    const double *xi;         // the draws of the chunk
+    double *y;                // the samples of the chunk, in the same layout (entries 2 N .. rows - 1 are not written)
+    double *part;             // factor_segment_base(rows / tm.T, S) partial blocks, then rows / tm.T parts of W' Xi, 3 x kFactorChunk doubles each
+    int64_t ld;               // >= rows + 3
+};
+// the partial blocks in front of tile row I's: rows g S .. g S + S - 1 have g + 1 segments each
+EKF_HD int64_t factor_segment_base(int64_t I, int64_t S) {
+    const int64_t g = I / S;
+    return S * g * (g + 1) / 2 + (I - g * S) * (g + 1);
+}
 
 // k_predict_model (predict_model.h): a chain of m <= kPredictModelMax motion steps through the models of ekfm::motion_eval, carried out in
 // order by ONE launch that reads buffer cur and writes buffer cur ^ 1, as k_predict.  No tile is read: the storage type does not matter.

@@ -63,6 +63,12 @@ int factor_tile_edge();
 hipError_t launch_factor_load(const DevState &st, const FactorMapArgs &a, int storage, hipStream_t s);
 hipError_t launch_factor_column(const FactorMapArgs &a, int k, int part, hipStream_t s);      // part 0: diagonal, 1: panel, 2: trailing update
 hipError_t launch_factor_finish(const DevState &st, const FactorMapArgs &a, hipStream_t s);
+// k_factor_apply / k_factor_sample (sample_map.h): x + C xi for one chunk of factor_chunk() draws, queued behind launch_factor_finish of
+// the same `a` (a.lr_off given: the finish stores all of L_r).  part 0: the apply pass, one partial block per segment into sa.part
+// (factor_partial_doubles(a.rows) doubles); part 1: the sums, x and the robot rows into sa.y.  Both return at once where a pivot failed.
+int factor_chunk();
+int64_t factor_partial_doubles(int64_t rows);
+hipError_t launch_factor_sample(const DevState &st, const FactorMapArgs &a, const FactorSampleArgs &sa, int part, hipStream_t s);
 
 // fused_predict != nullptr folds predict(u) into the correction (one launch instead of two, identical arithmetic)
 // fuse_downdate: the kernel also applies its pair to the landmark block (small maps: a.n_mm <= gather_fuse_max_rows(), one

@@ -62,6 +62,7 @@ namespace {
 #include "merge_pass.h"       // the fused downdate-and-compact pass of a batch of merges: k_merge_pass
 #include "nearest.h"          // the candidate search in front of a merge: k_nearest
 #include "factor_map.h"       // the Cholesky factorisation of P in a scratch store: k_factor_load / _rhs / _diag / _panel / _trail / _finish
+#include "sample_map.h"       // ... and the draws x + C xi behind it: k_factor_apply, k_factor_sample
 
 }  // namespace
 

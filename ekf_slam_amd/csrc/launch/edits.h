@@ -334,3 +334,27 @@ hipError_t launch_factor_finish(const DevState &st, const FactorMapArgs &a, hipS
     hipLaunchKernelGGL(k_factor_finish, dim3(1), dim3(kFactorBlock), 0, s, st, a);
     return hipGetLastError();
 }
+
+// ---- the draws behind it (sample_map.h: k_factor_apply, k_factor_sample) ----
+// Tiles per segment of a tile row.  16: a workgroup streams 512 KiB of the factor for one 8 KiB partial block (3 % of the store's bytes
+// written and read again), and 10 000 landmarks (313 tile rows) still make 3 220 workgroups, all of the same length but the last of each tile row.
+constexpr int kFactorSegment = 16;
+int factor_chunk() { return kFactorChunk; }
+// one partial block per segment, then per tile row its 3 x kFactorChunk part of W' Xi
+int64_t factor_partial_doubles(int64_t rows) {
+    const int64_t nF = rows / kFactorTile;
+    return factor_segment_base(nF, kFactorSegment) * (int64_t)(kFactorTile * kFactorChunk) + nF * (3 * kFactorChunk);
+}
+
+hipError_t launch_factor_sample(const DevState &st, const FactorMapArgs &a, const FactorSampleArgs &sa, int part, hipStream_t s) {
+    // every index the two kernels form lies inside the chunk (ld), the partial blocks (one per segment of the grid) and the store
+    if (!factor_args_ok(a) || !a.lr_off || !sa.xi || !sa.y || !sa.part || sa.ld < a.rows + 3 || part < 0 || part > 1) return hipErrorInvalidValue;
+    const int64_t nF = a.rows / kFactorTile, segments = factor_segment_base(nF, kFactorSegment);
+    if (segments > 0x7fffffffll) return hipErrorInvalidValue;
+    if (part == 0) {
+        if (segments == 0) return hipSuccess;
+        hipLaunchKernelGGL((k_factor_apply<kFactorTile, kFactorSegment>), dim3((unsigned)segments), dim3(4 * kFactorTile), 0, s, a, sa);
+    } else
+        hipLaunchKernelGGL((k_factor_sample<kFactorTile, kFactorSegment>), dim3((unsigned)(nF + 1)), dim3(kFactorBlock), 0, s, st, a, sa);
+    return hipGetLastError();
+}

@@ -544,6 +544,20 @@ class Engine:
         self._check(self.lib.ekf_factor_map(self.h, marshal.p_or_null(ref), nref, ctypes.byref(info), marshal.p_or_null(d2)))
         return marshal.factor_result(args)
 
+    # ---- draws from the posterior: x + C xi from the same factorisation (include/ekfslam.h: ekf_sample_map) ----
+    def sample_map(self, xi):
+        """(samples, info): row q of `samples` is x + C xi_q for the k draws in `xi` (one draw of 3 + 2 N entries, or one per row; in
+        x's order, standard normal where samples of N(x, P) are wanted -- the library generates no random numbers).  C is the Cholesky
+        factor of P in factor_map's elimination order (the landmark block first, the robot last) mapped back to x's order: C C' = P.
+        `info` is factor_map()'s dict without d2; where P is not definite every sample is NaN and info says where the factorisation
+        stopped.  One factorisation per call whatever k is; read-only and synchronising (ekf_sample_map)."""
+        return self._sample_map(marshal.sample_args(xi, 3 + 2 * self.N))
+
+    def _sample_map(self, args):
+        xi, k, out, info = args
+        self._check(self.lib.ekf_sample_map(self.h, _p(xi), k, _p(out), ctypes.byref(info)))
+        return marshal.sample_result(args)
+
     @staticmethod
     def model_invert(model, xr, z, lib=None):
         """(t, Gx, Gz): the landmark that z observes from the robot state xr = (x, y, theta in degrees) through EKF_MODEL_RANGE_BEARING

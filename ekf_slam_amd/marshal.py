@@ -225,6 +225,32 @@ def factor_result(args):
     return out
 
 
+def sample_args(xi, n, who="sample_map"):
+    """(xi, k, out, info) of sample_map as the ABI takes them, the arrays kept so that sample_result reads what the call wrote.  xi: one
+    draw of n = 3 + 2 N finite entries, or k >= 1 of them as the rows of a 2-D array (contiguous F64 from here on).  Anything else is
+    refused here, before any call."""
+    if xi is None:
+        raise ValueError("%s: xi is the draws, one per row" % who)
+    xv = np.ascontiguousarray(np.asarray(xi, dtype=np.float64))
+    if xv.ndim == 1:
+        xv = xv.reshape(1, -1)
+    if xv.ndim != 2 or xv.shape[0] < 1:
+        raise ValueError("%s: xi is k >= 1 draws, one per row" % who)
+    if xv.shape[1] != n:
+        raise ValueError("%s: a draw has 3 + 2 N = %d entries, got %d" % (who, n, xv.shape[1]))
+    if not np.all(np.isfinite(xv)):
+        raise ValueError("%s: xi is not finite" % who)
+    return xv, ctypes.c_int64(xv.shape[0]), np.full(xv.shape, np.nan), L.EkfFactorInfo()
+
+
+def sample_result(args):
+    """What sample_map returns from what the call wrote: (the samples, one per row; the dict of factor_result without 'd2')."""
+    _, _, out, info = args
+    res = factor_result((None, None, info, None))
+    del res["d2"]
+    return out, res
+
+
 def model_inits(entries, who="append_model"):
     """(ekf_model_init[], m) of a scan of new landmarks [(model, z, R, signature), ...]."""
     entries = list(entries)

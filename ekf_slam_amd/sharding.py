@@ -165,6 +165,11 @@ class ShardGroup:
         its own.  The call goes to the first shard so that the refusal is the library's (EKF_ERR_INVALID_ARG, nothing changed)."""
         return self.shards[0].factor_map(ref)
 
+    def sample_map(self, xi):
+        """Not built for a shard group, as factor_map, whose factorisation it is.  The call goes to the first shard so that the refusal
+        is the library's (EKF_ERR_INVALID_ARG, nothing changed)."""
+        return self.shards[0].sample_map(xi)
+
     def correct(self, z, R, idx0):
         for e in self.shards:
             e.correct_begin(z, R, idx0)

@@ -303,6 +303,43 @@ class _EkfBase:
         res = self._e.factor_map()
         return 0.5 * (res["n"] * math.log(2.0 * math.pi * math.e) + res["logdet"])
 
+    def sample_map(self, k=None, seed=None, xi=None):
+        """(samples, info): k joint draws of the posterior N(x, P) as the rows of `samples`, from ONE factorisation on the device
+        (Engine.sample_map; ekf_sample_map).  With `xi` (one draw, or one per row) the standard-normal draws are the caller's and a
+        sample is x + C xi; otherwise k draws come from numpy.random.default_rng(seed).standard_normal.  The heading entry is not
+        wrapped.  Where P is not definite every sample is NaN and `info` (factor_map's dict without d2) says where.  Read-only:
+        nothing goes into the trajectory log.  For a SUBSET of the landmarks, extract_map them first.  The reference has no such
+        method."""
+        if xi is None:
+            if k is None or int(k) < 1:
+                raise ValueError("sample_map: k >= 1 draws, or xi")
+            xi = np.random.default_rng(seed).standard_normal((int(k), 3 + 2 * self._e.N))
+        elif k is not None or seed is not None:
+            raise ValueError("sample_map: xi carries the draws; k and seed go with draws made here")
+        return self._e.sample_map(xi)
+
+    def _definite_samples(self, who, k, seed):
+        samples, info = self.sample_map(k, seed)
+        if not info["definite"]:
+            raise ValueError("%s: P is not positive definite (factor_map says where: bad_index %d)" % (who, info["bad_index"]))
+        return samples
+
+    def posterior_expectation(self, fn, k, seed=None):
+        """(mean, standard error of the mean) of fn(sample) over k >= 2 draws of the posterior (sample_map(k, seed)); fn takes a state
+        vector of 3 + 2 N entries and returns a scalar or a vector.  The standard error is the sample standard deviation (k - 1 in the
+        denominator) over sqrt(k).  ValueError where P is not positive definite."""
+        if int(k) < 2:
+            raise ValueError("posterior_expectation: k >= 2 draws")
+        vals = np.array([np.asarray(fn(row), dtype=np.float64) for row in self._definite_samples("posterior_expectation", k, seed)])
+        return vals.mean(axis=0), vals.std(axis=0, ddof=1) / math.sqrt(vals.shape[0])
+
+    def probability(self, event, k, seed=None):
+        """(p, standard error): the share p of k draws of the posterior for which event(sample) is true, and its binomial standard error
+        sqrt(p (1 - p) / k).  ValueError where P is not positive definite."""
+        hits = sum(1 for row in self._definite_samples("probability", k, seed) if event(row))
+        p = hits / float(int(k))
+        return p, math.sqrt(p * (1.0 - p) / int(k))
+
     def fuse_duplicates(self, gate, R=None, max_merges=None):
         """The SIMPLEST complete fusion policy, not the fastest: repeat { search; take the candidate with the smallest (d2, i) at or
         below `gate`; merge_landmarks(keep=j, drop=i, R) } until none is left or `max_merges` merges were made.  One search plus

@@ -639,6 +639,35 @@ typedef struct ekf_factor_info {
     double min_pivot, max_pivot;
 } ekf_factor_info;
 int32_t ekf_factor_map(ekf_handle *h, const double *ref /* nref x (3 + 2N), may be NULL */, int32_t nref, ekf_factor_info *info, double *d2 /* nref */);
+/* DRAWS FROM THE POSTERIOR: k joint samples x + C xi of the Gaussian N(x, P) the handle carries, from ONE factorisation -- ekf_factor_map's,
+ * with the factor applied to the caller's draws before it is forgotten.  xi is k rows of 3 + 2 N finite entries in x's order (robot
+ * first), standard normal where samples of the posterior are wanted; THE LIBRARY GENERATES NO RANDOM NUMBERS.  Row q of out is x + C xi_q.
+ *   C IS THE LOWER-TRIANGULAR CHOLESKY FACTOR OF P IN ekf_factor_map's ELIMINATION ORDER -- the landmark block first, rows ascending, the
+ *   robot last -- mapped back to x's order, so C C' = P in x's order.  Unlike P, C depends on that order: in elimination order it is
+ *   [L 0; W' L_r] with P(4:end, 4:end) = L L', W = L^-1 P(4:end, 1:3) and L_r L_r' = P(1:3, 1:3) - W' W, and a sample is
+ *       out(4:end) = x(4:end) + L xi(4:end),      out(1:3) = x(1:3) + W' xi(4:end) + L_r xi(1:3).
+ *   The unit vectors as draws return the columns of C.  The heading entry is x[2] plus its deviation, NOT wrapped.
+ * info is filled as by ekf_factor_map(h, NULL, 0, ..), bit for bit, and may not be NULL.  A P THAT IS NOT DEFINITE IS A RESULT: EKF_OK,
+ * info says where the factorisation stopped, and every entry of out is NaN.
+ * Promised: (1) xi = 0 gives out = x, bit for bit, an entry -0.0 included (a deviation of zero is not added); (2) row q of out depends on xi_q alone -- the same draw gives the same bits alone, first, last or
+ * in the middle of a batch of any k, and from call to call; (3) no atomics and no data-dependent order of summation.
+ * The draws are taken 16 at a time (one chunk: the N-width of the F64 matrix instruction), a partial last chunk padded with zeros.  Per
+ * chunk one streaming pass over the factor store forms L Xi on the F64 matrix cores, every tile read once, each tile row cut into
+ * segments of 16 tiles with one workgroup and one partial block each; a second launch sums the partial blocks in ascending order, adds
+ * x and forms the robot rows.  Chunks go up and come down through pinned staging of four chunks a direction, whatever k is; the host
+ * waits only for a slot's own readback four chunks later.  There is one chunk of draws and one of samples on the device and one stream:
+ * the copies and launches of successive chunks run one after another, the pinned slots only take the host's packing out of that line.  The chunks and the partial blocks (8 (N^2 / 32 + 80 N) bytes or so:
+ * 31 MB at 10 000 landmarks beside the 1.6 GB factor store) are part of ekf_factor_map's scratch: allocated before anything is
+ * flushed, counted by ekf_device_bytes, released with it.
+ * The apply passes count under EKF_KERNEL_ASSOCIATE, the second launches under EKF_KERNEL_COMPACT, the factorisation as in ekf_factor_map.
+ * Nothing is kept between calls: every call factors, so ask for all the draws of one state in one call.
+ * SYNCHRONISING and READ-ONLY exactly as ekf_factor_map.  Refused with nothing changed and nothing flushed: h, xi, out or info NULL,
+ * k < 1, a handle with world > 1 (a lone shard with cfg.force_sharded works) (EKF_ERR_INVALID_ARG); a sharded correction between begin
+ * and finish (EKF_ERR_STATE); then, once N is exact, an xi entry that is not finite (EKF_ERR_INVALID_ARG); EKF_ERR_HIP if the scratch
+ * cannot be allocated, before anything is queued.  A refusal leaves out untouched; an EKF_ERR_HIP once the launches have begun leaves
+ * every entry of out NaN.  For a SUBSET of the landmarks: ekf_extract_map, then this call on the small handle. */
+int32_t ekf_sample_map(ekf_handle *h, const double *xi /* k x (3 + 2N), one row per draw */, int64_t k /* >= 1 */, double *out /* k x (3 + 2N) */,
+                       ekf_factor_info *info);
 /* The step between the two: "WHICH landmark does this sighting belong to?", for a whole scan, under the conventions of ekf_observe_model.
  * ekf_associate keeps the reference's (signature-only by default, an unwrapped bearing, a range-scaled R) and cannot serve a filter
  * driven through the model calls.  For each of the m observations, d2(k, i) is, BIT FOR BIT, the d2 that ekf_model_innovation reports for

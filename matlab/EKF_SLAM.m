@@ -290,6 +290,16 @@ classdef EKF_SLAM < handle
             info = struct('n', v(1), 'definite', v(2) ~= 0, 'bad_index', v(3), 'bad_pivot', v(4), 'logdet', v(5), 'logdet_map', v(6), ...
                           'min_pivot', v(7), 'max_pivot', v(8));
         end
+        function [samples, info] = sampleMap(h, xi)
+            % DRAWS FROM THE POSTERIOR: samples(:, q) = x + C * xi(:, q) for the k columns of xi (n x k, n = 3 + 2 N; randn(n, k) for
+            % samples of the Gaussian the filter carries), from ONE factorisation on the GPU.  C is the lower-triangular Cholesky factor
+            % of P in factorMap's elimination order (the landmark block first, the robot last) mapped back to x's order: C * C' = P.
+            % The heading entry is not wrapped.  info is factorMap's struct; where P is not positive definite samples is all NaN.
+            % Read-only.  Not a method of the reference.
+            [samples, v] = h.gateway('sample_map', double(xi));
+            info = struct('n', v(1), 'definite', v(2) ~= 0, 'bad_index', v(3), 'bad_pivot', v(4), 'logdet', v(5), 'logdet_map', v(6), ...
+                          'min_pivot', v(7), 'max_pivot', v(8));
+        end
         function idx = addLandmarkRangeBearing(h, z, R, signature)
             % 'A landmark that is not in the map yet is seen at range z(1) and bearing z(2) (degrees, relative to the heading),
             % covariance R': it joins the map at the point that observation names.
