@@ -6,22 +6,7 @@ a2 b3 + a3 b2 + a3 b3: at most 2^-23 |a b| (|a2| <= 2^-8 |a|, |a3| <= 2^-16 |a|)
 square below 0.1 x 2^-24 |a b|, where ONE float rounding of the product has 0.29 x 2^-24 (its unit roundoff is 2^-24)."""
 import numpy as np
 
-
-def bf16_rn(v):
-    """float32 array -> the float32 value of its round-to-nearest-even bfloat16 (integer arithmetic on the bits, as bf16_rn_bits)."""
-    u = np.asarray(v, dtype=np.float32).view(np.uint32).astype(np.uint64)
-    r = ((u + 0x7FFF + ((u >> 16) & 1)) >> 16) << 16
-    return (r & 0xFFFFFFFF).astype(np.uint32).view(np.float32)
-
-
-def split3(v):
-    v = np.asarray(v, dtype=np.float32)
-    b1 = bf16_rn(v)
-    r1 = (v - b1).astype(np.float32)
-    b2 = bf16_rn(r1)
-    r2 = (r1 - b2).astype(np.float32)
-    b3 = bf16_rn(r2)
-    return b1, b2, b3, r1, r2
+from float_pass_cases import bf16_rn, split3                 # (the rule itself: shared with the emulations of the pass)
 
 
 def _samples(n, seed):
