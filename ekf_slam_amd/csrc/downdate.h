@@ -13,8 +13,9 @@ template <typename TS, int T, int kSlab>
 __global__ __launch_bounds__(kBlock) void k_downdate(const TS *__restrict__ tiles, TS *__restrict__ dst,
                                                      const int2 *__restrict__ work, int64_t nwork,
                                                      const double *__restrict__ Kp, const double *__restrict__ Gp,
-                                                     int64_t pair_stride, int pstart, int pcap, int npairs, TileMap tm) {
+                                                     int64_t pair_stride, int pstart, int pcap, int npairs, TileMap tm, int live) {
     // kSlab = rows of a tile one workgroup handles (T = whole tile); a work item is (tile, slab).
+    // live: landmark-block rows that hold state (PassJob::live_rows; INT_MAX: no bound) -- see k_downdate_w.
     // npairs pending (K_i, G_i) pairs are applied, in slot order, to registers between ONE load and ONE
     // store of every element: one pass over P for npairs update-steps.
     using V2 = typename Vec2<TS>::type;
@@ -33,6 +34,7 @@ __global__ __launch_bounds__(kBlock) void k_downdate(const TS *__restrict__ tile
         const int64_t w = it / kSlabsPerTile;
         const int slab = (int)(it - w * kSlabsPerTile);
         const int2 ij = work[w];
+        if (ij.x * T + slab * kSlab >= live) continue;               // a slab of padding rows: K is zero there (uniform per workgroup)
         const int64_t toff = tm.tile_offset(ij.x, ij.y) + (int64_t)slab * kSlab * T;
         const TS *__restrict__ tp = tiles + toff;
         TS *__restrict__ td = dst + toff;
@@ -137,7 +139,7 @@ __global__ __launch_bounds__(kBlock) void k_downdate_w(const TS *__restrict__ ti
                                                        const int2 *__restrict__ work, int64_t nwork,
                                                        const double *__restrict__ Kp, const double *__restrict__ Gp,
                                                        int64_t pair_stride, int pstart, int pcap, int npairs, TileMap tm,
-                                                       typename NextRowParam<kNext>::type nx) {
+                                                       typename NextRowParam<kNext>::type nx, int live, int head, int tail_shift) {
     using VL = typename Lane16<TS>::type;
     constexpr int kCols = Lane16<TS>::kCols;              // columns per lane: 2 (f64 tiles) or 4 (f32 tiles)
     constexpr int kLanesPerRow = T / kCols;               // 64: one row per wave instruction; 32: two rows
@@ -147,6 +149,7 @@ __global__ __launch_bounds__(kBlock) void k_downdate_w(const TS *__restrict__ ti
     constexpr int kSlabsPerTile = T / kSlab;
     static_assert(kLanesPerRow == 64 || kLanesPerRow == 32, "tile edge / storage type combination not supported");
     static_assert(kPasses >= 1 && kPasses <= 8 && kPasses * kRowsPerInstr * 4 == kSlab, "bad slab");
+    static_assert((kSlabsPerTile & (kSlabsPerTile - 1)) == 0, "slabs per tile: a power of two");
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int sub = lane / kLanesPerRow;                  // which of the kRowsPerInstr rows this lane is on
@@ -158,15 +161,42 @@ __global__ __launch_bounds__(kBlock) void k_downdate_w(const TS *__restrict__ ti
     // pass reads FIRST -- while they are still in the 256 MiB Infinity Cache (it keeps a line while the bytes touched between
     // two uses of it fit; a store larger than the cache that is always walked in the same direction never meets that).
     // Results do not depend on the order: every element is updated independently.
-    const int64_t nitems = (kXcd ? 8 : 1) * nwork * kSlabsPerTile;
-    const int64_t nv = nwork * kSlabsPerTile;
-    for (int64_t it = blockIdx.x; it < nitems; it += gridDim.x) {
-        const int64_t vf = kXcd ? (it >> 3) : it;
-        const int64_t vi = tm.reverse ? nv - 1 - vf : vf;
-        const int64_t w = vi / kSlabsPerTile;
-        const int slab = (int)(vi - w * kSlabsPerTile);
-        const int2 ij = work[kXcd ? (it & 7) * nwork + w : w];
+    // live (PassJob::live_rows of an in-place pass; INT_MAX: no bound): the landmark-block rows that hold state.  K is zero from there to
+    // the padded width, the update of those rows an identity, so a work item whose FIRST row lies at or beyond it is neither loaded nor
+    // stored -- a slab that straddles the bound is processed whole.  The test reads the work-list entry and the slab number alone:
+    // uniform per workgroup, scalar unit, in front of the first tile address.
+    // head, tail_shift (the one list, !kXcd; launch_downdate sets them): the workgroups such an item would occupy are not dispatched
+    // either where the list allows it.  The tiles of the LAST tile row are the list's trailing entries, so the item space is two ranges:
+    // `head` items that cover the tiles in front of them whole (kSlabsPerTile each), then 1 << tail_shift items per tile of the last
+    // row -- its slabs up to the bound, rounded up to a power of two (what the rounding adds meets the test above).  Item counts fit
+    // 32 bits (launch_downdate refuses others) and the tail is cut with a shift: no division by a run-time value.  Without a bound
+    // head covers every tile and the tail is empty.
+    __builtin_assume(npairs > 0);                         // (launch_downdate launches nothing otherwise: no flag to keep for the pair loop's guard)
+    using Index = typename std::conditional<kXcd, int64_t, uint32_t>::type;     // (the one list: item numbers, and item + grid, fit 32 bits)
+    const Index nv = kXcd ? (Index)(nwork * kSlabsPerTile) : (Index)(head + (((int)nwork - head / kSlabsPerTile) << tail_shift));
+    const Index nitems = (kXcd ? 8 : 1) * nv;
+    for (Index it = blockIdx.x; it < nitems; it += gridDim.x) {
+        const Index vf = kXcd ? (it >> 3) : it;
+        const Index vi = tm.reverse ? nv - 1 - vf : vf;
+        int64_t w;
+        int slab;
+        if (kXcd) {
+            w = vi / kSlabsPerTile;
+            slab = (int)(vi - w * kSlabsPerTile);
+        } else {
+            const int u = (int)vi, t = u - head;
+            const bool tail = u >= head;
+            const int sh = tail ? tail_shift : __builtin_ctz(kSlabsPerTile), un = tail ? t : u;
+            w = (tail ? head / kSlabsPerTile : 0) + (un >> sh);
+            slab = un & ((1 << sh) - 1);
+        }
+        // (the entry as ONE 8-byte scalar load: with the test below in front of the body the compiler otherwise fetches ij.y behind it,
+        // a second trip to the scalar cache in every workgroup)
+        const uint64_t e = *reinterpret_cast<const uint64_t *>(work + (kXcd ? (it & 7) * nwork + w : w));
+        const int2 ij = make_int2((int)(uint32_t)e, (int)(uint32_t)(e >> 32));
         if (kXcd && ij.x < 0) continue;
+        const int first = ij.x * T + slab * kSlab;                      // the work item's first landmark-block row
+        if (first >= live) continue;
         const int row0 = slab * kSlab + wave * kRowsPerWave;            // first tile row of this wavefront
         const int64_t toff = tm.tile_offset(ij.x, ij.y) + (int64_t)(row0 + sub) * T + kCols * cl;
         const TS *__restrict__ tp = tiles + toff;
@@ -178,7 +208,7 @@ __global__ __launch_bounds__(kBlock) void k_downdate_w(const TS *__restrict__ ti
             lane16_unpack(t, v[p]);
         }
         const int64_t gcol = (int64_t)ij.y * T + kCols * cl;
-        const int64_t krow = (int64_t)ij.x * T + row0;                  // wave-uniform
+        const int64_t krow = first + wave * kRowsPerWave;               // ij.x * T + row0, wave-uniform
         for (int i = 0; i < npairs; ++i) {
             const int64_t so = (int64_t)ring_slot(pstart, i, pcap) * pair_stride;
             const double2 *__restrict__ g2 = reinterpret_cast<const double2 *>(Gp + so) + gcol;

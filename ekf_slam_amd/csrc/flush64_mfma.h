@@ -28,7 +28,7 @@ template <typename TS, int T, int kChunk, int kCols = 128, int kWpe = (kChunk <=
 __global__ __launch_bounds__(64 * kWaves) __attribute__((amdgpu_waves_per_eu(kWpe, kWpe)))
 void k_flush_mfma(const TS *__restrict__ tiles, TS *__restrict__ dst, const int2 *__restrict__ work, int64_t nwork,
                   const double *__restrict__ Kp, const double *__restrict__ Gp, int64_t pair_stride, int pstart, int pcap,
-                  int npairs, TileMap tm) {
+                  int npairs, TileMap tm, int live) {
     constexpr int kBlock = 64 * kWaves;                               // (shadows the file-scope constant: this kernel's own workgroup size)
     constexpr int kRows = 16 * kWaves, kKPad = kRows + 16;
     constexpr int kE = 16 / (int)sizeof(TS);                          // columns in a lane's 16 bytes: 2 (f64) or 4 (f32)
@@ -50,6 +50,7 @@ void k_flush_mfma(const TS *__restrict__ tiles, TS *__restrict__ dst, const int2
         const int2 ij = work[(it & 7) * nwork + w];
         if (ij.x < 0) continue;                                       // padding of a shorter stream (uniform per workgroup)
         const int slab = sub / kColParts, cpart = sub - slab * kColParts;
+        if (ij.x * T + slab * kRows >= live) continue;                // kRows rows of padding (PassJob::live_rows, as k_downdate_w): K is zero there
         const int row0 = slab * kRows + wave * 16;
         const int64_t toff = tm.tile_offset(ij.x, ij.y) + (int64_t)(row0 + lr) * T + cpart * kCols + kE * lc;
         const TS *__restrict__ tp = tiles + toff;

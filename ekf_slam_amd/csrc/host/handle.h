@@ -87,6 +87,7 @@ struct ekf_handle {
     struct WorkSet {
         int2 *work = nullptr;          // the tiles, row by row
         int64_t nwork = 0;
+        int64_t nwork_head = 0;        // ... of them in front of the LAST tile row's (which are the trailing entries)
         // the same tiles arranged as 8 per-XCD streams of super-tiles (batched flush: keeps each XCD's K/G working set
         // inside its own 4 MiB L2); stream x is xcd[x * xcd_len .. ), padded with (-1,-1)
         int2 *xcd = nullptr;

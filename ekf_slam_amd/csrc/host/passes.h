@@ -20,11 +20,15 @@ int32_t refresh_work(ekf_handle *h) {
     int4 *segs = reinterpret_cast<int4 *>(h->wl_stage + b_work + b_xcd);
     size_t nw = 0;
     REQUIRE(h, h->st.tm.slots_for_rows(nt) <= h->work_cap, EKF_ERR_STATE, "work list overflow");
-    for (int64_t I = 0; I < nt; ++I)
+    size_t nw_head = 0;
+    for (int64_t I = 0; I < nt; ++I) {
+        if (I == nt - 1) nw_head = nw;
         for (int64_t J = 0; J <= I; ++J)
             if (h->st.tm.mine(I, J)) w[nw++] = make_int2((int)I, (int)J);
+    }
     if (nw) HIPCHK(h, hipMemcpyAsync(ws.work, w, nw * sizeof(int2), hipMemcpyHostToDevice, h->stream));
     ws.nwork = (int64_t)nw;
+    ws.nwork_head = (int64_t)nw_head;
     ws.rows = nt;
 
     // per-XCD streams: super-tiles of S x S tiles, largest first onto the least loaded stream
@@ -98,7 +102,7 @@ const PassAux *pass_aux(const ekf_handle *h, const ekf_handle::WorkSet &ws, Pass
 PassJob pass_job(const ekf_handle *h, const ekf_handle::WorkSet &ws, void *dst, PassAux &ax) {
     PassJob job = {};
     job.dst = dst;
-    job.work = ws.work; job.nwork = ws.nwork; job.work_xcd = ws.xcd; job.xcd_len = ws.xcd_len;
+    job.work = ws.work; job.nwork = ws.nwork; job.nwork_head = ws.nwork; job.work_xcd = ws.xcd; job.xcd_len = ws.xcd_len;
     job.pstart = h->pstart; job.npairs = h->npend;
     job.grid_cap = h->grid_cap; job.arith = h->cfg.pass_arith;
     job.aux = pass_aux(h, ws, ax);
@@ -223,6 +227,10 @@ int32_t flush_pending(ekf_handle *h, bool batch_done = false) {
         PassAux ax;
         PassJob job = pass_job(h, ws, h->st.tiles, ax);
         job.nx = nx.j >= 0 ? &nx : nullptr;
+        // In place: rows beyond the map hold no state and see zero K, so the pass leaves them out.  Read here, per launch, like the
+        // work set's own row count (refresh_work) -- an append between two passes moves it.
+        job.live_rows = 2 * n_hi(h);
+        if (ekf_tiles_for(job.live_rows, h->T) == ws.rows) job.nwork_head = ws.nwork_head;     // (else: no tail, every tile is dispatched whole)
         HIPCHK(h, launch_downdate(h->st, job, h->storage, h->stream, h->dd_kernel, &extracted));
         h->dd_pairs = h->npend;
     }

@@ -203,6 +203,13 @@ struct PassJob {
     int arith;                 // cfg.pass_arith
     const PassAux *aux;        // nullptr: the handle has no strip form
     const NextRow *nx;         // nullptr: no row-panel wanted
+    int64_t live_rows;         // in-place passes only: landmark-block rows that hold state (2 * the landmark count, or an upper bound of it).
+                               // K is zero from there to the padded width, so the update of those rows is an identity: k_downdate,
+                               // k_downdate_w and k_flush_mfma neither load nor store a work item that starts at or beyond it.  0: no bound --
+                               // a pass into a second store has to carry every row across
+    int64_t nwork_head;        // with live_rows: the entries of `work` in front of the last tile row's, which are its trailing ones.  Of THOSE tiles
+                               // k_downdate_w is dispatched for the slabs up to the bound only (rounded up to a power of two), not for all of
+                               // them.  nwork (or anything with live_rows == 0): every tile is dispatched whole
 };
 // kname: nullptr, or 64 bytes that receive the name of the kernel instance that was launched ("k_flush_mfma<double,128,8>");
 // *extracted tells whether that instance extracted job.nx (one pair per launch, wavefront-per-row tile shapes only)

@@ -45,6 +45,8 @@ hipError_t launch_downdate(const DevState &st, const PassJob &job, int storage, 
                                      ekf_tune_int("EKF_PASS_STRIP", 1) != 0, ekf_tune_int("EKF_FLUSH_XCD", 1) != 0 };
     const PassAux *aux = job.aux;
     const int T = st.tm.T, pstart = job.pstart, npairs = job.npairs;
+    // rows that hold state (in-place passes: PassJob::live_rows); the kernels that take it skip the work items of padding rows
+    const int live = job.live_rows > 0 && job.live_rows < INT_MAX ? (int)job.live_rows : INT_MAX;
     PassQuery q = { storage == 0 ? 8 : 4, T, npairs, job.arith, /*xcd_list*/ job.work_xcd && job.xcd_len > 0,
                     /*strip_list*/ aux && aux->segs && aux->nsegs > 0, /*planes*/ aux && aux->Kb3 && aux->Gb3, /*next_row*/ job.nx && job.nx->j >= 0,
                     /*slab_override*/ npairs > 1 ? slabm : slab1 };
@@ -61,10 +63,10 @@ hipError_t launch_downdate(const DevState &st, const PassJob &job, int storage, 
     }
 
     // the matrix-core kernels share one argument list; a work item is rows x cols of a tile, counted per XCD stream
-    auto flush = [&](auto kernel, auto ts, auto *Kp, auto *Gp, int rows, int cols) {
+    auto flush = [&](auto kernel, auto ts, auto *Kp, auto *Gp, int rows, int cols, auto... more) {
         using TS = decltype(ts);
         hipLaunchKernelGGL(kernel, dim3(clamp_grid(8 * job.xcd_len * (T / rows) * (T / cols), job.grid_cap)), dim3(kBlock), 0, s,
-                           (const TS *)st.tiles, (TS *)job.dst, job.work_xcd, job.xcd_len, Kp, Gp, st.pair_stride, pstart, st.pcap, npairs, st.tm);
+                           (const TS *)st.tiles, (TS *)job.dst, job.work_xcd, job.xcd_len, Kp, Gp, st.pair_stride, pstart, st.pcap, npairs, st.tm, more...);
     };
     switch (p.family) {
         case kInvalid: return hipErrorInvalidValue;
@@ -86,14 +88,15 @@ hipError_t launch_downdate(const DevState &st, const PassJob &job, int storage, 
             break;
         case kMfma64:                                   // (f64 tiles of edge 128, float tiles of edge 256)
             if (p.elt == 4) {
-                if (p.chunk == 4) flush(k_flush_mfma<float, 256, 4>, float{}, st.Kp, st.Gp, 64, 128);
-                else flush(k_flush_mfma<float, 256, 8>, float{}, st.Kp, st.Gp, 64, 128);
-            } else if (p.cols == 64) flush(k_flush_mfma<double, 128, 4, 64, 5>, double{}, st.Kp, st.Gp, 64, 64);
-            else if (p.chunk == 4) flush(k_flush_mfma<double, 128, 4>, double{}, st.Kp, st.Gp, 64, 128);
-            else flush(k_flush_mfma<double, 128, 8>, double{}, st.Kp, st.Gp, 64, 128);
+                if (p.chunk == 4) flush(k_flush_mfma<float, 256, 4>, float{}, st.Kp, st.Gp, 64, 128, live);
+                else flush(k_flush_mfma<float, 256, 8>, float{}, st.Kp, st.Gp, 64, 128, live);
+            } else if (p.cols == 64) flush(k_flush_mfma<double, 128, 4, 64, 5>, double{}, st.Kp, st.Gp, 64, 64, live);
+            else if (p.chunk == 4) flush(k_flush_mfma<double, 128, 4>, double{}, st.Kp, st.Gp, 64, 128, live);
+            else flush(k_flush_mfma<double, 128, 8>, double{}, st.Kp, st.Gp, 64, 128, live);
             break;
         case kDowndateW:
         case kDowndate: {
+            bool oversize = false;
             const bool built = with_shape(ValuShapes{}, p, [&](auto shape) {
                 using TS = typename decltype(shape)::TS;
                 constexpr int kT = decltype(shape)::T, kSlab = decltype(shape)::slab, kLanes = kT / Lane16<TS>::kCols;
@@ -102,17 +105,31 @@ hipError_t launch_downdate(const DevState &st, const PassJob &job, int storage, 
                 const dim3 grid(clamp_grid(job.nwork * (kT / kSlab), job.grid_cap)), grid_xcd(clamp_grid(8 * job.xcd_len * (kT / kSlab), job.grid_cap));
                 if constexpr (kLanes != 64 && kLanes != 32) {
                     hipLaunchKernelGGL((k_downdate<TS, kT, kSlab>), grid, dim3(kBlock), 0, s, src, dst, job.work, job.nwork, st.Kp, st.Gp,
-                                       st.pair_stride, pstart, st.pcap, npairs, st.tm);
+                                       st.pair_stride, pstart, st.pcap, npairs, st.tm, live);
                 } else {
+                    // the one list's item space (k_downdate_w: head, tail_shift): every tile whole -- or, under a bound, the tiles of the
+                    // last tile row (the entries from job.nwork_head on) only up to the slab that holds the bound, rounded up to a power of two
+                    constexpr int kSlabs = kT / kSlab;
+                    int64_t head = job.nwork * kSlabs, items = head;
+                    int tail_shift = 0;
+                    if (live != INT_MAX && job.nwork_head >= 0 && job.nwork_head < job.nwork) {
+                        const int in_last = live - (live - 1) / kT * kT, slabs = (in_last + kSlab - 1) / kSlab;
+                        while ((1 << tail_shift) < slabs) ++tail_shift;
+                        head = job.nwork_head * kSlabs;
+                        items = head + ((job.nwork - job.nwork_head) << tail_shift);
+                    }
+                    if (!p.xcd && items > INT_MAX) { oversize = true; return; }      // (k_downdate_w counts the one list's items in 32 bits)
+                    const dim3 grid_list(clamp_grid(items, job.grid_cap));
                     auto per_row = [&](auto kernel, dim3 g, const int2 *list, int64_t n, auto next) {
-                        hipLaunchKernelGGL(kernel, g, dim3(kBlock), 0, s, src, dst, list, n, st.Kp, st.Gp, st.pair_stride, pstart, st.pcap, npairs, st.tm, next);
+                        hipLaunchKernelGGL(kernel, g, dim3(kBlock), 0, s, src, dst, list, n, st.Kp, st.Gp, st.pair_stride, pstart, st.pcap, npairs, st.tm, next, live,
+                                           (int)head, tail_shift);
                     };
                     if (p.xcd) per_row(k_downdate_w<TS, kT, kSlab, true>, grid_xcd, job.work_xcd, job.xcd_len, NoNextRow{});
-                    else if (p.rowpanel) per_row(k_downdate_w<TS, kT, kSlab, false, true>, grid, job.work, job.nwork, *job.nx);
-                    else per_row(k_downdate_w<TS, kT, kSlab, false>, grid, job.work, job.nwork, NoNextRow{});
+                    else if (p.rowpanel) per_row(k_downdate_w<TS, kT, kSlab, false, true>, grid_list, job.work, job.nwork, *job.nx);
+                    else per_row(k_downdate_w<TS, kT, kSlab, false>, grid_list, job.work, job.nwork, NoNextRow{});
                 }
             });
-            if (!built) return hipErrorInvalidValue;
+            if (!built || oversize) return hipErrorInvalidValue;
             if (extracted) *extracted = p.rowpanel;
             break;
         }
