@@ -6,6 +6,8 @@
 // between calls: every call factors.  Unsharded only: the load reads every tile, and a shard holds only its own.
 // ekf_sample_map is the same factorisation (factor_run below is the body of both) with the draws x + C xi queued behind it, a chunk of
 // factor_chunk() draws at a time through pinned staging that does not grow with the number of draws.
+// ekf_solve_map is the same body again with the other direction queued behind the factorisation: C^-1 B or P^-1 B for the caller's k
+// right-hand sides, through the same chunks, slots and events.
 #pragma once
 namespace {
 constexpr int kSampleSlots = 4;            // chunks of pinned staging per direction (ekf_handle::ev_fslot)
@@ -27,6 +29,12 @@ void factor_release(ekf_handle *h) {
     h->bytes -= h->fs_bytes;
     h->fs_bytes = 0;
     h->fs_rows = -1;
+    // the solves' part
+    if (h->d_fsolve) hipFree(h->d_fsolve);
+    h->d_fsolve = nullptr;
+    h->bytes -= h->fv_bytes;
+    h->fv_bytes = 0;
+    h->fv_rows = -1;
 }
 
 // doubles of the second allocation for `rows` rows: the right-hand sides, the result block and the pivots, the reference states, L_r's
@@ -91,7 +99,29 @@ int32_t sample_alloc(ekf_handle *h, int64_t rows) {
     return EKF_OK;
 }
 
-// The body of ekf_factor_map and of ekf_sample_map (xi given: k draws, out their samples; ref is then NULL).  Order as in
+// ... and what the solves need on top of both (after sample_alloc of the same call): the inverses of the diagonal tiles.
+int32_t solve_alloc(ekf_handle *h, int64_t rows) {
+    if (h->fv_rows >= rows) return EKF_OK;
+    if (h->d_fsolve) hipFree(h->d_fsolve);
+    h->d_fsolve = nullptr;
+    h->bytes -= h->fv_bytes;
+    h->fv_bytes = 0;
+    h->fv_rows = -1;
+    const size_t inv = (size_t)solve_inverse_doubles(rows);
+    const size_t dev_bytes = (inv ? inv : 1) * sizeof(double);
+    const hipError_t e = hipMalloc((void **)&h->d_fsolve, dev_bytes);
+    if (e != hipSuccess) {
+        factor_release(h);
+        return fail(h, EKF_ERR_HIP, "solve_map: the inverses of the diagonal tiles could not be allocated; nothing was changed", e);
+    }
+    h->fv_rows = rows;
+    h->fv_bytes = (int64_t)dev_bytes;
+    h->bytes += h->fv_bytes;
+    return EKF_OK;
+}
+
+// The body of ekf_factor_map, of ekf_sample_map and of ekf_solve_map (form < 0: the draws; form 0 / 1: xi is B, the right-hand sides,
+// and out is P^-1 B / C^-1 B).  What follows speaks of ekf_sample_map (xi given: k draws, out their samples; ref is then NULL).  Order as in
 // ekf_nearest_landmarks: the rungs, with what depends on N checked once N is exact -> every allocation -> the flush -> the launches, none
 // waited for -> ONE readback (the result block and the pivots) -> the sums, on the host, in index order.  The draws go between the finish
 // and the readback: per chunk the upload of a pinned slot, the two launches and the download into a pinned slot, queued back to back; the
@@ -100,20 +130,21 @@ int32_t sample_alloc(ekf_handle *h, int64_t rows) {
 // slots take the host's packing and unpacking out of that line, nothing more.  `queued` is set once the launches begin: out is written
 // only from there on (slots are unpacked into it before the status is known).
 int32_t factor_body(ekf_handle *h, const std::string &who, const double *ref, int32_t nref, ekf_factor_info *info, double *d2, const double *xi,
-                    int64_t k, double *out, bool &queued) {
+                    int64_t k, double *out, int form, bool &queued) {
     TRY(edit_unsharded(h, who, "the factorisation reads and updates every tile of the lower triangle, and every shard holds only its own tiles"));
     TRY(edit_settled(h, who));
     const int64_t N = h->N, n = 3 + 2 * N;                 // (N is exact only now)
     for (int64_t i = 0; i < (int64_t)nref * n; ++i)
         REQUIRE(h, std::isfinite(ref[i]), EKF_ERR_INVALID_ARG, (who + "ref is not finite").c_str());
     if (xi)
-        for (int64_t i = 0; i < k * n; ++i) REQUIRE(h, std::isfinite(xi[i]), EKF_ERR_INVALID_ARG, (who + "xi is not finite").c_str());
+        for (int64_t i = 0; i < k * n; ++i) REQUIRE(h, std::isfinite(xi[i]), EKF_ERR_INVALID_ARG, (who + (form < 0 ? "xi is not finite" : "B is not finite")).c_str());
     const int TF = factor_tile_edge();
     FactorMapArgs a = {};
     a.tm = ekf_make_tilemap(TF, 1, 0);
     a.N = N; a.rows = a.tm.padded(2 * N); a.nref = nref; a.ref_stride = n;
     TRY(factor_alloc(h, a.rows));
     if (xi) TRY(sample_alloc(h, a.rows));
+    if (xi && form >= 0) TRY(solve_alloc(h, a.rows));
     TRY(edit_flushed(h));
     TRY(refresh_work(h));
     a.tiles = h->d_ftiles;
@@ -131,7 +162,8 @@ int32_t factor_body(ekf_handle *h, const std::string &who, const double *ref, in
     }
     // timed by family: the load, the right-hand sides and the tail under EKF_KERNEL_COMPACT, the diagonal tiles and the panels under
     // EKF_KERNEL_GATHER, the trailing updates under EKF_KERNEL_DOWNDATE; the draws' apply pass under EKF_KERNEL_ASSOCIATE (free in this
-    // call) and their sums under EKF_KERNEL_COMPACT
+    // call) and their sums under EKF_KERNEL_COMPACT; the solves' forward sweep of a chunk as ONE bracket under EKF_KERNEL_ASSOCIATE, its
+    // backward sweep as one under EKF_KERNEL_APPEND (both free in this call), the inverses and the robot tail under EKF_KERNEL_COMPACT
     if (N > 0) TIMED(h, EKF_KERNEL_COMPACT, launch_factor_load(h->st, a, h->storage, h->stream));
     const int64_t nF = a.rows / TF;
     for (int64_t c = 0; c < nF; ++c) {
@@ -159,6 +191,9 @@ int32_t factor_body(ekf_handle *h, const std::string &who, const double *ref, in
         FactorSampleArgs sa = {};
         double *d_xi = h->d_fsample, *d_y = d_xi + sample_chunk_doubles(h->fs_rows);
         sa.xi = d_xi; sa.y = d_y; sa.part = d_y + sample_chunk_doubles(h->fs_rows); sa.ld = ld;
+        FactorSolveArgs sv = {};
+        sv.b = d_xi; sv.y = d_y; sv.inv = h->d_fsolve; sv.ld = ld; sv.form = form;
+        if (form >= 0) TIMED(h, EKF_KERNEL_COMPACT, launch_solve_map(a, sv, 0, 0, h->stream));
         for (int64_t j = 0; j < nchunks; ++j) {
             const int slot = (int)(j % kSampleSlots);
             if (j >= kSampleSlots) {
@@ -173,9 +208,23 @@ int32_t factor_body(ekf_handle *h, const std::string &who, const double *ref, in
                 std::memcpy(u + c * ld + a.rows, row, 3 * sizeof(double));
             }
             HIPCHK(h, hipMemcpyAsync(d_xi, u, chunk * sizeof(double), hipMemcpyHostToDevice, h->stream));
-            TIMED(h, EKF_KERNEL_ASSOCIATE, launch_factor_sample(h->st, a, sa, 0, h->stream));
-            TIMED(h, EKF_KERNEL_COMPACT, launch_factor_sample(h->st, a, sa, 1, h->stream));
-            HIPCHK(h, hipMemcpyAsync(h->h_fy + (size_t)slot * chunk, d_y, chunk * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+            if (form < 0) {
+                TIMED(h, EKF_KERNEL_ASSOCIATE, launch_factor_sample(h->st, a, sa, 0, h->stream));
+                TIMED(h, EKF_KERNEL_COMPACT, launch_factor_sample(h->st, a, sa, 1, h->stream));
+            } else {
+                // the sweeps, sequential in the tile index: stream order is the only order between their workgroups
+                {
+                    TimedLaunch tl(h, EKF_KERNEL_ASSOCIATE);
+                    for (int64_t c = 0; c < nF; ++c) HIPCHK(h, launch_solve_map(a, sv, 1, (int)c, h->stream));
+                }
+                TIMED(h, EKF_KERNEL_COMPACT, launch_solve_map(a, sv, 2, 0, h->stream));
+                if (form == 0) {
+                    TimedLaunch tl(h, EKF_KERNEL_APPEND);
+                    for (int64_t c = nF - 1; c >= 0; --c) HIPCHK(h, launch_solve_map(a, sv, 3, (int)c, h->stream));
+                }
+            }
+            // P^-1 B is left in the chunk of right-hand sides, everything else in the chunk behind it
+            HIPCHK(h, hipMemcpyAsync(h->h_fy + (size_t)slot * chunk, form == 0 ? d_xi : d_y, chunk * sizeof(double), hipMemcpyDeviceToHost, h->stream));
             HIPCHK(h, hipEventRecord(h->ev_fslot[slot], h->stream));
         }
     }
@@ -215,9 +264,9 @@ int32_t factor_body(ekf_handle *h, const std::string &who, const double *ref, in
 // ... and no half-written samples: a call that fails once its launches have begun (EKF_ERR_HIP) leaves every entry of out NaN, as a
 // pivot that failed does; a refusal before that leaves out untouched.
 int32_t factor_run(ekf_handle *h, const std::string &who, const double *ref, int32_t nref, ekf_factor_info *info, double *d2, const double *xi,
-                   int64_t k, double *out) {
+                   int64_t k, double *out, int form = -1) {
     bool queued = false;
-    const int32_t rc = factor_body(h, who, ref, nref, info, d2, xi, k, out, queued);
+    const int32_t rc = factor_body(h, who, ref, nref, info, d2, xi, k, out, form, queued);
     if (rc != EKF_OK && xi && queued)
         for (int64_t i = 0; i < k * (3 + 2 * h->N); ++i) out[i] = NAN;
     return rc;
@@ -245,5 +294,16 @@ int32_t ekf_sample_map(ekf_handle *h, const double *xi, int64_t k, double *out, 
     REQUIRE(h, info != nullptr, EKF_ERR_INVALID_ARG, (who + "null info").c_str());
     REQUIRE(h, k >= 1, EKF_ERR_INVALID_ARG, (who + "k is at least 1 draw").c_str());
     return factor_run(h, who, nullptr, 0, info, nullptr, xi, k, out);
+}
+
+int32_t ekf_solve_map(ekf_handle *h, int32_t form, const double *B, int64_t k, double *out, ekf_factor_info *info) {
+    if (!h) return EKF_ERR_INVALID_ARG;
+    const std::string who = "solve_map: ";
+    REQUIRE(h, B != nullptr, EKF_ERR_INVALID_ARG, (who + "null B").c_str());
+    REQUIRE(h, out != nullptr, EKF_ERR_INVALID_ARG, (who + "null out").c_str());
+    REQUIRE(h, info != nullptr, EKF_ERR_INVALID_ARG, (who + "null info").c_str());
+    REQUIRE(h, k >= 1, EKF_ERR_INVALID_ARG, (who + "k is at least 1 right-hand side").c_str());
+    REQUIRE(h, form == EKF_SOLVE_FULL || form == EKF_SOLVE_HALF, EKF_ERR_INVALID_ARG, (who + "form is EKF_SOLVE_FULL or EKF_SOLVE_HALF").c_str());
+    return factor_run(h, who, nullptr, 0, info, nullptr, B, k, out, form);
 }
 }  // extern "C"

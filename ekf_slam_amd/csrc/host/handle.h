@@ -218,6 +218,10 @@ struct ekf_handle {
     double *d_fsample = nullptr, *h_fxi = nullptr, *h_fy = nullptr;
     hipEvent_t ev_fslot[4] = { nullptr, nullptr, nullptr, nullptr };
     int64_t fs_rows = -1, fs_bytes = 0;
+    // ekf_solve_map, part of the same scratch (released with it): the inverses of the factor's diagonal tiles, for fv_rows rows; the
+    // chunks and the pinned slots are ekf_sample_map's.  fv_bytes are counted in `bytes`.
+    double *d_fsolve = nullptr;
+    int64_t fv_rows = -1, fv_bytes = 0;
     // ---- linear observations (ekf_observe_linear / ekf_linear_innovation) ----
     // two records on the device and in pinned memory (the update-step's, then the probe's; behind them in the pinned area the two counters
     // ekf_linear_rejections reads), the device counters of launches that did not apply, the event behind a waited step's readback

@@ -178,6 +178,16 @@ EKF_HD int64_t factor_segment_base(int64_t I, int64_t S) {
     return S * g * (g + 1) / 2 + (I - g * S) * (g + 1);
 }
 
+// k_solve_* (solve_map.h): C^-1 B or P^-1 B for one chunk of kFactorChunk right-hand sides behind the same factorisation.  The chunks
+// have FactorSampleArgs' layout: a right-hand side is a column in elimination order, ld doubles apart.
+struct FactorSolveArgs {
+    double *b;                // in: the right-hand sides of the chunk; the forward sweep updates it in place; form 0: P^-1 b is left here
+    double *y;                // the forward sweep's result u = C^-1 b (form 1's result); the backward sweep updates it in place
+    double *inv;              // rows / tm.T tiles of edge tm.T, row-major: the inverses of the factor's diagonal tiles
+    int64_t ld;               // >= rows + 3
+    int32_t form;             // 0: P^-1 b (EKF_SOLVE_FULL), 1: C^-1 b (EKF_SOLVE_HALF)
+};
+
 // k_predict_model (predict_model.h): a chain of m <= kPredictModelMax motion steps through the models of ekfm::motion_eval, carried out in
 // order by ONE launch that reads buffer cur and writes buffer cur ^ 1, as k_predict.  No tile is read: the storage type does not matter.
 // The steps travel in the argument block, M as its six unique entries -- 80 bytes a step, 2.5 KiB at 32 (nine entries a step would not fit

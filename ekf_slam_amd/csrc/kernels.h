@@ -69,6 +69,12 @@ hipError_t launch_factor_finish(const DevState &st, const FactorMapArgs &a, hipS
 int factor_chunk();
 int64_t factor_partial_doubles(int64_t rows);
 hipError_t launch_factor_sample(const DevState &st, const FactorMapArgs &a, const FactorSampleArgs &sa, int part, hipStream_t s);
+// k_solve_* (solve_map.h): C^-1 B or P^-1 B for one chunk of factor_chunk() right-hand sides, queued behind launch_factor_finish of the
+// same `a` (a.lr_off given).  part 0: the inverses of the diagonal tiles into sv.inv (solve_inverse_doubles(a.rows) doubles), once a
+// call; part 1: step c of the forward sweep, c = 0 .. rows / T - 1 ascending; part 2: the robot tail; part 3: step c of the backward
+// sweep, c descending (sv.form 0 only).  All return at once where a pivot failed.
+int64_t solve_inverse_doubles(int64_t rows);
+hipError_t launch_solve_map(const FactorMapArgs &a, const FactorSolveArgs &sv, int part, int c, hipStream_t s);
 
 // fused_predict != nullptr folds predict(u) into the correction (one launch instead of two, identical arithmetic)
 // fuse_downdate: the kernel also applies its pair to the landmark block (small maps: a.n_mm <= gather_fuse_max_rows(), one

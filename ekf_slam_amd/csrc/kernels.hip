@@ -64,6 +64,7 @@ namespace {
 #include "nearest.h"          // the candidate search in front of a merge: k_nearest
 #include "factor_map.h"       // the Cholesky factorisation of P in a scratch store: k_factor_load / _rhs / _diag / _panel / _trail / _finish
 #include "sample_map.h"       // ... and the draws x + C xi behind it: k_factor_apply, k_factor_sample
+#include "solve_map.h"        // ... and the solves C^-1 B, P^-1 B: k_solve_invert, k_solve_forward, k_solve_tail, k_solve_backward
 
 }  // namespace
 

@@ -358,3 +358,24 @@ hipError_t launch_factor_sample(const DevState &st, const FactorMapArgs &a, cons
         hipLaunchKernelGGL((k_factor_sample<kFactorTile, kFactorSegment>), dim3((unsigned)(nF + 1)), dim3(kFactorBlock), 0, s, st, a, sa);
     return hipGetLastError();
 }
+
+// ---- the solves behind it (solve_map.h: k_solve_invert, k_solve_forward, k_solve_tail, k_solve_backward) ----
+int64_t solve_inverse_doubles(int64_t rows) { return rows * (int64_t)kFactorTile; }
+
+hipError_t launch_solve_map(const FactorMapArgs &a, const FactorSolveArgs &sv, int part, int c, hipStream_t s) {
+    // every index the kernels form lies inside the chunks (ld), the inverse tiles (one per tile row) and the store (c inside the grid)
+    if (!factor_args_ok(a) || !a.lr_off || !sv.b || !sv.y || !sv.inv || sv.ld < a.rows + 3 || (sv.form != 0 && sv.form != 1)) return hipErrorInvalidValue;
+    const int64_t nF = a.rows / kFactorTile;
+    if (part == 0) {
+        if (nF == 0) return hipSuccess;
+        hipLaunchKernelGGL(k_solve_invert<kFactorTile>, dim3((unsigned)nF), dim3(64), 0, s, a, sv);
+    } else if (part == 1 || part == 3) {
+        if (c < 0 || c >= nF || (part == 3 && sv.form != 0)) return hipErrorInvalidValue;
+        if (part == 1) hipLaunchKernelGGL(k_solve_forward<kFactorTile>, dim3((unsigned)(nF - c)), dim3(4 * kFactorTile), 0, s, a, sv, c);
+        else hipLaunchKernelGGL(k_solve_backward<kFactorTile>, dim3((unsigned)(c + 1)), dim3(4 * kFactorTile), 0, s, a, sv, c);
+    } else if (part == 2)
+        hipLaunchKernelGGL(k_solve_tail, dim3(1), dim3(kFactorBlock), 0, s, a, sv);
+    else
+        return hipErrorInvalidValue;
+    return hipGetLastError();
+}

@@ -558,6 +558,20 @@ class Engine:
         self._check(self.lib.ekf_sample_map(self.h, _p(xi), k, _p(out), ctypes.byref(info)))
         return marshal.sample_result(args)
 
+    # ---- the other direction: C^-1 B and P^-1 B from the same factorisation (include/ekfslam.h: ekf_solve_map) ----
+    def solve_map(self, B, form="full"):
+        """(out, info): row q of `out` is P^-1 b_q (form="full") or C^-1 b_q (form="half") for the k right-hand sides in `B` (one of
+        3 + 2 N entries, or one per row; in x's order).  C is the Cholesky factor of P in factor_map's elimination order (the landmark
+        block first, the robot last); the half form is C^-1 b mapped back to x's order, so |out_q|^2 = b_q' P^-1 b_q and the half form
+        of sample_map's samples minus x returns the draws.  No entry is wrapped.  `info` is factor_map()'s dict without d2; where P
+        is not definite every entry is NaN.  One factorisation per call whatever k is; read-only and synchronising (ekf_solve_map)."""
+        return self._solve_map(marshal.solve_args(B, form, 3 + 2 * self.N))
+
+    def _solve_map(self, args):
+        form, B, k, out, info = args
+        self._check(self.lib.ekf_solve_map(self.h, form, _p(B), k, _p(out), ctypes.byref(info)))
+        return marshal.solve_result(args)
+
     @staticmethod
     def model_invert(model, xr, z, lib=None):
         """(t, Gx, Gz): the landmark that z observes from the robot state xr = (x, y, theta in degrees) through EKF_MODEL_RANGE_BEARING

@@ -225,21 +225,21 @@ def factor_result(args):
     return out
 
 
-def sample_args(xi, n, who="sample_map"):
+def sample_args(xi, n, who="sample_map", what=("xi", "draw")):
     """(xi, k, out, info) of sample_map as the ABI takes them, the arrays kept so that sample_result reads what the call wrote.  xi: one
     draw of n = 3 + 2 N finite entries, or k >= 1 of them as the rows of a 2-D array (contiguous F64 from here on).  Anything else is
-    refused here, before any call."""
+    refused here, before any call.  `what`: how the messages name the array and one row of it."""
     if xi is None:
-        raise ValueError("%s: xi is the draws, one per row" % who)
+        raise ValueError("%s: %s is the %ss, one per row" % (who, what[0], what[1]))
     xv = np.ascontiguousarray(np.asarray(xi, dtype=np.float64))
     if xv.ndim == 1:
         xv = xv.reshape(1, -1)
     if xv.ndim != 2 or xv.shape[0] < 1:
-        raise ValueError("%s: xi is k >= 1 draws, one per row" % who)
+        raise ValueError("%s: %s is k >= 1 %ss, one per row" % (who, what[0], what[1]))
     if xv.shape[1] != n:
-        raise ValueError("%s: a draw has 3 + 2 N = %d entries, got %d" % (who, n, xv.shape[1]))
+        raise ValueError("%s: a %s has 3 + 2 N = %d entries, got %d" % (who, what[1], n, xv.shape[1]))
     if not np.all(np.isfinite(xv)):
-        raise ValueError("%s: xi is not finite" % who)
+        raise ValueError("%s: %s is not finite" % (who, what[0]))
     return xv, ctypes.c_int64(xv.shape[0]), np.full(xv.shape, np.nan), L.EkfFactorInfo()
 
 
@@ -249,6 +249,23 @@ def sample_result(args):
     res = factor_result((None, None, info, None))
     del res["d2"]
     return out, res
+
+
+SOLVE_FORMS = {"full": 0, "half": 1}        # EKF_SOLVE_FULL, EKF_SOLVE_HALF
+
+
+def solve_args(B, form, n, who="solve_map"):
+    """(form, B, k, out, info) of solve_map as the ABI takes them, the arrays kept so that solve_result reads what the call wrote.  B as
+    sample_args takes xi: one right-hand side of n = 3 + 2 N finite entries, or k >= 1 of them as rows; form is "full" or "half"."""
+    if form not in SOLVE_FORMS:
+        raise ValueError('%s: form is "full" (P^-1 b) or "half" (C^-1 b)' % who)
+    Bv, k, out, info = sample_args(B, n, who, ("B", "right-hand side"))
+    return ctypes.c_int32(SOLVE_FORMS[form]), Bv, k, out, info
+
+
+def solve_result(args):
+    """What solve_map returns from what the call wrote: (out, one row per right-hand side; the dict of factor_result without 'd2')."""
+    return sample_result(args[1:])
 
 
 def model_inits(entries, who="append_model"):

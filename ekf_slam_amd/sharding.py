@@ -170,6 +170,11 @@ class ShardGroup:
         is the library's (EKF_ERR_INVALID_ARG, nothing changed)."""
         return self.shards[0].sample_map(xi)
 
+    def solve_map(self, B, form="full"):
+        """Not built for a shard group, as factor_map, whose factorisation it is.  The call goes to the first shard so that the refusal
+        is the library's (EKF_ERR_INVALID_ARG, nothing changed)."""
+        return self.shards[0].solve_map(B, form)
+
     def correct(self, z, R, idx0):
         for e in self.shards:
             e.correct_begin(z, R, idx0)

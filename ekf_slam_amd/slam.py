@@ -340,6 +340,63 @@ class _EkfBase:
         p = hits / float(int(k))
         return p, math.sqrt(p * (1.0 - p) / int(k))
 
+    def solve_map(self, B, form="full"):
+        """(out, info): P^-1 b (form="full") or the whitened C^-1 b (form="half") for the right-hand sides in the rows of B, from ONE
+        factorisation on the device (Engine.solve_map; ekf_solve_map).  Plain linear algebra: no entry is wrapped.  Where P is not
+        definite every entry is NaN and `info` (factor_map's dict without d2) says where.  Read-only: nothing goes into the
+        trajectory log.  The reference has no such method."""
+        return self._e.solve_map(B, form)
+
+    def _definite_solve(self, who, B, form):
+        out, info = self._e.solve_map(B, form)
+        if not info["definite"]:
+            raise ValueError("%s: P is not positive definite (factor_map says where: bad_index %d)" % (who, info["bad_index"]))
+        return out
+
+    def _state_columns(self, who, idx):
+        """The indices into x of the robot (idx None) or of the landmarks idx, both entries of each, in idx's order."""
+        if idx is None:
+            return np.arange(3)
+        lm = np.asarray(idx, dtype=np.int64).reshape(-1)
+        if lm.size < 1 or lm.min() < 0 or lm.max() >= self._e.N or np.unique(lm).size != lm.size:
+            raise ValueError("%s: idx is distinct landmarks 0 .. N - 1, or None for the robot" % who)
+        return (3 + 2 * lm[:, None] + np.arange(2)[None, :]).reshape(-1)
+
+    def information_columns(self, idx=None):
+        """The columns of the information matrix Lambda = P^-1 that belong to the robot (idx None: 3 columns) or to the landmarks idx
+        (two each, in idx's order), as an (3 + 2 N) x m array, by unit right-hand sides through one solve_map call.  An entry that
+        is (nearly) zero means the two states are conditionally independent given the rest.  ValueError where P is not positive
+        definite."""
+        cols = self._state_columns("information_columns", idx)
+        n = 3 + 2 * self._e.N
+        B = np.zeros((cols.size, n))
+        B[np.arange(cols.size), cols] = 1.0
+        return self._definite_solve("information_columns", B, "full").T
+
+    def conditional_covariance(self, idx):
+        """inv(Lambda_AA) for the landmarks idx (2 m x 2 m, in idx's order): the covariance of that group GIVEN every other state, the
+        Schur complement P_AA - P_AB inv(P_BB) P_BA, from information_columns(idx).  How much smaller it is than the marginal block
+        of P says how much of what is known about the group is carried by the rest of the map."""
+        if idx is None:
+            raise ValueError("conditional_covariance: idx is the landmarks of the group")
+        cols = self._state_columns("conditional_covariance", idx)
+        Laa = self.information_columns(idx)[cols, :]
+        cov = np.linalg.inv(0.5 * (Laa + Laa.T))
+        return 0.5 * (cov + cov.T)
+
+    def mahalanobis(self, a, b):
+        """|C^-1 (a - b)|^2 = (a - b)' P^-1 (a - b) for two full states a and b (3 + 2 N entries each), the heading difference wrapped
+        into (-180, 180] as factor_map wraps x - ref: nees(x_true) is mahalanobis(x, x_true).  ValueError where P is not positive
+        definite."""
+        n = 3 + 2 * self._e.N
+        d = np.asarray(a, dtype=np.float64).reshape(-1) - np.asarray(b, dtype=np.float64).reshape(-1)
+        if d.size != n:
+            raise ValueError("mahalanobis: a state has 3 + 2 N = %d entries" % n)
+        if not -180.0 < d[2] <= 180.0:
+            d[2] = d[2] - 360.0 * math.ceil((d[2] - 180.0) / 360.0)
+        w = self._definite_solve("mahalanobis", d, "half")[0]
+        return float(w @ w)
+
     def fuse_duplicates(self, gate, R=None, max_merges=None):
         """The SIMPLEST complete fusion policy, not the fastest: repeat { search; take the candidate with the smallest (d2, i) at or
         below `gate`; merge_landmarks(keep=j, drop=i, R) } until none is left or `max_merges` merges were made.  One search plus

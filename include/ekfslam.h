@@ -668,6 +668,39 @@ int32_t ekf_factor_map(ekf_handle *h, const double *ref /* nref x (3 + 2N), may 
  * every entry of out NaN.  For a SUBSET of the landmarks: ekf_extract_map, then this call on the small handle. */
 int32_t ekf_sample_map(ekf_handle *h, const double *xi /* k x (3 + 2N), one row per draw */, int64_t k /* >= 1 */, double *out /* k x (3 + 2N) */,
                        ekf_factor_info *info);
+/* THE OTHER DIRECTION: C^-1 B AND P^-1 B for k right-hand sides the caller chooses, from ONE factorisation -- ekf_factor_map's again,
+ * with the two triangular solves queued behind it before the factor is forgotten.  B is k rows of 3 + 2 N finite entries in x's order.
+ * In ekf_factor_map's ELIMINATION ORDER (the landmark block m first, the robot r last) the factor is C = [L 0; W' L_r] and b = (b_m, b_r):
+ *       u_m = L^-1 b_m,      u_r = L_r^-1 (b_r - W' u_m),      z_r = L_r^-T u_r,      z_m = L^-T (u_m - W z_r).
+ *   EKF_SOLVE_HALF: row q of out is u = C^-1 b_q mapped back to x's order, out[0:3] = u_r and out[3:] = u_m: the WHITENED right-hand
+ *     side.  |out_q|^2 = b_q' P^-1 b_q (a Mahalanobis distance where b is a difference of states), and C^-1 (sample_q - x) returns
+ *     the draw xi_q of ekf_sample_map.  Like C, it depends on the elimination order.
+ *   EKF_SOLVE_FULL: row q of out is z = P^-1 b_q in x's order: the information vector with b = x, columns of the information matrix
+ *     with unit vectors.
+ * Plain linear algebra: NO entry is wrapped; wrap the heading entry of a state difference before the call.
+ * info is filled as by ekf_factor_map(h, NULL, 0, ..), bit for bit, and may not be NULL.  A P THAT IS NOT DEFINITE IS A RESULT: EKF_OK,
+ * info says where the factorisation stopped, and every entry of out is NaN.
+ * Promised: (1) row q of out depends on b_q alone -- the same right-hand side gives the same bits alone, first, last or in the middle
+ * of a batch of any k, across chunk boundaries; (2) B = 0 gives out = 0 in every entry; (3) two calls on the same state give the same
+ * bits: no atomics, no data-dependent order of summation.  Everything else is arithmetic in F64 with a forward error of a small
+ * multiple of cond(P) 2^-53.
+ * The right-hand sides are taken 16 at a time (ekf_sample_map's chunks, slots and events; the pinned staging does not grow with k).
+ * Once a call the diagonal tiles of L are inverted in parallel (rows / 64 tiles of scratch, 10 MB at 10 000 landmarks); per chunk the
+ * forward sweep is one launch per tile column, ascending -- every workgroup forms u_c = L_cc^-1 b_c for itself and then updates its
+ * own tile row, b_I -= L_Ic u_c, on the F64 matrix cores --, one small launch takes the robot tail, and for EKF_SOLVE_FULL the backward
+ * sweep mirrors the forward one over the tile rows, descending, with the transposed tiles.  STREAM ORDER IS THE ONLY ORDER between
+ * workgroups: 2 rows / 64 + 1 launches a chunk (half of that for EKF_SOLVE_HALF), no flags in memory, no atomics.
+ * The forward sweeps count under EKF_KERNEL_ASSOCIATE and the backward sweeps under EKF_KERNEL_APPEND (one bracket per chunk each),
+ * the inverses and the tails under EKF_KERNEL_COMPACT, the factorisation as in ekf_factor_map.
+ * Nothing is kept between calls: every call factors, so ask for all the right-hand sides of one state in one call.
+ * SYNCHRONISING and READ-ONLY exactly as ekf_factor_map.  Refused with nothing changed and nothing flushed: h, B, out or info NULL,
+ * k < 1, a form that is neither constant, a handle with world > 1 (a lone shard with cfg.force_sharded works) (EKF_ERR_INVALID_ARG);
+ * a sharded correction between begin and finish (EKF_ERR_STATE); then, once N is exact, a B entry that is not finite
+ * (EKF_ERR_INVALID_ARG); EKF_ERR_HIP if the scratch cannot be allocated, before anything is queued.  A refusal leaves out untouched;
+ * an EKF_ERR_HIP once the launches have begun leaves every entry of out NaN. */
+enum { EKF_SOLVE_FULL = 0, EKF_SOLVE_HALF = 1 };
+int32_t ekf_solve_map(ekf_handle *h, int32_t form, const double *B /* k x (3 + 2N), one row per right-hand side, x's order */,
+                      int64_t k /* >= 1 */, double *out /* k x (3 + 2N) */, ekf_factor_info *info);
 /* The step between the two: "WHICH landmark does this sighting belong to?", for a whole scan, under the conventions of ekf_observe_model.
  * ekf_associate keeps the reference's (signature-only by default, an unwrapped bearing, a range-scaled R) and cannot serve a filter
  * driven through the model calls.  For each of the m observations, d2(k, i) is, BIT FOR BIT, the d2 that ekf_model_innovation reports for

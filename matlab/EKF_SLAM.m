@@ -300,6 +300,17 @@ classdef EKF_SLAM < handle
             info = struct('n', v(1), 'definite', v(2) ~= 0, 'bad_index', v(3), 'bad_pivot', v(4), 'logdet', v(5), 'logdet_map', v(6), ...
                           'min_pivot', v(7), 'max_pivot', v(8));
         end
+        function [out, info] = solveMap(h, B, form)
+            % THE OTHER DIRECTION: out(:, q) = P \ B(:, q) (form 'full', the default) or the whitened C \ B(:, q) in x's order
+            % (form 'half': sum(out(:, q).^2) = B(:, q)' * (P \ B(:, q))) for the k columns of B (n x k, n = 3 + 2 N), from ONE
+            % factorisation on the GPU.  C is the Cholesky factor of P in factorMap's elimination order (the landmark block first, the
+            % robot last).  No entry is wrapped.  info is factorMap's struct; where P is not positive definite out is all NaN.
+            % Read-only.  Not a method of the reference.
+            if nargin < 3, form = 'full'; end
+            [out, v] = h.gateway('solve_map', double(B), double(strcmp(form, 'half')));
+            info = struct('n', v(1), 'definite', v(2) ~= 0, 'bad_index', v(3), 'bad_pivot', v(4), 'logdet', v(5), 'logdet_map', v(6), ...
+                          'min_pivot', v(7), 'max_pivot', v(8));
+        end
         function idx = addLandmarkRangeBearing(h, z, R, signature)
             % 'A landmark that is not in the map yet is seen at range z(1) and bearing z(2) (degrees, relative to the heading),
             % covariance R': it joins the map at the point that observation names.

@@ -27,7 +27,7 @@
  * (ekf_observe_model), the append through a model (ekf_append_model), the association of a scan under the models' conventions
  * (ekf_associate_model) and its one-to-one assignment (ekf_assign_model), the joint compatibility of a scan's pairings (ekf_joint_innovation) and their joint update
  * (ekf_observe_model_joint, relinearised: ekf_observe_model_joint_iterated), the relinearised model observation
- * (ekf_observe_model_iterated), the motion steps under them (ekf_predict_model), the join of a local map (ekf_join_map), the extraction of part of the map (ekf_extract_map), the map's change of frame (ekf_transform_map), the factorisation of P (ekf_factor_map) and the draws from the posterior behind it (ekf_sample_map) are the ones this gateway can live without: bound weakly, so that the gateway still links against a libekfslam (or a stand-in) that
+ * (ekf_observe_model_iterated), the motion steps under them (ekf_predict_model), the join of a local map (ekf_join_map), the extraction of part of the map (ekf_extract_map), the map's change of frame (ekf_transform_map), the factorisation of P (ekf_factor_map), the draws from the posterior behind it (ekf_sample_map) and the solves with the factor (ekf_solve_map) are the ones this gateway can live without: bound weakly, so that the gateway still links against a libekfslam (or a stand-in) that
  * predates them; their commands then raise a MATLAB error instead. */
 #if defined(__GNUC__)
 #pragma weak ekf_remove_landmarks
@@ -52,6 +52,7 @@
 #pragma weak ekf_transform_map
 #pragma weak ekf_factor_map
 #pragma weak ekf_sample_map
+#pragma weak ekf_solve_map
 #define HAVE_REMOVE_LANDMARKS (ekf_remove_landmarks != 0)
 #define HAVE_CONSTRAIN_LANDMARKS (ekf_constrain_landmarks != 0)
 #define HAVE_MERGE_LANDMARKS (ekf_merge_landmarks != 0)
@@ -74,6 +75,7 @@
 #define HAVE_TRANSFORM_MAP (ekf_transform_map != 0)
 #define HAVE_FACTOR_MAP (ekf_factor_map != 0)
 #define HAVE_SAMPLE_MAP (ekf_sample_map != 0)
+#define HAVE_SOLVE_MAP (ekf_solve_map != 0)
 #else
 #define HAVE_REMOVE_LANDMARKS 1
 #define HAVE_CONSTRAIN_LANDMARKS 1
@@ -96,6 +98,7 @@
 #define HAVE_TRANSFORM_MAP 1
 #define HAVE_FACTOR_MAP 1
 #define HAVE_SAMPLE_MAP 1
+#define HAVE_SOLVE_MAP 1
 #endif
 
 static void need(int nrhs, int want, const char *cmd) {
@@ -528,6 +531,29 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
             mexErrMsgIdAndTxt("ekfslam:usage", "sample_map: xi is n x k, n = 3 + 2 N entries a column and k >= 1 columns");
         mxArray *out = mxCreateDoubleMatrix((mwSize)n, k, mxREAL);
         const int32_t rc = ekf_sample_map(h, mxGetPr(prhs[2]), (int64_t)k, mxGetPr(out), &info);       /* (MATLAB arrays are column-major) */
+        if (rc != EKF_OK) { mxDestroyArray(out); check(h, rc); }
+        plhs[0] = out;
+        if (nlhs > 1) {
+            plhs[1] = mxCreateDoubleMatrix(1, 8, mxREAL);
+            double *o = mxGetPr(plhs[1]);
+            o[0] = (double)info.n; o[1] = (double)info.definite; o[2] = (double)(info.bad_index + 1); o[3] = info.bad_pivot;
+            o[4] = info.logdet; o[5] = info.logdet_map; o[6] = info.min_pivot; o[7] = info.max_pivot;
+        }
+        return;
+    }
+    if (!strcmp(cmd, "solve_map")) {              /* [out, info] = (h, B, form): P^-1 B (form 0) or C^-1 B (form 1) from one factorisation.  B: n x k, one
+                                                     right-hand side a column (n = 3 + 2 N, k >= 1); out: n x k, all NaN where P is not positive
+                                                     definite; info as factor_map's */
+        ekf_factor_info info;
+        need(nrhs, 4, cmd);
+        if (!HAVE_SOLVE_MAP) mexErrMsgIdAndTxt("ekfslam:usage", "solve_map: this libekfslam has no ekf_solve_map");
+        const int64_t n = nstate(h);
+        const mwSize nel = prhs[2] ? mxGetNumberOfElements(prhs[2]) : 0;
+        const mwSize k = nel / (mwSize)n;
+        if (nel == 0 || !mxGetPr(prhs[2]) || k * (mwSize)n != nel)
+            mexErrMsgIdAndTxt("ekfslam:usage", "solve_map: B is n x k, n = 3 + 2 N entries a column and k >= 1 columns");
+        mxArray *out = mxCreateDoubleMatrix((mwSize)n, k, mxREAL);
+        const int32_t rc = ekf_solve_map(h, (int32_t)mxGetScalar(prhs[3]), mxGetPr(prhs[2]), (int64_t)k, mxGetPr(out), &info);   /* (MATLAB arrays are column-major) */
         if (rc != EKF_OK) { mxDestroyArray(out); check(h, rc); }
         plhs[0] = out;
         if (nlhs > 1) {
