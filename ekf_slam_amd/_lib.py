@@ -210,6 +210,7 @@ SIGNATURES = {
     "ekf_factor_map": (_i32, [_vp, _dp, _i32, ctypes.POINTER(EkfFactorInfo), _dp]),
     "ekf_sample_map": (_i32, [_vp, _dp, _i64, _dp, ctypes.POINTER(EkfFactorInfo)]),
     "ekf_solve_map": (_i32, [_vp, _i32, _dp, _i64, _dp, ctypes.POINTER(EkfFactorInfo)]),
+    "ekf_multiply_map": (_i32, [_vp, _dp, _i64, _dp]),
     "ekf_associate_model": (_i32, [_vp, ctypes.POINTER(EkfModelObs), _i64, ctypes.POINTER(EkfModelMatch), _dp]),
     "ekf_assign_model": (_i32, [_vp, ctypes.POINTER(EkfModelObs), _i64, ctypes.POINTER(EkfModelAssigned), ctypes.POINTER(EkfModelMatch),
                                 ctypes.POINTER(_i64), _dp, _dp]),

@@ -18,6 +18,7 @@
 #include "host/extract_map.h"  // part of the map taken out into another handle, in the map frame or the robot frame: extract_map
 #include "host/transform_map.h" // the whole map moved into another frame, in place: transform_map
 #include "host/factor_map.h"   // the Cholesky factorisation of P in a scratch store -- definiteness, log det, NEES: factor_map
+#include "host/multiply_map.h" // the plain product P B on the handle's own tile store, no factorisation: multiply_map
 #include "host/associate_model.h" // which landmark a sighting belongs to, a scan per call: associate_model
 #include "host/assign_model.h" // ... and the scan assigned to the map one-to-one: assign_model
 #include "host/model_assigned.h" // ... and assigned, then applied step by step with no wait between: observe_model_assigned, assigned_scan_result

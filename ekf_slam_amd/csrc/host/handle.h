@@ -222,6 +222,13 @@ struct ekf_handle {
     // chunks and the pinned slots are ekf_sample_map's.  fv_bytes are counted in `bytes`.
     double *d_fsolve = nullptr;
     int64_t fv_rows = -1, fv_bytes = 0;
+    // ekf_multiply_map (host/multiply_map.h), a scratch of its own (the factor store is NOT part of it): in ONE device allocation a chunk of
+    // vectors, a chunk of products and the partial blocks of one tile pass, for pm_rows rows; kSampleSlots chunks of pinned staging per
+    // direction and the event behind each slot's readback.  Allocated at the first call, grown when N has outgrown it, released by
+    // ekf_destroy itself.  pm_bytes of the device part are counted in `bytes`.
+    double *d_pmul = nullptr, *h_pmb = nullptr, *h_pmy = nullptr;
+    hipEvent_t ev_pmslot[4] = { nullptr, nullptr, nullptr, nullptr };
+    int64_t pm_rows = -1, pm_bytes = 0;
     // ---- linear observations (ekf_observe_linear / ekf_linear_innovation) ----
     // two records on the device and in pinned memory (the update-step's, then the probe's; behind them in the pinned area the two counters
     // ekf_linear_rejections reads), the device counters of launches that did not apply, the event behind a waited step's readback

@@ -188,6 +188,23 @@ struct FactorSolveArgs {
     int32_t form;             // 0: P^-1 b (EKF_SOLVE_FULL), 1: C^-1 b (EKF_SOLVE_HALF)
 };
 
+// k_multiply_tiles / k_multiply_sum (multiply_map.h): P B for one chunk of kFactorChunk vectors on the handle's OWN tile store (the DevState's
+// tile map: any edge, either storage kind).  A chunk has FactorSampleArgs' layout under the handle's tile edge: a vector is a column, ld
+// doubles apart -- entries [0, rows) the landmark part in x's order (zero from 2 N on), entries rows .. rows + 2 the robot's.  Tile row I
+// is cut into segments of S tiles (I / S + 1 of them).
+struct MultiplyMapArgs {
+    const double *b;          // the vectors of the chunk
+    double *y;                // their products, in the same layout (entries 2 N .. rows - 1 are not written)
+    double *dpart;            // factor_segment_base(rows / T, S) direct partial blocks of T x kFactorChunk doubles, row-major
+    double *tpart;            // row_base(rows / T) blocks of the same shape: the transposed partial of tile (I, J), J < I, at slot(I, J) (the diagonal slots stay unused)
+    double *wpart;            // rows / T parts of strip B_m, 3 x kFactorChunk doubles each
+    int64_t ld;               // >= rows + 3
+    int64_t N;                // landmarks
+    int64_t rows;             // 2 N rounded up to whole tile rows of the handle's store
+    int32_t S;                // tiles per segment, >= 1
+    int32_t cur;              // the live buffer of Prr and the strip (the diagonal copies: dcur of the DevState)
+};
+
 // k_predict_model (predict_model.h): a chain of m <= kPredictModelMax motion steps through the models of ekfm::motion_eval, carried out in
 // order by ONE launch that reads buffer cur and writes buffer cur ^ 1, as k_predict.  No tile is read: the storage type does not matter.
 // The steps travel in the argument block, M as its six unique entries -- 80 bytes a step, 2.5 KiB at 32 (nine entries a step would not fit

@@ -75,6 +75,14 @@ hipError_t launch_factor_sample(const DevState &st, const FactorMapArgs &a, cons
 // sweep, c descending (sv.form 0 only).  All return at once where a pivot failed.
 int64_t solve_inverse_doubles(int64_t rows);
 hipError_t launch_solve_map(const FactorMapArgs &a, const FactorSolveArgs &sv, int part, int c, hipStream_t s);
+// k_multiply_tiles / k_multiply_sum / k_multiply_robot (multiply_map.h): P B for one chunk of factor_chunk() vectors on the handle's own tile store, no
+// factorisation in front.  multiply_segment(T): the tiles per segment for tile edge T (MultiplyMapArgs::S); multiply_partial_doubles:
+// the doubles behind dpart, tpart and wpart together, in that order (multiply_partial_offsets: where the last two begin).  part 0: the
+// tile pass (not launched for N = 0); part 1: the sums and, in a one-workgroup launch of its own, the robot rows into a.y.
+int multiply_segment(int T);
+int64_t multiply_partial_doubles(const TileMap &tm, int64_t rows);
+void multiply_partial_offsets(const TileMap &tm, int64_t rows, int64_t *tpart, int64_t *wpart);
+hipError_t launch_multiply_map(const DevState &st, const MultiplyMapArgs &a, int part, int storage, hipStream_t s);
 
 // fused_predict != nullptr folds predict(u) into the correction (one launch instead of two, identical arithmetic)
 // fuse_downdate: the kernel also applies its pair to the landmark block (small maps: a.n_mm <= gather_fuse_max_rows(), one

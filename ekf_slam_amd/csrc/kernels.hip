@@ -65,6 +65,7 @@ namespace {
 #include "factor_map.h"       // the Cholesky factorisation of P in a scratch store: k_factor_load / _rhs / _diag / _panel / _trail / _finish
 #include "sample_map.h"       // ... and the draws x + C xi behind it: k_factor_apply, k_factor_sample
 #include "solve_map.h"        // ... and the solves C^-1 B, P^-1 B: k_solve_invert, k_solve_forward, k_solve_tail, k_solve_backward
+#include "multiply_map.h"     // the plain product P B on the handle's own tile store, no factor: k_multiply_tiles, k_multiply_sum, k_multiply_robot
 
 }  // namespace
 

@@ -379,3 +379,42 @@ hipError_t launch_solve_map(const FactorMapArgs &a, const FactorSolveArgs &sv, i
         return hipErrorInvalidValue;
     return hipGetLastError();
 }
+
+// ---- the plain product P B on the handle's own store (multiply_map.h: k_multiply_tiles, k_multiply_sum) ----
+// Tiles per segment of a tile row: 256 columns' worth.  A workgroup then streams 2 tiles at the F64 production edge 128 and one at 256
+// for one direct partial block, and a map of 140 landmarks at edge 16 still has tile rows of two segments.
+int multiply_segment(int T) { return T >= 256 ? 1 : 256 / T; }
+void multiply_partial_offsets(const TileMap &tm, int64_t rows, int64_t *tpart, int64_t *wpart) {
+    const int64_t nT = rows / tm.T, blk = (int64_t)tm.T * kFactorChunk;
+    *tpart = factor_segment_base(nT, multiply_segment(tm.T)) * blk;
+    *wpart = *tpart + tm.row_base(nT) * blk;
+}
+int64_t multiply_partial_doubles(const TileMap &tm, int64_t rows) {
+    int64_t t, w;
+    multiply_partial_offsets(tm, rows, &t, &w);
+    return w + (rows / tm.T) * (3 * kFactorChunk);
+}
+
+hipError_t launch_multiply_map(const DevState &st, const MultiplyMapArgs &a, int part, int storage, hipStream_t s) {
+    // every index the kernels form lies inside the chunks (ld), the partial blocks (one per segment, one slot per tile, one part per tile
+    // row) and the handle's own store (an unsharded tile map, every landmark below 2 N inside the strip)
+    const int T = st.tm.T;
+    if (!a.b || !a.y || !a.dpart || !a.tpart || !a.wpart || a.N < 0 || st.tm.world != 1 || T < 16 || T > 16 * 4 * kMultiplyWaveBlocks || (T & (T - 1)) ||
+        2 * a.N > st.ldm || a.rows != st.tm.padded(2 * a.N) || a.ld < a.rows + 3 || a.S != multiply_segment(T) || (a.cur != 0 && a.cur != 1) || part < 0 || part > 1)
+        return hipErrorInvalidValue;
+    const int64_t nT = a.rows / T, segments = factor_segment_base(nT, a.S);
+    if (segments > 0x7fffffffll) return hipErrorInvalidValue;
+    if (part == 1) {
+        const int64_t grid = nT * cdiv((int64_t)T * kFactorChunk, (int64_t)kFactorBlock);
+        if (grid > 0x7fffffffll) return hipErrorInvalidValue;
+        if (grid > 0) hipLaunchKernelGGL(k_multiply_sum, dim3((unsigned)grid), dim3(kFactorBlock), 0, s, st, a);
+        hipLaunchKernelGGL(k_multiply_robot, dim3(1), dim3(kFactorBlock), 0, s, st, a);
+        return hipGetLastError();
+    }
+    if (segments == 0) return hipSuccess;
+    return with_storage(storage, [&](auto ts) {
+        using TS = decltype(ts);
+        if (T <= 128) hipLaunchKernelGGL((k_multiply_tiles<TS, 128>), dim3((unsigned)segments), dim3(kMultiplyBlock), 0, s, st, a);
+        else hipLaunchKernelGGL((k_multiply_tiles<TS, 256>), dim3((unsigned)segments), dim3(kMultiplyBlock), 0, s, st, a);
+    });
+}

@@ -572,6 +572,19 @@ class Engine:
         self._check(self.lib.ekf_solve_map(self.h, form, _p(B), k, _p(out), ctypes.byref(info)))
         return marshal.solve_result(args)
 
+    # ---- the plain product P B on the tile store, no factorisation (include/ekfslam.h: ekf_multiply_map) ----
+    def multiply_map(self, B):
+        """`out`: row q is P b_q for the k vectors in `B` (one of 3 + 2 N entries, or one per row; in x's order), P exactly what get_P()
+        reports, all arithmetic F64.  No entry is wrapped.  One read-only pass over the tile store per 16 vectors, no factorisation:
+        a row depends on its own vector alone, B = 0 gives 0, a unit vector returns a column of P.  Read-only and synchronising
+        (ekf_multiply_map)."""
+        return self._multiply_map(marshal.multiply_args(B, 3 + 2 * self.N))
+
+    def _multiply_map(self, args):
+        B, k, out = args
+        self._check(self.lib.ekf_multiply_map(self.h, _p(B), k, _p(out)))
+        return marshal.multiply_result(args)
+
     @staticmethod
     def model_invert(model, xr, z, lib=None):
         """(t, Gx, Gz): the landmark that z observes from the robot state xr = (x, y, theta in degrees) through EKF_MODEL_RANGE_BEARING

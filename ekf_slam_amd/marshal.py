@@ -268,6 +268,18 @@ def solve_result(args):
     return sample_result(args[1:])
 
 
+def multiply_args(B, n, who="multiply_map"):
+    """(B, k, out) of multiply_map as the ABI takes them, the arrays kept so that multiply_result reads what the call wrote.  B as
+    sample_args takes xi: one vector of n = 3 + 2 N finite entries, or k >= 1 of them as rows."""
+    Bv, k, out, _ = sample_args(B, n, who, ("B", "vector"))
+    return Bv, k, out
+
+
+def multiply_result(args):
+    """What multiply_map returns from what the call wrote: one row P b per vector."""
+    return args[2]
+
+
 def model_inits(entries, who="append_model"):
     """(ekf_model_init[], m) of a scan of new landmarks [(model, z, R, signature), ...]."""
     entries = list(entries)

@@ -175,6 +175,11 @@ class ShardGroup:
         is the library's (EKF_ERR_INVALID_ARG, nothing changed)."""
         return self.shards[0].solve_map(B, form)
 
+    def multiply_map(self, B):
+        """Not built for a shard group: the pass reads every tile, and a shard holds only its own.  The call goes to the first shard so
+        that the refusal is the library's (EKF_ERR_INVALID_ARG, nothing changed)."""
+        return self.shards[0].multiply_map(B)
+
     def correct(self, z, R, idx0):
         for e in self.shards:
             e.correct_begin(z, R, idx0)

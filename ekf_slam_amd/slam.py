@@ -397,6 +397,47 @@ class _EkfBase:
         w = self._definite_solve("mahalanobis", d, "half")[0]
         return float(w @ w)
 
+    def multiply_map(self, B):
+        """P b for the vectors in the rows of B, P exactly what get_P() reports, from one read-only pass over the tile store per 16
+        vectors on the device -- no factorisation (Engine.multiply_map; ekf_multiply_map).  Plain linear algebra: no entry is wrapped.
+        Read-only: nothing goes into the trajectory log.  The reference has no such method."""
+        return self._e.multiply_map(B)
+
+    def covariance_of(self, A):
+        """A P A' (m x m, symmetrised) for the m linear functions of the state in the rows of A (m x (3 + 2 N), or one row): the
+        covariance of a centroid, of the vector between two landmarks, of a path length, of any linear cost -- from ONE multiply_map
+        call with A's rows."""
+        n = 3 + 2 * self._e.N
+        Av = np.asarray(A, dtype=np.float64)
+        if Av.ndim == 1:
+            Av = Av.reshape(1, -1)
+        if Av.ndim != 2 or Av.shape[0] < 1 or Av.shape[1] != n:
+            raise ValueError("covariance_of: A is m >= 1 rows of 3 + 2 N = %d entries" % n)
+        cov = Av @ self._e.multiply_map(Av).T
+        return 0.5 * (cov + cov.T)
+
+    def cross_covariance(self, idx_a, idx_b):
+        """The block P[a, b] between two arbitrary groups of states: each of idx_a, idx_b is a list of distinct landmarks (two rows or
+        columns each, in the list's order) or None for the robot (three).  One multiply_map call with the unit vectors of the
+        SHORTER list; P is symmetric, so the block of the longer one is the transpose of what comes back."""
+        ca = self._state_columns("cross_covariance", idx_a)
+        cb = self._state_columns("cross_covariance", idx_b)
+        n = 3 + 2 * self._e.N
+        short, other = (ca, cb) if ca.size <= cb.size else (cb, ca)
+        E = np.zeros((short.size, n))
+        E[np.arange(short.size), short] = 1.0
+        block = self._e.multiply_map(E)[:, other]                # rows: P[short, other]
+        return block if ca.size <= cb.size else block.T
+
+    def solve_residual(self, B, form="full"):
+        """(z, r): z = solve_map(B, form)[0] and r = P z - b for each right-hand side, the a-posteriori check of a solve -- for
+        form="full" r is the residual of P z = b itself; for form="half" (z = C^-1 b) it is P z - b all the same, for a caller who
+        wants that product.  Two device calls: the solve, then one multiply_map of its result.  ValueError where P is not positive
+        definite."""
+        Bv = np.asarray(B, dtype=np.float64)
+        z = self._definite_solve("solve_residual", Bv, form)
+        return z, self._e.multiply_map(z) - Bv.reshape(z.shape)
+
     def fuse_duplicates(self, gate, R=None, max_merges=None):
         """The SIMPLEST complete fusion policy, not the fastest: repeat { search; take the candidate with the smallest (d2, i) at or
         below `gate`; merge_landmarks(keep=j, drop=i, R) } until none is left or `max_merges` merges were made.  One search plus

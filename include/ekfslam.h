@@ -701,6 +701,34 @@ int32_t ekf_sample_map(ekf_handle *h, const double *xi /* k x (3 + 2N), one row 
 enum { EKF_SOLVE_FULL = 0, EKF_SOLVE_HALF = 1 };
 int32_t ekf_solve_map(ekf_handle *h, int32_t form, const double *B /* k x (3 + 2N), one row per right-hand side, x's order */,
                       int64_t k /* >= 1 */, double *out /* k x (3 + 2N) */, ekf_factor_info *info);
+/* THE PLAIN PRODUCT P B for k vectors the caller chooses, with NO factorisation: one read-only pass over the handle's own tile store per
+ * 16 vectors.  B is k rows of 3 + 2 N finite entries in x's order; row q of out is P b_q in x's order.  What it is for: the covariance
+ * A P A' of linear functions of the map (a centroid, the vector between two landmarks, a path length), cross-covariance blocks between
+ * arbitrary landmark sets (unit vectors), the residual P z - b of an ekf_solve_map answer, P H' for an observation row that touches many
+ * landmarks.
+ * WHICH P: exactly what ekf_get_P reports at that moment -- float tiles widened to F64, every landmark's own 2 x 2 block from the live F64
+ * copies, every other entry of the landmark block the canonical lower-triangle entry (within diagonal tiles too), the robot block from
+ * Prr and the strip.  Plain linear algebra: NO entry is wrapped, and all arithmetic is F64 for every storage kind.  Rows and columns at
+ * or beyond 2 N never contribute, whatever the store holds below the map (they are masked by selection, not multiplied by zero).
+ * Promised: (1) row q of out depends on b_q alone -- the same vector gives the same bits alone, first, last or in the middle of a batch
+ * of any k, across chunk boundaries and from call to call; (2) B = 0 gives 0 in every entry; (3) the unit vector e_j returns column j
+ * of ekf_get_P, equal entry for entry as numbers (the sign of a zero is not promised); (4) no atomics and no data-dependent order of
+ * summation.  Each entry is a sum of 3 + 2 N products in a fixed order: |out - P b|_i <= 2 n 2^-53 (|P| |b|)_i.
+ * The vectors are taken 16 at a time; per chunk k_multiply_tiles makes one pass over the tile store on the F64 matrix cores -- every
+ * stored tile T_IJ is used twice by the workgroup that holds it, as T_IJ B_J and as T_IJ' B_I --, k_multiply_sum adds the partial blocks
+ * and the strip's part in a fixed order, and k_multiply_robot forms the robot rows.  The tile passes count under EKF_KERNEL_ASSOCIATE, the sums under EKF_KERNEL_COMPACT.
+ * The scratch is the call's own (a chunk in, a chunk out, the partial blocks -- about an eighth of the tile store's F64 bytes at edge
+ * 128 -- and four pinned chunks a direction whatever k is): allocated at the first call, grown when N has outgrown it, counted by
+ * ekf_device_bytes, released by ekf_destroy.  ekf_factor_map's factor store is not allocated.  N = 0: out = Prr b.
+ * SYNCHRONISING and READ-ONLY exactly as ekf_nearest_landmarks and ekf_factor_map: a recorded predict is carried out, pending pairs
+ * are applied, an asynchronous pass is retired (ekf_pending is 0 afterwards); x, s, P and ekf_P_digest are bit for bit those of a
+ * handle that only flushed; nothing is logged.  Refused with nothing changed and nothing flushed, in ekf_solve_map's order: h, B or out
+ * NULL, k < 1, a handle with world > 1 (a lone shard with cfg.force_sharded works) (EKF_ERR_INVALID_ARG); a sharded correction between
+ * begin and finish (EKF_ERR_STATE); then, once N is exact, a B entry that is not finite (EKF_ERR_INVALID_ARG); EKF_ERR_HIP if the
+ * scratch cannot be allocated, before anything is queued.  A refusal leaves out untouched; an EKF_ERR_HIP once the launches have begun
+ * leaves every entry of out NaN. */
+int32_t ekf_multiply_map(ekf_handle *h, const double *B /* k x (3 + 2N), one row per vector, x's order */,
+                         int64_t k /* >= 1 */, double *out /* k x (3 + 2N) */);
 /* The step between the two: "WHICH landmark does this sighting belong to?", for a whole scan, under the conventions of ekf_observe_model.
  * ekf_associate keeps the reference's (signature-only by default, an unwrapped bearing, a range-scaled R) and cannot serve a filter
  * driven through the model calls.  For each of the m observations, d2(k, i) is, BIT FOR BIT, the d2 that ekf_model_innovation reports for

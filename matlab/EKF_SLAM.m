@@ -311,6 +311,13 @@ classdef EKF_SLAM < handle
             info = struct('n', v(1), 'definite', v(2) ~= 0, 'bad_index', v(3), 'bad_pivot', v(4), 'logdet', v(5), 'logdet_map', v(6), ...
                           'min_pivot', v(7), 'max_pivot', v(8));
         end
+        function out = multiplyMap(h, B)
+            % THE PLAIN PRODUCT: out(:, q) = P * B(:, q) for the k columns of B (n x k, n = 3 + 2 N), P exactly what getP reports, with
+            % NO factorisation: one read-only pass over the tiled P on the GPU per 16 columns.  A * multiplyMap(A') is the covariance
+            % of the linear functions A * x; unit vectors return columns of P; P * z - b checks a solveMap answer.  No entry is
+            % wrapped.  Read-only.  Not a method of the reference.
+            out = h.gateway('multiply_map', double(B));
+        end
         function idx = addLandmarkRangeBearing(h, z, R, signature)
             % 'A landmark that is not in the map yet is seen at range z(1) and bearing z(2) (degrees, relative to the heading),
             % covariance R': it joins the map at the point that observation names.

@@ -27,7 +27,7 @@
  * (ekf_observe_model), the append through a model (ekf_append_model), the association of a scan under the models' conventions
  * (ekf_associate_model) and its one-to-one assignment (ekf_assign_model), the joint compatibility of a scan's pairings (ekf_joint_innovation) and their joint update
  * (ekf_observe_model_joint, relinearised: ekf_observe_model_joint_iterated), the relinearised model observation
- * (ekf_observe_model_iterated), the motion steps under them (ekf_predict_model), the join of a local map (ekf_join_map), the extraction of part of the map (ekf_extract_map), the map's change of frame (ekf_transform_map), the factorisation of P (ekf_factor_map), the draws from the posterior behind it (ekf_sample_map) and the solves with the factor (ekf_solve_map) are the ones this gateway can live without: bound weakly, so that the gateway still links against a libekfslam (or a stand-in) that
+ * (ekf_observe_model_iterated), the motion steps under them (ekf_predict_model), the join of a local map (ekf_join_map), the extraction of part of the map (ekf_extract_map), the map's change of frame (ekf_transform_map), the factorisation of P (ekf_factor_map), the draws from the posterior behind it (ekf_sample_map), the solves with the factor (ekf_solve_map) and the plain product P B (ekf_multiply_map) are the ones this gateway can live without: bound weakly, so that the gateway still links against a libekfslam (or a stand-in) that
  * predates them; their commands then raise a MATLAB error instead. */
 #if defined(__GNUC__)
 #pragma weak ekf_remove_landmarks
@@ -53,6 +53,7 @@
 #pragma weak ekf_factor_map
 #pragma weak ekf_sample_map
 #pragma weak ekf_solve_map
+#pragma weak ekf_multiply_map
 #define HAVE_REMOVE_LANDMARKS (ekf_remove_landmarks != 0)
 #define HAVE_CONSTRAIN_LANDMARKS (ekf_constrain_landmarks != 0)
 #define HAVE_MERGE_LANDMARKS (ekf_merge_landmarks != 0)
@@ -76,6 +77,7 @@
 #define HAVE_FACTOR_MAP (ekf_factor_map != 0)
 #define HAVE_SAMPLE_MAP (ekf_sample_map != 0)
 #define HAVE_SOLVE_MAP (ekf_solve_map != 0)
+#define HAVE_MULTIPLY_MAP (ekf_multiply_map != 0)
 #else
 #define HAVE_REMOVE_LANDMARKS 1
 #define HAVE_CONSTRAIN_LANDMARKS 1
@@ -99,6 +101,7 @@
 #define HAVE_FACTOR_MAP 1
 #define HAVE_SAMPLE_MAP 1
 #define HAVE_SOLVE_MAP 1
+#define HAVE_MULTIPLY_MAP 1
 #endif
 
 static void need(int nrhs, int want, const char *cmd) {
@@ -562,6 +565,21 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
             o[0] = (double)info.n; o[1] = (double)info.definite; o[2] = (double)(info.bad_index + 1); o[3] = info.bad_pivot;
             o[4] = info.logdet; o[5] = info.logdet_map; o[6] = info.min_pivot; o[7] = info.max_pivot;
         }
+        return;
+    }
+    if (!strcmp(cmd, "multiply_map")) {           /* out = (h, B): P B with no factorisation, one read-only pass over the tile store per 16 columns.  B: n x k, one
+                                                     vector a column (n = 3 + 2 N, k >= 1); out: n x k */
+        need(nrhs, 3, cmd);
+        if (!HAVE_MULTIPLY_MAP) mexErrMsgIdAndTxt("ekfslam:usage", "multiply_map: this libekfslam has no ekf_multiply_map");
+        const int64_t n = nstate(h);
+        const mwSize nel = prhs[2] ? mxGetNumberOfElements(prhs[2]) : 0;
+        const mwSize k = nel / (mwSize)n;
+        if (nel == 0 || !mxGetPr(prhs[2]) || k * (mwSize)n != nel)
+            mexErrMsgIdAndTxt("ekfslam:usage", "multiply_map: B is n x k, n = 3 + 2 N entries a column and k >= 1 columns");
+        mxArray *out = mxCreateDoubleMatrix((mwSize)n, k, mxREAL);
+        const int32_t rc = ekf_multiply_map(h, mxGetPr(prhs[2]), (int64_t)k, mxGetPr(out));   /* (MATLAB arrays are column-major) */
+        if (rc != EKF_OK) { mxDestroyArray(out); check(h, rc); }
+        plhs[0] = out;
         return;
     }
     if (!strcmp(cmd, "associate_model")) {        /* [match, d2] = (h, model m x 1 (1..4), z m x 2, R 2 x 2 x m, gate m x 1): which landmark each sighting of a
