@@ -132,6 +132,14 @@ class EkfMotion(ctypes.Structure):
     _fields_ = [("model", _i32), ("reserved", _i32), ("u", _d * 3), ("M", _d * 9)]
 
 
+EKF_DENSE_MAX = 16                                    # rows of one ekf_observe_dense call: one chunk of ekf_multiply_map
+
+
+class EkfObserveDenseResult(ctypes.Structure):
+    """struct ekf_observe_dense_result (include/ekfslam.h)."""
+    _fields_ = [("d2", _d), ("rows", _i32), ("outcome", _i32), ("bad_row", _i32)]
+
+
 EKF_FACTOR_REF_MAX = 8                                # reference states of one ekf_factor_map call
 
 
@@ -211,6 +219,8 @@ SIGNATURES = {
     "ekf_sample_map": (_i32, [_vp, _dp, _i64, _dp, ctypes.POINTER(EkfFactorInfo)]),
     "ekf_solve_map": (_i32, [_vp, _i32, _dp, _i64, _dp, ctypes.POINTER(EkfFactorInfo)]),
     "ekf_multiply_map": (_i32, [_vp, _dp, _i64, _dp]),
+    "ekf_observe_dense": (_i32, [_vp, _dp, _i64, _dp, _dp, ctypes.POINTER(_i32), _d, ctypes.POINTER(EkfObserveDenseResult), _dp, _dp]),
+    "ekf_observe_dense_innovation": (_i32, [_vp, _dp, _i64, _dp, _dp, ctypes.POINTER(_i32), ctypes.POINTER(EkfObserveDenseResult), _dp, _dp]),
     "ekf_associate_model": (_i32, [_vp, ctypes.POINTER(EkfModelObs), _i64, ctypes.POINTER(EkfModelMatch), _dp]),
     "ekf_assign_model": (_i32, [_vp, ctypes.POINTER(EkfModelObs), _i64, ctypes.POINTER(EkfModelAssigned), ctypes.POINTER(EkfModelMatch),
                                 ctypes.POINTER(_i64), _dp, _dp]),

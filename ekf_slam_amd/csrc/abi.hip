@@ -26,7 +26,8 @@
 #include "host/joint_search.h" // ... and searched on the device for the jointly compatible hypothesis, one readback: joint_search
 #include "host/joint_update.h" // ... and applied as ONE joint update behind a flush: observe_model_joint
 #include "host/joint_iter.h"   // ... relinearised: observe_model_joint_iterated, joint_iterate
-#include "host/predict_model.h" // motion steps with true Jacobians, a chain per launch: predict_model, motion_evaluate
+#include "host/dense_obs.h"    // a linear observation with a dense H: multiply_map's product, then joint_update's route: observe_dense, observe_dense_innovation
+#include "host/predict_model.h"// motion steps with true Jacobians, a chain per launch: predict_model, motion_evaluate
 #include "host/state.h"        // get / set, low-rank load, checkpoint, digest
 #include "host/lifecycle.h"    // ekf_create, ekf_destroy, the kernel timers
 

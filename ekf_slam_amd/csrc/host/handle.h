@@ -278,6 +278,16 @@ struct ekf_handle {
     // ... relinearised (ekf_observe_model_joint_iterated): k_joint_factor_iter's iteration record on the device and in pinned memory (allocated at
     // the first call and kept); read back behind ev_joint
     double *d_jiter = nullptr, *h_jiter = nullptr;
+    // ---- a linear observation with a dense H (ekf_observe_dense; host/dense_obs.h) ----
+    // the chunk of H's rows and of G = P H' are ekf_multiply_map's scratch above, its pairs go to d_mring; its own: the segments' partial
+    // sums (for dn_rows landmark rows; grown when N has outgrown them, released by ekf_destroy itself, dn_bytes counted in `bytes`), what
+    // k_dense_factor hands k_gather_dense, and the answer on the device and in pinned memory behind an event (allocated at the first call
+    // and kept)
+    double *d_dpart = nullptr;
+    int64_t dn_rows = -1, dn_bytes = 0;
+    DenseBlock *d_dblock = nullptr;
+    DenseOut *d_dout = nullptr, *h_dout = nullptr;
+    hipEvent_t ev_dense = nullptr;
     // ---- timers, what ekf_destroy releases, the error text ----
     KernelTimer timers[EKF_KERNEL_COUNT];
     std::vector<void *> allocs;       // device memory (dalloc), pinned memory (halloc) and events (new_event): what ekf_destroy releases

@@ -96,7 +96,7 @@ int32_t ekf_destroy(ekf_handle *h) {
     for (hipEvent_t e : h->events) hipEventDestroy(e);
     for (auto &t : h->timers) for (hipEvent_t e : t.ev) hipEventDestroy(e);
     for (void *p : h->allocs) hipFree(p);
-    for (void *p : { (void *)h->d_ftiles, (void *)h->d_fsmall, (void *)h->d_fsample, (void *)h->d_fsolve, (void *)h->d_pmul }) if (p) hipFree(p);   // ekf_factor_map's, ekf_sample_map's and ekf_solve_map's scratch (host/factor_map.h), ekf_multiply_map's (host/multiply_map.h)
+    for (void *p : { (void *)h->d_ftiles, (void *)h->d_fsmall, (void *)h->d_fsample, (void *)h->d_fsolve, (void *)h->d_pmul, (void *)h->d_dpart }) if (p) hipFree(p);   // ekf_factor_map's, ekf_sample_map's and ekf_solve_map's scratch (host/factor_map.h), ekf_multiply_map's (host/multiply_map.h), ekf_observe_dense's partial sums (host/dense_obs.h)
     for (void *p : { (void *)h->h_fres, (void *)h->h_fref, (void *)h->h_fxi, (void *)h->h_fy, (void *)h->h_pmb, (void *)h->h_pmy }) if (p) hipHostFree(p);
     for (void *p : h->pinned) hipHostFree(p);
     if (h->own_stream) hipStreamDestroy(h->own_stream);

@@ -40,6 +40,19 @@ int32_t multiply_alloc(ekf_handle *h, int64_t rows) {
     return EKF_OK;
 }
 
+// One chunk of the scratch as the launches take it (after multiply_alloc for `rows` and the flush: N and h->cur are final): the vectors at the
+// front, their products behind them, then the partial blocks.  ekf_observe_dense (host/dense_obs.h) runs the same two launches on it.
+MultiplyMapArgs multiply_chunk_args(const ekf_handle *h, int64_t rows) {
+    const TileMap &tm = h->st.tm;
+    MultiplyMapArgs a = {};
+    double *d_b = h->d_pmul, *d_y = d_b + sample_chunk_doubles(h->pm_rows), *d_part = d_y + sample_chunk_doubles(h->pm_rows);
+    int64_t toff = 0, woff = 0;
+    multiply_partial_offsets(tm, rows, &toff, &woff);
+    a.b = d_b; a.y = d_y; a.dpart = d_part; a.tpart = d_part + toff; a.wpart = d_part + woff;
+    a.ld = sample_ld(rows); a.N = h->N; a.rows = rows; a.S = multiply_segment(tm.T); a.cur = h->cur;
+    return a;
+}
+
 // Order as in factor_body: the rungs, with what depends on N checked once N is exact -> every allocation -> the flush -> the launches,
 // queued back to back.  Per chunk the upload of a pinned slot, the two launches and the download into a pinned slot; the host waits only
 // where it takes a slot again, kSampleSlots chunks later, for that slot's own download.  `queued` is set once the launches begin: out is
@@ -55,12 +68,8 @@ int32_t multiply_body(ekf_handle *h, const std::string &who, const double *B, in
     TRY(edit_flushed(h));
     const int64_t C = factor_chunk(), ld = sample_ld(rows), nchunks = (k + C - 1) / C;
     const size_t chunk = sample_chunk_doubles(rows);
-    MultiplyMapArgs a = {};
-    double *d_b = h->d_pmul, *d_y = d_b + sample_chunk_doubles(h->pm_rows), *d_part = d_y + sample_chunk_doubles(h->pm_rows);
-    int64_t toff = 0, woff = 0;
-    multiply_partial_offsets(tm, rows, &toff, &woff);
-    a.b = d_b; a.y = d_y; a.dpart = d_part; a.tpart = d_part + toff; a.wpart = d_part + woff;
-    a.ld = ld; a.N = N; a.rows = rows; a.S = multiply_segment(tm.T); a.cur = h->cur;
+    const MultiplyMapArgs a = multiply_chunk_args(h, rows);
+    double *d_b = h->d_pmul, *d_y = a.y;
     queued = true;
     auto unpack = [&](int64_t j) {
         const double *y = h->h_pmy + (size_t)(j % kSampleSlots) * chunk;

@@ -395,6 +395,45 @@ constexpr int kJointSubMax = 3 + 2 * kJointMax;       // entries of the largest 
 // that was irregular, or -1 (4) | the scan index of its first irregular pairing, or -1 (5) | ns (6) | 0 (7) | x'_sub = xi_used (8 .. 8 + ns)
 constexpr int kJointIterRecordDoubles = 8 + kJointSubMax + 1;
 
+// A linear observation with a DENSE k x n H (dense_obs.h, ekf_observe_dense): the rows of H are the vectors of ONE chunk of
+// k_multiply_tiles (MultiplyMapArgs' layout: row i is column i of the chunk b, its product G_i = P H_i' column i of y), kk = k rounded up
+// to even rows, the last one exactly empty where k is odd.  k_dense_gram cuts the landmark rows [0, 2 N) into segments of kDenseSegment
+// rows and leaves one block of kDensePartial sums per segment: the lower triangle of H G by rows ((i, j), j <= i, at i (i + 1) / 2 + j),
+// then the kDenseMax sums of H x.  k_dense_factor adds them in ascending segment order, then the robot's three terms, then R.
+constexpr int kDenseMax = kFactorChunk;
+constexpr int kDenseSegment = 128;
+constexpr int kDensePartial = kDenseMax * (kDenseMax + 1) / 2 + kDenseMax;
+struct DenseArgs {
+    const double *b;          // the chunk of H's rows (device)
+    const double *y;          // the chunk of G = P H' (device); rows 2 N .. rows - 1 are never read
+    double *part;             // cdiv(2 N, kDenseSegment) blocks of kDensePartial doubles
+    int64_t ld, rows;         // the chunk's leading dimension and the robot entries' offset (MultiplyMapArgs::ld, ::rows)
+    int64_t n_mm;             // 2 N
+    int32_t kk;               // rows of the stacked system, even, 2 .. kDenseMax
+    int32_t cur;
+};
+struct DenseSmall {           // what k_dense_factor alone reads: z, R (row-major, leading dimension kDenseMax) and the wrap flags, padded by the host
+    double z[kDenseMax];
+    double R[kDenseMax * kDenseMax];
+    int32_t wrap[kDenseMax];
+};
+// the answer of a call: ekf_observe_dense_result field by field (outcome: 1 regular, 0 irregular), then nu and S (leading dimension kDenseMax)
+struct DenseRecord {
+    double d2;
+    int32_t rows, outcome, bad_row;
+};
+struct DenseOut {
+    DenseRecord rec;
+    double nu[kDenseMax];
+    double S[kDenseMax * kDenseMax];
+};
+// what k_dense_factor hands k_gather_dense: L (the pivot's root on the diagonal), y = L^-1 nu, W_r = L^-1 G_r
+struct DenseBlock {
+    double L[kDenseMax * kDenseMax];
+    double y[kDenseMax];
+    double Wr[kDenseMax][3];
+};
+
 // ---- map edits, and the observations that share the constraint's device code ----
 // A constraint between two landmarks (constrain.h): "l_i - l_j was observed as (d0, d1) with noise covariance R".
 struct ConstrainArgs {

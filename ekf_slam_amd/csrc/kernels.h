@@ -325,6 +325,17 @@ hipError_t launch_joint_factor_iter(const DevState &st, const JointArgs &a, cons
 // landmark's live diagonal block into buffer dcur ^ 1; the caller flips both and lets ONE pass apply the pairs to the tiles.
 hipError_t launch_gather_joint(const DevState &st, const JointUpdateArgs &a, const JointBlock *blk, int storage, hipStream_t s);
 
+// A linear observation with a DENSE H (dense_obs.h, ekf_observe_dense), on a flushed state, behind launch_multiply_map's two stages on the
+// chunk that a.b / a.y name (the rows of H in, G = P H' out).  launch_dense_gram: k_dense_gram, a workgroup per segment of landmark rows,
+// the partial sums of H G and H x into a.part (dense_partial_doubles(2 N) doubles; no launch at N = 0).  launch_dense_factor: k_dense_factor,
+// one workgroup, read-only -- S, nu, the factorisation, d2 and the record into out, what the gather needs into blk.  launch_gather_dense:
+// k_gather_dense over the padded landmark block (one workgroup at N = 0), under launch_gather_joint's rules for `st`: the a.kk / 2 pairs go
+// to slots 0 .. a.kk / 2 - 1 of the PRIVATE F64 ring, x / Prr / strip into buffer a.cur ^ 1, the diagonal blocks into buffer dcur ^ 1.
+int64_t dense_partial_doubles(int64_t n_mm);
+hipError_t launch_dense_gram(const DevState &st, const DenseArgs &a, hipStream_t s);
+hipError_t launch_dense_factor(const DevState &st, const DenseArgs &a, const DenseSmall &sm, DenseOut *out, DenseBlock *blk, hipStream_t s);
+hipError_t launch_gather_dense(const DevState &st, const DenseArgs &a, const DenseBlock *blk, hipStream_t s);
+
 // ---- state I/O (launch/state_io.h) ----
 // dense (column-major, n x n, device) <-> tiled
 hipError_t launch_unpack_dense(const DevState &st, int cur, int64_t n_mm, double *dense, int storage, hipStream_t s);

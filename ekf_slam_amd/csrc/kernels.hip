@@ -66,6 +66,7 @@ namespace {
 #include "sample_map.h"       // ... and the draws x + C xi behind it: k_factor_apply, k_factor_sample
 #include "solve_map.h"        // ... and the solves C^-1 B, P^-1 B: k_solve_invert, k_solve_forward, k_solve_tail, k_solve_backward
 #include "multiply_map.h"     // the plain product P B on the handle's own tile store, no factor: k_multiply_tiles, k_multiply_sum, k_multiply_robot
+#include "dense_obs.h"        // ... and a linear observation with a dense H behind it: k_dense_gram, k_dense_factor, k_gather_dense
 
 }  // namespace
 

@@ -280,6 +280,43 @@ hipError_t launch_gather_joint(const DevState &st, const JointUpdateArgs &a, con
     });
 }
 
+// ---- a linear observation with a dense H (dense_obs.h), behind launch_multiply_map's two stages on the same chunk ----
+namespace {
+bool dense_args_ok(const DevState &st, const DenseArgs &a) {
+    // every row the kernels read lies inside the chunks (ld) and inside the strip; the robot's three entries lie behind the landmark rows
+    return a.b && a.y && a.part && a.kk >= 2 && a.kk <= kDenseMax && !(a.kk & 1) && a.n_mm >= 0 && !(a.n_mm & 1) && a.n_mm <= st.ldm &&
+           a.rows == st.tm.padded(a.n_mm) && a.ld >= a.rows + 3 && (a.cur == 0 || a.cur == 1) && st.tm.world == 1;
+}
+}  // namespace
+int64_t dense_partial_doubles(int64_t n_mm) { return cdiv(n_mm, (int64_t)kDenseSegment) * kDensePartial; }
+
+hipError_t launch_dense_gram(const DevState &st, const DenseArgs &a, hipStream_t s) {
+    if (!dense_args_ok(st, a)) return hipErrorInvalidValue;
+    const int64_t grid = cdiv(a.n_mm, (int64_t)kDenseSegment);
+    if (grid > 0x7fffffffll) return hipErrorInvalidValue;
+    if (grid == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_dense_gram, dim3((unsigned)grid), dim3(kDenseBlock), 0, s, st, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_dense_factor(const DevState &st, const DenseArgs &a, const DenseSmall &sm, DenseOut *out, DenseBlock *blk, hipStream_t s) {
+    if (!dense_args_ok(st, a) || !out || !blk) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_dense_factor, dim3(1), dim3(kDenseFactorBlock), 0, s, st, a, sm, out, blk);
+    return hipGetLastError();
+}
+
+hipError_t launch_gather_dense(const DevState &st, const DenseArgs &a, const DenseBlock *blk, hipStream_t s) {
+    // launch_gather_joint's checks: the pairs inside the private F64 ring, the padded block inside the strip.  N = 0 is one workgroup
+    // without a live lane: the robot part alone
+    if (!dense_args_ok(st, a) || !blk || a.kk / 2 > st.pcap || st.tm.padded(a.n_mm) > st.ldm || st.Gp32 || st.Kp32 || !st.Gp || !st.Kp)
+        return hipErrorInvalidValue;
+    const int64_t cols = st.tm.padded(a.n_mm);
+    const unsigned grid = (unsigned)(cols > 0 ? cdiv(cols, (int64_t)kBlock) : 1);
+    if (a.kk <= 4) hipLaunchKernelGGL(k_gather_dense<2>, dim3(grid), dim3(kBlock), 0, s, st, a, blk);
+    else hipLaunchKernelGGL(k_gather_dense<8>, dim3(grid), dim3(kBlock), 0, s, st, a, blk);
+    return hipGetLastError();
+}
+
 hipError_t launch_nearest(const DevState &st, int cur, int64_t N, const double R[4], NearestEntry *out, int storage, hipStream_t s) {
     if (N <= 0) return hipSuccess;
     // a group of landmarks (and a float lane's two) must lie inside one tile row / one tile; landmark indices are 32-bit in the kernel

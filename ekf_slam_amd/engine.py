@@ -585,6 +585,30 @@ class Engine:
         self._check(self.lib.ekf_multiply_map(self.h, _p(B), k, _p(out)))
         return marshal.multiply_result(args)
 
+    # ---- a linear observation with a dense H behind that product (include/ekfslam.h: ekf_observe_dense) ----
+    def observe_dense(self, H, z, R, gate=float("inf"), wrap_deg=None):
+        """"H x = z +- R" for k <= 16 rows that may touch every landmark: H a k x (3 + 2 N) array in x's order, or a list of
+        {state index: coefficient} rows; z the k values; R k x k (or its k diagonal entries; 0 conditions exactly); rows flagged in
+        wrap_deg have their innovation wrapped into (-180, 180].  Exact, no linearisation: S = H P H' + R, nu = z - H x, and with
+        L L' = S, W = L^-1 H P, y = L^-1 nu: x' = x + W' y, P' = P - W' W -- applied only if d2 = |y|^2 <= gate.  The pending pairs are
+        flushed first, ONE product pass and ONE update pass over P follow; nothing is waited for at the end.  Returns {'d2', 'rows',
+        'outcome', 'bad_row', 'nu' (k), 'S' (k x k)}, outcome EKF_LINEAR_APPLIED or EKF_LINEAR_GATED; an S with a pivot that is not
+        finite and positive raises EkfError and changes nothing (ekf_observe_dense)."""
+        return self._observe_dense(marshal.dense_args(H, z, R, 3 + 2 * self.N, gate, wrap_deg))
+
+    def _observe_dense(self, args):
+        H, k, z, R, wrap, gate, res, nu, S = args
+        self._check(self.lib.ekf_observe_dense(self.h, _p(H), k, _p(z), _p(R), wrap, gate, ctypes.byref(res), _p(nu), _p(S)))
+        return marshal.dense_result(args)
+
+    def dense_innovation(self, H, z, R, wrap_deg=None):
+        """What observe_dense would report -- the same dict, bit for bit, with no gate read -- and nothing changed beyond the flush;
+        an irregular S is reported (outcome EKF_LINEAR_IRREGULAR, 'bad_row'), not raised (ekf_observe_dense_innovation)."""
+        args = marshal.dense_args(H, z, R, 3 + 2 * self.N, marshal.INF, wrap_deg, who="dense_innovation")
+        H, k, z, R, wrap, _, res, nu, S = args
+        self._check(self.lib.ekf_observe_dense_innovation(self.h, _p(H), k, _p(z), _p(R), wrap, ctypes.byref(res), _p(nu), _p(S)))
+        return marshal.dense_result(args)
+
     @staticmethod
     def model_invert(model, xr, z, lib=None):
         """(t, Gx, Gz): the landmark that z observes from the robot state xr = (x, y, theta in degrees) through EKF_MODEL_RANGE_BEARING

@@ -280,6 +280,74 @@ def multiply_result(args):
     return args[2]
 
 
+def dense_rows(H, n, who="observe_dense"):
+    """H of observe_dense as a k x n array: a k x n array (one row of n entries: k = 1), or a list of {state index: coefficient} rows
+    (0-based indices into x; an index twice in a row cannot be written, an index outside the state is refused)."""
+    if isinstance(H, (list, tuple)) and len(H) > 0 and all(isinstance(r, dict) for r in H):
+        Hv = np.zeros((len(H), n))
+        for i, row in enumerate(H):
+            for col, v in row.items():
+                c = int(col)
+                if c != col or not 0 <= c < n:
+                    raise ValueError("%s: a state index of row %d is outside 0 .. %d" % (who, i, n - 1))
+                Hv[i, c] = float(v)
+        return Hv
+    Hv = np.asarray(H, dtype=np.float64)
+    if Hv.ndim == 1:
+        Hv = Hv.reshape(1, -1)
+    if Hv.ndim != 2 or Hv.shape[1] != n:
+        raise ValueError("%s: H is k x %d (one row per observation row, x's order)" % (who, n))
+    return np.ascontiguousarray(Hv)
+
+
+def dense_args(H, z, R, n, gate=INF, wrap_deg=None, who="observe_dense"):
+    """(H, k, z, R, wrap, gate, res, nu, S) of observe_dense as the ABI takes them, the arrays kept so that dense_result reads what the
+    call wrote.  Refused here, in the ABI's order: k outside 1 .. EKF_DENSE_MAX; z not k values or not finite; R not k x k (a single value
+    with k = 1, or k values: the diagonal), not finite, not exactly symmetric, a negative diagonal entry; a NaN gate; H not finite;
+    wrap_deg not k flags."""
+    Hv = dense_rows(H, n, who)
+    k = Hv.shape[0]
+    if not 1 <= k <= L.EKF_DENSE_MAX:
+        raise ValueError("%s: between 1 and %d rows" % (who, L.EKF_DENSE_MAX))
+    zv = _vec(z)
+    if zv.size != k:
+        raise ValueError("%s: z has one value per row of H" % who)
+    if not np.isfinite(zv).all():
+        raise ValueError("%s: z is not finite" % who)
+    Ra = np.asarray(R, dtype=np.float64)
+    if Ra.size == k and Ra.ndim < 2:
+        Ra = np.diag(Ra.reshape(-1))
+    if Ra.size != k * k:
+        raise ValueError("%s: R is k x k (or its k diagonal entries)" % who)
+    Ra = Ra.reshape(k, k)
+    if not np.isfinite(Ra).all():
+        raise ValueError("%s: R is not finite" % who)
+    if not np.array_equal(Ra, Ra.T):
+        raise ValueError("%s: R is not symmetric" % who)
+    if (np.diag(Ra) < 0.0).any():
+        raise ValueError("%s: R has a negative diagonal entry" % who)
+    gate = float(gate)
+    if gate != gate:
+        raise ValueError("%s: the gate is NaN" % who)
+    if not np.isfinite(Hv).all():
+        raise ValueError("%s: H is not finite" % who)
+    wrap = None
+    if wrap_deg is not None:
+        flags = [1 if w else 0 for w in wrap_deg]
+        if len(flags) != k:
+            raise ValueError("%s: wrap_deg has one flag per row of H" % who)
+        wrap = (ctypes.c_int32 * k)(*flags)
+    Rv = np.ascontiguousarray(Ra.reshape(-1, order="F"))
+    return Hv, k, zv, Rv, wrap, gate, L.EkfObserveDenseResult(), np.empty(k), np.empty(k * k)
+
+
+def dense_result(args):
+    """What observe_dense returns from what the call wrote: 'd2', 'rows', 'outcome', 'bad_row', 'nu' (k) and 'S' (k x k)."""
+    k, res, nu, S = args[1], args[6], args[7], args[8]
+    return {"d2": float(res.d2), "rows": int(res.rows), "outcome": int(res.outcome), "bad_row": int(res.bad_row), "nu": nu,
+            "S": S.reshape(k, k).T.copy()}
+
+
 def model_inits(entries, who="append_model"):
     """(ekf_model_init[], m) of a scan of new landmarks [(model, z, R, signature), ...]."""
     entries = list(entries)

@@ -438,6 +438,75 @@ class _EkfBase:
         z = self._definite_solve("solve_residual", Bv, form)
         return z, self._e.multiply_map(z) - Bv.reshape(z.shape)
 
+    def observe_dense(self, H, z, R, gate=float("inf"), wrap_deg=None):
+        """A linear observation "H x = z +- R" whose k <= 16 rows may touch EVERY landmark: H a k x (3 + 2 N) array in x's order or a
+        list of {state index: coefficient} rows (0-based indices into x), z the k values, R k x k (or its diagonal; 0 conditions
+        exactly), wrap_deg the rows whose innovation is an angle in degrees.  Exact, no linearisation; applied only if d2 <= gate.  One
+        product pass and one update pass over P on the device, the pending pairs flushed first (Engine.observe_dense;
+        ekf_observe_dense).  Returns {'d2', 'rows', 'outcome', 'bad_row', 'nu', 'S'}; an S that is not positive definite raises
+        EkfError and changes nothing.  Unsharded handles only.  The reference has no such method."""
+        args = marshal.dense_args(H, z, R, 3 + 2 * self._e.N, gate, wrap_deg)            # the one set of arrays: sent, then logged from
+        res = self._e._observe_dense(args)
+        if self.log is not None:
+            Hv, k, zv, Rv, wrap, g = args[:6]
+            self.log.record_dense_observation(Hv, zv, Rv.reshape(k, k).T, g, None if wrap is None else list(wrap))
+        return res
+
+    def dense_innovation(self, H, z, R, wrap_deg=None):
+        """What observe_dense would report (the same dict, no gate read), with nothing changed beyond the flush; an irregular S is
+        reported in 'outcome' and 'bad_row', not raised (Engine.dense_innovation; ekf_observe_dense_innovation).  Nothing is logged."""
+        return self._e.dense_innovation(H, z, R, wrap_deg)
+
+    @staticmethod
+    def _dense_gate(who, p, dof):
+        """The gate of a policy below: +inf (p None), or the chi-square quantile of probability p for dof rows."""
+        if p is None:
+            return float("inf")
+        if not 0.0 < float(p) < 1.0:
+            raise ValueError("%s: p lies strictly between 0 and 1, or is None for no gate" % who)
+        return chi2_quantile(p, dof)
+
+    def fix_centroid(self, idx, z, R, p=None):
+        """A position fix of the CENTROID of the landmarks idx (0-based, distinct, as cross_covariance takes them): the two rows
+        mean(l_i) = z +- R (2 x 2) as ONE observe_dense call -- a GPS fix of a surveyed group.  p: applied only if d2 stays below the
+        chi-square quantile of that probability for 2 rows (None: no gate).  Returns observe_dense's dict."""
+        cols = self._state_columns("fix_centroid", idx)
+        w = 1.0 / (cols.size // 2)
+        rows = [{int(c): w for c in cols[0::2]}, {int(c): w for c in cols[1::2]}]
+        return self.observe_dense(rows, z, R, self._dense_gate("fix_centroid", p, 2))
+
+    def constrain_displacements(self, pairs, deltas, R, p=None):
+        """Up to 8 displacement constraints l_i - l_j = delta +- R between landmark pairs (i, j) (0-based, i != j) as ONE joint update,
+        the joint form of constrain_landmarks -- a fiducial board, the corners of a building.  deltas: one (dx, dy) per pair; R:
+        2 m x 2 m over the stacked rows (pair 0's x, pair 0's y, pair 1's x, ...), or one 2 x 2 block that every pair shares.  p:
+        as for fix_centroid, for 2 m rows.  Returns observe_dense's dict."""
+        who = "constrain_displacements"
+        pairs = [tuple(self._landmark_numbers(who, *pr)) for pr in pairs]
+        m, N = len(pairs), self._e.N
+        if not 1 <= m <= 8 or any(len(pr) != 2 or pr[0] == pr[1] or not (0 <= pr[0] < N and 0 <= pr[1] < N) for pr in pairs):
+            raise ValueError("%s: 1 to 8 pairs (i, j) of different landmarks 0 .. N - 1" % who)
+        d = np.asarray(deltas, dtype=np.float64)
+        if d.size != 2 * m:
+            raise ValueError("%s: one (dx, dy) per pair" % who)
+        Ra = np.asarray(R, dtype=np.float64)
+        if Ra.size == 4 and m > 1:
+            Ra = np.kron(np.eye(m), Ra.reshape(2, 2))
+        rows = [{3 + 2 * i + r: 1.0, 3 + 2 * j + r: -1.0} for i, j in pairs for r in (0, 1)]
+        return self.observe_dense(rows, d.reshape(-1), Ra, self._dense_gate(who, p, 2 * m))
+
+    def condition_on(self, idx, values, p=None):
+        """The map CONDITIONED on up to 8 landmarks idx (0-based, distinct) whose positions became known exactly: l_i = values[i] with
+        R = 0, ONE observe_dense call.  Afterwards those landmarks' rows of P are zero (to rounding), so P is no longer positive
+        definite (factor_map says where) and the other landmarks carry their conditional covariance.  p: as for fix_centroid, for 2 m
+        rows.  Returns observe_dense's dict."""
+        cols = self._state_columns("condition_on", idx)
+        if cols.size > 16:
+            raise ValueError("condition_on: at most 8 landmarks")
+        v = np.asarray(values, dtype=np.float64).reshape(-1)
+        if v.size != cols.size:
+            raise ValueError("condition_on: one (x, y) per landmark")
+        return self.observe_dense([{int(c): 1.0} for c in cols], v, np.zeros((cols.size, cols.size)), self._dense_gate("condition_on", p, cols.size))
+
     def fuse_duplicates(self, gate, R=None, max_merges=None):
         """The SIMPLEST complete fusion policy, not the fastest: repeat { search; take the candidate with the smallest (d2, i) at or
         below `gate`; merge_landmarks(keep=j, drop=i, R) } until none is left or `max_merges` merges were made.  One search plus

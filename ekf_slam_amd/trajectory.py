@@ -39,6 +39,7 @@ FORMAT_JOINT = "ekfslam-trajectory-9"
 FORMAT_JOINT_ITERATED = "ekfslam-trajectory-10"
 FORMAT_JOIN_MAP = "ekfslam-trajectory-11"
 FORMAT_TRANSFORM_MAP = "ekfslam-trajectory-12"
+FORMAT_OBSERVE_DENSE = "ekfslam-trajectory-13"
 EDIT_KINDS = ("remove", "constrain", "merge", "merge_batch")        # what record_edit takes
 OBSERVE = "observe"                                                  # record_observation's
 OBSERVE_MODEL = "observe_model"                                      # record_model_observation's
@@ -49,12 +50,15 @@ OBSERVE_MODEL_JOINT = "observe_model_joint"                          # record_mo
 OBSERVE_MODEL_JOINT_ITERATED = "observe_model_joint_iterated"        # record_model_observation_joint_iterated's
 JOIN_MAP = "join_map"                                                # record_map_join's
 TRANSFORM_MAP = "transform_map"                                      # record_map_transform's
+OBSERVE_DENSE = "observe_dense"                                      # record_dense_observation's
 _FORMATS = (FORMAT, FORMAT_EDITS, FORMAT_BATCH, FORMAT_OBSERVE, FORMAT_MODEL, FORMAT_APPEND, FORMAT_PREDICT, FORMAT_ITERATED, FORMAT_JOINT,
             FORMAT_JOINT_ITERATED)
 # ... the ten formats of a log that speaks of ONE map; a log with a join also holds a second map's state and is written in the eleventh
 _ALL_FORMATS = _FORMATS + (FORMAT_JOIN_MAP,)
 # ... and every format a file may carry: the twelfth adds the map's change of frame (the two tuples above are counted by their users)
 _EVERY_FORMAT = _ALL_FORMATS + (FORMAT_TRANSFORM_MAP,)
+# ... and what save and load index: the thirteenth adds the linear observation with a dense H (the three tuples above keep their contents)
+_FORMATS_ON_DISK = _EVERY_FORMAT + (FORMAT_OBSERVE_DENSE,)
 _STEP_ARRAYS = ("u", "obs_ptr", "obs", "lm_ptr", "lm_index", "lm_loc")
 _EDIT_ARRAYS = ("edit_step", "edit_kind", "edit_ptr", "edit_idx", "edit_delta", "edit_R")
 
@@ -107,6 +111,24 @@ def _trim_motion(step):
     """u and M of the size the model reads: a model with two inputs left the rest of its row zero."""
     nu = EKF_MOTION_INPUTS.get(step[0], 3)
     return step[0], step[1][:nu].copy(), step[2][:nu, :nu].copy()
+
+
+def _dense_H(o):
+    """The k x n H of an 'observe_dense' payload from its (row, column, value) triplets."""
+    H = np.zeros((o["rows"], o["n"]))
+    H[o["row"], o["col"]] = o["val"]
+    return H
+
+
+def _replay_dense(engine, idx0, d, R, o):
+    engine.observe_dense(_dense_H(o), o["z"], o["R"], gate=o["gate"], wrap_deg=[int(w) for w in o["wrap"]])
+
+
+def _dense_shape(key, flat):
+    if key == "R":
+        k = int(round(flat.size ** 0.5))
+        return flat.reshape(k, k)
+    return flat
 
 
 _KINDS_TABLE = (
@@ -164,7 +186,19 @@ _KINDS_TABLE = (
           (_Field("frame", "frame", _I, ()), _Field("t", "t", _F, (3,), True), _Field("Sigma", "Sigma", _F, (3, 3), True))),
 )
 _KINDS = tuple(k.name for k in _KINDS_TABLE)
-_KIND = {k.name: k for k in _KINDS_TABLE}
+# ... the kinds of a file up to format 12, which their users count.  What save, load and replay go through is the table with the kinds
+# added since behind them (a kind's position is its number in a file's edit_kind, so the older numbers stay what they were):
+_KINDS_ON_DISK_TABLE = _KINDS_TABLE + (
+    # observe_dense: a linear observation with a dense k x n H, idx empty; per observation k, n, the gate, H SPARSE as (row, column, value)
+    # triplets of its non-zero entries in row-major order, z (k), R (k x k) and the wrap flags (k), each flattened behind CSR offsets of its own
+    _Kind(OBSERVE_DENSE, 13, _replay_dense, "dense_observations", "dense",
+          (_Field("rows", "rows", _I, ()), _Field("n", "n", _I, ()), _Field("gate", "gate", _F, ()), _Field("row", "row", _I, None),
+           _Field("col", "col", _I, None), _Field("val", "val", _F, None), _Field("z", "z", _F, None), _Field("R", "R", _F, None),
+           _Field("wrap", "wrap", _I, None)),
+          ragged=True, shape=_dense_shape),
+)
+_KINDS_ON_DISK = tuple(k.name for k in _KINDS_ON_DISK_TABLE)
+_KIND = {k.name: k for k in _KINDS_ON_DISK_TABLE}
 
 
 def _arrays_of(kind):
@@ -238,6 +272,7 @@ class TrajectoryLog:
         self.model_joint_iterations = {}  # position in self.edits of an 'observe_model_joint_iterated' edit -> the same list
         self.map_transforms = {}    # position in self.edits of a 'transform_map' edit -> {frame 0 / 1, t (3) or None, Sigma (3x3) or None}
         self.map_joins = {}         # position in self.edits of a 'join_map' edit -> {x (3 + 2 M), s (M), P dense, offset}: the local map
+        self.dense_observations = {}  # position in self.edits of an 'observe_dense' edit -> {rows, n, gate, row, col, val (H's triplets), z, R (k x k), wrap}
         self.observations = {}      # position in self.edits of an 'observe' edit -> {Hr (2x3), Hl (2x2x2), gate, wrap (2), rows}
 
     def __len__(self):
@@ -369,6 +404,24 @@ class TrajectoryLog:
         Sm = None if Sigma is None else np.asarray(Sigma, dtype=np.float64).reshape(3, 3).copy()
         self._record(TRANSFORM_MAP, payload=dict(frame=int(frame == "robot"), t=tv, Sigma=Sm))
 
+    def record_dense_observation(self, H, z, R, gate=float("inf"), wrap_deg=None):
+        """A linear observation with a dense H (observe_dense of ekf_slam_amd/slam.py) made now, i.e. after the len(self) steps recorded
+        so far: H (k x n) as the wrapper handed it to the engine -- kept as the triplets of its non-zero entries --, z (k), R (k x k,
+        symmetric), the gate and the wrap flags (None: none)."""
+        Hv = np.asarray(H, dtype=np.float64)
+        if Hv.ndim != 2 or Hv.shape[0] < 1:
+            raise ValueError("record_dense_observation: H is k >= 1 rows")
+        k, n = Hv.shape
+        zv, Rm = np.asarray(z, dtype=np.float64).reshape(-1).copy(), np.asarray(R, dtype=np.float64)
+        if zv.size != k or Rm.size != k * k:
+            raise ValueError("record_dense_observation: z has k values and R is k x k")
+        wv = np.zeros(k, dtype=np.int64) if wrap_deg is None else np.array([int(bool(w)) for w in wrap_deg], dtype=np.int64)
+        if wv.size != k:
+            raise ValueError("record_dense_observation: wrap_deg has k flags")
+        row, col = np.nonzero(Hv)
+        self._record(OBSERVE_DENSE, payload=dict(rows=int(k), n=int(n), gate=float(gate), row=row.astype(np.int64), col=col.astype(np.int64),
+                                                 val=Hv[row, col].copy(), z=zv, R=Rm.reshape(k, k).copy(), wrap=wv))
+
     def record_model_predict(self, steps):
         """One chain of motion steps (predict_model of ekf_slam_amd/slam.py) made now, i.e. after the len(self) steps recorded so far:
         steps = [(model, u, M), ...], at least one, u and M of the size the model reads (2 and 2 x 2, or 3 and 3 x 3)."""
@@ -388,18 +441,18 @@ class TrajectoryLog:
             data = np.concatenate(parts) if parts and ptr[-1] else np.zeros((0, width) if width else (0,))
             return ptr, data
         ver = max([1] + [_KIND[e[1]].format for e in self.edits])
-        arrays = dict(format=np.array(_EVERY_FORMAT[ver - 1]))
+        arrays = dict(format=np.array(_FORMATS_ON_DISK[ver - 1]))
         if self.edits:
             e_ptr, e_idx = ragged([e[2] for e in self.edits], 0)
             arrays.update(edit_step=np.array([e[0] for e in self.edits], dtype=np.int64),
-                          edit_kind=np.array([_KINDS.index(e[1]) for e in self.edits], dtype=np.int64), edit_ptr=e_ptr,
+                          edit_kind=np.array([_KINDS_ON_DISK.index(e[1]) for e in self.edits], dtype=np.int64), edit_ptr=e_ptr,
                           edit_idx=e_idx.astype(np.int64), edit_delta=np.array([e[3] for e in self.edits]).reshape(-1, 2),
                           edit_R=np.array([e[4] for e in self.edits]).reshape(-1, 2, 2))
         obs_ptr, obs = ragged(self.obs, 3)
         lm_ptr, lmi = ragged(self.lm_index, 0)
         _, lml = ragged(self.lm_loc, 2)
         arrays.update(u=np.array(self.u).reshape(-1, 2), obs_ptr=obs_ptr, obs=obs, lm_ptr=lm_ptr, lm_index=lmi, lm_loc=lml)
-        for kind in _KINDS_TABLE:
+        for kind in _KINDS_ON_DISK_TABLE:
             if kind.store and kind.format <= ver:
                 arrays.update(_pack(kind, getattr(self, kind.store)))
         np.savez_compressed(path, **arrays)
@@ -408,10 +461,10 @@ class TrajectoryLog:
     def load(path):
         g = np.load(path, allow_pickle=False)
         fmt = str(g["format"])
-        if fmt not in _EVERY_FORMAT:
-            raise ValueError("not an %s file" % " / ".join(_EVERY_FORMAT))
-        ver = _EVERY_FORMAT.index(fmt) + 1
-        held = [kind for kind in _KINDS_TABLE if kind.store and kind.format <= ver]
+        if fmt not in _FORMATS_ON_DISK:
+            raise ValueError("not an %s file" % " / ".join(_FORMATS_ON_DISK))
+        ver = _FORMATS_ON_DISK.index(fmt) + 1
+        held = [kind for kind in _KINDS_ON_DISK_TABLE if kind.store and kind.format <= ver]
         need = _STEP_ARRAYS + (_EDIT_ARRAYS if ver >= 2 else ()) + tuple(name for kind in held for name in _arrays_of(kind))
         missing = [k for k in need if k not in g.files]
         if missing:
@@ -425,7 +478,7 @@ class TrajectoryLog:
         if ver >= 2:
             for q in range(len(g["edit_step"])):
                 a, b = g["edit_ptr"][q], g["edit_ptr"][q + 1]
-                t.edits.append((int(g["edit_step"][q]), _KINDS[int(g["edit_kind"][q])], g["edit_idx"][a:b].astype(np.int64),
+                t.edits.append((int(g["edit_step"][q]), _KINDS_ON_DISK[int(g["edit_kind"][q])], g["edit_idx"][a:b].astype(np.int64),
                                 g["edit_delta"][q].copy(), g["edit_R"][q].copy()))
         for kind in held:
             _unpack(kind, g, getattr(t, kind.store))

@@ -729,6 +729,51 @@ int32_t ekf_solve_map(ekf_handle *h, int32_t form, const double *B /* k x (3 + 2
  * leaves every entry of out NaN. */
 int32_t ekf_multiply_map(ekf_handle *h, const double *B /* k x (3 + 2N), one row per vector, x's order */,
                          int64_t k /* >= 1 */, double *out /* k x (3 + 2N) */);
+/* A LINEAR OBSERVATION WITH A DENSE H: "H x = z +- R" for k <= EKF_DENSE_MAX rows of 3 + 2 N finite entries in x's order, every row free to
+ * touch every landmark -- the fix of a group's centroid, displacement constraints between several landmarks applied jointly, conditioning
+ * on landmarks whose positions became known (R = 0), a loop closure delivered as a linear factor.  Exact, no linearisation:
+ *     G = P H'      S = H G + R      nu = z - H x  (a row flagged in wrap_deg wrapped into (-180, 180], as ekf_observe_linear's)
+ * and, with L L' = S, W = L^-1 G' and y = L^-1 nu, the symmetric form of ekf_observe_model_joint, with no back substitution:
+ *     d2 = |y|^2        x' = x + W' y        P' = P - W' W.
+ * The heading is not re-wrapped afterwards.  res (required; rows = k), nu (k) and S (k x k, column-major, symmetric as read):
+ *   EKF_LINEAR_APPLIED    d2 <= gate (+inf: no gate): the update above ran.
+ *   EKF_LINEAR_GATED      d2 > gate: EKF_OK, nothing changed beyond the flush.
+ *   EKF_LINEAR_IRREGULAR  a pivot of S is not finite and positive (bad_row: the first such row, -1 otherwise): EKF_ERR_STATE, nothing
+ *                         changed beyond the flush -- the record is read back and waited for before anything is written -- and the
+ *                         handle goes on working.  Whether a singular S (R = 0 and two rows that say the same) is found so depends on
+ *                         the rounding of that pivot: it is exactly what the device computed.
+ * Neither refusal is counted by ekf_linear_rejections.  An odd k runs as k + 1 rows whose last is exactly empty (H = 0, R's row and
+ * column 0 but a 1 on the diagonal, z = 0) -- ekf_observe_linear's convention for rows == 1 --, and leaves the bits of the call with that
+ * row written out.
+ * G is ONE chunk of ekf_multiply_map (its tile pass and its sums, unchanged, in its scratch; no download); k_dense_gram forms the lower
+ * triangle of H G and H x over fixed segments of 128 rows, each in ascending row order, k_dense_factor adds them in ascending segment
+ * order, factors S and forms d2; after the decision k_gather_dense forms W column by column and the pairs (rows 2 p, 2 p + 1 of W, twice)
+ * go to ekf_merge_landmarks_batch's private F64 ring, slots 0 .. ceil(k / 2) - 1, and ONE F64-arithmetic pass applies them in place on
+ * the main stream (float tiles are rounded once per entry, whatever cfg.pass_arith).  No atomics, no data-dependent order.  Afterwards
+ * ekf_pending is 0 and ekf_downdate_kernel_name reports that pass with pairs = ceil(k / 2) (N = 0: no pass, the robot part alone).  The
+ * call does not wait at its end and does not enter the pending ring.  The tile pass, k_dense_gram and k_dense_factor count under
+ * EKF_KERNEL_ASSOCIATE, the sums under _COMPACT, the gather under _GATHER, the pass under _DOWNDATE.
+ * A SYNCHRONISING EDIT on ekf_multiply_map's rungs.  Order of a call: h, H, z, R or res NULL, k outside 1 .. EKF_DENSE_MAX, an entry of z
+ * or R that is not finite, R not exactly symmetric or with a negative diagonal entry, a NaN gate, an entry of H that is not finite
+ * (EKF_ERR_INVALID_ARG; on a handle with cfg.device_assoc == 4 and rows still unsettled H is read once N is exact, behind the rungs);
+ * world > 1 (EKF_ERR_INVALID_ARG; a lone cfg.force_sharded shard works); a sharded correction between begin and finish (EKF_ERR_STATE);
+ * every allocation; the flush (a recorded predict carried out, the pending pairs applied, a pass in flight retired); the chunk, the
+ * product, the two small launches, ONE readback and the decision; the gather; the pass.  R = 0 is allowed.
+ * ekf_observe_dense_innovation is the same body stopped after the decision (no gate): res, nu and S bit for bit what ekf_observe_dense
+ * would report; x, s, P and ekf_P_digest afterwards those of a handle that only flushed. */
+#define EKF_DENSE_MAX 16          /* rows per call = one chunk of ekf_multiply_map */
+typedef struct ekf_observe_dense_result {
+    double  d2;
+    int32_t rows;                  /* k */
+    int32_t outcome;               /* EKF_LINEAR_APPLIED, _GATED or _IRREGULAR                 */
+    int32_t bad_row;               /* the first row whose pivot is not finite and positive, or -1 */
+} ekf_observe_dense_result;
+int32_t ekf_observe_dense(ekf_handle *h, const double *H /* k x (3 + 2N), one row per observation row, x's order */,
+                          int64_t k, const double *z /* k */, const double *R /* k x k column-major */,
+                          const int32_t *wrap_deg /* k, may be NULL */, double gate,
+                          ekf_observe_dense_result *res /* required */, double *nu /* k, may be NULL */, double *S /* k x k, may be NULL */);
+int32_t ekf_observe_dense_innovation(ekf_handle *h, const double *H, int64_t k, const double *z, const double *R, const int32_t *wrap_deg,
+                                     ekf_observe_dense_result *res, double *nu, double *S);
 /* The step between the two: "WHICH landmark does this sighting belong to?", for a whole scan, under the conventions of ekf_observe_model.
  * ekf_associate keeps the reference's (signature-only by default, an unwrapped bearing, a range-scaled R) and cannot serve a filter
  * driven through the model calls.  For each of the m observations, d2(k, i) is, BIT FOR BIT, the d2 that ekf_model_innovation reports for

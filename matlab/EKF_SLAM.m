@@ -318,6 +318,17 @@ classdef EKF_SLAM < handle
             % wrapped.  Read-only.  Not a method of the reference.
             out = h.gateway('multiply_map', double(B));
         end
+        function [res, nu, S] = observeDense(h, H, z, R, gate, wrap)
+            % A LINEAR OBSERVATION WITH A DENSE H: 'H * x = z +- R' for k <= 16 rows (H: k x n, n = 3 + 2 N) that may touch EVERY landmark
+            % -- the fix of a group's centroid, displacement constraints applied jointly, conditioning with R = 0.  Exact, applied only
+            % if d2 <= gate (default Inf); wrap: the rows whose innovation is an angle in degrees (default none).  One product pass and
+            % one update pass over the tiled P on the GPU.  res: struct with d2, rows, outcome (1 applied, 2 gated) and bad_row; an S
+            % that is not positive definite is an error and changes nothing.  Not a method of the reference.
+            if nargin < 5, gate = Inf; end
+            if nargin < 6, wrap = []; end
+            [v, nu, S] = h.gateway('observe_dense', double(H).', double(z), double(R), double(gate), double(wrap));
+            res = struct('d2', v(1), 'rows', v(2), 'outcome', v(3), 'bad_row', v(4));
+        end
         function idx = addLandmarkRangeBearing(h, z, R, signature)
             % 'A landmark that is not in the map yet is seen at range z(1) and bearing z(2) (degrees, relative to the heading),
             % covariance R': it joins the map at the point that observation names.

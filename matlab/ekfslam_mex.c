@@ -54,6 +54,7 @@
 #pragma weak ekf_sample_map
 #pragma weak ekf_solve_map
 #pragma weak ekf_multiply_map
+#pragma weak ekf_observe_dense
 #define HAVE_REMOVE_LANDMARKS (ekf_remove_landmarks != 0)
 #define HAVE_CONSTRAIN_LANDMARKS (ekf_constrain_landmarks != 0)
 #define HAVE_MERGE_LANDMARKS (ekf_merge_landmarks != 0)
@@ -78,6 +79,7 @@
 #define HAVE_SAMPLE_MAP (ekf_sample_map != 0)
 #define HAVE_SOLVE_MAP (ekf_solve_map != 0)
 #define HAVE_MULTIPLY_MAP (ekf_multiply_map != 0)
+#define HAVE_OBSERVE_DENSE (ekf_observe_dense != 0)
 #else
 #define HAVE_REMOVE_LANDMARKS 1
 #define HAVE_CONSTRAIN_LANDMARKS 1
@@ -102,6 +104,7 @@
 #define HAVE_SAMPLE_MAP 1
 #define HAVE_SOLVE_MAP 1
 #define HAVE_MULTIPLY_MAP 1
+#define HAVE_OBSERVE_DENSE 1
 #endif
 
 static void need(int nrhs, int want, const char *cmd) {
@@ -580,6 +583,34 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
         const int32_t rc = ekf_multiply_map(h, mxGetPr(prhs[2]), (int64_t)k, mxGetPr(out));   /* (MATLAB arrays are column-major) */
         if (rc != EKF_OK) { mxDestroyArray(out); check(h, rc); }
         plhs[0] = out;
+        return;
+    }
+    if (!strcmp(cmd, "observe_dense")) {          /* [res, nu, S] = (h, H, z, R, gate, wrap): "H x = z +- R" for k <= 16 rows that may touch every landmark.  H: n x k,
+                                                     one ROW of the observation a column (n = 3 + 2 N); z: k; R: k x k; gate: scalar (Inf: none); wrap: k
+                                                     flags or empty; res = [d2 rows outcome bad_row], bad_row 1-based and 0 = none; nu: k x 1; S: k x k */
+        need(nrhs, 7, cmd);
+        if (!HAVE_OBSERVE_DENSE) mexErrMsgIdAndTxt("ekfslam:usage", "observe_dense: this libekfslam has no ekf_observe_dense");
+        const int64_t n = nstate(h);
+        const mwSize nel = prhs[2] ? mxGetNumberOfElements(prhs[2]) : 0;
+        const mwSize k = nel / (mwSize)n;
+        if (nel == 0 || !mxGetPr(prhs[2]) || k * (mwSize)n != nel || k > EKF_DENSE_MAX)
+            mexErrMsgIdAndTxt("ekfslam:usage", "observe_dense: H is n x k, n = 3 + 2 N entries a column and 1 <= k <= %d columns", EKF_DENSE_MAX);
+        if (!prhs[3] || mxGetNumberOfElements(prhs[3]) != k || !mxGetPr(prhs[3])) mexErrMsgIdAndTxt("ekfslam:usage", "observe_dense: z needs k elements");
+        if (!prhs[4] || mxGetNumberOfElements(prhs[4]) != k * k || !mxGetPr(prhs[4])) mexErrMsgIdAndTxt("ekfslam:usage", "observe_dense: R needs k x k elements");
+        const mwSize nw = prhs[6] ? mxGetNumberOfElements(prhs[6]) : 0;
+        if (nw != 0 && (nw != k || !mxGetPr(prhs[6]))) mexErrMsgIdAndTxt("ekfslam:usage", "observe_dense: wrap needs k elements, or none");
+        int32_t wrap[EKF_DENSE_MAX];
+        for (mwSize i = 0; i < nw; ++i) wrap[i] = mxGetPr(prhs[6])[i] != 0.0;
+        ekf_observe_dense_result res;
+        mxArray *nu = mxCreateDoubleMatrix(k, 1, mxREAL), *S = mxCreateDoubleMatrix(k, k, mxREAL);
+        const int32_t rc = ekf_observe_dense(h, mxGetPr(prhs[2]), (int64_t)k, mxGetPr(prhs[3]), mxGetPr(prhs[4]), nw ? wrap : NULL, mxGetScalar(prhs[5]),
+                                             &res, mxGetPr(nu), mxGetPr(S));        /* (MATLAB arrays are column-major: a column of H is a row of the ABI's) */
+        if (rc != EKF_OK) { mxDestroyArray(nu); mxDestroyArray(S); check(h, rc); }
+        plhs[0] = mxCreateDoubleMatrix(1, 4, mxREAL);
+        double *o = mxGetPr(plhs[0]);
+        o[0] = res.d2; o[1] = (double)res.rows; o[2] = (double)res.outcome; o[3] = (double)(res.bad_row + 1);
+        if (nlhs > 1) plhs[1] = nu; else mxDestroyArray(nu);
+        if (nlhs > 2) plhs[2] = S; else mxDestroyArray(S);
         return;
     }
     if (!strcmp(cmd, "associate_model")) {        /* [match, d2] = (h, model m x 1 (1..4), z m x 2, R 2 x 2 x m, gate m x 1): which landmark each sighting of a
