@@ -47,6 +47,54 @@ constexpr size_t kFactorTailDoubles = 4;
 int64_t sample_ld(int64_t rows) { return rows + 4; }
 size_t sample_chunk_doubles(int64_t rows) { return (size_t)sample_ld(rows) * (size_t)factor_chunk(); }
 
+// THE CHUNK PIPELINE of ekf_sample_map, ekf_solve_map (factor_body below) and ekf_multiply_map (host/multiply_map.h): the k vectors of
+// `src`, rows of n = 3 + 2 N entries in x's order, a chunk of factor_chunk() at a time.  A vector is a COLUMN of its chunk with the
+// landmark part first (`rows` entries, zero from 2 N on) and the robot's three behind it; a partial last chunk is zero-padded.  Per chunk:
+// a pinned slot of in_slots zeroed, packed and uploaded to d_in, launch_chunk() -- the caller's launches for one chunk, which returns a
+// status --, d_out downloaded into the slot of out_slots, that slot's event recorded.  The host waits only where it takes a slot again,
+// kSampleSlots chunks later, for that slot's own download, and unpacks it into the rows of `out` then; the last kSampleSlots slots are
+// left to chunk_stream_tail, after the caller's final synchronise.
+void chunk_unpack(const double *out_slots, int64_t rows, int64_t N, int64_t k, double *out, int64_t j) {
+    const int64_t C = factor_chunk(), ld = sample_ld(rows), n = 3 + 2 * N;
+    const double *y = out_slots + (size_t)(j % kSampleSlots) * sample_chunk_doubles(rows);
+    for (int64_t c = 0; c < C && j * C + c < k; ++c) {
+        double *o = out + (j * C + c) * n;
+        std::memcpy(o, y + c * ld + rows, 3 * sizeof(double));
+        std::memcpy(o + 3, y + c * ld, (size_t)(2 * N) * sizeof(double));
+    }
+}
+
+template <typename F>
+int32_t chunk_stream(ekf_handle *h, double *in_slots, double *out_slots, hipEvent_t *events, double *d_in, const double *d_out, int64_t rows,
+                     int64_t N, const double *src, int64_t k, double *out, F launch_chunk) {
+    const int64_t C = factor_chunk(), ld = sample_ld(rows), n = 3 + 2 * N, nchunks = (k + C - 1) / C;
+    const size_t chunk = sample_chunk_doubles(rows);
+    for (int64_t j = 0; j < nchunks; ++j) {
+        const int slot = (int)(j % kSampleSlots);
+        if (j >= kSampleSlots) {
+            HIPCHK(h, hipEventSynchronize(events[slot]));
+            chunk_unpack(out_slots, rows, N, k, out, j - kSampleSlots);
+        }
+        double *u = in_slots + (size_t)slot * chunk;
+        std::memset(u, 0, chunk * sizeof(double));
+        for (int64_t c = 0; c < C && j * C + c < k; ++c) {
+            const double *row = src + (j * C + c) * n;
+            std::memcpy(u + c * ld, row + 3, (size_t)(2 * N) * sizeof(double));
+            std::memcpy(u + c * ld + rows, row, 3 * sizeof(double));
+        }
+        HIPCHK(h, hipMemcpyAsync(d_in, u, chunk * sizeof(double), hipMemcpyHostToDevice, h->stream));
+        TRY(launch_chunk());
+        HIPCHK(h, hipMemcpyAsync(out_slots + (size_t)slot * chunk, d_out, chunk * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipEventRecord(events[slot], h->stream));
+    }
+    return EKF_OK;
+}
+
+void chunk_stream_tail(const double *out_slots, int64_t rows, int64_t N, int64_t k, double *out) {
+    const int64_t C = factor_chunk(), nchunks = (k + C - 1) / C;
+    for (int64_t j = nchunks > kSampleSlots ? nchunks - kSampleSlots : 0; j < nchunks; ++j) chunk_unpack(out_slots, rows, N, k, out, j);
+}
+
 // The scratch for `rows` rows (a multiple of the factor store's tile edge), everything that can fail for lack of memory, before anything
 // is queued.  Nothing is cleared (dalloc would clear on the null stream, which the handle's streams do not wait for): the launches write
 // every byte that is read, and the result block is cleared in stream order.  Nothing of it is in use here: every call ends drained.
@@ -175,58 +223,35 @@ int32_t factor_body(ekf_handle *h, const std::string &who, const double *ref, in
         if (c + 1 < nF) TIMED(h, EKF_KERNEL_DOWNDATE, launch_factor_column(a, (int)c, 2, h->stream));
     }
     TIMED(h, EKF_KERNEL_COMPACT, launch_factor_finish(h->st, a, h->stream));
-    // the draws: xi's rows permuted into elimination order as columns of a chunk on the way in (a partial last chunk zero-padded), the
-    // samples permuted back into rows of `out` on the way out
-    const int64_t C = factor_chunk(), ld = sample_ld(a.rows), nchunks = xi ? (k + C - 1) / C : 0;
-    const size_t chunk = sample_chunk_doubles(a.rows);
-    auto unpack = [&](int64_t j) {
-        const double *y = h->h_fy + (size_t)(j % kSampleSlots) * chunk;
-        for (int64_t c = 0; c < C && j * C + c < k; ++c) {
-            double *o = out + (j * C + c) * n;
-            std::memcpy(o, y + c * ld + a.rows, 3 * sizeof(double));
-            std::memcpy(o + 3, y + c * ld, (size_t)(2 * N) * sizeof(double));
-        }
-    };
+    // the draws: xi's rows permuted into elimination order as columns of a chunk on the way in, the samples permuted back into rows of
+    // `out` on the way out (chunk_stream)
     if (xi) {
+        const int64_t ld = sample_ld(a.rows);
         FactorSampleArgs sa = {};
         double *d_xi = h->d_fsample, *d_y = d_xi + sample_chunk_doubles(h->fs_rows);
         sa.xi = d_xi; sa.y = d_y; sa.part = d_y + sample_chunk_doubles(h->fs_rows); sa.ld = ld;
         FactorSolveArgs sv = {};
         sv.b = d_xi; sv.y = d_y; sv.inv = h->d_fsolve; sv.ld = ld; sv.form = form;
         if (form >= 0) TIMED(h, EKF_KERNEL_COMPACT, launch_solve_map(a, sv, 0, 0, h->stream));
-        for (int64_t j = 0; j < nchunks; ++j) {
-            const int slot = (int)(j % kSampleSlots);
-            if (j >= kSampleSlots) {
-                HIPCHK(h, hipEventSynchronize(h->ev_fslot[slot]));
-                unpack(j - kSampleSlots);
-            }
-            double *u = h->h_fxi + (size_t)slot * chunk;
-            std::memset(u, 0, chunk * sizeof(double));
-            for (int64_t c = 0; c < C && j * C + c < k; ++c) {
-                const double *row = xi + (j * C + c) * n;
-                std::memcpy(u + c * ld, row + 3, (size_t)(2 * N) * sizeof(double));
-                std::memcpy(u + c * ld + a.rows, row, 3 * sizeof(double));
-            }
-            HIPCHK(h, hipMemcpyAsync(d_xi, u, chunk * sizeof(double), hipMemcpyHostToDevice, h->stream));
+        // P^-1 B is left in the chunk of right-hand sides, everything else in the chunk behind it
+        TRY(chunk_stream(h, h->h_fxi, h->h_fy, h->ev_fslot, d_xi, form == 0 ? d_xi : d_y, a.rows, N, xi, k, out, [&]() -> int32_t {
             if (form < 0) {
                 TIMED(h, EKF_KERNEL_ASSOCIATE, launch_factor_sample(h->st, a, sa, 0, h->stream));
                 TIMED(h, EKF_KERNEL_COMPACT, launch_factor_sample(h->st, a, sa, 1, h->stream));
-            } else {
-                // the sweeps, sequential in the tile index: stream order is the only order between their workgroups
-                {
-                    TimedLaunch tl(h, EKF_KERNEL_ASSOCIATE);
-                    for (int64_t c = 0; c < nF; ++c) HIPCHK(h, launch_solve_map(a, sv, 1, (int)c, h->stream));
-                }
-                TIMED(h, EKF_KERNEL_COMPACT, launch_solve_map(a, sv, 2, 0, h->stream));
-                if (form == 0) {
-                    TimedLaunch tl(h, EKF_KERNEL_APPEND);
-                    for (int64_t c = nF - 1; c >= 0; --c) HIPCHK(h, launch_solve_map(a, sv, 3, (int)c, h->stream));
-                }
+                return EKF_OK;
             }
-            // P^-1 B is left in the chunk of right-hand sides, everything else in the chunk behind it
-            HIPCHK(h, hipMemcpyAsync(h->h_fy + (size_t)slot * chunk, form == 0 ? d_xi : d_y, chunk * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-            HIPCHK(h, hipEventRecord(h->ev_fslot[slot], h->stream));
-        }
+            // the sweeps, sequential in the tile index: stream order is the only order between their workgroups
+            {
+                TimedLaunch tl(h, EKF_KERNEL_ASSOCIATE);
+                for (int64_t c = 0; c < nF; ++c) HIPCHK(h, launch_solve_map(a, sv, 1, (int)c, h->stream));
+            }
+            TIMED(h, EKF_KERNEL_COMPACT, launch_solve_map(a, sv, 2, 0, h->stream));
+            if (form == 0) {
+                TimedLaunch tl(h, EKF_KERNEL_APPEND);
+                for (int64_t c = nF - 1; c >= 0; --c) HIPCHK(h, launch_solve_map(a, sv, 3, (int)c, h->stream));
+            }
+            return EKF_OK;
+        }));
     }
     HIPCHK(h, hipMemcpyAsync(h->h_fres, a.res, (kFactorRes + (size_t)(2 * N)) * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -255,7 +280,7 @@ int32_t factor_body(ekf_handle *h, const std::string &who, const double *ref, in
     for (int q = 0; q < nref; ++q) d2[q] = status == 0 ? res[8 + q] : NAN;
     // the samples of the last slots; where a pivot failed the launches returned at once and every entry is NaN
     if (xi && status == 0)
-        for (int64_t j = nchunks > kSampleSlots ? nchunks - kSampleSlots : 0; j < nchunks; ++j) unpack(j);
+        chunk_stream_tail(h->h_fy, a.rows, N, k, out);
     else if (xi)
         for (int64_t i = 0; i < k * n; ++i) out[i] = NAN;
     return EKF_OK;

@@ -3,8 +3,8 @@
 // READ-ONLY call on the rungs of host/edits.h, as ekf_nearest_landmarks and ekf_factor_map: a recorded predict carried out, the pending
 // pairs applied, an asynchronous pass retired; x, s, P, the diagonal copies and the digest are afterwards those of a handle that only
 // flushed.  No invalidation function is called and nothing is kept between calls but the scratch.  Unsharded only: the pass reads every
-// tile, and a shard holds only its own.  The chunks travel as ekf_sample_map's do (host/factor_map.h: kSampleSlots pinned slots a
-// direction, the host waits only where it takes a slot again), in a scratch and with events of this call's own, so that the byte counts
+// tile, and a shard holds only its own.  The chunks travel as ekf_sample_map's do, through the same chunk_stream (host/factor_map.h:
+// kSampleSlots pinned slots a direction, the host waits only where it takes a slot again), in a scratch and with events of this call's own, so that the byte counts
 // of the factor, sample and solve calls stay what they were.
 #pragma once
 namespace {
@@ -54,9 +54,8 @@ MultiplyMapArgs multiply_chunk_args(const ekf_handle *h, int64_t rows) {
 }
 
 // Order as in factor_body: the rungs, with what depends on N checked once N is exact -> every allocation -> the flush -> the launches,
-// queued back to back.  Per chunk the upload of a pinned slot, the two launches and the download into a pinned slot; the host waits only
-// where it takes a slot again, kSampleSlots chunks later, for that slot's own download.  `queued` is set once the launches begin: out is
-// written only from there on.
+// queued back to back by chunk_stream (host/factor_map.h): per chunk the upload of a pinned slot, the two launches and the download into
+// a pinned slot.  `queued` is set once the launches begin: out is written only from there on.
 int32_t multiply_body(ekf_handle *h, const std::string &who, const double *B, int64_t k, double *out, bool &queued) {
     TRY(edit_unsharded(h, who, "the product reads every tile of the lower triangle, and every shard holds only its own tiles"));
     TRY(edit_settled(h, who));
@@ -66,41 +65,16 @@ int32_t multiply_body(ekf_handle *h, const std::string &who, const double *B, in
     const int64_t rows = tm.padded(2 * N);
     TRY(multiply_alloc(h, rows));
     TRY(edit_flushed(h));
-    const int64_t C = factor_chunk(), ld = sample_ld(rows), nchunks = (k + C - 1) / C;
-    const size_t chunk = sample_chunk_doubles(rows);
     const MultiplyMapArgs a = multiply_chunk_args(h, rows);
-    double *d_b = h->d_pmul, *d_y = a.y;
     queued = true;
-    auto unpack = [&](int64_t j) {
-        const double *y = h->h_pmy + (size_t)(j % kSampleSlots) * chunk;
-        for (int64_t c = 0; c < C && j * C + c < k; ++c) {
-            double *o = out + (j * C + c) * n;
-            std::memcpy(o, y + c * ld + rows, 3 * sizeof(double));
-            std::memcpy(o + 3, y + c * ld, (size_t)(2 * N) * sizeof(double));
-        }
-    };
     // timed by family: the tile pass under EKF_KERNEL_ASSOCIATE, the sums under EKF_KERNEL_COMPACT (both free in this call)
-    for (int64_t j = 0; j < nchunks; ++j) {
-        const int slot = (int)(j % kSampleSlots);
-        if (j >= kSampleSlots) {
-            HIPCHK(h, hipEventSynchronize(h->ev_pmslot[slot]));
-            unpack(j - kSampleSlots);
-        }
-        double *u = h->h_pmb + (size_t)slot * chunk;
-        std::memset(u, 0, chunk * sizeof(double));
-        for (int64_t c = 0; c < C && j * C + c < k; ++c) {
-            const double *row = B + (j * C + c) * n;
-            std::memcpy(u + c * ld, row + 3, (size_t)(2 * N) * sizeof(double));
-            std::memcpy(u + c * ld + rows, row, 3 * sizeof(double));
-        }
-        HIPCHK(h, hipMemcpyAsync(d_b, u, chunk * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    TRY(chunk_stream(h, h->h_pmb, h->h_pmy, h->ev_pmslot, h->d_pmul, a.y, rows, N, B, k, out, [&]() -> int32_t {
         if (N > 0) TIMED(h, EKF_KERNEL_ASSOCIATE, launch_multiply_map(h->st, a, 0, h->storage, h->stream));
         TIMED(h, EKF_KERNEL_COMPACT, launch_multiply_map(h->st, a, 1, h->storage, h->stream));
-        HIPCHK(h, hipMemcpyAsync(h->h_pmy + (size_t)slot * chunk, d_y, chunk * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipEventRecord(h->ev_pmslot[slot], h->stream));
-    }
+        return EKF_OK;
+    }));
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    for (int64_t j = nchunks > kSampleSlots ? nchunks - kSampleSlots : 0; j < nchunks; ++j) unpack(j);
+    chunk_stream_tail(h->h_pmy, rows, N, k, out);
     return EKF_OK;
 }
 }  // namespace

@@ -54,36 +54,6 @@ hipError_t launch_extract_rows(const DevState &dst, const DevState &src, const E
 hipError_t launch_transform_state(const DevState &st, const TransformMapArgs &a, hipStream_t s);
 hipError_t launch_transform_tiles(const DevState &st, const TransformMapArgs &a, const int2 *work, int64_t ntiles, int storage, hipStream_t s);
 
-// k_factor_* (factor_map.h): P of the flushed state `st` factored in the scratch store `a` names -- read-only on st.  The caller queues the
-// whole right-looking blocked Cholesky with no host wait: launch_factor_load (the tiles and the right-hand sides; unsharded tile maps only),
-// then per tile column k = 0 .. a.rows / a.tm.T - 1 launch_factor_column's three parts in order (the last column has parts 1 and 2 empty),
-// then launch_factor_finish (the reductions and the 3 x 3 tail).  a.res must be cleared in front of them (stream order); every launch
-// returns at once when a.res[0] says that a pivot failed.  factor_tile_edge(): the edge of the factor store's tiles (the one that is built).
-int factor_tile_edge();
-hipError_t launch_factor_load(const DevState &st, const FactorMapArgs &a, int storage, hipStream_t s);
-hipError_t launch_factor_column(const FactorMapArgs &a, int k, int part, hipStream_t s);      // part 0: diagonal, 1: panel, 2: trailing update
-hipError_t launch_factor_finish(const DevState &st, const FactorMapArgs &a, hipStream_t s);
-// k_factor_apply / k_factor_sample (sample_map.h): x + C xi for one chunk of factor_chunk() draws, queued behind launch_factor_finish of
-// the same `a` (a.lr_off given: the finish stores all of L_r).  part 0: the apply pass, one partial block per segment into sa.part
-// (factor_partial_doubles(a.rows) doubles); part 1: the sums, x and the robot rows into sa.y.  Both return at once where a pivot failed.
-int factor_chunk();
-int64_t factor_partial_doubles(int64_t rows);
-hipError_t launch_factor_sample(const DevState &st, const FactorMapArgs &a, const FactorSampleArgs &sa, int part, hipStream_t s);
-// k_solve_* (solve_map.h): C^-1 B or P^-1 B for one chunk of factor_chunk() right-hand sides, queued behind launch_factor_finish of the
-// same `a` (a.lr_off given).  part 0: the inverses of the diagonal tiles into sv.inv (solve_inverse_doubles(a.rows) doubles), once a
-// call; part 1: step c of the forward sweep, c = 0 .. rows / T - 1 ascending; part 2: the robot tail; part 3: step c of the backward
-// sweep, c descending (sv.form 0 only).  All return at once where a pivot failed.
-int64_t solve_inverse_doubles(int64_t rows);
-hipError_t launch_solve_map(const FactorMapArgs &a, const FactorSolveArgs &sv, int part, int c, hipStream_t s);
-// k_multiply_tiles / k_multiply_sum / k_multiply_robot (multiply_map.h): P B for one chunk of factor_chunk() vectors on the handle's own tile store, no
-// factorisation in front.  multiply_segment(T): the tiles per segment for tile edge T (MultiplyMapArgs::S); multiply_partial_doubles:
-// the doubles behind dpart, tpart and wpart together, in that order (multiply_partial_offsets: where the last two begin).  part 0: the
-// tile pass (not launched for N = 0); part 1: the sums and, in a one-workgroup launch of its own, the robot rows into a.y.
-int multiply_segment(int T);
-int64_t multiply_partial_doubles(const TileMap &tm, int64_t rows);
-void multiply_partial_offsets(const TileMap &tm, int64_t rows, int64_t *tpart, int64_t *wpart);
-hipError_t launch_multiply_map(const DevState &st, const MultiplyMapArgs &a, int part, int storage, hipStream_t s);
-
 // fused_predict != nullptr folds predict(u) into the correction (one launch instead of two, identical arithmetic)
 // fuse_downdate: the kernel also applies its pair to the landmark block (small maps: a.n_mm <= gather_fuse_max_rows(), one
 // workgroup); the pair is then NOT written to the pending ring and no downdate launch must follow
@@ -324,6 +294,38 @@ hipError_t launch_joint_factor_iter(const DevState &st, const JointArgs &a, cons
 // name a PRIVATE F64 pair ring (Gp32 == nullptr): the a.np pairs go to its slots 0 .. a.np - 1, x / Prr / strip into buffer a.cur ^ 1, every
 // landmark's live diagonal block into buffer dcur ^ 1; the caller flips both and lets ONE pass apply the pairs to the tiles.
 hipError_t launch_gather_joint(const DevState &st, const JointUpdateArgs &a, const JointBlock *blk, int storage, hipStream_t s);
+
+// ---- the calls that treat P as a matrix: the factorisation, the draws and the solves behind it, the plain product, the dense
+// observation behind that (launch/map_algebra.h; what sizes their grids and scratch: launch/map_sizes.h, host code without HIP) ----
+// k_factor_* (factor_map.h): P of the flushed state `st` factored in the scratch store `a` names -- read-only on st.  The caller queues the
+// whole right-looking blocked Cholesky with no host wait: launch_factor_load (the tiles and the right-hand sides; unsharded tile maps only),
+// then per tile column k = 0 .. a.rows / a.tm.T - 1 launch_factor_column's three parts in order (the last column has parts 1 and 2 empty),
+// then launch_factor_finish (the reductions and the 3 x 3 tail).  a.res must be cleared in front of them (stream order); every launch
+// returns at once when a.res[0] says that a pivot failed.  factor_tile_edge(): the edge of the factor store's tiles (the one that is built).
+int factor_tile_edge();
+hipError_t launch_factor_load(const DevState &st, const FactorMapArgs &a, int storage, hipStream_t s);
+hipError_t launch_factor_column(const FactorMapArgs &a, int k, int part, hipStream_t s);      // part 0: diagonal, 1: panel, 2: trailing update
+hipError_t launch_factor_finish(const DevState &st, const FactorMapArgs &a, hipStream_t s);
+// k_factor_apply / k_factor_sample (sample_map.h): x + C xi for one chunk of factor_chunk() draws, queued behind launch_factor_finish of
+// the same `a` (a.lr_off given: the finish stores all of L_r).  part 0: the apply pass, one partial block per segment into sa.part
+// (factor_partial_doubles(a.rows) doubles); part 1: the sums, x and the robot rows into sa.y.  Both return at once where a pivot failed.
+int factor_chunk();
+int64_t factor_partial_doubles(int64_t rows);
+hipError_t launch_factor_sample(const DevState &st, const FactorMapArgs &a, const FactorSampleArgs &sa, int part, hipStream_t s);
+// k_solve_* (solve_map.h): C^-1 B or P^-1 B for one chunk of factor_chunk() right-hand sides, queued behind launch_factor_finish of the
+// same `a` (a.lr_off given).  part 0: the inverses of the diagonal tiles into sv.inv (solve_inverse_doubles(a.rows) doubles), once a
+// call; part 1: step c of the forward sweep, c = 0 .. rows / T - 1 ascending; part 2: the robot tail; part 3: step c of the backward
+// sweep, c descending (sv.form 0 only).  All return at once where a pivot failed.
+int64_t solve_inverse_doubles(int64_t rows);
+hipError_t launch_solve_map(const FactorMapArgs &a, const FactorSolveArgs &sv, int part, int c, hipStream_t s);
+// k_multiply_tiles / k_multiply_sum / k_multiply_robot (multiply_map.h): P B for one chunk of factor_chunk() vectors on the handle's own tile store, no
+// factorisation in front.  multiply_segment(T): the tiles per segment for tile edge T (MultiplyMapArgs::S); multiply_partial_doubles:
+// the doubles behind dpart, tpart and wpart together, in that order (multiply_partial_offsets: where the last two begin).  part 0: the
+// tile pass (not launched for N = 0); part 1: the sums and, in a one-workgroup launch of its own, the robot rows into a.y.
+int multiply_segment(int T);
+int64_t multiply_partial_doubles(const TileMap &tm, int64_t rows);
+void multiply_partial_offsets(const TileMap &tm, int64_t rows, int64_t *tpart, int64_t *wpart);
+hipError_t launch_multiply_map(const DevState &st, const MultiplyMapArgs &a, int part, int storage, hipStream_t s);
 
 // A linear observation with a DENSE H (dense_obs.h, ekf_observe_dense), on a flushed state, behind launch_multiply_map's two stages on the
 // chunk that a.b / a.y name (the rows of H in, G = P H' out).  launch_dense_gram: k_dense_gram, a workgroup per segment of landmark rows,

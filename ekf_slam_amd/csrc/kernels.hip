@@ -63,6 +63,7 @@ namespace {
 #include "merge_pass.h"       // the fused downdate-and-compact pass of a batch of merges: k_merge_pass
 #include "nearest.h"          // the candidate search in front of a merge: k_nearest
 #include "factor_map.h"       // the Cholesky factorisation of P in a scratch store: k_factor_load / _rhs / _diag / _panel / _trail / _finish
+#include "map_blocks.h"       // what the calls on P as a matrix share: chunk_k, tile_mac, segment_of, chunk_tree_sums
 #include "sample_map.h"       // ... and the draws x + C xi behind it: k_factor_apply, k_factor_sample
 #include "solve_map.h"        // ... and the solves C^-1 B, P^-1 B: k_solve_invert, k_solve_forward, k_solve_tail, k_solve_backward
 #include "multiply_map.h"     // the plain product P B on the handle's own tile store, no factor: k_multiply_tiles, k_multiply_sum, k_multiply_robot
@@ -75,5 +76,7 @@ namespace {
 #include "launch/steps.h"         // predict, append, gather, row-panels, association
 #include "launch/pass_select.h"   // which pass instance runs: a pure function, no HIP
 #include "launch/passes.h"        // launch_downdate, the row copies behind an asynchronous pass
-#include "launch/edits.h"         // compact, constrain, linear observation, joint innovation, joint search and joint update, merge pass, nearest, the factorisation
+#include "launch/edits.h"         // compact, extract, transform, merge pass, constrain, linear and model observations, joint innovation, joint search and joint update, nearest
+#include "launch/map_sizes.h"     // the sizing arithmetic of the calls that treat P as a matrix: host code, no HIP
+#include "launch/map_algebra.h"   // the factorisation, the draws and the solves behind it, the plain product, the dense observation
 #include "launch/state_io.h"      // dense <-> tiled, block reads, low-rank load, digest

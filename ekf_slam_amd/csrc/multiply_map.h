@@ -1,6 +1,7 @@
 // Fragment of kernels.hip (included there, inside its anonymous namespace, after solve_map.h; it uses factor_map.h's d4_t, kFactorBlock
-// and factor_source): the plain product P B on the handle's own tile store (ekf_multiply_map) -- k_multiply_tiles, k_multiply_sum, k_multiply_robot.
+// and factor_source and map_blocks.h's chunk_k, segment_of and chunk_tree_sums): the plain product P B on the handle's own tile store (ekf_multiply_map) -- k_multiply_tiles, k_multiply_sum, k_multiply_robot.
 #pragma once
+#include "map_blocks.h"         // (kernels.hip has it in front already; a host build that names this fragment alone gets it here)
 
 // ---------------------------------------------------------------------------------------------------
 // THE PRODUCT (ekf_multiply_map).  P = [Prr Prm; Pmr Pmm] of a flushed handle is exactly what ekf_get_P reports: the landmark block
@@ -22,17 +23,17 @@
 //     k_multiply_robot  one workgroup: the robot rows (queued with the sums; it reads what k_multiply_tiles left, nothing of theirs)
 // SELECTION, NOT MULTIPLICATION BY ZERO: an entry of P in a row or column at or beyond 2 N is the constant 0 whatever the store holds
 // there (in-place passes skip those rows, removals leave rows behind), the strip likewise; rows at or beyond 2 N are never written.
-// ARITHMETIC OF ONE ENTRY, row i = T R + u of the landmark block, vector v.  multiply_k(s, t) is the k order of a tile: steps s = 0 ..
-// T / 4 - 1 ascending, the four terms t of one matrix instruction ascending (the instruction is a k-ordered chain of correctly rounded
-// FMAs, flush64_mfma.h; EKF_FACTOR_FMA_TWIN compiles the same chains entry by entry).
+// ARITHMETIC OF ONE ENTRY, row i = T R + u of the landmark block, vector v.  chunk_k(s, t) is the k order of a tile (map_blocks.h: steps
+// s = 0 .. T / 4 - 1, the matrix instruction and its plain-FMA twin); k_multiply_tiles' two loops are tile_mac's form for a run-time
+// edge T, float tiles and the multiply_entry path.  (Folded into one function the tile pass measured 1 to 3 % slower: DESIGN.md section 3z.)
 //   direct, per segment g of tile row R: d_g = 0, then fma(P(i, T J + k), b_v[T J + k], d_g) over the segment's tiles J ascending and
-//     in a tile over k in multiply_k's order;
-//   transposed, per tile (I, R), I > R: t_I = 0, then fma(P(T I + k, i), b_v[T I + k], t_I) over k in multiply_k's order;
+//     in a tile over k in chunk_k's order;
+//   transposed, per tile (I, R), I > R: t_I = 0, then fma(P(T I + k, i), b_v[T I + k], t_I) over k in chunk_k's order;
 //   the entry: ((((d_0 + d_1) + ..) + t_{R+1}) + t_{R+2} + ..), then fma(strip[2][i], b_r[2], fma(strip[1][i], b_r[1], fma(strip[0][i],
 //     b_r[0], .))).
 // Robot row q: per tile row I a chain w_I = fma(strip[q][T I + u], b_v[T I + u], .) over u ascending (rows at or beyond 2 N: the constant
-// 0); lane t of k_multiply_robot adds w_I for I = t, t + 256, .. ascending to 0, the 256 sums meet in k_factor_finish's pairwise
-// tree, and the entry is fma(Prr[q][2], b_r[2], fma(Prr[q][1], b_r[1], fma(Prr[q][0], b_r[0], that sum))).
+// 0); lane t of k_multiply_robot adds w_I for I = t, t + 256, .. ascending to 0, the 256 sums meet in chunk_tree_sums' pairwise
+// tree (map_blocks.h), and the entry is fma(Prr[q][2], b_r[2], fma(Prr[q][1], b_r[1], fma(Prr[q][0], b_r[0], that sum))).
 // Nothing depends on v, on what the other columns hold or on how many chunks a call has: a vector's product is the same bits wherever
 // it stands.  No atomics, no data-dependent order.  b = 0 gives 0 in every chain; b = e_j leaves one product p * 1 in every chain, so
 // the result is column j of P entry for entry (the sign of a zero aside).
@@ -40,9 +41,6 @@
 
 constexpr int kMultiplyBlock = 256;        // four wavefronts; a wavefront owns the 16-row blocks wave, wave + 4, .. of a tile
 constexpr int kMultiplyWaveBlocks = 4;     // at most: T <= 256
-
-// the k index of step s, term t: sample_k's order -- steps 2 p and 2 p + 1 of term t are the ADJACENT entries 8 p + 2 t, 8 p + 2 t + 1
-__device__ __forceinline__ constexpr int multiply_k(int s, int t) { return 8 * (s >> 1) + 2 * t + (s & 1); }
 
 // Pmm(r, c) as the product takes it: the constant 0 at or beyond 2 N (n2), else what ekf_get_P reports
 template <typename TS>
@@ -61,14 +59,8 @@ __global__ __launch_bounds__(kMultiplyBlock) void k_multiply_tiles(DevState st, 
     __shared__ double BJ[kFactorChunk][kPitch];
     const int T = st.tm.T, S = a.S, nb = T >> 4, kPairs = T >> 3;
     const int64_t n2 = 2 * a.N;
-    // segment w of the grid: tile rows g S .. g S + S - 1 have g + 1 segments each (factor_segment_base)
-    const int64_t w = blockIdx.x;
-    int64_t g = (int64_t)((sqrt(8.0 * (double)w / S + 1.0) - 1.0) * 0.5);
-    while (S * g * (g + 1) / 2 > w) --g;
-    while (S * (g + 1) * (g + 2) / 2 <= w) ++g;
-    const int64_t in = w - S * g * (g + 1) / 2;
-    const int I = (int)(g * S + in / (g + 1)), seg = (int)(in % (g + 1));
-    const int J0 = seg * S, J1 = J0 + S <= I + 1 ? J0 + S : I + 1;
+    int I, seg, J0, J1;
+    segment_of(blockIdx.x, S, I, seg, J0, J1);
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, lr = lane >> 4, lc = lane & 15;
     const TS *__restrict__ tiles = (const TS *)st.tiles;
     const int64_t rowI = (int64_t)I * T;
@@ -95,7 +87,7 @@ __global__ __launch_bounds__(kMultiplyBlock) void k_multiply_tiles(DevState st, 
             for (int r = 0; r < 4; ++r)
                 for (int s = 0; s < 2 * kPairs; ++s)
                     for (int t = 0; t < 4; ++t) {
-                        const int row = 16 * rb + lr + 4 * r, k = multiply_k(s, t);
+                        const int row = 16 * rb + lr + 4 * r, k = chunk_k(s, t);
                         const double p = slow ? multiply_entry<TS>(st, n2, rowI + row, colJ + k) : (double)tp[row * T + k];
                         acc[r] = fma(p, BJ[lc][k], acc[r]);
                     }
@@ -125,7 +117,7 @@ __global__ __launch_bounds__(kMultiplyBlock) void k_multiply_tiles(DevState st, 
             for (int r = 0; r < 4; ++r)
                 for (int s = 0; s < 2 * kPairs; ++s)
                     for (int t = 0; t < 4; ++t) {
-                        const int col = 16 * cb + lr + 4 * r, k = multiply_k(s, t);
+                        const int col = 16 * cb + lr + 4 * r, k = chunk_k(s, t);
                         const double p = slow ? multiply_entry<TS>(st, n2, rowI + k, colJ + col) : (double)tp[k * T + col];
                         acc[r] = fma(p, BI[lc][k], acc[r]);
                     }
@@ -200,19 +192,7 @@ __global__ __launch_bounds__(kFactorBlock) void k_multiply_robot(DevState st, Mu
 #pragma unroll
         for (int s = 0; s < 3 * kFactorChunk; ++s) acc[s] = acc[s] + a.wpart[I * (3 * kFactorChunk) + s];
     }
-#pragma unroll
-    for (int q = 0; q < 3; ++q) {
-#pragma unroll
-        for (int c = 0; c < kFactorChunk; ++c) red[c][tid] = acc[q * kFactorChunk + c];
-        __syncthreads();
-        for (int off = kFactorBlock / 2; off > 0; off >>= 1) {
-            if (tid < off)
-                for (int c = 0; c < kFactorChunk; ++c) red[c][tid] = red[c][tid] + red[c][tid + off];
-            __syncthreads();
-        }
-        if (tid < kFactorChunk) sums[q * kFactorChunk + tid] = red[tid][0];
-        __syncthreads();
-    }
+    chunk_tree_sums(acc, red, sums);
     if (tid >= kFactorChunk) return;
     const double *__restrict__ prr = st.prr[a.cur];
     const double *__restrict__ br = a.b + (int64_t)tid * a.ld + a.rows;

@@ -1,5 +1,7 @@
-// Fragment of kernels.hip (included there, inside its anonymous namespace, after factor_map.h, whose d4_t and kFactorBlock it uses): the draws x + C xi behind the factorisation of P (ekf_sample_map) -- k_factor_apply, k_factor_sample.
+// Fragment of kernels.hip (included there, inside its anonymous namespace, after map_blocks.h, whose tile_mac, segment_of and
+// chunk_tree_sums it uses): the draws x + C xi behind the factorisation of P (ekf_sample_map) -- k_factor_apply, k_factor_sample.
 #pragma once
+#include "map_blocks.h"         // (kernels.hip has it in front already; a host build that names this fragment alone gets it here)
 
 // ---------------------------------------------------------------------------------------------------
 // THE DRAWS (ekf_sample_map).  After a factorisation that succeeded the factor store holds L (diagonal tiles lower-triangular with zeros
@@ -11,25 +13,18 @@
 //                      column, on v_mfma_f64_16x16x4_f64, every tile read from HBM once per chunk -- the hot path; one partial block out
 //                      (and, from the first segment of each tile row, that row's 3 x 16 part of W' Xi)
 //     k_factor_sample  workgroup I < rows / TF: tile row I's partial blocks summed in ascending segment order, x_m added, written;
-//                      the last workgroup: the parts of W' Xi summed by the fixed tree of k_factor_finish, the 3 x 3 tail, the robot
+//                      the last workgroup: the parts of W' Xi summed by chunk_tree_sums' fixed tree, the 3 x 3 tail, the robot
 //                      rows written
 // ARITHMETIC OF ONE ENTRY (row i of tile row I, draw c): per segment p = 0 starts a chain fma(L[i][k], xi_c[k], p) over the segment's
-// tiles J ascending and inside a tile over k in sample_k's order (steps s ascending, the four terms t of a matrix instruction ascending:
-// the instruction is a k-ordered chain of correctly rounded FMAs, flush64_mfma.h; EKF_FACTOR_FMA_TWIN compiles that chain entry by entry);
+// tiles J ascending and inside a tile over k in chunk_k's order (tile_mac, map_blocks.h: the matrix instruction and its plain-FMA twin);
 // the entry is x[3 + 64 I + i] + (((p_0 + p_1) + p_2) + ..), or x's entry itself where that sum is zero (sample_add).  Robot row q: per tile row I a chain w_I = fma(W[r][q], xi_c[r], .) over its
 // TF rows ascending (a lane of the row's first segment in k_factor_apply; kept behind the partial blocks); lane t of the last workgroup
-// of k_factor_sample adds w_I for I = t, t + 256, .. ascending to 0, the 256 sums meet in k_factor_finish's pairwise tree, then t_q =
+// of k_factor_sample adds w_I for I = t, t + 256, .. ascending to 0, the 256 sums meet in chunk_tree_sums' pairwise tree (map_blocks.h), then t_q =
 // that sum with fma(L_r[q][j], xi_r[j], .) for j = 0 .. q in turn, and the entry is x[q] + t_q (sample_add).  Nothing depends on c, on what the other columns hold or
 // on how many chunks a call has: a draw's sample is the same bits wherever it stands.  No atomics.  xi = 0 gives +0 in every chain: x, signed zeros included.  xi = e_j leaves one term in every chain, so the sample is fl(x + C[:, j]).
 // In k_factor_apply a lane's A operands come straight from one tile row; the B operands, the same for all four wavefronts, are staged
 // through LDS once per tile (which is why a draw is a column: its TF entries are contiguous).
 // ---------------------------------------------------------------------------------------------------
-
-// The k index of the apply pass: step s, term t.  Steps 2 p and 2 p + 1 of term t are the two ADJACENT doubles 8 p + 2 t and 8 p + 2 t + 1,
-// one 16-byte load, and the four terms' loads of one row lie side by side: a load instruction of a wavefront reads 64 contiguous bytes of
-// each of 16 tile rows, and two of them in a row use every 128-byte line whole.  (k_factor_trail's factor_k gives a lane 16 contiguous
-// doubles, so that each of its load instructions touches 64 lines for 16 bytes each; what either order cost this pass: DESIGN.md section 3x.)
-template <int TF> __device__ __forceinline__ constexpr int sample_k(int s, int t) { return 8 * (s >> 1) + 2 * t + (s & 1); }
 
 // x + d, and x itself where the deviation is zero: x + (+0) would turn an entry -0.0 of x into +0.0, and xi = 0 is to return x bit for bit
 __device__ __forceinline__ double sample_add(double x, double d) { return d == 0.0 ? x : x + d; }
@@ -37,16 +32,9 @@ __device__ __forceinline__ double sample_add(double x, double d) { return d == 0
 template <int TF, int S>
 __global__ __launch_bounds__(4 * TF) void k_factor_apply(FactorMapArgs a, FactorSampleArgs sa) {
     static_assert(TF % 16 == 0 && TF <= 64 && kFactorChunk == 16 && S >= 1, "whole 16 x 16 blocks (an even number of steps), at most four wavefronts, one block of draws");
-    constexpr int kSteps = TF / 4;
     if (a.res[0] != 0.0) return;
-    // segment w of the grid: tile rows g S .. g S + S - 1 have g + 1 segments each (factor_segment_base)
-    const int64_t w = blockIdx.x;
-    int64_t g = (int64_t)((sqrt(8.0 * (double)w / S + 1.0) - 1.0) * 0.5);
-    while (S * g * (g + 1) / 2 > w) --g;
-    while (S * (g + 1) * (g + 2) / 2 <= w) ++g;
-    const int64_t in = w - S * g * (g + 1) / 2;
-    const int I = (int)(g * S + in / (g + 1)), seg = (int)(in % (g + 1));
-    const int J0 = seg * S, J1 = J0 + S <= I + 1 ? J0 + S : I + 1;
+    int I, seg, J0, J1;
+    segment_of(blockIdx.x, S, I, seg, J0, J1);
     const int tid = threadIdx.x, lane = tid & 63, lr = lane >> 4, lc = lane & 15;
     const int row0 = 16 * (tid >> 6);
     // Xi_J, TF entries of each of the 16 draws, goes through LDS once per tile for all four wavefronts (read straight from the L2 it was
@@ -71,20 +59,7 @@ __global__ __launch_bounds__(4 * TF) void k_factor_apply(FactorMapArgs a, Factor
             double *const xn = buf ? xs0 : xs1;
             xn[0] = g4[0]; xn[1] = g4[1]; xn[2] = g4[2]; xn[3] = g4[3];
         }
-#if defined(EKF_FACTOR_FMA_TWIN)
-        for (int r = 0; r < 4; ++r)
-            for (int s = 0; s < kSteps; ++s)
-                for (int t = 0; t < 4; ++t)
-                    acc[r] = fma(L[(row0 + lr + 4 * r) * TF + sample_k<TF>(s, t)], XJ[sample_k<TF>(s, t)], acc[r]);
-#else
-        double av[kSteps], bv[kSteps];
-#pragma unroll
-        for (int s = 0; s < kSteps; ++s) av[s] = L[(row0 + lc) * TF + sample_k<TF>(s, lr)];
-#pragma unroll
-        for (int s = 0; s < kSteps; ++s) bv[s] = XJ[sample_k<TF>(s, lr)];
-#pragma unroll
-        for (int s = 0; s < kSteps; ++s) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(av[s], bv[s], acc, 0, 0, 0);
-#endif
+        tile_mac<TF, false, false>(acc, L, XJ, row0, lr, lc);
         __syncthreads();
     }
     double *__restrict__ out = sa.part + (factor_segment_base(I, S) + seg) * (int64_t)(TF * kFactorChunk);
@@ -132,19 +107,7 @@ __global__ __launch_bounds__(kFactorBlock) void k_factor_sample(DevState st, Fac
 #pragma unroll
         for (int s = 0; s < 3 * kFactorChunk; ++s) acc[s] = acc[s] + wp[I * (3 * kFactorChunk) + s];
     }
-#pragma unroll
-    for (int q = 0; q < 3; ++q) {
-#pragma unroll
-        for (int c = 0; c < kFactorChunk; ++c) red[c][tid] = acc[q * kFactorChunk + c];
-        __syncthreads();
-        for (int off = kFactorBlock / 2; off > 0; off >>= 1) {
-            if (tid < off)
-                for (int c = 0; c < kFactorChunk; ++c) red[c][tid] = red[c][tid] + red[c][tid + off];
-            __syncthreads();
-        }
-        if (tid < kFactorChunk) sums[q * kFactorChunk + tid] = red[tid][0];
-        __syncthreads();
-    }
+    chunk_tree_sums(acc, red, sums);
     if (tid >= kFactorChunk) return;
     const double *__restrict__ e = sa.xi + (int64_t)tid * sa.ld + a.rows;
     double *__restrict__ y = sa.y + (int64_t)tid * sa.ld + a.rows;

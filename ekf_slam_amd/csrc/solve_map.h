@@ -1,7 +1,8 @@
-// Fragment of kernels.hip (included there, inside its anonymous namespace, after sample_map.h, whose sample_k and kFactorChunk layout it
-// uses): the solves C^-1 B and P^-1 B behind the factorisation of P (ekf_solve_map) -- k_solve_invert, k_solve_forward, k_solve_tail,
+// Fragment of kernels.hip (included there, inside its anonymous namespace, after sample_map.h, whose chunk layout it shares, and
+// map_blocks.h, whose tile_mac and chunk_tree_sums it uses): the solves C^-1 B and P^-1 B behind the factorisation of P (ekf_solve_map) -- k_solve_invert, k_solve_forward, k_solve_tail,
 // k_solve_backward.
 #pragma once
+#include "map_blocks.h"         // (kernels.hip has it in front already; a host build that names this fragment alone gets it here)
 
 // ---------------------------------------------------------------------------------------------------
 // THE SOLVES (ekf_solve_map).  The factor in elimination order is C = [L 0; W' L_r] (sample_map.h), and for b = (b_m, b_r)
@@ -12,7 +13,7 @@
 //     k_solve_forward   one launch per tile column c ascending, one workgroup per tile row I >= c: every workgroup forms u_c = X_cc b_c
 //                       for itself (a TF x TF x 16 product); workgroup 0 writes it to y, workgroup I - c > 0 goes on to
 //                       b_I -= L_Ic u_c.  b_c is only read in launch c, b_I only by its own workgroup: no workgroup reads what another writes.
-//     k_solve_tail      one workgroup: W' u by k_factor_finish's fixed tree, then the 3 x 3 solves, a lane per column: u_r into y
+//     k_solve_tail      one workgroup: W' u by chunk_tree_sums' fixed tree, then the 3 x 3 solves, a lane per column: u_r into y
 //                       (form 1) or z_r into b (form 0)
 //     k_solve_backward  form 0 only, one launch per tile row c DESCENDING, one workgroup per tile column J <= c: every workgroup forms
 //                       z_c = X_cc' (v_c - W_c z_r) for itself, v the contents of y; workgroup 0 writes it to b, workgroup c - J > 0
@@ -24,47 +25,15 @@
 // ARITHMETIC OF ONE ENTRY, right-hand side q (nothing depends on the other columns or on how many chunks a call has: a row of the result
 // is the same bits wherever its right-hand side stands).  X_cc: column j by forward substitution, x_i = (delta_ij - sum_{p < i} L_ip x_p)
 // / L_ii as a chain fma(-L_ip, x_p, .) over p ascending, exact zeros above the diagonal.  Every product is a chain fma(A_ik, x_k, acc)
-// over k in solve_k's order (steps s ascending, the four terms t of a matrix instruction ascending; the instruction is a k-ordered chain
-// of correctly rounded FMAs, flush64_mfma.h; EKF_FACTOR_FMA_TWIN compiles that chain entry by entry), started from 0 for u_c and z_c and
+// over k in chunk_k's order (tile_mac, map_blocks.h: the matrix instruction and its plain-FMA twin), started from 0 for u_c and z_c and
 // from the entry itself for the updates, with A = -L (negation is exact).  So entry i of tile row I of u is the chain over X_II's row
 // applied to b_I less the updates of tile columns 0 .. I - 1 in that order; the backward sweep mirrors it with tile rows nF - 1 .. c + 1
 // descending and, LAST, the fold fma(-W_i2, z_r2, fma(-W_i1, z_r1, fma(-W_i0, z_r0, v_i))) on the way into LDS.  W' u: lane t chains
-// fma(W[r][q], u[r], .) over its rows r = t, t + 256, .. ascending, the 256 sums meet in k_factor_finish's pairwise tree; then
+// fma(W[r][q], u[r], .) over its rows r = t, t + 256, .. ascending, the 256 sums meet in chunk_tree_sums' pairwise tree (map_blocks.h); then
 // t_q = b_r[q] - that sum, u_r by forward and z_r by backward substitution on L_r (res[3..5], lr_off) with the products as FMAs.
 // No atomics, no flags between workgroups, no data-dependent order.  b = 0 gives zeros throughout.  Every launch returns at once where
 // a pivot failed (res[0] != 0).
 // ---------------------------------------------------------------------------------------------------
-
-// the k index of both sweeps: sample_k's (two adjacent doubles per 16-byte load of an untransposed operand row)
-template <int TF> __device__ __forceinline__ constexpr int solve_k(int s, int t) { return sample_k<TF>(s, t); }
-
-// acc(16 rows from row0 of the product, column lc) += op(A) X, A a TF x TF tile, row-major, read as it stands (kTrans false) or transposed,
-// negated or not; X the column lc of the staged right-hand sides, TF entries in LDS.  Lane (lr, lc) holds rows row0 + lr + 4 r.
-template <int TF, bool kTrans, bool kNeg>
-__device__ __forceinline__ void solve_mac(d4_t &acc, const double *__restrict__ A, const double *__restrict__ X, int row0, int lr, int lc) {
-    constexpr int kSteps = TF / 4;
-#if defined(EKF_FACTOR_FMA_TWIN)
-    (void)lc;
-    for (int r = 0; r < 4; ++r)
-        for (int s = 0; s < kSteps; ++s)
-            for (int t = 0; t < 4; ++t) {
-                const int i = row0 + lr + 4 * r;
-                const double v = kTrans ? A[solve_k<TF>(s, t) * TF + i] : A[i * TF + solve_k<TF>(s, t)];
-                acc[r] = fma(kNeg ? -v : v, X[solve_k<TF>(s, t)], acc[r]);
-            }
-#else
-    double av[kSteps], bv[kSteps];
-#pragma unroll
-    for (int s = 0; s < kSteps; ++s) {
-        const double v = kTrans ? A[solve_k<TF>(s, lr) * TF + row0 + lc] : A[(row0 + lc) * TF + solve_k<TF>(s, lr)];
-        av[s] = kNeg ? -v : v;
-    }
-#pragma unroll
-    for (int s = 0; s < kSteps; ++s) bv[s] = X[solve_k<TF>(s, lr)];
-#pragma unroll
-    for (int s = 0; s < kSteps; ++s) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(av[s], bv[s], acc, 0, 0, 0);
-#endif
-}
 
 // Grid rows / TF, one wavefront each.  Lane j < TF owns column j of X = L_cc^-1 in registers (every index static: the loops unroll, as
 // in k_factor_panel); every lane reads the same entry of L_cc from LDS.  A lane's entries above its diagonal are chains of zeros.
@@ -107,7 +76,7 @@ __global__ __launch_bounds__(4 * TF) void k_solve_forward(FactorMapArgs a, Facto
     }
     __syncthreads();
     d4_t acc = {0.0, 0.0, 0.0, 0.0};
-    solve_mac<TF, false, false>(acc, sv.inv + (int64_t)c * (TF * TF), &Bs[lc][0], row0, lr, lc);
+    tile_mac<TF, false, false>(acc, sv.inv + (int64_t)c * (TF * TF), &Bs[lc][0], row0, lr, lc);
     if (blockIdx.x == 0) {
         double *__restrict__ yc = sv.y + (int64_t)lc * sv.ld + (int64_t)c * TF + row0 + lr;
 #pragma unroll
@@ -121,7 +90,7 @@ __global__ __launch_bounds__(4 * TF) void k_solve_forward(FactorMapArgs a, Facto
     double *__restrict__ bI = sv.b + (int64_t)lc * sv.ld + (int64_t)I * TF + row0 + lr;
 #pragma unroll
     for (int r = 0; r < 4; ++r) acc[r] = bI[4 * r];
-    solve_mac<TF, false, true>(acc, a.tiles + a.tm.tile_offset(I, c), &Us[lc][0], row0, lr, lc);
+    tile_mac<TF, false, true>(acc, a.tiles + a.tm.tile_offset(I, c), &Us[lc][0], row0, lr, lc);
 #pragma unroll
     for (int r = 0; r < 4; ++r) bI[4 * r] = acc[r];
 }
@@ -146,19 +115,7 @@ __global__ __launch_bounds__(kFactorBlock) void k_solve_tail(FactorMapArgs a, Fa
             acc[2 * kFactorChunk + c] = fma(w2, u, acc[2 * kFactorChunk + c]);
         }
     }
-#pragma unroll
-    for (int q = 0; q < 3; ++q) {
-#pragma unroll
-        for (int c = 0; c < kFactorChunk; ++c) red[c][tid] = acc[q * kFactorChunk + c];
-        __syncthreads();
-        for (int off = kFactorBlock / 2; off > 0; off >>= 1) {
-            if (tid < off)
-                for (int c = 0; c < kFactorChunk; ++c) red[c][tid] = red[c][tid] + red[c][tid + off];
-            __syncthreads();
-        }
-        if (tid < kFactorChunk) sums[q * kFactorChunk + tid] = red[tid][0];
-        __syncthreads();
-    }
+    chunk_tree_sums(acc, red, sums);
     if (tid >= kFactorChunk) return;
     double *__restrict__ br = sv.b + (int64_t)tid * sv.ld + a.rows;
     const double l00 = a.res[3], l11 = a.res[4], l22 = a.res[5], l10 = a.lr_off[0], l20 = a.lr_off[1], l21 = a.lr_off[2];
@@ -193,7 +150,7 @@ __global__ __launch_bounds__(4 * TF) void k_solve_backward(FactorMapArgs a, Fact
     }
     __syncthreads();
     d4_t acc = {0.0, 0.0, 0.0, 0.0};
-    solve_mac<TF, true, false>(acc, sv.inv + (int64_t)c * (TF * TF), &Vs[lc][0], row0, lr, lc);
+    tile_mac<TF, true, false>(acc, sv.inv + (int64_t)c * (TF * TF), &Vs[lc][0], row0, lr, lc);
     if (blockIdx.x == 0) {
         double *__restrict__ zc = sv.b + (int64_t)lc * sv.ld + (int64_t)c * TF + row0 + lr;
 #pragma unroll
@@ -207,7 +164,7 @@ __global__ __launch_bounds__(4 * TF) void k_solve_backward(FactorMapArgs a, Fact
     double *__restrict__ vJ = sv.y + (int64_t)lc * sv.ld + (int64_t)J * TF + row0 + lr;
 #pragma unroll
     for (int r = 0; r < 4; ++r) acc[r] = vJ[4 * r];
-    solve_mac<TF, true, true>(acc, a.tiles + a.tm.tile_offset(c, J), &Zs[lc][0], row0, lr, lc);
+    tile_mac<TF, true, true>(acc, a.tiles + a.tm.tile_offset(c, J), &Zs[lc][0], row0, lr, lc);
 #pragma unroll
     for (int r = 0; r < 4; ++r) vJ[4 * r] = acc[r];
 }

@@ -32,7 +32,7 @@ import numpy as np  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 STATES = ((10000, 128, "f64", 8, True), (40000, 256, "f32", 4, False))
-TF = 64                                                       # the factor store's tile edge (launch/edits.h: kFactorTile)
+TF = 64                                                       # the factor store's tile edge (launch/map_sizes.h: kFactorTile)
 MFMA_F64_RATE = "44-48 TFLOP/s (scripts/probes/mfma_f64_rate.hip)"
 
 

@@ -41,7 +41,7 @@ def built_constant(path, name):
     return int(m.group(1))
 
 
-TF, CHUNK = built_constant("launch/edits.h", "kFactorTile"), built_constant("kernel_args.h", "kFactorChunk")
+TF, CHUNK = built_constant("launch/map_sizes.h", "kFactorTile"), built_constant("kernel_args.h", "kFactorChunk")
 KS = (1, 16, 256)
 FORMS = ("full", "half")
 

@@ -1,5 +1,5 @@
 // Host emulation of the kernels of ekf_multiply_map (tests/test_multiply_map_cpu.py compiles and runs it; no GPU, no HIP runtime): the
-// kernel SOURCE ekf_slam_amd/csrc/multiply_map.h (with factor_map.h, whose factor_source it reads P through) behind kernel_host_shim.h,
+// kernel SOURCE ekf_slam_amd/csrc/multiply_map.h (with factor_map.h, whose factor_source it reads P through) behind map_algebra_rig.h,
 // a workgroup with barriers as threads, the matrix-core loops as their plain-FMA twins in the same k order (EKF_FACTOR_FMA_TWIN) -- per
 // chunk of kFactorChunk vectors k_multiply_tiles and k_multiply_sum, launch after launch as host/multiply_map.h queues them, on the
 // store's own tile map: tile edges 16 .. 256, F64 or float tiles.
@@ -12,85 +12,9 @@
 // NaN.  The chunks are packed and unpacked as host/multiply_map.h does it, the result chunk and the partial blocks poisoned first, so
 // that an entry no launch wrote (or one written that must not be) shows.  Each case checks here that the launches left the state bit
 // for bit as it was.
-#include <cmath>
-#include <cstdint>
-#include <cstdio>
-#include <condition_variable>
-#include <cstring>
-#include <functional>
-#include <mutex>
-#include <string>
-#include <thread>
-#include <vector>
-#include <pthread.h>
-#include "kernel_host_shim.h"
-#include "emulated_state.h"
-
-static thread_local Idx lane_idx, group_idx;
-static pthread_barrier_t group_barrier;
-#define threadIdx lane_idx
-#define blockIdx group_idx
-#define __syncthreads() pthread_barrier_wait(&group_barrier)
-#define EKF_FACTOR_FMA_TWIN 1
-typedef double d4_t __attribute__((vector_size(32)));
-#include "factor_map.h"
+#include "map_algebra_rig.h"
 #include "multiply_map.h"
-
-// the launchers' arithmetic (ekf_slam_amd/csrc/launch/edits.h: multiply_segment, multiply_partial_offsets), restated
-static int segment_of(int T) { return T >= 256 ? 1 : 256 / T; }
-
-// workgroups first .. last - 1 of a grid, the lanes of each as threads made once: lane t of every workgroup is worker t of a pool
-struct LanePool {
-    std::vector<std::thread> workers;
-    std::mutex m;
-    std::condition_variable go, done;
-    std::function<void()> body;
-    long gen = 0;
-    int lanes = 0, group = 0, left = 0;
-    bool stop = false;
-    void work(int t) {
-        long seen = 0;
-        for (;;) {
-            std::function<void()> f;
-            {
-                std::unique_lock<std::mutex> lk(m);
-                go.wait(lk, [&] { return stop || (gen != seen && t < lanes); });
-                if (stop) return;
-                seen = gen;
-                f = body;
-                lane_idx.x = (unsigned)t; group_idx.x = (unsigned)group;
-            }
-            f();
-            std::lock_guard<std::mutex> lk(m);
-            if (--left == 0) done.notify_one();
-        }
-    }
-    void run(int b, int n, const std::function<void()> &f) {
-        std::unique_lock<std::mutex> lk(m);
-        while ((int)workers.size() < n) { const int t = (int)workers.size(); workers.emplace_back([this, t] { work(t); }); }
-        body = f; group = b; lanes = n; left = n; ++gen;
-        go.notify_all();
-        done.wait(lk, [&] { return left == 0; });
-        lanes = 0;
-    }
-    ~LanePool() {
-        { std::lock_guard<std::mutex> lk(m); stop = true; }
-        go.notify_all();
-        for (auto &th : workers) th.join();
-    }
-};
-static LanePool pool;
-template <typename F> static void launch_threads(int first, int last, int lanes, F body) {
-    for (int b = first; b < last; ++b) {
-        pthread_barrier_init(&group_barrier, nullptr, (unsigned)lanes);
-        pool.run(b, lanes, body);
-        pthread_barrier_destroy(&group_barrier);
-    }
-}
-// ... and one after another (no barrier on the way)
-template <typename F> static void launch_lanes(int first, int last, int lanes, F body) {
-    for (int b = first; b < last; ++b) for (int t = 0; t < lanes; ++t) { lane_idx.x = (unsigned)t; group_idx.x = (unsigned)b; body(); }
-}
+#include "launch/map_sizes.h"      // multiply_segment, multiply_partial_offsets, multiply_partial_doubles: the launchers' own arithmetic
 
 struct Case { std::string name; int T, isfloat, N, k; };
 
@@ -116,11 +40,12 @@ template <typename TS, int TMAX> static int run_case(const Case &c, const std::s
     const Store<TS> S0(S);
     const DevState st = S.st;
     const int64_t rows = S.tm.padded(2 * N), nT = rows / T, ld = rows + 4, blk = (int64_t)T * kFactorChunk;
-    const int Sg = segment_of(T);
-    const int64_t segments = factor_segment_base(nT, Sg), toff = segments * blk, woff = toff + S.tm.row_base(nT) * blk;
-    const double kPoison = -7.0;
+    const int Sg = multiply_segment(T);
+    const int64_t segments = factor_segment_base(nT, Sg);
+    int64_t toff, woff;
+    multiply_partial_offsets(S.tm, rows, &toff, &woff);
     const size_t chunk = (size_t)ld * kFactorChunk;
-    std::vector<double> cb(chunk + 1), cy(chunk + 1), part((size_t)(woff + nT * 3 * kFactorChunk) + 1), out((size_t)k * n, kPoison);
+    std::vector<double> cb(chunk + 1), cy(chunk + 1), part((size_t)multiply_partial_doubles(S.tm, rows) + 1), out((size_t)k * n, kPoison);
     MultiplyMapArgs a = {};
     a.b = cb.data(); a.y = cy.data(); a.dpart = part.data(); a.tpart = part.data() + toff; a.wpart = part.data() + woff;
     a.ld = ld; a.N = N; a.rows = rows; a.S = Sg; a.cur = S.cur;
@@ -130,11 +55,7 @@ template <typename TS, int TMAX> static int run_case(const Case &c, const std::s
         cy.assign(cy.size(), kPoison);
         part.assign(part.size(), kPoison);
         cb.back() = kPoison;
-        for (int64_t q = 0; q < kFactorChunk && j * kFactorChunk + q < k; ++q) {
-            const double *row = B + (j * kFactorChunk + q) * n;
-            memcpy(cb.data() + q * ld, row + 3, (size_t)(2 * N) * 8);
-            memcpy(cb.data() + q * ld + rows, row, 24);
-        }
+        pack_chunk(cb.data(), B, j, k, N, rows, ld);
         if (N > 0) launch_threads(0, (int)segments, kMultiplyBlock, [&] { k_multiply_tiles<TS, TMAX>(st, a); });
         const int sum_grid = (int)(nT * ((blk + kFactorBlock - 1) / kFactorBlock));
         launch_lanes(0, sum_grid, kFactorBlock, [&] { k_multiply_sum(st, a); });
@@ -145,16 +66,10 @@ template <typename TS, int TMAX> static int run_case(const Case &c, const std::s
                 if ((cy[q * ld + i] == kPoison) == written) ++bad;              // every live entry written, nothing else
             }
         if (cy.back() != kPoison || cb.back() != kPoison || part.back() != kPoison) ++bad;
-        for (int64_t q = 0; q < kFactorChunk && j * kFactorChunk + q < k; ++q) {
-            double *o = out.data() + (j * kFactorChunk + q) * n;
-            memcpy(o, cy.data() + q * ld + rows, 24);
-            memcpy(o + 3, cy.data() + q * ld, (size_t)(2 * N) * 8);
-        }
+        unpack_chunk(out.data(), cy.data(), j, k, N, rows, ld);
     }
     // nothing of the state was written
-    bad += differ(S.x[0], S0.x[0], "x") + differ(S.x[1], S0.x[1], "x other") + differ(S.prr[0], S0.prr[0], "prr") + differ(S.strip[0], S0.strip[0], "strip") +
-           differ(S.diag[0], S0.diag[0], "diag") + differ(S.diag[1], S0.diag[1], "diag other") + differ(S.s, S0.s, "s") +
-           differ(S.ring, S0.ring, "pair ring") + differ(S.tiles, S0.tiles, "tiles") + differ(S.small, S0.small, "small");
+    bad += state_differs(S, S0);
     f = fopen((dir + "/" + c.name + ".out").c_str(), "wb");
     if (!f) return 1000;
     put(f, out.data(), out.size());

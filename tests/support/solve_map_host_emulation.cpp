@@ -1,7 +1,6 @@
 // Host emulation of the kernels of ekf_solve_map (tests/test_solve_map_cpu.py compiles and runs it; no GPU, no HIP runtime): the
-// factorisation exactly as sample_map_host_emulation.cpp runs it -- the kernel SOURCES ekf_slam_amd/csrc/factor_map.h, sample_map.h and
-// solve_map.h behind kernel_host_shim.h, a workgroup with barriers as threads, the matrix-core loops as their plain-FMA twins in the same
-// k order (EKF_FACTOR_FMA_TWIN) -- then k_solve_invert once and per chunk of kFactorChunk right-hand sides the forward sweep, the robot
+// factorisation exactly as sample_map_host_emulation.cpp runs it (FactoredCase of map_algebra_rig.h), then from the kernel SOURCE
+// ekf_slam_amd/csrc/solve_map.h k_solve_invert once and per chunk of kFactorChunk right-hand sides the forward sweep, the robot
 // tail and, for form 0, the backward sweep, launch after launch in the order host/factor_map.h queues them.  Factor tile edges 16 and
 // 32; the source store is F64 or float with its own tile edge.
 // The cases -- one line "name TF Tsrc float N k form" each -- are read from argv[1]/cases.txt (or argv[1]/argv[2], so that several
@@ -11,122 +10,20 @@
 // then the factor C in elimination order as the factorisation left it in the store.  The chunks are packed and unpacked as
 // host/factor_map.h does it, the result chunk and the inverse tiles poisoned first, so that an entry no launch wrote shows.  Each case
 // checks here that the launches left the state bit for bit as it was.
-#include <cmath>
-#include <cstdint>
-#include <cstdio>
-#include <condition_variable>
-#include <cstring>
-#include <functional>
-#include <mutex>
-#include <string>
-#include <thread>
-#include <vector>
-#include <pthread.h>
-#include "kernel_host_shim.h"
-#include "emulated_state.h"
-
-static thread_local Idx lane_idx, group_idx;
-static pthread_barrier_t group_barrier;
-#define threadIdx lane_idx
-#define blockIdx group_idx
-#define __syncthreads() pthread_barrier_wait(&group_barrier)
-#define EKF_FACTOR_FMA_TWIN 1
-typedef double d4_t __attribute__((vector_size(32)));
-#include "factor_map.h"
+#include "map_algebra_rig.h"
 #include "sample_map.h"
 #include "solve_map.h"
-
-// workgroups first .. last - 1 of a grid, the lanes of each as threads.  The sweeps are hundreds of small launches a case, so the
-// threads are made once: lane t of every workgroup is worker t of a pool that sleeps between workgroups.
-struct LanePool {
-    std::vector<std::thread> workers;
-    std::mutex m;
-    std::condition_variable go, done;
-    std::function<void()> body;
-    long gen = 0;
-    int lanes = 0, group = 0, left = 0;
-    bool stop = false;
-    void work(int t) {
-        long seen = 0;
-        for (;;) {
-            std::function<void()> f;
-            {
-                std::unique_lock<std::mutex> lk(m);
-                go.wait(lk, [&] { return stop || (gen != seen && t < lanes); });
-                if (stop) return;
-                seen = gen;
-                f = body;
-                lane_idx.x = (unsigned)t; group_idx.x = (unsigned)group;
-            }
-            f();
-            std::lock_guard<std::mutex> lk(m);
-            if (--left == 0) done.notify_one();
-        }
-    }
-    void run(int b, int n, const std::function<void()> &f) {
-        std::unique_lock<std::mutex> lk(m);
-        while ((int)workers.size() < n) { const int t = (int)workers.size(); workers.emplace_back([this, t] { work(t); }); }
-        body = f; group = b; lanes = n; left = n; ++gen;
-        go.notify_all();
-        done.wait(lk, [&] { return left == 0; });
-        lanes = 0;
-    }
-    ~LanePool() {
-        { std::lock_guard<std::mutex> lk(m); stop = true; }
-        go.notify_all();
-        for (auto &th : workers) th.join();
-    }
-};
-static LanePool pool;
-template <typename F> static void launch_threads(int first, int last, int lanes, F body) {
-    for (int b = first; b < last; ++b) {
-        pthread_barrier_init(&group_barrier, nullptr, (unsigned)lanes);
-        pool.run(b, lanes, body);
-        pthread_barrier_destroy(&group_barrier);
-    }
-}
-// ... and one after another (no barrier on the way)
-template <typename F> static void launch_lanes(int first, int last, int lanes, F body) {
-    for (int b = first; b < last; ++b) for (int t = 0; t < lanes; ++t) { lane_idx.x = (unsigned)t; group_idx.x = (unsigned)b; body(); }
-}
 
 struct Case { std::string name; int TF, Tsrc, isfloat, N, k, form; };
 
 template <typename TS, int TF> static int run_case(const Case &c, const std::string &dir) {
     const int N = c.N, n = 3 + 2 * N, k = c.k;
-    std::vector<double> in((size_t)n + (size_t)n * n + (size_t)k * n);
-    FILE *f = fopen((dir + "/" + c.name + ".in").c_str(), "rb");
-    if (!f || fread(in.data(), 8, in.size(), f) != in.size()) return 1000;
-    fclose(f);
-    const double *x = in.data(), *P = x + n, *xi = P + (size_t)n * n;
-    Store<TS> S(c.Tsrc, N, N + 3);
-    for (int i = 0; i < n; ++i) S.x[0][i] = x[i];
-    for (int q = 0; q < N; ++q) S.s[q] = q + 1.0;
-    scatter(S, [&](int r, int col) { return P[(size_t)col * n + r]; });
-    for (auto &v : S.ring) v = 0.25;
-    const Store<TS> S0(S);
-    FactorMapArgs a = {};
-    a.tm = ekf_make_tilemap(TF, 1, 0);
-    a.N = N; a.rows = a.tm.padded(2 * N); a.nref = 0; a.ref_stride = n; a.cur = S.cur;
-    const int nF = (int)(a.rows / TF);
-    const double kPoison = -7.0;
-    std::vector<double> tiles((size_t)(a.tm.row_base(nF) > 0 ? a.tm.row_base(nF) : 1) * TF * TF, kPoison), rhs((size_t)a.rows * kFactorRhs + 1, kPoison);
-    std::vector<double> res((size_t)kFactorRes + a.rows, 0.0), tail(4, kPoison);
-    for (int64_t i = 0; i < a.rows; ++i) res[kFactorRes + i] = kPoison;
-    a.tiles = tiles.data(); a.rhs = rhs.data(); a.res = res.data(); a.ref = nullptr; a.lr_off = tail.data();
-    const DevState st = S.st;
-    if (N > 0) {
-        launch_lanes(0, (int)((a.rows + kFactorBlock - 1) / kFactorBlock), kFactorBlock, [&] { k_factor_rhs(st, a); });
-        launch_lanes(0, (int)a.tm.row_base(nF), kFactorBlock, [&] { k_factor_load<TS, TF>(st, a); });
-    }
-    for (int col = 0; col < nF; ++col) {
-        launch_threads(0, 1, kFactorBlock, [&] { k_factor_diag<TF>(a, col); });
-        const int m = nF - 1 - col;
-        if (m == 0) continue;
-        launch_threads(0, m, 64, [&] { k_factor_panel<TF>(a, col); });
-        launch_lanes(0, m * (m + 1) / 2, 4 * TF, [&] { k_factor_trail<TF>(a, col); });
-    }
-    launch_threads(0, 1, kFactorBlock, [&] { k_factor_finish(st, a); });
+    FactoredCase<TS, TF> fc(dir, c.name, c.Tsrc, N, (size_t)k * n, 0, true);
+    if (!fc.ok) return 1000;
+    fc.run();
+    const FactorMapArgs &a = fc.a;
+    const std::vector<double> &res = fc.res;
+    const int nF = fc.nF;
     // the right-hand sides, a chunk at a time
     const int64_t ld = a.rows + 4;
     const size_t chunk = (size_t)ld * kFactorChunk;
@@ -141,11 +38,7 @@ template <typename TS, int TF> static int run_case(const Case &c, const std::str
         cb.assign(cb.size(), 0.0);
         cy.assign(cy.size(), kPoison);
         cb.back() = kPoison;
-        for (int64_t q = 0; q < kFactorChunk && j * kFactorChunk + q < k; ++q) {
-            const double *row = xi + (j * kFactorChunk + q) * n;
-            memcpy(cb.data() + q * ld, row + 3, (size_t)(2 * N) * 8);
-            memcpy(cb.data() + q * ld + a.rows, row, 24);
-        }
+        pack_chunk(cb.data(), fc.extra, j, k, N, a.rows, ld);
         for (int col = 0; col < nF; ++col) launch_threads(0, nF - col, 4 * TF, [&] { k_solve_forward<TF>(a, sv, col); });
         launch_threads(0, 1, kFactorBlock, [&] { k_solve_tail(a, sv); });
         if (c.form == 0)
@@ -155,36 +48,15 @@ template <typename TS, int TF> static int run_case(const Case &c, const std::str
             for (int64_t q = 0; q < kFactorChunk; ++q)
                 for (int64_t i = 0; i < a.rows + 3; ++i) if (cr[q * ld + i] == kPoison) ++bad;     // every entry of the result written
         if (cy.back() != kPoison || cb.back() != kPoison || inv.back() != kPoison) ++bad;
-        for (int64_t q = 0; q < kFactorChunk && j * kFactorChunk + q < k; ++q) {
-            double *o = out.data() + (j * kFactorChunk + q) * n;
-            memcpy(o, cr.data() + q * ld + a.rows, 24);
-            memcpy(o + 3, cr.data() + q * ld, (size_t)(2 * N) * 8);
-        }
+        unpack_chunk(out.data(), cr.data(), j, k, N, a.rows, ld);
     }
     if (res[0] != 0.0) out.assign(out.size(), NAN);
-    // nothing of the state was written
-    bad += differ(S.x[0], S0.x[0], "x") + differ(S.x[1], S0.x[1], "x other") + differ(S.prr[0], S0.prr[0], "prr") + differ(S.strip[0], S0.strip[0], "strip") +
-           differ(S.diag[0], S0.diag[0], "diag") + differ(S.diag[1], S0.diag[1], "diag other") + differ(S.s, S0.s, "s") +
-           differ(S.ring, S0.ring, "pair ring") + differ(S.tiles, S0.tiles, "tiles") + differ(S.small, S0.small, "small");
-    if (rhs.back() != kPoison || tail[3] != kPoison) ++bad;
-    f = fopen((dir + "/" + c.name + ".out").c_str(), "wb");
+    bad += fc.untouched();
+    FILE *f = fopen((dir + "/" + c.name + ".out").c_str(), "wb");
     if (!f) return 1000;
     put(f, res.data(), res.size());
     put(f, out.data(), out.size());
-    // THE FACTOR THE LAUNCHES SOLVED WITH, read out of what the factorisation left: C = [L 0; W' L_r] in elimination order, n x n row-major --
-    // L from the factor store (above the diagonal as stored), W from columns 0..2 of the
-    // right-hand sides, L_r from res[3..5] and lr_off; NaN throughout where a pivot failed
-    std::vector<double> C((size_t)n * n, res[0] == 0.0 ? 0.0 : NAN);
-    if (res[0] == 0.0) {
-        for (int r = 0; r < 2 * N; ++r)
-            for (int col = 0; col < 2 * N; ++col)
-                if (col / TF <= r / TF) C[(size_t)r * n + col] = tiles[a.tm.tile_offset(r / TF, col / TF) + (size_t)(r % TF) * TF + col % TF];
-        for (int q = 0; q < 3; ++q)
-            for (int col = 0; col < 2 * N; ++col) C[(size_t)(2 * N + q) * n + col] = rhs[(size_t)col * kFactorRhs + q];
-        double *Lr = C.data() + (size_t)(2 * N) * n + 2 * N;
-        Lr[0] = res[3]; Lr[n] = tail[0]; Lr[n + 1] = res[4]; Lr[2 * n] = tail[1]; Lr[2 * n + 1] = tail[2]; Lr[2 * n + 2] = res[5];
-    }
-    put(f, C.data(), C.size());
+    fc.put_factor(f);
     fclose(f);
     printf("%s: %d differences\n", c.name.c_str(), bad);
     return bad;

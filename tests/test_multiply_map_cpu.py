@@ -155,10 +155,13 @@ def test_kernel_sources_on_the_host_under_the_sanitizers(tmp_path):
 
 
 def test_the_sources_keep_what_the_header_promises():
-    """No atomics in the kernels; one k order, multiply_k, named by the twin; the host layer never touches the factor store."""
+    """No atomics in the kernels; one k order, chunk_k of map_blocks.h, named by the twins of both parts of a tile and defined nowhere
+    else; the host layer never touches the factor store."""
     src = open(os.path.join(ROOT, "ekf_slam_amd", "csrc", "multiply_map.h")).read()
     code = src.split("// -----")[-1]
-    assert "atomic" not in code and "multiply_k(s, t)" in code and "EKF_FACTOR_FMA_TWIN" in code
+    assert "atomic" not in code and code.count("chunk_k(s, t)") == 2 and code.count("#if defined(EKF_FACTOR_FMA_TWIN)") == 2
+    assert "multiply_k" not in src and "int chunk_k(" not in src
+    assert "int chunk_k(int s, int t) { return 8 * (s >> 1) + 2 * t + (s & 1); }" in open(os.path.join(ROOT, "ekf_slam_amd", "csrc", "map_blocks.h")).read()
     host = open(os.path.join(ROOT, "ekf_slam_amd", "csrc", "host", "multiply_map.h")).read()
     assert "factor_alloc" not in host and "d_ftiles" not in host and "d_fsample" not in host
 

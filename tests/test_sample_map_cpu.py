@@ -20,6 +20,7 @@ from mex_harness import PRELUDE_SHOWN, driver, driver_without, transcript_of
 dp = ctypes.POINTER(ctypes.c_double)
 SIZES = [0, 1, 13, 16, 40]          # N = 16 at edge 32 ends exactly on a tile edge; N = 40 at edge 16 has five tile columns
 PTHREAD = ["-O2", "-mfma", "-ffp-contract=off", "-pthread"]
+CSRC = os.path.join(ROOT, "ekf_slam_amd", "csrc")
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -227,14 +228,47 @@ def test_kernel_sources_on_the_host_under_the_sanitizers(tmp_path):
 
 
 def test_the_twin_runs_the_matrix_instructions_k_order():
-    """The plain-FMA twin of the apply pass and its matrix-core loop name their k index through the same function, sample_k,
-    and the finish stores the rest of L_r only where it is asked to."""
-    src = open(os.path.join(ROOT, "ekf_slam_amd", "csrc", "sample_map.h")).read()
+    """The plain-FMA twin of a tile's product with a chunk and its matrix-core loop name their k index through the same function,
+    chunk_k, in the ONE place that holds them, tile_mac of map_blocks.h; the apply pass goes through it once per tile and holds no
+    matrix instruction of its own; the finish stores the rest of L_r only where it is asked to."""
+    mac = _tile_mac()
+    assert mac.count("chunk_k(s, t)") == 3 and mac.count("chunk_k(s, lr)") == 3
+    twin, _, device = mac.partition("#else")
+    assert "#if defined(EKF_FACTOR_FMA_TWIN)" in twin and "__builtin_amdgcn_mfma" not in twin and "#endif" in device
+    assert mac.count("__builtin_amdgcn_mfma") == 1 and "__builtin_amdgcn_mfma_f64_16x16x4f64(av[s], bv[s], acc, 0, 0, 0)" in device
+    src = open(os.path.join(CSRC, "sample_map.h")).read()
+    assert "__builtin_amdgcn_mfma" not in src and "EKF_FACTOR_FMA_TWIN" not in src
     body = src[src.index("void k_factor_apply("):src.index("void k_factor_sample(")]
-    assert body.count("sample_k<TF>(s, t)") == 2 and body.count("sample_k<TF>(s, lr)") == 2
-    assert "__builtin_amdgcn_mfma_f64_16x16x4f64(av[s], bv[s], acc, 0, 0, 0)" in body and body.count("__syncthreads()") == 2
+    assert body.count("tile_mac<") == 1 and body.count("tile_mac<TF, false, false>") == 1 and body.count("__syncthreads()") == 2
     assert "atomicAdd" not in src and "__hip_atomic" not in src
-    assert "if (a.lr_off) {" in open(os.path.join(ROOT, "ekf_slam_amd", "csrc", "factor_map.h")).read()
+    assert "if (a.lr_off) {" in open(os.path.join(CSRC, "factor_map.h")).read()
+
+
+def _tile_mac():
+    """The text of tile_mac in map_blocks.h: from its name to the next function."""
+    blocks = open(os.path.join(CSRC, "map_blocks.h")).read()
+    rest = blocks[blocks.index("void tile_mac("):]
+    return rest[:rest.index("__device__", 1)]
+
+
+def test_segment_of_inverts_factor_segment_base(tmp_path):
+    """segment_of, the decode both segment kernels share, compiled for the host: for S in {1, 2, 16} and every tile-row count nF <= 40
+    it visits every (I, seg), I < nF, exactly once over w in [0, factor_segment_base(nF, S)), in factor_segment_base's order, with
+    J0 = seg S and J1 = min(J0 + S, I + 1) -- nF = 1, I = S - 1, I = S and w = base - 1, where the square root's guess can be off by
+    one, among them.  The program prints one line "S nF I seg J0 J1" per w; the expectation is built here."""
+    exe = host_build("segment_of_host", str(tmp_path / "segment_of_host"), flags=PTHREAD)
+    r = subprocess.run([exe, "40", "1", "2", "16"], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-2000:]
+    got = {}
+    for ln in r.stdout.split("\n"):
+        if ln:
+            v = [int(t) for t in ln.split()]
+            got.setdefault((v[0], v[1]), []).append(tuple(v[2:]))
+    assert sorted(got) == [(S, nF) for S in (1, 2, 16) for nF in range(1, 41)]
+    for (S, nF), rows in got.items():
+        want = [(I, seg, seg * S, min(seg * S + S, I + 1)) for I in range(nF) for seg in range(I // S + 1)]
+        assert rows == want, (S, nF)
+        assert len(set((I, seg) for I, seg, _, _ in rows)) == len(rows) == sum(I // S + 1 for I in range(nF))
 
 
 # ------------------------------------------------------------------------------------------------------------------

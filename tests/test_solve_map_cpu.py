@@ -265,18 +265,26 @@ def test_kernel_sources_on_the_host_under_the_sanitizers(tmp_path):
 
 
 def test_the_twin_runs_the_matrix_instructions_k_order():
-    """The plain-FMA twin of the sweeps' product and its matrix-core loop name their k index through the same function, solve_k; both
-    sweeps go through that one product; no atomics anywhere."""
-    src = open(os.path.join(ROOT, "ekf_slam_amd", "csrc", "solve_map.h")).read()
-    body = src[src.index("void solve_mac("):src.index("void k_solve_invert(")]
-    assert body.count("solve_k<TF>(s, t)") == 3 and body.count("solve_k<TF>(s, lr)") == 3
-    assert "__builtin_amdgcn_mfma_f64_16x16x4f64(av[s], bv[s], acc, 0, 0, 0)" in body and "#if defined(EKF_FACTOR_FMA_TWIN)" in body
-    assert "__builtin_amdgcn_mfma" not in src.replace(body, "")
+    """The plain-FMA twin of the sweeps' product and its matrix-core loop name their k index through the same function, chunk_k, in
+    the ONE place that holds them, tile_mac of map_blocks.h; both sweeps go through that one product and hold no matrix instruction
+    of their own; no atomics anywhere."""
+    csrc = os.path.join(ROOT, "ekf_slam_amd", "csrc")
+    blocks = open(os.path.join(csrc, "map_blocks.h")).read()
+    rest = blocks[blocks.index("void tile_mac("):]
+    body = rest[:rest.index("__device__", 1)]                  # up to the next function
+    assert body.count("chunk_k(s, t)") == 3 and body.count("chunk_k(s, lr)") == 3
+    twin, _, device = body.partition("#else")
+    assert "#if defined(EKF_FACTOR_FMA_TWIN)" in twin and "__builtin_amdgcn_mfma" not in twin and "#endif" in device
+    assert body.count("__builtin_amdgcn_mfma") == 1 and "__builtin_amdgcn_mfma_f64_16x16x4f64(av[s], bv[s], acc, 0, 0, 0)" in device
+    assert "__builtin_amdgcn_mfma" not in blocks.replace(body, "")
+    src = open(os.path.join(csrc, "solve_map.h")).read()
+    assert "__builtin_amdgcn_mfma" not in src and "EKF_FACTOR_FMA_TWIN" not in src
     fwd = src[src.index("void k_solve_forward("):src.index("void k_solve_tail(")]
     bwd = src[src.index("void k_solve_backward("):]
-    assert fwd.count("solve_mac<TF, false, ") == 2 and bwd.count("solve_mac<TF, true, ") == 2
+    assert fwd.count("tile_mac<TF, false, ") == 2 and bwd.count("tile_mac<TF, true, ") == 2
+    assert fwd.count("tile_mac<") == 2 and bwd.count("tile_mac<") == 2
     assert fwd.count("__syncthreads()") == 2 and bwd.count("__syncthreads()") == 2
-    assert "atomic" not in src.split("// -----")[-1]
+    assert "atomic" not in src.split("// -----")[-1] and "atomic" not in blocks.split("// -----")[-1]
 
 
 # ------------------------------------------------------------------------------------------------------------------
